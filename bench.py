@@ -1,17 +1,23 @@
 #!/usr/bin/env python3
 """bench.py — BA iterations/s + Mmatches/s on BASELINE.json's headline configuration.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one Levenberg–Marquardt iteration (linearise if the last step was accepted, build the Schur complement,
 factor + solve the reduced camera system, back-substitute, evaluate the trial cost) of the 500-camera / 200k-point /
-1.2M-observation synthetic scene (BASELINE config 3), problem resident in HBM.  Rank 0 prints ONE JSON line.  The same
-line carries the other half of the metric — exhaustive 2-NN + ratio tests over ALL 249 500 ordered image pairs of the
-scene (integer SIFT-like descriptors, and once more on non-integral VLFeat-style floats) — plus the triangulation /
-reprojection, geometric-verification and pose-initialiser legs, `roofline` for the dominant BA kernel and `cpu_baseline`
-(the CPU oracle on this box's host cores: 1 thread and all cores).
+1.2M-observation synthetic scene (BASELINE config 3), problem resident in HBM.  Rank 0 prints ONE JSON line.  A plain run
+does only what the headline needs: scene, W warm-up iterations, K timed iterations, the line (`value` = BA iterations/s,
+`ms_per_step` = ms per timed iteration).
 
+  --full                the same line also carries the other half of the metric — exhaustive 2-NN + ratio tests over ALL
+                        249 500 ordered image pairs of the scene (integer SIFT-like descriptors, and once more on non-integral
+                        VLFeat-style floats) — plus the triangulation / reprojection, geometric-verification and pose-initialiser
+                        legs, the per-kernel profiled pass with `roofline` for the dominant BA kernel, the one-shot solve and
+                        `cpu_baseline` (the CPU oracle on the host's cores: 1 thread and all cores)
+  --dump-outputs DIR    after the timed iterations, what they computed as DIR/<name>.npy (float64): the adjusted cam_pose,
+                        cam_model and point arrays (rank 0's points when N > 1), the per-iteration cost and [initial, final] cost
+                        (of the last run of at most STEP_CHUNK iterations: K steps are timed as such runs from one start state)
   --config 5 --window   BASELINE config 5: partial bundle adjustment of the newest of 2000 cameras (window chosen by the
                         host as PartialBundleAdjustment does, one CameraModel per camera, GPS rows on the window)
 """
@@ -43,6 +49,15 @@ def fixed_iteration_options(steps):
     return capi.default_options(max_num_iterations=steps, function_tolerance=-1.0, gradient_tolerance=-1.0,
                                 parameter_tolerance=-1.0, max_num_consecutive_invalid_steps=1 << 30,
                                 min_trust_region_radius=0.0)
+
+
+# The one stopping rule that cannot be switched off: once a solve has converged every step is rejected, each rejection divides
+# the trust-region radius by a factor that doubles every time, and some 46 rejections in a row take it to 0 (MIN_RADIUS) - a
+# run asked for more iterations than that ends early.  K steps are therefore timed as runs of at most STEP_CHUNK iterations,
+# each from the same start state: every timed step is an iteration of the same LM trajectory whatever K is, and K <= STEP_CHUNK
+# is one run as before.  (Fixed-iteration solves end by themselves after 69 / 182 / 1282 iterations at configs 1 / 2 / 3; the
+# config 5 problems run past 3000.)
+STEP_CHUNK = 50
 
 
 def ba_algorithmic_bytes(n_obs, n_pts, n_cams, n_red):
@@ -114,7 +129,12 @@ def main():
     ap.add_argument("--pose-images", type=int, default=1024, help="images / pairs in the pose-initialiser leg")
     ap.add_argument("--chain-images", type=int, default=96, help="images in the resident-chain leg (all their ordered pairs)")
     ap.add_argument("--backend", default=None, help="torch.distributed backend for N>1 (default nccl = RCCL)")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beyond the headline: profiled pass + rooflines, one-shot solve, matching, extras, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed iterations computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -126,21 +146,21 @@ def main():
             sys.exit(spawn_ranks(args.gpus))
         raise SystemExit("WORLD_SIZE %d != --gpus %d" % (world, args.gpus))
 
-    import torch
-    # one rank per GPU on the real node; a rehearsal with more ranks than GPUs (gloo, one test GPU) shares devices
-    local_rank = local_rank % max(1, torch.cuda.device_count())
-    dist = None
+    # torch only carries the collectives of N > 1 ranks: one rank leaves the GPU to the library alone and does not pay for
+    # importing torch (its first import on a fresh machine can take longer than the whole timed run)
+    torch = dist = None
     if world > 1:
+        import torch
         import torch.distributed as dist
+        # one rank per GPU on the real node; a rehearsal with more ranks than GPUs (gloo, one test GPU) shares devices
+        local_rank = local_rank % max(1, torch.cuda.device_count())
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         backend = args.backend or "nccl"
         torch.cuda.set_device(local_rank)
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
-    else:
-        torch.cuda.set_device(local_rank)
-    if world > max(1, torch.cuda.device_count()):
-        # a rehearsal with more ranks than GPUs: tell the library how many contexts launch on this device at the same time
-        os.environ["MSFM_DEVICE_SHARE"] = str(-(-world // max(1, torch.cuda.device_count())))
+        if world > max(1, torch.cuda.device_count()):
+            # a rehearsal with more ranks than GPUs: tell the library how many contexts launch on this device at the same time
+            os.environ["MSFM_DEVICE_SHARE"] = str(-(-world // max(1, torch.cuda.device_count())))
 
     ctx = capi.Context(local_rank)
     collective = "none (1 rank)"
@@ -155,10 +175,10 @@ def main():
 
     def barrier():
         ctx.synchronize()
-        torch.cuda.synchronize()
         if world > 1:
+            torch.cuda.synchronize()
             dist.barrier()
-        torch.cuda.synchronize()
+            torch.cuda.synchronize()
 
     def max_over_ranks(x):
         if world == 1:
@@ -166,6 +186,14 @@ def main():
         t = torch.tensor([x], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
+
+    def finish(out):
+        log("done")
+        if rank == 0:
+            print(json.dumps(out))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
 
     # ------------------------------------------------------------------ scene (seeded, identical on every rank)
     t0 = time.time()
@@ -196,26 +224,62 @@ def main():
     ba = ctx.ba(mine)
     start = (mine.cam_pose.copy(), mine.cam_model.copy(), mine.point.copy())
 
+    def run_iterations(n):
+        """n LM iterations as runs of at most STEP_CHUNK, each from `start` (uploaded outside the timed window): the seconds
+        inside the runs (maximum over ranks) and the last run's summary with the step counts of all runs."""
+        secs, res, ok, bad = 0.0, None, 0, 0
+        for k in [STEP_CHUNK] * (n // STEP_CHUNK) + ([n % STEP_CHUNK] if n % STEP_CHUNK else []):
+            ba.upload(*start)
+            barrier()
+            t0 = time.perf_counter()
+            res = ba.run(fixed_iteration_options(k))
+            barrier()
+            secs += max_over_ranks(time.perf_counter() - t0)
+            assert res["num_iterations"] == k, res["termination"]
+            ok, bad = ok + res["num_successful_steps"], bad + res["num_unsuccessful_steps"]
+        return secs, dict(res, num_iterations=n, num_successful_steps=ok, num_unsuccessful_steps=bad)
+
     # ------------------------------------------------------------------ BA: warmup, then exactly K iterations
     if args.warmup > 0:
-        ba.run(fixed_iteration_options(args.warmup))
-    ba.upload(*start)
-    barrier()
-    t0 = time.perf_counter()
-    res = ba.run(fixed_iteration_options(args.steps))
-    barrier()
-    ba_s = max_over_ranks(time.perf_counter() - t0)
-    assert res["num_iterations"] == args.steps, res["termination"]
+        run_iterations(args.warmup)
+    ba_s, res = run_iterations(args.steps)
+    n_red = res["num_reduced_params"]
+    it_s = args.steps / ba_s
+    log("BA: %.1f iterations/s (%.3f ms per LM iteration)" % (it_s, 1e3 * ba_s / args.steps))
+    out = dict(metric="BA iterations/sec", value=it_s, unit="iterations/s", n_gpus=world, steps=args.steps,
+               warmup=args.warmup, ms_per_step=1e3 * ba_s / args.steps, higher_is_better=True, scaling="strong",
+               vs_baseline=None, dtype="f64", data="synthetic",
+               config=dict(workload=workload, reduced_system_order=n_red,
+                           parallelism="points sharded over %d rank(s), camera block all-reduced" % world, collective=collective,
+                           scaling_expectation="matching, verification, triangulation: no collective, rate proportional to N; bundle adjustment at this "
+                                               "size is Amdahl-bound - every rank repeats the dense-Schur factorisation of the %d-column camera system "
+                                               "(~0.45 of ~0.93 ms per iteration at N = 1): <= 1.6 x at N = 8 by any partitioning (DESIGN.md 5)" % n_red,
+                           successful_steps=res["num_successful_steps"], unsuccessful_steps=res["num_unsuccessful_steps"],
+                           setup_ms=res["setup_ms"], scene_gen_s=gen_s),
+               ba_cost=dict(initial=res["initial_cost"], final=res["final_cost"]))
+    if args.dump_outputs and rank == 0:
+        # the parameters after the last timed iteration (before any later leg uploads the start state again) and its summary
+        cp, cm, pt = ba.download()
+        dump = dict(cam_pose=cp, cam_model=cm, point=pt, iteration_cost=res["iterations"]["cost"],
+                    cost=np.array([res["initial_cost"], res["final_cost"]]))
+        assert sum(a.nbytes for a in dump.values()) <= 64 << 20   # config 5's million points are 24 MB
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in dump.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+        log("outputs written to %s" % args.dump_outputs)
+    if not args.full:
+        ba.close()
+        finish(out)
+        return
 
     # profiled pass (HIP events per kernel class on the ctx stream) for the roofline figures
     # (two passes, per kernel class the one with the smaller total: the event pairs around every launch make the pass sensitive to
     #  whatever else the box does - one collection of round 5 read 360 us for a kernel that rocprofv3 and the other passes put at 300)
     ba_stats = None
     for _ in range(2):
-        ba.upload(*start)
         ctx.profile(True)
         ctx.profile_reset()
-        res_p = ba.run(fixed_iteration_options(args.steps))
+        _, res_p = run_iterations(args.steps)
         st = ctx.profile_get()
         ctx.profile(False)
         if ba_stats is None:
@@ -227,6 +291,7 @@ def main():
 
     # the same K iterations as ONE msfm_ba_solve call on the host arrays (what replaces ceres::Solve in the reference):
     # index-structure setup + upload + K iterations + download, on the warm GPU; reported beside `value`, never as it
+    # (K capped at STEP_CHUNK: one call cannot run more iterations of the timed trajectory)
     one_shot = None
     if rank == 0 and world == 1:
         tmp = A.BaArrays(full.cam_pose, full.cam_model, full.cam_model_of_cam, full.point, full.obs_cam, full.obs_pt, full.obs_xy, full.pt_weight,
@@ -236,16 +301,13 @@ def main():
         for _ in range(2):   # the incremental loop solves again and again: the second call (device-block cache warm) is the steady state
             tmp.cam_pose[:], tmp.cam_model[:], tmp.point[:] = full.cam_pose, full.cam_model, full.point
             t0 = time.perf_counter()
-            r1 = ctx.ba_solve(tmp, fixed_iteration_options(args.steps))
+            r1 = ctx.ba_solve(tmp, fixed_iteration_options(min(args.steps, STEP_CHUNK)))
             dt = time.perf_counter() - t0
             os_s = dt if os_s is None else min(os_s, dt)
         one_shot = dict(ms=1e3 * os_s, iterations=r1["num_iterations"], setup_ms=r1["setup_ms"], iterations_per_s=r1["num_iterations"] / os_s,
                         note="msfm_ba_solve on host arrays (what replaces ceres::Solve): upload + index structures built on the device + "
                              "iterations + download + destroy; best of two calls")
 
-    n_red = res["num_reduced_params"]
-    it_s = args.steps / ba_s
-    log("BA: %.1f iterations/s (%.3f ms per LM iteration)" % (it_s, 1e3 * ba_s / args.steps))
     n_act_obs = res["num_residuals"] // 2
     alg_bytes = ba_algorithmic_bytes(n_act_obs, int(win["pt_mutable"].sum()) if win else sc.n_points,
                                      int(win["cam_mutable"].sum()) if win else sc.n_cams, n_red)
@@ -401,22 +463,12 @@ def main():
     attach_util(rooflines.get("chol_panel_mfma"), "ba")
     if roofline.get("kernel") == "chol_panel_mfma":
         attach_util(roofline, "ba")
-    out = dict(metric="BA iterations/sec", value=it_s, unit="iterations/s", n_gpus=world, steps=args.steps,
-               warmup=args.warmup, ms_per_step=1e3 * ba_s / args.steps, higher_is_better=True, scaling="strong",
-               vs_baseline=None, dtype="f64", data="synthetic",
-               config=dict(workload=workload, reduced_system_order=n_red,
-                           parallelism="points sharded over %d rank(s), camera block all-reduced" % world, collective=collective,
-                           scaling_expectation="matching, verification, triangulation: no collective, rate proportional to N; bundle adjustment at this "
-                                               "size is Amdahl-bound - every rank repeats the dense-Schur factorisation of the %d-column camera system "
-                                               "(~0.45 of ~0.93 ms per iteration at N = 1): <= 1.6 x at N = 8 by any partitioning (DESIGN.md 5)" % n_red,
-                           successful_steps=res["num_successful_steps"], unsuccessful_steps=res["num_unsuccessful_steps"],
-                           setup_ms=res["setup_ms"], scene_gen_s=gen_s),
-               roofline=roofline, roofline_whole_step=whole, kernel_rooflines=rooflines, ba_kernels=kernels,
+    out.update(roofline=roofline, roofline_whole_step=whole, kernel_rooflines=rooflines, ba_kernels=kernels,
                bound_note=("`bound` names the roof the dominant kernel is priced against (the contract's two values; 'mfma' = the FP64 rate, "
                            "which vector and matrix pipe share), not a throughput limit that has been reached: an LM iteration moves ~1.1 GB "
                            "(PMC) = ~14 % of HBM bandwidth and executes ~15 GFLOP = ~20 % of the FP64 roof - it is latency- and issue-bound "
                            "(dependent pivot chains, LDS gathers, two or three waves per SIMD)"),
-               ba_cost=dict(initial=res["initial_cost"], final=res["final_cost"]), ba_one_shot=one_shot)
+               ba_one_shot=one_shot)
     ba.close()
 
     # ------------------------------------------------------------------ matching legs: every ordered pair of the scene
@@ -781,13 +833,7 @@ def main():
             out["speedup_vs_cpu_port"]["matching_vs_all_cores"] = out["matching"]["value"] / cpu["matching"]["value"]
             out["speedup_vs_cpu_port"]["matching_note"] = "against exact brute force on the CPU, not against the reference's approximate kd-tree"
 
-
-    log("done")
-    if rank == 0:
-        print(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

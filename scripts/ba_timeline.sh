@@ -4,7 +4,7 @@ set -o pipefail
 R=$PWD; O=$R/gpurun_out/tl; rm -rf $O; mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-matching --no-extras > $O/kt.log 2>&1 || { tail -5 $O/kt.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt -- python3 $R/bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-matching --no-extras > $O/kt.log 2>&1 || { tail -5 $O/kt.log; exit 1; }
 cd $R
 python3 - <<'PY'
 import csv, glob

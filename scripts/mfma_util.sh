@@ -19,6 +19,6 @@ run() {   # name, program + args
 }
 run knn_i8 python3 $R/scripts/knn_only.py 48
 run knn_f16 python3 $R/scripts/knn_float_only.py
-run ba python3 $R/bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-matching --no-extras
+run ba python3 $R/bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-matching --no-extras
 cd $R
 python3 scripts/mfma_util_to_json.py $O $O/r05_mfma_util.json

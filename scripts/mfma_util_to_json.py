@@ -49,7 +49,7 @@ def main():
         res[wl] = e
     res["_source"] = ("rocprofv3 --pmc passes of scripts/mfma_util.sh (one counter group per pass, program directly after --): "
                       "scripts/knn_only.py 48 (2256 pairs, int8), scripts/knn_float_only.py (552 pairs, f16), "
-                      "bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-matching --no-extras (k_chain: the persistent panel chain)")
+                      "bench.py --steps 5 --warmup 1 --full --no-cpu-baseline --no-matching --no-extras (k_chain: the persistent panel chain)")
     import hashlib
     h = hashlib.sha256()
     d = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "metricsfm_amd", "csrc")

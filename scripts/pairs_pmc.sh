@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cd /tmp
 for set in "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" "TCP_TCC_READ_REQ_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_LATENCY_sum SQ_WAVE_CYCLES" "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum SQ_BUSY_CYCLES" "SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_WAIT_INST_ANY"; do
   n=$(echo $set | tr ' ' '_')
-  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $O/$n -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-matching > $O/$n.log 2>&1 || echo "pass $n failed"
+  timeout -k 10 200 rocprofv3 --pmc $set --output-format csv -d $O/$n -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-matching > $O/$n.log 2>&1 || echo "pass $n failed"
   f=$(find $O/$n -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python3 - "$f" <<'PY'
 import csv,sys,collections

@@ -1,9 +1,9 @@
 """Turn the two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) into profiles/pmc_traffic.json.
 
   cd /tmp && export TMPDIR=/tmp
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/pmc_f -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-matching
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/pmc_w -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-matching
-  python3 scripts/pmc_to_json.py /tmp/pmc_f /tmp/pmc_w profiles/pmc_traffic.json profiles/r01_pmc
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d pmc_f -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-matching
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d pmc_w -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-matching
+  python3 scripts/pmc_to_json.py pmc_f pmc_w profiles/pmc_traffic.json profiles/r01_pmc
 
 bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: on gfx950 FETCH_SIZE tallies the 128-byte requests of wide
 coalesced reads at 64 bytes (MI355X_MICROARCH.md, HBM section); 16-byte gathers are NOT under-counted, so for the gather
@@ -43,7 +43,7 @@ def main():
         shutil.copy(ff, prefix + "_fetch_size.csv")
         shutil.copy(wf, prefix + "_write_size.csv")
     res, raw = {}, {}
-    src = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --steps 3 --warmup 1 --no-cpu-baseline "
+    src = ("rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "
            "--no-matching`; bytes = (2*FETCH_SIZE + WRITE_SIZE)*1024 (gfx950 FETCH_SIZE counts wide reads at 1/2, MI355X_MICROARCH.md "
            "HBM section); gather kernels are not under-counted: see bytes_per_launch_uncorrected")
     for cls, pats in CLASSES.items():

@@ -9,7 +9,7 @@ for mode in fold nofold; do
   g=0
   for set in "${GROUPS_[@]}"; do
     if [ $mode = nofold ]; then export MSFM_NO_FOLD=1; else unset MSFM_NO_FOLD; fi
-    timeout -k 10 240 rocprofv3 --pmc $set --output-format csv -d $O/$mode.$g -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-matching --no-extras > $O/$mode.$g.log 2>&1 || echo "pass $mode.$g failed"
+    timeout -k 10 240 rocprofv3 --pmc $set --output-format csv -d $O/$mode.$g -- python3 $R/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-matching --no-extras > $O/$mode.$g.log 2>&1 || echo "pass $mode.$g failed"
     g=$((g + 1))
   done
 done

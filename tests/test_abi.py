@@ -57,8 +57,11 @@ def test_defaults_are_the_ceres_defaults():
 
 
 def test_no_cpu_fallback_without_gpu():
-    import torch
-    if torch.cuda.is_available():
+    # torch is asked in a child process: it brings its own HIP runtime, and initialising that one here, after libmsfm has
+    # loaded the runtime it links, leaves libmsfm without a device for the rest of the test session
+    probe = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"],
+                           capture_output=True, text=True, timeout=300, check=True)
+    if probe.stdout.strip().splitlines()[-1] == "True":
         pytest.skip("a GPU is visible here")
     with pytest.raises(capi.MsfmError) as e:
         capi.Context(0)

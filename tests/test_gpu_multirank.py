@@ -104,7 +104,7 @@ def test_bench_starts_its_own_ranks():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--config", "2", "--steps", "4",
-                          "--warmup", "1", "--no-matching", "--no-cpu-baseline", "--verify-pairs", "64", "--pose-images", "32"],
+                          "--warmup", "1", "--full", "--no-matching", "--no-cpu-baseline", "--verify-pairs", "64", "--pose-images", "32"],
                          env=env, cwd=ROOT, timeout=900, capture_output=True, text=True)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
