@@ -42,11 +42,6 @@ static int chunk_for(long total, int max_chunk) {
   const long c = 64 * ((total / 1024 + 63) / 64);
   return (int)std::max<long>(64, std::min<long>(max_chunk, c));
 }
-static int ftf_chunk(long rows) {
-  const char* e = getenv("MSFM_FTF_CHUNK");   // (experiments)
-  const int v = e ? atoi(e) : 0;
-  return v >= 64 ? v : chunk_for(rows, FTF_CHUNK);
-}
 // FTF partial layout
 #define F_JCJC 0     // 36
 #define F_JMJC 36    // 18 (3x6)
@@ -325,13 +320,6 @@ struct PointPtrs {
 #define FOLD_NREC (256 + FOLD_OVF)   // records of 2 x 10 doubles (two 16-byte aligned halves of 9) in the 48 KB row park
 #define FOLD_WORDS 1024      // words (slot headers + entries) of one pass, staged in LDS
 #define FOLD_PASS_SLOTS 128  // slots of one pass at most: four threads per slot, two rounds
-#ifdef MSFM_FOLD_STAMPS
-// developer build only (make CXXFLAGS+=-DMSFM_FOLD_STAMPS): clock stamps of wave 0 of every folding workgroup
-__device__ long long g_fold_stamps[8192][8];
-#define FSTAMP(i) do { if (fold && tid == 0 && blockIdx.x < 8192) g_fold_stamps[blockIdx.x][i] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define FSTAMP(i) do {} while (0)
-#endif
 __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restrict__ gmax_partial, double* sh, double* park, unsigned* ent_s) {
   const int tid = threadIdx.x, sub = tid & 7;
   const int pb = blockIdx.x * 32 + (tid >> 3);
@@ -351,7 +339,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     fp1 = __builtin_amdgcn_readfirstlane(P.fold_wg_pass_first[blockIdx.x + 1]);
     stage(__builtin_amdgcn_readfirstlane(P.fold_pass[fp0].off), __builtin_amdgcn_readfirstlane(P.fold_pass[fp0].words));
   }
-  FSTAMP(0);
   int f = 0, l = 0;
   if (act) { f = P.pt_first[pb]; l = P.pt_first[pb + 1]; }
   const bool single = (l - f) <= 8;
@@ -375,7 +362,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
       g0 += a0 * r0 + b0 * r1; g1 += a1 * r0 + b1 * r1; g2 += a2 * r0 + b2 * r1;
     }
   }
-  FSTAMP(1);
   GROUP_SUM(V00) GROUP_SUM(V10) GROUP_SUM(V11) GROUP_SUM(V20) GROUP_SUM(V21) GROUP_SUM(V22)
   GROUP_SUM(g0) GROUP_SUM(g1) GROUP_SUM(g2)
 
@@ -424,7 +410,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
       }
     }
   }
-  FSTAMP(2);
   if (P.mode != 1) {
     // camera entries: T = (Jc^T Jp) L^-T (one 144-byte record per observation, camera-major), T.u
     // Stores: neighbouring lanes hold the observations of ONE point - eight different cameras, eight far-apart addresses,
@@ -514,9 +499,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     {
       double Tk[18];
       int cpk;
-      FSTAMP(3);
       round(0, Tk, cpk);
-      FSTAMP(4);
       // (point, intrinsics-block) entries: Tm = (sum Jm^T Jp) L^-T.  After the first round and after the park has turned into
       // the record store, so that the lane that forms Tm can put it beside the records (its first entry's: with one intrinsics
       // block that is the only one; a point without an entry leaves zeros): the lane's Jm and Jp rows cross the barrier in
@@ -599,7 +582,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
 #pragma unroll
         for (int k = 0; k < 9; k++) ((k & 1) ? H1 : H0)[(tid + (k >> 1)) * 10 + 9] = 0.0;
       }
-      FSTAMP(5);
       for (int rd = 8; __any(f + rd < l); rd += 8) {
         const int ovf = (fold && act) ? P.fold_ovf_off[pb] : 0;   // (asked for before the round's own loads)
         round(rd, Tk, cpk);
@@ -610,7 +592,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
         }
       }
     }
-    FSTAMP(6);
     if (fold) {
       const int q = tid & 3, ra = q >> 1, rb = q & 1, sl4 = tid >> 2;   // rows 3 ra .. of record i times rows 3 rb .. of record j
       for (int p = fp0; p < fp1; p++) {
@@ -695,7 +676,6 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
             for (int c = 0; c < 3; c++) out[(3 * ra + a) * 6 + 3 * rb + c] = acc[a * 3 + c];
         }
       }
-      FSTAMP(7);
     }
   }
   if (P.store_rows) {
@@ -1409,45 +1389,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     if (i < l) {
       // rows of frozen blocks come out as zeros, so no branches
       double jp[6], r0, r1, q0, q1;
-#ifdef MSFM_BACKSUB_DIRECTIONAL
-      // Round 5, measured and NOT the default: q = -(J_c z_c + J_m z_m) as the directional derivative of the row's residual along
-      // the (unscaled) camera / intrinsics step instead of eighteen Jacobian columns contracted with it (msfm_reproj_dir): the
-      // same corrected, scaled quantities to rounding (every parity test green), 164 binary64 operations per row less (710 -> 546
-      // in the kernel's stream) - and the kernel SLOWER, 101 -> 117 us at config 3 (1 077 -> 1 056 iterations/s): the step and
-      // the scales now stand in front of the projection instead of behind it, one more level in the chain of dependent gathers
-      // of a kernel that waits for memory at three waves per SIMD.  A frozen block has a zero scale, hence a zero step.
-      {
-        const BaPtrs& B = P.B;
-        const int c = B.o_cam[i], m = B.o_model[i], p = B.o_pt[i];
-        const int cb = B.o_cb[i], mb = B.o_mb[i], pbk = B.o_pb[i];
-        double pose[6], rc[4], cm[3], X[3];
-#pragma unroll
-        for (int j = 0; j < 6; j++) pose[j] = B.cam[6 * (size_t)c + j];
-#pragma unroll
-        for (int j = 0; j < 4; j++) rc[j] = B.rot[4 * (size_t)c + j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) { cm[j] = B.model[3 * (size_t)m + j]; X[j] = B.pt[3 * (size_t)p + j]; }
-        const double* zcp = P.z + 6 * (cb >= 0 ? cb : 0);
-        const double* zmp = P.z + 6 * P.ncb + 3 * (mb >= 0 ? mb : 0);
-        double zw[3], zt[3], zmv[3], sp[3];
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-          zw[j] = cb >= 0 ? B.scale_c[6 * cb + j] * zcp[j] : 0.0;
-          zt[j] = cb >= 0 ? B.scale_c[6 * cb + 3 + j] * zcp[3 + j] : 0.0;
-          zmv[j] = mb >= 0 ? B.scale_m[3 * mb + j] * zmp[j] : 0.0;
-          sp[j] = pbk >= 0 ? B.scale_p[3 * (size_t)pbk + j] : 0.0;
-        }
-        double r[2], Jp[6], d[2];
-        msfm_reproj_dir(pose, rc, cm, X, B.o_x[i], B.o_y[i], B.o_w[i], zw, zt, zmv, r, Jp, d);
-        double rho0, rho1;
-        msfm_huber(B.huber, r[0] * r[0] + r[1] * r[1], rho0, rho1);
-        const double sq = sqrt(rho1);
-        r0 = sq * r[0]; r1 = sq * r[1];
-        q0 = -(sq * d[0]); q1 = -(sq * d[1]);
-#pragma unroll
-        for (int j = 0; j < 3; j++) { const double spj = sq * sp[j]; jp[j] = spj * Jp[j]; jp[3 + j] = spj * Jp[3 + j]; }
-      }
-#else
       {
         const int cb = P.B.o_cb[i], mb = P.B.o_mb[i];
         double jc[12], jm[6], zc[6], zm[3];
@@ -1465,7 +1406,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
         for (int j = 0; j < 3; j++) { q0 -= jm[j] * zm[j]; q1 -= jm[3 + j] * zm[j]; }
       }
-#endif
       const double a0 = jp[0], a1 = jp[1], a2 = jp[2], b0 = jp[3], b1 = jp[4], b2 = jp[5];
       V00 += a0 * a0 + b0 * b0; V10 += a1 * a0 + b1 * b0; V11 += a1 * a1 + b1 * b1;
       V20 += a2 * a0 + b2 * b0; V21 += a2 * a1 + b2 * b1; V22 += a2 * a2 + b2 * b2;
@@ -1695,6 +1635,7 @@ struct msfm_ba {
   int ncb = 0, nmb = 0, npb = 0, nred = 0, npad = 0;
   // solver layout of the reduced system: camera block cb at column cb_off[cb], intrinsics at mo + 3 mb, order nsys
   int nsys = 0, mo = 0, n_padcol = 0;
+  msfm_env env;   // the switches as they were at msfm_ba_create (common.h)
   msfm_chol_plan plan;
   msfm_chol_ws* chol_ws = nullptr;   // hand-off state of the persistent panel chain (chol.hip)
   DevBuf<int> cb_off, padcol;
@@ -2131,7 +2072,7 @@ static void order_camera_blocks(msfm_ctx* ctx, msfm_ba* ba, const std::vector<in
     }
     ba->plan.n_levels = nl;
     for (int g : T.seps[0][0].cams) place(g);
-    if (getenv("MSFM_VERBOSE") && ctx->rank == 0) {
+    if (msfm_env_process().verbose && ctx->rank == 0) {
       fprintf(stderr, "msfm: camera graph %d nodes ->", ng);
       for (int l = 0; l < nl; l++) {
         fprintf(stderr, " level %d:", l);
@@ -2206,21 +2147,6 @@ MSFM_API void msfm_ba_destroy(msfm_ba* ba) {
   if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);   // the pair kernels read T / Tm and write the partials freed below
   msfm_chol_ws_destroy(ba->chol_ws);
   ba->chol_ws = nullptr;
-#ifdef MSFM_FOLD_STAMPS
-  if (ba->fold.on) {
-    static long long h[8192][8];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_fold_stamps), sizeof(h)) == hipSuccess) {
-      double d[8] = {0}; int n = 0;
-      for (int w = 0; w < std::min(8192, ba->fold.n_wg); w++) {
-        if (h[w][7] <= h[w][0]) continue;
-        for (int k = 1; k < 8; k++) d[k] += (double)(h[w][k] - h[w][k - 1]);
-        n++;
-      }
-      fprintf(stderr, "msfm: k_point stamps (mean over %d workgroups, cycles of wave 0): linearise %.0f, reduce+factor %.0f, Tm %.0f, round 0 %.0f, records %.0f, later rounds %.0f, fold passes %.0f\n",
-              n, d[1] / n, d[2] / n, d[3] / n, d[4] / n, d[5] / n, d[6] / n, d[7] / n);
-    }
-  }
-#endif
   if (ba->h_scal) (void)hipHostFree(ba->h_scal);
   if (ba->h_fail) (void)hipHostFree(ba->h_fail);
   delete ba;
@@ -2364,10 +2290,6 @@ __global__ __launch_bounds__(256) void k_point_keys(int Np, const uint8_t* __res
   vals[pu_pos[p]] = p;
 }
 
-__global__ __launch_bounds__(256) void k_compact_used(int Np, const uint8_t* __restrict__ pu, const int* __restrict__ pu_pos, int* __restrict__ vals) {
-  const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p < Np && pu[p]) vals[pu_pos[p]] = p;
-}
 __global__ __launch_bounds__(256) void k_u8_to_int(int n, const uint8_t* __restrict__ a, int* __restrict__ b) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) b[i] = a[i] ? 1 : 0;
@@ -2902,25 +2824,14 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   using namespace devsetup;
   FoldTables& F = ba->fold;
   F.on = false;
-  static const bool off = getenv("MSFM_NO_FOLD") != nullptr;
   const int npb = ba->npb, ncb = ba->ncb;
   // (small problems keep the gather path: their pair list fits the caches anyway and the tables would only lengthen the set-up;
   //  MSFM_FOLD_MIN overrides the threshold, e.g. 0 to fold everything in a test)
-  static const long fold_min = getenv("MSFM_FOLD_MIN") ? atol(getenv("MSFM_FOLD_MIN")) : 262144;
-  if (off || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
+  if (ba->env.no_fold || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < ba->env.fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
   hipStream_t s = ctx->stream;
   DevBuf<char> tmp;
   const int n_wg = cdiv(npb, 32);
   F.n_wg = n_wg;
-  static const bool laps = getenv("MSFM_FOLD_LAPS") != nullptr;   // developer switch: where the set-up time goes
-  auto t_last = std::chrono::steady_clock::now();
-  auto flap = [&](const char* what) {
-    if (!laps) return;
-    (void)hipStreamSynchronize(s);
-    const auto t = std::chrono::steady_clock::now();
-    fprintf(stderr, "msfm: fold set-up %-28s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - t_last).count());
-    t_last = t;
-  };
   DTRY(F.wg_fold.alloc(n_wg)); DTRY(F.ovf_off.alloc(npb));
   hipLaunchKernelGGL(k_fold_wg, dim3(cdiv(n_wg, 256)), dim3(256), 0, s, npb, n_wg, ba->pt_first.p, F.ovf_off.p, F.wg_fold.p);
   DevBuf<int> count, offset;
@@ -2933,7 +2844,6 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   DTRY(hipMemcpyAsync(&E, offset.p + npb, sizeof(int), hipMemcpyDeviceToHost, s));
   DTRY(hipStreamSynchronize(s));
   if (E <= 0) return MSFM_OK;
-  flap("count entries");
   DevBuf<unsigned long long> key, key_s, slot_key2, slot_key2_s;
   DevBuf<unsigned> val;
   DevBuf<int> head, slot_of, slot_id, slot_id_s;
@@ -2946,10 +2856,8 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     const int bits = 32 + bits_for(std::max(2, n_wg));
     DTRY(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));
     if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
-    flap("emit entries");
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));   // stable: point order inside a slot
   }
-  flap("sort entries");
   DTRY(head.alloc((size_t)E + 1)); DTRY(slot_of.alloc((size_t)E + 1));
   DTRY(hipMemsetAsync(head.p + E, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_fold_heads, dim3(cdiv(E, 256)), dim3(256), 0, s, E, key_s.p, head.p);
@@ -2964,7 +2872,6 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   DevBuf<int> wg_slot_first;
   DTRY(wg_slot_first.alloc((size_t)n_wg + 1));
   hipLaunchKernelGGL(k_fold_wg_first, dim3(cdiv(n_wg + 1, 256)), dim3(256), 0, s, n_wg, NS, slot_key2.p, wg_slot_first.p);
-  flap("slots");
   // the passes and the stream they read
   DevBuf<int> perm;
   {
@@ -2979,7 +2886,6 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
     DTRY(hipStreamSynchronize(s));
   }
-  flap("slot order");
   {
     DevBuf<int> wg_npass, wg_words, words_first, slot_ent_pos;
     DTRY(wg_npass.alloc((size_t)n_wg + 1)); DTRY(wg_words.alloc((size_t)n_wg + 1)); DTRY(words_first.alloc((size_t)n_wg + 1));
@@ -3021,7 +2927,6 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   DTRY(F.blk_range.alloc(2 * (size_t)std::max(1, ba->cc.n_blocks)));
   hipLaunchKernelGGL(k_fold_blk_range, dim3(cdiv(std::max(1, ba->cc.n_blocks), 256)), dim3(256), 0, s, ba->cc.n_blocks, NS, ncb, ba->cc.blk_row.p, ba->cc.blk_col.p,
                      slot_key2_s.p, F.blk_range.p);
-  flap("passes, stream, ranks, ranges");
   // the same entries leave the gather path
   DevBuf<uint8_t> folded;
   DTRY(folded.alloc((size_t)std::max(1, ba->NCR)));
@@ -3050,12 +2955,10 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     return MSFM_OK;
   };
   MSFM_TRY(live_chunks(ba->cc, 36, F.n_live, F.live_chunk, &F.blk_live));
-  flap("mark + live chunks");
   // intrinsics x camera list: with ONE intrinsics block every point has at most one (point, intrinsics) entry and the
   // products Tm_p T^T of a camera are summed over exactly the records of its diagonal slots
   F.mc_on = false;
-  static const bool mc_off = getenv("MSFM_NO_FOLD_MC") != nullptr;
-  if (!mc_off && ba->nmb == 1 && ba->mc.n_pairs > 0) {
+  if (ba->nmb == 1 && ba->mc.n_pairs > 0) {
     DTRY(F.mc_range.alloc(2 * (size_t)ba->mc.n_blocks));
     hipLaunchKernelGGL(k_fold_mc_range, dim3(cdiv(ba->mc.n_blocks, 256)), dim3(256), 0, s, ba->mc.n_blocks, NS, ba->mc.blk_col.p, slot_key2_s.p, F.mc_range.p);
     // (diagonal keys are the ncb smallest: their slots have the ranks 0 .. n_diag - 1)
@@ -3092,13 +2995,12 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
       F.mc_all = F.mc_n_live == 0;
     }
   }
-  flap("intrinsics x camera");
   DTRY(hipGetLastError());
   DTRY(hipStreamSynchronize(s));   // the temporaries above go back to the pool
   F.n_slots = NS; F.n_entries = E;
   F.on = true;
   F.all = E == ba->cc.n_pairs;
-  if (getenv("MSFM_VERBOSE") && ctx->rank == 0)
+  if (msfm_env_process().verbose && ctx->rank == 0)
     fprintf(stderr, "msfm: fold tables: %d workgroups, %d passes, %d slots (%.1f MB of partials), %d of %d entries folded; intrinsics x camera: %s, %d diagonal slots, %d of %d chunks live\n",
             n_wg, F.n_pass, NS, NS * 288e-6, E, ba->cc.n_pairs, F.mc_on ? "folded" : "gathered", F.n_diag, F.mc_n_live, ba->mc.n_chunks);
   return MSFM_OK;
@@ -3159,8 +3061,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   std::vector<int> gnode(Nc, -1), gcam;
   for (int c = 0; c < Nc; c++) if (cu[c]) { gnode[c] = (int)gcam.size(); gcam.push_back(c); }
   const int ng = (int)gcam.size();
-  const char* env = getenv("MSFM_CHOL_DOMAINS");
-  const int force = env ? atoi(env) : -1;
+  const int force = ba->env.chol_domains;
   std::vector<uint8_t> adjb;
   if (ng >= 128 && ng <= 4096 && force != 0) {
     DevBuf<int> d_gnode;
@@ -3235,16 +3136,11 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   DTRY(hipStreamSynchronize(s));
   ba->npb = npb;
   DTRY(ba->pb_pt.alloc((size_t)std::max(1, npb)));
-  const bool order_points = !getenv("MSFM_POINT_ORDER") || atoi(getenv("MSFM_POINT_ORDER")) != 0;
   if (npb) {
-    if (order_points) {
-      DTRY(d_keys.alloc(npb)); DTRY(d_keys_sorted.alloc(npb)); DTRY(d_vals.alloc(npb));
-      hipLaunchKernelGGL(k_point_keys, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_pos.p, d_run_first.p, d_obs_cam.p, d_cam_slot.p,
-                         ncb >= 0xFFFF ? 1 : 0, d_keys.p, d_vals.p);
-      DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, ba->pb_pt.p, (size_t)npb, 64, s, tmp));
-    } else {
-      hipLaunchKernelGGL(k_compact_used, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_pos.p, ba->pb_pt.p);
-    }
+    DTRY(d_keys.alloc(npb)); DTRY(d_keys_sorted.alloc(npb)); DTRY(d_vals.alloc(npb));
+    hipLaunchKernelGGL(k_point_keys, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_pos.p, d_run_first.p, d_obs_cam.p, d_cam_slot.p,
+                       ncb >= 0xFFFF ? 1 : 0, d_keys.p, d_vals.p);
+    DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, ba->pb_pt.p, (size_t)npb, 64, s, tmp));
   }
   DTRY(d_pt_slot.alloc((size_t)std::max(1, Np))); DTRY(d_len.alloc((size_t)npb + 1)); DTRY(ba->pt_first.alloc((size_t)npb + 1));
   DTRY(hipMemsetAsync(d_len.p + npb, 0, sizeof(int), s));
@@ -3317,7 +3213,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
                                      ba->pm_mb.p, ba->o_pm.p, d_err.p);
   // ---- FTF chunks (host: O(cameras + rows / 1024)) ----
   std::vector<int> f_start, f_end, cam_chunk_first(ncb + 1, 0);
-  const int fchunk = ftf_chunk(cam_first[ncb]);
+  const int fchunk = chunk_for(cam_first[ncb], FTF_CHUNK);
   for (int c = 0; c < ncb; c++) {
     cam_chunk_first[c] = (int)f_start.size();
     for (int e = cam_first[c]; e < cam_first[c + 1]; e += fchunk) { f_start.push_back(e); f_end.push_back(std::min(e + fchunk, cam_first[c + 1])); }
@@ -3403,8 +3299,7 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
     std::vector<int> gnode(Nc, -1), gcam;
     for (int c = 0; c < Nc; c++) if (cu[c]) { gnode[c] = (int)gcam.size(); gcam.push_back(c); }
     const int ng = (int)gcam.size();
-    const char* env = getenv("MSFM_CHOL_DOMAINS");  // "0": dense order, "1".."3": force that bisection depth
-    const int force = env ? atoi(env) : -1;
+    const int force = ba->env.chol_domains;  // 0: dense order, 1..3: force that bisection depth
     std::vector<uint8_t> adjb8;
     if (ng >= 128 && ng <= 4096 && force != 0) {
       // adjacency as a 0/1 matrix: cameras sharing an eliminated point; max-reduced over the ranks' shards
@@ -3439,45 +3334,43 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
     // Points seen by the same cameras become neighbours, so the records of a camera pair's common points are
     // runs in both cameras' segments (the pair kernel's gathers and k_point's scattered stores turn near-sequential).
     // Internal only: h_pb_pt maps block -> caller's point index.
-    if (!getenv("MSFM_POINT_ORDER") || atoi(getenv("MSFM_POINT_ORDER")) != 0) {
-      // key: the four smallest camera blocks, 16 bits each (21 bits x 3 when there are more than 65535 blocks)
-      const bool wide = ba->ncb >= 0xFFFF;
-      std::vector<std::pair<uint64_t, int>>& keyed = H.keyed;
-      keyed.resize(ba->h_pb_pt.size());
-      const int nk = wide ? 3 : 4, bits = wide ? 21 : 16;
-      par_ranges(keyed.size(), host_threads(), [&](int, size_t i0, size_t i1) {
-        std::vector<int> cams;
-        for (size_t i = i0; i < i1; i++) {
-          const int p = ba->h_pb_pt[i];   // still in ascending point order here
-          cams.clear();
-          for (int e = run_first[p]; e < run_first[p + 1]; e++)
-            if (cam_slot[P->obs_cam[e]] >= 0) cams.push_back(cam_slot[P->obs_cam[e]]);
-          std::sort(cams.begin(), cams.end());
-          uint64_t k = 0;
-          for (int q = 0; q < nk; q++) k = (k << bits) | (uint64_t)(q < (int)cams.size() ? cams[q] : ((1 << bits) - 1));
-          keyed[i] = {k, p};
-        }
-      });
-      {  // sort: pieces in parallel, then pairwise merges (ties fall back to the caller's point index)
-        const int nt = (int)std::max<size_t>(1, std::min<size_t>(host_threads(), keyed.size() / 8192 + 1));
-        std::vector<size_t> cut(nt + 1);
-        for (int t = 0; t <= nt; t++) cut[t] = keyed.size() * t / nt;
-        {
-          std::vector<std::thread> th;
-          for (int t = 1; t < nt; t++) th.emplace_back([&, t] { std::sort(keyed.begin() + cut[t], keyed.begin() + cut[t + 1]); });
-          std::sort(keyed.begin() + cut[0], keyed.begin() + cut[1]);
-          for (auto& x : th) x.join();
-        }
-        for (int w = 1; w < nt; w *= 2) {
-          std::vector<std::thread> th;
-          for (int t = 0; t + w < nt; t += 2 * w)
-            th.emplace_back([&, t, w] { std::inplace_merge(keyed.begin() + cut[t], keyed.begin() + cut[t + w], keyed.begin() + cut[std::min(nt, t + 2 * w)]); });
-          for (auto& x : th) x.join();
-        }
+    // key: the four smallest camera blocks, 16 bits each (21 bits x 3 when there are more than 65535 blocks)
+    const bool wide = ba->ncb >= 0xFFFF;
+    std::vector<std::pair<uint64_t, int>>& keyed = H.keyed;
+    keyed.resize(ba->h_pb_pt.size());
+    const int nk = wide ? 3 : 4, bits = wide ? 21 : 16;
+    par_ranges(keyed.size(), host_threads(), [&](int, size_t i0, size_t i1) {
+      std::vector<int> cams;
+      for (size_t i = i0; i < i1; i++) {
+        const int p = ba->h_pb_pt[i];   // still in ascending point order here
+        cams.clear();
+        for (int e = run_first[p]; e < run_first[p + 1]; e++)
+          if (cam_slot[P->obs_cam[e]] >= 0) cams.push_back(cam_slot[P->obs_cam[e]]);
+        std::sort(cams.begin(), cams.end());
+        uint64_t k = 0;
+        for (int q = 0; q < nk; q++) k = (k << bits) | (uint64_t)(q < (int)cams.size() ? cams[q] : ((1 << bits) - 1));
+        keyed[i] = {k, p};
       }
-      if (keyed.size() == ba->h_pb_pt.size())
-        for (size_t i = 0; i < keyed.size(); i++) ba->h_pb_pt[i] = keyed[i].second;
+    });
+    {  // sort: pieces in parallel, then pairwise merges (ties fall back to the caller's point index)
+      const int nt = (int)std::max<size_t>(1, std::min<size_t>(host_threads(), keyed.size() / 8192 + 1));
+      std::vector<size_t> cut(nt + 1);
+      for (int t = 0; t <= nt; t++) cut[t] = keyed.size() * t / nt;
+      {
+        std::vector<std::thread> th;
+        for (int t = 1; t < nt; t++) th.emplace_back([&, t] { std::sort(keyed.begin() + cut[t], keyed.begin() + cut[t + 1]); });
+        std::sort(keyed.begin() + cut[0], keyed.begin() + cut[1]);
+        for (auto& x : th) x.join();
+      }
+      for (int w = 1; w < nt; w *= 2) {
+        std::vector<std::thread> th;
+        for (int t = 0; t + w < nt; t += 2 * w)
+          th.emplace_back([&, t, w] { std::inplace_merge(keyed.begin() + cut[t], keyed.begin() + cut[t + w], keyed.begin() + cut[std::min(nt, t + 2 * w)]); });
+        for (auto& x : th) x.join();
+      }
     }
+    if (keyed.size() == ba->h_pb_pt.size())
+      for (size_t i = 0; i < keyed.size(); i++) ba->h_pb_pt[i] = keyed[i].second;
     for (size_t i = 0; i < ba->h_pb_pt.size(); i++) pt_slot[ba->h_pb_pt[i]] = ba->npb++;
     HIP_TRY(ctx, ba->cb_off.from(cb_off_h.empty() ? std::vector<int>(1, 0) : cb_off_h, s));
     HIP_TRY(ctx, ba->padcol.from(padcol_h.empty() ? std::vector<int>(1, 0) : padcol_h, s));
@@ -3625,7 +3518,7 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
   lap("positions + pm entries");
   // ---- FTF chunks (camera-major rows) ----
   std::vector<int> f_start, f_end, cam_chunk_first(ncb + 1, 0);
-  const int fchunk = ftf_chunk(cam_first[ncb]);
+  const int fchunk = chunk_for(cam_first[ncb], FTF_CHUNK);
   for (int c = 0; c < ncb; c++) {
     cam_chunk_first[c] = (int)f_start.size();
     for (int e = cam_first[c]; e < cam_first[c + 1]; e += fchunk) { f_start.push_back(e); f_end.push_back(std::min(e + fchunk, cam_first[c + 1])); }
@@ -3751,7 +3644,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   *out = nullptr;
   struct ExitLap {   // declared first, destroyed last: the time to the very end of the call, host vectors released
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-    bool on = getenv("MSFM_VERBOSE") != nullptr;
+    bool on = msfm_env_process().verbose;
     ~ExitLap() { if (on) fprintf(stderr, "msfm: create returned after          %7.2f ms (from entry)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count()); }
   } exit_lap;
   if (P->n_cams <= 0 || P->n_models <= 0 || P->n_points < 0 || P->n_obs < 0 || !P->cam_pose || !P->cam_model ||
@@ -3762,7 +3655,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
     if (P->cam_model_of_cam[c] < 0 || P->cam_model_of_cam[c] >= P->n_models)
       return msfm_set_error(ctx, MSFM_E_INVAL, "cam_model_of_cam[%d] out of range", c);
   const auto t0 = std::chrono::steady_clock::now();
-  const bool verbose = getenv("MSFM_VERBOSE") != nullptr;
+  const bool verbose = exit_lap.on;
   if (verbose) fprintf(stderr, "msfm: create input checked after     %7.2f ms (from entry)\n", std::chrono::duration<double, std::milli>(t0 - exit_lap.t).count());
   auto lap = [&](const char* what) {
     if (verbose && ctx->rank == 0)
@@ -3773,11 +3666,11 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   msfm_ba* ba = new msfm_ba();
   struct Guard { msfm_ba* p; ~Guard() { if (p) msfm_ba_destroy(p); } } guard{ba};
   ba->ctx = ctx;
+  ba->env = msfm_env_read();
   ctx->children++;
   ba->world_at_create = ctx->world;
   {
-    const char* e = getenv("MSFM_CREATE_HOST");
-    const bool on_host = e && atoi(e) != 0;
+    const bool on_host = ba->env.create_host;
     if (on_host && bulk_on_device) return msfm_set_error(ctx, MSFM_E_INVAL, "MSFM_CREATE_HOST=1 needs the problem arrays in host memory");
     MSFM_TRY(on_host ? create_structures_host(ctx, P, ba, lap) : create_structures_device(ctx, P, ba, lap, bulk_on_device));
     MSFM_TRY(build_fold_device(ctx, ba));   // from the resident structures: the same tables whichever way those were built
@@ -3829,7 +3722,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart);
   AL(gmax_buf, (size_t)ba->nblk_pt + 6 * (size_t)ncb + 3 * (size_t)nmb + 8);
   AL(scal, S_N); AL(sloc, S_N); AL(spec, 8);
-  { const char* e = getenv("MSFM_SPEC"); ba->spec_on = !(e && atoi(e) == 0); }
+  ba->spec_on = ba->env.spec;
   HIP_TRY(ctx, ba->fail.alloc(4));
 #undef AL
   // the first solve's solution buffer starts out "pending"; from then on every solve marks the other one (k_backsolve_chain)
@@ -4022,8 +3915,8 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   Q.fold_pass = F.pass.p; Q.fold_stream = F.stream.p; Q.fold_partial = F.partial.p;
   Q.fold_mc_partial = (F.on && F.mc_on) ? F.mc_partial.p : nullptr;
   Q.spec = spec;
-  { static const bool keep = getenv("MSFM_KEEP_T") != nullptr && atoi(getenv("MSFM_KEEP_T")) != 0; Q.keep_T = keep ? 1 : 0; }
-  { static const bool d = !(getenv("MSFM_TU_DIRECT") != nullptr && atoi(getenv("MSFM_TU_DIRECT")) == 0); Q.tu_direct = d ? 1 : 0; }
+  Q.keep_T = ba->env.keep_t ? 1 : 0;
+  Q.tu_direct = ba->env.tu_direct ? 1 : 0;
   hipLaunchKernelGGL(k_point, dim3(ba->nblk_pt), dim3(256), 0, ctx->stream, Q, ba->gmax_buf.p);
 }
 
@@ -4067,16 +3960,14 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
   };
   // Round 3: with the gather path (the three pair kernels fill the chip by themselves) the fork gave nothing (1.277 ms per
   // iteration with it, 1.255-1.273 without); with the fold tables the pair kernels are three short launches and the fork
-  // pays again (1.251 -> 1.229 ms per iteration at config 3).  So: forked when the fold tables are on, MSFM_OVERLAP=0 / 1 forces.
-  static const char* overlap_env = getenv("MSFM_OVERLAP");
-  const bool overlap = overlap_env ? atoi(overlap_env) != 0 : ba->fold.on;
+  // pays again (1.251 -> 1.229 ms per iteration at config 3).  So: forked when the fold tables are on.
+  const bool overlap = ba->fold.on;
   // (round 4, later: with the fold tables and one intrinsics block everything between k_point and the assembly is ONE launch on
   //  the main stream - k_sums - and nothing is forked)
-  static const char* fused_env = getenv("MSFM_FUSED_SUMS");
   // (also for the problems too small for the fold tables - the window of a new camera: their full pair lists are three
   //  latency-bound launches of 13-25 us one after the other; a LARGE problem without fold tables keeps the separate launches,
   //  whose pair kernels want more waves per SIMD than this launch has)
-  const bool fused = mode == 0 && ba->n_fchunks > 0 && (ba->fold.on || ba->cc.n_pairs < 262144) && !(fused_env && atoi(fused_env) == 0);
+  const bool fused = mode == 0 && ba->n_fchunks > 0 && (ba->fold.on || ba->cc.n_pairs < 262144) && ba->env.fused_sums;
   const bool forked = mode == 0 && !ctx->profile && overlap && !fused;
   // zero fill of the reduced system in front of the assembly (reads nothing: with the fork it runs on the second stream too)
   auto zero_system = [&](hipStream_t sz) -> int {
@@ -4272,7 +4163,7 @@ static int wait_scalars(msfm_ba* ba) {
   // spin on the sequence number: the wake-up of a blocking wait costs more than the whole hand-over.  Bounded: a wedged kernel,
   // or a peer rank that left the loop so that a collective never completes, must surface as an error code, not as a host thread
   // spinning forever; a launch or execution error surfaces through the stream query that accompanies the clock check.
-  static const double limit_s = [] { const char* e = getenv("MSFM_SYNC_TIMEOUT_S"); const double v = e ? atof(e) : 120.0; return v > 0 ? v : 120.0; }();
+  const double limit_s = msfm_env_process().sync_timeout_s;
   const volatile unsigned long long* flag = reinterpret_cast<const volatile unsigned long long*>(ba->h_scal + H_SEQ);
   unsigned long long spins = 0;
   const auto t0 = std::chrono::steady_clock::now();   // taken once: the deadline never re-arms, whatever the poll count does
@@ -4299,7 +4190,7 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
   if (ba->nred > 0) {
     double* const zcur = ba->zsys.p + (size_t)ba->zflip * (ba->npad + 8);
     double* const znext = ba->zsys.p + (size_t)(ba->zflip ^ 1) * (ba->npad + 8);
-    const int rc = msfm_chol_factor_solve(ctx, ba->M.p, ba->npad, ba->nsys, ba->Linv.p, ba->w.p, zcur, ba->fail.p,
+    const int rc = msfm_chol_factor_solve(ctx, ba->env, ba->M.p, ba->npad, ba->nsys, ba->Linv.p, ba->w.p, zcur, ba->fail.p,
                                           ba->plan.n_levels > 0 ? &ba->plan : nullptr, znext, ba->chol_ws);
     if (rc != MSFM_OK) {
       // the call may have stopped before the solve kernel marked znext: neither half can be trusted to be "pending"
@@ -4336,8 +4227,7 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     }
     const int ngps = (ba->has_gps && lead) ? ncb : 0;
     const int nrest = (ba->A - ba->AE) + ngps;
-    const char* tail_env = getenv("MSFM_FUSED_TAIL");   // (read per call: the tests switch it inside one process)
-    if (!(tail_env && atoi(tail_env) == 0)) {
+    if (ba->env.fused_tail) {
       // model cost change of the remaining rows + cost at the candidate (all rows, GPS rows) in one launch, one reduction for
       // the four sums (the failure bits of the factorisation / finiteness checks are final here)
       t.stop();   // (the class ba_backsub ends here: what follows is timed as ba_cost)
@@ -4400,7 +4290,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
   hipEvent_t& ev0 = evs.a;
   hipEvent_t& ev1 = evs.b;
   const auto run_t0 = std::chrono::steady_clock::now();
-  const bool verbose = getenv("MSFM_VERBOSE") != nullptr && ctx->rank == 0;
+  const bool verbose = msfm_env_process().verbose && ctx->rank == 0;
   auto lap = [&](const char* what) {
     if (verbose) fprintf(stderr, "msfm: run %-31s %7.2f ms\n", what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - run_t0).count());
   };

@@ -23,12 +23,6 @@
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
 
-// cycle-counter probes for scripts/chol_probe.hip (compiled out of the library)
-#ifndef MSFM_PROBE
-#define MSFM_PROBE(i)
-#define MSFM_PROBE_ARM(j0)
-#endif
-
 __device__ __forceinline__ double readlane_f64(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
@@ -55,7 +49,7 @@ __device__ __forceinline__ void quad_abt(const double* X, const double* Y, int w
 // Panel kernel: right-looking, one launch per 64-column panel, the next panel's potrf + trsm folded
 // into the launch with no cross-workgroup dependency (every column-0 workgroup factors the updated
 // diagonal block redundantly, bit-identically), organised around the only thing that bounds the
-// launch: the dependent chain of a column-0 workgroup.  Measured on MI355X (scripts/chol_probe.hip)
+// launch: the dependent chain of a column-0 workgroup.  Measured on MI355X (with cycle stamps, since removed)
 // that chain is ~36 k cycles; a first version with one 64-row tile per workgroup, right-looking
 // potrf16 and the triangular solve after the last pivot took ~65 k.
 //
@@ -351,32 +345,23 @@ __device__ __forceinline__ void panel_col0(double* __restrict__ M, int ld, const
     for (int i = 0; i < 4; i++) D0[i] = M[(size_t)(t0 + lk + 4 * i) * ld + t0 + lr];
     if (upd) p0_store(Bs, tid, pv);
     __syncthreads();
-    MSFM_PROBE(1);
     if (upd) D0 = mm_nt_neg<16>(Bs, 0, Bs, 0, 0, lr, lk, D0);
     tile_st(Ls, 0, 0, lr, lk, D0);
     __syncthreads();
-    MSFM_PROBE(2);
     potrf16_v2<0, FULL>(Ls, dinv, dvec, ncol, lane, fail);
     __syncthreads();
-    MSFM_PROBE(3);
     __syncthreads();  // A1
-    MSFM_PROBE(4);
     if (FULL || 16 < ncol) potrf16_v2<1, FULL>(Ls, dinv, dvec, ncol, lane, fail);
     else potrf16_skip<1>(dinv, lane);   // nothing but padding from here on (last block of the system)
     __syncthreads();
-    MSFM_PROBE(5);
     __syncthreads();  // A2
-    MSFM_PROBE(6);
     if (FULL || 32 < ncol) potrf16_v2<2, FULL>(Ls, dinv, dvec, ncol, lane, fail);
     else potrf16_skip<2>(dinv, lane);   // nothing but padding from here on (last block of the system)
     __syncthreads();
-    MSFM_PROBE(7);
     __syncthreads();  // A3
-    MSFM_PROBE(8);
     if (FULL || 48 < ncol) potrf16_v2<3, FULL>(Ls, dinv, dvec, ncol, lane, fail);
     else potrf16_skip<3>(dinv, lane);   // nothing but padding from here on (last block of the system)
     __syncthreads();
-    MSFM_PROBE(9);
   } else {
     // ================= helper waves: one 16-row tile of the new panel each =================
     d2 pv[8];
@@ -521,7 +506,6 @@ __device__ __forceinline__ void panel_col0(double* __restrict__ M, int ld, const
       }
     }
   }
-  MSFM_PROBE(10);
 }
 
 // grid: for every job its column-0 workgroups, then the 64x64 tiles (I, J), jmin <= J <= I < nt, of the
@@ -539,8 +523,6 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
     if ((int)blockIdx.x >= jobs.job[k].wg0) ji = k;
   const PanelJob& jb = jobs.job[ji];
   const int bl = blockIdx.x - jb.wg0;
-  MSFM_PROBE_ARM(jb.j0);
-  MSFM_PROBE(0);
   if (bl < jb.ncw) {
     panel_col0<FULL>(M, ld, jb, bl, n, Dinv, Ldiag, fail, /*Bs=*/Bs, /*Ls=*/As, /*dinv=*/sm + 80, /*dvec=*/sm);
     return;
@@ -657,24 +639,6 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
 // Every poll is bounded and gives up for the whole launch once MSFM_FAIL_SYNC is set (the host returns MSFM_E_DEVICE).
 // The arithmetic and its order are exactly those of the launch chain: the factor is bit-identical.
 // =======================================================================================
-// cycle stamps of one row-owner workgroup per step (scripts/chol_probe.hip; compiled out of the library)
-#ifdef MSFM_CHAIN_STAMPS
-__device__ long long g_chain_stamp[256][8];
-__device__ int g_chain_stamp_wg = 0;
-__device__ int g_chain_stamp_jobs = 0;        // stamp only launches with this many jobs (0: all)
-__device__ volatile int g_chain_stamp_on = 0;
-__device__ long long g_chain_task_t[8192][4];   // per ticket: taken, counters there, products done / stored, published (wall clock, 10 ns)
-__device__ long long g_chain_row_t[256][2];     // per step of the stamped row owner: step start, pivots done (wall clock)
-#define BSTAMP(tk, i) do { if (threadIdx.x == 0 && g_chain_stamp_on && (tk) >= 0 && (tk) < 8192) g_chain_task_t[tk][i] = (long long)wall_clock64(); } while (0)
-#define RSTAMP(i) do { if (threadIdx.x == 0 && (int)blockIdx.x == g_chain_stamp_wg && l < 256 && g_chain_stamp_on) g_chain_row_t[l][i] = (long long)wall_clock64(); } while (0)
-#define CSTAMP(i) do { if (threadIdx.x == 0 && (int)blockIdx.x == g_chain_stamp_wg && l < 256 && g_chain_stamp_on) g_chain_stamp[l][i] = (long long)__builtin_readcyclecounter(); } while (0)
-#define CSTAMP_H(i) do { if (threadIdx.x == 64 && (int)blockIdx.x == g_chain_stamp_wg && l < 256 && g_chain_stamp_on) g_chain_stamp[l][i] = (long long)__builtin_readcyclecounter(); } while (0)
-#else
-#define BSTAMP(tk, i) do {} while (0)
-#define RSTAMP(i) do {} while (0)
-#define CSTAMP(i) do {} while (0)
-#define CSTAMP_H(i) do {} while (0)
-#endif
 struct ChainJob {
   int begin;            // first column of the node
   int P;                // factor steps = 64-column blocks of the node
@@ -803,7 +767,7 @@ __device__ __forceinline__ double hb_safe(double v) {   // (no arithmetic produc
 // the pivot wave (wave 0) and three helper waves with one 16-row tile of the panel each.  The bodies are panel_col0's; what
 // differs is where the operands come from and go to.
 //
-// One coherent (sc1) round trip costs ~2.5 k cycles on MI355X (measured: scripts/chol_probe), a step's pivot chain 19 k, so
+// One coherent (sc1) round trip costs ~2.5 k cycles on MI355X (measured with cycle stamps), a step's pivot chain 19 k, so
 // a step must not pay more than the one round trip it cannot avoid (L[t, t-1] from its owners):
 //  * the next step's tiles of the diagonal block and of the own rows are fetched DURING the current step, at the start of a
 //    helper phase, once their counters (asked for one phase earlier, tested without waiting) say that the bulk workgroups
@@ -847,14 +811,11 @@ __device__ __forceinline__ void chain_pivot_step(const ChainJob& jb, const Chain
   const bool upd = l > 0;
   const int ncol = min(NB, n - t0);
   const int tb = t0 / NB;
-  CSTAMP(0);
-  RSTAMP(0);
   if (upd) {
     d2 pv[8];
     hb_poll(cH, (size_t)tb, tid, 16 * min(4, jb.nrt - 4 * l), pv, ctl.spin_limit, fail, ctl.dbg, l);
     p0_store(Bs, tid, pv);
   }
-  CSTAMP(2);
   CHAIN_BAR(CB_S1);   // L[t, t-1] and the block's tile (0, 0) are in LDS
   d4 D0;
 #pragma unroll
@@ -862,7 +823,6 @@ __device__ __forceinline__ void chain_pivot_step(const ChainJob& jb, const Chain
   if (upd) D0 = mm_nt_neg<16>(Bs, 0, Bs, 0, 0, lr, lk, D0);
   tile_st(Ls, 0, 0, lr, lk, D0);
   CHAIN_BAR(CB_S2);
-  CSTAMP(3);
   potrf16_v2<0, FULL>(Ls, dinv, dvec, ncol, lane, fail);
   CHAIN_BAR(CB_P0);
   CHAIN_BAR(CB_A1);
@@ -877,8 +837,6 @@ __device__ __forceinline__ void chain_pivot_step(const ChainJob& jb, const Chain
   if (FULL || 48 < ncol) potrf16_v2<3, FULL>(Ls, dinv, dvec, ncol, lane, fail);
   else potrf16_skip<3>(dinv, lane);
   CHAIN_BAR(CB_P3);
-  CSTAMP(4);
-  RSTAMP(1);
 }
 
 // what a helper wave carries from step to step
@@ -984,7 +942,6 @@ __device__ __forceinline__ void chain_helper_step(double* __restrict__ M, coh_bu
 #pragma unroll
     for (int i = 0; i < 4; i++) d00s[4 * lane + i] = D00[i];
   }
-  CSTAMP_H(5);
   CHAIN_BAR(CB_S1);   // S1
 #define MSFM_KC(s) (16 * ((s) >> 2) + 4 * lk + ((s) & 3))
   // ---- column 0 of the updated diagonal block: one 16x16 tile per wave ----
@@ -1077,7 +1034,6 @@ __device__ __forceinline__ void chain_helper_step(double* __restrict__ M, coh_bu
     for (int s = 0; s < 4; s++) Y = __builtin_amdgcn_mfma_f64_16x16x4f64(dinv[(48 + plr) * DV + 4 * lk + s], T[3][s], Y, 0, 0, 0);
     X[3] = Y;
     chain_emit(cM, cH, ld, mrow, to_hb, hrow, 3, Y, lk);   // the last sixteen columns: everybody's next step waits for them
-    CSTAMP_H(6);
 #pragma unroll
     for (int q = 0; q < 4; q++)
 #pragma unroll
@@ -1085,7 +1041,6 @@ __device__ __forceinline__ void chain_helper_step(double* __restrict__ M, coh_bu
     C.flag_step = l + 1;   // released behind the next poll (or on exit)
   }
   fetch_ahead();
-  CSTAMP_H(7);
 #undef MSFM_KC
   if (is_pub) {
     // (publish_subpanel of the last quarter by the helper waves alone: the pivot wave is already on its way to the next step)
@@ -1124,7 +1079,7 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
   const int lr = lane & 15, lk = lane >> 4;
   const int qrow = 32 * wr + lk, qcol = 32 * wc + lr;
   const int total = ctl.n_tasks;
-  int* const tkt = task + 37;   // the tickets of the three slots (stamps only)
+  int* const tkt = task + 37;   // the tickets of the three slots (read by nothing now that the cycle stamps are gone; k_chain is kept as measured)
   const coh_buf cC = coh_make(ctl.corners ? ctl.corners : M, ctl.corners ? (size_t)8 * ctl.ldc * ctl.ldc * sizeof(double) : 8);
   // l < 0: none.  For the products (types 0, 1): rows ri / rj of the panel at column j0; the tile lives at coff in M (type 0) or in
   // the corner pieces (type 1, leading dimension cld; zero: its first panel, nothing to load); the counters it waits for are
@@ -1137,7 +1092,6 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
     int* o = task + 12 * slot;
     o[0] = q.l; o[1] = q.k; o[2] = q.type; o[3] = q.ti; o[4] = q.tj; o[5] = q.I; o[6] = q.J; o[7] = q.piece; o[8] = q.seq; o[9] = q.urgent;
     tkt[slot] = t;
-    BSTAMP(t < total ? t : -1, 0);
   };
   auto decode = [&](int slot, Tile& T) {
     const int* o = task + 12 * slot;
@@ -1263,7 +1217,6 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
   if (nxt.l >= 0 && nxt.type == 2) { mtask = nxt; nxt.l = -1; }
   if (wave == 0) { wait_flags(cur); if (is_product(nxt)) ask(nxt); }
   __syncthreads();
-  BSTAMP(cur.tk, 1);
   fetch(cur);
   for (;;) {
 #pragma unroll
@@ -1292,7 +1245,7 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       pending = nullptr;
     }
     const bool ready = task[36] != 0 && nxt.l >= 0;
-    if (ready) { fetch(nxt); BSTAMP(nxt.tk, 1); }   // in flight under the products below
+    if (ready) fetch(nxt);   // in flight under the products below
     decode(2, nn);
     if (nn.l >= 0 && nn.type == 2) { mtask = nn; nn.l = -1; }   // a merge: no more products for this workgroup
     if (wave == 0 && nn.l >= 0) ask(nn);
@@ -1309,7 +1262,6 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
     const bool last = nxt.l < 0;
     if (cur.urgent || last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next step's row owners wait for this tile
     __syncthreads();   // B2: every wave's part of the tile is issued (urgent: out); everybody is done with As / Bs and task[]
-    BSTAMP(cur.tk, 2);
     if (tid == 0) {
       if (cur.urgent || last) __hip_atomic_store(cur.hist, ctl.base + (unsigned)cur.dval, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       else { pending = cur.hist; pending_l = cur.dval; }
@@ -1325,7 +1277,6 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       }
       if (wave == 0) wait_flags(nxt);
       __syncthreads();
-      BSTAMP(nxt.tk, 1);
       fetch(nxt);
     }
     cur = nxt;
@@ -1360,9 +1311,6 @@ __global__ __launch_bounds__(256) void k_chain(double* __restrict__ M, int ld, i
       if ((int)blockIdx.x >= jobs.job[k].wg0) ji = k;
     const ChainJob& jb = jobs.job[ji];
     const int b = blockIdx.x - jb.wg0;
-#ifdef MSFM_CHAIN_STAMPS
-    if (tid == 0 && (int)blockIdx.x == g_chain_stamp_wg) g_chain_stamp_on = g_chain_stamp_jobs == 0 || jobs.count == g_chain_stamp_jobs;
-#endif
     if (wave == 0) {
       for (int l = 0; chain_alive(jb, b, l); l++) {
         if (n - (jb.begin + NB * l) >= NB) chain_pivot_step<true>(jb, ctl, cH, l, n, fail, Bs, As, sm + 80, sm, d00s, barlog);
@@ -1881,8 +1829,6 @@ struct ChainLaunch {
   int task_off = 0, n_tasks = 0;   // the launch's tiles in ws->tasks
   int steps = 0;        // panel steps on its critical path (for the timers)
   bool usable = false;
-  bool corner_folded = false;   // the level's corner update runs as tasks of the launch
-  int corner_b0 = 0;
 };
 // The deferred corner update of a tree level: per 64-row block of the B square (rows from b0 on) the panels of the level that lie
 // under the block's node, and into how many pieces a tile's panels are cut (k_corner_syrk / the corner tasks of k_chain).
@@ -1920,13 +1866,6 @@ static void corner_plan(const msfm_chol_plan* plan, int lv, int nrows, CornerPla
       }
     if (wgs <= 560 || target >= 64) break;
   }
-  static const int target_env = getenv("MSFM_CORNER_TARGET") ? atoi(getenv("MSFM_CORNER_TARGET")) : 0;
-  if (target_env > 0) {
-    target = target_env; smax = 1;
-    for (int I = 0; I < nB64; I++)
-      for (int J = 0; J <= I; J++)
-        smax = std::max(smax, corner_splits(std::min((int)R.phi[I], (int)R.phi[J]) - std::max((int)R.plo[I], (int)R.plo[J]), target));
-  }
   C.target = target; C.smax = smax;
 }
 
@@ -1962,12 +1901,12 @@ int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out) {
 void msfm_chol_ws_destroy(msfm_chol_ws* w) { delete w; }
 
 // The launches of a plan: one per tree level (its K node chains side by side), then the root chain.
-static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan) {
+static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan, bool force) {
   msfm_ctx* ctx = ws->ctx;
   const int nrows = n + 1, n_levels = plan ? plan->n_levels : 0;
   unsigned long long sig = 1469598103934665603ull;
   auto mix = [&](long v) { sig = (sig ^ (unsigned long long)v) * 1099511628211ull; };
-  mix(n); mix(n_levels);
+  mix(n); mix(n_levels); mix(force);
   for (int lv = 0; lv < n_levels; lv++) {
     mix(plan->level[lv].K); mix(plan->level[lv].b0);
     for (int k = 0; k < plan->level[lv].K; k++) { mix(plan->level[lv].node[k].begin); mix(plan->level[lv].node[k].end); mix(plan->level[lv].node[k].leaf_lo); mix(plan->level[lv].node[k].leaf_hi); }
@@ -2029,7 +1968,6 @@ static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan) {
       // every tile of every launch step, in priority order: key = l + 0.6 (J - 1) (see chain_bulk)
       struct Keyed { int key; ChainTask t; };
       std::vector<Keyed> lt;
-      static const int slope = getenv("MSFM_CHAIN_SLOPE") ? std::max(0, std::min(9, atoi(getenv("MSFM_CHAIN_SLOPE")))) : 6;   // tenths; 0: step by step
       for (int l = 1; l <= J.n_steps; l++) {
         int step_tasks = 0;
         for (int k = 0; k < J.count; k++) {
@@ -2037,69 +1975,14 @@ static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan) {
           const int nA = J.job[k].nA64 - l, nB = J.job[k].nB64;
           for (int Jc = 1; Jc < nA; Jc++)
             for (int I = Jc; I < nA + nB; I++) {
-              lt.push_back(Keyed{10 * l + slope * (Jc - 1), ChainTask{0, (short)k, (short)l, (short)(4 * (I + l)), (short)(4 * (Jc + l)), (short)I, (short)Jc, 0, 0,
+              lt.push_back(Keyed{10 * l + 6 * (Jc - 1), ChainTask{0, (short)k, (short)l, (short)(4 * (I + l)), (short)(4 * (Jc + l)), (short)I, (short)Jc, 0, 0,
                                                                            (short)(Jc == 1 ? 1 : 0), 0, 0}});
               step_tasks++;
             }
         }
         max_step_tasks = std::max(max_step_tasks, step_tasks);
       }
-      // the level's corner update as tasks of the same launch (instead of k_corner_syrk / k_merge_corners behind it):
-      // for every tile of the B square and every piece of its panel list one task per panel, in the panel order of k_corner_syrk
-      // (the pieces' sums are then bit for bit those of the launches); a piece's tasks get non-decreasing keys, so the list stays
-      // a linear extension of the dependencies; the merges come last.
-      // Measured at config 3's tree (scripts/chol_probe 3137 . plan): 0.535 ms folded against 0.456 ms with the two launches - the
-      // 3 140 per-panel corner tasks (each reads and writes its 32 KB piece: k_corner_syrk keeps it in registers over a piece's
-      // panels) more than double the bulk work and sit in front of the next steps' urgent tiles.  So the launches stay the
-      // default; MSFM_CORNER_FOLD=1 takes this path (bit-identical factor, checked by the probe).
-      static const bool corner_launches = getenv("MSFM_CORNER_FOLD") == nullptr;
-      std::vector<Keyed> merges;
-      if (lv < n_levels && !corner_launches && plan->corners && J.count > 0) {
-        CornerPlan CP;
-        corner_plan(plan, lv, nrows, CP);
-        if (CP.nB64 <= MSFM_CORNER_MAX_BLOCKS && CP.nB64 <= 180) {
-          L.corner_folded = true;
-          L.corner_b0 = CP.sb;
-          auto job_of_panel = [&](int p, int& k, int& l) {
-            for (k = 0; k < J.count; k++)
-              if (64 * p >= J.job[k].begin && 64 * p < J.job[k].begin + 64 * J.job[k].P) { l = p - J.job[k].begin / 64; return true; }
-            return false;
-          };
-          auto row_tile = [&](const ChainJob& jb, int row) {   // the job's tile index of a row of range B (-1: not among its rows)
-            int t = 4 * jb.nA64;
-            for (int g = 0; g < jb.nseg; g++) {
-              if (row >= jb.sb0[g] && row < jb.sb0[g] + 16 * jb.sn16[g]) return t + (row - jb.sb0[g]) / 16;
-              t += jb.sn16[g];
-            }
-            return -1;
-          };
-          for (int I = 0; I < CP.nB64 && L.corner_folded; I++)
-            for (int Jc = 0; Jc <= I && L.corner_folded; Jc++) {
-              const int p_begin = std::max((int)CP.R.plo[I], (int)CP.R.plo[Jc]), np = std::min((int)CP.R.phi[I], (int)CP.R.phi[Jc]);
-              const int len = np - p_begin;
-              if (len <= 0) continue;
-              const int ns = corner_splits(len, CP.target);
-              for (int r = 0; r < ns; r++) {
-                int key = 0, seq = 0;
-                for (int pp = p_begin + r; pp < np; pp += ns, seq++) {
-                  int k = 0, l = 0;
-                  if (!job_of_panel(pp, k, l)) { L.corner_folded = false; break; }
-                  const int ti = row_tile(J.job[k], CP.sb + 64 * I), tj = row_tile(J.job[k], CP.sb + 64 * Jc);
-                  if (ti < 0 || tj < 0) { L.corner_folded = false; break; }
-                  key = std::max(key, 10 * (l + 1) + 14);
-                  lt.push_back(Keyed{key, ChainTask{1, (short)k, (short)l, (short)ti, (short)tj, (short)I, (short)Jc, (short)r, (short)seq, 0, 0, 0}});
-                }
-              }
-              merges.push_back(Keyed{0x7fffffff, ChainTask{2, 0, (short)len, 0, 0, (short)I, (short)Jc, (short)ns, 0, 0, 0, 0}});
-            }
-          if (!L.corner_folded) {   // (cannot happen with the trees choose_dissection builds; keep the launches then)
-            lt.erase(std::remove_if(lt.begin(), lt.end(), [](const Keyed& q) { return q.t.type != 0; }), lt.end());
-            merges.clear();
-          }
-        }
-      }
       std::stable_sort(lt.begin(), lt.end(), [](const Keyed& a, const Keyed& b) { return a.key < b.key; });
-      for (const Keyed& q : merges) lt.push_back(q);
       for (const Keyed& q : lt) table.push_back(q.t);
       L.n_tasks = (int)lt.size();
     }
@@ -2108,7 +1991,7 @@ static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan) {
     J.n_bulk_wg = std::max(1, std::min(room, max_step_tasks));
     // usable: every row owner resident with room to spare (other processes may share the device), a bulk workgroup for
     // every three tiles of the busiest step at least
-    static const bool force = getenv("MSFM_CHAIN_FORCE") != nullptr;   // (probes: take the chain whatever the tile count)
+    // (force, MSFM_CHAIN_FORCE: take the chain whatever the tile count)
     // (a device shared with other contexts that launch the same kernel at the same time - ranks are synchronised by the
     //  reduction in front of the factorisation - must hold the row owners of all of them, or none makes progress)
     const int share = std::max(1, ctx->device_share);
@@ -2130,17 +2013,14 @@ static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan) {
   return MSFM_OK;
 }
 
+// polls of a bounded in-kernel wait: a poll is an L2 round trip plus s_sleep, ~0.3 us; the bound is MSFM_SYNC_TIMEOUT_S, as for the
+// host's own spin
 static unsigned chain_spin_limit() {
-  static const unsigned v = [] {
-    const char* e = getenv("MSFM_SYNC_TIMEOUT_S");
-    const double s = e ? atof(e) : 120.0;
-    return (unsigned)std::min(4.0e9, std::max(1.0e4, (s > 0 ? s : 120.0) * 3.0e6));
-  }();
-  return v;
+  return (unsigned)std::min(4.0e9, std::max(1.0e4, msfm_env_process().sync_timeout_s * 3.0e6));
 }
 
-static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int npad, int n, double* Dinv, double* Ldiag, int* fail, double* corners,
-                        int ldc) {
+static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int npad, int n, double* Dinv, double* Ldiag, int* fail,
+                        int ldc, bool trace) {
   msfm_ctx* ctx = ws->ctx;
   ChainCtl c;
   const size_t nt16 = npad / 16, nb = npad / NB;
@@ -2157,12 +2037,12 @@ static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int n
   c.base = (++ws->flag_epoch & 0xFFFFFu) << 12;   // per LAUNCH: the launches of one solve reuse the rowflag slots of their jobs
   c.spin_limit = chain_spin_limit();
   c.nblk = (int)nb;
-  c.corners = L.corner_folded ? corners : nullptr;
+  c.corners = nullptr;   // (the corner update runs as k_corner_syrk / k_merge_corners behind the launch)
   c.cornerflag = ws->flags.p + 8 * nt16 + nb * nb;
-  c.ldc = ldc; c.corner_b0 = L.corner_b0;
+  c.ldc = ldc; c.corner_b0 = 0;
   c.dbg = ws->tickets.p + 8;
 #ifdef MSFM_CHAIN_BARCHECK
-  if (getenv("MSFM_CHAIN_TRACE")) fprintf(stderr, "k_chain: n %d, %d row owners, %d bulk workgroups, %d steps\n", n, L.jobs.n_row_wg, L.jobs.n_bulk_wg, L.steps);
+  if (trace) fprintf(stderr, "k_chain: n %d, %d row owners, %d bulk workgroups, %d steps\n", n, L.jobs.n_row_wg, L.jobs.n_bulk_wg, L.steps);
 #endif
   hipLaunchKernelGGL(k_chain, dim3(L.jobs.n_row_wg + L.jobs.n_bulk_wg), dim3(256), 0, ctx->stream, M, npad, n, Dinv, Ldiag, fail, L.jobs, c);
   return MSFM_OK;
@@ -2172,7 +2052,7 @@ static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int n
 // MSFM_Z_PENDING everywhere (msfm_chol_fill_pending once, afterwards the previous call's z_next) and gets z_next back in that
 // state - the two buffers alternate from solve to solve and no fill launch sits on the critical path.  Without it the
 // function fills z itself first.
-int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
+int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
                            const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws) {
   if (!M || !work || !w || !z || !fail || npad % NB != 0 || n < 1 || n + 1 > npad)
     return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad workspace (null buffer or size)");
@@ -2185,10 +2065,9 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
   const int n_levels = plan ? plan->n_levels : 0;
   // the persistent chain (one launch per tree level) when the caller keeps a workspace for it; MSFM_CHOL_LAUNCHES=1: the
   // round-3 chain of one launch per 64-column panel, for comparison
-  const bool chol_launches_env = getenv("MSFM_CHOL_LAUNCHES") != nullptr;   // (read per call: the tests switch it between solves)
-  bool use_chain = ws && !chol_launches_env && ws->npad == npad && ws->capacity > 0 && (size_t)npad * npad * sizeof(double) < 0xFFFFFFFFull;   // (32-bit buffer offsets)
+  bool use_chain = ws && !env.chol_launches && ws->npad == npad && ws->capacity > 0 && (size_t)npad * npad * sizeof(double) < 0xFFFFFFFFull;   // (32-bit buffer offsets)
   if (use_chain) {
-    MSFM_TRY(chain_build(ws, n, plan));
+    MSFM_TRY(chain_build(ws, n, plan, env.chain_force));
     if ((int)ws->launch.size() != n_levels + 1) use_chain = false;
   }
   if (use_chain) {
@@ -2237,7 +2116,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
       chain_timer.count = 0;
       const bool lv_chain = use_chain && ws->launch[lv].usable;
       if (lv_chain) {
-        MSFM_TRY(chain_launch(ws, ws->launch[lv], M, npad, n, Dinv, Ldiag, fail, plan->corners, ldc));
+        MSFM_TRY(chain_launch(ws, ws->launch[lv], M, npad, n, Dinv, Ldiag, fail, ldc, env.chain_trace));
         chain_timer.count = ws->launch[lv].steps;   // (counted in panel steps, so that a step's time compares with the launch chain's)
       }
       for (int l = 0; l < maxp && !lv_chain; l++) {
@@ -2268,7 +2147,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
         chain_timer.count++;
       }
       chain_timer.stop();
-      if (maxp > 0 && !(lv_chain && ws->launch[lv].corner_folded)) {
+      if (maxp > 0) {
         KTimer t(ctx, "chol_corner_syrk");
         t.count = 2;
         const int nB64 = cdiv(nrows - sb, 64), ntile = nB64 * (nB64 + 1) / 2;
@@ -2288,7 +2167,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
   root_timer.count = 0;
   const bool root_chain = use_chain && ws->launch[n_levels].usable;
   if (root_chain) {
-    MSFM_TRY(chain_launch(ws, ws->launch[n_levels], M, npad, n, Dinv, Ldiag, fail, nullptr, 0));
+    MSFM_TRY(chain_launch(ws, ws->launch[n_levels], M, npad, n, Dinv, Ldiag, fail, 0, env.chain_trace));
     root_timer.count = ws->launch[n_levels].steps;
   }
   for (int t0 = t_first; t0 < n && !root_chain; t0 += NB) {
@@ -2309,7 +2188,6 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
   {
     KTimer t(ctx, "chol_backsolve");
     const int nblk = cdiv(n, NB);
-    static const bool launches_env = getenv("MSFM_BACKSOLVE_LAUNCHES") != nullptr;   // the round-2 chain of launches, for comparison
     // per device: min(MSFM_BACKSOLVE_CHAIN_MAX, resident workgroups of k_backsolve_chain), 0 = not asked yet (atomic: the
     // per-rank host threads of msfm_multi come through here at the same time; both would store the same value)
     static std::atomic<int> chain_max[64];
@@ -2318,7 +2196,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
       cmax = std::max(1, std::min(MSFM_BACKSOLVE_CHAIN_MAX, resident_workgroups(ctx, k_backsolve_chain, 256)));
       chain_max[ctx->device & 63].store(cmax, std::memory_order_relaxed);
     }
-    const bool chain = !launches_env && nblk <= cmax;
+    const bool chain = nblk <= cmax;   // (otherwise the round-2 chain of launches)
     if (!chain) hipLaunchKernelGGL(k_trinv64_full, dim3(nblk + cdiv(npad, 256)), dim3(256), 0, s, Ldiag, n, Dinv, Linv, nblk, M, npad, w, npad,
                                    (unsigned long long*)nullptr);
     if (chain) {
@@ -2335,14 +2213,8 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* wo
           bt.level[lv].node[k].leaf_lo = nd.leaf_lo; bt.level[lv].node[k].leaf_hi = nd.leaf_hi;
         }
       }
-      // a poll is an L2 round trip plus s_sleep: ~0.3 us; the bound is MSFM_SYNC_TIMEOUT_S (default 120 s, as for the host's own spin)
-      static const unsigned spin_limit = [] {
-        const char* e = getenv("MSFM_SYNC_TIMEOUT_S");
-        const double v = e ? atof(e) : 120.0;
-        return (unsigned)std::min(4.0e9, std::max(1.0e4, (v > 0 ? v : 120.0) * 3.0e6));
-      }();
       hipLaunchKernelGGL(k_backsolve_chain, dim3(nblk), dim3(256), 0, s, M, npad, n, nblk, bt, Ldiag, Dinv, z,
-                         reinterpret_cast<unsigned long long*>(z_next), fail, spin_limit);
+                         reinterpret_cast<unsigned long long*>(z_next), fail, chain_spin_limit());
     } else if (z_next) {
       MSFM_TRY(msfm_chol_fill_pending(ctx, z_next, npad));   // keep the caller's alternation intact on the launch-chain path
     }

@@ -17,6 +17,37 @@
 
 #define MSFM_API extern "C" __attribute__((visibility("default")))
 
+// Every environment switch of the library, with its default (INTEGRATION.md says what each does).  msfm_env_read() in
+// ctx.hip is the only reader of the environment:
+//  - the bundle-adjustment and factorisation switches are copied into a problem at msfm_ba_create (msfm_ba::env) and read
+//    from there by msfm_ba_run and the factorisation it calls: set them before creating the problem;
+//  - the process-wide settings are read once, at first use (msfm_env_process());
+//  - MSFM_MULTI_FAIL_RANK is read at the entry of msfm_multi_ba_solve, before the rank threads start.
+struct msfm_env {
+  int chol_domains = -1;          // MSFM_CHOL_DOMAINS: -1 automatic, 0 dense order, 1..3 that bisection depth
+  bool chol_launches = false;     // MSFM_CHOL_LAUNCHES (set): one launch per 64-column panel instead of the persistent chain
+  bool chain_force = false;       // MSFM_CHAIN_FORCE (set): the persistent chain whatever the tile count
+  bool chain_trace = false;       // MSFM_CHAIN_TRACE (set): the shape of every k_chain launch to stderr (MSFM_CHAIN_BARCHECK build)
+  bool create_host = false;       // MSFM_CREATE_HOST=1: msfm_ba_create builds its index structures on the host
+  long fold_min = 262144;         // MSFM_FOLD_MIN: camera pairs below which a problem keeps the gather path
+  bool no_fold = false;           // MSFM_NO_FOLD (set): the gather path whatever the size
+  bool fused_sums = true;         // MSFM_FUSED_SUMS=0: per-camera sums, pair-list residue and zero fill as separate launches
+  bool fused_tail = true;         // MSFM_FUSED_TAIL=0: the launches behind the back substitution one by one
+  bool keep_t = false;            // MSFM_KEEP_T=1: folding workgroups store their T records too
+  bool tu_direct = true;          // MSFM_TU_DIRECT=0: T.u through the lane exchange
+  bool spec = true;               // MSFM_SPEC=0: the next linearisation enqueued only after the step's read-back
+  // process-wide
+  size_t pool_bytes = (size_t)16384 << 20;   // MSFM_POOL_MB: freed device blocks the cache keeps
+  bool pool_debug = false;        // MSFM_POOL_DEBUG (set): a free that disagrees with the pool's record aborts
+  int host_threads = 0;           // MSFM_HOST_THREADS (1..64; default min(hardware threads, 8))
+  double sync_timeout_s = 120.0;  // MSFM_SYNC_TIMEOUT_S: bound of every host and device wait on a stream or a peer
+  int device_share = 1;           // MSFM_DEVICE_SHARE: processes that use this device at the same time
+  bool verbose = false;           // MSFM_VERBOSE (set): set-up and solve timings to stderr
+  int multi_fail_rank = -1;       // MSFM_MULTI_FAIL_RANK (test hook): this rank of msfm_multi_ba_solve fails before it joins
+};
+msfm_env msfm_env_read();              // the environment as it is now
+const msfm_env& msfm_env_process();    // its first reading, kept for the life of the process
+
 struct msfm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -143,14 +174,7 @@ static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 // Host-side helper: the index structures of a 10^6-observation problem (msfm_ba_create) and the per-pair iteration tables
 // of the RANSAC (geo.hip) are built by a few threads (MSFM_HOST_THREADS, default min(hardware threads, 8));
 // fn(t, begin, end) gets one contiguous range per thread.
-static inline int host_threads() {
-  static const int n = [] {
-    const char* e = getenv("MSFM_HOST_THREADS");
-    const int v = e ? atoi(e) : std::min(8, (int)std::thread::hardware_concurrency());
-    return std::max(1, std::min(v, 64));
-  }();
-  return n;
-}
+static inline int host_threads() { return msfm_env_process().host_threads; }
 template <class F>
 static inline void par_ranges(size_t n, int nt, F&& fn, size_t grain = 4096) {   // at least `grain` items per thread
   nt = (int)std::max<size_t>(1, std::min<size_t>(nt, n / grain + 1));
@@ -224,6 +248,7 @@ struct msfm_chol_plan {
 struct msfm_chol_ws;   // hand-off state of the persistent panel chain (chol.hip): flags, hand-off buffers, ticket counters
 int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out);
 void msfm_chol_ws_destroy(msfm_chol_ws* ws);
-int msfm_chol_factor_solve(msfm_ctx* ctx, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
+// env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE)
+int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
                            const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr);
 int msfm_chol_fill_pending(msfm_ctx* ctx, double* z, int npad);   // "not solved yet" marks of k_backsolve_chain

@@ -11,6 +11,37 @@ int msfm_set_error(msfm_ctx* ctx, int code, const char* fmt, ...) {
   return code;
 }
 
+msfm_env msfm_env_read() {
+  msfm_env E;
+  auto get = [](const char* name) { return getenv(name); };   // (the library's one read of the environment)
+  auto num = [&](const char* name, int unset) { const char* e = get(name); return e ? atoi(e) : unset; };
+  E.chol_domains = num("MSFM_CHOL_DOMAINS", E.chol_domains);
+  E.chol_launches = get("MSFM_CHOL_LAUNCHES") != nullptr;
+  E.chain_force = get("MSFM_CHAIN_FORCE") != nullptr;
+  E.chain_trace = get("MSFM_CHAIN_TRACE") != nullptr;
+  E.create_host = num("MSFM_CREATE_HOST", 0) != 0;
+  if (const char* e = get("MSFM_FOLD_MIN")) E.fold_min = atol(e);
+  E.no_fold = get("MSFM_NO_FOLD") != nullptr;
+  E.fused_sums = num("MSFM_FUSED_SUMS", 1) != 0;
+  E.fused_tail = num("MSFM_FUSED_TAIL", 1) != 0;
+  E.keep_t = num("MSFM_KEEP_T", 0) != 0;
+  E.tu_direct = num("MSFM_TU_DIRECT", 1) != 0;
+  E.spec = num("MSFM_SPEC", 1) != 0;
+  if (const char* e = get("MSFM_POOL_MB")) E.pool_bytes = (size_t)atol(e) << 20;
+  E.pool_debug = get("MSFM_POOL_DEBUG") != nullptr;
+  E.host_threads = std::max(1, std::min(num("MSFM_HOST_THREADS", std::min(8, (int)std::thread::hardware_concurrency())), 64));
+  if (const char* e = get("MSFM_SYNC_TIMEOUT_S")) E.sync_timeout_s = atof(e) > 0 ? atof(e) : 120.0;
+  E.device_share = std::max(1, num("MSFM_DEVICE_SHARE", 1));
+  E.verbose = get("MSFM_VERBOSE") != nullptr;
+  E.multi_fail_rank = num("MSFM_MULTI_FAIL_RANK", -1);
+  return E;
+}
+
+const msfm_env& msfm_env_process() {
+  static const msfm_env E = msfm_env_read();   // (thread-safe initialisation: the rank threads of msfm_multi may get here first)
+  return E;
+}
+
 MSFM_API int msfm_version(void) { return MSFM_VERSION; }
 
 MSFM_API int msfm_ctx_create(int device, msfm_ctx** out) {
@@ -28,10 +59,7 @@ MSFM_API int msfm_ctx_create(int device, msfm_ctx** out) {
     return MSFM_E_DEVICE;
   }
   ctx->device = device;
-  {
-    const char* e = getenv("MSFM_DEVICE_SHARE");   // several processes on this device (the multi-rank tests on a one-GPU box)
-    ctx->device_share = e ? std::max(1, atoi(e)) : 1;
-  }
+  ctx->device_share = msfm_env_process().device_share;   // several processes on this device (the multi-rank tests on a one-GPU box)
   *out = ctx;
   return MSFM_OK;
 }
@@ -52,14 +80,8 @@ struct Pool {
   std::multimap<std::pair<int, size_t>, void*> free_blocks;  // (device, capacity) -> block
   size_t cached_bytes = 0;
   size_t mismatches = 0;
-  size_t limit() {
-    static const size_t v = [] { const char* e = getenv("MSFM_POOL_MB"); return (size_t)(e ? atol(e) : 16384) << 20; }();
-    return v;
-  }
-  bool debug() {
-    static const bool v = getenv("MSFM_POOL_DEBUG") != nullptr;
-    return v;
-  }
+  size_t limit() { return msfm_env_process().pool_bytes; }
+  bool debug() { return msfm_env_process().pool_debug; }
 };
 Pool& pool() { static Pool* p = new Pool(); return *p; }  // intentionally never destroyed (no hipFree at process exit)
 size_t round_capacity(size_t bytes) {
@@ -161,7 +183,7 @@ MSFM_API void msfm_ctx_destroy(msfm_ctx* ctx) {
   if (ctx->children > 0) {
     // descriptor sets, match results and resident problems hold ctx->stream: destroying the context under them would
     // leave their destroy functions with a dangling pointer.  Keep the context (a leak, reported) instead.
-    if (getenv("MSFM_VERBOSE")) fprintf(stderr, "msfm_ctx_destroy: %d object(s) created from this context are still alive; context kept until they go\n", ctx->children);
+    if (msfm_env_process().verbose) fprintf(stderr, "msfm_ctx_destroy: %d object(s) created from this context are still alive; context kept until they go\n", ctx->children);
     ctx->orphaned = true;
     return;
   }
@@ -298,7 +320,7 @@ void msfm_ctx_forget_rccl(msfm_ctx* ctx) {
 }
 
 int msfm_stream_wait_bounded(msfm_ctx* ctx, hipStream_t s, const char* what) {
-  static const double limit_s = [] { const char* e = getenv("MSFM_SYNC_TIMEOUT_S"); const double v = e ? atof(e) : 120.0; return v > 0 ? v : 120.0; }();
+  const double limit_s = msfm_env_process().sync_timeout_s;
   const auto t0 = std::chrono::steady_clock::now();
   unsigned long polls = 0;
   for (;;) {

@@ -10,8 +10,7 @@
 //   = 4 waves = 256 query descriptors of one image pair; each wave keeps its 64 queries as MFMA B fragments in
 //   registers for the whole sweep, train descriptors stream through a double-buffered XOR-swizzled LDS tile shared
 //   by the 4 waves; the running top-2 per query lives in packed keys (m << 9 | parity << 8 | row), 3 VALU operations
-//   per candidate (lshl_or, min, med3).  MSFM_KNN_BF16=1 selects the older bf16 kernel (128 queries per workgroup,
-//   fp32 accumulators, 4 VALU operations per candidate) for comparison.
+//   per candidate (lshl_or, min, med3).
 // General path (any float32 descriptors): one f16 MFMA product per term with a rigorous error bound, the four
 //   smallest approximate distances per half-wave lane, exact binary64 re-evaluation of the plausible candidates and a
 //   certificate that nothing outside the lists can win; the rare uncertified query is redone by exact brute force.
@@ -26,14 +25,11 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32;
 
 #define DIM 128
 #define TT 64          // train rows per LDS tile
-#define WIN 256        // rows per packed-key window
 #define QPB 256        // queries per workgroup (4 waves x 64)
-#define NORM_BIAS 8388608.0f  // 2^23: keeps a2 - 2ab positive for the integer key
 
 struct msfm_match_result;
 static void orphan_result(msfm_match_result* R);
@@ -44,8 +40,6 @@ struct msfm_descset {
   std::vector<DevBuf<float>*> kp;            // [count][2] keypoint positions (msfm_descset_upload_keypoints), nullptr: none
   std::vector<int> count;
   std::vector<DevBuf<float>*> f32;       // [count][dim]
-  std::vector<DevBuf<unsigned short>*> bf16;  // [count][dim], train copy (plain) — query copy is scaled by -2 on load
-  std::vector<DevBuf<float>*> norm;      // [count]  |a|^2
   // int8 forms for the i8 MFMA kernel: train rows a-128, query rows 127-b, and the per-row terms of
   //   |a-b|^2 = 2 sum (a-128)(127-b) + sum (a-127)^2 + sum (128-b)^2 - 128
   std::vector<DevBuf<signed char>*> ti8, qi8;   // [count][128]
@@ -68,24 +62,18 @@ struct msfm_descset {
   unsigned long kp_generation = 0;
 };
 
-// ---- prep: f32 -> bf16, squared norms, integrality flag -------------------------------
-__global__ __launch_bounds__(256) void k_desc_prep(const float* __restrict__ d, int count, unsigned short* __restrict__ out,
-                                                    float* __restrict__ norm, int* __restrict__ nonint, unsigned* __restrict__ vmax) {
+// ---- prep: integrality flag, largest |value| -----------------------------------------------
+__global__ __launch_bounds__(256) void k_desc_prep(const float* __restrict__ d, int count, int* __restrict__ nonint, unsigned* __restrict__ vmax) {
   // one wave per row, lane handles 2 of the 128 values
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= count) return;
   const float2 v = reinterpret_cast<const float2*>(d + (size_t)row * DIM)[lane];
   const bool bad = !(v.x >= 0.f && v.x <= 255.f && v.x == truncf(v.x) && v.y >= 0.f && v.y <= 255.f && v.y == truncf(v.y));
   if (bad) atomicOr(nonint, 1);
-  ushort2 o;
-  o.x = (unsigned short)(__float_as_uint(v.x) >> 16);  // exact for integers <= 255 (low mantissa bits are zero)
-  o.y = (unsigned short)(__float_as_uint(v.y) >> 16);
-  reinterpret_cast<ushort2*>(out + (size_t)row * DIM)[lane] = o;
-  float s = v.x * v.x + v.y * v.y;
   float m = fmaxf(fabsf(v.x), fabsf(v.y));
 #pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off, 64); m = fmaxf(m, __shfl_xor(m, off, 64)); }
-  if (lane == 0) { norm[row] = s; atomicMax(vmax, __float_as_uint(m)); }
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  if (lane == 0) atomicMax(vmax, __float_as_uint(m));
 }
 
 // int8 operands + the per-row integer terms (see msfm_descset).  One wave per row.
@@ -108,16 +96,7 @@ __global__ __launch_bounds__(256) void k_desc_prep_i8(const float* __restrict__ 
   if (lane == 0) { tcin[row] = (alpha >> 1) + (1 << 21); tpar[row] = alpha & 1; qbeta[row] = beta - 128; }
 }
 
-// ---- fast path --------------------------------------------------------------------------
-struct PairTask {
-  const unsigned short* train;  // bf16 [n_train][128]
-  const unsigned short* query;
-  const float* tnorm;
-  const float* qnorm;
-  int n_train, n_query;
-  int out_off;                  // offset of this pair's queries in the flat outputs
-};
-
+// ---- int8 fast path ---------------------------------------------------------------------------
 __device__ __forceinline__ u32 umed3(u32 a, u32 b, u32 c) {
   u32 r;
   asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
@@ -157,153 +136,10 @@ __device__ __forceinline__ void top2_insert(u32& d0, int& i0, u32& d1, int& i1, 
   i1 = ni1;
 }
 
-// merge a window's two packed keys into the lane's running (distance, row) top-2
-__device__ __forceinline__ void flush_window(u32& k0, u32& k1, u32& D0, int& I0, u32& D1, int& I1, int base) {
-  if (k0 != 0xffffffffu) top2_insert(D0, I0, D1, I1, k0 >> 8, base + (int)(k0 & 255u));
-  if (k1 != 0xffffffffu) top2_insert(D0, I0, D1, I1, k1 >> 8, base + (int)(k1 & 255u));
-  k0 = k1 = 0xffffffffu;
-}
-
-__device__ __forceinline__ void load_query_frags(const unsigned short* qp, int h, bf16x8* bq) {
-#pragma unroll
-  for (int ks = 0; ks < 8; ks++) {
-    const uint4 raw = *reinterpret_cast<const uint4*>(qp + ks * 16 + h * 8);
-    u32 w[4] = {raw.x, raw.y, raw.z, raw.w};
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      // each 16-bit half: bf16 v -> -2v (exponent + 1, sign set); v == 0 stays +0
-      u32 lo16 = w[j] & 0xffffu, hi16 = w[j] >> 16;
-      lo16 = lo16 ? ((lo16 + 0x0080u) | 0x8000u) : 0u;
-      hi16 = hi16 ? ((hi16 + 0x0080u) | 0x8000u) : 0u;
-      w[j] = lo16 | (hi16 << 16);
-    }
-    bq[ks] = __builtin_bit_cast(bf16x8, make_uint4(w[0], w[1], w[2], w[3]));
-  }
-}
-
-// 1 workgroup = 4 waves = 256 queries of one pair; each wave keeps 2 x 32 queries as B fragments
-// (every A fragment read from LDS feeds two MFMAs).  Train tiles of 64 rows are double-buffered:
-// the global loads of tile t+1 are issued before the MFMAs of tile t and written to the other LDS
-// buffer afterwards, one barrier per tile.
-__global__ __launch_bounds__(256, 2) void k_knn2_bf16(const PairTask* __restrict__ tasks, const int* __restrict__ tile_first, int n_pairs,
-                                                       float ratio_good, float ratio_all, int32_t* __restrict__ code,
-                                                       int* __restrict__ ids, float* __restrict__ sqd, int* __restrict__ n_all,
-                                                       int* __restrict__ n_good) {
-  __shared__ __attribute__((aligned(16))) unsigned char lds_a[2][TT * 256];
-  __shared__ __attribute__((aligned(16))) float lds_n[2][TT];
-  int lo = 0, hi = n_pairs - 1;
-  const int bid = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tile_first[mid] <= bid) lo = mid; else hi = mid - 1;
-  }
-  const int pair = lo;
-  const PairTask T = tasks[pair];
-  const int q0 = (bid - tile_first[pair]) * QPB;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int r = lane & 31, h = lane >> 5;
-  const int qa = q0 + wave * 64 + r, qb = qa + 32;
-  const bool va = qa < T.n_query, vb = qb < T.n_query;
-  bf16x8 bqa[8], bqb[8];
-  load_query_frags(T.query + (size_t)(va ? qa : 0) * DIM, h, bqa);
-  load_query_frags(T.query + (size_t)(vb ? qb : 0) * DIM, h, bqb);
-  u32 aD0 = 0xffffffffu, aD1 = 0xffffffffu, bD0 = 0xffffffffu, bD1 = 0xffffffffu;
-  int aI0 = 0x7fffffff, aI1 = 0x7fffffff, bI0 = 0x7fffffff, bI1 = 0x7fffffff;
-  u32 ak0 = 0xffffffffu, ak1 = 0xffffffffu, bk0 = 0xffffffffu, bk1 = 0xffffffffu;
-  const int n_tiles = (T.n_train + TT - 1) / TT;
-  // staging assignment: thread -> 4 chunks of 16 B (row = c >> 4, chunk = c & 15), XOR-swizzled per row
-  uint4 stage[4];
-  float stage_n = 0.f;
-  auto fetch = [&](int tile) {
-    const int t0 = tile * TT;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int c = tid + 256 * i, row = c >> 4, ch = c & 15;
-      stage[i] = make_uint4(0, 0, 0, 0);
-      if (t0 + row < T.n_train) stage[i] = *reinterpret_cast<const uint4*>(T.train + (size_t)(t0 + row) * DIM + ch * 8);
-    }
-    if (tid < TT) stage_n = (t0 + tid < T.n_train) ? T.tnorm[t0 + tid] + NORM_BIAS : 16777215.0f;  // padding rows lose every comparison
-  };
-  auto commit = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const int c = tid + 256 * i, row = c >> 4, ch = c & 15;
-      *reinterpret_cast<uint4*>(&lds_a[buf][row * 256 + ((ch ^ (row & 15)) << 4)]) = stage[i];
-    }
-    if (tid < TT) lds_n[buf][tid] = stage_n;
-  };
-  fetch(0);
-  commit(0);
-  __syncthreads();
-  int cur = 0;
-  for (int tile = 0; tile < n_tiles; tile++) {
-    if (tile + 1 < n_tiles) fetch(tile + 1);
-    const unsigned char* la = lds_a[cur];
-    const float* ln = lds_n[cur];
-#pragma unroll
-    for (int st = 0; st < 2; st++) {
-      f32x16 acca, accb;
-#pragma unroll
-      for (int g = 0; g < 4; g++) {
-        const f32x4 nv = *reinterpret_cast<const f32x4*>(&ln[st * 32 + 8 * g + 4 * h]);
-        acca[4 * g + 0] = nv.x; acca[4 * g + 1] = nv.y; acca[4 * g + 2] = nv.z; acca[4 * g + 3] = nv.w;
-      }
-      accb = acca;
-      const int row = st * 32 + r;
-#pragma unroll
-      for (int ks = 0; ks < 8; ks++) {
-        const int ch = 2 * ks + h;
-        const bf16x8 a = *reinterpret_cast<const bf16x8*>(la + row * 256 + ((ch ^ (row & 15)) << 4));
-        acca = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bqa[ks], acca, 0, 0, 0);
-        accb = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, bqb[ks], accb, 0, 0, 0);
-      }
-      const int wbase = ((tile & 3) * 2 + st) * 32;
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const u32 idx = (u32)(wbase + (reg & 3) + 8 * (reg >> 2));
-        const u32 keya = ((u32)acca[reg] << 8) | idx;  // v_cvt_u32_f32 of an exact integer < 2^24
-        const u32 keyb = ((u32)accb[reg] << 8) | idx;
-        const u32 na0 = min(ak0, keya);
-        ak1 = umed3(ak0, ak1, keya);
-        ak0 = na0;
-        const u32 nb0 = min(bk0, keyb);
-        bk1 = umed3(bk0, bk1, keyb);
-        bk0 = nb0;
-      }
-    }
-    if ((tile & 3) == 3 || tile == n_tiles - 1) {
-      const int base = (tile & ~3) * TT + 4 * h;
-      flush_window(ak0, ak1, aD0, aI0, aD1, aI1, base);
-      flush_window(bk0, bk1, bD0, bI0, bD1, bI1, base);
-    }
-    if (tile + 1 < n_tiles) commit(cur ^ 1);
-    __syncthreads();
-    cur ^= 1;
-  }
-#pragma unroll
-  for (int s = 0; s < 2; s++) {
-    u32 D0 = s ? bD0 : aD0, D1 = s ? bD1 : aD1;
-    int I0 = s ? bI0 : aI0, I1 = s ? bI1 : aI1;
-    const int q = s ? qb : qa;
-    const bool qvalid = s ? vb : va;
-    // merge the two lane halves (rows 4h+..) of each query
-    const u32 pd0 = __shfl_xor(D0, 32, 64), pd1 = __shfl_xor(D1, 32, 64);
-    const int pi0 = __shfl_xor(I0, 32, 64), pi1 = __shfl_xor(I1, 32, 64);
-    top2_insert(D0, I0, D1, I1, pd0, pi0);
-    top2_insert(D0, I0, D1, I1, pd1, pi1);
-    if (h == 0 && qvalid) {
-      const int b2 = (int)T.qnorm[q];
-      const float d0 = (float)((int)D0 - 8388608 + b2), d1 = (float)((int)D1 - 8388608 + b2);
-      const size_t o = (size_t)T.out_off + q;
-      if (ids) { ids[2 * o] = I0; ids[2 * o + 1] = I1; sqd[2 * o] = d0; sqd[2 * o + 1] = d1; }
-      if (code) code[o] = ratio_code(d0, d1, I0, ratio_good, ratio_all, &n_all[pair], &n_good[pair]);
-    }
-  }
-}
-
-// ---- int8 fast path ---------------------------------------------------------------------------
-// Same structure as k_knn2_bf16 on v_mfma_i32_32x32x32_i8 (twice the bf16 MFMA rate, K = 32 per
-// instruction, exact int32 accumulation).  With A = a-128 and B' = 127-b (both fit int8),
+// 1 workgroup = 4 waves = 256 queries of one pair; each wave keeps 2 x 32 queries as B fragments of
+// v_mfma_i32_32x32x32_i8 (every A fragment read from LDS feeds two MFMAs; K = 32 per instruction, exact int32
+// accumulation).  Train tiles of 64 rows are double-buffered: the loads of tile t+1 are issued before the MFMAs
+// of tile t, one barrier per tile.  With A = a-128 and B' = 127-b (both fit int8),
 //   |a-b|^2 = 2 A.B' + alpha(a) + beta(b),  alpha = sum (a-127)^2,  beta = sum (128-b)^2 - 128,
 // the accumulator is started at (alpha >> 1) + 2^21 so m = A.B' + (alpha>>1) + 2^21 >= 0 and
 // 2 m + (alpha & 1) orders the candidates of one query exactly like the distance.  The per-row word
@@ -311,14 +147,8 @@ __global__ __launch_bounds__(256, 2) void k_knn2_bf16(const PairTask* __restrict
 // v_lshl_or_b32 (key = m << 9 | c), v_min_u32, v_med3_u32.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x16 __attribute__((ext_vector_type(16)));
+constexpr int KNN_GROUP = 4;   // register slots whose compares are taken together (the selection loop of k_knn2_i8)
 
-#ifdef MSFM_KNN_HITSTATS
-__device__ unsigned long long g_knn_hits[8][8];   // [train tile / 8][slots of a group of four with a candidate under the threshold]
-extern "C" __attribute__((visibility("default"))) int msfm_dbg_knn_hits(unsigned long long* out, int reset) {
-  if (reset) { static unsigned long long z[64]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_knn_hits), z, sizeof z); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_knn_hits), 64 * sizeof(unsigned long long));
-}
-#endif
 struct PairTask8 {
   const signed char* train;  // [n_train][128]  a - 128
   const signed char* query;  // [n_query][128]  127 - b
@@ -414,18 +244,13 @@ __global__ __launch_bounds__(256, 4) void k_knn2_i8(const PairTask8* __restrict_
     const unsigned char* la = lds_a[cur];
 #pragma unroll
     for (int st = 0; st < 2; st++) {
-      i32x16 acca, accb;
-#if defined(MSFM_KNN_NOFILTER) || !defined(MSFM_KNN_CC_LDS)
-      i32x16 cc;
-#endif
+      i32x16 acca, accb, cc;
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         const i32x4 nv = *reinterpret_cast<const i32x4*>(&lds_cin[cur][st * 32 + 8 * g + 4 * h]);
         acca[4 * g + 0] = nv.x; acca[4 * g + 1] = nv.y; acca[4 * g + 2] = nv.z; acca[4 * g + 3] = nv.w;
-#if defined(MSFM_KNN_NOFILTER) || !defined(MSFM_KNN_CC_LDS)
         const i32x4 cv = *reinterpret_cast<const i32x4*>(&lds_c[cur][st * 32 + 8 * g + 4 * h]);
         cc[4 * g + 0] = cv.x; cc[4 * g + 1] = cv.y; cc[4 * g + 2] = cv.z; cc[4 * g + 3] = cv.w;
-#endif
       }
       accb = acca;
       const int row = st * 32 + r;
@@ -441,78 +266,24 @@ __global__ __launch_bounds__(256, 4) void k_knn2_i8(const PairTask8* __restrict_
       // not formed at all.  The thresholds are taken once per 32-row step (a stale threshold is only larger: conservative);
       // the three selection operations run for a register slot only when some lane of the wave has a candidate under its
       // threshold in one of the two query sets - late in the sweep that is one slot in five (a row enters a lane's top two
-      // with probability 2 / (rows seen + 1)).  MSFM_KNN_NOFILTER (compile time) keeps the unconditional form.
-#ifndef MSFM_KNN_NOFILTER
-#ifndef MSFM_KNN_GROUP
-#define MSFM_KNN_GROUP 4
-#endif
-#ifndef MSFM_KNN_NOSHARE
+      // with probability 2 / (rows seen + 1)).
       // (aTl / bTl: the second smallest m over the lists of BOTH lanes that hold this query - see the flush below)
-      u32 thra = min(ak1 >> 9, aTl), thrb = min(bk1 >> 9, bTl);
-#else
-      u32 thra = min(ak1 >> 9, aD1 >> 1), thrb = min(bk1 >> 9, bD1 >> 1);
-#endif
+      const u32 thra = min(ak1 >> 9, aTl), thrb = min(bk1 >> 9, bTl);
       // all the compares of a group of register slots first (their results are wave masks in scalar registers - no compare ->
       // branch latency per slot), then the selection for the slots whose mask is not empty.  The key formation is volatile
       // assembly so that it stays inside the conditional block (the compiler would otherwise hoist it in front of the tests).
-#ifdef MSFM_KNN_SPLIT_SETS
-      // (variant: one test per query set and slot - half the candidates per test, twice the tests)
 #pragma unroll
-      for (int g = 0; g < 16 / MSFM_KNN_GROUP; g++) {
-        unsigned long long ha[MSFM_KNN_GROUP], hb[MSFM_KNN_GROUP];
+      for (int g = 0; g < 16 / KNN_GROUP; g++) {
+        unsigned long long hm[KNN_GROUP];
 #pragma unroll
-        for (int j = 0; j < MSFM_KNN_GROUP; j++) {
-          ha[j] = __builtin_amdgcn_ballot_w64((u32)acca[MSFM_KNN_GROUP * g + j] <= thra);
-          hb[j] = __builtin_amdgcn_ballot_w64((u32)accb[MSFM_KNN_GROUP * g + j] <= thrb);
-        }
+        for (int j = 0; j < KNN_GROUP; j++)
+          hm[j] = __builtin_amdgcn_ballot_w64((u32)acca[KNN_GROUP * g + j] <= thra) | __builtin_amdgcn_ballot_w64((u32)accb[KNN_GROUP * g + j] <= thrb);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int j = 0; j < MSFM_KNN_GROUP; j++) {
-          const int reg = MSFM_KNN_GROUP * g + j;
-          if (ha[j] != 0ull) {
-            u32 keya;
-            asm volatile("v_lshl_or_b32 %0, %1, 9, %2" : "=v"(keya) : "v"(acca[reg]), "v"(cc[reg]));
-            const u32 na0 = min(ak0, keya);
-            ak1 = umed3(ak0, ak1, keya);
-            ak0 = na0;
-          }
-          if (hb[j] != 0ull) {
-            u32 keyb;
-            asm volatile("v_lshl_or_b32 %0, %1, 9, %2" : "=v"(keyb) : "v"(accb[reg]), "v"(cc[reg]));
-            const u32 nb0 = min(bk0, keyb);
-            bk1 = umed3(bk0, bk1, keyb);
-            bk0 = nb0;
-          }
-        }
-      }
-#else
-#pragma unroll
-      for (int g = 0; g < 16 / MSFM_KNN_GROUP; g++) {
-        unsigned long long hm[MSFM_KNN_GROUP];
-#ifdef MSFM_KNN_THR_GROUP
-        if (g > 0) { thra = min(ak1 >> 9, aD1 >> 1); thrb = min(bk1 >> 9, bD1 >> 1); }
-#endif
-#pragma unroll
-        for (int j = 0; j < MSFM_KNN_GROUP; j++)
-          hm[j] = __builtin_amdgcn_ballot_w64((u32)acca[MSFM_KNN_GROUP * g + j] <= thra) | __builtin_amdgcn_ballot_w64((u32)accb[MSFM_KNN_GROUP * g + j] <= thrb);
-        __builtin_amdgcn_sched_barrier(0);
-#ifdef MSFM_KNN_HITSTATS
-        if (lane == 0) {
-          int nh = 0;
-          for (int j = 0; j < MSFM_KNN_GROUP; j++) nh += hm[j] != 0ull;
-          atomicAdd(&g_knn_hits[min(tile >> 3, 7)][nh], 1ull);
-        }
-#endif
-#pragma unroll
-        for (int j = 0; j < MSFM_KNN_GROUP; j++) {
+        for (int j = 0; j < KNN_GROUP; j++) {
           if (hm[j] == 0ull) continue;
-          const int reg = MSFM_KNN_GROUP * g + j;
-#ifndef MSFM_KNN_CC_LDS
+          const int reg = KNN_GROUP * g + j;
           const u32 cw = (u32)cc[reg];
-#else
-          // (MSFM_KNN_CC_LDS: the row word fetched only here - sixteen registers less in the loop; measured slower: 1 707 against 1 750)
-          const u32 cw = (u32)lds_c[cur][st * 32 + 8 * (reg >> 2) + 4 * h + (reg & 3)];
-#endif
           u32 keya, keyb;
           asm volatile("v_lshl_or_b32 %0, %1, 9, %2" : "=v"(keya) : "v"(acca[reg]), "v"(cw));
           asm volatile("v_lshl_or_b32 %0, %1, 9, %2" : "=v"(keyb) : "v"(accb[reg]), "v"(cw));
@@ -524,26 +295,11 @@ __global__ __launch_bounds__(256, 4) void k_knn2_i8(const PairTask8* __restrict_
           bk0 = nb0;
         }
       }
-#endif
-#else
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const u32 keya = ((u32)acca[reg] << 9) | (u32)cc[reg];
-        const u32 keyb = ((u32)accb[reg] << 9) | (u32)cc[reg];
-        const u32 na0 = min(ak0, keya);
-        ak1 = umed3(ak0, ak1, keya);
-        ak0 = na0;
-        const u32 nb0 = min(bk0, keyb);
-        bk1 = umed3(bk0, bk1, keyb);
-        bk0 = nb0;
-      }
-#endif
     }
     if ((tile & 3) == 3 || tile == n_tiles - 1) {
       const int base = (tile & ~3) * TT;
       flush_window8(ak0, ak1, aD0, aI0, aD1, aI1, base);
       flush_window8(bk0, bk1, bD0, bI0, bD1, bI1, base);
-#ifndef MSFM_KNN_NOSHARE
       // A query's train rows are split between lanes r and r + 32, each with its own list.  A candidate worse than the second
       // best of the two lists TOGETHER cannot be among the query's two nearest, whichever lane it falls to: that bound (formed
       // here, where the lists change - once per 256 rows) halves the candidates that pass the compare filter late in the sweep
@@ -556,7 +312,6 @@ __global__ __launch_bounds__(256, 4) void k_knn2_i8(const PairTask8* __restrict_
         const auto b1 = __builtin_amdgcn_permlane32_swap(bD1 >> 1, bD1 >> 1, false, false);
         bTl = min(max((u32)b0[0], (u32)b0[1]), min((u32)b1[0], (u32)b1[1]));
       }
-#endif
     }
     if (tile + 1 < n_tiles) commit(cur ^ 1);
     __syncthreads();
@@ -582,63 +337,6 @@ __global__ __launch_bounds__(256, 4) void k_knn2_i8(const PairTask8* __restrict_
   }
 }
 
-// ---- general path: exact binary64 brute force, k sequential ------------------------------
-struct PairTaskF {
-  const float* train;
-  const float* query;
-  int n_train, n_query, out_off;
-};
-
-__global__ __launch_bounds__(64) void k_knn2_exact(const PairTaskF* __restrict__ tasks, const int* __restrict__ tile_first, int n_pairs,
-                                                    float ratio_good, float ratio_all, int32_t* __restrict__ code,
-                                                    int* __restrict__ ids, float* __restrict__ sqd, int* __restrict__ n_all,
-                                                    int* __restrict__ n_good) {
-  __shared__ float ta[64 * (DIM + 1)];
-  int lo = 0, hi = n_pairs - 1;
-  const int bid = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tile_first[mid] <= bid) lo = mid; else hi = mid - 1;
-  }
-  const int pair = lo;
-  const PairTaskF T = tasks[pair];
-  const int q = (bid - tile_first[pair]) * 64 + threadIdx.x;
-  const bool qvalid = q < T.n_query;
-  float qv[DIM];
-  const float* qp = T.query + (size_t)(qvalid ? q : 0) * DIM;
-#pragma unroll
-  for (int k = 0; k < DIM; k++) qv[k] = qp[k];
-  double d0 = __builtin_inf(), d1 = __builtin_inf();
-  int i0 = -1, i1 = -1;
-  for (int t0 = 0; t0 < T.n_train; t0 += 64) {
-    __syncthreads();
-    for (int e = threadIdx.x; e < 64 * DIM; e += 64) {
-      const int row = e / DIM, k = e % DIM;
-      ta[row * (DIM + 1) + k] = (t0 + row < T.n_train) ? T.train[(size_t)(t0 + row) * DIM + k] : 0.f;
-    }
-    __syncthreads();
-    const int nrow = min(64, T.n_train - t0);
-    for (int row = 0; row < nrow; row++) {
-      const float* a = &ta[row * (DIM + 1)];
-      double s = 0.0;
-#pragma unroll
-      for (int k = 0; k < DIM; k++) {
-        const double d = (double)a[k] - (double)qv[k];
-        s = fma(d, d, s);
-      }
-      const int t = t0 + row;
-      if (s < d0) { d1 = d0; i1 = i0; d0 = s; i0 = t; }
-      else if (s < d1) { d1 = s; i1 = t; }
-    }
-  }
-  if (qvalid) {
-    const float f0 = (float)d0, f1 = (float)d1;
-    const size_t o = (size_t)T.out_off + q;
-    if (ids) { ids[2 * o] = i0; ids[2 * o + 1] = i1; sqd[2 * o] = f0; sqd[2 * o + 1] = f1; }
-    if (code) code[o] = ratio_code(f0, f1, i0, ratio_good, ratio_all, &n_all[pair], &n_good[pair]);
-  }
-}
-
 // ---- certified f16 path for non-integral descriptors --------------------------------------------
 // The reference's extractors hand over non-integral floats (feature_extractor_vl_sift.cpp:202: 512.0F * x, never cast).
 // One f16 MFMA product per term gives every squared distance to within a bound E that follows from the operand
@@ -656,9 +354,6 @@ __global__ __launch_bounds__(64) void k_knn2_exact(const PairTaskF* __restrict__
 // (k_exact_flagged), so the result is exact for every finite input; how many took that road is reported in the
 // result object (msfm_match_result_stats).
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-#ifndef MSFM_KNN_F16_PROBE
-#define MSFM_KNN_F16_PROBE 0
-#endif
 
 __global__ __launch_bounds__(256) void k_desc_prep_f16(const float* __restrict__ d, int count, float scale, unsigned short* __restrict__ th,
                                                         unsigned short* __restrict__ qh, float* __restrict__ n2s, float* __restrict__ rerr,
@@ -791,19 +486,12 @@ __device__ __forceinline__ void merge_window4(u32 (&g)[4], int (&gb)[4], u32 w0,
 // nearest DISTANCE then lies between the smallest lower bound and the smallest upper bound of the others, the float ratio is
 // monotone in both distances (float conversion and float division are monotone), and if `ratio < th` comes out the same at
 // both ends of its interval it is the exact answer: the code is written without a single exact evaluation (94 % of the
-// queries on 512-norm SIFT-like data, scripts/knn_f16_stats.py; 0.13 exact evaluations per query instead of 2.1).  Otherwise -
+// queries on 512-norm SIFT-like data; 0.13 exact evaluations per query instead of 2.1).  Otherwise -
 // and whenever the 2-NN arrays are kept - the candidates are evaluated by the oracle's definition as before.
 // (the exact evaluations of a wave are pooled: every lane files its candidates of both query sets in a work list in LDS, the
 // wave walks the list sixty-four entries at a time - one lane per (query, row), all lanes busy - and every lane then reads its
 // own results back.  Per-slot evaluation `if (eval_j) exact_sqdist(...)` made the whole wave wait through up to eight rounds of
 // 128 dependent binary64 operations whenever one lane had a candidate in that slot.)
-#ifdef MSFM_KNN_F16_STATS   // developer counters (scripts/knn_f16_stats.py): valid queries, queries decided from intervals, exact evaluations, list rounds
-__device__ unsigned long long g_f16_stats[8];
-extern "C" __attribute__((visibility("default"))) int msfm_dbg_f16_stats(unsigned long long* out, int reset) {
-  if (reset) { static unsigned long long z[8]; return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_f16_stats), z, sizeof z); }
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_f16_stats), 8 * sizeof(unsigned long long));
-}
-#endif
 // Is the outcome of the ratio tests the same for every pair of distances d0 in [lo0, hi0], d1 in [lo1, hi1] (hi0 < lo1)?  The
 // float distances the exact path would form lie in [(float)lo, (float)hi] (rounding is monotone), its float ratio in
 // [r_lo, r_hi] (float division is monotone in both operands); the 1e-30 guard keeps zeros, subnormal ratios and 0 / 0 on the
@@ -848,7 +536,6 @@ __device__ __forceinline__ void epi_prepare(const PairTaskH& T, int q, bool qval
   const double b_mine = gi[3] < T.n_train ? (double)__uint_as_float(gv[3]) : inf;
   const double b_other = oi[3] < T.n_train ? (double)__uint_as_float(ov[3]) : inf;
   double unl = fmin(b_mine, b_other);
-#ifndef MSFM_KNN_F16_NOFILTER
   // ... and the rows the compare filter of the main loop dropped were above a threshold that was never smaller than
   // T = (second smallest key of the two final lists, low byte filled) (1 + 2^-15) + 2.01 E  (the loop adds 2.05 E, rounded up; a
   // window's or an earlier flush's second smallest is never below the final one, and the two smallest rows of a query are
@@ -864,7 +551,6 @@ __device__ __forceinline__ void epi_prepare(const PairTaskH& T, int q, bool qval
     }
     if (k2 < 0x7f800000u) unl = fmin(unl, (double)__uint_as_float(k2) * (1.0 + 3.0517578125e-5) + 2.01 * E);
   }
-#endif
   Q.unl_bound = unl - G - E;
   // scaled-distance interval of a listed row: [val - G - E, val (1 + 2^-15) - G + E]  (val = key with its low byte cleared)
   // the two smallest values over both lists (both lanes of a query see the same eight entries: every decision below that
@@ -882,7 +568,6 @@ __device__ __forceinline__ void epi_prepare(const PairTaskH& T, int q, bool qval
   }
   bool certain = false;
   float fa = 0.f, fb = 1.f;
-#ifndef MSFM_KNN_F16_NOFASTCODE
   if (!keep_knn && v2 < 0x7f800000u) {
     const double inv_s2 = 1.0 / (double)T.s2;   // a power of two: exact
     const double x1 = (double)__uint_as_float(v1), x2 = (double)__uint_as_float(v2);
@@ -891,7 +576,6 @@ __device__ __forceinline__ void epi_prepare(const PairTaskH& T, int q, bool qval
     const double lo1 = (fmin(x2, unl) - G - E) * inv_s2 * (1.0 - 1e-12), hi1 = (x2 * (1.0 + 3.0517578125e-5) - G + E) * inv_s2 * (1.0 + 1e-12);
     certain = ratio_certain(lo0, hi0, lo1, hi1, ratio_good, ratio_all, fa, fb);
   }
-#endif
   Q.certain = certain; Q.fa = fa; Q.fb = fb; Q.id1 = id1;
   double h1 = inf, h2 = inf;  // the two smallest upper bounds over both lists
 #pragma unroll
@@ -930,7 +614,7 @@ __device__ __forceinline__ void epi_file(EpiQuery& Q, int q, int2* __restrict__ 
 // of 6e-3: all but ~0.3 % of these queries are decided here (0.126 -> 0.0003 exact evaluations per query on 512-norm SIFT-like data,
 // the wave's round of 128 dependent binary64 operations runs in 0.8 % of the waves instead of 97 %).  On that data the kernel's time
 // did not change (18.75 ms either way on 4 032 pairs: the round was hidden behind the CU's other workgroup); the pass is kept for
-// data whose ratios crowd a threshold, where the f16 intervals decide little (-DMSFM_KNN_F16_NOREFINE: without it).
+// data whose ratios crowd a threshold, where the f16 intervals decide little.
 __device__ __forceinline__ void epi_refine(const PairTaskH& T, EpiQuery& Q, const float* __restrict__ r32, float ratio_good, float ratio_all) {
   float b0 = __builtin_inff(), b1 = __builtin_inff();
   int j0 = 0x7fffffff, j1 = 0x7fffffff;
@@ -994,15 +678,12 @@ __device__ __forceinline__ void epi_finish(const PairTaskH& T, int pair, int q, 
 }
 
 // 1 workgroup = 4 waves = 256 queries of one pair (two query sets of 32 per wave, every A fragment feeds two MFMAs);
-// train tiles of 64 rows double-buffered through XOR-swizzled LDS, as the integer kernels.
-#ifndef MSFM_KNN_F16_WGS
-#define MSFM_KNN_F16_WGS 3   // (round 5: three workgroups per CU since the tile fetch needs no staging registers: 875 -> 960 Mmatches/s on 4 032 pairs)
-#endif
-__global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTaskH* __restrict__ tasks, const int* __restrict__ tile_first, int n_pairs,
+// train tiles of 64 rows double-buffered through XOR-swizzled LDS, as in the integer kernel.
+// (round 5: three workgroups per CU since the tile fetch needs no staging registers: 875 -> 960 Mmatches/s on 4 032 pairs)
+__global__ __launch_bounds__(256, 3) void k_knn2_f16(const PairTaskH* __restrict__ tasks, const int* __restrict__ tile_first, int n_pairs,
                                                       float ratio_good, float ratio_all, int32_t* __restrict__ code, int* __restrict__ ids,
                                                       float* __restrict__ sqd, int* __restrict__ n_all, int* __restrict__ n_good,
-                                                      int* __restrict__ flagged, int* __restrict__ nf_group, int* __restrict__ n_flagged,
-                                                      int debug_mode) {
+                                                      int* __restrict__ flagged, int* __restrict__ nf_group, int* __restrict__ n_flagged) {
   __shared__ __attribute__((aligned(16))) unsigned char lds_a[2][TT * 256];
   __shared__ __attribute__((aligned(16))) float lds_n[2][TT];
   int lo = 0, hi = n_pairs - 1;
@@ -1056,9 +737,8 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
     if (tid < TT) lds_n[buf][tid] = (tile * TT + tid < T.n_train) ? stage_n + T.shift : 3.0e38f;  // padding rows lose every comparison
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the wave's own LDS-DMA pieces have landed (s_barrier does not wait for them)
   };
-  u32 keymask;
+  u32 keymask;   // (in a VGPR: v_and_or_b32 below, a VOP3, takes one scalar / literal operand only)
   asm volatile("v_mov_b32 %0, 0xffffff00" : "=v"(keymask));
-#ifndef MSFM_KNN_F16_NOFILTER
   // Round 5: one compare per candidate, against the query's SECOND smallest value so far plus twice the error bound (below).
   // aU / bU: threshold bits from the lists of both lanes of a query (formed at the window flush), mA / mB: 2.05 E of the lane's
   // two queries, rounded up.
@@ -1071,7 +751,6 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
     mA = __uint_as_float(__float_as_uint((float)(2.05 * Ea)) + 1u);
     mB = __uint_as_float(__float_as_uint((float)(2.05 * Eb)) + 1u);
   }
-#endif
   fetch(0, 0);
   commit(0, 0);
   __syncthreads();
@@ -1098,7 +777,6 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
         accb = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, bqb[ks], accb, 0, 0, 0);
       }
       const int wbase = ((tile & 3) * 2 + st) * 32;
-#ifndef MSFM_KNN_F16_NOFILTER
       // Round 5: one compare per candidate.  With v2 the second smallest accumulator value a query has met - in this lane's
       // current window (a1) or in the lists of both its lanes at the last flush (aU) - a row whose value exceeds
       // v2 (1 + 2^-15) + 2 E has an exact distance above that of two other rows (every value is within E of the exact scaled
@@ -1107,15 +785,8 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
       // hit rate, measured slower than the unconditional chain.)  An empty window key is a NaN pattern: above every finite
       // value as an unsigned integer, so everything passes.  All compares of a group of four register slots first (wave masks
       // in scalar registers), then the ten selection operations for the slots with a hit in either query set.
-#if MSFM_KNN_F16_PROBE == 1     // (timing probes, wrong results: no candidate ever passes)
-      const u32 ta = 0u, tb = 0u;
-#else
       const u32 ta = min(__float_as_uint(__builtin_fmaf(__uint_as_float(a1 | 255u), 1.0000306f, mA)), aU);
       const u32 tb = min(__float_as_uint(__builtin_fmaf(__uint_as_float(b1 | 255u), 1.0000306f, mB)), bU);
-#endif
-#if MSFM_KNN_F16_PROBE == 2     // (no selection at all: the accumulators are consumed by two operations per step)
-      a0 = min(a0, __float_as_uint(acca[0]) ^ __float_as_uint(acca[15])); b0 = min(b0, __float_as_uint(accb[0]) ^ __float_as_uint(accb[15]));
-#else
 #pragma unroll
       for (int g = 0; g < 4; g++) {
         unsigned long long hm[4];
@@ -1135,19 +806,6 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
           b3 = umed3(b2, b3, kb); b2 = umed3(b1, b2, kb); b1 = umed3(b0, b1, kb); b0 = min(b0, kb);
         }
       }
-#endif
-#else
-#pragma unroll
-      for (int reg = 0; reg < 16; reg++) {
-        const u32 idx = (u32)(wbase + (reg & 3) + 8 * (reg >> 2));
-        // one v_and_or_b32 per key: the mask sits in a VGPR (a VOP3 takes one scalar / literal operand only).  The
-        // accumulators must be read by an instruction the compiler sees: it places the MFMA -> VALU wait states
-        const u32 ka = (__float_as_uint(acca[reg]) & keymask) | idx;
-        const u32 kb = (__float_as_uint(accb[reg]) & keymask) | idx;
-        a3 = umed3(a2, a3, ka); a2 = umed3(a1, a2, ka); a1 = umed3(a0, a1, ka); a0 = min(a0, ka);
-        b3 = umed3(b2, b3, kb); b2 = umed3(b1, b2, kb); b1 = umed3(b0, b1, kb); b0 = min(b0, kb);
-      }
-#endif
     }
     if ((tile & 3) == 3 || tile == n_tiles - 1) {
       const int base = (tile & ~3) * TT + 4 * h;
@@ -1155,7 +813,6 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
       merge_window4(gvb, gib, b0, b1, b2, b3, base);
       a0 = a1 = a2 = a3 = 0xffffffffu;
       b0 = b1 = b2 = b3 = 0xffffffffu;
-#ifndef MSFM_KNN_F16_NOFILTER
       // the second smallest key over the sorted lists of BOTH lanes of a query: min(max(x0, y0), min(x1, y1))
       {
         const auto s0 = __builtin_amdgcn_permlane32_swap(gva[0], gva[0], false, false);
@@ -1167,43 +824,23 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
         const u32 w2 = min(max((u32)t0[0], (u32)t0[1]), min((u32)t1[0], (u32)t1[1])) | 255u;
         bU = __float_as_uint(__builtin_fmaf(__uint_as_float(w2), 1.0000306f, mB));
       }
-#endif
     }
     if (tile + 1 < n_tiles) commit(cur ^ 1, tile + 1);
     __syncthreads();
     cur ^= 1;
-  }
-  if (debug_mode == 1) {   // timing experiment: main loop only
-    if (va && h == 0) code[(size_t)T.out_off + qa] = (int)gva[0] + gia[1];
-    if (vb && h == 0) code[(size_t)T.out_off + qb] = (int)gvb[0] + gib[1];
-    return;
   }
   // Epilogue.  Every wave is past its last read of the train tiles (the loop ends with a barrier): their 32 KB become four
   // wave-private work lists - 512 (train row, query row) entries and 512 results each (a lane files at most eight candidates).
   EpiQuery A, B;
   epi_prepare(T, qa, va, gva, gia, ids != nullptr, ratio_good, ratio_all, A);
   epi_prepare(T, qb, vb, gvb, gib, ids != nullptr, ratio_good, ratio_all, B);
-  if (debug_mode == 2) {   // timing experiment: main loop + interval decisions only
-    if (va && h == 0) code[(size_t)T.out_off + qa] = A.id1 + (int)A.certain;
-    if (vb && h == 0) code[(size_t)T.out_off + qb] = B.id1 + (int)B.certain;
-    return;
-  }
   int2* ent = reinterpret_cast<int2*>(&lds_a[0][0] + wave * 8192);
   double* res = reinterpret_cast<double*>(&lds_a[0][0] + wave * 8192 + 4096);
   int n_ent = 0;
   epi_file(A, qa, ent, n_ent);
   epi_file(B, qb, ent, n_ent);
-#ifdef MSFM_KNN_F16_STATS
-  {
-    const int nv = __builtin_popcountll(__builtin_amdgcn_ballot_w64(va && h == 0)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(vb && h == 0));
-    const int nc = __builtin_popcountll(__builtin_amdgcn_ballot_w64(va && h == 0 && A.certain)) + __builtin_popcountll(__builtin_amdgcn_ballot_w64(vb && h == 0 && B.certain));
-    if (lane == 0) { atomicAdd(&g_f16_stats[0], (unsigned long long)nv); atomicAdd(&g_f16_stats[1], (unsigned long long)nc);
-                     atomicAdd(&g_f16_stats[2], (unsigned long long)n_ent); atomicAdd(&g_f16_stats[3], (unsigned long long)((n_ent + 63) / 64)); }
-  }
-#endif
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-#ifndef MSFM_KNN_F16_NOREFINE
   if (!ids && n_ent > 0) {
     // binary32 distances of every filed (train row, query row) by the whole wave: lanes 0-31 fetch the train row, lanes 32-63 the
     // query row, sixteen coalesced bytes each; eight entries' loads in flight at a time (the float32 rows are cold: the sweep read
@@ -1238,14 +875,10 @@ __global__ __launch_bounds__(256, MSFM_KNN_F16_WGS) void k_knn2_f16(const PairTa
     n_ent = 0;
     epi_file(A, qa, ent, n_ent);
     epi_file(B, qb, ent, n_ent);
-#ifdef MSFM_KNN_F16_STATS
-    if (lane == 0) { atomicAdd(&g_f16_stats[4], (unsigned long long)n_ent); atomicAdd(&g_f16_stats[5], (unsigned long long)((n_ent + 63) / 64)); }
-#endif
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-#endif
-  for (int e = lane; e < (debug_mode == 3 ? 0 : n_ent); e += 64) {   // (3: timing experiment without the exact evaluations)
+  for (int e = lane; e < n_ent; e += 64) {
     const int2 x = ent[e];
     res[e] = exact_sqdist(T.tf32 + (size_t)x.x * DIM, T.qf32 + (size_t)x.y * DIM);
   }
@@ -1414,7 +1047,7 @@ MSFM_API int msfm_descset_create(msfm_ctx* ctx, int n_images, int dim, msfm_desc
   s->ctx = ctx; s->n_images = n_images; s->dim = dim;
   s->count.assign(n_images, 0);
   s->kp.assign(n_images, nullptr);
-  s->f32.assign(n_images, nullptr); s->bf16.assign(n_images, nullptr); s->norm.assign(n_images, nullptr);
+  s->f32.assign(n_images, nullptr);
   s->th16.assign(n_images, nullptr); s->qh16.assign(n_images, nullptr); s->n2s.assign(n_images, nullptr); s->n2s_max.assign(n_images, 0.f);
   s->rerr.assign(n_images, nullptr); s->rerr_max.assign(n_images, 0.f);
   s->f16_exp.assign(n_images, INT_MIN);
@@ -1438,8 +1071,6 @@ MSFM_API void msfm_descset_destroy(msfm_descset* s) {
   for (msfm_match_result* r : s->results) orphan_result(r);   // their codes / counts stay readable, a rerun is refused
   for (auto p : s->kp) delete p;
   for (auto p : s->f32) delete p;
-  for (auto p : s->bf16) delete p;
-  for (auto p : s->norm) delete p;
   for (auto p : s->th16) delete p;
   for (auto p : s->qh16) delete p;
   for (auto p : s->n2s) delete p;
@@ -1469,26 +1100,23 @@ MSFM_API int msfm_descset_upload(msfm_descset* s, int image, const float* desc, 
   s->generation++;
   delete s->kp[image]; s->kp[image] = nullptr;   // positions belong to the features they were uploaded with
   s->kp_generation++;
-  delete s->f32[image]; delete s->bf16[image]; delete s->norm[image];
+  delete s->f32[image];
   delete s->th16[image]; delete s->qh16[image]; delete s->n2s[image]; delete s->rerr[image];
   s->th16[image] = new DevBuf<unsigned short>(); s->qh16[image] = new DevBuf<unsigned short>(); s->n2s[image] = new DevBuf<float>();
   s->rerr[image] = new DevBuf<float>();
   s->n2s_max[image] = 0.f;
   s->f16_exp[image] = INT_MIN;
   delete s->ti8[image]; delete s->qi8[image]; delete s->tcin[image]; delete s->tpar[image]; delete s->qbeta[image];
-  s->f32[image] = new DevBuf<float>(); s->bf16[image] = new DevBuf<unsigned short>(); s->norm[image] = new DevBuf<float>();
+  s->f32[image] = new DevBuf<float>();
   s->ti8[image] = new DevBuf<signed char>(); s->qi8[image] = new DevBuf<signed char>();
   s->tcin[image] = new DevBuf<int>(); s->tpar[image] = new DevBuf<int>(); s->qbeta[image] = new DevBuf<int>();
   s->count[image] = count;
   if (count == 0) return MSFM_OK;
   HIP_TRY(ctx, s->f32[image]->alloc((size_t)count * DIM));
-  HIP_TRY(ctx, s->bf16[image]->alloc((size_t)count * DIM));
-  HIP_TRY(ctx, s->norm[image]->alloc(count));
   HIP_TRY(ctx, s->ti8[image]->alloc((size_t)count * DIM)); HIP_TRY(ctx, s->qi8[image]->alloc((size_t)count * DIM));
   HIP_TRY(ctx, s->tcin[image]->alloc(count)); HIP_TRY(ctx, s->tpar[image]->alloc(count)); HIP_TRY(ctx, s->qbeta[image]->alloc(count));
   HIP_TRY(ctx, s->f32[image]->upload(desc, (size_t)count * DIM, st));
-  hipLaunchKernelGGL(k_desc_prep, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->bf16[image]->p,
-                     s->norm[image]->p, s->nonint.p, s->vmax_dev.p);
+  hipLaunchKernelGGL(k_desc_prep, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->nonint.p, s->vmax_dev.p);
   hipLaunchKernelGGL(k_desc_prep_i8, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->ti8[image]->p,
                      s->qi8[image]->p, s->tcin[image]->p, s->tpar[image]->p, s->qbeta[image]->p);
   HIP_TRY(ctx, hipGetLastError());
@@ -1589,14 +1217,10 @@ struct msfm_match_result {
   DevBuf<int32_t> code;
   DevBuf<int> ids, n_all, n_good, tile_first;
   DevBuf<float> sqd;
-  DevBuf<PairTask> tasks;
   DevBuf<PairTask8> tasks8;
-  DevBuf<PairTaskF> tasksf;
   DevBuf<PairTaskH> tasksh;
   DevBuf<int> flagged, n_flagged, pair_off, group_first, nf_group;
   int n_groups = 0;
-  bool use_exact = false;  // MSFM_KNN_EXACT=1: brute-force FP64 kernel for non-integral data instead of the certified f16 path
-  bool use_bf16 = false;  // MSFM_KNN_BF16=1 selects the bf16 MFMA kernel instead of the int8 one
   int n_tiles = 0;
   bool exact_path = false;
   unsigned long generation = 0;   // of the descriptor set when the task tables were built
@@ -1629,24 +1253,19 @@ static int launch_match(msfm_match_result* R) {
   HIP_TRY(ctx, hipMemsetAsync(R->n_all.p, 0, sizeof(int) * R->n_pairs, st));
   HIP_TRY(ctx, hipMemsetAsync(R->n_good.p, 0, sizeof(int) * R->n_pairs, st));
   if (R->n_tiles == 0) return MSFM_OK;
-  if (!R->exact_path && !R->use_bf16) {
+  if (!R->exact_path) {
     KTimer t(ctx, "knn2_i8_mfma");
     hipLaunchKernelGGL(k_knn2_i8, dim3(R->n_tiles), dim3(256), 0, st, R->tasks8.p, R->tile_first.p, R->n_pairs, R->ratio_good,
                        R->ratio_all, R->code.p, R->keep_knn ? R->ids.p : (int*)nullptr, R->keep_knn ? R->sqd.p : (float*)nullptr,
                        R->n_all.p, R->n_good.p);
-  } else if (!R->exact_path) {
-    KTimer t(ctx, "knn2_bf16_mfma");
-    hipLaunchKernelGGL(k_knn2_bf16, dim3(R->n_tiles), dim3(256), 0, st, R->tasks.p, R->tile_first.p, R->n_pairs, R->ratio_good,
-                       R->ratio_all, R->code.p, R->keep_knn ? R->ids.p : (int*)nullptr, R->keep_knn ? R->sqd.p : (float*)nullptr,
-                       R->n_all.p, R->n_good.p);
-  } else if (!R->use_exact) {
+  } else {
     {
       KTimer t(ctx, "knn2_f16_mfma");
       HIP_TRY(ctx, hipMemsetAsync(R->n_flagged.p, 0, sizeof(int), st));
       HIP_TRY(ctx, hipMemsetAsync(R->nf_group.p, 0, sizeof(int) * std::max(1, R->n_groups), st));   // per-group flagged counters
       hipLaunchKernelGGL(k_knn2_f16, dim3(R->n_tiles), dim3(256), 0, st, R->tasksh.p, R->tile_first.p, R->n_pairs, R->ratio_good, R->ratio_all,
                          R->code.p, R->keep_knn ? R->ids.p : (int*)nullptr, R->keep_knn ? R->sqd.p : (float*)nullptr, R->n_all.p, R->n_good.p,
-                         R->flagged.p, R->nf_group.p, R->n_flagged.p, getenv("MSFM_KNN_DEBUG") ? atoi(getenv("MSFM_KNN_DEBUG")) : 0);
+                         R->flagged.p, R->nf_group.p, R->n_flagged.p);
     }
     {
       KTimer t(ctx, "knn2_exact_flagged_f64");
@@ -1655,11 +1274,6 @@ static int launch_match(msfm_match_result* R) {
                            R->ratio_all, R->code.p, R->keep_knn ? R->ids.p : (int*)nullptr, R->keep_knn ? R->sqd.p : (float*)nullptr, R->n_all.p,
                            R->n_good.p);
     }
-  } else {
-    KTimer t(ctx, "knn2_exact_f64");
-    hipLaunchKernelGGL(k_knn2_exact, dim3(R->n_tiles), dim3(64), 0, st, R->tasksf.p, R->tile_first.p, R->n_pairs, R->ratio_good,
-                       R->ratio_all, R->code.p, R->keep_knn ? R->ids.p : (int*)nullptr, R->keep_knn ? R->sqd.p : (float*)nullptr,
-                       R->n_all.p, R->n_good.p);
   }
   if (R->slam && R->gate_max_nq > 0) {
     KTimer t(ctx, "slam_prior_gates");
@@ -1693,16 +1307,11 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   R->set = s; R->n_pairs = n_pairs; R->keep_knn = keep_knn != 0; R->ratio_good = ratio_good; R->ratio_all = ratio_all;
   R->pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
   R->exact_path = s->h_nonint != 0;
-  { const char* e = getenv("MSFM_KNN_BF16"); R->use_bf16 = e && e[0] == '1'; }
-  { const char* e = getenv("MSFM_KNN_EXACT"); R->use_exact = e && e[0] == '1'; }
-  const bool certified = R->exact_path && !R->use_exact;
+  const bool certified = R->exact_path;
   if (certified) MSFM_TRY(ensure_f16_forms(s));
-  const int qpb = (R->exact_path && !certified) ? 64 : QPB;
   std::vector<PairTaskH> tasksh(certified ? n_pairs : 0);
   std::vector<int> pair_off(n_pairs + 1, 0), group_first;
   std::vector<int> tile_first(n_pairs + 1, 0);
-  std::vector<PairTask> tasks(n_pairs);
-  std::vector<PairTaskF> tasksf(n_pairs);
   std::vector<PairTask8> tasks8(n_pairs);
   long off = 0;
   long tiles = 0;
@@ -1712,9 +1321,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
     R->out_off.push_back((int)off);
     R->nq.push_back(nq);
     tile_first[p] = (int)tiles;
-    tasks[p] = PairTask{s->bf16[a]->p, nq ? s->bf16[b]->p : nullptr, s->norm[a]->p, nq ? s->norm[b]->p : nullptr, s->count[a], nq, (int)off};
     tasks8[p] = PairTask8{s->ti8[a]->p, nq ? s->qi8[b]->p : nullptr, s->tcin[a]->p, s->tpar[a]->p, nq ? s->qbeta[b]->p : nullptr, s->count[a], nq, (int)off, s->zero_row.p};
-    tasksf[p] = PairTaskF{s->f32[a]->p, nq ? s->f32[b]->p : nullptr, s->count[a], nq, (int)off};
     pair_off[p] = (int)off;
     if (certified) {
       const float ex = (float)s->f16_exp[a];
@@ -1730,7 +1337,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
                             (int)off, (int)group_first.size() - 1, pair_off[group_first.back()]};
     }
     off += nq;
-    tiles += cdiv(nq, qpb);
+    tiles += cdiv(nq, QPB);
     if (off > 0x7fffffffL || tiles > 0x7fffffffL) return msfm_set_error(ctx, MSFM_E_INVAL, "too many queries in one call; split the pair list");
   }
   tile_first[n_pairs] = (int)tiles;
@@ -1752,7 +1359,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   if (R->keep_knn) { HIP_TRY(ctx, R->ids.alloc(std::max<long>(1, 2 * off))); HIP_TRY(ctx, R->sqd.alloc(std::max<long>(1, 2 * off))); }
   HIP_TRY(ctx, R->n_all.alloc(std::max(1, n_pairs))); HIP_TRY(ctx, R->n_good.alloc(std::max(1, n_pairs)));
   HIP_TRY(ctx, R->tile_first.from(tile_first, st));
-  if (n_pairs) { HIP_TRY(ctx, R->tasks.from(tasks, st)); HIP_TRY(ctx, R->tasksf.from(tasksf, st)); HIP_TRY(ctx, R->tasks8.from(tasks8, st)); }
+  if (n_pairs) HIP_TRY(ctx, R->tasks8.from(tasks8, st));
   if (slam) {
     std::vector<SlamGateTask> gt(n_pairs);
     for (int p = 0; p < n_pairs; p++) {

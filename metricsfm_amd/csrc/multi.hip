@@ -114,9 +114,8 @@ void abort_comms(msfm_multi* mc) {
 }
 
 // (test hook) MSFM_MULTI_FAIL_RANK=r: rank r of the next collective-bearing call returns an error before it joins anything
-int injected_failure(msfm_multi* mc, int r) {
-  const char* e = getenv("MSFM_MULTI_FAIL_RANK");
-  if (!e || atoi(e) != r) return MSFM_OK;
+int injected_failure(msfm_multi* mc, int r, int fail_rank) {
+  if (r != fail_rank) return MSFM_OK;
   return msfm_set_error(mc->ctx[r], MSFM_E_INVAL, "injected failure (MSFM_MULTI_FAIL_RANK)");
 }
 
@@ -239,6 +238,7 @@ MSFM_API const char* msfm_multi_last_error(const msfm_multi* mc) { return mc ? m
 // ---- bundle adjustment: points split over the contexts (shard.point_ranges restated) ----
 MSFM_API int msfm_multi_ba_solve(msfm_multi* mc, msfm_ba_problem* P, const msfm_ba_options* opt, msfm_ba_summary* summary) {
   if (!mc || !P || !opt || !summary) return MSFM_E_INVAL;
+  const int fail_rank = msfm_env_read().multi_fail_rank;   // (read here, on the caller's thread, before the rank threads start)
   if (mc->n == 1) {
     const int rc = msfm_ba_solve(mc->ctx[0], P, opt, summary);
     return rc == MSFM_OK ? rc : fail(mc, rc, msfm_last_error(mc->ctx[0]));
@@ -293,7 +293,7 @@ MSFM_API int msfm_multi_ba_solve(msfm_multi* mc, msfm_ba_problem* P, const msfm_
       sm->iterations = summary->iterations ? its[r].data() : nullptr;
       sm->iterations_capacity = summary->iterations ? summary->iterations_capacity : 0;
     }
-    MSFM_TRY(injected_failure(mc, r));
+    MSFM_TRY(injected_failure(mc, r, fail_rank));
     return msfm_ba_solve(mc->ctx[r], &S, opt, sm);
   }, true);
   return rc;

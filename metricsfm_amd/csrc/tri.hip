@@ -126,12 +126,6 @@ __device__ __forceinline__ void tri_midpoint_track(const TrackPtrs& T, int t, do
   mse[t] = m;
   ok[t] = !(sqrt(m) > th_error || !track_angle_ok(T, b, e, X, cos_min));
 }
-__global__ __launch_bounds__(256) void k_tri_midpoint(TrackPtrs T, double th_error, double cos_min, double* __restrict__ Xo,
-                                                       double* __restrict__ mse, uint8_t* __restrict__ ok) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= T.n_tracks) return;
-  tri_midpoint_track(T, t, th_error, cos_min, Xo, mse, ok);
-}
 
 // ---- the staged form: 64 tracks per workgroup, observations through LDS ----
 #define TRI_TPB 64      // tracks per workgroup
@@ -437,13 +431,6 @@ __global__ __launch_bounds__(256) void k_tri_dlt(TrackPtrs T, double th_error, d
   ok[t] = !(sqrt(m) > th_error || !track_angle_ok(T, b, e, X, cos_min));
 }
 
-__global__ __launch_bounds__(256) void k_reproject(TrackPtrs T, const double* __restrict__ X, double* __restrict__ mse) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= T.n_tracks) return;
-  const double Xt[3] = {X[3 * (size_t)t], X[3 * (size_t)t + 1], X[3 * (size_t)t + 2]};
-  mse[t] = track_mse(T, T.off[t], T.off[t + 1], Xt);
-}
-
 struct F9 { double f[9]; };
 __global__ __launch_bounds__(256) void k_epipolar(const float* __restrict__ pt1, const float* __restrict__ pt2, int n, F9 F, double th,
                                                    uint8_t* __restrict__ inlier) {
@@ -457,10 +444,6 @@ __global__ __launch_bounds__(256) void k_epipolar(const float* __restrict__ pt1,
 }
 
 // ---- host ----
-static bool tri_staged() {   // MSFM_TRI_STAGED=0: the thread-per-track kernels (comparison)
-  static const bool on = [] { const char* e = getenv("MSFM_TRI_STAGED"); return !(e && atoi(e) == 0); }();
-  return on;
-}
 struct TrackDev {
   DevBuf<int> off, cam;
   DevBuf<double> xy, R, t, c, fk;
@@ -503,8 +486,7 @@ static int triangulate(msfm_ctx* ctx, const msfm_tracks* T, double th_error, dou
   {
     KTimer t(ctx, dlt ? "tri_dlt" : "tri_midpoint");
     if (dlt) hipLaunchKernelGGL(k_tri_dlt, dim3(cdiv(n, 256)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
-    else if (tri_staged()) hipLaunchKernelGGL(k_tri_midpoint_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
-    else hipLaunchKernelGGL(k_tri_midpoint, dim3(cdiv(n, 256)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
+    else hipLaunchKernelGGL(k_tri_midpoint_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(X, dX.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
@@ -519,8 +501,7 @@ static int triangulate(msfm_ctx* ctx, const msfm_tracks* T, double th_error, dou
 int tri_midpoint_dev(msfm_ctx* ctx, const TrackPtrs& T, double th_error, double th_angle, double* dX, double* dmse, uint8_t* dok) {
   if (T.n_tracks == 0) return MSFM_OK;
   KTimer t(ctx, "tri_midpoint");
-  if (tri_staged()) hipLaunchKernelGGL(k_tri_midpoint_staged, dim3(cdiv(T.n_tracks, TRI_TPB)), dim3(256), 0, ctx->stream, T, th_error, cos(th_angle), dX, dmse, dok);
-  else hipLaunchKernelGGL(k_tri_midpoint, dim3(cdiv(T.n_tracks, 256)), dim3(256), 0, ctx->stream, T, th_error, cos(th_angle), dX, dmse, dok);
+  hipLaunchKernelGGL(k_tri_midpoint_staged, dim3(cdiv(T.n_tracks, TRI_TPB)), dim3(256), 0, ctx->stream, T, th_error, cos(th_angle), dX, dmse, dok);
   HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
 }
@@ -549,8 +530,7 @@ MSFM_API int msfm_reproject_mse_batch(msfm_ctx* ctx, const msfm_tracks* T, const
   HIP_TRY(ctx, dX.upload(X, 3 * (size_t)n, s));
   {
     KTimer t(ctx, "tri_reproject");
-    if (tri_staged()) hipLaunchKernelGGL(k_reproject_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, dX.p, dm.p);
-    else hipLaunchKernelGGL(k_reproject, dim3(cdiv(n, 256)), dim3(256), 0, s, D.ptrs, dX.p, dm.p);
+    hipLaunchKernelGGL(k_reproject_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, dX.p, dm.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(mse, dm.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));

@@ -25,8 +25,7 @@ t0 = time.perf_counter()
 res.rerun()
 ctx.synchronize()
 dt = time.perf_counter() - t0
-out["float_descriptors"] = dict(pairs=len(pairs), ms=1e3 * dt, Mmatches_per_s=1e-6 * len(pairs) * 4096 / dt,
-                                path="MSFM_KNN_EXACT=%s" % os.environ.get("MSFM_KNN_EXACT", "0"))
+out["float_descriptors"] = dict(pairs=len(pairs), ms=1e3 * dt, Mmatches_per_s=1e-6 * len(pairs) * 4096 / dt)
 ctx.profile(True); ctx.profile_reset(); res.rerun(); ctx.synchronize(); out["float_kernels"] = ctx.profile_get(); ctx.profile(False)
 out["float_stats"] = res.stats()
 # ---- track building at config 3 scale: every ordered pair's matches of the 500-camera scene (+ 2 % wrong ones) ----
