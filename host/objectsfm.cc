@@ -3,6 +3,7 @@
 
 #include <cstdio>
 #include <fstream>
+#include <iomanip>
 #include <cstdlib>
 #include <limits>
 #include <stdexcept>
@@ -753,6 +754,91 @@ void QueryMatch(const std::string& fold, int idx, std::vector<int>& image_ids,
     std::vector<std::pair<int, int>> mt(num_match);
     for (int i = 0; i < num_match; i++) mt[i] = std::make_pair(tmp[2 * i], tmp[2 * i + 1]);
     match_pts.push_back(mt);
+  }
+}
+
+void SLAMGPS::FeatureMatchingPriors(std::vector<std::vector<int>>& ids, std::vector<std::vector<Mat3>>& Fs,
+                                    std::vector<std::vector<Mat3>>& Hs) {
+  // cams_info (slam_gps.cc:324-327): camera id -> index in cams_; the points' observations in std::map key order
+  std::map<int, int> cams_info;
+  for (size_t i = 0; i < cams_.size(); i++) cams_info.insert(std::make_pair(cams_[i]->id_, (int)i));
+  std::vector<int32_t> off(1, 0), cam;
+  std::vector<double> xy;
+  for (Point3D* p : pts_) {
+    auto it1 = p->pts2d_.begin();
+    for (auto it2 = p->cams_.begin(); it2 != p->cams_.end(); ++it1, ++it2) {
+      cam.push_back(cams_info.find(it2->second->id_)->second);
+      xy.push_back(it1->second.x);
+      xy.push_back(it1->second.y);
+    }
+    off.push_back((int32_t)cam.size());
+  }
+  msfm_tracks t = {};
+  t.n_tracks = (int)pts_.size();
+  t.n_cams = (int)cams_.size();
+  t.track_off = off.data();
+  t.track_cam = cam.data();
+  t.track_xy = xy.data();
+  msfm_slam_prior_options o;
+  msfm_slam_prior_default_options(&o);
+  o.th_epipolar = (float)(2.0 / resize_ratio);   // float th_epipolar = 2.0 / resize_ratio;  (:316)
+  o.th_distance = (float)(5.0 / resize_ratio);   // float th_distance = 5.0 / resize_ratio;  (:317)
+  const size_t cap = std::max<size_t>(1, cams_.size() * (2 * o.win_size - 1));
+  std::vector<int> pairs(2 * cap);
+  std::vector<double> F(9 * cap), H(9 * cap);
+  int n = 0;
+  if (msfm_slam_priors(Context(), &t, &o, &n, pairs.data(), F.data(), H.data(), nullptr, nullptr) != MSFM_OK)
+    throw std::runtime_error(std::string("msfm_slam_priors: ") + msfm_last_error(Context()));
+  ids.assign(cams_.size(), {});
+  Fs.assign(cams_.size(), {});
+  Hs.assign(cams_.size(), {});
+  for (int k = 0; k < n; k++) {
+    Mat3 f, h;
+    for (int q = 0; q < 9; q++) { f.m[q] = F[9 * (size_t)k + q]; h.m[q] = H[9 * (size_t)k + q]; }
+    ids[pairs[2 * k]].push_back(pairs[2 * k + 1]);
+    Fs[pairs[2 * k]].push_back(f);
+    Hs[pairs[2 * k]].push_back(h);
+  }
+}
+
+void SLAMGPS::WriteOutPriorInfo(const std::string& file, const std::vector<std::vector<int>>& ids, const std::vector<std::vector<Mat3>>& Fs,
+                                const std::vector<std::vector<Mat3>>& Hs) {
+  std::ofstream ff(file);
+  ff << std::fixed << std::setprecision(12);
+  ff << ids.size() << std::endl;
+  for (size_t i = 0; i < ids.size(); i++) {
+    ff << ids[i].size() << std::endl;
+    for (size_t j = 0; j < ids[i].size(); j++) {
+      ff << ids[i][j] << " ";
+      for (int m = 0; m < 3; m++)
+        for (int n = 0; n < 3; n++) {
+          ff << Fs[i][j](m, n) << " ";
+          ff << Hs[i][j](m, n) << " ";
+        }
+      ff << std::endl;
+    }
+  }
+}
+
+void SLAMGPS::ReadinPriorInfo(const std::string& file, std::vector<std::vector<int>>& ids, std::vector<std::vector<Mat3>>& Fs,
+                              std::vector<std::vector<Mat3>>& Hs) {
+  std::ifstream ff(file);
+  int num = 0;
+  ff >> num;
+  ids.assign(num, {});
+  Fs.assign(num, {});
+  Hs.assign(num, {});
+  for (int i = 0; i < num; i++) {
+    int n = 0;
+    ff >> n;
+    ids[i].resize(n);
+    Fs[i].resize(n);
+    Hs[i].resize(n);
+    for (int j = 0; j < n; j++) {
+      ff >> ids[i][j];
+      for (int m = 0; m < 3; m++)
+        for (int q = 0; q < 3; q++) ff >> Fs[i][j](m, q) >> Hs[i][j](m, q);
+    }
   }
 }
 

@@ -187,10 +187,23 @@ class IncrementalSfM {
 class SLAMGPS {
  public:
   void FullBundleAdjustment();
+  // SLAMGPS::FeatureMatching step 1 (slam_gps.cc:323-423) through msfm_slam_priors: camera i's kept window partners ids[i]
+  // (ascending) with the prior F / H of each (row-major [9]), from pts_ (observations in std::map key order) over cams_.
+  // Window and thresholds of :314-319: win 5, 20 shared points, th_epipolar = 2.0 / resize_ratio, th_distance =
+  // 5.0 / resize_ratio (binary32, as the reference's `float` locals), th_ratio_f 0.5, th_h_f_ratio 0.90.
+  void FeatureMatchingPriors(std::vector<std::vector<int>>& ids, std::vector<std::vector<Mat3>>& Fs, std::vector<std::vector<Mat3>>& Hs);
+  // feature/prior.txt (slam_gps.cc:1821-1885): the camera count, per camera n and n lines `id F00 H00 F01 H01 ... F22 H22`
+  static void WriteOutPriorInfo(const std::string& file, const std::vector<std::vector<int>>& ids, const std::vector<std::vector<Mat3>>& Fs,
+                                const std::vector<std::vector<Mat3>>& Hs);
+  static void ReadinPriorInfo(const std::string& file, std::vector<std::vector<int>>& ids, std::vector<std::vector<Mat3>>& Fs,
+                              std::vector<std::vector<Mat3>>& Hs);
   std::vector<Camera*> cams_;
   std::vector<CameraModel*> cam_models_;
   std::vector<Point3D*> pts_;
   std::vector<Vec3> cams_gps_;               // cv::Point3d cams_gps_ (slam_gps.h)
+  // slam_gps.h:135, set to 0.5 by SLAMGPS::SLAMGPS (slam_gps.cc:55): the SLAM observations are stored at full resolution,
+  // (px - cx) / resize_ratio (:199), and step 1's pixel thresholds scale with it (:316-317)
+  double resize_ratio = 0.5;
   bool minimizer_progress_to_stdout_ = true; // slam_gps.cc:682
   msfm_ba_summary summary_;
   std::vector<msfm_ba_iteration> iterations_;

@@ -396,6 +396,72 @@ void msfm_fransac_default_options(msfm_fransac_options* opt);
 int msfm_fundamental_ransac_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1,
                                   const float* pt2, const msfm_fransac_options* opt, double* F,
                                   uint8_t* inlier, int* n_inliers, uint8_t* ok);
+/* cv::findHomography(pts1, pts2, mask, RANSAC, th) of OpenCV 2.4 (cvFindHomography + CvHomographyEstimator), batched over
+ * image pairs: the prior homography of SLAMGPS::FeatureMatching step 1 (SfM/src/slam_gps.cc:402).  4-point samples with
+ * OpenCV's collinearity check (300 attempts), error = binary32 squared transfer distance into image 2 <= threshold^2, at most
+ * max_iterations samples with the adaptive stop of cvRANSACUpdateNumIters (confidence 0.995, 4 model points), then (polish)
+ * a refit on the inliers and 10 Levenberg-Marquardt iterations, as cvFindHomography does.  The sampler is counter based:
+ * sample h of pair p (its index in this call) depends only on (seed, p, h).  Pair p owns correspondences
+ * [offsets[p], offsets[p+1]); pt1 / pt2 are cv::Point2f pairs, H maps pt1 to pt2.
+ * Out: H[p][9] row-major with H[8] = 1 (zeros when no model), inlier[total] = the RANSAC mask of the best sample's model
+ * (not recomputed after the polish), n_inliers[p], ok[p] = cvFindHomography's result.  N == 4: the direct fit, mask all
+ * ones; N < 4: ok = 0, mask 0; no model found: ok = 0, H = 0 and the mask all ONES (cvFindHomography's temporary mask starts
+ * at ones and is written back only when a model was found), so n_inliers = N.
+ * Departure at N == 4: the direct fit is the exact 8x9 null space, and a rank-deficient system (e.g. four collinear points)
+ * or a non-finite H gives ok = 0; OpenCV's runKernel (LtL eigenvector) returns 1 for any set whose spreads are
+ * >= DBL_EPSILON, with whatever H that eigenvector gives.
+ * MSFM_E_INVAL: max_iterations outside [1, 65536], confidence outside (0, 1), offsets not starting at 0 or decreasing. */
+typedef struct msfm_hransac_options {
+  double threshold;   /* 3.0   ransacReprojThreshold (<= 0 -> 3.0, as OpenCV does)                               */
+  double confidence;  /* 0.995 fixed inside cvFindHomography                                                     */
+  int max_iterations; /* 2000  fixed inside cvFindHomography                                                     */
+  int polish;         /* 1: refit on the inliers + 10-iteration LM refine, as cvFindHomography does;
+                         0: the best sample's model as found                                                     */
+  uint64_t seed;
+} msfm_hransac_options;
+void msfm_hransac_default_options(msfm_hransac_options* opt);
+int msfm_homography_ransac_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
+                                 const msfm_hransac_options* opt, double* H /*[n][9]*/, uint8_t* inlier /*[total]*/,
+                                 int* n_inliers, uint8_t* ok);
+
+/* SLAMGPS::FeatureMatching step 1 (SfM/src/slam_gps.cc:323-423) in one call: the matching graph of a SLAM run and the prior
+ * F and H of every kept image pair, which msfm_match_pairs_slam (step 2) takes.  For camera i ascending and j ascending
+ * over [max(i - win_size, 0), min(i + win_size, n_cams)), j != i (:348-357; offsets -win_size .. win_size - 1):
+ *   shared   the SLAM points seen by both cameras, ascending point index (math::same_in_vectors, :330-340, :360-364);
+ *            fewer than th_same_pts -> skipped (verdict 1)
+ *   pts1/2   their observations in i / j as cv::Point2f (binary32, :365-382)
+ *   F        msfm_fundamental_ransac_batch (cv::findFundamentalMat(FM_RANSAC, th_epipolar), :385-393) over the list of the
+ *            candidates with enough shared points (sampler index = position in that list, confidence 0.99, 2000 samples,
+ *            seed_f); rejected if (float)n_f < (float)n * th_ratio_f or n_f < 30 (:396, binary32; verdict 2)
+ *   H        msfm_homography_ransac_batch (cv::findHomography(RANSAC, th_distance), :400-408) on the same list (seed_h,
+ *            default options otherwise); rejected if (float)n_h > (float)n_f * th_h_f_ratio (:409, binary32; verdict 3)
+ *   kept     (i, j, F, H) in (i, j) order (:411-415) - exactly the pairs / F / H of msfm_match_pairs_slam.
+ * H is not run for candidates the F gate rejects (their candidate row says -1); kept results do not depend on it.
+ * A candidate whose F RANSAC finds no model has n_f = 0 (msfm_fundamental_ransac_batch's mask is 0 then) and verdict 2;
+ * cvFindFundamentalMat would leave its mask at all ones, so the reference counts n_f = N there - a rare departure that the
+ * composition of the public calls defines.
+ * The SLAM points come as msfm_tracks: n_tracks points, n_cams cameras, track_off / track_cam / track_xy (cam_* unused, may
+ * be NULL).  MSFM_E_INVAL: two observations of one point in one camera (pts1 / pts2 would not line up), a camera outside
+ * [0, n_cams), win_size < 1, th_same_pts < 15 (below 15 OpenCV 2.4's findFundamentalMat does not run RANSAC),
+ * th_epipolar <= 0 or NaN and th_distance NaN (what the two public calls refuse; th_distance <= 0 means 3.0, as there).
+ * The default thresholds are those of resize_ratio = 1; SLAMGPS::SLAMGPS sets resize_ratio = 0.5 (slam_gps.cc:55), so a
+ * reference run uses th_epipolar = 4 and th_distance = 10 px on observations stored at full resolution (:199).
+ * cap = n_cams * (2 * win_size - 1) bounds both outputs.  Out: n_pairs kept pairs [cap][2], F / H [cap][9]; candidates (may
+ * be NULL) [cap][6] = i, j, n_shared, n_inliers_f, n_inliers_h (-1: not run), verdict (0 kept, 1 shared, 2 F gate, 3 H gate)
+ * for every window slot in (i, j) order, *n_candidates rows. */
+typedef struct msfm_slam_prior_options {
+  int win_size;        /* 5    slam_gps.cc:314 */
+  int th_same_pts;     /* 20   :315            */
+  float th_epipolar;   /* 2.0 / resize_ratio  :316 */
+  float th_distance;   /* 5.0 / resize_ratio  :317 */
+  float th_ratio_f;    /* 0.5  :318 */
+  float th_h_f_ratio;  /* 0.90 :319 */
+  uint64_t seed_f, seed_h;
+} msfm_slam_prior_options;
+void msfm_slam_prior_default_options(msfm_slam_prior_options* opt);
+int msfm_slam_priors(msfm_ctx* ctx, const msfm_tracks* points, const msfm_slam_prior_options* opt, int* n_pairs,
+                     int* pairs, double* F, double* H, int* n_candidates, int* candidates);
+
 /* The closed-form filter above for many pairs at once (fine_matching_graph.cc:148-150: applied to the
  * "all" match set only when the pair's RANSAC succeeded): pairs with ok[p] == 0 get all-zero masks
  * (ok may be NULL = every pair). */

@@ -42,6 +42,18 @@ class FransacOptions(C.Structure):
                 ("min_points", C.c_int), ("min_inliers", C.c_int), ("seed", C.c_uint64)]
 
 
+class HransacOptions(C.Structure):
+    """msfm_hransac_options (include/msfm.h)."""
+    _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int), ("polish", C.c_int),
+                ("seed", C.c_uint64)]
+
+
+class SlamPriorOptions(C.Structure):
+    """msfm_slam_prior_options (include/msfm.h)."""
+    _fields_ = [("win_size", C.c_int), ("th_same_pts", C.c_int), ("th_epipolar", C.c_float), ("th_distance", C.c_float),
+                ("th_ratio_f", C.c_float), ("th_h_f_ratio", C.c_float), ("seed_f", C.c_uint64), ("seed_h", C.c_uint64)]
+
+
 class SlamMatchOptions(C.Structure):
     """msfm_slam_match_options (include/msfm.h)."""
     _fields_ = [("th_first_second_ratio", C.c_float), ("th_epipolar", C.c_float), ("th_distance", C.c_float)]

@@ -27,7 +27,8 @@ SYMBOLS = [
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
     "msfm_epipolar_filter", "msfm_fransac_default_options", "msfm_fundamental_ransac_batch",
-    "msfm_epipolar_filter_batch", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
+    "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
+    "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
     "msfm_epnp_ransac_batch", "msfm_relpose_5pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
     "msfm_ctx_create_multi", "msfm_multi_destroy", "msfm_multi_size", "msfm_multi_ctx", "msfm_multi_last_error", "msfm_multi_ba_solve",
     "msfm_multi_triangulate_midpoint_batch", "msfm_multi_triangulate_dlt_batch", "msfm_multi_reproject_mse_batch", "msfm_multi_match_pairs",
@@ -98,6 +99,14 @@ def lib():
     L.msfm_fransac_default_options.restype = None
     L.msfm_fundamental_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, C.POINTER(A.FransacOptions),
                                                 A.c_double_p, A.c_u8_p, A.c_int_p, A.c_u8_p]
+    L.msfm_hransac_default_options.argtypes = [C.POINTER(A.HransacOptions)]
+    L.msfm_hransac_default_options.restype = None
+    L.msfm_homography_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, C.POINTER(A.HransacOptions),
+                                               A.c_double_p, A.c_u8_p, A.c_int_p, A.c_u8_p]
+    L.msfm_slam_prior_default_options.argtypes = [C.POINTER(A.SlamPriorOptions)]
+    L.msfm_slam_prior_default_options.restype = None
+    L.msfm_slam_priors.argtypes = [vp, C.POINTER(A.Tracks), C.POINTER(A.SlamPriorOptions), C.POINTER(i), A.c_int_p, A.c_double_p,
+                                   A.c_double_p, C.POINTER(i), A.c_int_p]
     L.msfm_epipolar_filter_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, A.c_double_p, A.c_u8_p, d, A.c_u8_p]
     L.msfm_epnp_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64, A.c_double_p,
                                          A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p]
@@ -204,6 +213,26 @@ def build_tracks_flat(n_features, pairs, match_off, matches):
 def fransac_options(**kw):
     o = A.FransacOptions()
     lib().msfm_fransac_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def hransac_options(**kw):
+    o = A.HransacOptions()
+    lib().msfm_hransac_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def slam_prior_options(**kw):
+    o = A.SlamPriorOptions()
+    lib().msfm_slam_prior_default_options(C.byref(o))
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
@@ -375,6 +404,45 @@ class Context:
                                                        A.ptr(pt2, A.c_float_p), C.byref(o), A.ptr(F, A.c_double_p),
                                                        A.ptr(inl, A.c_u8_p), A.ptr(nin, A.c_int_p), A.ptr(ok, A.c_u8_p)))
         return F, inl[:len(pt1)], nin[:n_pairs], ok[:n_pairs]
+
+    def homography_ransac(self, offsets, pt1, pt2, **opts):
+        """cv::findHomography(pt1, pt2, mask, RANSAC, threshold) for a batch of pairs (slam_gps.cc:402).
+        offsets[n_pairs+1] delimit each pair's correspondences in pt1/pt2 (float32 [total][2]).
+        Returns H [n_pairs][3][3] (H[2,2] = 1, zeros when no model), inlier mask [total], n_inliers [n_pairs], ok [n_pairs]."""
+        offsets = A.as_c(offsets, np.int32)
+        pt1 = A.as_c(np.asarray(pt1, dtype=np.float32).reshape(-1, 2), np.float32)
+        pt2 = A.as_c(np.asarray(pt2, dtype=np.float32).reshape(-1, 2), np.float32)
+        n_pairs = len(offsets) - 1
+        o = hransac_options(**opts)
+        H = np.zeros((max(1, n_pairs), 3, 3), dtype=np.float64)
+        inl = np.zeros(max(1, len(pt1)), dtype=np.uint8)
+        nin = np.zeros(max(1, n_pairs), dtype=np.int32)
+        ok = np.zeros(max(1, n_pairs), dtype=np.uint8)
+        self.check(lib().msfm_homography_ransac_batch(self._h, n_pairs, A.ptr(offsets, A.c_int_p), A.ptr(pt1, A.c_float_p),
+                                                      A.ptr(pt2, A.c_float_p), C.byref(o), A.ptr(H, A.c_double_p),
+                                                      A.ptr(inl, A.c_u8_p), A.ptr(nin, A.c_int_p), A.ptr(ok, A.c_u8_p)))
+        return H[:n_pairs], inl[:len(pt1)], nin[:n_pairs], ok[:n_pairs]
+
+    def slam_priors(self, n_cams, track_off, track_cam, track_xy, **opts):
+        """SLAMGPS::FeatureMatching step 1 (slam_gps.cc:323-423): the SLAM points as CSR tracks (track_off [n+1], track_cam,
+        track_xy [obs][2]) of n_cams cameras.  Returns (pairs [k][2], F [k][3][3], H [k][3][3], candidates [slots][6] =
+        i, j, n_shared, n_inliers_f, n_inliers_h, verdict) - pairs / F / H are what match_pairs_slam takes."""
+        o = slam_prior_options(**opts)
+        toff = A.as_c(np.asarray(track_off, dtype=np.int32), np.int32)
+        tcam = A.as_c(np.asarray(track_cam, dtype=np.int32).reshape(-1), np.int32)
+        txy = A.as_c(np.asarray(track_xy, dtype=np.float64).reshape(-1, 2), np.float64)
+        t = A.Tracks()
+        t.n_tracks, t.n_cams = len(toff) - 1, int(n_cams)
+        t.track_off, t.track_cam, t.track_xy = A.ptr(toff, A.c_int_p), A.ptr(tcam, A.c_int_p), A.ptr(txy, A.c_double_p)
+        cap = max(1, int(n_cams) * (2 * max(1, o.win_size) - 1))
+        pairs = np.zeros((cap, 2), dtype=np.int32)
+        F = np.zeros((cap, 3, 3)); H = np.zeros((cap, 3, 3))
+        cand = np.zeros((cap, 6), dtype=np.int32)
+        n, nc = C.c_int(0), C.c_int(0)
+        self.check(lib().msfm_slam_priors(self._h, C.byref(t), C.byref(o), C.byref(n), A.ptr(pairs, A.c_int_p), A.ptr(F, A.c_double_p),
+                                          A.ptr(H, A.c_double_p), C.byref(nc), A.ptr(cand, A.c_int_p)))
+        k = n.value
+        return pairs[:k], F[:k], H[:k], cand[:nc.value]
 
     def epnp_ransac(self, offsets, pts_w, pts_2d, f, max_iter=200, seed=0x4D53464D50):
         """AbsolutePoseEstimation::AbsolutePoseWithFocalLength for a batch of images (absolute_pose_estimation.cc:42-58):

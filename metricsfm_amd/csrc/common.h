@@ -190,6 +190,11 @@ static inline void par_ranges(size_t n, int nt, F&& fn, size_t grain = 4096) {  
 struct msfm_fransac_options;
 int geo_fransac_dev(msfm_ctx* ctx, int n_pairs, const int* h_offsets, const int* d_off, const float* d1, const float* d2,
                     const msfm_fransac_options* opt, double* dF, uint8_t* d_in, int* d_nin, uint8_t* d_ok);
+struct msfm_hransac_options;
+// active (host, may be NULL): pairs with active[p] == 0 are skipped (no model); the sampler index of pair p stays p
+int geo_hransac_dev(msfm_ctx* ctx, int n_pairs, const int* h_offsets, const int* d_off, const float* d1, const float* d2,
+                    const msfm_hransac_options* opt, const uint8_t* active, double* dH, uint8_t* d_in, int* d_nin, uint8_t* d_ok);
+int geo_hransac_check(msfm_ctx* ctx, int n_pairs, const int* h_offsets, const msfm_hransac_options* opt);
 int geo_epipolar_batch_dev(msfm_ctx* ctx, int total, const int* d_pair_of, const float* d1, const float* d2, const double* dF,
                            const uint8_t* d_ok, double th, uint8_t* d_in);
 struct msfm_track_dev {   // CSR tracks on the device: observations of a track in ascending image order

@@ -6,6 +6,9 @@ be consumed by the unmodified incremental pipeline and vice versa.
                                 read back by Graph::QueryMatch, SfM/src/graph.cc:92-137)
   <output_fold>/graph_matching.txt   text, N rows of N counts separated by ' ', each row ends with ' \\n'
                                (WriteOutMatchGraph, fine_matching_graph.cc:275-292; Graph::ReadinMatchingGraph, graph.cc:72-85)
+  <fold>/feature/prior.txt     text, the prior F / H of SLAMGPS::FeatureMatching step 1: the camera count, then per camera
+                               i a line with n and n lines `j F00 H00 F01 H01 ... F22 H22 ` (std::fixed, 12 decimals)
+                               (SLAMGPS::WriteOutPriorInfo / ReadinPriorInfo, SfM/src/slam_gps.cc:1821-1885)
 Native little-endian ints, as the reference writes them with ofstream::write.
 """
 import os
@@ -67,3 +70,36 @@ def codes_to_matches(code):
     in_all = (code[m2] & A.MSFM_MATCH_NOT_ALL) == 0      # the two ratio tests are independent (:118-130)
     allm = np.column_stack([m1, m2])
     return allm[good], allm[in_all]
+
+
+def write_prior_info(path, n_cams, pairs, F, H):
+    """SLAMGPS::WriteOutPriorInfo (slam_gps.cc:1821-1847) of the kept pairs of step 1: pairs [k][2] = (i, j) grouped by i
+    (the order msfm_slam_priors returns), F / H [k][3][3]."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    F = np.asarray(F, dtype=np.float64).reshape(-1, 9)
+    H = np.asarray(H, dtype=np.float64).reshape(-1, 9)
+    rows = [[] for _ in range(int(n_cams))]
+    for (i, j), f, h in zip(pairs, F, H):
+        rows[int(i)].append((int(j), f, h))
+    out = ["%d\n" % int(n_cams)]
+    for r in rows:
+        out.append("%d\n" % len(r))
+        for j, f, h in r:
+            out.append("%d " % j + "".join("%.12f %.12f " % (f[k], h[k]) for k in range(9)) + "\n")
+    with open(path, "w") as fh:
+        fh.write("".join(out))
+
+
+def read_prior_info(path):
+    """SLAMGPS::ReadinPriorInfo (slam_gps.cc:1849-1885) -> (n_cams, pairs [k][2], F [k][3][3], H [k][3][3]) in file order."""
+    tok = open(path).read().split()
+    p = 0
+    n_cams = int(tok[p]); p += 1
+    pairs, F, H = [], [], []
+    for i in range(n_cams):
+        n = int(tok[p]); p += 1
+        for _ in range(n):
+            j = int(tok[p]); p += 1
+            v = np.array(tok[p:p + 18], dtype=np.float64); p += 18
+            pairs.append((i, j)); F.append(v[0::2].reshape(3, 3)); H.append(v[1::2].reshape(3, 3))
+    return (n_cams, np.array(pairs, dtype=np.int32).reshape(-1, 2), np.array(F).reshape(-1, 3, 3), np.array(H).reshape(-1, 3, 3))
