@@ -291,8 +291,14 @@ typedef struct msfm_ba_layout {
   int fold_slots, fold_passes;
   long long mc_entries, mc_entries_folded;
   int fold_mc_slots;
-  int reserved_;
+  /* how the last factorisation of msfm_ba_run ran (0 before the first one): MSFM_PATH_LEVEL_CHAIN(l) = tree level l as one
+   * persistent k_chain launch, MSFM_PATH_ROOT_CHAIN = the root chain as one, MSFM_PATH_BACKSOLVE_CHAIN = the back
+   * substitution as one k_backsolve_chain launch; a clear bit = one launch per 64-column panel / block pair */
+  int solve_paths;
 } msfm_ba_layout;
+#define MSFM_PATH_LEVEL_CHAIN(l) (1 << (l))
+#define MSFM_PATH_ROOT_CHAIN (1 << 3)
+#define MSFM_PATH_BACKSOLVE_CHAIN (1 << 4)
 int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out);
 
 /* The elimination order of msfm_ba_create as a host-only function (no device, no context: a diagnostic for tests and for

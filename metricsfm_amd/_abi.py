@@ -14,6 +14,14 @@ MSFM_MATCH_GOOD = 0x40000000
 MSFM_MATCH_NOT_ALL = 0x20000000
 MSFM_MATCH_ID_MASK = 0x1FFFFFFF
 MSFM_MAX_KERNEL_STATS = 32
+# msfm_ba_layout.solve_paths
+MSFM_PATH_ROOT_CHAIN = 1 << 3
+MSFM_PATH_BACKSOLVE_CHAIN = 1 << 4
+
+
+def MSFM_PATH_LEVEL_CHAIN(level):
+    return 1 << level
+
 
 TERMINATION = {1: "CONVERGENCE_FUNCTION", 2: "CONVERGENCE_GRADIENT", 3: "CONVERGENCE_PARAMETER",
                4: "NO_CONVERGENCE", 5: "FAILURE", 6: "MIN_RADIUS"}
@@ -33,7 +41,7 @@ class BaLayout(C.Structure):
                 ("separator_cols", C.c_int), ("panel_launches", C.c_int), ("n_levels", C.c_int), ("level_nodes", C.c_int * 3),
                 ("level_begin", C.c_int * 3), ("root_cols", C.c_int),
                 ("cc_entries", C.c_longlong), ("cc_entries_folded", C.c_longlong), ("fold_slots", C.c_int), ("fold_passes", C.c_int),
-                ("mc_entries", C.c_longlong), ("mc_entries_folded", C.c_longlong), ("fold_mc_slots", C.c_int), ("reserved_", C.c_int)]
+                ("mc_entries", C.c_longlong), ("mc_entries_folded", C.c_longlong), ("fold_mc_slots", C.c_int), ("solve_paths", C.c_int)]
 
 
 class FransacOptions(C.Structure):

@@ -1641,6 +1641,7 @@ struct msfm_ba {
   DevBuf<int> cb_off, padcol;
   DevBuf<double> zsys, corners;
   int zflip = 0;   // which half of zsys the next solve writes (the other half is being marked "pending" meanwhile)
+  int solve_paths = 0;   // MSFM_PATH_* of the last factorisation (msfm_ba_layout.solve_paths)
   int A = 0, AE = 0, NCR = 0, NPM = 0;
   bool has_gps = false;
   double gps_weight = 0;
@@ -3807,6 +3808,7 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
     out->fold_passes = ba->fold.n_pass;
     if (ba->fold.mc_on) { out->mc_entries_folded = ba->fold.mc_entries_folded; out->fold_mc_slots = ba->fold.n_diag; }
   }
+  out->solve_paths = ba->solve_paths;
   return MSFM_OK;
 }
 
@@ -4191,7 +4193,7 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     double* const zcur = ba->zsys.p + (size_t)ba->zflip * (ba->npad + 8);
     double* const znext = ba->zsys.p + (size_t)(ba->zflip ^ 1) * (ba->npad + 8);
     const int rc = msfm_chol_factor_solve(ctx, ba->env, ba->M.p, ba->npad, ba->nsys, ba->Linv.p, ba->w.p, zcur, ba->fail.p,
-                                          ba->plan.n_levels > 0 ? &ba->plan : nullptr, znext, ba->chol_ws);
+                                          ba->plan.n_levels > 0 ? &ba->plan : nullptr, znext, ba->chol_ws, &ba->solve_paths);
     if (rc != MSFM_OK) {
       // the call may have stopped before the solve kernel marked znext: neither half can be trusted to be "pending"
       // any more (a stale half would be taken for published values by the next solve) - mark both again

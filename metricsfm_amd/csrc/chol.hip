@@ -2053,7 +2053,8 @@ static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int n
 // state - the two buffers alternate from solve to solve and no fill launch sits on the critical path.  Without it the
 // function fills z itself first.
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
-                           const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws) {
+                           const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws, int* paths) {
+  if (paths) *paths = 0;   // (a call that fails reports no path)
   if (!M || !work || !w || !z || !fail || npad % NB != 0 || n < 1 || n + 1 > npad)
     return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad workspace (null buffer or size)");
   hipStream_t s = ctx->stream;
@@ -2061,10 +2062,10 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
   double* Dinv = work;
   double* Linv = work + (size_t)npad * 16;
   double* Ldiag = work + (size_t)npad * 80;
-  int t_first = 0;
+  int t_first = 0, ran = 0;   // ran: the MSFM_PATH_* bits of this call
   const int n_levels = plan ? plan->n_levels : 0;
   // the persistent chain (one launch per tree level) when the caller keeps a workspace for it; MSFM_CHOL_LAUNCHES=1: the
-  // round-3 chain of one launch per 64-column panel, for comparison
+  // round-3 chain of one launch per 64-column panel and the back substitution by block pairs, for comparison
   bool use_chain = ws && !env.chol_launches && ws->npad == npad && ws->capacity > 0 && (size_t)npad * npad * sizeof(double) < 0xFFFFFFFFull;   // (32-bit buffer offsets)
   if (use_chain) {
     MSFM_TRY(chain_build(ws, n, plan, env.chain_force));
@@ -2118,6 +2119,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
       if (lv_chain) {
         MSFM_TRY(chain_launch(ws, ws->launch[lv], M, npad, n, Dinv, Ldiag, fail, ldc, env.chain_trace));
         chain_timer.count = ws->launch[lv].steps;   // (counted in panel steps, so that a step's time compares with the launch chain's)
+        ran |= MSFM_PATH_LEVEL_CHAIN(lv);
       }
       for (int l = 0; l < maxp && !lv_chain; l++) {
         PanelJobs jobs;
@@ -2169,6 +2171,7 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
   if (root_chain) {
     MSFM_TRY(chain_launch(ws, ws->launch[n_levels], M, npad, n, Dinv, Ldiag, fail, 0, env.chain_trace));
     root_timer.count = ws->launch[n_levels].steps;
+    ran |= MSFM_PATH_ROOT_CHAIN;
   }
   for (int t0 = t_first; t0 < n && !root_chain; t0 += NB) {
     // the separator (or the whole matrix): one job per launch, its first block has nothing left to apply
@@ -2196,7 +2199,8 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
       cmax = std::max(1, std::min(MSFM_BACKSOLVE_CHAIN_MAX, resident_workgroups(ctx, k_backsolve_chain, 256)));
       chain_max[ctx->device & 63].store(cmax, std::memory_order_relaxed);
     }
-    const bool chain = nblk <= cmax;   // (otherwise the round-2 chain of launches)
+    const bool chain = nblk <= cmax && !env.chol_launches;   // (otherwise the round-2 chain of launches)
+    if (chain) ran |= MSFM_PATH_BACKSOLVE_CHAIN;
     if (!chain) hipLaunchKernelGGL(k_trinv64_full, dim3(nblk + cdiv(npad, 256)), dim3(256), 0, s, Ldiag, n, Dinv, Linv, nblk, M, npad, w, npad,
                                    (unsigned long long*)nullptr);
     if (chain) {
@@ -2277,5 +2281,6 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
     if (ws) ws->dirty = true;
     return msfm_set_error(ctx, MSFM_E_DEVICE, "cholesky launch: %s", hipGetErrorString(e));
   }
+  if (paths) *paths = ran;
   return MSFM_OK;
 }

@@ -253,7 +253,8 @@ struct msfm_chol_plan {
 struct msfm_chol_ws;   // hand-off state of the persistent panel chain (chol.hip): flags, hand-off buffers, ticket counters
 int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out);
 void msfm_chol_ws_destroy(msfm_chol_ws* ws);
-// env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE)
+// env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE); paths (optional): the
+// MSFM_PATH_* bits of msfm_ba_layout.solve_paths for the launches this call enqueued
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
-                           const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr);
+                           const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr, int* paths = nullptr);
 int msfm_chol_fill_pending(msfm_ctx* ctx, double* z, int npad);   // "not solved yet" marks of k_backsolve_chain

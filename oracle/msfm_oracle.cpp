@@ -1082,8 +1082,10 @@ ORC_API int orc_ba_solve(msfm_ba_problem* P, const msfm_ba_options* options, msf
 // One linearisation + reduced system, exported for kernel-level parity tests:
 // fills S (nred x nred, upper triangle valid, row-major), rhs (nred), and the point-space
 // quantities; returns nred.  radius is the trust-region radius the LM diagonal uses.
+// scale (optional, nred): the Jacobi scale of the reduced columns (cameras, then intrinsics; 1 without jacobi_scaling) -
+// a step y of S y = rhs moves the parameters by -y * scale.
 ORC_API int orc_ba_reduced_system(msfm_ba_problem* P, const msfm_ba_options* options, double radius,
-                                  double* S, double* rhs, int cap, double* cost, double* gmax) {
+                                  double* S, double* rhs, int cap, double* cost, double* gmax, double* scale) {
   Ba B; B.P = P; B.opt = *options;
   ba_setup(B);
   const double c = ba_evaluate(B, B.cam, B.model, B.pt, true);
@@ -1102,6 +1104,10 @@ ORC_API int orc_ba_reduced_system(msfm_ba_problem* P, const msfm_ba_options* opt
   const int n = B.nred;
   memcpy(S, B.lhs.data(), sizeof(double) * (size_t)n * n);
   for (int i = 0; i < n; i++) rhs[i] = B.rhs[i];
+  if (scale) {
+    std::copy(B.scale_c.begin(), B.scale_c.end(), scale);
+    std::copy(B.scale_m.begin(), B.scale_m.end(), scale + B.scale_c.size());
+  }
   return n;
 }
 

@@ -35,7 +35,7 @@ def lib():
         _lib.orc_ba_solve.argtypes = [C.POINTER(A.BaProblem), C.POINTER(A.BaOptions), C.POINTER(A.BaSummary)]
         _lib.orc_ba_options_default.argtypes = [C.POINTER(A.BaOptions)]
         _lib.orc_ba_reduced_system.argtypes = [C.POINTER(A.BaProblem), C.POINTER(A.BaOptions), C.c_double,
-                                               A.c_double_p, A.c_double_p, C.c_int, A.c_double_p, A.c_double_p]
+                                               A.c_double_p, A.c_double_p, C.c_int, A.c_double_p, A.c_double_p, A.c_double_p]
         for f in (_lib.orc_triangulate_midpoint_batch, _lib.orc_triangulate_dlt_batch):
             f.argtypes = [C.POINTER(A.Tracks), C.c_double, C.c_double, A.c_double_p, A.c_double_p, A.c_u8_p]
         _lib.orc_reproject_mse_batch.argtypes = [C.POINTER(A.Tracks), A.c_double_p, A.c_double_p]
@@ -110,17 +110,22 @@ def ba_solve(arrays: A.BaArrays, options=None, capacity=512):
     return buf.result()
 
 
-def ba_reduced_system(arrays: A.BaArrays, radius=1e4, options=None):
+def ba_reduced_system(arrays: A.BaArrays, radius=1e4, options=None, with_scale=False):
+    """S (upper triangle valid), rhs, cost and max-norm of the gradient at the arrays' parameters; with_scale=True appends
+    the Jacobi scale of the reduced columns (a step y of S y = rhs moves the parameters by -y * scale)."""
     options = options or default_options()
     n = 6 * arrays.struct.n_cams + 3 * arrays.struct.n_models
-    S = np.zeros((n, n))
+    S = np.empty((n, n))
     rhs = np.zeros(n)
+    scale = np.zeros(n) if with_scale else None
     cost, gmax = C.c_double(), C.c_double()
     m = lib().orc_ba_reduced_system(C.byref(arrays.struct), C.byref(options), radius, A.ptr(S, A.c_double_p),
-                                    A.ptr(rhs, A.c_double_p), n, C.byref(cost), C.byref(gmax))
+                                    A.ptr(rhs, A.c_double_p), n, C.byref(cost), C.byref(gmax), A.ptr(scale, A.c_double_p))
     if m < 0:
         raise RuntimeError("capacity")
     S = S.reshape(-1)[: m * m].reshape(m, m)
+    if with_scale:
+        return S, rhs[:m], cost.value, gmax.value, scale[:m]
     return S, rhs[:m], cost.value, gmax.value
 
 

@@ -37,15 +37,20 @@ def test_every_declared_symbol_is_exported_and_bound():
 
 def test_struct_layouts_match_the_c_compiler(tmp_path):
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu\\n",'
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu '
+                   '%zu %zu %zu %d %d %d %d\\n",'
                    'sizeof(msfm_ba_problem),sizeof(msfm_ba_options),sizeof(msfm_ba_iteration),sizeof(msfm_ba_summary),'
                    'sizeof(msfm_tracks),sizeof(msfm_kernel_stat),offsetof(msfm_ba_problem,gps_weight),'
-                   'offsetof(msfm_ba_summary,solve_ms),offsetof(msfm_ba_options,jacobi_scaling));return 0;}\n')
+                   'offsetof(msfm_ba_summary,solve_ms),offsetof(msfm_ba_options,jacobi_scaling),'
+                   'sizeof(msfm_ba_layout),offsetof(msfm_ba_layout,fold_mc_slots),offsetof(msfm_ba_layout,solve_paths),'
+                   'MSFM_PATH_LEVEL_CHAIN(0),MSFM_PATH_LEVEL_CHAIN(2),MSFM_PATH_ROOT_CHAIN,MSFM_PATH_BACKSOLVE_CHAIN);return 0;}\n')
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
     want = [C.sizeof(A.BaProblem), C.sizeof(A.BaOptions), C.sizeof(A.BaIteration), C.sizeof(A.BaSummary), C.sizeof(A.Tracks),
-            C.sizeof(A.KernelStat), A.BaProblem.gps_weight.offset, A.BaSummary.solve_ms.offset, A.BaOptions.jacobi_scaling.offset]
+            C.sizeof(A.KernelStat), A.BaProblem.gps_weight.offset, A.BaSummary.solve_ms.offset, A.BaOptions.jacobi_scaling.offset,
+            C.sizeof(A.BaLayout), A.BaLayout.fold_mc_slots.offset, A.BaLayout.solve_paths.offset,
+            A.MSFM_PATH_LEVEL_CHAIN(0), A.MSFM_PATH_LEVEL_CHAIN(2), A.MSFM_PATH_ROOT_CHAIN, A.MSFM_PATH_BACKSOLVE_CHAIN]
     assert got == want
 
 
