@@ -567,6 +567,39 @@ void AbsolutePoseBatch(const std::vector<std::vector<Vec3>>& pts_w, const std::v
   }
 }
 
+// AbsolutePoseEstimation::AbsolutePoseWithoutFocalLength (absolute_pose_estimation.cc:28-40) for many images: the EPNPF sweep
+// over (0.5 + 0.01 i) * f_estimated, i < 350, 200 samples each (absolute_pose_via_epnpf.cc:34-63), then Error at the kept focal
+// length.  f_out[p] is what the caller hands to SetFocalLength once avg_error passes th_mse_localization (sfm_incremental.cc:673-704).
+void AbsolutePoseWithoutFocalLengthBatch(const std::vector<std::vector<Vec3>>& pts_w, const std::vector<std::vector<Vec2>>& pts_2d,
+                                         const std::vector<double>& f_estimated, std::vector<double>& f_out, std::vector<RTPose>& poses,
+                                         std::vector<std::vector<double>>& errors, std::vector<double>& avg_error) {
+  const int n = (int)pts_w.size();
+  std::vector<int> off(n + 1, 0);
+  for (int p = 0; p < n; p++) off[p + 1] = off[p] + (int)pts_w[p].size();
+  std::vector<double> X(3 * (size_t)std::max(1, off[n])), x(2 * (size_t)std::max(1, off[n])), R(9 * (size_t)std::max(1, n)),
+      t(3 * (size_t)std::max(1, n)), err(std::max(1, off[n]));
+  for (int p = 0; p < n; p++)
+    for (size_t i = 0; i < pts_w[p].size(); i++) {
+      const size_t e = off[p] + i;
+      for (int k = 0; k < 3; k++) X[3 * e + k] = pts_w[p][i][k];
+      x[2 * e] = pts_2d[p][i].x; x[2 * e + 1] = pts_2d[p][i].y;
+    }
+  msfm_epnpf_options opt;
+  msfm_epnpf_default_options(&opt);
+  opt.seed = kPoseSeed;
+  avg_error.assign(std::max(1, n), 0.0);
+  f_out.assign(std::max(1, n), 0.0);
+  check(msfm_epnpf_sweep_batch(Context(), n, off.data(), X.data(), x.data(), f_estimated.data(), &opt, f_out.data(), R.data(), t.data(),
+                               err.data(), avg_error.data(), nullptr, nullptr, nullptr), "epnpf_sweep_batch");
+  avg_error.resize(n); f_out.resize(n);
+  poses.resize(n); errors.resize(n);
+  for (int p = 0; p < n; p++) {
+    for (int k = 0; k < 9; k++) poses[p].R.m[k] = R[9 * (size_t)p + k];
+    for (int k = 0; k < 3; k++) poses[p].t[k] = t[3 * (size_t)p + k];
+    errors[p].assign(err.begin() + off[p], err.begin() + off[p + 1]);
+  }
+}
+
 bool AbsolutePoseEstimation::AbsolutePoseWithFocalLength(std::vector<Vec3>& pts_w, std::vector<Vec2>& pts_2d, double f, RTPose& pose_absolute,
                                                          std::vector<double>& errors, double& avg_error) {
   std::vector<RTPose> poses;

@@ -252,6 +252,11 @@ class RelativePoseEstimation {
 // Many images / pairs in one call each (the batched form the GPU wants; same results as the per-item calls above).
 void AbsolutePoseBatch(const std::vector<std::vector<Vec3>>& pts_w, const std::vector<std::vector<Vec2>>& pts_2d, const std::vector<double>& f,
                        std::vector<RTPose>& poses, std::vector<std::vector<double>>& errors, std::vector<double>& avg_error);
+// AbsolutePoseWithoutFocalLength for many images (absolute_pose_estimation.cc:28-40): the EPNPF focal sweep around f_estimated
+// (the reference: 1.2 * max(w, h), sfm_incremental.cc:675); f_out = the focal length it keeps, for SetFocalLength (:704).
+void AbsolutePoseWithoutFocalLengthBatch(const std::vector<std::vector<Vec3>>& pts_w, const std::vector<std::vector<Vec2>>& pts_2d,
+                                         const std::vector<double>& f_estimated, std::vector<double>& f_out, std::vector<RTPose>& poses,
+                                         std::vector<std::vector<double>>& errors, std::vector<double>& avg_error);
 
 // The per-image feature file of the extraction stage (Database::WriteoutImageFeature / ReadinImageFeatures,
 // SfM/src/database.cc:490-541, :352-423): header, centred keypoints, raw descriptors.  cv::Mat -> flat float rows.

@@ -556,6 +556,40 @@ void msfm_chain_destroy(msfm_chain* chain);
 int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w,
                            const double* pts_2d, const double* f, int max_iter, uint64_t seed, double* R,
                            double* t, double* errors, double* avg_error, int* best_iter);
+/* AbsolutePoseEstimation::AbsolutePoseWithoutFocalLength (absolute_pose_estimation.cc:28-40, the arm of
+ * IncrementalSfM::LocalizeImage an image without a known focal length takes, sfm_incremental.cc:673-704) for a batch of
+ * images.  Per image AbsolutePoseEPNPF::EPNPF (absolute_pose_via_epnpf.cc:34-63): n_steps = (int)((f_ratio_max -
+ * f_ratio_min) / f_ratio_step) candidate focal lengths f_i = (f_ratio_min + i * f_ratio_step) * f_init (:44, :49), one
+ * complete EPNPRansac of `max_iter` samples at each, the first step whose kept sample has the smallest error below
+ * 1000000.0 wins (:46, :56) - then AbsolutePoseEstimation::Error over all correspondences at the winning focal length (:35).
+ * Step i of image p IS problem p * n_steps + i of msfm_epnp_ransac_batch with focal length f_i and the same seed and
+ * max_iter, bit for bit (the reference likewise continues one std::rand stream through the sweep, so its steps draw
+ * different samples); the whole sweep runs on the device, the correspondences are uploaded once and only one record per
+ * step exists there.  The reference's quirk is kept: the minimal solver's "no fit" value 100000.0 is below the 1000000.0
+ * start, so a sweep whose every step failed keeps step 0; only an image with fewer than 4 points keeps none. */
+typedef struct msfm_epnpf_options {
+  double f_ratio_min;  /* 0.5   absolute_pose_estimation.cc:31 */
+  double f_ratio_max;  /* 4.00  absolute_pose_estimation.cc:32 */
+  double f_ratio_step; /* 0.01  absolute_pose_via_epnpf.cc:41 */
+  int32_t max_iter;    /* 200   absolute_pose_via_epnpf.cc:39; 1..65536 */
+  uint64_t seed;
+} msfm_epnpf_options;
+void msfm_epnpf_default_options(msfm_epnpf_options* opt);
+/* (int)((f_ratio_max - f_ratio_min) / f_ratio_step) in binary64 (350 for the defaults); MSFM_E_INVAL (< 0) unless
+ * f_ratio_step > 0, f_ratio_max > f_ratio_min and the count is in 1..65535. */
+int msfm_epnpf_num_steps(const msfm_epnpf_options* opt);
+/* In : as msfm_epnp_ransac_batch, with f_init[n] = the guess the candidates scale (the reference: 1.2 * max(w, h),
+ *      sfm_incremental.cc:675); n_problems <= 65535 and n_problems * n_steps must fit an int.
+ * Out: f_out [n] = the kept candidate (the reference's SetFocalLength argument, sfm_incremental.cc:704); R, t, errors,
+ *      avg_error = what msfm_epnp_ransac_batch returns for problem p * n_steps + best_step; best_step [n] and
+ *      best_iter [n] (each may be NULL) = the kept step and its kept sample; step_error [n][n_steps] (may be NULL) = each
+ *      step's error over its kept sample's own four points (absolute_pose_via_epnp.cc:129-133; 1e9 when no sample ran).
+ *      No step kept (fewer than 4 points): f_out = f_init, best_step = best_iter = -1, the rest as
+ *      msfm_epnp_ransac_batch returns it for such an image. */
+int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w,
+                           const double* pts_2d, const double* f_init, const msfm_epnpf_options* opt, double* f_out,
+                           double* R, double* t, double* errors, double* avg_error, int* best_step, int* best_iter,
+                           double* step_error);
 /* RelativePoseEstimation::RelativePoseWithFocalLength (SfM/src/orientation/relative_pose_estimation.cc:91-120,
  * called for the seed pair, sfm_incremental.cc:309) for a batch of image pairs.  Per pair, on points divided by the
  * focal lengths: EssentialMatrixFivePoints::FivePointEssentialMatrixRANSAC (essential_matrix_five_point.cc:30-92) -

@@ -62,6 +62,12 @@ class SlamPriorOptions(C.Structure):
                 ("th_ratio_f", C.c_float), ("th_h_f_ratio", C.c_float), ("seed_f", C.c_uint64), ("seed_h", C.c_uint64)]
 
 
+class EpnpfOptions(C.Structure):
+    """msfm_epnpf_options (include/msfm.h)."""
+    _fields_ = [("f_ratio_min", C.c_double), ("f_ratio_max", C.c_double), ("f_ratio_step", C.c_double), ("max_iter", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
 class SlamMatchOptions(C.Structure):
     """msfm_slam_match_options (include/msfm.h)."""
     _fields_ = [("th_first_second_ratio", C.c_float), ("th_epipolar", C.c_float), ("th_distance", C.c_float)]

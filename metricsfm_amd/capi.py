@@ -29,7 +29,8 @@ SYMBOLS = [
     "msfm_epipolar_filter", "msfm_fransac_default_options", "msfm_fundamental_ransac_batch",
     "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
     "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
-    "msfm_epnp_ransac_batch", "msfm_relpose_5pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
+    "msfm_epnp_ransac_batch", "msfm_epnpf_default_options", "msfm_epnpf_num_steps", "msfm_epnpf_sweep_batch",
+    "msfm_relpose_5pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
     "msfm_ctx_create_multi", "msfm_multi_destroy", "msfm_multi_size", "msfm_multi_ctx", "msfm_multi_last_error", "msfm_multi_ba_solve",
     "msfm_multi_triangulate_midpoint_batch", "msfm_multi_triangulate_dlt_batch", "msfm_multi_reproject_mse_batch", "msfm_multi_match_pairs",
 ]
@@ -110,6 +111,12 @@ def lib():
     L.msfm_epipolar_filter_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, A.c_double_p, A.c_u8_p, d, A.c_u8_p]
     L.msfm_epnp_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64, A.c_double_p,
                                          A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p]
+    L.msfm_epnpf_default_options.argtypes = [C.POINTER(A.EpnpfOptions)]
+    L.msfm_epnpf_default_options.restype = None
+    L.msfm_epnpf_num_steps.argtypes = [C.POINTER(A.EpnpfOptions)]
+    L.msfm_epnpf_sweep_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, C.POINTER(A.EpnpfOptions),
+                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p, A.c_int_p,
+                                         A.c_double_p]
     L.msfm_relpose_5pt_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64,
                                          A.c_double_p, A.c_double_p, A.c_double_p, A.c_u8_p, A.c_int_p]
     L.msfm_rccl_get_unique_id.argtypes = [vp, C.POINTER(C.c_ubyte)]
@@ -158,6 +165,22 @@ def default_options(**kw):
             raise AttributeError(k)
         setattr(o, k, v)
     return o
+
+
+def epnpf_options(**kw):
+    """msfm_epnpf_options with the reference's values (0.5, 4.0, 0.01, 200 samples); keywords override fields."""
+    o = A.EpnpfOptions()
+    lib().msfm_epnpf_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def epnpf_num_steps(**kw):
+    """Candidate focal lengths of the sweep these options describe: (int)((f_ratio_max - f_ratio_min) / f_ratio_step), < 0 if invalid."""
+    return lib().msfm_epnpf_num_steps(C.byref(epnpf_options(**kw)))
 
 
 def _flatten_matches(n_features, pairs, matches_per_pair):
@@ -459,6 +482,31 @@ class Context:
                                                 A.ptr(f, A.c_double_p), max_iter, seed, A.ptr(R, A.c_double_p), A.ptr(t, A.c_double_p),
                                                 A.ptr(err, A.c_double_p), A.ptr(avg, A.c_double_p), A.ptr(best, A.c_int_p)))
         return R[:n], t[:n], err[:len(pts_w)], avg[:n], best[:n]
+
+    def epnpf_sweep(self, offsets, pts_w, pts_2d, f_init, f_ratio_min=0.5, f_ratio_max=4.0, f_ratio_step=0.01, max_iter=200,
+                    seed=0x4D53464D50, keep_step_errors=False):
+        """AbsolutePoseEstimation::AbsolutePoseWithoutFocalLength for a batch of images (absolute_pose_estimation.cc:28-40):
+        the EPNPF focal sweep (absolute_pose_via_epnpf.cc:34-63) - an EPnP RANSAC at every candidate
+        (f_ratio_min + i * f_ratio_step) * f_init - + the reprojection errors of all correspondences at the kept candidate.
+        Returns f [n], R [n][3][3], t [n][3], errors [total], avg_error [n], best_step [n], best_iter [n]
+        [, step_error [n][n_steps] with keep_step_errors]."""
+        offsets = A.as_c(offsets, np.int32)
+        pts_w = A.as_c(np.asarray(pts_w, dtype=np.float64).reshape(-1, 3), np.float64)
+        pts_2d = A.as_c(np.asarray(pts_2d, dtype=np.float64).reshape(-1, 2), np.float64)
+        n = len(offsets) - 1
+        f_init = A.as_c(np.broadcast_to(np.asarray(f_init, dtype=np.float64), (n,)).copy(), np.float64)
+        o = A.EpnpfOptions(f_ratio_min, f_ratio_max, f_ratio_step, max_iter, seed)
+        n_steps = lib().msfm_epnpf_num_steps(C.byref(o))
+        f = np.zeros(max(1, n)); R = np.zeros((max(1, n), 3, 3)); t = np.zeros((max(1, n), 3)); err = np.zeros(max(1, len(pts_w)))
+        avg = np.zeros(max(1, n)); bstep = np.zeros(max(1, n), dtype=np.int32); biter = np.zeros(max(1, n), dtype=np.int32)
+        # invalid options: the call below reports them (no step array is touched before its checks)
+        serr = np.zeros((max(1, n), max(1, n_steps))) if keep_step_errors else None
+        self.check(lib().msfm_epnpf_sweep_batch(self._h, n, A.ptr(offsets, A.c_int_p), A.ptr(pts_w, A.c_double_p), A.ptr(pts_2d, A.c_double_p),
+                                                A.ptr(f_init, A.c_double_p), C.byref(o), A.ptr(f, A.c_double_p), A.ptr(R, A.c_double_p),
+                                                A.ptr(t, A.c_double_p), A.ptr(err, A.c_double_p), A.ptr(avg, A.c_double_p),
+                                                A.ptr(bstep, A.c_int_p), A.ptr(biter, A.c_int_p), A.ptr(serr, A.c_double_p)))
+        out = (f[:n], R[:n], t[:n], err[:len(pts_w)], avg[:n], bstep[:n], biter[:n])
+        return out + (serr[:n],) if keep_step_errors else out
 
     def relpose_5pt(self, offsets, pts_ref, pts_cur, f_ref, f_cur, ransac_times=100, seed=0x4D53464D45):
         """RelativePoseEstimation::RelativePoseWithFocalLength for a batch of image pairs (relative_pose_estimation.cc:91-120):

@@ -5,6 +5,10 @@
 //        (max_iter samples of 4 correspondences, EPnP on each :142-185 / compute_pose :472-519, the sample with the
 //         smallest error over its own four points wins), then AbsolutePoseEstimation::Error over all points (:67-103);
 //     called when an image is localised against the model, sfm_incremental.cc:646.
+//   AbsolutePoseEstimation::AbsolutePoseWithoutFocalLength SfM/src/orientation/absolute_pose_estimation.cc:28-40
+//     -> AbsolutePoseEPNPF::EPNPF                           SfM/src/orientation/absolute_pose_via_epnpf.cc:34-63
+//        (350 candidate focal lengths, an EPNPRansac at each, the first smallest kept-sample error wins), then Error;
+//     called when the image has no focal length yet, sfm_incremental.cc:673-704.
 //   RelativePoseEstimation::RelativePoseWithFocalLength    SfM/src/orientation/relative_pose_estimation.cc:91-120
 //     -> EssentialMatrixFivePoints::FivePointEssentialMatrixRANSAC  essential_matrix_five_point.cc:30-92
 //        (100 samples of 5 matches, every real solution of every sample scored by the Sampson sum :333-349), then
@@ -22,6 +26,7 @@
 #include "common.h"
 
 #include <cfloat>
+#include <climits>
 #include <cmath>
 
 #pragma clang fp contract(off)
@@ -549,6 +554,135 @@ __global__ __launch_bounds__(256) void k_epnp_select(int H, const int* __restric
     for (int i = 0; i < 9; i++) Rout[9 * (size_t)p + i] = R[i];
     for (int i = 0; i < 3; i++) tout[3 * (size_t)p + i] = t[i];
     best_iter[p] = best;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Focal sweep: AbsolutePoseEstimation::AbsolutePoseWithoutFocalLength (absolute_pose_estimation.cc:28-40) ->
+// AbsolutePoseEPNPF::EPNPF (absolute_pose_via_epnpf.cc:34-63).  Step i of image p is problem p * n_steps + i of
+// msfm_epnp_ransac_batch at f_i = (f_ratio_min + i * f_ratio_step) * f_init[p]: same sampler index, same minimal solve.
+// ---------------------------------------------------------------------------------------------------------------
+#define EPNPF_BLOCK 256
+
+// grid (n_steps, images), one workgroup per step: thread tid runs samples tid, tid + EPNPF_BLOCK, ... and keeps its first
+// smallest; the workgroup's first smallest (wave shuffles, then LDS across the waves; a tie goes to the lower sample, which
+// is what the sequential `if (error_temp < error)` from 1e9 keeps) is the only thing written: step_err / step_it /
+// step_pose[q] = {R[9], t[3]} with q = p * n_steps + i.  No sample ran (N < 4): {1e9, -1, zeros}.
+__global__ __launch_bounds__(EPNPF_BLOCK) void k_epnpf_sweep(int H, int n_steps, const int* __restrict__ off,
+                                                             const double* __restrict__ pts_w, const double* __restrict__ pts_2d,
+                                                             const double* __restrict__ f_init, double f_ratio_min, double f_ratio_step,
+                                                             uint64_t seed, double* __restrict__ step_err, int* __restrict__ step_it,
+                                                             double* __restrict__ step_pose) {
+  constexpr int NW = EPNPF_BLOCK / POSE_WAVE;
+  __shared__ double s_e[NW];
+  __shared__ int s_i[NW];
+  const int p = blockIdx.y, i = blockIdx.x, tid = threadIdx.x;
+  const int q = p * n_steps + i;
+  const int o = off[p], N = off[p + 1] - o;
+  const double f_i = (f_ratio_min + (double)i * f_ratio_step) * f_init[p];  // :49
+  double be = 1000000000.0, bR[9], bt[3];
+  int bi = -1;
+  if (N >= 4)
+    for (int it = tid; it < H; it += EPNPF_BLOCK) {
+      int idx[4];
+      pose_sample<4>(seed, 0x45506E50ull, q, it, N, idx);
+      EpnpState S;
+      for (int k = 0; k < 4; k++) {
+        for (int j = 0; j < 3; j++) S.pws[3 * k + j] = pts_w[3 * ((size_t)o + idx[k]) + j];
+        for (int j = 0; j < 2; j++) S.us[2 * k + j] = pts_2d[2 * ((size_t)o + idx[k]) + j];
+      }
+      double R[9], t[3];
+      const double e = epnp_minimal(S, f_i, R, t);
+      if (e < be) {
+        be = e; bi = it;
+        for (int k = 0; k < 9; k++) bR[k] = R[k];
+        for (int k = 0; k < 3; k++) bt[k] = t[k];
+      }
+    }
+  // bi == -1 compares as the largest index: a thread without a sample never displaces one that has
+  double we = be;
+  int wi = bi;
+  for (int m = POSE_WAVE / 2; m > 0; m >>= 1) {
+    const double e2 = __shfl_xor(we, m, POSE_WAVE);
+    const int i2 = __shfl_xor(wi, m, POSE_WAVE);
+    if (e2 < we || (e2 == we && (unsigned)i2 < (unsigned)wi)) { we = e2; wi = i2; }
+  }
+  if (NW > 1) {
+    if ((tid & (POSE_WAVE - 1)) == 0) { s_e[tid / POSE_WAVE] = we; s_i[tid / POSE_WAVE] = wi; }
+    __syncthreads();
+    we = s_e[0]; wi = s_i[0];
+    for (int w = 1; w < NW; w++) {
+      const double e2 = s_e[w];
+      const int i2 = s_i[w];
+      if (e2 < we || (e2 == we && (unsigned)i2 < (unsigned)wi)) { we = e2; wi = i2; }
+    }
+  }
+  if (wi < 0 ? tid == 0 : bi == wi) {  // sample wi ran on exactly one thread
+    step_err[q] = wi < 0 ? 1000000000.0 : be;
+    step_it[q] = wi;
+    for (int k = 0; k < 9; k++) step_pose[12 * (size_t)q + k] = wi < 0 ? 0.0 : bR[k];
+    for (int k = 0; k < 3; k++) step_pose[12 * (size_t)q + 9 + k] = wi < 0 ? 0.0 : bt[k];
+  }
+}
+
+// One workgroup per image: the step the sequential loop `if (error_i < error)` from error = 1000000.0 keeps
+// (absolute_pose_via_epnpf.cc:46, :56 - the first smallest; epnp_minimal's 100000.0 qualifies, the 1e9 of "no sample" does
+// not), then AbsolutePoseEstimation::Error over all points at that step's focal length (absolute_pose_estimation.cc:35,
+// :67-103); the sum of squares is taken in point order.  No step kept: f_init, the zero pose, best_step = best_iter = -1.
+__global__ __launch_bounds__(256) void k_epnpf_select(int n_steps, const int* __restrict__ off, const double* __restrict__ pts_w,
+                                                      const double* __restrict__ pts_2d, const double* __restrict__ f_init,
+                                                      double f_ratio_min, double f_ratio_step, const double* __restrict__ step_err,
+                                                      const int* __restrict__ step_it, const double* __restrict__ step_pose,
+                                                      double* __restrict__ f_out, double* __restrict__ Rout, double* __restrict__ tout,
+                                                      double* __restrict__ errors, double* __restrict__ avg_error,
+                                                      int* __restrict__ best_step, int* __restrict__ best_iter) {
+  __shared__ double s_e[256];
+  __shared__ int s_i[256];
+  __shared__ double s_pose[12];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int o = off[p], N = off[p + 1] - o;
+  const size_t q0 = (size_t)p * n_steps;
+  double be = 1000000.0;
+  int bi = -1;
+  for (int i = tid; i < n_steps; i += 256) {
+    const double e = step_err[q0 + i];
+    if (e < be) { be = e; bi = i; }
+  }
+  s_e[tid] = be; s_i[tid] = bi;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) {
+      const double e2 = s_e[tid + st];
+      const int i2 = s_i[tid + st];
+      if (i2 >= 0 && (s_i[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && i2 < s_i[tid]))) { s_e[tid] = e2; s_i[tid] = i2; }
+    }
+    __syncthreads();
+  }
+  const int best = s_i[0];
+  if (tid < 12) s_pose[tid] = best >= 0 ? step_pose[12 * (q0 + best) + tid] : 0.0;
+  __syncthreads();
+  double R[9], t[3];
+  for (int i = 0; i < 9; i++) R[i] = s_pose[i];
+  for (int i = 0; i < 3; i++) t[i] = s_pose[9 + i];
+  const double fp = best >= 0 ? (f_ratio_min + (double)best * f_ratio_step) * f_init[p] : f_init[p];
+  for (int i = tid; i < N; i += 256) {
+    const double e = pose_reproj_err(R, t, fp, pts_w + 3 * ((size_t)o + i), pts_2d + 2 * ((size_t)o + i));
+    errors[o + i] = fabs(e) < 10.0 ? e : 1000.0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    int count = 0;
+    for (int i = 0; i < N; i++) {
+      const double e = errors[o + i];
+      if (e < 10.0) { sum += e * e; count++; }
+    }
+    avg_error[p] = count == 0 ? 10000.0 : sqrt(sum / count);
+    for (int i = 0; i < 9; i++) Rout[9 * (size_t)p + i] = R[i];
+    for (int i = 0; i < 3; i++) tout[3 * (size_t)p + i] = t[i];
+    f_out[p] = fp;
+    best_step[p] = best;
+    best_iter[p] = best >= 0 ? step_it[q0 + best] : -1;
   }
 }
 
@@ -1152,6 +1286,85 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   if (total) HIP_TRY(ctx, hipMemcpyAsync(errors, d_err.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(avg_error, d_avg.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_best.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return MSFM_OK;
+}
+
+MSFM_API void msfm_epnpf_default_options(msfm_epnpf_options* o) {
+  if (!o) return;
+  o->f_ratio_min = 0.5;
+  o->f_ratio_max = 4.00;
+  o->f_ratio_step = 0.01;
+  o->max_iter = 200;
+  o->seed = 0x4D53464D50ull;
+}
+
+// int num_sample = (f_ratio_max - f_ratio_min) / f_ratio_step   (absolute_pose_via_epnpf.cc:44), in binary64
+MSFM_API int msfm_epnpf_num_steps(const msfm_epnpf_options* o) {
+  if (!o || !(o->f_ratio_step > 0.0) || !(o->f_ratio_max > o->f_ratio_min)) return MSFM_E_INVAL;
+  const double q = (o->f_ratio_max - o->f_ratio_min) / o->f_ratio_step;
+  if (!(q >= 1.0) || !(q < 65536.0)) return MSFM_E_INVAL;
+  return (int)q;
+}
+
+MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w, const double* pts_2d,
+                                    const double* f_init, const msfm_epnpf_options* opt, double* f_out, double* R, double* t,
+                                    double* errors, double* avg_error, int* best_step, int* best_iter, double* step_error) {
+  if (!ctx || n_problems < 0 || !offsets || !f_init || !opt || !f_out || !R || !t || !avg_error) return MSFM_E_INVAL;
+  if (!(opt->f_ratio_step > 0.0) || !(opt->f_ratio_max > opt->f_ratio_min))
+    return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: need f_ratio_step > 0 and f_ratio_max > f_ratio_min");
+  const int n_steps = msfm_epnpf_num_steps(opt);
+  if (n_steps < 1) return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: the options give a step count outside 1..65535");
+  if (opt->max_iter < 1 || opt->max_iter > 65536) return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: max_iter out of range");
+  if (n_problems == 0) return MSFM_OK;
+  if (n_problems > 65535) return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: at most 65535 problems per call");
+  if ((long long)n_problems * n_steps > INT_MAX)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: n_problems * n_steps = %lld does not fit an int", (long long)n_problems * n_steps);
+  MSFM_TRY(pose_check_offsets(ctx, "epnpf", n_problems, offsets));
+  const int total = offsets[n_problems];
+  if (total > 0 && (!pts_w || !pts_2d || !errors)) return MSFM_E_INVAL;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const size_t Q = (size_t)n_problems * n_steps;
+  DevBuf<int> d_off, d_sit, d_bstep, d_biter;
+  DevBuf<double> d_w, d_2d, d_f, d_serr, d_spose, d_fo, d_R, d_t, d_err, d_avg;
+  HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
+  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
+  HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_2d.alloc(2 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_w.upload(pts_w, 3 * (size_t)total, s));
+  HIP_TRY(ctx, d_2d.upload(pts_2d, 2 * (size_t)total, s));
+  HIP_TRY(ctx, d_f.alloc(n_problems));
+  HIP_TRY(ctx, d_f.upload(f_init, n_problems, s));
+  HIP_TRY(ctx, d_serr.alloc(Q));
+  HIP_TRY(ctx, d_sit.alloc(Q));
+  HIP_TRY(ctx, d_spose.alloc(12 * Q));
+  HIP_TRY(ctx, d_fo.alloc(n_problems));
+  HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_problems));
+  HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_problems));
+  HIP_TRY(ctx, d_err.alloc((size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_avg.alloc(n_problems));
+  HIP_TRY(ctx, d_bstep.alloc(n_problems));
+  HIP_TRY(ctx, d_biter.alloc(n_problems));
+  {
+    KTimer tm(ctx, "pose_epnpf_sweep");
+    hipLaunchKernelGGL(k_epnpf_sweep, dim3(n_steps, n_problems), dim3(EPNPF_BLOCK), 0, s, opt->max_iter, n_steps, d_off.p, d_w.p, d_2d.p,
+                       d_f.p, opt->f_ratio_min, opt->f_ratio_step, opt->seed, d_serr.p, d_sit.p, d_spose.p);
+  }
+  {
+    KTimer tm(ctx, "pose_epnpf_select");
+    hipLaunchKernelGGL(k_epnpf_select, dim3(n_problems), dim3(256), 0, s, n_steps, d_off.p, d_w.p, d_2d.p, d_f.p, opt->f_ratio_min,
+                       opt->f_ratio_step, d_serr.p, d_sit.p, d_spose.p, d_fo.p, d_R.p, d_t.p, d_err.p, d_avg.p, d_bstep.p, d_biter.p);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(f_out, d_fo.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  if (total) HIP_TRY(ctx, hipMemcpyAsync(errors, d_err.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(avg_error, d_avg.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  if (best_step) HIP_TRY(ctx, hipMemcpyAsync(best_step, d_bstep.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_biter.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
+  if (step_error) HIP_TRY(ctx, hipMemcpyAsync(step_error, d_serr.p, sizeof(double) * Q, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return MSFM_OK;
 }
