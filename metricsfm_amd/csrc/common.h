@@ -171,6 +171,20 @@ struct DevBuf {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// The sum of an int over the 64 lanes of a wave (butterfly 32 .. 1), in every lane.
+__device__ static inline int wave_sum_int(int c) {
+  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  return c;
+}
+
+// The CSR offsets of a batch call (n + 1 entries, n > 0); `who` prefixes the message.
+static inline int msfm_check_offsets(msfm_ctx* ctx, const char* who, int n, const int* offsets) {
+  if (offsets[0] != 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: offsets[0] must be 0", who);
+  for (int p = 0; p < n; p++)
+    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: offsets must be non-decreasing", who);
+  return MSFM_OK;
+}
+
 // Host-side helper: the index structures of a 10^6-observation problem (msfm_ba_create) and the per-pair iteration tables
 // of the RANSAC (geo.hip) are built by a few threads (MSFM_HOST_THREADS, default min(hardware threads, 8));
 // fn(t, begin, end) gets one contiguous range per thread.

@@ -1,5 +1,40 @@
-// Batched fundamental-matrix RANSAC for gfx950 — the geometric-verification stage that follows the
-// ratio tests in the reference's matching loop:
+// Batched two-view RANSAC for gfx950: one estimator-independent two-pass core, instantiated for the fundamental matrix (F)
+// and for the homography (H).
+//
+// THE CORE (k_ransac_models / k_ransac_count / k_ransac_select, host driver ransac_two_pass, all templates over an estimator):
+//   models   one GPU thread = one sample: the minimal solver, its work matrix in LDS (E::WORK doubles per thread), writes one
+//            record per sample (E::Rec: E::MODELS matrices and a status).
+//   scoring  one LANE = one correspondence and the model is uniform over the wave: its nine numbers arrive through the scalar
+//            cache as SGPR operands, a count is the wave sum of the lanes' inlier flags.  256 threads per block; the pair's
+//            correspondences wait in LDS (1 024 at a time), wave w takes samples [32 w, 32 w + 32) of the block's 128 one
+//            after the other.  The first form of this file scored with one thread per sample walking all matches, its three
+//            models in scratch memory and lanes idle wherever a sample had fewer models: 5.2 ms for the first 128 samples of
+//            the 9 120 pairs of 96 images, of which the solver was 0.24.
+//   replay   all samples of a range are scored in parallel; one wave per pair then replays OpenCV's sequential loop over the
+//            per-sample counts in sample order (the budget shrinks whenever a better model appears: cvRANSACUpdateNumIters,
+//            tabulated on the host as R[g] per distinct N), which selects exactly the model the sequential loop would have
+//            kept, recomputes it and writes the matrix, the inlier mask, the count and the verdict.
+//   two passes  most pairs stop after a few dozen samples: pass 1 scores and replays the first H1 = min(H, 128) samples of
+//            every admitted pair; a pair whose budget is still above H1 goes onto the need list (E::TRIM: with its budget), and pass 2
+//            scores samples [H1, Hs) for the listed pairs only and replays [0, Hs).  Hs = H, or with E::TRIM the largest
+//            listed budget, and then each pair's samples at or past its own budget are not drawn either (`lim`).
+// What an estimator carries (everything else is shared):
+//    1. sample -> models: E::sample (F: geo_solve7, 0..3 matrices; H: hr_sample, one matrix and a status 0 model, 1 no model,
+//       2 no admissible subset in 300 attempts); E::n_models(status).
+//    2. count encoding: E::code (F: -1 for a model slot the sample does not have; H: -1 no model, -2 status 2).
+//    3. replay: best starts at E::POINTS - 1; with E::HAS_STOP the loop ends at the first -2.
+//    4. no winner: mask E::NO_WINNER_MASK everywhere (F 0 with n_inliers 0; H 1 with n_inliers N), zero matrix, ok 0.
+//    5. verdict with a winner: E::verdict (F: count >= min_inliers; H: 1).
+//    6. inlier predicate: E::inlier (geo_inlier: binary64 compare; hr_inlier: error rounded to binary32, then compared).
+//    7. second range: E::TRIM (H scores [H1, Hs) with a per-pair limit; F scores [H1, H) for every deferred pair and has
+//       the budget code compiled out: it records no budgets).
+//    8. the KTimer class names E::T_SCORE, E::T_REST, E::T_SELECT.
+//   In the host wrappers (geo_fransac_dev / geo_hransac_dev), not in the traits:
+//    9. admission: F N >= min_points && N >= 8; H N > 4 && (!active || active[p]).
+//   10. before the passes F zero-fills the four outputs, H runs k_hransac_small; after them H runs k_hransac_polish if asked.
+//   11. H maps threshold <= 0 to 3.0.
+//
+// F: the geometric-verification stage that follows the ratio tests in the reference's matching loop:
 //   GeoVerification::GeoVerificationFundamental   SfM/src/utils/geo_verification.cc:30-58
 //     -> cv::findFundamentalMat(pt1, pt2, status, cv::FM_RANSAC, 3.0)   (OpenCV 2.4, not in the tree)
 //   called per image pair from FineMatchingGraph::BuildMatchGraph, fine_matching_graph.cc:138-153.
@@ -11,13 +46,36 @@
 // is statistical; parity with oracle/ (same counter-based sampler) is exact:
 // this file uses only + - * / sqrt on doubles, in a fixed order, with contraction off.
 //
-// Models: one GPU thread = one sample (k_fransac_models: the 7-point solver, work matrix in LDS).  Scoring: one LANE = one
-// MATCH and the model is uniform over the wave (k_fransac_count: its nine numbers arrive through the scalar cache as SGPR
-// operands, a count is the population count of the wave's inlier mask) - the first form of this file scored with one thread
-// per sample walking all matches, its three models in scratch memory and lanes idle wherever a sample had fewer models:
-// 5.2 ms for the first 128 samples of the 9 120 pairs of 96 images, of which the solver was 0.24.  All samples of a range are
-// scored in parallel; the adaptive stop is then replayed over the per-sample inlier counts in sample order, which selects
-// exactly the model the sequential loop would have kept.
+// H: cv::findHomography(pts1, pts2, mask, RANSAC, th) of OpenCV 2.4 (cvFindHomography +
+// CvHomographyEstimator + CvModelEstimator2::runRANSAC + CvLevMarq), called per image pair by SLAMGPS::FeatureMatching
+// step 1 (slam_gps.cc:400-408).  Restated from OpenCV's published source, which is not on this machine; where memory of it
+// could be wrong, or where this restatement departs from it on purpose:
+//   - sampler: counter based (as geo_solve7), not OpenCV's cvRNG stream; a repeated index is redrawn, a subset with three
+//     collinear points in either image (checkSubset, checkPartialSubsets = false: |dx2 dy1 - dy2 dx1| <= FLT_EPSILON
+//     (|dx1| + |dy1| + |dx2| + |dy2|)) costs one of 300 attempts; 300 failures end the loop (at sample 0: no model).
+//   - model of a sample: OpenCV forms the 9x9 LtL of the normalised DLT rows and takes cvEigenVV's last eigenvector; here
+//     the exact 8x9 null space by Gauss-Jordan with full pivoting (the same vector for four points, other rounding).  A
+//     sample whose normalisation has a sum of absolute deviations < DBL_EPSILON, whose system is rank deficient, or whose
+//     denormalised H is not finite has no model (OpenCV would keep a NaN / inf model that scores 0 and never wins).
+//   - N == 4 (cvFindHomography's direct fit, no RANSAC): the same exact null space on the four points in their order; a
+//     rank-deficient system (four collinear points, say) or a non-finite H gives ok = 0 with the mask of ones.  OpenCV's
+//     runKernel returns 1 there for any set whose spreads are >= DBL_EPSILON, with the LtL eigenvector it finds: a departure,
+//     unlike the "no model" of a RANSAC sample (which could only ever score 0 and never win).
+//   - H is scaled by division by H[8] (OpenCV multiplies by 1 / H[8]), so that H[8] = 1 exactly.
+//   - error: err = (float)(dx^2 + dy^2) of the transfer into image 2 with ww = 1 / (h6 x + h7 y + 1), inlier iff
+//     (double)err <= th^2 - OpenCV keeps err in a CV_32F row and compares it with the double threshold^2.
+//   - stop: a sample wins if good > max(best, 3); niters = cvRANSACUpdateNumIters(0.995, (N - good) / N, 4, niters),
+//     tabulated per distinct N on the host with max_iters = the option's limit and capped by the current niters.
+//   - polish (cvFindHomography after a successful RANSAC): refit on the inliers (LtL summed over them, eigenvector of its
+//     smallest eigenvalue by cyclic Jacobi - OpenCV's Jacobi picks the largest off-diagonal pivot instead), then CvLevMarq
+//     for 10 iterations on h0..h7: lambda = 10^k as the decimal literal (OpenCV: exp(k ln 10)), diagonal times (1 + lambda),
+//     the step by the eigen-decomposition of the damped 8x8 (OpenCV: cvSVD + cvSVBkSb, singular values <= 2 eps sum(w)
+//     dropped), stop after 10 iterations or when |dp| / (|p| + DBL_EPSILON) < DBL_EPSILON.  Sums over the inliers run in
+//     the polish kernel's order: lane l of a wave takes correspondences l, l + 64, ... ascending, then the butterfly
+//     d = 32 .. 1 (tests/hransac_ref.cpp restates it); OpenCV sums the compressed inliers in index order.
+//   - the mask is that of the best sample's model, not recomputed after the polish (as OpenCV returns it).
+// Beside the core the H path has k_hransac_small (pairs of at most four correspondences and pairs the caller left out)
+// and k_hransac_polish, one wave per pair each.
 #include "common.h"
 
 #include <cfloat>
@@ -36,11 +94,6 @@ __host__ __device__ static inline uint64_t geo_sm64(uint64_t& s) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-
-struct GeoModels {
-  int n;
-  double F[3][9];
-};
 
 __device__ static inline double geo_det3(const double* m) {
   return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
@@ -106,10 +159,11 @@ __device__ static inline int geo_cubic(double c3, double c2, double c1, double c
 }
 
 // The 7-point solver for sample `h` of pair `pair`.  A: this thread's 7x9 work matrix, element
-// (r, c) at A[(r * 9 + c) * stride]  (LDS, one column of a [63][stride] array per thread).
-__device__ static inline void geo_solve7(uint64_t seed, int pair, int h, int N, const float2* __restrict__ p1,
-                                          const float2* __restrict__ p2, double* A, int stride, GeoModels& out) {
-  out.n = 0;
+// (r, c) at A[(r * 9 + c) * stride]  (LDS, one column of a [63][stride] array per thread).  Returns the number of
+// models (0..3) and writes them to M[0..].
+__device__ static inline int geo_solve7(uint64_t seed, int pair, int h, int N, const float2* __restrict__ p1,
+                                          const float2* __restrict__ p2, double* A, int stride, double (*M)[9]) {
+  int n = 0;
   uint64_t s = seed ^ ((uint64_t)pair * 0xD1342543DE82EF95ull) ^ ((uint64_t)h * 0xA24BAED4963EE407ull);
   int idx[7];
   for (int k = 0; k < 7; k++) {
@@ -138,7 +192,7 @@ __device__ static inline void geo_solve7(uint64_t seed, int pair, int h, int N, 
         const double v = fabs(AT(r, c));
         if (v > best) { best = v; pr = r; pc = c; }
       }
-    if (!(best > 0.0)) return;  // degenerate sample (or NaN input): no model
+    if (!(best > 0.0)) return 0;  // degenerate sample (or NaN input): no model
     if (pr != i)
       for (int c = 0; c < 9; c++) { const double t = AT(i, c); AT(i, c) = AT(pr, c); AT(pr, c) = t; }
     if (pc != i) {
@@ -187,9 +241,10 @@ __device__ static inline void geo_solve7(uint64_t seed, int pair, int h, int N, 
       const double inv = 1.0 / mu;
       for (int k = 0; k < 9; k++) F[k] = F[k] * inv;
     }
-    for (int k = 0; k < 9; k++) out.F[out.n][k] = F[k];
-    out.n++;
+    for (int k = 0; k < 9; k++) M[n][k] = F[k];
+    n++;
   }
+  return n;
 }
 
 // max(d1^2 / |l1|^2, d2^2 / |l2|^2) with l2 = F x1 (line in image 2), l1 = F^T x2
@@ -208,455 +263,6 @@ __device__ static inline bool geo_inlier(const double* F, double x1, double y1, 
   const double err = e1 > e2 ? e1 : e2;
   return err <= th2;  // false for NaN
 }
-
-// The models of samples [h0, h1) of the pairs in `slot_pair`: grid (ceil((h1 - h0) / 64), n_slots), thread = sample.
-// models[slot][h - h0]: up to three fundamental matrices and their number.
-struct GeoModelRec { double F[3][9]; int n, pad; };
-__global__ __launch_bounds__(GEO_WAVE) void k_fransac_models(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ n_slots_dev,
-                                                              const int* __restrict__ off, const float2* __restrict__ pt1, const float2* __restrict__ pt2,
-                                                              uint64_t seed, GeoModelRec* __restrict__ models) {
-  __shared__ double A[63 * GEO_WAVE];
-  if (n_slots_dev && (int)blockIdx.y >= *n_slots_dev) return;
-  const int slot = blockIdx.y, pair = slot_pair[slot], h = h0 + blockIdx.x * GEO_WAVE + threadIdx.x;
-  const int o = off[pair], N = off[pair + 1] - o;
-  if (h >= h1) return;
-  GeoModels m;
-  m.n = 0;
-  geo_solve7(seed, pair, h, N, pt1 + o, pt2 + o, A + threadIdx.x, GEO_WAVE, m);
-  GeoModelRec* r = models + (size_t)slot * (h1 - h0) + (h - h0);
-  for (int q = 0; q < 3; q++)
-    for (int k = 0; k < 9; k++) r->F[q][k] = q < m.n ? m.F[q][k] : 0.0;
-  r->n = m.n;
-  r->pad = 0;
-}
-
-// Inlier counts of those models: grid (ceil((h1 - h0) / 128), n_slots), 256 threads; the pair's matches wait in LDS (1024
-// at a time), wave w takes samples [32 w, 32 w + 32) of the block's 128 one after the other, lane = match.
-// counts[slot][h - h0][3] (-1: no such model).
-#define GEO_CNT_SAMPLES 128
-// counts[slot][cs samples][3]: this launch's samples start at sample `co` of a slot's row (a range taken in several pieces shares one array).
-__global__ __launch_bounds__(256) void k_fransac_count(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ n_slots_dev,
-                                                        const int* __restrict__ off, const float2* __restrict__ pt1, const float2* __restrict__ pt2,
-                                                        double th2, const GeoModelRec* __restrict__ models, int* __restrict__ counts, int cs, int co) {
-  __shared__ float4 pts[1024];
-  __shared__ int cnt_s[GEO_CNT_SAMPLES * 3];
-  if (n_slots_dev && (int)blockIdx.y >= *n_slots_dev) return;
-  const int slot = blockIdx.y, pair = slot_pair[slot];
-  const int o = off[pair], N = off[pair + 1] - o;
-  const int HS = h1 - h0;
-  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int s_first = blockIdx.x * GEO_CNT_SAMPLES + 32 * wave;   // first sample (relative to h0) of this wave
-  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES * 3; e += 256) cnt_s[e] = 0;
-  for (int base = 0; base < N; base += 1024) {
-    const int nb = min(1024, N - base);
-    __syncthreads();
-    for (int e = threadIdx.x; e < nb; e += 256) {
-      const float2 a = pt1[o + base + e], b = pt2[o + base + e];
-      pts[e] = make_float4(a.x, a.y, b.x, b.y);
-    }
-    __syncthreads();
-    for (int j = 0; j < 32; j++) {
-      const int hs = s_first + j;
-      if (hs >= HS) break;
-      const GeoModelRec* r = models + (size_t)slot * HS + hs;
-      const int nm = r->n;
-      for (int q = 0; q < nm; q++) {
-        double F[9];
-#pragma unroll
-        for (int k = 0; k < 9; k++) F[k] = r->F[q][k];
-        int c = 0;
-        for (int e = lane; e < nb; e += 64) {
-          const float4 p = pts[e];
-          c += geo_inlier(F, p.x, p.y, p.z, p.w, th2) ? 1 : 0;
-        }
-        for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-        if (lane == 0) cnt_s[(32 * wave + j) * 3 + q] += c;   // (only this wave touches these entries)
-      }
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES * 3; e += 256) {
-    const int hs = blockIdx.x * GEO_CNT_SAMPLES + e / 3, q = e % 3;
-    if (hs < HS) counts[((size_t)slot * cs + co + hs) * 3 + q] = q < models[(size_t)slot * HS + hs].n ? cnt_s[e] : -1;
-  }
-}
-
-// One wave per pair: replay OpenCV's sequential loop over the counts (niters shrinks whenever a
-// better model appears: cvRANSACUpdateNumIters, tabulated on the host as R[g] per distinct N), recompute
-// the winning model, write F, the inlier mask and the verdict of GeoVerificationFundamental.
-// Two passes: pass 1 (grid = the pairs with enough matches, `slot_pair`) replays the first H1 samples only; pairs whose budget
-// is still larger than H1 are appended to `need_list` (and finished by pass 2 over all H samples: grid = that list, the
-// counts of samples [H1, H) in counts2[k]), the others are final.
-__global__ __launch_bounds__(GEO_WAVE) void k_fransac_select(int H, int H1, int pass, const int* __restrict__ slot_pair, int* __restrict__ need_list,
-                                                              int* __restrict__ need_count, const int* __restrict__ off, const float2* __restrict__ pt1,
-                                                              const float2* __restrict__ pt2, uint64_t seed, double th2,
-                                                              int min_inliers, const int* __restrict__ counts1, const int* __restrict__ counts2,
-                                                              const int* __restrict__ niters_tab, const int* __restrict__ tab_off, double* __restrict__ Fout,
-                                                              uint8_t* __restrict__ inlier, int* __restrict__ n_inliers,
-                                                              uint8_t* __restrict__ ok) {
-  __shared__ double A[63];
-  __shared__ double Fw[9];
-  __shared__ int win[3];
-  __shared__ int cl[3 * 1024];
-  const int lane = threadIdx.x;
-  if (pass == 2 && (int)blockIdx.x >= *need_count) return;
-  const int slot = pass == 2 ? need_list[blockIdx.x] : (int)blockIdx.x;
-  const int pair = slot_pair[slot];
-  const int o = off[pair], N = off[pair + 1] - o;
-  const int Hscan = pass == 1 ? H1 : H;
-  if (lane == 0) { win[0] = -1; win[1] = 0; win[2] = H; }
-  {
-    const int* R = niters_tab + tab_off[pair];  // N + 1 entries (the table of this N)
-    int best = 6;                          // a model must beat modelPoints - 1
-    for (int h0 = 0; h0 < Hscan; h0 += 1024) {
-      __syncthreads();
-      if (h0 >= win[2]) break;  // uniform: win[2] is shared
-      const int nh = min(1024, Hscan - h0);
-      for (int e = lane; e < 3 * nh; e += GEO_WAVE) {
-        const int h = h0 + e / 3, q = e % 3;
-        cl[e] = h < H1 ? counts1[((size_t)slot * H1 + h) * 3 + q] : counts2[((size_t)blockIdx.x * (H - H1) + (h - H1)) * 3 + q];
-      }
-      __syncthreads();
-      if (lane == 0) {
-        int niters = win[2];
-        for (int h = h0; h < h0 + nh && h < niters; h++)
-          for (int q = 0; q < 3; q++) {
-            const int g = cl[(h - h0) * 3 + q];
-            if (g > best) {
-              best = g; win[0] = h; win[1] = q;
-              const int r = R[g];
-              if (r < niters) niters = r;
-            }
-          }
-        win[2] = niters;
-      }
-    }
-  }
-  __syncthreads();
-  if (pass == 1) {
-    const bool more = win[2] > H1 && H1 < H;  // the sequential loop would have gone on past H1
-    if (more) {
-      if (lane == 0) need_list[atomicAdd(need_count, 1)] = slot;
-      return;
-    }
-  }
-  const int wh = win[0];
-  if (wh < 0) {
-    for (int e = lane; e < N; e += GEO_WAVE) inlier[o + e] = 0;
-    if (lane == 0) {
-      for (int k = 0; k < 9; k++) Fout[(size_t)pair * 9 + k] = 0.0;
-      n_inliers[pair] = 0;
-      ok[pair] = 0;
-    }
-    return;
-  }
-  if (lane == 0) {
-    GeoModels m;
-    geo_solve7(seed, pair, wh, N, pt1 + o, pt2 + o, A, 1, m);
-    for (int k = 0; k < 9; k++) { Fw[k] = m.F[win[1]][k]; Fout[(size_t)pair * 9 + k] = Fw[k]; }
-  }
-  __syncthreads();
-  double F[9];
-  for (int k = 0; k < 9; k++) F[k] = Fw[k];
-  int c = 0;
-  for (int e = lane; e < N; e += GEO_WAVE) {
-    const float2 a = pt1[o + e], b = pt2[o + e];
-    const bool in = geo_inlier(F, a.x, a.y, b.x, b.y, th2);
-    inlier[o + e] = in ? 1 : 0;
-    c += in ? 1 : 0;
-  }
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-  if (lane == 0) {
-    n_inliers[pair] = c;
-    ok[pair] = c >= min_inliers ? 1 : 0;  // match_inliers.size() < 30 -> false
-  }
-}
-
-// l = F [x1, y1, 1]; l /= hypot(l0, l1); inlier iff |l . [x2, y2, 1]| < th   (geo_verification.cc:60-79),
-// for every pair whose F was accepted.
-__global__ __launch_bounds__(256) void k_epipolar_batch(int total, const int* __restrict__ pair_of, const float2* __restrict__ pt1,
-                                                         const float2* __restrict__ pt2, const double* __restrict__ F,
-                                                         const uint8_t* __restrict__ ok, double th, uint8_t* __restrict__ inlier) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= total) return;
-  const int p = pair_of[e];
-  if (ok && !ok[p]) { inlier[e] = 0; return; }
-  const double* f = F + (size_t)p * 9;
-  const double x1 = pt1[e].x, y1 = pt1[e].y, x2 = pt2[e].x, y2 = pt2[e].y;
-  double l0 = f[0] * x1 + f[1] * y1 + f[2];
-  double l1 = f[3] * x1 + f[4] * y1 + f[5];
-  double l2 = f[6] * x1 + f[7] * y1 + f[8];
-  const double n = sqrt(l0 * l0 + l1 * l1);
-  l0 = l0 / n; l1 = l1 / n; l2 = l2 / n;
-  const double dis = l0 * x2 + l1 * y2 + l2;
-  inlier[e] = fabs(dis) < th ? 1 : 0;
-}
-
-__global__ void k_gather_int(int n, const int* __restrict__ idx, const int* __restrict__ src, int* __restrict__ dst) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) dst[i] = src[idx[i]];
-}
-
-// cvRANSACUpdateNumIters(p, ep, model_points, max_iters) for ep = (N - g) / N, clamped to max_iters
-static int geo_update_num_iters(double p, double ep, int model_points, int max_iters) {
-  p = std::max(p, 0.0); p = std::min(p, 1.0);
-  ep = std::max(ep, 0.0); ep = std::min(ep, 1.0);
-  double num = std::max(1.0 - p, DBL_MIN);
-  double denom = 1.0 - std::pow(1.0 - ep, model_points);
-  if (denom < DBL_MIN) return 0;
-  num = std::log(num);
-  denom = std::log(denom);
-  if (denom >= 0 || -num >= max_iters * (-denom)) return max_iters;
-  return (int)std::lrint(num / denom);
-}
-
-MSFM_API void msfm_fransac_default_options(msfm_fransac_options* o) {
-  if (!o) return;
-  o->threshold = 3.0;
-  o->confidence = 0.99;
-  o->max_iterations = 2000;
-  o->min_points = 30;
-  o->min_inliers = 30;
-  o->seed = 0x4D53464D46ull;
-}
-
-// The verification of a batch of pairs on points that are already resident: d1 / d2 hold the pairs' matches back to back,
-// h_offsets (host) and d_off (device) delimit them; results stay on the device.  msfm_fundamental_ransac_batch is this
-// between an upload and a download, msfm_chain_verify (chain.hip) calls it on points gathered from the match codes.
-int geo_fransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d_off, const float* d1, const float* d2,
-                    const msfm_fransac_options* opt, double* dF, uint8_t* d_in, int* d_nin, uint8_t* d_ok) {
-  hipStream_t s = ctx->stream;
-  const int H = opt->max_iterations;
-  // R[g] = cvRANSACUpdateNumIters for g inliers of N: a pow and two logs per entry.  The table of a pair depends on its N
-  // alone, so one table per DISTINCT N is formed (and kept from call to call while confidence and sample limit stay the same:
-  // the matching loop verifies thousands of pairs with one set of options) - at 9 120 pairs of ~125 good matches each the
-  // per-pair tables were 1.1 M evaluations, 7 of the 15 ms of msfm_chain_verify on sixteen host threads.
-  std::vector<int> tab, tab_off(std::max(1, n_pairs), 0);
-  {
-    struct TabCache { std::mutex mu; double conf = -1.0; int H = -1; std::unordered_map<int, std::vector<int>> by_n; size_t entries = 0; };
-    static TabCache cache;
-    std::lock_guard<std::mutex> lock(cache.mu);
-    if (cache.conf != opt->confidence || cache.H != H || cache.entries > (size_t)32 << 20) {
-      cache.by_n.clear(); cache.entries = 0; cache.conf = opt->confidence; cache.H = H;
-    }
-    std::vector<int> missing;
-    for (int p = 0; p < n_pairs; p++) {
-      const int N = offsets[p + 1] - offsets[p];
-      if (N >= opt->min_points && N >= 8 && cache.by_n.find(N) == cache.by_n.end()) { cache.by_n[N]; missing.push_back(N); }
-    }
-    std::vector<std::vector<int>*> slot(missing.size());
-    for (size_t k = 0; k < missing.size(); k++) { slot[k] = &cache.by_n[missing[k]]; slot[k]->resize((size_t)missing[k] + 1); cache.entries += (size_t)missing[k] + 1; }
-    par_ranges(missing.size(), host_threads(), [&](int, size_t k0, size_t k1) {
-      for (size_t k = k0; k < k1; k++) {
-        const int N = missing[k];
-        int* R = slot[k]->data();
-        for (int g = 0; g <= N; g++) R[g] = geo_update_num_iters(opt->confidence, (double)(N - g) / N, 7, H);
-      }
-    }, 4);
-    std::unordered_map<int, int> at;   // N -> offset of its table in this call's upload
-    for (int p = 0; p < n_pairs; p++) {
-      const int N = offsets[p + 1] - offsets[p];
-      if (!(N >= opt->min_points && N >= 8)) continue;   // (the kernels do not look at the table of such a pair)
-      auto it = at.find(N);
-      if (it == at.end()) {
-        it = at.emplace(N, (int)tab.size()).first;
-        const std::vector<int>& R = cache.by_n[N];
-        tab.insert(tab.end(), R.begin(), R.end());
-      }
-      tab_off[p] = it->second;
-    }
-    if (tab.empty()) tab.push_back(H);
-  }
-  DevBuf<int> d_tab_off;
-  HIP_TRY(ctx, d_tab_off.from(tab_off, s));
-  DevBuf<int> d_tab;
-  HIP_TRY(ctx, d_tab.from(tab, s));
-  const double th2 = opt->threshold * opt->threshold;
-  // pairs without enough matches (GeoVerificationFundamental: pt1.size() < 30 -> false) get their verdict here; the others
-  // form the slot list the kernels run over
-  std::vector<int> slot_pair;
-  for (int p = 0; p < n_pairs; p++) {
-    const int N = offsets[p + 1] - offsets[p];
-    if (N >= opt->min_points && N >= 8) slot_pair.push_back(p);
-  }
-  const int n_slots = (int)slot_pair.size();
-  HIP_TRY(ctx, hipMemsetAsync(dF, 0, sizeof(double) * 9 * (size_t)n_pairs, s));
-  HIP_TRY(ctx, hipMemsetAsync(d_in, 0, (size_t)std::max(1, offsets[n_pairs]), s));
-  HIP_TRY(ctx, hipMemsetAsync(d_nin, 0, sizeof(int) * (size_t)n_pairs, s));
-  HIP_TRY(ctx, hipMemsetAsync(d_ok, 0, (size_t)n_pairs, s));
-  if (n_slots == 0) { HIP_TRY(ctx, hipStreamSynchronize(s)); return MSFM_OK; }
-  // Most pairs stop after a few dozen samples (cvRANSACUpdateNumIters): score the first H1 samples of every pair,
-  // replay them, and run the remaining H - H1 samples only for the pairs whose budget is still open.
-  const int H1 = std::min(H, 128);
-  DevBuf<int> d_slot_pair, d_need, d_counts1, d_counts2;
-  DevBuf<GeoModelRec> d_models1, d_models2;
-  HIP_TRY(ctx, d_slot_pair.from(slot_pair, s));
-  HIP_TRY(ctx, d_need.alloc((size_t)n_slots + 1));   // [0]: how many, [1..]: the slots
-  HIP_TRY(ctx, hipMemsetAsync(d_need.p, 0, sizeof(int), s));
-  HIP_TRY(ctx, d_counts1.alloc((size_t)n_slots * H1 * 3));
-  HIP_TRY(ctx, d_models1.alloc((size_t)n_slots * H1));
-  const float2* p1 = reinterpret_cast<const float2*>(d1);
-  const float2* p2 = reinterpret_cast<const float2*>(d2);
-  // the models of a sample range live in memory only between the two kernels: a long range is taken in pieces of `piece`
-  // samples that reuse one model buffer (224 bytes per sample and pair: 1 872 samples at once would be 420 KB per pair)
-  auto score = [&](int h0, int h1, int piece, int ns, const int* slots, GeoModelRec* models, int* counts, const char* name) {
-    KTimer t(ctx, name);
-    for (int a = h0; a < h1; a += piece) {
-      const int b = std::min(h1, a + piece);
-      for (int p0 = 0; p0 < ns; p0 += 32768) {  // grid.y limit
-        const int np = std::min(32768, ns - p0);
-        hipLaunchKernelGGL(k_fransac_models, dim3(cdiv(b - a, GEO_WAVE), np), dim3(GEO_WAVE), 0, s, a, b, slots + p0, (const int*)nullptr, d_off,
-                           p1, p2, opt->seed, models + (size_t)p0 * piece);
-        hipLaunchKernelGGL(k_fransac_count, dim3(cdiv(b - a, GEO_CNT_SAMPLES), np), dim3(256), 0, s, a, b, slots + p0, (const int*)nullptr, d_off,
-                           p1, p2, th2, models + (size_t)p0 * piece, counts + (size_t)p0 * (h1 - h0) * 3, h1 - h0, a - h0);
-      }
-    }
-  };
-  auto select = [&](int pass, int grid) {
-    KTimer t(ctx, "geo_fransac_select");
-    hipLaunchKernelGGL(k_fransac_select, dim3(grid), dim3(GEO_WAVE), 0, s, H, H1, pass, d_slot_pair.p, d_need.p + 1, d_need.p, d_off, p1, p2, opt->seed, th2,
-                       opt->min_inliers, d_counts1.p, d_counts2.p, d_tab.p, d_tab_off.p, dF, d_in, d_nin, d_ok);
-  };
-  score(0, H1, H1, n_slots, d_slot_pair.p, d_models1.p, d_counts1.p, "geo_fransac_score");
-  select(1, n_slots);
-  if (H1 < H) {
-    int n_need = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_need, d_need.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    if (n_need > 0) {
-      const int piece = std::min(H - H1, 256);
-      HIP_TRY(ctx, d_counts2.alloc((size_t)n_need * (H - H1) * 3));
-      HIP_TRY(ctx, d_models2.alloc((size_t)n_need * piece));
-      // the list holds SLOTS; the kernels of the second range want pairs
-      DevBuf<int> d_need_pair;
-      HIP_TRY(ctx, d_need_pair.alloc(n_need));
-      hipLaunchKernelGGL(k_gather_int, dim3(cdiv(n_need, 256)), dim3(256), 0, s, n_need, d_need.p + 1, d_slot_pair.p, d_need_pair.p);
-      score(H1, H, piece, n_need, d_need_pair.p, d_models2.p, d_counts2.p, "geo_fransac_score_rest");
-      select(2, n_need);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipStreamSynchronize(s));
-      return MSFM_OK;
-    }
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamSynchronize(s));   // the tables and counters above are released on return
-  return MSFM_OK;
-}
-
-MSFM_API int msfm_fundamental_ransac_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
-                                           const msfm_fransac_options* opt, double* F, uint8_t* inlier, int* n_inliers, uint8_t* ok) {
-  if (!ctx || n_pairs < 0 || !offsets || !opt || !F || !n_inliers || !ok) return MSFM_E_INVAL;
-  if (opt->max_iterations < 1 || opt->max_iterations > 65536 || !(opt->threshold > 0.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: bad options");
-  if (n_pairs == 0) return MSFM_OK;
-  if (offsets[0] != 0) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: offsets[0] must be 0");
-  for (int p = 0; p < n_pairs; p++)
-    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: offsets must be non-decreasing");
-  const int total = offsets[n_pairs];
-  if (total > 0 && (!pt1 || !pt2 || !inlier)) return MSFM_E_INVAL;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DevBuf<int> d_off, d_nin;
-  DevBuf<float> d1, d2;
-  DevBuf<double> dF;
-  DevBuf<uint8_t> d_in, d_ok;
-  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d2.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
-  HIP_TRY(ctx, dF.alloc((size_t)n_pairs * 9));
-  HIP_TRY(ctx, d_in.alloc((size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_nin.alloc(n_pairs));
-  HIP_TRY(ctx, d_ok.alloc(n_pairs));
-  MSFM_TRY(geo_fransac_dev(ctx, n_pairs, offsets, d_off.p, d1.p, d2.p, opt, dF.p, d_in.p, d_nin.p, d_ok.p));
-  HIP_TRY(ctx, hipMemcpyAsync(F, dF.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(n_inliers, d_nin.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return MSFM_OK;
-}
-
-// The closed-form filter of a batch on resident points (pair_of[e] = pair of match e): msfm_epipolar_filter_batch without its
-// transfers; msfm_chain_verify calls it on the "all" sets gathered from the match codes.
-int geo_epipolar_batch_dev(msfm_ctx* ctx, int total, const int* d_pair_of, const float* d1, const float* d2, const double* dF,
-                           const uint8_t* d_ok, double th, uint8_t* d_in) {
-  if (total == 0) return MSFM_OK;
-  KTimer t(ctx, "geo_epipolar_filter");
-  hipLaunchKernelGGL(k_epipolar_batch, dim3(cdiv(total, 256)), dim3(256), 0, ctx->stream, total, d_pair_of, reinterpret_cast<const float2*>(d1),
-                     reinterpret_cast<const float2*>(d2), dF, d_ok, th, d_in);
-  HIP_TRY(ctx, hipGetLastError());
-  return MSFM_OK;
-}
-
-MSFM_API int msfm_epipolar_filter_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
-                                        const double* F, const uint8_t* ok, double th, uint8_t* inlier) {
-  if (!ctx || n_pairs < 0 || !offsets || !F) return MSFM_E_INVAL;
-  if (n_pairs == 0) return MSFM_OK;
-  const int total = offsets[n_pairs];
-  if (total == 0) return MSFM_OK;
-  if (!pt1 || !pt2 || !inlier) return MSFM_E_INVAL;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  std::vector<int> pair_of(total);
-  for (int p = 0; p < n_pairs; p++) {
-    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "epipolar: offsets must be non-decreasing");
-    for (int e = offsets[p]; e < offsets[p + 1]; e++) pair_of[e] = p;
-  }
-  DevBuf<int> d_po;
-  DevBuf<float> d1, d2;
-  DevBuf<double> dF;
-  DevBuf<uint8_t> d_in, d_ok;
-  HIP_TRY(ctx, d_po.from(pair_of, s));
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)total)); HIP_TRY(ctx, d2.alloc(2 * (size_t)total));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s)); HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
-  HIP_TRY(ctx, dF.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, dF.upload(F, 9 * (size_t)n_pairs, s));
-  HIP_TRY(ctx, d_in.alloc(total));
-  if (ok) { HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_ok.upload(ok, n_pairs, s)); }
-  {
-    KTimer t(ctx, "geo_epipolar_filter");
-    hipLaunchKernelGGL(k_epipolar_batch, dim3(cdiv(total, 256)), dim3(256), 0, s, total, d_po.p, reinterpret_cast<const float2*>(d1.p),
-                       reinterpret_cast<const float2*>(d2.p), dF.p, ok ? d_ok.p : nullptr, th, d_in.p);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return MSFM_OK;
-}
-
-// ============================================================================================================================
-// Batched homography RANSAC: cv::findHomography(pts1, pts2, mask, RANSAC, th) of OpenCV 2.4 (cvFindHomography +
-// CvHomographyEstimator + CvModelEstimator2::runRANSAC + CvLevMarq), called per image pair by SLAMGPS::FeatureMatching
-// step 1 (slam_gps.cc:400-408).  Restated from OpenCV's published source, which is not on this machine; where memory of it
-// could be wrong, or where this restatement departs from it on purpose:
-//   - sampler: counter based (as geo_solve7), not OpenCV's cvRNG stream; a repeated index is redrawn, a subset with three
-//     collinear points in either image (checkSubset, checkPartialSubsets = false: |dx2 dy1 - dy2 dx1| <= FLT_EPSILON
-//     (|dx1| + |dy1| + |dx2| + |dy2|)) costs one of 300 attempts; 300 failures end the loop (at sample 0: no model).
-//   - model of a sample: OpenCV forms the 9x9 LtL of the normalised DLT rows and takes cvEigenVV's last eigenvector; here
-//     the exact 8x9 null space by Gauss-Jordan with full pivoting (the same vector for four points, other rounding).  A
-//     sample whose normalisation has a sum of absolute deviations < DBL_EPSILON, whose system is rank deficient, or whose
-//     denormalised H is not finite has no model (OpenCV would keep a NaN / inf model that scores 0 and never wins).
-//   - N == 4 (cvFindHomography's direct fit, no RANSAC): the same exact null space on the four points in their order; a
-//     rank-deficient system (four collinear points, say) or a non-finite H gives ok = 0 with the mask of ones.  OpenCV's
-//     runKernel returns 1 there for any set whose spreads are >= DBL_EPSILON, with the LtL eigenvector it finds: a departure,
-//     unlike the "no model" of a RANSAC sample (which could only ever score 0 and never win).
-//   - H is scaled by division by H[8] (OpenCV multiplies by 1 / H[8]), so that H[8] = 1 exactly.
-//   - error: err = (float)(dx^2 + dy^2) of the transfer into image 2 with ww = 1 / (h6 x + h7 y + 1), inlier iff
-//     (double)err <= th^2 - OpenCV keeps err in a CV_32F row and compares it with the double threshold^2.
-//   - stop: a sample wins if good > max(best, 3); niters = cvRANSACUpdateNumIters(0.995, (N - good) / N, 4, niters),
-//     tabulated per distinct N on the host with max_iters = the option's limit and capped by the current niters.
-//   - polish (cvFindHomography after a successful RANSAC): refit on the inliers (LtL summed over them, eigenvector of its
-//     smallest eigenvalue by cyclic Jacobi - OpenCV's Jacobi picks the largest off-diagonal pivot instead), then CvLevMarq
-//     for 10 iterations on h0..h7: lambda = 10^k as the decimal literal (OpenCV: exp(k ln 10)), diagonal times (1 + lambda),
-//     the step by the eigen-decomposition of the damped 8x8 (OpenCV: cvSVD + cvSVBkSb, singular values <= 2 eps sum(w)
-//     dropped), stop after 10 iterations or when |dp| / (|p| + DBL_EPSILON) < DBL_EPSILON.  Sums over the inliers run in
-//     the polish kernel's order: lane l of a wave takes correspondences l, l + 64, ... ascending, then the butterfly
-//     d = 32 .. 1 (tests/hransac_ref.cpp restates it); OpenCV sums the compressed inliers in index order.
-//   - the mask is that of the best sample's model, not recomputed after the polish (as OpenCV returns it).
-// Kernels as the F path: models (thread = sample), scoring (lane = correspondence, model uniform over the wave), a replay
-// of the sequential loop per pair in two passes, the polish with one wave per pair.  The second pass draws and scores only
-// samples that can still be replayed: up to the largest budget among the deferred pairs, and for each pair below its own.
 
 __device__ static inline bool hr_check_subset(const double* x, const double* y) {
   for (int i = 0; i < 4; i++)
@@ -875,46 +481,92 @@ __device__ static inline int hr_sample(uint64_t seed, int pair, int h, int N, co
   return 2;
 }
 
-struct GeoHRec { double H[9]; int st, pad; };
+// ---- the estimators (the header comment lists what each member stands for) ----
+struct FEstimator {
+  static constexpr int POINTS = 7, MODELS = 3, WORK = 63;   // WORK: the 7x9 matrix of geo_solve7
+  static constexpr int NO_MODEL = 0;                        // the status is the number of models
+  static constexpr bool HAS_STOP = false, TRIM = false;
+  static constexpr int NO_WINNER_MASK = 0;
+  static constexpr const char *T_SCORE = "geo_fransac_score", *T_REST = "geo_fransac_score_rest", *T_SELECT = "geo_fransac_select";
+  struct Rec { double M[3][9]; int st, pad; };
+  __device__ static inline int sample(uint64_t seed, int pair, int h, int N, const float2* __restrict__ p1, const float2* __restrict__ p2,
+                                      double* A, int stride, double (*M)[9]) {
+    return geo_solve7(seed, pair, h, N, p1, p2, A, stride, M);
+  }
+  __device__ static inline int n_models(int st) { return st; }
+  __device__ static inline int code(int st, int q, int c) { return q < st ? c : -1; }
+  __device__ static inline bool inlier(const double* F, double x1, double y1, double x2, double y2, double th2) {
+    return geo_inlier(F, x1, y1, x2, y2, th2);
+  }
+  __device__ static inline int verdict(int c, int min_inliers) { return c >= min_inliers ? 1 : 0; }   // match_inliers.size() < 30 -> false
+};
 
-// The models of samples [h0, h1): grid (ceil((h1 - h0) / 64), n_slots), thread = sample.  lim (may be NULL): row y's budget;
-// samples at or past it can never be replayed and are written as "no model" without being drawn (the scoring skips them).
-__global__ __launch_bounds__(GEO_WAVE) void k_hransac_models(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ lim,
-                                                              const int* __restrict__ off, const float2* __restrict__ pt1,
-                                                              const float2* __restrict__ pt2, uint64_t seed, GeoHRec* __restrict__ models) {
-  __shared__ double A[72 * GEO_WAVE];
+struct HEstimator {
+  static constexpr int POINTS = 4, MODELS = 1, WORK = 72;   // WORK: the 8x9 matrix of hr_solve4
+  static constexpr int NO_MODEL = 1;                        // the status is hr_sample's
+  static constexpr bool HAS_STOP = true, TRIM = true;
+  static constexpr int NO_WINNER_MASK = 1;
+  static constexpr const char *T_SCORE = "geo_hransac_score", *T_REST = "geo_hransac_score_rest", *T_SELECT = "geo_hransac_select";
+  struct Rec { double M[1][9]; int st, pad; };
+  __device__ static inline int sample(uint64_t seed, int pair, int h, int N, const float2* __restrict__ p1, const float2* __restrict__ p2,
+                                      double* A, int stride, double (*M)[9]) {
+    return hr_sample(seed, pair, h, N, p1, p2, A, stride, M[0]);
+  }
+  __device__ static inline int n_models(int st) { return st == 0 ? 1 : 0; }
+  __device__ static inline int code(int st, int q, int c) { return st == 0 ? c : -st; }
+  __device__ static inline bool inlier(const double* H, double x1, double y1, double x2, double y2, double th2) {
+    return hr_inlier(H, x1, y1, x2, y2, th2);
+  }
+  __device__ static inline int verdict(int, int) { return 1; }
+};
+
+// The three kernels are `static`: the LDS arrays of a template kernel otherwise get linkonce linkage, which keeps the
+// compiler from trimming them (k_ransac_select then takes 16 / 24 bytes more than it needs).
+
+// The models of samples [h0, h1) of the pairs in `slot_pair`: grid (ceil((h1 - h0) / 64), n_slots), thread = sample.
+// models[slot][h - h0]: the sample's record.  lim (may be NULL): row y's budget; samples at or past it can never be replayed
+// and are written as "no model" without being drawn (the scoring skips them).  Compiled in with E::TRIM only.
+template <class E>
+static __global__ __launch_bounds__(GEO_WAVE) void k_ransac_models(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ lim,
+                                                             const int* __restrict__ off, const float2* __restrict__ pt1,
+                                                             const float2* __restrict__ pt2, uint64_t seed, typename E::Rec* __restrict__ models) {
+  __shared__ double A[E::WORK * GEO_WAVE];
   const int slot = blockIdx.y, pair = slot_pair[slot], h = h0 + blockIdx.x * GEO_WAVE + threadIdx.x;
   const int o = off[pair], N = off[pair + 1] - o;
   if (h >= h1) return;
-  double H[9];
-  const int st = lim && h >= lim[slot] ? 1 : hr_sample(seed, pair, h, N, pt1 + o, pt2 + o, A + threadIdx.x, GEO_WAVE, H);
-  GeoHRec* r = models + (size_t)slot * (h1 - h0) + (h - h0);
-  for (int k = 0; k < 9; k++) r->H[k] = st == 0 ? H[k] : 0.0;
+  double M[E::MODELS][9];
+  const int st = E::TRIM && lim && h >= lim[slot] ? E::NO_MODEL : E::sample(seed, pair, h, N, pt1 + o, pt2 + o, A + threadIdx.x, GEO_WAVE, M);
+  typename E::Rec* r = models + (size_t)slot * (h1 - h0) + (h - h0);
+  for (int q = 0; q < E::MODELS; q++)
+    for (int k = 0; k < 9; k++) r->M[q][k] = q < E::n_models(st) ? M[q][k] : 0.0;
   r->st = st;
   r->pad = 0;
 }
 
-// Inlier counts of those models (k_fransac_count's layout, one model per sample): counts[slot][cs] at sample co + (h - h0);
-// -1: the sample has no model, -2: no admissible subset.
-__global__ __launch_bounds__(256) void k_hransac_count(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ lim,
-                                                        const int* __restrict__ off,
-                                                        const float2* __restrict__ pt1, const float2* __restrict__ pt2, double th2,
-                                                        const GeoHRec* __restrict__ models, int* __restrict__ counts, int cs, int co) {
+// Inlier counts of those models: grid (ceil((h1 - h0) / 128), n_slots), 256 threads; the pair's correspondences wait in LDS
+// (1024 at a time), wave w takes samples [32 w, 32 w + 32) of the block's 128 one after the other, lane = correspondence.
+// counts[slot][cs samples][E::MODELS] (E::code): this launch's samples start at sample `co` of a slot's row (a range taken
+// in several pieces shares one array).
+#define GEO_CNT_SAMPLES 128
+template <class E>
+static __global__ __launch_bounds__(256) void k_ransac_count(int h0, int h1, const int* __restrict__ slot_pair, const int* __restrict__ lim,
+                                                       const int* __restrict__ off, const float2* __restrict__ pt1, const float2* __restrict__ pt2,
+                                                       double th2, const typename E::Rec* __restrict__ models, int* __restrict__ counts, int cs, int co) {
   __shared__ float4 pts[1024];
-  __shared__ int cnt_s[GEO_CNT_SAMPLES];
+  __shared__ int cnt_s[GEO_CNT_SAMPLES * E::MODELS];
   const int slot = blockIdx.y, pair = slot_pair[slot];
   const int o = off[pair], N = off[pair + 1] - o;
   const int HS = h1 - h0;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  const int s_first = blockIdx.x * GEO_CNT_SAMPLES + 32 * wave;
-  if (lim && h0 + (int)blockIdx.x * GEO_CNT_SAMPLES >= lim[slot]) {   // every sample of this block is past the budget
-    for (int e = threadIdx.x; e < GEO_CNT_SAMPLES; e += 256) {
-      const int hs = blockIdx.x * GEO_CNT_SAMPLES + e;
-      if (hs < HS) counts[(size_t)slot * cs + co + hs] = -1;
+  const int s_first = blockIdx.x * GEO_CNT_SAMPLES + 32 * wave;   // first sample (relative to h0) of this wave
+  if (E::TRIM && lim && h0 + (int)blockIdx.x * GEO_CNT_SAMPLES >= lim[slot]) {   // every sample of this block is past the budget
+    for (int e = threadIdx.x; e < GEO_CNT_SAMPLES * E::MODELS; e += 256) {
+      const int hs = blockIdx.x * GEO_CNT_SAMPLES + e / E::MODELS, q = e % E::MODELS;
+      if (hs < HS) counts[((size_t)slot * cs + co + hs) * E::MODELS + q] = E::code(E::NO_MODEL, q, 0);
     }
     return;
   }
-  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES; e += 256) cnt_s[e] = 0;
+  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES * E::MODELS; e += 256) cnt_s[e] = 0;
   for (int base = 0; base < N; base += 1024) {
     const int nb = min(1024, N - base);
     __syncthreads();
@@ -926,47 +578,47 @@ __global__ __launch_bounds__(256) void k_hransac_count(int h0, int h1, const int
     for (int j = 0; j < 32; j++) {
       const int hs = s_first + j;
       if (hs >= HS) break;
-      const GeoHRec* r = models + (size_t)slot * HS + hs;
-      if (r->st != 0) continue;
-      double H[9];
+      const typename E::Rec* r = models + (size_t)slot * HS + hs;   // (uniform over the wave: scalar loads)
+      const int nm = E::n_models(r->st);
+      for (int q = 0; q < nm; q++) {
+        double F[9];
 #pragma unroll
-      for (int k = 0; k < 9; k++) H[k] = r->H[k];
-      int c = 0;
-      for (int e = lane; e < nb; e += 64) {
-        const float4 p = pts[e];
-        c += hr_inlier(H, p.x, p.y, p.z, p.w, th2) ? 1 : 0;
+        for (int k = 0; k < 9; k++) F[k] = r->M[q][k];
+        int c = 0;
+        for (int e = lane; e < nb; e += 64) {
+          const float4 p = pts[e];
+          c += E::inlier(F, p.x, p.y, p.z, p.w, th2) ? 1 : 0;
+        }
+        c = wave_sum_int(c);
+        if (lane == 0) cnt_s[(32 * wave + j) * E::MODELS + q] += c;   // (only this wave touches these entries)
       }
-      for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
-      if (lane == 0) cnt_s[32 * wave + j] += c;
     }
   }
   __syncthreads();
-  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES; e += 256) {
-    const int hs = blockIdx.x * GEO_CNT_SAMPLES + e;
-    if (hs < HS) {
-      const int st = models[(size_t)slot * HS + hs].st;
-      counts[(size_t)slot * cs + co + hs] = st == 0 ? cnt_s[e] : -st;
-    }
+  for (int e = threadIdx.x; e < GEO_CNT_SAMPLES * E::MODELS; e += 256) {
+    const int hs = blockIdx.x * GEO_CNT_SAMPLES + e / E::MODELS, q = e % E::MODELS;
+    if (hs < HS) counts[((size_t)slot * cs + co + hs) * E::MODELS + q] = E::code(models[(size_t)slot * HS + hs].st, q, cnt_s[e]);
   }
 }
 
-// One wave per pair: replay runRANSAC's loop over the counts (two passes as k_fransac_select), recompute the winning
-// sample's model, write H (unpolished), the mask, n_inliers and ok.  No winner: H = 0, mask all ones, n_inliers = N.
-// H = max_iterations (the loop's first budget); pass 1 replays samples [0, H1) and, for a pair whose budget b is still
-// above H1, appends it to need_list and raises *need_max to b.  Pass 2 replays [0, Hs) with Hs = that maximum: the replay
-// of [0, H1) reaches the same budget b <= Hs again, and the budget only shrinks, so no sample at or past Hs can be reached;
-// counts2 holds samples [H1, Hs) of the k-th listed pair at row k.
-__global__ __launch_bounds__(GEO_WAVE) void k_hransac_select(int H, int Hs, int H1, int pass, const int* __restrict__ slot_pair, int* __restrict__ need_list,
-                                                              int* __restrict__ need_count, int* __restrict__ need_max, int* __restrict__ need_budget,
-                                                              const int* __restrict__ off, const float2* __restrict__ pt1,
-                                                              const float2* __restrict__ pt2, uint64_t seed, double th2,
-                                                              const int* __restrict__ counts1, const int* __restrict__ counts2,
-                                                              const int* __restrict__ niters_tab, const int* __restrict__ tab_off, double* __restrict__ Hout,
-                                                              uint8_t* __restrict__ inlier, int* __restrict__ n_inliers, uint8_t* __restrict__ ok) {
-  __shared__ double A[72];
-  __shared__ double Hw[9];
+// One wave per pair: replay the sequential loop over the counts, recompute the winning sample's model, write the matrix
+// (H: unpolished), the mask, n_inliers and the verdict.  H = max_iterations (the loop's first budget); pass 1 (grid = the
+// admitted pairs, `slot_pair`) replays samples [0, H1) and, for a pair whose budget b is still above H1, appends it to
+// need_list and (E::TRIM) records b in need_budget and raises *need_max to b; the others are final.  Pass 2 (grid = that
+// list) replays [0, Hs): the replay of [0, H1) reaches the same budget b <= Hs again, and the budget only shrinks, so no sample at or past
+// Hs can be reached; counts2 holds samples [H1, Hs) of the k-th listed pair at row k.
+template <class E>
+static __global__ __launch_bounds__(GEO_WAVE) void k_ransac_select(int H, int Hs, int H1, int pass, const int* __restrict__ slot_pair, int* __restrict__ need_list,
+                                                             int* __restrict__ need_count, int* __restrict__ need_max, int* __restrict__ need_budget,
+                                                             const int* __restrict__ off, const float2* __restrict__ pt1,
+                                                             const float2* __restrict__ pt2, uint64_t seed, double th2, int min_inliers,
+                                                             const int* __restrict__ counts1, const int* __restrict__ counts2,
+                                                             const int* __restrict__ niters_tab, const int* __restrict__ tab_off, double* __restrict__ Mout,
+                                                             uint8_t* __restrict__ inlier, int* __restrict__ n_inliers, uint8_t* __restrict__ ok) {
+  __shared__ double A[E::WORK];
+  __shared__ double Mw[9];
   __shared__ int win[3];
-  __shared__ int cl[1024];
+  __shared__ int cl[E::MODELS * 1024];
   const int lane = threadIdx.x;
   if (pass == 2 && (int)blockIdx.x >= *need_count) return;
   const int slot = pass == 2 ? need_list[blockIdx.x] : (int)blockIdx.x;
@@ -975,75 +627,367 @@ __global__ __launch_bounds__(GEO_WAVE) void k_hransac_select(int H, int Hs, int 
   const int Hscan = pass == 1 ? H1 : Hs;
   if (lane == 0) { win[0] = -1; win[1] = 0; win[2] = H; }
   {
-    const int* R = niters_tab + tab_off[pair];
-    int best = 3;   // a model must beat modelPoints - 1
+    const int* R = niters_tab + tab_off[pair];  // N + 1 entries (the table of this N)
+    int best = E::POINTS - 1;                   // a model must beat modelPoints - 1
     for (int h0 = 0; h0 < Hscan; h0 += 1024) {
       __syncthreads();
-      if (h0 >= win[2]) break;
+      if (h0 >= win[2]) break;  // uniform: win[2] is shared
       const int nh = min(1024, Hscan - h0);
-      for (int e = lane; e < nh; e += GEO_WAVE) {
-        const int h = h0 + e;
-        cl[e] = h < H1 ? counts1[(size_t)slot * H1 + h] : counts2[(size_t)blockIdx.x * (Hs - H1) + (h - H1)];
+      for (int e = lane; e < E::MODELS * nh; e += GEO_WAVE) {
+        const int h = h0 + e / E::MODELS, q = e % E::MODELS;
+        cl[e] = h < H1 ? counts1[((size_t)slot * H1 + h) * E::MODELS + q]
+                       : counts2[((size_t)blockIdx.x * (Hs - H1) + (h - H1)) * E::MODELS + q];
       }
       __syncthreads();
       if (lane == 0) {
         int niters = win[2];
-        for (int h = h0; h < h0 + nh && h < niters; h++) {
-          const int g = cl[h - h0];
-          if (g == -2) { niters = h; break; }   // getSubset failed: the loop ends (at h = 0 without a model)
-          if (g > best) {
-            best = g; win[0] = h;
-            const int r = R[g];
-            if (r < niters) niters = r;
+        for (int h = h0; h < h0 + nh && h < niters; h++)
+          for (int q = 0; q < E::MODELS; q++) {
+            const int g = cl[(h - h0) * E::MODELS + q];
+            // getSubset failed: the loop over h ends (at h = 0 without a model) - niters = h stops it, `break` only leaves the q loop
+            if (E::HAS_STOP && g == -2) { niters = h; break; }
+            if (g > best) {
+              best = g; win[0] = h; win[1] = q;
+              const int r = R[g];
+              if (r < niters) niters = r;
+            }
           }
-        }
         win[2] = niters;
       }
     }
   }
   __syncthreads();
   if (pass == 1) {
-    const bool more = win[2] > H1 && H1 < H;
+    const bool more = win[2] > H1 && H1 < H;  // the sequential loop would have gone on past H1
     if (more) {
       if (lane == 0) {
         const int k = atomicAdd(need_count, 1);
         need_list[k] = slot;
-        need_budget[k] = win[2];
-        atomicMax(need_max, win[2]);
+        if (E::TRIM) {   // (an estimator that does not trim records nothing: profiles/ransac_core_ab.jsonl, the variant lines, has the cost)
+          need_budget[k] = win[2];
+          atomicMax(need_max, win[2]);
+        }
       }
       return;
     }
   }
   const int wh = win[0];
   if (wh < 0) {
-    for (int e = lane; e < N; e += GEO_WAVE) inlier[o + e] = 1;
+    for (int e = lane; e < N; e += GEO_WAVE) inlier[o + e] = E::NO_WINNER_MASK;
     if (lane == 0) {
-      for (int k = 0; k < 9; k++) Hout[(size_t)pair * 9 + k] = 0.0;
-      n_inliers[pair] = N;
+      for (int k = 0; k < 9; k++) Mout[(size_t)pair * 9 + k] = 0.0;
+      n_inliers[pair] = E::NO_WINNER_MASK ? N : 0;
       ok[pair] = 0;
     }
     return;
   }
   if (lane == 0) {
-    double Hm[9];
-    hr_sample(seed, pair, wh, N, pt1 + o, pt2 + o, A, 1, Hm);
-    for (int k = 0; k < 9; k++) { Hw[k] = Hm[k]; Hout[(size_t)pair * 9 + k] = Hm[k]; }
+    double M[E::MODELS][9];
+    E::sample(seed, pair, wh, N, pt1 + o, pt2 + o, A, 1, M);
+    for (int k = 0; k < 9; k++) { Mw[k] = M[E::MODELS > 1 ? win[1] : 0][k]; Mout[(size_t)pair * 9 + k] = Mw[k]; }
   }
   __syncthreads();
-  double Hm[9];
-  for (int k = 0; k < 9; k++) Hm[k] = Hw[k];
+  double F[9];
+  for (int k = 0; k < 9; k++) F[k] = Mw[k];
   int c = 0;
   for (int e = lane; e < N; e += GEO_WAVE) {
     const float2 a = pt1[o + e], b = pt2[o + e];
-    const bool in = hr_inlier(Hm, a.x, a.y, b.x, b.y, th2);
+    const bool in = E::inlier(F, a.x, a.y, b.x, b.y, th2);
     inlier[o + e] = in ? 1 : 0;
     c += in ? 1 : 0;
   }
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  c = wave_sum_int(c);
   if (lane == 0) {
     n_inliers[pair] = c;
-    ok[pair] = 1;
+    ok[pair] = E::verdict(c, min_inliers);
   }
+}
+
+// l = F [x1, y1, 1]; l /= hypot(l0, l1); inlier iff |l . [x2, y2, 1]| < th   (geo_verification.cc:60-79),
+// for every pair whose F was accepted.
+__global__ __launch_bounds__(256) void k_epipolar_batch(int total, const int* __restrict__ pair_of, const float2* __restrict__ pt1,
+                                                         const float2* __restrict__ pt2, const double* __restrict__ F,
+                                                         const uint8_t* __restrict__ ok, double th, uint8_t* __restrict__ inlier) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  const int p = pair_of[e];
+  if (ok && !ok[p]) { inlier[e] = 0; return; }
+  const double* f = F + (size_t)p * 9;
+  const double x1 = pt1[e].x, y1 = pt1[e].y, x2 = pt2[e].x, y2 = pt2[e].y;
+  double l0 = f[0] * x1 + f[1] * y1 + f[2];
+  double l1 = f[3] * x1 + f[4] * y1 + f[5];
+  double l2 = f[6] * x1 + f[7] * y1 + f[8];
+  const double n = sqrt(l0 * l0 + l1 * l1);
+  l0 = l0 / n; l1 = l1 / n; l2 = l2 / n;
+  const double dis = l0 * x2 + l1 * y2 + l2;
+  inlier[e] = fabs(dis) < th ? 1 : 0;
+}
+
+__global__ void k_gather_int(int n, const int* __restrict__ idx, const int* __restrict__ src, int* __restrict__ dst) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) dst[i] = src[idx[i]];
+}
+
+// cvRANSACUpdateNumIters(p, ep, model_points, max_iters) for ep = (N - g) / N, clamped to max_iters
+static int geo_update_num_iters(double p, double ep, int model_points, int max_iters) {
+  p = std::max(p, 0.0); p = std::min(p, 1.0);
+  ep = std::max(ep, 0.0); ep = std::min(ep, 1.0);
+  double num = std::max(1.0 - p, DBL_MIN);
+  double denom = 1.0 - std::pow(1.0 - ep, model_points);
+  if (denom < DBL_MIN) return 0;
+  num = std::log(num);
+  denom = std::log(denom);
+  if (denom >= 0 || -num >= max_iters * (-denom)) return max_iters;
+  return (int)std::lrint(num / denom);
+}
+
+// R[g] = cvRANSACUpdateNumIters(confidence, (N - g) / N, E::POINTS, H) for g inliers of N: a pow and two logs per entry.  The
+// table of a pair depends on its N alone, so one table per DISTINCT N is formed (and kept from call to call while confidence
+// and sample limit stay the same: the matching loop verifies thousands of pairs with one set of options) - at 9 120 pairs of
+// ~125 good matches each the per-pair tables were 1.1 M evaluations, 7 of the 15 ms of msfm_chain_verify on sixteen host
+// threads.  tab: the tables of this call's admitted pairs back to back, tab_off[p]: where pair p's begins (0 for a pair that
+// is not admitted: the kernels do not look at its table).  One cache per estimator (the static below).
+template <class E>
+static void ransac_iter_tables(double confidence, int H, int n_pairs, const int* offsets, const std::vector<int>& slot_pair,
+                               std::vector<int>& tab, std::vector<int>& tab_off) {
+  struct TabCache { std::mutex mu; double conf = -1.0; int H = -1; std::unordered_map<int, std::vector<int>> by_n; size_t entries = 0; };
+  static TabCache cache;
+  tab.clear();
+  tab_off.assign(std::max(1, n_pairs), 0);
+  std::lock_guard<std::mutex> lock(cache.mu);
+  if (cache.conf != confidence || cache.H != H || cache.entries > (size_t)32 << 20) {
+    cache.by_n.clear(); cache.entries = 0; cache.conf = confidence; cache.H = H;
+  }
+  std::vector<int> missing;
+  for (int p : slot_pair) {
+    const int N = offsets[p + 1] - offsets[p];
+    if (cache.by_n.find(N) == cache.by_n.end()) { cache.by_n[N]; missing.push_back(N); }
+  }
+  std::vector<std::vector<int>*> slot(missing.size());
+  for (size_t k = 0; k < missing.size(); k++) { slot[k] = &cache.by_n[missing[k]]; slot[k]->resize((size_t)missing[k] + 1); cache.entries += (size_t)missing[k] + 1; }
+  par_ranges(missing.size(), host_threads(), [&](int, size_t k0, size_t k1) {
+    for (size_t k = k0; k < k1; k++) {
+      const int N = missing[k];
+      int* R = slot[k]->data();
+      for (int g = 0; g <= N; g++) R[g] = geo_update_num_iters(confidence, (double)(N - g) / N, E::POINTS, H);
+    }
+  }, 4);
+  std::unordered_map<int, int> at;   // N -> offset of its table in this call's upload
+  for (int p : slot_pair) {
+    const int N = offsets[p + 1] - offsets[p];
+    auto it = at.find(N);
+    if (it == at.end()) {
+      it = at.emplace(N, (int)tab.size()).first;
+      const std::vector<int>& R = cache.by_n[N];
+      tab.insert(tab.end(), R.begin(), R.end());
+    }
+    tab_off[p] = it->second;
+  }
+  if (tab.empty()) tab.push_back(H);   // (no admitted pair: the upload is never empty)
+}
+
+struct RansacRun { int H; double confidence, th2; uint64_t seed; int min_inliers; };
+// The device buffers of one run.  The driver only enqueues: its caller keeps these until it has synchronised the stream.
+template <class E>
+struct RansacWork {
+  DevBuf<int> tab_off, tab, slot_pair, need, budget, counts1, counts2, need_pair;
+  DevBuf<typename E::Rec> models1, models2;
+};
+
+// The two passes for the pairs in slot_pair (not empty) on points that are already resident: d_off (device) and offsets (host)
+// delimit the pairs' correspondences in p1 / p2; the results of the listed pairs go to dM, d_in, d_nin, d_ok.  Ends with
+// work enqueued on the stream (after a second pass: with that pass enqueued).
+template <class E>
+static int ransac_two_pass(msfm_ctx* ctx, const RansacRun& run, int n_pairs, const int* offsets, const int* d_off, const float2* p1,
+                           const float2* p2, const std::vector<int>& slot_pair, RansacWork<E>& w, double* dM, uint8_t* d_in, int* d_nin,
+                           uint8_t* d_ok) {
+  hipStream_t s = ctx->stream;
+  const int H = run.H, n_slots = (int)slot_pair.size();
+  std::vector<int> tab, tab_off;
+  ransac_iter_tables<E>(run.confidence, H, n_pairs, offsets, slot_pair, tab, tab_off);
+  HIP_TRY(ctx, w.tab_off.from(tab_off, s));
+  HIP_TRY(ctx, w.tab.from(tab, s));
+  // Most pairs stop after a few dozen samples (cvRANSACUpdateNumIters): score the first H1 samples of every pair,
+  // replay them, and run the remaining samples only for the pairs whose budget is still open.
+  const int H1 = std::min(H, 128);
+  HIP_TRY(ctx, w.slot_pair.from(slot_pair, s));
+  HIP_TRY(ctx, w.need.alloc((size_t)n_slots + 2));   // [0]: how many, [1]: their largest budget, [2..]: the slots
+  if (E::TRIM) HIP_TRY(ctx, w.budget.alloc(n_slots));   // the budget of each listed slot after pass 1 (without E::TRIM: none, and [1] stays 0)
+  HIP_TRY(ctx, hipMemsetAsync(w.need.p, 0, 2 * sizeof(int), s));
+  HIP_TRY(ctx, w.counts1.alloc((size_t)n_slots * H1 * E::MODELS));
+  HIP_TRY(ctx, w.models1.alloc((size_t)n_slots * H1));
+  // the models of a sample range live in memory only between the two kernels: a long range is taken in pieces of `piece`
+  // samples that reuse one model buffer (F: 224 bytes per sample and pair: 1 872 samples at once would be 420 KB per pair)
+  auto score = [&](int h0, int h1, int piece, int ns, const int* slots, const int* lim, typename E::Rec* models, int* counts, const char* name) {
+    KTimer t(ctx, name);
+    for (int a = h0; a < h1; a += piece) {
+      const int b = std::min(h1, a + piece);
+      for (int q0 = 0; q0 < ns; q0 += 32768) {   // grid.y limit
+        const int np = std::min(32768, ns - q0);
+        const int* lq = lim ? lim + q0 : (const int*)nullptr;
+        hipLaunchKernelGGL(k_ransac_models<E>, dim3(cdiv(b - a, GEO_WAVE), np), dim3(GEO_WAVE), 0, s, a, b, slots + q0, lq, d_off, p1, p2, run.seed,
+                           models + (size_t)q0 * piece);
+        hipLaunchKernelGGL(k_ransac_count<E>, dim3(cdiv(b - a, GEO_CNT_SAMPLES), np), dim3(256), 0, s, a, b, slots + q0, lq, d_off, p1, p2, run.th2,
+                           models + (size_t)q0 * piece, counts + (size_t)q0 * (h1 - h0) * E::MODELS, h1 - h0, a - h0);
+      }
+    }
+  };
+  auto select = [&](int pass, int grid, int Hs) {
+    KTimer t(ctx, E::T_SELECT);
+    hipLaunchKernelGGL(k_ransac_select<E>, dim3(grid), dim3(GEO_WAVE), 0, s, H, Hs, H1, pass, w.slot_pair.p, w.need.p + 2, w.need.p, w.need.p + 1,
+                       w.budget.p, d_off, p1, p2, run.seed, run.th2, run.min_inliers, w.counts1.p, w.counts2.p, w.tab.p, w.tab_off.p, dM, d_in,
+                       d_nin, d_ok);
+  };
+  score(0, H1, H1, n_slots, w.slot_pair.p, nullptr, w.models1.p, w.counts1.p, E::T_SCORE);
+  select(1, n_slots, H1);
+  if (H1 < H) {
+    int need[2] = {0, 0};   // pairs still open after the first H1 samples, and the largest budget among them
+    HIP_TRY(ctx, hipMemcpyAsync(need, w.need.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIP_TRY(ctx, hipStreamSynchronize(s));
+    const int n_need = need[0];
+    if (n_need > 0) {
+      // samples at or past a pair's budget can never be replayed.  E::TRIM: score [H1, Hs) only, Hs = the largest open budget
+      // (<= H), and within it each pair's samples below its own budget (w.budget, in need-list order); otherwise all of [H1, H)
+      const int Hs = E::TRIM ? std::min(H, need[1]) : H;
+      const int piece = std::min(Hs - H1, 256);
+      HIP_TRY(ctx, w.counts2.alloc((size_t)n_need * (Hs - H1) * E::MODELS));
+      HIP_TRY(ctx, w.models2.alloc((size_t)n_need * piece));
+      // the list holds SLOTS; the kernels of the second range want pairs
+      HIP_TRY(ctx, w.need_pair.alloc(n_need));
+      hipLaunchKernelGGL(k_gather_int, dim3(cdiv(n_need, 256)), dim3(256), 0, s, n_need, w.need.p + 2, w.slot_pair.p, w.need_pair.p);
+      score(H1, Hs, piece, n_need, w.need_pair.p, E::TRIM ? w.budget.p : (const int*)nullptr, w.models2.p, w.counts2.p, E::T_REST);
+      select(2, n_need, Hs);
+    }
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return MSFM_OK;
+}
+
+// Behind the two public batch calls: upload the offsets and the two point arrays, allocate the four outputs, run(d_off, d1,
+// d2, dM, d_in, d_nin, d_ok), download.
+template <class Run>
+static int ransac_batch_io(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2, double* M, uint8_t* inlier,
+                           int* n_inliers, uint8_t* ok, Run&& run) {
+  const int total = offsets[n_pairs];
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf<int> d_off, d_nin;
+  DevBuf<float> d1, d2;
+  DevBuf<double> dM;
+  DevBuf<uint8_t> d_in, d_ok;
+  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
+  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
+  HIP_TRY(ctx, d1.alloc(2 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d2.alloc(2 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s));
+  HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
+  HIP_TRY(ctx, dM.alloc((size_t)n_pairs * 9));
+  HIP_TRY(ctx, d_in.alloc((size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_nin.alloc(n_pairs));
+  HIP_TRY(ctx, d_ok.alloc(n_pairs));
+  MSFM_TRY(run(d_off.p, d1.p, d2.p, dM.p, d_in.p, d_nin.p, d_ok.p));
+  HIP_TRY(ctx, hipMemcpyAsync(M, dM.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  if (total) HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(n_inliers, d_nin.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return MSFM_OK;
+}
+
+MSFM_API void msfm_fransac_default_options(msfm_fransac_options* o) {
+  if (!o) return;
+  o->threshold = 3.0;
+  o->confidence = 0.99;
+  o->max_iterations = 2000;
+  o->min_points = 30;
+  o->min_inliers = 30;
+  o->seed = 0x4D53464D46ull;
+}
+
+// The verification of a batch of pairs on points that are already resident: d1 / d2 hold the pairs' matches back to back,
+// h_offsets (host) and d_off (device) delimit them; results stay on the device.  msfm_fundamental_ransac_batch is this
+// between an upload and a download, msfm_chain_verify (chain.hip) calls it on points gathered from the match codes.
+int geo_fransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d_off, const float* d1, const float* d2,
+                    const msfm_fransac_options* opt, double* dF, uint8_t* d_in, int* d_nin, uint8_t* d_ok) {
+  hipStream_t s = ctx->stream;
+  // pairs without enough matches (GeoVerificationFundamental: pt1.size() < 30 -> false) get their verdict here; the others
+  // form the slot list the kernels run over
+  std::vector<int> slot_pair;
+  for (int p = 0; p < n_pairs; p++) {
+    const int N = offsets[p + 1] - offsets[p];
+    if (N >= opt->min_points && N >= 8) slot_pair.push_back(p);
+  }
+  HIP_TRY(ctx, hipMemsetAsync(dF, 0, sizeof(double) * 9 * (size_t)n_pairs, s));
+  HIP_TRY(ctx, hipMemsetAsync(d_in, 0, (size_t)std::max(1, offsets[n_pairs]), s));
+  HIP_TRY(ctx, hipMemsetAsync(d_nin, 0, sizeof(int) * (size_t)n_pairs, s));
+  HIP_TRY(ctx, hipMemsetAsync(d_ok, 0, (size_t)n_pairs, s));
+  RansacWork<FEstimator> w;
+  if (!slot_pair.empty())
+    MSFM_TRY(ransac_two_pass<FEstimator>(ctx, {opt->max_iterations, opt->confidence, opt->threshold * opt->threshold, opt->seed, opt->min_inliers},
+                                         n_pairs, offsets, d_off, reinterpret_cast<const float2*>(d1), reinterpret_cast<const float2*>(d2),
+                                         slot_pair, w, dF, d_in, d_nin, d_ok));
+  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the buffers of the run are released on return)
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_fundamental_ransac_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
+                                           const msfm_fransac_options* opt, double* F, uint8_t* inlier, int* n_inliers, uint8_t* ok) {
+  if (!ctx || n_pairs < 0 || !offsets || !opt || !F || !n_inliers || !ok) return MSFM_E_INVAL;
+  if (opt->max_iterations < 1 || opt->max_iterations > 65536 || !(opt->threshold > 0.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: bad options");
+  if (n_pairs == 0) return MSFM_OK;
+  MSFM_TRY(msfm_check_offsets(ctx, "fransac", n_pairs, offsets));
+  if (offsets[n_pairs] > 0 && (!pt1 || !pt2 || !inlier)) return MSFM_E_INVAL;
+  return ransac_batch_io(ctx, n_pairs, offsets, pt1, pt2, F, inlier, n_inliers, ok,
+                         [&](const int* d_off, const float* d1, const float* d2, double* dF, uint8_t* d_in, int* d_nin, uint8_t* d_ok) {
+                           return geo_fransac_dev(ctx, n_pairs, offsets, d_off, d1, d2, opt, dF, d_in, d_nin, d_ok);
+                         });
+}
+
+// The closed-form filter of a batch on resident points (pair_of[e] = pair of match e): msfm_epipolar_filter_batch without its
+// transfers; msfm_chain_verify calls it on the "all" sets gathered from the match codes.
+int geo_epipolar_batch_dev(msfm_ctx* ctx, int total, const int* d_pair_of, const float* d1, const float* d2, const double* dF,
+                           const uint8_t* d_ok, double th, uint8_t* d_in) {
+  if (total == 0) return MSFM_OK;
+  KTimer t(ctx, "geo_epipolar_filter");
+  hipLaunchKernelGGL(k_epipolar_batch, dim3(cdiv(total, 256)), dim3(256), 0, ctx->stream, total, d_pair_of, reinterpret_cast<const float2*>(d1),
+                     reinterpret_cast<const float2*>(d2), dF, d_ok, th, d_in);
+  HIP_TRY(ctx, hipGetLastError());
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_epipolar_filter_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
+                                        const double* F, const uint8_t* ok, double th, uint8_t* inlier) {
+  if (!ctx || n_pairs < 0 || !offsets || !F) return MSFM_E_INVAL;
+  if (n_pairs == 0) return MSFM_OK;
+  const int total = offsets[n_pairs];
+  if (total == 0) return MSFM_OK;
+  if (!pt1 || !pt2 || !inlier) return MSFM_E_INVAL;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  std::vector<int> pair_of(total);
+  for (int p = 0; p < n_pairs; p++) {
+    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "epipolar: offsets must be non-decreasing");
+    for (int e = offsets[p]; e < offsets[p + 1]; e++) pair_of[e] = p;
+  }
+  DevBuf<int> d_po;
+  DevBuf<float> d1, d2;
+  DevBuf<double> dF;
+  DevBuf<uint8_t> d_in, d_ok;
+  HIP_TRY(ctx, d_po.from(pair_of, s));
+  HIP_TRY(ctx, d1.alloc(2 * (size_t)total)); HIP_TRY(ctx, d2.alloc(2 * (size_t)total));
+  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s)); HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
+  HIP_TRY(ctx, dF.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, dF.upload(F, 9 * (size_t)n_pairs, s));
+  HIP_TRY(ctx, d_in.alloc(total));
+  if (ok) { HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_ok.upload(ok, n_pairs, s)); }
+  {
+    KTimer t(ctx, "geo_epipolar_filter");
+    hipLaunchKernelGGL(k_epipolar_batch, dim3(cdiv(total, 256)), dim3(256), 0, s, total, d_po.p, reinterpret_cast<const float2*>(d1.p),
+                       reinterpret_cast<const float2*>(d2.p), dF.p, ok ? d_ok.p : nullptr, th, d_in.p);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return MSFM_OK;
 }
 
 __device__ static inline double hr_wave_sum(double v) {
@@ -1052,7 +996,7 @@ __device__ static inline double hr_wave_sum(double v) {
 }
 
 // Pairs with N == 4 (cvFindHomography: the direct fit, mask all ones) and N < 4 (no model, mask 0), and pairs the caller
-// left out (as "no model").  One wave per pair; pairs with N > 4 that run RANSAC are left to k_hransac_select.
+// left out (as "no model").  One wave per pair; pairs with N > 4 that run RANSAC are left to k_ransac_select.
 __global__ __launch_bounds__(GEO_WAVE) void k_hransac_small(int n_pairs, const int* __restrict__ off, const uint8_t* __restrict__ active,
                                                              const float2* __restrict__ pt1, const float2* __restrict__ pt2, double* __restrict__ Hout,
                                                              uint8_t* __restrict__ inlier, int* __restrict__ n_inliers, uint8_t* __restrict__ ok) {
@@ -1249,15 +1193,12 @@ int geo_hransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d
                     const msfm_hransac_options* opt, const uint8_t* active, double* dH, uint8_t* d_in, int* d_nin, uint8_t* d_ok) {
   hipStream_t s = ctx->stream;
   if (n_pairs == 0) return MSFM_OK;
-  const int H = opt->max_iterations;
   const double thr = opt->threshold > 0.0 ? opt->threshold : 3.0;
-  const double th2 = thr * thr;
   const float2* p1 = reinterpret_cast<const float2*>(d1);
   const float2* p2 = reinterpret_cast<const float2*>(d2);
   std::vector<int> slot_pair;
   for (int p = 0; p < n_pairs; p++)
     if (offsets[p + 1] - offsets[p] > 4 && (!active || active[p])) slot_pair.push_back(p);
-  const int n_slots = (int)slot_pair.size();
   DevBuf<uint8_t> d_active;
   if (active) {
     HIP_TRY(ctx, d_active.alloc(n_pairs));
@@ -1269,101 +1210,17 @@ int geo_hransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d
                        p1, p2, dH, d_in, d_nin, d_ok);
   }
   HIP_TRY(ctx, hipGetLastError());
-  if (n_slots == 0) { HIP_TRY(ctx, hipStreamSynchronize(s)); return MSFM_OK; }
-  // R[g] = cvRANSACUpdateNumIters(conf, (N - g) / N, 4, H): one table per distinct N, kept while the options stay the same
-  std::vector<int> tab, tab_off(n_pairs, 0);
-  {
-    struct TabCache { std::mutex mu; double conf = -1.0; int H = -1; std::unordered_map<int, std::vector<int>> by_n; size_t entries = 0; };
-    static TabCache cache;
-    std::lock_guard<std::mutex> lock(cache.mu);
-    if (cache.conf != opt->confidence || cache.H != H || cache.entries > (size_t)32 << 20) {
-      cache.by_n.clear(); cache.entries = 0; cache.conf = opt->confidence; cache.H = H;
+  RansacWork<HEstimator> w;
+  if (!slot_pair.empty()) {
+    MSFM_TRY(ransac_two_pass<HEstimator>(ctx, {opt->max_iterations, opt->confidence, thr * thr, opt->seed, 0}, n_pairs, offsets, d_off, p1, p2,
+                                         slot_pair, w, dH, d_in, d_nin, d_ok));
+    if (opt->polish) {
+      KTimer t(ctx, "geo_hransac_polish");
+      hipLaunchKernelGGL(k_hransac_polish, dim3((int)slot_pair.size()), dim3(GEO_WAVE), 0, s, w.slot_pair.p, d_off, p1, p2, d_ok, d_in, dH);
     }
-    std::vector<int> missing;
-    for (int p : slot_pair) {
-      const int N = offsets[p + 1] - offsets[p];
-      if (cache.by_n.find(N) == cache.by_n.end()) { cache.by_n[N]; missing.push_back(N); }
-    }
-    std::vector<std::vector<int>*> slot(missing.size());
-    for (size_t k = 0; k < missing.size(); k++) { slot[k] = &cache.by_n[missing[k]]; slot[k]->resize((size_t)missing[k] + 1); cache.entries += (size_t)missing[k] + 1; }
-    par_ranges(missing.size(), host_threads(), [&](int, size_t k0, size_t k1) {
-      for (size_t k = k0; k < k1; k++) {
-        const int N = missing[k];
-        int* R = slot[k]->data();
-        for (int g = 0; g <= N; g++) R[g] = geo_update_num_iters(opt->confidence, (double)(N - g) / N, 4, H);
-      }
-    }, 4);
-    std::unordered_map<int, int> at;
-    for (int p : slot_pair) {
-      const int N = offsets[p + 1] - offsets[p];
-      auto it = at.find(N);
-      if (it == at.end()) {
-        it = at.emplace(N, (int)tab.size()).first;
-        const std::vector<int>& R = cache.by_n[N];
-        tab.insert(tab.end(), R.begin(), R.end());
-      }
-      tab_off[p] = it->second;
-    }
+    HIP_TRY(ctx, hipGetLastError());
   }
-  DevBuf<int> d_tab_off, d_tab, d_slot_pair, d_need, d_budget, d_counts1, d_counts2;
-  DevBuf<GeoHRec> d_models1, d_models2;
-  HIP_TRY(ctx, d_tab_off.from(tab_off, s));
-  HIP_TRY(ctx, d_tab.from(tab, s));
-  const int H1 = std::min(H, 128);
-  HIP_TRY(ctx, d_slot_pair.from(slot_pair, s));
-  HIP_TRY(ctx, d_need.alloc((size_t)n_slots + 2));   // [0]: how many, [1]: their largest budget, [2..]: the slots
-  HIP_TRY(ctx, d_budget.alloc(n_slots));               // the budget of each listed slot after pass 1
-  HIP_TRY(ctx, hipMemsetAsync(d_need.p, 0, 2 * sizeof(int), s));
-  HIP_TRY(ctx, d_counts1.alloc((size_t)n_slots * H1));
-  HIP_TRY(ctx, d_models1.alloc((size_t)n_slots * H1));
-  auto score = [&](int h0, int h1, int piece, int ns, const int* slots, const int* lim, GeoHRec* models, int* counts, const char* name) {
-    KTimer t(ctx, name);
-    for (int a = h0; a < h1; a += piece) {
-      const int b = std::min(h1, a + piece);
-      for (int q0 = 0; q0 < ns; q0 += 32768) {   // grid.y limit
-        const int np = std::min(32768, ns - q0);
-        hipLaunchKernelGGL(k_hransac_models, dim3(cdiv(b - a, GEO_WAVE), np), dim3(GEO_WAVE), 0, s, a, b, slots + q0, lim ? lim + q0 : (const int*)nullptr,
-                           d_off, p1, p2, opt->seed, models + (size_t)q0 * piece);
-        hipLaunchKernelGGL(k_hransac_count, dim3(cdiv(b - a, GEO_CNT_SAMPLES), np), dim3(256), 0, s, a, b, slots + q0, lim ? lim + q0 : (const int*)nullptr,
-                           d_off, p1, p2, th2,
-                           models + (size_t)q0 * piece, counts + (size_t)q0 * (h1 - h0), h1 - h0, a - h0);
-      }
-    }
-  };
-  auto select = [&](int pass, int grid, int Hs) {
-    KTimer t(ctx, "geo_hransac_select");
-    hipLaunchKernelGGL(k_hransac_select, dim3(grid), dim3(GEO_WAVE), 0, s, H, Hs, H1, pass, d_slot_pair.p, d_need.p + 2, d_need.p, d_need.p + 1,
-                       d_budget.p, d_off, p1, p2, opt->seed, th2, d_counts1.p, d_counts2.p, d_tab.p, d_tab_off.p, dH, d_in, d_nin, d_ok);
-  };
-  score(0, H1, H1, n_slots, d_slot_pair.p, nullptr, d_models1.p, d_counts1.p, "geo_hransac_score");
-  select(1, n_slots, H1);
-  if (H1 < H) {
-    int need[2] = {0, 0};   // pairs still open after the first H1 samples, and the largest budget among them
-    HIP_TRY(ctx, hipMemcpyAsync(need, d_need.p, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    const int n_need = need[0];
-    if (n_need > 0) {
-      // samples at or past a pair's budget can never be replayed: score [H1, Hs) only, Hs = the largest open budget (<= H),
-      // and within it each pair's samples below its own budget (d_budget, in need-list order)
-      const int Hs = std::min(H, need[1]);
-      const int piece = std::min(Hs - H1, 256);
-      HIP_TRY(ctx, d_counts2.alloc((size_t)n_need * (Hs - H1)));
-      HIP_TRY(ctx, d_models2.alloc((size_t)n_need * piece));
-      DevBuf<int> d_need_pair;
-      HIP_TRY(ctx, d_need_pair.alloc(n_need));
-      hipLaunchKernelGGL(k_gather_int, dim3(cdiv(n_need, 256)), dim3(256), 0, s, n_need, d_need.p + 2, d_slot_pair.p, d_need_pair.p);
-      score(H1, Hs, piece, n_need, d_need_pair.p, d_budget.p, d_models2.p, d_counts2.p, "geo_hransac_score_rest");
-      select(2, n_need, Hs);
-      HIP_TRY(ctx, hipGetLastError());
-      HIP_TRY(ctx, hipStreamSynchronize(s));   // (d_need_pair is released on leaving this block)
-    }
-  }
-  if (opt->polish) {
-    KTimer t(ctx, "geo_hransac_polish");
-    hipLaunchKernelGGL(k_hransac_polish, dim3(n_slots), dim3(GEO_WAVE), 0, s, d_slot_pair.p, d_off, p1, p2, d_ok, d_in, dH);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the buffers of the run are released on return)
   return MSFM_OK;
 }
 
@@ -1372,10 +1229,7 @@ int geo_hransac_check(msfm_ctx* ctx, int n_pairs, const int* offsets, const msfm
   if (!(opt->confidence > 0.0 && opt->confidence < 1.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: confidence outside (0, 1)");
   if (!(opt->threshold == opt->threshold)) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: threshold is NaN");
   if (n_pairs == 0) return MSFM_OK;
-  if (offsets[0] != 0) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: offsets[0] must be 0");
-  for (int p = 0; p < n_pairs; p++)
-    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: offsets must be non-decreasing");
-  return MSFM_OK;
+  return msfm_check_offsets(ctx, "hransac", n_pairs, offsets);
 }
 
 MSFM_API int msfm_homography_ransac_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const float* pt1, const float* pt2,
@@ -1383,29 +1237,9 @@ MSFM_API int msfm_homography_ransac_batch(msfm_ctx* ctx, int n_pairs, const int*
   if (!ctx || n_pairs < 0 || !offsets || !opt || !H || !n_inliers || !ok) return MSFM_E_INVAL;
   MSFM_TRY(geo_hransac_check(ctx, n_pairs, offsets, opt));
   if (n_pairs == 0) return MSFM_OK;
-  const int total = offsets[n_pairs];
-  if (total > 0 && (!pt1 || !pt2 || !inlier)) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: missing point or mask buffers");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DevBuf<int> d_off, d_nin;
-  DevBuf<float> d1, d2;
-  DevBuf<double> dH;
-  DevBuf<uint8_t> d_in, d_ok;
-  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d2.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
-  HIP_TRY(ctx, dH.alloc((size_t)n_pairs * 9));
-  HIP_TRY(ctx, d_in.alloc((size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_nin.alloc(n_pairs));
-  HIP_TRY(ctx, d_ok.alloc(n_pairs));
-  MSFM_TRY(geo_hransac_dev(ctx, n_pairs, offsets, d_off.p, d1.p, d2.p, opt, nullptr, dH.p, d_in.p, d_nin.p, d_ok.p));
-  HIP_TRY(ctx, hipMemcpyAsync(H, dH.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(n_inliers, d_nin.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
-  return MSFM_OK;
+  if (offsets[n_pairs] > 0 && (!pt1 || !pt2 || !inlier)) return msfm_set_error(ctx, MSFM_E_INVAL, "hransac: missing point or mask buffers");
+  return ransac_batch_io(ctx, n_pairs, offsets, pt1, pt2, H, inlier, n_inliers, ok,
+                         [&](const int* d_off, const float* d1, const float* d2, double* dH, uint8_t* d_in, int* d_nin, uint8_t* d_ok) {
+                           return geo_hransac_dev(ctx, n_pairs, offsets, d_off, d1, d2, opt, nullptr, dH, d_in, d_nin, d_ok);
+                         });
 }

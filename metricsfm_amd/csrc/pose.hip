@@ -1235,13 +1235,6 @@ __global__ __launch_bounds__(256) void k_e5_select(int T, const int* __restrict_
   }
 }
 
-static int pose_check_offsets(msfm_ctx* ctx, const char* who, int n, const int* offsets) {
-  if (offsets[0] != 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: offsets[0] must be 0", who);
-  for (int p = 0; p < n; p++)
-    if (offsets[p + 1] < offsets[p]) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: offsets must be non-decreasing", who);
-  return MSFM_OK;
-}
-
 MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w, const double* pts_2d,
                                     const double* f, int max_iter, uint64_t seed, double* R, double* t, double* errors, double* avg_error,
                                     int* best_iter) {
@@ -1249,7 +1242,7 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   if (max_iter < 1 || max_iter > 65536) return msfm_set_error(ctx, MSFM_E_INVAL, "epnp: max_iter out of range");
   if (n_problems == 0) return MSFM_OK;
   if (n_problems > 65535) return msfm_set_error(ctx, MSFM_E_INVAL, "epnp: at most 65535 problems per call");
-  MSFM_TRY(pose_check_offsets(ctx, "epnp", n_problems, offsets));
+  MSFM_TRY(msfm_check_offsets(ctx, "epnp", n_problems, offsets));
   const int total = offsets[n_problems];
   if (total > 0 && (!pts_w || !pts_2d || !errors)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1320,7 +1313,7 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   if (n_problems > 65535) return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: at most 65535 problems per call");
   if ((long long)n_problems * n_steps > INT_MAX)
     return msfm_set_error(ctx, MSFM_E_INVAL, "epnpf: n_problems * n_steps = %lld does not fit an int", (long long)n_problems * n_steps);
-  MSFM_TRY(pose_check_offsets(ctx, "epnpf", n_problems, offsets));
+  MSFM_TRY(msfm_check_offsets(ctx, "epnpf", n_problems, offsets));
   const int total = offsets[n_problems];
   if (total > 0 && (!pts_w || !pts_2d || !errors)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1376,7 +1369,7 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   if (ransac_times < 1 || ransac_times > 65536) return msfm_set_error(ctx, MSFM_E_INVAL, "relpose: ransac_times out of range");
   if (n_pairs == 0) return MSFM_OK;
   if (n_pairs > 65535) return msfm_set_error(ctx, MSFM_E_INVAL, "relpose: at most 65535 pairs per call");
-  MSFM_TRY(pose_check_offsets(ctx, "relpose", n_pairs, offsets));
+  MSFM_TRY(msfm_check_offsets(ctx, "relpose", n_pairs, offsets));
   const int total = offsets[n_pairs];
   if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(PRIOR_WAVE) void k_prior_count(const int* __restric
   const int a0 = cam_off[i], a1 = cam_off[i + 1], b0 = cam_off[j], b1 = cam_off[j + 1];
   int c = 0;
   for (int e = a0 + lane; e < a1; e += PRIOR_WAVE) c += prior_find(cam_pt, b0, b1, cam_pt[e]) >= 0 ? 1 : 0;
-  for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
+  c = wave_sum_int(c);
   if (lane == 0) cnt[slot] = c;
 }
 
