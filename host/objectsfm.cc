@@ -626,6 +626,45 @@ bool RelativePoseEstimation::RelativePoseWithFocalLength(std::vector<Vec2>& pts_
   return true;
 }
 
+// RelativePoseEstimation::RelativePoseWithoutFocalLength (relative_pose_estimation.cc:29-83) for several pairs: 200 samples of
+// 8 matches each (fundamental_matrix_eight_point.cc:52), focal lengths and pose from the kept F.
+void RelativePoseWithoutFocalLengthBatch(const std::vector<std::vector<Vec2>>& pts_ref, const std::vector<std::vector<Vec2>>& pts_cur,
+                                         std::vector<double>& f_ref, std::vector<double>& f_cur, std::vector<RTPoseRelative>& poses,
+                                         std::vector<uint8_t>& ok) {
+  const int n = (int)pts_cur.size();
+  std::vector<int> off(n + 1, 0);
+  for (int p = 0; p < n; p++) off[p + 1] = off[p] + (int)pts_cur[p].size();
+  const size_t m = (size_t)std::max(1, n);
+  std::vector<double> a(2 * (size_t)std::max(1, off[n])), b(a.size()), F(9 * m), E(9 * m), R(9 * m), t(3 * m);
+  for (int p = 0; p < n; p++)
+    for (size_t i = 0; i < pts_cur[p].size(); i++) {
+      const size_t e = off[p] + i;
+      a[2 * e] = pts_ref[p][i].x; a[2 * e + 1] = pts_ref[p][i].y; b[2 * e] = pts_cur[p][i].x; b[2 * e + 1] = pts_cur[p][i].y;
+    }
+  f_ref.assign(m, 0.0); f_cur.assign(m, 0.0); ok.assign(m, 0);
+  check(msfm_relpose_8pt_batch(Context(), n, off.data(), a.data(), b.data(), 200, kPoseSeed, F.data(), f_ref.data(), f_cur.data(), E.data(),
+                               R.data(), t.data(), ok.data(), nullptr, nullptr, nullptr), "relpose_8pt_batch");
+  f_ref.resize(n); f_cur.resize(n); ok.resize(n);
+  poses.resize(n);
+  for (int p = 0; p < n; p++) {
+    for (int k = 0; k < 9; k++) poses[p].R.m[k] = R[9 * (size_t)p + k];
+    for (int k = 0; k < 3; k++) poses[p].t[k] = t[3 * (size_t)p + k];
+  }
+}
+
+bool RelativePoseEstimation::RelativePoseWithoutFocalLength(std::vector<Vec2>& pts_ref, std::vector<Vec2>& pts_cur, double& f_ref,
+                                                            double& f_cur, RTPoseRelative& pose_relative) {
+  std::vector<double> f1, f2;
+  std::vector<RTPoseRelative> poses;
+  std::vector<uint8_t> ok;
+  RelativePoseWithoutFocalLengthBatch({pts_ref}, {pts_cur}, f1, f2, poses, ok);
+  if (!ok[0]) return false;  // f_ref, f_cur and the pose stay as they were, as in the reference
+  f_ref = f1[0];
+  f_cur = f2[0];
+  pose_relative = poses[0];
+  return true;
+}
+
 std::vector<std::vector<std::pair<int, int>>> VerifyPairs(const std::vector<PairMatches>& matches,
                                                           const std::vector<std::vector<Point2f>>& keypoints) {
   const int np = (int)matches.size();

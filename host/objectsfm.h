@@ -248,7 +248,18 @@ class RelativePoseEstimation {
   // five-point RANSAC on points / f, then the pose from the best essential matrix     (relative_pose_estimation.cc:91-120)
   static bool RelativePoseWithFocalLength(std::vector<Vec2>& pts_ref, std::vector<Vec2>& pts_cur, double f_ref, double f_cur,
                                           RTPoseRelative& pose_relative);
+  // normalised eight-point F RANSAC on centred pixels, both focal lengths from F, then the pose from E = K2 F K1
+  //                                                                                    (relative_pose_estimation.cc:29-83)
+  static bool RelativePoseWithoutFocalLength(std::vector<Vec2>& pts_ref, std::vector<Vec2>& pts_cur, double& f_ref, double& f_cur,
+                                             RTPoseRelative& pose_relative);
 };
+// RelativePoseWithoutFocalLength for several candidate seed pairs at once: the reference walks its sorted pair list one by
+// one until a pair reconstructs (sfm_incremental.cc:224-415), the host can hand over the top K instead.  ok[p] is the
+// per-pair return value; f_ref, f_cur and poses of a failed pair are zero.  Pair p draws the samples of pair index p: a
+// single-pair call equals entry 0 of a batch.
+void RelativePoseWithoutFocalLengthBatch(const std::vector<std::vector<Vec2>>& pts_ref, const std::vector<std::vector<Vec2>>& pts_cur,
+                                         std::vector<double>& f_ref, std::vector<double>& f_cur, std::vector<RTPoseRelative>& poses,
+                                         std::vector<uint8_t>& ok);
 // Many images / pairs in one call each (the batched form the GPU wants; same results as the per-item calls above).
 void AbsolutePoseBatch(const std::vector<std::vector<Vec3>>& pts_w, const std::vector<std::vector<Vec2>>& pts_2d, const std::vector<double>& f,
                        std::vector<RTPose>& poses, std::vector<std::vector<double>>& errors, std::vector<double>& avg_error);

@@ -603,6 +603,31 @@ int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* offsets, co
 int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const double* pts_ref,
                            const double* pts_cur, const double* f_ref, const double* f_cur, int ransac_times,
                            uint64_t seed, double* E, double* R, double* t, uint8_t* ok, int* n_candidates);
+/* RelativePoseEstimation::RelativePoseWithoutFocalLength (relative_pose_estimation.cc:29-83, the arm of
+ * IncrementalSfM::FindSeedPairThenReconstruct a seed pair takes when a focal length is missing,
+ * sfm_incremental.cc:306-333) for a batch of image pairs.  Per pair, on centred pixels NOT divided by a focal length:
+ * FundamentalMatrixEightPoint::NormalizedEightPointFundamentalMatrixRANSAC (fundamental_matrix_eight_point.cc:30-97) -
+ * `ransac_times` (reference: 200) samples of 8 matches (all matches at once when there are 8..15), each through the
+ * normalised eight-point fit (:105-168: centroid / RMS-to-sqrt(2) normalisation :175-203, the kernel of the constraint
+ * matrix by full-pivot LU for 8 rows - a kernel of another dimension drops the sample - or its last right singular
+ * vector for more, rank 2 enforced, T2^T F T1), every fit scored by the Sampson sum over all matches (:205-221), the
+ * first smallest sum below 1000000.0 kept and the FIRST fit when none is (:82-96) - then
+ * RelativePoseFromFundamentalMatrix::ReltivePoseFromFMatrix (relative_pose_from_fundamental_matrix.cc:25-51): Hartley's
+ * focal lengths from F (:56-123; the rotation of each epipole onto the x-z plane is formed as c = e0 / |(e0, e1)|,
+ * s = -e1 / |(e0, e1)| - the cosine and sine of the reference's atan2(-e1, e0) without a libm call), E = diag(f2, f2, 1)
+ * F diag(f1, f1, 1) (:125-136), and the decomposition and cheirality vote of msfm_relpose_5pt_batch on pixel / f, whose
+ * verdict the reference ignores.  Sample `it` of pair `p` is a pure function of (seed, p, it, number of matches).
+ * Out: F [n][9] row-major with x_cur^T F x_ref = 0 on centred pixels; f_ref, f_cur [n]; E [n][9] row-major with
+ *      x_cur^T E x_ref = 0 on (pixel / f, 1); R [n][9], t [n][3] as the reference returns them in RTPoseRelative; ok [n];
+ *      best_iter [n] = the kept sample (0 in the all-matches case), best_error [n] = its Sampson sum (1000000.0 when the
+ *      first fit was kept by default), n_candidates [n] = fits scored; each of the three may be NULL.
+ *      Fewer than 8 matches or no fit: ok = 0, every output zero, best_iter = -1, best_error = 1000000.0.
+ *      Focal lengths not extractable (an epipole with x == 0, or an f^2 < 0; a NaN passes, as in the reference): ok = 0,
+ *      F, best_iter, best_error and n_candidates stand, the rest is zero. */
+int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const double* pts_ref,
+                           const double* pts_cur, int ransac_times, uint64_t seed, double* F, double* f_ref,
+                           double* f_cur, double* E, double* R, double* t, uint8_t* ok, int* best_iter,
+                           double* best_error, int* n_candidates);
 
 /* ==================================================================================== *
  *  Single-process multi-GPU context

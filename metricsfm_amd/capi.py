@@ -30,7 +30,7 @@ SYMBOLS = [
     "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
     "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
     "msfm_epnp_ransac_batch", "msfm_epnpf_default_options", "msfm_epnpf_num_steps", "msfm_epnpf_sweep_batch",
-    "msfm_relpose_5pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
+    "msfm_relpose_5pt_batch", "msfm_relpose_8pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
     "msfm_ctx_create_multi", "msfm_multi_destroy", "msfm_multi_size", "msfm_multi_ctx", "msfm_multi_last_error", "msfm_multi_ba_solve",
     "msfm_multi_triangulate_midpoint_batch", "msfm_multi_triangulate_dlt_batch", "msfm_multi_reproject_mse_batch", "msfm_multi_match_pairs",
 ]
@@ -119,6 +119,9 @@ def lib():
                                          A.c_double_p]
     L.msfm_relpose_5pt_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64,
                                          A.c_double_p, A.c_double_p, A.c_double_p, A.c_u8_p, A.c_int_p]
+    L.msfm_relpose_8pt_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, i, C.c_uint64, A.c_double_p, A.c_double_p,
+                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_u8_p, A.c_int_p, A.c_double_p,
+                                         A.c_int_p]
     L.msfm_rccl_get_unique_id.argtypes = [vp, C.POINTER(C.c_ubyte)]
     L.msfm_ctx_init_rccl.argtypes = [vp, C.POINTER(C.c_ubyte), i, i]
     L.msfm_ctx_allreduce.argtypes = [vp, vp, C.c_size_t, i]
@@ -525,6 +528,28 @@ class Context:
                                                 A.ptr(E, A.c_double_p), A.ptr(R, A.c_double_p), A.ptr(t, A.c_double_p), A.ptr(ok, A.c_u8_p),
                                                 A.ptr(nc, A.c_int_p)))
         return E[:n], R[:n], t[:n], ok[:n], nc[:n]
+
+    def relpose_8pt(self, offsets, pts_ref, pts_cur, ransac_times=200, seed=0x4D53464D38, diagnostics=True):
+        """RelativePoseEstimation::RelativePoseWithoutFocalLength for a batch of image pairs (relative_pose_estimation.cc:29-83):
+        normalised eight-point F RANSAC on centred pixels, both focal lengths from F, E, and the decomposition of E.
+        Returns F [n][3][3], f_ref [n], f_cur [n], E [n][3][3], R [n][3][3], t [n][3], ok [n], best_iter [n], best_error [n],
+        n_candidates [n]; the last three are None with diagnostics=False (the library is then handed NULL for them)."""
+        offsets = A.as_c(offsets, np.int32)
+        pts_ref = A.as_c(np.asarray(pts_ref, dtype=np.float64).reshape(-1, 2), np.float64)
+        pts_cur = A.as_c(np.asarray(pts_cur, dtype=np.float64).reshape(-1, 2), np.float64)
+        n = len(offsets) - 1
+        m = max(1, n)
+        F = np.zeros((m, 3, 3)); E = np.zeros((m, 3, 3)); R = np.zeros((m, 3, 3)); t = np.zeros((m, 3))
+        f1 = np.zeros(m); f2 = np.zeros(m); ok = np.zeros(m, dtype=np.uint8)
+        bi = np.zeros(m, dtype=np.int32) if diagnostics else None
+        be = np.zeros(m) if diagnostics else None
+        nc = np.zeros(m, dtype=np.int32) if diagnostics else None
+        self.check(lib().msfm_relpose_8pt_batch(self._h, n, A.ptr(offsets, A.c_int_p), A.ptr(pts_ref, A.c_double_p), A.ptr(pts_cur, A.c_double_p),
+                                                ransac_times, seed, A.ptr(F, A.c_double_p), A.ptr(f1, A.c_double_p), A.ptr(f2, A.c_double_p),
+                                                A.ptr(E, A.c_double_p), A.ptr(R, A.c_double_p), A.ptr(t, A.c_double_p), A.ptr(ok, A.c_u8_p),
+                                                A.ptr(bi, A.c_int_p), A.ptr(be, A.c_double_p), A.ptr(nc, A.c_int_p)))
+        out = (F[:n], f1[:n], f2[:n], E[:n], R[:n], t[:n], ok[:n])
+        return out + ((bi[:n], be[:n], nc[:n]) if diagnostics else (None, None, None))
 
     def epipolar_filter_batch(self, offsets, pt1, pt2, F, ok=None, th=3.0):
         offsets = A.as_c(offsets, np.int32)

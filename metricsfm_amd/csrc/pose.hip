@@ -14,11 +14,20 @@
 //        (100 samples of 5 matches, every real solution of every sample scored by the Sampson sum :333-349), then
 //        RelativePoseFromEssentialMatrix::ReltivePoseFromEMatrix    relative_pose_from_essential_matrix.cc:33-104;
 //     called for the seed pair, sfm_incremental.cc:309.
+//   RelativePoseEstimation::RelativePoseWithoutFocalLength SfM/src/orientation/relative_pose_estimation.cc:29-83
+//     -> FundamentalMatrixEightPoint::NormalizedEightPointFundamentalMatrixRANSAC  fundamental_matrix_eight_point.cc:30-97
+//        (200 samples of 8 matches on centred pixels, the normalised eight-point fit of each :105-168 scored by the Sampson
+//        sum :205-221, the first fit kept when no sum is below 1e6), then
+//        RelativePoseFromFundamentalMatrix::ReltivePoseFromFMatrix  relative_pose_from_fundamental_matrix.cc:25-136
+//        (Hartley's two focal lengths from F, E = diag(f2, f2, 1) F diag(f1, f1, 1)) and ReltivePoseFromEMatrix on pixel / f;
+//     called for the seed pair when a focal length is missing, sfm_incremental.cc:319.  The reference rotates each epipole
+//     onto the x-z plane by theta = atan2(-e1, e0), cos(theta), sin(theta); here c = e0 / sqrt(e0^2 + e1^2) and
+//     s = -e1 / sqrt(e0^2 + e1^2) - the same rotation without libm, whose device and host versions differ in the last bit.
 // The linear algebra behind them lives in OpenCV 2.4 (cvSVD, cvInvert, cvSolve: one-sided Jacobi SVD) and Eigen 3
 // (FullPivLU, EigenSolver), neither in the tree: restated from their published algorithms.  std::random_shuffle is
 // replaced by a counter-based sampler keyed by (seed, problem, iteration), so parity with the reference is
-// statistical and parity with oracle/pose_oracle.cpp is exact: this file uses only + - * / sqrt on doubles, in a
-// fixed order, with contraction off.
+// statistical and parity with oracle/pose_oracle.cpp (the eight-point arm: tests/relposef_ref.cpp) is exact: this file
+// uses only + - * / sqrt on doubles, in a fixed order, with contraction off.
 //
 // One GPU thread = one minimal sample.  A sample's solver state (a 12x12 Jacobi SVD for EPnP, the 10x20 constraint
 // matrix and a 10x10 QR iteration for the five-point solver) is a few KB of thread-private memory; all samples of
@@ -1123,6 +1132,70 @@ __global__ __launch_bounds__(256) void k_e5_score(int T, const int* __restrict__
   cand_err[((size_t)p * T + it) * 10 + slot] = total;
 }
 
+// RelativePoseFromEssentialMatrix::ReltivePoseFromEMatrix (relative_pose_from_essential_matrix.cc:33-104) by one workgroup
+// of 256 threads, shared by the five-point and the eight-point arm: thread 0 decomposes E (column-major, :81-104) into
+// the four (R, t) hypotheses, every match (pts / f1, pts / f2) votes for the first one that puts it in front of both
+// cameras (:33-79), thread 0 writes the first hypothesis with the most votes to Rout[9], tout[3].  s_votes must be zero
+// on entry; all threads of the workgroup call it.
+__device__ static void pose_from_E_block(const double* E, int N, const double* __restrict__ pts_ref, const double* __restrict__ pts_cur,
+                                         double f1, double f2, int tid, double (*s_R)[9], double (*s_t)[3], int* s_votes,
+                                         double* Rout, double* tout) {
+  if (tid == 0) {
+    double Ut[9], W[3], Vt[9], U[3][3], V[3][3];
+    for (int i = 0; i < 3; i++)      // Ut = Em^T with Em(i, j) = E[i + 3 j]
+      for (int k = 0; k < 3; k++) Ut[i * 3 + k] = E[k + 3 * i];
+    pose_jsvd<3, 3, true>(Ut, W, Vt);
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) { U[i][j] = Ut[j * 3 + i]; V[i][j] = Vt[j * 3 + i]; }
+    const double detU = U[0][0] * (U[1][1] * U[2][2] - U[1][2] * U[2][1]) - U[0][1] * (U[1][0] * U[2][2] - U[1][2] * U[2][0]) +
+                        U[0][2] * (U[1][0] * U[2][1] - U[1][1] * U[2][0]);
+    if (detU < 0) for (int i = 0; i < 3; i++) U[i][2] *= -1.0;
+    const double detV = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
+                        V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
+    if (detV < 0) for (int i = 0; i < 3; i++) V[i][2] *= -1.0;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        const double r1 = -U[i][1] * V[j][0] + U[i][0] * V[j][1] + U[i][2] * V[j][2];
+        const double r2 = U[i][1] * V[j][0] + -U[i][0] * V[j][1] + U[i][2] * V[j][2];
+        s_R[0][3 * i + j] = r1; s_R[1][3 * i + j] = r1; s_R[2][3 * i + j] = r2; s_R[3][3 * i + j] = r2;
+      }
+    const double tn = sqrt(U[0][2] * U[0][2] + U[1][2] * U[1][2] + U[2][2] * U[2][2]);
+    double t[3];
+    for (int i = 0; i < 3; i++) t[i] = U[i][2] / tn;
+    for (int h = 0; h < 4; h++) {
+      const double sg = (h & 1) ? -1.0 : 1.0;
+      for (int i = 0; i < 3; i++) s_t[h][i] = -(s_R[h][i] * (sg * t[0]) + s_R[h][3 + i] * (sg * t[1]) + s_R[h][6 + i] * (sg * t[2]));
+    }
+  }
+  __syncthreads();
+  for (int i = tid; i < N; i += 256) {
+    const double d1[3] = {pts_ref[2 * (size_t)i] / f1, pts_ref[2 * (size_t)i + 1] / f1, 1.0};
+    const double q[3] = {pts_cur[2 * (size_t)i] / f2, pts_cur[2 * (size_t)i + 1] / f2, 1.0};
+    for (int h = 0; h < 4; h++) {
+      const double* R = s_R[h];
+      const double* tt = s_t[h];
+      double c[3], d2[3];
+      for (int k = 0; k < 3; k++) {
+        c[k] = -(R[k] * tt[0] + R[3 + k] * tt[1] + R[6 + k] * tt[2]);
+        d2[k] = R[k] * q[0] + R[3 + k] * q[1] + R[6 + k] * q[2];
+      }
+      const double d1sq = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2], d2sq = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
+      const double d12 = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
+      const double d1p = d1[0] * c[0] + d1[1] * c[1] + d1[2] * c[2], d2p = d2[0] * c[0] + d2[1] * c[1] + d2[2] * c[2];
+      if (d2sq * d1p - d12 * d2p > 0 && d12 * d1p - d1sq * d2p > 0) { atomicAdd(&s_votes[h], 1); break; }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    int mx = s_votes[0];
+    for (int h = 1; h < 4; h++) mx = s_votes[h] > mx ? s_votes[h] : mx;
+    int h = 0;
+    while (s_votes[h] != mx) h++;
+    for (int i = 0; i < 9; i++) Rout[i] = s_R[h][i];
+    for (int i = 0; i < 3; i++) tout[i] = s_t[h][i];
+  }
+}
+
 // One workgroup per pair: replay `if (error_i < error_min)` from 1e6 over the candidates in (sample, slot) order, then
 // DecomposeEssentialMatrix (:81-104) and the cheirality vote over all matches (:33-79).
 __global__ __launch_bounds__(256) void k_e5_select(int T, const int* __restrict__ off, const double* __restrict__ pts_ref,
@@ -1174,65 +1247,269 @@ __global__ __launch_bounds__(256) void k_e5_select(int T, const int* __restrict_
     return;
   }
   const double* E = cand_E + ((size_t)p * T + key / 10) * 90 + 9 * (key % 10);
+  pose_from_E_block(E, N, pts_ref + 2 * (size_t)o, pts_cur + 2 * (size_t)o, f_ref[p], f_cur[p], tid, s_R, s_t, s_votes,
+                    Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
   if (tid == 0) {
-    double Ut[9], W[3], Vt[9], U[3][3], V[3][3];
-    for (int i = 0; i < 3; i++)      // Ut = Em^T with Em(i, j) = E[i + 3 j]
-      for (int k = 0; k < 3; k++) Ut[i * 3 + k] = E[k + 3 * i];
-    pose_jsvd<3, 3, true>(Ut, W, Vt);
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) { U[i][j] = Ut[j * 3 + i]; V[i][j] = Vt[j * 3 + i]; }
-    const double detU = U[0][0] * (U[1][1] * U[2][2] - U[1][2] * U[2][1]) - U[0][1] * (U[1][0] * U[2][2] - U[1][2] * U[2][0]) +
-                        U[0][2] * (U[1][0] * U[2][1] - U[1][1] * U[2][0]);
-    if (detU < 0) for (int i = 0; i < 3; i++) U[i][2] *= -1.0;
-    const double detV = V[0][0] * (V[1][1] * V[2][2] - V[1][2] * V[2][1]) - V[0][1] * (V[1][0] * V[2][2] - V[1][2] * V[2][0]) +
-                        V[0][2] * (V[1][0] * V[2][1] - V[1][1] * V[2][0]);
-    if (detV < 0) for (int i = 0; i < 3; i++) V[i][2] *= -1.0;
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        const double r1 = -U[i][1] * V[j][0] + U[i][0] * V[j][1] + U[i][2] * V[j][2];
-        const double r2 = U[i][1] * V[j][0] + -U[i][0] * V[j][1] + U[i][2] * V[j][2];
-        s_R[0][3 * i + j] = r1; s_R[1][3 * i + j] = r1; s_R[2][3 * i + j] = r2; s_R[3][3 * i + j] = r2;
-      }
-    const double tn = sqrt(U[0][2] * U[0][2] + U[1][2] * U[1][2] + U[2][2] * U[2][2]);
-    double t[3];
-    for (int i = 0; i < 3; i++) t[i] = U[i][2] / tn;
-    for (int h = 0; h < 4; h++) {
-      const double sg = (h & 1) ? -1.0 : 1.0;
-      for (int i = 0; i < 3; i++) s_t[h][i] = -(s_R[h][i] * (sg * t[0]) + s_R[h][3 + i] * (sg * t[1]) + s_R[h][6 + i] * (sg * t[2]));
-    }
-  }
-  __syncthreads();
-  const double f1 = f_ref[p], f2 = f_cur[p];
-  for (int i = tid; i < N; i += 256) {
-    const double d1[3] = {pts_ref[2 * ((size_t)o + i)] / f1, pts_ref[2 * ((size_t)o + i) + 1] / f1, 1.0};
-    const double q[3] = {pts_cur[2 * ((size_t)o + i)] / f2, pts_cur[2 * ((size_t)o + i) + 1] / f2, 1.0};
-    for (int h = 0; h < 4; h++) {
-      const double* R = s_R[h];
-      const double* tt = s_t[h];
-      double c[3], d2[3];
-      for (int k = 0; k < 3; k++) {
-        c[k] = -(R[k] * tt[0] + R[3 + k] * tt[1] + R[6 + k] * tt[2]);
-        d2[k] = R[k] * q[0] + R[3 + k] * q[1] + R[6 + k] * q[2];
-      }
-      const double d1sq = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2], d2sq = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
-      const double d12 = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2];
-      const double d1p = d1[0] * c[0] + d1[1] * c[1] + d1[2] * c[2], d2p = d2[0] * c[0] + d2[1] * c[1] + d2[2] * c[2];
-      if (d2sq * d1p - d12 * d2p > 0 && d12 * d1p - d1sq * d2p > 0) { atomicAdd(&s_votes[h], 1); break; }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int mx = s_votes[0];
-    for (int h = 1; h < 4; h++) mx = s_votes[h] > mx ? s_votes[h] : mx;
-    int h = 0;
-    while (s_votes[h] != mx) h++;
-    for (int i = 0; i < 9; i++) Rout[9 * (size_t)p + i] = s_R[h][i];
-    for (int i = 0; i < 3; i++) tout[3 * (size_t)p + i] = s_t[h][i];
     for (int i = 0; i < 3; i++)
       for (int j = 0; j < 3; j++) Eout[9 * (size_t)p + 3 * i + j] = E[i + 3 * j];
     ok[p] = 1;
     n_candidates[p] = nE;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Normalised eight-point fundamental matrix (fundamental_matrix_eight_point.cc) and Hartley's focal lengths from F
+// (relative_pose_from_fundamental_matrix.cc:56-123): the seed pair without focal lengths.
+// ---------------------------------------------------------------------------------------------------------------
+#define F8_SALT 0x38707446ull
+#define F8_MAXN 15
+
+// NormalizeImagePoints (:175-203): centroid, then the RMS distance to it scaled to sqrt(2).  T = {s, tx, ty} stands
+// for the matrix [s 0 tx; 0 s ty; 0 0 1].
+__device__ static void f8_normalize(const double* x, int n, double* xn, double* T) {
+  double cx = 0.0, cy = 0.0;
+  for (int i = 0; i < n; i++) { cx += x[2 * i]; cy += x[2 * i + 1]; }
+  cx = cx / n; cy = cy / n;
+  double ss = 0.0;
+  for (int i = 0; i < n; i++) {
+    const double dx = x[2 * i] - cx, dy = x[2 * i + 1] - cy;
+    ss += dx * dx + dy * dy;
+  }
+  const double s = 1.4142135623730951 / sqrt(ss / n);
+  T[0] = s; T[1] = -1.0 * s * cx; T[2] = -1.0 * s * cy;
+  for (int i = 0; i < n; i++) { xn[2 * i] = s * x[2 * i] + T[1]; xn[2 * i + 1] = s * x[2 * i + 1] + T[2]; }
+}
+
+// NormalizedEightPointFundamentalMatrix (:105-168) on n in [8, 15] matches x1[2n], x2[2n]; F row-major with
+// x2^T F x1 = 0.  Eight matches: the kernel of the 8x9 constraint matrix by full-pivot LU, false unless it is
+// one-dimensional; more: the last right singular vector, the constraint matrix padded with zero rows to F8_MAXN so
+// that one instance of the Jacobi SVD serves every size (a zero row adds exact zeros to each of its sums).
+__device__ static bool f8_fit(const double* x1, const double* x2, int n, double* F) {
+  double a[2 * F8_MAXN], b[2 * F8_MAXN], T1[3], T2[3], fv[9];
+  f8_normalize(x1, n, a, T1);
+  f8_normalize(x2, n, b, T2);
+  if (n == 8) {
+    double A[72];
+    for (int i = 0; i < 8; i++) {
+      double* r = A + 9 * i;
+      r[0] = a[2 * i] * b[2 * i]; r[1] = a[2 * i + 1] * b[2 * i]; r[2] = 1.0 * b[2 * i];
+      r[3] = a[2 * i] * b[2 * i + 1]; r[4] = a[2 * i + 1] * b[2 * i + 1]; r[5] = 1.0 * b[2 * i + 1];
+      r[6] = a[2 * i]; r[7] = a[2 * i + 1]; r[8] = 1.0;
+    }
+    int pr[8], pc[9];
+    double maxpivot;
+    const int nz = p5_fullpiv_lu(A, 8, 9, 9, pr, pc, &maxpivot);
+    const double thr = maxpivot * (DBL_EPSILON * 8);
+    int rank = 0;
+    for (int i = 0; i < nz; i++) rank += fabs(A[i * 9 + i]) > thr;
+    if (rank != 8) return false;
+    double y[8];
+    for (int i = 7; i >= 0; i--) y[i] = A[i * 9 + 8];
+    for (int i = 7; i >= 0; i--) {
+      y[i] = y[i] / A[i * 9 + i];
+      for (int j = 0; j < i; j++) y[j] -= A[j * 9 + i] * y[i];
+    }
+    for (int i = 0; i < 8; i++) fv[pc[i]] = -y[i];
+    fv[pc[8]] = 1.0;
+  } else {
+    double At[9 * F8_MAXN], W[9], Vt[81];
+    for (int k = 0; k < F8_MAXN; k++) {
+      double r[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+      if (k < n) {
+        r[0] = a[2 * k] * b[2 * k]; r[1] = a[2 * k + 1] * b[2 * k]; r[2] = 1.0 * b[2 * k];
+        r[3] = a[2 * k] * b[2 * k + 1]; r[4] = a[2 * k + 1] * b[2 * k + 1]; r[5] = 1.0 * b[2 * k + 1];
+        r[6] = a[2 * k]; r[7] = a[2 * k + 1]; r[8] = 1.0;
+      }
+      for (int c = 0; c < 9; c++) At[c * F8_MAXN + k] = r[c];
+    }
+    pose_jsvd<F8_MAXN, 9, true>(At, W, Vt);
+    for (int i = 0; i < 9; i++) fv[i] = Vt[72 + i];
+  }
+  // closest rank-2 matrix (:155-162), then T2^T F T1 (:165)
+  double Ut[9], W[3], Vt[9], G[9], H[9];
+  for (int i = 0; i < 3; i++)
+    for (int k = 0; k < 3; k++) Ut[i * 3 + k] = fv[k * 3 + i];
+  pose_jsvd<3, 3, true>(Ut, W, Vt);
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) G[3 * r + c] = Ut[r] * W[0] * Vt[c] + Ut[3 + r] * W[1] * Vt[3 + c];
+  for (int r = 0; r < 3; r++) {
+    H[3 * r] = G[3 * r] * T1[0];
+    H[3 * r + 1] = G[3 * r + 1] * T1[0];
+    H[3 * r + 2] = G[3 * r] * T1[1] + G[3 * r + 1] * T1[2] + G[3 * r + 2];
+  }
+  for (int c = 0; c < 3; c++) {
+    F[c] = T2[0] * H[c];
+    F[3 + c] = T2[0] * H[3 + c];
+    F[6 + c] = T2[1] * H[c] + T2[2] * H[3 + c] + H[6 + c];
+  }
+  return true;
+}
+
+// FocalLengthFromFMatrix (:56-123), F row-major.  The reference turns each epipole onto the x-z plane by
+// theta = atan2(-e1, e0) and cos / sin of it; c = e0 / sqrt(e0^2 + e1^2), s = -e1 / sqrt(e0^2 + e1^2) are that same
+// cosine and sine without a libm call.  A NaN f^2 passes the `< 0` test, as it does there.  e1, e2 (may be null)
+// receive the epipoles.
+__device__ static bool f8_focal(const double* F, double* f1, double* f2, double* e1out, double* e2out) {
+  double A[9], W[3], V1[9], V2[9];
+  for (int i = 0; i < 3; i++)
+    for (int k = 0; k < 3; k++) A[i * 3 + k] = F[k * 3 + i];
+  pose_jsvd<3, 3, true>(A, W, V1);
+  for (int i = 0; i < 9; i++) A[i] = F[i];
+  pose_jsvd<3, 3, true>(A, W, V2);
+  const double* e1 = V1 + 6;
+  const double* e2 = V2 + 6;
+  if (e1out) for (int i = 0; i < 3; i++) { e1out[i] = e1[i]; e2out[i] = e2[i]; }
+  if (e1[0] == 0 || e2[0] == 0) return false;
+  const double n1 = sqrt(e1[0] * e1[0] + e1[1] * e1[1]), n2 = sqrt(e2[0] * e2[0] + e2[1] * e2[1]);
+  const double c1 = e1[0] / n1, s1 = -e1[1] / n1, c2 = e2[0] / n2, s2 = -e2[1] / n2;
+  double M[6], Fr[4];  // rows 0, 1 of rotation2 * F, then the upper-left 2x2 of (rotation2 * F) * rotation1^T
+  for (int j = 0; j < 3; j++) { M[j] = c2 * F[j] - s2 * F[3 + j]; M[3 + j] = s2 * F[j] + c2 * F[3 + j]; }
+  for (int i = 0; i < 2; i++) { Fr[2 * i] = M[3 * i] * c1 - M[3 * i + 1] * s1; Fr[2 * i + 1] = M[3 * i] * s1 + M[3 * i + 1] * c1; }
+  const double e1x = c1 * e1[0] - s1 * e1[1], e1z = e1[2], e2x = c2 * e2[0] - s2 * e2[1], e2z = e2[2];
+  const double i1 = 1.0 / e1z, i2 = 1.0 / e2z;
+  const double a = i2 * Fr[0] * i1, b = i2 * Fr[1], c = Fr[2] * i1, d = Fr[3];
+  const double f1sq = (-a * c * e1x * e1x) / (a * c * e1z * e1z + b * d);
+  const double f2sq = (-a * b * e2x * e2x) / (a * b * e2z * e2z + c * d);
+  if (f1sq < 0 || f2sq < 0) return false;
+  *f1 = sqrt(f1sq);
+  *f2 = sqrt(f2sq);
+  return true;
+}
+
+// grid (ceil(T / 64), pairs): thread = sample `it` of pair blockIdx.y.  cand_F[(p * T + it) * 9] row-major,
+// cand_ok[p * T + it].  A pair with 8..15 matches has one "sample": all of them (:40-49).
+__global__ __launch_bounds__(POSE_WAVE) void k_f8_hyp(int T, const int* __restrict__ off, const double* __restrict__ pts_ref,
+                                                      const double* __restrict__ pts_cur, uint64_t seed, double* __restrict__ cand_F,
+                                                      uint8_t* __restrict__ cand_ok) {
+  const int p = blockIdx.y, it = blockIdx.x * POSE_WAVE + threadIdx.x;
+  if (it >= T) return;
+  const int o = off[p], N = off[p + 1] - o;
+  uint8_t* cok = cand_ok + (size_t)p * T + it;
+  if (N < 8 || (N < 16 && it > 0)) { *cok = 0; return; }
+  int idx[F8_MAXN];
+  int n = 8;
+  if (N < 16) { n = N; for (int k = 0; k < N; k++) idx[k] = k; }
+  else pose_sample<8>(seed, F8_SALT, p, it, N, idx);
+  double a[2 * F8_MAXN], b[2 * F8_MAXN];
+  for (int k = 0; k < n; k++) {
+    a[2 * k] = pts_ref[2 * ((size_t)o + idx[k])]; a[2 * k + 1] = pts_ref[2 * ((size_t)o + idx[k]) + 1];
+    b[2 * k] = pts_cur[2 * ((size_t)o + idx[k])]; b[2 * k + 1] = pts_cur[2 * ((size_t)o + idx[k]) + 1];
+  }
+  double F[9];
+  const bool good = f8_fit(a, b, n, F);
+  if (good) {
+    double* out = cand_F + ((size_t)p * T + it) * 9;
+    for (int k = 0; k < 9; k++) out[k] = F[k];
+  }
+  *cok = good ? 1 : 0;
+}
+
+// workgroup = candidate (pair, sample): the Sampson sum over all matches (Error :205-221).  The terms are independent, so
+// all threads form them, 256 matches at a time; thread 0 adds them in match order - the sum the sequential loop forms.
+__global__ __launch_bounds__(256) void k_f8_score(int T, const int* __restrict__ off, const double* __restrict__ pts_ref,
+                                                  const double* __restrict__ pts_cur, const double* __restrict__ cand_F,
+                                                  const uint8_t* __restrict__ cand_ok, double* __restrict__ cand_err) {
+  __shared__ double s_term[256];
+  const int p = blockIdx.y, it = blockIdx.x, tid = threadIdx.x;
+  if (!cand_ok[(size_t)p * T + it]) return;
+  const int o = off[p], N = off[p + 1] - o;
+  double F[9];
+  for (int k = 0; k < 9; k++) F[k] = cand_F[((size_t)p * T + it) * 9 + k];
+  double total = 0.0;
+  for (int base = 0; base < N; base += 256) {
+    const int i = base + tid;
+    if (i < N) {
+      const double ax = pts_ref[2 * ((size_t)o + i)], ay = pts_ref[2 * ((size_t)o + i) + 1];
+      const double bx = pts_cur[2 * ((size_t)o + i)], by = pts_cur[2 * ((size_t)o + i) + 1];
+      const double l0 = F[0] * ax + F[1] * ay + F[2] * 1.0, l1 = F[3] * ax + F[4] * ay + F[5] * 1.0, l2 = F[6] * ax + F[7] * ay + F[8] * 1.0;
+      const double num = bx * l0 + by * l1 + 1.0 * l2;
+      const double d0 = bx * F[0] + by * F[3] + 1.0 * F[6], d1 = bx * F[1] + by * F[4] + 1.0 * F[7];
+      const double den = d0 * d0 + d1 * d1 + l0 * l0 + l1 * l1;
+      s_term[tid] = num * num / den;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      const int m = N - base < 256 ? N - base : 256;
+      for (int k = 0; k < m; k++) total += s_term[k];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) cand_err[(size_t)p * T + it] = total;
+}
+
+// One workgroup per pair: replay `if (error_i < error_min)` from 1e6 over the candidates in sample order (the first
+// candidate is kept when none is below, :82-96), then on thread 0 the focal lengths and E = diag(f2, f2, 1) F
+// diag(f1, f1, 1) (relative_pose_from_fundamental_matrix.cc:125-136), then the decomposition and cheirality vote on
+// pts / f (:39-48), whose verdict the reference ignores.
+__global__ __launch_bounds__(256) void k_f8_select(int T, const int* __restrict__ off, const double* __restrict__ pts_ref,
+                                                   const double* __restrict__ pts_cur, const double* __restrict__ cand_F,
+                                                   const uint8_t* __restrict__ cand_ok, const double* __restrict__ cand_err,
+                                                   double* __restrict__ Fout, double* __restrict__ f1out, double* __restrict__ f2out,
+                                                   double* __restrict__ Eout, double* __restrict__ Rout, double* __restrict__ tout,
+                                                   uint8_t* __restrict__ ok, int* __restrict__ best_iter, double* __restrict__ best_error,
+                                                   int* __restrict__ n_candidates) {
+  __shared__ double s_e[256];
+  __shared__ int s_k[256], s_first[256], s_cnt[256];
+  __shared__ double s_R[4][9], s_t[4][3], s_E[9], s_f[2];
+  __shared__ int s_votes[4], s_fok;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int o = off[p], N = off[p + 1] - o;
+  double be = 1000000.0;
+  int bk = -1, first = 0x7fffffff, cnt = 0;
+  for (int it = tid; it < T; it += 256) {
+    if (!cand_ok[(size_t)p * T + it]) continue;
+    cnt++;
+    if (it < first) first = it;
+    const double e = cand_err[(size_t)p * T + it];
+    if (e < be) { be = e; bk = it; }
+  }
+  s_e[tid] = be; s_k[tid] = bk; s_first[tid] = first; s_cnt[tid] = cnt;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) {
+      const double e2 = s_e[tid + st];
+      const int k2 = s_k[tid + st];
+      if (k2 >= 0 && (s_k[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && k2 < s_k[tid]))) { s_e[tid] = e2; s_k[tid] = k2; }
+      if (s_first[tid + st] < s_first[tid]) s_first[tid] = s_first[tid + st];
+      s_cnt[tid] += s_cnt[tid + st];
+    }
+    __syncthreads();
+  }
+  const int nC = s_cnt[0];
+  if (tid < 4) s_votes[tid] = 0;
+  if (tid == 0) {
+    for (int k = 0; k < 9; k++) { Fout[9 * (size_t)p + k] = 0.0; Eout[9 * (size_t)p + k] = 0.0; Rout[9 * (size_t)p + k] = 0.0; }
+    for (int k = 0; k < 3; k++) tout[3 * (size_t)p + k] = 0.0;
+    f1out[p] = 0.0; f2out[p] = 0.0;
+    ok[p] = 0;
+    best_iter[p] = -1; best_error[p] = 1000000.0; n_candidates[p] = nC;
+    s_fok = 0;
+    if (nC > 0) {
+      const int key = s_k[0] >= 0 ? s_k[0] : s_first[0];
+      const double* F = cand_F + ((size_t)p * T + key) * 9;
+      for (int k = 0; k < 9; k++) Fout[9 * (size_t)p + k] = F[k];
+      best_iter[p] = key;
+      if (s_k[0] >= 0) best_error[p] = s_e[0];
+      double f1, f2;
+      if (f8_focal(F, &f1, &f2, nullptr, nullptr)) {
+        const double d1[3] = {f1, f1, 1.0}, d2[3] = {f2, f2, 1.0};
+        for (int i = 0; i < 3; i++)
+          for (int j = 0; j < 3; j++) {
+            const double e = d2[i] * F[3 * i + j] * d1[j];
+            Eout[9 * (size_t)p + 3 * i + j] = e;
+            s_E[i + 3 * j] = e;
+          }
+        f1out[p] = f1; f2out[p] = f2;
+        s_f[0] = f1; s_f[1] = f2;
+        ok[p] = 1;
+        s_fok = 1;
+      }
+    }
+  }
+  __syncthreads();
+  if (!s_fok) return;
+  pose_from_E_block(s_E, N, pts_ref + 2 * (size_t)o, pts_cur + 2 * (size_t)o, s_f[0], s_f[1], tid, s_R, s_t, s_votes,
+                    Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
 }
 
 MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w, const double* pts_2d,
@@ -1411,6 +1688,62 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  if (n_candidates) HIP_TRY(ctx, hipMemcpyAsync(n_candidates, d_nc.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const double* pts_ref, const double* pts_cur,
+                                    int ransac_times, uint64_t seed, double* F, double* f_ref, double* f_cur, double* E, double* R, double* t,
+                                    uint8_t* ok, int* best_iter, double* best_error, int* n_candidates) {
+  if (!ctx || n_pairs < 0 || !offsets || !F || !f_ref || !f_cur || !E || !R || !t || !ok) return MSFM_E_INVAL;
+  if (ransac_times < 1 || ransac_times > 65536) return msfm_set_error(ctx, MSFM_E_INVAL, "relpose8: ransac_times out of range");
+  if (n_pairs == 0) return MSFM_OK;
+  if (n_pairs > 65535) return msfm_set_error(ctx, MSFM_E_INVAL, "relpose8: at most 65535 pairs per call");
+  MSFM_TRY(msfm_check_offsets(ctx, "relpose8", n_pairs, offsets));
+  const int total = offsets[n_pairs];
+  if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int T = ransac_times;
+  DevBuf<int> d_off, d_bi, d_nc;
+  DevBuf<double> d_a, d_b, d_cF, d_ce, d_F, d_f1, d_f2, d_E, d_R, d_t, d_be;
+  DevBuf<uint8_t> d_cok, d_ok;
+  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
+  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
+  HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_b.alloc(2 * (size_t)std::max(1, total)));
+  HIP_TRY(ctx, d_a.upload(pts_ref, 2 * (size_t)total, s));
+  HIP_TRY(ctx, d_b.upload(pts_cur, 2 * (size_t)total, s));
+  HIP_TRY(ctx, d_cF.alloc((size_t)n_pairs * T * 9));
+  HIP_TRY(ctx, d_ce.alloc((size_t)n_pairs * T));
+  HIP_TRY(ctx, d_cok.alloc((size_t)n_pairs * T));
+  HIP_TRY(ctx, d_F.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs));
+  HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs)); HIP_TRY(ctx, d_f1.alloc(n_pairs)); HIP_TRY(ctx, d_f2.alloc(n_pairs));
+  HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_bi.alloc(n_pairs)); HIP_TRY(ctx, d_be.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
+  {
+    KTimer tm(ctx, "pose_f8_hyp");
+    hipLaunchKernelGGL(k_f8_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off.p, d_a.p, d_b.p, seed, d_cF.p, d_cok.p);
+  }
+  {
+    KTimer tm(ctx, "pose_f8_score");
+    hipLaunchKernelGGL(k_f8_score, dim3(T, n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_cF.p, d_cok.p, d_ce.p);
+  }
+  {
+    KTimer tm(ctx, "pose_f8_select");
+    hipLaunchKernelGGL(k_f8_select, dim3(n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_cF.p, d_cok.p, d_ce.p, d_F.p, d_f1.p, d_f2.p,
+                       d_E.p, d_R.p, d_t.p, d_ok.p, d_bi.p, d_be.p, d_nc.p);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(F, d_F.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(f_ref, d_f1.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(f_cur, d_f2.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(E, d_E.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_bi.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
+  if (best_error) HIP_TRY(ctx, hipMemcpyAsync(best_error, d_be.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   if (n_candidates) HIP_TRY(ctx, hipMemcpyAsync(n_candidates, d_nc.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return MSFM_OK;
