@@ -295,6 +295,10 @@ typedef struct msfm_ba_layout {
    * persistent k_chain launch, MSFM_PATH_ROOT_CHAIN = the root chain as one, MSFM_PATH_BACKSOLVE_CHAIN = the back
    * substitution as one k_backsolve_chain launch; a clear bit = one launch per 64-column panel / block pair */
   int solve_paths;
+  /* eliminated points by track length class (msfm_ba_create orders them class-major): up to 8 rows, 9..16 rows, more.  The
+   * point kernels give a point of the first class 8 lanes, of the second 16 - one row per lane - and take the rows of the
+   * third in rounds of 8; a workgroup never mixes classes */
+  int npb_S, npb_L, npb_X;
 } msfm_ba_layout;
 #define MSFM_PATH_LEVEL_CHAIN(l) (1 << (l))
 #define MSFM_PATH_ROOT_CHAIN (1 << 3)

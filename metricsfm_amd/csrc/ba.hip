@@ -6,13 +6,13 @@
 // of the reference's projection model, Huber(1) corrector, Jacobi column scaling; written
 // point-major SoA (for the per-point kernels) and camera-major AoS (for the per-camera sums).
 // Per linear solve:
-//   k_point      one thread per point: V = Jp^T Jp + D^2, 3x3 Cholesky, T = (Jc^T Jp) L^-T per
+//   k_point      8 or 16 lanes per point, lane = observation (PtMap): V = Jp^T Jp + D^2, 3x3 Cholesky, T = (Jc^T Jp) L^-T per
 //                observation, T.u for the right-hand side
 //   k_ftf        one wave per chunk of a camera's observations: Jc^T Jc, Jm^T Jc, Jm^T Jm, J^T r
 //   k_pairs      one wave per chunk of a (block row, block col) pair list: sum T_a T_b^T — the
 //                Schur complement contributions W V^-1 W^T, reduced in a fixed order (no atomics)
 //   k_asm_*      assemble S and rhs into the padded dense matrix; chol.hip factors and solves
-//   k_backsub    one thread per point: back substitution, candidate point, model cost change
+//   k_backsub    the same lane groups: back substitution, candidate point, model cost change
 // The LM control flow (step acceptance, radius update, stopping rules) follows Ceres 1.13's
 // TrustRegionMinimizer and runs on the host; one small scalar read-back per phase.
 #include <algorithm>
@@ -285,8 +285,34 @@ __global__ __launch_bounds__(1024) void k_reduce(ReduceJobs J, double* __restric
 // (record_i | record_j << 16) - which one wave instruction per 256 words copies straight into LDS.  slot0: the first slot's
 // index in workgroup-major numbering (for its rank); n_diag: how many of the pass's slots (its first ones) are camera-diagonal.
 struct FoldPass { int off, words, slot0, n_slots, n_diag, pad0, pad1, pad2; };
+// The point workgroups of k_point and k_backsub.  msfm_ba_create orders the eliminated points by track length class first:
+// S = up to 8 rows, L = 9..16 rows, X = more.  An S workgroup holds 32 points with 8 lanes each, an L workgroup 16 points
+// with 16 lanes each - lane = row, every row is linearised exactly once - and an X workgroup 32 points with 8 lanes each that
+// take their rows in rounds of 8.  A workgroup never mixes classes (a wave that held ONE long point among short ones used to
+// run the long-track code in full for it: 4.0 linearisations per wave of k_point at config 3 where one is enough); the last
+// workgroup of a class may be partly filled.
+struct PtMap {
+  int nS, nL, nX;   // points per class: blocks [0, nS), [nS, nS + nL), [nS + nL, npb)
+  int wS, wL;       // workgroups of the first two classes (the X workgroups follow)
+};
+__host__ __device__ inline int ptmap_lanes(const PtMap& m, int w) { return w < m.wS ? 8 : w < m.wS + m.wL ? 16 : 0; }   // (0: X, rounds)
+__host__ __device__ inline int ptmap_wg_first(const PtMap& m, int w) {
+  return w < m.wS ? 32 * w : w < m.wS + m.wL ? m.nS + 16 * (w - m.wS) : m.nS + m.nL + 32 * (w - m.wS - m.wL);
+}
+__host__ __device__ inline int ptmap_wg_end(const PtMap& m, int w) {   // one past the workgroup's last point
+  const int e = ptmap_wg_first(m, w) + (ptmap_lanes(m, w) == 16 ? 16 : 32);
+  const int cap = w < m.wS ? m.nS : w < m.wS + m.wL ? m.nS + m.nL : m.nS + m.nL + m.nX;
+  return e < cap ? e : cap;
+}
+__host__ __device__ inline int ptmap_wg_of(const PtMap& m, int pb) {
+  return pb < m.nS ? pb >> 5 : pb < m.nS + m.nL ? m.wS + ((pb - m.nS) >> 4) : m.wS + m.wL + ((pb - m.nS - m.nL) >> 5);
+}
+__host__ __device__ inline int ptmap_class(int rows) { return rows <= 8 ? 0 : rows <= 16 ? 1 : 2; }
+static inline PtMap ptmap_make(int nS, int nL, int nX) { return PtMap{nS, nL, nX, (nS + 31) / 32, (nL + 15) / 16}; }
+static inline int ptmap_n_wg(const PtMap& m) { const int n = m.wS + m.wL + (m.nX + 31) / 32; return n > 0 ? n : 1; }   // (an empty launch is not one)
 struct PointPtrs {
   BaPtrs B;            // row data, parameters and scales the rows are linearised with
+  PtMap map;
   int npb, NCR;
   const int *pt_first, *pm_first, *pm_mb;
   double *diag_p;
@@ -297,7 +323,7 @@ struct PointPtrs {
   double* cost_partial;
   int* fail;
   // FoldTables (fold_wg nullptr: every product goes through the pair lists)
-  const int *fold_wg, *fold_ovf_off, *fold_wg_pass_first, *fold_slot_rank;
+  const int *fold_wg, *fold_wg_pass_first, *fold_slot_rank;
   const FoldPass* fold_pass;
   const unsigned* fold_stream;
   double* fold_partial;
@@ -310,23 +336,28 @@ struct PointPtrs {
 };
 
 // (8-lane groups; after the first two steps the four lanes of a quad hold the same value, so adding lane 7 - i is adding lane i ^ 4)
-#define GROUP_SUM(x) { x += dpp_f64<MSFM_DPP_XOR1>(x); x += dpp_f64<MSFM_DPP_XOR2>(x); x += dpp_f64<MSFM_DPP_HALF_MIRROR>(x); }
+#define GROUP_SUM8(x) { x += dpp_f64<MSFM_DPP_XOR1>(x); x += dpp_f64<MSFM_DPP_XOR2>(x); x += dpp_f64<MSFM_DPP_HALF_MIRROR>(x); }
+// (16-lane groups: the partner lane ^ 8 first - both then hold x_s + x_{s+8}, what one lane summed over two rounds of 8 - then as above)
+#define GROUP_SUM(x) { if constexpr (LPP == 16) x += dpp_f64<MSFM_DPP_ROR8>(x); GROUP_SUM8(x) }
 
-// 8 lanes per point, lane = observation (rounds of 8 for longer tracks).  Every lane linearises its own row
-// (obs_linearize: the row data is read coalesced, the parameters come from cache), the per-point sums are 3-step
-// reductions inside the 8-lane group, and every lane then finishes its own observation's T = (Jc^T Jp) L^-T.
-// 256 threads = 32 points.  Tracks of up to 8 views keep their rows in registers; longer ones linearise them again.
-#define FOLD_OVF 51   // second-round records (rows 8..15 of a point) a workgroup can park beside the 256 first-round ones
-#define FOLD_NREC (256 + FOLD_OVF)   // records of 2 x 10 doubles (two 16-byte aligned halves of 9) in the 48 KB row park
+// LPP lanes per point, lane = observation: LPP = 8 and 16 in the S and L workgroups (PtMap), where every lane linearises its
+// own row exactly once (obs_linearize: the row data is read coalesced, the parameters come from cache) and parks it in LDS;
+// LPP = 0 in the X workgroups: 8 lanes per point, rounds of 8, and the rows are linearised again wherever they are needed.
+// The per-point sums are reductions inside the lane group, and every lane then finishes its own observation's
+// T = (Jc^T Jp) L^-T.
+#define FOLD_NREC 256        // records of 2 x 10 doubles (two 16-byte aligned halves of 9) in the 48 KB row park: one per lane
 #define FOLD_WORDS 1024      // words (slot headers + entries) of one pass, staged in LDS
 #define FOLD_PASS_SLOTS 128  // slots of one pass at most: four threads per slot, two rounds
+template <int LPP>
 __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restrict__ gmax_partial, double* sh, double* park, unsigned* ent_s) {
-  const int tid = threadIdx.x, sub = tid & 7;
-  const int pb = blockIdx.x * 32 + (tid >> 3);
-  const bool act = pb < P.npb;
+  constexpr int GW = LPP ? LPP : 8;    // lanes of a point
+  constexpr bool single = LPP != 0;    // the point's rows are all in the lanes of its group
+  const int tid = threadIdx.x, sub = tid & (GW - 1);
+  const int pb = ptmap_wg_first(P.map, blockIdx.x) + tid / GW;
+  const bool act = pb < ptmap_wg_end(P.map, blockIdx.x);
   // FoldTables: the slot headers and entries of the workgroup's first pass start on their way into LDS now (one
   // global_load_lds_dwordx4 per wave and 256 words; nothing waits for them before the fold phase at the end)
-  const bool fold = P.fold_wg != nullptr && P.mode != 1 && P.fold_wg[blockIdx.x] != 0;
+  const bool fold = single && P.fold_wg != nullptr && P.mode != 1 && P.fold_wg[blockIdx.x] != 0;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   auto stage = [&](int off, int words) {
     if (256 * wv < words)
@@ -341,26 +372,30 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
   }
   int f = 0, l = 0;
   if (act) { f = P.pt_first[pb]; l = P.pt_first[pb + 1]; }
-  const bool single = (l - f) <= 8;
   double V00 = 0, V10 = 0, V11 = 0, V20 = 0, V21 = 0, V22 = 0, g0 = 0, g1 = 0, g2 = 0;
-  // The lane's row of the (only) round waits in LDS (component-major, one column per thread: no bank conflicts) while
-  // the point's 3x3 system is reduced and factored - 48 registers less across that phase.
+  // The lane's row waits in LDS (component-major, one column per thread: no bank conflicts) while the point's 3x3 system is
+  // reduced and factored - 48 registers less across that phase.
   double cost = 0.0;
-  for (int base = f; base < l; base += 8) {
-    const int i = base + sub;
-    if (i < l) {
-      double r0, r1, jcs[12], jms[6], jps[6];
-      const double ci = obs_linearize(P.B, i, r0, r1, jcs, jms, jps);
+  auto lin_row = [&](int i) {
+    double r0, r1, jcs[12], jms[6], jps[6];
+    const double ci = obs_linearize(P.B, i, r0, r1, jcs, jms, jps);
+    if constexpr (single) {
 #pragma unroll
       for (int k = 0; k < 12; k++) park[k * 256 + tid] = jcs[k];
 #pragma unroll
       for (int k = 0; k < 6; k++) { park[(12 + k) * 256 + tid] = jms[k]; park[(18 + k) * 256 + tid] = jps[k]; }
-      if (P.store_rows) cost += ci;
-      const double a0 = jps[0], a1 = jps[1], a2 = jps[2], b0 = jps[3], b1 = jps[4], b2 = jps[5];
-      V00 += a0 * a0 + b0 * b0; V10 += a1 * a0 + b1 * b0; V11 += a1 * a1 + b1 * b1;
-      V20 += a2 * a0 + b2 * b0; V21 += a2 * a1 + b2 * b1; V22 += a2 * a2 + b2 * b2;
-      g0 += a0 * r0 + b0 * r1; g1 += a1 * r0 + b1 * r1; g2 += a2 * r0 + b2 * r1;
     }
+    if (P.store_rows) cost += ci;
+    const double a0 = jps[0], a1 = jps[1], a2 = jps[2], b0 = jps[3], b1 = jps[4], b2 = jps[5];
+    V00 += a0 * a0 + b0 * b0; V10 += a1 * a0 + b1 * b0; V11 += a1 * a1 + b1 * b1;
+    V20 += a2 * a0 + b2 * b0; V21 += a2 * a1 + b2 * b1; V22 += a2 * a2 + b2 * b2;
+    g0 += a0 * r0 + b0 * r1; g1 += a1 * r0 + b1 * r1; g2 += a2 * r0 + b2 * r1;
+  };
+  if constexpr (single) {
+    if (f + sub < l) lin_row(f + sub);
+  } else {
+    for (int base = f; base < l; base += 8)
+      if (base + sub < l) lin_row(base + sub);
   }
   GROUP_SUM(V00) GROUP_SUM(V10) GROUP_SUM(V11) GROUP_SUM(V20) GROUP_SUM(V21) GROUP_SUM(V22)
   GROUP_SUM(g0) GROUP_SUM(g1) GROUP_SUM(g2)
@@ -420,7 +455,8 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     // 0.28 -> 0.49 ms).
     // Round 3 (FoldTables): in a folding workgroup every record also stays in LDS (record-major, where the parked rows were,
     // once every lane is done with those) and the camera x camera products are formed from there below.
-    const int wl = tid & 63, tsrc = ((wl & 7) << 3) | (wl >> 3);
+    // (16 lanes per point: (point q of 4, observation s) -> lane 4 s + q)
+    const int wl = tid & 63, tsrc = GW == 16 ? ((wl & 3) << 4) | (wl >> 2) : ((wl & 7) << 3) | (wl >> 3);
     const bool need_T = !fold || P.fold_mc_partial == nullptr || P.keep_T;   // (uniform over the workgroup)
     auto round = [&](int rd, double (&Tk)[18], int& cpk) {
       const int i = f + rd + sub;
@@ -510,7 +546,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
         if (f + sub < l) my_mb = P.B.o_mb[f + sub];   // (the lane's row of the first round)
       }
       double pjm[6], pjp[6];
-      if (single) {
+      if constexpr (single) {
 #pragma unroll
         for (int k = 0; k < 6; k++) { pjm[k] = park[(12 + k) * 256 + tid]; pjp[k] = park[(18 + k) * 256 + tid]; }
       }
@@ -552,7 +588,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
         }
       };
       // (two separate paths, so that the rows held in registers are not alive beside the linearisation of the long tracks)
-      if (single) {
+      if constexpr (single) {
         for (int e = pe0; e < pe1; e++) {
           const int mb = e == pe0 ? mb_first : P.pm_mb[e];
           double W[9];
@@ -582,15 +618,8 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
 #pragma unroll
         for (int k = 0; k < 9; k++) ((k & 1) ? H1 : H0)[(tid + (k >> 1)) * 10 + 9] = 0.0;
       }
-      for (int rd = 8; __any(f + rd < l); rd += 8) {
-        const int ovf = (fold && act) ? P.fold_ovf_off[pb] : 0;   // (asked for before the round's own loads)
-        round(rd, Tk, cpk);
-        if (fold && cpk >= 0) {
-          const int rec = 256 + ovf + (rd - 8) + sub;
-          rec_st(rec, Tk);
-          H0[rec * 10 + 9] = (double)(tid >> 3);   // (a second-round record names its point)
-        }
-      }
+      if constexpr (!single)
+        for (int rd = 8; __any(f + rd < l); rd += 8) round(rd, Tk, cpk);
     }
     if (fold) {
       const int q = tid & 3, ra = q >> 1, rb = q & 1, sl4 = tid >> 2;   // rows 3 ra .. of record i times rows 3 rb .. of record j
@@ -647,9 +676,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
               for (int c = 0; c < 3; c++)
                 acc[a * 3 + c] += ti[a * 3] * tj[c * 3] + ti[a * 3 + 1] * tj[c * 3 + 1] + ti[a * 3 + 2] * tj[c * 3 + 2];
             if (mcd && (pr & 0xffffu) == (pr >> 16)) {
-              const int rec = (int)(pr & 0xffffu);
-              int r0 = rec & ~7;
-              if (rec >= 256) r0 = 8 * (int)H0[rec * 10 + 9];   // (second-round record: its point is written beside it)
+              const int r0 = (int)(pr & 0xffffu) & ~(GW - 1);   // (the first record of the point)
               double tm[6];
 #pragma unroll
               for (int k6 = 0; k6 < 6; k6++) { const int k = 3 * ma0 + k6; tm[k6] = ((k & 1) ? H1 : H0)[(r0 + (k >> 1)) * 10 + 9]; }   // (row 3 is never used)
@@ -686,13 +713,17 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
   if (threadIdx.x == 0) gmax_partial[blockIdx.x] = t;
 }
 // (three waves per SIMD: 168 registers with three dwords of scratch, against 175 and two waves: 0.337 -> 0.309 ms at C3;
-// the 48 KB of parked rows allow exactly three workgroups per CU)
+// the 48 KB of parked rows allow exactly three workgroups per CU.  With one body per length class - none of which holds
+// both the parked-row path and the linearise-again path - the kernel needs 145 registers and no scratch.)
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_point(PointPtrs P, double* __restrict__ gmax_partial) {
   __shared__ double sh[4];
   __shared__ double park[24 * 256];
   __shared__ __attribute__((aligned(16))) unsigned ent_s[FOLD_WORDS];
   if (P.spec && P.spec[0] == 0.0) return;   // enqueued ahead of a step that was not accepted
-  k_point_body(P, gmax_partial, sh, park, ent_s);
+  const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
+  if (lanes == 8) k_point_body<8>(P, gmax_partial, sh, park, ent_s);
+  else if (lanes == 16) k_point_body<16>(P, gmax_partial, sh, park, ent_s);
+  else k_point_body<0>(P, gmax_partial, sh, park, ent_s);
 }
 
 // The static inputs of a row in camera-major order (k_ftf): built once per problem from the resident row arrays.
@@ -1360,6 +1391,7 @@ __global__ __launch_bounds__(256) void k_update_params(int ncb, int nmb, const i
 
 struct BackPtrs {
   BaPtrs B;   // the rows are linearised again (obs_linearize) at the point the reduced system was built at
+  PtMap map;
   int npb, ncb;
   const int *pt_first, *pb_pt;
   const double *ptL, *z;
@@ -1370,22 +1402,25 @@ struct BackPtrs {
   double* rot_c;
 };
 
-// 8 lanes per point, lane = observation, single pass: besides y = sum Jp^T (r + q) with
+// The workgroups and lane groups of k_point (PtMap: LPP = 8 or 16 lanes per point, lane = observation, or rounds of 8 for
+// LPP = 0), single pass: besides y = sum Jp^T (r + q) with
 // q = -(Jc z_c + Jm z_m), the group accumulates the moments that give this point's model cost change
 //   -(J s)^T (r + J s / 2) = -[ sp.g + sum q.r + 1/2 sp^T V sp + sp.(sum Jp^T q) + 1/2 sum q.q ]
 // so the step sp (known only after the group reduction) never needs a second sweep.
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_backsub(BackPtrs P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
-                                                  double* __restrict__ x2_partial) {
-  __shared__ double sh[4];
-  const int tid = threadIdx.x, sub = tid & 7;
-  const int pb = blockIdx.x * 32 + (tid >> 3);
-  const bool act = pb < P.npb;
+template <int LPP>
+__device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
+                                               double* __restrict__ x2_partial, double* sh) {
+  constexpr int GW = LPP ? LPP : 8;
+  const int tid = threadIdx.x, sub = tid & (GW - 1);
+  const int pb = ptmap_wg_first(P.map, blockIdx.x) + tid / GW;
+  const bool act = pb < ptmap_wg_end(P.map, blockIdx.x);
   for (int c = blockIdx.x * 256 + tid; c < P.Nc; c += gridDim.x * 256) msfm_rot_prepare(P.cam_c + 6 * (size_t)c, P.rot_c + 4 * (size_t)c);
   int f = 0, l = 0;
   if (act) { f = P.pt_first[pb]; l = P.pt_first[pb + 1]; }
   double V00 = 0, V10 = 0, V11 = 0, V20 = 0, V21 = 0, V22 = 0, g0 = 0, g1 = 0, g2 = 0, h0 = 0, h1 = 0, h2 = 0, qr = 0, qq = 0;
-  for (int base = f; base < l; base += 8) {
-    const int i = base + sub;
+  const int n_rounds = LPP ? 1 : (l - f + 7) >> 3;   // (S, L: one trip of either loop)
+  for (int rd = 0; rd < n_rounds; rd++) {
+    const int i = f + GW * rd + sub;
     if (i < l) {
       // rows of frozen blocks come out as zeros, so no branches
       double jp[6], r0, r1, q0, q1;
@@ -1442,9 +1477,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   }
   // the candidate to every row of the point in camera-major order (what k_ftf reads if the step is accepted): lane = row again
   // (measured: trading the records between the lanes first, as k_point does for its T stores, made this SLOWER - 104 against 98 us)
-  cand0 = __shfl(cand0, 0, 8); cand1 = __shfl(cand1, 0, 8); cand2 = __shfl(cand2, 0, 8);
-  for (int base = f; base < l; base += 8) {
-    const int i = base + sub;
+  cand0 = __shfl(cand0, 0, GW); cand1 = __shfl(cand1, 0, GW); cand2 = __shfl(cand2, 0, GW);
+  for (int rd = 0; rd < n_rounds; rd++) {
+    const int i = f + GW * rd + sub;
     if (i < l) {
       const int cp = P.B.o_cpos[i];
       if (cp >= 0) { double* xr = P.cm_Xc + 3 * (size_t)cp; xr[0] = cand0; xr[1] = cand1; xr[2] = cand2; }
@@ -1454,6 +1489,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const double t1 = block_sum256(dx2, sh);
   const double t2 = block_sum256(x2, sh);
   if (threadIdx.x == 0) { mcc_partial[blockIdx.x] = t0; dx2_partial[blockIdx.x] = t1; x2_partial[blockIdx.x] = t2; }
+}
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_backsub(BackPtrs P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
+                                                  double* __restrict__ x2_partial) {
+  __shared__ double sh[4];
+  const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
+  if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  else if (lanes == 16) k_backsub_body<16>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  else k_backsub_body<0>(P, mcc_partial, dx2_partial, x2_partial, sh);
 }
 
 // model cost change of rows without an eliminated point (obs [AE, A)) and of the GPS rows.
@@ -1599,16 +1642,16 @@ __global__ __launch_bounds__(256) void k_pack_blocks(int nblk, const int* __rest
 // its 32 points in LDS; the entries (record i, record j) of those points are sorted by block at create time, every distinct
 // block of a workgroup is a SLOT, four threads sum a slot's 6 x 6 products in point order and write ONE partial per slot
 // (config 3: 268 k slots = 77 MB instead of 4.8 M entry pairs = 1.3 GB of gathered T records).  The assembly adds a
-// block's slot partials (ranked by block) to its chunk partials.  Workgroups whose records do not fit (a point with more
-// than 16 rows, more than FOLD_OVF second-round records) keep the gather path: their entries stay live in the pair list,
-// the others are marked (pa < 0) and skipped by k_pairs.
+// block's slot partials (ranked by block) to its chunk partials.  A record is the T of one lane's row, so the S and L
+// workgroups (PtMap) fold; the X workgroups (points with more than 16 rows) keep the gather path: their entries stay live in
+// the pair list, the others are marked (pa < 0) and skipped by k_pairs.
 struct FoldTables {
   bool on = false;
   bool all = false;   // every entry of the camera x camera list is folded: k_pairs<6,6> and its chunk partials are not needed at all
   int n_live = 0;     // chunks of the camera x camera list that still hold a live entry (the others' partials stay zero)
   DevBuf<int> live_chunk;
   int n_wg = 0, n_slots = 0, n_entries = 0, n_pass = 0;
-  DevBuf<int> wg_fold, ovf_off, wg_pass_first, slot_rank, blk_range;
+  DevBuf<int> wg_fold, wg_pass_first, slot_rank, blk_range;
   DevBuf<uint8_t> blk_live;   // camera x camera blocks that still have an entry on the gather path
   DevBuf<FoldPass> pass;
   DevBuf<unsigned> stream;   // per pass: slot headers, then entries (FoldPass); FOLD_WORDS words of padding behind the last pass
@@ -1633,6 +1676,7 @@ struct msfm_ba {
   msfm_ctx* ctx = nullptr;
   int Nc = 0, Nm = 0, Np = 0;
   int ncb = 0, nmb = 0, npb = 0, nred = 0, npad = 0;
+  PtMap map = {0, 0, 0, 0, 0};   // the eliminated points by track length class, and their workgroups
   // solver layout of the reduced system: camera block cb at column cb_off[cb], intrinsics at mo + 3 mb, order nsys
   int nsys = 0, mo = 0, n_padcol = 0;
   msfm_env env;   // the switches as they were at msfm_ba_create (common.h)
@@ -2295,6 +2339,15 @@ __global__ __launch_bounds__(256) void k_u8_to_int(int n, const uint8_t* __restr
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) b[i] = a[i] ? 1 : 0;
 }
+// length class of every point in key order (PtMap), and how many points each class has
+__global__ __launch_bounds__(256) void k_point_classes(int npb, const int* __restrict__ pb_pt, const int* __restrict__ cnt, int* __restrict__ cls,
+                                                        int* __restrict__ n_class) {
+  const int pb = blockIdx.x * 256 + threadIdx.x;
+  if (pb >= npb) return;
+  const int c = ptmap_class(cnt[pb_pt[pb]]);
+  cls[pb] = c;
+  atomicAdd(&n_class[c], 1);
+}
 __global__ __launch_bounds__(256) void k_point_lengths(int npb, const int* __restrict__ pb_pt, const int* __restrict__ cnt, int* __restrict__ len,
                                                         int* __restrict__ pt_slot) {
   const int pb = blockIdx.x * 256 + threadIdx.x;
@@ -2613,32 +2666,26 @@ struct PairBuild {
 
 // ---- fold tables (FoldTables above), built from the resident index structures whichever way those were made ----
 namespace devsetup {
-__global__ __launch_bounds__(256) void k_fold_wg(int npb, int n_wg, const int* __restrict__ pt_first, int* __restrict__ ovf_off, int* __restrict__ wg_fold) {
+__global__ __launch_bounds__(256) void k_fold_wg(PtMap map, int n_wg, int* __restrict__ wg_fold) {
   const int w = blockIdx.x * 256 + threadIdx.x;
-  if (w >= n_wg) return;
-  int ovf = 0, ok = 1;
-  for (int pb = 32 * w; pb < min(npb, 32 * w + 32); pb++) {
-    const int k = pt_first[pb + 1] - pt_first[pb];
-    ovf_off[pb] = ovf;
-    if (k > 16) ok = 0;
-    ovf += max(0, k - 8);
-  }
-  wg_fold[w] = ok && ovf <= FOLD_OVF;
+  if (w < n_wg) wg_fold[w] = ptmap_lanes(map, w) != 0;   // (record = lane: every S and L workgroup folds)
 }
 // block key of a slot: the camera-diagonal blocks first (a workgroup's diagonal slots are then its first ones, and their
 // ranks are 0 .. number of diagonal slots - 1: the index of the intrinsics x camera partials)
 __host__ __device__ inline unsigned fold_block_key(int row, int col, int ncb) { return row == col ? (unsigned)row : (unsigned)ncb + (unsigned)row * (unsigned)ncb + (unsigned)col; }
 template <bool EMIT>
-__global__ __launch_bounds__(256) void k_fold_entries(int npb, int ncb, const int* __restrict__ pt_first, const int* __restrict__ o_cb,
-                                                       const int* __restrict__ o_cpos, const int* __restrict__ wg_fold, const int* __restrict__ ovf_off,
+__global__ __launch_bounds__(256) void k_fold_entries(int npb, int ncb, PtMap map, const int* __restrict__ pt_first, const int* __restrict__ o_cb,
+                                                       const int* __restrict__ o_cpos, const int* __restrict__ wg_fold,
                                                        int* __restrict__ count, const int* __restrict__ offset, unsigned long long* __restrict__ key,
                                                        unsigned* __restrict__ val) {
   const int pb = blockIdx.x * 256 + threadIdx.x;
   if (pb >= npb) return;
   int n = 0;
-  if (wg_fold[pb >> 5]) {
-    const int f = pt_first[pb], l = pt_first[pb + 1], w = pb >> 5, base = EMIT ? offset[pb] : 0;
-    auto rec = [&](int i) { const int r = i - f; return r < 8 ? ((pb & 31) << 3) + r : 256 + ovf_off[pb] + (r - 8); };
+  const int w = ptmap_wg_of(map, pb);
+  if (wg_fold[w]) {
+    const int f = pt_first[pb], l = pt_first[pb + 1], base = EMIT ? offset[pb] : 0;
+    const int rec0 = (pb - ptmap_wg_first(map, w)) * ptmap_lanes(map, w);   // (the lane of the point's first row)
+    auto rec = [&](int i) { return rec0 + (i - f); };
     for (int i = f; i < l; i++) {
       if (o_cpos[i] < 0) continue;
       for (int j = f; j < l; j++) {
@@ -2767,10 +2814,10 @@ __global__ __launch_bounds__(256) void k_fold_stream_entries(int E, const int* _
   const int sl = slot_of[e] + head[e] - 1;   // (slot_of: exclusive count of slot heads)
   stream[slot_ent_pos[sl] + (e - slot_ent_first[sl])] = ent[e];
 }
-__global__ __launch_bounds__(256) void k_fold_mark_cpos(int npb, const int* __restrict__ pt_first, const int* __restrict__ o_cpos, const int* __restrict__ wg_fold,
+__global__ __launch_bounds__(256) void k_fold_mark_cpos(int npb, PtMap map, const int* __restrict__ pt_first, const int* __restrict__ o_cpos, const int* __restrict__ wg_fold,
                                                          uint8_t* __restrict__ folded) {
   const int pb = blockIdx.x * 256 + threadIdx.x;
-  if (pb >= npb || !wg_fold[pb >> 5]) return;
+  if (pb >= npb || !wg_fold[ptmap_wg_of(map, pb)]) return;
   for (int i = pt_first[pb]; i < pt_first[pb + 1]; i++) if (o_cpos[i] >= 0) folded[o_cpos[i]] = 1;
 }
 __global__ __launch_bounds__(256) void k_fold_live_flags(int nch, const int* __restrict__ ch_start, const int* __restrict__ ch_end, const int* __restrict__ pa,
@@ -2831,15 +2878,15 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   if (ba->env.no_fold || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < ba->env.fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
   hipStream_t s = ctx->stream;
   DevBuf<char> tmp;
-  const int n_wg = cdiv(npb, 32);
+  const int n_wg = ptmap_n_wg(ba->map);
   F.n_wg = n_wg;
-  DTRY(F.wg_fold.alloc(n_wg)); DTRY(F.ovf_off.alloc(npb));
-  hipLaunchKernelGGL(k_fold_wg, dim3(cdiv(n_wg, 256)), dim3(256), 0, s, npb, n_wg, ba->pt_first.p, F.ovf_off.p, F.wg_fold.p);
+  DTRY(F.wg_fold.alloc(n_wg));
+  hipLaunchKernelGGL(k_fold_wg, dim3(cdiv(n_wg, 256)), dim3(256), 0, s, ba->map, n_wg, F.wg_fold.p);
   DevBuf<int> count, offset;
   DTRY(count.alloc((size_t)npb + 1)); DTRY(offset.alloc((size_t)npb + 1));
   DTRY(hipMemsetAsync(count.p, 0, sizeof(int) * ((size_t)npb + 1), s));
-  hipLaunchKernelGGL((k_fold_entries<false>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
-                     F.ovf_off.p, count.p, (const int*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr);
+  hipLaunchKernelGGL((k_fold_entries<false>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->map, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
+                     count.p, (const int*)nullptr, (unsigned long long*)nullptr, (unsigned*)nullptr);
   DTRY(excl_scan(count.p, offset.p, (size_t)npb + 1, s, tmp));
   int E = 0;
   DTRY(hipMemcpyAsync(&E, offset.p + npb, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -2850,8 +2897,8 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   DevBuf<int> head, slot_of, slot_id, slot_id_s;
   DevBuf<unsigned> ent_sorted;
   DTRY(key.alloc(E)); DTRY(key_s.alloc(E)); DTRY(val.alloc(E)); DTRY(ent_sorted.alloc(E));
-  hipLaunchKernelGGL((k_fold_entries<true>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
-                     F.ovf_off.p, (int*)nullptr, offset.p, key.p, val.p);
+  hipLaunchKernelGGL((k_fold_entries<true>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->map, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
+                     (int*)nullptr, offset.p, key.p, val.p);
   {
     size_t bytes = 0;
     const int bits = 32 + bits_for(std::max(2, n_wg));
@@ -2932,7 +2979,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   DevBuf<uint8_t> folded;
   DTRY(folded.alloc((size_t)std::max(1, ba->NCR)));
   DTRY(hipMemsetAsync(folded.p, 0, (size_t)std::max(1, ba->NCR), s));
-  hipLaunchKernelGGL(k_fold_mark_cpos, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ba->pt_first.p, ba->o_cpos.p, F.wg_fold.p, folded.p);
+  hipLaunchKernelGGL(k_fold_mark_cpos, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ba->map, ba->pt_first.p, ba->o_cpos.p, F.wg_fold.p, folded.p);
   hipLaunchKernelGGL(k_fold_mark_pairs, dim3(cdiv(ba->cc.n_pairs, 256)), dim3(256), 0, s, ba->cc.n_pairs, folded.p, ba->cc.pa.p);
   DTRY(F.partial.alloc((size_t)NS * 36));
   // chunks that keep a live entry: the gather kernel visits only those, the partials of the others are zero for good
@@ -3125,8 +3172,10 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     DTRY(ba->gps.from(gps_cb, s));
   }
   lap("camera order");
-  // ---- order of the eliminated points: by their smallest camera blocks, ties by the caller's index (stable sort) ----
-  DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len;
+  // ---- order of the eliminated points: by length class (PtMap), then by their smallest camera blocks, ties by the caller's
+  // index (two stable sorts, the minor key first) ----
+  DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len, d_cls, d_cls_sorted, d_n_class;
+  int n_class[3] = {0, 0, 0};
   DevBuf<unsigned long long> d_keys, d_keys_sorted;
   DTRY(d_pu_int.alloc((size_t)Np + 1)); DTRY(d_pu_pos.alloc((size_t)Np + 1));
   DTRY(hipMemsetAsync(d_pu_int.p + Np, 0, sizeof(int), s));
@@ -3141,7 +3190,12 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     DTRY(d_keys.alloc(npb)); DTRY(d_keys_sorted.alloc(npb)); DTRY(d_vals.alloc(npb));
     hipLaunchKernelGGL(k_point_keys, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_pos.p, d_run_first.p, d_obs_cam.p, d_cam_slot.p,
                        ncb >= 0xFFFF ? 1 : 0, d_keys.p, d_vals.p);
-    DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, ba->pb_pt.p, (size_t)npb, 64, s, tmp));
+    DTRY(d_vals_sorted.alloc(npb)); DTRY(d_cls.alloc(npb)); DTRY(d_cls_sorted.alloc(npb)); DTRY(d_n_class.alloc(3));
+    DTRY(hipMemsetAsync(d_n_class.p, 0, sizeof(int) * 3, s));
+    DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, d_vals_sorted.p, (size_t)npb, 64, s, tmp));
+    hipLaunchKernelGGL(k_point_classes, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, d_vals_sorted.p, d_cnt.p, d_cls.p, d_n_class.p);
+    DTRY(sort_pairs(d_cls.p, d_cls_sorted.p, d_vals_sorted.p, ba->pb_pt.p, (size_t)npb, 2, s, tmp));
+    DTRY(hipMemcpyAsync(n_class, d_n_class.p, sizeof n_class, hipMemcpyDeviceToHost, s));   // (read with AE below)
   }
   DTRY(d_pt_slot.alloc((size_t)std::max(1, Np))); DTRY(d_len.alloc((size_t)npb + 1)); DTRY(ba->pt_first.alloc((size_t)npb + 1));
   DTRY(hipMemsetAsync(d_len.p + npb, 0, sizeof(int), s));
@@ -3161,6 +3215,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   DTRY(hipMemcpyAsync(&AE, ba->pt_first.p + npb, sizeof(int), hipMemcpyDeviceToHost, s));
   DTRY(hipStreamSynchronize(s));
   ba->AE = AE;
+  ba->map = ptmap_make(n_class[0], n_class[1], n_class[2]);
   const int A = ba->A = AE + n_frozen_rows;
   ba->n_residuals = 2 * A + (ba->has_gps ? 3 * ncb : 0);
   lap("point order");
@@ -3370,8 +3425,15 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
         for (auto& x : th) x.join();
       }
     }
-    if (keyed.size() == ba->h_pb_pt.size())
-      for (size_t i = 0; i < keyed.size(); i++) ba->h_pb_pt[i] = keyed[i].second;
+    if (keyed.size() == ba->h_pb_pt.size()) {
+      // length class major (PtMap), the key order inside a class
+      int n_class[3] = {0, 0, 0};
+      auto cls = [&](int p) { return ptmap_class(run_first[p + 1] - run_first[p]); };
+      for (size_t i = 0; i < keyed.size(); i++) n_class[cls(keyed[i].second)]++;
+      size_t at[3] = {0, (size_t)n_class[0], (size_t)n_class[0] + n_class[1]};
+      for (size_t i = 0; i < keyed.size(); i++) ba->h_pb_pt[at[cls(keyed[i].second)]++] = keyed[i].second;
+      ba->map = ptmap_make(n_class[0], n_class[1], n_class[2]);
+    }
     for (size_t i = 0; i < ba->h_pb_pt.size(); i++) pt_slot[ba->h_pb_pt[i]] = ba->npb++;
     HIP_TRY(ctx, ba->cb_off.from(cb_off_h.empty() ? std::vector<int>(1, 0) : cb_off_h, s));
     HIP_TRY(ctx, ba->padcol.from(padcol_h.empty() ? std::vector<int>(1, 0) : padcol_h, s));
@@ -3718,7 +3780,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   AL(M, (size_t)ba->npad * ba->npad); AL(Linv, (size_t)ba->npad * 144); /* 16x16 inverses + full 64x64 block inverses + diagonal blocks of L */ AL(w, ba->npad); AL(z, ba->npad + 8); AL(zsys, 2 * ((size_t)ba->npad + 8));   /* two solution buffers that alternate from solve to solve (k_backsolve_chain) */
   AL(g_r, 3 * (size_t)ncb); AL(g_J, 3 * (size_t)ncb);
   ba->nblk_obs = cdiv(As, 256);
-  ba->nblk_pt = cdiv(std::max(1, npb), 32);  // 8 lanes per point
+  ba->nblk_pt = ptmap_n_wg(ba->map);
   const size_t npart = (size_t)ba->nblk_obs + ba->nblk_pt + cdiv(std::max(1, ncb), 256) + 64;
   AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart);
   AL(gmax_buf, (size_t)ba->nblk_pt + 6 * (size_t)ncb + 3 * (size_t)nmb + 8);
@@ -3809,6 +3871,7 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
     if (ba->fold.mc_on) { out->mc_entries_folded = ba->fold.mc_entries_folded; out->fold_mc_slots = ba->fold.n_diag; }
   }
   out->solve_paths = ba->solve_paths;
+  out->npb_S = ba->map.nS; out->npb_L = ba->map.nL; out->npb_X = ba->map.nX;
   return MSFM_OK;
 }
 
@@ -3905,7 +3968,7 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   KTimer t(ctx, "ba_point");
   PointPtrs Q;
   Q.B = make_ptrs(ba, candidate, ba->lin_huber);
-  Q.npb = ba->npb; Q.NCR = std::max(1, ba->NCR); Q.pt_first = ba->pt_first.p;
+  Q.map = ba->map; Q.npb = ba->npb; Q.NCR = std::max(1, ba->NCR); Q.pt_first = ba->pt_first.p;
   Q.pm_first = ba->pm_first.p; Q.pm_mb = ba->pm_mb.p;
   Q.diag_p = ba->diag_p.p; Q.ptL = ba->ptL.p; Q.ptg = ba->ptg.p;
   Q.T = ba->T.p; Q.Tu = ba->Tu.p; Q.Tm = ba->Tm.p; Q.Tmu = ba->Tmu.p;
@@ -3913,7 +3976,7 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   Q.reuse_diag = reuse_diag; Q.mode = mode; Q.fail = ba->fail.p;
   Q.store_rows = store_rows ? 1 : 0; Q.cost_partial = ba->partial.p;
   const FoldTables& F = ba->fold;
-  Q.fold_wg = F.on ? F.wg_fold.p : nullptr; Q.fold_ovf_off = F.ovf_off.p; Q.fold_wg_pass_first = F.wg_pass_first.p; Q.fold_slot_rank = F.slot_rank.p;
+  Q.fold_wg = F.on ? F.wg_fold.p : nullptr; Q.fold_wg_pass_first = F.wg_pass_first.p; Q.fold_slot_rank = F.slot_rank.p;
   Q.fold_pass = F.pass.p; Q.fold_stream = F.stream.p; Q.fold_partial = F.partial.p;
   Q.fold_mc_partial = (F.on && F.mc_on) ? F.mc_partial.p : nullptr;
   Q.spec = spec;
@@ -4219,7 +4282,7 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     if (npb) {
       BackPtrs Q;
       Q.B = make_ptrs(ba, false, ba->lin_huber);
-      Q.npb = npb; Q.ncb = ncb; Q.pt_first = ba->pt_first.p; Q.pb_pt = ba->pb_pt.p;
+      Q.map = ba->map; Q.npb = npb; Q.ncb = ncb; Q.pt_first = ba->pt_first.p; Q.pb_pt = ba->pb_pt.p;
       Q.ptL = ba->ptL.p; Q.z = ba->z.p; Q.pt_c = ba->pt_c.p; Q.cm_Xc = ba->cm_Xc.p;
       Q.Nc = ba->Nc; Q.cam_c = ba->cam_c.p; Q.rot_c = ba->rot_c.p;
       hipLaunchKernelGGL(k_backsub, dim3(nbp), dim3(256), 0, s, Q, ba->partial.p, ba->partial2.p + off, ba->partial3.p + off);
