@@ -1,6 +1,7 @@
 // See objectsfm.h.  Host-side glue only: gather -> C ABI -> scatter.
 #include "objectsfm.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <fstream>
 #include <iomanip>
@@ -428,6 +429,151 @@ void IncrementalSfM::RemovePointOutliers() {
     if (std::sqrt(p->mse_) > options_.th_mse_outliers) p->is_bad_estimated_ = true;
     p->is_new_added_ = false;
   }
+}
+
+// ---- IncrementalSfM: which image to localise next -------------------------------------------------
+void IncrementalSfM::SetMatches(const std::vector<int>& n_features, const std::vector<int>& pair_img, const std::vector<int>& match_off,
+                                const std::vector<int>& matches) {
+  const int n = (int)n_features.size(), np = (int)pair_img.size() / 2;
+  if ((int)match_off.size() != np + 1 || (np && (int)matches.size() < 2 * match_off[np])) throw std::runtime_error("SetMatches: sizes");
+  msfm_match_store* st = nullptr;
+  check(msfm_match_store_create(Context(), n, n_features.data(), np, pair_img.data(), match_off.data(), matches.data(), &st),
+        "msfm_match_store_create");   // (checks the pair order and every index)
+  store_.reset(st, msfm_match_store_destroy);
+  graph_.n_features = n_features; graph_.pair_img = pair_img; graph_.match_off = match_off; graph_.matches = matches;
+  graph_.match_graph_.assign((size_t)n * n, 0);
+  for (int p = 0; p < np; p++) graph_.match_graph_[(size_t)pair_img[2 * p] * n + pair_img[2 * p + 1]] = match_off[p + 1] - match_off[p];
+  if (is_img_processed_.empty()) is_img_processed_.assign(n, false);
+  if (localize_fail_times_.empty()) localize_fail_times_.assign(n, 0);
+}
+
+// sfm_incremental.cc:423-438
+static std::vector<int> candidate_images(const IncrementalSfM& s) {
+  const int num_imgs = (int)s.graph_.n_features.size();
+  std::vector<int> image_ids;
+  for (size_t i = 0; i < s.cams_.size(); ++i) {
+    const int id_img = s.cams_[i]->id_img_;
+    for (int j = 0; j < num_imgs; ++j)
+      if (s.graph_.match_graph_[(size_t)id_img * num_imgs + j] > 0 && !s.is_img_processed_[j] &&
+          s.localize_fail_times_[j] < s.options_.th_max_failure_localization)
+        image_ids.push_back(j);
+  }
+  std::sort(image_ids.begin(), image_ids.end());   // math::unique_vector
+  image_ids.erase(std::unique(image_ids.begin(), image_ids.end()), image_ids.end());
+  return image_ids;
+}
+
+void IncrementalSfM::FindImageToLocalize(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
+                                         std::vector<std::vector<int>>& visible_cams) {
+  image_ids.clear(); corres_2d3d.clear(); visible_cams.clear();
+  if (!store_) throw std::runtime_error("FindImageToLocalize: SetMatches first");
+  const std::vector<int> cand = candidate_images(*this);
+  if (cand.empty()) return;
+  // the flat state: camera -> image, (camera, local feature) -> point, and what the search reads of a point
+  std::vector<int> cam_img(cams_.size()), feat_point, fail(cand.size());
+  for (size_t c = 0; c < cams_.size(); c++) {
+    const int img = cams_[c]->id_img_, nf = graph_.n_features[img];
+    cam_img[c] = img;
+    const size_t at = feat_point.size();
+    feat_point.resize(at + nf, -1);
+    for (auto& kv : cams_[c]->pts_) {
+      const long local = (long)kv.first - (long)options_.idx_max_per_image * img;
+      if (local < 0 || local >= nf) continue;   // (no match of this image can name it)
+      const int id = kv.second->id_;
+      if (id < 0 || id >= (int)pts_.size() || pts_[id] != kv.second) throw std::runtime_error("FindImageToLocalize: pts_[i]->id_ != i");
+      feat_point[at + local] = id;
+    }
+  }
+  std::vector<uint8_t> pt_bad(pts_.size());
+  std::vector<double> pt_mse(pts_.size());
+  std::vector<int> pt_views(pts_.size());
+  for (size_t i = 0; i < pts_.size(); i++) {
+    pt_bad[i] = pts_[i]->is_bad_estimated_; pt_mse[i] = pts_[i]->mse_; pt_views[i] = (int)pts_[i]->cams_.size();
+  }
+  for (size_t k = 0; k < cand.size(); k++) fail[k] = localize_fail_times_[cand[k]];
+  msfm_localize_problem P{};
+  P.n_cams = (int)cams_.size(); P.cam_img = cam_img.data(); P.feat_point = feat_point.data();
+  P.n_points = (int)pts_.size(); P.pt_bad = pt_bad.data(); P.pt_mse = pt_mse.data(); P.pt_views = pt_views.data();
+  P.n_cand = (int)cand.size(); P.cand_img = cand.data(); P.fail_times = fail.data();
+  msfm_localize_set* set = nullptr;
+  check(msfm_localize_candidates(Context(), store_.get(), &P, &set), "msfm_localize_candidates");
+  int n_kept = 0, n_corr = 0, n_vis = 0;
+  msfm_localize_set_size(set, &n_kept, &n_corr, &n_vis, nullptr, nullptr);
+  std::vector<int> rank(n_kept), coff(n_kept + 1), cf(n_corr), cp(n_corr), voff(n_kept + 1), vc(n_vis);
+  msfm_localize_set_fetch(set, rank.data(), coff.data(), cf.data(), cp.data(), voff.data(), vc.data(), nullptr, nullptr);
+  msfm_localize_set_destroy(set);
+  corres_2d3d.resize(n_kept); visible_cams.resize(n_kept);
+  for (int r = 0; r < n_kept; r++) {
+    image_ids.push_back(cand[rank[r]]);
+    for (int e = coff[r]; e < coff[r + 1]; e++) corres_2d3d[r].push_back(std::make_pair(cf[e], cp[e]));
+    visible_cams[r].assign(vc.begin() + voff[r], vc.begin() + voff[r + 1]);
+  }
+}
+
+void IncrementalSfM::FindImageToLocalizeHost(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
+                                             std::vector<std::vector<int>>& visible_cams) const {
+  const int num_imgs = (int)graph_.n_features.size();
+  image_ids = candidate_images(*this);
+  corres_2d3d.clear(); visible_cams.clear();
+  if (image_ids.empty()) return;
+  // "QueryMatch(i, j)" on the lists in memory: pair index of (i, j)
+  std::map<std::pair<int, int>, int> pair_at;
+  for (int p = 0; p < (int)graph_.pair_img.size() / 2; p++) pair_at[std::make_pair(graph_.pair_img[2 * p], graph_.pair_img[2 * p + 1])] = p;
+  corres_2d3d.resize(image_ids.size());
+  visible_cams.resize(image_ids.size());
+  for (size_t i = 0; i < image_ids.size(); i++) {
+    const int id_img_i = image_ids[i];
+    std::vector<int> visible_cams_i;
+    std::map<int, int> corres_2d3d_i;        // first, idx of 2d keypoints; second, idx of 3d points
+    std::map<int, double> corres_2d3d_info_i;
+    for (int id_img_j = 0; id_img_j < num_imgs; ++id_img_j) {
+      if (!(graph_.match_graph_[(size_t)id_img_i * num_imgs + id_img_j] > 0 && is_img_processed_[id_img_j])) continue;   // :457
+      auto iter_i_c = img_cam_map_.find(id_img_j);
+      if (iter_i_c == img_cam_map_.end()) continue;
+      const int idx_cam = iter_i_c->second;
+      auto pit = pair_at.find(std::make_pair(id_img_i, id_img_j));
+      if (pit == pair_at.end()) continue;
+      int count_2d3d_ij = 0;
+      for (int m = graph_.match_off[pit->second]; m < graph_.match_off[pit->second + 1]; m++) {   // :480
+        const int idx_i_local = graph_.matches[2 * (size_t)m], idx_j_local = graph_.matches[2 * (size_t)m + 1];
+        const int idx_j_global = idx_j_local + options_.idx_max_per_image * id_img_j;
+        auto iter_cam_3dpt = cams_[idx_cam]->pts_.find(idx_j_global);
+        if (iter_cam_3dpt != cams_[idx_cam]->pts_.end() && !iter_cam_3dpt->second->is_bad_estimated_) {   // :486-487
+          corres_2d3d_i.insert(std::pair<int, int>(idx_i_local, iter_cam_3dpt->second->id_));
+          double mse_3dpt = iter_cam_3dpt->second->mse_;
+          if (iter_cam_3dpt->second->cams_.size() <= 2) mse_3dpt += 3.0;
+          corres_2d3d_info_i.insert(std::pair<int, double>(idx_i_local, mse_3dpt));
+          count_2d3d_ij++;
+        }
+      }
+      if (count_2d3d_ij > options_.th_visible_matches) visible_cams_i.push_back(idx_cam);   // :503
+    }
+    if (corres_2d3d_i.empty()) continue;
+    std::vector<std::pair<int, double>> sorted_i(corres_2d3d_info_i.begin(), corres_2d3d_info_i.end());
+    std::sort(sorted_i.begin(), sorted_i.end(), [](const std::pair<int, double>& l, const std::pair<int, double>& r) {   // :524 + the ties
+      const bool ln = std::isnan(l.second), rn = std::isnan(r.second);
+      if (ln != rn) return rn;
+      if (!ln && l.second != r.second) return l.second < r.second;
+      return l.first < r.first;
+    });
+    for (auto& e : sorted_i) corres_2d3d[i].push_back(std::pair<int, int>(e.first, corres_2d3d_i[e.first]));
+    visible_cams[i] = visible_cams_i;
+  }
+  // :537-562
+  std::vector<std::pair<int, int>> idx_num(image_ids.size());
+  for (size_t i = 0; i < image_ids.size(); i++)
+    idx_num[i] = std::make_pair((int)i, (int)(corres_2d3d[i].size() / (5 + localize_fail_times_[image_ids[i]])));
+  std::stable_sort(idx_num.begin(), idx_num.end(), [](const std::pair<int, int>& l, const std::pair<int, int>& r) { return l.second > r.second; });
+  std::vector<int> ids_sort;
+  std::vector<std::vector<std::pair<int, int>>> corres_sort;
+  std::vector<std::vector<int>> visible_sort;
+  for (auto& e : idx_num) {
+    if (e.second <= 0) continue;
+    ids_sort.push_back(image_ids[e.first]);
+    corres_sort.push_back(corres_2d3d[e.first]);
+    visible_sort.push_back(visible_cams[e.first]);
+  }
+  image_ids = ids_sort; corres_2d3d = corres_sort; visible_cams = visible_sort;
 }
 
 void SLAMGPS::FullBundleAdjustment() {

@@ -11,6 +11,7 @@
 #include <array>
 #include <cmath>
 #include <map>
+#include <memory>
 #include <random>
 #include <string>
 #include <utility>
@@ -157,6 +158,15 @@ struct IncrementalSfMOptions {       // basic_structs.h:147-227, the fields this
   double th_mse_outliers = 3.0;      // test_sfm.cc:46 (UAV), 1.0 for WEB (:57)
   int th_visible_matches = 5;        // `count_2d3d_ij > 5`, sfm_incremental.cc:503
   bool use_same_camera = false;      // basic_structs.h:167
+  int idx_max_per_image = 1000000;   // basic_structs.h:171: global feature id = local + idx_max_per_image * image
+  int th_max_failure_localization = 5;   // basic_structs.h:176
+};
+// What FindImageToLocalize reads of Graph (SfM/src/graph/graph.h): match_graph_ and the verified match lists - here in memory
+// in the flat layout of msfm_match_store_create instead of behind Graph::QueryMatch's `<i>_match` files (graph.cc:92-137).
+struct MatchGraph {
+  std::vector<int> match_graph_;                 // [num_imgs * num_imgs] matches of the ordered pair (i, j)
+  std::vector<int> n_features;                   // [num_imgs]
+  std::vector<int> pair_img, match_off, matches; // pairs strictly ascending in (idx1, idx2)
 };
 class IncrementalSfM {
  public:
@@ -169,6 +179,24 @@ class IncrementalSfM {
   void PartialBundleAdjustment(int idx);                                 // sfm_incremental.cc:917-1014
   void FullBundleAdjustment();                                           // sfm_incremental.cc:1016-1026
   void RemovePointOutliers();                                            // sfm_incremental.cc:1831-1863 (one batched reprojection)
+  // The verified matches of the image set (pair_img [P][2] strictly ascending, match_off [P+1], matches [M][2]): fills graph_
+  // and uploads them once into a msfm_match_store; sizes is_img_processed_ / localize_fail_times_ when they are empty.
+  void SetMatches(const std::vector<int>& n_features, const std::vector<int>& pair_img, const std::vector<int>& match_off,
+                  const std::vector<int>& matches);
+  // sfm_incremental.cc:417-563: the candidate images (:423-438) on the host, then one msfm_localize_candidates call on the
+  // flat state gathered from cams_ / pts_ (pts_[i]->id_ == i, as LocalizeImage :599 indexes them).  Ties the reference's
+  // std::sort leaves open go to the lower feature / the lower image id.
+  void FindImageToLocalize(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
+                           std::vector<std::vector<int>>& visible_cams);
+  // The same function as the reference writes it - std::map walks on one thread - over the matches in memory (same ties):
+  // what scripts/localize_bench.py times the library call against, and a second opinion for tests/localize_host_check.cc.
+  void FindImageToLocalizeHost(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
+                               std::vector<std::vector<int>>& visible_cams) const;
+  MatchGraph graph_;
+  std::vector<bool> is_img_processed_;
+  std::vector<int> localize_fail_times_;
+  std::map<int, int> img_cam_map_;           // image id -> index in cams_
+  std::shared_ptr<msfm_match_store> store_;  // the resident copy of graph_'s matches
   std::vector<Camera*> cams_;
   std::vector<CameraModel*> cam_models_;
   std::vector<Point3D*> pts_;

@@ -542,6 +542,74 @@ int msfm_chain_fetch_point_tracks(msfm_chain* chain, int* track_of_point /*[n_po
 void msfm_chain_destroy(msfm_chain* chain);
 
 /* ======================================================================================
+ *  Which image to localise next: the batched 2D-3D correspondence search
+ * ====================================================================================== */
+/* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference
+ * re-reads and parses `<i>_match` in Graph::QueryMatch, SfM/src/graph/graph.cc:92-137, per candidate x registered image).
+ * pair_img[p] = (idx1, idx2) as WriteOutMatches(idx1, idx2, ...) stores it (fine_matching_graph.cc:184), matches[m] =
+ * (feature in idx1, feature in idx2): the layout of msfm_tracks_build.  A feature of idx1 may occur in several matches of a
+ * pair (ptr_id[0] is not unique over the queries, graph.cc:116-129): kept.  Pairs must be strictly ascending in
+ * (idx1, idx2) - the reference's visiting order - and every feature index inside its image (checked on the device), else
+ * MSFM_E_INVAL.  The store keeps a row index by idx1: QueryMatch(i, j) is "row i, entry j".
+ * msfm_match_store_from_chain copies the matches of a verified chain (and the keypoints it holds) device to device; the
+ * chain may be destroyed afterwards.  A store counts as a child of its context. */
+typedef struct msfm_match_store msfm_match_store;
+int msfm_match_store_create(msfm_ctx* ctx, int n_images, const int* n_features, int n_pairs,
+                            const int* pair_img /*[n_pairs][2]*/, const int* match_off /*[n_pairs+1]*/,
+                            const int* matches /*[match_off[n_pairs]][2]*/, msfm_match_store** out);
+int msfm_match_store_from_chain(msfm_chain* chain, msfm_match_store** out);
+void msfm_match_store_destroy(msfm_match_store* store);
+
+/* The search of IncrementalSfM::FindImageToLocalize (SfM/src/sfm_incremental.cc:440-562) for a whole candidate list.
+ * (Which images are candidates, :423-438, is a loop over the match graph: metricsfm_amd/localize.py::candidate_images.)
+ * Per candidate image i, registered images j in ascending image id that have a store pair (i, j) with matches (:452-474),
+ * that pair's matches in stored order (:480):
+ *   - (f_i, f_j) qualifies when p = feat_point[cam(j)][f_j] >= 0 and !pt_bad[p] (:486-487);
+ *   - it inserts f_i -> p and f_i -> pt_mse[p] + (pt_views[p] <= 2 ? 3.0 : 0.0) with std::map::insert semantics: the first
+ *     qualifying match that names f_i wins, over all j (:489-496);
+ *   - count_2d3d_ij counts every qualifying match, also those whose insert did not take (:497); cam(j) is visible when
+ *     the count is > 5 (:503), visible cameras in the order of the walk;
+ *   - correspondences ordered by that mse ascending (:517-531); std::sort leaves ties open - here they go to the lower
+ *     f_i, NaN last (-0.0 = +0.0);
+ *   - score = n_corr / (5 + fail_times), integer division (:543); candidates by score descending, ties to the lower
+ *     image id; score 0 dropped (:552).
+ * In : n_cams, cam_img[n_cams] (img_cam_map_ inverted; is_img_processed_ is true exactly for these);
+ *      feat_point: for camera c, local feature f -> point id held by cams_[c]->pts_ or -1, cameras in order, camera c
+ *      starting at the sum of n_features[cam_img[c']] over c' < c;  n_points, pt_bad (is_bad_estimated_), pt_mse (mse_),
+ *      pt_views (cams_.size());  n_cand, cand_img (strictly ascending, none registered), fail_times (>= 0).
+ *      Optional: point_xyz [n_points][3] asks for pts_w / pts_2d; the keypoints then come from the store (made from a
+ *      chain) or from `keypoints`, float [sum of n_features][2] in image order (only the kept candidates' rows are read).
+ * Out: a msfm_localize_set.  rank[n_kept] = indices into cand_img in output order; row r of the CSR arrays belongs to
+ *      candidate rank[r]: corr_off[n_kept+1], corr_feat / corr_point [n_corr] in sorted order; vis_off[n_kept+1], vis_cam
+ *      [n_visible] (camera indices).  With point_xyz: pts_w [n_corr][3], pts_2d [n_corr][2] (keypoints float -> double,
+ *      :592-600) - with offsets = corr_off exactly what msfm_epnp_ransac_batch / msfm_epnpf_sweep_batch take.
+ *      A candidate's rows do not depend on which other candidates are in the call.
+ * feat_point >= n_points is MSFM_E_INVAL (checked on the device before anything is indexed by it).  Per call the host
+ * sends feat_point, the point arrays and four integers per walked pair; h2d_bytes of msfm_localize_set_size reports it. */
+typedef struct msfm_localize_problem {
+  int32_t n_cams;
+  const int32_t* cam_img;
+  const int32_t* feat_point;
+  int32_t n_points;
+  const uint8_t* pt_bad;
+  const double* pt_mse;
+  const int32_t* pt_views;
+  int32_t n_cand;
+  const int32_t* cand_img;
+  const int32_t* fail_times;
+  const double* point_xyz;   /* optional */
+  const float* keypoints;    /* optional */
+} msfm_localize_problem;
+typedef struct msfm_localize_set msfm_localize_set;
+int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* store, const msfm_localize_problem* problem,
+                             msfm_localize_set** out);
+int msfm_localize_set_size(const msfm_localize_set* set, int* n_kept, int* n_corr, int* n_visible, int* has_points,
+                           int64_t* h2d_bytes);
+int msfm_localize_set_fetch(const msfm_localize_set* set, int* rank, int* corr_off, int* corr_feat, int* corr_point,
+                            int* vis_off, int* vis_cam, double* pts_w, double* pts_2d);
+void msfm_localize_set_destroy(msfm_localize_set* set);
+
+/* ======================================================================================
  *  Pose initialisers ahead of each bundle adjustment  
  * ====================================================================================== */
 /* AbsolutePoseEstimation::AbsolutePoseWithFocalLength (SfM/src/orientation/absolute_pose_estimation.cc:42-58, called

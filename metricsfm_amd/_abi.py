@@ -105,6 +105,13 @@ class Tracks(C.Structure):
                 ("cam_fk", c_double_p)]
 
 
+class LocalizeProblem(C.Structure):
+    """msfm_localize_problem (include/msfm.h)."""
+    _fields_ = [("n_cams", C.c_int32), ("cam_img", c_int_p), ("feat_point", c_int_p), ("n_points", C.c_int32), ("pt_bad", c_u8_p),
+                ("pt_mse", c_double_p), ("pt_views", c_int_p), ("n_cand", C.c_int32), ("cand_img", c_int_p), ("fail_times", c_int_p),
+                ("point_xyz", c_double_p), ("keypoints", c_float_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

@@ -23,6 +23,8 @@ SYMBOLS = [
     "msfm_chain_create", "msfm_chain_verify", "msfm_chain_matches", "msfm_chain_fetch_matches", "msfm_chain_build_tracks",
     "msfm_chain_fetch_tracks", "msfm_chain_triangulate", "msfm_chain_fetch_points", "msfm_chain_ba_create", "msfm_chain_fetch_point_tracks",
     "msfm_chain_destroy",
+    "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
+    "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
@@ -143,6 +145,15 @@ def lib():
     L.msfm_chain_fetch_point_tracks.argtypes = [vp, A.c_int_p]
     L.msfm_chain_destroy.argtypes = [vp]
     L.msfm_chain_destroy.restype = None
+    L.msfm_match_store_create.argtypes = [vp, i, A.c_int_p, i, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(vp)]
+    L.msfm_match_store_from_chain.argtypes = [vp, C.POINTER(vp)]
+    L.msfm_match_store_destroy.argtypes = [vp]
+    L.msfm_match_store_destroy.restype = None
+    L.msfm_localize_candidates.argtypes = [vp, vp, C.POINTER(A.LocalizeProblem), C.POINTER(vp)]
+    L.msfm_localize_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
+    L.msfm_localize_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
+    L.msfm_localize_set_destroy.argtypes = [vp]
+    L.msfm_localize_set_destroy.restype = None
     L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
     L.msfm_multi_destroy.argtypes = [vp]
     L.msfm_multi_destroy.restype = None
@@ -392,6 +403,53 @@ class Context:
         self.check(lib().msfm_tracks_build_device(self._h, len(nf), A.ptr(nf, A.c_int_p), len(pr), A.ptr(pr, A.c_int_p),
                                                   A.ptr(off, A.c_int_p), A.ptr(fl, A.c_int_p), C.byref(h)))
         return _fetch_track_set(h)
+
+    def match_store(self, n_features, pairs, match_off, matches):
+        """msfm_match_store_create: the verified matches resident on the device (pairs [P][2] strictly ascending in (idx1, idx2),
+        match_off [P+1], matches [M][2]: the flat layout of `build_tracks`)."""
+        return MatchStore(self, n_features, pairs, match_off, matches)
+
+    def localize_candidates(self, store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=None, keypoints=None):
+        """msfm_localize_candidates (sfm_incremental.cc:440-562): the 2D-3D correspondences and visible cameras of every candidate
+        image, ranked.  Returns a dict: rank [n_kept] (indices into cand_img), corr_off, corr_feat, corr_point, vis_off, vis_cam,
+        h2d_bytes and, with point_xyz, pts_w [n_corr][3] / pts_2d [n_corr][2] (offsets = corr_off for `epnp_ransac`).
+        keypoints: flat float [sum of n_features][2] for a store that was not made from a chain."""
+        cam_img, feat_point, pt_views, cand_img, fail_times = (A.as_c(np.asarray(x, dtype=np.int32), np.int32)
+                                                               for x in (cam_img, feat_point, pt_views, cand_img, fail_times))
+        pt_bad = A.as_c(np.asarray(pt_bad, dtype=np.uint8), np.uint8)
+        pt_mse = A.as_c(np.asarray(pt_mse, dtype=np.float64), np.float64)
+        if not (len(pt_bad) == len(pt_mse) == len(pt_views)) or len(cand_img) != len(fail_times):
+            raise ValueError("pt_bad / pt_mse / pt_views and cand_img / fail_times must have equal lengths")
+        in_store = (cam_img >= 0) & (cam_img < len(store.n_features))     # (an image outside the store: the library reports it)
+        if in_store.all() and len(feat_point) != int(store.n_features[cam_img].sum()):
+            raise ValueError("feat_point must hold one entry per feature of every registered image")
+        xyz = None if point_xyz is None else A.as_c(np.asarray(point_xyz, dtype=np.float64).reshape(-1, 3), np.float64)
+        if xyz is not None and len(xyz) != len(pt_bad):
+            raise ValueError("point_xyz must hold one row per point")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        P = A.LocalizeProblem(len(cam_img), A.ptr(cam_img, A.c_int_p), A.ptr(feat_point, A.c_int_p), len(pt_bad), A.ptr(pt_bad, A.c_u8_p),
+                              A.ptr(pt_mse, A.c_double_p), A.ptr(pt_views, A.c_int_p), len(cand_img), A.ptr(cand_img, A.c_int_p),
+                              A.ptr(fail_times, A.c_int_p), A.ptr(xyz, A.c_double_p), A.ptr(kp, A.c_float_p))
+        h = C.c_void_p()
+        self.check(lib().msfm_localize_candidates(self._h, store._h, C.byref(P), C.byref(h)))
+        try:
+            nk, nc, nv, hp, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+            lib().msfm_localize_set_size(h, C.byref(nk), C.byref(nc), C.byref(nv), C.byref(hp), C.byref(nb))
+            nk, nc, nv = nk.value, nc.value, nv.value
+            rank, coff, voff = np.zeros(max(1, nk), np.int32), np.zeros(nk + 1, np.int32), np.zeros(nk + 1, np.int32)
+            cf, cp, vc = np.zeros(max(1, nc), np.int32), np.zeros(max(1, nc), np.int32), np.zeros(max(1, nv), np.int32)
+            pw = np.zeros((max(1, nc), 3)) if hp.value else None
+            p2 = np.zeros((max(1, nc), 2)) if hp.value else None
+            lib().msfm_localize_set_fetch(h, A.ptr(rank, A.c_int_p), A.ptr(coff, A.c_int_p), A.ptr(cf, A.c_int_p), A.ptr(cp, A.c_int_p),
+                                          A.ptr(voff, A.c_int_p), A.ptr(vc, A.c_int_p), A.ptr(pw, A.c_double_p), A.ptr(p2, A.c_double_p))
+        finally:
+            lib().msfm_localize_set_destroy(h)
+        out = dict(rank=rank[:nk], corr_off=coff, corr_feat=cf[:nc], corr_point=cp[:nc], vis_off=voff, vis_cam=vc[:nv], h2d_bytes=nb.value)
+        if hp.value:
+            out["pts_w"], out["pts_2d"] = pw[:nc], p2[:nc]
+        return out
 
     def triangulate_midpoint(self, tracks, th_error, th_angle, X0=None):
         return self._tri(lib().msfm_triangulate_midpoint_batch, tracks, th_error, th_angle, X0)
@@ -736,6 +794,42 @@ class Chain:
     def close(self):
         if self._h:
             lib().msfm_chain_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MatchStore:
+    """msfm_match_store: the verified matches of an image set resident on the device, indexed by idx1 (include/msfm.h)."""
+
+    def __init__(self, ctx: Context, n_features, pairs, match_off, matches):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        nf, off = (A.as_c(np.asarray(x, dtype=np.int32), np.int32) for x in (n_features, match_off))
+        pr = A.as_c(np.asarray(pairs, dtype=np.int32).reshape(-1, 2), np.int32)
+        fl = A.as_c(np.asarray(matches, dtype=np.int32).reshape(-1, 2), np.int32)
+        if len(off) != len(pr) + 1 or (len(pr) and len(fl) < off[-1]):
+            raise ValueError("match_off must have one entry more than pairs and end inside matches")
+        self.n_features = nf
+        ctx.check(lib().msfm_match_store_create(ctx._h, len(nf), A.ptr(nf, A.c_int_p), len(pr), A.ptr(pr, A.c_int_p), A.ptr(off, A.c_int_p),
+                                                A.ptr(fl, A.c_int_p), C.byref(self._h)))
+
+    @classmethod
+    def from_chain(cls, chain):
+        """msfm_match_store_from_chain: the matches (and keypoints) of a verified Chain, copied device to device."""
+        self = cls.__new__(cls)
+        self.ctx, self._h = chain.ctx, C.c_void_p()
+        self.n_features = np.asarray(chain.res.ds.counts, dtype=np.int32)
+        self.ctx.check(lib().msfm_match_store_from_chain(chain._h, C.byref(self._h)))
+        return self
+
+    def close(self):
+        if self._h:
+            lib().msfm_match_store_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

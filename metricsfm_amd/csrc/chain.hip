@@ -312,6 +312,12 @@ MSFM_API int msfm_chain_matches(msfm_chain* C, int* n_matches, uint8_t* ok, doub
   return MSFM_OK;
 }
 
+int chain_match_view(msfm_chain* C, ChainMatchView* out) {
+  if (!C->verified) return msfm_set_error(C->ctx, MSFM_E_INVAL, "msfm_match_store_from_chain: msfm_chain_verify first");
+  *out = ChainMatchView{C->ctx, C->n_images, C->n_pairs, C->pairs.data(), C->count.data(), C->off_fin.data(), C->d_match.p, C->kp_own.p, C->kp};
+  return MSFM_OK;
+}
+
 MSFM_API int msfm_chain_fetch_matches(msfm_chain* C, int pair, int* matches) {
   if (!C || pair < 0 || pair >= C->n_pairs) return MSFM_E_INVAL;
   msfm_ctx* ctx = C->ctx;

@@ -44,6 +44,7 @@ struct msfm_env {
   int device_share = 1;           // MSFM_DEVICE_SHARE: processes that use this device at the same time
   bool verbose = false;           // MSFM_VERBOSE (set): set-up and solve timings to stderr
   int multi_fail_rank = -1;       // MSFM_MULTI_FAIL_RANK (test hook): this rank of msfm_multi_ba_solve fails before it joins
+  int localize_lds_max = 4096;    // MSFM_LOCALIZE_LDS_MAX: longest segment msfm_localize_candidates sorts in LDS (0: all through rocPRIM); read per call
 };
 msfm_env msfm_env_read();              // the environment as it is now
 const msfm_env& msfm_env_process();    // its first reading, kept for the life of the process
@@ -231,6 +232,18 @@ struct MatchView {
   bool slam;
 };
 int match_result_view(msfm_match_result* R, MatchView* out);   // MSFM_E_INVAL when the result is stale or orphaned
+// What localize.hip needs of a verified chain (chain.hip) to make a match store of its own
+struct ChainMatchView {
+  msfm_ctx* ctx;
+  int n_images, n_pairs;
+  const int* pairs;              // host [n_pairs][2]
+  const int* count;              // host [n_images]: features per image
+  const int* match_off;          // host [n_pairs + 1]
+  const int* d_match;            // device [match_off[n_pairs]][2]
+  const float* d_kp;             // device [sum of count][2], images in order
+  std::vector<const float*> kp;  // per image, nullptr: no keypoints
+};
+int chain_match_view(msfm_chain* C, ChainMatchView* out);   // MSFM_E_INVAL before msfm_chain_verify
 
 struct TrackPtrs {   // tri.hip: CSR tracks + cameras as the reference keeps them, device pointers
   int n_tracks;

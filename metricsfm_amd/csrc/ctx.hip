@@ -34,6 +34,7 @@ msfm_env msfm_env_read() {
   E.device_share = std::max(1, num("MSFM_DEVICE_SHARE", 1));
   E.verbose = get("MSFM_VERBOSE") != nullptr;
   E.multi_fail_rank = num("MSFM_MULTI_FAIL_RANK", -1);
+  E.localize_lds_max = num("MSFM_LOCALIZE_LDS_MAX", E.localize_lds_max);
   return E;
 }
 
