@@ -216,43 +216,80 @@ class SparseLM:
         pose[self.cu] += delta[:a].reshape(-1, 6); model[self.mu] += delta[a:b].reshape(-1, 3); point[self.pu] += delta[b:].reshape(-1, 3)
         return pose, model, point
 
-    def run(self, iters, radius=1e4, min_relative_decrease=1e-3):
-        """TrustRegionMinimizer (Ceres 1.13) with LevenbergMarquardtStrategy, monotonic steps; returns the parameters and
-        one record per iteration: cost after it, accepted?, |gradient|_max, |step|."""
+    def run(self, iters, radius=1e4, min_relative_decrease=1e-3, jacobi_scaling=True, min_lm_diagonal=1e-6, max_lm_diagonal=1e32,
+            max_radius=1e16, min_radius=1e-32, max_invalid=5, function_tolerance=-1.0, gradient_tolerance=-1.0,
+            parameter_tolerance=-1.0):
+        """TrustRegionMinimizer (Ceres 1.13) with LevenbergMarquardtStrategy, monotonic steps.  Returns the parameters, one
+        record per recorded iteration (cost after it, ok = accepted?, valid?, |gradient|_max, |step|, rho, cost change, the
+        radius the NEXT step will use) and the name of the termination.  Order of one iteration, as in Ceres:
+          record the row -> iteration cap -> gradient test -> minimum-radius test -> solve
+          -> invalid step (model cost change <= 0 or a non-finite step): the max_invalid-th in a row ends the run with FAILURE
+             and is not recorded, else radius / 2, 4, ... with the LM diagonal kept
+          -> parameter test |step| <= tol (|x| + tol) and function test |cost change| <= tol cost: both end the run unrecorded
+          -> rho > min_relative_decrease accepts: radius = min(max_radius, radius / max(1/3, 1 - (2 rho - 1)^3)), else the
+             rejection divides the radius by 2, 4, ... and keeps the LM diagonal.
+        The tolerances are off by default (a negative tolerance never fires)."""
         import scipy.sparse.linalg as spl
         sp = self.sp
         a = self.a
         pose, model, point = a.cam_pose.copy(), a.cam_model.copy(), a.point.copy()
         cost = self.cost(pose, model, point)
         r, J = self.linearise(pose, model, point)
-        scale = 1.0 / (1.0 + np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel()))
+        if jacobi_scaling:
+            scale = 1.0 / (1.0 + np.sqrt(np.asarray(J.multiply(J).sum(0)).ravel()))
+        else:
+            scale = np.ones(self.n)
         J = J @ sp.diags(scale)
-        rec = [dict(cost=cost, ok=1, gmax=np.abs(J.T @ r / scale).max() if self.n else 0.0, step=0.0)]
-        dec, reuse, diag = 2.0, False, None
-        for _ in range(iters):
+        x_norm = np.linalg.norm(self.pack(pose, model, point))
+        row = dict(cost=cost, ok=1, valid=1, gmax=np.abs(J.T @ r / scale).max() if self.n else 0.0, step=0.0, rho=0.0, change=0.0)
+        rec = []
+        dec, reuse, diag, invalid = 2.0, False, None, 0
+        while True:
+            row["radius"] = radius
+            rec.append(row)
+            if len(rec) - 1 >= iters:
+                return (pose, model, point), rec, "NO_CONVERGENCE"
+            if row["gmax"] <= gradient_tolerance:
+                return (pose, model, point), rec, "CONVERGENCE_GRADIENT"
+            if radius <= min_radius:
+                return (pose, model, point), rec, "MIN_RADIUS"
             if not reuse:
-                diag = np.clip(np.asarray(J.multiply(J).sum(0)).ravel(), 1e-6, 1e32)
+                diag = np.clip(np.asarray(J.multiply(J).sum(0)).ravel(), min_lm_diagonal, max_lm_diagonal)
             H = (J.T @ J + sp.diags(np.sqrt(diag / radius) ** 2)).tocsc()
             y = spl.splu(H).solve(J.T @ r)
             step = -y
             m = J @ step
             mcc = -m @ (r + m / 2)
+            reuse = True
+            if not (np.isfinite(step).all() and mcc > 0):
+                invalid += 1
+                if invalid >= max_invalid:
+                    return (pose, model, point), rec, "FAILURE"
+                radius /= dec
+                dec *= 2
+                row = dict(cost=cost, ok=0, valid=0, gmax=row["gmax"], step=0.0, rho=0.0, change=0.0)
+                continue
+            invalid = 0
             delta = step * scale
             cp, cm_, cx = self.apply(pose, model, point, delta)
             ccost = self.cost(cp, cm_, cx)
             x_old = self.pack(pose, model, point)
             snorm = np.linalg.norm(self.pack(cp, cm_, cx) - x_old)
+            if snorm <= parameter_tolerance * (x_norm + parameter_tolerance):
+                return (pose, model, point), rec, "CONVERGENCE_PARAMETER"
+            if abs(cost - ccost) <= function_tolerance * cost:
+                return (pose, model, point), rec, "CONVERGENCE_FUNCTION"
             rho = (cost - ccost) / mcc
-            if mcc > 0 and rho > min_relative_decrease:
+            if rho > min_relative_decrease:
+                change = cost - ccost
                 pose, model, point, cost = cp, cm_, cx, ccost
+                x_norm = np.linalg.norm(self.pack(pose, model, point))
                 r, J = self.linearise(pose, model, point)
                 J = J @ sp.diags(scale)
-                radius = min(1e16, radius / max(1 / 3, 1 - (2 * rho - 1) ** 3))
+                radius = min(max_radius, radius / max(1 / 3, 1 - (2 * rho - 1) ** 3))
                 dec, reuse = 2.0, False
-                rec.append(dict(cost=cost, ok=1, gmax=np.abs(J.T @ r / scale).max(), step=snorm))
+                row = dict(cost=cost, ok=1, valid=1, gmax=np.abs(J.T @ r / scale).max(), step=snorm, rho=rho, change=change)
             else:
                 radius /= dec
                 dec *= 2
-                reuse = True
-                rec.append(dict(cost=ccost, ok=0, gmax=rec[-1]["gmax"], step=snorm))
-        return (pose, model, point), rec
+                row = dict(cost=ccost, ok=0, valid=1, gmax=row["gmax"], step=snorm, rho=rho, change=cost - ccost)

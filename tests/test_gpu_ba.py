@@ -42,6 +42,41 @@ def check_parity(ctx, O, make_arrays, opts_kw=None, tol_param=1e-7, tol_cost=1e-
     return r_gpu, r_ref, a_gpu
 
 
+def check_parity_strict(r_gpu, r_ref, a_gpu, a_ref, tol_param=1e-7, tol_cost=1e-9):
+    """Everything check_parity compares, on two finished solves, plus what it leaves out: relative_decrease and cost_change
+    per row (rtol 1e-5, atol 1e-9 x the row's cost), the step counters and initial_cost.  Returns the largest deviations
+    measured (cost and rho over the rows, parameters over the three arrays) for the record; prints them before it asserts."""
+    ig, ir = r_gpu["iterations"], r_ref["iterations"]
+    dev = dict(cost=0.0, param=0.0, rho=0.0)
+    if len(ig) == len(ir):
+        dev["cost"] = float((np.abs(ig["cost"] - ir["cost"]) / np.maximum(np.abs(ir["cost"]), 1e-300)).max())
+        dev["rho"] = float((np.abs(ig["relative_decrease"] - ir["relative_decrease"]) / np.maximum(np.abs(ir["relative_decrease"]), 1e-300)).max())
+        dev["param"] = float(max(_rel(getattr(a_gpu, n), getattr(a_ref, n)) for n in ("cam_pose", "cam_model", "point")))
+    print("deviation GPU vs oracle: cost %.2e (bar %.0e)  parameters %.2e (bar %.0e)  rho %.2e (bar 1e-05 + 1e-9 cost)"
+          % (dev["cost"], tol_cost, dev["param"], tol_param, dev["rho"]))
+    assert r_gpu["num_residuals"] == r_ref["num_residuals"]
+    assert r_gpu["num_reduced_params"] == r_ref["num_reduced_params"]
+    assert r_gpu["termination"] == r_ref["termination"], (r_gpu["termination"], r_ref["termination"])
+    assert r_gpu["num_iterations"] == r_ref["num_iterations"]
+    assert r_gpu["num_successful_steps"] == r_ref["num_successful_steps"]
+    assert r_gpu["num_unsuccessful_steps"] == r_ref["num_unsuccessful_steps"]
+    np.testing.assert_array_equal(ig["step_is_successful"], ir["step_is_successful"])
+    np.testing.assert_array_equal(ig["step_is_valid"], ir["step_is_valid"])
+    np.testing.assert_allclose(ig["cost"], ir["cost"], rtol=tol_cost)
+    np.testing.assert_allclose(ig["trust_region_radius"], ir["trust_region_radius"], rtol=1e-6)
+    np.testing.assert_allclose(ig["gradient_max_norm"], ir["gradient_max_norm"], rtol=1e-5, atol=1e-9)
+    np.testing.assert_allclose(ig["step_norm"], ir["step_norm"], rtol=1e-5, atol=1e-12)
+    for k in range(len(ir)):
+        for f in ("relative_decrease", "cost_change"):
+            assert abs(ig[f][k] - ir[f][k]) <= 1e-5 * abs(ir[f][k]) + 1e-9 * abs(ir["cost"][k]), (f, k, ig[f][k], ir[f][k])
+    assert abs(r_gpu["initial_cost"] - r_ref["initial_cost"]) <= tol_cost * abs(r_ref["initial_cost"])
+    assert abs(r_gpu["final_cost"] - r_ref["final_cost"]) <= tol_cost * abs(r_ref["final_cost"])
+    assert _rel(a_gpu.cam_pose, a_ref.cam_pose) < tol_param
+    assert _rel(a_gpu.cam_model, a_ref.cam_model) < tol_param
+    assert _rel(a_gpu.point, a_ref.point) < tol_param
+    return dev
+
+
 def test_ba_config1_full(ctx, oracle):
     sc = scene.config_scene(1)
     r, _, a = check_parity(ctx, oracle, lambda: A.BaArrays.from_scene(sc), dict(max_num_iterations=50))

@@ -273,18 +273,30 @@ def test_threaded_oracle_is_bit_identical_to_one_thread(oracle):
     np.testing.assert_array_equal(s1, s4)
 
 
-def _compare_with_sparse_lm(oracle, arr_factory, iters, radius=1e4, tol=1e-9):
+def _compare_with_sparse_lm(oracle, arr_factory, iters, radius=1e4, tol=1e-9, opts=None, huber=1.0):
+    """The oracle against SparseLM on the same problem.  Without `opts` the stopping rules are off and the run has `iters`
+    iterations; `opts` (msfm_ba_options fields) go to both solvers.  Same termination, number of recorded rows, accept and
+    valid sequences; cost to `tol`, |gradient|_max and |step| to 1e-6, the radius to 1e-6."""
     from tests.independent_lm import SparseLM
+    from tests import ba_option_cases as K
     arr = arr_factory()
-    res = oracle.ba_solve(arr, oracle.default_options(max_num_iterations=iters, function_tolerance=-1.0, parameter_tolerance=-1.0,
-                                                      gradient_tolerance=-1.0, initial_trust_region_radius=radius))
-    (p, m, X), rec = SparseLM(arr_factory()).run(iters, radius)
+    o = dict(max_num_iterations=iters, function_tolerance=-1.0, parameter_tolerance=-1.0, gradient_tolerance=-1.0,
+             initial_trust_region_radius=radius)
+    o.update(opts or {})
+    res = oracle.ba_solve(arr, oracle.default_options(**o))
+    (p, m, X), rec, term = SparseLM(arr_factory(), huber=o.get("huber_delta", huber)).run(o["max_num_iterations"], **K.sparse_lm_kwargs(o))
     it = res["iterations"]
-    assert len(it) == len(rec) == iters + 1
+    assert res["termination"] == term, (res["termination"], term)
+    assert len(it) == len(rec) == res["num_iterations"] + 1
+    if opts is None:
+        assert len(it) == iters + 1
     np.testing.assert_array_equal(it["step_is_successful"], [q["ok"] for q in rec])
+    np.testing.assert_array_equal(it["step_is_valid"], [q["valid"] for q in rec])
     np.testing.assert_allclose(it["cost"], [q["cost"] for q in rec], rtol=tol)
     np.testing.assert_allclose(it["gradient_max_norm"], [q["gmax"] for q in rec], rtol=1e-6, atol=1e-9)
     np.testing.assert_allclose(it["step_norm"][1:], [q["step"] for q in rec[1:]], rtol=1e-6)
+    np.testing.assert_allclose(it["trust_region_radius"], [q["radius"] for q in rec], rtol=1e-6)
+    res["sparse_lm"] = rec
     return arr, (p, m, X), it
 
 
@@ -374,3 +386,60 @@ def test_slam_gate_known_answers(oracle):
         dx, dy = p2[0] - q[0] * sc, p2[1] - q[1] * sc
         want.append(-1 if np.sqrt(dx * dx + dy * dy) > np.float32(40) * np.float32(5.0) else int(ids[m, 0]))
     assert code.tolist() == want and nk == sum(w >= 0 for w in want) and 0 < nk < nr
+
+
+# ---- the oracle's handling of msfm_ba_options, its stopping rules and its failure path, pinned before the GPU is compared with it ----
+def _option_case(oracle, name):
+    from tests import ba_option_cases as K
+    c = K.CASES[name]
+    tol = 1e-8 if c["scene"] == "J" else 1e-9      # (J: rejected trial steps with costs 300x the accepted ones)
+    arr, (p, m, X), it = _compare_with_sparse_lm(oracle, lambda: K.case_arrays(name), None, tol=tol, opts=c["opts"])
+    if name in K.EXPECT:
+        res = oracle.ba_solve(K.case_arrays(name), oracle.default_options(**c["opts"]))
+        assert (res["termination"], res["num_iterations"]) == K.EXPECT[name]
+    # both solvers end at the same parameters (loosely: nothing fixes the gauge, cond ~ radius)
+    for g, r in ((arr.cam_pose, p), (arr.cam_model, m), (arr.point, X)):
+        assert np.abs(g - r).max() <= 1e-6 * np.abs(r).max()
+    return it
+
+
+@pytest.mark.parametrize("name", ["huber-O-0.25", "huber-O-4", "huber-O-1e6", "huber-G-0.25", "huber-G-4", "huber-J-0.25", "huber-J-400"])
+def test_oracle_huber_delta_against_sparse_solver(oracle, name):
+    """huber_delta other than 1: reprojection rows of free and frozen blocks and GPS rows on both sides of the threshold."""
+    _option_case(oracle, name)
+
+
+@pytest.mark.parametrize("name", ["lmdiag-default", "lmdiag-min10", "lmdiag-max1e-4", "lmdiag-noscale", "lmdiag-zero-weight"])
+def test_oracle_lm_diagonal_options_against_sparse_solver(oracle, name):
+    """min_lm_diagonal / max_lm_diagonal clamps that bind, with and without the Jacobi scaling, and points of zero weight
+    whose blocks are the clamped diagonal alone."""
+    _option_case(oracle, name)
+
+
+@pytest.mark.parametrize("name", ["cap-R", "mrd-O", "mrd-J", "minrad-R", "minrad-J", "grad-R", "grad-R-late", "grad-J", "param-R", "func-R"])
+def test_oracle_radius_and_stopping_rules_against_sparse_solver(oracle, name):
+    """The radius cap, min_relative_decrease, and every termination by a radius or a tolerance, in the Ceres 1.13 order."""
+    _option_case(oracle, name)
+
+
+@pytest.mark.parametrize("name", ["fail-Z-5", "fail-Z-3", "fail-Z-1", "grad-Z"])
+def test_oracle_invalid_steps_and_failure_against_sparse_solver(oracle, name):
+    """All weights zero: the model cost change is exactly 0, every step invalid; the radius is divided by 2, 4, 8, ... and the
+    max_num_consecutive_invalid_steps-th invalid step in a row ends the run with FAILURE, unrecorded."""
+    from tests import ba_option_cases as K
+    it = _option_case(oracle, name)
+    assert (it["cost"] == 0).all() and (it["step_is_valid"][1:] == 0).all()
+    np.testing.assert_array_equal(it["trust_region_radius"], [1e4, 5e3, 1.25e3, 156.25, 9.765625][:len(it)])
+
+
+def test_option_cases_meet_the_condition_on_their_inputs(oracle):
+    """Every decision of every compared trajectory has a margin in the oracle (tests/ba_option_cases.py: decision_margins,
+    firing_margin) and ends as the table says - so that the GPU comparison never sits on the rounding floor."""
+    from tests import ba_option_cases as K
+    for name, c in K.CASES.items():
+        res = oracle.ba_solve(K.case_arrays(name), oracle.default_options(**c["opts"]))
+        K.decision_margins(res, c["opts"], gradient_factor=1.3 if name == "grad-J" else 2.0)
+        if name in K.EXPECT:
+            assert (res["termination"], res["num_iterations"]) == K.EXPECT[name], name
+    for name in ("param-R", "func-R"):
+        K.firing_margin(oracle.ba_solve, oracle.default_options, name)
