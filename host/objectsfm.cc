@@ -7,6 +7,7 @@
 #include <iomanip>
 #include <cstdlib>
 #include <limits>
+#include <numeric>
 #include <stdexcept>
 
 namespace objectsfm {
@@ -429,6 +430,219 @@ void IncrementalSfM::RemovePointOutliers() {
     if (std::sqrt(p->mse_) > options_.th_mse_outliers) p->is_bad_estimated_ = true;
     p->is_new_added_ = false;
   }
+}
+
+// ---- IncrementalSfM: the seed pair ----------------------------------------------------------------
+IncrementalSfM::IncrementalSfM() { msfm_seed_default_options(&seed_options_); }
+
+void IncrementalSfM::SortImagePairs(std::vector<std::pair<int, int>>& seed_pair_hyps) const {
+  const int num_img = (int)graph_.n_features.size();
+  std::vector<float> match_strength(num_img, 0);
+  for (int i = 0; i < num_img; i++) {
+    float sum = 0;                                   // math::sum(T*, int, float&), basic_funcs.h:50-57
+    for (int j = 0; j < num_img; j++) sum += graph_.match_graph_[(size_t)i * num_img + j];
+    match_strength[i] = (float)std::log(sum + 2.0);
+  }
+  std::vector<std::pair<int, float>> pairs;
+  for (int i = 0; i + 1 < num_img; i++) {
+    if (is_img_processed_[i]) continue;
+    for (int j = i + 1; j < num_img; j++) {
+      const int num_match_ij = graph_.match_graph_[(size_t)i * num_img + j];
+      if (!num_match_ij || is_img_processed_[j]) continue;
+      const double strength = match_strength[i] * match_strength[j] * std::log((double)num_match_ij);
+      pairs.push_back(std::pair<int, float>(i * num_img + j, (float)strength));
+    }
+  }
+  std::sort(pairs.begin(), pairs.end(), [](const std::pair<int, float>& l, const std::pair<int, float>& r) {
+    return l.second > r.second || (l.second == r.second && l.first < r.first);
+  });
+  seed_pair_hyps.clear();
+  for (auto& p : pairs) seed_pair_hyps.push_back(std::make_pair(p.first / num_img, p.first % num_img));
+}
+
+namespace {
+struct SeedAnswer {   // one hypothesis behind the gates
+  bool pass = false;
+  double f[2] = {0, 0};
+  Mat3 R; Vec3 t;
+  std::vector<int> pt_match;
+  std::vector<double> X, mse;
+};
+}  // namespace
+
+// :252-290, :334, :352-373, :401-408 for the hypothesis that passed: two cameras, their model(s), the accepted points
+static void seed_adopt(IncrementalSfM& s, int id_img1, int id_img2, const SeedAnswer& a) {
+  const int nf_first1 = std::accumulate(s.graph_.n_features.begin(), s.graph_.n_features.begin() + id_img1, 0);
+  const int nf_first2 = std::accumulate(s.graph_.n_features.begin(), s.graph_.n_features.begin() + id_img2, 0);
+  int m0 = -1;
+  for (size_t p = 0; p < s.graph_.pair_img.size() / 2; p++)
+    if (s.graph_.pair_img[2 * p] == id_img1 && s.graph_.pair_img[2 * p + 1] == id_img2) m0 = s.graph_.match_off[p];
+  if (m0 < 0) throw std::runtime_error("FindSeedPairThenReconstruct: the winning pair is not in graph_");
+  // the seed search starts a model (:253): a caller that still holds cameras, models or points of an earlier one owns them
+  if (!s.cams_.empty() || !s.cam_models_.empty() || !s.pts_.empty())
+    throw std::runtime_error("FindSeedPairThenReconstruct: cams_ / cam_models_ / pts_ must be empty");
+  s.cams_.assign(2, nullptr);
+  for (int k = 0; k < 2; k++) { s.cams_[k] = new Camera; s.cams_[k]->AssociateImage(k ? id_img2 : id_img1); s.cams_[k]->SetID(k); }
+  const bool shared = s.image_model_[id_img1] == s.image_model_[id_img2];
+  for (int k = 0; k < (shared ? 1 : 2); k++) {
+    CameraModel* m = new CameraModel(k, 0, 0, 0.0, a.f[k], "", "");
+    s.cam_models_.push_back(m);
+  }
+  s.cams_[0]->AssociateCamereModel(s.cam_models_[s.cam_models_.size() - (shared ? 1 : 2)]);
+  s.cams_[1]->AssociateCamereModel(s.cam_models_.back());
+  s.cams_[0]->cam_model_->AddCamera(0);
+  s.cams_[1]->cam_model_->AddCamera(1);
+  Mat3 I; for (int k = 0; k < 9; k++) I.m[k] = (k % 4 == 0) ? 1.0 : 0.0;
+  Vec3 zero; for (int k = 0; k < 3; k++) zero[k] = 0.0;
+  s.cams_[0]->SetRTPose(I, zero);
+  s.cams_[1]->SetRTPose(a.R, a.t);
+  for (size_t e = 0; e < a.pt_match.size(); e++) {
+    const int f1 = s.graph_.matches[2 * (size_t)(m0 + a.pt_match[e])], f2 = s.graph_.matches[2 * (size_t)(m0 + a.pt_match[e]) + 1];
+    Point3D* pt = new Point3D;
+    pt->id_ = (int)s.pts_.size();
+    const int g1 = f1 + id_img1 * s.options_.idx_max_per_image, g2 = f2 + id_img2 * s.options_.idx_max_per_image;
+    pt->AddObservation(s.cams_[0], s.keypoints_[2 * (size_t)(nf_first1 + f1)], s.keypoints_[2 * (size_t)(nf_first1 + f1) + 1], g1);
+    pt->AddObservation(s.cams_[1], s.keypoints_[2 * (size_t)(nf_first2 + f2)], s.keypoints_[2 * (size_t)(nf_first2 + f2) + 1], g2);
+    for (int k = 0; k < 3; k++) pt->data[k] = a.X[3 * e + k];
+    pt->mse_ = a.mse[e];
+    s.pts_.push_back(pt);
+    s.cams_[0]->AddPoints(pt, g1);
+    s.cams_[1]->AddPoints(pt, g2);
+  }
+  if (s.seed_adjust_) {
+    s.FullBundleAdjustment();   // :393
+    s.RemovePointOutliers();    // :396
+  }
+  s.cams_[0]->visible_cams_.push_back(0); s.cams_[0]->visible_cams_.push_back(1);   // :401-408
+  s.cams_[1]->visible_cams_.push_back(1); s.cams_[1]->visible_cams_.push_back(0);
+  s.is_img_processed_[id_img1] = true; s.is_img_processed_[id_img2] = true;
+  s.img_cam_map_.insert(std::make_pair(id_img1, 0));
+  s.img_cam_map_.insert(std::make_pair(id_img2, 1));
+}
+
+static void seed_check_inputs(const IncrementalSfM& s, const char* who) {
+  const size_t n = s.graph_.n_features.size();
+  const size_t rows = (size_t)std::accumulate(s.graph_.n_features.begin(), s.graph_.n_features.end(), 0);
+  if (!s.store_ || s.keypoints_.size() != 2 * rows || s.image_focal_.size() != n || s.image_model_.size() != n)
+    throw std::runtime_error(std::string(who) + ": SetMatches, SetKeypoints, image_focal_ and image_model_ first");
+}
+
+bool IncrementalSfM::FindSeedPairThenReconstruct() {
+  seed_check_inputs(*this, "FindSeedPairThenReconstruct");
+  std::vector<std::pair<int, int>> hyps;
+  SortImagePairs(hyps);
+  seed_hyps_visited_ = 0;
+  msfm_seed_options opt = seed_options_;
+  opt.th_mse_reprojection = options_.th_mse_reprojection; opt.th_angle_small = options_.th_angle_small;
+  opt.th_seedpair_structures = options_.th_seedpair_structures;
+  for (size_t c0 = 0; c0 < hyps.size(); c0 += seed_chunk_) {
+    const int n = (int)std::min(hyps.size() - c0, (size_t)seed_chunk_);
+    std::vector<int> hyp_img(2 * (size_t)n);
+    std::vector<double> cam_fk(6 * (size_t)n, 0.0);
+    std::vector<uint8_t> same(n);
+    for (int h = 0; h < n; h++) {
+      const int i1 = hyps[c0 + h].first, i2 = hyps[c0 + h].second;
+      hyp_img[2 * h] = i1; hyp_img[2 * h + 1] = i2;
+      cam_fk[6 * h] = image_focal_[i1]; cam_fk[6 * h + 3] = image_focal_[i2];
+      same[h] = image_model_[i1] == image_model_[i2];
+    }
+    msfm_seed_problem P{};
+    P.n_hyp = n; P.hyp_img = hyp_img.data(); P.cam_fk = cam_fk.data(); P.same_model = same.data(); P.keypoints = keypoints_.data();
+    msfm_seed_set* set = nullptr;
+    check(msfm_seed_hypotheses(Context(), store_.get(), &P, &opt, &set), "msfm_seed_hypotheses");
+    int n_points = 0, winner = -1;
+    msfm_seed_set_size(set, nullptr, &n_points, &winner, nullptr);
+    if (winner < 0) { msfm_seed_set_destroy(set); continue; }
+    std::vector<double> f(2 * (size_t)n), R(9 * (size_t)n), t(3 * (size_t)n), X(3 * (size_t)std::max(1, n_points)), mse(std::max(1, n_points));
+    std::vector<int> pt_off(n + 1), pt_match(std::max(1, n_points));
+    msfm_seed_set_fetch(set, nullptr, nullptr, nullptr, nullptr, f.data(), R.data(), t.data(), nullptr, pt_off.data(), pt_match.data(), X.data(),
+                        mse.data());
+    msfm_seed_set_destroy(set);
+    SeedAnswer a;
+    a.pass = true;
+    a.f[0] = f[2 * winner]; a.f[1] = f[2 * winner + 1];
+    for (int k = 0; k < 9; k++) a.R.m[k] = R[9 * (size_t)winner + k];
+    for (int k = 0; k < 3; k++) a.t[k] = t[3 * (size_t)winner + k];
+    a.pt_match.assign(pt_match.begin() + pt_off[winner], pt_match.begin() + pt_off[winner + 1]);
+    a.X.assign(X.begin() + 3 * (size_t)pt_off[winner], X.begin() + 3 * (size_t)pt_off[winner + 1]);
+    a.mse.assign(mse.begin() + pt_off[winner], mse.begin() + pt_off[winner + 1]);
+    seed_hyps_visited_ = (int)c0 + winner + 1;
+    seed_adopt(*this, hyps[c0 + winner].first, hyps[c0 + winner].second, a);
+    return true;
+  }
+  return false;
+}
+
+bool IncrementalSfM::FindSeedPairThenReconstructHost() {
+  seed_check_inputs(*this, "FindSeedPairThenReconstructHost");
+  std::vector<std::pair<int, int>> hyps;
+  SortImagePairs(hyps);
+  seed_hyps_visited_ = 0;
+  std::vector<int> first(graph_.n_features.size() + 1, 0);
+  for (size_t i = 0; i < graph_.n_features.size(); i++) first[i + 1] = first[i] + graph_.n_features[i];
+  for (size_t i = 0; i < hyps.size(); i++) {
+    const int id_img1 = hyps[i].first, id_img2 = hyps[i].second;
+    seed_hyps_visited_ = (int)i + 1;
+    int m0 = 0, cnt = 0;   // graph_.QueryMatch(id_img1, id_img2, matches), :249
+    for (size_t p = 0; p < graph_.pair_img.size() / 2; p++)
+      if (graph_.pair_img[2 * p] == id_img1 && graph_.pair_img[2 * p + 1] == id_img2) { m0 = graph_.match_off[p]; cnt = graph_.match_off[p + 1] - m0; }
+    // :294-304 - behind h empty problems, so that the pose call draws the samples of problem h = i % seed_chunk_
+    const int h = (int)(i % (size_t)seed_chunk_);
+    std::vector<int> off(h + 2, 0);
+    off[h + 1] = cnt;
+    std::vector<double> a(2 * (size_t)std::max(1, cnt)), b(a.size());
+    for (int j = 0; j < cnt; j++) {
+      const size_t r1 = (size_t)first[id_img1] + graph_.matches[2 * (size_t)(m0 + j)], r2 = (size_t)first[id_img2] + graph_.matches[2 * (size_t)(m0 + j) + 1];
+      a[2 * j] = keypoints_[2 * r1]; a[2 * j + 1] = keypoints_[2 * r1 + 1]; b[2 * j] = keypoints_[2 * r2]; b[2 * j + 1] = keypoints_[2 * r2 + 1];
+    }
+    const size_t m = (size_t)h + 1;
+    std::vector<double> E(9 * m), R(9 * m), t(3 * m), f1(m, 0.0), f2(m, 0.0);
+    std::vector<uint8_t> ok(m, 0);
+    SeedAnswer ans;
+    ans.f[0] = image_focal_[id_img1]; ans.f[1] = image_focal_[id_img2];
+    if (ans.f[0] && ans.f[1]) {   // :307-315
+      f1[h] = ans.f[0]; f2[h] = ans.f[1];
+      check(msfm_relpose_5pt_batch(Context(), h + 1, off.data(), a.data(), b.data(), f1.data(), f2.data(), seed_options_.ransac_times_5pt,
+                                   seed_options_.seed_5pt, E.data(), R.data(), t.data(), ok.data(), nullptr), "relpose_5pt_batch");
+      if (!ok[h]) continue;
+    } else {                      // :316-333
+      std::vector<double> F(9 * m);
+      check(msfm_relpose_8pt_batch(Context(), h + 1, off.data(), a.data(), b.data(), seed_options_.ransac_times_8pt, seed_options_.seed_8pt, F.data(),
+                                   f1.data(), f2.data(), E.data(), R.data(), t.data(), ok.data(), nullptr, nullptr, nullptr), "relpose_8pt_batch");
+      if (!ok[h]) continue;
+      if (image_model_[id_img1] == image_model_[id_img2]) { ans.f[0] = (f1[h] + f2[h]) / 2.0; ans.f[1] = ans.f[0]; }
+      else { ans.f[0] = f1[h]; ans.f[1] = f2[h]; }
+    }
+    for (int k = 0; k < 9; k++) ans.R.m[k] = R[9 * (size_t)h + k];
+    for (int k = 0; k < 3; k++) ans.t[k] = t[3 * (size_t)h + k];
+    // :344-374: Trianglate2 of every match on two temporary cameras (the batch form of Point3D::Trianglate2, one call)
+    Camera cam[2];
+    CameraModel model[2];
+    Mat3 I; for (int k = 0; k < 9; k++) I.m[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    Vec3 zero; for (int k = 0; k < 3; k++) zero[k] = 0.0;
+    for (int k = 0; k < 2; k++) { model[k].SetFocalLength(ans.f[k]); cam[k].AssociateCamereModel(&model[k]); cam[k].SetID(k); }
+    cam[0].SetRTPose(I, zero);
+    cam[1].SetRTPose(ans.R, ans.t);
+    std::vector<Point3D> tmp(cnt);
+    std::vector<Point3D*> ptrs(cnt);
+    for (int j = 0; j < cnt; j++) {
+      tmp[j].AddObservation(&cam[0], a[2 * j], a[2 * j + 1], 0);
+      tmp[j].AddObservation(&cam[1], b[2 * j], b[2 * j + 1], 1);
+      ptrs[j] = &tmp[j];
+    }
+    std::vector<char> okp;
+    if (cnt) TrianglateBatch(ptrs, options_.th_mse_reprojection, options_.th_angle_small, false, &okp);
+    for (int j = 0; j < cnt; j++)
+      if (okp[j]) {
+        ans.pt_match.push_back(j);
+        for (int k = 0; k < 3; k++) ans.X.push_back(tmp[j].data[k]);
+        ans.mse.push_back(tmp[j].mse_);
+      }
+    if ((int)ans.pt_match.size() < options_.th_seedpair_structures || (int)ans.pt_match.size() < cnt / 5) continue;   // :380-381
+    seed_adopt(*this, id_img1, id_img2, ans);
+    return true;
+  }
+  return false;
 }
 
 // ---- IncrementalSfM: which image to localise next -------------------------------------------------

@@ -160,6 +160,9 @@ struct IncrementalSfMOptions {       // basic_structs.h:147-227, the fields this
   bool use_same_camera = false;      // basic_structs.h:167
   int idx_max_per_image = 1000000;   // basic_structs.h:171: global feature id = local + idx_max_per_image * image
   int th_max_failure_localization = 5;   // basic_structs.h:176
+  double th_mse_reprojection = 3.0;      // basic_structs.h:187
+  double th_angle_small = 3.0 / 180.0 * 3.1415;   // basic_structs.h:190
+  int th_seedpair_structures = 20;       // basic_structs.h:174
 };
 // What FindImageToLocalize reads of Graph (SfM/src/graph/graph.h): match_graph_ and the verified match lists - here in memory
 // in the flat layout of msfm_match_store_create instead of behind Graph::QueryMatch's `<i>_match` files (graph.cc:92-137).
@@ -192,6 +195,28 @@ class IncrementalSfM {
   // what scripts/localize_bench.py times the library call against, and a second opinion for tests/localize_host_check.cc.
   void FindImageToLocalizeHost(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
                                std::vector<std::vector<int>>& visible_cams) const;
+  // sfm_incremental.cc:1790-1829: the image pairs in the order the seed search tries them.  Row sums in binary32, the C
+  // library's log; ties, which the reference's std::sort leaves open, go to the lower i * num_img + j.
+  void SortImagePairs(std::vector<std::pair<int, int>>& seed_pair_hyps) const;
+  // sfm_incremental.cc:224-415.  The ranked pairs go to msfm_seed_hypotheses on the resident store in chunks of seed_chunk_
+  // until a chunk has a winner (hypothesis h of a chunk draws the samples of problem h); the winner's two cameras, their
+  // models and its points become cams_ / cam_models_ / pts_, then FullBundleAdjustment, RemovePointOutliers and the
+  // bookkeeping of :401-408.  Needs SetMatches, SetKeypoints and the per-image image_focal_ / image_model_.
+  bool FindSeedPairThenReconstruct();
+  // The same function as the reference writes it: one hypothesis at a time through RelativePoseWith[out]FocalLength's library
+  // calls and Trianglate2 per match, on host arrays.  Hypothesis i of the walk is handed to the pose call as problem
+  // i % seed_chunk_ behind empty problems, so it draws the samples the batched call draws: same poses bit for bit, points
+  // to the 1e-9 by which msfm_triangulate_midpoint_batch differs.  What scripts/seed_bench.py times the batched call against.
+  bool FindSeedPairThenReconstructHost();
+  void SetKeypoints(const std::vector<float>& keypoints) { keypoints_ = keypoints; }   // [sum of n_features][2], images in order
+  std::vector<float> keypoints_;
+  std::vector<double> image_focal_;          // per image: f of its camera model in pixels, 0.0 = unknown (CameraModel::f_)
+  std::vector<int> image_model_;             // per image: images with equal values share a CameraModel (CameraAssociateCameraModel)
+  int seed_chunk_ = 64;
+  bool seed_adjust_ = true;                  // false: stop behind the gates, before FullBundleAdjustment (tests, timing)
+  int seed_hyps_visited_ = 0;                // hypotheses the reference's loop visits up to and including the winner
+  msfm_seed_options seed_options_;           // filled by the constructor from msfm_seed_default_options and options_
+  IncrementalSfM();
   MatchGraph graph_;
   std::vector<bool> is_img_processed_;
   std::vector<int> localize_fail_times_;

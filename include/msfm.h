@@ -701,6 +701,63 @@ int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const
                            double* f_cur, double* E, double* R, double* t, uint8_t* ok, int* best_iter,
                            double* best_error, int* n_candidates);
 
+/* ======================================================================================
+ *  Which seed pair reconstructs, and with which points: the hypotheses of a model's first pair in one call
+ * ====================================================================================== */
+/* The loop body of IncrementalSfM::FindSeedPairThenReconstruct (SfM/src/sfm_incremental.cc:235-390) up to and including its
+ * two gates, for a list of hypotheses at once, on the resident match store.  (The order of the list, SortImagePairs
+ * :1790-1829, uses the C library's log and stays on the host: metricsfm_amd/seed.py::sort_image_pairs,
+ * IncrementalSfM::SortImagePairs of host/objectsfm.cc.)  Per hypothesis h = (id_img1, id_img2) of hyp_img, in that order:
+ *   matches  QueryMatch(id_img1, id_img2) = store row id_img1, entry id_img2, in stored order (:249); a pair the store does
+ *            not hold has 0 matches; a feature that occurs in several matches stays in all of them; keypoints go float ->
+ *            double (:298-303)
+ *   arm      both f != 0: RelativePoseWithFocalLength with the given f (:307-315); otherwise RelativePoseWithoutFocalLength on
+ *            centred pixels, and BOTH focal lengths are replaced (:316-333): with same_model[h] both become (f1 + f2) / 2
+ *            (:324-327), else f1 and f2 (:330-331).  The pose was formed with the unaveraged values; that quirk is kept.
+ *   pose     hypothesis h IS problem h of an n_hyp-problem call of msfm_relpose_5pt_batch (ransac_times_5pt, seed_5pt) or
+ *            msfm_relpose_8pt_batch (ransac_times_8pt, seed_8pt) in which the problems of the other arm are empty, bit for
+ *            bit: the sample key (seed, p, it[, n]) is the hypothesis index, and splitting a list over calls is the
+ *            caller's business.  !ok (:313, :321): pose_ok = 0, no points, pass = 0; f = the given values, R = t = c = 0.
+ *   cameras  camera 0 is [I|0] with centre 0 (:290); camera 1 has R = R21, t = t21 as returned and c = -(R^T t), each
+ *            component summed left to right as Camera::SetRTPose of host/objectsfm.cc does (:334)
+ *   points   every match is one two-view Point3D::Trianglate2(th_mse_reprojection, th_angle_small) with camera 0's
+ *            observation first (:344-374); the points are the accepted ones in match order: pt_match (index into the
+ *            pair's matches), X, mse.  Operation order of msfm_triangulate_midpoint_batch, but compiled without fused
+ *            multiply-adds and with + - * / sqrt only, so a CPU restatement built with -ffp-contract=off agrees bit for bit;
+ *            msfm_triangulate_midpoint_batch itself is contracted and agrees with this (and with its oracle) to 1e-9.
+ *   gates    pass = pose_ok && n_points >= th_seedpair_structures && n_points >= n_matches / 5, integer division (:380-381)
+ *   winner   the first h with pass, or -1; every hypothesis is answered (the reference stops at the winner).
+ * keypoints (optional): float [sum of n_features][2] in image order, as in msfm_localize_problem; only the rows of the
+ * hypotheses' images are uploaded.  Without it the store must hold the keypoints of those images (made from a chain).
+ * Nothing that scales with the store's matches crosses PCIe: h2d_bytes of msfm_seed_set_size reports what was sent.
+ * MSFM_E_INVAL: n_hyp outside [0, 65535], an image id outside the store, id_img1 == id_img2, no keypoints for an image,
+ * a negative or NaN f, th_mse_reprojection or th_angle_small NaN, th_seedpair_structures < 0, ransac_times outside
+ * [1, 65536].  The context stays usable.
+ * msfm_seed_set_fetch (every pointer may be NULL): arm [n] (5 or 8), pose_ok [n], pass [n], n_matches [n], f [n][2],
+ * R [n][9] row-major, t [n][3], c [n][3] of camera 1, pt_off [n+1], pt_match / X [..][3] / mse over pt_off[n] points. */
+typedef struct msfm_seed_options {      /* msfm_seed_default_options fills the reference's values */
+  double th_mse_reprojection;           /* 3.0                  basic_structs.h:187 */
+  double th_angle_small;                /* 3.0 / 180.0 * 3.1415 basic_structs.h:190, radians */
+  int32_t th_seedpair_structures;       /* 20                   basic_structs.h:174 */
+  int32_t ransac_times_5pt, ransac_times_8pt;   /* 100, 200 */
+  uint64_t seed_5pt, seed_8pt;          /* 0x4D53464D45, 0x4D53464D38: the defaults of the two relpose calls' Python binding */
+} msfm_seed_options;
+void msfm_seed_default_options(msfm_seed_options* opt);
+typedef struct msfm_seed_problem {
+  int32_t n_hyp;                        /* <= 65535 */
+  const int32_t* hyp_img;               /* [n_hyp][2] (id_img1, id_img2), tried in this order */
+  const double* cam_fk;                 /* [n_hyp][2][3]: f (0.0 = unknown), k1, k2 of each camera's model */
+  const uint8_t* same_model;            /* [n_hyp] both cameras share one CameraModel (:324) */
+  const float* keypoints;               /* optional */
+} msfm_seed_problem;
+typedef struct msfm_seed_set msfm_seed_set;
+int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* store, const msfm_seed_problem* problem,
+                         const msfm_seed_options* opt, msfm_seed_set** out);
+int msfm_seed_set_size(const msfm_seed_set* set, int* n_hyp, int* n_points, int* winner, int64_t* h2d_bytes);
+int msfm_seed_set_fetch(const msfm_seed_set* set, uint8_t* arm, uint8_t* pose_ok, uint8_t* pass, int* n_matches, double* f /*[n][2]*/,
+                        double* R /*[n][9]*/, double* t, double* c, int* pt_off /*[n+1]*/, int* pt_match, double* X, double* mse);
+void msfm_seed_set_destroy(msfm_seed_set* set);
+
 /* ==================================================================================== *
  *  Single-process multi-GPU context
  * ==================================================================================== */

@@ -112,6 +112,17 @@ class LocalizeProblem(C.Structure):
                 ("point_xyz", c_double_p), ("keypoints", c_float_p)]
 
 
+class SeedOptions(C.Structure):
+    """msfm_seed_options (include/msfm.h)."""
+    _fields_ = [("th_mse_reprojection", C.c_double), ("th_angle_small", C.c_double), ("th_seedpair_structures", C.c_int32),
+                ("ransac_times_5pt", C.c_int32), ("ransac_times_8pt", C.c_int32), ("seed_5pt", C.c_uint64), ("seed_8pt", C.c_uint64)]
+
+
+class SeedProblem(C.Structure):
+    """msfm_seed_problem (include/msfm.h)."""
+    _fields_ = [("n_hyp", C.c_int32), ("hyp_img", c_int_p), ("cam_fk", c_double_p), ("same_model", c_u8_p), ("keypoints", c_float_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

@@ -25,6 +25,7 @@ SYMBOLS = [
     "msfm_chain_destroy",
     "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
     "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
+    "msfm_seed_default_options", "msfm_seed_hypotheses", "msfm_seed_set_size", "msfm_seed_set_fetch", "msfm_seed_set_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
@@ -154,6 +155,14 @@ def lib():
     L.msfm_localize_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
     L.msfm_localize_set_destroy.argtypes = [vp]
     L.msfm_localize_set_destroy.restype = None
+    L.msfm_seed_default_options.argtypes = [C.POINTER(A.SeedOptions)]
+    L.msfm_seed_default_options.restype = None
+    L.msfm_seed_hypotheses.argtypes = [vp, vp, C.POINTER(A.SeedProblem), C.POINTER(A.SeedOptions), C.POINTER(vp)]
+    L.msfm_seed_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
+    L.msfm_seed_set_fetch.argtypes = [vp, A.c_u8_p, A.c_u8_p, A.c_u8_p, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
+                                      A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
+    L.msfm_seed_set_destroy.argtypes = [vp]
+    L.msfm_seed_set_destroy.restype = None
     L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
     L.msfm_multi_destroy.argtypes = [vp]
     L.msfm_multi_destroy.restype = None
@@ -185,6 +194,17 @@ def epnpf_options(**kw):
     """msfm_epnpf_options with the reference's values (0.5, 4.0, 0.01, 200 samples); keywords override fields."""
     o = A.EpnpfOptions()
     lib().msfm_epnpf_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def seed_options(**kw):
+    """msfm_seed_options with the reference's values (3.0 px, 3 degrees, 20 points, 100 / 200 samples); keywords override fields."""
+    o = A.SeedOptions()
+    lib().msfm_seed_default_options(C.byref(o))
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
@@ -450,6 +470,41 @@ class Context:
         if hp.value:
             out["pts_w"], out["pts_2d"] = pw[:nc], p2[:nc]
         return out
+
+    def seed_hypotheses(self, store, hyp_img, cam_fk, same_model, keypoints=None, **opts):
+        """msfm_seed_hypotheses (sfm_incremental.cc:235-390): pose, two-view points and the two gates of every seed-pair
+        hypothesis, on the resident store.  hyp_img [n][2], cam_fk [n][2][3] (f with 0 = unknown, k1, k2), same_model [n];
+        opts: fields of msfm_seed_options.  Returns a dict: arm, pose_ok, pass, n_matches, f [n][2], R [n][3][3], t, c [n][3],
+        pt_off [n+1], pt_match, X [..][3], mse, winner (-1: none), h2d_bytes."""
+        hyp = A.as_c(np.asarray(hyp_img, dtype=np.int32).reshape(-1, 2), np.int32)
+        n = len(hyp)
+        fk = A.as_c(np.asarray(cam_fk, dtype=np.float64).reshape(-1, 2, 3), np.float64)
+        same = A.as_c(np.asarray(same_model, dtype=np.uint8).reshape(-1), np.uint8)
+        if len(fk) != n or len(same) != n:
+            raise ValueError("hyp_img, cam_fk and same_model must describe the same number of hypotheses")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        P = A.SeedProblem(n, A.ptr(hyp, A.c_int_p), A.ptr(fk, A.c_double_p), A.ptr(same, A.c_u8_p), A.ptr(kp, A.c_float_p))
+        o = seed_options(**opts)
+        h = C.c_void_p()
+        self.check(lib().msfm_seed_hypotheses(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
+        try:
+            nh, npt, win, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+            lib().msfm_seed_set_size(h, C.byref(nh), C.byref(npt), C.byref(win), C.byref(nb))
+            npt, m = npt.value, max(1, n)
+            arm, pok, pas = (np.zeros(m, np.uint8) for _ in range(3))
+            nm, poff, ptm = np.zeros(m, np.int32), np.zeros(n + 1, np.int32), np.zeros(max(1, npt), np.int32)
+            f, R, t, c = np.zeros((m, 2)), np.zeros((m, 3, 3)), np.zeros((m, 3)), np.zeros((m, 3))
+            X, mse = np.zeros((max(1, npt), 3)), np.zeros(max(1, npt))
+            dp = A.c_double_p
+            lib().msfm_seed_set_fetch(h, A.ptr(arm, A.c_u8_p), A.ptr(pok, A.c_u8_p), A.ptr(pas, A.c_u8_p), A.ptr(nm, A.c_int_p), A.ptr(f, dp),
+                                      A.ptr(R, dp), A.ptr(t, dp), A.ptr(c, dp), A.ptr(poff, A.c_int_p), A.ptr(ptm, A.c_int_p), A.ptr(X, dp),
+                                      A.ptr(mse, dp))
+        finally:
+            lib().msfm_seed_set_destroy(h)
+        return {"arm": arm[:n], "pose_ok": pok[:n], "pass": pas[:n], "n_matches": nm[:n], "f": f[:n], "R": R[:n], "t": t[:n], "c": c[:n],
+                "pt_off": poff, "pt_match": ptm[:npt], "X": X[:npt], "mse": mse[:npt], "winner": win.value, "h2d_bytes": nb.value}
 
     def triangulate_midpoint(self, tracks, th_error, th_angle, X0=None):
         return self._tri(lib().msfm_triangulate_midpoint_batch, tracks, th_error, th_angle, X0)

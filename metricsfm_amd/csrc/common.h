@@ -245,6 +245,30 @@ struct ChainMatchView {
 };
 int chain_match_view(msfm_chain* C, ChainMatchView* out);   // MSFM_E_INVAL before msfm_chain_verify
 
+// A resident copy of the verified matches (localize.hip creates and destroys it; seed.hip reads it too)
+struct msfm_match_store {
+  msfm_ctx* ctx = nullptr;
+  int n_images = 0, n_pairs = 0, M = 0;
+  std::vector<int> n_features, feat_off, pair_img, match_off;
+  std::vector<int> row_off;       // [n_images + 1]: the pairs with idx1 = i are row_off[i] .. row_off[i + 1]  ("QueryMatch(i, j)" = row i, entry j)
+  std::vector<uint8_t> has_kp;    // per image: d_kp holds its keypoints (a store made from a chain)
+  DevBuf<int> d_match;            // [M][2]
+  DevBuf<float> d_kp;             // [feat_off[n_images]][2]
+};
+
+// The device halves of msfm_relpose_5pt_batch / msfm_relpose_8pt_batch (pose.hip): device buffers in, the three launches,
+// device buffers out; no synchronisation.  The exports are upload + this + download; seed.hip calls the same functions on
+// the buffers its gather kernel wrote.  The candidate scratch belongs to the caller, who keeps it until the stream has been
+// synchronised.  d_off [n_pairs + 1], points [off[n_pairs]][2], outputs [n_pairs] records.
+struct Relpose5Scratch { DevBuf<double> cE, ce; DevBuf<int> cn; };
+int pose_relpose5_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, const double* d_f_ref,
+                      const double* d_f_cur, int ransac_times, uint64_t seed, Relpose5Scratch& ws, double* dE, double* dR, double* dt,
+                      uint8_t* d_ok, int* d_ncand);
+struct Relpose8Scratch { DevBuf<double> cF, ce; DevBuf<uint8_t> cok; };
+int pose_relpose8_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, int ransac_times,
+                      uint64_t seed, Relpose8Scratch& ws, double* dF, double* d_f_ref, double* d_f_cur, double* dE, double* dR, double* dt,
+                      uint8_t* d_ok, int* d_best_iter, double* d_best_error, int* d_ncand);
+
 struct TrackPtrs {   // tri.hip: CSR tracks + cameras as the reference keeps them, device pointers
   int n_tracks;
   const int *off, *cam;

@@ -35,16 +35,6 @@
 #define LOC_LDS_MAX 4096
 #define LOC_BIG 0x7fffffff
 
-struct msfm_match_store {
-  msfm_ctx* ctx = nullptr;
-  int n_images = 0, n_pairs = 0, M = 0;
-  std::vector<int> n_features, feat_off, pair_img, match_off;
-  std::vector<int> row_off;       // [n_images + 1]: the pairs with idx1 = i are row_off[i] .. row_off[i + 1]  ("QueryMatch(i, j)" = row i, entry j)
-  std::vector<uint8_t> has_kp;    // per image: d_kp holds its keypoints (a store made from a chain)
-  DevBuf<int> d_match;            // [M][2]
-  DevBuf<float> d_kp;             // [feat_off[n_images]][2]
-};
-
 struct msfm_localize_set {
   std::vector<int> rank, corr_off, corr_feat, corr_point, vis_off, vis_cam;
   std::vector<double> pts_w, pts_2d;

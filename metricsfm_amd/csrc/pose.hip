@@ -1639,6 +1639,33 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   return MSFM_OK;
 }
 
+int pose_relpose5_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, const double* d_f_ref,
+                      const double* d_f_cur, int ransac_times, uint64_t seed, Relpose5Scratch& ws, double* dE, double* dR, double* dt,
+                      uint8_t* d_ok, int* d_ncand) {
+  hipStream_t s = ctx->stream;
+  const int T = ransac_times;
+  HIP_TRY(ctx, ws.cE.alloc((size_t)n_pairs * T * 90));
+  HIP_TRY(ctx, ws.ce.alloc((size_t)n_pairs * T * 10));
+  HIP_TRY(ctx, ws.cn.alloc((size_t)n_pairs * T));
+  {
+    KTimer tm(ctx, "pose_e5_hyp");
+    hipLaunchKernelGGL(k_e5_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, seed,
+                       ws.cE.p, ws.cn.p);
+  }
+  {
+    KTimer tm(ctx, "pose_e5_score");
+    hipLaunchKernelGGL(k_e5_score, dim3(cdiv(T * 10, 256), n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, ws.cE.p,
+                       ws.cn.p, ws.ce.p);
+  }
+  {
+    KTimer tm(ctx, "pose_e5_select");
+    hipLaunchKernelGGL(k_e5_select, dim3(n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, ws.cE.p, ws.cn.p, ws.ce.p, dE,
+                       dR, dt, d_ok, d_ncand);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return MSFM_OK;
+}
+
 MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const double* pts_ref, const double* pts_cur,
                                     const double* f_ref, const double* f_cur, int ransac_times, uint64_t seed, double* E, double* R, double* t,
                                     uint8_t* ok, int* n_candidates) {
@@ -1651,10 +1678,10 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int T = ransac_times;
-  DevBuf<int> d_off, d_cn, d_nc;
-  DevBuf<double> d_a, d_b, d_f1, d_f2, d_cE, d_ce, d_E, d_R, d_t;
+  DevBuf<int> d_off, d_nc;
+  DevBuf<double> d_a, d_b, d_f1, d_f2, d_E, d_R, d_t;
   DevBuf<uint8_t> d_ok;
+  Relpose5Scratch ws;
   HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
   HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
@@ -1663,33 +1690,40 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   HIP_TRY(ctx, d_b.upload(pts_cur, 2 * (size_t)total, s));
   HIP_TRY(ctx, d_f1.alloc(n_pairs)); HIP_TRY(ctx, d_f1.upload(f_ref, n_pairs, s));
   HIP_TRY(ctx, d_f2.alloc(n_pairs)); HIP_TRY(ctx, d_f2.upload(f_cur, n_pairs, s));
-  HIP_TRY(ctx, d_cE.alloc((size_t)n_pairs * T * 90));
-  HIP_TRY(ctx, d_ce.alloc((size_t)n_pairs * T * 10));
-  HIP_TRY(ctx, d_cn.alloc((size_t)n_pairs * T));
   HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs));
   HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
-  {
-    KTimer tm(ctx, "pose_e5_hyp");
-    hipLaunchKernelGGL(k_e5_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, seed,
-                       d_cE.p, d_cn.p);
-  }
-  {
-    KTimer tm(ctx, "pose_e5_score");
-    hipLaunchKernelGGL(k_e5_score, dim3(cdiv(T * 10, 256), n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, d_cE.p,
-                       d_cn.p, d_ce.p);
-  }
-  {
-    KTimer tm(ctx, "pose_e5_select");
-    hipLaunchKernelGGL(k_e5_select, dim3(n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, d_cE.p, d_cn.p, d_ce.p, d_E.p,
-                       d_R.p, d_t.p, d_ok.p, d_nc.p);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  MSFM_TRY(pose_relpose5_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, ransac_times, seed, ws, d_E.p, d_R.p, d_t.p, d_ok.p, d_nc.p));
   HIP_TRY(ctx, hipMemcpyAsync(E, d_E.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   if (n_candidates) HIP_TRY(ctx, hipMemcpyAsync(n_candidates, d_nc.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
+  return MSFM_OK;
+}
+
+int pose_relpose8_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, int ransac_times,
+                      uint64_t seed, Relpose8Scratch& ws, double* dF, double* d_f_ref, double* d_f_cur, double* dE, double* dR, double* dt,
+                      uint8_t* d_ok, int* d_best_iter, double* d_best_error, int* d_ncand) {
+  hipStream_t s = ctx->stream;
+  const int T = ransac_times;
+  HIP_TRY(ctx, ws.cF.alloc((size_t)n_pairs * T * 9));
+  HIP_TRY(ctx, ws.ce.alloc((size_t)n_pairs * T));
+  HIP_TRY(ctx, ws.cok.alloc((size_t)n_pairs * T));
+  {
+    KTimer tm(ctx, "pose_f8_hyp");
+    hipLaunchKernelGGL(k_f8_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off, d_ref, d_cur, seed, ws.cF.p, ws.cok.p);
+  }
+  {
+    KTimer tm(ctx, "pose_f8_score");
+    hipLaunchKernelGGL(k_f8_score, dim3(T, n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, ws.cF.p, ws.cok.p, ws.ce.p);
+  }
+  {
+    KTimer tm(ctx, "pose_f8_select");
+    hipLaunchKernelGGL(k_f8_select, dim3(n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, ws.cF.p, ws.cok.p, ws.ce.p, dF, d_f_ref, d_f_cur,
+                       dE, dR, dt, d_ok, d_best_iter, d_best_error, d_ncand);
+  }
+  HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
 }
 
@@ -1705,36 +1739,21 @@ MSFM_API int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  const int T = ransac_times;
   DevBuf<int> d_off, d_bi, d_nc;
-  DevBuf<double> d_a, d_b, d_cF, d_ce, d_F, d_f1, d_f2, d_E, d_R, d_t, d_be;
-  DevBuf<uint8_t> d_cok, d_ok;
+  DevBuf<double> d_a, d_b, d_F, d_f1, d_f2, d_E, d_R, d_t, d_be;
+  DevBuf<uint8_t> d_ok;
+  Relpose8Scratch ws;
   HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
   HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
   HIP_TRY(ctx, d_b.alloc(2 * (size_t)std::max(1, total)));
   HIP_TRY(ctx, d_a.upload(pts_ref, 2 * (size_t)total, s));
   HIP_TRY(ctx, d_b.upload(pts_cur, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_cF.alloc((size_t)n_pairs * T * 9));
-  HIP_TRY(ctx, d_ce.alloc((size_t)n_pairs * T));
-  HIP_TRY(ctx, d_cok.alloc((size_t)n_pairs * T));
   HIP_TRY(ctx, d_F.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs));
   HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs)); HIP_TRY(ctx, d_f1.alloc(n_pairs)); HIP_TRY(ctx, d_f2.alloc(n_pairs));
   HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_bi.alloc(n_pairs)); HIP_TRY(ctx, d_be.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
-  {
-    KTimer tm(ctx, "pose_f8_hyp");
-    hipLaunchKernelGGL(k_f8_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off.p, d_a.p, d_b.p, seed, d_cF.p, d_cok.p);
-  }
-  {
-    KTimer tm(ctx, "pose_f8_score");
-    hipLaunchKernelGGL(k_f8_score, dim3(T, n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_cF.p, d_cok.p, d_ce.p);
-  }
-  {
-    KTimer tm(ctx, "pose_f8_select");
-    hipLaunchKernelGGL(k_f8_select, dim3(n_pairs), dim3(256), 0, s, T, d_off.p, d_a.p, d_b.p, d_cF.p, d_cok.p, d_ce.p, d_F.p, d_f1.p, d_f2.p,
-                       d_E.p, d_R.p, d_t.p, d_ok.p, d_bi.p, d_be.p, d_nc.p);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  MSFM_TRY(pose_relpose8_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, ransac_times, seed, ws, d_F.p, d_f1.p, d_f2.p, d_E.p, d_R.p, d_t.p, d_ok.p, d_bi.p,
+                             d_be.p, d_nc.p));
   HIP_TRY(ctx, hipMemcpyAsync(F, d_F.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(f_ref, d_f1.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(f_cur, d_f2.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
