@@ -790,6 +790,126 @@ void IncrementalSfM::FindImageToLocalizeHost(std::vector<int>& image_ids, std::v
   image_ids = ids_sort; corres_2d3d = corres_sort; visible_cams = visible_sort;
 }
 
+// ---- IncrementalSfM: the new points of the image just localised -------------------------------------
+// sfm_incremental.cc:755-915.  The flat state of cams_ / pts_ (as FindImageToLocalize gathers it, plus the poses), one
+// msfm_new_points call for the newest camera against its visible_cams_, then :899-910 on the answer.
+void IncrementalSfM::GenerateNew3DPoints() {
+  if (!store_) throw std::runtime_error("GenerateNew3DPoints: SetMatches first");
+  if (cams_.empty()) throw std::runtime_error("GenerateNew3DPoints: no camera");
+  size_t rows = 0;
+  std::vector<size_t> first(graph_.n_features.size() + 1, 0);
+  for (size_t i = 0; i < graph_.n_features.size(); i++) { rows += graph_.n_features[i]; first[i + 1] = rows; }
+  if (keypoints_.size() != 2 * rows) throw std::runtime_error("GenerateNew3DPoints: SetKeypoints first");
+  const int idx_cam_1 = (int)cams_.size() - 1;
+  const int id_img_1 = cams_[idx_cam_1]->id_img_;
+  std::vector<int> cam_img(cams_.size()), feat_point;
+  std::vector<double> R, t, c, fk;
+  for (size_t k = 0; k < cams_.size(); k++) {
+    const Camera* cm = cams_[k];
+    const int img = cm->id_img_, nf = graph_.n_features[img];
+    cam_img[k] = img;
+    const size_t at = feat_point.size();
+    feat_point.resize(at + nf, -1);
+    for (auto& kv : cm->pts_) {   // pts_.find(id) != pts_.end(), :804-805: whatever the point's state
+      const long local = (long)kv.first - (long)options_.idx_max_per_image * img;
+      if (local >= 0 && local < nf) feat_point[at + local] = std::max(0, kv.second->id_);
+    }
+    for (int q = 0; q < 9; q++) R.push_back(cm->pos_rt_.R.m[q]);
+    for (int q = 0; q < 3; q++) { t.push_back(cm->pos_rt_.t[q]); c.push_back(cm->pos_ac_.c[q]); }
+    fk.push_back(cm->cam_model_->f_); fk.push_back(cm->cam_model_->k1_); fk.push_back(cm->cam_model_->k2_);
+  }
+  const std::vector<int>& visible = cams_[idx_cam_1]->visible_cams_;
+  const int vis_off[2] = {0, (int)visible.size()};
+  msfm_new_points_options o;
+  msfm_new_points_default_options(&o);
+  o.th_mse_reprojection = options_.th_mse_reprojection; o.th_angle_small = options_.th_angle_small; o.th_angle_large = options_.th_angle_large;
+  msfm_new_points_problem P{};
+  P.n_cams = (int)cams_.size(); P.cam_img = cam_img.data(); P.feat_point = feat_point.data(); P.n_points = (int)pts_.size();
+  P.cam_R = R.data(); P.cam_t = t.data(); P.cam_c = c.data(); P.cam_fk = fk.data();
+  P.n_new = 1; P.new_cam = &idx_cam_1; P.vis_off = vis_off; P.vis_cam = visible.data(); P.keypoints = keypoints_.data();
+  msfm_new_points_set* set = nullptr;
+  check(msfm_new_points(Context(), store_.get(), &P, &o, &set), "msfm_new_points");
+  int n = 0;
+  msfm_new_points_set_size(set, nullptr, &n, nullptr, nullptr);
+  std::vector<int> cam2(n), f1(n), f2(n);
+  std::vector<double> X(3 * (size_t)n), mse(n);
+  std::vector<uint8_t> takes1(n), takes2(n);
+  msfm_new_points_set_fetch(set, nullptr, cam2.data(), f1.data(), f2.data(), nullptr, nullptr, X.data(), mse.data(), takes1.data(), takes2.data(),
+                            nullptr, nullptr, nullptr, nullptr);
+  msfm_new_points_set_destroy(set);
+  for (int i = 0; i < n; i++) {   // :899-910
+    const int idx_cam_2 = cam2[i], id_img_2 = cams_[idx_cam_2]->id_img_;
+    const int id_pt1_global = f1[i] + id_img_1 * options_.idx_max_per_image, id_pt2_global = f2[i] + id_img_2 * options_.idx_max_per_image;
+    const size_t r1 = first[id_img_1] + f1[i], r2 = first[id_img_2] + f2[i];
+    Point3D* pt = new Point3D;
+    pt->AddObservation(cams_[idx_cam_1], keypoints_[2 * r1], keypoints_[2 * r1 + 1], id_pt1_global);
+    pt->AddObservation(cams_[idx_cam_2], keypoints_[2 * r2], keypoints_[2 * r2 + 1], id_pt2_global);
+    pt->is_new_added_ = true;
+    for (int q = 0; q < 3; q++) pt->data[q] = X[3 * (size_t)i + q];
+    pt->mse_ = mse[i];
+    pt->id_ = (int)pts_.size();
+    pts_.push_back(pt);
+    cams_[idx_cam_1]->AddPoints(pt, id_pt1_global);
+    cams_[idx_cam_2]->AddPoints(pt, id_pt2_global);
+    // the library's claims are these two inserts
+    if ((cams_[idx_cam_1]->pts_[id_pt1_global] == pt) != (takes1[i] != 0) || (cams_[idx_cam_2]->pts_[id_pt2_global] == pt) != (takes2[i] != 0))
+      throw std::runtime_error("GenerateNew3DPoints: takes1 / takes2 disagree with Camera::AddPoints");
+  }
+  num_new_points_ = n;
+}
+
+// The same function as the reference writes it, over the matches and keypoints in memory.
+void IncrementalSfM::GenerateNew3DPointsHost() {
+  if (cams_.empty()) throw std::runtime_error("GenerateNew3DPointsHost: no camera");
+  std::vector<size_t> first(graph_.n_features.size() + 1, 0);
+  for (size_t i = 0; i < graph_.n_features.size(); i++) first[i + 1] = first[i] + graph_.n_features[i];
+  if (keypoints_.size() != 2 * first.back()) throw std::runtime_error("GenerateNew3DPointsHost: SetKeypoints first");
+  std::map<std::pair<int, int>, int> pair_at;   // "QueryMatch(i, j)" on the lists in memory
+  for (int p = 0; p < (int)graph_.pair_img.size() / 2; p++) pair_at[std::make_pair(graph_.pair_img[2 * p], graph_.pair_img[2 * p + 1])] = p;
+  struct Point3DNew { Point3D* pt; int id_cam1, id_cam2, id_pt1, id_pt2; };
+  const int idx_cam_1 = (int)cams_.size() - 1;
+  const int id_img_1 = cams_[idx_cam_1]->id_img_;
+  std::vector<std::pair<Point3DNew, int>> pts_new;
+  for (size_t i = 0; i < cams_[idx_cam_1]->visible_cams_.size(); i++) {
+    const int idx_cam_2 = cams_[idx_cam_1]->visible_cams_[i];
+    if (idx_cam_2 == idx_cam_1) continue;
+    const int id_img_2 = cams_[idx_cam_2]->id_img_;
+    auto pit = pair_at.find(std::make_pair(id_img_1, id_img_2));
+    if (pit == pair_at.end()) continue;
+    const int m0 = graph_.match_off[pit->second], cnt = graph_.match_off[pit->second + 1] - m0;
+    double th_tri_angle = options_.th_angle_small;   // :780-784
+    if (cnt > 500) th_tri_angle = options_.th_angle_large;
+    for (int j = 0; j < cnt; j++) {
+      const int id_pt1_local = graph_.matches[2 * (size_t)(m0 + j)], id_pt2_local = graph_.matches[2 * (size_t)(m0 + j) + 1];
+      const int id_pt1_global = id_pt1_local + id_img_1 * options_.idx_max_per_image;
+      const int id_pt2_global = id_pt2_local + id_img_2 * options_.idx_max_per_image;
+      if (cams_[idx_cam_1]->pts_.find(id_pt1_global) != cams_[idx_cam_1]->pts_.end() ||
+          cams_[idx_cam_2]->pts_.find(id_pt2_global) != cams_[idx_cam_2]->pts_.end())
+        continue;
+      const size_t r1 = first[id_img_1] + id_pt1_local, r2 = first[id_img_2] + id_pt2_local;
+      Point3D* pt_temp = new Point3D;
+      pt_temp->AddObservation(cams_[idx_cam_1], keypoints_[2 * r1], keypoints_[2 * r1 + 1], id_pt1_global);
+      pt_temp->AddObservation(cams_[idx_cam_2], keypoints_[2 * r2], keypoints_[2 * r2 + 1], id_pt2_global);
+      pt_temp->is_new_added_ = true;
+      if (pt_temp->Trianglate2(options_.th_mse_reprojection, th_tri_angle))   // :821, one call per candidate
+        pts_new.push_back(std::make_pair(Point3DNew{pt_temp, idx_cam_1, idx_cam_2, id_pt1_global, id_pt2_global}, (int)pt_temp->mse_));   // :829
+      else
+        delete pt_temp;
+    }
+  }
+  // :897 - std::sort leaves ties open; here, as in msfm_new_points, they keep the order of the walk
+  std::stable_sort(pts_new.begin(), pts_new.end(),
+                   [](const std::pair<Point3DNew, int>& lhs, const std::pair<Point3DNew, int>& rhs) { return lhs.second < rhs.second; });
+  for (size_t i = 0; i < pts_new.size(); i++) {
+    const Point3DNew& p = pts_new[i].first;
+    p.pt->id_ = (int)pts_.size();
+    pts_.push_back(p.pt);
+    cams_[p.id_cam1]->AddPoints(p.pt, p.id_pt1);
+    cams_[p.id_cam2]->AddPoints(p.pt, p.id_pt2);
+  }
+  num_new_points_ = (int)pts_new.size();
+}
+
 void SLAMGPS::FullBundleAdjustment() {
   // slam_gps.cc:690-712 adds ReprojectionErrorPoseCamXYZ for every observation of every non-bad point with the point's
   // own weight: everything is free, and the weight rule of BundleAdjuster does not apply

@@ -121,8 +121,8 @@ msfm_ctx* Context();
 // Call before the first GPU call.  Matching, triangulation / reprojection and the bundle adjustment then split inside the library.
 void UseGpus(int n_gpus, bool share_device_0 = false);
 
-// Batched forms the pipeline should prefer (IncrementalSfM::GenerateNew3DPoints /
-// RemovePointOutliers, sfm_incremental.cc:755-915,1831-1863): one kernel launch for all points.
+// Batched forms the pipeline should prefer (RemovePointOutliers, sfm_incremental.cc:1831-1863; GenerateNew3DPoints has its
+// own call, IncrementalSfM::GenerateNew3DPoints below): one kernel launch for all points.
 void TrianglateBatch(const std::vector<Point3D*>& pts, double th_error, double th_angle, bool dlt, std::vector<char>* ok);
 void ReprojectionBatch(const std::vector<Point3D*>& pts);
 
@@ -163,6 +163,7 @@ struct IncrementalSfMOptions {       // basic_structs.h:147-227, the fields this
   double th_mse_reprojection = 3.0;      // basic_structs.h:187
   double th_angle_small = 3.0 / 180.0 * 3.1415;   // basic_structs.h:190
   int th_seedpair_structures = 20;       // basic_structs.h:174
+  double th_angle_large = 5.0 / 180.0 * 3.1415;   // basic_structs.h:191
 };
 // What FindImageToLocalize reads of Graph (SfM/src/graph/graph.h): match_graph_ and the verified match lists - here in memory
 // in the flat layout of msfm_match_store_create instead of behind Graph::QueryMatch's `<i>_match` files (graph.cc:92-137).
@@ -208,6 +209,17 @@ class IncrementalSfM {
   // i % seed_chunk_ behind empty problems, so it draws the samples the batched call draws: same poses bit for bit, points
   // to the 1e-9 by which msfm_triangulate_midpoint_batch differs.  What scripts/seed_bench.py times the batched call against.
   bool FindSeedPairThenReconstructHost();
+  // sfm_incremental.cc:755-915 for the newest camera (cams_.size() - 1) and its visible_cams_: the flat state gathered from
+  // cams_ / pts_, one msfm_new_points call on the resident store, then the points appended in the call's order - two
+  // observations, is_new_added_, id, Camera::AddPoints (:899-910).  Needs SetMatches and SetKeypoints.  std::sort's ties (:897)
+  // keep the order of the walk.  The call is always handed keypoints_, so the keypoint rows of the involved images are
+  // uploaded every time, also when the store came from a chain and holds them (the appended observations need keypoints_ anyway).
+  void GenerateNew3DPoints();
+  // The same function as the reference writes it: one Point3D::Trianglate2 per candidate (a library call each), the same tie
+  // rule.  Same points, order and inserts, coordinates to the 1e-9 by which msfm_triangulate_midpoint_batch differs.  What
+  // scripts/newpoints_bench.py times the batched call against, and a second opinion for tests/newpoints_host_check.cc.
+  void GenerateNew3DPointsHost();
+  int num_new_points_ = 0;                   // points the last of the two appended
   void SetKeypoints(const std::vector<float>& keypoints) { keypoints_ = keypoints; }   // [sum of n_features][2], images in order
   std::vector<float> keypoints_;
   std::vector<double> image_focal_;          // per image: f of its camera model in pixels, 0.0 = unknown (CameraModel::f_)

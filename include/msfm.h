@@ -758,6 +758,79 @@ int msfm_seed_set_fetch(const msfm_seed_set* set, uint8_t* arm, uint8_t* pose_ok
                         double* R /*[n][9]*/, double* t, double* c, int* pt_off /*[n+1]*/, int* pt_match, double* X, double* mse);
 void msfm_seed_set_destroy(msfm_seed_set* set);
 
+/* ======================================================================================
+ *  The new 3D points of a localised image: every match with a visible camera in one call
+ * ====================================================================================== */
+/* IncrementalSfM::GenerateNew3DPoints (SfM/src/sfm_incremental.cc:755-915) on the resident match store, for a list of new
+ * cameras at once.  The reference's case is n_new = 1 (the camera just localised); each new camera c1 (image i1) is answered
+ * independently against the handed state - its rows do not depend on which other new cameras are in the call - and the host
+ * decides how to apply several.  Per new camera:
+ *   walk       its visible cameras in listed order, duplicates included (:766-894); c2 == c1 is skipped (:769); the matches
+ *              are QueryMatch(i1, i2) = store row i1, entry i2, in stored order (:777); a pair the store does not hold has 0
+ *              matches.  A skipped or empty entry keeps its place in the per-entry outputs.
+ *   angle      th_angle_large when the pair's match count (all matches, before any filter) is > th_matches_large, else
+ *              th_angle_small (:780-784); the cosine of both is formed once on the host with the C library
+ *   candidate  match (f1, f2) is one when feat_point[c1][f1] < 0 and feat_point[c2][f2] < 0 (:804-808): only `>= 0` is read of
+ *              feat_point, which stands for cams_[c]->pts_.find(..) != end() and does not depend on is_bad_estimated_.  The
+ *              state does not change during the walk: a feature that occurs in several matches, within a pair or across
+ *              visible cameras, yields a candidate in each.  Kept as the reference has it.
+ *   point      a two-view Point3D::Trianglate2(th_mse_reprojection, th_angle) with c1's observation first, keypoints float ->
+ *              double (:810-821): the arithmetic of msfm_seed_hypotheses' points - no fused multiply-adds, + - * / sqrt only,
+ *              so a CPU restatement built with -ffp-contract=off agrees bit for bit and msfm_triangulate_midpoint_batch to
+ *              1e-9.  A failed LLT, sqrt(mse) > th_mse_reprojection or an insufficient angle: not accepted.  The 100000.0 of
+ *              a point behind a camera (structure.cc:280-284) is an mse like any other.  Poses and models must be finite:
+ *              an accepted point whose mse is NaN has no key in the reference ((int)NaN is undefined); here it sorts first.
+ *   order      ascending by mse TRUNCATED to int - the reference stores it through std::pair<Point3DNew*, int> (:829, :897).
+ *              std::sort leaves ties open; here ties keep the order of the walk (a stable sort).
+ *   claims     in that order every point is appended to pts_ (its id is n_points + its position), and Camera::AddPoints is
+ *              std::map::insert (:908-909): the first point that names (c1, f1) takes that slot of camera c1, later ones do
+ *              not; the same for (c2, f2).  takes1 / takes2 say which inserts took: what a host that rebuilds feat_point needs.
+ * In : n_cams, cam_img, feat_point, n_points as in msfm_localize_problem (feat_point: camera c starts at the sum of
+ *      n_features[cam_img[c']] over c' < c; n_points = pts_.size(), the id base); cam_R [n_cams][9], cam_t, cam_c, cam_fk
+ *      [n_cams][3] as in msfm_tracks; new_cam [n_new] camera indices; vis_off [n_new+1], vis_cam: each new camera's
+ *      visible_cams_ as listed.  keypoints (optional): float [sum of n_features][2] in image order; without it the store
+ *      must hold the keypoints of the involved images (made from a chain).
+ * Per call the host sends the feat_point and pose rows of the involved cameras (the new ones and their visible ones), for a
+ * host-made store those images' keypoint rows, and a few integers per visible entry: nothing that scales with the store's
+ * matches.  h2d_bytes of msfm_new_points_set_size reports it.  One stream synchronisation, at the end; the set is host memory.
+ * MSFM_E_INVAL: n_new outside [0, 65535], a camera index outside n_cams, a cam_img outside the store or listed twice, no
+ * keypoints for an involved image, a NaN threshold, th_mse_reprojection negative or >= 46340 (the key is an int of a value
+ * up to its square), th_matches_large < 0, vis_off not ascending from 0.  The context stays usable.
+ * msfm_new_points_set_fetch (every pointer may be NULL): pt_off [n_new+1]; per point e of new camera k (pt_off[k] <= e <
+ * pt_off[k+1], id n_points + e - pt_off[k]) in sorted order: cam2 (camera index), feat1, feat2 (local features), vis_entry
+ * (index into that camera's visible list), pt_match (index into the pair's matches), X [..][3], mse, takes1, takes2; per
+ * visible entry (vis_off's indexing): n_matches, large (1: th_angle_large applied), n_candidates, n_accepted. */
+typedef struct msfm_new_points_options {   /* msfm_new_points_default_options fills the reference's values */
+  double th_mse_reprojection;              /* 3.0                  basic_structs.h:187 */
+  double th_angle_small;                   /* 3.0 / 180.0 * 3.1415 basic_structs.h:190, radians */
+  double th_angle_large;                   /* 5.0 / 180.0 * 3.1415 basic_structs.h:191 */
+  int32_t th_matches_large;                /* 500                  sfm_incremental.cc:781 */
+} msfm_new_points_options;
+void msfm_new_points_default_options(msfm_new_points_options* opt);
+typedef struct msfm_new_points_problem {
+  int32_t n_cams;
+  const int32_t* cam_img;
+  const int32_t* feat_point;
+  int32_t n_points;
+  const double* cam_R;
+  const double* cam_t;
+  const double* cam_c;
+  const double* cam_fk;
+  int32_t n_new;                           /* <= 65535 */
+  const int32_t* new_cam;
+  const int32_t* vis_off;
+  const int32_t* vis_cam;
+  const float* keypoints;                  /* optional */
+} msfm_new_points_problem;
+typedef struct msfm_new_points_set msfm_new_points_set;
+int msfm_new_points(msfm_ctx* ctx, const msfm_match_store* store, const msfm_new_points_problem* problem,
+                    const msfm_new_points_options* opt, msfm_new_points_set** out);
+int msfm_new_points_set_size(const msfm_new_points_set* set, int* n_new, int* n_points, int* n_entries, int64_t* h2d_bytes);
+int msfm_new_points_set_fetch(const msfm_new_points_set* set, int* pt_off /*[n_new+1]*/, int* cam2, int* feat1, int* feat2, int* vis_entry,
+                              int* pt_match, double* X, double* mse, uint8_t* takes1, uint8_t* takes2, int* n_matches /*[n_entries]*/,
+                              uint8_t* large, int* n_candidates, int* n_accepted);
+void msfm_new_points_set_destroy(msfm_new_points_set* set);
+
 /* ==================================================================================== *
  *  Single-process multi-GPU context
  * ==================================================================================== */

@@ -123,6 +123,19 @@ class SeedProblem(C.Structure):
     _fields_ = [("n_hyp", C.c_int32), ("hyp_img", c_int_p), ("cam_fk", c_double_p), ("same_model", c_u8_p), ("keypoints", c_float_p)]
 
 
+class NewPointsOptions(C.Structure):
+    """msfm_new_points_options (include/msfm.h)."""
+    _fields_ = [("th_mse_reprojection", C.c_double), ("th_angle_small", C.c_double), ("th_angle_large", C.c_double),
+                ("th_matches_large", C.c_int32)]
+
+
+class NewPointsProblem(C.Structure):
+    """msfm_new_points_problem (include/msfm.h)."""
+    _fields_ = [("n_cams", C.c_int32), ("cam_img", c_int_p), ("feat_point", c_int_p), ("n_points", C.c_int32), ("cam_R", c_double_p),
+                ("cam_t", c_double_p), ("cam_c", c_double_p), ("cam_fk", c_double_p), ("n_new", C.c_int32), ("new_cam", c_int_p),
+                ("vis_off", c_int_p), ("vis_cam", c_int_p), ("keypoints", c_float_p)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

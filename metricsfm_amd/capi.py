@@ -26,6 +26,7 @@ SYMBOLS = [
     "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
     "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
     "msfm_seed_default_options", "msfm_seed_hypotheses", "msfm_seed_set_size", "msfm_seed_set_fetch", "msfm_seed_set_destroy",
+    "msfm_new_points_default_options", "msfm_new_points", "msfm_new_points_set_size", "msfm_new_points_set_fetch", "msfm_new_points_set_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
@@ -163,6 +164,14 @@ def lib():
                                       A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
     L.msfm_seed_set_destroy.argtypes = [vp]
     L.msfm_seed_set_destroy.restype = None
+    L.msfm_new_points_default_options.argtypes = [C.POINTER(A.NewPointsOptions)]
+    L.msfm_new_points_default_options.restype = None
+    L.msfm_new_points.argtypes = [vp, vp, C.POINTER(A.NewPointsProblem), C.POINTER(A.NewPointsOptions), C.POINTER(vp)]
+    L.msfm_new_points_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
+    L.msfm_new_points_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p,
+                                            A.c_u8_p, A.c_u8_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p]
+    L.msfm_new_points_set_destroy.argtypes = [vp]
+    L.msfm_new_points_set_destroy.restype = None
     L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
     L.msfm_multi_destroy.argtypes = [vp]
     L.msfm_multi_destroy.restype = None
@@ -205,6 +214,17 @@ def seed_options(**kw):
     """msfm_seed_options with the reference's values (3.0 px, 3 degrees, 20 points, 100 / 200 samples); keywords override fields."""
     o = A.SeedOptions()
     lib().msfm_seed_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def new_points_options(**kw):
+    """msfm_new_points_options with the reference's values (3.0 px, 3 and 5 degrees, 500 matches); keywords override fields."""
+    o = A.NewPointsOptions()
+    lib().msfm_new_points_default_options(C.byref(o))
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
@@ -505,6 +525,53 @@ class Context:
             lib().msfm_seed_set_destroy(h)
         return {"arm": arm[:n], "pose_ok": pok[:n], "pass": pas[:n], "n_matches": nm[:n], "f": f[:n], "R": R[:n], "t": t[:n], "c": c[:n],
                 "pt_off": poff, "pt_match": ptm[:npt], "X": X[:npt], "mse": mse[:npt], "winner": win.value, "h2d_bytes": nb.value}
+
+    def new_points(self, store, cam_img, feat_point, n_points, cam_R, cam_t, cam_c, cam_fk, new_cam, vis_off, vis_cam, keypoints=None, **opts):
+        """msfm_new_points (sfm_incremental.cc:755-915): the new two-view points of every new camera against its visible cameras,
+        on the resident store.  cam_img [n_cams], feat_point (flat, one entry per feature of every camera's image, -1 = no
+        point), cam_R [n][3][3], cam_t / cam_c / cam_fk [n][3], new_cam [n_new], vis_off [n_new+1], vis_cam; opts: fields of
+        msfm_new_points_options.  Returns a dict: pt_off [n_new+1]; per point cam2, feat1, feat2, vis_entry, pt_match, X [..][3],
+        mse, takes1, takes2; per visible entry n_matches, large, n_candidates, n_accepted; h2d_bytes."""
+        cam_img, feat_point, new_cam, vis_off, vis_cam = (A.as_c(np.asarray(x, dtype=np.int32).reshape(-1), np.int32)
+                                                          for x in (cam_img, feat_point, new_cam, vis_off, vis_cam))
+        nc, nn = len(cam_img), len(new_cam)
+        R = A.as_c(np.asarray(cam_R, dtype=np.float64).reshape(-1, 9), np.float64)
+        t, c, fk = (A.as_c(np.asarray(x, dtype=np.float64).reshape(-1, 3), np.float64) for x in (cam_t, cam_c, cam_fk))
+        if not (len(R) == len(t) == len(c) == len(fk) == nc):
+            raise ValueError("cam_img, cam_R, cam_t, cam_c and cam_fk must describe the same number of cameras")
+        if len(vis_off) != nn + 1:
+            raise ValueError("vis_off must hold n_new + 1 offsets")
+        if nn and 0 <= vis_off[-1] and len(vis_cam) != vis_off[-1]:
+            raise ValueError("vis_cam must hold vis_off[n_new] entries")
+        in_store = (cam_img >= 0) & (cam_img < len(store.n_features))     # (an image outside the store: the library reports it)
+        if in_store.all() and len(feat_point) != int(store.n_features[cam_img].sum()):
+            raise ValueError("feat_point must hold one entry per feature of every camera's image")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        dp, ip, up = A.c_double_p, A.c_int_p, A.c_u8_p
+        P = A.NewPointsProblem(nc, A.ptr(cam_img, ip), A.ptr(feat_point, ip), int(n_points), A.ptr(R, dp), A.ptr(t, dp), A.ptr(c, dp),
+                               A.ptr(fk, dp), nn, A.ptr(new_cam, ip), A.ptr(vis_off, ip), A.ptr(vis_cam, ip), A.ptr(kp, A.c_float_p))
+        o = new_points_options(**opts)
+        h = C.c_void_p()
+        self.check(lib().msfm_new_points(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
+        try:
+            n1, npt, ne, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+            lib().msfm_new_points_set_size(h, C.byref(n1), C.byref(npt), C.byref(ne), C.byref(nb))
+            npt, ne = npt.value, ne.value
+            m, e = max(1, npt), max(1, ne)
+            poff = np.zeros(nn + 1, np.int32)
+            cam2, f1, f2, ve, ptm = (np.zeros(m, np.int32) for _ in range(5))
+            X, mse, t1, t2 = np.zeros((m, 3)), np.zeros(m), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+            nm, ncand, nacc, large = np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.uint8)
+            lib().msfm_new_points_set_fetch(h, A.ptr(poff, ip), A.ptr(cam2, ip), A.ptr(f1, ip), A.ptr(f2, ip), A.ptr(ve, ip), A.ptr(ptm, ip),
+                                            A.ptr(X, dp), A.ptr(mse, dp), A.ptr(t1, up), A.ptr(t2, up), A.ptr(nm, ip), A.ptr(large, up),
+                                            A.ptr(ncand, ip), A.ptr(nacc, ip))
+        finally:
+            lib().msfm_new_points_set_destroy(h)
+        return {"pt_off": poff, "cam2": cam2[:npt], "feat1": f1[:npt], "feat2": f2[:npt], "vis_entry": ve[:npt], "pt_match": ptm[:npt],
+                "X": X[:npt], "mse": mse[:npt], "takes1": t1[:npt], "takes2": t2[:npt], "n_matches": nm[:ne], "large": large[:ne],
+                "n_candidates": ncand[:ne], "n_accepted": nacc[:ne], "h2d_bytes": nb.value}
 
     def triangulate_midpoint(self, tracks, th_error, th_angle, X0=None):
         return self._tri(lib().msfm_triangulate_midpoint_batch, tracks, th_error, th_angle, X0)
