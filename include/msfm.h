@@ -296,9 +296,12 @@ typedef struct msfm_ba_layout {
    * substitution as one k_backsolve_chain launch; a clear bit = one launch per 64-column panel / block pair */
   int solve_paths;
   /* eliminated points by track length class (msfm_ba_create orders them class-major): up to 8 rows, 9..16 rows, more.  The
-   * point kernels give a point of the first class 8 lanes, of the second 16 - one row per lane - and take the rows of the
-   * third in rounds of 8; a workgroup never mixes classes */
+   * point kernels give a point of up to 4 rows 4 lanes, of 5..8 rows 8 lanes, of 9..16 rows 16 - one row per lane - and take
+   * the rows of longer tracks in rounds of 8; a workgroup never mixes lane widths.  npb_S counts every point of up to 8
+   * rows; npb_S4 says how many of those have up to 4 rows (they come first and have the 4 lanes when the problem has more
+   * than MSFM_LANES4_MIN eliminated points, default 24 576; in a smaller problem they are 8-lane points in the common order) */
   int npb_S, npb_L, npb_X;
+  int npb_S4;
 } msfm_ba_layout;
 #define MSFM_PATH_LEVEL_CHAIN(l) (1 << (l))
 #define MSFM_PATH_ROOT_CHAIN (1 << 3)

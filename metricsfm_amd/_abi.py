@@ -42,7 +42,7 @@ class BaLayout(C.Structure):
                 ("level_begin", C.c_int * 3), ("root_cols", C.c_int),
                 ("cc_entries", C.c_longlong), ("cc_entries_folded", C.c_longlong), ("fold_slots", C.c_int), ("fold_passes", C.c_int),
                 ("mc_entries", C.c_longlong), ("mc_entries_folded", C.c_longlong), ("fold_mc_slots", C.c_int), ("solve_paths", C.c_int),
-                ("npb_S", C.c_int), ("npb_L", C.c_int), ("npb_X", C.c_int)]
+                ("npb_S", C.c_int), ("npb_L", C.c_int), ("npb_X", C.c_int), ("npb_S4", C.c_int)]
 
 
 class FransacOptions(C.Structure):

@@ -6,7 +6,7 @@
 // of the reference's projection model, Huber(1) corrector, Jacobi column scaling; written
 // point-major SoA (for the per-point kernels) and camera-major AoS (for the per-camera sums).
 // Per linear solve:
-//   k_point      8 or 16 lanes per point, lane = observation (PtMap): V = Jp^T Jp + D^2, 3x3 Cholesky, T = (Jc^T Jp) L^-T per
+//   k_point      4, 8 or 16 lanes per point, lane = observation (PtMap): V = Jp^T Jp + D^2, 3x3 Cholesky, T = (Jc^T Jp) L^-T per
 //                observation, T.u for the right-hand side
 //   k_ftf        one wave per chunk of a camera's observations: Jc^T Jc, Jm^T Jc, Jm^T Jm, J^T r
 //   k_pairs      one wave per chunk of a (block row, block col) pair list: sum T_a T_b^T — the
@@ -285,31 +285,6 @@ __global__ __launch_bounds__(1024) void k_reduce(ReduceJobs J, double* __restric
 // (record_i | record_j << 16) - which one wave instruction per 256 words copies straight into LDS.  slot0: the first slot's
 // index in workgroup-major numbering (for its rank); n_diag: how many of the pass's slots (its first ones) are camera-diagonal.
 struct FoldPass { int off, words, slot0, n_slots, n_diag, pad0, pad1, pad2; };
-// The point workgroups of k_point and k_backsub.  msfm_ba_create orders the eliminated points by track length class first:
-// S = up to 8 rows, L = 9..16 rows, X = more.  An S workgroup holds 32 points with 8 lanes each, an L workgroup 16 points
-// with 16 lanes each - lane = row, every row is linearised exactly once - and an X workgroup 32 points with 8 lanes each that
-// take their rows in rounds of 8.  A workgroup never mixes classes (a wave that held ONE long point among short ones used to
-// run the long-track code in full for it: 4.0 linearisations per wave of k_point at config 3 where one is enough); the last
-// workgroup of a class may be partly filled.
-struct PtMap {
-  int nS, nL, nX;   // points per class: blocks [0, nS), [nS, nS + nL), [nS + nL, npb)
-  int wS, wL;       // workgroups of the first two classes (the X workgroups follow)
-};
-__host__ __device__ inline int ptmap_lanes(const PtMap& m, int w) { return w < m.wS ? 8 : w < m.wS + m.wL ? 16 : 0; }   // (0: X, rounds)
-__host__ __device__ inline int ptmap_wg_first(const PtMap& m, int w) {
-  return w < m.wS ? 32 * w : w < m.wS + m.wL ? m.nS + 16 * (w - m.wS) : m.nS + m.nL + 32 * (w - m.wS - m.wL);
-}
-__host__ __device__ inline int ptmap_wg_end(const PtMap& m, int w) {   // one past the workgroup's last point
-  const int e = ptmap_wg_first(m, w) + (ptmap_lanes(m, w) == 16 ? 16 : 32);
-  const int cap = w < m.wS ? m.nS : w < m.wS + m.wL ? m.nS + m.nL : m.nS + m.nL + m.nX;
-  return e < cap ? e : cap;
-}
-__host__ __device__ inline int ptmap_wg_of(const PtMap& m, int pb) {
-  return pb < m.nS ? pb >> 5 : pb < m.nS + m.nL ? m.wS + ((pb - m.nS) >> 4) : m.wS + m.wL + ((pb - m.nS - m.nL) >> 5);
-}
-__host__ __device__ inline int ptmap_class(int rows) { return rows <= 8 ? 0 : rows <= 16 ? 1 : 2; }
-static inline PtMap ptmap_make(int nS, int nL, int nX) { return PtMap{nS, nL, nX, (nS + 31) / 32, (nL + 15) / 16}; }
-static inline int ptmap_n_wg(const PtMap& m) { const int n = m.wS + m.wL + (m.nX + 31) / 32; return n > 0 ? n : 1; }   // (an empty launch is not one)
 struct PointPtrs {
   BaPtrs B;            // row data, parameters and scales the rows are linearised with
   PtMap map;
@@ -335,12 +310,13 @@ struct PointPtrs {
   int tu_direct;   // (MSFM_TU_DIRECT=0: T.u through the lane exchange as well)
 };
 
-// (8-lane groups; after the first two steps the four lanes of a quad hold the same value, so adding lane 7 - i is adding lane i ^ 4)
-#define GROUP_SUM8(x) { x += dpp_f64<MSFM_DPP_XOR1>(x); x += dpp_f64<MSFM_DPP_XOR2>(x); x += dpp_f64<MSFM_DPP_HALF_MIRROR>(x); }
+// (4-lane groups: the two steps inside a quad.  8-lane groups: after those the four lanes of a quad hold the same value, so adding
+//  lane 7 - i is adding lane i ^ 4 - for a point of up to 4 rows that adds +0.0, so its sums have the bits the 8-lane form gave)
+#define GROUP_SUM4(x) { x += dpp_f64<MSFM_DPP_XOR1>(x); x += dpp_f64<MSFM_DPP_XOR2>(x); }
 // (16-lane groups: the partner lane ^ 8 first - both then hold x_s + x_{s+8}, what one lane summed over two rounds of 8 - then as above)
-#define GROUP_SUM(x) { if constexpr (LPP == 16) x += dpp_f64<MSFM_DPP_ROR8>(x); GROUP_SUM8(x) }
+#define GROUP_SUM(x) { if constexpr (LPP == 16) x += dpp_f64<MSFM_DPP_ROR8>(x); GROUP_SUM4(x) if constexpr (LPP != 4) x += dpp_f64<MSFM_DPP_HALF_MIRROR>(x); }
 
-// LPP lanes per point, lane = observation: LPP = 8 and 16 in the S and L workgroups (PtMap), where every lane linearises its
+// LPP lanes per point, lane = observation: LPP = 4, 8 and 16 in the Q, S and L workgroups (PtMap), where every lane linearises its
 // own row exactly once (obs_linearize: the row data is read coalesced, the parameters come from cache) and parks it in LDS;
 // LPP = 0 in the X workgroups: 8 lanes per point, rounds of 8, and the rows are linearised again wherever they are needed.
 // The per-point sums are reductions inside the lane group, and every lane then finishes its own observation's
@@ -455,8 +431,8 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     // 0.28 -> 0.49 ms).
     // Round 3 (FoldTables): in a folding workgroup every record also stays in LDS (record-major, where the parked rows were,
     // once every lane is done with those) and the camera x camera products are formed from there below.
-    // (16 lanes per point: (point q of 4, observation s) -> lane 4 s + q)
-    const int wl = tid & 63, tsrc = GW == 16 ? ((wl & 3) << 4) | (wl >> 2) : ((wl & 7) << 3) | (wl >> 3);
+    // (16 lanes per point: (point q of 4, observation s) -> lane 4 s + q; 4 lanes per point: (point q of 16, observation s) -> lane 16 s + q)
+    const int wl = tid & 63, tsrc = GW == 16 ? ((wl & 3) << 4) | (wl >> 2) : GW == 4 ? ((wl & 15) << 2) | (wl >> 4) : ((wl & 7) << 3) | (wl >> 3);
     const bool need_T = !fold || P.fold_mc_partial == nullptr || P.keep_T;   // (uniform over the workgroup)
     auto round = [&](int rd, double (&Tk)[18], int& cpk) {
       const int i = f + rd + sub;
@@ -528,6 +504,14 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     // thread fetches its nine values with four 16-byte reads and one 8-byte read
     double* const H0 = park;
     double* const H1 = park + FOLD_NREC * 10;
+    // Tm of a point for the intrinsics x camera products of the fold phase: with 8 or 16 lanes in the spare tenth doubles of the
+    // point's first five records; a point of 4 lanes has only four records, so the Q workgroups keep the nine values of each of
+    // their 64 points in the 8 KB of the park that the record store leaves free
+    double* const TM4 = park + 2 * FOLD_NREC * 10;
+    auto tm_slot = [&](int rec0, int k) -> double* {   // (rec0: the first record of the point)
+      if constexpr (LPP == 4) return TM4 + (rec0 >> 2) * 9 + k;
+      else return ((k & 1) ? H1 : H0) + (rec0 + (k >> 1)) * 10 + 9;
+    };
     auto rec_st = [&](int rec, const double (&Tk)[18]) {
 #pragma unroll
       for (int k = 0; k < 9; k++) { H0[rec * 10 + k] = Tk[k]; H1[rec * 10 + k] = Tk[9 + k]; }
@@ -569,10 +553,10 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
             const double t2 = (W[a * 3 + 2] - l20 * t0 - l21 * t1) * i22;
             Tm[a * 3 + 0] = t0; Tm[a * 3 + 1] = t1; Tm[a * 3 + 2] = t2;
             Tmu[a] = t0 * u0 + t1 * u1 + t2 * u2;
-            if (pads) {   // into the tenth doubles of the point's first five records, for the intrinsics x camera products below
+            if (pads) {   // beside the records (tm_slot), for the intrinsics x camera products below
               const double tv[3] = {t0, t1, t2};
 #pragma unroll
-              for (int c = 0; c < 3; c++) { const int k = a * 3 + c; ((k & 1) ? H1 : H0)[(tid + (k >> 1)) * 10 + 9] = tv[c]; }
+              for (int c = 0; c < 3; c++) *tm_slot(tid, a * 3 + c) = tv[c];
             }
           }
         }
@@ -616,7 +600,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
       }
       if (fold && P.fold_mc_partial && sub == 0 && act && pe0 == pe1) {
 #pragma unroll
-        for (int k = 0; k < 9; k++) ((k & 1) ? H1 : H0)[(tid + (k >> 1)) * 10 + 9] = 0.0;
+        for (int k = 0; k < 9; k++) *tm_slot(tid, k) = 0.0;
       }
       if constexpr (!single)
         for (int rd = 8; __any(f + rd < l); rd += 8) round(rd, Tk, cpk);
@@ -679,7 +663,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
               const int r0 = (int)(pr & 0xffffu) & ~(GW - 1);   // (the first record of the point)
               double tm[6];
 #pragma unroll
-              for (int k6 = 0; k6 < 6; k6++) { const int k = 3 * ma0 + k6; tm[k6] = ((k & 1) ? H1 : H0)[(r0 + (k >> 1)) * 10 + 9]; }   // (row 3 is never used)
+              for (int k6 = 0; k6 < 6; k6++) { const int k = 3 * ma0 + k6; tm[k6] = *tm_slot(r0, k); }   // (row 3 is never used; what is read for it lies inside the park)
 #pragma unroll
               for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -721,7 +705,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   __shared__ __attribute__((aligned(16))) unsigned ent_s[FOLD_WORDS];
   if (P.spec && P.spec[0] == 0.0) return;   // enqueued ahead of a step that was not accepted
   const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
-  if (lanes == 8) k_point_body<8>(P, gmax_partial, sh, park, ent_s);
+  if (lanes == 4) k_point_body<4>(P, gmax_partial, sh, park, ent_s);
+  else if (lanes == 8) k_point_body<8>(P, gmax_partial, sh, park, ent_s);
   else if (lanes == 16) k_point_body<16>(P, gmax_partial, sh, park, ent_s);
   else k_point_body<0>(P, gmax_partial, sh, park, ent_s);
 }
@@ -1402,7 +1387,7 @@ struct BackPtrs {
   double* rot_c;
 };
 
-// The workgroups and lane groups of k_point (PtMap: LPP = 8 or 16 lanes per point, lane = observation, or rounds of 8 for
+// The workgroups and lane groups of k_point (PtMap: LPP = 4, 8 or 16 lanes per point, lane = observation, or rounds of 8 for
 // LPP = 0), single pass: besides y = sum Jp^T (r + q) with
 // q = -(Jc z_c + Jm z_m), the group accumulates the moments that give this point's model cost change
 //   -(J s)^T (r + J s / 2) = -[ sp.g + sum q.r + 1/2 sp^T V sp + sp.(sum Jp^T q) + 1/2 sum q.q ]
@@ -1494,7 +1479,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                                                   double* __restrict__ x2_partial) {
   __shared__ double sh[4];
   const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
-  if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  if (lanes == 4) k_backsub_body<4>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  else if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh);
   else if (lanes == 16) k_backsub_body<16>(P, mcc_partial, dx2_partial, x2_partial, sh);
   else k_backsub_body<0>(P, mcc_partial, dx2_partial, x2_partial, sh);
 }
@@ -1676,7 +1662,8 @@ struct msfm_ba {
   msfm_ctx* ctx = nullptr;
   int Nc = 0, Nm = 0, Np = 0;
   int ncb = 0, nmb = 0, npb = 0, nred = 0, npad = 0;
-  PtMap map = {0, 0, 0, 0, 0};   // the eliminated points by track length class, and their workgroups
+  PtMap map = {0, 0, 0, 0, 0, 0, 0};
+  int n_short4 = 0;   // points of up to 4 rows (the Q class, or the front of S where the problem is too small for it: ptmap_use_lanes4)   // the eliminated points by track length class, and their workgroups
   // solver layout of the reduced system: camera block cb at column cb_off[cb], intrinsics at mo + 3 mb, order nsys
   int nsys = 0, mo = 0, n_padcol = 0;
   msfm_env env;   // the switches as they were at msfm_ba_create (common.h)
@@ -2340,12 +2327,12 @@ __global__ __launch_bounds__(256) void k_u8_to_int(int n, const uint8_t* __restr
   if (i < n) b[i] = a[i] ? 1 : 0;
 }
 // length class of every point in key order (PtMap), and how many points each class has
-__global__ __launch_bounds__(256) void k_point_classes(int npb, const int* __restrict__ pb_pt, const int* __restrict__ cnt, int* __restrict__ cls,
+__global__ __launch_bounds__(256) void k_point_classes(int npb, int lanes4, const int* __restrict__ pb_pt, const int* __restrict__ cnt, int* __restrict__ cls,
                                                         int* __restrict__ n_class) {
   const int pb = blockIdx.x * 256 + threadIdx.x;
   if (pb >= npb) return;
   const int c = ptmap_class(cnt[pb_pt[pb]]);
-  cls[pb] = c;
+  cls[pb] = (c == 0 && !lanes4) ? 1 : c;   // (without the 4-lane class its points are S points; they are still counted)
   atomicAdd(&n_class[c], 1);
 }
 __global__ __launch_bounds__(256) void k_point_lengths(int npb, const int* __restrict__ pb_pt, const int* __restrict__ cnt, int* __restrict__ len,
@@ -2668,7 +2655,7 @@ struct PairBuild {
 namespace devsetup {
 __global__ __launch_bounds__(256) void k_fold_wg(PtMap map, int n_wg, int* __restrict__ wg_fold) {
   const int w = blockIdx.x * 256 + threadIdx.x;
-  if (w < n_wg) wg_fold[w] = ptmap_lanes(map, w) != 0;   // (record = lane: every S and L workgroup folds)
+  if (w < n_wg) wg_fold[w] = ptmap_lanes(map, w) != 0;   // (record = lane: every Q, S and L workgroup folds)
 }
 // block key of a slot: the camera-diagonal blocks first (a workgroup's diagonal slots are then its first ones, and their
 // ranks are 0 .. number of diagonal slots - 1: the index of the intrinsics x camera partials)
@@ -3175,7 +3162,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   // ---- order of the eliminated points: by length class (PtMap), then by their smallest camera blocks, ties by the caller's
   // index (two stable sorts, the minor key first) ----
   DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len, d_cls, d_cls_sorted, d_n_class;
-  int n_class[3] = {0, 0, 0};
+  int n_class[PTMAP_CLASSES] = {0, 0, 0, 0};
   DevBuf<unsigned long long> d_keys, d_keys_sorted;
   DTRY(d_pu_int.alloc((size_t)Np + 1)); DTRY(d_pu_pos.alloc((size_t)Np + 1));
   DTRY(hipMemsetAsync(d_pu_int.p + Np, 0, sizeof(int), s));
@@ -3190,10 +3177,10 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     DTRY(d_keys.alloc(npb)); DTRY(d_keys_sorted.alloc(npb)); DTRY(d_vals.alloc(npb));
     hipLaunchKernelGGL(k_point_keys, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_pos.p, d_run_first.p, d_obs_cam.p, d_cam_slot.p,
                        ncb >= 0xFFFF ? 1 : 0, d_keys.p, d_vals.p);
-    DTRY(d_vals_sorted.alloc(npb)); DTRY(d_cls.alloc(npb)); DTRY(d_cls_sorted.alloc(npb)); DTRY(d_n_class.alloc(3));
-    DTRY(hipMemsetAsync(d_n_class.p, 0, sizeof(int) * 3, s));
+    DTRY(d_vals_sorted.alloc(npb)); DTRY(d_cls.alloc(npb)); DTRY(d_cls_sorted.alloc(npb)); DTRY(d_n_class.alloc(PTMAP_CLASSES));
+    DTRY(hipMemsetAsync(d_n_class.p, 0, sizeof(int) * PTMAP_CLASSES, s));
     DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, d_vals_sorted.p, (size_t)npb, 64, s, tmp));
-    hipLaunchKernelGGL(k_point_classes, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, d_vals_sorted.p, d_cnt.p, d_cls.p, d_n_class.p);
+    hipLaunchKernelGGL(k_point_classes, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ptmap_use_lanes4(npb, ba->env.lanes4_min) ? 1 : 0, d_vals_sorted.p, d_cnt.p, d_cls.p, d_n_class.p);
     DTRY(sort_pairs(d_cls.p, d_cls_sorted.p, d_vals_sorted.p, ba->pb_pt.p, (size_t)npb, 2, s, tmp));
     DTRY(hipMemcpyAsync(n_class, d_n_class.p, sizeof n_class, hipMemcpyDeviceToHost, s));   // (read with AE below)
   }
@@ -3215,7 +3202,8 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   DTRY(hipMemcpyAsync(&AE, ba->pt_first.p + npb, sizeof(int), hipMemcpyDeviceToHost, s));
   DTRY(hipStreamSynchronize(s));
   ba->AE = AE;
-  ba->map = ptmap_make(n_class[0], n_class[1], n_class[2]);
+  ba->map = ptmap_make(n_class, ptmap_use_lanes4(npb, ba->env.lanes4_min));
+  ba->n_short4 = n_class[0];
   const int A = ba->A = AE + n_frozen_rows;
   ba->n_residuals = 2 * A + (ba->has_gps ? 3 * ncb : 0);
   lap("point order");
@@ -3427,12 +3415,16 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
     }
     if (keyed.size() == ba->h_pb_pt.size()) {
       // length class major (PtMap), the key order inside a class
-      int n_class[3] = {0, 0, 0};
+      int n_class[PTMAP_CLASSES] = {0, 0, 0, 0};
+      const bool lanes4 = ptmap_use_lanes4((int)keyed.size(), ba->env.lanes4_min);
       auto cls = [&](int p) { return ptmap_class(run_first[p + 1] - run_first[p]); };
       for (size_t i = 0; i < keyed.size(); i++) n_class[cls(keyed[i].second)]++;
-      size_t at[3] = {0, (size_t)n_class[0], (size_t)n_class[0] + n_class[1]};
-      for (size_t i = 0; i < keyed.size(); i++) ba->h_pb_pt[at[cls(keyed[i].second)]++] = keyed[i].second;
-      ba->map = ptmap_make(n_class[0], n_class[1], n_class[2]);
+      ba->n_short4 = n_class[0];
+      if (!lanes4) { n_class[1] += n_class[0]; n_class[0] = 0; }
+      size_t at[PTMAP_CLASSES] = {0};
+      for (int c = 1; c < PTMAP_CLASSES; c++) at[c] = at[c - 1] + (size_t)n_class[c - 1];
+      for (size_t i = 0; i < keyed.size(); i++) { const int c = cls(keyed[i].second); ba->h_pb_pt[at[(c == 0 && !lanes4) ? 1 : c]++] = keyed[i].second; }
+      ba->map = ptmap_make(n_class, true);
     }
     for (size_t i = 0; i < ba->h_pb_pt.size(); i++) pt_slot[ba->h_pb_pt[i]] = ba->npb++;
     HIP_TRY(ctx, ba->cb_off.from(cb_off_h.empty() ? std::vector<int>(1, 0) : cb_off_h, s));
@@ -3871,7 +3863,7 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
     if (ba->fold.mc_on) { out->mc_entries_folded = ba->fold.mc_entries_folded; out->fold_mc_slots = ba->fold.n_diag; }
   }
   out->solve_paths = ba->solve_paths;
-  out->npb_S = ba->map.nS; out->npb_L = ba->map.nL; out->npb_X = ba->map.nX;
+  out->npb_S = ba->map.nQ + ba->map.nS; out->npb_L = ba->map.nL; out->npb_X = ba->map.nX; out->npb_S4 = ba->n_short4;
   return MSFM_OK;
 }
 

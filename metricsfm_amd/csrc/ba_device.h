@@ -254,3 +254,53 @@ __device__ __forceinline__ double block_max256(double v, double* sh) {
   __syncthreads();
   return t;
 }
+
+// The point workgroups of k_point and k_backsub.  msfm_ba_create orders the eliminated points by track length class first:
+// Q = up to 4 rows, S = 5..8 rows, L = 9..16 rows, X = more.  A Q workgroup holds 64 points with 4 lanes each, an S workgroup
+// 32 points with 8 lanes each, an L workgroup 16 points with 16 lanes each - lane = row, every row is linearised exactly
+// once - and an X workgroup 32 points with 8 lanes each that take their rows in rounds of 8.  A workgroup never mixes classes
+// (a wave that held ONE long point among short ones used to run the long-track code in full for it: 4.0 linearisations per
+// wave of k_point at config 3 where one is enough); the last workgroup of a class may be partly filled.  The point kernels
+// are issue- and latency-bound FP64 at three waves per SIMD - a wave costs the same whatever the number of its live lanes -
+// so the lane width follows the track length as far as the in-row lane operations (DPP) allow.
+// (host and device, and nothing below needs the device: tests/ptmap_host_check.cc walks these functions on the CPU)
+struct PtMap {
+  int nQ, nS, nL, nX;   // points per class: blocks [0, nQ), [nQ, nQ + nS), [nQ + nS, nQ + nS + nL), [nQ + nS + nL, npb)
+  int wQ, wS, wL;       // workgroups of the first three classes (the X workgroups follow)
+};
+__host__ __device__ inline int ptmap_lanes(const PtMap& m, int w) { return w < m.wQ ? 4 : w < m.wQ + m.wS ? 8 : w < m.wQ + m.wS + m.wL ? 16 : 0; }   // (0: X, rounds)
+__host__ __device__ inline int ptmap_wg_points(int lanes) { return lanes ? 256 / lanes : 32; }   // points of a full workgroup
+__host__ __device__ inline int ptmap_wg_first(const PtMap& m, int w) {
+  if (w < m.wQ) return 64 * w;
+  w -= m.wQ;
+  if (w < m.wS) return m.nQ + 32 * w;
+  w -= m.wS;
+  if (w < m.wL) return m.nQ + m.nS + 16 * w;
+  return m.nQ + m.nS + m.nL + 32 * (w - m.wL);
+}
+__host__ __device__ inline int ptmap_wg_end(const PtMap& m, int w) {   // one past the workgroup's last point
+  const int e = ptmap_wg_first(m, w) + ptmap_wg_points(ptmap_lanes(m, w));
+  const int cap = w < m.wQ ? m.nQ : w < m.wQ + m.wS ? m.nQ + m.nS : w < m.wQ + m.wS + m.wL ? m.nQ + m.nS + m.nL : m.nQ + m.nS + m.nL + m.nX;
+  return e < cap ? e : cap;
+}
+__host__ __device__ inline int ptmap_wg_of(const PtMap& m, int pb) {
+  if (pb < m.nQ) return pb >> 6;
+  pb -= m.nQ;
+  if (pb < m.nS) return m.wQ + (pb >> 5);
+  pb -= m.nS;
+  if (pb < m.nL) return m.wQ + m.wS + (pb >> 4);
+  return m.wQ + m.wS + m.wL + ((pb - m.nL) >> 5);
+}
+#define PTMAP_CLASSES 4
+__host__ __device__ inline int ptmap_class(int rows) { return rows <= 4 ? 0 : rows <= 8 ? 1 : rows <= 16 ? 2 : 3; }
+// A problem whose points fit three workgroups per CU even at 32 points each has them all resident at once: the launch then
+// lasts as long as its slowest workgroup, fewer and fuller workgroups save nothing, and the points of up to 4 rows stay S points
+// in key order (measured on the 20 000-point window of config 5: 0.188 -> 0.191 ms per iteration with the class, k_point 26.6 ->
+// 28.2 us).  min_points: MSFM_LANES4_MIN (0: always, what the tests use; < 0: the default, 32 x 3 x 256 CUs).
+inline bool ptmap_use_lanes4(int npb, long min_points) { return npb > (min_points < 0 ? 32L * 3 * 256 : min_points); }
+// (n: the points of up to 4, 5..8, 9..16 and more rows; lanes4 false: the first two share the S class)
+inline PtMap ptmap_make(const int (&n)[PTMAP_CLASSES], bool lanes4) {
+  const int nQ = lanes4 ? n[0] : 0, nS = lanes4 ? n[1] : n[0] + n[1];
+  return PtMap{nQ, nS, n[2], n[3], (nQ + 63) / 64, (nS + 31) / 32, (n[2] + 15) / 16};
+}
+inline int ptmap_n_wg(const PtMap& m) { const int n = m.wQ + m.wS + m.wL + (m.nX + 31) / 32; return n > 0 ? n : 1; }   // (an empty launch is not one)

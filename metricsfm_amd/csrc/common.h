@@ -31,6 +31,7 @@ struct msfm_env {
   bool create_host = false;       // MSFM_CREATE_HOST=1: msfm_ba_create builds its index structures on the host
   long fold_min = 262144;         // MSFM_FOLD_MIN: camera pairs below which a problem keeps the gather path
   bool no_fold = false;           // MSFM_NO_FOLD (set): the gather path whatever the size
+  long lanes4_min = -1;           // MSFM_LANES4_MIN: eliminated points above which those of up to 4 rows get 4 lanes (ptmap_use_lanes4; -1: default)
   bool fused_sums = true;         // MSFM_FUSED_SUMS=0: per-camera sums, pair-list residue and zero fill as separate launches
   bool fused_tail = true;         // MSFM_FUSED_TAIL=0: the launches behind the back substitution one by one
   bool keep_t = false;            // MSFM_KEEP_T=1: folding workgroups store their T records too

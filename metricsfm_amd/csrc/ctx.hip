@@ -22,6 +22,7 @@ msfm_env msfm_env_read() {
   E.create_host = num("MSFM_CREATE_HOST", 0) != 0;
   if (const char* e = get("MSFM_FOLD_MIN")) E.fold_min = atol(e);
   E.no_fold = get("MSFM_NO_FOLD") != nullptr;
+  if (const char* e = get("MSFM_LANES4_MIN")) E.lanes4_min = atol(e);
   E.fused_sums = num("MSFM_FUSED_SUMS", 1) != 0;
   E.fused_tail = num("MSFM_FUSED_TAIL", 1) != 0;
   E.keep_t = num("MSFM_KEEP_T", 0) != 0;
