@@ -433,7 +433,7 @@ void IncrementalSfM::RemovePointOutliers() {
 }
 
 // ---- IncrementalSfM: the seed pair ----------------------------------------------------------------
-IncrementalSfM::IncrementalSfM() { msfm_seed_default_options(&seed_options_); }
+IncrementalSfM::IncrementalSfM() { msfm_seed_default_options(&seed_options_); msfm_localize_pose_default_options(&localize_options_); }
 
 void IncrementalSfM::SortImagePairs(std::vector<std::pair<int, int>>& seed_pair_hyps) const {
   const int num_img = (int)graph_.n_features.size();
@@ -677,40 +677,53 @@ static std::vector<int> candidate_images(const IncrementalSfM& s) {
   return image_ids;
 }
 
+// The flat state of cams_ / pts_ - camera -> image, (camera, local feature) -> point, what the search reads of a point - and one
+// msfm_localize_candidates call for `cand`; with_points: point_xyz and keypoints_ go along, and the set keeps its
+// correspondences on the device for msfm_localize_poses.  The set is the caller's.
+static msfm_localize_set* localize_search(IncrementalSfM& s, const std::vector<int>& cand, bool with_points) {
+  std::vector<int> cam_img(s.cams_.size()), feat_point, fail(cand.size());
+  for (size_t c = 0; c < s.cams_.size(); c++) {
+    const int img = s.cams_[c]->id_img_, nf = s.graph_.n_features[img];
+    cam_img[c] = img;
+    const size_t at = feat_point.size();
+    feat_point.resize(at + nf, -1);
+    for (auto& kv : s.cams_[c]->pts_) {
+      const long local = (long)kv.first - (long)s.options_.idx_max_per_image * img;
+      if (local < 0 || local >= nf) continue;   // (no match of this image can name it)
+      const int id = kv.second->id_;
+      if (id < 0 || id >= (int)s.pts_.size() || s.pts_[id] != kv.second) throw std::runtime_error("FindImageToLocalize: pts_[i]->id_ != i");
+      feat_point[at + local] = id;
+    }
+  }
+  std::vector<uint8_t> pt_bad(s.pts_.size());
+  std::vector<double> pt_mse(s.pts_.size()), xyz;
+  std::vector<int> pt_views(s.pts_.size());
+  for (size_t i = 0; i < s.pts_.size(); i++) {
+    pt_bad[i] = s.pts_[i]->is_bad_estimated_; pt_mse[i] = s.pts_[i]->mse_; pt_views[i] = (int)s.pts_[i]->cams_.size();
+  }
+  for (size_t k = 0; k < cand.size(); k++) fail[k] = s.localize_fail_times_[cand[k]];
+  msfm_localize_problem P{};
+  P.n_cams = (int)s.cams_.size(); P.cam_img = cam_img.data(); P.feat_point = feat_point.data();
+  P.n_points = (int)s.pts_.size(); P.pt_bad = pt_bad.data(); P.pt_mse = pt_mse.data(); P.pt_views = pt_views.data();
+  P.n_cand = (int)cand.size(); P.cand_img = cand.data(); P.fail_times = fail.data();
+  if (with_points) {   // :592-600
+    xyz.resize(3 * std::max<size_t>(1, s.pts_.size()));
+    for (size_t i = 0; i < s.pts_.size(); i++)
+      for (int q = 0; q < 3; q++) xyz[3 * i + q] = s.pts_[i]->data[q];
+    P.point_xyz = xyz.data(); P.keypoints = s.keypoints_.data();
+  }
+  msfm_localize_set* set = nullptr;
+  check(msfm_localize_candidates(Context(), s.store_.get(), &P, &set), "msfm_localize_candidates");
+  return set;
+}
+
 void IncrementalSfM::FindImageToLocalize(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
                                          std::vector<std::vector<int>>& visible_cams) {
   image_ids.clear(); corres_2d3d.clear(); visible_cams.clear();
   if (!store_) throw std::runtime_error("FindImageToLocalize: SetMatches first");
   const std::vector<int> cand = candidate_images(*this);
   if (cand.empty()) return;
-  // the flat state: camera -> image, (camera, local feature) -> point, and what the search reads of a point
-  std::vector<int> cam_img(cams_.size()), feat_point, fail(cand.size());
-  for (size_t c = 0; c < cams_.size(); c++) {
-    const int img = cams_[c]->id_img_, nf = graph_.n_features[img];
-    cam_img[c] = img;
-    const size_t at = feat_point.size();
-    feat_point.resize(at + nf, -1);
-    for (auto& kv : cams_[c]->pts_) {
-      const long local = (long)kv.first - (long)options_.idx_max_per_image * img;
-      if (local < 0 || local >= nf) continue;   // (no match of this image can name it)
-      const int id = kv.second->id_;
-      if (id < 0 || id >= (int)pts_.size() || pts_[id] != kv.second) throw std::runtime_error("FindImageToLocalize: pts_[i]->id_ != i");
-      feat_point[at + local] = id;
-    }
-  }
-  std::vector<uint8_t> pt_bad(pts_.size());
-  std::vector<double> pt_mse(pts_.size());
-  std::vector<int> pt_views(pts_.size());
-  for (size_t i = 0; i < pts_.size(); i++) {
-    pt_bad[i] = pts_[i]->is_bad_estimated_; pt_mse[i] = pts_[i]->mse_; pt_views[i] = (int)pts_[i]->cams_.size();
-  }
-  for (size_t k = 0; k < cand.size(); k++) fail[k] = localize_fail_times_[cand[k]];
-  msfm_localize_problem P{};
-  P.n_cams = (int)cams_.size(); P.cam_img = cam_img.data(); P.feat_point = feat_point.data();
-  P.n_points = (int)pts_.size(); P.pt_bad = pt_bad.data(); P.pt_mse = pt_mse.data(); P.pt_views = pt_views.data();
-  P.n_cand = (int)cand.size(); P.cand_img = cand.data(); P.fail_times = fail.data();
-  msfm_localize_set* set = nullptr;
-  check(msfm_localize_candidates(Context(), store_.get(), &P, &set), "msfm_localize_candidates");
+  msfm_localize_set* set = localize_search(*this, cand, false);
   int n_kept = 0, n_corr = 0, n_vis = 0;
   msfm_localize_set_size(set, &n_kept, &n_corr, &n_vis, nullptr, nullptr);
   std::vector<int> rank(n_kept), coff(n_kept + 1), cf(n_corr), cp(n_corr), voff(n_kept + 1), vc(n_vis);
@@ -788,6 +801,171 @@ void IncrementalSfM::FindImageToLocalizeHost(std::vector<int>& image_ids, std::v
     visible_sort.push_back(visible_cams[e.first]);
   }
   image_ids = ids_sort; corres_2d3d = corres_sort; visible_cams = visible_sort;
+}
+
+// ---- IncrementalSfM: the localisation of the next image --------------------------------------------
+// CameraAssociateCameraModel as far as image_model_ describes it: the model of a camera whose image shares the value
+static CameraModel* model_of_image(const IncrementalSfM& s, int id_img) {
+  for (const Camera* c : s.cams_)
+    if (s.image_model_[c->id_img_] == s.image_model_[id_img]) return c->cam_model_;
+  return nullptr;
+}
+
+static void localize_check_inputs(const IncrementalSfM& s, const char* who) {
+  seed_check_inputs(s, who);
+  for (size_t i = 0; i < s.image_focal_.size(); i++)
+    if (s.image_focal_[i] == 0.0 && s.image_focal_init_.size() != s.image_focal_.size())
+      throw std::runtime_error(std::string(who) + ": image_focal_init_ for the images without a focal length");
+}
+
+// :575-589: the camera of `id_img` on its model (an existing one, or a new one that is not yet in cam_models_)
+static Camera* localize_new_camera(const IncrementalSfM& s, int id_img) {
+  Camera* cam_new = new Camera;
+  cam_new->AssociateImage(id_img);
+  CameraModel* model = model_of_image(s, id_img);
+  if (!model) model = new CameraModel((int)s.cam_models_.size(), 0, 0, 0.0, s.image_focal_[id_img], "", "");
+  cam_new->AssociateCamereModel(model);
+  return cam_new;
+}
+
+static void localize_drop_camera(Camera* cam) {
+  if (cam->cam_model_->num_cams_ == 0) delete cam->cam_model_;
+  delete cam;
+}
+
+// :733-748
+static void localize_register_camera(IncrementalSfM& s, Camera* cam_new, const std::vector<int>& visible_cams) {
+  if (cam_new->cam_model_->num_cams_ == 0) s.cam_models_.push_back(cam_new->cam_model_);
+  cam_new->SetID((int)s.cams_.size());
+  cam_new->cam_model_->AddCamera(cam_new->id_);
+  s.cams_.push_back(cam_new);
+  s.UpdateVisibleGraph((int)s.cams_.size() - 1, visible_cams);
+}
+
+bool IncrementalSfM::LocalizeNextImage() {
+  localize_check_inputs(*this, "LocalizeNextImage");
+  localize_image_ids_.clear(); localize_failed_.clear(); localize_count_inliers_ = 0;
+  const std::vector<int> cand = candidate_images(*this);
+  if (cand.empty()) return false;
+  std::shared_ptr<msfm_localize_set> set(localize_search(*this, cand, true), msfm_localize_set_destroy);
+  int n_kept = 0, n_corr = 0, n_vis = 0;
+  msfm_localize_set_size(set.get(), &n_kept, &n_corr, &n_vis, nullptr, nullptr);
+  if (n_kept == 0) return false;   // :137
+  found_seed_ = true;              // :141
+  std::vector<int> rank(n_kept), coff(n_kept + 1), cf(n_corr), cp(n_corr), voff(n_kept + 1), vc(n_vis);
+  msfm_localize_set_fetch(set.get(), rank.data(), coff.data(), cf.data(), cp.data(), voff.data(), vc.data(), nullptr, nullptr);
+  std::vector<double> row_f(n_kept), row_f_init(n_kept, 0.0);
+  for (int r = 0; r < n_kept; r++) {
+    const int img = cand[rank[r]];
+    localize_image_ids_.push_back(img);
+    const CameraModel* model = model_of_image(*this, img);
+    row_f[r] = model ? model->f_ : image_focal_[img];   // :644
+    if (row_f[r] == 0.0) row_f_init[r] = image_focal_init_[img];
+  }
+  std::vector<uint8_t> added(std::max<size_t>(1, pts_.size()));
+  for (size_t i = 0; i < pts_.size(); i++) added[i] = pts_[i]->is_new_added_;
+  msfm_localize_pose_options opt = localize_options_;
+  opt.th_mse_localization = options_.th_mse_localization; opt.th_min_2d3d_corres = options_.th_min_2d3d_corres;
+  std::vector<uint8_t> tried(n_kept), arm(n_kept), state(std::max(1, n_corr));
+  std::vector<double> f(n_kept), R(9 * (size_t)n_kept), t(3 * (size_t)n_kept);
+  std::vector<int> n_inliers(n_kept);
+  int winner = -1;
+  while (opt.first_row >= 0) {   // :146-159, max_tries rows per call
+    msfm_localize_pose_set* ps = nullptr;
+    check(msfm_localize_poses(Context(), set.get(), row_f.data(), row_f_init.data(), (int)pts_.size(), added.data(), &opt, &ps), "msfm_localize_poses");
+    int next_row = -1;
+    msfm_localize_pose_set_size(ps, nullptr, nullptr, nullptr, &winner, &next_row);
+    msfm_localize_pose_set_fetch(ps, tried.data(), arm.data(), nullptr, f.data(), R.data(), t.data(), nullptr, nullptr, nullptr, n_inliers.data(), nullptr,
+                                 nullptr, state.data());
+    msfm_localize_pose_set_destroy(ps);
+    for (int r = 0; r < n_kept; r++)
+      if (tried[r] && (winner < 0 || r < winner)) {   // :650 / :681
+        localize_fail_times_[localize_image_ids_[r]]++;
+        localize_failed_.push_back(localize_image_ids_[r]);
+      }
+    if (winner >= 0) break;
+    opt.first_row = next_row;
+  }
+  if (winner < 0) return false;    // :160-164
+  const int id_img = localize_image_ids_[winner];
+  size_t first = 0;
+  for (int i = 0; i < id_img; i++) first += graph_.n_features[i];
+  Camera* cam_new = localize_new_camera(*this, id_img);
+  if (arm[winner] == 2) cam_new->cam_model_->SetFocalLength(f[winner]);   // :703
+  RTPose pose;
+  for (int q = 0; q < 9; q++) pose.R.m[q] = R[9 * (size_t)winner + q];
+  for (int q = 0; q < 3; q++) pose.t[q] = t[3 * (size_t)winner + q];
+  cam_new->SetRTPose(pose.R, pose.t);                                     // :705
+  for (int e = coff[winner]; e < coff[winner + 1]; e++) {                 // :709-729 as the call reports it
+    Point3D* pt = pts_[cp[e]];
+    if (state[e] == 1) { pt->is_bad_estimated_ = true; continue; }
+    if ((state[e] == 2) != !pt->is_new_added_) throw std::runtime_error("LocalizeNextImage: corr_state disagrees with is_new_added_");
+    if (state[e] != 2) continue;
+    const int idx_2d_global = cf[e] + id_img * options_.idx_max_per_image;
+    pt->AddObservation(cam_new, keypoints_[2 * (first + cf[e])], keypoints_[2 * (first + cf[e]) + 1], idx_2d_global);
+    pt->is_new_added_ = true;
+    cam_new->AddPoints(pt, idx_2d_global);
+    localize_count_inliers_++;
+  }
+  if (localize_count_inliers_ != n_inliers[winner]) throw std::runtime_error("LocalizeNextImage: n_inliers disagrees with the walk");
+  localize_register_camera(*this, cam_new, std::vector<int>(vc.begin() + voff[winner], vc.begin() + voff[winner + 1]));
+  return true;
+}
+
+bool IncrementalSfM::LocalizeImage(int id_img, std::vector<std::pair<int, int>>& corres_2d3d, std::vector<int>& visible_cams) {
+  if (corres_2d3d.size() < 3) return false;   // :567
+  localize_check_inputs(*this, "LocalizeImage");
+  size_t first = 0;
+  for (int i = 0; i < id_img; i++) first += graph_.n_features[i];
+  Camera* cam_new = localize_new_camera(*this, id_img);
+  // :592-600, flat, as problem localize_row_ behind empty problems
+  const int r = localize_row_, N = (int)corres_2d3d.size();
+  std::vector<int> off(r + 2, 0);
+  off[r + 1] = N;
+  std::vector<double> pts_w(3 * (size_t)N), pts_2d(2 * (size_t)N), fs(r + 1, 1.0), Rr(9 * (size_t)(r + 1)), tr(3 * (size_t)(r + 1)), avg(r + 1),
+      error_reproj(N), f_out(r + 1);
+  for (int i = 0; i < N; i++) {
+    const int idx_2d = corres_2d3d[i].first, idx_3d = corres_2d3d[i].second;
+    pts_2d[2 * (size_t)i] = keypoints_[2 * (first + idx_2d)]; pts_2d[2 * (size_t)i + 1] = keypoints_[2 * (first + idx_2d) + 1];
+    for (int q = 0; q < 3; q++) pts_w[3 * (size_t)i + q] = pts_[idx_3d]->data[q];
+  }
+  const bool known = cam_new->cam_model_->f_ != 0.0;   // :644
+  if (known) {
+    fs[r] = cam_new->cam_model_->f_;
+    check(msfm_epnp_ransac_batch(Context(), r + 1, off.data(), pts_w.data(), pts_2d.data(), fs.data(), localize_options_.max_iter,
+                                 localize_options_.seed, Rr.data(), tr.data(), error_reproj.data(), avg.data(), nullptr), "epnp_ransac_batch");
+  } else {
+    fs[r] = image_focal_init_[id_img];                 // :675
+    check(msfm_epnpf_sweep_batch(Context(), r + 1, off.data(), pts_w.data(), pts_2d.data(), fs.data(), &localize_options_.sweep, f_out.data(),
+                                 Rr.data(), tr.data(), error_reproj.data(), avg.data(), nullptr, nullptr, nullptr), "epnpf_sweep_batch");
+  }
+  const double avg_error = avg[r];
+  if (avg_error > options_.th_mse_localization) {      // :648 / :679
+    localize_fail_times_[id_img]++;
+    localize_drop_camera(cam_new);
+    return false;
+  }
+  if (!known) cam_new->cam_model_->SetFocalLength(f_out[r]);   // :703
+  RTPose pose;
+  for (int q = 0; q < 9; q++) pose.R.m[q] = Rr[9 * (size_t)r + q];
+  for (int q = 0; q < 3; q++) pose.t[q] = tr[3 * (size_t)r + q];
+  cam_new->SetRTPose(pose.R, pose.t);
+  int count_inliers = 0;
+  for (int i = 0; i < N; i++) {                        // :709-729
+    const int idx_3d = corres_2d3d[i].second;
+    if (error_reproj[i] > avg_error) { pts_[idx_3d]->is_bad_estimated_ = true; continue; }
+    const int idx_2d_local = corres_2d3d[i].first;
+    const int idx_2d_global = idx_2d_local + id_img * options_.idx_max_per_image;
+    if (!pts_[idx_3d]->is_new_added_) {
+      pts_[idx_3d]->AddObservation(cam_new, pts_2d[2 * (size_t)i], pts_2d[2 * (size_t)i + 1], idx_2d_global);
+      pts_[idx_3d]->is_new_added_ = true;
+      cam_new->AddPoints(pts_[idx_3d], idx_2d_global);
+      count_inliers++;
+    }
+  }
+  localize_count_inliers_ = count_inliers;
+  localize_register_camera(*this, cam_new, visible_cams);
+  return true;
 }
 
 // ---- IncrementalSfM: the new points of the image just localised -------------------------------------

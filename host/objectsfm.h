@@ -152,8 +152,8 @@ class BundleAdjuster {  // optimizer.h / optimizer.cc:31-232
 };
 
 // The bundle-adjustment side of the incremental loop (SfM/src/sfm_incremental.h/.cc): which cameras and points a
-// partial adjustment frees, the full adjustment, the outlier sweep.  Localisation, seed search and file handling stay
-// with their own stages (pose initialisers / matching above).
+// partial adjustment frees, the full adjustment, the outlier sweep - and, on the resident match store, the seed search, the
+// search for the next image, its localisation and its new points.  File handling stays with its own stage (matching above).
 struct IncrementalSfMOptions {       // basic_structs.h:147-227, the fields this part reads
   double th_mse_outliers = 3.0;      // test_sfm.cc:46 (UAV), 1.0 for WEB (:57)
   int th_visible_matches = 5;        // `count_2d3d_ij > 5`, sfm_incremental.cc:503
@@ -164,6 +164,8 @@ struct IncrementalSfMOptions {       // basic_structs.h:147-227, the fields this
   double th_angle_small = 3.0 / 180.0 * 3.1415;   // basic_structs.h:190
   int th_seedpair_structures = 20;       // basic_structs.h:174
   double th_angle_large = 5.0 / 180.0 * 3.1415;   // basic_structs.h:191
+  int th_min_2d3d_corres = 20;           // basic_structs.h:177
+  double th_mse_localization = 5.0;      // basic_structs.h:186
 };
 // What FindImageToLocalize reads of Graph (SfM/src/graph/graph.h): match_graph_ and the verified match lists - here in memory
 // in the flat layout of msfm_match_store_create instead of behind Graph::QueryMatch's `<i>_match` files (graph.cc:92-137).
@@ -196,6 +198,27 @@ class IncrementalSfM {
   // what scripts/localize_bench.py times the library call against, and a second opinion for tests/localize_host_check.cc.
   void FindImageToLocalizeHost(std::vector<int>& image_ids, std::vector<std::vector<std::pair<int, int>>>& corres_2d3d,
                                std::vector<std::vector<int>>& visible_cams) const;
+  // Run :126-164 (sfm_incremental.cc): FindImageToLocalize, then the tries of :146-159 around LocalizeImage (:565-753) through
+  // two library calls - msfm_localize_candidates with the points, whose correspondences stay on the device, and
+  // msfm_localize_poses on that set, in chunks of localize_options_.max_tries rows until a row passes or the rows run out.  The
+  // tried rows ahead of the winner get their localize_fail_times_ incremented (:650 / :681); the winner becomes a Camera - on
+  // the CameraModel of a camera whose image has the same image_model_ (at that model's current f_), else on a new one that
+  // starts at image_focal_ (0.0: the sweep around image_focal_init_, :675, and SetFocalLength, :703) - with SetRTPose, the
+  // observations and bad flags of :708-729 as the call reports them, and UpdateVisibleGraph (:748).  As in the reference
+  // is_img_processed_ / img_cam_map_ are the caller's (Run :175-176).  Returns whether an image was localised.
+  // Needs SetMatches, SetKeypoints, image_focal_, image_model_ and, for images without a focal length, image_focal_init_.
+  bool LocalizeNextImage();
+  // The reference's function for one image, through the public pose calls on host arrays.  The image is handed to them as
+  // problem localize_row_ (its row in FindImageToLocalize's order, set by the caller) behind empty problems, so it draws the
+  // samples the batched call draws: the same camera bit for bit.  A second opinion for tests/localizepose_host_check.cc and
+  // what scripts/localizepose_bench.py times the batched call against.
+  bool LocalizeImage(int id_img, std::vector<std::pair<int, int>>& corres_2d3d, std::vector<int>& visible_cams);
+  int localize_row_ = 0;
+  msfm_localize_pose_options localize_options_;   // msfm_localize_pose_default_options; the two thresholds come from options_ at each call
+  std::vector<double> image_focal_init_;     // per image: 1.2 * max(w, h) (:675), read where the model has no focal length
+  std::vector<int> localize_image_ids_;      // of the last LocalizeNextImage: the ranked candidates,
+  std::vector<int> localize_failed_;         // the images whose fail counter it incremented,
+  int localize_count_inliers_ = 0;           // count_inliers (:727) of the winner
   // sfm_incremental.cc:1790-1829: the image pairs in the order the seed search tries them.  Row sums in binary32, the C
   // library's log; ties, which the reference's std::sort leaves open, go to the lower i * num_img + j.
   void SortImagePairs(std::vector<std::pair<int, int>>& seed_pair_hyps) const;

@@ -588,7 +588,10 @@ void msfm_match_store_destroy(msfm_match_store* store);
  *      :592-600) - with offsets = corr_off exactly what msfm_epnp_ransac_batch / msfm_epnpf_sweep_batch take.
  *      A candidate's rows do not depend on which other candidates are in the call.
  * feat_point >= n_points is MSFM_E_INVAL (checked on the device before anything is indexed by it).  Per call the host
- * sends feat_point, the point arrays and four integers per walked pair; h2d_bytes of msfm_localize_set_size reports it. */
+ * sends feat_point, the point arrays and four integers per walked pair; h2d_bytes of msfm_localize_set_size reports it.
+ * A set made with point_xyz keeps corr_point / pts_w / pts_2d on the device as well, for msfm_localize_poses below, until
+ * msfm_localize_set_destroy.  A set counts as a child of its context, like a store: destroy it before the context (a
+ * context destroyed first is kept alive until its last child has gone). */
 typedef struct msfm_localize_problem {
   int32_t n_cams;
   const int32_t* cam_img;
@@ -665,6 +668,55 @@ int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* offsets, co
                            const double* pts_2d, const double* f_init, const msfm_epnpf_options* opt, double* f_out,
                            double* R, double* t, double* errors, double* avg_error, int* best_step, int* best_iter,
                            double* step_error);
+
+/* ---- the localisation tries of one round, on the resident correspondence set (msfm_localize_candidates above) ---- */
+/* The try loop of IncrementalSfM::Run (SfM/src/sfm_incremental.cc:143-164) around IncrementalSfM::LocalizeImage (:565-753)
+ * for the ranked rows of a msfm_localize_set in one call, on the correspondences the set keeps on the device.  A failed
+ * try returns at :670 / :701 before any state but localize_fail_times_ is touched, so the rows are independent and the
+ * batch gives the answer of the one-at-a-time loop.
+ *   - row r is eligible when its correspondence count is >= th_min_2d3d_corres (:148) and >= 3 (:567); tried rows are the
+ *     first max_tries eligible rows with index >= first_row (max_tries = 0: all of them); next_row = the first eligible row
+ *     behind the last tried one, or -1 - a host that found no winner calls again with first_row = next_row;
+ *   - row_f[r] != 0 (:644-672): row r IS problem r of msfm_epnp_ransac_batch(n_kept, corr_off, pts_w, pts_2d, row_f,
+ *     max_iter, seed), bit for bit; row_f[r] == 0 (:673-704): row r IS problem r of msfm_epnpf_sweep_batch(n_kept, corr_off,
+ *     pts_w, pts_2d, row_f_init, &sweep), f[r] = the kept focal length (:703).  The samples of a row depend on (seed, r,
+ *     sample) only, so first_row / max_tries change no row's result.  An arm without a tried row is not launched;
+ *   - pass[r] = !(avg_error[r] > th_mse_localization), the negation of :648 / :679 (a NaN passes, as there); winner = the
+ *     first tried row that passes, or -1;
+ *   - corr_state, for passing rows, walks the row's correspondences in order as :709-729 does: 1 = errors[i] > avg_error
+ *     (the point becomes is_bad_estimated_, :713-717); 2 = an inlier whose point is not pt_new_added and which is the first
+ *     such inlier of the row naming that point (AddObservation / Camera::AddPoints take it, :721-728); 3 = an inlier whose
+ *     point has is_new_added_ already, from pt_new_added or from an earlier correspondence of this row.  n_inliers counts
+ *     state 2 (count_inliers, :727), n_outliers state 1.  A point may be taken through one feature and marked bad through
+ *     another: both are reported.
+ * In : row_f [n_kept] (>= 0; 0.0 = unknown), row_f_init [n_kept] (read where row_f == 0; may be NULL when no row needs it),
+ *      n_points (> every point id of the set), pt_new_added [n_points] or NULL = all 0.
+ * Out: a msfm_localize_pose_set (host memory only).  Per row: tried, arm (0 untried, 1 known focal length, 2 sweep),
+ *      pass, f (row_f on arm 1), R [3][3], t [3], avg_error, best_step (-1 on arm 1), best_iter, n_inliers, n_outliers; per
+ *      correspondence, in the layout of corr_off: errors, corr_state.  Untried rows hold zeros.  Every fetch pointer may be NULL.
+ * No correspondence crosses PCIe on the way in and the host waits once.  Scratch: tried rows x n_points integers.
+ * MSFM_E_INVAL: a set made without point_xyz, n_points not above a point id of the set, max_iter or the sweep options outside
+ * what the two pose calls take, first_row < 0, max_tries < 0, a negative or NaN row_f. */
+typedef struct msfm_localize_pose_options {
+  double th_mse_localization; /* 5.0  basic_structs.h:186 */
+  int32_t th_min_2d3d_corres; /* 20   basic_structs.h:177 */
+  int32_t max_iter;           /* 200  EPnP samples, known-focal arm; 1..65536 */
+  uint64_t seed;              /* 0x4D53464D50, the hosts' default for msfm_epnp_ransac_batch */
+  msfm_epnpf_options sweep;   /* msfm_epnpf_default_options */
+  int32_t first_row;          /* 0 */
+  int32_t max_tries;          /* 16; 0 = every eligible row */
+} msfm_localize_pose_options;
+typedef struct msfm_localize_pose_set msfm_localize_pose_set;
+void msfm_localize_pose_default_options(msfm_localize_pose_options* opt);
+int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* set, const double* row_f, const double* row_f_init,
+                        int n_points, const uint8_t* pt_new_added, const msfm_localize_pose_options* opt,
+                        msfm_localize_pose_set** out);
+int msfm_localize_pose_set_size(const msfm_localize_pose_set* set, int* n_rows, int* n_corr, int* n_tried, int* winner,
+                                int* next_row);
+int msfm_localize_pose_set_fetch(const msfm_localize_pose_set* set, uint8_t* tried, uint8_t* arm, uint8_t* pass, double* f,
+                                 double* R, double* t, double* avg_error, int* best_step, int* best_iter, int* n_inliers,
+                                 int* n_outliers, double* errors /*[n_corr]*/, uint8_t* corr_state /*[n_corr]*/);
+void msfm_localize_pose_set_destroy(msfm_localize_pose_set* set);
 /* RelativePoseEstimation::RelativePoseWithFocalLength (SfM/src/orientation/relative_pose_estimation.cc:91-120,
  * called for the seed pair, sfm_incremental.cc:309) for a batch of image pairs.  Per pair, on points divided by the
  * focal lengths: EssentialMatrixFivePoints::FivePointEssentialMatrixRANSAC (essential_matrix_five_point.cc:30-92) -

@@ -112,6 +112,12 @@ class LocalizeProblem(C.Structure):
                 ("point_xyz", c_double_p), ("keypoints", c_float_p)]
 
 
+class LocalizePoseOptions(C.Structure):
+    """msfm_localize_pose_options (include/msfm.h)."""
+    _fields_ = [("th_mse_localization", C.c_double), ("th_min_2d3d_corres", C.c_int32), ("max_iter", C.c_int32), ("seed", C.c_uint64),
+                ("sweep", EpnpfOptions), ("first_row", C.c_int32), ("max_tries", C.c_int32)]
+
+
 class SeedOptions(C.Structure):
     """msfm_seed_options (include/msfm.h)."""
     _fields_ = [("th_mse_reprojection", C.c_double), ("th_angle_small", C.c_double), ("th_seedpair_structures", C.c_int32),

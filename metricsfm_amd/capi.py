@@ -25,6 +25,8 @@ SYMBOLS = [
     "msfm_chain_destroy",
     "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
     "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
+    "msfm_localize_pose_default_options", "msfm_localize_poses", "msfm_localize_pose_set_size", "msfm_localize_pose_set_fetch",
+    "msfm_localize_pose_set_destroy",
     "msfm_seed_default_options", "msfm_seed_hypotheses", "msfm_seed_set_size", "msfm_seed_set_fetch", "msfm_seed_set_destroy",
     "msfm_new_points_default_options", "msfm_new_points", "msfm_new_points_set_size", "msfm_new_points_set_fetch", "msfm_new_points_set_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
@@ -156,6 +158,14 @@ def lib():
     L.msfm_localize_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
     L.msfm_localize_set_destroy.argtypes = [vp]
     L.msfm_localize_set_destroy.restype = None
+    L.msfm_localize_pose_default_options.argtypes = [C.POINTER(A.LocalizePoseOptions)]
+    L.msfm_localize_pose_default_options.restype = None
+    L.msfm_localize_poses.argtypes = [vp, vp, A.c_double_p, A.c_double_p, C.c_int, A.c_u8_p, C.POINTER(A.LocalizePoseOptions), C.POINTER(vp)]
+    L.msfm_localize_pose_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p]
+    L.msfm_localize_pose_set_fetch.argtypes = [vp, A.c_u8_p, A.c_u8_p, A.c_u8_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p,
+                                               A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_u8_p]
+    L.msfm_localize_pose_set_destroy.argtypes = [vp]
+    L.msfm_localize_pose_set_destroy.restype = None
     L.msfm_seed_default_options.argtypes = [C.POINTER(A.SeedOptions)]
     L.msfm_seed_default_options.restype = None
     L.msfm_seed_hypotheses.argtypes = [vp, vp, C.POINTER(A.SeedProblem), C.POINTER(A.SeedOptions), C.POINTER(vp)]
@@ -207,6 +217,24 @@ def epnpf_options(**kw):
         if not hasattr(o, k):
             raise AttributeError(k)
         setattr(o, k, v)
+    return o
+
+
+def localize_pose_options(**kw):
+    """msfm_localize_pose_options with the reference's values (5.0 px, 20 correspondences, 200 samples, the default sweep, 16 tries);
+    keywords override fields, `sweep` takes a dict of msfm_epnpf_options fields."""
+    o = A.LocalizePoseOptions()
+    lib().msfm_localize_pose_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        if k == "sweep" and isinstance(v, dict):
+            for sk, sv in v.items():
+                if not hasattr(o.sweep, sk):
+                    raise AttributeError(sk)
+                setattr(o.sweep, sk, sv)
+        else:
+            setattr(o, k, v)
     return o
 
 
@@ -449,11 +477,9 @@ class Context:
         match_off [P+1], matches [M][2]: the flat layout of `build_tracks`)."""
         return MatchStore(self, n_features, pairs, match_off, matches)
 
-    def localize_candidates(self, store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=None, keypoints=None):
-        """msfm_localize_candidates (sfm_incremental.cc:440-562): the 2D-3D correspondences and visible cameras of every candidate
-        image, ranked.  Returns a dict: rank [n_kept] (indices into cand_img), corr_off, corr_feat, corr_point, vis_off, vis_cam,
-        h2d_bytes and, with point_xyz, pts_w [n_corr][3] / pts_2d [n_corr][2] (offsets = corr_off for `epnp_ransac`).
-        keypoints: flat float [sum of n_features][2] for a store that was not made from a chain."""
+    def localize_set(self, store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=None, keypoints=None):
+        """msfm_localize_candidates, the result kept as a `LocalizeSet`: `fetch()` is the dict of `localize_candidates`, and with
+        point_xyz the correspondences stay on the device for `poses(...)` (msfm_localize_poses).  Close it before the context."""
         cam_img, feat_point, pt_views, cand_img, fail_times = (A.as_c(np.asarray(x, dtype=np.int32), np.int32)
                                                                for x in (cam_img, feat_point, pt_views, cand_img, fail_times))
         pt_bad = A.as_c(np.asarray(pt_bad, dtype=np.uint8), np.uint8)
@@ -474,22 +500,18 @@ class Context:
                               A.ptr(fail_times, A.c_int_p), A.ptr(xyz, A.c_double_p), A.ptr(kp, A.c_float_p))
         h = C.c_void_p()
         self.check(lib().msfm_localize_candidates(self._h, store._h, C.byref(P), C.byref(h)))
+        return LocalizeSet(self, h)
+
+    def localize_candidates(self, store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=None, keypoints=None):
+        """msfm_localize_candidates (sfm_incremental.cc:440-562): the 2D-3D correspondences and visible cameras of every candidate
+        image, ranked.  Returns a dict: rank [n_kept] (indices into cand_img), corr_off, corr_feat, corr_point, vis_off, vis_cam,
+        h2d_bytes and, with point_xyz, pts_w [n_corr][3] / pts_2d [n_corr][2] (offsets = corr_off for `epnp_ransac`).
+        keypoints: flat float [sum of n_features][2] for a store that was not made from a chain."""
+        st = self.localize_set(store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=point_xyz, keypoints=keypoints)
         try:
-            nk, nc, nv, hp, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-            lib().msfm_localize_set_size(h, C.byref(nk), C.byref(nc), C.byref(nv), C.byref(hp), C.byref(nb))
-            nk, nc, nv = nk.value, nc.value, nv.value
-            rank, coff, voff = np.zeros(max(1, nk), np.int32), np.zeros(nk + 1, np.int32), np.zeros(nk + 1, np.int32)
-            cf, cp, vc = np.zeros(max(1, nc), np.int32), np.zeros(max(1, nc), np.int32), np.zeros(max(1, nv), np.int32)
-            pw = np.zeros((max(1, nc), 3)) if hp.value else None
-            p2 = np.zeros((max(1, nc), 2)) if hp.value else None
-            lib().msfm_localize_set_fetch(h, A.ptr(rank, A.c_int_p), A.ptr(coff, A.c_int_p), A.ptr(cf, A.c_int_p), A.ptr(cp, A.c_int_p),
-                                          A.ptr(voff, A.c_int_p), A.ptr(vc, A.c_int_p), A.ptr(pw, A.c_double_p), A.ptr(p2, A.c_double_p))
+            return st.fetch()
         finally:
-            lib().msfm_localize_set_destroy(h)
-        out = dict(rank=rank[:nk], corr_off=coff, corr_feat=cf[:nc], corr_point=cp[:nc], vis_off=voff, vis_cam=vc[:nv], h2d_bytes=nb.value)
-        if hp.value:
-            out["pts_w"], out["pts_2d"] = pw[:nc], p2[:nc]
-        return out
+            st.close()
 
     def seed_hypotheses(self, store, hyp_img, cam_fk, same_model, keypoints=None, **opts):
         """msfm_seed_hypotheses (sfm_incremental.cc:235-390): pose, two-view points and the two gates of every seed-pair
@@ -953,6 +975,80 @@ class MatchStore:
         if self._h:
             lib().msfm_match_store_destroy(self._h)
             self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class LocalizeSet:
+    """msfm_localize_set: the ranked candidates of one round; made with point_xyz it keeps their correspondences on the device."""
+
+    def __init__(self, ctx: Context, h):
+        self.ctx, self._h = ctx, h
+        nk, nc, nv, hp, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        lib().msfm_localize_set_size(h, C.byref(nk), C.byref(nc), C.byref(nv), C.byref(hp), C.byref(nb))
+        self.n_kept, self.n_corr, self.n_visible, self.has_points, self.h2d_bytes = nk.value, nc.value, nv.value, bool(hp.value), nb.value
+
+    def fetch(self):
+        nk, nc, nv = self.n_kept, self.n_corr, self.n_visible
+        rank, coff, voff = np.zeros(max(1, nk), np.int32), np.zeros(nk + 1, np.int32), np.zeros(nk + 1, np.int32)
+        cf, cp, vc = np.zeros(max(1, nc), np.int32), np.zeros(max(1, nc), np.int32), np.zeros(max(1, nv), np.int32)
+        pw = np.zeros((max(1, nc), 3)) if self.has_points else None
+        p2 = np.zeros((max(1, nc), 2)) if self.has_points else None
+        lib().msfm_localize_set_fetch(self._h, A.ptr(rank, A.c_int_p), A.ptr(coff, A.c_int_p), A.ptr(cf, A.c_int_p), A.ptr(cp, A.c_int_p),
+                                      A.ptr(voff, A.c_int_p), A.ptr(vc, A.c_int_p), A.ptr(pw, A.c_double_p), A.ptr(p2, A.c_double_p))
+        out = dict(rank=rank[:nk], corr_off=coff, corr_feat=cf[:nc], corr_point=cp[:nc], vis_off=voff, vis_cam=vc[:nv], h2d_bytes=self.h2d_bytes)
+        if self.has_points:
+            out["pts_w"], out["pts_2d"] = pw[:nc], p2[:nc]
+        return out
+
+    def poses(self, row_f, row_f_init=None, n_points=0, pt_new_added=None, **opts):
+        """msfm_localize_poses (sfm_incremental.cc:143-164 around :565-753): the tries of the ranked rows in one call.  row_f [n_kept]
+        (0.0 = unknown, then row_f_init is read); pt_new_added [n_points] or None; opts: fields of msfm_localize_pose_options.
+        Returns a dict: tried, arm, pass, f, R [n][3][3], t [n][3], avg_error, best_step, best_iter, n_inliers, n_outliers per row;
+        errors, corr_state per correspondence; n_tried, winner, next_row."""
+        n = self.n_kept
+        f = A.as_c(np.broadcast_to(np.asarray(row_f, dtype=np.float64), (n,)).copy(), np.float64)
+        fi = None if row_f_init is None else A.as_c(np.broadcast_to(np.asarray(row_f_init, dtype=np.float64), (n,)).copy(), np.float64)
+        added = None if pt_new_added is None else A.as_c(np.asarray(pt_new_added, dtype=np.uint8).reshape(-1), np.uint8)
+        if added is not None:
+            if n_points and n_points != len(added):
+                raise ValueError("pt_new_added must hold n_points entries")
+            n_points = len(added)
+        o = localize_pose_options(**opts)
+        h = C.c_void_p()
+        self.ctx.check(lib().msfm_localize_poses(self.ctx._h, self._h, A.ptr(f, A.c_double_p), A.ptr(fi, A.c_double_p), int(n_points),
+                                                 A.ptr(added, A.c_u8_p), C.byref(o), C.byref(h)))
+        try:
+            nr, nc, ntr, win, nxt = (C.c_int32() for _ in range(5))
+            lib().msfm_localize_pose_set_size(h, C.byref(nr), C.byref(nc), C.byref(ntr), C.byref(win), C.byref(nxt))
+            nc, m = nc.value, max(1, n)
+            tried, arm, pas, state = np.zeros(m, np.uint8), np.zeros(m, np.uint8), np.zeros(m, np.uint8), np.zeros(max(1, nc), np.uint8)
+            fo, R, t, avg, err = np.zeros(m), np.zeros((m, 3, 3)), np.zeros((m, 3)), np.zeros(m), np.zeros(max(1, nc))
+            bs, bi, nin, nout = (np.zeros(m, np.int32) for _ in range(4))
+            dp, ip, up = A.c_double_p, A.c_int_p, A.c_u8_p
+            lib().msfm_localize_pose_set_fetch(h, A.ptr(tried, up), A.ptr(arm, up), A.ptr(pas, up), A.ptr(fo, dp), A.ptr(R, dp), A.ptr(t, dp),
+                                               A.ptr(avg, dp), A.ptr(bs, ip), A.ptr(bi, ip), A.ptr(nin, ip), A.ptr(nout, ip), A.ptr(err, dp),
+                                               A.ptr(state, up))
+        finally:
+            lib().msfm_localize_pose_set_destroy(h)
+        return {"tried": tried[:n], "arm": arm[:n], "pass": pas[:n], "f": fo[:n], "R": R[:n], "t": t[:n], "avg_error": avg[:n],
+                "best_step": bs[:n], "best_iter": bi[:n], "n_inliers": nin[:n], "n_outliers": nout[:n], "errors": err[:nc],
+                "corr_state": state[:nc], "n_tried": ntr.value, "winner": win.value, "next_row": nxt.value}
+
+    def close(self):
+        if self._h:
+            lib().msfm_localize_set_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
 
     def __del__(self):
         try:

@@ -257,6 +257,31 @@ struct msfm_match_store {
   DevBuf<float> d_kp;             // [feat_off[n_images]][2]
 };
 
+// What msfm_localize_candidates leaves behind (localize.hip creates and destroys it; localize_pose.hip reads it).  A set made
+// with point_xyz keeps the device arrays its gather kernel wrote - corr_point, pts_w, pts_2d in the layout of corr_off - until
+// msfm_localize_set_destroy, so msfm_localize_poses moves no correspondence over PCIe.
+struct msfm_localize_set {
+  msfm_ctx* ctx = nullptr;
+  std::vector<int> rank, corr_off, corr_feat, corr_point, vis_off, vis_cam;
+  std::vector<double> pts_w, pts_2d;
+  bool have_pts = false;
+  int64_t h2d_bytes = 0;
+  DevBuf<int> d_cp;               // [n_corr]           (have_pts and n_corr > 0 only)
+  DevBuf<double> d_pw, d_p2;      // [n_corr][3], [n_corr][2]
+};
+
+// The device halves of msfm_epnp_ransac_batch / msfm_epnpf_sweep_batch (pose.hip), in the manner of the two below: device
+// buffers in, the two launches, device buffers out; no synchronisation.  The sample scratch belongs to the caller, who keeps
+// it until the stream has been synchronised.  d_off [n_problems + 1], d_f / d_f_init [n_problems], errors [off[n_problems]].
+struct EpnpScratch { DevBuf<double> hyp; };
+int pose_epnp_dev(msfm_ctx* ctx, int n_problems, const int* d_off, const double* d_w, const double* d_2d, const double* d_f, int max_iter,
+                  uint64_t seed, EpnpScratch& ws, double* dR, double* dt, double* d_err, double* d_avg, int* d_best_iter);
+struct EpnpfScratch { DevBuf<double> step_err, step_pose; DevBuf<int> step_it; };   // step_err: [n_problems][n_steps], the public step_error
+struct msfm_epnpf_options;
+int pose_epnpf_dev(msfm_ctx* ctx, int n_problems, int n_steps, const int* d_off, const double* d_w, const double* d_2d, const double* d_f_init,
+                   const msfm_epnpf_options* opt, EpnpfScratch& ws, double* d_f_out, double* dR, double* dt, double* d_err, double* d_avg,
+                   int* d_best_step, int* d_best_iter);
+
 // The device halves of msfm_relpose_5pt_batch / msfm_relpose_8pt_batch (pose.hip): device buffers in, the three launches,
 // device buffers out; no synchronisation.  The exports are upload + this + download; seed.hip calls the same functions on
 // the buffers its gather kernel wrote.  The candidate scratch belongs to the caller, who keeps it until the stream has been

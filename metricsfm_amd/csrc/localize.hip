@@ -19,6 +19,7 @@
 //   sort        by that key, ties to the lower f_i (= emit order): segments of up to LOC_LDS_MAX in LDS (bitonic on
 //               (key, emit index)), longer ones by rocPRIM's stable segmented radix sort - a total order, so both agree
 //   k_gather    corr_feat / corr_point in sorted order and, when asked for, pts_w / pts_2d as msfm_epnp_ransac_batch takes them
+//               (these three stay on the device inside the set: msfm_localize_poses, localize_pose.hip, reads them there)
 // Integer atomics only; nothing depends on the order in which threads run.  Per call the host sends O(registered features +
 // points + pairs of the candidates' rows); nothing that scales with the number of matches crosses PCIe.
 #include <algorithm>
@@ -34,13 +35,6 @@
 // through rocPRIM).
 #define LOC_LDS_MAX 4096
 #define LOC_BIG 0x7fffffff
-
-struct msfm_localize_set {
-  std::vector<int> rank, corr_off, corr_feat, corr_point, vis_off, vis_cam;
-  std::vector<double> pts_w, pts_2d;
-  bool have_pts = false;
-  int64_t h2d_bytes = 0;
-};
 
 namespace loc {
 
@@ -358,9 +352,11 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   }
   const int nwp = (int)wp.size();
   std::unique_ptr<msfm_localize_set> R(new msfm_localize_set());
+  R->ctx = ctx;
   R->have_pts = want_pts;
   R->corr_off.assign(1, 0); R->vis_off.assign(1, 0);
-  if (nk == 0) { *out = R.release(); return MSFM_OK; }
+  auto hand_over = [&]() { ctx->children++; *out = R.release(); return MSFM_OK; };   // a set is a child of its context, like a store
+  if (nk == 0) return hand_over();
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const msfm_env env = msfm_env_read();
@@ -426,7 +422,7 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
     R->vis_off.push_back((int)R->vis_cam.size());
   }
   R->h2d_bytes = h2d;
-  if (T == 0) { *out = R.release(); return MSFM_OK; }
+  if (T == 0) return hand_over();
   // ---- emit, sort, gather ----
   std::vector<int> kp_off(nk, 0);
   DevBuf<float> d_kp_up;
@@ -500,8 +496,8 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   }
   LC_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
   R->h2d_bytes = h2d;
-  *out = R.release();
-  return MSFM_OK;
+  if (want_pts) { R->d_cp.swap(d_cp); R->d_pw.swap(d_pw); R->d_p2.swap(d_p2); }   // resident for msfm_localize_poses
+  return hand_over();
 }
 
 MSFM_API int msfm_localize_set_size(const msfm_localize_set* R, int* n_kept, int* n_corr, int* n_visible, int* has_points, int64_t* h2d_bytes) {
@@ -529,4 +525,13 @@ MSFM_API int msfm_localize_set_fetch(const msfm_localize_set* R, int* rank, int*
   return MSFM_OK;
 }
 
-MSFM_API void msfm_localize_set_destroy(msfm_localize_set* R) { delete R; }
+MSFM_API void msfm_localize_set_destroy(msfm_localize_set* R) {
+  if (!R) return;
+  msfm_ctx* ctx = R->ctx;
+  if (R->d_cp.p) {   // blocks go back to the pool only behind the work that may still read them
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  delete R;
+  msfm_ctx_child_released(ctx);
+}

@@ -1512,6 +1512,24 @@ __global__ __launch_bounds__(256) void k_f8_select(int T, const int* __restrict_
                     Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
 }
 
+int pose_epnp_dev(msfm_ctx* ctx, int n_problems, const int* d_off, const double* d_w, const double* d_2d, const double* d_f, int max_iter,
+                  uint64_t seed, EpnpScratch& ws, double* dR, double* dt, double* d_err, double* d_avg, int* d_best_iter) {
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, ws.hyp.alloc((size_t)n_problems * max_iter * 13));
+  {
+    KTimer tm(ctx, "pose_epnp_hyp");
+    hipLaunchKernelGGL(k_epnp_hyp, dim3(cdiv(max_iter, POSE_WAVE), n_problems), dim3(POSE_WAVE), 0, s, max_iter, d_off, d_w, d_2d, d_f, seed,
+                       ws.hyp.p);
+  }
+  {
+    KTimer tm(ctx, "pose_epnp_select");
+    hipLaunchKernelGGL(k_epnp_select, dim3(n_problems), dim3(256), 0, s, max_iter, d_off, d_w, d_2d, d_f, ws.hyp.p, dR, dt, d_err, d_avg,
+                       d_best_iter);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return MSFM_OK;
+}
+
 MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w, const double* pts_2d,
                                     const double* f, int max_iter, uint64_t seed, double* R, double* t, double* errors, double* avg_error,
                                     int* best_iter) {
@@ -1525,7 +1543,8 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<int> d_off, d_best;
-  DevBuf<double> d_w, d_2d, d_f, d_hyp, d_R, d_t, d_err, d_avg;
+  DevBuf<double> d_w, d_2d, d_f, d_R, d_t, d_err, d_avg;
+  EpnpScratch ws;
   HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
   HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
@@ -1534,23 +1553,12 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, d_2d.upload(pts_2d, 2 * (size_t)total, s));
   HIP_TRY(ctx, d_f.alloc(n_problems));
   HIP_TRY(ctx, d_f.upload(f, n_problems, s));
-  HIP_TRY(ctx, d_hyp.alloc((size_t)n_problems * max_iter * 13));
   HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_problems));
   HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_problems));
   HIP_TRY(ctx, d_err.alloc((size_t)std::max(1, total)));
   HIP_TRY(ctx, d_avg.alloc(n_problems));
   HIP_TRY(ctx, d_best.alloc(n_problems));
-  {
-    KTimer tm(ctx, "pose_epnp_hyp");
-    hipLaunchKernelGGL(k_epnp_hyp, dim3(cdiv(max_iter, POSE_WAVE), n_problems), dim3(POSE_WAVE), 0, s, max_iter, d_off.p, d_w.p, d_2d.p,
-                       d_f.p, seed, d_hyp.p);
-  }
-  {
-    KTimer tm(ctx, "pose_epnp_select");
-    hipLaunchKernelGGL(k_epnp_select, dim3(n_problems), dim3(256), 0, s, max_iter, d_off.p, d_w.p, d_2d.p, d_f.p, d_hyp.p, d_R.p, d_t.p,
-                       d_err.p, d_avg.p, d_best.p);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  MSFM_TRY(pose_epnp_dev(ctx, n_problems, d_off.p, d_w.p, d_2d.p, d_f.p, max_iter, seed, ws, d_R.p, d_t.p, d_err.p, d_avg.p, d_best.p));
   HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   if (total) HIP_TRY(ctx, hipMemcpyAsync(errors, d_err.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
@@ -1577,6 +1585,28 @@ MSFM_API int msfm_epnpf_num_steps(const msfm_epnpf_options* o) {
   return (int)q;
 }
 
+int pose_epnpf_dev(msfm_ctx* ctx, int n_problems, int n_steps, const int* d_off, const double* d_w, const double* d_2d, const double* d_f_init,
+                   const msfm_epnpf_options* opt, EpnpfScratch& ws, double* d_f_out, double* dR, double* dt, double* d_err, double* d_avg,
+                   int* d_best_step, int* d_best_iter) {
+  hipStream_t s = ctx->stream;
+  const size_t Q = (size_t)n_problems * n_steps;
+  HIP_TRY(ctx, ws.step_err.alloc(Q));
+  HIP_TRY(ctx, ws.step_it.alloc(Q));
+  HIP_TRY(ctx, ws.step_pose.alloc(12 * Q));
+  {
+    KTimer tm(ctx, "pose_epnpf_sweep");
+    hipLaunchKernelGGL(k_epnpf_sweep, dim3(n_steps, n_problems), dim3(EPNPF_BLOCK), 0, s, opt->max_iter, n_steps, d_off, d_w, d_2d, d_f_init,
+                       opt->f_ratio_min, opt->f_ratio_step, opt->seed, ws.step_err.p, ws.step_it.p, ws.step_pose.p);
+  }
+  {
+    KTimer tm(ctx, "pose_epnpf_select");
+    hipLaunchKernelGGL(k_epnpf_select, dim3(n_problems), dim3(256), 0, s, n_steps, d_off, d_w, d_2d, d_f_init, opt->f_ratio_min,
+                       opt->f_ratio_step, ws.step_err.p, ws.step_it.p, ws.step_pose.p, d_f_out, dR, dt, d_err, d_avg, d_best_step, d_best_iter);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return MSFM_OK;
+}
+
 MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* offsets, const double* pts_w, const double* pts_2d,
                                     const double* f_init, const msfm_epnpf_options* opt, double* f_out, double* R, double* t,
                                     double* errors, double* avg_error, int* best_step, int* best_iter, double* step_error) {
@@ -1596,8 +1626,9 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t Q = (size_t)n_problems * n_steps;
-  DevBuf<int> d_off, d_sit, d_bstep, d_biter;
-  DevBuf<double> d_w, d_2d, d_f, d_serr, d_spose, d_fo, d_R, d_t, d_err, d_avg;
+  DevBuf<int> d_off, d_bstep, d_biter;
+  DevBuf<double> d_w, d_2d, d_f, d_fo, d_R, d_t, d_err, d_avg;
+  EpnpfScratch ws;
   HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
   HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
@@ -1606,9 +1637,6 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, d_2d.upload(pts_2d, 2 * (size_t)total, s));
   HIP_TRY(ctx, d_f.alloc(n_problems));
   HIP_TRY(ctx, d_f.upload(f_init, n_problems, s));
-  HIP_TRY(ctx, d_serr.alloc(Q));
-  HIP_TRY(ctx, d_sit.alloc(Q));
-  HIP_TRY(ctx, d_spose.alloc(12 * Q));
   HIP_TRY(ctx, d_fo.alloc(n_problems));
   HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_problems));
   HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_problems));
@@ -1616,17 +1644,8 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, d_avg.alloc(n_problems));
   HIP_TRY(ctx, d_bstep.alloc(n_problems));
   HIP_TRY(ctx, d_biter.alloc(n_problems));
-  {
-    KTimer tm(ctx, "pose_epnpf_sweep");
-    hipLaunchKernelGGL(k_epnpf_sweep, dim3(n_steps, n_problems), dim3(EPNPF_BLOCK), 0, s, opt->max_iter, n_steps, d_off.p, d_w.p, d_2d.p,
-                       d_f.p, opt->f_ratio_min, opt->f_ratio_step, opt->seed, d_serr.p, d_sit.p, d_spose.p);
-  }
-  {
-    KTimer tm(ctx, "pose_epnpf_select");
-    hipLaunchKernelGGL(k_epnpf_select, dim3(n_problems), dim3(256), 0, s, n_steps, d_off.p, d_w.p, d_2d.p, d_f.p, opt->f_ratio_min,
-                       opt->f_ratio_step, d_serr.p, d_sit.p, d_spose.p, d_fo.p, d_R.p, d_t.p, d_err.p, d_avg.p, d_bstep.p, d_biter.p);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  MSFM_TRY(pose_epnpf_dev(ctx, n_problems, n_steps, d_off.p, d_w.p, d_2d.p, d_f.p, opt, ws, d_fo.p, d_R.p, d_t.p, d_err.p, d_avg.p, d_bstep.p,
+                          d_biter.p));
   HIP_TRY(ctx, hipMemcpyAsync(f_out, d_fo.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
@@ -1634,7 +1653,7 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, hipMemcpyAsync(avg_error, d_avg.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   if (best_step) HIP_TRY(ctx, hipMemcpyAsync(best_step, d_bstep.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
   if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_biter.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (step_error) HIP_TRY(ctx, hipMemcpyAsync(step_error, d_serr.p, sizeof(double) * Q, hipMemcpyDeviceToHost, s));
+  if (step_error) HIP_TRY(ctx, hipMemcpyAsync(step_error, ws.step_err.p, sizeof(double) * Q, hipMemcpyDeviceToHost, s));
   HIP_TRY(ctx, hipStreamSynchronize(s));
   return MSFM_OK;
 }
