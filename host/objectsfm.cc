@@ -1036,6 +1036,116 @@ void IncrementalSfM::GenerateNew3DPoints() {
   num_new_points_ = n;
 }
 
+// ---- IncrementalSfM: the second half of a round in one call ---------------------------------------
+void IncrementalSfM::AdjustRound(int idx_new_cam, bool full) {
+  if (!store_) throw std::runtime_error("AdjustRound: SetMatches first");
+  if (idx_new_cam < 0 || idx_new_cam >= (int)cams_.size()) throw std::runtime_error("AdjustRound: no such camera");
+  if (!cams_gps_.empty()) throw std::runtime_error("AdjustRound: no GPS rows (PartialBundleAdjustment / FullBundleAdjustment attach them)");
+  size_t kp_rows = 0;
+  for (int v : graph_.n_features) kp_rows += v;
+  if (keypoints_.size() != 2 * kp_rows) throw std::runtime_error("AdjustRound: SetKeypoints first");
+  const int nc = (int)cams_.size(), nm = (int)cam_models_.size(), np = (int)pts_.size();
+  std::map<const Camera*, int> cam_id;
+  std::map<const CameraModel*, int> model_id;
+  for (int k = 0; k < nc; k++) cam_id[cams_[k]] = k;
+  for (int m = 0; m < nm; m++) model_id[cam_models_[m]] = m;
+  // the camera side (Camera::pts_) and the solver's parameter blocks
+  std::vector<int> cam_img(nc), feat_point, model_of_cam(nc);
+  std::vector<double> cam_pose(6 * (size_t)nc), cam_model(3 * (size_t)nm);
+  std::vector<uint8_t> model_mut(nm);
+  for (int k = 0; k < nc; k++) {
+    const Camera* cm = cams_[k];
+    const int img = cm->id_img_, nf = graph_.n_features[img];
+    cam_img[k] = img;
+    const size_t at = feat_point.size();
+    feat_point.resize(at + nf, -1);
+    for (auto& kv : cm->pts_) {
+      const long local = (long)kv.first - (long)options_.idx_max_per_image * img;
+      if (local < 0 || local >= nf) throw std::runtime_error("AdjustRound: a key of Camera::pts_ is no feature of its image");
+      feat_point[at + local] = kv.second->id_;
+    }
+    for (int q = 0; q < 6; q++) cam_pose[6 * (size_t)k + q] = cm->data[q];
+    model_of_cam[k] = model_id.at(cm->cam_model_);
+  }
+  for (int m = 0; m < nm; m++) {
+    for (int q = 0; q < 3; q++) cam_model[3 * (size_t)m + q] = cam_models_[m]->data[q];
+    model_mut[m] = cam_models_[m]->is_mutable_;
+  }
+  // the point side (Point3D::cams_): one row per observation
+  std::vector<int> obs_point, obs_cam, obs_feat;
+  std::vector<double> xyz(3 * (size_t)np), mse(np);
+  std::vector<uint8_t> bad(np), mut(np), added(np);
+  for (int i = 0; i < np; i++) {
+    const Point3D* p = pts_[i];
+    if (p->id_ != i) throw std::runtime_error("AdjustRound: pts_[i]->id_ != i");
+    for (auto& kv : p->cams_) {
+      obs_point.push_back(i);
+      obs_cam.push_back(cam_id.at(kv.second));
+      obs_feat.push_back((int)((long)kv.first - (long)options_.idx_max_per_image * kv.second->id_img_));
+    }
+    for (int q = 0; q < 3; q++) xyz[3 * (size_t)i + q] = p->data[q];
+    mse[i] = p->mse_; bad[i] = p->is_bad_estimated_; mut[i] = p->is_mutable_; added[i] = p->is_new_added_;
+  }
+  const std::vector<int>& visible = cams_[idx_new_cam]->visible_cams_;
+  msfm_round_options o;
+  msfm_round_default_options(&o);
+  o.partial.max_num_iterations = bundle_partial_options_.max_num_iterations;
+  o.partial.progress_to_stdout = bundle_partial_options_.minimizer_progress_to_stdout ? 1 : 0;
+  o.partial.num_threads = bundle_partial_options_.num_threads;
+  o.full.max_num_iterations = bundle_full_options_.max_num_iterations;
+  o.full.progress_to_stdout = bundle_full_options_.minimizer_progress_to_stdout ? 1 : 0;
+  o.full.num_threads = bundle_full_options_.num_threads;
+  o.th_mse_outliers = options_.th_mse_outliers;
+  msfm_round_problem P{};
+  P.n_cams = nc; P.cam_img = cam_img.data(); P.feat_point = feat_point.data(); P.n_points = np; P.keypoints = keypoints_.data();
+  P.n_obs = (int)obs_point.size(); P.obs_point = obs_point.data(); P.obs_cam = obs_cam.data(); P.obs_feat = obs_feat.data();
+  P.cam_pose = cam_pose.data(); P.n_models = nm; P.cam_model = cam_model.data(); P.cam_model_of_cam = model_of_cam.data();
+  P.model_mutable = model_mut.data();
+  P.point_xyz = xyz.data(); P.pt_bad = bad.data(); P.pt_mse = mse.data(); P.pt_mutable = mut.data(); P.pt_new_added = added.data();
+  P.new_cam = idx_new_cam; P.n_visible = (int)visible.size(); P.visible = visible.data();
+  P.do_partial = 1; P.do_full = full ? 1 : 0; P.do_outliers = 1;
+  msfm_round_set* set = nullptr;
+  check(msfm_round_adjust(Context(), store_.get(), &P, &o, &set), "msfm_round_adjust");
+  std::vector<double> R(9 * (size_t)nc), t(3 * (size_t)nc), c(3 * (size_t)nc);
+  for (int k = 0; k < 2; k++) {
+    round_iterations_[k].assign((size_t)std::max(0, k ? o.full.max_num_iterations : o.partial.max_num_iterations) + 2, msfm_ba_iteration());
+    round_summary_[k] = msfm_ba_summary();
+    round_summary_[k].iterations = round_iterations_[k].data();
+    round_summary_[k].iterations_capacity = (int)round_iterations_[k].size();
+  }
+  msfm_round_set_fetch(set, cam_pose.data(), cam_model.data(), R.data(), t.data(), c.data(), nullptr, xyz.data(), mut.data(), bad.data(), mse.data(),
+                       added.data(), nullptr, round_counts_, &round_adjust_[0][0], round_solved_, round_summary_);
+  msfm_round_set_destroy(set);
+  // BundleAdjuster::UpdateParameters and the flags, as the call reports them
+  const int m_new = model_of_cam[idx_new_cam];
+  std::vector<uint8_t> cam_free(nc, full ? 1 : 0);
+  if (!full) {
+    for (int k = 0; k < nc; k++) cam_free[k] = model_of_cam[k] == m_new;
+    for (int v : visible) cam_free[v] = 1;
+  }
+  for (int k = 0; k < nc; k++) {
+    Camera* cm = cams_[k];
+    for (int q = 0; q < 6; q++) cm->data[q] = cam_pose[6 * (size_t)k + q];
+    for (int q = 0; q < 3; q++) { cm->pos_ac_.a[q] = cm->data[q]; cm->pos_rt_.t[q] = t[3 * (size_t)k + q]; cm->pos_ac_.c[q] = c[3 * (size_t)k + q]; }
+    for (int q = 0; q < 9; q++) cm->pos_rt_.R.m[q] = R[9 * (size_t)k + q];
+    for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) cm->M[4 * r + q] = R[9 * (size_t)k + 3 * r + q]; cm->M[4 * r + 3] = t[3 * (size_t)k + r]; }
+    cm->is_mutable_ = cam_free[k] != 0;
+  }
+  for (int m = 0; m < nm; m++) {
+    for (int q = 0; q < 3; q++) cam_models_[m]->data[q] = cam_model[3 * (size_t)m + q];
+    cam_models_[m]->UpdataModelFromData();
+  }
+  for (int i = 0; i < np; i++) {
+    Point3D* p = pts_[i];
+    for (int q = 0; q < 3; q++) p->data[q] = xyz[3 * (size_t)i + q];
+    p->mse_ = mse[i]; p->is_bad_estimated_ = bad[i] != 0; p->is_mutable_ = mut[i] != 0; p->is_new_added_ = added[i] != 0;
+  }
+  const int last = full && round_solved_[1] ? 1 : 0;   // summary_: of the last adjustment
+  iterations_ = round_iterations_[last];
+  summary_ = round_summary_[last];
+  summary_.iterations = iterations_.data();
+}
+
 // The same function as the reference writes it, over the matches and keypoints in memory.
 void IncrementalSfM::GenerateNew3DPointsHost() {
   if (cams_.empty()) throw std::runtime_error("GenerateNew3DPointsHost: no camera");

@@ -243,6 +243,19 @@ class IncrementalSfM {
   // scripts/newpoints_bench.py times the batched call against, and a second opinion for tests/newpoints_host_check.cc.
   void GenerateNew3DPointsHost();
   int num_new_points_ = 0;                   // points the last of the two appended
+  // Run :172-186 (sfm_incremental.cc) for camera idx_new_cam in ONE msfm_round_adjust call: PartialBundleAdjustment(idx_new_cam),
+  // with `full` FullBundleAdjustment behind it, then RemovePointOutliers.  Both sides of the flat state are gathered from the
+  // std::maps - the camera side from Camera::pts_ as GenerateNew3DPoints gathers it, the point side (one row per observation)
+  // from Point3D::cams_ - and everything is written back: Camera::data / pos_rt_ / pos_ac_ / M and is_mutable_, CameraModel::data
+  // and f_, k1_, k2_, Point3D::data, is_mutable_, is_bad_estimated_, mse_, is_new_added_.  Needs SetMatches and SetKeypoints
+  // (the observations' coordinates are the keypoints, as :592-600 / :810-821 store them) and pts_[i]->id_ == i; no GPS rows.
+  // The three methods above remain the one-stage-at-a-time form.
+  void AdjustRound(int idx_new_cam, bool full);
+  int round_counts_[3] = {0, 0, 0};          // of the last AdjustRound: count_outliers, count_new_add, count_outliers_new_add (:1833-1862)
+  int round_adjust_[2][2] = {{0, 0}, {0, 0}};   // "adjust cams" / "adjust pts" (:962-963) of the partial and of the full solve
+  int round_solved_[2] = {0, 0};
+  msfm_ba_summary round_summary_[2] = {};    // (iterations point into round_iterations_)
+  std::vector<msfm_ba_iteration> round_iterations_[2];
   void SetKeypoints(const std::vector<float>& keypoints) { keypoints_ = keypoints; }   // [sum of n_features][2], images in order
   std::vector<float> keypoints_;
   std::vector<double> image_focal_;          // per image: f of its camera model in pixels, 0.0 = unknown (CameraModel::f_)

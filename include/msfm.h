@@ -886,6 +886,113 @@ int msfm_new_points_set_fetch(const msfm_new_points_set* set, int* pt_off /*[n_n
                               uint8_t* large, int* n_candidates, int* n_accepted);
 void msfm_new_points_set_destroy(msfm_new_points_set* set);
 
+/* ======================================================================================
+ *  Adjusting a round: partial / full bundle adjustment and the outlier removal in one call
+ * ====================================================================================== */
+/* The second half of a round of IncrementalSfM::Run (SfM/src/sfm_incremental.cc:172-186) on the flat state, behind
+ * msfm_localize_candidates / msfm_localize_poses / msfm_new_points: PartialBundleAdjustment(new_cam) (:917-1014), every fifth
+ * image FullBundleAdjustment (:1016-1026), RemovePointOutliers (:1831-1863).  The three switches do_partial / do_full /
+ * do_outliers pick the stages; they always run in that order (:174-186), each on what the one before left.  No GPS rows (the
+ * SLAM path has its own driver) and no Normalize / Perturb: found_seed_ is true before any round's adjustment (:141), so
+ * RunOptimizetion's is_initial_run is false.
+ * The state has both sides of the object graph.  feat_point is Camera::pts_ (as in msfm_new_points_problem); the rows
+ * obs_point / obs_cam / obs_feat [n_obs] are Point3D::cams_ / pts2d_, one row per Point3D::AddObservation (camera index, local
+ * feature), in any order.  The two differ wherever a Camera::AddPoints insert did not take (msfm_new_points' takes1 / takes2).
+ *   point side the observations of a point are ordered by the key of cams_ (structure.cc:134), feature + image * idx_max_per_image:
+ *              (image id, local feature) ascending - neither camera index order nor row order.  std::map::insert keeps the
+ *              first of several rows with one key; they carry the same keypoint, so which one cannot show.  pt_views[p] is
+ *              the number of distinct keys.  An observation's xy is the keypoint of (image, feature), float -> double
+ *              (:592-600, :810-821).
+ *   frozen     ImmutableCamsPoints (:1865-1878): every camera, and every point that occurs in some feat_point row, bad ones
+ *              included.  A point no camera holds keeps its incoming pt_mutable (Point3D::is_mutable_, 1 for a new point,
+ *              structure.cc:34): that is why the flag is state.
+ *   partial    (:919-945) frees every camera of new_cam's model and every camera of `visible` (new_cam's visible_cams_ as
+ *              listed, itself first), and for each freed camera the points of its own feat_point row that are not bad.
+ *   full       MutableCamsPoints (:1880-1893): every camera is free, every point held by some camera is free, bad ones
+ *              included; other points keep their flag.
+ *   gather     optimizer.cc:59-129: bad points are skipped, the others go in ascending id, rows in key order; weight 1.0 at
+ *              two views, weight_partial / weight_full at three or more, 1.0 otherwise.  What is handed to the solver is the
+ *              compact problem: only rows whose camera or point is free (the others get no residual block, :86-125), only
+ *              points with such a row, renumbered in ascending id; the masks pass through.  A stage whose problem has no
+ *              row is skipped: solved[stage] = 0, no error.
+ *   solve      msfm_ba_create + msfm_ba_run on device arrays (the route of msfm_chain_ba_create): parameters, summary and
+ *              iteration rows are those of msfm_ba_solve on the same arrays, bit for bit.  UpdateParameters: the points
+ *              return to their state ids on the device; cam_R / cam_t / cam_c = -R^T t / cam_fk are formed per camera as
+ *              Camera::UpdatePoseFromData (camera.cc:113-137) and UpdataModelFromData do, the angle-axis conversion on the
+ *              host inside the library with the C library's sin / cos.  "adjust cams" / "adjust pts" (:947-963) are the free
+ *              cameras and the free points of all pts_ at each solve.
+ *   outliers   bad points are skipped, their pt_mse and pt_new_added left as they are.  For every other point
+ *              Point3D::Reprojection (structure.cc:267-300) over its rows in key order: pt_c = M (X, 1); pt_c.z < 0 sets mse
+ *              100000.0 and returns at that row (strict: a NaN walks on); otherwise (u - x)^2 + (v - y)^2 is accumulated in
+ *              that order and divided by the row count (no row: 0 / 0).  sqrt(mse) > th_mse_outliers marks the point bad (a
+ *              NaN does not); pt_new_added is cleared for every visited point.  + - * / sqrt only, no fused multiply-add: a
+ *              sequential restatement in doubles agrees bit for bit.  counts = count_outliers, count_new_add,
+ *              count_outliers_new_add (:1833-1862).
+ * In : n_cams, cam_img, feat_point, n_points, keypoints as in msfm_new_points_problem (the store supplies n_features and,
+ *      made from a chain, the keypoints; otherwise `keypoints`); the rows; cam_pose [n_cams][6], cam_model [n_models][3],
+ *      cam_model_of_cam, model_mutable (optional) as in msfm_ba_problem; point_xyz [n_points][3], pt_bad, pt_mse, pt_mutable
+ *      [n_points]; pt_new_added (optional, NULL = all 0); new_cam (-1: none), visible [n_visible].
+ * Per call the host sends feat_point, the rows, the point arrays and flags and the cameras; h2d_bytes of
+ * msfm_round_set_size reports it (what msfm_ba_create sends of its own - cameras, masks - is not counted).  The host waits
+ * for the sizes of each stage's problem, where msfm_ba_create / msfm_ba_run wait themselves, for the cameras after a solve,
+ * and at the end (with keep_problem also for the assembled arrays).
+ * MSFM_E_INVAL: an index outside its array (feat_point and the rows are checked on the device before anything is indexed by
+ * them), new_cam or a visible camera outside n_cams, a cam_img outside the store or listed twice, no keypoints for an image
+ * that has an observation, do_partial without new_cam, a NaN or negative threshold or weight, and a key that does not fit
+ * the sort: the bit width of n_cams - 1 plus the bit width of the largest feature count - 1 must not exceed 32.  The
+ * context stays usable.  A set counts as a child of its context.
+ * msfm_round_set_fetch (every pointer may be NULL): cam_pose, cam_model, cam_R [n_cams][9], cam_t, cam_c, cam_fk [n_cams][3];
+ * point_xyz, pt_mutable (as the last solve set it), pt_bad, pt_mse, pt_new_added, pt_views [n_points]; counts [3]; adjust
+ * [2][2] = cams, pts of the partial and of the full solve; solved [2]; summary [2] (the caller's `iterations` /
+ * `iterations_capacity` are kept and filled).  msfm_round_set_fetch_problem (sets made with keep_problem): the assembled
+ * problem of stage 0 (partial) or 1 (full) - n_points, n_obs, kept [n_points] (the state id of every problem point), obs_cam,
+ * obs_pt [n_obs], obs_xy [n_obs][2], pt_weight [n_points], cam_mutable [n_cams], pt_mutable [n_points]. */
+typedef struct msfm_round_options {        /* msfm_round_default_options fills the reference's values */
+  msfm_ba_options partial;                 /* msfm_ba_options_default with 100 iterations  basic_structs.h:181-182 */
+  msfm_ba_options full;
+  double weight_partial;                   /* 2.0                  sfm_incremental.cc:1012 */
+  double weight_full;                      /* 1.0                  sfm_incremental.cc:1024 */
+  double th_mse_outliers;                  /* 1.0                  basic_structs.h:188 */
+  int32_t keep_problem;                    /* 1: keep each solve's assembled arrays for msfm_round_set_fetch_problem */
+} msfm_round_options;
+void msfm_round_default_options(msfm_round_options* opt);
+typedef struct msfm_round_problem {
+  int32_t n_cams;
+  const int32_t* cam_img;
+  const int32_t* feat_point;
+  int32_t n_points;
+  const float* keypoints;                  /* optional */
+  int32_t n_obs;
+  const int32_t* obs_point;
+  const int32_t* obs_cam;
+  const int32_t* obs_feat;
+  const double* cam_pose;
+  int32_t n_models;
+  const double* cam_model;
+  const int32_t* cam_model_of_cam;
+  const uint8_t* model_mutable;            /* optional */
+  const double* point_xyz;
+  const uint8_t* pt_bad;
+  const double* pt_mse;
+  const uint8_t* pt_mutable;
+  const uint8_t* pt_new_added;             /* optional */
+  int32_t new_cam;                         /* -1: none */
+  int32_t n_visible;
+  const int32_t* visible;
+  int32_t do_partial, do_full, do_outliers;
+} msfm_round_problem;
+typedef struct msfm_round_set msfm_round_set;
+int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* store, const msfm_round_problem* problem,
+                      const msfm_round_options* opt, msfm_round_set** out);
+int msfm_round_set_size(const msfm_round_set* set, int* n_cams, int* n_models, int* n_points, int64_t* h2d_bytes);
+int msfm_round_set_fetch(const msfm_round_set* set, double* cam_pose, double* cam_model, double* cam_R, double* cam_t, double* cam_c,
+                         double* cam_fk, double* point_xyz, uint8_t* pt_mutable, uint8_t* pt_bad, double* pt_mse, uint8_t* pt_new_added,
+                         int32_t* pt_views, int32_t* counts /*[3]*/, int32_t* adjust /*[2][2]*/, int32_t* solved /*[2]*/,
+                         msfm_ba_summary* summary /*[2]*/);
+int msfm_round_set_fetch_problem(const msfm_round_set* set, int stage, int* n_points, int* n_obs, int32_t* kept, int32_t* obs_cam,
+                                 int32_t* obs_pt, double* obs_xy, double* pt_weight, uint8_t* cam_mutable, uint8_t* pt_mutable);
+void msfm_round_set_destroy(msfm_round_set* set);
+
 /* ==================================================================================== *
  *  Single-process multi-GPU context
  * ==================================================================================== */

@@ -142,6 +142,22 @@ class NewPointsProblem(C.Structure):
                 ("vis_off", c_int_p), ("vis_cam", c_int_p), ("keypoints", c_float_p)]
 
 
+class RoundOptions(C.Structure):
+    """msfm_round_options (include/msfm.h)."""
+    _fields_ = [("partial", BaOptions), ("full", BaOptions), ("weight_partial", C.c_double), ("weight_full", C.c_double),
+                ("th_mse_outliers", C.c_double), ("keep_problem", C.c_int32)]
+
+
+class RoundProblem(C.Structure):
+    """msfm_round_problem (include/msfm.h)."""
+    _fields_ = [("n_cams", C.c_int32), ("cam_img", c_int_p), ("feat_point", c_int_p), ("n_points", C.c_int32), ("keypoints", c_float_p),
+                ("n_obs", C.c_int32), ("obs_point", c_int_p), ("obs_cam", c_int_p), ("obs_feat", c_int_p), ("cam_pose", c_double_p),
+                ("n_models", C.c_int32), ("cam_model", c_double_p), ("cam_model_of_cam", c_int_p), ("model_mutable", c_u8_p),
+                ("point_xyz", c_double_p), ("pt_bad", c_u8_p), ("pt_mse", c_double_p), ("pt_mutable", c_u8_p), ("pt_new_added", c_u8_p),
+                ("new_cam", C.c_int32), ("n_visible", C.c_int32), ("visible", c_int_p), ("do_partial", C.c_int32), ("do_full", C.c_int32),
+                ("do_outliers", C.c_int32)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

@@ -29,6 +29,8 @@ SYMBOLS = [
     "msfm_localize_pose_set_destroy",
     "msfm_seed_default_options", "msfm_seed_hypotheses", "msfm_seed_set_size", "msfm_seed_set_fetch", "msfm_seed_set_destroy",
     "msfm_new_points_default_options", "msfm_new_points", "msfm_new_points_set_size", "msfm_new_points_set_fetch", "msfm_new_points_set_destroy",
+    "msfm_round_default_options", "msfm_round_adjust", "msfm_round_set_size", "msfm_round_set_fetch", "msfm_round_set_fetch_problem",
+    "msfm_round_set_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
@@ -182,6 +184,16 @@ def lib():
                                             A.c_u8_p, A.c_u8_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p]
     L.msfm_new_points_set_destroy.argtypes = [vp]
     L.msfm_new_points_set_destroy.restype = None
+    L.msfm_round_default_options.argtypes = [C.POINTER(A.RoundOptions)]
+    L.msfm_round_default_options.restype = None
+    L.msfm_round_adjust.argtypes = [vp, vp, C.POINTER(A.RoundProblem), C.POINTER(A.RoundOptions), C.POINTER(vp)]
+    L.msfm_round_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
+    L.msfm_round_set_fetch.argtypes = [vp] + [A.c_double_p] * 7 + [A.c_u8_p, A.c_u8_p, A.c_double_p, A.c_u8_p, A.c_int_p, A.c_int_p, A.c_int_p,
+                                              A.c_int_p, C.POINTER(A.BaSummary)]
+    L.msfm_round_set_fetch_problem.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p, A.c_u8_p,
+                                               A.c_u8_p]
+    L.msfm_round_set_destroy.argtypes = [vp]
+    L.msfm_round_set_destroy.restype = None
     L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
     L.msfm_multi_destroy.argtypes = [vp]
     L.msfm_multi_destroy.restype = None
@@ -257,6 +269,24 @@ def new_points_options(**kw):
         if not hasattr(o, k):
             raise AttributeError(k)
         setattr(o, k, v)
+    return o
+
+
+def round_options(**kw):
+    """msfm_round_options with the reference's values (100 iterations for both solves, weights 2.0 / 1.0, 1.0 px); keywords
+    override fields, `partial` / `full` take a dict of msfm_ba_options fields."""
+    o = A.RoundOptions()
+    lib().msfm_round_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        if k in ("partial", "full") and isinstance(v, dict):
+            for sk, sv in v.items():
+                if not hasattr(getattr(o, k), sk):
+                    raise AttributeError(sk)
+                setattr(getattr(o, k), sk, sv)
+        else:
+            setattr(o, k, v)
     return o
 
 
@@ -594,6 +624,97 @@ class Context:
         return {"pt_off": poff, "cam2": cam2[:npt], "feat1": f1[:npt], "feat2": f2[:npt], "vis_entry": ve[:npt], "pt_match": ptm[:npt],
                 "X": X[:npt], "mse": mse[:npt], "takes1": t1[:npt], "takes2": t2[:npt], "n_matches": nm[:ne], "large": large[:ne],
                 "n_candidates": ncand[:ne], "n_accepted": nacc[:ne], "h2d_bytes": nb.value}
+
+    def round_adjust(self, store, cam_img, feat_point, obs_point, obs_cam, obs_feat, cam_pose, cam_model, cam_model_of_cam, point_xyz, pt_bad,
+                     pt_mse, pt_mutable, pt_new_added=None, new_cam=-1, visible=(), partial=True, full=False, outliers=True, model_mutable=None,
+                     keypoints=None, capacity=512, **opts):
+        """msfm_round_adjust (sfm_incremental.cc:172-186): PartialBundleAdjustment(new_cam), FullBundleAdjustment and
+        RemovePointOutliers - the stages `partial` / `full` / `outliers` switch on, in that order - on the flat state with both of
+        its sides: feat_point (Camera::pts_) and the rows obs_point / obs_cam / obs_feat (Point3D::cams_).  opts: fields of
+        msfm_round_options (`partial_options` / `full_options`: dicts of msfm_ba_options fields).  Returns a dict: cam_pose,
+        cam_model, cam_R [n][3][3], cam_t, cam_c, cam_fk, point_xyz, pt_mutable, pt_bad, pt_mse, pt_new_added, pt_views,
+        count_outliers, count_new_add, count_outliers_new_add, adjust_cams / adjust_pts [2], solved [2], summary (a list of two:
+        the summary dict of `ba_solve`, or None for a stage that did not solve), h2d_bytes and, with keep_problem=1, problem (a
+        list of two dicts: kept, obs_cam, obs_pt, obs_xy, pt_weight, cam_mutable, pt_mutable)."""
+        ip, dp, up = A.c_int_p, A.c_double_p, A.c_u8_p
+        cam_img, feat_point, obs_point, obs_cam, obs_feat, mcam, visible = (A.as_c(np.asarray(x, dtype=np.int32).reshape(-1), np.int32) for x in (
+            cam_img, feat_point, obs_point, obs_cam, obs_feat, cam_model_of_cam, visible))
+        nc, no = len(cam_img), len(obs_point)
+        pose = A.as_c(np.asarray(cam_pose, dtype=np.float64).reshape(-1, 6), np.float64)
+        model = A.as_c(np.asarray(cam_model, dtype=np.float64).reshape(-1, 3), np.float64)
+        xyz = A.as_c(np.asarray(point_xyz, dtype=np.float64).reshape(-1, 3), np.float64)
+        mse = A.as_c(np.asarray(pt_mse, dtype=np.float64).reshape(-1), np.float64)
+        bad, mut = (A.as_c(np.asarray(x, dtype=np.uint8).reshape(-1), np.uint8) for x in (pt_bad, pt_mutable))
+        added = None if pt_new_added is None else A.as_c(np.asarray(pt_new_added, dtype=np.uint8).reshape(-1), np.uint8)
+        mm = None if model_mutable is None else A.as_c(np.asarray(model_mutable, dtype=np.uint8).reshape(-1), np.uint8)
+        npt, nm = len(xyz), len(model)
+        if not (len(pose) == len(mcam) == nc):
+            raise ValueError("cam_img, cam_pose and cam_model_of_cam must describe the same number of cameras")
+        if not (len(obs_cam) == len(obs_feat) == no):
+            raise ValueError("obs_point, obs_cam and obs_feat must hold one entry per observation")
+        if not (len(mse) == len(bad) == len(mut) == npt) or (added is not None and len(added) != npt):
+            raise ValueError("point_xyz, pt_bad, pt_mse, pt_mutable and pt_new_added must hold one entry per point")
+        if mm is not None and len(mm) != nm:
+            raise ValueError("model_mutable must hold one entry per model")
+        in_store = (cam_img >= 0) & (cam_img < len(store.n_features))     # (an image outside the store: the library reports it)
+        if in_store.all() and len(feat_point) != int(store.n_features[cam_img].sum()):
+            raise ValueError("feat_point must hold one entry per feature of every camera's image")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        P = A.RoundProblem(nc, A.ptr(cam_img, ip), A.ptr(feat_point, ip), npt, A.ptr(kp, A.c_float_p), no, A.ptr(obs_point, ip), A.ptr(obs_cam, ip),
+                           A.ptr(obs_feat, ip), A.ptr(pose, dp), nm, A.ptr(model, dp), A.ptr(mcam, ip), A.ptr(mm, up), A.ptr(xyz, dp), A.ptr(bad, up),
+                           A.ptr(mse, dp), A.ptr(mut, up), A.ptr(added, up), int(new_cam), len(visible), A.ptr(visible, ip), int(bool(partial)),
+                           int(bool(full)), int(bool(outliers)))
+        opts = dict(opts)
+        for k in ("partial", "full"):
+            if k + "_options" in opts:
+                opts[k] = opts.pop(k + "_options")
+        o = round_options(**opts)
+        h = C.c_void_p()
+        self.check(lib().msfm_round_adjust(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
+        try:
+            nb = C.c_int64()
+            lib().msfm_round_set_size(h, None, None, None, C.byref(nb))
+            c1, m1, p1 = max(1, nc), max(1, nm), max(1, npt)
+            o_pose, o_model, o_R = np.zeros((c1, 6)), np.zeros((m1, 3)), np.zeros((c1, 3, 3))
+            o_t, o_c, o_fk, o_xyz, o_mse = np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((p1, 3)), np.zeros(p1)
+            o_mut, o_bad, o_added, o_views = np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.int32)
+            counts, adjust, solved = np.zeros(3, np.int32), np.zeros((2, 2), np.int32), np.zeros(2, np.int32)
+            bufs = [A.SummaryBuf(capacity), A.SummaryBuf(capacity)]
+            sums = (A.BaSummary * 2)()
+            for k in range(2):
+                sums[k].iterations, sums[k].iterations_capacity = bufs[k].struct.iterations, capacity
+            self.check(lib().msfm_round_set_fetch(h, A.ptr(o_pose, dp), A.ptr(o_model, dp), A.ptr(o_R, dp), A.ptr(o_t, dp), A.ptr(o_c, dp), A.ptr(o_fk, dp),
+                                                  A.ptr(o_xyz, dp), A.ptr(o_mut, up), A.ptr(o_bad, up), A.ptr(o_mse, dp), A.ptr(o_added, up),
+                                                  A.ptr(o_views, ip), A.ptr(counts, ip), A.ptr(adjust, ip), A.ptr(solved, ip), sums))
+            summary = []
+            for k in range(2):
+                C.memmove(C.byref(bufs[k].struct), C.byref(sums[k]), C.sizeof(A.BaSummary))
+                summary.append(bufs[k].result() if solved[k] else None)
+            out = {"cam_pose": o_pose[:nc], "cam_model": o_model[:nm], "cam_R": o_R[:nc], "cam_t": o_t[:nc], "cam_c": o_c[:nc], "cam_fk": o_fk[:nc],
+                   "point_xyz": o_xyz[:npt], "pt_mutable": o_mut[:npt], "pt_bad": o_bad[:npt], "pt_mse": o_mse[:npt], "pt_new_added": o_added[:npt],
+                   "pt_views": o_views[:npt], "count_outliers": int(counts[0]), "count_new_add": int(counts[1]),
+                   "count_outliers_new_add": int(counts[2]), "adjust_cams": adjust[:, 0].copy(), "adjust_pts": adjust[:, 1].copy(), "solved": solved,
+                   "summary": summary, "h2d_bytes": nb.value}
+            if o.keep_problem:
+                out["problem"] = []
+                for stage in range(2):
+                    n_p, n_o = C.c_int32(), C.c_int32()
+                    self.check(lib().msfm_round_set_fetch_problem(h, stage, C.byref(n_p), C.byref(n_o), None, None, None, None, None, None, None))
+                    n_p, n_o = n_p.value, n_o.value
+                    kept, q_cam, q_pt = np.zeros(max(1, n_p), np.int32), np.zeros(max(1, n_o), np.int32), np.zeros(max(1, n_o), np.int32)
+                    q_xy, q_w = np.zeros((max(1, n_o), 2)), np.zeros(max(1, n_p))
+                    q_cm, q_pm = np.zeros(c1, np.uint8), np.zeros(max(1, n_p), np.uint8)
+                    ran = bool(partial) if stage == 0 else bool(full)
+                    if ran:
+                        self.check(lib().msfm_round_set_fetch_problem(h, stage, None, None, A.ptr(kept, ip), A.ptr(q_cam, ip), A.ptr(q_pt, ip), A.ptr(q_xy, dp),
+                                                                      A.ptr(q_w, dp), A.ptr(q_cm, up), A.ptr(q_pm, up)))
+                    out["problem"].append({"kept": kept[:n_p], "obs_cam": q_cam[:n_o], "obs_pt": q_pt[:n_o], "obs_xy": q_xy[:n_o], "pt_weight": q_w[:n_p],
+                                           "cam_mutable": q_cm[:nc if ran else 0], "pt_mutable": q_pm[:n_p]})
+        finally:
+            lib().msfm_round_set_destroy(h)
+        return out
 
     def triangulate_midpoint(self, tracks, th_error, th_angle, X0=None):
         return self._tri(lib().msfm_triangulate_midpoint_batch, tracks, th_error, th_angle, X0)

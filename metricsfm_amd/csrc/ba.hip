@@ -3889,6 +3889,10 @@ MSFM_API int msfm_ba_download_params(msfm_ba* ba, double* cam_pose, double* cam_
   return MSFM_OK;
 }
 
+// The resident points of a problem, [n_points][3] in the caller's order: adjust.hip scatters them back to their state ids
+// on the device instead of taking them through the host.
+const double* ba_device_points(const msfm_ba* ba) { return ba->pt.p; }
+
 // ---- phases ----------------------------------------------------------------------------
 static BaPtrs make_ptrs(msfm_ba* ba, bool candidate, double huber) {
   BaPtrs P;

@@ -305,6 +305,7 @@ struct msfm_ba_problem;
 struct msfm_ba;
 // msfm_ba_create with the bulk arrays of the problem (obs_cam, obs_pt, obs_xy, point, pt_weight, pt_mutable) in DEVICE memory
 int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device, msfm_ba** out);
+const double* ba_device_points(const msfm_ba* ba);   // the resident points [n_points][3] of a problem (adjust.hip scatters them on the device)
 int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_off, const int* d_nf, const int* d_fo, int n_pairs,
                      const int* d_pair, const int* d_moff, const int* d_match, int M, msfm_track_dev* out);
 

@@ -5,7 +5,7 @@ Run :143-164 around LocalizeImage (:565-753) through one msfm_localize_poses cal
 device (`localize_next_image`), and LocalizeImage's state changes on the flat state (`apply_localized_image`)."""
 import numpy as np
 
-from . import capi
+from . import adjust, capi
 
 TH_MAX_FAILURE_LOCALIZATION = 5   # basic_structs.h:176
 
@@ -96,7 +96,9 @@ def apply_localized_image(state, result, k1=0.0, k2=0.0):
     appended (cam_img; a feat_point row of -1 with the state-2 features set, Camera::AddPoints :725; cam_R, cam_t, cam_c = -R^T t
     as SetRTPose keeps it; cam_fk = (f, k1, k2)), the state-1 points become bad (:715), the state-2 points gain a view and
     is_new_added_ (:723-724; pt_new_added is created when the state has none).  Returns the new camera's visible list as
-    UpdateVisibleGraph (:1895-1903) builds it: itself, then the visible cameras - what `newpoints.generate_new_points` takes."""
+    UpdateVisibleGraph (:1895-1903) builds it: itself, then the visible cameras - what `newpoints.generate_new_points` takes.
+    A state with the point side (obs_point / obs_cam / obs_feat, `newpoints.py`) gets one row per state-2 correspondence, in
+    correspondence order (Point3D::AddObservation, :723)."""
     if result["image"] < 0:
         raise ValueError("no image was localised")
     im = int(result["image"])
@@ -123,4 +125,5 @@ def apply_localized_image(state, result, k1=0.0, k2=0.0):
     added = np.array(state["pt_new_added"], dtype=np.uint8) if "pt_new_added" in state else np.zeros(len(bad), np.uint8)
     added[pt[st == 2]] = 1
     state["pt_new_added"] = added
+    adjust.append_observations(state, pt[st == 2], np.full(int((st == 2).sum()), new_cam, np.int32), feat[st == 2])
     return [new_cam] + [int(c) for c in result["visible"]]

@@ -5,12 +5,19 @@ state the next round reads (`apply_new_points`, :899-910).
 The flat state is a dict in the layout `localize.find_images_to_localize` and `window.partial_bundle_adjustment_problem` read:
   n_features [n_images]; cam_img [n_cams]; feat_point (camera c starts at the sum of n_features[cam_img[c']] over c' < c;
   local feature -> point id or -1); cam_R [n_cams][3][3], cam_t, cam_c, cam_fk [n_cams][3]; point_xyz [n_points][3], pt_bad,
-  pt_mse, pt_views [n_points]."""
+  pt_mse, pt_views [n_points].
+Optional keys, the point side (the state above keeps only the camera side, Camera::pts_; `adjust.adjust_round` needs both):
+  obs_point, obs_cam, obs_feat [n_obs] int32: Point3D::cams_ / pts2d_, one row per Point3D::AddObservation in call order -
+  point id, camera index, local feature.  The two sides differ wherever a Camera::AddPoints insert did not take (takes1 /
+  takes2 below): the observation exists, the feat_point entry belongs to an earlier point.
+  pt_mutable [n_points] uint8: Point3D::is_mutable_, 1 for a new point (structure.cc:34).
+`adjust.point_side_from_seed` makes them from a seed result; `apply_new_points` and `localize.apply_localized_image` keep them up
+to date when the state has them, and behave as before when it has not.  pt_new_added [n_points] (is_new_added_) is optional too."""
 from collections import namedtuple
 
 import numpy as np
 
-from . import capi
+from . import adjust, capi
 
 NewPoints = namedtuple("NewPoints", "X mse cam2 feat1 feat2 takes1 takes2")
 
@@ -45,4 +52,10 @@ def apply_new_points(state, result, new_cam=None):
     state["pt_mse"] = np.concatenate([np.asarray(state["pt_mse"], dtype=np.float64), r.mse])
     state["pt_views"] = np.concatenate([np.asarray(state["pt_views"], dtype=np.int32), np.full(n, 2, np.int32)])
     state["pt_bad"] = np.concatenate([np.asarray(state["pt_bad"], dtype=np.uint8), np.zeros(n, np.uint8)])
+    if "obs_point" in state:   # Point3D::AddObservation of both views (:810-821), whether or not the camera-side inserts took
+        adjust.append_observations(state, np.repeat(ids, 2), np.column_stack([np.full(n, c1, np.int32), r.cam2]), np.column_stack([r.feat1, r.feat2]))
+    if "pt_new_added" in state:   # is_new_added_ = true, :819
+        state["pt_new_added"] = np.concatenate([np.asarray(state["pt_new_added"], dtype=np.uint8), np.ones(n, np.uint8)])
+    if "pt_mutable" in state:
+        state["pt_mutable"] = np.concatenate([np.asarray(state["pt_mutable"], dtype=np.uint8), np.ones(n, np.uint8)])
     return ids
