@@ -993,6 +993,116 @@ int msfm_round_set_fetch_problem(const msfm_round_set* set, int stage, int* n_po
                                  int32_t* obs_pt, double* obs_xy, double* pt_weight, uint8_t* cam_mutable, uint8_t* pt_mutable);
 void msfm_round_set_destroy(msfm_round_set* set);
 
+/* ======================================================================================
+ *  The resident state: a model's flat state kept on the device across its rounds
+ * ====================================================================================== */
+/* msfm_round_adjust sends the whole flat state with every call and reads every point array back.  A msfm_recon keeps that
+ * state on the device: it is uploaded once, when the object is made, and msfm_recon_adjust runs the round's adjustment on it
+ * in place.  The object is a child of its context and is bound to one match store, which must outlive it.
+ *   device  feat_point (room for every feature of the store: an image has at most one camera), obs_point / obs_cam /
+ *           obs_feat, point_xyz, pt_bad, pt_mse, pt_views, pt_mutable, pt_new_added, and the keypoints of a store that was
+ *           not made from a chain (all images' rows, in the store's order).  Capacity and length are kept apart:
+ *           reserve_points / reserve_obs ask for room beyond the initial lengths.
+ *   host    inside the object, O(cameras): cam_img, cam_pose, cam_model, cam_model_of_cam, model_mutable, cam_R, cam_t,
+ *           cam_c, cam_fk. */
+/* msfm_recon_create: the fields of msfm_recon_init are those of msfm_round_problem plus pt_views and the cameras as the
+ * flat state keeps them (cam_R [n_cams][9], cam_t, cam_c, cam_fk [n_cams][3]).  It is the only call that sends anything that
+ * scales with points, observations or features.  The host waits once, for the answer of the index check.  MSFM_E_INVAL is what
+ * msfm_round_adjust refuses of a state: a feat_point entry >= n_points or a row with an index outside its array (checked on
+ * the device; nothing is kept of a refused state), a cam_img outside the store or listed twice, a cam_model_of_cam outside
+ * n_models, no keypoints for an image that has an observation, a key that does not fit the sort. */
+typedef struct msfm_recon_init {
+  int32_t n_cams;
+  const int32_t* cam_img;
+  const int32_t* feat_point;
+  int32_t n_points;
+  const float* keypoints;                  /* optional: [sum of the store's n_features][2] */
+  int32_t n_obs;
+  const int32_t* obs_point;
+  const int32_t* obs_cam;
+  const int32_t* obs_feat;
+  const double* cam_pose;
+  int32_t n_models;
+  const double* cam_model;
+  const int32_t* cam_model_of_cam;
+  const uint8_t* model_mutable;            /* optional */
+  const double* cam_R;
+  const double* cam_t;
+  const double* cam_c;
+  const double* cam_fk;
+  const double* point_xyz;
+  const uint8_t* pt_bad;
+  const double* pt_mse;
+  const int32_t* pt_views;
+  const uint8_t* pt_mutable;
+  const uint8_t* pt_new_added;             /* optional */
+  int32_t reserve_points, reserve_obs;     /* capacities to start with, where larger than n_points / n_obs */
+} msfm_recon_init;
+typedef struct msfm_recon msfm_recon;
+int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* store, const msfm_recon_init* init, msfm_recon** out);
+/* msfm_recon_size: the lengths, the capacities in elements, and the bytes sent to the device since (and including) creation.
+ * msfm_recon_fetch downloads the state (every pointer may be NULL; the host waits once): cam_img [n_cams], feat_point [the
+ * cameras' features, camera after camera], the rows [n_obs], the point arrays [n_points], the camera tables. */
+int msfm_recon_size(const msfm_recon* recon, int* n_cams, int* n_models, int* n_points, int* n_obs, int64_t* cap_points,
+                    int64_t* cap_obs, int64_t* h2d_bytes);
+int msfm_recon_fetch(msfm_recon* recon, int32_t* cam_img, int32_t* feat_point, int32_t* obs_point, int32_t* obs_cam, int32_t* obs_feat,
+                     double* point_xyz, uint8_t* pt_bad, double* pt_mse, int32_t* pt_views, uint8_t* pt_mutable, uint8_t* pt_new_added,
+                     double* cam_pose, double* cam_model, int32_t* cam_model_of_cam, double* cam_R, double* cam_t, double* cam_c,
+                     double* cam_fk);
+/* msfm_recon_localize is FindImageToLocalize (msfm_localize_candidates) plus the try loop of Run :143-164 (msfm_localize_poses)
+ * on the resident arrays; the library walks the ranked rows in chunks of opt->max_tries itself (first_row / next_row) until a
+ * row passes or the rows run out.  cand_img [n_cand] strictly ascending with fail_times, cand_f (0.0: the sweep arm around
+ * cand_f_init) per candidate.  Sent: the candidate lists, four integers per walked pair, per chunk the rows' tables.  The state
+ * is not written.  The winner (image = -1: none) comes back in msfm_recon_winner, whose counts size msfm_recon_localize_fetch:
+ * ranked [n_ranked] image ids, failed [n_failed] (the tried rows ahead of the winner; all tried rows without one), visible
+ * [n_visible] (the winner's visible cameras).  The winner row's corr_feat / corr_point / corr_state stay on the device inside
+ * the object as a pending localisation; the next localize call that succeeds or the destroy call drops them; a
+ * refused call leaves the lists and the pending winner of the call before as they were.  MSFM_E_INVAL: what the two
+ * flat calls refuse (a registered candidate, cand_img not ascending, option ranges). */
+typedef struct msfm_recon_winner {
+  int32_t image, row;                      /* -1: no row passed */
+  int32_t n_corr, n_inliers, n_outliers;   /* of the winner's row */
+  int32_t n_ranked, n_failed, n_visible, n_chunks;
+  double f, R[9], t[3], avg_error;
+} msfm_recon_winner;
+int msfm_recon_localize(msfm_recon* recon, int n_cand, const int32_t* cand_img, const int32_t* fail_times, const double* cand_f,
+                        const double* cand_f_init, const msfm_localize_pose_options* opt, msfm_recon_winner* out);
+int msfm_recon_localize_fetch(const msfm_recon* recon, int32_t* ranked, int32_t* failed, int32_t* visible);
+/* msfm_recon_commit_camera is LocalizeImage :705-748 for the pending winner, on the device: the new camera's feat_point row
+ * is filled with -1 and gets the state-2 correspondences, state 1 marks its point bad, state 2 gives its point a view and
+ * pt_new_added and appends one row, in correspondence order (an exclusive scan of state == 2).  The host supplies the
+ * angle-axis block cam_pose6 and the model: an existing index, or n_models to append cam_model3 (model_mutable: its flag).
+ * cam_R / cam_t are the localised values, cam_c = -(R^T t), cam_fk = (the localised f, the model's k1, k2).  Nothing that scales with the state is sent.
+ * visible (optional) [1 + n_visible]: the camera itself, then the winner's visible cameras.  MSFM_E_INVAL, before any write:
+ * no pending winner (none found, or committed already), a model beyond n_models, a new model without cam_model3. */
+int msfm_recon_commit_camera(msfm_recon* recon, const double* cam_pose6, int model, const double* cam_model3, int model_mutable, int* new_cam,
+                             int32_t* visible);
+/* msfm_recon_new_points is msfm_new_points for one camera of the state and its visible list on the resident feat_point and
+ * keypoints, followed by sfm_incremental.cc:899-910 on the device: every new point is appended (xyz, its mse, two views, not
+ * bad, new, mutable), its two rows (id, new_cam, feat1), (id, cam2, feat2) go behind the existing rows, and feat_point gets the
+ * inserts that took - what newpoints.apply_new_points does to the flat state.  Sent: the walk's tables and the cameras of the
+ * visible list (O(visible)).  The host waits twice: for the accepted counts, which size the append (n_new; arrays that are too
+ * short move into blocks of twice the need first, device to device), and at the end.  stats (optional, may be NULL): the whole
+ * msfm_new_points_set of the call for msfm_new_points_set_fetch - that read-back is the flat call's; destroy it with
+ * msfm_new_points_set_destroy.  MSFM_E_INVAL is what msfm_new_points refuses - new_cam or a visible camera outside n_cams, a
+ * NaN or out-of-range threshold, no keypoints of an involved image - and is found before the first write. */
+int msfm_recon_new_points(msfm_recon* recon, int new_cam, int n_visible, const int32_t* visible, const msfm_new_points_options* opt,
+                          int* n_new, msfm_new_points_set** stats);
+/* msfm_recon_adjust is msfm_round_adjust on the resident arrays: the same stages, rules, kernels and waits (see there).  It
+ * sends the camera tables only - per camera a handful of integers and flags and, for the outlier stage, 15 doubles; nothing
+ * that scales with points or rows.  point_xyz, pt_bad, pt_mse, pt_new_added and (after a solve) pt_mutable are written in
+ * place; pt_views is not written; the cameras and models are updated in the object's host tables.  The result is a
+ * msfm_round_set without point arrays: msfm_round_set_size reports n_points = 0 and this call's h2d_bytes,
+ * msfm_round_set_fetch leaves the point pointers untouched and fills cameras, counts, adjust, solved and the summaries;
+ * msfm_round_set_fetch_problem works as ever.  MSFM_E_INVAL - new_cam or a visible camera outside n_cams, do_partial without
+ * new_cam, a NaN or negative threshold or weight - is found before the first write: the state is what it was and the context
+ * stays usable.  What a solve itself reports (msfm_ba_create / msfm_ba_run) comes after the first stage may have written its
+ * points, while the host tables keep the cameras of before the call: such an object is to be destroyed. */
+int msfm_recon_adjust(msfm_recon* recon, int new_cam, int n_visible, const int32_t* visible, int do_partial, int do_full, int do_outliers,
+                      const msfm_round_options* opt, msfm_round_set** out);
+/* msfm_recon_destroy waits for the context's stream before the blocks go back to the pool. */
+void msfm_recon_destroy(msfm_recon* recon);
+
 /* ==================================================================================== *
  *  Single-process multi-GPU context
  * ==================================================================================== */

@@ -158,6 +158,23 @@ class RoundProblem(C.Structure):
                 ("do_outliers", C.c_int32)]
 
 
+class ReconInit(C.Structure):
+    """msfm_recon_init (include/msfm.h)."""
+    _fields_ = [("n_cams", C.c_int32), ("cam_img", c_int_p), ("feat_point", c_int_p), ("n_points", C.c_int32), ("keypoints", c_float_p),
+                ("n_obs", C.c_int32), ("obs_point", c_int_p), ("obs_cam", c_int_p), ("obs_feat", c_int_p), ("cam_pose", c_double_p),
+                ("n_models", C.c_int32), ("cam_model", c_double_p), ("cam_model_of_cam", c_int_p), ("model_mutable", c_u8_p),
+                ("cam_R", c_double_p), ("cam_t", c_double_p), ("cam_c", c_double_p), ("cam_fk", c_double_p),
+                ("point_xyz", c_double_p), ("pt_bad", c_u8_p), ("pt_mse", c_double_p), ("pt_views", c_int_p), ("pt_mutable", c_u8_p),
+                ("pt_new_added", c_u8_p), ("reserve_points", C.c_int32), ("reserve_obs", C.c_int32)]
+
+
+class ReconWinner(C.Structure):
+    """msfm_recon_winner (include/msfm.h)."""
+    _fields_ = [("image", C.c_int32), ("row", C.c_int32), ("n_corr", C.c_int32), ("n_inliers", C.c_int32), ("n_outliers", C.c_int32),
+                ("n_ranked", C.c_int32), ("n_failed", C.c_int32), ("n_visible", C.c_int32), ("n_chunks", C.c_int32),
+                ("f", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("avg_error", C.c_double)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

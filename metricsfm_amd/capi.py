@@ -31,6 +31,9 @@ SYMBOLS = [
     "msfm_new_points_default_options", "msfm_new_points", "msfm_new_points_set_size", "msfm_new_points_set_fetch", "msfm_new_points_set_destroy",
     "msfm_round_default_options", "msfm_round_adjust", "msfm_round_set_size", "msfm_round_set_fetch", "msfm_round_set_fetch_problem",
     "msfm_round_set_destroy",
+    "msfm_recon_create", "msfm_recon_size", "msfm_recon_fetch", "msfm_recon_adjust", "msfm_recon_new_points", "msfm_recon_localize", "msfm_recon_localize_fetch",
+    "msfm_recon_commit_camera",
+    "msfm_recon_destroy",
     "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
@@ -194,6 +197,18 @@ def lib():
                                                A.c_u8_p]
     L.msfm_round_set_destroy.argtypes = [vp]
     L.msfm_round_set_destroy.restype = None
+    i64p = C.POINTER(C.c_int64)
+    L.msfm_recon_create.argtypes = [vp, vp, C.POINTER(A.ReconInit), C.POINTER(vp)]
+    L.msfm_recon_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, i64p, i64p, i64p]
+    L.msfm_recon_fetch.argtypes = [vp] + [A.c_int_p] * 5 + [A.c_double_p, A.c_u8_p, A.c_double_p, A.c_int_p, A.c_u8_p, A.c_u8_p, A.c_double_p,
+                                          A.c_double_p, A.c_int_p] + [A.c_double_p] * 4
+    L.msfm_recon_adjust.argtypes = [vp, i, i, A.c_int_p, i, i, i, C.POINTER(A.RoundOptions), C.POINTER(vp)]
+    L.msfm_recon_new_points.argtypes = [vp, i, i, A.c_int_p, C.POINTER(A.NewPointsOptions), A.c_int_p, C.POINTER(vp)]
+    L.msfm_recon_localize.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p, C.POINTER(A.LocalizePoseOptions), C.POINTER(A.ReconWinner)]
+    L.msfm_recon_localize_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p]
+    L.msfm_recon_commit_camera.argtypes = [vp, A.c_double_p, i, A.c_double_p, i, A.c_int_p, A.c_int_p]
+    L.msfm_recon_destroy.argtypes = [vp]
+    L.msfm_recon_destroy.restype = None
     L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
     L.msfm_multi_destroy.argtypes = [vp]
     L.msfm_multi_destroy.restype = None
@@ -375,6 +390,69 @@ def slam_prior_options(**kw):
     return o
 
 
+def _new_points_set_result(h, nn):
+    """The dict `Context.new_points` documents from a msfm_new_points_set of nn new cameras (the caller destroys it)."""
+    dp, ip, up = A.c_double_p, A.c_int_p, A.c_u8_p
+    n1, npt, ne, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+    lib().msfm_new_points_set_size(h, C.byref(n1), C.byref(npt), C.byref(ne), C.byref(nb))
+    npt, ne = npt.value, ne.value
+    m, e = max(1, npt), max(1, ne)
+    poff = np.zeros(nn + 1, np.int32)
+    cam2, f1, f2, ve, ptm = (np.zeros(m, np.int32) for _ in range(5))
+    X, mse, t1, t2 = np.zeros((m, 3)), np.zeros(m), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
+    nm, ncand, nacc, large = np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.uint8)
+    lib().msfm_new_points_set_fetch(h, A.ptr(poff, ip), A.ptr(cam2, ip), A.ptr(f1, ip), A.ptr(f2, ip), A.ptr(ve, ip), A.ptr(ptm, ip),
+                                    A.ptr(X, dp), A.ptr(mse, dp), A.ptr(t1, up), A.ptr(t2, up), A.ptr(nm, ip), A.ptr(large, up),
+                                    A.ptr(ncand, ip), A.ptr(nacc, ip))
+    return {"pt_off": poff, "cam2": cam2[:npt], "feat1": f1[:npt], "feat2": f2[:npt], "vis_entry": ve[:npt], "pt_match": ptm[:npt],
+            "X": X[:npt], "mse": mse[:npt], "takes1": t1[:npt], "takes2": t2[:npt], "n_matches": nm[:ne], "large": large[:ne],
+            "n_candidates": ncand[:ne], "n_accepted": nacc[:ne], "h2d_bytes": nb.value}
+
+
+def _round_set_result(ctx, h, nc, nm, npt, partial, full, keep_problem, capacity):
+    """The dict `Context.round_adjust` documents from a msfm_round_set (the caller destroys it)."""
+    ip, dp, up = A.c_int_p, A.c_double_p, A.c_u8_p
+    nb = C.c_int64()
+    lib().msfm_round_set_size(h, None, None, None, C.byref(nb))
+    c1, m1, p1 = max(1, nc), max(1, nm), max(1, npt)
+    o_pose, o_model, o_R = np.zeros((c1, 6)), np.zeros((m1, 3)), np.zeros((c1, 3, 3))
+    o_t, o_c, o_fk, o_xyz, o_mse = np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((p1, 3)), np.zeros(p1)
+    o_mut, o_bad, o_added, o_views = np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.int32)
+    counts, adjust, solved = np.zeros(3, np.int32), np.zeros((2, 2), np.int32), np.zeros(2, np.int32)
+    bufs = [A.SummaryBuf(capacity), A.SummaryBuf(capacity)]
+    sums = (A.BaSummary * 2)()
+    for k in range(2):
+        sums[k].iterations, sums[k].iterations_capacity = bufs[k].struct.iterations, capacity
+    ctx.check(lib().msfm_round_set_fetch(h, A.ptr(o_pose, dp), A.ptr(o_model, dp), A.ptr(o_R, dp), A.ptr(o_t, dp), A.ptr(o_c, dp), A.ptr(o_fk, dp),
+                                         A.ptr(o_xyz, dp), A.ptr(o_mut, up), A.ptr(o_bad, up), A.ptr(o_mse, dp), A.ptr(o_added, up),
+                                         A.ptr(o_views, ip), A.ptr(counts, ip), A.ptr(adjust, ip), A.ptr(solved, ip), sums))
+    summary = []
+    for k in range(2):
+        C.memmove(C.byref(bufs[k].struct), C.byref(sums[k]), C.sizeof(A.BaSummary))
+        summary.append(bufs[k].result() if solved[k] else None)
+    out = {"cam_pose": o_pose[:nc], "cam_model": o_model[:nm], "cam_R": o_R[:nc], "cam_t": o_t[:nc], "cam_c": o_c[:nc], "cam_fk": o_fk[:nc],
+           "point_xyz": o_xyz[:npt], "pt_mutable": o_mut[:npt], "pt_bad": o_bad[:npt], "pt_mse": o_mse[:npt], "pt_new_added": o_added[:npt],
+           "pt_views": o_views[:npt], "count_outliers": int(counts[0]), "count_new_add": int(counts[1]),
+           "count_outliers_new_add": int(counts[2]), "adjust_cams": adjust[:, 0].copy(), "adjust_pts": adjust[:, 1].copy(), "solved": solved,
+           "summary": summary, "h2d_bytes": nb.value}
+    if keep_problem:
+        out["problem"] = []
+        for stage in range(2):
+            n_p, n_o = C.c_int32(), C.c_int32()
+            ctx.check(lib().msfm_round_set_fetch_problem(h, stage, C.byref(n_p), C.byref(n_o), None, None, None, None, None, None, None))
+            n_p, n_o = n_p.value, n_o.value
+            kept, q_cam, q_pt = np.zeros(max(1, n_p), np.int32), np.zeros(max(1, n_o), np.int32), np.zeros(max(1, n_o), np.int32)
+            q_xy, q_w = np.zeros((max(1, n_o), 2)), np.zeros(max(1, n_p))
+            q_cm, q_pm = np.zeros(c1, np.uint8), np.zeros(max(1, n_p), np.uint8)
+            ran = bool(partial) if stage == 0 else bool(full)
+            if ran:
+                ctx.check(lib().msfm_round_set_fetch_problem(h, stage, None, None, A.ptr(kept, ip), A.ptr(q_cam, ip), A.ptr(q_pt, ip), A.ptr(q_xy, dp),
+                                                             A.ptr(q_w, dp), A.ptr(q_cm, up), A.ptr(q_pm, up)))
+            out["problem"].append({"kept": kept[:n_p], "obs_cam": q_cam[:n_o], "obs_pt": q_pt[:n_o], "obs_xy": q_xy[:n_o], "pt_weight": q_w[:n_p],
+                                   "cam_mutable": q_cm[:nc if ran else 0], "pt_mutable": q_pm[:n_p]})
+    return out
+
+
 class Context:
     """One per GPU (one process per GPU)."""
 
@@ -507,6 +585,12 @@ class Context:
         match_off [P+1], matches [M][2]: the flat layout of `build_tracks`)."""
         return MatchStore(self, n_features, pairs, match_off, matches)
 
+    def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
+        """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
+        as a `Recon`; cam_pose / cam_model / cam_model_of_cam are the solver's parameter blocks as `adjust.adjust_round` takes
+        them.  keypoints: every image's rows, for a store that was not made from a chain.  Close it before its store."""
+        return Recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints, model_mutable, reserve_points, reserve_obs)
+
     def localize_set(self, store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=None, keypoints=None):
         """msfm_localize_candidates, the result kept as a `LocalizeSet`: `fetch()` is the dict of `localize_candidates`, and with
         point_xyz the correspondences stay on the device for `poses(...)` (msfm_localize_poses).  Close it before the context."""
@@ -608,22 +692,9 @@ class Context:
         h = C.c_void_p()
         self.check(lib().msfm_new_points(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
         try:
-            n1, npt, ne, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
-            lib().msfm_new_points_set_size(h, C.byref(n1), C.byref(npt), C.byref(ne), C.byref(nb))
-            npt, ne = npt.value, ne.value
-            m, e = max(1, npt), max(1, ne)
-            poff = np.zeros(nn + 1, np.int32)
-            cam2, f1, f2, ve, ptm = (np.zeros(m, np.int32) for _ in range(5))
-            X, mse, t1, t2 = np.zeros((m, 3)), np.zeros(m), np.zeros(m, np.uint8), np.zeros(m, np.uint8)
-            nm, ncand, nacc, large = np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.int32), np.zeros(e, np.uint8)
-            lib().msfm_new_points_set_fetch(h, A.ptr(poff, ip), A.ptr(cam2, ip), A.ptr(f1, ip), A.ptr(f2, ip), A.ptr(ve, ip), A.ptr(ptm, ip),
-                                            A.ptr(X, dp), A.ptr(mse, dp), A.ptr(t1, up), A.ptr(t2, up), A.ptr(nm, ip), A.ptr(large, up),
-                                            A.ptr(ncand, ip), A.ptr(nacc, ip))
+            return _new_points_set_result(h, nn)
         finally:
             lib().msfm_new_points_set_destroy(h)
-        return {"pt_off": poff, "cam2": cam2[:npt], "feat1": f1[:npt], "feat2": f2[:npt], "vis_entry": ve[:npt], "pt_match": ptm[:npt],
-                "X": X[:npt], "mse": mse[:npt], "takes1": t1[:npt], "takes2": t2[:npt], "n_matches": nm[:ne], "large": large[:ne],
-                "n_candidates": ncand[:ne], "n_accepted": nacc[:ne], "h2d_bytes": nb.value}
 
     def round_adjust(self, store, cam_img, feat_point, obs_point, obs_cam, obs_feat, cam_pose, cam_model, cam_model_of_cam, point_xyz, pt_bad,
                      pt_mse, pt_mutable, pt_new_added=None, new_cam=-1, visible=(), partial=True, full=False, outliers=True, model_mutable=None,
@@ -674,44 +745,7 @@ class Context:
         h = C.c_void_p()
         self.check(lib().msfm_round_adjust(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
         try:
-            nb = C.c_int64()
-            lib().msfm_round_set_size(h, None, None, None, C.byref(nb))
-            c1, m1, p1 = max(1, nc), max(1, nm), max(1, npt)
-            o_pose, o_model, o_R = np.zeros((c1, 6)), np.zeros((m1, 3)), np.zeros((c1, 3, 3))
-            o_t, o_c, o_fk, o_xyz, o_mse = np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((c1, 3)), np.zeros((p1, 3)), np.zeros(p1)
-            o_mut, o_bad, o_added, o_views = np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.uint8), np.zeros(p1, np.int32)
-            counts, adjust, solved = np.zeros(3, np.int32), np.zeros((2, 2), np.int32), np.zeros(2, np.int32)
-            bufs = [A.SummaryBuf(capacity), A.SummaryBuf(capacity)]
-            sums = (A.BaSummary * 2)()
-            for k in range(2):
-                sums[k].iterations, sums[k].iterations_capacity = bufs[k].struct.iterations, capacity
-            self.check(lib().msfm_round_set_fetch(h, A.ptr(o_pose, dp), A.ptr(o_model, dp), A.ptr(o_R, dp), A.ptr(o_t, dp), A.ptr(o_c, dp), A.ptr(o_fk, dp),
-                                                  A.ptr(o_xyz, dp), A.ptr(o_mut, up), A.ptr(o_bad, up), A.ptr(o_mse, dp), A.ptr(o_added, up),
-                                                  A.ptr(o_views, ip), A.ptr(counts, ip), A.ptr(adjust, ip), A.ptr(solved, ip), sums))
-            summary = []
-            for k in range(2):
-                C.memmove(C.byref(bufs[k].struct), C.byref(sums[k]), C.sizeof(A.BaSummary))
-                summary.append(bufs[k].result() if solved[k] else None)
-            out = {"cam_pose": o_pose[:nc], "cam_model": o_model[:nm], "cam_R": o_R[:nc], "cam_t": o_t[:nc], "cam_c": o_c[:nc], "cam_fk": o_fk[:nc],
-                   "point_xyz": o_xyz[:npt], "pt_mutable": o_mut[:npt], "pt_bad": o_bad[:npt], "pt_mse": o_mse[:npt], "pt_new_added": o_added[:npt],
-                   "pt_views": o_views[:npt], "count_outliers": int(counts[0]), "count_new_add": int(counts[1]),
-                   "count_outliers_new_add": int(counts[2]), "adjust_cams": adjust[:, 0].copy(), "adjust_pts": adjust[:, 1].copy(), "solved": solved,
-                   "summary": summary, "h2d_bytes": nb.value}
-            if o.keep_problem:
-                out["problem"] = []
-                for stage in range(2):
-                    n_p, n_o = C.c_int32(), C.c_int32()
-                    self.check(lib().msfm_round_set_fetch_problem(h, stage, C.byref(n_p), C.byref(n_o), None, None, None, None, None, None, None))
-                    n_p, n_o = n_p.value, n_o.value
-                    kept, q_cam, q_pt = np.zeros(max(1, n_p), np.int32), np.zeros(max(1, n_o), np.int32), np.zeros(max(1, n_o), np.int32)
-                    q_xy, q_w = np.zeros((max(1, n_o), 2)), np.zeros(max(1, n_p))
-                    q_cm, q_pm = np.zeros(c1, np.uint8), np.zeros(max(1, n_p), np.uint8)
-                    ran = bool(partial) if stage == 0 else bool(full)
-                    if ran:
-                        self.check(lib().msfm_round_set_fetch_problem(h, stage, None, None, A.ptr(kept, ip), A.ptr(q_cam, ip), A.ptr(q_pt, ip), A.ptr(q_xy, dp),
-                                                                      A.ptr(q_w, dp), A.ptr(q_cm, up), A.ptr(q_pm, up)))
-                    out["problem"].append({"kept": kept[:n_p], "obs_cam": q_cam[:n_o], "obs_pt": q_pt[:n_o], "obs_xy": q_xy[:n_o], "pt_weight": q_w[:n_p],
-                                           "cam_mutable": q_cm[:nc if ran else 0], "pt_mutable": q_pm[:n_p]})
+            out = _round_set_result(self, h, nc, nm, npt, partial, full, o.keep_problem, capacity)
         finally:
             lib().msfm_round_set_destroy(h)
         return out
@@ -1095,6 +1129,161 @@ class MatchStore:
     def close(self):
         if self._h:
             lib().msfm_match_store_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Recon:
+    """msfm_recon: a model's flat state resident on the device across its rounds (include/msfm.h)."""
+    INT = ("cam_img", "feat_point", "obs_point", "obs_cam", "obs_feat", "pt_views")
+    U8 = ("pt_bad", "pt_mutable", "pt_new_added")
+
+    def __init__(self, ctx: Context, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, model_mutable=None, reserve_points=0,
+                 reserve_obs=0):
+        self.ctx, self.store, self._h, self._n_visible = ctx, store, C.c_void_p(), 0
+        ip, dp, up = A.c_int_p, A.c_double_p, A.c_u8_p
+        a = {k: A.as_c(np.asarray(state[k], dtype=np.int32).reshape(-1), np.int32) for k in self.INT}
+        a.update({k: A.as_c(np.asarray(state[k], dtype=np.uint8).reshape(-1), np.uint8) for k in self.U8 if state.get(k) is not None})
+        a["cam_model_of_cam"] = A.as_c(np.asarray(cam_model_of_cam, dtype=np.int32).reshape(-1), np.int32)
+        for k, v, w in (("cam_pose", cam_pose, 6), ("cam_model", cam_model, 3), ("cam_R", state["cam_R"], 9), ("cam_t", state["cam_t"], 3),
+                        ("cam_c", state["cam_c"], 3), ("cam_fk", state["cam_fk"], 3), ("point_xyz", state["point_xyz"], 3), ("pt_mse", state["pt_mse"], 1)):
+            a[k] = A.as_c(np.asarray(v, dtype=np.float64).reshape(-1, w), np.float64)
+        nc, no, npt, nm = len(a["cam_img"]), len(a["obs_point"]), len(a["point_xyz"]), len(a["cam_model"])
+        if not all(len(a[k]) == nc for k in ("cam_pose", "cam_model_of_cam", "cam_R", "cam_t", "cam_c", "cam_fk")):
+            raise ValueError("cam_img, cam_pose, cam_model_of_cam and cam_R / cam_t / cam_c / cam_fk must describe the same number of cameras")
+        if not (len(a["obs_cam"]) == len(a["obs_feat"]) == no):
+            raise ValueError("obs_point, obs_cam and obs_feat must hold one entry per observation")
+        if not all(len(a[k]) == npt for k in ("pt_mse", "pt_views", "pt_bad", "pt_mutable")) or len(a.get("pt_new_added", a["pt_bad"])) != npt:
+            raise ValueError("point_xyz, pt_bad, pt_mse, pt_views, pt_mutable and pt_new_added must hold one entry per point")
+        mm = None if model_mutable is None else A.as_c(np.asarray(model_mutable, dtype=np.uint8).reshape(-1), np.uint8)
+        if mm is not None and len(mm) != nm:
+            raise ValueError("model_mutable must hold one entry per model")
+        in_store = (a["cam_img"] >= 0) & (a["cam_img"] < len(store.n_features))     # (an image outside the store: the library reports it)
+        if in_store.all() and len(a["feat_point"]) != int(store.n_features[a["cam_img"]].sum()):
+            raise ValueError("feat_point must hold one entry per feature of every camera's image")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        g = a.get
+        P = A.ReconInit(nc, A.ptr(g("cam_img"), ip), A.ptr(g("feat_point"), ip), npt, A.ptr(kp, A.c_float_p), no, A.ptr(g("obs_point"), ip),
+                        A.ptr(g("obs_cam"), ip), A.ptr(g("obs_feat"), ip), A.ptr(g("cam_pose"), dp), nm, A.ptr(g("cam_model"), dp),
+                        A.ptr(g("cam_model_of_cam"), ip), A.ptr(mm, up), A.ptr(g("cam_R"), dp), A.ptr(g("cam_t"), dp), A.ptr(g("cam_c"), dp),
+                        A.ptr(g("cam_fk"), dp), A.ptr(g("point_xyz"), dp), A.ptr(g("pt_bad"), up), A.ptr(g("pt_mse"), dp), A.ptr(g("pt_views"), ip),
+                        A.ptr(g("pt_mutable"), up), A.ptr(g("pt_new_added"), up), int(reserve_points), int(reserve_obs))
+        ctx.check(lib().msfm_recon_create(ctx._h, store._h, C.byref(P), C.byref(self._h)))
+
+    def size(self):
+        """msfm_recon_size: n_cams, n_models, n_points, n_obs, cap_points, cap_obs and h2d_bytes (sent since creation, creation included)."""
+        n = [C.c_int32() for _ in range(4)]
+        b = [C.c_int64() for _ in range(3)]
+        self.ctx.check(lib().msfm_recon_size(self._h, *[C.byref(x) for x in n + b]))
+        return dict(zip(("n_cams", "n_models", "n_points", "n_obs", "cap_points", "cap_obs", "h2d_bytes"), [x.value for x in n + b]))
+
+    def fetch(self):
+        """msfm_recon_fetch: the flat state as a dict in the dtypes and shapes of `newpoints.py`, plus cam_pose, cam_model and
+        cam_model_of_cam."""
+        ip, dp, up = A.c_int_p, A.c_double_p, A.c_u8_p
+        z = self.size()
+        nc, nm, npt, no = z["n_cams"], z["n_models"], z["n_points"], z["n_obs"]
+        cam_img = np.zeros(max(1, nc), np.int32)
+        self.ctx.check(lib().msfm_recon_fetch(self._h, A.ptr(cam_img, ip), *[None] * 17))
+        nfp = int(self.store.n_features[cam_img[:nc]].sum())
+        i32, f64, u8 = np.int32, np.float64, np.uint8
+        # (key, rows, trailing shape, dtype) in the order of msfm_recon_fetch behind cam_img
+        spec = [("feat_point", nfp, (), i32), ("obs_point", no, (), i32), ("obs_cam", no, (), i32), ("obs_feat", no, (), i32),
+                ("point_xyz", npt, (3,), f64), ("pt_bad", npt, (), u8), ("pt_mse", npt, (), f64), ("pt_views", npt, (), i32),
+                ("pt_mutable", npt, (), u8), ("pt_new_added", npt, (), u8), ("cam_pose", nc, (6,), f64), ("cam_model", nm, (3,), f64),
+                ("cam_model_of_cam", nc, (), i32), ("cam_R", nc, (3, 3), f64), ("cam_t", nc, (3,), f64), ("cam_c", nc, (3,), f64), ("cam_fk", nc, (3,), f64)]
+        bufs = [np.zeros((max(1, rows),) + shape, dt) for _, rows, shape, dt in spec]
+        typ = {i32: ip, f64: dp, u8: up}
+        self.ctx.check(lib().msfm_recon_fetch(self._h, None, *[A.ptr(b, typ[dt]) for b, (_, _, _, dt) in zip(bufs, spec)]))
+        out = {"n_features": np.array(self.store.n_features), "cam_img": cam_img[:nc]}
+        out.update({key: b[:rows] for b, (key, rows, _, _) in zip(bufs, spec)})
+        return out
+
+    def localize(self, cand_img, fail_times, cand_f, cand_f_init=None, **opts):
+        """msfm_recon_localize: FindImageToLocalize and the try loop on the resident state.  cand_img ascending, fail_times, cand_f
+        (0.0: the sweep around cand_f_init) per candidate; opts: fields of msfm_localize_pose_options.  Returns a dict in the keys of
+        `localize.localize_next_image`: image (-1: none), row, image_ids, failed_images, n_calls and, with a winner, f, R, t,
+        avg_error, n_inliers, n_outliers, visible.  The winner stays pending in the object for `commit_camera`."""
+        ip, dp = A.c_int_p, A.c_double_p
+        cand, fail = (A.as_c(np.asarray(x, dtype=np.int32).reshape(-1), np.int32) for x in (cand_img, fail_times))
+        f = A.as_c(np.asarray(cand_f, dtype=np.float64).reshape(-1), np.float64)
+        fi = None if cand_f_init is None else A.as_c(np.asarray(cand_f_init, dtype=np.float64).reshape(-1), np.float64)
+        if not (len(fail) == len(f) == len(cand)) or (fi is not None and len(fi) != len(cand)):
+            raise ValueError("cand_img, fail_times, cand_f and cand_f_init must hold one entry per candidate")
+        o = localize_pose_options(**opts)
+        w = A.ReconWinner()
+        self.ctx.check(lib().msfm_recon_localize(self._h, len(cand), A.ptr(cand, ip), A.ptr(fail, ip), A.ptr(f, dp), A.ptr(fi, dp), C.byref(o), C.byref(w)))
+        ranked, failed, vis = np.zeros(max(1, w.n_ranked), np.int32), np.zeros(max(1, w.n_failed), np.int32), np.zeros(max(1, w.n_visible), np.int32)
+        self.ctx.check(lib().msfm_recon_localize_fetch(self._h, A.ptr(ranked, ip), A.ptr(failed, ip), A.ptr(vis, ip)))
+        self._n_visible = int(w.n_visible)
+        out = dict(image=int(w.image), row=int(w.row), image_ids=[int(x) for x in ranked[:w.n_ranked]],
+                   failed_images=[int(x) for x in failed[:w.n_failed]], n_calls=int(w.n_chunks))
+        if w.image >= 0:
+            out.update(f=float(w.f), R=np.array(w.R, np.float64).reshape(3, 3), t=np.array(w.t, np.float64), avg_error=float(w.avg_error),
+                       n_inliers=int(w.n_inliers), n_outliers=int(w.n_outliers), n_corr=int(w.n_corr), visible=vis[:w.n_visible].copy())
+        return out
+
+    def commit_camera(self, cam_pose6, model, cam_model3=None, model_mutable=True):
+        """msfm_recon_commit_camera: `localize.apply_localized_image` for the pending winner, on the device.  cam_pose6: the new
+        camera's angle-axis and translation; model: an existing model, or n_models with cam_model3 = (f, k1, k2) to append one.
+        Returns the visible list, the new camera first."""
+        pose = A.as_c(np.asarray(cam_pose6, dtype=np.float64).reshape(6), np.float64)
+        m3 = None if cam_model3 is None else A.as_c(np.asarray(cam_model3, dtype=np.float64).reshape(3), np.float64)
+        vis = np.zeros(1 + self._n_visible, np.int32)
+        new_cam = C.c_int32()
+        self.ctx.check(lib().msfm_recon_commit_camera(self._h, A.ptr(pose, A.c_double_p), int(model), A.ptr(m3, A.c_double_p), int(bool(model_mutable)),
+                                                      C.byref(new_cam), A.ptr(vis, A.c_int_p)))
+        return [int(x) for x in vis]
+
+    def new_points(self, new_cam, visible, stats=False, **opts):
+        """msfm_recon_new_points: `Context.new_points` for the camera `new_cam` and its visible list on the resident state, the new
+        points appended on the device as `newpoints.apply_new_points` appends them to the flat state.  Returns their number;
+        with stats=True the dict of `Context.new_points` (h2d_bytes: of this call) with n_new added.  opts: fields of
+        msfm_new_points_options."""
+        visible = A.as_c(np.asarray(visible, dtype=np.int32).reshape(-1), np.int32)
+        o = new_points_options(**opts)
+        n, h = C.c_int32(), C.c_void_p()
+        self.ctx.check(lib().msfm_recon_new_points(self._h, int(new_cam), len(visible), A.ptr(visible, A.c_int_p), C.byref(o), C.byref(n),
+                                                   C.byref(h) if stats else None))
+        if not stats:
+            return n.value
+        try:
+            return dict(_new_points_set_result(h, 1), n_new=n.value)
+        finally:
+            lib().msfm_new_points_set_destroy(h)
+
+    def adjust(self, new_cam=-1, visible=(), partial=True, full=False, outliers=True, capacity=512, **opts):
+        """msfm_recon_adjust: `Context.round_adjust` on the resident state, written in place.  Returns its dict without the point
+        arrays (they stay on the device; `fetch()` reads them): cam_pose, cam_model, cam_R, cam_t, cam_c, cam_fk, the counts,
+        adjust_cams / adjust_pts, solved, summary, h2d_bytes (of this call) and, with keep_problem=1, problem."""
+        visible = A.as_c(np.asarray(visible, dtype=np.int32).reshape(-1), np.int32)
+        opts = dict(opts)
+        for k in ("partial", "full"):
+            if k + "_options" in opts:
+                opts[k] = opts.pop(k + "_options")
+        o = round_options(**opts)
+        z = self.size()
+        h = C.c_void_p()
+        self.ctx.check(lib().msfm_recon_adjust(self._h, int(new_cam), len(visible), A.ptr(visible, A.c_int_p), int(bool(partial)), int(bool(full)),
+                                               int(bool(outliers)), C.byref(o), C.byref(h)))
+        try:
+            out = _round_set_result(self.ctx, h, z["n_cams"], z["n_models"], 0, partial, full, o.keep_problem, capacity)
+        finally:
+            lib().msfm_round_set_destroy(h)
+        for k in ("point_xyz", "pt_mutable", "pt_bad", "pt_mse", "pt_new_added", "pt_views"):
+            del out[k]
+        return out
+
+    def close(self):
+        if self._h:
+            lib().msfm_recon_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

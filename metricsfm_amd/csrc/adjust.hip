@@ -15,6 +15,9 @@
 //   solve       ba_create_impl(bulk_on_device) + msfm_ba_run, as msfm_chain_ba_create; k_scatter_points puts the result back
 //   k_outliers  one thread per point over its sorted segment: Reprojection and the flags of RemovePointOutliers
 // The host waits where it needs a count - the sizes of a stage's problem, what the solve does itself - and at the end.
+// The call is three parts: round_tables (the checks that need no bulk array, the O(cameras) tables), round_adjust_dev (everything on
+// device arrays, written in place) and the export, which uploads the bulk arrays in front of the core and reads the points back
+// behind it.  recon.hip calls the first two on the arrays a msfm_recon keeps resident.
 // k_outliers is compiled without fused multiply-adds, + - * / sqrt only (the discipline of newpoints.hip and seed.hip):
 // tests/round_ref.py, a sequential restatement in doubles, agrees bit for bit.
 #include <algorithm>
@@ -30,41 +33,10 @@
 
 #pragma clang fp contract(off)
 
-struct msfm_round_set {
-  msfm_ctx* ctx = nullptr;
-  int n_cams = 0, n_models = 0, n_points = 0;
-  std::vector<double> cam_pose, cam_model, cam_R, cam_t, cam_c, cam_fk, point_xyz, pt_mse;
-  std::vector<uint8_t> pt_mutable, pt_bad, pt_new_added;
-  std::vector<int> pt_views;
-  int counts[3] = {0, 0, 0};        // count_outliers, count_new_add, count_outliers_new_add
-  int adjust[2][2] = {{0, 0}, {0, 0}};   // "adjust cams", "adjust pts" of each solve
-  int solved[2] = {0, 0};
-  msfm_ba_summary summary[2];
-  std::vector<msfm_ba_iteration> rows[2];
-  bool keep_problem = false;
-  struct Problem {
-    int n_points = 0, n_obs = 0;
-    std::vector<int> kept, obs_cam, obs_pt;
-    std::vector<double> obs_xy, pt_weight;
-    std::vector<uint8_t> cam_mutable, pt_mutable;
-  } problem[2];
-  int64_t h2d_bytes = 0;
-};
-
 namespace adj {
 
 #define ADJ_CAM 15    // R (9), t (3), fk (3)
 #define ADJ_BIG 0x7fffffff
-
-// the segment of position x: off[lo] <= x < off[lo + 1] (empty segments are stepped over)
-__device__ static inline int segment_of(const int* __restrict__ off, int n, int x) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
 
 __global__ __launch_bounds__(256) void k_check_points(int FP, int n_points, const int* __restrict__ fp, int* __restrict__ err) {
   const int x = blockIdx.x * 256 + threadIdx.x;
@@ -117,7 +89,7 @@ __global__ __launch_bounds__(256) void k_attach(int FP, int n_cams, int n_points
   const int p = fp[x];
   if (p < 0 || p >= n_points) return;
   att[p] = 1;
-  if (cam_free && !pt_bad[p] && cam_free[segment_of(cam_fo, n_cams, x)]) freed[p] = 1;
+  if (cam_free && !pt_bad[p] && cam_free[csr_segment_of(cam_fo, n_cams, x)]) freed[p] = 1;
 }
 
 // full = 0: frozen where attached, then freed (:919-945); full = 1: free where attached (:1880-1893); a point no camera holds
@@ -280,81 +252,81 @@ MSFM_API void msfm_round_default_options(msfm_round_options* o) {
   o->keep_problem = 0;
 }
 
-MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const msfm_round_problem* P, const msfm_round_options* opt_in,
-                               msfm_round_set** out) {
-  using namespace adj;
-  const char* who = "msfm_round_adjust";
-  if (!ctx) return MSFM_E_INVAL;
-  if (!S || !P || !out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
-  *out = nullptr;
-  if (S->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the store belongs to another context", who);
-  msfm_round_options opt;
-  if (opt_in) opt = *opt_in; else msfm_round_default_options(&opt);
-  const int ni = S->n_images, nc = P->n_cams, nm = P->n_models, np = P->n_points, no = P->n_obs;
-  const bool solve = P->do_partial || P->do_full;
-  if (nc < 0 || nm < 0 || np < 0 || no < 0 || P->n_visible < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: negative count", who);
-  if ((nc && (!P->cam_img || !P->cam_pose || !P->cam_model_of_cam)) || (nm && !P->cam_model) || (no && (!P->obs_point || !P->obs_cam || !P->obs_feat)) ||
-      (np && (!P->point_xyz || !P->pt_bad || !P->pt_mse || !P->pt_mutable)) || (P->n_visible && !P->visible))
-    return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
+// The checks that need no bulk array, and O(cameras) on the host: feat_point rows, image ranks, keypoint rows
+int round_tables(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const RoundArgs& A, bool packed_kp, const msfm_round_options& opt,
+                 RoundTables* T) {
+  const int ni = S->n_images, nc = A.n_cams, nm = A.n_models;
   if (!(opt.th_mse_outliers >= 0.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: th_mse_outliers = %g is NaN or negative", who, opt.th_mse_outliers);
   if (!(opt.weight_partial >= 0.0) || !(opt.weight_full >= 0.0))
     return msfm_set_error(ctx, MSFM_E_INVAL, "%s: a weight is NaN or negative", who);
-  if (P->do_partial && P->new_cam < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: do_partial without new_cam", who);
-  if (P->new_cam >= nc || P->new_cam < -1) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: new_cam = %d outside n_cams = %d", who, P->new_cam, nc);
-  for (int q = 0; q < P->n_visible; q++)
-    if (P->visible[q] < 0 || P->visible[q] >= nc)
-      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: visible[%d] = %d outside n_cams = %d", who, q, P->visible[q], nc);
+  if (A.do_partial && A.new_cam < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: do_partial without new_cam", who);
+  if (A.new_cam >= nc || A.new_cam < -1) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: new_cam = %d outside n_cams = %d", who, A.new_cam, nc);
+  for (int q = 0; q < A.n_visible; q++)
+    if (A.visible[q] < 0 || A.visible[q] >= nc)
+      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: visible[%d] = %d outside n_cams = %d", who, q, A.visible[q], nc);
   for (int c = 0; c < nc; c++)
-    if (P->cam_model_of_cam[c] < 0 || P->cam_model_of_cam[c] >= nm)
-      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: cam_model_of_cam[%d] = %d outside n_models = %d", who, c, P->cam_model_of_cam[c], nm);
-  // ---- O(cameras) on the host: feat_point rows, image ranks, keypoint rows ----
-  std::vector<int> cam_fo(nc + 1, 0), rank(std::max(1, nc), 0), cam_of_rank(std::max(1, nc), 0), kp_base(std::max(1, nc), 0);
-  int max_feat = 1;
-  long kp_rows = 0;
-  bool all_kp = true;
+    if (A.cam_model_of_cam[c] < 0 || A.cam_model_of_cam[c] >= nm)
+      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: cam_model_of_cam[%d] = %d outside n_models = %d", who, c, A.cam_model_of_cam[c], nm);
+  T->cam_fo.assign(nc + 1, 0); T->rank.assign(std::max(1, nc), 0); T->cam_of_rank.assign(std::max(1, nc), 0); T->kp_base.assign(std::max(1, nc), 0);
+  T->max_feat = 1;
+  T->kp_rows = 0;
+  T->all_kp = true;
   {
     std::vector<uint8_t> seen(std::max(1, ni), 0);
     for (int c = 0; c < nc; c++) {
-      const int im = P->cam_img[c];
+      const int im = A.cam_img[c];
       if (im < 0 || im >= ni) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: cam_img[%d] = %d is no image of the store", who, c, im);
       if (seen[im]) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: image %d has two cameras", who, im);
       seen[im] = 1;
-      if ((long)cam_fo[c] + S->n_features[im] > 0x7fffffffL) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: more than 2^31 registered features", who);
-      cam_fo[c + 1] = cam_fo[c] + S->n_features[im];
-      max_feat = std::max(max_feat, S->n_features[im]);
-      if (P->keypoints) { kp_base[c] = (int)kp_rows; kp_rows += S->n_features[im]; }
-      else { kp_base[c] = S->feat_off[im]; all_kp = all_kp && S->has_kp[im]; }
+      if ((long)T->cam_fo[c] + S->n_features[im] > 0x7fffffffL) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: more than 2^31 registered features", who);
+      T->cam_fo[c + 1] = T->cam_fo[c] + S->n_features[im];
+      T->max_feat = std::max(T->max_feat, S->n_features[im]);
+      if (packed_kp) { T->kp_base[c] = (int)T->kp_rows; T->kp_rows += S->n_features[im]; }
+      else { T->kp_base[c] = S->feat_off[im]; T->all_kp = T->all_kp && S->has_kp[im]; }
     }
-    std::iota(cam_of_rank.begin(), cam_of_rank.begin() + nc, 0);
-    std::sort(cam_of_rank.begin(), cam_of_rank.begin() + nc, [&](int a, int b) { return P->cam_img[a] < P->cam_img[b]; });
-    for (int r = 0; r < nc; r++) rank[cam_of_rank[r]] = r;
+    std::iota(T->cam_of_rank.begin(), T->cam_of_rank.begin() + nc, 0);
+    std::sort(T->cam_of_rank.begin(), T->cam_of_rank.begin() + nc, [&](int a, int b) { return A.cam_img[a] < A.cam_img[b]; });
+    for (int r = 0; r < nc; r++) T->rank[T->cam_of_rank[r]] = r;
   }
-  if (!all_kp)   // a store without some image's keypoints: that image must have no observation (a walk over obs_cam)
-    for (int i = 0; i < no; i++) {
-      const int c = P->obs_cam[i];
-      if (c >= 0 && c < nc && !S->has_kp[P->cam_img[c]])
-        return msfm_set_error(ctx, MSFM_E_INVAL, "%s: no keypoints of image %d (argument or chain)", who, P->cam_img[c]);
-    }
-  const int FP = cam_fo[nc];
-  if (FP && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
-  const int bf = bits_for((unsigned)(max_feat - 1)), br = bits_for((unsigned)std::max(0, nc - 1));
-  if (bf + br > 32)
-    return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %d cameras and %d features in an image need %d + %d bits: the sort key holds image rank and feature in 32", who, nc,
-                          max_feat, br, bf);
+  T->bf = adj::bits_for((unsigned)(T->max_feat - 1));
   // the free cameras of the partial stage (:922-945): the new camera's model, and its visible cameras
-  std::vector<uint8_t> cam_free(std::max(1, nc), 0), cam_all(std::max(1, nc), 1);
-  if (P->do_partial) {
-    const int m = P->cam_model_of_cam[P->new_cam];
-    for (int c = 0; c < nc; c++) cam_free[c] = P->cam_model_of_cam[c] == m ? 1 : 0;
-    for (int q = 0; q < P->n_visible; q++) cam_free[P->visible[q]] = 1;
+  T->cam_free.assign(std::max(1, nc), 0); T->cam_all.assign(std::max(1, nc), 1);
+  if (A.do_partial) {
+    const int m = A.cam_model_of_cam[A.new_cam];
+    for (int c = 0; c < nc; c++) T->cam_free[c] = A.cam_model_of_cam[c] == m ? 1 : 0;
+    for (int q = 0; q < A.n_visible; q++) T->cam_free[A.visible[q]] = 1;
   }
-  std::unique_ptr<msfm_round_set> R(new msfm_round_set());
-  R->ctx = ctx; R->n_cams = nc; R->n_models = nm; R->n_points = np;
-  R->keep_problem = opt.keep_problem != 0;
-  R->cam_pose.assign(P->cam_pose, P->cam_pose + 6 * (size_t)nc);
-  R->cam_model.assign(P->cam_model, P->cam_model + 3 * (size_t)nm);
-  memset(R->summary, 0, sizeof R->summary);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return MSFM_OK;
+}
+
+int round_fp_error(msfm_ctx* ctx, const char* who, const std::vector<int>& cam_fo, int n_cams, int n_points, int x) {
+  int c = 0;
+  while (c + 1 < n_cams && cam_fo[c + 1] <= x) c++;
+  return msfm_set_error(ctx, MSFM_E_INVAL, "%s: feat_point of camera %d, feature %d is no point (n_points = %d)", who, c, x - cam_fo[c], n_points);
+}
+
+int round_row_error(msfm_ctx* ctx, const char* who, int row, int point, int cam, int feat) {
+  return msfm_set_error(ctx, MSFM_E_INVAL, "%s: observation %d = (point %d, camera %d, feature %d) names an index outside its array", who, row, point, cam,
+                        feat);
+}
+
+int round_key_check(msfm_ctx* ctx, const char* who, int n_cams, const RoundTables& T) {
+  const int br = adj::bits_for((unsigned)std::max(0, n_cams - 1));
+  if (T.bf + br > 32)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %d cameras and %d features in an image need %d + %d bits: the sort key holds image rank and feature in 32", who,
+                          n_cams, T.max_feat, br, T.bf);
+  return MSFM_OK;
+}
+
+// The call behind its bulk uploads: the camera tables go up, every kernel and both solves run on the arrays of D, which are
+// written in place.  R arrives with cam_pose / cam_model set and leaves with everything but h2d_bytes; with fetch_points the
+// one read-back at the end carries the point arrays into it, without it the last solve's pt_mutable goes into D.pt_mutable.
+int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const RoundTables& T, const RoundDev& D, const msfm_round_options& opt,
+                     int64_t* h2d_bytes, msfm_round_set* R, bool fetch_points) {
+  using namespace adj;
+  const int nc = A.n_cams, nm = A.n_models, np = A.n_points, no = A.n_obs, FP = T.cam_fo[nc], bf = T.bf;
+  const bool solve = A.do_partial || A.do_full;
+  const std::vector<int>& cam_fo = T.cam_fo;
   hipStream_t s = ctx->stream;
   int64_t h2d = 0;
   auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
@@ -364,29 +336,13 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
     return buf.upload(h, cnt, s);
   };
   const size_t npx = (size_t)np, nox = (size_t)no;
-  // ---- one batch of uploads ----
-  DevBuf<int> d_fp, d_fo, d_op, d_oc, d_of, d_rank, d_cor, d_kpb, d_err, d_cnt;
-  DevBuf<double> d_xyz, d_mse, d_cam;
-  DevBuf<uint8_t> d_bad, d_mut_in, d_added, d_free, d_call;
-  DevBuf<float> d_kp_up;
-  AJ_TRY(up(d_fp, P->feat_point, (size_t)FP)); AJ_TRY(up(d_fo, cam_fo.data(), (size_t)nc + 1));
-  AJ_TRY(up(d_op, P->obs_point, nox)); AJ_TRY(up(d_oc, P->obs_cam, nox)); AJ_TRY(up(d_of, P->obs_feat, nox));
-  AJ_TRY(up(d_rank, rank.data(), (size_t)nc)); AJ_TRY(up(d_cor, cam_of_rank.data(), (size_t)nc)); AJ_TRY(up(d_kpb, kp_base.data(), (size_t)nc));
-  AJ_TRY(up(d_xyz, P->point_xyz, 3 * npx)); AJ_TRY(up(d_mse, P->pt_mse, npx));
-  AJ_TRY(up(d_bad, P->pt_bad, npx)); AJ_TRY(up(d_mut_in, P->pt_mutable, npx));
-  AJ_TRY(up(d_free, cam_free.data(), (size_t)nc)); AJ_TRY(up(d_call, cam_all.data(), (size_t)nc));
-  if (P->pt_new_added) AJ_TRY(up(d_added, P->pt_new_added, npx));
-  else { AJ_TRY(d_added.alloc(std::max<size_t>(1, npx))); AJ_TRY(hipMemsetAsync(d_added.p, 0, std::max<size_t>(1, npx), s)); }
-  std::vector<float> h_kp;   // (lives to the final wait)
-  if (P->keypoints) {   // the rows of the cameras' images only, packed in camera order
-    h_kp.resize(2 * (size_t)kp_rows);
-    for (int c = 0; c < nc; c++) {
-      const int im = P->cam_img[c];
-      std::copy(P->keypoints + 2 * (size_t)S->feat_off[im], P->keypoints + 2 * ((size_t)S->feat_off[im] + S->n_features[im]), h_kp.begin() + 2 * (size_t)kp_base[c]);
-    }
-    AJ_TRY(up(d_kp_up, h_kp.data(), h_kp.size()));
-  }
-  const float* d_kp = P->keypoints ? d_kp_up.p : S->d_kp.p;
+  DevBuf<int> d_fo, d_rank, d_cor, d_kpb, d_err, d_cnt;
+  DevBuf<double> d_cam;
+  DevBuf<uint8_t> d_free, d_call;
+  AJ_TRY(up(d_fo, cam_fo.data(), (size_t)nc + 1));
+  AJ_TRY(up(d_rank, T.rank.data(), (size_t)nc)); AJ_TRY(up(d_cor, T.cam_of_rank.data(), (size_t)nc)); AJ_TRY(up(d_kpb, T.kp_base.data(), (size_t)nc));
+  AJ_TRY(up(d_free, T.cam_free.data(), (size_t)nc)); AJ_TRY(up(d_call, T.cam_all.data(), (size_t)nc));
+  const float* d_kp = D.kp;
   // err: feat_point entry, obs row; cnt: free points of the partial / the full stage, the three counts of the outlier stage
   AJ_TRY(d_err.alloc(2)); AJ_TRY(d_cnt.alloc(8));
   AJ_TRY(hipMemsetD32Async((hipDeviceptr_t)d_err.p, ADJ_BIG, 2, s));
@@ -414,8 +370,9 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   {
     KTimer tm(ctx, "round_keys");
     tm.count = (FP ? 1 : 0) + (no ? 1 : 0);
-    if (FP) hipLaunchKernelGGL(k_check_points, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, np, d_fp.p, d_err.p);
-    if (no) hipLaunchKernelGGL(k_key, dim3(cdiv(no, 256)), dim3(256), 0, s, no, np, nc, d_op.p, d_oc.p, d_of.p, d_fo.p, d_rank.p, bf, d_key.p, d_err.p + 1);
+    if (FP) hipLaunchKernelGGL(k_check_points, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, np, D.feat_point, d_err.p);
+    if (no) hipLaunchKernelGGL(k_key, dim3(cdiv(no, 256)), dim3(256), 0, s, no, np, nc, D.obs_point, D.obs_cam, D.obs_feat, d_fo.p, d_rank.p, bf, d_key.p,
+                               d_err.p + 1);
   }
   AJ_TRY(hipGetLastError());
   if (no) {
@@ -433,22 +390,26 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   }
   if (FP && np) {
     KTimer tm(ctx, "round_attach");
-    hipLaunchKernelGGL(k_attach, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, nc, np, d_fo.p, d_fp.p, P->do_partial ? d_free.p : (const uint8_t*)nullptr, d_bad.p,
-                       d_att.p, d_freed.p);
+    hipLaunchKernelGGL(k_attach, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, nc, np, d_fo.p, D.feat_point, A.do_partial ? d_free.p : (const uint8_t*)nullptr,
+                       D.pt_bad, d_att.p, d_freed.p);
   }
   AJ_TRY(hipGetLastError());
   int err[2] = {ADJ_BIG, ADJ_BIG};
   bool err_read = false;
   auto index_error = [&]() -> int {   // after a synchronisation that carried d_err
     err_read = true;
-    if (err[0] != ADJ_BIG) {
-      int c = 0;
-      while (c + 1 < nc && cam_fo[c + 1] <= err[0]) c++;
-      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: feat_point of camera %d, feature %d is no point (n_points = %d)", who, c, err[0] - cam_fo[c], np);
+    if (err[0] != ADJ_BIG) return round_fp_error(ctx, who, cam_fo, nc, np, err[0]);
+    if (err[1] != ADJ_BIG) {
+      int row[3] = {0, 0, 0};
+      if (A.h_obs_point) { row[0] = A.h_obs_point[err[1]]; row[1] = A.h_obs_cam[err[1]]; row[2] = A.h_obs_feat[err[1]]; }
+      else {   // the rows live on the device only
+        AJ_TRY(hipMemcpyAsync(&row[0], D.obs_point + err[1], sizeof(int), hipMemcpyDeviceToHost, s));
+        AJ_TRY(hipMemcpyAsync(&row[1], D.obs_cam + err[1], sizeof(int), hipMemcpyDeviceToHost, s));
+        AJ_TRY(hipMemcpyAsync(&row[2], D.obs_feat + err[1], sizeof(int), hipMemcpyDeviceToHost, s));
+        AJ_TRY(hipStreamSynchronize(s));
+      }
+      return round_row_error(ctx, who, err[1], row[0], row[1], row[2]);
     }
-    if (err[1] != ADJ_BIG)
-      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: observation %d = (point %d, camera %d, feature %d) names an index outside its array", who, err[1],
-                            P->obs_point[err[1]], P->obs_cam[err[1]], P->obs_feat[err[1]]);
     return MSFM_OK;
   };
   // ---- the two solves ----
@@ -465,16 +426,16 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   };
   bool mut_done = false;
   for (int stage = 0; stage < 2; stage++) {
-    if (!(stage == 0 ? P->do_partial : P->do_full)) continue;
-    const std::vector<uint8_t>& cam_mut = stage == 0 ? cam_free : cam_all;
+    if (!(stage == 0 ? A.do_partial : A.do_full)) continue;
+    const std::vector<uint8_t>& cam_mut = stage == 0 ? T.cam_free : T.cam_all;
     const uint8_t* d_cam_mut = stage == 0 ? d_free.p : d_call.p;
     const msfm_ba_options& bo = stage == 0 ? opt.partial : opt.full;
     AJ_TRY(hipMemsetAsync(keep_pt.p, 0, sizeof(int) * (npx + 1), s));
     {
       KTimer tm(ctx, "round_keep");
       tm.count = (np ? 1 : 0) + 1;
-      if (np) hipLaunchKernelGGL(k_pt_mutable, dim3(cdiv(np, 256)), dim3(256), 0, s, np, stage, d_att.p, d_freed.p, d_mut_in.p, d_mut.p, d_cnt.p + stage);
-      hipLaunchKernelGGL(k_keep, dim3(cdiv(no + 1, 256)), dim3(256), 0, s, no, np, d_key_s.p, d_first.p, d_cor.p, bf, d_cam_mut, d_mut.p, d_bad.p, keep_row.p,
+      if (np) hipLaunchKernelGGL(k_pt_mutable, dim3(cdiv(np, 256)), dim3(256), 0, s, np, stage, d_att.p, d_freed.p, D.pt_mutable, d_mut.p, d_cnt.p + stage);
+      hipLaunchKernelGGL(k_keep, dim3(cdiv(no + 1, 256)), dim3(256), 0, s, no, np, d_key_s.p, d_first.p, d_cor.p, bf, d_cam_mut, d_mut.p, D.pt_bad, keep_row.p,
                          keep_pt.p);
     }
     mut_done = true;
@@ -501,7 +462,7 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
     {
       KTimer tm(ctx, "round_emit");
       hipLaunchKernelGGL(k_emit, dim3(cdiv(std::max(no, np), 256)), dim3(256), 0, s, no, np, d_key_s.p, keep_row.p, new_row.p, keep_pt.p, new_pt.p, d_cor.p, bf,
-                         d_kpb.p, d_kp, d_views.p, stage == 0 ? opt.weight_partial : opt.weight_full, d_xyz.p, d_mut.p, obs_cam.p, obs_pt.p, obs_xy.p, ptw.p,
+                         d_kpb.p, d_kp, d_views.p, stage == 0 ? opt.weight_partial : opt.weight_full, D.point_xyz, d_mut.p, obs_cam.p, obs_pt.p, obs_xy.p, ptw.p,
                          point.p, pmut.p, kept.p);
     }
     AJ_TRY(hipGetLastError());
@@ -518,9 +479,9 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
     msfm_ba_problem B;
     memset(&B, 0, sizeof B);
     B.n_cams = nc; B.n_models = nm; B.n_points = npk; B.n_obs = nok;
-    B.cam_pose = R->cam_pose.data(); B.cam_model = R->cam_model.data(); B.cam_model_of_cam = P->cam_model_of_cam;
+    B.cam_pose = R->cam_pose.data(); B.cam_model = R->cam_model.data(); B.cam_model_of_cam = A.cam_model_of_cam;
     B.point = point.p; B.obs_cam = obs_cam.p; B.obs_pt = obs_pt.p; B.obs_xy = obs_xy.p; B.pt_weight = ptw.p;
-    B.cam_mutable = cam_mut.data(); B.model_mutable = P->model_mutable; B.pt_mutable = pmut.p;
+    B.cam_mutable = cam_mut.data(); B.model_mutable = A.model_mutable; B.pt_mutable = pmut.p;
     msfm_ba* ba = nullptr;
     // an error return releases the buffers above to the block cache: only behind a wait for what was enqueued on them
     auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
@@ -534,7 +495,7 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
     // BundleAdjuster::UpdateParameters: the points on the device, cameras and models through the host copy the next stage starts from
     {
       KTimer tm(ctx, "round_scatter_points");
-      hipLaunchKernelGGL(k_scatter_points, dim3(cdiv(npk, 256)), dim3(256), 0, s, npk, kept.p, ba_device_points(ba), d_xyz.p);
+      hipLaunchKernelGGL(k_scatter_points, dim3(cdiv(npk, 256)), dim3(256), 0, s, npk, kept.p, ba_device_points(ba), D.point_xyz);
     }
     AJ_TRY(hipGetLastError());
     if (int rc = msfm_ba_download_params(ba, R->cam_pose.data(), R->cam_model.data(), nullptr)) return fail(rc);   // (synchronises: the scatter has run)
@@ -546,33 +507,113 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   for (int c = 0; c < nc; c++) {
     const size_t cx = (size_t)c;
     pose_to_camera(R->cam_pose.data() + 6 * cx, R->cam_R.data() + 9 * cx, R->cam_t.data() + 3 * cx, R->cam_c.data() + 3 * cx);
-    std::copy(R->cam_model.begin() + 3 * (size_t)P->cam_model_of_cam[c], R->cam_model.begin() + 3 * (size_t)P->cam_model_of_cam[c] + 3, R->cam_fk.begin() + 3 * cx);
+    std::copy(R->cam_model.begin() + 3 * (size_t)A.cam_model_of_cam[c], R->cam_model.begin() + 3 * (size_t)A.cam_model_of_cam[c] + 3, R->cam_fk.begin() + 3 * cx);
     double* C = cam.data() + ADJ_CAM * cx;
     std::copy(R->cam_R.begin() + 9 * cx, R->cam_R.begin() + 9 * cx + 9, C);
     std::copy(R->cam_t.begin() + 3 * cx, R->cam_t.begin() + 3 * cx + 3, C + 9);
     std::copy(R->cam_fk.begin() + 3 * cx, R->cam_fk.begin() + 3 * cx + 3, C + 12);
   }
-  if (P->do_outliers && np) {
+  if (A.do_outliers && np) {
     AJ_TRY(up(d_cam, cam.data(), ADJ_CAM * (size_t)nc));
     KTimer tm(ctx, "round_outliers");
-    hipLaunchKernelGGL(k_outliers, dim3(cdiv(np, 256)), dim3(256), 0, s, np, d_seg.p, d_key_s.p, d_first.p, d_cor.p, bf, d_kpb.p, d_kp, d_cam.p, d_xyz.p,
-                       opt.th_mse_outliers, d_bad.p, d_mse.p, d_added.p, d_cnt.p + 2);
+    hipLaunchKernelGGL(k_outliers, dim3(cdiv(np, 256)), dim3(256), 0, s, np, d_seg.p, d_key_s.p, d_first.p, d_cor.p, bf, d_kpb.p, d_kp, d_cam.p, D.point_xyz,
+                       opt.th_mse_outliers, D.pt_bad, D.pt_mse, D.pt_new_added, d_cnt.p + 2);
   }
   AJ_TRY(hipGetLastError());
   // ---- one read-back ----
-  R->point_xyz.resize(3 * npx); R->pt_mse.resize(npx); R->pt_mutable.resize(npx); R->pt_bad.resize(npx); R->pt_new_added.resize(npx); R->pt_views.resize(npx);
-  if (np) {
-    AJ_TRY(hipMemcpyAsync(R->point_xyz.data(), d_xyz.p, sizeof(double) * 3 * npx, hipMemcpyDeviceToHost, s));
-    AJ_TRY(hipMemcpyAsync(R->pt_mse.data(), d_mse.p, sizeof(double) * npx, hipMemcpyDeviceToHost, s));
-    AJ_TRY(hipMemcpyAsync(R->pt_mutable.data(), mut_done ? d_mut.p : d_mut_in.p, npx, hipMemcpyDeviceToHost, s));
-    AJ_TRY(hipMemcpyAsync(R->pt_bad.data(), d_bad.p, npx, hipMemcpyDeviceToHost, s));
-    AJ_TRY(hipMemcpyAsync(R->pt_new_added.data(), d_added.p, npx, hipMemcpyDeviceToHost, s));
-    AJ_TRY(hipMemcpyAsync(R->pt_views.data(), d_views.p, sizeof(int) * npx, hipMemcpyDeviceToHost, s));
+  if (fetch_points) {
+    R->point_xyz.resize(3 * npx); R->pt_mse.resize(npx); R->pt_mutable.resize(npx); R->pt_bad.resize(npx); R->pt_new_added.resize(npx); R->pt_views.resize(npx);
+    if (np) {
+      AJ_TRY(hipMemcpyAsync(R->point_xyz.data(), D.point_xyz, sizeof(double) * 3 * npx, hipMemcpyDeviceToHost, s));
+      AJ_TRY(hipMemcpyAsync(R->pt_mse.data(), D.pt_mse, sizeof(double) * npx, hipMemcpyDeviceToHost, s));
+      AJ_TRY(hipMemcpyAsync(R->pt_mutable.data(), mut_done ? d_mut.p : D.pt_mutable, npx, hipMemcpyDeviceToHost, s));
+      AJ_TRY(hipMemcpyAsync(R->pt_bad.data(), D.pt_bad, npx, hipMemcpyDeviceToHost, s));
+      AJ_TRY(hipMemcpyAsync(R->pt_new_added.data(), D.pt_new_added, npx, hipMemcpyDeviceToHost, s));
+      AJ_TRY(hipMemcpyAsync(R->pt_views.data(), d_views.p, sizeof(int) * npx, hipMemcpyDeviceToHost, s));
+    }
+  } else if (mut_done && np) {   // the resident caller keeps the flag where it keeps the rest
+    AJ_TRY(hipMemcpyAsync(D.pt_mutable, d_mut.p, npx, hipMemcpyDeviceToDevice, s));
   }
   AJ_TRY(hipMemcpyAsync(R->counts, d_cnt.p + 2, sizeof(int) * 3, hipMemcpyDeviceToHost, s));
   if (!err_read) AJ_TRY(hipMemcpyAsync(err, d_err.p, sizeof err, hipMemcpyDeviceToHost, s));
   AJ_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
   if (!err_read) MSFM_TRY(index_error());
+  *h2d_bytes += h2d;
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const msfm_round_problem* P, const msfm_round_options* opt_in,
+                               msfm_round_set** out) {
+  const char* who = "msfm_round_adjust";
+  if (!ctx) return MSFM_E_INVAL;
+  if (!S || !P || !out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
+  *out = nullptr;
+  if (S->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the store belongs to another context", who);
+  msfm_round_options opt;
+  if (opt_in) opt = *opt_in; else msfm_round_default_options(&opt);
+  const int nc = P->n_cams, nm = P->n_models, np = P->n_points, no = P->n_obs;
+  if (nc < 0 || nm < 0 || np < 0 || no < 0 || P->n_visible < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: negative count", who);
+  if ((nc && (!P->cam_img || !P->cam_pose || !P->cam_model_of_cam)) || (nm && !P->cam_model) || (no && (!P->obs_point || !P->obs_cam || !P->obs_feat)) ||
+      (np && (!P->point_xyz || !P->pt_bad || !P->pt_mse || !P->pt_mutable)) || (P->n_visible && !P->visible))
+    return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
+  RoundArgs A;
+  A.n_cams = nc; A.n_models = nm; A.n_points = np; A.n_obs = no;
+  A.cam_img = P->cam_img; A.cam_model_of_cam = P->cam_model_of_cam; A.model_mutable = P->model_mutable;
+  A.h_obs_point = P->obs_point; A.h_obs_cam = P->obs_cam; A.h_obs_feat = P->obs_feat;
+  A.new_cam = P->new_cam; A.n_visible = P->n_visible; A.visible = P->visible;
+  A.do_partial = P->do_partial != 0; A.do_full = P->do_full != 0; A.do_outliers = P->do_outliers != 0;
+  RoundTables T;
+  MSFM_TRY(round_tables(ctx, who, S, A, P->keypoints != nullptr, opt, &T));
+  if (!T.all_kp)   // a store without some image's keypoints: that image must have no observation (a walk over obs_cam)
+    for (int i = 0; i < no; i++) {
+      const int c = P->obs_cam[i];
+      if (c >= 0 && c < nc && !S->has_kp[P->cam_img[c]])
+        return msfm_set_error(ctx, MSFM_E_INVAL, "%s: no keypoints of image %d (argument or chain)", who, P->cam_img[c]);
+    }
+  const int FP = T.cam_fo[nc];
+  if (FP && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
+  MSFM_TRY(round_key_check(ctx, who, nc, T));
+  std::unique_ptr<msfm_round_set> R(new msfm_round_set());
+  R->ctx = ctx; R->n_cams = nc; R->n_models = nm; R->n_points = np;
+  R->keep_problem = opt.keep_problem != 0;
+  R->cam_pose.assign(P->cam_pose, P->cam_pose + 6 * (size_t)nc);
+  R->cam_model.assign(P->cam_model, P->cam_model + 3 * (size_t)nm);
+  memset(R->summary, 0, sizeof R->summary);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  int64_t h2d = 0;
+  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
+    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
+    if (e != hipSuccess) return e;
+    h2d += (int64_t)(cnt * sizeof(*h));
+    return buf.upload(h, cnt, s);
+  };
+  const size_t npx = (size_t)np, nox = (size_t)no;
+  // ---- one batch of uploads: the bulk arrays here, the camera tables in the core ----
+  DevBuf<int> d_fp, d_op, d_oc, d_of;
+  DevBuf<double> d_xyz, d_mse;
+  DevBuf<uint8_t> d_bad, d_mut_in, d_added;
+  DevBuf<float> d_kp_up;
+  AJ_TRY(up(d_fp, P->feat_point, (size_t)FP));
+  AJ_TRY(up(d_op, P->obs_point, nox)); AJ_TRY(up(d_oc, P->obs_cam, nox)); AJ_TRY(up(d_of, P->obs_feat, nox));
+  AJ_TRY(up(d_xyz, P->point_xyz, 3 * npx)); AJ_TRY(up(d_mse, P->pt_mse, npx));
+  AJ_TRY(up(d_bad, P->pt_bad, npx)); AJ_TRY(up(d_mut_in, P->pt_mutable, npx));
+  if (P->pt_new_added) AJ_TRY(up(d_added, P->pt_new_added, npx));
+  else { AJ_TRY(d_added.alloc(std::max<size_t>(1, npx))); AJ_TRY(hipMemsetAsync(d_added.p, 0, std::max<size_t>(1, npx), s)); }
+  std::vector<float> h_kp;   // (lives to the final wait)
+  if (P->keypoints) {   // the rows of the cameras' images only, packed in camera order
+    h_kp.resize(2 * (size_t)T.kp_rows);
+    for (int c = 0; c < nc; c++) {
+      const int im = P->cam_img[c];
+      std::copy(P->keypoints + 2 * (size_t)S->feat_off[im], P->keypoints + 2 * ((size_t)S->feat_off[im] + S->n_features[im]), h_kp.begin() + 2 * (size_t)T.kp_base[c]);
+    }
+    AJ_TRY(up(d_kp_up, h_kp.data(), h_kp.size()));
+  }
+  RoundDev D;
+  D.feat_point = d_fp.p; D.obs_point = d_op.p; D.obs_cam = d_oc.p; D.obs_feat = d_of.p;
+  D.point_xyz = d_xyz.p; D.pt_mse = d_mse.p; D.pt_bad = d_bad.p; D.pt_mutable = d_mut_in.p; D.pt_new_added = d_added.p;
+  D.kp = P->keypoints ? d_kp_up.p : S->d_kp.p;
+  MSFM_TRY(round_adjust_dev(ctx, who, A, T, D, opt, &h2d, R.get(), /*fetch_points=*/true));
   R->h2d_bytes = h2d;
   ctx->children++;   // a set is a child of its context, like a store
   *out = R.release();

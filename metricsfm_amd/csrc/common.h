@@ -179,6 +179,16 @@ __device__ static inline int wave_sum_int(int c) {
   return c;
 }
 
+// the segment of position x in CSR offsets: off[lo] <= x < off[lo + 1] (empty segments are stepped over)
+__device__ static inline int csr_segment_of(const int* __restrict__ off, int n, int x) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (off[mid] <= x) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
 // The CSR offsets of a batch call (n + 1 entries, n > 0); `who` prefixes the message.
 static inline int msfm_check_offsets(msfm_ctx* ctx, const char* who, int n, const int* offsets) {
   if (offsets[0] != 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: offsets[0] must be 0", who);
@@ -267,8 +277,26 @@ struct msfm_localize_set {
   bool have_pts = false;
   int64_t h2d_bytes = 0;
   DevBuf<int> d_cp;               // [n_corr]           (have_pts and n_corr > 0 only)
+  DevBuf<int> d_cf;               // [n_corr] corr_feat (sets of localize_candidates_dev with resident arrays only)
   DevBuf<double> d_pw, d_p2;      // [n_corr][3], [n_corr][2]
 };
+
+struct LocalizeDev {   // the bulk arrays of the state on the device (recon.hip's); kp: every image's rows, or NULL = the store's
+  const int* feat_point; const uint8_t* pt_bad; const double* pt_mse; const int* pt_views; const double* point_xyz; const float* kp;
+};
+struct msfm_localize_problem;
+int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const msfm_localize_problem* P, const LocalizeDev* dev,
+                            msfm_localize_set** out);
+struct msfm_localize_pose_set {   // host memory only
+  int n = 0, n_corr = 0, n_tried = 0, winner = -1, next_row = -1;
+  std::vector<uint8_t> tried, arm, pass, state;
+  std::vector<double> f, R, t, avg, errors;
+  std::vector<int> best_step, best_iter, n_in, n_out;
+};
+struct msfm_localize_pose_options;
+int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* L, const double* row_f, const double* row_f_init, int n_points,
+                       const uint8_t* pt_new_added, const uint8_t* d_added_dev, const msfm_localize_pose_options* opt_in, msfm_localize_pose_set** out,
+                       DevBuf<uint8_t>* keep_state, int64_t* h2d_bytes);
 
 // The device halves of msfm_epnp_ransac_batch / msfm_epnpf_sweep_batch (pose.hip), in the manner of the two below: device
 // buffers in, the two launches, device buffers out; no synchronisation.  The sample scratch belongs to the caller, who keeps
@@ -306,6 +334,108 @@ struct msfm_ba;
 // msfm_ba_create with the bulk arrays of the problem (obs_cam, obs_pt, obs_xy, point, pt_weight, pt_mutable) in DEVICE memory
 int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device, msfm_ba** out);
 const double* ba_device_points(const msfm_ba* ba);   // the resident points [n_points][3] of a problem (adjust.hip scatters them on the device)
+
+// ---- adjusting a round (adjust.hip): msfm_round_adjust is its checks + upload + round_adjust_dev + download; recon.hip calls
+// the same core on the arrays it keeps resident ----
+struct msfm_round_set {
+  msfm_ctx* ctx = nullptr;
+  int n_cams = 0, n_models = 0, n_points = 0;   // (n_points = 0 and empty point arrays: a set of msfm_recon_adjust, whose points stay on the device)
+  std::vector<double> cam_pose, cam_model, cam_R, cam_t, cam_c, cam_fk, point_xyz, pt_mse;
+  std::vector<uint8_t> pt_mutable, pt_bad, pt_new_added;
+  std::vector<int> pt_views;
+  int counts[3] = {0, 0, 0};        // count_outliers, count_new_add, count_outliers_new_add
+  int adjust[2][2] = {{0, 0}, {0, 0}};   // "adjust cams", "adjust pts" of each solve
+  int solved[2] = {0, 0};
+  msfm_ba_summary summary[2];
+  std::vector<msfm_ba_iteration> rows[2];
+  bool keep_problem = false;
+  struct Problem {
+    int n_points = 0, n_obs = 0;
+    std::vector<int> kept, obs_cam, obs_pt;
+    std::vector<double> obs_xy, pt_weight;
+    std::vector<uint8_t> cam_mutable, pt_mutable;
+  } problem[2];
+  int64_t h2d_bytes = 0;
+};
+struct RoundArgs {     // counts and the O(cameras) arguments, host pointers
+  int n_cams = 0, n_models = 0, n_points = 0, n_obs = 0;
+  const int* cam_img = nullptr; const int* cam_model_of_cam = nullptr; const uint8_t* model_mutable = nullptr;
+  const int *h_obs_point = nullptr, *h_obs_cam = nullptr, *h_obs_feat = nullptr;   // the rows on the host, where the caller has them (a refusal's text)
+  int new_cam = -1, n_visible = 0;
+  const int* visible = nullptr;
+  bool do_partial = false, do_full = false, do_outliers = false;
+};
+struct RoundTables {   // what round_tables makes of them
+  std::vector<int> cam_fo, rank, cam_of_rank, kp_base;   // kp_base[c]: the first keypoint row of camera c in RoundDev::kp
+  std::vector<uint8_t> cam_free, cam_all;
+  int max_feat = 1, bf = 1;
+  long kp_rows = 0;        // packed_kp: rows of a keypoint array that holds the cameras' images only, in camera order
+  bool all_kp = true;      // !packed_kp: the store has the keypoints of every camera's image
+};
+struct RoundDev {      // the bulk arrays, device pointers; the point arrays and flags are written in place
+  const int *feat_point = nullptr, *obs_point = nullptr, *obs_cam = nullptr, *obs_feat = nullptr;
+  double *point_xyz = nullptr, *pt_mse = nullptr;
+  uint8_t *pt_bad = nullptr, *pt_mutable = nullptr, *pt_new_added = nullptr;
+  const float* kp = nullptr;
+};
+// packed_kp: kp_base counts rows of a packed upload; otherwise it is the store's feat_off (a resident array of every image's rows)
+int round_tables(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const RoundArgs& A, bool packed_kp, const msfm_round_options& opt,
+                 RoundTables* T);
+// the two refusals of the device-side index check, worded once: x = the first bad feat_point entry / row = the first bad row
+int round_fp_error(msfm_ctx* ctx, const char* who, const std::vector<int>& cam_fo, int n_cams, int n_points, int x);
+int round_row_error(msfm_ctx* ctx, const char* who, int row, int point, int cam, int feat);
+int round_key_check(msfm_ctx* ctx, const char* who, int n_cams, const RoundTables& T);
+int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const RoundTables& T, const RoundDev& D, const msfm_round_options& opt,
+                     int64_t* h2d_bytes, msfm_round_set* R, bool fetch_points);
+
+// ---- a new camera's points (newpoints.hip): msfm_new_points is newpoints_plan + a packed upload of the involved cameras' rows +
+// newpoints_dev + download; recon.hip runs plan and kernels on its resident feat_point and keypoints and appends on the device ----
+struct msfm_new_points_set {
+  int n_new = 0, n_entries = 0;
+  std::vector<int> pt_off, cam2, feat1, feat2, vis_entry, pt_match, n_matches, n_candidates, n_accepted;
+  std::vector<double> X, mse;
+  std::vector<uint8_t> takes1, takes2, large;
+  int64_t h2d_bytes = 0;
+};
+struct NewPointsEnt {   // one visible entry of one new camera
+  int m0;             // first match of the pair in the store
+  int fp1, fp2;       // first feat_point row of camera 1 / 2 in the feat_point array the kernels get
+  int kp1, kp2;       // first keypoint row of image 1 / 2
+  int cam1, cam2;     // rows of the uploaded camera table
+  int slot1, slot2;   // first claim slot of camera 1 / 2 in this new camera's slot table
+  int k;              // the new camera
+  int large;          // th_angle_large applies (:781)
+};
+struct NewPointsArgs {   // host pointers: the cameras and the lists
+  int n_cams = 0;
+  const int* cam_img = nullptr;
+  const double *cam_R = nullptr, *cam_t = nullptr, *cam_c = nullptr, *cam_fk = nullptr;
+  int n_new = 0;
+  const int *new_cam = nullptr, *vis_off = nullptr, *vis_cam = nullptr;
+};
+#define NP_KP_STORE 0    // the store's keypoints (made from a chain): a camera's rows start at feat_off of its image
+#define NP_KP_PACKED 1   // a packed upload of the involved cameras' rows
+#define NP_KP_ALL 2      // an array of every image's rows in the store's order (a resident state's)
+struct NewPointsPlan {
+  int nn = 0, E = 0, M = 0;   // new cameras, visible entries, matches of the walk
+  long fp_rows = 0, kp_rows = 0, n_slots = 0;
+  std::vector<NewPointsEnt> ent;
+  std::vector<int> cam_fo, off_all, blk_off, cam_off, involved, fp_base, kp_base;
+};
+struct NewPointsDev {   // what newpoints_dev allocates; d_out is the result block, the o_* its layout (newpoints.hip)
+  DevBuf<NewPointsEnt> d_ent;
+  DevBuf<int> d_offa, d_blk, d_val, d_val_s, d_slot;
+  DevBuf<double> d_cam, d_Xall, d_mseall;
+  DevBuf<unsigned long long> d_key, d_key_s;
+  DevBuf<char> tmp, d_out;
+  size_t o_mse = 0, o_w = 0, o_f1 = 0, o_f2 = 0, o_nc = 0, o_na = 0, o_t1 = 0, o_t2 = 0, out_bytes = 0;
+};
+struct msfm_new_points_options;
+int newpoints_plan(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const NewPointsArgs& P, const msfm_new_points_options& opt,
+                   bool fp_resident, int kp_mode, NewPointsPlan* L, msfm_new_points_set* R);
+int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs& P, const NewPointsPlan& L, const msfm_new_points_options& opt,
+                  const int* d_fp, const float* d_kp, int64_t* h2d_bytes, NewPointsDev* W);
+void newpoints_collect(const NewPointsArgs& P, const NewPointsPlan& L, const NewPointsDev& W, const char* hb, msfm_new_points_set* R);
 int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_off, const int* d_nf, const int* d_fo, int n_pairs,
                      const int* d_pair, const int* d_moff, const int* d_match, int M, msfm_track_dev* out);
 

@@ -297,15 +297,18 @@ MSFM_API void msfm_match_store_destroy(msfm_match_store* S) {
   msfm_ctx_child_released(ctx);
 }
 
-MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, const msfm_localize_problem* P, msfm_localize_set** out) {
+// The call on device arrays: with `dev` the bulk arrays of the state (feat_point, pt_bad, pt_mse, pt_views, point_xyz, keypoints)
+// are the caller's resident ones - P then carries counts and the O(cameras + candidates) lists only - and the set keeps its
+// correspondences on the device without reading pts_w / pts_2d back.  msfm_localize_candidates is this with dev = NULL: it uploads.
+int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const msfm_localize_problem* P, const LocalizeDev* dev,
+                            msfm_localize_set** out) {
   using namespace loc;
-  const char* who = "msfm_localize_candidates";
   if (!ctx) return MSFM_E_INVAL;
   if (!S || !P || !out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
   *out = nullptr;
   if (S->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the store belongs to another context", who);
   const int ni = S->n_images, nc = P->n_cams, nk = P->n_cand, npt = P->n_points;
-  if (nc < 0 || nk < 0 || npt < 0 || (nc && !P->cam_img) || (nk && (!P->cand_img || !P->fail_times)) || (npt && (!P->pt_bad || !P->pt_mse || !P->pt_views)))
+  if (nc < 0 || nk < 0 || npt < 0 || (nc && !P->cam_img) || (nk && (!P->cand_img || !P->fail_times)) || (npt && !dev && (!P->pt_bad || !P->pt_mse || !P->pt_views)))
     return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array or negative count", who);
   // ---- O(images + cameras + candidates) on the host ----
   std::vector<int> cam_of_img(std::max(1, ni), -1), cam_fo(nc + 1, 0);
@@ -318,7 +321,7 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
     cam_fo[c + 1] = cam_fo[c] + S->n_features[im];
   }
   const int FP = cam_fo[nc];
-  if (FP && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
+  if (FP && !dev && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
   std::vector<int> slot_off(nk + 1, 0);
   for (int k = 0; k < nk; k++) {
     const int im = P->cand_img[k];
@@ -329,10 +332,11 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
     if ((long)slot_off[k] + S->n_features[im] > 0x7fffffffL) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: more than 2^31 candidate features", who);
     slot_off[k + 1] = slot_off[k] + S->n_features[im];
   }
-  const bool want_pts = P->point_xyz != nullptr;
+  const bool want_pts = dev || P->point_xyz != nullptr;
+  const bool own_kp = dev ? dev->kp != nullptr : P->keypoints != nullptr;   // keypoints that do not come from the store
   if (want_pts) {
     for (int k = 0; k < nk; k++)
-      if (!P->keypoints && !S->has_kp[P->cand_img[k]])
+      if (!own_kp && !S->has_kp[P->cand_img[k]])
         return msfm_set_error(ctx, MSFM_E_INVAL, "%s: point_xyz given, but no keypoints of candidate image %d (argument or chain)", who, P->cand_img[k]);
   }
   // the walk of :452-474 as a list: per candidate (ascending) its row of the store, entries with a registered idx2 and matches
@@ -373,8 +377,15 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   DevBuf<int> d_fp, d_views, d_slot, d_first, d_pcount, d_ncorr, d_err;
   DevBuf<uint8_t> d_bad;
   DevBuf<double> d_mse;
-  LC_TRY(up(d_wp, wp.data(), (size_t)nwp)); LC_TRY(up(d_fp, P->feat_point, (size_t)FP)); LC_TRY(up(d_bad, P->pt_bad, (size_t)npt));
-  LC_TRY(up(d_mse, P->pt_mse, (size_t)npt)); LC_TRY(up(d_views, P->pt_views, (size_t)npt)); LC_TRY(up(d_slot, slot_off.data(), (size_t)nk + 1));
+  LC_TRY(up(d_wp, wp.data(), (size_t)nwp)); LC_TRY(up(d_slot, slot_off.data(), (size_t)nk + 1));
+  if (!dev) {
+    LC_TRY(up(d_fp, P->feat_point, (size_t)FP)); LC_TRY(up(d_bad, P->pt_bad, (size_t)npt));
+    LC_TRY(up(d_mse, P->pt_mse, (size_t)npt)); LC_TRY(up(d_views, P->pt_views, (size_t)npt));
+  }
+  const int* fp_p = dev ? dev->feat_point : d_fp.p;
+  const uint8_t* bad_p = dev ? dev->pt_bad : d_bad.p;
+  const double* mse_p = dev ? dev->pt_mse : d_mse.p;
+  const int* views_p = dev ? dev->pt_views : d_views.p;
   LC_TRY(d_first.alloc(std::max(1, S_slots))); LC_TRY(d_pcount.alloc(nwp)); LC_TRY(d_ncorr.alloc(nk)); LC_TRY(d_err.alloc(1));
   const int big = LOC_BIG;
   LC_TRY(hipMemcpyAsync(d_err.p, &big, sizeof(int), hipMemcpyHostToDevice, s));
@@ -383,8 +394,8 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   {
     KTimer t(ctx, "localize_resolve");
     t.count = (FP ? 1 : 0) + (W ? 1 : 0) + 1;
-    if (FP) hipLaunchKernelGGL(k_check_points, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, npt, d_fp.p, d_err.p);
-    if (W) hipLaunchKernelGGL(k_resolve, dim3(cdiv(W, 256)), dim3(256), 0, s, (int)W, nwp, d_wp.p, S->d_match.p, d_fp.p, npt, d_bad.p, d_slot.p,
+    if (FP) hipLaunchKernelGGL(k_check_points, dim3(cdiv(FP, 256)), dim3(256), 0, s, FP, npt, fp_p, d_err.p);
+    if (W) hipLaunchKernelGGL(k_resolve, dim3(cdiv(W, 256)), dim3(256), 0, s, (int)W, nwp, d_wp.p, S->d_match.p, fp_p, npt, bad_p, d_slot.p,
                               d_first.p, d_pcount.p);
     hipLaunchKernelGGL(k_count, dim3(nk), dim3(256), 0, s, d_slot.p, d_first.p, d_ncorr.p);
   }
@@ -429,8 +440,11 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   DevBuf<double> d_xyz, d_pw, d_p2;
   const float* d_kp = nullptr;
   if (want_pts) {
-    LC_TRY(up(d_xyz, P->point_xyz, 3 * (size_t)npt));
-    if (P->keypoints) {   // the rows of the kept candidates only
+    if (!dev) LC_TRY(up(d_xyz, P->point_xyz, 3 * (size_t)npt));
+    if (dev && dev->kp) {   // every image's rows, resident
+      for (int k = 0; k < nk; k++) kp_off[k] = S->feat_off[P->cand_img[k]];
+      d_kp = dev->kp;
+    } else if (P->keypoints) {   // the rows of the kept candidates only
       long n = 0;
       for (int r = 0; r < nkept; r++) { kp_off[order[r]] = (int)n; n += S->n_features[P->cand_img[order[r]]]; }
       LC_TRY(d_kp_up.alloc(2 * (size_t)std::max(1L, n)));
@@ -462,7 +476,7 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   LC_TRY(hipMemsetAsync(d_idx_s.p, 0, sizeof(int) * (size_t)T, s));   // (k_gather indexes with it: never an uninitialised value)
   {
     KTimer t(ctx, "localize_emit");
-    hipLaunchKernelGGL(k_emit, dim3(nk), dim3(256), 0, s, d_slot.p, d_out.p, d_kpo.p, d_first.p, nwp, d_wp.p, S->d_match.p, d_fp.p, d_mse.p, d_views.p,
+    hipLaunchKernelGGL(k_emit, dim3(nk), dim3(256), 0, s, d_slot.p, d_out.p, d_kpo.p, d_first.p, nwp, d_wp.p, S->d_match.p, fp_p, mse_p, views_p,
                        d_key.p, d_idx.p, d_feat.p, d_point.p, d_kprow.p);
   }
   if (!sb.empty()) {
@@ -482,14 +496,14 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   }
   {
     KTimer t(ctx, "localize_gather");
-    hipLaunchKernelGGL(k_gather, dim3(cdiv(T, 256)), dim3(256), 0, s, (int)T, d_idx_s.p, d_feat.p, d_point.p, d_kprow.p, d_xyz.p, d_kp,
+    hipLaunchKernelGGL(k_gather, dim3(cdiv(T, 256)), dim3(256), 0, s, (int)T, d_idx_s.p, d_feat.p, d_point.p, d_kprow.p, dev ? dev->point_xyz : d_xyz.p, d_kp,
                        d_cf.p, d_cp.p, want_pts ? d_pw.p : nullptr, want_pts ? d_p2.p : nullptr);
   }
   LC_TRY(hipGetLastError());
   R->corr_feat.resize(T); R->corr_point.resize(T);
   LC_TRY(hipMemcpyAsync(R->corr_feat.data(), d_cf.p, sizeof(int) * (size_t)T, hipMemcpyDeviceToHost, s));
   LC_TRY(hipMemcpyAsync(R->corr_point.data(), d_cp.p, sizeof(int) * (size_t)T, hipMemcpyDeviceToHost, s));
-  if (want_pts) {
+  if (want_pts && !dev) {
     R->pts_w.resize(3 * (size_t)T); R->pts_2d.resize(2 * (size_t)T);
     LC_TRY(hipMemcpyAsync(R->pts_w.data(), d_pw.p, sizeof(double) * 3 * (size_t)T, hipMemcpyDeviceToHost, s));
     LC_TRY(hipMemcpyAsync(R->pts_2d.data(), d_p2.p, sizeof(double) * 2 * (size_t)T, hipMemcpyDeviceToHost, s));
@@ -497,7 +511,12 @@ MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, 
   LC_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
   R->h2d_bytes = h2d;
   if (want_pts) { R->d_cp.swap(d_cp); R->d_pw.swap(d_pw); R->d_p2.swap(d_p2); }   // resident for msfm_localize_poses
+  if (dev) R->d_cf.swap(d_cf);   // (a resident state commits the winner's row from the device)
   return hand_over();
+}
+
+MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, const msfm_localize_problem* P, msfm_localize_set** out) {
+  return localize_candidates_dev(ctx, "msfm_localize_candidates", S, P, nullptr, out);
 }
 
 MSFM_API int msfm_localize_set_size(const msfm_localize_set* R, int* n_kept, int* n_corr, int* n_visible, int* has_points, int64_t* h2d_bytes) {

@@ -22,12 +22,6 @@
 
 #define LP_BIG 0x7fffffff
 
-struct msfm_localize_pose_set {   // host memory only
-  int n = 0, n_corr = 0, n_tried = 0, winner = -1, next_row = -1;
-  std::vector<uint8_t> tried, arm, pass, state;
-  std::vector<double> f, R, t, avg, errors;
-  std::vector<int> best_step, best_iter, n_in, n_out;
-};
 
 namespace lpose {
 
@@ -150,10 +144,13 @@ MSFM_API void msfm_localize_pose_default_options(msfm_localize_pose_options* o) 
   o->max_tries = 16;
 }
 
-MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, const double* row_f, const double* row_f_init, int n_points,
-                                 const uint8_t* pt_new_added, const msfm_localize_pose_options* opt_in, msfm_localize_pose_set** out) {
+// The call with pt_new_added optionally on the device (d_added, a resident state's: nothing is uploaded for it then) and, with
+// keep_state, the corr_state array [n_corr] handed to the caller on the device as well; h2d_bytes (optional) is incremented at
+// every upload.  msfm_localize_poses is this with none of the three.
+int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* L, const double* row_f, const double* row_f_init, int n_points,
+                       const uint8_t* pt_new_added, const uint8_t* d_added_dev, const msfm_localize_pose_options* opt_in, msfm_localize_pose_set** out,
+                       DevBuf<uint8_t>* keep_state, int64_t* h2d_bytes) {
   using namespace lpose;
-  const char* who = "msfm_localize_poses";
   if (!ctx) return MSFM_E_INVAL;
   if (!L || !out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
   *out = nullptr;
@@ -225,9 +222,16 @@ MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, cons
   DevBuf<uint8_t> d_added, d_pass, d_state;
   EpnpScratch ws1;
   EpnpfScratch ws2;
-  LP_TRY(d_slot.from(slot, s)); LP_TRY(d_toff.from(toff, s)); LP_TRY(d_off1.from(off1, s)); LP_TRY(d_off2.from(off2, s));
+  int64_t h2d = 0;
+  auto up = [&](auto& buf, const auto& v) -> hipError_t { h2d += (int64_t)(v.size() * sizeof(v[0])); return buf.from(v, s); };
+  LP_TRY(up(d_slot, slot)); LP_TRY(up(d_toff, toff)); LP_TRY(up(d_off1, off1)); LP_TRY(up(d_off2, off2));
   LP_TRY(d_rowf.alloc(n)); LP_TRY(d_rowf.upload(row_f, n, s));
-  if (pt_new_added && n_points) { LP_TRY(d_added.alloc(n_points)); LP_TRY(d_added.upload(pt_new_added, n_points, s)); }
+  h2d += (int64_t)sizeof(double) * n;
+  if (!d_added_dev && pt_new_added && n_points) {
+    LP_TRY(d_added.alloc(n_points)); LP_TRY(d_added.upload(pt_new_added, n_points, s));
+    h2d += n_points;
+  }
+  const uint8_t* added_p = d_added_dev ? d_added_dev : d_added.p;
   LP_TRY(d_w1.alloc(3 * (size_t)std::max(1, E1))); LP_TRY(d_x1.alloc(2 * (size_t)std::max(1, E1))); LP_TRY(d_e1.alloc(std::max(1, E1)));
   LP_TRY(d_w2.alloc(3 * (size_t)std::max(1, E2))); LP_TRY(d_x2.alloc(2 * (size_t)std::max(1, E2))); LP_TRY(d_e2.alloc(std::max(1, E2)));
   LP_TRY(d_f.alloc(n)); LP_TRY(d_R.alloc(9 * (size_t)n)); LP_TRY(d_t.alloc(3 * (size_t)n)); LP_TRY(d_avg.alloc(n)); LP_TRY(d_bstep.alloc(n));
@@ -256,7 +260,7 @@ MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, cons
     a1 = ArmOut{nullptr, d_R1.p, d_t1.p, d_a1.p, nullptr, d_bi1.p};
   }
   if (E2) {   // :673-704
-    LP_TRY(d_finit.from(f_init, s));
+    LP_TRY(up(d_finit, f_init));
     LP_TRY(d_f2.alloc(n)); LP_TRY(d_R2.alloc(9 * (size_t)n)); LP_TRY(d_t2.alloc(3 * (size_t)n)); LP_TRY(d_a2.alloc(n)); LP_TRY(d_bs2.alloc(n));
     LP_TRY(d_bi2.alloc(n));
     MSFM_TRY(pose_epnpf_dev(ctx, n, n_steps, d_off2.p, d_w2.p, d_x2.p, d_finit.p, &opt.sweep, ws2, d_f2.p, d_R2.p, d_t2.p, d_e2.p, d_a2.p,
@@ -269,9 +273,9 @@ MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, cons
     hipLaunchKernelGGL(k_rows, dim3(cdiv(nt, 64)), dim3(64), 0, s, nt, d_slot.p, a1, a2, d_rowf.p, opt.th_mse_localization, d_f.p, d_R.p, d_t.p,
                        d_avg.p, d_bstep.p, d_biter.p, d_pass.p);
     hipLaunchKernelGGL(k_first, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, d_e1.p, d_e2.p, d_avg.p, d_pass.p, L->d_cp.p,
-                       n_points, d_added.p, d_first.p);
+                       n_points, added_p, d_first.p);
     hipLaunchKernelGGL(k_state, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, d_e1.p, d_e2.p, d_avg.p, d_pass.p, L->d_cp.p,
-                       n_points, d_added.p, d_first.p, d_err.p, d_state.p, d_nin.p, d_nout.p);
+                       n_points, added_p, d_first.p, d_err.p, d_state.p, d_nin.p, d_nout.p);
   }
   LP_TRY(hipGetLastError());
   // ---- one read-back, one wait ----
@@ -284,8 +288,15 @@ MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, cons
   LP_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
   for (int r = 0; r < n; r++)
     if (R->tried[r] && R->pass[r]) { R->winner = r; break; }
+  if (keep_state) keep_state->swap(d_state);
+  if (h2d_bytes) *h2d_bytes += h2d;
   *out = R.release();
   return MSFM_OK;
+}
+
+MSFM_API int msfm_localize_poses(msfm_ctx* ctx, const msfm_localize_set* L, const double* row_f, const double* row_f_init, int n_points,
+                                 const uint8_t* pt_new_added, const msfm_localize_pose_options* opt_in, msfm_localize_pose_set** out) {
+  return localize_poses_dev(ctx, "msfm_localize_poses", L, row_f, row_f_init, n_points, pt_new_added, nullptr, opt_in, out, nullptr, nullptr);
 }
 
 MSFM_API int msfm_localize_pose_set_size(const msfm_localize_pose_set* R, int* n_rows, int* n_corr, int* n_tried, int* winner, int* next_row) {
