@@ -209,12 +209,6 @@ __global__ __launch_bounds__(256) void k_outliers(int n_points, const int* __res
   }
 }
 
-static int bits_for(unsigned v) {   // bits that hold every value 0 .. v
-  int b = 1;
-  while (b < 32 && (v >> b)) b++;
-  return b;
-}
-
 // Camera::UpdatePoseFromData (camera.cc:113-137): rotation::AngleAxisToRotationMatrix with the C library's sin / cos, then
 // c = -(R^T t), the products summed in row order
 static void pose_to_camera(const double* pose, double* R, double* t, double* c) {
@@ -288,7 +282,7 @@ int round_tables(msfm_ctx* ctx, const char* who, const msfm_match_store* S, cons
     std::sort(T->cam_of_rank.begin(), T->cam_of_rank.begin() + nc, [&](int a, int b) { return A.cam_img[a] < A.cam_img[b]; });
     for (int r = 0; r < nc; r++) T->rank[T->cam_of_rank[r]] = r;
   }
-  T->bf = adj::bits_for((unsigned)(T->max_feat - 1));
+  T->bf = bits_for((unsigned)(T->max_feat - 1));
   // the free cameras of the partial stage (:922-945): the new camera's model, and its visible cameras
   T->cam_free.assign(std::max(1, nc), 0); T->cam_all.assign(std::max(1, nc), 1);
   if (A.do_partial) {
@@ -311,7 +305,7 @@ int round_row_error(msfm_ctx* ctx, const char* who, int row, int point, int cam,
 }
 
 int round_key_check(msfm_ctx* ctx, const char* who, int n_cams, const RoundTables& T) {
-  const int br = adj::bits_for((unsigned)std::max(0, n_cams - 1));
+  const int br = bits_for((unsigned)std::max(0, n_cams - 1));
   if (T.bf + br > 32)
     return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %d cameras and %d features in an image need %d + %d bits: the sort key holds image rank and feature in 32", who,
                           n_cams, T.max_feat, br, T.bf);
@@ -328,30 +322,22 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   const bool solve = A.do_partial || A.do_full;
   const std::vector<int>& cam_fo = T.cam_fo;
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
   const size_t npx = (size_t)np, nox = (size_t)no;
-  DevBuf<int> d_fo, d_rank, d_cor, d_kpb, d_err, d_cnt;
+  DevBuf<int> d_fo, d_rank, d_cor, d_kpb, d_err, d_cnt, d_views, d_seg, keep_row, keep_pt, new_row, new_pt;
   DevBuf<double> d_cam;
-  DevBuf<uint8_t> d_free, d_call;
-  AJ_TRY(up(d_fo, cam_fo.data(), (size_t)nc + 1));
-  AJ_TRY(up(d_rank, T.rank.data(), (size_t)nc)); AJ_TRY(up(d_cor, T.cam_of_rank.data(), (size_t)nc)); AJ_TRY(up(d_kpb, T.kp_base.data(), (size_t)nc));
-  AJ_TRY(up(d_free, T.cam_free.data(), (size_t)nc)); AJ_TRY(up(d_call, T.cam_all.data(), (size_t)nc));
+  DevBuf<uint8_t> d_free, d_call, d_first, d_att, d_freed, d_mut;
+  DevBuf<unsigned long long> d_key, d_key_s;
+  DevBuf<char> tmp;
+  DevScope sc(ctx);
+  AJ_TRY(sc.up(d_fo, cam_fo.data(), (size_t)nc + 1));
+  AJ_TRY(sc.up(d_rank, T.rank.data(), (size_t)nc)); AJ_TRY(sc.up(d_cor, T.cam_of_rank.data(), (size_t)nc)); AJ_TRY(sc.up(d_kpb, T.kp_base.data(), (size_t)nc));
+  AJ_TRY(sc.up(d_free, T.cam_free.data(), (size_t)nc)); AJ_TRY(sc.up(d_call, T.cam_all.data(), (size_t)nc));
   const float* d_kp = D.kp;
   // err: feat_point entry, obs row; cnt: free points of the partial / the full stage, the three counts of the outlier stage
   AJ_TRY(d_err.alloc(2)); AJ_TRY(d_cnt.alloc(8));
   AJ_TRY(hipMemsetD32Async((hipDeviceptr_t)d_err.p, ADJ_BIG, 2, s));
   AJ_TRY(hipMemsetAsync(d_cnt.p, 0, sizeof(int) * 8, s));
   // ---- the point side in std::map order ----
-  DevBuf<unsigned long long> d_key, d_key_s;
-  DevBuf<uint8_t> d_first, d_att, d_freed, d_mut;
-  DevBuf<int> d_views, d_seg;
-  DevBuf<char> tmp;
   AJ_TRY(d_key.alloc(std::max<size_t>(1, nox))); AJ_TRY(d_key_s.alloc(std::max<size_t>(1, nox))); AJ_TRY(d_first.alloc(std::max<size_t>(1, nox)));
   AJ_TRY(d_views.alloc(npx + 1)); AJ_TRY(d_seg.alloc(npx + 2));
   AJ_TRY(d_att.alloc(std::max<size_t>(1, npx))); AJ_TRY(d_freed.alloc(std::max<size_t>(1, npx))); AJ_TRY(d_mut.alloc(std::max<size_t>(1, npx)));
@@ -413,7 +399,6 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
     return MSFM_OK;
   };
   // ---- the two solves ----
-  DevBuf<int> keep_row, keep_pt, new_row, new_pt;
   if (solve) {
     AJ_TRY(keep_row.alloc(nox + 1)); AJ_TRY(keep_pt.alloc(npx + 1)); AJ_TRY(new_row.alloc(nox + 1)); AJ_TRY(new_pt.alloc(npx + 1));
   }
@@ -457,6 +442,7 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
     DevBuf<int> obs_cam, obs_pt, kept;
     DevBuf<double> obs_xy, point, ptw;
     DevBuf<uint8_t> pmut;
+    DevScope stage_sc(ctx);   // the problem's blocks: the solve below reads them
     AJ_TRY(obs_cam.alloc(nok)); AJ_TRY(obs_pt.alloc(nok)); AJ_TRY(obs_xy.alloc(2 * (size_t)nok));
     AJ_TRY(point.alloc(3 * (size_t)npk)); AJ_TRY(ptw.alloc(npk)); AJ_TRY(pmut.alloc(npk)); AJ_TRY(kept.alloc(npk));
     {
@@ -483,22 +469,21 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
     B.point = point.p; B.obs_cam = obs_cam.p; B.obs_pt = obs_pt.p; B.obs_xy = obs_xy.p; B.pt_weight = ptw.p;
     B.cam_mutable = cam_mut.data(); B.model_mutable = A.model_mutable; B.pt_mutable = pmut.p;
     msfm_ba* ba = nullptr;
-    // an error return releases the buffers above to the block cache: only behind a wait for what was enqueued on them
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(s); return rc; };
-    if (int rc = ba_create_impl(ctx, &B, /*bulk_on_device=*/true, &ba)) return fail(rc);
+    MSFM_TRY(ba_create_impl(ctx, &B, /*bulk_on_device=*/true, &ba));
     struct Guard { msfm_ba* p; ~Guard() { if (p) msfm_ba_destroy(p); } } guard{ba};
     R->rows[stage].assign((size_t)std::max(0, bo.max_num_iterations) + 2, msfm_ba_iteration());
     msfm_ba_summary& sum = R->summary[stage];
     sum.iterations = R->rows[stage].data();
     sum.iterations_capacity = (int)R->rows[stage].size();
-    if (int rc = msfm_ba_run(ba, &bo, &sum)) return fail(rc);
+    MSFM_TRY(msfm_ba_run(ba, &bo, &sum));
     // BundleAdjuster::UpdateParameters: the points on the device, cameras and models through the host copy the next stage starts from
     {
       KTimer tm(ctx, "round_scatter_points");
       hipLaunchKernelGGL(k_scatter_points, dim3(cdiv(npk, 256)), dim3(256), 0, s, npk, kept.p, ba_device_points(ba), D.point_xyz);
     }
     AJ_TRY(hipGetLastError());
-    if (int rc = msfm_ba_download_params(ba, R->cam_pose.data(), R->cam_model.data(), nullptr)) return fail(rc);   // (synchronises: the scatter has run)
+    MSFM_TRY(msfm_ba_download_params(ba, R->cam_pose.data(), R->cam_model.data(), nullptr));   // (synchronises: the scatter has run)
+    stage_sc.dismiss();
     R->solved[stage] = 1;
   }
   // ---- Camera::UpdatePoseFromData / UpdataModelFromData ----
@@ -514,7 +499,7 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
     std::copy(R->cam_fk.begin() + 3 * cx, R->cam_fk.begin() + 3 * cx + 3, C + 12);
   }
   if (A.do_outliers && np) {
-    AJ_TRY(up(d_cam, cam.data(), ADJ_CAM * (size_t)nc));
+    AJ_TRY(sc.up(d_cam, cam.data(), ADJ_CAM * (size_t)nc));
     KTimer tm(ctx, "round_outliers");
     hipLaunchKernelGGL(k_outliers, dim3(cdiv(np, 256)), dim3(256), 0, s, np, d_seg.p, d_key_s.p, d_first.p, d_cor.p, bf, d_kpb.p, d_kp, d_cam.p, D.point_xyz,
                        opt.th_mse_outliers, D.pt_bad, D.pt_mse, D.pt_new_added, d_cnt.p + 2);
@@ -536,9 +521,9 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   }
   AJ_TRY(hipMemcpyAsync(R->counts, d_cnt.p + 2, sizeof(int) * 3, hipMemcpyDeviceToHost, s));
   if (!err_read) AJ_TRY(hipMemcpyAsync(err, d_err.p, sizeof err, hipMemcpyDeviceToHost, s));
-  AJ_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
+  AJ_TRY(sc.finish());   // the scratch above is released on return
   if (!err_read) MSFM_TRY(index_error());
-  *h2d_bytes += h2d;
+  *h2d_bytes += sc.h2d;
   return MSFM_OK;
 }
 
@@ -581,24 +566,18 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   memset(R->summary, 0, sizeof R->summary);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
   const size_t npx = (size_t)np, nox = (size_t)no;
   // ---- one batch of uploads: the bulk arrays here, the camera tables in the core ----
   DevBuf<int> d_fp, d_op, d_oc, d_of;
   DevBuf<double> d_xyz, d_mse;
   DevBuf<uint8_t> d_bad, d_mut_in, d_added;
   DevBuf<float> d_kp_up;
-  AJ_TRY(up(d_fp, P->feat_point, (size_t)FP));
-  AJ_TRY(up(d_op, P->obs_point, nox)); AJ_TRY(up(d_oc, P->obs_cam, nox)); AJ_TRY(up(d_of, P->obs_feat, nox));
-  AJ_TRY(up(d_xyz, P->point_xyz, 3 * npx)); AJ_TRY(up(d_mse, P->pt_mse, npx));
-  AJ_TRY(up(d_bad, P->pt_bad, npx)); AJ_TRY(up(d_mut_in, P->pt_mutable, npx));
-  if (P->pt_new_added) AJ_TRY(up(d_added, P->pt_new_added, npx));
+  DevScope sc(ctx);
+  AJ_TRY(sc.up(d_fp, P->feat_point, (size_t)FP));
+  AJ_TRY(sc.up(d_op, P->obs_point, nox)); AJ_TRY(sc.up(d_oc, P->obs_cam, nox)); AJ_TRY(sc.up(d_of, P->obs_feat, nox));
+  AJ_TRY(sc.up(d_xyz, P->point_xyz, 3 * npx)); AJ_TRY(sc.up(d_mse, P->pt_mse, npx));
+  AJ_TRY(sc.up(d_bad, P->pt_bad, npx)); AJ_TRY(sc.up(d_mut_in, P->pt_mutable, npx));
+  if (P->pt_new_added) AJ_TRY(sc.up(d_added, P->pt_new_added, npx));
   else { AJ_TRY(d_added.alloc(std::max<size_t>(1, npx))); AJ_TRY(hipMemsetAsync(d_added.p, 0, std::max<size_t>(1, npx), s)); }
   std::vector<float> h_kp;   // (lives to the final wait)
   if (P->keypoints) {   // the rows of the cameras' images only, packed in camera order
@@ -607,14 +586,15 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
       const int im = P->cam_img[c];
       std::copy(P->keypoints + 2 * (size_t)S->feat_off[im], P->keypoints + 2 * ((size_t)S->feat_off[im] + S->n_features[im]), h_kp.begin() + 2 * (size_t)T.kp_base[c]);
     }
-    AJ_TRY(up(d_kp_up, h_kp.data(), h_kp.size()));
+    AJ_TRY(sc.up(d_kp_up, h_kp.data(), h_kp.size()));
   }
   RoundDev D;
   D.feat_point = d_fp.p; D.obs_point = d_op.p; D.obs_cam = d_oc.p; D.obs_feat = d_of.p;
   D.point_xyz = d_xyz.p; D.pt_mse = d_mse.p; D.pt_bad = d_bad.p; D.pt_mutable = d_mut_in.p; D.pt_new_added = d_added.p;
   D.kp = P->keypoints ? d_kp_up.p : S->d_kp.p;
-  MSFM_TRY(round_adjust_dev(ctx, who, A, T, D, opt, &h2d, R.get(), /*fetch_points=*/true));
-  R->h2d_bytes = h2d;
+  MSFM_TRY(round_adjust_dev(ctx, who, A, T, D, opt, &sc.h2d, R.get(), /*fetch_points=*/true));
+  sc.dismiss();   // (the core's finish())
+  R->h2d_bytes = sc.h2d;
   ctx->children++;   // a set is a child of its context, like a store
   *out = R.release();
   return MSFM_OK;

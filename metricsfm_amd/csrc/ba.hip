@@ -2865,11 +2865,15 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   if (ba->env.no_fold || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < ba->env.fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
   hipStream_t s = ctx->stream;
   DevBuf<char> tmp;
+  DevBuf<int> count, offset, head, slot_of, slot_id, slot_id_s, slot_ent_first, wg_slot_first, perm;
+  DevBuf<unsigned long long> key, key_s, slot_key2, slot_key2_s;
+  DevBuf<unsigned> val, ent_sorted;
+  DevBuf<uint8_t> folded;
+  DevScope sc(ctx);
   const int n_wg = ptmap_n_wg(ba->map);
   F.n_wg = n_wg;
   DTRY(F.wg_fold.alloc(n_wg));
   hipLaunchKernelGGL(k_fold_wg, dim3(cdiv(n_wg, 256)), dim3(256), 0, s, ba->map, n_wg, F.wg_fold.p);
-  DevBuf<int> count, offset;
   DTRY(count.alloc((size_t)npb + 1)); DTRY(offset.alloc((size_t)npb + 1));
   DTRY(hipMemsetAsync(count.p, 0, sizeof(int) * ((size_t)npb + 1), s));
   hipLaunchKernelGGL((k_fold_entries<false>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->map, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
@@ -2878,17 +2882,13 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   int E = 0;
   DTRY(hipMemcpyAsync(&E, offset.p + npb, sizeof(int), hipMemcpyDeviceToHost, s));
   DTRY(hipStreamSynchronize(s));
-  if (E <= 0) return MSFM_OK;
-  DevBuf<unsigned long long> key, key_s, slot_key2, slot_key2_s;
-  DevBuf<unsigned> val;
-  DevBuf<int> head, slot_of, slot_id, slot_id_s;
-  DevBuf<unsigned> ent_sorted;
+  if (E <= 0) { sc.dismiss(); return MSFM_OK; }   // (behind the wait above)
   DTRY(key.alloc(E)); DTRY(key_s.alloc(E)); DTRY(val.alloc(E)); DTRY(ent_sorted.alloc(E));
   hipLaunchKernelGGL((k_fold_entries<true>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->map, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
                      (int*)nullptr, offset.p, key.p, val.p);
   {
     size_t bytes = 0;
-    const int bits = 32 + bits_for(std::max(2, n_wg));
+    const int bits = 32 + bits_for((long)std::max(2, n_wg));
     DTRY(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));
     if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));   // stable: point order inside a slot
@@ -2900,32 +2900,30 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   int NS = 0;
   DTRY(hipMemcpyAsync(&NS, slot_of.p + E, sizeof(int), hipMemcpyDeviceToHost, s));
   DTRY(hipStreamSynchronize(s));
-  DevBuf<int> slot_ent_first;
   DTRY(slot_ent_first.alloc((size_t)NS + 1)); DTRY(slot_key2.alloc(NS)); DTRY(slot_key2_s.alloc(NS)); DTRY(slot_id.alloc(NS)); DTRY(slot_id_s.alloc(NS));
   hipLaunchKernelGGL(k_fold_slots, dim3(cdiv(E, 256)), dim3(256), 0, s, E, key_s.p, head.p, slot_of.p, slot_ent_first.p, slot_key2.p, slot_id.p);
   DTRY(hipMemcpyAsync(slot_ent_first.p + NS, &E, sizeof(int), hipMemcpyHostToDevice, s));
-  DevBuf<int> wg_slot_first;
   DTRY(wg_slot_first.alloc((size_t)n_wg + 1));
   hipLaunchKernelGGL(k_fold_wg_first, dim3(cdiv(n_wg + 1, 256)), dim3(256), 0, s, n_wg, NS, slot_key2.p, wg_slot_first.p);
   // the passes and the stream they read
-  DevBuf<int> perm;
   {
     DevBuf<unsigned long long> pk, pk_s;
     DevBuf<int> pid;
+    DevScope blk(ctx);
     DTRY(pk.alloc(NS)); DTRY(pk_s.alloc(NS)); DTRY(pid.alloc(NS)); DTRY(perm.alloc(NS));
     hipLaunchKernelGGL(k_fold_perm_key, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, ncb, slot_key2.p, slot_ent_first.p, wg_slot_first.p, pk.p, pid.p);
     size_t bytes = 0;
-    const int bits = 32 + bits_for(std::max(2, n_wg));
+    const int bits = 32 + bits_for((long)std::max(2, n_wg));
     DTRY(rocprim::radix_sort_pairs(nullptr, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
     if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
-    DTRY(hipStreamSynchronize(s));
+    DTRY(blk.finish());
   }
   {
-    DevBuf<int> wg_npass, wg_words, words_first, slot_ent_pos;
+    DevBuf<int> wg_npass, wg_words, words_first, slot_ent_pos, too_large;
+    DevScope blk(ctx);
     DTRY(wg_npass.alloc((size_t)n_wg + 1)); DTRY(wg_words.alloc((size_t)n_wg + 1)); DTRY(words_first.alloc((size_t)n_wg + 1));
     DTRY(F.wg_pass_first.alloc((size_t)n_wg + 1)); DTRY(slot_ent_pos.alloc(NS));
-    DevBuf<int> too_large;
     DTRY(too_large.alloc(1)); DTRY(hipMemsetAsync(too_large.p, 0, sizeof(int), s));
     DTRY(hipMemsetAsync(wg_npass.p + n_wg, 0, sizeof(int), s)); DTRY(hipMemsetAsync(wg_words.p + n_wg, 0, sizeof(int), s));
     hipLaunchKernelGGL((k_fold_passes<false>), dim3(cdiv(n_wg, 256)), dim3(256), 0, s, n_wg, ncb, wg_slot_first.p, slot_ent_first.p, slot_key2.p, perm.p, wg_npass.p, wg_words.p,
@@ -2937,14 +2935,17 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DTRY(hipMemcpyAsync(&npass, F.wg_pass_first.p + n_wg, sizeof(int), hipMemcpyDeviceToHost, s));
     DTRY(hipMemcpyAsync(&nwords, words_first.p + n_wg, sizeof(int), hipMemcpyDeviceToHost, s));
     DTRY(hipStreamSynchronize(s));
-    if (h_too_large || npass < 0 || nwords < 0) return MSFM_OK;   // (k_fold_passes: a slot too large to stage; nothing has been marked yet)
+    if (h_too_large || npass < 0 || nwords < 0) {   // (k_fold_passes: a slot too large to stage; nothing has been marked yet)
+      blk.dismiss(); sc.dismiss();   // (behind the wait above)
+      return MSFM_OK;
+    }
     DTRY(F.pass.alloc((size_t)std::max(1, npass))); DTRY(F.stream.alloc((size_t)nwords + FOLD_WORDS));
     DTRY(hipMemsetAsync(F.stream.p, 0, sizeof(unsigned) * ((size_t)nwords + FOLD_WORDS), s));
     hipLaunchKernelGGL((k_fold_passes<true>), dim3(cdiv(n_wg, 256)), dim3(256), 0, s, n_wg, ncb, wg_slot_first.p, slot_ent_first.p, slot_key2.p, perm.p, (int*)nullptr, (int*)nullptr,
                        F.wg_pass_first.p, words_first.p, F.pass.p, F.stream.p, slot_ent_pos.p, (int*)nullptr);
     hipLaunchKernelGGL(k_fold_stream_entries, dim3(cdiv(E, 256)), dim3(256), 0, s, E, head.p, slot_of.p, slot_ent_first.p, slot_ent_pos.p, ent_sorted.p, F.stream.p);
     F.n_pass = npass;
-    DTRY(hipStreamSynchronize(s));
+    DTRY(blk.finish());
   }
   {
     size_t bytes = 0;
@@ -2954,16 +2955,16 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   }
   {
     DevBuf<int> rank;   // by slot; k_point asks by position inside the workgroup's passes
+    DevScope blk(ctx);
     DTRY(rank.alloc(NS)); DTRY(F.slot_rank.alloc(NS));
     hipLaunchKernelGGL(k_fold_rank, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, slot_id_s.p, rank.p);
     hipLaunchKernelGGL(k_fold_gather_rank, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, perm.p, rank.p, F.slot_rank.p);
-    DTRY(hipStreamSynchronize(s));
+    DTRY(blk.finish());
   }
   DTRY(F.blk_range.alloc(2 * (size_t)std::max(1, ba->cc.n_blocks)));
   hipLaunchKernelGGL(k_fold_blk_range, dim3(cdiv(std::max(1, ba->cc.n_blocks), 256)), dim3(256), 0, s, ba->cc.n_blocks, NS, ncb, ba->cc.blk_row.p, ba->cc.blk_col.p,
                      slot_key2_s.p, F.blk_range.p);
   // the same entries leave the gather path
-  DevBuf<uint8_t> folded;
   DTRY(folded.alloc((size_t)std::max(1, ba->NCR)));
   DTRY(hipMemsetAsync(folded.p, 0, (size_t)std::max(1, ba->NCR), s));
   hipLaunchKernelGGL(k_fold_mark_cpos, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ba->map, ba->pt_first.p, ba->o_cpos.p, F.wg_fold.p, folded.p);
@@ -2972,6 +2973,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   // chunks that keep a live entry: the gather kernel visits only those, the partials of the others are zero for good
   auto live_chunks = [&](PairJobs& J, int width, int& n_live, DevBuf<int>& live, DevBuf<uint8_t>* blk_live) -> int {
     DevBuf<int> lf, lpos;
+    DevScope blk(ctx);
     const int nch = J.n_chunks;
     DTRY(lf.alloc((size_t)nch + 1)); DTRY(lpos.alloc((size_t)nch + 1));
     DTRY(hipMemsetAsync(lf.p + nch, 0, sizeof(int), s));
@@ -2986,7 +2988,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
       hipLaunchKernelGGL(k_fold_blk_live, dim3(cdiv(std::max(1, J.n_blocks), 256)), dim3(256), 0, s, J.n_blocks, J.blk_chunk_first.p, lf.p, blk_live->p);
     }
     DTRY(hipMemsetAsync(J.partial.p, 0, sizeof(double) * width * (size_t)std::max(1, nch), s));
-    DTRY(hipStreamSynchronize(s));
+    DTRY(blk.finish());
     return MSFM_OK;
   };
   MSFM_TRY(live_chunks(ba->cc, 36, F.n_live, F.live_chunk, &F.blk_live));
@@ -2998,16 +3000,16 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     hipLaunchKernelGGL(k_fold_mc_range, dim3(cdiv(ba->mc.n_blocks, 256)), dim3(256), 0, s, ba->mc.n_blocks, NS, ba->mc.blk_col.p, slot_key2_s.p, F.mc_range.p);
     // (diagonal keys are the ncb smallest: their slots have the ranks 0 .. n_diag - 1)
     {
-      DevBuf<int> one;
+      DevBuf<int> one, colbuf;
+      DevScope blk(ctx);
       DTRY(one.alloc(2));
       int col = ncb;   // k_fold_mc_range on a single pseudo block with column ncb gives lower_bound(ncb << 32) in range[0]
-      DevBuf<int> colbuf;
       DTRY(colbuf.alloc(1));
       DTRY(hipMemcpyAsync(colbuf.p, &col, sizeof(int), hipMemcpyHostToDevice, s));
       hipLaunchKernelGGL(k_fold_mc_range, dim3(1), dim3(256), 0, s, 1, NS, colbuf.p, slot_key2_s.p, one.p);
       int h[2] = {0, 0};
       DTRY(hipMemcpyAsync(h, one.p, sizeof(h), hipMemcpyDeviceToHost, s));
-      DTRY(hipStreamSynchronize(s));
+      DTRY(blk.finish());
       F.n_diag = h[0];
     }
     if (F.n_diag > 0) {
@@ -3018,12 +3020,13 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
       {
         // (how many entries left the gather list: reported by msfm_ba_get_layout)
         DevBuf<int> cnt;
+        DevScope blk(ctx);
         DTRY(cnt.alloc(1));
         DTRY(hipMemsetAsync(cnt.p, 0, sizeof(int), s));
         hipLaunchKernelGGL(k_fold_count_marked, dim3(std::min(1024, cdiv(ba->mc.n_pairs, 256))), dim3(256), 0, s, ba->mc.n_pairs, ba->mc.pa.p, cnt.p);
         int h = 0;
         DTRY(hipMemcpyAsync(&h, cnt.p, sizeof(int), hipMemcpyDeviceToHost, s));
-        DTRY(hipStreamSynchronize(s));
+        DTRY(blk.finish());
         F.mc_entries_folded = h;
       }
       F.mc_on = true;
@@ -3031,7 +3034,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     }
   }
   DTRY(hipGetLastError());
-  DTRY(hipStreamSynchronize(s));   // the temporaries above go back to the pool
+  DTRY(sc.finish());   // the temporaries above go back to the pool
   F.n_slots = NS; F.n_entries = E;
   F.on = true;
   F.all = E == ba->cc.n_pairs;
@@ -3052,10 +3055,13 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   };
   const int Nc = ba->Nc = P->n_cams, Nm = ba->Nm = P->n_models, Np = ba->Np = P->n_points, No = P->n_obs;
   DevBuf<char> tmp;
-  // ---- the caller's arrays (the only bulk PCIe traffic of the set-up) ----
-  DevBuf<int> d_obs_cam, d_obs_pt, d_model_of_cam;
+  DevBuf<int> d_obs_cam, d_obs_pt, d_model_of_cam, d_cnt, d_run_first, d_err, d_cam_slot, d_model_slot, d_fflag, d_fpos, d_cam_hist, d_cam_first, d_pm_count;
+  DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len, d_cls, d_cls_sorted, d_n_class;
   DevBuf<double> d_obs_xy, d_ptw;
-  DevBuf<uint8_t> d_cam_mut, d_model_mut, d_pt_mut;
+  DevBuf<uint8_t> d_cam_mut, d_model_mut, d_pt_mut, d_cu, d_mu, d_pu;
+  DevBuf<unsigned long long> d_keys, d_keys_sorted;
+  DevScope sc(ctx);
+  // ---- the caller's arrays (the only bulk PCIe traffic of the set-up) ----
   DTRY(d_obs_cam.alloc((size_t)std::max(1, No))); DTRY(d_obs_pt.alloc((size_t)std::max(1, No))); DTRY(d_obs_xy.alloc(2 * (size_t)std::max(1, No)));
   DTRY(d_model_of_cam.alloc(Nc));
   if (No) {
@@ -3068,8 +3074,6 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   if (P->model_mutable) { DTRY(d_model_mut.alloc(Nm)); DTRY(d_model_mut.upload(P->model_mutable, Nm, s)); }
   if (P->pt_mutable && Np) { DTRY(d_pt_mut.alloc(Np)); DTRY(bulk(d_pt_mut.p, P->pt_mutable, (size_t)Np)); }
   // ---- validation, block usage, observations per point ----
-  DevBuf<uint8_t> d_cu, d_mu, d_pu;
-  DevBuf<int> d_cnt, d_run_first, d_err;
   DTRY(d_cu.alloc(Nc)); DTRY(d_mu.alloc(Nm)); DTRY(d_pu.alloc((size_t)std::max(1, Np)));
   DTRY(d_cnt.alloc((size_t)Np + 1)); DTRY(d_run_first.alloc((size_t)Np + 1)); DTRY(d_err.alloc(4));
   DTRY(hipMemsetAsync(d_cu.p, 0, Nc, s)); DTRY(hipMemsetAsync(d_mu.p, 0, Nm, s)); DTRY(hipMemsetAsync(d_pu.p, 0, (size_t)std::max(1, Np), s));
@@ -3101,6 +3105,8 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   if (ng >= 128 && ng <= 4096 && force != 0) {
     DevBuf<int> d_gnode;
     DevBuf<uint8_t> d_adj;
+    DevBuf<double> dadj;
+    DevScope blk(ctx);
     DTRY(d_gnode.from(gnode, s));
     DTRY(d_adj.alloc((size_t)ng * ng));
     DTRY(hipMemsetAsync(d_adj.p, 0, (size_t)ng * ng, s));
@@ -3111,7 +3117,6 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     if (ctx->world > 1) {   // the graph must be the same on every rank: max-reduce over the ranks' shards
       std::vector<double> adjm(adjb.size());
       for (size_t k = 0; k < adjm.size(); k++) adjm[k] = adjb[k] ? 1.0 : 0.0;
-      DevBuf<double> dadj;
       DTRY(dadj.from(adjm, s));
       DTRY(hipStreamSynchronize(s));
       const int rc = ctx->allreduce(ctx->allreduce_user, dadj.p, adjm.size(), MSFM_REDUCE_MAX, (void*)s);
@@ -3120,6 +3125,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
       MSFM_TRY(msfm_stream_wait_bounded(ctx, s, "the all-reduce of the camera graph"));   // (bounded: a peer that failed never joins)
       for (size_t k = 0; k < adjm.size(); k++) adjb[k] = adjm[k] != 0.0;
     }
+    blk.dismiss();   // (behind the wait for the graph, or the bounded one)
   }
   std::vector<int> cb_off_h, padcol_h;
   order_camera_blocks(ctx, ba, gcam, adjb, force, cam_slot, cb_off_h, padcol_h);
@@ -3134,7 +3140,6 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   ba->gps_weight = P->gps_weight;
   DTRY(ba->cb_off.from(cb_off_h.empty() ? std::vector<int>(1, 0) : cb_off_h, s));
   DTRY(ba->padcol.from(padcol_h.empty() ? std::vector<int>(1, 0) : padcol_h, s));
-  DevBuf<int> d_cam_slot, d_model_slot;
   DTRY(d_cam_slot.from(cam_slot, s)); DTRY(d_model_slot.from(model_slot, s));
   // cameras of each intrinsics block (host, O(cameras))
   std::vector<int> cb_mb(std::max(1, ncb), -1), mcam_first(nmb + 1, 0), mcam;
@@ -3161,9 +3166,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   lap("camera order");
   // ---- order of the eliminated points: by length class (PtMap), then by their smallest camera blocks, ties by the caller's
   // index (two stable sorts, the minor key first) ----
-  DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len, d_cls, d_cls_sorted, d_n_class;
   int n_class[PTMAP_CLASSES] = {0, 0, 0, 0};
-  DevBuf<unsigned long long> d_keys, d_keys_sorted;
   DTRY(d_pu_int.alloc((size_t)Np + 1)); DTRY(d_pu_pos.alloc((size_t)Np + 1));
   DTRY(hipMemsetAsync(d_pu_int.p + Np, 0, sizeof(int), s));
   if (Np) hipLaunchKernelGGL(k_u8_to_int, dim3(cdiv(Np, 256)), dim3(256), 0, s, Np, d_pu.p, d_pu_int.p);
@@ -3189,7 +3192,6 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   if (npb) hipLaunchKernelGGL(k_point_lengths, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ba->pb_pt.p, d_cnt.p, d_len.p, d_pt_slot.p);
   DTRY(excl_scan(d_len.p, ba->pt_first.p, (size_t)npb + 1, s, tmp));
   // frozen points seen by free cameras: flags and their ranks
-  DevBuf<int> d_fflag, d_fpos;
   int n_frozen_rows = 0;
   if (P->pt_mutable && No) {
     DTRY(d_fflag.alloc((size_t)No + 1)); DTRY(d_fpos.alloc((size_t)No + 1));
@@ -3211,7 +3213,6 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   const size_t As = (size_t)std::max(1, A);
   DTRY(ba->o_cam.alloc(As)); DTRY(ba->o_model.alloc(As)); DTRY(ba->o_pt.alloc(As)); DTRY(ba->o_cb.alloc(As)); DTRY(ba->o_mb.alloc(As));
   DTRY(ba->o_pb.alloc(As)); DTRY(ba->o_cpos.alloc(As)); DTRY(ba->o_pm.alloc(As)); DTRY(ba->o_x.alloc(As)); DTRY(ba->o_y.alloc(As)); DTRY(ba->o_w.alloc(As));
-  DevBuf<int> d_cam_hist, d_cam_first;
   DTRY(d_cam_hist.alloc((size_t)ncb + 1)); DTRY(d_cam_first.alloc((size_t)ncb + 1));
   DTRY(hipMemsetAsync(d_cam_hist.p, 0, sizeof(int) * ((size_t)ncb + 1), s));
   RowOut R{ba->o_cam.p, ba->o_model.p, ba->o_pt.p, ba->o_cb.p, ba->o_mb.p, ba->o_pb.p, ba->o_x.p, ba->o_y.p, ba->o_w.p};
@@ -3231,15 +3232,15 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   hipLaunchKernelGGL(k_fill_int, dim3(cdiv(std::max(1, NCR), 256)), dim3(256), 0, s, std::max(1, NCR), -1, ba->cpos_pb.p);
   if (A && NCR) {
     DevBuf<int> rk, rv, rks, rvs;
+    DevScope blk(ctx);
     DTRY(rk.alloc(A)); DTRY(rv.alloc(A)); DTRY(rks.alloc(A)); DTRY(rvs.alloc(A));
     hipLaunchKernelGGL(k_row_keys, dim3(cdiv(A, 256)), dim3(256), 0, s, A, ncb, ba->o_cb.p, rk.p, rv.p);
     DTRY(sort_pairs(rk.p, rks.p, rv.p, rvs.p, (size_t)A, bits_for((long)ncb + 1), s, tmp));
     hipLaunchKernelGGL(k_assign_positions, dim3(cdiv(NCR, 256)), dim3(256), 0, s, NCR, rks.p, rvs.p, ba->o_pb.p, ba->o_cpos.p, ba->cpos_pb.p);
-    DTRY(hipStreamSynchronize(s));   // the sort buffers go out of scope
+    DTRY(blk.finish());   // the sort buffers go out of scope
   }
   lap("rows + camera positions");
   // ---- (point, intrinsics block) entries ----
-  DevBuf<int> d_pm_count;
   DTRY(d_pm_count.alloc((size_t)npb + 1)); DTRY(ba->pm_first.alloc((size_t)npb + 1));
   DTRY(hipMemsetAsync(d_pm_count.p, 0, sizeof(int) * ((size_t)npb + 1), s));
   DTRY(hipMemsetAsync(d_err.p, 0x7f, sizeof(int) * 4, s));
@@ -3275,15 +3276,17 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     PairBuild<0> b0(ctx, ba, ba->cc, 36, ba->pt_first.p, ba->pm_first.p, ba->pm_mb.p, tmp, want_blocks);
     PairBuild<1> b1(ctx, ba, ba->mc, 18, ba->pt_first.p, ba->pm_first.p, ba->pm_mb.p, tmp, false);
     PairBuild<2> b2(ctx, ba, ba->mm, 12, ba->pt_first.p, ba->pm_first.p, ba->pm_mb.p, tmp, false);
+    DevScope blk(ctx);
     MSFM_TRY(b0.phase1()); MSFM_TRY(b1.phase1()); MSFM_TRY(b2.phase1());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     MSFM_TRY(b0.phase2()); MSFM_TRY(b1.phase2()); MSFM_TRY(b2.phase2());
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     MSFM_TRY(b0.phase3()); MSFM_TRY(b1.phase3()); MSFM_TRY(b2.phase3());
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host copies of the counts and the temporaries go out of scope
+    HIP_TRY(ctx, blk.finish());   // the host copies of the counts and the temporaries go out of scope
   }
   lap("pairs cc");
   lap("pairs mc mm");
+  sc.dismiss();   // (behind the wait of the pair lists)
   return MSFM_OK;
 }
 #undef DTRY
@@ -3362,12 +3365,14 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
         std::vector<double> adjm((size_t)ng * ng);
         for (size_t k = 0; k < adjm.size(); k++) adjm[k] = adjb[k] ? 1.0 : 0.0;
         DevBuf<double> dadj;
+        DevScope blk(ctx);
         HIP_TRY(ctx, dadj.from(adjm, s));
         HIP_TRY(ctx, hipStreamSynchronize(s));
         const int rc = ctx->allreduce(ctx->allreduce_user, dadj.p, adjm.size(), MSFM_REDUCE_MAX, (void*)s);
         if (rc != 0) return msfm_set_error(ctx, MSFM_E_DEVICE, "all-reduce hook failed: %d", rc);
         HIP_TRY(ctx, hipMemcpyAsync(adjm.data(), dadj.p, sizeof(double) * adjm.size(), hipMemcpyDeviceToHost, s));
         MSFM_TRY(msfm_stream_wait_bounded(ctx, s, "the all-reduce of the camera graph"));
+        blk.dismiss();
         for (size_t k = 0; k < adjm.size(); k++) adjb[k] = adjm[k] != 0.0;
       }
       adjb8.assign(adjb.begin(), adjb.end());
@@ -3737,6 +3742,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
     std::vector<double> ind((size_t)ncb * ncb, 0.0);
     for (int b = 0; b < ba->cc.n_blocks; b++) ind[(size_t)ba->cc.h_row[b] * ncb + ba->cc.h_col[b]] = 1.0;
     DevBuf<double> dind;
+    DevScope blk(ctx);
     HIP_TRY(ctx, dind.from(ind, s));
     HIP_TRY(ctx, hipStreamSynchronize(s));
     {
@@ -3753,7 +3759,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
     HIP_TRY(ctx, ba->u_row.from(ur, s));
     HIP_TRY(ctx, ba->u_col.from(uc, s));
     HIP_TRY(ctx, ba->pack.alloc((size_t)std::max(1, ba->n_ublk) * 36 + (size_t)(ba->nsys - ba->mo + 1) * ba->npad));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
+    HIP_TRY(ctx, blk.finish());
   }
   const size_t As = std::max(1, A);
 #define AL(buf, n) HIP_TRY(ctx, ba->buf.alloc((size_t)std::max<size_t>(1, (n))))
@@ -3805,6 +3811,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   {
     // camera-major statics of the rows and the camera of every k_ftf chunk
     DevBuf<int> cm_row;
+    DevScope blk(ctx);
     HIP_TRY(ctx, cm_row.alloc((size_t)std::max(1, NCR)));
     HIP_TRY(ctx, hipMemsetAsync(ba->cm_pt.p, 0, sizeof(int) * (size_t)std::max(1, NCR), s));
     HIP_TRY(ctx, hipMemsetAsync(ba->cm_xyw.p, 0, sizeof(double) * 3 * (size_t)std::max(1, NCR), s));
@@ -3816,7 +3823,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
     if (ba->n_fchunks)
       hipLaunchKernelGGL(k_chunk_cam, dim3(cdiv(ba->n_fchunks, 256)), dim3(256), 0, s, ba->n_fchunks, ba->f_start.p, cm_row.p, ba->o_cam.p, ba->o_model.p,
                          ba->o_cb.p, ba->o_mb.p, ba->chunk_cam.p);
-    HIP_TRY(ctx, hipStreamSynchronize(s));   // (cm_row goes back to the pool)
+    HIP_TRY(ctx, blk.finish());   // (cm_row goes back to the pool)
   }
   HIP_TRY(ctx, hipMemsetAsync(ba->T.p, 0, sizeof(double) * std::max<size_t>(1, 18 * (size_t)NCR), s));
   HIP_TRY(ctx, hipMemsetAsync(ba->Tu.p, 0, sizeof(double) * std::max<size_t>(1, 6 * (size_t)NCR), s));

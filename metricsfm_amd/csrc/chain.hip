@@ -209,6 +209,7 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
   C->feat_off.assign(v.n_images + 1, 0);
   for (int i = 0; i < v.n_images; i++) C->feat_off[i + 1] = C->feat_off[i] + v.count[i];
   hipStream_t s = ctx->stream;
+  DevScope sc(ctx);   // (an error return deletes the chain)
   C->kp.assign(v.n_images, nullptr);
   CH_TRY(C->kp_own.alloc(2 * (size_t)std::max(1, C->feat_off[v.n_images])));
   for (int i = 0; i < v.n_images; i++) {
@@ -227,6 +228,7 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
   C->n_good = ng; C->n_all = na;   // sizes of matches_good / matches_all per pair: msfm_chain_verify gathers them
   ctx->children++;
   *out = C.release();
+  sc.dismiss();   // the chain keeps its block (with pairs: behind the wait above)
   return MSFM_OK;
 }
 
@@ -256,6 +258,7 @@ MSFM_API int msfm_chain_verify(msfm_chain* C, msfm_match_result* res, const msfm
   DevBuf<float> g1, g2, a1, a2;
   DevBuf<double> dF;
   DevBuf<uint8_t> in_g, in_a, d_ok;
+  DevScope sc(ctx);
   CH_TRY(d_src.from(src, s)); CH_TRY(d_offg.from(off_g, s)); CH_TRY(d_offa.from(off_a, s));
   CH_TRY(m_good.alloc(2 * (size_t)std::max(1, tg))); CH_TRY(g1.alloc(2 * (size_t)std::max(1, tg))); CH_TRY(g2.alloc(2 * (size_t)std::max(1, tg)));
   CH_TRY(m_all.alloc(2 * (size_t)std::max(1, ta))); CH_TRY(a1.alloc(2 * (size_t)std::max(1, ta))); CH_TRY(a2.alloc(2 * (size_t)std::max(1, ta)));
@@ -296,7 +299,7 @@ MSFM_API int msfm_chain_verify(msfm_chain* C, msfm_match_result* res, const msfm
     hipLaunchKernelGGL(chn::k_compact_matches, dim3(np), dim3(256), 0, s, d_offa.p, C->d_moff.p, in_a.p, m_all.p, C->d_match.p);
   }
   CH_TRY(hipGetLastError());
-  CH_TRY(hipStreamSynchronize(s));   // the scratch above goes back to the pool
+  CH_TRY(sc.finish());   // the scratch above goes back to the pool
   C->verified = true;
   return MSFM_OK;
 }
@@ -372,10 +375,9 @@ MSFM_API int msfm_chain_triangulate(msfm_chain* C, int n_cams, const double* cam
   const msfm_track_dev& T = C->tracks;
   const int nt = T.n_tracks, no = T.n_obs;
   DevBuf<double> dR, dt, dc, dfk;
-  CH_TRY(dR.alloc(9 * (size_t)n_cams)); CH_TRY(dR.upload(cam_R, 9 * (size_t)n_cams, s));
-  CH_TRY(dt.alloc(3 * (size_t)n_cams)); CH_TRY(dt.upload(cam_t, 3 * (size_t)n_cams, s));
-  CH_TRY(dc.alloc(3 * (size_t)n_cams)); CH_TRY(dc.upload(cam_c, 3 * (size_t)n_cams, s));
-  CH_TRY(dfk.alloc(3 * (size_t)n_cams)); CH_TRY(dfk.upload(cam_fk, 3 * (size_t)n_cams, s));
+  DevScope sc(ctx);
+  CH_TRY(sc.up(dR, cam_R, 9 * (size_t)n_cams)); CH_TRY(sc.up(dt, cam_t, 3 * (size_t)n_cams));
+  CH_TRY(sc.up(dc, cam_c, 3 * (size_t)n_cams)); CH_TRY(sc.up(dfk, cam_fk, 3 * (size_t)n_cams));
   CH_TRY(C->d_kp.from(C->kp, s));
   CH_TRY(C->xy.alloc(2 * (size_t)std::max(1, no)));
   CH_TRY(C->X.alloc(3 * (size_t)std::max(1, nt))); CH_TRY(C->mse.alloc(std::max(1, nt))); CH_TRY(C->tok.alloc(std::max(1, nt)));
@@ -387,12 +389,12 @@ MSFM_API int msfm_chain_triangulate(msfm_chain* C, int n_cams, const double* cam
   if (n_accepted) {
     std::vector<uint8_t> okh(std::max(1, nt));
     if (nt) CH_TRY(hipMemcpyAsync(okh.data(), C->tok.p, nt, hipMemcpyDeviceToHost, s));
-    CH_TRY(hipStreamSynchronize(s));
+    CH_TRY(sc.finish());
     int n = 0;
     for (int t = 0; t < nt; t++) n += okh[t] != 0;
     *n_accepted = n;
   } else {
-    CH_TRY(hipStreamSynchronize(s));   // the camera arrays above are released on return
+    CH_TRY(sc.finish());   // the camera arrays above are released on return
   }
   C->triangulated = true;
   return MSFM_OK;
@@ -425,8 +427,10 @@ MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, doubl
   hipStream_t s = ctx->stream;
   const msfm_track_dev& T = C->tracks;
   const int nt = T.n_tracks;
-  DevBuf<int> keep, keep_obs, new_pt, new_obs;
+  DevBuf<int> keep, keep_obs, new_pt, new_obs, obs_cam, obs_pt;
+  DevBuf<double> obs_xy, point, ptw;
   DevBuf<char> tmp;
+  DevScope sc(ctx);
   CH_TRY(keep.alloc((size_t)nt + 1)); CH_TRY(keep_obs.alloc((size_t)nt + 1)); CH_TRY(new_pt.alloc((size_t)nt + 1)); CH_TRY(new_obs.alloc((size_t)nt + 1));
   hipLaunchKernelGGL(chn::k_keep, dim3(cdiv(nt + 1, 256)), dim3(256), 0, s, nt, T.off.p, C->tok.p, min_views, keep.p, keep_obs.p);
   auto scan = [&](const int* in, int* o, size_t n) -> hipError_t {
@@ -443,8 +447,6 @@ MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, doubl
   CH_TRY(hipMemcpyAsync(&no, new_obs.p + nt, sizeof(int), hipMemcpyDeviceToHost, s));
   CH_TRY(hipStreamSynchronize(s));
   if (np == 0) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_ba_create: no track qualifies (%d tracks)", nt);
-  DevBuf<int> obs_cam, obs_pt;
-  DevBuf<double> obs_xy, point, ptw;
   CH_TRY(obs_cam.alloc(no)); CH_TRY(obs_pt.alloc(no)); CH_TRY(obs_xy.alloc(2 * (size_t)no)); CH_TRY(point.alloc(3 * (size_t)np)); CH_TRY(ptw.alloc(np));
   CH_TRY(C->track_of_point.alloc(np));
   hipLaunchKernelGGL(chn::k_ba_arrays, dim3(cdiv(nt, 256)), dim3(256), 0, s, nt, T.off.p, T.img.p, C->xy.p, C->X.p, keep.p, new_pt.p, new_obs.p, weight_ge3,
@@ -456,7 +458,7 @@ MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, doubl
   P.cam_pose = cam_pose; P.cam_model = cam_model; P.cam_model_of_cam = cam_model_of_cam;
   P.point = point.p; P.obs_cam = obs_cam.p; P.obs_pt = obs_pt.p; P.obs_xy = obs_xy.p; P.pt_weight = ptw.p;
   MSFM_TRY(ba_create_impl(ctx, &P, /*bulk_on_device=*/true, out));
-  CH_TRY(hipStreamSynchronize(s));
+  CH_TRY(sc.finish());
   C->n_ba_points = np; C->n_ba_obs = no;
   if (n_points) *n_points = np;
   if (n_observations) *n_observations = no;

@@ -171,6 +171,47 @@ struct DevBuf {
   }
 };
 
+// The device scratch of one call: what a function enqueues on ctx->stream while it owns local blocks happens inside a DevScope.
+// Its destructor waits for the stream unless the scope has been settled, so a return at any point - HIP_TRY, MSFM_TRY - gives no
+// block back to the cache that the stream still uses (the cache hands a freed block to the next context at once).
+// A destructor runs before those of the objects declared earlier: declare the scope AFTER every DevBuf, and every scratch struct
+// that holds DevBufs, of the function.  (DevBuf's constructor does nothing: a block that is allocated late is declared early.)
+// Blocks that move into a result object by swap after finish() are not the scope's business any more.
+struct DevScope {
+  hipStream_t s;
+  int64_t h2d = 0;        // bytes the up() calls have moved
+  bool settled = false;
+  explicit DevScope(msfm_ctx* ctx) : s(ctx->stream) {}
+  DevScope(const DevScope&) = delete;
+  DevScope& operator=(const DevScope&) = delete;
+  ~DevScope() { if (!settled) (void)hipStreamSynchronize(s); }
+  // a block of max(1, count, capacity) elements, and count elements of h into it
+  template <typename T, typename U>
+  hipError_t up(DevBuf<T>& buf, const U* h, size_t count, size_t capacity = 0) {
+    const hipError_t e = buf.alloc(std::max<size_t>(1, std::max(count, capacity)));
+    if (e != hipSuccess) return e;
+    h2d += (int64_t)(count * sizeof(U));
+    return buf.upload(h, count, s);
+  }
+  template <typename T, typename U>
+  hipError_t up(DevBuf<T>& buf, const std::vector<U>& v) { return up(buf, v.data(), v.size()); }
+  template <typename T>
+  hipError_t down(T* h, const T* d, size_t count) {   // (a null h: the caller does not want the array)
+    if (!h || !count) return hipSuccess;
+    return hipMemcpyAsync(h, d, count * sizeof(T), hipMemcpyDeviceToHost, s);
+  }
+  hipError_t finish() { settled = true; return hipStreamSynchronize(s); }   // the call's last wait; its error is the caller's to report
+  // only directly behind a wait the code can point to (a callee's finish(), msfm_ba_download_params), or where every block
+  // has gone to a result object that the caller gets
+  void dismiss() { settled = true; }
+};
+
+static inline int bits_for(unsigned v) {   // bits that hold every value 0 .. v
+  int b = 1;
+  while (b < 32 && (v >> b)) b++;
+  return b;
+}
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // The sum of an int over the 64 lanes of a wave (butterfly 32 .. 1), in every lane.
@@ -434,7 +475,7 @@ struct msfm_new_points_options;
 int newpoints_plan(msfm_ctx* ctx, const char* who, const msfm_match_store* S, const NewPointsArgs& P, const msfm_new_points_options& opt,
                    bool fp_resident, int kp_mode, NewPointsPlan* L, msfm_new_points_set* R);
 int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs& P, const NewPointsPlan& L, const msfm_new_points_options& opt,
-                  const int* d_fp, const float* d_kp, int64_t* h2d_bytes, NewPointsDev* W);
+                  const int* d_fp, const float* d_kp, DevScope& sc, NewPointsDev* W);
 void newpoints_collect(const NewPointsArgs& P, const NewPointsPlan& L, const NewPointsDev& W, const char* hb, msfm_new_points_set* R);
 int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_off, const int* d_nf, const int* d_fo, int n_pairs,
                      const int* d_pair, const int* d_moff, const int* d_match, int M, msfm_track_dev* out);

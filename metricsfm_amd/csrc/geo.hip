@@ -787,7 +787,7 @@ static void ransac_iter_tables(double confidence, int H, int n_pairs, const int*
 }
 
 struct RansacRun { int H; double confidence, th2; uint64_t seed; int min_inliers; };
-// The device buffers of one run.  The driver only enqueues: its caller keeps these until it has synchronised the stream.
+// The device buffers of one run.  The driver only enqueues: its caller declares these in front of its scope.
 template <class E>
 struct RansacWork {
   DevBuf<int> tab_off, tab, slot_pair, need, budget, counts1, counts2, need_pair;
@@ -870,27 +870,24 @@ static int ransac_batch_io(msfm_ctx* ctx, int n_pairs, const int* offsets, const
                            int* n_inliers, uint8_t* ok, Run&& run) {
   const int total = offsets[n_pairs];
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   DevBuf<int> d_off, d_nin;
   DevBuf<float> d1, d2;
   DevBuf<double> dM;
   DevBuf<uint8_t> d_in, d_ok;
-  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d2.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
+  DevScope sc(ctx);
+  HIP_TRY(ctx, sc.up(d_off, offsets, (size_t)n_pairs + 1));
+  HIP_TRY(ctx, sc.up(d1, pt1, 2 * (size_t)total));
+  HIP_TRY(ctx, sc.up(d2, pt2, 2 * (size_t)total));
   HIP_TRY(ctx, dM.alloc((size_t)n_pairs * 9));
   HIP_TRY(ctx, d_in.alloc((size_t)std::max(1, total)));
   HIP_TRY(ctx, d_nin.alloc(n_pairs));
   HIP_TRY(ctx, d_ok.alloc(n_pairs));
   MSFM_TRY(run(d_off.p, d1.p, d2.p, dM.p, d_in.p, d_nin.p, d_ok.p));
-  HIP_TRY(ctx, hipMemcpyAsync(M, dM.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(n_inliers, d_nin.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(M, dM.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(inlier, d_in.p, (size_t)total));
+  HIP_TRY(ctx, sc.down(n_inliers, d_nin.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(ok, d_ok.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -922,11 +919,12 @@ int geo_fransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d
   HIP_TRY(ctx, hipMemsetAsync(d_nin, 0, sizeof(int) * (size_t)n_pairs, s));
   HIP_TRY(ctx, hipMemsetAsync(d_ok, 0, (size_t)n_pairs, s));
   RansacWork<FEstimator> w;
+  DevScope sc(ctx);
   if (!slot_pair.empty())
     MSFM_TRY(ransac_two_pass<FEstimator>(ctx, {opt->max_iterations, opt->confidence, opt->threshold * opt->threshold, opt->seed, opt->min_inliers},
                                          n_pairs, offsets, d_off, reinterpret_cast<const float2*>(d1), reinterpret_cast<const float2*>(d2),
                                          slot_pair, w, dF, d_in, d_nin, d_ok));
-  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the buffers of the run are released on return)
+  HIP_TRY(ctx, sc.finish());   // (the buffers of the run are released on return)
   return MSFM_OK;
 }
 
@@ -973,20 +971,20 @@ MSFM_API int msfm_epipolar_filter_batch(msfm_ctx* ctx, int n_pairs, const int* o
   DevBuf<float> d1, d2;
   DevBuf<double> dF;
   DevBuf<uint8_t> d_in, d_ok;
-  HIP_TRY(ctx, d_po.from(pair_of, s));
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)total)); HIP_TRY(ctx, d2.alloc(2 * (size_t)total));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)total, s)); HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)total, s));
-  HIP_TRY(ctx, dF.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, dF.upload(F, 9 * (size_t)n_pairs, s));
+  DevScope sc(ctx);
+  HIP_TRY(ctx, sc.up(d_po, pair_of));
+  HIP_TRY(ctx, sc.up(d1, pt1, 2 * (size_t)total)); HIP_TRY(ctx, sc.up(d2, pt2, 2 * (size_t)total));
+  HIP_TRY(ctx, sc.up(dF, F, 9 * (size_t)n_pairs));
   HIP_TRY(ctx, d_in.alloc(total));
-  if (ok) { HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_ok.upload(ok, n_pairs, s)); }
+  if (ok) HIP_TRY(ctx, sc.up(d_ok, ok, (size_t)n_pairs));
   {
     KTimer t(ctx, "geo_epipolar_filter");
     hipLaunchKernelGGL(k_epipolar_batch, dim3(cdiv(total, 256)), dim3(256), 0, s, total, d_po.p, reinterpret_cast<const float2*>(d1.p),
                        reinterpret_cast<const float2*>(d2.p), dF.p, ok ? d_ok.p : nullptr, th, d_in.p);
   }
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(inlier, d_in.p, (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(inlier, d_in.p, (size_t)total));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -1200,17 +1198,15 @@ int geo_hransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d
   for (int p = 0; p < n_pairs; p++)
     if (offsets[p + 1] - offsets[p] > 4 && (!active || active[p])) slot_pair.push_back(p);
   DevBuf<uint8_t> d_active;
-  if (active) {
-    HIP_TRY(ctx, d_active.alloc(n_pairs));
-    HIP_TRY(ctx, d_active.upload(active, n_pairs, s));
-  }
+  RansacWork<HEstimator> w;
+  DevScope sc(ctx);
+  if (active) HIP_TRY(ctx, sc.up(d_active, active, (size_t)n_pairs));
   {
     KTimer t(ctx, "geo_hransac_small");
     hipLaunchKernelGGL(k_hransac_small, dim3(n_pairs), dim3(GEO_WAVE), 0, s, n_pairs, d_off, active ? d_active.p : (const uint8_t*)nullptr,
                        p1, p2, dH, d_in, d_nin, d_ok);
   }
   HIP_TRY(ctx, hipGetLastError());
-  RansacWork<HEstimator> w;
   if (!slot_pair.empty()) {
     MSFM_TRY(ransac_two_pass<HEstimator>(ctx, {opt->max_iterations, opt->confidence, thr * thr, opt->seed, 0}, n_pairs, offsets, d_off, p1, p2,
                                          slot_pair, w, dH, d_in, d_nin, d_ok));
@@ -1220,7 +1216,7 @@ int geo_hransac_dev(msfm_ctx* ctx, int n_pairs, const int* offsets, const int* d
     }
     HIP_TRY(ctx, hipGetLastError());
   }
-  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the buffers of the run are released on return)
+  HIP_TRY(ctx, sc.finish());   // (the buffers of the run are released on return)
   return MSFM_OK;
 }
 

@@ -1043,7 +1043,8 @@ MSFM_API int msfm_descset_create(msfm_ctx* ctx, int n_images, int dim, msfm_desc
   if (!ctx || !out || n_images <= 0) return MSFM_E_INVAL;
   if (dim != DIM) return msfm_set_error(ctx, MSFM_E_INVAL, "descriptor dim %d not supported (128 = SIFT)", dim);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  msfm_descset* s = new msfm_descset();
+  std::unique_ptr<msfm_descset> s(new msfm_descset());
+  DevScope sc(ctx);   // (a failed create deletes the set)
   s->ctx = ctx; s->n_images = n_images; s->dim = dim;
   s->count.assign(n_images, 0);
   s->kp.assign(n_images, nullptr);
@@ -1054,12 +1055,11 @@ MSFM_API int msfm_descset_create(msfm_ctx* ctx, int n_images, int dim, msfm_desc
   s->ti8.assign(n_images, nullptr); s->qi8.assign(n_images, nullptr); s->tcin.assign(n_images, nullptr); s->tpar.assign(n_images, nullptr); s->qbeta.assign(n_images, nullptr);
   if (s->vmax_dev.alloc(1) != hipSuccess || s->n2smax_dev.alloc(2 * (size_t)n_images) != hipSuccess || s->nonint.alloc(1) != hipSuccess ||
       s->zero_row.alloc(256) != hipSuccess || hipMemsetAsync(s->zero_row.p, 0, 256, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(s->nonint.p, 0, sizeof(int), ctx->stream) != hipSuccess || hipMemsetAsync(s->vmax_dev.p, 0, sizeof(unsigned), ctx->stream) != hipSuccess) {
-    delete s;
+      hipMemsetAsync(s->nonint.p, 0, sizeof(int), ctx->stream) != hipSuccess || hipMemsetAsync(s->vmax_dev.p, 0, sizeof(unsigned), ctx->stream) != hipSuccess)
     return msfm_set_error(ctx, MSFM_E_NOMEM, "descset alloc");
-  }
   ctx->children++;   // only a set that exists counts: a failed create must not keep the context alive for good
-  *out = s;
+  *out = s.release();
+  sc.dismiss();   // the set keeps its blocks
   return MSFM_OK;
 }
 
@@ -1300,6 +1300,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   }
   msfm_match_result* R = new msfm_match_result();
   struct Guard { msfm_match_result* p; msfm_ctx* c; ~Guard() { if (p) { delete p; msfm_ctx_child_released(c); } } } guard{R, ctx};
+  DevScope sc(ctx);   // (an error return deletes the result)
   ctx->children++;
   R->generation = s->generation;
   R->kp_generation = s->kp_generation;
@@ -1377,6 +1378,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   HIP_TRY(ctx, hipStreamSynchronize(st));
   MSFM_TRY(launch_match(R));
   guard.p = nullptr;
+  sc.dismiss();   // the result keeps its blocks
   s->results.push_back(R);
   *out = R;
   return MSFM_OK;

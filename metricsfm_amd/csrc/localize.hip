@@ -222,6 +222,7 @@ static int store_finish(msfm_ctx* ctx, msfm_match_store* S, const char* who) {
   if (S->M == 0) return MSFM_OK;
   hipStream_t s = ctx->stream;
   DevBuf<int> d_nf, d_pair, d_moff, err;
+  DevScope sc(ctx);
   LC_TRY(d_nf.from(S->n_features, s)); LC_TRY(d_pair.from(S->pair_img, s)); LC_TRY(d_moff.from(S->match_off, s)); LC_TRY(err.alloc(1));
   const int big = LOC_BIG;
   LC_TRY(hipMemcpyAsync(err.p, &big, sizeof(int), hipMemcpyHostToDevice, s));
@@ -229,7 +230,7 @@ static int store_finish(msfm_ctx* ctx, msfm_match_store* S, const char* who) {
   LC_TRY(hipGetLastError());
   int bad = big;
   LC_TRY(hipMemcpyAsync(&bad, err.p, sizeof(int), hipMemcpyDeviceToHost, s));
-  LC_TRY(hipStreamSynchronize(s));
+  LC_TRY(sc.finish());
   if (bad != big) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: match %d names a feature outside its image", who, bad);
   return MSFM_OK;
 }
@@ -249,11 +250,11 @@ MSFM_API int msfm_match_store_create(msfm_ctx* ctx, int n_images, const int* n_f
   S->pair_img.assign(pair_img, pair_img + 2 * (size_t)n_pairs);
   if (n_pairs) S->match_off.assign(match_off, match_off + n_pairs + 1); else S->match_off.assign(1, 0);
   S->has_kp.assign(std::max(1, n_images), 0);
+  DevScope sc(ctx);   // (an error return deletes the store: the upload is over before its block goes back)
   LC_TRY(S->d_match.alloc(2 * (size_t)std::max(1, M)));
   LC_TRY(S->d_match.upload(matches, 2 * (size_t)M, ctx->stream));
-  const int rc = store_finish(ctx, S.get(), "msfm_match_store_create");
-  if (rc != MSFM_OK) { (void)hipStreamSynchronize(ctx->stream); return rc; }   // (the upload is over before the block goes back)
-  LC_TRY(hipStreamSynchronize(ctx->stream));
+  MSFM_TRY(store_finish(ctx, S.get(), "msfm_match_store_create"));
+  LC_TRY(sc.finish());
   ctx->children++;
   *out = S.release();
   return MSFM_OK;
@@ -276,13 +277,13 @@ MSFM_API int msfm_match_store_from_chain(msfm_chain* chain, msfm_match_store** o
   long nf = 0;
   for (int i = 0; i < v.n_images; i++) { S->has_kp[i] = v.kp[i] != nullptr; nf += v.count[i]; }
   // copies of its own, device to device: the chain may be destroyed while the store lives
+  DevScope sc(ctx);
   LC_TRY(S->d_match.alloc(2 * (size_t)std::max(1, S->M)));
   if (S->M) LC_TRY(hipMemcpyAsync(S->d_match.p, v.d_match, sizeof(int) * 2 * (size_t)S->M, hipMemcpyDeviceToDevice, s));
   LC_TRY(S->d_kp.alloc(2 * (size_t)std::max(1L, nf)));
   if (nf) LC_TRY(hipMemcpyAsync(S->d_kp.p, v.d_kp, sizeof(float) * 2 * (size_t)nf, hipMemcpyDeviceToDevice, s));
-  const int rc = store_finish(ctx, S.get(), "msfm_match_store_from_chain");
-  if (rc != MSFM_OK) { (void)hipStreamSynchronize(s); return rc; }
-  LC_TRY(hipStreamSynchronize(s));
+  MSFM_TRY(store_finish(ctx, S.get(), "msfm_match_store_from_chain"));
+  LC_TRY(sc.finish());
   ctx->children++;
   *out = S.release();
   return MSFM_OK;
@@ -365,22 +366,20 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
   hipStream_t s = ctx->stream;
   const msfm_env env = msfm_env_read();
   const int lds_max = std::max(0, std::min(env.localize_lds_max, LOC_LDS_MAX));
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t n) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, n));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(n * sizeof(*h));
-    return buf.upload(h, n, s);
-  };
   const int S_slots = slot_off[nk];
   DevBuf<WorkPair> d_wp;
   DevBuf<int> d_fp, d_views, d_slot, d_first, d_pcount, d_ncorr, d_err;
   DevBuf<uint8_t> d_bad;
-  DevBuf<double> d_mse;
-  LC_TRY(up(d_wp, wp.data(), (size_t)nwp)); LC_TRY(up(d_slot, slot_off.data(), (size_t)nk + 1));
+  DevBuf<double> d_mse, d_xyz, d_pw, d_p2;
+  DevBuf<float> d_kp_up;
+  DevBuf<int> d_out, d_kpo, d_idx, d_idx_s, d_feat, d_point, d_kprow, d_cf, d_cp, d_sb, d_se, d_lb, d_le;   // (of the second half: emit, sort, gather)
+  DevBuf<unsigned long long> d_key, d_key_s;
+  DevBuf<char> tmp;
+  DevScope sc(ctx);
+  LC_TRY(sc.up(d_wp, wp.data(), (size_t)nwp)); LC_TRY(sc.up(d_slot, slot_off.data(), (size_t)nk + 1));
   if (!dev) {
-    LC_TRY(up(d_fp, P->feat_point, (size_t)FP)); LC_TRY(up(d_bad, P->pt_bad, (size_t)npt));
-    LC_TRY(up(d_mse, P->pt_mse, (size_t)npt)); LC_TRY(up(d_views, P->pt_views, (size_t)npt));
+    LC_TRY(sc.up(d_fp, P->feat_point, (size_t)FP)); LC_TRY(sc.up(d_bad, P->pt_bad, (size_t)npt));
+    LC_TRY(sc.up(d_mse, P->pt_mse, (size_t)npt)); LC_TRY(sc.up(d_views, P->pt_views, (size_t)npt));
   }
   const int* fp_p = dev ? dev->feat_point : d_fp.p;
   const uint8_t* bad_p = dev ? dev->pt_bad : d_bad.p;
@@ -432,15 +431,13 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     R->vis_cam.insert(R->vis_cam.end(), vis[r].begin(), vis[r].end());
     R->vis_off.push_back((int)R->vis_cam.size());
   }
-  R->h2d_bytes = h2d;
-  if (T == 0) return hand_over();
+  R->h2d_bytes = sc.h2d;
+  if (T == 0) { sc.dismiss(); return hand_over(); }   // (behind the wait above: nothing has been enqueued since)
   // ---- emit, sort, gather ----
   std::vector<int> kp_off(nk, 0);
-  DevBuf<float> d_kp_up;
-  DevBuf<double> d_xyz, d_pw, d_p2;
   const float* d_kp = nullptr;
   if (want_pts) {
-    if (!dev) LC_TRY(up(d_xyz, P->point_xyz, 3 * (size_t)npt));
+    if (!dev) LC_TRY(sc.up(d_xyz, P->point_xyz, 3 * (size_t)npt));
     if (dev && dev->kp) {   // every image's rows, resident
       for (int k = 0; k < nk; k++) kp_off[k] = S->feat_off[P->cand_img[k]];
       d_kp = dev->kp;
@@ -453,7 +450,7 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
         const size_t cnt = 2 * (size_t)S->n_features[im];
         if (cnt) LC_TRY(hipMemcpyAsync(d_kp_up.p + 2 * (size_t)kp_off[order[r]], P->keypoints + 2 * (size_t)S->feat_off[im], sizeof(float) * cnt,
                                        hipMemcpyHostToDevice, s));
-        h2d += (int64_t)(sizeof(float) * cnt);
+        sc.h2d += (int64_t)(sizeof(float) * cnt);
       }
       d_kp = d_kp_up.p;
     } else {
@@ -467,10 +464,7 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     const int b = R->corr_off[r], e = R->corr_off[r + 1];
     if (e - b <= lds_max) { sb.push_back(b); se.push_back(e); } else { lb.push_back(b); le.push_back(e); }
   }
-  DevBuf<int> d_out, d_kpo, d_idx, d_idx_s, d_feat, d_point, d_kprow, d_cf, d_cp, d_sb, d_se, d_lb, d_le;
-  DevBuf<unsigned long long> d_key, d_key_s;
-  DevBuf<char> tmp;
-  LC_TRY(up(d_out, out_off.data(), (size_t)nk)); LC_TRY(up(d_kpo, kp_off.data(), (size_t)nk));
+  LC_TRY(sc.up(d_out, out_off.data(), (size_t)nk)); LC_TRY(sc.up(d_kpo, kp_off.data(), (size_t)nk));
   LC_TRY(d_key.alloc(T)); LC_TRY(d_idx.alloc(T)); LC_TRY(d_idx_s.alloc(T)); LC_TRY(d_feat.alloc(T)); LC_TRY(d_point.alloc(T)); LC_TRY(d_kprow.alloc(T));
   LC_TRY(d_cf.alloc(T)); LC_TRY(d_cp.alloc(T));
   LC_TRY(hipMemsetAsync(d_idx_s.p, 0, sizeof(int) * (size_t)T, s));   // (k_gather indexes with it: never an uninitialised value)
@@ -480,13 +474,13 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
                        d_key.p, d_idx.p, d_feat.p, d_point.p, d_kprow.p);
   }
   if (!sb.empty()) {
-    LC_TRY(up(d_sb, sb.data(), sb.size())); LC_TRY(up(d_se, se.data(), se.size()));
+    LC_TRY(sc.up(d_sb, sb)); LC_TRY(sc.up(d_se, se));
     KTimer t(ctx, "localize_sort_lds");
     hipLaunchKernelGGL(k_sort_lds, dim3((unsigned)sb.size()), dim3(256), 0, s, d_sb.p, d_se.p, d_key.p, d_idx.p, d_idx_s.p);
   }
   if (!lb.empty()) {
     // stable, so equal keys keep the emit order = ascending f_i: the order k_sort_lds spells out
-    LC_TRY(up(d_lb, lb.data(), lb.size())); LC_TRY(up(d_le, le.data(), le.size()));
+    LC_TRY(sc.up(d_lb, lb)); LC_TRY(sc.up(d_le, le));
     LC_TRY(d_key_s.alloc(T));
     size_t bytes = 0;
     LC_TRY(rocprim::segmented_radix_sort_pairs(nullptr, bytes, d_key.p, d_key_s.p, d_idx.p, d_idx_s.p, (unsigned)T, (unsigned)lb.size(), d_lb.p, d_le.p, 0, 64, s));
@@ -508,8 +502,8 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     LC_TRY(hipMemcpyAsync(R->pts_w.data(), d_pw.p, sizeof(double) * 3 * (size_t)T, hipMemcpyDeviceToHost, s));
     LC_TRY(hipMemcpyAsync(R->pts_2d.data(), d_p2.p, sizeof(double) * 2 * (size_t)T, hipMemcpyDeviceToHost, s));
   }
-  LC_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
-  R->h2d_bytes = h2d;
+  LC_TRY(sc.finish());   // the scratch above is released on return
+  R->h2d_bytes = sc.h2d;
   if (want_pts) { R->d_cp.swap(d_cp); R->d_pw.swap(d_pw); R->d_p2.swap(d_p2); }   // resident for msfm_localize_poses
   if (dev) R->d_cf.swap(d_cf);   // (a resident state commits the winner's row from the device)
   return hand_over();

@@ -222,15 +222,10 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
   DevBuf<uint8_t> d_added, d_pass, d_state;
   EpnpScratch ws1;
   EpnpfScratch ws2;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto& v) -> hipError_t { h2d += (int64_t)(v.size() * sizeof(v[0])); return buf.from(v, s); };
-  LP_TRY(up(d_slot, slot)); LP_TRY(up(d_toff, toff)); LP_TRY(up(d_off1, off1)); LP_TRY(up(d_off2, off2));
-  LP_TRY(d_rowf.alloc(n)); LP_TRY(d_rowf.upload(row_f, n, s));
-  h2d += (int64_t)sizeof(double) * n;
-  if (!d_added_dev && pt_new_added && n_points) {
-    LP_TRY(d_added.alloc(n_points)); LP_TRY(d_added.upload(pt_new_added, n_points, s));
-    h2d += n_points;
-  }
+  DevScope sc(ctx);
+  LP_TRY(sc.up(d_slot, slot)); LP_TRY(sc.up(d_toff, toff)); LP_TRY(sc.up(d_off1, off1)); LP_TRY(sc.up(d_off2, off2));
+  LP_TRY(sc.up(d_rowf, row_f, (size_t)n));
+  if (!d_added_dev && pt_new_added && n_points) LP_TRY(sc.up(d_added, pt_new_added, (size_t)n_points));
   const uint8_t* added_p = d_added_dev ? d_added_dev : d_added.p;
   LP_TRY(d_w1.alloc(3 * (size_t)std::max(1, E1))); LP_TRY(d_x1.alloc(2 * (size_t)std::max(1, E1))); LP_TRY(d_e1.alloc(std::max(1, E1)));
   LP_TRY(d_w2.alloc(3 * (size_t)std::max(1, E2))); LP_TRY(d_x2.alloc(2 * (size_t)std::max(1, E2))); LP_TRY(d_e2.alloc(std::max(1, E2)));
@@ -260,7 +255,7 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
     a1 = ArmOut{nullptr, d_R1.p, d_t1.p, d_a1.p, nullptr, d_bi1.p};
   }
   if (E2) {   // :673-704
-    LP_TRY(up(d_finit, f_init));
+    LP_TRY(sc.up(d_finit, f_init));
     LP_TRY(d_f2.alloc(n)); LP_TRY(d_R2.alloc(9 * (size_t)n)); LP_TRY(d_t2.alloc(3 * (size_t)n)); LP_TRY(d_a2.alloc(n)); LP_TRY(d_bs2.alloc(n));
     LP_TRY(d_bi2.alloc(n));
     MSFM_TRY(pose_epnpf_dev(ctx, n, n_steps, d_off2.p, d_w2.p, d_x2.p, d_finit.p, &opt.sweep, ws2, d_f2.p, d_R2.p, d_t2.p, d_e2.p, d_a2.p,
@@ -279,17 +274,16 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
   }
   LP_TRY(hipGetLastError());
   // ---- one read-back, one wait ----
-  auto down = [&](auto* h, const auto& buf, size_t cnt) { return hipMemcpyAsync(h, buf.p, sizeof(*h) * cnt, hipMemcpyDeviceToHost, s); };
-  LP_TRY(down(R->pass.data(), d_pass, (size_t)n)); LP_TRY(down(R->f.data(), d_f, (size_t)n)); LP_TRY(down(R->R.data(), d_R, 9 * (size_t)n));
-  LP_TRY(down(R->t.data(), d_t, 3 * (size_t)n)); LP_TRY(down(R->avg.data(), d_avg, (size_t)n));
-  LP_TRY(down(R->best_step.data(), d_bstep, (size_t)n)); LP_TRY(down(R->best_iter.data(), d_biter, (size_t)n));
-  LP_TRY(down(R->n_in.data(), d_nin, (size_t)n)); LP_TRY(down(R->n_out.data(), d_nout, (size_t)n));
-  LP_TRY(down(R->errors.data(), d_err, (size_t)T)); LP_TRY(down(R->state.data(), d_state, (size_t)T));
-  LP_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
+  LP_TRY(sc.down(R->pass.data(), d_pass.p, (size_t)n)); LP_TRY(sc.down(R->f.data(), d_f.p, (size_t)n)); LP_TRY(sc.down(R->R.data(), d_R.p, 9 * (size_t)n));
+  LP_TRY(sc.down(R->t.data(), d_t.p, 3 * (size_t)n)); LP_TRY(sc.down(R->avg.data(), d_avg.p, (size_t)n));
+  LP_TRY(sc.down(R->best_step.data(), d_bstep.p, (size_t)n)); LP_TRY(sc.down(R->best_iter.data(), d_biter.p, (size_t)n));
+  LP_TRY(sc.down(R->n_in.data(), d_nin.p, (size_t)n)); LP_TRY(sc.down(R->n_out.data(), d_nout.p, (size_t)n));
+  LP_TRY(sc.down(R->errors.data(), d_err.p, (size_t)T)); LP_TRY(sc.down(R->state.data(), d_state.p, (size_t)T));
+  LP_TRY(sc.finish());   // the scratch above is released on return
   for (int r = 0; r < n; r++)
     if (R->tried[r] && R->pass[r]) { R->winner = r; break; }
   if (keep_state) keep_state->swap(d_state);
-  if (h2d_bytes) *h2d_bytes += h2d;
+  if (h2d_bytes) *h2d_bytes += sc.h2d;
   *out = R.release();
   return MSFM_OK;
 }

@@ -124,12 +124,6 @@ __global__ __launch_bounds__(256) void k_emit(int M, int E, const int* __restric
   takes2[p] = slot[(size_t)e.slot2 + f2] == p ? 1 : 0;
 }
 
-static int bits_for(unsigned v) {   // bits that hold every value 0 .. v
-  int b = 1;
-  while (b < 32 && (v >> b)) b++;
-  return b;
-}
-
 }  // namespace newpts
 
 #define NP_TRY(e) HIP_TRY(ctx, (e))
@@ -238,9 +232,9 @@ int newpoints_plan(msfm_ctx* ctx, const char* who, const msfm_match_store* S, co
 }
 
 // The kernels of the call on device arrays: the walk's tables go up, k_tri / sort / k_claim / k_emit run, the result block
-// W->d_out is left on the device.  No synchronisation; W belongs to the caller, who keeps it until the stream has been waited for.
+// W->d_out is left on the device.  No synchronisation: W belongs to the caller, who declares it in front of the scope `sc`.
 int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs& P, const NewPointsPlan& L, const msfm_new_points_options& opt,
-                  const int* d_fp, const float* d_kp, int64_t* h2d_bytes, NewPointsDev* W) {
+                  const int* d_fp, const float* d_kp, DevScope& sc, NewPointsDev* W) {
   using namespace newpts;
   const int E = L.E, M = L.M, nn = L.nn;
   // the sentinel of a match that yields no point sorts behind every (int)mse: sqrt(mse) <= th gives mse <= th^2 (1 + 2^-52)
@@ -248,13 +242,6 @@ int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs&
   const int key_bits = bits_for(sentinel), cam_bits = nn > 1 ? bits_for((unsigned)(nn - 1)) : 0;
   const unsigned key_mask = key_bits >= 32 ? 0xffffffffu : ((1u << key_bits) - 1u);
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
   const int ninv = (int)L.involved.size();
   std::vector<double> cam(NP_CAM * (size_t)ninv);
   for (int r = 0; r < ninv; r++) {
@@ -265,8 +252,8 @@ int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs&
     std::copy(P.cam_c + 3 * c, P.cam_c + 3 * c + 3, C + 12);
     std::copy(P.cam_fk + 3 * c, P.cam_fk + 3 * c + 3, C + 15);
   }
-  NP_TRY(up(W->d_ent, L.ent.data(), (size_t)E)); NP_TRY(up(W->d_offa, L.off_all.data(), (size_t)E + 1)); NP_TRY(up(W->d_blk, L.blk_off.data(), (size_t)E + 1));
-  NP_TRY(up(W->d_cam, cam.data(), cam.size()));
+  NP_TRY(sc.up(W->d_ent, L.ent.data(), (size_t)E)); NP_TRY(sc.up(W->d_offa, L.off_all.data(), (size_t)E + 1)); NP_TRY(sc.up(W->d_blk, L.blk_off.data(), (size_t)E + 1));
+  NP_TRY(sc.up(W->d_cam, cam));
   const size_t Mx = (size_t)M;
   NP_TRY(W->d_key.alloc(Mx)); NP_TRY(W->d_key_s.alloc(Mx)); NP_TRY(W->d_val.alloc(Mx)); NP_TRY(W->d_val_s.alloc(Mx));
   NP_TRY(W->d_Xall.alloc(3 * Mx)); NP_TRY(W->d_mseall.alloc(Mx));
@@ -311,7 +298,6 @@ int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs&
                        W->d_slot.p, W->d_Xall.p, W->d_mseall.p, d_w, d_f1, d_f2, d_X, d_mse, d_t1, d_t2);
   }
   NP_TRY(hipGetLastError());
-  *h2d_bytes += h2d;
   return MSFM_OK;
 }
 
@@ -380,16 +366,10 @@ MSFM_API int msfm_new_points(msfm_ctx* ctx, const msfm_match_store* S, const msf
   if (L.M == 0) { *out = R.release(); return MSFM_OK; }   // (also n_new = 0 and empty visible lists)
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
   NewPointsDev W;
   DevBuf<int> d_fp;
   DevBuf<float> d_kp_up;
+  DevScope sc(ctx);
   // the rows of the involved cameras only, packed on the host: one copy per table instead of one per camera
   const int ninv = (int)L.involved.size();
   std::vector<int> h_fp((size_t)L.fp_rows);
@@ -402,16 +382,16 @@ MSFM_API int msfm_new_points(msfm_ctx* ctx, const msfm_match_store* S, const msf
     if (P->keypoints)
       std::copy(P->keypoints + 2 * (size_t)S->feat_off[im], P->keypoints + 2 * ((size_t)S->feat_off[im] + cnt), h_kp.begin() + 2 * (size_t)L.kp_base[r]);
   }
-  NP_TRY(up(d_fp, h_fp.data(), h_fp.size()));
-  if (P->keypoints) NP_TRY(up(d_kp_up, h_kp.data(), h_kp.size()));
-  MSFM_TRY(newpoints_dev(ctx, S, A, L, opt, d_fp.p, P->keypoints ? d_kp_up.p : S->d_kp.p, &h2d, &W));
+  NP_TRY(sc.up(d_fp, h_fp));
+  if (P->keypoints) NP_TRY(sc.up(d_kp_up, h_kp));
+  MSFM_TRY(newpoints_dev(ctx, S, A, L, opt, d_fp.p, P->keypoints ? d_kp_up.p : S->d_kp.p, sc, &W));
   // ---- one read-back: the two counts per entry and the point arrays at the capacity of the walk (M is known here, the
   //      accepted counts are not) ----
   std::vector<double> h_out((W.out_bytes + 7) / 8);   // (doubles: the block's alignment)
   NP_TRY(hipMemcpyAsync(h_out.data(), W.d_out.p, W.out_bytes, hipMemcpyDeviceToHost, s));
-  NP_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
+  NP_TRY(sc.finish());   // the scratch above is released on return
   newpoints_collect(A, L, W, (const char*)h_out.data(), R.get());
-  R->h2d_bytes = h2d;
+  R->h2d_bytes = sc.h2d;
   *out = R.release();
   return MSFM_OK;
 }

@@ -1545,6 +1545,7 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   DevBuf<int> d_off, d_best;
   DevBuf<double> d_w, d_2d, d_f, d_R, d_t, d_err, d_avg;
   EpnpScratch ws;
+  DevScope sc(ctx);
   HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
   HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
@@ -1559,12 +1560,12 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, d_avg.alloc(n_problems));
   HIP_TRY(ctx, d_best.alloc(n_problems));
   MSFM_TRY(pose_epnp_dev(ctx, n_problems, d_off.p, d_w.p, d_2d.p, d_f.p, max_iter, seed, ws, d_R.p, d_t.p, d_err.p, d_avg.p, d_best.p));
-  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(errors, d_err.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(avg_error, d_avg.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_best.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(errors, d_err.p, (size_t)total));
+  HIP_TRY(ctx, sc.down(avg_error, d_avg.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(best_iter, d_best.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -1629,6 +1630,7 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   DevBuf<int> d_off, d_bstep, d_biter;
   DevBuf<double> d_w, d_2d, d_f, d_fo, d_R, d_t, d_err, d_avg;
   EpnpfScratch ws;
+  DevScope sc(ctx);
   HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
   HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
@@ -1646,15 +1648,15 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   HIP_TRY(ctx, d_biter.alloc(n_problems));
   MSFM_TRY(pose_epnpf_dev(ctx, n_problems, n_steps, d_off.p, d_w.p, d_2d.p, d_f.p, opt, ws, d_fo.p, d_R.p, d_t.p, d_err.p, d_avg.p, d_bstep.p,
                           d_biter.p));
-  HIP_TRY(ctx, hipMemcpyAsync(f_out, d_fo.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (total) HIP_TRY(ctx, hipMemcpyAsync(errors, d_err.p, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(avg_error, d_avg.p, sizeof(double) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (best_step) HIP_TRY(ctx, hipMemcpyAsync(best_step, d_bstep.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_biter.p, sizeof(int) * (size_t)n_problems, hipMemcpyDeviceToHost, s));
-  if (step_error) HIP_TRY(ctx, hipMemcpyAsync(step_error, ws.step_err.p, sizeof(double) * Q, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(f_out, d_fo.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(errors, d_err.p, (size_t)total));
+  HIP_TRY(ctx, sc.down(avg_error, d_avg.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(best_step, d_bstep.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(best_iter, d_biter.p, (size_t)n_problems));
+  HIP_TRY(ctx, sc.down(step_error, ws.step_err.p, Q));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -1701,6 +1703,7 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   DevBuf<double> d_a, d_b, d_f1, d_f2, d_E, d_R, d_t;
   DevBuf<uint8_t> d_ok;
   Relpose5Scratch ws;
+  DevScope sc(ctx);
   HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
   HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
@@ -1712,12 +1715,12 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs));
   HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
   MSFM_TRY(pose_relpose5_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, ransac_times, seed, ws, d_E.p, d_R.p, d_t.p, d_ok.p, d_nc.p));
-  HIP_TRY(ctx, hipMemcpyAsync(E, d_E.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (n_candidates) HIP_TRY(ctx, hipMemcpyAsync(n_candidates, d_nc.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(E, d_E.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(ok, d_ok.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(n_candidates, d_nc.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -1762,6 +1765,7 @@ MSFM_API int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   DevBuf<double> d_a, d_b, d_F, d_f1, d_f2, d_E, d_R, d_t, d_be;
   DevBuf<uint8_t> d_ok;
   Relpose8Scratch ws;
+  DevScope sc(ctx);
   HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
   HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
   HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
@@ -1773,16 +1777,16 @@ MSFM_API int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_bi.alloc(n_pairs)); HIP_TRY(ctx, d_be.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
   MSFM_TRY(pose_relpose8_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, ransac_times, seed, ws, d_F.p, d_f1.p, d_f2.p, d_E.p, d_R.p, d_t.p, d_ok.p, d_bi.p,
                              d_be.p, d_nc.p));
-  HIP_TRY(ctx, hipMemcpyAsync(F, d_F.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(f_ref, d_f1.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(f_cur, d_f2.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(E, d_E.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(R, d_R.p, sizeof(double) * 9 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(t, d_t.p, sizeof(double) * 3 * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, d_ok.p, (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (best_iter) HIP_TRY(ctx, hipMemcpyAsync(best_iter, d_bi.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (best_error) HIP_TRY(ctx, hipMemcpyAsync(best_error, d_be.p, sizeof(double) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  if (n_candidates) HIP_TRY(ctx, hipMemcpyAsync(n_candidates, d_nc.p, sizeof(int) * (size_t)n_pairs, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(F, d_F.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(f_ref, d_f1.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(f_cur, d_f2.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(E, d_E.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(ok, d_ok.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(best_iter, d_bi.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(best_error, d_be.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.down(n_candidates, d_nc.p, (size_t)n_pairs));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }

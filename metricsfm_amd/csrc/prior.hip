@@ -123,8 +123,11 @@ MSFM_API int msfm_slam_priors(msfm_ctx* ctx, const msfm_tracks* P, const msfm_sl
   if (n_slots == 0) return MSFM_OK;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  DevBuf<int> d_slot, d_cam_off, d_cam_pt, d_cam_obs, d_cnt;
-  DevBuf<float> d_xy;
+  DevBuf<int> d_slot, d_cam_off, d_cam_pt, d_cam_obs, d_cnt, d_cand, d_off, d_nin;
+  DevBuf<float> d_xy, d1, d2;
+  DevBuf<double> dF, dH;
+  DevBuf<uint8_t> d_in, d_ok;
+  DevScope sc(ctx);
   HIP_TRY(ctx, d_slot.from(slot_ij, s));
   HIP_TRY(ctx, d_cam_off.from(cam_off, s));
   HIP_TRY(ctx, d_cam_pt.from(cam_pt, s));
@@ -149,10 +152,6 @@ MSFM_API int msfm_slam_priors(msfm_ctx* ctx, const msfm_tracks* P, const msfm_sl
   std::vector<uint8_t> fpass(std::max(1, n_cand), 0);
   if (n_cand > 0) {
     const int total = off[n_cand];
-    DevBuf<int> d_cand, d_off, d_nin;
-    DevBuf<float> d1, d2;
-    DevBuf<double> dF, dH;
-    DevBuf<uint8_t> d_in, d_ok;
     HIP_TRY(ctx, d_cand.from(cand_slot, s));
     HIP_TRY(ctx, d_off.from(off, s));
     HIP_TRY(ctx, d1.alloc(2 * (size_t)total));
@@ -200,6 +199,7 @@ MSFM_API int msfm_slam_priors(msfm_ctx* ctx, const msfm_tracks* P, const msfm_sl
       HIP_TRY(ctx, hipStreamSynchronize(s));
     }
   }
+  sc.dismiss();   // behind the last of the waits above: nothing has been enqueued since
   // verdicts in slot order
   int kept = 0, c = 0;
   for (int k = 0; k < n_slots; k++) {

@@ -130,6 +130,11 @@ static RoundArgs args_of(const msfm_recon* Q) {
   return A;
 }
 
+// the refusal of every call but fetch and destroy once a solve has failed behind a stage that had written
+static int poisoned_error(msfm_ctx* ctx, const char* who) {
+  return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an earlier msfm_recon_adjust failed inside a solve: the object can only be fetched or destroyed", who);
+}
+
 }  // namespace rec
 
 #define RC_TRY(e) HIP_TRY(ctx, (e))
@@ -176,28 +181,20 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   Q->cam_c.assign(P->cam_c, P->cam_c + 3 * ncx); Q->cam_fk.assign(P->cam_fk, P->cam_fk + 3 * ncx);
   RC_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt, size_t cap) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cap));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
-  // what is enqueued below uses the object's buffers: an error return releases them only behind a wait (adjust.hip, `fail`)
   DevBuf<int> d_fo, d_err;
-  struct Wait { hipStream_t s; bool on = true; ~Wait() { if (on) (void)hipStreamSynchronize(s); } } wait{s};
-  RC_TRY(up(Q->d_fp, P->feat_point, (size_t)FP, total));
-  RC_TRY(up(Q->d_op, P->obs_point, nox, Q->cap_obs)); RC_TRY(up(Q->d_oc, P->obs_cam, nox, Q->cap_obs)); RC_TRY(up(Q->d_of, P->obs_feat, nox, Q->cap_obs));
-  RC_TRY(up(Q->d_xyz, P->point_xyz, 3 * npx, 3 * Q->cap_points)); RC_TRY(up(Q->d_mse, P->pt_mse, npx, Q->cap_points));
-  RC_TRY(up(Q->d_views, P->pt_views, npx, Q->cap_points));
-  RC_TRY(up(Q->d_bad, P->pt_bad, npx, Q->cap_points)); RC_TRY(up(Q->d_mut, P->pt_mutable, npx, Q->cap_points));
-  if (P->pt_new_added) RC_TRY(up(Q->d_added, P->pt_new_added, npx, Q->cap_points));
+  DevScope sc(ctx);   // (Q's blocks too: an error return deletes the object)
+  RC_TRY(sc.up(Q->d_fp, P->feat_point, (size_t)FP, total));
+  RC_TRY(sc.up(Q->d_op, P->obs_point, nox, Q->cap_obs)); RC_TRY(sc.up(Q->d_oc, P->obs_cam, nox, Q->cap_obs)); RC_TRY(sc.up(Q->d_of, P->obs_feat, nox, Q->cap_obs));
+  RC_TRY(sc.up(Q->d_xyz, P->point_xyz, 3 * npx, 3 * Q->cap_points)); RC_TRY(sc.up(Q->d_mse, P->pt_mse, npx, Q->cap_points));
+  RC_TRY(sc.up(Q->d_views, P->pt_views, npx, Q->cap_points));
+  RC_TRY(sc.up(Q->d_bad, P->pt_bad, npx, Q->cap_points)); RC_TRY(sc.up(Q->d_mut, P->pt_mutable, npx, Q->cap_points));
+  if (P->pt_new_added) RC_TRY(sc.up(Q->d_added, P->pt_new_added, npx, Q->cap_points));
   else { RC_TRY(Q->d_added.alloc(Q->cap_points)); RC_TRY(hipMemsetAsync(Q->d_added.p, 0, Q->cap_points, s)); }
   if (P->keypoints) {   // every image's rows, in the store's order: camera c reads from feat_off[cam_img[c]], now and after any append
-    RC_TRY(up(Q->d_kp, P->keypoints, 2 * total, 2 * total));
+    RC_TRY(sc.up(Q->d_kp, P->keypoints, 2 * total, 2 * total));
     Q->own_kp = true;
   }
-  RC_TRY(up(d_fo, T.cam_fo.data(), ncx + 1, ncx + 1));
+  RC_TRY(sc.up(d_fo, T.cam_fo.data(), ncx + 1, ncx + 1));
   RC_TRY(d_err.alloc(2));
   RC_TRY(hipMemsetD32Async((hipDeviceptr_t)d_err.p, REC_BIG, 2, s));
   {
@@ -209,11 +206,10 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   RC_TRY(hipGetLastError());
   int err[2] = {REC_BIG, REC_BIG};
   RC_TRY(hipMemcpyAsync(err, d_err.p, sizeof err, hipMemcpyDeviceToHost, s));
-  RC_TRY(hipStreamSynchronize(s));
-  wait.on = false;
+  RC_TRY(sc.finish());
   if (err[0] != REC_BIG) return round_fp_error(ctx, who, T.cam_fo, nc, np, err[0]);
   if (err[1] != REC_BIG) return round_row_error(ctx, who, err[1], P->obs_point[err[1]], P->obs_cam[err[1]], P->obs_feat[err[1]]);
-  Q->h2d_bytes = h2d;
+  Q->h2d_bytes = sc.h2d;
   ctx->children++;   // a child of its context, like a store
   *out = Q.release();
   return MSFM_OK;
@@ -247,19 +243,15 @@ MSFM_API int msfm_recon_fetch(msfm_recon* Q, int32_t* cam_img, int32_t* feat_poi
   if (cam_c) std::copy(Q->cam_c.begin(), Q->cam_c.end(), cam_c);
   if (cam_fk) std::copy(Q->cam_fk.begin(), Q->cam_fk.end(), cam_fk);
   RC_TRY(hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
+  DevScope sc(ctx);
   size_t FP = 0;
   for (int c = 0; c < Q->n_cams; c++) FP += (size_t)Q->store->n_features[Q->cam_img[c]];
   const size_t npx = (size_t)Q->n_points, nox = (size_t)Q->n_obs;
-  auto down = [&](auto* h, const auto* d, size_t cnt) -> hipError_t {
-    if (!h || !cnt) return hipSuccess;
-    return hipMemcpyAsync(h, d, cnt * sizeof(*h), hipMemcpyDeviceToHost, s);
-  };
-  RC_TRY(down(feat_point, Q->d_fp.p, FP));
-  RC_TRY(down(obs_point, Q->d_op.p, nox)); RC_TRY(down(obs_cam, Q->d_oc.p, nox)); RC_TRY(down(obs_feat, Q->d_of.p, nox));
-  RC_TRY(down(point_xyz, Q->d_xyz.p, 3 * npx)); RC_TRY(down(pt_bad, Q->d_bad.p, npx)); RC_TRY(down(pt_mse, Q->d_mse.p, npx));
-  RC_TRY(down(pt_views, Q->d_views.p, npx)); RC_TRY(down(pt_mutable, Q->d_mut.p, npx)); RC_TRY(down(pt_new_added, Q->d_added.p, npx));
-  RC_TRY(hipStreamSynchronize(s));
+  RC_TRY(sc.down(feat_point, Q->d_fp.p, FP));
+  RC_TRY(sc.down(obs_point, Q->d_op.p, nox)); RC_TRY(sc.down(obs_cam, Q->d_oc.p, nox)); RC_TRY(sc.down(obs_feat, Q->d_of.p, nox));
+  RC_TRY(sc.down(point_xyz, Q->d_xyz.p, 3 * npx)); RC_TRY(sc.down(pt_bad, Q->d_bad.p, npx)); RC_TRY(sc.down(pt_mse, Q->d_mse.p, npx));
+  RC_TRY(sc.down(pt_views, Q->d_views.p, npx)); RC_TRY(sc.down(pt_mutable, Q->d_mut.p, npx)); RC_TRY(sc.down(pt_new_added, Q->d_added.p, npx));
+  RC_TRY(sc.finish());
   return MSFM_OK;
 }
 
@@ -276,7 +268,7 @@ MSFM_API int msfm_recon_adjust(msfm_recon* Q, int new_cam, int n_visible, const 
   if (n_visible && !visible) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
   // every refusal lies in front of the first write to the state: the checks of msfm_round_adjust that need no bulk array
   // (the indices of the state were checked when it was uploaded)
-  if (Q->poisoned) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an earlier msfm_recon_adjust failed inside a solve: the object can only be fetched or destroyed", who);
+  if (Q->poisoned) return rec::poisoned_error(ctx, who);
   RoundArgs A = rec::args_of(Q);
   A.new_cam = new_cam; A.n_visible = n_visible; A.visible = visible;
   A.do_partial = do_partial != 0; A.do_full = do_full != 0; A.do_outliers = do_outliers != 0;
@@ -309,7 +301,7 @@ MSFM_API int msfm_recon_adjust(msfm_recon* Q, int new_cam, int n_visible, const 
 }
 
 // Room for `points` points and `obs` rows: the arrays that are too short move into blocks of twice the need, device to device on
-// the context's stream; the old blocks go back to the pool only behind a wait for what was enqueued on them (adjust.hip, `fail`).
+// the context's stream; the old blocks go back to the pool only behind the scope's wait for the copies that read them.
 static int recon_reserve(msfm_recon* Q, size_t points, size_t obs) {
   msfm_ctx* ctx = Q->ctx;
   hipStream_t s = ctx->stream;
@@ -321,29 +313,19 @@ static int recon_reserve(msfm_recon* Q, size_t points, size_t obs) {
   DevBuf<int> op, oc, of, views;
   DevBuf<double> xyz, mse;
   DevBuf<uint8_t> bad, mut, added;
+  DevScope sc(ctx);
   auto move = [&](auto& fresh, auto& old, size_t cap, size_t cnt) -> hipError_t {
     hipError_t e = fresh.alloc(cap);
     if (e != hipSuccess) return e;
     if (cnt) e = hipMemcpyAsync(fresh.p, old.p, cnt * sizeof(*old.p), hipMemcpyDeviceToDevice, s);
     return e;
   };
-  hipError_t e = hipSuccess;
-  if (go) {
-    if (e == hipSuccess) e = move(op, Q->d_op, co, no);
-    if (e == hipSuccess) e = move(oc, Q->d_oc, co, no);
-    if (e == hipSuccess) e = move(of, Q->d_of, co, no);
-  }
+  if (go) { RC_TRY(move(op, Q->d_op, co, no)); RC_TRY(move(oc, Q->d_oc, co, no)); RC_TRY(move(of, Q->d_of, co, no)); }
   if (gp) {
-    if (e == hipSuccess) e = move(xyz, Q->d_xyz, 3 * cp, 3 * np);
-    if (e == hipSuccess) e = move(mse, Q->d_mse, cp, np);
-    if (e == hipSuccess) e = move(views, Q->d_views, cp, np);
-    if (e == hipSuccess) e = move(bad, Q->d_bad, cp, np);
-    if (e == hipSuccess) e = move(mut, Q->d_mut, cp, np);
-    if (e == hipSuccess) e = move(added, Q->d_added, cp, np);
+    RC_TRY(move(xyz, Q->d_xyz, 3 * cp, 3 * np)); RC_TRY(move(mse, Q->d_mse, cp, np)); RC_TRY(move(views, Q->d_views, cp, np));
+    RC_TRY(move(bad, Q->d_bad, cp, np)); RC_TRY(move(mut, Q->d_mut, cp, np)); RC_TRY(move(added, Q->d_added, cp, np));
   }
-  const hipError_t w = hipStreamSynchronize(s);   // the copies have read the old blocks (and on an error nothing is pending on the new ones)
-  RC_TRY(e);
-  RC_TRY(w);
+  RC_TRY(sc.finish());   // the copies have read the old blocks
   if (go) { Q->d_op.swap(op); Q->d_oc.swap(oc); Q->d_of.swap(of); Q->cap_obs = co; }
   if (gp) { Q->d_xyz.swap(xyz); Q->d_mse.swap(mse); Q->d_views.swap(views); Q->d_bad.swap(bad); Q->d_mut.swap(mut); Q->d_added.swap(added); Q->cap_points = cp; }
   return MSFM_OK;
@@ -363,7 +345,7 @@ MSFM_API int msfm_recon_new_points(msfm_recon* Q, int new_cam, int n_visible, co
   if (n_visible && !visible) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
   msfm_new_points_options opt;
   if (opt_in) opt = *opt_in; else msfm_new_points_default_options(&opt);
-  if (Q->poisoned) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an earlier msfm_recon_adjust failed inside a solve: the object can only be fetched or destroyed", who);
+  if (Q->poisoned) return rec::poisoned_error(ctx, who);
   const int vis_off[2] = {0, n_visible};
   NewPointsArgs A;
   A.n_cams = Q->n_cams; A.cam_img = Q->cam_img.data();
@@ -379,12 +361,10 @@ MSFM_API int msfm_recon_new_points(msfm_recon* Q, int new_cam, int n_visible, co
   }
   RC_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
   NewPointsDev W;
   DevBuf<int> d_row_cam;
-  // W's blocks and d_row_cam go back to the pool on return: only behind a wait for what was enqueued on them
-  struct Wait { hipStream_t s; bool on = true; ~Wait() { if (on) (void)hipStreamSynchronize(s); } } wait{s};
-  MSFM_TRY(newpoints_dev(ctx, S, A, L, opt, Q->d_fp.p, Q->own_kp ? Q->d_kp.p : S->d_kp.p, &h2d, &W));
+  DevScope sc(ctx);
+  MSFM_TRY(newpoints_dev(ctx, S, A, L, opt, Q->d_fp.p, Q->own_kp ? Q->d_kp.p : S->d_kp.p, sc, &W));
   // what comes back: the accepted count of every visible entry - their sum sizes the append; with `stats` the whole block
   const size_t Ex = (size_t)L.E;
   std::vector<double> h_out;
@@ -407,9 +387,7 @@ MSFM_API int msfm_recon_new_points(msfm_recon* Q, int new_cam, int n_visible, co
   const int n = (int)total;
   if (n) {
     MSFM_TRY(recon_reserve(Q, (size_t)Q->n_points + (size_t)n, (size_t)Q->n_obs + 2 * (size_t)n));
-    RC_TRY(d_row_cam.alloc(L.involved.size()));
-    RC_TRY(d_row_cam.upload(L.involved.data(), L.involved.size(), s));
-    h2d += (int64_t)(sizeof(int) * L.involved.size());
+    RC_TRY(sc.up(d_row_cam, L.involved));
     {
       KTimer tm(ctx, "recon_append_points");
       hipLaunchKernelGGL(k_append_points, dim3(cdiv(n, 256)), dim3(256), 0, s, n, L.E, new_cam, Q->n_points, Q->n_obs, W.d_offa.p, W.d_ent.p, d_row_cam.p,
@@ -418,10 +396,11 @@ MSFM_API int msfm_recon_new_points(msfm_recon* Q, int new_cam, int n_visible, co
                          Q->d_op.p, Q->d_oc.p, Q->d_of.p, Q->d_xyz.p, Q->d_mse.p, Q->d_views.p, Q->d_bad.p, Q->d_mut.p, Q->d_added.p);
     }
     RC_TRY(hipGetLastError());
-    Q->n_points += n; Q->n_obs += 2 * n;
   }
-  Q->h2d_bytes += h2d;
-  R->h2d_bytes = h2d;
+  RC_TRY(sc.finish());   // the append has read W's blocks
+  Q->n_points += n; Q->n_obs += 2 * n;
+  Q->h2d_bytes += sc.h2d;
+  R->h2d_bytes = sc.h2d;
   *n_new = n;
   if (stats) *stats = R.release();
   return MSFM_OK;
@@ -433,7 +412,7 @@ MSFM_API int msfm_recon_localize(msfm_recon* Q, int n_cand, const int32_t* cand_
   if (!Q) return MSFM_E_INVAL;
   msfm_ctx* ctx = Q->ctx;
   if (!out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
-  if (Q->poisoned) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an earlier msfm_recon_adjust failed inside a solve: the object can only be fetched or destroyed", who);
+  if (Q->poisoned) return rec::poisoned_error(ctx, who);
   if (n_cand < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: negative count", who);
   if (n_cand && (!cand_img || !fail_times || !cand_f)) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
   msfm_localize_pose_options opt;
@@ -449,6 +428,7 @@ MSFM_API int msfm_recon_localize(msfm_recon* Q, int n_cand, const int32_t* cand_
   W.image = -1; W.row = -1;
   RC_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
+  DevScope sc(ctx);   // the pending blocks of this call
   msfm_localize_problem P;
   memset(&P, 0, sizeof P);
   P.n_cams = Q->n_cams; P.cam_img = Q->cam_img.data(); P.n_points = Q->n_points; P.n_cand = n_cand; P.cand_img = cand_img; P.fail_times = fail_times;
@@ -472,7 +452,7 @@ MSFM_API int msfm_recon_localize(msfm_recon* Q, int n_cand, const int32_t* cand_
     o.first_row = row;
     msfm_localize_pose_set* R = nullptr;
     DevBuf<uint8_t> d_state;
-    struct Wait { hipStream_t s; ~Wait() { (void)hipStreamSynchronize(s); } } wait{s};   // d_state returns to the pool behind the copies below
+    DevScope chunk(ctx);   // d_state returns to the pool behind the copies below: never settled, every chunk ends in its wait
     MSFM_TRY(localize_poses_dev(ctx, who, L, row_f.data(), cand_f_init ? row_fi.data() : nullptr, Q->n_points, nullptr, Q->d_added.p, &o, &R, &d_state, &h2d));
     std::unique_ptr<msfm_localize_pose_set> own(R);
     W.n_chunks++;
@@ -497,7 +477,7 @@ MSFM_API int msfm_recon_localize(msfm_recon* Q, int n_cand, const int32_t* cand_
   }
   W.n_failed = (int)failed.size();
   W.n_visible = (int)visible.size();
-  RC_TRY(hipStreamSynchronize(s));   // the old pending blocks return to the pool behind whatever read them
+  RC_TRY(sc.finish());   // the old pending blocks return to the pool behind whatever read them
   Q->ranked.swap(ranked); Q->failed.swap(failed); Q->visible.swap(visible);
   Q->pend_feat.swap(pend_feat); Q->pend_point.swap(pend_point); Q->pend_state.swap(pend_state);
   Q->pending = pending;
@@ -522,7 +502,7 @@ MSFM_API int msfm_recon_commit_camera(msfm_recon* Q, const double* cam_pose6, in
   if (!Q) return MSFM_E_INVAL;
   msfm_ctx* ctx = Q->ctx;
   if (!cam_pose6 || !new_cam) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
-  if (Q->poisoned) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an earlier msfm_recon_adjust failed inside a solve: the object can only be fetched or destroyed", who);
+  if (Q->poisoned) return rec::poisoned_error(ctx, who);
   if (!Q->pending) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: no pending localisation (none found, or committed already)", who);
   if (model < 0 || model > Q->n_models) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: model = %d outside n_models = %d", who, model, Q->n_models);
   if (model == Q->n_models && !cam_model3) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: a new model needs cam_model3", who);
@@ -537,7 +517,7 @@ MSFM_API int msfm_recon_commit_camera(msfm_recon* Q, const double* cam_pose6, in
   MSFM_TRY(recon_reserve(Q, (size_t)Q->n_points, (size_t)Q->n_obs + (size_t)n2));
   DevBuf<int> flag, pos;
   DevBuf<char> tmp;
-  struct Wait { hipStream_t s; ~Wait() { (void)hipStreamSynchronize(s); } } wait{s};   // the scratch returns to the pool behind the launches
+  DevScope sc(ctx);
   RC_TRY(flag.alloc((size_t)n + 1)); RC_TRY(pos.alloc((size_t)n + 1));
   size_t bytes = 0;
   RC_TRY(rocprim::exclusive_scan(nullptr, bytes, flag.p, pos.p, 0, (size_t)n + 1, rocprim::plus<int>(), s));
@@ -552,6 +532,7 @@ MSFM_API int msfm_recon_commit_camera(msfm_recon* Q, const double* cam_pose6, in
                        Q->d_fp.p, Q->d_bad.p, Q->d_views.p, Q->d_added.p, Q->d_op.p, Q->d_oc.p, Q->d_of.p);
   }
   RC_TRY(hipGetLastError());
+  RC_TRY(sc.finish());
   // the host tables: SetRTPose keeps R, t and c = -(R^T t), the products summed in row order
   if (model == Q->n_models) {
     Q->cam_model.insert(Q->cam_model.end(), cam_model3, cam_model3 + 3);

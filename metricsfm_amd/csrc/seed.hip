@@ -39,23 +39,13 @@ namespace seed {
 
 struct Hyp { int m0, kp1, kp2, arm; };   // first match in the store, keypoint rows of image 1 / 2, 5 or 8
 
-// the segment of position x: off[lo] <= x < off[lo + 1] (empty segments are stepped over)
-__device__ static inline int segment_of(const int* __restrict__ off, int n, int x) {
-  int lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid] <= x) lo = mid; else hi = mid;
-  }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void k_gather(int M, int n, const int* __restrict__ off_all, const Hyp* __restrict__ hyp,
                                                  const int* __restrict__ off5, const int* __restrict__ off8, const int* __restrict__ matches,
                                                  const float* __restrict__ kp, double* __restrict__ ref5, double* __restrict__ cur5,
                                                  double* __restrict__ ref8, double* __restrict__ cur8) {
   const int m = blockIdx.x * 256 + threadIdx.x;
   if (m >= M) return;
-  const int h = segment_of(off_all, n, m);
+  const int h = csr_segment_of(off_all, n, m);
   const Hyp H = hyp[h];
   const int j = m - off_all[h];
   const size_t sm = (size_t)H.m0 + j;
@@ -106,7 +96,7 @@ __global__ __launch_bounds__(256) void k_tri(int n, const int* __restrict__ blk_
                                               const uint8_t* __restrict__ pose_ok, const double* __restrict__ cam, double th_error, double cos_min,
                                               uint8_t* __restrict__ flag, double* __restrict__ Xall, double* __restrict__ mse_all) {
   __shared__ double s_cam[SEED_CAM + 12];   // + camera 0: R = I (9), t = c = 0 (3)
-  const int h = segment_of(blk_off, n, (int)blockIdx.x);   // (uniform)
+  const int h = csr_segment_of(blk_off, n, (int)blockIdx.x);   // (uniform)
   if (threadIdx.x < SEED_CAM) s_cam[threadIdx.x] = cam[SEED_CAM * (size_t)h + threadIdx.x];
   else if (threadIdx.x < SEED_CAM + 12) { const int k = threadIdx.x - SEED_CAM; s_cam[threadIdx.x] = (k == 0 || k == 4 || k == 8) ? 1.0 : 0.0; }
   __syncthreads();
@@ -240,13 +230,6 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   if (n == 0) { *out = R.release(); return MSFM_OK; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  int64_t h2d = 0;
-  auto up = [&](auto& buf, const auto* h, size_t cnt) -> hipError_t {
-    hipError_t e = buf.alloc(std::max<size_t>(1, cnt));
-    if (e != hipSuccess) return e;
-    h2d += (int64_t)(cnt * sizeof(*h));
-    return buf.upload(h, cnt, s);
-  };
   DevBuf<Hyp> d_hyp;
   DevBuf<int> d_offa, d_off5, d_off8, d_blk, d_nc5, d_bi8, d_nc8, d_ptm, d_count;
   DevBuf<double> d_fk, d_ref5, d_cur5, d_ref8, d_cur8, d_f5a, d_f5b, d_E5, d_R5, d_t5, d_F8, d_f8a, d_f8b, d_E8, d_R8, d_t8, d_be8;
@@ -255,16 +238,17 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   DevBuf<float> d_kp_up;
   Relpose5Scratch ws5;
   Relpose8Scratch ws8;
-  SD_TRY(up(d_hyp, hyp.data(), (size_t)n)); SD_TRY(up(d_offa, off_all.data(), (size_t)n + 1)); SD_TRY(up(d_off5, off5.data(), (size_t)n + 1));
-  SD_TRY(up(d_off8, off8.data(), (size_t)n + 1)); SD_TRY(up(d_blk, blk_off.data(), (size_t)n + 1)); SD_TRY(up(d_fk, P->cam_fk, 6 * (size_t)n));
-  SD_TRY(up(d_same, P->same_model, (size_t)n));
+  DevScope sc(ctx);
+  SD_TRY(sc.up(d_hyp, hyp.data(), (size_t)n)); SD_TRY(sc.up(d_offa, off_all.data(), (size_t)n + 1)); SD_TRY(sc.up(d_off5, off5.data(), (size_t)n + 1));
+  SD_TRY(sc.up(d_off8, off8.data(), (size_t)n + 1)); SD_TRY(sc.up(d_blk, blk_off.data(), (size_t)n + 1)); SD_TRY(sc.up(d_fk, P->cam_fk, 6 * (size_t)n));
+  SD_TRY(sc.up(d_same, P->same_model, (size_t)n));
   const float* d_kp = S->d_kp.p;
   if (P->keypoints) {   // the rows of the hypotheses' images only
     SD_TRY(d_kp_up.alloc(2 * (size_t)std::max(1L, kp_rows)));
     for (int im : kp_imgs) {
       const size_t cnt = 2 * (size_t)S->n_features[im];
       if (cnt) SD_TRY(hipMemcpyAsync(d_kp_up.p + 2 * (size_t)kp_base[im], P->keypoints + 2 * (size_t)S->feat_off[im], sizeof(float) * cnt, hipMemcpyHostToDevice, s));
-      h2d += (int64_t)(sizeof(float) * cnt);
+      sc.h2d += (int64_t)(sizeof(float) * cnt);
     }
     d_kp = d_kp_up.p;
   }
@@ -287,7 +271,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   if (M5) {
     // the eight-point hypotheses' entries (problems without matches) are not read
     for (int h = 0; h < n; h++) { f5_ref[h] = P->cam_fk[6 * (size_t)h]; f5_cur[h] = P->cam_fk[6 * (size_t)h + 3]; }
-    SD_TRY(up(d_f5a, f5_ref.data(), (size_t)n)); SD_TRY(up(d_f5b, f5_cur.data(), (size_t)n));
+    SD_TRY(sc.up(d_f5a, f5_ref.data(), (size_t)n)); SD_TRY(sc.up(d_f5b, f5_cur.data(), (size_t)n));
     SD_TRY(d_E5.alloc(9 * (size_t)n)); SD_TRY(d_nc5.alloc(n));
     MSFM_TRY(pose_relpose5_dev(ctx, n, d_off5.p, d_ref5.p, d_cur5.p, d_f5a.p, d_f5b.p, opt.ransac_times_5pt, opt.seed_5pt, ws5, d_E5.p, d_R5.p, d_t5.p,
                                d_ok5.p, d_nc5.p));
@@ -327,7 +311,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     SD_TRY(hipMemcpyAsync(X.data(), d_X.p, sizeof(double) * 3 * (size_t)M, hipMemcpyDeviceToHost, s));
     SD_TRY(hipMemcpyAsync(mse.data(), d_mse.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, s));
   }
-  SD_TRY(hipStreamSynchronize(s));   // the scratch above is released on return
+  SD_TRY(sc.finish());   // the scratch above is released on return
   for (int h = 0; h < n; h++) {
     const double* C = cam.data() + SEED_CAM * (size_t)h;
     std::copy(C, C + 9, R->R.begin() + 9 * (size_t)h);
@@ -344,7 +328,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     std::copy(X.begin() + 3 * b, X.begin() + 3 * (b + k), R->X.begin() + 3 * e);
     std::copy(mse.begin() + b, mse.begin() + b + k, R->mse.begin() + e);
   }
-  R->h2d_bytes = h2d;
+  R->h2d_bytes = sc.h2d;
   *out = R.release();
   return MSFM_OK;
 }

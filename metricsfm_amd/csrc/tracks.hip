@@ -222,6 +222,7 @@ int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_o
   DevBuf<int> ga, gb, ia, ib, first, parent, is_new, new_before, point_of, err, val, val_s, head, slot;
   DevBuf<unsigned long long> key, key_s;
   DevBuf<char> tmp;
+  DevScope sc(ctx);
   TTRY(ga.alloc(M)); TTRY(gb.alloc(M)); TTRY(ia.alloc(M)); TTRY(ib.alloc(M));
   TTRY(first.alloc(std::max(1, NF))); TTRY(parent.alloc(std::max(1, NF))); TTRY(point_of.alloc(std::max(1, NF)));
   TTRY(is_new.alloc((size_t)M + 1)); TTRY(new_before.alloc((size_t)M + 1)); TTRY(err.alloc(1));
@@ -263,7 +264,7 @@ int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_o
   TTRY(out->off.alloc((size_t)n_tracks + 1)); TTRY(out->img.alloc(std::max(1, n_obs))); TTRY(out->feat.alloc(std::max(1, n_obs)));
   hipLaunchKernelGGL(k_compact, dim3(cdiv(E, 256)), dim3(256), 0, s, E, n_images, key_s.p, val_s.p, head.p, slot.p, out->img.p, out->feat.p, out->off.p);
   TTRY(hipMemcpyAsync(out->off.p + n_tracks, &n_obs, sizeof(int), hipMemcpyHostToDevice, s));
-  TTRY(hipStreamSynchronize(s));   // the scratch above is released on return
+  TTRY(sc.finish());   // the scratch above is released on return
   hipError_t le = hipGetLastError();
   if (le != hipSuccess) return msfm_set_error(ctx, MSFM_E_DEVICE, "msfm_tracks_build_device: %s", hipGetErrorString(le));
 #undef TTRY
@@ -297,22 +298,17 @@ MSFM_API int msfm_tracks_build_device(msfm_ctx* ctx, int n_images, const int* n_
   if (M == 0) { *out = S; return MSFM_OK; }
   std::unique_ptr<msfm_track_set> guard(S);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
   DevBuf<int> d_nf, d_fo, d_pair, d_moff, d_match;
-  HIP_TRY(ctx, d_nf.alloc(n_images)); HIP_TRY(ctx, d_nf.upload(n_features, n_images, s));
-  HIP_TRY(ctx, d_fo.from(feat_off, s));
-  HIP_TRY(ctx, d_pair.alloc(2 * (size_t)n_pairs)); HIP_TRY(ctx, d_pair.upload(pair_img, 2 * (size_t)n_pairs, s));
-  HIP_TRY(ctx, d_moff.alloc((size_t)n_pairs + 1)); HIP_TRY(ctx, d_moff.upload(match_off, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d_match.alloc(2 * (size_t)M)); HIP_TRY(ctx, d_match.upload(matches, 2 * (size_t)M, s));
   msfm_track_dev D;
+  DevScope sc(ctx);
+  HIP_TRY(ctx, sc.up(d_nf, n_features, (size_t)n_images)); HIP_TRY(ctx, sc.up(d_fo, feat_off));
+  HIP_TRY(ctx, sc.up(d_pair, pair_img, 2 * (size_t)n_pairs)); HIP_TRY(ctx, sc.up(d_moff, match_off, (size_t)n_pairs + 1));
+  HIP_TRY(ctx, sc.up(d_match, matches, 2 * (size_t)M));
   MSFM_TRY(tracks_build_dev(ctx, n_images, feat_off, d_nf.p, d_fo.p, n_pairs, d_pair.p, d_moff.p, d_match.p, M, &D));
   S->off.resize((size_t)D.n_tracks + 1); S->img.resize(D.n_obs); S->feat.resize(D.n_obs);
-  HIP_TRY(ctx, hipMemcpyAsync(S->off.data(), D.off.p, sizeof(int) * ((size_t)D.n_tracks + 1), hipMemcpyDeviceToHost, s));
-  if (D.n_obs) {
-    HIP_TRY(ctx, hipMemcpyAsync(S->img.data(), D.img.p, sizeof(int) * (size_t)D.n_obs, hipMemcpyDeviceToHost, s));
-    HIP_TRY(ctx, hipMemcpyAsync(S->feat.data(), D.feat.p, sizeof(int) * (size_t)D.n_obs, hipMemcpyDeviceToHost, s));
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(S->off.data(), D.off.p, (size_t)D.n_tracks + 1));
+  HIP_TRY(ctx, sc.down(S->img.data(), D.img.p, (size_t)D.n_obs)); HIP_TRY(ctx, sc.down(S->feat.data(), D.feat.p, (size_t)D.n_obs));
+  HIP_TRY(ctx, sc.finish());
   *out = guard.release();
   return MSFM_OK;
 }

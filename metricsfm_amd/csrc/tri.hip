@@ -450,7 +450,7 @@ struct TrackDev {
   TrackPtrs ptrs;
 };
 
-static int upload_tracks(msfm_ctx* ctx, const msfm_tracks* T, TrackDev& D) {
+static int upload_tracks(msfm_ctx* ctx, const msfm_tracks* T, TrackDev& D, DevScope& sc) {   // (D lives in front of the caller's scope)
   if (!ctx || !T || T->n_tracks < 0 || T->n_cams <= 0 || !T->track_off || !T->cam_R || !T->cam_t || !T->cam_c || !T->cam_fk)
     return msfm_set_error(ctx, MSFM_E_INVAL, "tracks: null arrays");
   const int n = T->n_tracks;
@@ -459,14 +459,11 @@ static int upload_tracks(msfm_ctx* ctx, const msfm_tracks* T, TrackDev& D) {
   const int no = T->track_off[n];
   for (int i = 0; i < no; i++) if (T->track_cam[i] < 0 || T->track_cam[i] >= T->n_cams) return msfm_set_error(ctx, MSFM_E_INVAL, "track_cam[%d] out of range", i);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, D.off.alloc(n + 1)); HIP_TRY(ctx, D.off.upload(T->track_off, n + 1, s));
-  HIP_TRY(ctx, D.cam.alloc(std::max(1, no))); HIP_TRY(ctx, D.cam.upload(T->track_cam, no, s));
-  HIP_TRY(ctx, D.xy.alloc(std::max(1, 2 * no))); HIP_TRY(ctx, D.xy.upload(T->track_xy, 2 * (size_t)no, s));
-  HIP_TRY(ctx, D.R.alloc(9 * (size_t)T->n_cams)); HIP_TRY(ctx, D.R.upload(T->cam_R, 9 * (size_t)T->n_cams, s));
-  HIP_TRY(ctx, D.t.alloc(3 * (size_t)T->n_cams)); HIP_TRY(ctx, D.t.upload(T->cam_t, 3 * (size_t)T->n_cams, s));
-  HIP_TRY(ctx, D.c.alloc(3 * (size_t)T->n_cams)); HIP_TRY(ctx, D.c.upload(T->cam_c, 3 * (size_t)T->n_cams, s));
-  HIP_TRY(ctx, D.fk.alloc(3 * (size_t)T->n_cams)); HIP_TRY(ctx, D.fk.upload(T->cam_fk, 3 * (size_t)T->n_cams, s));
+  const size_t nc = (size_t)T->n_cams;
+  HIP_TRY(ctx, sc.up(D.off, T->track_off, (size_t)n + 1)); HIP_TRY(ctx, sc.up(D.cam, T->track_cam, (size_t)no));
+  HIP_TRY(ctx, sc.up(D.xy, T->track_xy, 2 * (size_t)no));
+  HIP_TRY(ctx, sc.up(D.R, T->cam_R, 9 * nc)); HIP_TRY(ctx, sc.up(D.t, T->cam_t, 3 * nc)); HIP_TRY(ctx, sc.up(D.c, T->cam_c, 3 * nc));
+  HIP_TRY(ctx, sc.up(D.fk, T->cam_fk, 3 * nc));
   D.ptrs = TrackPtrs{n, D.off.p, D.cam.p, D.xy.p, D.R.p, D.t.p, D.c.p, D.fk.p};
   return MSFM_OK;
 }
@@ -475,24 +472,23 @@ static int triangulate(msfm_ctx* ctx, const msfm_tracks* T, double th_error, dou
                        bool dlt) {
   if (!X || !mse || !ok) return MSFM_E_INVAL;
   TrackDev D;
-  MSFM_TRY(upload_tracks(ctx, T, D));
-  const int n = T->n_tracks;
-  if (n == 0) return MSFM_OK;
-  hipStream_t s = ctx->stream;
   DevBuf<double> dX, dm;
   DevBuf<uint8_t> dok;
-  HIP_TRY(ctx, dX.alloc(3 * (size_t)n)); HIP_TRY(ctx, dm.alloc(n)); HIP_TRY(ctx, dok.alloc(n));
-  HIP_TRY(ctx, dX.upload(X, 3 * (size_t)n, s));  // X is in/out: untouched on LLT failure
+  DevScope sc(ctx);
+  MSFM_TRY(upload_tracks(ctx, T, D, sc));
+  const int n = T->n_tracks;
+  if (n == 0) return MSFM_OK;   // (the scope waits for the uploads)
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, dm.alloc(n)); HIP_TRY(ctx, dok.alloc(n));
+  HIP_TRY(ctx, sc.up(dX, X, 3 * (size_t)n));  // X is in/out: untouched on LLT failure
   {
     KTimer t(ctx, dlt ? "tri_dlt" : "tri_midpoint");
     if (dlt) hipLaunchKernelGGL(k_tri_dlt, dim3(cdiv(n, 256)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
     else hipLaunchKernelGGL(k_tri_midpoint_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, th_error, cos(th_angle), dX.p, dm.p, dok.p);
   }
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(X, dX.p, sizeof(double) * 3 * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(mse, dm.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipMemcpyAsync(ok, dok.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(X, dX.p, 3 * (size_t)n)); HIP_TRY(ctx, sc.down(mse, dm.p, (size_t)n)); HIP_TRY(ctx, sc.down(ok, dok.p, (size_t)n));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -521,20 +517,21 @@ MSFM_API int msfm_triangulate_dlt_batch(msfm_ctx* ctx, const msfm_tracks* T, dou
 MSFM_API int msfm_reproject_mse_batch(msfm_ctx* ctx, const msfm_tracks* T, const double* X, double* mse) {
   if (!ctx || !X || !mse) return MSFM_E_INVAL;
   TrackDev D;
-  MSFM_TRY(upload_tracks(ctx, T, D));
-  const int n = T->n_tracks;
-  if (n == 0) return MSFM_OK;
-  hipStream_t s = ctx->stream;
   DevBuf<double> dX, dm;
-  HIP_TRY(ctx, dX.alloc(3 * (size_t)n)); HIP_TRY(ctx, dm.alloc(n));
-  HIP_TRY(ctx, dX.upload(X, 3 * (size_t)n, s));
+  DevScope sc(ctx);
+  MSFM_TRY(upload_tracks(ctx, T, D, sc));
+  const int n = T->n_tracks;
+  if (n == 0) return MSFM_OK;   // (the scope waits for the uploads)
+  hipStream_t s = ctx->stream;
+  HIP_TRY(ctx, dm.alloc(n));
+  HIP_TRY(ctx, sc.up(dX, X, 3 * (size_t)n));
   {
     KTimer t(ctx, "tri_reproject");
     hipLaunchKernelGGL(k_reproject_staged, dim3(cdiv(n, TRI_TPB)), dim3(256), 0, s, D.ptrs, dX.p, dm.p);
   }
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(mse, dm.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(mse, dm.p, (size_t)n));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
@@ -546,13 +543,13 @@ MSFM_API int msfm_epipolar_filter(msfm_ctx* ctx, const float* pt1, const float* 
   hipStream_t s = ctx->stream;
   DevBuf<float> d1, d2;
   DevBuf<uint8_t> di;
-  HIP_TRY(ctx, d1.alloc(2 * (size_t)n)); HIP_TRY(ctx, d2.alloc(2 * (size_t)n)); HIP_TRY(ctx, di.alloc(n));
-  HIP_TRY(ctx, d1.upload(pt1, 2 * (size_t)n, s)); HIP_TRY(ctx, d2.upload(pt2, 2 * (size_t)n, s));
+  DevScope sc(ctx);
+  HIP_TRY(ctx, sc.up(d1, pt1, 2 * (size_t)n)); HIP_TRY(ctx, sc.up(d2, pt2, 2 * (size_t)n)); HIP_TRY(ctx, di.alloc(n));
   F9 f;
   for (int k = 0; k < 9; k++) f.f[k] = F[k];
   hipLaunchKernelGGL(k_epipolar, dim3(cdiv(n, 256)), dim3(256), 0, s, d1.p, d2.p, n, f, th, di.p);
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(inlier, di.p, (size_t)n, hipMemcpyDeviceToHost, s));
-  HIP_TRY(ctx, hipStreamSynchronize(s));
+  HIP_TRY(ctx, sc.down(inlier, di.p, (size_t)n));
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
