@@ -1682,4 +1682,165 @@ void SLAMGPS::ReadinPriorInfo(const std::string& file, std::vector<std::vector<i
   }
 }
 
+// ---- SLAM + GPS registration (slam_gps.cc:98-119) ---------------------------------------------
+void Camera::Transformation(const Mat3& R, const Vec3& t, double scale) {
+  const double* A = R.m;
+  const double c00 = A[4] * A[8] - A[5] * A[7], c01 = A[5] * A[6] - A[3] * A[8], c02 = A[3] * A[7] - A[4] * A[6];
+  const double invdet = 1.0 / (A[0] * c00 + A[1] * c01 + A[2] * c02);
+  Mat3 Ri, Rn, sR;
+  Ri.m[0] = c00 * invdet; Ri.m[1] = (A[2] * A[7] - A[1] * A[8]) * invdet; Ri.m[2] = (A[1] * A[5] - A[2] * A[4]) * invdet;
+  Ri.m[3] = c01 * invdet; Ri.m[4] = (A[0] * A[8] - A[2] * A[6]) * invdet; Ri.m[5] = (A[2] * A[3] - A[0] * A[5]) * invdet;
+  Ri.m[6] = c02 * invdet; Ri.m[7] = (A[1] * A[6] - A[0] * A[7]) * invdet; Ri.m[8] = (A[0] * A[4] - A[1] * A[3]) * invdet;
+  for (int r = 0; r < 3; r++)
+    for (int c = 0; c < 3; c++) Rn(r, c) = pos_rt_.R(r, 0) * Ri(0, c) + pos_rt_.R(r, 1) * Ri(1, c) + pos_rt_.R(r, 2) * Ri(2, c);
+  pos_rt_.R = Rn;                                             // pos_rt_.R = pos_rt_.R * R.inverse()
+  for (int k = 0; k < 9; k++) sR.m[k] = scale * R.m[k];
+  const Vec3 rc = sR * pos_ac_.c;
+  for (int k = 0; k < 3; k++) pos_ac_.c[k] = rc[k] + t[k];    // pos_ac_.c = scale * R * pos_ac_.c + t
+  const Vec3 rt = pos_rt_.R * pos_ac_.c;
+  for (int k = 0; k < 3; k++) pos_rt_.t[k] = -rt[k];          // pos_rt_.t = -pos_rt_.R * pos_ac_.c
+  rotation::RotationMatrixToAngleAxis(pos_rt_.R, pos_ac_.a);
+  UpdateDataFromPose();
+}
+
+void SLAMGPS::AbsoluteOrientationWithGPSGlobal() {
+  const size_t n = cams_.size();
+  std::vector<double> R(9 * n), c(3 * n), g(3 * n), oR(9 * n), ot(3 * n), oc(3 * n), oa(3 * n), og(3 * n);
+  orient_weight_.assign(n, 0.0);
+  for (size_t i = 0; i < n; i++) {
+    for (int k = 0; k < 9; k++) R[9 * i + k] = cams_[i]->pos_rt_.R.m[k];
+    for (int k = 0; k < 3; k++) { c[3 * i + k] = cams_[i]->pos_ac_.c[k]; g[3 * i + k] = cams_gps_[i][k]; }
+  }
+  msfm_gps_orient_result out;
+  out.cam_R = oR.data(); out.cam_t = ot.data(); out.cam_c = oc.data(); out.cam_aa = oa.data(); out.gps = og.data(); out.weight = orient_weight_.data();
+  if (msfm_gps_orient_global((int)n, R.data(), c.data(), g.data(), nullptr, &out) != MSFM_OK)
+    throw std::runtime_error("AbsoluteOrientationWithGPSGlobal: fewer than 3 cameras");
+  for (size_t i = 0; i < n; i++) {
+    Camera* cm = cams_[i];
+    for (int k = 0; k < 9; k++) cm->pos_rt_.R.m[k] = oR[9 * i + k];
+    for (int k = 0; k < 3; k++) { cm->pos_rt_.t[k] = ot[3 * i + k]; cm->pos_ac_.c[k] = oc[3 * i + k]; cm->pos_ac_.a[k] = oa[3 * i + k]; cams_gps_[i][k] = og[3 * i + k]; }
+    cm->UpdateDataFromPose();
+  }
+  for (int k = 0; k < 9; k++) orient_R_.m[k] = out.Rg[k];
+  for (int k = 0; k < 3; k++) { orient_t_[k] = out.tg[k]; gps_offset_[k] = out.offset[k]; }
+  orient_scale_ = out.scale; orient_err_ = out.err;
+}
+
+namespace {
+// pts_ as CSR rows over cams_ (camera index = position in cams_), a point's observations in std::map order
+struct SlamFlat {
+  std::vector<int32_t> off, cam;
+  std::vector<double> xy, R, t, c, fk, dc, X;
+  std::vector<uint8_t> ok;
+  msfm_tracks tr;
+  SlamFlat(const std::vector<Camera*>& cams, const std::vector<Point3D*>& pts) {
+    std::map<const Camera*, int> index;
+    for (size_t i = 0; i < cams.size(); i++) {
+      index[cams[i]] = (int)i;
+      for (int k = 0; k < 9; k++) R.push_back(cams[i]->pos_rt_.R.m[k]);
+      for (int k = 0; k < 3; k++) { t.push_back(cams[i]->pos_rt_.t[k]); c.push_back(cams[i]->pos_ac_.c[k]); }
+      const CameraModel* m = cams[i]->cam_model_;
+      fk.push_back(m->f_); fk.push_back(m->k1_); fk.push_back(m->k2_);
+      dc.push_back(m->dcx_); dc.push_back(m->dcy_);
+    }
+    off.push_back(0);
+    for (const Point3D* p : pts) {
+      auto ip = p->pts2d_.begin();
+      for (auto ic = p->cams_.begin(); ic != p->cams_.end(); ++ic, ++ip) {
+        cam.push_back(index.at(ic->second));
+        xy.push_back(ip->second.x); xy.push_back(ip->second.y);
+      }
+      off.push_back((int32_t)cam.size());
+      for (int k = 0; k < 3; k++) X.push_back(p->data[k]);
+      ok.push_back(p->is_bad_estimated_ ? 0 : 1);
+    }
+    tr.n_tracks = (int)pts.size(); tr.n_cams = (int)cams.size();
+    tr.track_off = off.data(); tr.track_cam = cam.data(); tr.track_xy = xy.data();
+    tr.cam_R = R.data(); tr.cam_t = t.data(); tr.cam_c = c.data(); tr.cam_fk = fk.data();
+  }
+};
+}  // namespace
+
+void SLAMGPS::GetAccuracy() {
+  SlamFlat F(cams_, pts_);
+  const size_t n = pts_.size();
+  accuracy_errors_.assign(n, 0.0); accuracy_mse_.assign(n, 0.0); accuracy_n_obs_.assign(n, 0);
+  std::vector<uint8_t> ok(n);
+  int n_in = 0;
+  check(msfm_point_accuracy_batch(Context(), &F.tr, F.dc.data(), F.X.data(), F.ok.data(), 0, th_outlier_, accuracy_errors_.data(), accuracy_mse_.data(),
+                                  accuracy_n_obs_.data(), ok.data(), &count_outliers_, &n_in), "point_accuracy");
+  for (size_t i = 0; i < n; i++) if (!ok[i]) pts_[i]->is_bad_estimated_ = true;   // slam_gps.cc:1587-1590 (a bad point's error is 1000.0)
+}
+
+void SLAMGPS::GetAccuracyHost() {
+  const size_t n = pts_.size();
+  accuracy_errors_.assign(n, 1000.0); accuracy_mse_.assign(n, 0.0); accuracy_n_obs_.assign(n, 0);   // accuracy_accessment.cc:94
+  for (size_t i = 0; i < n; i++) {
+    Point3D* p = pts_[i];
+    if (p->is_bad_estimated_) continue;                                              // :95-97
+    std::vector<double> errors;
+    auto iter_pts = p->pts2d_.begin();
+    for (auto iter_cams = p->cams_.begin(); iter_cams != p->cams_.end(); ++iter_cams, ++iter_pts) {   // :45-61
+      const double* M = iter_cams->second->M;
+      const CameraModel* m = iter_cams->second->cam_model_;
+      const double pc0 = M[0] * p->data[0] + M[1] * p->data[1] + M[2] * p->data[2] + M[3];
+      const double pc1 = M[4] * p->data[0] + M[5] * p->data[1] + M[6] * p->data[2] + M[7];
+      const double pc2 = M[8] * p->data[0] + M[9] * p->data[1] + M[10] * p->data[2] + M[11];
+      if (pc2 > 0) {
+        const double x = pc0 / pc2, y = pc1 / pc2;
+        const double r2 = x * x + y * y;
+        const double distortion = 1.0 + r2 * (m->k1_ + m->k2_ * r2);
+        const double u = m->f_ * distortion * x + m->dcx_, v = m->f_ * distortion * y + m->dcy_;
+        const double du = u - iter_pts->second.x, dv = v - iter_pts->second.y;
+        errors.push_back(du * du + dv * dv);
+      }
+    }
+    if (errors.size() <= 1) continue;                                                // :64-66
+    double e_avg = 0.0, e_mse = 0.0;
+    for (size_t k = 0; k < errors.size(); k++) e_avg += errors[k];
+    e_avg /= errors.size();
+    for (size_t k = 0; k < errors.size(); k++) e_mse += (errors[k] - e_avg) * (errors[k] - e_avg);
+    e_mse = std::sqrt(e_mse / (errors.size() - 1));
+    accuracy_errors_[i] = e_avg; accuracy_mse_[i] = e_mse; accuracy_n_obs_[i] = (int)errors.size();
+  }
+  count_outliers_ = 0;
+  for (size_t i = 0; i < n; i++)                                                     // slam_gps.cc:1584-1592
+    if (accuracy_errors_[i] > th_outlier_) { pts_[i]->is_bad_estimated_ = true; count_outliers_++; }
+}
+
+void SLAMGPS::GPSRegistration2() {
+  SlamFlat F(cams_, pts_);
+  std::vector<double> g(3 * cams_.size());
+  for (size_t i = 0; i < cams_.size(); i++) for (int k = 0; k < 3; k++) g[3 * i + k] = cams_gps_[i][k];
+  check(msfm_gps_register_points(Context(), F.tr.n_tracks, F.off.data(), F.cam.data(), F.ok.data(), F.tr.n_cams, F.c.data(), g.data(), F.X.data()),
+        "gps_register_points");
+  for (size_t i = 0; i < pts_.size(); i++) for (int k = 0; k < 3; k++) pts_[i]->data[k] = F.X[3 * i + k];
+  for (size_t i = 0; i < cams_.size(); i++) cams_[i]->SetACPose(cams_[i]->pos_ac_.a, cams_gps_[i]);   // :980-982
+}
+
+void SLAMGPS::GPSRegistration2Host() {
+  std::vector<Vec3> cam_offset(cams_.size());                                        // :920-924
+  std::map<const Camera*, int> cams_info;
+  for (size_t i = 0; i < cams_.size(); i++) {
+    for (int k = 0; k < 3; k++) cam_offset[i][k] = cams_gps_[i][k] - cams_[i]->pos_ac_.c[k];
+    cams_info[cams_[i]] = (int)i;
+  }
+  for (size_t i = 0; i < pts_.size(); i++) {                                         // :933-978
+    Point3D* p = pts_[i];
+    if (p->is_bad_estimated_) continue;
+    double offset_i[3] = {0.0, 0.0, 0.0}, weight_i = 0.0;
+    for (auto it = p->cams_.begin(); it != p->cams_.end(); ++it) {
+      const int id_cam = cams_info.at(it->second);
+      const double dx = p->data[0] - cams_[id_cam]->pos_ac_.c(0), dy = p->data[1] - cams_[id_cam]->pos_ac_.c(1), dz = p->data[2] - cams_[id_cam]->pos_ac_.c(2);
+      const double dis = std::sqrt(dx * dx + dy * dy + dz * dz);
+      const double w = 1.0 / (std::sqrt(dis) + 5.0);
+      weight_i += w;
+      for (int k = 0; k < 3; k++) offset_i[k] += w * cam_offset[id_cam][k];
+    }
+    for (int k = 0; k < 3; k++) offset_i[k] /= weight_i;
+    for (int k = 0; k < 3; k++) p->data[k] += offset_i[k];
+  }
+  for (size_t i = 0; i < cams_.size(); i++) cams_[i]->SetACPose(cams_[i]->pos_ac_.a, cams_gps_[i]);
+}
+
 }  // namespace objectsfm

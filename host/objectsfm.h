@@ -81,6 +81,7 @@ class Camera {  // camera.h:34-85
   void AssociateCamereModel(CameraModel* cam_model) { cam_model_ = cam_model; }
   void SetRTPose(const Mat3& R, const Vec3& t);   // camera.cc:43-54
   void SetACPose(const Vec3& a, const Vec3& c);   // camera.cc:69-80
+  void Transformation(const Mat3& R, const Vec3& t, double scale);   // camera.cc:79-87 (R.inverse() by cofactors)
   void UpdateDataFromPose();                      // camera.cc:89-111
   void UpdatePoseFromData();                      // camera.cc:113-137
   void SetMutable(bool is_mutable) { is_mutable_ = is_mutable; }
@@ -302,6 +303,30 @@ class SLAMGPS {
   std::vector<CameraModel*> cam_models_;
   std::vector<Point3D*> pts_;
   std::vector<Vec3> cams_gps_;               // cv::Point3d cams_gps_ (slam_gps.h)
+  // The registration steps of Run (slam_gps.cc:98-119), each one library call on arrays gathered from cams_ / pts_ (a point's
+  // observations in std::map order, camera index = position in cams_) and written back:
+  //   AbsoluteOrientationWithGPSGlobal (:1596-1674) msfm_gps_orient_global: cams_ get R, t, c, a and data / M; cams_gps_ is
+  //                                    shifted; gps_offset_, orient_scale_, orient_err_, orient_weight_ are kept
+  //   GetAccuracy (:1573-1594)         msfm_point_accuracy_batch with ok_in = !is_bad_estimated_ (min_views 0: Triangulation
+  //                                    has flagged the short tracks, :643): accuracy_errors_ is `errors`, points above
+  //                                    th_outlier_ become is_bad_estimated_
+  //   GPSRegistration2 (:917-983)      msfm_gps_register_points on the non-bad points, then every camera onto its GPS
+  //                                    position with SetACPose
+  // The ...Host forms are the literal walks over the object graph, one point at a time.
+  void AbsoluteOrientationWithGPSGlobal();
+  void GetAccuracy();
+  void GetAccuracyHost();
+  void GPSRegistration2();
+  void GPSRegistration2Host();
+  Vec3 gps_offset_;
+  double th_outlier_ = 3.0;                  // slam_gps.cc:1587
+  double orient_scale_ = 0.0, orient_err_ = 0.0;
+  Mat3 orient_R_;
+  Vec3 orient_t_;
+  std::vector<double> orient_weight_;
+  std::vector<double> accuracy_errors_, accuracy_mse_;   // per point: e_avg (1000.0 where there is none), e_mse
+  std::vector<int> accuracy_n_obs_;
+  int count_outliers_ = 0;
   // slam_gps.h:135, set to 0.5 by SLAMGPS::SLAMGPS (slam_gps.cc:55): the SLAM observations are stored at full resolution,
   // (px - cx) / resize_ratio (:199), and step 1's pixel thresholds scale with it (:316-317)
   double resize_ratio = 0.5;

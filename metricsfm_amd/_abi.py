@@ -175,6 +175,18 @@ class ReconWinner(C.Structure):
                 ("f", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("avg_error", C.c_double)]
 
 
+class GpsregOptions(C.Structure):
+    """msfm_gpsreg_options (include/msfm.h)."""
+    _fields_ = [("window", C.c_int32), ("min_views", C.c_int32), ("clip_deg", C.c_double), ("th_outlier", C.c_double)]
+
+
+class GpsOrientResult(C.Structure):
+    """msfm_gps_orient_result (include/msfm.h)."""
+    _fields_ = [("cam_R", c_double_p), ("cam_t", c_double_p), ("cam_c", c_double_p), ("cam_aa", c_double_p), ("gps", c_double_p),
+                ("weight", c_double_p), ("Rg", C.c_double * 9), ("tg", C.c_double * 3), ("scale", C.c_double), ("err", C.c_double),
+                ("offset", C.c_double * 3)]
+
+
 class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 

@@ -23,6 +23,8 @@ SYMBOLS = [
     "msfm_chain_create", "msfm_chain_verify", "msfm_chain_matches", "msfm_chain_fetch_matches", "msfm_chain_build_tracks",
     "msfm_chain_fetch_tracks", "msfm_chain_triangulate", "msfm_chain_fetch_points", "msfm_chain_ba_create", "msfm_chain_fetch_point_tracks",
     "msfm_chain_destroy",
+    "msfm_gpsreg_default_options", "msfm_gps_orient_global", "msfm_point_accuracy_batch", "msfm_gps_register_points",
+    "msfm_chain_accuracy", "msfm_chain_fetch_accuracy", "msfm_chain_gps_register", "msfm_chain_ba_create_gps", "msfm_chain_store_points",
     "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
     "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
     "msfm_localize_pose_default_options", "msfm_localize_poses", "msfm_localize_pose_set_size", "msfm_localize_pose_set_fetch",
@@ -154,6 +156,18 @@ def lib():
     L.msfm_chain_fetch_point_tracks.argtypes = [vp, A.c_int_p]
     L.msfm_chain_destroy.argtypes = [vp]
     L.msfm_chain_destroy.restype = None
+    L.msfm_gpsreg_default_options.argtypes = [C.POINTER(A.GpsregOptions)]
+    L.msfm_gpsreg_default_options.restype = None
+    L.msfm_gps_orient_global.argtypes = [i, A.c_double_p, A.c_double_p, A.c_double_p, C.POINTER(A.GpsregOptions), C.POINTER(A.GpsOrientResult)]
+    L.msfm_point_accuracy_batch.argtypes = [vp, C.POINTER(A.Tracks), A.c_double_p, A.c_double_p, A.c_u8_p, i, d, A.c_double_p, A.c_double_p,
+                                            A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p]
+    L.msfm_gps_register_points.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_u8_p, i, A.c_double_p, A.c_double_p, A.c_double_p]
+    L.msfm_chain_accuracy.argtypes = [vp, i, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, i, d, A.c_int_p, A.c_int_p]
+    L.msfm_chain_fetch_accuracy.argtypes = [vp, A.c_double_p, A.c_double_p, A.c_int_p]
+    L.msfm_chain_gps_register.argtypes = [vp, i, A.c_double_p, A.c_double_p]
+    L.msfm_chain_ba_create_gps.argtypes = [vp, i, i, A.c_double_p, A.c_double_p, A.c_int_p, i, d, A.c_double_p, d, A.c_double_p, C.POINTER(vp),
+                                           A.c_int_p, A.c_int_p]
+    L.msfm_chain_store_points.argtypes = [vp, vp]
     L.msfm_match_store_create.argtypes = [vp, i, A.c_int_p, i, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(vp)]
     L.msfm_match_store_from_chain.argtypes = [vp, C.POINTER(vp)]
     L.msfm_match_store_destroy.argtypes = [vp]
@@ -308,6 +322,39 @@ def round_options(**kw):
 def epnpf_num_steps(**kw):
     """Candidate focal lengths of the sweep these options describe: (int)((f_ratio_max - f_ratio_min) / f_ratio_step), < 0 if invalid."""
     return lib().msfm_epnpf_num_steps(C.byref(epnpf_options(**kw)))
+
+
+def gpsreg_options(**kw):
+    """msfm_gpsreg_options with the reference's values (window 20, min_views 3, clip 80 degrees, th_outlier 3.0)."""
+    o = A.GpsregOptions()
+    lib().msfm_gpsreg_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise AttributeError(k)
+        setattr(o, k, v)
+    return o
+
+
+def gps_orient_global(cam_R, cam_c, gps, **opts):
+    """msfm_gps_orient_global (host only, no context): AbsoluteOrientationWithGPSGlobal, slam_gps.cc:1596-1674.  Returns a
+    dict: the transformed cameras cam_R / cam_t / cam_c / cam_aa, the shifted gps, weight, Rg, tg, scale, err, offset."""
+    R = A.as_c(np.asarray(cam_R, dtype=np.float64).reshape(-1, 9), np.float64)
+    c = A.as_c(np.asarray(cam_c, dtype=np.float64).reshape(-1, 3), np.float64)
+    g = A.as_c(np.asarray(gps, dtype=np.float64).reshape(-1, 3), np.float64)
+    n = len(c)
+    if len(R) != n or len(g) != n:
+        raise ValueError("gps_orient_global: cam_R, cam_c and gps must have one row per camera")
+    o = gpsreg_options(**opts)
+    out = dict(cam_R=np.zeros((n, 9)), cam_t=np.zeros((n, 3)), cam_c=np.zeros((n, 3)), cam_aa=np.zeros((n, 3)), gps=np.zeros((n, 3)),
+               weight=np.zeros(n))
+    r = A.GpsOrientResult()
+    for k, v in out.items():
+        setattr(r, k, A.ptr(v, A.c_double_p))
+    rc = lib().msfm_gps_orient_global(n, A.ptr(R, A.c_double_p), A.ptr(c, A.c_double_p), A.ptr(g, A.c_double_p), C.byref(o), C.byref(r))
+    if rc != 0:
+        raise MsfmError(rc, "msfm_gps_orient_global: invalid input (fewer than 3 cameras?)")
+    out.update(Rg=np.array(r.Rg).reshape(3, 3), tg=np.array(r.tg), scale=r.scale, err=r.err, offset=np.array(r.offset))
+    return out
 
 
 def _flatten_matches(n_features, pairs, matches_per_pair):
@@ -763,6 +810,27 @@ class Context:
                                                   A.ptr(mse, A.c_double_p)))
         return mse
 
+    def point_accuracy(self, tracks, X, ok_in, cam_dc=None, min_views=3, th_outlier=3.0):
+        """msfm_point_accuracy_batch (GetAccuracy, slam_gps.cc:1573-1594): e_avg, e_mse, n_used, ok_out, n_outliers, n_inliers."""
+        n = tracks.struct.n_tracks
+        X, ok_in, dc = A.as_c(X, np.float64), A.as_c(ok_in, np.uint8), A.as_c(cam_dc, np.float64)
+        e_avg, e_mse, n_used, ok = np.zeros(n), np.zeros(n), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        n_out, n_in = C.c_int32(), C.c_int32()
+        self.check(lib().msfm_point_accuracy_batch(self._h, C.byref(tracks.struct), A.ptr(dc, A.c_double_p), A.ptr(X, A.c_double_p),
+                                                   A.ptr(ok_in, A.c_u8_p), min_views, th_outlier, A.ptr(e_avg, A.c_double_p),
+                                                   A.ptr(e_mse, A.c_double_p), A.ptr(n_used, A.c_int_p), A.ptr(ok, A.c_u8_p),
+                                                   C.byref(n_out), C.byref(n_in)))
+        return e_avg, e_mse, n_used, ok, n_out.value, n_in.value
+
+    def gps_register_points(self, track_off, track_cam, ok, cam_c, gps, X):
+        """msfm_gps_register_points (the point loop of GPSRegistration2, slam_gps.cc:933-978): the shifted copy of X."""
+        off, cam, ok = A.as_c(track_off, np.int32), A.as_c(track_cam, np.int32), A.as_c(ok, np.uint8)
+        c, g = A.as_c(np.asarray(cam_c, dtype=np.float64).reshape(-1, 3), np.float64), A.as_c(np.asarray(gps, dtype=np.float64).reshape(-1, 3), np.float64)
+        X = np.array(X, dtype=np.float64, order="C")
+        self.check(lib().msfm_gps_register_points(self._h, len(off) - 1, A.ptr(off, A.c_int_p), A.ptr(cam, A.c_int_p), A.ptr(ok, A.c_u8_p), len(c),
+                                                  A.ptr(c, A.c_double_p), A.ptr(g, A.c_double_p), A.ptr(X, A.c_double_p)))
+        return X
+
     def epipolar_filter(self, pt1, pt2, F, th=3.0):
         pt1, pt2 = A.as_c(pt1, np.float32), A.as_c(pt2, np.float32)
         F = A.as_c(np.asarray(F, dtype=np.float64).reshape(9), np.float64)
@@ -1070,14 +1138,27 @@ class Chain:
         self.ctx.check(lib().msfm_chain_fetch_points(self._h, A.ptr(X, A.c_double_p), A.ptr(mse, A.c_double_p), A.ptr(ok, A.c_u8_p)))
         return X[:self.n_tracks], mse[:self.n_tracks], ok[:self.n_tracks]
 
-    def ba_create(self, cam_pose, cam_model, cam_model_of_cam, min_views=3, weight_ge3=1.0):
+    def ba_create(self, cam_pose, cam_model, cam_model_of_cam, min_views=3, weight_ge3=1.0, gps_xyz=None, gps_weight=0.0):
         """msfm_chain_ba_create: returns a BaResident on the accepted tracks (its `.arrays` hold only the camera side: the
-        points live on the device; `download()` returns them in `track_of_point` order)."""
+        points live on the device; `download()` returns them in `track_of_point` order).  With gps_xyz [n_cams][3]:
+        msfm_chain_ba_create_gps, the problem carries the GPS rows of slam_gps.cc:818-830; gps_weight <= 0 is the rule of
+        :824 and `gps_weight_used` of the result says what it gave."""
         cam_pose, cam_model = A.as_c(np.array(cam_pose, dtype=np.float64), np.float64), A.as_c(np.array(cam_model, dtype=np.float64), np.float64)
         moc = A.as_c(np.asarray(cam_model_of_cam, dtype=np.int32), np.int32)
         h, npt, nob = C.c_void_p(), C.c_int32(), C.c_int32()
-        self.ctx.check(lib().msfm_chain_ba_create(self._h, len(cam_pose), len(cam_model), A.ptr(cam_pose, A.c_double_p), A.ptr(cam_model, A.c_double_p),
-                                                  A.ptr(moc, A.c_int_p), min_views, weight_ge3, C.byref(h), C.byref(npt), C.byref(nob)))
+        used = None
+        if gps_xyz is None:
+            self.ctx.check(lib().msfm_chain_ba_create(self._h, len(cam_pose), len(cam_model), A.ptr(cam_pose, A.c_double_p), A.ptr(cam_model, A.c_double_p),
+                                                      A.ptr(moc, A.c_int_p), min_views, weight_ge3, C.byref(h), C.byref(npt), C.byref(nob)))
+        else:
+            g = A.as_c(np.asarray(gps_xyz, dtype=np.float64).reshape(-1, 3), np.float64)
+            if len(g) != len(cam_pose):
+                raise ValueError("ba_create: gps_xyz needs one row per camera")
+            w = C.c_double()
+            self.ctx.check(lib().msfm_chain_ba_create_gps(self._h, len(cam_pose), len(cam_model), A.ptr(cam_pose, A.c_double_p),
+                                                          A.ptr(cam_model, A.c_double_p), A.ptr(moc, A.c_int_p), min_views, weight_ge3,
+                                                          A.ptr(g, A.c_double_p), gps_weight, C.byref(w), C.byref(h), C.byref(npt), C.byref(nob)))
+            used = w.value
         top = np.zeros(npt.value, np.int32)
         self.ctx.check(lib().msfm_chain_fetch_point_tracks(self._h, A.ptr(top, A.c_int_p)))
 
@@ -1088,7 +1169,34 @@ class Chain:
         ba = BaResident.__new__(BaResident)
         ba.ctx, ba.arrays, ba._h = self.ctx, sh, h
         ba.track_of_point, ba.n_obs = top, nob.value
+        if used is not None:
+            ba.gps_weight_used = used
         return ba
+
+    def accuracy(self, R, t, fk, cam_dc=None, min_views=3, th_outlier=3.0):
+        """msfm_chain_accuracy (GetAccuracy): the resident ok becomes ok_out; returns (n_outliers, n_inliers)."""
+        R, t, fk, dc = (A.as_c(None if x is None else np.asarray(x, dtype=np.float64), np.float64) for x in (R, t, fk, cam_dc))
+        n_out, n_in = C.c_int32(), C.c_int32()
+        self.ctx.check(lib().msfm_chain_accuracy(self._h, len(t), A.ptr(R, A.c_double_p), A.ptr(t, A.c_double_p), A.ptr(fk, A.c_double_p),
+                                                 A.ptr(dc, A.c_double_p), min_views, th_outlier, C.byref(n_out), C.byref(n_in)))
+        return n_out.value, n_in.value
+
+    def fetch_accuracy(self):
+        n = max(1, self.n_tracks)
+        e_avg, e_mse, n_used = np.zeros(n), np.zeros(n), np.zeros(n, np.int32)
+        self.ctx.check(lib().msfm_chain_fetch_accuracy(self._h, A.ptr(e_avg, A.c_double_p), A.ptr(e_mse, A.c_double_p), A.ptr(n_used, A.c_int_p)))
+        return e_avg[:self.n_tracks], e_mse[:self.n_tracks], n_used[:self.n_tracks]
+
+    def gps_register(self, cam_c, gps):
+        """msfm_chain_gps_register: the point loop of GPSRegistration2 on the resident X."""
+        c, g = (A.as_c(np.asarray(x, dtype=np.float64).reshape(-1, 3), np.float64) for x in (cam_c, gps))
+        if len(c) != len(g):
+            raise ValueError("gps_register: cam_c and gps need one row per camera")
+        self.ctx.check(lib().msfm_chain_gps_register(self._h, len(c), A.ptr(c, A.c_double_p), A.ptr(g, A.c_double_p)))
+
+    def store_points(self, ba):
+        """msfm_chain_store_points: the adjusted points of `ba` (the BaResident this chain made last) back into the resident X."""
+        self.ctx.check(lib().msfm_chain_store_points(self._h, ba._h))
 
     def close(self):
         if self._h:

@@ -185,6 +185,11 @@ struct msfm_chain {
   // bundle adjustment
   int n_ba_points = 0, n_ba_obs = 0;
   DevBuf<int> track_of_point;
+  const msfm_ba* last_ba = nullptr;      // the problem track_of_point belongs to (msfm_chain_store_points takes no other)
+  // GetAccuracy (gpsreg.hip)
+  bool have_accuracy = false;
+  DevBuf<double> e_avg, e_mse;
+  DevBuf<int> n_used;
 };
 
 #define CH_TRY(e) HIP_TRY(ctx, (e))
@@ -416,8 +421,10 @@ MSFM_API int msfm_chain_fetch_points(msfm_chain* C, double* X, double* mse, uint
   return MSFM_OK;
 }
 
-MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, double* cam_pose, double* cam_model, const int32_t* cam_model_of_cam,
-                                  int min_views, double weight_ge3, msfm_ba** out, int* n_points, int* n_observations) {
+// msfm_chain_ba_create (gps_xyz == nullptr: no GPS rows) and msfm_chain_ba_create_gps
+static int chain_ba_create(msfm_chain* C, int n_cams, int n_models, double* cam_pose, double* cam_model, const int32_t* cam_model_of_cam, int min_views,
+                           double weight_ge3, const double* gps_xyz, double gps_weight, double* gps_weight_used, msfm_ba** out, int* n_points,
+                           int* n_observations) {
   if (!C || !out || !cam_pose || !cam_model || !cam_model_of_cam) return MSFM_E_INVAL;
   msfm_ctx* ctx = C->ctx;
   *out = nullptr;
@@ -457,11 +464,109 @@ MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, doubl
   P.n_cams = n_cams; P.n_models = n_models; P.n_points = np; P.n_obs = no;
   P.cam_pose = cam_pose; P.cam_model = cam_model; P.cam_model_of_cam = cam_model_of_cam;
   P.point = point.p; P.obs_cam = obs_cam.p; P.obs_pt = obs_pt.p; P.obs_xy = obs_xy.p; P.pt_weight = ptw.p;
+  if (gps_xyz) {   // the GPS rows of FullBundleAdjustment, slam_gps.cc:818-830; the weight of :824 is an integer division
+    P.gps_xyz = gps_xyz;
+    P.gps_weight = gps_weight > 0.0 ? gps_weight : (double)(no / n_cams);
+    if (gps_weight_used) *gps_weight_used = P.gps_weight;
+  }
+  C->last_ba = nullptr;   // (track_of_point has been rewritten)
   MSFM_TRY(ba_create_impl(ctx, &P, /*bulk_on_device=*/true, out));
   CH_TRY(sc.finish());
   C->n_ba_points = np; C->n_ba_obs = no;
+  C->last_ba = *out;
   if (n_points) *n_points = np;
   if (n_observations) *n_observations = no;
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_chain_ba_create(msfm_chain* C, int n_cams, int n_models, double* cam_pose, double* cam_model, const int32_t* cam_model_of_cam,
+                                  int min_views, double weight_ge3, msfm_ba** out, int* n_points, int* n_observations) {
+  return chain_ba_create(C, n_cams, n_models, cam_pose, cam_model, cam_model_of_cam, min_views, weight_ge3, nullptr, 0.0, nullptr, out, n_points,
+                         n_observations);
+}
+
+MSFM_API int msfm_chain_ba_create_gps(msfm_chain* C, int n_cams, int n_models, double* cam_pose, double* cam_model, const int32_t* cam_model_of_cam,
+                                      int min_views, double weight_ge3, const double* gps_xyz, double gps_weight, double* gps_weight_used,
+                                      msfm_ba** out, int* n_points, int* n_observations) {
+  if (!C) return MSFM_E_INVAL;
+  if (!gps_xyz || !(gps_weight == gps_weight)) return msfm_set_error(C->ctx, MSFM_E_INVAL, "msfm_chain_ba_create_gps: gps_xyz is null or gps_weight NaN");
+  return chain_ba_create(C, n_cams, n_models, cam_pose, cam_model, cam_model_of_cam, min_views, weight_ge3, gps_xyz, gps_weight, gps_weight_used, out,
+                         n_points, n_observations);
+}
+
+// ---- the SLAM + GPS registration steps on the resident tracks / xy / X / tok (kernels: gpsreg.hip) ----
+MSFM_API int msfm_chain_accuracy(msfm_chain* C, int n_cams, const double* cam_R, const double* cam_t, const double* cam_fk, const double* cam_dc,
+                                 int min_views, double th_outlier, int* n_outliers, int* n_inliers) {
+  if (!C || !cam_R || !cam_t || !cam_fk) return MSFM_E_INVAL;
+  msfm_ctx* ctx = C->ctx;
+  if (!C->triangulated) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_accuracy: msfm_chain_triangulate first");
+  if (n_cams < C->n_images) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_accuracy: %d cameras for %d images", n_cams, C->n_images);
+  if (!(th_outlier == th_outlier)) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_accuracy: th_outlier is NaN");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const msfm_track_dev& T = C->tracks;
+  const int nt = T.n_tracks;
+  DevBuf<double> dR, dt, dfk, ddc;
+  DevBuf<int> dcount;
+  DevScope sc(ctx);
+  CH_TRY(sc.up(dR, cam_R, 9 * (size_t)n_cams)); CH_TRY(sc.up(dt, cam_t, 3 * (size_t)n_cams)); CH_TRY(sc.up(dfk, cam_fk, 3 * (size_t)n_cams));
+  if (cam_dc) CH_TRY(sc.up(ddc, cam_dc, 2 * (size_t)n_cams));
+  CH_TRY(dcount.alloc(1));
+  if (!C->have_accuracy) {
+    CH_TRY(C->e_avg.alloc(std::max(1, nt))); CH_TRY(C->e_mse.alloc(std::max(1, nt))); CH_TRY(C->n_used.alloc(std::max(1, nt)));
+  }
+  const AccuracyPtrs P{nt, T.off.p, T.img.p, C->xy.p, dR.p, dt.p, dfk.p, cam_dc ? ddc.p : nullptr, C->X.p, C->tok.p, min_views, th_outlier,
+                       C->e_avg.p, C->e_mse.p, C->n_used.p, C->tok.p};
+  MSFM_TRY(gps_accuracy_dev(ctx, P, T.n_obs, dcount.p));
+  int outl = 0;
+  CH_TRY(sc.down(&outl, dcount.p, 1));
+  CH_TRY(sc.finish());
+  C->have_accuracy = true;
+  if (n_outliers) *n_outliers = outl;
+  if (n_inliers) *n_inliers = nt - outl;
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_chain_fetch_accuracy(msfm_chain* C, double* e_avg, double* e_mse, int32_t* n_used) {
+  if (!C) return MSFM_E_INVAL;
+  msfm_ctx* ctx = C->ctx;
+  if (!C->have_accuracy) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_fetch_accuracy: msfm_chain_accuracy first");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int nt = C->tracks.n_tracks;
+  if (nt) {
+    if (e_avg) CH_TRY(hipMemcpyAsync(e_avg, C->e_avg.p, sizeof(double) * (size_t)nt, hipMemcpyDeviceToHost, s));
+    if (e_mse) CH_TRY(hipMemcpyAsync(e_mse, C->e_mse.p, sizeof(double) * (size_t)nt, hipMemcpyDeviceToHost, s));
+    if (n_used) CH_TRY(hipMemcpyAsync(n_used, C->n_used.p, sizeof(int32_t) * (size_t)nt, hipMemcpyDeviceToHost, s));
+  }
+  CH_TRY(hipStreamSynchronize(s));
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_chain_gps_register(msfm_chain* C, int n_cams, const double* cam_c, const double* gps) {
+  if (!C || !cam_c || !gps) return MSFM_E_INVAL;
+  msfm_ctx* ctx = C->ctx;
+  if (!C->triangulated) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_gps_register: msfm_chain_triangulate first");
+  if (n_cams < C->n_images) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_gps_register: %d cameras for %d images", n_cams, C->n_images);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const msfm_track_dev& T = C->tracks;
+  const std::vector<double> offs = gps_cam_offsets(n_cams, cam_c, gps);
+  DevBuf<double> dc, doff;
+  DevScope sc(ctx);
+  CH_TRY(sc.up(dc, cam_c, 3 * (size_t)n_cams)); CH_TRY(sc.up(doff, offs));
+  const RegisterPtrs P{T.n_tracks, T.off.p, T.img.p, C->tok.p, dc.p, doff.p, C->X.p};
+  MSFM_TRY(gps_register_dev(ctx, P));
+  CH_TRY(sc.finish());
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_chain_store_points(msfm_chain* C, msfm_ba* ba) {
+  if (!C || !ba) return MSFM_E_INVAL;
+  msfm_ctx* ctx = C->ctx;
+  if (ba != C->last_ba || C->n_ba_points == 0)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_store_points: not the problem this chain made last");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  MSFM_TRY(gps_store_points_dev(ctx, C->n_ba_points, C->track_of_point.p, ba_device_points(ba), C->X.p));
+  CH_TRY(hipStreamSynchronize(ctx->stream));
   return MSFM_OK;
 }
 

@@ -370,6 +370,30 @@ struct TrackPtrs {   // tri.hip: CSR tracks + cameras as the reference keeps the
   const double *xy, *R, *t, *c, *fk;
 };
 int tri_midpoint_dev(msfm_ctx* ctx, const TrackPtrs& T, double th_error, double th_angle, double* dX, double* dmse, uint8_t* dok);
+// ---- registering the SLAM model on its GPS track (gpsreg.hip): device-array cores, no synchronisation ----
+struct AccuracyPtrs {   // GetAccuracy on CSR tracks; dc [n_cams][2] or nullptr = 0; the last four are written
+  int n_tracks;
+  const int *off, *cam;
+  const double *xy, *R, *t, *fk, *dc, *X;
+  const uint8_t* ok_in;
+  int min_views;
+  double th_outlier;
+  double *e_avg, *e_mse;
+  int* n_used;
+  uint8_t* ok_out;   // may be ok_in: a track's flag is read and written by one thread
+};
+struct RegisterPtrs {   // the point loop of GPSRegistration2; cam_offset [n_cams][3] = gps - cam_c; X in / out
+  int n_tracks;
+  const int *off, *cam;
+  const uint8_t* ok;
+  const double *cam_c, *cam_offset;
+  double* X;
+};
+int gps_accuracy_dev(msfm_ctx* ctx, const AccuracyPtrs& P, int n_rows, int* d_n_outliers);
+int gps_register_dev(msfm_ctx* ctx, const RegisterPtrs& P);
+int gps_store_points_dev(msfm_ctx* ctx, int n_points, const int* d_track_of_point, const double* d_point, double* dX);
+std::vector<double> gps_cam_offsets(int n_cams, const double* cam_c, const double* gps);
+
 struct msfm_ba_problem;
 struct msfm_ba;
 // msfm_ba_create with the bulk arrays of the problem (obs_cam, obs_pt, obs_xy, point, pt_weight, pt_mutable) in DEVICE memory
