@@ -302,7 +302,12 @@ typedef struct msfm_ba_layout {
    * than MSFM_LANES4_MIN eliminated points, default 24 576; in a smaller problem they are 8-lane points in the common order) */
   int npb_S, npb_L, npb_X;
   int npb_S4;
+  /* how the last reduced system of msfm_ba_run was assembled (0 before the first one): MSFM_PATH_ASM_BESIDE = the fold partials
+   * were summed into the system by workgroups of the per-camera sums' launch and the blocks finished by the launches that
+   * form the per-camera and per-intrinsics sums; 0 = by a launch of its own behind them */
+  int assemble_paths;
 } msfm_ba_layout;
+#define MSFM_PATH_ASM_BESIDE 1
 #define MSFM_PATH_LEVEL_CHAIN(l) (1 << (l))
 #define MSFM_PATH_ROOT_CHAIN (1 << 3)
 #define MSFM_PATH_BACKSOLVE_CHAIN (1 << 4)

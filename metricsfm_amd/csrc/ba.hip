@@ -244,12 +244,12 @@ __global__ __launch_bounds__(256) void k_gps(int ncb, const int* __restrict__ cb
 
 // Sum (or max) `n` partials in a fixed order into scal[slot]: one workgroup of 1024 threads, each
 // thread a fixed strided subset (independent loads in flight), then a fixed wave / block tree.
-// Up to four independent reductions of per-workgroup partials in one launch (block b = job b), each in the fixed order
+// Up to six independent reductions of per-workgroup partials in one launch (block b = job b), each in the fixed order
 // of the single-job form; block 0 can also publish the failure flag.  One launch instead of one per scalar: every tiny
 // dependent launch costs ~4.5 us on the LM iteration's critical path.
 struct ReduceJobs {
   int count;
-  struct { const double* p; int n; int slot; int is_max; } job[4];
+  struct { const double* p; int n; int slot; int is_max; } job[6];
   const int* fail;
   int fail_slot;
 };
@@ -872,13 +872,33 @@ __global__ __launch_bounds__(256) void k_ftf(int nchunk, const int* __restrict__
 
 // Sum the FTF partials of each camera block (fixed order) -> camftf[cb][PSTRIDE]; the GPS rows
 // are folded in by the lead rank only (the buffer is summed over ranks afterwards).
+// fin.M set (one rank, the fold-sum workgroups of k_sums have stored -sum of the fold partials into every block of M): the
+// camera's blocks are finished here, where its sums are at hand - the diagonal block (+ Jc^T Jc + damping), its intrinsics x
+// camera block (+ Jm^T Jc) and its six entries of the rhs row, each entry by the operations, in the order, of asm_cc / asm_mc /
+// asm_rhs_cam; the workgroups behind the last camera write the identity of the padding columns.
+struct CamFinish {
+  double* M; int ld, n, mo;
+  const int *cb_off, *cb_mb;
+  double radius;
+  int n_padcol; const int* padcol;
+};
+__device__ __forceinline__ void cc_diag_finish(double& v0, double& v1, double f0, double f1, int a, int c, const double* __restrict__ diag_c6, double radius) {
+  v0 += f0; v1 += f1;
+  if (a == c) { const double q = sqrt(diag_c6[a] / radius); v0 += q * q; }
+  if (a == c + 1) { const double q = sqrt(diag_c6[a] / radius); v1 += q * q; }
+}
 __global__ __launch_bounds__(128) void k_camftf(int ncb, const int* __restrict__ cam_chunk_first,
                                                  const double* __restrict__ partial, double* __restrict__ camftf,
                                                  const double* __restrict__ g_r, const double* __restrict__ g_J, int add_gps, int post,
                                                  double* __restrict__ diag_c, const double* __restrict__ scale_c, int reuse_diag, int mode,
-                                                 double dmin, double dmax, double* __restrict__ gmax_c) {
+                                                 double dmin, double dmax, double* __restrict__ gmax_c, CamFinish fin) {
   __shared__ double sums[PSTRIDE];
   const int cb = blockIdx.x, t = threadIdx.x;
+  if (cb >= ncb) {   // (only with fin.M) identity on the padding columns
+    const int i = (cb - ncb) * 128 + t;
+    if (i < fin.n_padcol) fin.M[(size_t)fin.padcol[i] * fin.ld + fin.padcol[i]] = 1.0;
+    return;
+  }
   if (t < PSTRIDE) {
     double s = 0.0;
     int ch = cam_chunk_first[cb];
@@ -910,6 +930,22 @@ __global__ __launch_bounds__(128) void k_camftf(int ncb, const int* __restrict__
     else if (!reuse_diag) diag_c[i] = fmin(fmax(d, dmin), dmax);
     gmax_c[i] = fabs(sums[F_JCR + t] / scale_c[i]);
   }
+  if (!fin.M) return;
+  __syncthreads();   // (the camera's LM diagonal, written above unless it is reused)
+  const int off = fin.cb_off[cb];
+  if (t < 18) {
+    const int e = 2 * t, a = e / 6, c = e % 6;
+    double2* at = reinterpret_cast<double2*>(&fin.M[(size_t)(off + a) * fin.ld + off + c]);
+    double2 v = *at;
+    cc_diag_finish(v.x, v.y, sums[F_JCJC + e], sums[F_JCJC + e + 1], a, c, diag_c + 6 * (size_t)cb, fin.radius);
+    *at = v;
+  } else if (t >= 32 && t < 50) {
+    const int e = t - 32, mb = fin.cb_mb[cb];
+    if (mb >= 0) fin.M[(size_t)(fin.mo + 3 * mb + e / 6) * fin.ld + off + e % 6] += sums[F_JMJC + e];
+  } else if (t >= 64 && t < 70) {
+    const int a = t - 64;
+    fin.M[(size_t)fin.n * fin.ld + off + a] = sums[F_JCR + a] - sums[F_TU + a];
+  }
 }
 
 // From the (globally summed) camftf: LM diagonal / raw column norms of the camera columns and
@@ -929,11 +965,45 @@ __global__ void k_cam_post(int ncb, const double* __restrict__ camftf, double* _
 
 // Per intrinsics block: sum camftf(Jm^T Jm | Jm^T r) over its cameras (one wave, lanes strided,
 // fixed butterfly) -> modelsum[mb][12]; LM diagonal / raw norms; gradient.
-__global__ __launch_bounds__(64) void k_modelsum(const int* __restrict__ mcam_first, const int* __restrict__ mcam,
+// fin.M set (see CamFinish; one intrinsics block at most, so its diagonal block is the only intrinsics x intrinsics block): the
+// launch has a second wave, which sums the block's chunk partials (written by the launch before) beside the model sum; the
+// first wave then assembles the block and its rhs entries from both, as asm_mm does.
+struct ModelFinish {
+  double* M; int ld, n, mo, n_mm;
+  const int *mm_row, *mm_col, *mm_first; const double* mm_partial;
+  double radius;
+};
+__device__ __forceinline__ void mm_chunk_sums(int b, const int* __restrict__ blk_chunk_first, const double* __restrict__ partial, int lane, double (&acc)[12]);
+__device__ __forceinline__ void mm_finish(int mb, int lane, const ModelFinish& f, const double* mmacc, const double* __restrict__ modelsum, const double* __restrict__ diag_m) {
+  if (lane < 9) {
+    const int a = lane / 3, c = lane % 3;
+    double v = -mmacc[lane];
+    v += modelsum[12 * (size_t)mb + lane];
+    if (a == c) { const double q = sqrt(diag_m[3 * mb + a] / f.radius); v += q * q; }
+    f.M[(size_t)(f.mo + 3 * mb + a) * f.ld + f.mo + 3 * mb + c] = v;
+  } else if (lane < 12) {
+    f.M[(size_t)f.n * f.ld + f.mo + 3 * mb + lane - 9] = modelsum[12 * (size_t)mb + lane] - mmacc[lane];
+  }
+}
+__global__ __launch_bounds__(128) void k_modelsum(const int* __restrict__ mcam_first, const int* __restrict__ mcam,
                                                   const double* __restrict__ camftf, double* __restrict__ modelsum,
                                                   double* __restrict__ diag_m, const double* __restrict__ scale_m, int reuse_diag,
-                                                  int mode, double dmin, double dmax, double* __restrict__ gmax_m) {
-  const int mb = blockIdx.x, lane = threadIdx.x;
+                                                  int mode, double dmin, double dmax, double* __restrict__ gmax_m, ModelFinish fin) {
+  __shared__ double mmacc[13];   // the second wave's sums; [12]: the block is in the list
+  const int mb = blockIdx.x, lane = threadIdx.x & 63;
+  if (threadIdx.x >= 64) {   // (only with fin.M)
+    int blk = -1;
+    for (int b = 0; b < fin.n_mm; b++) if (fin.mm_row[b] == mb && fin.mm_col[b] == mb) blk = b;
+    if (blk >= 0) {
+      double a12[12];
+      mm_chunk_sums(blk, fin.mm_first, fin.mm_partial, lane, a12);
+#pragma unroll
+      for (int k = 0; k < 12; k++) if (k == lane) mmacc[k] = a12[k];
+    }
+    if (lane == 0) mmacc[12] = blk >= 0 ? 1.0 : 0.0;
+    __syncthreads();
+    return;
+  }
   double acc[12];
 #pragma unroll
   for (int k = 0; k < 12; k++) acc[k] = 0.0;
@@ -969,6 +1039,9 @@ __global__ __launch_bounds__(64) void k_modelsum(const int* __restrict__ mcam_fi
       gmax_m[3 * mb + a] = fabs(acc[9 + a] / scale_m[3 * mb + a]);
     }
   }
+  if (!fin.M) return;
+  __syncthreads();   // (the second wave's sums; modelsum and diag_m of this block, written by lane 0 above, are read back by the other lanes)
+  if (mmacc[12] != 0.0) mm_finish(mb, lane, fin, mmacc, modelsum, diag_m);
 }
 
 // jacobian_scaling = 1 / (1 + sqrt(squared column norm))  (Ceres, iteration 0)
@@ -1092,8 +1165,25 @@ __global__ __launch_bounds__(256) void k_zero_system(double* __restrict__ M, int
 // kernel trace) and three 19 us launches for next to no work.  Here they are ONE launch on the main stream: the residue and
 // the zero tiles are its first workgroups and finish in the shadow of the camera chunks.  Same arithmetic per chunk, so the
 // partials - and the solve - are bit-identical to the separate launches (MSFM_FUSED_SUMS=0).
+// (MSFM_ASM_BESIDE) When every camera x camera and intrinsics x camera entry is folded, the sum of a block's fold partials needs
+// k_point alone, and only the last additions of a camera's diagonal block, of its intrinsics x camera block and the rhs need the
+// per-camera sums: the fold-sum workgroups below store -sum into M beside the camera chunks (a latency-bound gather next to
+// an issue-bound FP64 pass), k_camftf / k_modelsum finish the blocks (CamFinish), and k_asm_all has nothing left.  The
+// launch has two waves per SIMD, so a wave keeps more loads in flight than k_asm_all's: each of its three 18-lane groups takes a
+// block of its own and asks for the whole list at once when the three lists are short (up to sixteen partials: every
+// off-diagonal block but a few), and sums them in the order the three groups of asm_cc would have; longer lists are shared
+// by the three groups as there.  The zero fill cannot share a launch with these stores: it moves behind the solve (k_tail).
+struct FoldSumArgs {
+  int n_mc_wg, n_cc_wg;   // workgroups, in this order
+  int n_cc, n_mc, mo;
+  const int *cc_row, *cc_col, *cc_range, *mc_row, *mc_col, *mc_range, *cb_off;
+  const double *cc_fold_partial, *mc_fold_partial;
+};
+__device__ __forceinline__ void fold_sum_cc(int wave_task, int lane, const FoldSumArgs& f, double* __restrict__ M, int ld);
+__device__ __forceinline__ void fold_sum_mc(int b, int lane, const FoldSumArgs& f, double* __restrict__ M, int ld);
 struct SumsArgs {
   int n_zero, n_mc_wg, n_mm_wg, n_cc_wg, n_ftf_wg;   // workgroups of each part, in this order
+  FoldSumArgs fs;   // (behind the pair lists' workgroups, in front of the camera chunks; n_zero is 0 with them)
   // zero fill
   double* M; int ld; ZeroMap Z;
   // pair lists: intrinsics x camera (live chunks), intrinsics x intrinsics (all), camera x camera (live chunks)
@@ -1122,7 +1212,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     return;
   }
   b -= a.n_cc_wg;
+  if (b < a.fs.n_mc_wg) {
+    const int blk = 4 * b + ((int)threadIdx.x >> 6);
+    if (blk < a.fs.n_mc) fold_sum_mc(blk, (int)threadIdx.x & 63, a.fs, a.M, a.ld);
+    return;
+  }
+  b -= a.fs.n_mc_wg;
+  if (b < a.fs.n_cc_wg) { fold_sum_cc(4 * b + ((int)threadIdx.x >> 6), (int)threadIdx.x & 63, a.fs, a.M, a.ld); return; }
+  b -= a.fs.n_cc_wg;
   ftf_body(b, a.f_n, a.f_start, a.f_end, a.P, a.R, a.Tu, a.cpos_pb, a.f_partial);
+}
+
+// The sum of a block's fold partials f0 .. f1 - 1 as the three 18-lane groups of a wave form it together: group `sub` takes the
+// partials sub, sub + 3, ... in four running sums (its partials 0, 1, 2, 3 mod 4), sixteen loads in flight per round, combined in
+// a fixed order; groups 1 and 2 hand their sums to group 0, which adds the total to s0 / s1 (entries t, t + 1 of the block).
+// Every lane of the wave takes part in the exchange (groups beyond the third come with f1 = 0).
+__device__ __forceinline__ void cc_fold_shared(int f0, int f1, int sub, int t, int lane, const double* __restrict__ fold_partial, double& s0, double& s1) {
+  double2 q0 = make_double2(0.0, 0.0), q1 = q0, q2 = q0, q3 = q0;
+  const double2* fp = reinterpret_cast<const double2*>(fold_partial + t);
+  int sl = f0 + sub;
+  for (; sl + 45 < f1; sl += 48) {
+    double2 v[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) v[j] = fp[(size_t)(sl + 3 * j) * 18];
+#pragma unroll
+    for (int j = 0; j < 16; j += 4) {
+      q0.x += v[j].x; q0.y += v[j].y; q1.x += v[j + 1].x; q1.y += v[j + 1].y;
+      q2.x += v[j + 2].x; q2.y += v[j + 2].y; q3.x += v[j + 3].x; q3.y += v[j + 3].y;
+    }
+  }
+  for (; sl + 9 < f1; sl += 12) {
+    const double2 v0 = fp[(size_t)sl * 18], v1 = fp[(size_t)(sl + 3) * 18], v2 = fp[(size_t)(sl + 6) * 18], v3 = fp[(size_t)(sl + 9) * 18];
+    q0.x += v0.x; q0.y += v0.y; q1.x += v1.x; q1.y += v1.y; q2.x += v2.x; q2.y += v2.y; q3.x += v3.x; q3.y += v3.y;
+  }
+  for (; sl < f1; sl += 3) { const double2 v = fp[(size_t)sl * 18]; q0.x += v.x; q0.y += v.y; }
+  const double g0 = (q0.x + q1.x) + (q2.x + q3.x), g1 = (q0.y + q1.y) + (q2.y + q3.y);
+  const double a0 = __shfl(g0, lane + 18), a1 = __shfl(g1, lane + 18);
+  const double b0 = __shfl(g0, lane + 36), b1 = __shfl(g1, lane + 36);
+  s0 += (g0 + a0) + b0;
+  s1 += (g1 + a1) + b1;
+}
+// the same for one entry per lane (the 3 x 6 partials of the intrinsics x camera blocks)
+__device__ __forceinline__ void mc_fold_shared(int f0, int f1, int sub, int t, int lane, const double* __restrict__ fold_partial, double& s) {
+  double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+  int sl = f0 + sub;
+  for (; sl + 45 < f1; sl += 48) {
+    double v[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) v[j] = fold_partial[(size_t)(sl + 3 * j) * 18 + t];
+#pragma unroll
+    for (int j = 0; j < 16; j += 4) { q0 += v[j]; q1 += v[j + 1]; q2 += v[j + 2]; q3 += v[j + 3]; }
+  }
+  for (; sl + 9 < f1; sl += 12) {
+    const double v0 = fold_partial[(size_t)sl * 18 + t], v1 = fold_partial[(size_t)(sl + 3) * 18 + t];
+    const double v2 = fold_partial[(size_t)(sl + 6) * 18 + t], v3 = fold_partial[(size_t)(sl + 9) * 18 + t];
+    q0 += v0; q1 += v1; q2 += v2; q3 += v3;
+  }
+  for (; sl < f1; sl += 3) q0 += fold_partial[(size_t)sl * 18 + t];
+  const double g = (q0 + q1) + (q2 + q3);
+  const double ga = __shfl(g, lane + 18), gb = __shfl(g, lane + 36);
+  s += (g + ga) + gb;
 }
 
 // camera-camera blocks: one block per 64-thread workgroup; 18 threads hold two neighbouring entries of a row each (16-byte
@@ -1147,42 +1296,15 @@ __device__ __forceinline__ void asm_cc(int b, int sub, int t2, const int* __rest
       s0 += v.x; s1 += v.y;
     }
   if (blk_fold_range) {   // the products formed inside k_point: one partial per (workgroup, block), in workgroup order
-    // four running sums per group (its partials 0, 1, 2, 3 mod 4), sixteen loads in flight per round, combined in a fixed order
-    double2 q0 = make_double2(0.0, 0.0), q1 = q0, q2 = q0, q3 = q0;
     const int f0 = blk_fold_range[2 * b], f1 = sub < 3 ? blk_fold_range[2 * b + 1] : 0;
-    const double2* fp = reinterpret_cast<const double2*>(fold_partial + t);
-    int sl = f0 + sub;
-    for (; sl + 45 < f1; sl += 48) {
-      double2 v[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) v[j] = fp[(size_t)(sl + 3 * j) * 18];
-#pragma unroll
-      for (int j = 0; j < 16; j += 4) {
-        q0.x += v[j].x; q0.y += v[j].y; q1.x += v[j + 1].x; q1.y += v[j + 1].y;
-        q2.x += v[j + 2].x; q2.y += v[j + 2].y; q3.x += v[j + 3].x; q3.y += v[j + 3].y;
-      }
-    }
-    for (; sl + 9 < f1; sl += 12) {
-      const double2 v0 = fp[(size_t)sl * 18], v1 = fp[(size_t)(sl + 3) * 18], v2 = fp[(size_t)(sl + 6) * 18], v3 = fp[(size_t)(sl + 9) * 18];
-      q0.x += v0.x; q0.y += v0.y; q1.x += v1.x; q1.y += v1.y; q2.x += v2.x; q2.y += v2.y; q3.x += v3.x; q3.y += v3.y;
-    }
-    for (; sl < f1; sl += 3) { const double2 v = fp[(size_t)sl * 18]; q0.x += v.x; q0.y += v.y; }
-    const double g0 = (q0.x + q1.x) + (q2.x + q3.x), g1 = (q0.y + q1.y) + (q2.y + q3.y);
-    // groups 1 and 2 hand their sums to group 0 (every lane of the wave takes part in the exchange)
-    const int lane = (int)threadIdx.x;
-    const double a0 = __shfl(g0, lane + 18), a1 = __shfl(g1, lane + 18);
-    const double b0 = __shfl(g0, lane + 36), b1 = __shfl(g1, lane + 36);
-    s0 += (g0 + a0) + b0;
-    s1 += (g1 + a1) + b1;
+    cc_fold_shared(f0, f1, sub, t, (int)threadIdx.x & 63, fold_partial, s0, s1);
   }
   if (sub != 0) return;
   double v0 = -s0, v1 = -s1;
   const int a = t / 6, c = t % 6;
   if (rb == cbk && lead) {
     const double2 f = *reinterpret_cast<const double2*>(camftf + (size_t)rb * PSTRIDE + F_JCJC + t);
-    v0 += f.x; v1 += f.y;
-    if (a == c) { const double q = sqrt(diag_c[6 * rb + a] / radius); v0 += q * q; }
-    if (a == c + 1) { const double q = sqrt(diag_c[6 * rb + a] / radius); v1 += q * q; }
+    cc_diag_finish(v0, v1, f.x, f.y, a, c, diag_c + 6 * (size_t)rb, radius);
   }
   *reinterpret_cast<double2*>(&M[(size_t)(cb_off[rb] + a) * ld + cb_off[cbk] + c]) = make_double2(v0, v1);
 }
@@ -1200,25 +1322,8 @@ __device__ __forceinline__ void asm_mc(int b, const int* __restrict__ blk_row, c
   if (sub == 0 && blk_chunk_first)
     for (int ch = blk_chunk_first[b]; ch < blk_chunk_first[b + 1]; ch++) s += partial[(size_t)ch * 18 + t];
   if (fold_range) {   // the products formed inside k_point: one partial per (workgroup, camera), in workgroup order
-    double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
     const int f0 = fold_range[2 * b], f1 = sub < 3 ? fold_range[2 * b + 1] : 0;
-    int sl = f0 + sub;
-    for (; sl + 45 < f1; sl += 48) {
-      double v[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) v[j] = fold_partial[(size_t)(sl + 3 * j) * 18 + t];
-#pragma unroll
-      for (int j = 0; j < 16; j += 4) { q0 += v[j]; q1 += v[j + 1]; q2 += v[j + 2]; q3 += v[j + 3]; }
-    }
-    for (; sl + 9 < f1; sl += 12) {
-      const double v0 = fold_partial[(size_t)sl * 18 + t], v1 = fold_partial[(size_t)(sl + 3) * 18 + t];
-      const double v2 = fold_partial[(size_t)(sl + 6) * 18 + t], v3 = fold_partial[(size_t)(sl + 9) * 18 + t];
-      q0 += v0; q1 += v1; q2 += v2; q3 += v3;
-    }
-    for (; sl < f1; sl += 3) q0 += fold_partial[(size_t)sl * 18 + t];
-    const double g = (q0 + q1) + (q2 + q3);
-    const double ga = __shfl(g, lane + 18), gb = __shfl(g, lane + 36);
-    s += (g + ga) + gb;
+    mc_fold_shared(f0, f1, sub, t, lane, fold_partial, s);
   }
   if (sub != 0) return;
   double v = -s;
@@ -1227,8 +1332,93 @@ __device__ __forceinline__ void asm_mc(int b, const int* __restrict__ blk_row, c
   M[(size_t)(mo + 3 * mb + a) * ld + cb_off[cb] + c] = v;
 }
 
+// The fold-sum workgroups of k_sums (FoldSumArgs): -sum of the fold partials into M, nothing else.
+// wave_task: the camera x camera blocks 3 * wave_task .. + 2, one per 18-lane group when their lists are short.
+__device__ __forceinline__ void fold_sum_cc(int wave_task, int lane, const FoldSumArgs& f, double* __restrict__ M, int ld) {
+  const int sub = lane / 18, t2 = lane - 18 * sub, t = 2 * t2;
+  const int b = 3 * wave_task + sub;
+  const bool mine = sub < 3 && b < f.n_cc;
+  int f0 = 0, f1 = 0, rb = 0, cbk = 0;
+  if (mine) { f0 = f.cc_range[2 * b]; f1 = f.cc_range[2 * b + 1]; rb = f.cc_row[b]; cbk = f.cc_col[b]; }
+  double s0 = 0.0, s1 = 0.0;
+  if (__builtin_amdgcn_ballot_w64(f1 - f0 > 16) == 0ull) {
+    // every list short: the group asks for its whole list at once and sums it as three groups sharing it would have
+    const int n = f1 - f0;
+    const double2* fp = reinterpret_cast<const double2*>(f.cc_fold_partial + t) + (size_t)f0 * 18;
+    double2 v[16];
+#pragma unroll
+    for (int j = 0; j < 16; j++) v[j] = j < n ? fp[(size_t)j * 18] : make_double2(0.0, 0.0);
+    double g0[3], g1[3];
+#pragma unroll
+    for (int g = 0; g < 3; g++) {
+      const int m = (n - g + 2) / 3;   // partials g, g + 3, ... of the list
+      const bool four = m >= 4;        // (one round of four running sums, the rest into the first: m <= 6)
+      double2 q0 = make_double2(0.0, 0.0), q1 = q0, q2 = q0, q3 = q0;
+#pragma unroll
+      for (int k = 0; k < 6; k++) {
+        const int j = g + 3 * k;
+        if (j < 16 && k < m) {
+          if (four && k == 1) { q1.x += v[j].x; q1.y += v[j].y; }
+          else if (four && k == 2) { q2.x += v[j].x; q2.y += v[j].y; }
+          else if (four && k == 3) { q3.x += v[j].x; q3.y += v[j].y; }
+          else { q0.x += v[j].x; q0.y += v[j].y; }
+        }
+      }
+      g0[g] = (q0.x + q1.x) + (q2.x + q3.x); g1[g] = (q0.y + q1.y) + (q2.y + q3.y);
+    }
+    s0 += (g0[0] + g0[1]) + g0[2];
+    s1 += (g1[0] + g1[1]) + g1[2];
+    if (!mine) return;
+  } else {
+    // a long list among them (a camera's diagonal block): the three blocks one after the other, each list shared by the groups
+    double r0 = 0.0, r1 = 0.0;
+#pragma unroll 1
+    for (int g = 0; g < 3; g++) {
+      const int bf0 = __shfl(f0, 18 * g), bf1 = __shfl(f1, 18 * g);
+      double u0 = 0.0, u1 = 0.0;
+      cc_fold_shared(bf0, sub < 3 ? bf1 : 0, sub, t, lane, f.cc_fold_partial, u0, u1);
+      // (group 0 holds the block's sums: hand them to the block's own group)
+      const double w0 = __shfl(u0, t2), w1 = __shfl(u1, t2);
+      if (sub == g) { r0 = w0; r1 = w1; }
+    }
+    if (!mine) return;
+    s0 = r0; s1 = r1;
+  }
+  *reinterpret_cast<double2*>(&M[(size_t)(f.cb_off[rb] + t / 6) * ld + f.cb_off[cbk] + t % 6]) = make_double2(-s0, -s1);
+}
+__device__ __forceinline__ void fold_sum_mc(int b, int lane, const FoldSumArgs& f, double* __restrict__ M, int ld) {
+  const int sub = lane / 18, t = lane - 18 * sub;
+  const int mb = f.mc_row[b], cb = f.mc_col[b];
+  double s = 0.0;
+  mc_fold_shared(f.mc_range[2 * b], sub < 3 ? f.mc_range[2 * b + 1] : 0, sub, t, lane, f.mc_fold_partial, s);
+  if (sub != 0) return;
+  M[(size_t)(f.mo + 3 * mb + t / 6) * ld + f.cb_off[cb] + t % 6] = -s;
+}
+
 // intrinsics-intrinsics blocks: one wave per block, lanes strided over chunks.
 // partial layout per chunk: 9 (Tm Tm'^T) + 3 (sum Tm.u, self pairs only).
+__device__ __forceinline__ void mm_chunk_sums(int b, const int* __restrict__ blk_chunk_first, const double* __restrict__ partial, int lane, double (&acc)[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; k++) acc[k] = 0.0;
+  int ch = blk_chunk_first[b] + lane;
+  const int ch1 = blk_chunk_first[b + 1];
+  for (; ch + 192 < ch1; ch += 256) {   // the records of four of a lane's chunks asked for at once, added in chunk order as below
+    double v[4][12];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int k = 0; k < 12; k++) v[j][k] = partial[(size_t)(ch + 64 * j) * 12 + k];
+#pragma unroll
+    for (int j = 0; j < 4; j++)
+#pragma unroll
+      for (int k = 0; k < 12; k++) acc[k] += v[j][k];
+  }
+  for (; ch < ch1; ch += 64)
+#pragma unroll
+    for (int k = 0; k < 12; k++) acc[k] += partial[(size_t)ch * 12 + k];
+#pragma unroll
+  for (int k = 0; k < 12; k++) acc[k] = wave_sum(acc[k]);
+}
 __device__ __forceinline__ void asm_mm(int b, const int* __restrict__ blk_row, const int* __restrict__ blk_col,
                                        const int* __restrict__ blk_chunk_first, const double* __restrict__ partial,
                                        const double* __restrict__ modelsum, const double* __restrict__ diag_m, double radius,
@@ -1236,13 +1426,7 @@ __device__ __forceinline__ void asm_mm(int b, const int* __restrict__ blk_row, c
   const int lane = threadIdx.x;
   const int rb = blk_row[b], cbk = blk_col[b];
   double acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = 0.0;
-  for (int ch = blk_chunk_first[b] + lane; ch < blk_chunk_first[b + 1]; ch += 64)
-#pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] += partial[(size_t)ch * 12 + k];
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = wave_sum(acc[k]);
+  mm_chunk_sums(b, blk_chunk_first, partial, lane, acc);
   if (lane < 9) {
     const int a = lane / 3, c = lane % 3;
     double v = 0.0;
@@ -1527,7 +1711,12 @@ __global__ __launch_bounds__(256) void k_mcc_rest(int A, int AE, int ncb, const 
 // rows (k_mcc_rest), the cost at the candidate (k_linearize<false> over all rows) and of its GPS rows (k_gps<false>) - three
 // launches of ~5 us each for the window of a new camera, whose sums then share one k_reduce.  The same workgroups with the same
 // partial slots as the separate launches (the cost partials in a buffer of their own: both sets are alive at once now).
+// n_zero > 0: the zero fill of the reduced system for the NEXT assembly comes first (MSFM_ASM_BESIDE: the fold-sum workgroups of
+// k_sums store into M, so the fill cannot share their launch).  The factor is dead once the back substitution has run - what
+// follows it (k_update_params, k_backsub, this launch, the next k_point) reads the solution vector only - and the stores hide
+// behind the cost pass.
 struct TailArgs {
+  int n_zero; double* M; int ld; ZeroMap Z;
   int n_mcc, n_cost, n_gps;   // workgroups
   // model cost change of the remaining rows
   int A, AE, ncb; const int *o_cb, *o_mb; const double *lin_r, *lin_Jc, *lin_Jm, *z; int has_gps; const double *g_r, *g_J; double* mcc_partial;
@@ -1538,6 +1727,8 @@ struct TailArgs {
 __global__ __launch_bounds__(256) void k_tail(TailArgs a) {
   __shared__ double sh[4];
   int b = blockIdx.x;
+  if (b < a.n_zero) { zero_tile_body(b, a.M, a.ld, a.Z); return; }
+  b -= a.n_zero;
   if (b < a.n_mcc) { mcc_rest_block(b, a.A, a.AE, a.ncb, a.o_cb, a.o_mb, a.lin_r, a.lin_Jc, a.lin_Jm, a.z, a.has_gps, a.g_r, a.g_J, a.mcc_partial, sh); return; }
   b -= a.n_mcc;
   if (b < a.n_cost) { linearize_block<false>(a.P, 0, b, a.cost_partial, sh); return; }
@@ -1701,6 +1892,11 @@ struct msfm_ba {
   DevBuf<double> M, Linv, w, z;
   DevBuf<double> gps, g_r, g_J;
   DevBuf<double> partial, partial2, partial3, partial4, gmax_buf, scal, sloc;
+  DevBuf<double> partial_x;   // cost partials at x (k_point, the rows of frozen points, the GPS rows): alive until the step's last k_reduce
+  bool m_zeroed = false;      // M is zeroed for the next assembly (k_tail, behind a completed solve); cleared by every assembly
+  int asm_paths = 0;          // MSFM_PATH_ASM_BESIDE of the last assembly (msfm_ba_layout.assemble_paths)
+  int n_defer = 0;            // jobs of the assembly's k_reduce that the step's last k_reduce takes over (run_solve)
+  struct { const double* p; int n; int slot; int is_max; } defer[2];
   double* swrite = nullptr;  // where the kernels put scalars: scal (one rank) or sloc (partials, summed by reduce_scalars)
   DevBuf<int> fail;
   double* h_scal = nullptr;  // pinned, mapped: [0, 16) scalars, [16] sequence number, [17] decision code, [18] radius (k_publish_scalars)
@@ -3780,7 +3976,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   ba->nblk_obs = cdiv(As, 256);
   ba->nblk_pt = ptmap_n_wg(ba->map);
   const size_t npart = (size_t)ba->nblk_obs + ba->nblk_pt + cdiv(std::max(1, ncb), 256) + 64;
-  AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart);
+  AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart); AL(partial_x, npart);
   AL(gmax_buf, (size_t)ba->nblk_pt + 6 * (size_t)ncb + 3 * (size_t)nmb + 8);
   AL(scal, S_N); AL(sloc, S_N); AL(spec, 8);
   ba->spec_on = ba->env.spec;
@@ -3870,6 +4066,7 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
     if (ba->fold.mc_on) { out->mc_entries_folded = ba->fold.mc_entries_folded; out->fold_mc_slots = ba->fold.n_diag; }
   }
   out->solve_paths = ba->solve_paths;
+  out->assemble_paths = ba->asm_paths;
   out->npb_S = ba->map.nQ + ba->map.nS; out->npb_L = ba->map.nL; out->npb_X = ba->map.nX; out->npb_S4 = ba->n_short4;
   return MSFM_OK;
 }
@@ -3942,8 +4139,8 @@ static int run_evaluate(msfm_ba* ba, bool candidate, bool jac, double huber, int
     // [nblk_pt, nblk_pt + ntail)) and the GPS rows.  The sum into `slot` follows k_point.
     KTimer t(ctx, "ba_linearize");
     const int ntail = cdiv(ba->A - ba->AE, 256);
-    if (ntail) hipLaunchKernelGGL(k_linearize<true>, dim3(ntail), dim3(256), 0, s, P, ba->AE, ba->partial.p + ba->nblk_pt, spec);
-    if (ng) hipLaunchKernelGGL(k_gps<true>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial.p + ba->nblk_pt + ntail, spec);
+    if (ntail) hipLaunchKernelGGL(k_linearize<true>, dim3(ntail), dim3(256), 0, s, P, ba->AE, ba->partial_x.p + ba->nblk_pt, spec);
+    if (ng) hipLaunchKernelGGL(k_gps<true>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial_x.p + ba->nblk_pt + ntail, spec);
     ba->lin_pending = true;
     ba->lin_huber = huber;
     (void)slot;   // S_XCOST
@@ -3977,7 +4174,7 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   Q.T = ba->T.p; Q.Tu = ba->Tu.p; Q.Tm = ba->Tm.p; Q.Tmu = ba->Tmu.p;
   Q.radius = radius; Q.dmin = opt->min_lm_diagonal; Q.dmax = opt->max_lm_diagonal;
   Q.reuse_diag = reuse_diag; Q.mode = mode; Q.fail = ba->fail.p;
-  Q.store_rows = store_rows ? 1 : 0; Q.cost_partial = ba->partial.p;
+  Q.store_rows = store_rows ? 1 : 0; Q.cost_partial = ba->partial_x.p;
   const FoldTables& F = ba->fold;
   Q.fold_wg = F.on ? F.wg_fold.p : nullptr; Q.fold_wg_pass_first = F.wg_pass_first.p; Q.fold_slot_rank = F.slot_rank.p;
   Q.fold_pass = F.pass.p; Q.fold_stream = F.stream.p; Q.fold_partial = F.partial.p;
@@ -3988,9 +4185,33 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   hipLaunchKernelGGL(k_point, dim3(ba->nblk_pt), dim3(256), 0, ctx->stream, Q, ba->gmax_buf.p);
 }
 
+// the tiles of M that the zero fill covers as a ZeroMap (0: the plain memset is needed instead)
+static int ba_zero_map(const msfm_ba* ba, ZeroMap& Z) {
+  const int nb64 = ba->npad / 64;
+  if (ba->ctx->world > 1 || nb64 > 256) return 0;
+  Z.nb = nb64;
+  for (int b = 0; b < nb64; b++) { Z.lev[b] = 127; Z.lo[b] = 0; Z.hi[b] = 0x7fff; }   // root chain / dense order: couples to everything
+  for (int lv = 0; lv < ba->plan.n_levels; lv++)
+    for (int k = 0; k < ba->plan.level[lv].K; k++) {
+      const msfm_chol_node& nd = ba->plan.level[lv].node[k];
+      for (int b = nd.begin / 64; b < nd.end / 64; b++) { Z.lev[b] = (unsigned char)lv; Z.lo[b] = (short)nd.leaf_lo; Z.hi[b] = (short)nd.leaf_hi; }
+    }
+  return nb64 * (nb64 + 1) / 2;
+}
+// Where the fold partials can be summed beside the per-camera sums (FoldSumArgs): one rank (with several, the all-reduce of the
+// per-camera sums sits between the two parts), every camera x camera and intrinsics x camera entry folded (no block needs chunk
+// partials that the same launch writes), no per-class timers, a system the ZeroMap holds.
+static bool asm_beside_ok(const msfm_ba* ba) {
+  const FoldTables& F = ba->fold;
+  return ba->env.asm_beside && ba->env.fused_sums && ba->ctx->world <= 1 && !ba->ctx->profile && ba->ncb > 0 && ba->nmb <= 1 && ba->n_fchunks > 0 && F.on && F.all &&
+         (ba->mc.n_blocks == 0 || (F.mc_on && F.mc_all)) && ba->npad / 64 <= 256;
+}
+
 // point kernel + camera sums (+, for mode 0, the reduced system in M).  point_enqueued: the point kernel of this
-// linearisation point is already in the stream (msfm_ba_run enqueued it ahead of the step's read-back).
-static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool point_enqueued = false) {
+// linearisation point is already in the stream (msfm_ba_run enqueued it ahead of the step's read-back).  will_solve: run_solve
+// follows (its last k_reduce can then take the sums of this call's over).
+static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool point_enqueued = false,
+                        bool will_solve = false) {
   msfm_ctx* ctx = ba->ctx;
   hipStream_t s = ctx->stream;
   const int ncb = ba->ncb, nmb = ba->nmb;
@@ -4037,6 +4258,9 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
   //  whose pair kernels want more waves per SIMD than this launch has)
   const bool fused = mode == 0 && ba->n_fchunks > 0 && (ba->fold.on || ba->cc.n_pairs < 262144) && ba->env.fused_sums;
   const bool forked = mode == 0 && !ctx->profile && overlap && !fused;
+  const bool beside = fused && asm_beside_ok(ba);
+  const bool m_zeroed = ba->m_zeroed;
+  if (mode == 0) { ba->m_zeroed = false; ba->n_defer = 0; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; }
   // zero fill of the reduced system in front of the assembly (reads nothing: with the fork it runs on the second stream too)
   auto zero_system = [&](hipStream_t sz) -> int {
     const int nb64 = ba->npad / 64;
@@ -4055,18 +4279,6 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       hipLaunchKernelGGL(k_zero_system, dim3(nb64 * (nb64 + 1) / 2), dim3(256), 0, sz, ba->M.p, ba->npad, Z);
     }
     return MSFM_OK;
-  };
-  auto zero_map = [&](ZeroMap& Z) -> int {   // the tiles k_sums fills (0: the plain memset is needed instead)
-    const int nb64 = ba->npad / 64;
-    if (ctx->world > 1 || nb64 > 256) return 0;
-    Z.nb = nb64;
-    for (int b = 0; b < nb64; b++) { Z.lev[b] = 127; Z.lo[b] = 0; Z.hi[b] = 0x7fff; }
-    for (int lv = 0; lv < ba->plan.n_levels; lv++)
-      for (int k = 0; k < ba->plan.level[lv].K; k++) {
-        const msfm_chol_node& nd = ba->plan.level[lv].node[k];
-        for (int b = nd.begin / 64; b < nd.end / 64; b++) { Z.lev[b] = (unsigned char)lv; Z.lo[b] = (short)nd.leaf_lo; Z.hi[b] = (short)nd.leaf_hi; }
-      }
-    return nb64 * (nb64 + 1) / 2;
   };
   if (forked) {
     if (!ctx->stream2) {
@@ -4094,8 +4306,9 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     if (fused) {
       const size_t ncr = (size_t)std::max(1, ba->NCR);
       SumsArgs a;
-      a.n_zero = zero_map(a.Z);
-      if (a.n_zero == 0) MSFM_TRY(zero_system(s));
+      // (beside: the fold-sum workgroups store into M, so it is zeroed beforehand - by the k_tail of the last solve, or here)
+      a.n_zero = beside ? 0 : ba_zero_map(ba, a.Z);
+      if (beside ? !m_zeroed : a.n_zero == 0) MSFM_TRY(zero_system(s));
       a.M = ba->M.p; a.ld = ba->npad;
       const bool mc_sparse = ba->fold.on && ba->fold.mc_on;
       a.mc_n = mc_sparse ? ba->fold.mc_n_live : ba->mc.n_chunks; a.mc_start = ba->mc.ch_start.p; a.mc_end = ba->mc.ch_end.p; a.mc_pa = ba->mc.pa.p; a.mc_pb = ba->mc.pb.p;
@@ -4108,17 +4321,32 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       a.R = CamRows{ba->cm_pt.p, ba->cm_X.p, ba->cm_xyw.p, ba->cm_xyw.p + ncr, ba->cm_xyw.p + 2 * ncr, ba->chunk_cam.p};
       a.Tu = ba->Tu.p; a.cpos_pb = ba->cpos_pb.p; a.f_partial = ba->f_partial.p;
       a.n_mc_wg = cdiv(a.mc_n, 4); a.n_mm_wg = cdiv(a.mm_n, 4); a.n_cc_wg = cdiv(a.cc_n, 4); a.n_ftf_wg = cdiv(a.f_n, 4);
-      hipLaunchKernelGGL(k_sums, dim3(a.n_zero + a.n_mc_wg + a.n_mm_wg + a.n_cc_wg + a.n_ftf_wg), dim3(256), 0, s, a);
+      memset(&a.fs, 0, sizeof a.fs);
+      int n_rest = a.n_ftf_wg;   // workgroups behind the pair lists'
+      if (beside) {
+        FoldSumArgs& f = a.fs;
+        f.n_cc = ba->cc.n_blocks; f.n_mc = ba->mc.n_blocks; f.mo = ba->mo;
+        f.n_cc_wg = cdiv(cdiv(f.n_cc, 3), 4); f.n_mc_wg = cdiv(f.n_mc, 4);
+        f.cc_row = ba->cc.blk_row.p; f.cc_col = ba->cc.blk_col.p; f.cc_range = ba->fold.blk_range.p; f.cc_fold_partial = ba->fold.partial.p;
+        f.mc_row = ba->mc.blk_row.p; f.mc_col = ba->mc.blk_col.p; f.mc_range = ba->fold.mc_range.p; f.mc_fold_partial = ba->fold.mc_partial.p;
+        f.cb_off = ba->cb_off.p;
+        n_rest += f.n_mc_wg + f.n_cc_wg;
+      }
+      hipLaunchKernelGGL(k_sums, dim3(a.n_zero + a.n_mc_wg + a.n_mm_wg + a.n_cc_wg + n_rest), dim3(256), 0, s, a);
     } else if (ba->n_fchunks) {
       const size_t ncr = (size_t)std::max(1, ba->NCR);
       const CamRows R{ba->cm_pt.p, ba->cm_X.p, ba->cm_xyw.p, ba->cm_xyw.p + ncr, ba->cm_xyw.p + 2 * ncr, ba->chunk_cam.p};
       hipLaunchKernelGGL(k_ftf, dim3(cdiv(ba->n_fchunks, 4)), dim3(256), 0, s, ba->n_fchunks, ba->f_start.p, ba->f_end.p,
                          make_ptrs(ba, false, ba->lin_huber), R, ba->Tu.p, ba->cpos_pb.p, ba->f_partial.p);
     }
-    if (ncb)
-      hipLaunchKernelGGL(k_camftf, dim3(ncb), dim3(128), 0, s, ncb, ba->cam_chunk_first.p, ba->f_partial.p, ba->camftf.p,
+    if (ncb) {
+      CamFinish fin;
+      memset(&fin, 0, sizeof fin);
+      if (beside) fin = CamFinish{ba->M.p, ba->npad, ba->nsys, ba->mo, ba->cb_off.p, ba->cb_mb.p, radius, ba->n_padcol, ba->padcol.p};
+      hipLaunchKernelGGL(k_camftf, dim3(ncb + (beside ? cdiv(ba->n_padcol, 128) : 0)), dim3(128), 0, s, ncb, ba->cam_chunk_first.p, ba->f_partial.p, ba->camftf.p,
                          ba->g_r.p, ba->g_J.p, (ba->has_gps && lead) ? 1 : 0, ctx->world <= 1 ? 1 : 0, ba->diag_c.p, ba->scale_c.p,
-                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_c);
+                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_c, fin);
+    }
   }
   if (ncb) MSFM_TRY(allreduce(ba, ba->camftf.p, (size_t)ncb * PSTRIDE, MSFM_REDUCE_SUM));  // per-camera sums over all shards
   {
@@ -4126,9 +4354,13 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     if (ncb && ctx->world > 1)
       hipLaunchKernelGGL(k_cam_post, dim3(cdiv(6 * ncb, 256)), dim3(256), 0, s, ncb, ba->camftf.p, ba->diag_c.p, ba->scale_c.p,
                          reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_c);
-    if (nmb)
-      hipLaunchKernelGGL(k_modelsum, dim3(nmb), dim3(64), 0, s, ba->mcam_first.p, ba->mcam.p, ba->camftf.p, ba->modelsum.p,
-                         ba->diag_m.p, ba->scale_m.p, reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_m);
+    if (nmb) {
+      ModelFinish fin;
+      memset(&fin, 0, sizeof fin);
+      if (beside) fin = ModelFinish{ba->M.p, ba->npad, ba->nsys, ba->mo, ba->mm.n_blocks, ba->mm.blk_row.p, ba->mm.blk_col.p, ba->mm.blk_chunk_first.p, ba->mm.partial.p, radius};
+      hipLaunchKernelGGL(k_modelsum, dim3(nmb), dim3(beside ? 128 : 64), 0, s, ba->mcam_first.p, ba->mcam.p, ba->camftf.p, ba->modelsum.p,
+                         ba->diag_m.p, ba->scale_m.p, reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_m, fin);
+    }
   }
   if (mode == 1) return MSFM_OK;
   {
@@ -4138,12 +4370,19 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     if (store_rows) {
       // cost at x: k_point's blocks, the frozen points' rows, the GPS rows (lead rank only) - see run_evaluate
       const int ntail = cdiv(ba->A - ba->AE, 256), ng = (ba->has_gps && lead) ? cdiv(ncb, 256) : 0;
-      rj.job[1] = {ba->partial.p, ba->nblk_pt + ntail + ng, S_XCOST, 0};
+      rj.job[1] = {ba->partial_x.p, ba->nblk_pt + ntail + ng, S_XCOST, 0};
       rj.count = 2;
     }
     rj.fail = ba->fail.p;
     rj.fail_slot = S_FAIL;
-    hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
+    if (beside && will_solve && ba->env.fused_tail) {
+      // nothing reads these sums before k_publish_scalars: the last k_reduce of the step takes them (run_solve), off the path
+      // to the factorisation
+      ba->n_defer = rj.count;
+      for (int j = 0; j < rj.count; j++) { ba->defer[j].p = rj.job[j].p; ba->defer[j].n = rj.job[j].n; ba->defer[j].slot = rj.job[j].slot; ba->defer[j].is_max = rj.job[j].is_max; }
+    } else {
+      hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
+    }
   }
   if (forked) {
     join.armed = false;
@@ -4172,7 +4411,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     aa.n_padcol = ctx->world <= 1 ? ba->n_padcol : 0;
     aa.padcol = ba->padcol.p;
     const int nasm = aa.n_cc + aa.n_mc + aa.n_mm + aa.n_rhs + cdiv(aa.n_padcol, 64);
-    if (nasm) hipLaunchKernelGGL(k_asm_all, dim3(nasm), dim3(64), 0, s, aa);
+    if (nasm && !beside) hipLaunchKernelGGL(k_asm_all, dim3(nasm), dim3(64), 0, s, aa);   // (beside: M is complete already)
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return msfm_set_error(ctx, MSFM_E_DEVICE, "assemble launch: %s", hipGetErrorString(e));
@@ -4264,6 +4503,7 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
       // the call may have stopped before the solve kernel marked znext: neither half can be trusted to be "pending"
       // any more (a stale half would be taken for published values by the next solve) - mark both again
       (void)msfm_chol_fill_pending(ctx, ba->zsys.p, 2 * (ba->npad + 8));
+      ba->m_zeroed = false;
       return rc;
     }
     ba->zflip ^= 1;   // only a completed solve hands the other half over
@@ -4300,6 +4540,9 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
       // the four sums (the failure bits of the factorisation / finiteness checks are final here)
       t.stop();   // (the class ba_backsub ends here: what follows is timed as ba_cost)
       TailArgs a;
+      // (the factor in M is dead behind the back substitution: zeroed here for the next assembly where that one sums beside)
+      a.n_zero = (ba->nred > 0 && asm_beside_ok(ba)) ? ba_zero_map(ba, a.Z) : 0;
+      a.M = ba->M.p; a.ld = ba->npad;
       a.n_mcc = nrest ? cdiv(nrest, 256) : 0;
       a.A = ba->A; a.AE = ba->AE; a.ncb = ncb; a.o_cb = ba->o_cb.p; a.o_mb = ba->o_mb.p; a.lin_r = ba->lin_r.p; a.lin_Jc = ba->lin_Jc.p; a.lin_Jm = ba->lin_Jm.p;
       a.z = ba->z.p; a.has_gps = ngps ? 1 : 0; a.g_r = ba->g_r.p; a.g_J = ba->g_J.p; a.mcc_partial = ba->partial.p + moff;
@@ -4310,16 +4553,19 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
       a.cb_cam = ba->cb_cam.p; a.cam_c = a.P.cam; a.gps = ba->gps.p; a.gps_weight = ba->gps_weight; a.huber = opt->huber_delta; a.scale_c = ba->scale_c.p;
       a.g_r_w = ba->g_r.p; a.g_J_w = ba->g_J.p;   // (not written: WRITE_JAC is false)
       KTimer t2(ctx, "ba_cost");
-      hipLaunchKernelGGL(k_tail, dim3(a.n_mcc + a.n_cost + a.n_gps), dim3(256), 0, s, a);
+      hipLaunchKernelGGL(k_tail, dim3(a.n_zero + a.n_mcc + a.n_cost + a.n_gps), dim3(256), 0, s, a);
+      ba->m_zeroed = a.n_zero > 0;
       ReduceJobs rj;
       rj.count = 4;
       rj.job[0] = {ba->partial.p, moff, S_MCC, 0};
       rj.job[1] = {ba->partial2.p, off, S_DX2, 0};
       rj.job[2] = {ba->partial3.p, off, S_X2, 0};
       rj.job[3] = {ba->partial4.p, a.n_cost + (lead ? a.n_gps : 0), S_COST, 0};
+      for (int j = 0; j < ba->n_defer; j++) rj.job[rj.count++] = {ba->defer[j].p, ba->defer[j].n, ba->defer[j].slot, ba->defer[j].is_max};   // (the assembly's: S_GMAX, S_XCOST)
+      ba->n_defer = 0;
       rj.fail = ba->fail.p;
       rj.fail_slot = S_FAIL;
-      hipLaunchKernelGGL(k_reduce, dim3(4), dim3(1024), 0, s, rj, ba->swrite);
+      hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
       hipError_t e2 = hipGetLastError();
       if (e2 != hipSuccess) return msfm_set_error(ctx, MSFM_E_DEVICE, "solve launch: %s", hipGetErrorString(e2));
       return MSFM_OK;
@@ -4390,6 +4636,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     hipLaunchKernelGGL(k_cam_points, dim3(cdiv(ba->NCR, 256)), dim3(256), 0, s, ba->NCR, ba->cm_pt.p, ba->pt.p, ba->cm_X.p, ba->cm_Xc.p);
   lap("scales reset");
   hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, s, ba->fail.p);
+  ba->m_zeroed = false;   // (the first assembly of a run zero-fills for itself)
   double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
   bool reuse_diag = false;
   // ---- IterationZero ----
@@ -4418,8 +4665,8 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
   auto assemble_and_step = [&](bool point_enqueued) -> int {
     LmDecide D;
     D.fresh = ba->lin_pending ? 1 : 0;
-    MSFM_TRY(run_assemble(ba, opt, radius, reuse_diag, 0, point_enqueued));
     D.on = (iteration < opt->max_num_iterations && radius > opt->min_trust_region_radius) ? 1 : 0;
+    MSFM_TRY(run_assemble(ba, opt, radius, reuse_diag, 0, point_enqueued, D.on != 0));
     if (D.on) MSFM_TRY(run_solve(ba, opt));
     MSFM_TRY(reduce_scalars(ba));
     D.x_cost = x_cost; D.radius = radius;

@@ -34,6 +34,7 @@ struct msfm_env {
   long lanes4_min = -1;           // MSFM_LANES4_MIN: eliminated points above which those of up to 4 rows get 4 lanes (ptmap_use_lanes4; -1: default)
   bool fused_sums = true;         // MSFM_FUSED_SUMS=0: per-camera sums, pair-list residue and zero fill as separate launches
   bool fused_tail = true;         // MSFM_FUSED_TAIL=0: the launches behind the back substitution one by one
+  bool asm_beside = true;         // MSFM_ASM_BESIDE=0: the Schur fold partials summed after the per-camera sums (k_asm_all), not beside them
   bool keep_t = false;            // MSFM_KEEP_T=1: folding workgroups store their T records too
   bool tu_direct = true;          // MSFM_TU_DIRECT=0: T.u through the lane exchange
   bool spec = true;               // MSFM_SPEC=0: the next linearisation enqueued only after the step's read-back

@@ -25,6 +25,7 @@ msfm_env msfm_env_read() {
   if (const char* e = get("MSFM_LANES4_MIN")) E.lanes4_min = atol(e);
   E.fused_sums = num("MSFM_FUSED_SUMS", 1) != 0;
   E.fused_tail = num("MSFM_FUSED_TAIL", 1) != 0;
+  E.asm_beside = num("MSFM_ASM_BESIDE", 1) != 0;
   E.keep_t = num("MSFM_KEEP_T", 0) != 0;
   E.tu_direct = num("MSFM_TU_DIRECT", 1) != 0;
   E.spec = num("MSFM_SPEC", 1) != 0;
