@@ -1682,6 +1682,75 @@ void SLAMGPS::ReadinPriorInfo(const std::string& file, std::vector<std::vector<i
   }
 }
 
+void SLAMGPS::FeatureMatching(const std::vector<std::vector<float>>& descriptors, const std::vector<std::vector<Point2f>>& keypoints,
+                              const std::vector<std::vector<int>>& ids, const std::vector<std::vector<Mat3>>& Fs, const std::vector<std::vector<Mat3>>& Hs,
+                              std::vector<std::vector<std::vector<std::pair<int, int>>>>& matches_out, std::vector<std::vector<int>>& match_graph_out) {
+  const size_t n_img = descriptors.size();
+  if (keypoints.size() != n_img || ids.size() > n_img || Fs.size() != ids.size() || Hs.size() != ids.size())
+    throw std::runtime_error("SLAMGPS::FeatureMatching: descriptors, keypoints and priors do not belong together");
+  // the pair list in the order the loops of :432 / :451 walk it
+  std::vector<int> flat;
+  std::vector<double> F, H;
+  for (size_t i = 0; i < ids.size(); i++) {
+    if (Fs[i].size() != ids[i].size() || Hs[i].size() != ids[i].size()) throw std::runtime_error("SLAMGPS::FeatureMatching: one F and one H per id");
+    for (size_t j = 0; j < ids[i].size(); j++) {
+      flat.push_back((int)i); flat.push_back(ids[i][j]);
+      F.insert(F.end(), Fs[i][j].m, Fs[i][j].m + 9);
+      H.insert(H.end(), Hs[i][j].m, Hs[i][j].m + 9);
+    }
+  }
+  const int n_pairs = (int)(flat.size() / 2);
+  matches_out.assign(n_img, {});
+  for (size_t i = 0; i < ids.size(); i++) matches_out[i].assign(ids[i].size(), {});
+  match_graph_out.assign(n_img, std::vector<int>(n_img, 0));   // :426-430
+  if (n_pairs == 0) return;
+  msfm_descset* set = nullptr;
+  msfm_match_result* res = nullptr;
+  msfm_chain* chain = nullptr;
+  auto release = [&] {
+    if (chain) msfm_chain_destroy(chain);
+    if (res) msfm_match_result_destroy(res);
+    if (set) msfm_descset_destroy(set);
+  };
+  try {
+    check(msfm_descset_create(Context(), (int)n_img, 128, &set), "descset_create");
+    for (size_t i = 0; i < n_img; i++) {
+      const int n = (int)(descriptors[i].size() / 128);
+      if (keypoints[i].size() != (size_t)n) throw std::runtime_error("SLAMGPS::FeatureMatching: one keypoint per descriptor");
+      check(msfm_descset_upload(set, (int)i, descriptors[i].data(), n), "descset_upload");
+      if (n == 0) continue;
+      std::vector<float> xy(2 * (size_t)n);
+      for (int k = 0; k < n; k++) { xy[2 * k] = keypoints[i][k].x; xy[2 * k + 1] = keypoints[i][k].y; }
+      check(msfm_descset_upload_keypoints(set, (int)i, xy.data(), n), "descset_upload_keypoints");
+    }
+    msfm_slam_match_options mo;
+    msfm_slam_match_default_options(&mo);               // th_first_second_ratio 0.80 (:320)
+    mo.th_epipolar = (float)(2.0 / resize_ratio);       // :316
+    mo.th_distance = (float)(5.0 / resize_ratio);       // :317
+    check(msfm_match_pairs_slam(set, flat.data(), n_pairs, F.data(), H.data(), &mo, 0, &res), "match_pairs_slam");
+    check(msfm_chain_create(res, &chain), "chain_create");
+    msfm_fransac_options fo;
+    msfm_fransac_default_options(&fo);
+    check(msfm_chain_verify_slam(chain, res, &fo), "chain_verify_slam");
+    std::vector<int> n_m((size_t)n_pairs);
+    check(msfm_chain_matches(chain, n_m.data(), nullptr, nullptr), "chain_matches");
+    int p = 0;
+    for (size_t i = 0; i < ids.size(); i++)
+      for (size_t j = 0; j < ids[i].size(); j++, p++) {
+        std::vector<int> m(2 * (size_t)std::max(1, n_m[p]));
+        check(msfm_chain_fetch_matches(chain, p, m.data()), "chain_fetch_matches");
+        auto& out = matches_out[i][j];
+        out.resize((size_t)n_m[p]);
+        for (int k = 0; k < n_m[p]; k++) out[k] = std::make_pair(m[2 * k], m[2 * k + 1]);
+        match_graph_out[i][ids[i][j]] = n_m[p];          // :540
+      }
+  } catch (...) {
+    release();
+    throw;
+  }
+  release();
+}
+
 // ---- SLAM + GPS registration (slam_gps.cc:98-119) ---------------------------------------------
 void Camera::Transformation(const Mat3& R, const Vec3& t, double scale) {
   const double* A = R.m;

@@ -284,6 +284,7 @@ class IncrementalSfM {
   std::vector<msfm_ba_iteration> iterations_;
 };
 
+struct Point2f;
 // SLAMGPS::FullBundleAdjustment (SfM/src/slam_gps.cc:675-863): every non-bad point's observations as
 // ReprojectionErrorPoseCamXYZ rows with the point's weight, the absolute GPS rows, max 200 iterations, 8 threads.
 class SLAMGPS {
@@ -299,6 +300,15 @@ class SLAMGPS {
                                 const std::vector<std::vector<Mat3>>& Hs);
   static void ReadinPriorInfo(const std::string& file, std::vector<std::vector<int>>& ids, std::vector<std::vector<Mat3>>& Fs,
                               std::vector<std::vector<Mat3>>& Hs);
+  // SLAMGPS::FeatureMatching step 2 (slam_gps.cc:425-555) for the ids / Fs / Hs of FeatureMatchingPriors: descriptors [image][n*128]
+  // and keypoints (centred pixels) uploaded once, then msfm_match_pairs_slam (the three checks, :469-503), msfm_chain_create and
+  // msfm_chain_verify_slam (GeoVerificationFundamental on all survivors, :513; the pair keeps `inliers` whatever the verdict,
+  // :514-518).  matches_out[i][j] = the kept (feature in i, feature in ids[i][j]) of pair (i, ids[i][j]), fetched with
+  // msfm_chain_fetch_matches; match_graph_out[i][ids[i][j]] = their number (:540).  Thresholds as in FeatureMatchingPriors,
+  // th_first_second_ratio 0.80 (:320).
+  void FeatureMatching(const std::vector<std::vector<float>>& descriptors, const std::vector<std::vector<Point2f>>& keypoints,
+                       const std::vector<std::vector<int>>& ids, const std::vector<std::vector<Mat3>>& Fs, const std::vector<std::vector<Mat3>>& Hs,
+                       std::vector<std::vector<std::vector<std::pair<int, int>>>>& matches_out, std::vector<std::vector<int>>& match_graph_out);
   std::vector<Camera*> cams_;
   std::vector<CameraModel*> cam_models_;
   std::vector<Point3D*> pts_;

@@ -520,12 +520,22 @@ void msfm_track_set_destroy(msfm_track_set* set);
  * sfm_incremental.cc:755-915).  Each step runs the kernels of its host-array counterpart on device buffers and gives
  * the same result bit for bit; between the descriptor / keypoint upload and msfm_ba_download_params only a few integers
  * per image pair and the cameras cross PCIe.  Image index = camera index.
- *   msfm_chain_create       takes the codes of a msfm_match_pairs result (not the SLAM form) whose descriptor set holds the
- *                           keypoints of every image involved (msfm_descset_upload_keypoints)
+ *   msfm_chain_create       takes the codes of a msfm_match_pairs or msfm_match_pairs_slam result whose descriptor set holds
+ *                           the keypoints of every image involved (msfm_descset_upload_keypoints); the chain records the form
  *   msfm_chain_verify       per pair: GeoVerificationFundamental on matches_good (msfm_fundamental_ransac_batch, pair p of the
  *                           list = pair p of the sampler), then, if it succeeded, the closed-form filter with th_filter (3.0)
  *                           on matches_all; a pair keeps the surviving matches_all entries, a failed pair none
  *                           (fine_matching_graph.cc:138-153, :182-186)
+ *   msfm_chain_verify_slam  the verification of a SLAM-form chain, the tail of SLAMGPS::FeatureMatching step 2
+ *                           (slam_gps.cc:503-541): GeoVerificationFundamental on ALL survivors of the pair's three checks in
+ *                           query order (pair p of the list = pair p of the sampler), no good / all split and no filter
+ *                           behind it; the pair keeps the entries of the RANSAC mask WHATEVER the verdict:
+ *                             < min_points survivors              -> no RANSAC, no match, ok = 0
+ *                             >= min_points, < min_inliers inliers -> ok = 0 and those 1..29 matches are kept
+ *                             no model found                       -> mask of msfm_fundamental_ransac_batch is 0: no match
+ *                           matches are (train feature in id1, query feature m in id2) in ascending m.  Each verify call
+ *                           refuses a chain of the other form, a second call and a result the chain was not made from
+ *                           (MSFM_E_INVAL; the chain stays usable)
  *   msfm_chain_build_tracks msfm_tracks_build_device on those matches, pairs in the order of the match result
  *   msfm_chain_triangulate  msfm_triangulate_midpoint_batch on every track (X starts at 0), observations from the keypoints
  *   msfm_chain_ba_create    msfm_ba_create on the tracks with ok = 1 and >= min_views observations (slam_gps.cc:638-648:
@@ -535,6 +545,7 @@ void msfm_track_set_destroy(msfm_track_set* set);
 typedef struct msfm_chain msfm_chain;
 int msfm_chain_create(msfm_match_result* res, msfm_chain** out);
 int msfm_chain_verify(msfm_chain* chain, msfm_match_result* res, const msfm_fransac_options* opt, double th_filter);
+int msfm_chain_verify_slam(msfm_chain* chain, msfm_match_result* res, const msfm_fransac_options* opt);
 int msfm_chain_matches(msfm_chain* chain, int* n_matches /*[n_pairs]*/, uint8_t* ok /*[n_pairs]*/, double* F /*[n_pairs][9]*/);
 int msfm_chain_fetch_matches(msfm_chain* chain, int pair, int* matches /*[n_matches[pair]][2]*/);
 int msfm_chain_build_tracks(msfm_chain* chain, int* n_tracks, int* n_observations);

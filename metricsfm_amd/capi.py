@@ -20,7 +20,7 @@ SYMBOLS = [
     "msfm_knn2_f32", "msfm_descset_create", "msfm_descset_upload", "msfm_descset_count", "msfm_descset_destroy",
     "msfm_match_pairs", "msfm_match_result_counts", "msfm_match_result_fetch", "msfm_match_result_stats", "msfm_match_result_destroy",
     "msfm_match_pairs_rerun", "msfm_descset_upload_keypoints", "msfm_slam_match_default_options", "msfm_match_pairs_slam",
-    "msfm_chain_create", "msfm_chain_verify", "msfm_chain_matches", "msfm_chain_fetch_matches", "msfm_chain_build_tracks",
+    "msfm_chain_create", "msfm_chain_verify", "msfm_chain_verify_slam", "msfm_chain_matches", "msfm_chain_fetch_matches", "msfm_chain_build_tracks",
     "msfm_chain_fetch_tracks", "msfm_chain_triangulate", "msfm_chain_fetch_points", "msfm_chain_ba_create", "msfm_chain_fetch_point_tracks",
     "msfm_chain_destroy",
     "msfm_gpsreg_default_options", "msfm_gps_orient_global", "msfm_point_accuracy_batch", "msfm_gps_register_points",
@@ -146,6 +146,7 @@ def lib():
     L.msfm_track_set_destroy.restype = None
     L.msfm_chain_create.argtypes = [vp, C.POINTER(vp)]
     L.msfm_chain_verify.argtypes = [vp, vp, C.POINTER(A.FransacOptions), d]
+    L.msfm_chain_verify_slam.argtypes = [vp, vp, C.POINTER(A.FransacOptions)]
     L.msfm_chain_matches.argtypes = [vp, A.c_int_p, A.c_u8_p, A.c_double_p]
     L.msfm_chain_fetch_matches.argtypes = [vp, i, A.c_int_p]
     L.msfm_chain_build_tracks.argtypes = [vp, A.c_int_p, A.c_int_p]
@@ -1036,6 +1037,7 @@ class MatchResult:
         self.ds, self.ctx = ds, ds.ctx
         self.pairs = A.as_c(np.asarray(pairs).reshape(-1, 2), np.int32)
         self.keep_knn = keep_knn
+        self.slam = slam is not None
         self._h = C.c_void_p()
         if slam is not None:
             F, H, kw = slam
@@ -1098,10 +1100,22 @@ class Chain:
         self.n_pairs = len(res.pairs)
         self._h = C.c_void_p()
         self.ctx.check(lib().msfm_chain_create(res._h, C.byref(self._h)))
+        self.slam = bool(getattr(res, "slam", False))
 
     def verify(self, th_filter=3.0, **opts):
         o = fransac_options(**opts)
         self.ctx.check(lib().msfm_chain_verify(self._h, self.res._h, C.byref(o), th_filter))
+        return self._matches()
+
+    def verify_slam(self, res=None, **opts):
+        """msfm_chain_verify_slam (slam_gps.cc:503-541): the RANSAC on all survivors of a pair; a pair keeps the entries of the
+        mask whatever the verdict, so ok = 0 with n_matches > 0 is a legal outcome.  `res`: the match result to pass (default:
+        the one the chain was made from)."""
+        o = fransac_options(**opts)
+        self.ctx.check(lib().msfm_chain_verify_slam(self._h, (res or self.res)._h, C.byref(o)))
+        return self._matches()
+
+    def _matches(self):
         n = np.zeros(max(1, self.n_pairs), np.int32)
         ok = np.zeros(max(1, self.n_pairs), np.uint8)
         F = np.zeros((max(1, self.n_pairs), 3, 3))

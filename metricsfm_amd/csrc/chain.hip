@@ -13,6 +13,22 @@
 // upload and the download of the adjusted parameters is a few integers per image pair (match counts, needed on the host
 // to size the next step) plus the cameras.  Every step gives bit for bit what its host-array counterpart gives on the same
 // input (tests/test_gpu_chain.py).
+//
+// A chain takes either form of match result and keeps which one it was made from:
+//   msfm_match_pairs       codes with good / all sets -> msfm_chain_verify (above)
+//   msfm_match_pairs_slam  codes = survivors of the ratio test and the two prior gates -> msfm_chain_verify_slam: the tail of
+//                          SLAMGPS::FeatureMatching step 2 (SfM/src/slam_gps.cc:503-541).  GeoVerificationFundamental runs on ALL
+//                          survivors of a pair in query order; there is no good / all split and no closed-form filter behind it.
+//                          Then `matches[j] = {matches[j][inliers[k]]}` whatever the function returned:
+//     - fewer than min_points (30) survivors: the function returns before RANSAC, `inliers` is empty, the pair keeps NO match;
+//     - min_points or more survivors but fewer than min_inliers (30) RANSAC inliers: the function returns false with `inliers`
+//       already filled, so the pair KEEPS those 1..29 matches - ok = 0 with n_matches > 0 (in msfm_chain_verify a failed pair
+//       keeps none);
+//     - no model found: the mask of msfm_fundamental_ransac_batch is all zero and the pair keeps nothing (the documented
+//       departure of that call, which msfm_slam_priors carries too).
+//   Kept matches are (train feature in id1, query feature m in id2) in ascending m, pairs in the order of the match result.
+//   Everything behind the verification (tracks, triangulation, accuracy, registration, bundle adjustment, match store) is the
+//   same code on either form (tests/test_gpu_slam_chain.py).
 #include <algorithm>
 #include <cstring>
 #include <memory>
@@ -76,6 +92,32 @@ __global__ __launch_bounds__(256) void k_gather_sets(const PairSrc* __restrict__
       m_all[2 * e] = id; m_all[2 * e + 1] = m;
       a1[2 * e] = x1; a1[2 * e + 1] = y1; a2[2 * e] = x2; a2[2 * e + 1] = y2;
       pair_of_all[e] = blockIdx.x;
+    }
+    na += tot;
+  }
+}
+
+// One workgroup per pair of a SLAM-form result (slam_gps.cc:503-519): every code >= 0 is a survivor of the three checks and its
+// code the bare train index; (id, m) and the two cv::Point2f go to the pair's offset in query order.  One set, no pair_of
+// array: the RANSAC that follows walks the set by offsets.  off_all + cap bounds the pair's rows (cap = the n_all the chain read
+// at create time): a result whose codes were recomputed since then cannot write past them.
+__global__ __launch_bounds__(256) void k_gather_slam(const PairSrc* __restrict__ src, const int* __restrict__ off_all, const int32_t* __restrict__ code,
+                                                      int* __restrict__ m_all, float* __restrict__ a1, float* __restrict__ a2) {
+  __shared__ int wt[4];
+  const PairSrc S = src[blockIdx.x];
+  const int cap = off_all[blockIdx.x + 1] - S.off_all;
+  int na = 0;
+  for (int m0 = 0; m0 < S.nq; m0 += 256) {
+    const int m = m0 + threadIdx.x;
+    const int32_t c = m < S.nq ? code[S.off + m] : -1;
+    const bool any = c >= 0;
+    int tot;
+    const int ra = block_rank(any, wt, tot);
+    if (any && na + ra < cap) {
+      const int id = c & MSFM_MATCH_ID_MASK;
+      const size_t e = (size_t)S.off_all + na + ra;
+      m_all[2 * e] = id; m_all[2 * e + 1] = m;
+      a1[2 * e] = S.kp1[2 * id]; a1[2 * e + 1] = S.kp1[2 * id + 1]; a2[2 * e] = S.kp2[2 * m]; a2[2 * e + 1] = S.kp2[2 * m + 1];
     }
     na += tot;
   }
@@ -169,8 +211,11 @@ struct msfm_chain {
   std::vector<const float*> kp;
   DevBuf<const float*> d_kp;
   // verification
+  bool slam = false;                     // made from a msfm_match_pairs_slam result: msfm_chain_verify_slam, not msfm_chain_verify
+  const msfm_match_result* src = nullptr;   // the result the chain was made from (compared, never read through)
   bool verified = false;
-  std::vector<int> n_good, n_all;        // sizes of matches_good / matches_all per pair (read back once at create time)
+  std::vector<int> n_good, n_all;        // sizes of matches_good / matches_all per pair (read back once at create time);
+                                         // SLAM form: n_all = survivors of the three checks, n_good is not used
   std::vector<int> n_fin, off_fin;       // matches_inliers per pair and their prefix sums
   std::vector<uint8_t> ok;
   std::vector<double> F;
@@ -200,7 +245,6 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
   MatchView v;
   MSFM_TRY(match_result_view(res, &v));
   msfm_ctx* ctx = v.ctx;
-  if (v.slam) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_create: the codes of msfm_match_pairs_slam carry no good / all sets");
   for (int p = 0; p < v.n_pairs; p++) {
     const int a = v.pairs[2 * p], b = v.pairs[2 * p + 1];
     if (!v.kp[a] || (v.count[b] > 0 && !v.kp[b]))
@@ -209,6 +253,7 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::unique_ptr<msfm_chain> C(new msfm_chain());
   C->ctx = ctx; C->n_images = v.n_images; C->n_pairs = v.n_pairs;
+  C->slam = v.slam; C->src = res;
   C->pairs.assign(v.pairs, v.pairs + 2 * (size_t)v.n_pairs);
   C->count = v.count;
   C->feat_off.assign(v.n_images + 1, 0);
@@ -240,6 +285,7 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
 MSFM_API int msfm_chain_verify(msfm_chain* C, msfm_match_result* res, const msfm_fransac_options* opt, double th_filter) {
   if (!C || !res || !opt) return MSFM_E_INVAL;
   msfm_ctx* ctx = C->ctx;
+  if (C->slam) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify: the chain was made from a msfm_match_pairs_slam result (msfm_chain_verify_slam)");
   if (C->verified) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify: already done");
   if (opt->max_iterations < 1 || opt->max_iterations > 65536 || !(opt->threshold > 0.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: bad options");
   MatchView v;
@@ -293,6 +339,75 @@ MSFM_API int msfm_chain_verify(msfm_chain* C, msfm_match_result* res, const msfm
     CH_TRY(hipStreamSynchronize(s));
     for (int p = 0; p < np; p++) C->off_fin[p + 1] = C->off_fin[p] + C->n_fin[p];
   }
+  const int M = C->off_fin[np];
+  CH_TRY(C->d_moff.from(C->off_fin, s));
+  CH_TRY(C->d_match.alloc(2 * (size_t)std::max(1, M)));
+  CH_TRY(C->d_pair.from(C->pairs.empty() ? std::vector<int>(2, 0) : C->pairs, s));
+  CH_TRY(C->d_nf.from(C->count, s));
+  CH_TRY(C->d_fo.from(C->feat_off, s));
+  if (np) {
+    KTimer t(ctx, "chain_compact_matches");
+    hipLaunchKernelGGL(chn::k_compact_matches, dim3(np), dim3(256), 0, s, d_offa.p, C->d_moff.p, in_a.p, m_all.p, C->d_match.p);
+  }
+  CH_TRY(hipGetLastError());
+  CH_TRY(sc.finish());   // the scratch above goes back to the pool
+  C->verified = true;
+  return MSFM_OK;
+}
+
+// The tail of SLAMGPS::FeatureMatching step 2 (slam_gps.cc:503-541) for every pair of a SLAM-form result: the conventions are in
+// the header comment of this file.
+MSFM_API int msfm_chain_verify_slam(msfm_chain* C, msfm_match_result* res, const msfm_fransac_options* opt) {
+  if (!C || !res || !opt) return MSFM_E_INVAL;
+  msfm_ctx* ctx = C->ctx;
+  if (!C->slam) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify_slam: the chain was made from a msfm_match_pairs result (msfm_chain_verify)");
+  if (C->verified) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify_slam: already done");
+  if (opt->max_iterations < 1 || opt->max_iterations > 65536 || !(opt->threshold > 0.0)) return msfm_set_error(ctx, MSFM_E_INVAL, "fransac: bad options");
+  if (res != C->src) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify_slam: not the match result the chain was created from");
+  MatchView v;
+  MSFM_TRY(match_result_view(res, &v));
+  if (v.ctx != ctx || v.n_pairs != C->n_pairs || !v.slam)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_verify_slam: not the match result the chain was created from");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  const int np = C->n_pairs;
+  std::vector<int> off_a(np + 1, 0);
+  for (int p = 0; p < np; p++) off_a[p + 1] = off_a[p] + C->n_all[p];
+  const int ta = off_a[np];
+  std::vector<chn::PairSrc> src(std::max(1, np));
+  for (int p = 0; p < np; p++) {
+    const int a = C->pairs[2 * p], b = C->pairs[2 * p + 1];
+    src[p] = chn::PairSrc{C->kp[a], v.nq[p] ? C->kp[b] : nullptr, v.nq[p], v.out_off[p], 0, off_a[p]};
+  }
+  DevBuf<chn::PairSrc> d_src;
+  DevBuf<int> d_offa, m_all, d_nin;
+  DevBuf<float> a1, a2;
+  DevBuf<double> dF;
+  DevBuf<uint8_t> in_a, d_ok;
+  DevScope sc(ctx);
+  CH_TRY(d_src.from(src, s)); CH_TRY(d_offa.from(off_a, s));
+  CH_TRY(m_all.alloc(2 * (size_t)std::max(1, ta))); CH_TRY(a1.alloc(2 * (size_t)std::max(1, ta))); CH_TRY(a2.alloc(2 * (size_t)std::max(1, ta)));
+  CH_TRY(dF.alloc(9 * (size_t)std::max(1, np))); CH_TRY(in_a.alloc(std::max(1, ta)));
+  CH_TRY(d_nin.alloc(std::max(1, np))); CH_TRY(d_ok.alloc(std::max(1, np)));
+  std::vector<int> n_fin(std::max(1, np), 0), off_fin(np + 1, 0);
+  std::vector<uint8_t> ok(std::max(1, np), 0);
+  std::vector<double> F(9 * (size_t)std::max(1, np), 0.0);
+  if (np) {
+    {
+      KTimer t(ctx, "chain_gather_slam");
+      hipLaunchKernelGGL(chn::k_gather_slam, dim3(np), dim3(256), 0, s, d_src.p, d_offa.p, v.code, m_all.p, a1.p, a2.p);
+    }
+    CH_TRY(hipGetLastError());
+    // GeoVerificationFundamental on all survivors (slam_gps.cc:521); the mask and n_inliers of a pair whose verdict is 0 stay
+    // as the RANSAC left them, which is what :524-529 keeps
+    MSFM_TRY(geo_fransac_dev(ctx, np, off_a.data(), d_offa.p, a1.p, a2.p, opt, dF.p, in_a.p, d_nin.p, d_ok.p));
+    CH_TRY(sc.down(n_fin.data(), d_nin.p, (size_t)np));
+    CH_TRY(sc.down(ok.data(), d_ok.p, (size_t)np));
+    CH_TRY(sc.down(F.data(), dF.p, 9 * (size_t)np));
+    CH_TRY(hipStreamSynchronize(s));
+    for (int p = 0; p < np; p++) off_fin[p + 1] = off_fin[p] + n_fin[p];
+  }
+  C->n_fin.swap(n_fin); C->off_fin.swap(off_fin); C->ok.swap(ok); C->F.swap(F);
   const int M = C->off_fin[np];
   CH_TRY(C->d_moff.from(C->off_fin, s));
   CH_TRY(C->d_match.alloc(2 * (size_t)std::max(1, M)));
