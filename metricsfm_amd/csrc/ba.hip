@@ -145,9 +145,9 @@ __device__ __forceinline__ double obs_linearize(const BaPtrs& P, int i, double& 
   return 0.5 * rho0;
 }
 // --------------------------------------------------------------------------------------
-// k_linearize: thread per active observation, rows [i0, A).  <false>: the cost only (trial points).  <true>: the stored
-// linearisation of the rows that belong to no eliminated point (i0 = AE; their point is frozen) - the rows of the
-// eliminated points are linearised inside k_point.
+// linearize_block: thread per active observation, rows [i0, A).  <false>: the cost only (trial points; a part of k_tail).
+// <true>, launched as k_linearize: the stored linearisation of the rows that belong to no eliminated point (i0 = AE; their
+// point is frozen) - the rows of the eliminated points are linearised inside k_point.
 // --------------------------------------------------------------------------------------
 template <bool WRITE_JAC>
 __device__ __forceinline__ void linearize_block(const BaPtrs& P, int i0, int blk, double* __restrict__ cost_partial, double* sh) {
@@ -157,7 +157,7 @@ __device__ __forceinline__ void linearize_block(const BaPtrs& P, int i0, int blk
     if (WRITE_JAC) {
       double r0, r1, jc[12], jm[6], jp[6];
       cost = obs_linearize(P, i, r0, r1, jc, jm, jp);
-      // stored rows exist for [AE, A) only: component-major over the A - AE rows (read by k_mcc_rest)
+      // stored rows exist for [AE, A) only: component-major over the A - AE rows (read by mcc_rest_block)
       const size_t nt = (size_t)(P.A - P.AE), it = (size_t)(i - P.AE);
       P.lin_r[it] = r0;
       P.lin_r[nt + it] = r1;
@@ -306,8 +306,6 @@ struct PointPtrs {
   // A launch enqueued BEFORE the host has seen the step it follows (msfm_ba_run): spec[0] != 0 if the device-side decision
   // (k_publish_scalars) accepted that step - else the launch ends at once - and spec[1] = the new trust-region radius.
   const double* spec;
-  int keep_T;   // MSFM_KEEP_T=1: store every T record as rounds 1-3 did (comparison)
-  int tu_direct;   // (MSFM_TU_DIRECT=0: T.u through the lane exchange as well)
 };
 
 // (4-lane groups: the two steps inside a quad.  8-lane groups: after those the four lanes of a quad hold the same value, so adding
@@ -433,7 +431,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     // once every lane is done with those) and the camera x camera products are formed from there below.
     // (16 lanes per point: (point q of 4, observation s) -> lane 4 s + q; 4 lanes per point: (point q of 16, observation s) -> lane 16 s + q)
     const int wl = tid & 63, tsrc = GW == 16 ? ((wl & 3) << 4) | (wl >> 2) : GW == 4 ? ((wl & 15) << 2) | (wl >> 4) : ((wl & 7) << 3) | (wl >> 3);
-    const bool need_T = !fold || P.fold_mc_partial == nullptr || P.keep_T;   // (uniform over the workgroup)
+    const bool need_T = !fold || P.fold_mc_partial == nullptr;   // (uniform over the workgroup)
     auto round = [&](int rd, double (&Tk)[18], int& cpk) {
       const int i = f + rd + sub;
       int cp = -1;
@@ -467,7 +465,7 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
       cpk = cp;
 #pragma unroll
       for (int k = 0; k < 18; k++) Tk[k] = T[k];
-      if (!need_T && P.tu_direct) {
+      if (!need_T) {
         // (only T.u leaves the workgroup: 48 contiguous bytes per row, stored from the lane that formed them - no exchange)
         if (cp >= 0) {
           double2* Tu2 = reinterpret_cast<double2*>(P.Tu + 6 * (size_t)cp);
@@ -1128,13 +1126,13 @@ __device__ __forceinline__ void pairs_body(int blk, int nblk, int nchunk, const 
   }
   wave_reduce_store<NOUT>(acc, partial + (size_t)chunk * NOUT, lane);
 }
-template <int DA, int DB, bool WITH_U, bool SPARSE = false>
+// (the full lists of a problem without fold tables; the sparse residue of a folded one is a part of k_sums)
+template <int DA, int DB, bool WITH_U>
 __global__ __launch_bounds__(256) void k_pairs(int nchunk, const int* __restrict__ ch_start, const int* __restrict__ ch_end,
                                                 const int* __restrict__ pa, const int* __restrict__ pb,
                                                 const double* __restrict__ TA, const double* __restrict__ TB,
-                                                const double* __restrict__ UA, size_t plane, double* __restrict__ partial,
-                                                const int* __restrict__ live = nullptr) {
-  pairs_body<DA, DB, WITH_U, SPARSE>(blockIdx.x, gridDim.x, nchunk, ch_start, ch_end, pa, pb, TA, TB, UA, plane, partial, live);
+                                                const double* __restrict__ UA, size_t plane, double* __restrict__ partial) {
+  pairs_body<DA, DB, WITH_U>(blockIdx.x, gridDim.x, nchunk, ch_start, ch_end, pa, pb, TA, TB, UA, plane, partial, nullptr);
 }
 
 // --------------------------------------------------------------------------------------
@@ -1163,8 +1161,8 @@ __global__ __launch_bounds__(256) void k_zero_system(double* __restrict__ M, int
 // full: one 3 x 3 product per point) and the zero fill of the reduced system - rounds 3-4 ran the residue and the fill as
 // four launches on a second stream beside k_ftf: two events on the main stream (13 + 6 us of idle time around them in the
 // kernel trace) and three 19 us launches for next to no work.  Here they are ONE launch on the main stream: the residue and
-// the zero tiles are its first workgroups and finish in the shadow of the camera chunks.  Same arithmetic per chunk, so the
-// partials - and the solve - are bit-identical to the separate launches (MSFM_FUSED_SUMS=0).
+// the zero tiles are its first workgroups and finish in the shadow of the camera chunks.  Same arithmetic per chunk as the
+// separate launches (k_ftf, k_pairs: the plain form of run_assemble), so the partials - and the solve - have the same bits.
 // (MSFM_ASM_BESIDE) When every camera x camera and intrinsics x camera entry is folded, the sum of a block's fold partials needs
 // k_point alone, and only the last additions of a camera's diagonal block, of its intrinsics x camera block and the rhs need the
 // per-camera sums: the fold-sum workgroups below store -sum into M beside the camera chunks (a latency-bound gather next to
@@ -1514,7 +1512,7 @@ __global__ void k_scale_scal(double* __restrict__ scal, int slot, double f) { sc
 // z = solution of S z = rhs (scaled space); step = -z.
 // --------------------------------------------------------------------------------------
 // The camera and intrinsics part of the step in one launch: the solution leaves the solver's elimination order (zsys) for
-// the block order of the BA kernels (z, read by k_backsub / k_mcc_rest), with the finiteness check on the way, and the
+// the block order of the BA kernels (z, read by k_backsub / k_tail), with the finiteness check on the way, and the
 // candidates x - z * scale go to the candidate buffers.  (Inactive blocks of the candidate buffers were filled once, at the
 // start of the run: nothing writes them.)  One launch instead of k_gather_z + k_copy3 + 2 x k_update_blocks.
 __global__ __launch_bounds__(256) void k_update_params(int ncb, int nmb, const int* __restrict__ cb_cam, const int* __restrict__ mb_model,
@@ -1698,19 +1696,11 @@ __device__ __forceinline__ void mcc_rest_block(int blk, int A, int AE, int ncb, 
   const double s = block_sum256(mcc, sh);
   if (threadIdx.x == 0) mcc_partial[blk] = s;
 }
-__global__ __launch_bounds__(256) void k_mcc_rest(int A, int AE, int ncb, const int* __restrict__ o_cb, const int* __restrict__ o_mb,
-                                                   const double* __restrict__ lin_r, const double* __restrict__ lin_Jc,
-                                                   const double* __restrict__ lin_Jm, const double* __restrict__ z, int has_gps,
-                                                   const double* __restrict__ g_r, const double* __restrict__ g_J,
-                                                   double* __restrict__ mcc_partial) {
-  __shared__ double sh[4];
-  mcc_rest_block(blockIdx.x, A, AE, ncb, o_cb, o_mb, lin_r, lin_Jc, lin_Jm, z, has_gps, g_r, g_J, mcc_partial, sh);
-}
 
 // What follows the back substitution in ONE launch: the model cost change of the rows without an eliminated point and of the GPS
-// rows (k_mcc_rest), the cost at the candidate (k_linearize<false> over all rows) and of its GPS rows (k_gps<false>) - three
-// launches of ~5 us each for the window of a new camera, whose sums then share one k_reduce.  The same workgroups with the same
-// partial slots as the separate launches (the cost partials in a buffer of their own: both sets are alive at once now).
+// rows (mcc_rest_block), the cost at the candidate (linearize_block<false> over all rows) and of its GPS rows (gps_block<false>) -
+// as three launches they cost ~5 us each for the window of a new camera; their sums share one k_reduce.  The cost partials have
+// a buffer of their own: both sets are alive at once.
 // n_zero > 0: the zero fill of the reduced system for the NEXT assembly comes first (MSFM_ASM_BESIDE: the fold-sum workgroups of
 // k_sums store into M, so the fill cannot share their launch).  The factor is dead once the back substitution has run - what
 // follows it (k_update_params, k_backsub, this launch, the next k_point) reads the solution vector only - and the stores hide
@@ -1906,7 +1896,7 @@ struct msfm_ba {
   unsigned long long scal_seq = 0;
   int* h_fail = nullptr;
   int nblk_obs = 0, nblk_pt = 0;
-  bool lin_pending = false;   // run_evaluate(jac) was asked for: the next k_point linearises, writes the camera rows and the cost
+  bool lin_pending = false;   // enqueue_linearize_rest was called: the next k_point linearises, writes the camera rows and the cost
   double lin_huber = 1.0;
   double setup_ms = 0;
   int world_at_create = 1;
@@ -2372,7 +2362,6 @@ MSFM_API void msfm_ba_destroy(msfm_ba* ba) {
   msfm_ctx* ctx = ba->ctx;
   (void)hipSetDevice(ctx->device);   // the caller's thread may have another device current (Python __del__ after set_device)
   (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);   // the pair kernels read T / Tm and write the partials freed below
   msfm_chol_ws_destroy(ba->chol_ws);
   ba->chol_ws = nullptr;
   if (ba->h_scal) (void)hipHostFree(ba->h_scal);
@@ -4123,41 +4112,24 @@ static int allreduce(msfm_ba* ba, double* buf, size_t count, int op) {
   return MSFM_OK;
 }
 
-// cost (and, with jac, the stored linearisation) at x or at the candidate -> scal[slot]
-// (local partial; summed over ranks by the caller together with the other scalars)
-static int run_evaluate(msfm_ba* ba, bool candidate, bool jac, double huber, int slot, bool with_fail = false, const double* spec = nullptr) {
+// Enqueues the linearisation of the rows that k_point does not take - those of frozen points and the GPS rows - at x or at
+// the candidate, and marks the linearisation point as new.  The rows of the eliminated points are linearised inside the next
+// k_point (run_assemble), which also writes their camera-major copies and cost partials [0, nblk_pt); the partials of these
+// rows follow them (blocks [nblk_pt, nblk_pt + ntail), then the GPS rows'), and run_assemble sums them all into S_XCOST
+// (local partial; summed over ranks together with the other scalars).  spec: see PointPtrs::spec.
+static void enqueue_linearize_rest(msfm_ba* ba, bool candidate, double huber, const double* spec = nullptr) {
   msfm_ctx* ctx = ba->ctx;
   hipStream_t s = ctx->stream;
-  const bool lead = ctx->rank == 0;
   // every rank needs the GPS rows' Jacobian (k_cam_post uses g_J via camftf only on the lead), but
   // only the lead rank counts their cost
-  const int nb = ba->nblk_obs, ng = ba->has_gps ? cdiv(ba->ncb, 256) : 0;
+  const int ng = ba->has_gps ? cdiv(ba->ncb, 256) : 0;
   BaPtrs P = make_ptrs(ba, candidate, huber);
-  if (jac) {
-    // The rows of the eliminated points are linearised inside the next k_point (run_assemble), which also writes their
-    // camera-major copies and cost partials [0, nblk_pt); here only the rows of frozen points (their blocks
-    // [nblk_pt, nblk_pt + ntail)) and the GPS rows.  The sum into `slot` follows k_point.
-    KTimer t(ctx, "ba_linearize");
-    const int ntail = cdiv(ba->A - ba->AE, 256);
-    if (ntail) hipLaunchKernelGGL(k_linearize<true>, dim3(ntail), dim3(256), 0, s, P, ba->AE, ba->partial_x.p + ba->nblk_pt, spec);
-    if (ng) hipLaunchKernelGGL(k_gps<true>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial_x.p + ba->nblk_pt + ntail, spec);
-    ba->lin_pending = true;
-    ba->lin_huber = huber;
-    (void)slot;   // S_XCOST
-    return MSFM_OK;
-  }
-  {
-    KTimer t(ctx, "ba_cost");
-    hipLaunchKernelGGL(k_linearize<false>, dim3(nb), dim3(256), 0, s, P, 0, ba->partial.p, (const double*)nullptr);
-    if (ng) hipLaunchKernelGGL(k_gps<false>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial.p + nb, (const double*)nullptr);
-    ReduceJobs rj;
-    rj.count = 1;
-    rj.job[0] = {ba->partial.p, nb + (lead ? ng : 0), slot, 0};
-    rj.fail = with_fail ? ba->fail.p : nullptr;   // after the solve: the factorisation's / finiteness failure bits are final here
-    rj.fail_slot = S_FAIL;
-    hipLaunchKernelGGL(k_reduce, dim3(1), dim3(1024), 0, s, rj, ba->swrite);
-  }
-  return MSFM_OK;
+  KTimer t(ctx, "ba_linearize");
+  const int ntail = cdiv(ba->A - ba->AE, 256);
+  if (ntail) hipLaunchKernelGGL(k_linearize<true>, dim3(ntail), dim3(256), 0, s, P, ba->AE, ba->partial_x.p + ba->nblk_pt, spec);
+  if (ng) hipLaunchKernelGGL(k_gps<true>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial_x.p + ba->nblk_pt + ntail, spec);
+  ba->lin_pending = true;
+  ba->lin_huber = huber;
 }
 
 // The point kernel: linearises the rows of the eliminated points at x (or, `candidate`, at the candidate: the launch that
@@ -4180,8 +4152,6 @@ static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius,
   Q.fold_pass = F.pass.p; Q.fold_stream = F.stream.p; Q.fold_partial = F.partial.p;
   Q.fold_mc_partial = (F.on && F.mc_on) ? F.mc_partial.p : nullptr;
   Q.spec = spec;
-  Q.keep_T = ba->env.keep_t ? 1 : 0;
-  Q.tu_direct = ba->env.tu_direct ? 1 : 0;
   hipLaunchKernelGGL(k_point, dim3(ba->nblk_pt), dim3(256), 0, ctx->stream, Q, ba->gmax_buf.p);
 }
 
@@ -4203,8 +4173,21 @@ static int ba_zero_map(const msfm_ba* ba, ZeroMap& Z) {
 // partials that the same launch writes), no per-class timers, a system the ZeroMap holds.
 static bool asm_beside_ok(const msfm_ba* ba) {
   const FoldTables& F = ba->fold;
-  return ba->env.asm_beside && ba->env.fused_sums && ba->ctx->world <= 1 && !ba->ctx->profile && ba->ncb > 0 && ba->nmb <= 1 && ba->n_fchunks > 0 && F.on && F.all &&
+  return ba->env.asm_beside && ba->ctx->world <= 1 && !ba->ctx->profile && ba->ncb > 0 && ba->nmb <= 1 && ba->n_fchunks > 0 && F.on && F.all &&
          (ba->mc.n_blocks == 0 || (F.mc_on && F.mc_all)) && ba->npad / 64 <= 256;
+}
+// The form a mode-0 assembly takes between k_point and the factorisation (run_assemble; run_solve asks for the NEXT assembly's):
+//   beside  k_sums with the fold-sum workgroups, k_camftf / k_modelsum finish the blocks in M, no k_asm_all
+//   fused   k_sums with the zero tiles (per-camera sums, pair-list residue or short full lists, zero fill in one launch), k_asm_all
+//   plain   k_ftf, the k_pairs launches, the zero fill and k_asm_all one after the other
+// fused also takes the problems too small for the fold tables - the window of a new camera: their full pair lists are three
+// latency-bound launches of 13-25 us one after the other.  A LARGE problem without fold tables keeps the separate launches,
+// whose pair kernels want more waves per SIMD than k_sums has; so does one without camera chunks, which has nothing to fuse.
+enum AsmForm { ASM_PLAIN, ASM_FUSED, ASM_BESIDE };
+static AsmForm asm_form(const msfm_ba* ba) {
+  if (asm_beside_ok(ba)) return ASM_BESIDE;
+  if (ba->n_fchunks > 0 && (ba->fold.on || ba->cc.n_pairs < 262144)) return ASM_FUSED;
+  return ASM_PLAIN;
 }
 
 // point kernel + camera sums (+, for mode 0, the reduced system in M).  point_enqueued: the point kernel of this
@@ -4219,86 +4202,32 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
   const bool store_rows = ba->lin_pending;   // new linearisation point (else: the same rows again, new radius)
   ba->lin_pending = false;
   if (!point_enqueued) launch_point(ba, opt, radius, reuse_diag, mode, store_rows, false, nullptr);
-  // The Schur pair products read only what k_point wrote (T, Tm, Tmu) and write their own partials; the per-camera sums
-  // (k_ftf ... k_modelsum, with the multi-rank exchange of camftf) read T.u and the camera rows.  Outside profiling runs
-  // the pair products therefore go to a second stream beside them and the two meet again at the assembly (with the
-  // per-class timers on, everything stays on the main stream so that the timings remain per kernel).
-  // (order: the two small lists first - they share the chip with k_ftf, which needs the bandwidth as much as the
-  // camera x camera list does, so those two would only slow each other down - and the large list last, beside the
-  // latency-bound k_camftf / k_modelsum / k_reduce tail of the main stream)
-  auto launch_pairs = [&](hipStream_t sp) {
-    if (ba->fold.on && ba->fold.mc_on) {
-      if (ba->fold.mc_n_live)
-        hipLaunchKernelGGL((k_pairs<3, 6, false, true>), dim3(cdiv(ba->fold.mc_n_live, 4)), dim3(256), 0, sp, ba->fold.mc_n_live, ba->mc.ch_start.p,
-                           ba->mc.ch_end.p, ba->mc.pa.p, ba->mc.pb.p, ba->Tm.p, ba->T.p, (const double*)nullptr, (size_t)std::max(1, ba->NCR),
-                           ba->mc.partial.p, ba->fold.mc_live_chunk.p);
-    } else if (ba->mc.n_chunks)
-      hipLaunchKernelGGL((k_pairs<3, 6, false>), dim3(cdiv(ba->mc.n_chunks, 4)), dim3(256), 0, sp, ba->mc.n_chunks, ba->mc.ch_start.p,
-                         ba->mc.ch_end.p, ba->mc.pa.p, ba->mc.pb.p, ba->Tm.p, ba->T.p, (const double*)nullptr, (size_t)std::max(1, ba->NCR), ba->mc.partial.p);
+  const AsmForm form = mode == 0 ? asm_form(ba) : ASM_PLAIN;   // (mode 1 takes the per-camera sums only: k_ftf)
+  const bool fused = form != ASM_PLAIN, beside = form == ASM_BESIDE;
+  // plain form: the Schur pair products read only what k_point wrote (T, Tm, Tmu) and write their own partials (the fold tables
+  // are off here - with them the assembly is fused - so the lists are the full ones)
+  auto launch_pairs = [&]() {
+    const size_t ncr = (size_t)std::max(1, ba->NCR);
+    if (ba->mc.n_chunks)
+      hipLaunchKernelGGL((k_pairs<3, 6, false>), dim3(cdiv(ba->mc.n_chunks, 4)), dim3(256), 0, s, ba->mc.n_chunks, ba->mc.ch_start.p,
+                         ba->mc.ch_end.p, ba->mc.pa.p, ba->mc.pb.p, ba->Tm.p, ba->T.p, (const double*)nullptr, ncr, ba->mc.partial.p);
     if (ba->mm.n_chunks)
-      hipLaunchKernelGGL((k_pairs<3, 3, true>), dim3(cdiv(ba->mm.n_chunks, 4)), dim3(256), 0, sp, ba->mm.n_chunks, ba->mm.ch_start.p,
+      hipLaunchKernelGGL((k_pairs<3, 3, true>), dim3(cdiv(ba->mm.n_chunks, 4)), dim3(256), 0, s, ba->mm.n_chunks, ba->mm.ch_start.p,
                          ba->mm.ch_end.p, ba->mm.pa.p, ba->mm.pb.p, ba->Tm.p, ba->Tm.p, ba->Tmu.p, (size_t)0, ba->mm.partial.p);
-    if (ba->fold.on) {
-      if (ba->fold.n_live)
-        hipLaunchKernelGGL((k_pairs<6, 6, false, true>), dim3(cdiv(ba->fold.n_live, 4)), dim3(256), 0, sp, ba->fold.n_live, ba->cc.ch_start.p,
-                           ba->cc.ch_end.p, ba->cc.pa.p, ba->cc.pb.p, ba->T.p, ba->T.p, (const double*)nullptr, (size_t)std::max(1, ba->NCR),
-                           ba->cc.partial.p, ba->fold.live_chunk.p);
-    } else if (ba->cc.n_chunks)
-      hipLaunchKernelGGL((k_pairs<6, 6, false>), dim3(cdiv(ba->cc.n_chunks, 4)), dim3(256), 0, sp, ba->cc.n_chunks, ba->cc.ch_start.p,
-                         ba->cc.ch_end.p, ba->cc.pa.p, ba->cc.pb.p, ba->T.p, ba->T.p, (const double*)nullptr, (size_t)std::max(1, ba->NCR), ba->cc.partial.p);
+    if (ba->cc.n_chunks)
+      hipLaunchKernelGGL((k_pairs<6, 6, false>), dim3(cdiv(ba->cc.n_chunks, 4)), dim3(256), 0, s, ba->cc.n_chunks, ba->cc.ch_start.p,
+                         ba->cc.ch_end.p, ba->cc.pa.p, ba->cc.pb.p, ba->T.p, ba->T.p, (const double*)nullptr, ncr, ba->cc.partial.p);
   };
-  // Round 3: with the gather path (the three pair kernels fill the chip by themselves) the fork gave nothing (1.277 ms per
-  // iteration with it, 1.255-1.273 without); with the fold tables the pair kernels are three short launches and the fork
-  // pays again (1.251 -> 1.229 ms per iteration at config 3).  So: forked when the fold tables are on.
-  const bool overlap = ba->fold.on;
-  // (round 4, later: with the fold tables and one intrinsics block everything between k_point and the assembly is ONE launch on
-  //  the main stream - k_sums - and nothing is forked)
-  // (also for the problems too small for the fold tables - the window of a new camera: their full pair lists are three
-  //  latency-bound launches of 13-25 us one after the other; a LARGE problem without fold tables keeps the separate launches,
-  //  whose pair kernels want more waves per SIMD than this launch has)
-  const bool fused = mode == 0 && ba->n_fchunks > 0 && (ba->fold.on || ba->cc.n_pairs < 262144) && ba->env.fused_sums;
-  const bool forked = mode == 0 && !ctx->profile && overlap && !fused;
-  const bool beside = fused && asm_beside_ok(ba);
   const bool m_zeroed = ba->m_zeroed;
   if (mode == 0) { ba->m_zeroed = false; ba->n_defer = 0; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; }
-  // zero fill of the reduced system in front of the assembly (reads nothing: with the fork it runs on the second stream too)
-  auto zero_system = [&](hipStream_t sz) -> int {
-    const int nb64 = ba->npad / 64;
-    if (ctx->world > 1 || nb64 > 256) {
-      // (several ranks sum whole rows of M: every entry must be defined)
-      HIP_TRY(ctx, hipMemsetAsync(ba->M.p, 0, sizeof(double) * (size_t)ba->npad * ba->npad, sz));
-    } else {
-      ZeroMap Z;
-      Z.nb = nb64;
-      for (int b = 0; b < nb64; b++) { Z.lev[b] = 127; Z.lo[b] = 0; Z.hi[b] = 0x7fff; }   // root chain / dense order: couples to everything
-      for (int lv = 0; lv < ba->plan.n_levels; lv++)
-        for (int k = 0; k < ba->plan.level[lv].K; k++) {
-          const msfm_chol_node& nd = ba->plan.level[lv].node[k];
-          for (int b = nd.begin / 64; b < nd.end / 64; b++) { Z.lev[b] = (unsigned char)lv; Z.lo[b] = (short)nd.leaf_lo; Z.hi[b] = (short)nd.leaf_hi; }
-        }
-      hipLaunchKernelGGL(k_zero_system, dim3(nb64 * (nb64 + 1) / 2), dim3(256), 0, sz, ba->M.p, ba->npad, Z);
-    }
+  // zero fill of the reduced system in front of the assembly, as a launch of its own
+  auto zero_system = [&]() -> int {
+    ZeroMap Z;
+    const int n_zero = ba_zero_map(ba, Z);
+    if (n_zero) hipLaunchKernelGGL(k_zero_system, dim3(n_zero), dim3(256), 0, s, ba->M.p, ba->npad, Z);
+    else HIP_TRY(ctx, hipMemsetAsync(ba->M.p, 0, sizeof(double) * (size_t)ba->npad * ba->npad, s));   // (several ranks sum whole rows of M: every entry must be defined)
     return MSFM_OK;
   };
-  if (forked) {
-    if (!ctx->stream2) {
-      HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-      HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-    }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, s));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    launch_pairs(ctx->stream2);
-    MSFM_TRY(zero_system(ctx->stream2));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-  }
-  // Every way out of this function from here on - the error returns of the collective hook and of HIP_TRY included - must
-  // leave the second stream joined: whoever synchronises ctx->stream afterwards (msfm_ba_destroy, the pool) then also
-  // waits for the pair kernels that read T / Tm and write the partials.
-  struct JoinGuard {
-    msfm_ctx* c; hipStream_t s; bool armed;
-    ~JoinGuard() { if (armed && hipStreamWaitEvent(s, c->ev_join, 0) != hipSuccess) (void)hipStreamSynchronize(c->stream2); }
-  } join{ctx, s, forked};
   double* gmax_c = ba->gmax_buf.p + ba->nblk_pt;
   double* gmax_m = gmax_c + 6 * (size_t)ncb;
   {
@@ -4308,7 +4237,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       SumsArgs a;
       // (beside: the fold-sum workgroups store into M, so it is zeroed beforehand - by the k_tail of the last solve, or here)
       a.n_zero = beside ? 0 : ba_zero_map(ba, a.Z);
-      if (beside ? !m_zeroed : a.n_zero == 0) MSFM_TRY(zero_system(s));
+      if (beside ? !m_zeroed : a.n_zero == 0) MSFM_TRY(zero_system());
       a.M = ba->M.p; a.ld = ba->npad;
       const bool mc_sparse = ba->fold.on && ba->fold.mc_on;
       a.mc_n = mc_sparse ? ba->fold.mc_n_live : ba->mc.n_chunks; a.mc_start = ba->mc.ch_start.p; a.mc_end = ba->mc.ch_end.p; a.mc_pa = ba->mc.pa.p; a.mc_pb = ba->mc.pb.p;
@@ -4368,14 +4297,14 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     rj.count = 1;
     rj.job[0] = {ba->gmax_buf.p, ba->nblk_pt + 6 * ncb + 3 * nmb, S_GMAX, 1};
     if (store_rows) {
-      // cost at x: k_point's blocks, the frozen points' rows, the GPS rows (lead rank only) - see run_evaluate
+      // cost at x: k_point's blocks, the frozen points' rows, the GPS rows (lead rank only) - see enqueue_linearize_rest
       const int ntail = cdiv(ba->A - ba->AE, 256), ng = (ba->has_gps && lead) ? cdiv(ncb, 256) : 0;
       rj.job[1] = {ba->partial_x.p, ba->nblk_pt + ntail + ng, S_XCOST, 0};
       rj.count = 2;
     }
     rj.fail = ba->fail.p;
     rj.fail_slot = S_FAIL;
-    if (beside && will_solve && ba->env.fused_tail) {
+    if (beside && will_solve) {
       // nothing reads these sums before k_publish_scalars: the last k_reduce of the step takes them (run_solve), off the path
       // to the factorisation
       ba->n_defer = rj.count;
@@ -4384,17 +4313,13 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
     }
   }
-  if (forked) {
-    join.armed = false;
-    const hipError_t je = hipStreamWaitEvent(s, ctx->ev_join, 0);
-    if (je != hipSuccess) { (void)hipStreamSynchronize(ctx->stream2); HIP_TRY(ctx, je); }
-  } else if (!fused) {
+  if (!fused) {
     KTimer t(ctx, "ba_schur_pairs");
-    launch_pairs(s);
+    launch_pairs();
   }
   {
     KTimer t(ctx, "ba_assemble");
-    if (!forked && !fused) MSFM_TRY(zero_system(s));   // (forked: done on the second stream beside the per-camera sums, joined above)
+    if (!fused) MSFM_TRY(zero_system());
     AsmArgs aa;
     aa.n_cc = ba->cc.n_blocks; aa.n_mc = ba->mc.n_blocks; aa.n_mm = ba->mm.n_blocks; aa.n_rhs = cdiv(6 * ncb, 64);
     aa.cc_row = ba->cc.blk_row.p; aa.cc_col = ba->cc.blk_col.p; aa.cc_first = (ba->fold.on && ba->fold.all) ? nullptr : ba->cc.blk_chunk_first.p; aa.cc_partial = ba->cc.partial.p;
@@ -4509,19 +4434,17 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     ba->zflip ^= 1;   // only a completed solve hands the other half over
     zsolved = zcur;
   }
+  int off = 0, moff = 0;   // partial2 = |dx|^2 partials, partial3 = |x|^2 partials (off of each), partial = model cost partials (moff)
   {
     KTimer t(ctx, "ba_backsub");
     const int nbu = cdiv(std::max(1, ba->nred), 256), nbp = ba->nblk_pt;
-    int off = 0;
     const double wrep = lead ? 1.0 : 0.0;
-    // partial2 = |dx|^2 partials, partial3 = |x|^2 partials, partial = model cost partials
     if (ba->nred > 0) {
       hipLaunchKernelGGL(k_update_params, dim3(nbu), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo, zsolved,
                          ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->cam_c.p, ba->model.p, ba->model_c.p, ba->z.p, ba->fail.p,
                          ba->partial2.p + off, ba->partial3.p + off, wrep);
       off += nbu;
     }
-    int moff = 0;
     if (npb) {
       BackPtrs Q;
       Q.B = make_ptrs(ba, false, ba->lin_huber);
@@ -4533,58 +4456,40 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     } else {
       hipLaunchKernelGGL(k_rot_cache, dim3(cdiv(std::max(1, ba->Nc), 256)), dim3(256), 0, s, ba->Nc, ba->cam_c.p, ba->rot_c.p);
     }
+  }
+  {
+    // model cost change of the remaining rows + cost at the candidate (all rows, GPS rows) in one launch, one reduction for
+    // the four sums (the failure bits of the factorisation / finiteness checks are final here)
+    KTimer t(ctx, "ba_cost");
     const int ngps = (ba->has_gps && lead) ? ncb : 0;
     const int nrest = (ba->A - ba->AE) + ngps;
-    if (ba->env.fused_tail) {
-      // model cost change of the remaining rows + cost at the candidate (all rows, GPS rows) in one launch, one reduction for
-      // the four sums (the failure bits of the factorisation / finiteness checks are final here)
-      t.stop();   // (the class ba_backsub ends here: what follows is timed as ba_cost)
-      TailArgs a;
-      // (the factor in M is dead behind the back substitution: zeroed here for the next assembly where that one sums beside)
-      a.n_zero = (ba->nred > 0 && asm_beside_ok(ba)) ? ba_zero_map(ba, a.Z) : 0;
-      a.M = ba->M.p; a.ld = ba->npad;
-      a.n_mcc = nrest ? cdiv(nrest, 256) : 0;
-      a.A = ba->A; a.AE = ba->AE; a.ncb = ncb; a.o_cb = ba->o_cb.p; a.o_mb = ba->o_mb.p; a.lin_r = ba->lin_r.p; a.lin_Jc = ba->lin_Jc.p; a.lin_Jm = ba->lin_Jm.p;
-      a.z = ba->z.p; a.has_gps = ngps ? 1 : 0; a.g_r = ba->g_r.p; a.g_J = ba->g_J.p; a.mcc_partial = ba->partial.p + moff;
-      moff += a.n_mcc;
-      a.P = make_ptrs(ba, /*candidate=*/true, opt->huber_delta);
-      a.n_cost = ba->nblk_obs; a.cost_partial = ba->partial4.p;
-      a.n_gps = ba->has_gps ? cdiv(ncb, 256) : 0;
-      a.cb_cam = ba->cb_cam.p; a.cam_c = a.P.cam; a.gps = ba->gps.p; a.gps_weight = ba->gps_weight; a.huber = opt->huber_delta; a.scale_c = ba->scale_c.p;
-      a.g_r_w = ba->g_r.p; a.g_J_w = ba->g_J.p;   // (not written: WRITE_JAC is false)
-      KTimer t2(ctx, "ba_cost");
-      hipLaunchKernelGGL(k_tail, dim3(a.n_zero + a.n_mcc + a.n_cost + a.n_gps), dim3(256), 0, s, a);
-      ba->m_zeroed = a.n_zero > 0;
-      ReduceJobs rj;
-      rj.count = 4;
-      rj.job[0] = {ba->partial.p, moff, S_MCC, 0};
-      rj.job[1] = {ba->partial2.p, off, S_DX2, 0};
-      rj.job[2] = {ba->partial3.p, off, S_X2, 0};
-      rj.job[3] = {ba->partial4.p, a.n_cost + (lead ? a.n_gps : 0), S_COST, 0};
-      for (int j = 0; j < ba->n_defer; j++) rj.job[rj.count++] = {ba->defer[j].p, ba->defer[j].n, ba->defer[j].slot, ba->defer[j].is_max};   // (the assembly's: S_GMAX, S_XCOST)
-      ba->n_defer = 0;
-      rj.fail = ba->fail.p;
-      rj.fail_slot = S_FAIL;
-      hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
-      hipError_t e2 = hipGetLastError();
-      if (e2 != hipSuccess) return msfm_set_error(ctx, MSFM_E_DEVICE, "solve launch: %s", hipGetErrorString(e2));
-      return MSFM_OK;
-    }
-    if (nrest) {
-      hipLaunchKernelGGL(k_mcc_rest, dim3(cdiv(nrest, 256)), dim3(256), 0, s, ba->A, ba->AE, ncb, ba->o_cb.p, ba->o_mb.p, ba->lin_r.p,
-                         ba->lin_Jc.p, ba->lin_Jm.p, ba->z.p, ngps ? 1 : 0, ba->g_r.p, ba->g_J.p, ba->partial.p + moff);
-      moff += cdiv(nrest, 256);
-    }
+    TailArgs a;
+    // (the factor in M is dead behind the back substitution: zeroed here for the next assembly where that one sums beside)
+    a.n_zero = (ba->nred > 0 && asm_form(ba) == ASM_BESIDE) ? ba_zero_map(ba, a.Z) : 0;
+    a.M = ba->M.p; a.ld = ba->npad;
+    a.n_mcc = nrest ? cdiv(nrest, 256) : 0;
+    a.A = ba->A; a.AE = ba->AE; a.ncb = ncb; a.o_cb = ba->o_cb.p; a.o_mb = ba->o_mb.p; a.lin_r = ba->lin_r.p; a.lin_Jc = ba->lin_Jc.p; a.lin_Jm = ba->lin_Jm.p;
+    a.z = ba->z.p; a.has_gps = ngps ? 1 : 0; a.g_r = ba->g_r.p; a.g_J = ba->g_J.p; a.mcc_partial = ba->partial.p + moff;
+    moff += a.n_mcc;
+    a.P = make_ptrs(ba, /*candidate=*/true, opt->huber_delta);
+    a.n_cost = ba->nblk_obs; a.cost_partial = ba->partial4.p;
+    a.n_gps = ba->has_gps ? cdiv(ncb, 256) : 0;
+    a.cb_cam = ba->cb_cam.p; a.cam_c = a.P.cam; a.gps = ba->gps.p; a.gps_weight = ba->gps_weight; a.huber = opt->huber_delta; a.scale_c = ba->scale_c.p;
+    a.g_r_w = ba->g_r.p; a.g_J_w = ba->g_J.p;   // (not written: WRITE_JAC is false)
+    hipLaunchKernelGGL(k_tail, dim3(a.n_zero + a.n_mcc + a.n_cost + a.n_gps), dim3(256), 0, s, a);
+    ba->m_zeroed = a.n_zero > 0;
     ReduceJobs rj;
-    rj.count = 3;
+    rj.count = 4;
     rj.job[0] = {ba->partial.p, moff, S_MCC, 0};
     rj.job[1] = {ba->partial2.p, off, S_DX2, 0};
     rj.job[2] = {ba->partial3.p, off, S_X2, 0};
-    rj.fail = nullptr;
+    rj.job[3] = {ba->partial4.p, a.n_cost + (lead ? a.n_gps : 0), S_COST, 0};
+    for (int j = 0; j < ba->n_defer; j++) rj.job[rj.count++] = {ba->defer[j].p, ba->defer[j].n, ba->defer[j].slot, ba->defer[j].is_max};   // (the assembly's: S_GMAX, S_XCOST)
+    ba->n_defer = 0;
+    rj.fail = ba->fail.p;
     rj.fail_slot = S_FAIL;
-    hipLaunchKernelGGL(k_reduce, dim3(3), dim3(1024), 0, s, rj, ba->swrite);
+    hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
   }
-  MSFM_TRY(run_evaluate(ba, /*candidate=*/true, /*jac=*/false, opt->huber_delta, S_COST, /*with_fail=*/true));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return msfm_set_error(ctx, MSFM_E_DEVICE, "solve launch: %s", hipGetErrorString(e));
   return MSFM_OK;
@@ -4640,7 +4545,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
   double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
   bool reuse_diag = false;
   // ---- IterationZero ----
-  MSFM_TRY(run_evaluate(ba, false, true, opt->huber_delta, S_XCOST));
+  enqueue_linearize_rest(ba, false, opt->huber_delta);
   lap("first evaluate enqueued");
   if (opt->jacobi_scaling) {
     // squared column norms of the corrected, unscaled Jacobian -> scaling -> re-linearise scaled
@@ -4648,7 +4553,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     if (ncb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(6 * ncb, 256)), dim3(256), 0, s, 6 * ncb, ba->diag_c.p, ba->scale_c.p);
     if (nmb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(3 * nmb, 256)), dim3(256), 0, s, 3 * nmb, ba->diag_m.p, ba->scale_m.p);
     if (npb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(3 * npb, 256)), dim3(256), 0, s, 3 * npb, ba->diag_p.p, ba->scale_p.p);
-    MSFM_TRY(run_evaluate(ba, false, true, opt->huber_delta, S_XCOST));
+    enqueue_linearize_rest(ba, false, opt->huber_delta);
   }
   int iteration = 0, num_invalid = 0, termination = 0;
   lap("iteration zero enqueued");
@@ -4676,7 +4581,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     spec_inflight = false;
     if (D.on && ba->spec_on) {
       // x_{k+1} would be the present candidate buffers
-      MSFM_TRY(run_evaluate(ba, /*candidate=*/true, /*jac=*/true, opt->huber_delta, S_XCOST, false, ba->spec.p));
+      enqueue_linearize_rest(ba, /*candidate=*/true, opt->huber_delta, ba->spec.p);
       launch_point(ba, opt, radius, false, 0, true, /*candidate=*/true, ba->spec.p);
       ba->lin_pending = false;   // becomes true again if the host finds the step accepted
       spec_inflight = true;
@@ -4750,7 +4655,7 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
         ba->lin_huber = opt->huber_delta;
         point_enqueued = true;
       } else {
-        MSFM_TRY(run_evaluate(ba, false, true, opt->huber_delta, S_XCOST));
+        enqueue_linearize_rest(ba, false, opt->huber_delta);
       }
     }
     MSFM_TRY(assemble_and_step(point_enqueued));

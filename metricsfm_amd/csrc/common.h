@@ -32,11 +32,7 @@ struct msfm_env {
   long fold_min = 262144;         // MSFM_FOLD_MIN: camera pairs below which a problem keeps the gather path
   bool no_fold = false;           // MSFM_NO_FOLD (set): the gather path whatever the size
   long lanes4_min = -1;           // MSFM_LANES4_MIN: eliminated points above which those of up to 4 rows get 4 lanes (ptmap_use_lanes4; -1: default)
-  bool fused_sums = true;         // MSFM_FUSED_SUMS=0: per-camera sums, pair-list residue and zero fill as separate launches
-  bool fused_tail = true;         // MSFM_FUSED_TAIL=0: the launches behind the back substitution one by one
   bool asm_beside = true;         // MSFM_ASM_BESIDE=0: the Schur fold partials summed after the per-camera sums (k_asm_all), not beside them
-  bool keep_t = false;            // MSFM_KEEP_T=1: folding workgroups store their T records too
-  bool tu_direct = true;          // MSFM_TU_DIRECT=0: T.u through the lane exchange
   bool spec = true;               // MSFM_SPEC=0: the next linearisation enqueued only after the step's read-back
   // process-wide
   size_t pool_bytes = (size_t)16384 << 20;   // MSFM_POOL_MB: freed device blocks the cache keeps
@@ -53,11 +49,9 @@ const msfm_env& msfm_env_process();    // its first reading, kept for the life o
 
 struct msfm_ctx {
   int device = 0;
+  // the context's one stream: the library opens no other on a context, so whoever waits for it has waited for everything
+  // the context enqueued
   hipStream_t stream = nullptr;
-  // second stream for work that does not depend on what the main stream is doing (the Schur pair products run beside
-  // the per-camera sums: both only read what k_point wrote); created on first use, fork / join by the two events
-  hipStream_t stream2 = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   std::string err;
   // multi-GPU hook
   msfm_allreduce_fn allreduce = nullptr;

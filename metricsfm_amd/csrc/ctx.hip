@@ -23,11 +23,7 @@ msfm_env msfm_env_read() {
   if (const char* e = get("MSFM_FOLD_MIN")) E.fold_min = atol(e);
   E.no_fold = get("MSFM_NO_FOLD") != nullptr;
   if (const char* e = get("MSFM_LANES4_MIN")) E.lanes4_min = atol(e);
-  E.fused_sums = num("MSFM_FUSED_SUMS", 1) != 0;
-  E.fused_tail = num("MSFM_FUSED_TAIL", 1) != 0;
   E.asm_beside = num("MSFM_ASM_BESIDE", 1) != 0;
-  E.keep_t = num("MSFM_KEEP_T", 0) != 0;
-  E.tu_direct = num("MSFM_TU_DIRECT", 1) != 0;
   E.spec = num("MSFM_SPEC", 1) != 0;
   if (const char* e = get("MSFM_POOL_MB")) E.pool_bytes = (size_t)atol(e) << 20;
   E.pool_debug = get("MSFM_POOL_DEBUG") != nullptr;
@@ -200,10 +196,6 @@ MSFM_API void msfm_ctx_destroy(msfm_ctx* ctx) {
   if (ctx->ba_scratch && ctx->ba_scratch_free) ctx->ba_scratch_free(ctx->ba_scratch);
   for (auto& p : ctx->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
   for (auto e : ctx->event_pool) (void)hipEventDestroy(e);
-  if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);   // before its events go
-  if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-  if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);
-  if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);
   (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }

@@ -265,7 +265,7 @@ def test_ba_full_size_properties(ctx, monkeypatch):
 
 def test_ba_two_runs_are_bitwise_identical(ctx):
     """Determinism: every reduction has a fixed shape, so two solves of the headline configuration - fold
-    tables on, pair kernels on the second stream - give bitwise the same trajectory and parameters."""
+    tables on - give bitwise the same trajectory and parameters."""
     from metricsfm_amd import capi
     sc = scene.config_scene(3)
     runs = []
@@ -317,7 +317,10 @@ def test_ba_one_model_per_camera_beyond_the_corner_table(ctx):
 def test_ba_folded_schur_products_match_the_oracle_and_the_gather_path(oracle):
     """The camera x camera Schur products formed inside k_point (FoldTables, ba.hip) instead of by the gather kernel: forced on
     for small problems (MSFM_FOLD_MIN=0) - long tracks that need the second-round record area, frozen cameras / points, several
-    intrinsics blocks, GPS rows - each against the oracle, and against the gather path (MSFM_NO_FOLD=1) to rounding."""
+    intrinsics blocks, GPS rows - each against the oracle, and against the gather path (MSFM_NO_FOLD=1) to rounding.
+    A folding workgroup does not store its T records (their only readers are pair-list entries that did not fold, and a
+    workgroup folds all of its entries or none) and sends T.u out without the lane exchange: a reader of an unstored record
+    would show against the oracle here."""
     import subprocess
     import sys
     code = ("import sys, numpy as np; sys.path.insert(0, %r)\n"
@@ -343,21 +346,54 @@ def test_ba_folded_schur_products_match_the_oracle_and_the_gather_path(oracle):
             "run(sc, cam_mutable=cm, pt_mutable=pm, gps_xyz=sc.gps_xyz, gps_weight=50.0)\n"
             "print(repr(out))\n") % ROOT
     outs = {}
-    for name, env in (("fold", dict(MSFM_FOLD_MIN="0")), ("gather", dict(MSFM_NO_FOLD="1")), ("fold_separate_launches", dict(MSFM_FOLD_MIN="0", MSFM_FUSED_SUMS="0")),
-                      ("fold_all_T_stored", dict(MSFM_FOLD_MIN="0", MSFM_KEEP_T="1", MSFM_TU_DIRECT="0"))):
+    for name, env in (("fold", dict(MSFM_FOLD_MIN="0")), ("gather", dict(MSFM_NO_FOLD="1"))):
         r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-3000:]
         outs[name] = eval(r.stdout.strip().splitlines()[-1])
     for a, b in zip(outs["fold"], outs["gather"]):
         np.testing.assert_allclose(a, b, rtol=1e-8)   # (the two paths sum in different orders: equal only to rounding; both
                                                       #  already matched the oracle to 1e-9 above, rejected trial steps included)
-    # round 4: per-camera sums, pair-list residue and zero fill as ONE launch (k_sums) against the separate launches on two streams:
-    # the same arithmetic per chunk, so every cost of every trajectory is the same number
-    assert outs["fold"] == outs["fold_separate_launches"]
-    # round 4: a folding workgroup does not store its T records (their only readers are pair-list entries that did not fold, and a
-    # workgroup folds all of its entries or none) and sends T.u out without the lane exchange: storing everything as before
-    # must give the same numbers - a reader of an unstored record would show here
-    assert outs["fold"] == outs["fold_all_T_stored"]
+
+
+def test_ba_plain_assembly_form_matches_the_oracle_and_itself(oracle, monkeypatch):
+    """The assembly as separate launches (k_ftf, the k_pairs launches, the zero fill, k_asm_all: the plain form of run_assemble) -
+    what a large problem without fold tables takes, and a problem without camera chunks.  (a) 26 ring cameras x 1000 points
+    with the fold tables off: every point is seen by every camera, 26 * 25 / 2 * 1000 = 325 000 camera pairs before the diagonal ones, above the
+    262 144 at which a problem without fold tables leaves k_sums; against the oracle, and two runs in fresh contexts bitwise
+    equal.  (b) one intrinsics block, every camera frozen, the points free: no camera block, so no camera chunk (the rows of a
+    frozen camera hold its intrinsics constant too, so nothing is left in the reduced system: the points move alone)."""
+    from metricsfm_amd import capi
+    monkeypatch.setenv("MSFM_NO_FOLD", "1")
+    sc = scene.make_ring_scene(26, 1000, seed=76)
+    arrays = lambda: A.BaArrays.from_scene(sc)
+    runs = []
+    for first in (True, False):
+        c = capi.Context(0)
+        try:
+            if first:
+                ba = c.ba(arrays())
+                fold = ba.layout()["fold"]
+                ba.close()
+                assert fold["cc_entries"] >= 262144 and fold["cc_entries_folded"] == 0, fold
+                r, _, a = check_parity(c, oracle, arrays, dict(max_num_iterations=8))
+            else:
+                a = arrays()
+                r = c.ba_solve(a, capi.default_options(max_num_iterations=8))
+            runs.append((r, a))
+        finally:
+            c.close()
+    (r0, a0), (r1, a1) = runs
+    for key in ("cost", "gradient_max_norm", "step_norm", "trust_region_radius"):
+        np.testing.assert_array_equal(r0["iterations"][key], r1["iterations"][key])
+    for name in ("cam_pose", "cam_model", "point"):
+        np.testing.assert_array_equal(getattr(a0, name), getattr(a1, name))
+    sc6 = scene.make_ring_scene(6, 300, seed=77)
+    c = capi.Context(0)
+    try:
+        r, _, a = check_parity(c, oracle, lambda: A.BaArrays.from_scene(sc6, cam_mutable=np.zeros(6, np.uint8)), dict(max_num_iterations=8))
+    finally:
+        c.close()
+    assert r["num_reduced_params"] == 0 and r["num_successful_steps"] >= 1 and (a.cam_pose == sc6.cam_pose).all()
 
 
 def test_ba_domains_with_window_masks(ctx, oracle, monkeypatch):
@@ -692,15 +728,11 @@ def test_ba_device_side_verdict_and_launch_ahead_are_bit_identical_to_the_host_o
     ]
     for mk, kw in cases:
         out = []
-        # (third variant: the launches behind the back substitution - model cost change of the remaining rows, cost at the
-        #  candidate, its GPS rows - separately instead of as k_tail with one reduction for the four sums)
-        for spec, tail in (("0", "1"), ("1", "1"), ("1", "0")):
+        for spec in ("0", "1"):
             monkeypatch.setenv("MSFM_SPEC", spec)
-            monkeypatch.setenv("MSFM_FUSED_TAIL", tail)
             a = mk()
             r = ctx.ba_solve(a, capi.default_options(**kw))
             out.append((r, a))
-        monkeypatch.delenv("MSFM_FUSED_TAIL")
         (r0, a0) = out[0]
         for (r1, a1) in out[1:]:
             assert r0["termination"] == r1["termination"] and r0["num_iterations"] == r1["num_iterations"]

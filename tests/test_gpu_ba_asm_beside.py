@@ -161,6 +161,3 @@ def test_asm_beside_resident_runs_and_the_assembly_without_a_solve(monkeypatch):
     # has no solve behind it: its sums are reduced at once and nothing zeroes M for the next run)
     _both(monkeypatch, arrays, [dict(max_num_iterations=5), dict(max_num_iterations=5)], runs=2, upload_between=True)
     _both(monkeypatch, arrays, [dict(max_num_iterations=0), dict(max_num_iterations=1), dict(max_num_iterations=3)], runs=3)
-    # the launches behind the back substitution one by one: nothing zeroes M behind the solve, the assembly's k_reduce stays
-    a = _both(monkeypatch, arrays, dict(max_num_iterations=8), env=dict(MSFM_FUSED_TAIL="0"))
-    _same(a, _run(monkeypatch, arrays, dict(max_num_iterations=8), True))
