@@ -1307,6 +1307,174 @@ bool GeoVerification::GeoVerificationFundamental(std::vector<Point2f>& pt1, std:
   return true;
 }
 
+// ---- which pairs to match (initial_matching_graph.cc:164-294) ----
+namespace math {
+// basic_funcs.h:127-152: the first group is never unique (its first element is compared with itself), the last never pushed
+static std::vector<int> keep_unique_vector(std::vector<int> data) {
+  std::vector<int> kept;
+  std::sort(data.begin(), data.end());
+  int v = data[0];
+  bool is_unique = true;
+  for (int x : data) {
+    if (x != v) {
+      if (is_unique) kept.push_back(v);
+      v = x;
+      is_unique = true;
+    } else {
+      is_unique = false;
+    }
+  }
+  return kept;
+}
+// basic_funcs.cc:380-408: the index that opens a group, when the group before it was unique
+static std::vector<int> keep_unique_idx_vector(const std::vector<int>& data) {
+  std::vector<std::pair<int, int>> by_word(data.size());
+  for (size_t i = 0; i < data.size(); i++) by_word[i] = {(int)i, data[i]};
+  std::stable_sort(by_word.begin(), by_word.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.second < b.second; });
+  std::vector<int> unique_idx;
+  bool is_unique = true;
+  int v = by_word[0].second;
+  for (const auto& e : by_word) {
+    if (e.second != v) {
+      if (is_unique) unique_idx.push_back(e.first);
+      v = e.second;
+      is_unique = true;
+    } else {
+      is_unique = false;
+    }
+  }
+  return unique_idx;
+}
+}  // namespace math
+
+void InitialMatchingGraph::Reset(int n, int K) {
+  match_graph_init.assign(n, {});
+  hyp_img_.assign(n, std::vector<int>(K, 0));
+  n_init_.assign(n, std::vector<int>(K, 0));
+  n_inliers_.assign(n, std::vector<int>(K, 0));
+  verdict_.assign(n, std::vector<uint8_t>(K, 0));
+}
+
+static int ThNumMatch(int num_imgs, int max_hypotheses) {   // :168-169
+  if (max_hypotheses > 0) return max_hypotheses;
+  int k = std::min(std::max(200, num_imgs / 10), num_imgs - 1);
+  return k > 500 ? 500 : k;
+}
+
+void InitialMatchingGraph::BuildInitialMatchGraphFeature(const std::vector<std::vector<int>>& words, int num_words,
+                                                         const std::vector<std::vector<Point2f>>& keypoints) {
+  const int n = (int)words.size();
+  std::vector<int> n_features(n), flat_words;
+  std::vector<uint8_t> has_words(n);
+  std::vector<float> kp;
+  for (int i = 0; i < n; i++) {
+    n_features[i] = (int)keypoints[i].size();
+    has_words[i] = words[i].empty() ? 0 : 1;
+    if (has_words[i] && words[i].size() != keypoints[i].size()) throw std::runtime_error("BuildInitialMatchGraphFeature: one word per feature");
+    for (int f = 0; f < n_features[i]; f++) {
+      flat_words.push_back(has_words[i] ? words[i][f] : 0);
+      kp.push_back(keypoints[i][f].x); kp.push_back(keypoints[i][f].y);
+    }
+  }
+  msfm_wordset* ws = nullptr;
+  check(msfm_wordset_create(Context(), n, n_features.data(), has_words.data(), flat_words.data(), num_words, kp.data(), max_hypotheses_, &ws),
+        "msfm_wordset_create");
+  int K = 0;
+  msfm_wordset_size(ws, nullptr, &K, nullptr, nullptr, nullptr);
+  Reset(n, K);
+  std::vector<int> hyp((size_t)n * K);
+  int rc = msfm_wordset_fetch(ws, nullptr, hyp.data(), nullptr, nullptr, nullptr, nullptr);
+  for (int i = 0; i < n && rc == MSFM_OK; i++) std::copy(hyp.begin() + (size_t)i * K, hyp.begin() + (size_t)(i + 1) * K, hyp_img_[i].begin());
+  msfm_pair_select_options opt;
+  msfm_pair_select_default_options(&opt);
+  for (int r0 = 0; r0 < n && rc == MSFM_OK; r0 += rows_per_call_) {
+    const int rows = std::min(rows_per_call_, n - r0);
+    msfm_pair_set* ps = nullptr;
+    rc = msfm_pair_select(ws, r0, rows, &opt, &ps);
+    if (rc != MSFM_OK) break;
+    std::vector<int> ni((size_t)rows * K), nin((size_t)rows * K);
+    std::vector<uint8_t> ver((size_t)rows * K);
+    msfm_pair_set_fetch(ps, ni.data(), nin.data(), ver.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+    msfm_pair_set_destroy(ps);
+    for (int r = 0; r < rows; r++)
+      for (int s = 0; s < K; s++) {
+        const size_t h = (size_t)r * K + s;
+        n_init_[r0 + r][s] = ni[h]; n_inliers_[r0 + r][s] = nin[h]; verdict_[r0 + r][s] = ver[h];
+        if (ver[h] == 0) match_graph_init[r0 + r].push_back(hyp_img_[r0 + r][s]);   // :280-284
+      }
+  }
+  const std::string err = rc == MSFM_OK ? "" : msfm_last_error(Context());
+  msfm_wordset_destroy(ws);
+  if (rc != MSFM_OK) throw std::runtime_error("BuildInitialMatchGraphFeature: " + err);
+}
+
+void InitialMatchingGraph::MatchGraphFeatureHost(const std::vector<std::vector<int>>& words, int num_words,
+                                                 const std::vector<std::vector<Point2f>>& keypoints) {
+  const int num_imgs = (int)words.size();
+  const int th_num_match = ThNumMatch(num_imgs, max_hypotheses_);
+  Reset(num_imgs, th_num_match);
+  // similarity_graph.cc:88-117, :63-81
+  std::vector<std::vector<int>> inverted_file(num_words);
+  for (int i = 0; i < num_imgs; i++)
+    if (!words[i].empty())
+      for (int id : math::keep_unique_vector(words[i])) inverted_file[id].push_back(i);
+  const size_t th_bin_size = (size_t)(num_words / 100);
+  for (auto& bin : inverted_file)
+    if (!bin.empty() && bin.size() > th_bin_size) bin.clear();
+  std::vector<std::vector<int>> similarity_matrix(num_imgs, std::vector<int>(num_imgs, 0));
+  for (const auto& bin : inverted_file)
+    for (size_t m = 0; m + 1 < bin.size(); m++)
+      for (size_t k = m + 1; k < bin.size(); k++) { similarity_matrix[bin[m]][bin[k]]++; similarity_matrix[bin[k]][bin[m]]++; }
+  // :188-203
+  std::vector<std::map<int, int>> pt_word_map(num_imgs);
+  for (int i = 0; i < num_imgs; i++) {
+    if (words[i].empty()) continue;
+    for (int idx : math::keep_unique_idx_vector(words[i])) pt_word_map[i].insert({words[i][idx], idx});
+  }
+  msfm_fransac_options fo;
+  msfm_fransac_default_options(&fo);
+  for (int r0 = 0; r0 < num_imgs; r0 += rows_per_call_) {
+    const int rows = std::min(rows_per_call_, num_imgs - r0);
+    std::vector<int> off(1, 0);
+    std::vector<float> a, b;
+    for (int idx1 = r0; idx1 < r0 + rows; idx1++) {
+      // :216-231
+      std::vector<std::pair<int, int>> sim_sort;
+      for (int j = 0; j < num_imgs; j++)
+        if (j != idx1) sim_sort.push_back({j, similarity_matrix[idx1][j]});
+      std::stable_sort(sim_sort.begin(), sim_sort.end(), [](const std::pair<int, int>& x, const std::pair<int, int>& y) { return x.second > y.second; });
+      for (int j = 0; j < th_num_match; j++) {
+        const int idx2 = sim_sort[j].first;
+        hyp_img_[idx1][j] = idx2;
+        // :242-253
+        int n_matches = 0;
+        for (const auto& it1 : pt_word_map[idx1]) {
+          const auto it2 = pt_word_map[idx2].find(it1.first);
+          if (it2 == pt_word_map[idx2].end()) continue;
+          const Point2f &p = keypoints[idx1][it1.second], &q = keypoints[idx2][it2->second];
+          a.push_back(p.x); a.push_back(p.y); b.push_back(q.x); b.push_back(q.y);
+          n_matches++;
+        }
+        n_init_[idx1][j] = n_matches;
+        off.push_back(off.back() + n_matches);
+      }
+    }
+    const int H = rows * th_num_match;
+    std::vector<double> F(9 * (size_t)H);
+    std::vector<uint8_t> inlier(std::max<size_t>(1, a.size() / 2)), ok(H);
+    std::vector<int> nin(H);
+    check(msfm_fundamental_ransac_batch(Context(), H, off.data(), a.data(), b.data(), &fo, F.data(), inlier.data(), nin.data(), ok.data()),
+          "fundamental_ransac");
+    for (int r = 0; r < rows; r++)
+      for (int s = 0; s < th_num_match; s++) {
+        const int h = r * th_num_match + s, i = r0 + r;
+        n_inliers_[i][s] = nin[h];
+        verdict_[i][s] = n_init_[i][s] < 30 ? 1 : !ok[h] ? 2 : !(nin[h] > 20) ? 3 : 0;   // :254, :270, :274
+        if (verdict_[i][s] == 0) match_graph_init[i].push_back(hyp_img_[i][s]);
+      }
+  }
+}
+
 // ---- pose initialisers ----
 static const uint64_t kPoseSeed = 0x4D53464D50ull;
 

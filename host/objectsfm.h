@@ -370,6 +370,29 @@ class GeoVerification {
 std::vector<std::vector<std::pair<int, int>>> VerifyPairs(const std::vector<PairMatches>& matches,
                                                           const std::vector<std::vector<Point2f>>& keypoints);
 
+// Which image pairs are matched at all, matching_type "feature" (SfM/src/graph/initial_matching_graph.h/.cc:164-294 with the
+// inverted-file similarity of similarity_graph.cc:47-117).  words[i] = Database::words_id_[i] (empty: `<i>_words` is empty),
+// num_words = Database::max_words_id_, keypoints[image][feature] = the centred pixels of database.cc:522-527.
+// BuildInitialMatchGraphFeature is one msfm_wordset_create plus msfm_pair_select per rows_per_call_ images;
+// MatchGraphFeatureHost walks the reference's loops (std::map per image, one hypothesis after the other) and hands the joined
+// points of the same rows_per_call_ images to one msfm_fundamental_ransac_batch, so that every hypothesis keeps its sampler
+// index: both fill the same members with the same values (tests/pairselect_host_check.cc).  Ties the reference leaves to
+// std::sort are fixed as msfm.h says: the lowest feature of a repeated word, the lower image id at equal similarity.
+class InitialMatchingGraph {
+ public:
+  int rows_per_call_ = 64;   // decides which samples a pair sees: keep it when results are to be reproduced
+  int max_hypotheses_ = 0;   // 0: th_num_match of :168-169
+  std::vector<std::vector<int>> match_graph_init;              // :47: per image the images to match it against
+  std::vector<std::vector<int>> hyp_img_, n_init_, n_inliers_;  // per image and slot: set_idx2, matches_init.size(), inliers
+  std::vector<std::vector<uint8_t>> verdict_;                  // per image and slot: 0 kept, 1 / 2 / 3 = the gate that refused
+  void BuildInitialMatchGraphFeature(const std::vector<std::vector<int>>& words, int num_words,
+                                     const std::vector<std::vector<Point2f>>& keypoints);
+  void MatchGraphFeatureHost(const std::vector<std::vector<int>>& words, int num_words,
+                             const std::vector<std::vector<Point2f>>& keypoints);
+ private:
+  void Reset(int n, int K);
+};
+
 // Pose initialisers (SfM/src/orientation/{absolute,relative}_pose_estimation.h).  Eigen::Vector3d / Vector2d / Matrix3d
 // become Vec3 / Vec2 / Mat3; RTPoseRelative has the fields of RTPose (basic_structs.h:126-138).
 typedef RTPose RTPoseRelative;

@@ -645,6 +645,69 @@ int msfm_chain_ba_create_gps(msfm_chain* chain, int n_cams, int n_models, double
 int msfm_chain_store_points(msfm_chain* chain, msfm_ba* ba);
 
 /* ======================================================================================
+ *  Which image pairs to match: hypotheses from visual words, verified in batches
+ * ====================================================================================== */
+/* InitialMatchingGraph::match_graph_feature (SfM/src/graph/initial_matching_graph.cc:164-294) with the inverted-file
+ * similarity of SimilarityGraph::SimilarityGraphInvFile (similarity_graph.cc:47-117).  Input is what the reference reads from
+ * its `<i>_words` and `<i>_feature` files: per image the word id of every feature (Database::words_id_[i]) and the keypoints.
+ * Sort an image's word ids; the runs of equal ids are its groups g0 < g1 < ... < gm.  The reference's quirks are kept:
+ *   inverted file  the image enters word w's bin iff w's group is a single feature and is neither g0 (keep_unique_vector,
+ *                  basic_funcs.h:127-152, compares the first element with itself) nor gm (the last group is never pushed, so
+ *                  id num_words never reaches the num_words-sized table).  A bin with more than num_words / 100 images
+ *                  (integer division) is emptied (:109-116).
+ *   similarity     S[a][b] = bins that hold both images (:68-81): symmetric, zero diagonal; int32 here, the same integers in
+ *                  float there.
+ *   hypotheses     image i: all j != i by S[i][j] descending, the first K (:216-231).  Equal similarity goes to the lower
+ *                  image id (the reference leaves ties to std::sort).  Images without words take part with similarity 0.
+ *   word table     keep_unique_idx_vector (basic_funcs.cc:380-408): group g_k, k >= 2, gives the entry (its word, its lowest
+ *                  feature index) iff g_(k-1) is a single feature, whatever its own size; g0 and g1 never do.  (Lowest feature:
+ *                  the reference's std::sort leaves it open.)  No stop-word rule here; an image without words has no entries.
+ *   join           hypothesis (i, j): the entries of i's table in ascending word order whose word is in j's table, as
+ *                  (feature of i, feature of j) (:242-253); n_init = their number.
+ *   verification   problem r * K + s of ONE msfm_fundamental_ransac_batch call holds the joined keypoints of row r, slot s of a
+ *                  msfm_pair_select call, all of them (min_points rejects the short ones): F, inlier, n_inliers, ok of the
+ *                  chunk are that call's, bit for bit.  The sampler index is the position in the call, so how a host cuts the
+ *                  images into chunks decides which samples a pair sees (as for the seed search).
+ *   verdict        0 kept: n_init >= th_init_matches (:254), ok (:270), n_inliers > th_inliers (:274); 1: too few joined
+ *                  matches; 2: GeoVerificationFundamental false; 3: verified, but not more than th_inliers inliers.
+ *   pairs          the kept hypotheses as (idx1, idx2) in (row, slot) order = match_graph_init; the `pairs` of msfm_match_pairs.
+ * msfm_wordset_create does everything that does not depend on the options once - word tables, similarity matrix, ranked
+ * hypotheses, keypoints - and keeps it on the device; a set counts as a child of its context.  max_hypotheses = 0: the rule
+ * of :168-169, min(max(200, n / 10), n - 1) capped at 500; > 0: that many (<= n - 1).  word_id and keypoints are flat over
+ * all images back to back; the word rows of an image with has_words = 0 are ignored.
+ * msfm_wordset_size: n_inverted = images entered into bins before the stop rule, n_mapped = word-table entries.
+ * msfm_wordset_fetch (every pointer may be NULL): similarity [n][n], hyp_img / hyp_sim [n][K], map_off [n + 1],
+ * map_word / map_feat [n_mapped] (image i's table is map_off[i] .. map_off[i + 1], ascending word).
+ * msfm_pair_select answers rows [first_image, first_image + n_rows) with one host wait for the offsets and one for the
+ * answer (plus those of the RANSAC); options.max_hypotheses = 0: the set's K, else the first that many slots (<= K).
+ * msfm_pair_set_fetch (every pointer may be NULL): n_init / n_inliers / verdict [rows][K], pairs [n_kept][2], F [rows][K][9],
+ * init_off [rows * K + 1], init_matches [n_init_total][2], init_inlier [n_init_total].  A pair set is host memory only.
+ * MSFM_E_INVAL, the objects stay usable: a NULL pointer, n_images < 2 (or above 46340), a word id outside [0, num_words],
+ * max_hypotheses out of range, first_image / n_rows out of range, a chunk whose joined matches do not fit int32. */
+typedef struct msfm_wordset msfm_wordset;
+typedef struct msfm_pair_set msfm_pair_set;
+typedef struct msfm_pair_select_options {   /* msfm_pair_select_default_options fills the reference's values */
+  int32_t th_init_matches;       /* 30 (:254) */
+  int32_t th_inliers;            /* 20 (:274) */
+  int32_t max_hypotheses;        /* 0 */
+  msfm_fransac_options fransac;  /* msfm_fransac_default_options */
+} msfm_pair_select_options;
+void msfm_pair_select_default_options(msfm_pair_select_options* opt);
+int msfm_wordset_create(msfm_ctx* ctx, int n_images, const int* n_features /*[n]*/, const uint8_t* has_words /*[n]*/,
+                        const int32_t* word_id, int num_words /* Database::max_words_id_ */, const float* keypoints /*[..][2]*/,
+                        int max_hypotheses, msfm_wordset** out);
+int msfm_wordset_size(const msfm_wordset* set, int* n_images, int* n_hypotheses, int64_t* n_inverted, int64_t* n_mapped,
+                      int64_t* h2d_bytes);
+int msfm_wordset_fetch(const msfm_wordset* set, int32_t* similarity, int32_t* hyp_img, int32_t* hyp_sim, int32_t* map_off,
+                       int32_t* map_word, int32_t* map_feat);
+void msfm_wordset_destroy(msfm_wordset* set);
+int msfm_pair_select(msfm_wordset* set, int first_image, int n_rows, const msfm_pair_select_options* opt, msfm_pair_set** out);
+int msfm_pair_set_size(const msfm_pair_set* set, int* n_rows, int* n_hypotheses, int* n_kept, int64_t* n_init_total);
+int msfm_pair_set_fetch(const msfm_pair_set* set, int32_t* n_init, int32_t* n_inliers, uint8_t* verdict, int32_t* pairs, double* F,
+                        int32_t* init_off, int32_t* init_matches, uint8_t* init_inlier);
+void msfm_pair_set_destroy(msfm_pair_set* set);
+
+/* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search
  * ====================================================================================== */
 /* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference

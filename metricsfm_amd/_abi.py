@@ -53,6 +53,11 @@ class FransacOptions(C.Structure):
                 ("min_points", C.c_int), ("min_inliers", C.c_int), ("seed", C.c_uint64)]
 
 
+class PairSelectOptions(C.Structure):
+    """msfm_pair_select_options (include/msfm.h)."""
+    _fields_ = [("th_init_matches", C.c_int32), ("th_inliers", C.c_int32), ("max_hypotheses", C.c_int32), ("fransac", FransacOptions)]
+
+
 class HransacOptions(C.Structure):
     """msfm_hransac_options (include/msfm.h)."""
     _fields_ = [("threshold", C.c_double), ("confidence", C.c_double), ("max_iterations", C.c_int), ("polish", C.c_int),

@@ -40,6 +40,8 @@ SYMBOLS = [
     "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
     "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
     "msfm_epipolar_filter", "msfm_fransac_default_options", "msfm_fundamental_ransac_batch",
+    "msfm_pair_select_default_options", "msfm_wordset_create", "msfm_wordset_size", "msfm_wordset_fetch", "msfm_wordset_destroy",
+    "msfm_pair_select", "msfm_pair_set_size", "msfm_pair_set_fetch", "msfm_pair_set_destroy",
     "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
     "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
     "msfm_epnp_ransac_batch", "msfm_epnpf_default_options", "msfm_epnpf_num_steps", "msfm_epnpf_sweep_batch",
@@ -213,6 +215,18 @@ def lib():
     L.msfm_round_set_destroy.argtypes = [vp]
     L.msfm_round_set_destroy.restype = None
     i64p = C.POINTER(C.c_int64)
+    L.msfm_pair_select_default_options.argtypes = [C.POINTER(A.PairSelectOptions)]
+    L.msfm_pair_select_default_options.restype = None
+    L.msfm_wordset_create.argtypes = [vp, i, A.c_int_p, A.c_u8_p, A.c_int_p, i, A.c_float_p, i, C.POINTER(vp)]
+    L.msfm_wordset_size.argtypes = [vp, A.c_int_p, A.c_int_p, i64p, i64p, i64p]
+    L.msfm_wordset_fetch.argtypes = [vp] + [A.c_int_p] * 6
+    L.msfm_wordset_destroy.argtypes = [vp]
+    L.msfm_wordset_destroy.restype = None
+    L.msfm_pair_select.argtypes = [vp, i, i, C.POINTER(A.PairSelectOptions), C.POINTER(vp)]
+    L.msfm_pair_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, i64p]
+    L.msfm_pair_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_double_p, A.c_int_p, A.c_int_p, A.c_u8_p]
+    L.msfm_pair_set_destroy.argtypes = [vp]
+    L.msfm_pair_set_destroy.restype = None
     L.msfm_recon_create.argtypes = [vp, vp, C.POINTER(A.ReconInit), C.POINTER(vp)]
     L.msfm_recon_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, i64p, i64p, i64p]
     L.msfm_recon_fetch.argtypes = [vp] + [A.c_int_p] * 5 + [A.c_double_p, A.c_u8_p, A.c_double_p, A.c_int_p, A.c_u8_p, A.c_u8_p, A.c_double_p,
@@ -415,6 +429,21 @@ def fransac_options(**kw):
         if not hasattr(o, k):
             raise AttributeError(k)
         setattr(o, k, v)
+    return o
+
+
+def pair_select_options(**kw):
+    """msfm_pair_select_options with the reference's values (30 joined matches, more than 20 inliers, the set's K); keywords
+    override fields, and the fields of msfm_fransac_options go to `fransac`."""
+    o = A.PairSelectOptions()
+    lib().msfm_pair_select_default_options(C.byref(o))
+    for k, v in kw.items():
+        if k != "fransac" and hasattr(o, k):
+            setattr(o, k, v)
+        elif hasattr(o.fransac, k):
+            setattr(o.fransac, k, v)
+        else:
+            raise AttributeError(k)
     return o
 
 
@@ -632,6 +661,11 @@ class Context:
         """msfm_match_store_create: the verified matches resident on the device (pairs [P][2] strictly ascending in (idx1, idx2),
         match_off [P+1], matches [M][2]: the flat layout of `build_tracks`)."""
         return MatchStore(self, n_features, pairs, match_off, matches)
+
+    def wordset(self, n_features, words, num_words, keypoints, max_hypotheses=0):
+        """msfm_wordset_create: word tables, similarity matrix and ranked hypotheses of an image set, resident as a `Wordset`.
+        words: per image the word id of every feature, or None / empty for an image without words (`<i>_words` empty)."""
+        return Wordset(self, n_features, words, num_words, keypoints, max_hypotheses)
 
     def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
         """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
@@ -1251,6 +1285,81 @@ class MatchStore:
     def close(self):
         if self._h:
             lib().msfm_match_store_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Wordset:
+    """msfm_wordset: which image pairs to match, from the word id of every feature (include/msfm.h)."""
+
+    def __init__(self, ctx: Context, n_features, words, num_words, keypoints, max_hypotheses=0):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        nf = A.as_c(np.asarray(n_features, dtype=np.int32).reshape(-1), np.int32)
+        if len(words) != len(nf):
+            raise ValueError("one word list (or None) per image")
+        has = np.array([w is not None and len(w) > 0 for w in words], dtype=np.uint8)
+        off = np.concatenate([[0], np.cumsum(nf, dtype=np.int64)])
+        flat = np.zeros(max(1, int(off[-1])), dtype=np.int32)
+        for k, w in enumerate(words):
+            if has[k]:
+                if len(w) != nf[k]:
+                    raise ValueError("image %d: %d word ids for %d features" % (k, len(w), nf[k]))
+                flat[off[k]:off[k + 1]] = w
+        kp = A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if len(kp) != off[-1]:
+            raise ValueError("keypoints must hold one row per feature of every image")
+        ctx.check(lib().msfm_wordset_create(ctx._h, len(nf), A.ptr(nf, A.c_int_p), A.ptr(has, A.c_u8_p), A.ptr(flat, A.c_int_p), int(num_words),
+                                            A.ptr(kp, A.c_float_p), int(max_hypotheses), C.byref(self._h)))
+        n, k, ni, nm, nb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        lib().msfm_wordset_size(self._h, C.byref(n), C.byref(k), C.byref(ni), C.byref(nm), C.byref(nb))
+        self.n_images, self.n_hypotheses, self.n_inverted, self.n_mapped, self.h2d_bytes = n.value, k.value, ni.value, nm.value, nb.value
+
+    def fetch(self, similarity=True):
+        """msfm_wordset_fetch: dict of similarity [n][n] (or None), hyp_img / hyp_sim [n][K], map_off [n + 1], map_word, map_feat."""
+        n, k, m = self.n_images, self.n_hypotheses, max(1, self.n_mapped)
+        S = np.zeros((n, n), np.int32) if similarity else None
+        hi, hs = np.zeros((n, k), np.int32), np.zeros((n, k), np.int32)
+        mo, mw, mf = np.zeros(n + 1, np.int32), np.zeros(m, np.int32), np.zeros(m, np.int32)
+        ip = A.c_int_p
+        self.ctx.check(lib().msfm_wordset_fetch(self._h, A.ptr(S, ip), A.ptr(hi, ip), A.ptr(hs, ip), A.ptr(mo, ip), A.ptr(mw, ip), A.ptr(mf, ip)))
+        return {"similarity": S, "hyp_img": hi, "hyp_sim": hs, "map_off": mo, "map_word": mw[:self.n_mapped], "map_feat": mf[:self.n_mapped]}
+
+    def select(self, first_image=0, n_rows=None, details=True, **opts):
+        """msfm_pair_select for the rows [first_image, first_image + n_rows) (default: to the last image); opts: fields of
+        msfm_pair_select_options and of its msfm_fransac_options.  Returns a dict: pairs [n_kept][2], n_init / n_inliers /
+        verdict [rows][K] and, with details, F [rows][K][3][3], init_off, init_matches [..][2], init_inlier."""
+        rows = self.n_images - first_image if n_rows is None else n_rows
+        o = pair_select_options(**opts)
+        h = C.c_void_p()
+        self.ctx.check(lib().msfm_pair_select(self._h, first_image, rows, C.byref(o), C.byref(h)))
+        try:
+            nr, k, nk, tot = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+            lib().msfm_pair_set_size(h, C.byref(nr), C.byref(k), C.byref(nk), C.byref(tot))
+            rows, k, nk, tot = nr.value, k.value, nk.value, tot.value
+            ni, nin, ver = np.zeros((rows, k), np.int32), np.zeros((rows, k), np.int32), np.zeros((rows, k), np.uint8)
+            pairs = np.zeros((max(1, nk), 2), np.int32)
+            F = np.zeros((rows, k, 3, 3)) if details else None
+            off = np.zeros(rows * k + 1, np.int32) if details else None
+            im = np.zeros((max(1, tot), 2), np.int32) if details else None
+            inl = np.zeros(max(1, tot), np.uint8) if details else None
+            lib().msfm_pair_set_fetch(h, A.ptr(ni, A.c_int_p), A.ptr(nin, A.c_int_p), A.ptr(ver, A.c_u8_p), A.ptr(pairs, A.c_int_p),
+                                      A.ptr(F, A.c_double_p), A.ptr(off, A.c_int_p), A.ptr(im, A.c_int_p), A.ptr(inl, A.c_u8_p))
+        finally:
+            lib().msfm_pair_set_destroy(h)
+        out = {"pairs": pairs[:nk], "n_init": ni, "n_inliers": nin, "verdict": ver}
+        if details:
+            out.update(F=F, init_off=off, init_matches=im[:tot], init_inlier=inl[:tot])
+        return out
+
+    def close(self):
+        if self._h:
+            lib().msfm_wordset_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -9,6 +9,9 @@ the reference's extraction stage can feed libmsfm and libmsfm's results can feed
   bundle.rd.out                 text, "# Bundle file v0.3" (IncrementalSfM::SaveForCMVS, sfm_incremental.cc:1302-1353): fixed, 8 decimals;
       per camera f k1 k2 / R (row-major, 9 values) / t; per point X Y Z / 255 255 255 / view list, where the reference
       truncates the image coordinates to int before printing them as float (:1342-1345).
+  <output_fold>/<idx>_words     binary (Database::WriteoutWordsForImage / ReadinWordsForImage, database.cc:869-945): int32 count, int32[count]
+      word ids and float32[count] weights of the image's bag of words, int32 max_words_id_, int32 num_pts, int32[num_pts] the word
+      id of every feature.  An image without words is an EMPTY file (:911).
   sfm_openmvs.txt, temp_result  text: the OpenMVS hand-over (:1147-1245) and the reconstruction checkpoint (:1465-1749), below.
 Native little-endian, as the reference writes them with ofstream::write."""
 import os
@@ -64,6 +67,41 @@ def read_image_feature(fold, idx):
     info = dict(rows=rows, cols=cols, zoom_ratio=zoom, f_mm=f_mm, f_pixel=f_px, gps_latitude=lat, gps_longitude=lon, cam_maker=maker,
                 cam_model=model)
     return info, kp, desc
+
+
+def words_file(fold, idx):
+    return os.path.join(fold, "%d_words" % idx)
+
+
+def write_words(fold, idx, bow_ids, bow_weights, max_words_id, word_id):
+    """bow_ids / bow_weights: the image's fbow vector (ascending id, as std::map iterates); word_id: the word of every feature.
+    bow_ids None: an image without words, an empty file."""
+    with open(words_file(fold, idx), "wb") as f:
+        if bow_ids is None:
+            return
+        ids, w = np.asarray(bow_ids, dtype=np.int32).reshape(-1), np.asarray(bow_weights, dtype=np.float32).reshape(-1)
+        if len(ids) != len(w):
+            raise ValueError("one weight per word")
+        wid = np.asarray(word_id, dtype=np.int32).reshape(-1)
+        f.write(struct.pack("<i", len(ids)))
+        ids.tofile(f)
+        w.tofile(f)
+        f.write(struct.pack("<ii", int(max_words_id), len(wid)))
+        wid.tofile(f)
+
+
+def read_words(fold, idx):
+    """-> (bow_ids, bow_weights, max_words_id, word_id), or (None, None, None, None) for an empty file."""
+    with open(words_file(fold, idx), "rb") as f:
+        head = f.read(4)
+        if len(head) < 4:
+            return None, None, None, None
+        n = struct.unpack("<i", head)[0]
+        ids = np.fromfile(f, dtype=np.int32, count=n)
+        w = np.fromfile(f, dtype=np.float32, count=n)
+        max_id, npts = struct.unpack("<ii", f.read(8))
+        wid = np.fromfile(f, dtype=np.int32, count=npts)
+    return ids, w, max_id, wid
 
 
 def write_bundle_out(path, cam_fk, cam_R, cam_t, points, views):

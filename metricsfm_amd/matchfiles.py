@@ -9,6 +9,11 @@ be consumed by the unmodified incremental pipeline and vice versa.
   <fold>/feature/prior.txt     text, the prior F / H of SLAMGPS::FeatureMatching step 1: the camera count, then per camera
                                i a line with n and n lines `j F00 H00 F01 H01 ... F22 H22 ` (std::fixed, 12 decimals)
                                (SLAMGPS::WriteOutPriorInfo / ReadinPriorInfo, SfM/src/slam_gps.cc:1821-1885)
+  <output_fold>/init_match_graph.txt   text: the image count, id_last (the last image whose row is final), then per image
+                               `n j0 j1 ... ` - every number followed by one blank, the line too
+                               (InitialMatchingGraph::WriteOutInitMatchGraph / ReadinInitMatchGraph, initial_matching_graph.cc:296-344)
+  <output_fold>/similarity_graph.txt   text: N, then N rows of N floats as operator<< prints them (%g), each followed by one blank
+                               (WriteOutSimilarityGraph / ReadinSimilarityGraph, initial_matching_graph.cc:357-392)
 Native little-endian ints, as the reference writes them with ofstream::write.
 """
 import os
@@ -59,6 +64,42 @@ def write_out_match_graph(fold, match_graph):
 def read_in_matching_graph(fold, n):
     vals = np.array(open(os.path.join(fold, "graph_matching.txt")).read().split(), dtype=np.int64)
     return vals.reshape(n, n)
+
+
+def write_init_match_graph(fold, match_graph_init, id_last=None):
+    """match_graph_init: per image the list of images to match it against; id_last defaults to the last image (:80)."""
+    n = len(match_graph_init)
+    with open(os.path.join(fold, "init_match_graph.txt"), "wb") as f:
+        f.write(("%d\n%d\n" % (n, n - 1 if id_last is None else id_last)).encode())
+        for row in match_graph_init:
+            f.write(("%d " % len(row) + "".join("%d " % int(v) for v in row) + "\n").encode())
+
+
+def read_init_match_graph(fold):
+    """-> (match_graph_init as a list of int lists, id_last)."""
+    tok = open(os.path.join(fold, "init_match_graph.txt")).read().split()
+    n, id_last = int(tok[0]), int(tok[1])
+    rows, p = [], 2
+    for _ in range(n):
+        k = int(tok[p])
+        rows.append([int(v) for v in tok[p + 1:p + 1 + k]])
+        p += 1 + k
+    return rows, id_last
+
+
+def write_similarity_graph(fold, similarity):
+    """similarity [n][n]; the reference keeps the counts in float and prints them with the stream's default format."""
+    s = np.asarray(similarity, dtype=np.float32)
+    with open(os.path.join(fold, "similarity_graph.txt"), "wb") as f:
+        f.write(("%d\n" % len(s)).encode())
+        for row in s:
+            f.write(("".join("%g " % float(v) for v in row) + "\n").encode())
+
+
+def read_similarity_graph(fold):
+    tok = open(os.path.join(fold, "similarity_graph.txt")).read().split()
+    n = int(tok[0])
+    return np.array(tok[1:1 + n * n], dtype=np.float32).reshape(n, n)
 
 
 def codes_to_matches(code):
