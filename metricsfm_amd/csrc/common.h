@@ -8,6 +8,7 @@
 #include <cstring>
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <utility>
@@ -209,6 +210,15 @@ static inline int bits_for(unsigned v) {   // bits that hold every value 0 .. v
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// splitmix64: the counter-based samplers of geo.hip and pose.hip draw from it, each with its own salts and key mixing
+__host__ __device__ static inline uint64_t sm64(uint64_t& s) {
+  s += 0x9E3779B97F4A7C15ull;
+  uint64_t z = s;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+
 // The sum of an int over the 64 lanes of a wave (butterfly 32 .. 1), in every lane.
 __device__ static inline int wave_sum_int(int c) {
   for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
@@ -334,30 +344,54 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
                        const uint8_t* pt_new_added, const uint8_t* d_added_dev, const msfm_localize_pose_options* opt_in, msfm_localize_pose_set** out,
                        DevBuf<uint8_t>* keep_state, int64_t* h2d_bytes);
 
-// The device halves of msfm_epnp_ransac_batch / msfm_epnpf_sweep_batch (pose.hip), in the manner of the two below: device
-// buffers in, the two launches, device buffers out; no synchronisation.  The sample scratch belongs to the caller, who keeps
-// it until the stream has been synchronised.  d_off [n_problems + 1], d_f / d_f_init [n_problems], errors [off[n_problems]].
-struct EpnpScratch { DevBuf<double> hyp; };
-int pose_epnp_dev(msfm_ctx* ctx, int n_problems, const int* d_off, const double* d_w, const double* d_2d, const double* d_f, int max_iter,
-                  uint64_t seed, EpnpScratch& ws, double* dR, double* dt, double* d_err, double* d_avg, int* d_best_iter);
-struct EpnpfScratch { DevBuf<double> step_err, step_pose; DevBuf<int> step_it; };   // step_err: [n_problems][n_steps], the public step_error
+// The device halves of the four pose initialisers (pose.hip): msfm_epnp_ransac_batch, msfm_epnpf_sweep_batch,
+// msfm_relpose_5pt_batch, msfm_relpose_8pt_batch.  An export is its checks, sc.up of the inputs, the result's alloc, the _dev
+// call and sc.down of the outputs; localize_pose.hip and seed.hip call the same _dev functions on the buffers their gather
+// kernels wrote.  A _dev function sizes the result's candidate scratch from the sample count and enqueues the launches; it
+// does not synchronise, so the result (outputs and scratch) lives until its caller has: declare it before the DevScope.
+struct PoseView {         // the problems of one call, device pointers
+  int n;                  // problems (images / pairs)
+  const int* off;         // [n + 1]
+  const double *a, *b;    // [off[n]] rows: absolute pose: world points [3] and image points [2]; relative pose: ref and cur [2]
+  const double *f1, *f2;  // [n] or null: EPnP f / sweep f_init in f1; five-point f_ref, f_cur; eight-point none
+};
+static inline hipError_t hip_first_error(std::initializer_list<hipError_t> es) {   // (a braced list is evaluated left to right)
+  for (const hipError_t e : es) if (e != hipSuccess) return e;
+  return hipSuccess;
+}
+struct EpnpResult {
+  DevBuf<double> R, t, avg, err; DevBuf<int> best_iter;   // [n] records; err [total]
+  DevBuf<double> hyp;                                      // scratch
+  hipError_t alloc(size_t n, size_t total) {
+    return hip_first_error({R.alloc(9 * n), t.alloc(3 * n), avg.alloc(n), err.alloc(std::max<size_t>(1, total)), best_iter.alloc(n)});
+  }
+};
+struct EpnpfResult {
+  DevBuf<double> f, R, t, avg, err; DevBuf<int> best_step, best_iter;
+  DevBuf<double> step_err, step_pose; DevBuf<int> step_it;   // scratch; step_err [n][n_steps] is the public step_error
+  hipError_t alloc(size_t n, size_t total) {
+    return hip_first_error({f.alloc(n), R.alloc(9 * n), t.alloc(3 * n), avg.alloc(n), err.alloc(std::max<size_t>(1, total)), best_step.alloc(n),
+                            best_iter.alloc(n)});
+  }
+};
+struct Relpose5Result {
+  DevBuf<double> E, R, t; DevBuf<uint8_t> ok; DevBuf<int> n_cand;   // [n] records
+  DevBuf<double> cE, ce; DevBuf<int> cn;                            // scratch
+  hipError_t alloc(size_t n, size_t /*total*/) { return hip_first_error({E.alloc(9 * n), R.alloc(9 * n), t.alloc(3 * n), ok.alloc(n), n_cand.alloc(n)}); }
+};
+struct Relpose8Result {
+  DevBuf<double> F, f_ref, f_cur, E, R, t, best_error; DevBuf<uint8_t> ok; DevBuf<int> best_iter, n_cand;
+  DevBuf<double> cF, ce; DevBuf<uint8_t> cok;                       // scratch
+  hipError_t alloc(size_t n, size_t /*total*/) {
+    return hip_first_error({F.alloc(9 * n), f_ref.alloc(n), f_cur.alloc(n), E.alloc(9 * n), R.alloc(9 * n), t.alloc(3 * n), best_error.alloc(n),
+                            ok.alloc(n), best_iter.alloc(n), n_cand.alloc(n)});
+  }
+};
 struct msfm_epnpf_options;
-int pose_epnpf_dev(msfm_ctx* ctx, int n_problems, int n_steps, const int* d_off, const double* d_w, const double* d_2d, const double* d_f_init,
-                   const msfm_epnpf_options* opt, EpnpfScratch& ws, double* d_f_out, double* dR, double* dt, double* d_err, double* d_avg,
-                   int* d_best_step, int* d_best_iter);
-
-// The device halves of msfm_relpose_5pt_batch / msfm_relpose_8pt_batch (pose.hip): device buffers in, the three launches,
-// device buffers out; no synchronisation.  The exports are upload + this + download; seed.hip calls the same functions on
-// the buffers its gather kernel wrote.  The candidate scratch belongs to the caller, who keeps it until the stream has been
-// synchronised.  d_off [n_pairs + 1], points [off[n_pairs]][2], outputs [n_pairs] records.
-struct Relpose5Scratch { DevBuf<double> cE, ce; DevBuf<int> cn; };
-int pose_relpose5_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, const double* d_f_ref,
-                      const double* d_f_cur, int ransac_times, uint64_t seed, Relpose5Scratch& ws, double* dE, double* dR, double* dt,
-                      uint8_t* d_ok, int* d_ncand);
-struct Relpose8Scratch { DevBuf<double> cF, ce; DevBuf<uint8_t> cok; };
-int pose_relpose8_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, int ransac_times,
-                      uint64_t seed, Relpose8Scratch& ws, double* dF, double* d_f_ref, double* d_f_cur, double* dE, double* dR, double* dt,
-                      uint8_t* d_ok, int* d_best_iter, double* d_best_error, int* d_ncand);
+int pose_epnp_dev(msfm_ctx* ctx, const PoseView& V, int max_iter, uint64_t seed, EpnpResult& out);
+int pose_epnpf_dev(msfm_ctx* ctx, const PoseView& V, int n_steps, const msfm_epnpf_options* opt, EpnpfResult& out);
+int pose_relpose5_dev(msfm_ctx* ctx, const PoseView& V, int ransac_times, uint64_t seed, Relpose5Result& out);
+int pose_relpose8_dev(msfm_ctx* ctx, const PoseView& V, int ransac_times, uint64_t seed, Relpose8Result& out);
 
 struct TrackPtrs {   // tri.hip: CSR tracks + cameras as the reference keeps them, device pointers
   int n_tracks;

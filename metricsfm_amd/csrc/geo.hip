@@ -87,14 +87,6 @@
 
 #define GEO_WAVE 64
 
-__host__ __device__ static inline uint64_t geo_sm64(uint64_t& s) {
-  s += 0x9E3779B97F4A7C15ull;
-  uint64_t z = s;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 __device__ static inline double geo_det3(const double* m) {
   return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
@@ -168,7 +160,7 @@ __device__ static inline int geo_solve7(uint64_t seed, int pair, int h, int N, c
   int idx[7];
   for (int k = 0; k < 7; k++) {
     for (;;) {
-      const int v = (int)(geo_sm64(s) % (uint64_t)N);
+      const int v = (int)(sm64(s) % (uint64_t)N);
       bool dup = false;
       for (int j = 0; j < k; j++) dup = dup || (idx[j] == v);
       if (!dup) { idx[k] = v; break; }
@@ -463,7 +455,7 @@ __device__ static inline int hr_sample(uint64_t seed, int pair, int h, int N, co
     int idx[4];
     for (int k = 0; k < 4; k++) {
       for (;;) {
-        const int v = (int)(geo_sm64(s) % (uint64_t)N);
+        const int v = (int)(sm64(s) % (uint64_t)N);
         bool dup = false;
         for (int j = 0; j < k; j++) dup = dup || (idx[j] == v);
         if (!dup) { idx[k] = v; break; }

@@ -216,19 +216,19 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<Slot> d_slot;
-  DevBuf<int> d_toff, d_off1, d_off2, d_bi1, d_bs2, d_bi2, d_first, d_bstep, d_biter, d_nin, d_nout;
-  DevBuf<double> d_rowf, d_finit, d_w1, d_x1, d_w2, d_x2, d_R1, d_t1, d_e1, d_a1, d_f2, d_R2, d_t2, d_e2, d_a2;
+  DevBuf<int> d_toff, d_off1, d_off2, d_first, d_bstep, d_biter, d_nin, d_nout;
+  DevBuf<double> d_rowf, d_finit, d_w1, d_x1, d_w2, d_x2;
   DevBuf<double> d_f, d_R, d_t, d_avg, d_err;
   DevBuf<uint8_t> d_added, d_pass, d_state;
-  EpnpScratch ws1;
-  EpnpfScratch ws2;
+  EpnpResult r1;
+  EpnpfResult r2;
   DevScope sc(ctx);
   LP_TRY(sc.up(d_slot, slot)); LP_TRY(sc.up(d_toff, toff)); LP_TRY(sc.up(d_off1, off1)); LP_TRY(sc.up(d_off2, off2));
   LP_TRY(sc.up(d_rowf, row_f, (size_t)n));
   if (!d_added_dev && pt_new_added && n_points) LP_TRY(sc.up(d_added, pt_new_added, (size_t)n_points));
   const uint8_t* added_p = d_added_dev ? d_added_dev : d_added.p;
-  LP_TRY(d_w1.alloc(3 * (size_t)std::max(1, E1))); LP_TRY(d_x1.alloc(2 * (size_t)std::max(1, E1))); LP_TRY(d_e1.alloc(std::max(1, E1)));
-  LP_TRY(d_w2.alloc(3 * (size_t)std::max(1, E2))); LP_TRY(d_x2.alloc(2 * (size_t)std::max(1, E2))); LP_TRY(d_e2.alloc(std::max(1, E2)));
+  LP_TRY(d_w1.alloc(3 * (size_t)std::max(1, E1))); LP_TRY(d_x1.alloc(2 * (size_t)std::max(1, E1)));
+  LP_TRY(d_w2.alloc(3 * (size_t)std::max(1, E2))); LP_TRY(d_x2.alloc(2 * (size_t)std::max(1, E2)));
   LP_TRY(d_f.alloc(n)); LP_TRY(d_R.alloc(9 * (size_t)n)); LP_TRY(d_t.alloc(3 * (size_t)n)); LP_TRY(d_avg.alloc(n)); LP_TRY(d_bstep.alloc(n));
   LP_TRY(d_biter.alloc(n)); LP_TRY(d_pass.alloc(n)); LP_TRY(d_nin.alloc(n)); LP_TRY(d_nout.alloc(n));
   LP_TRY(d_err.alloc(T)); LP_TRY(d_state.alloc(T));
@@ -250,26 +250,24 @@ int localize_poses_dev(msfm_ctx* ctx, const char* who, const msfm_localize_set* 
   LP_TRY(hipGetLastError());
   ArmOut a1{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}, a2 = a1;
   if (E1) {   // :644-672
-    LP_TRY(d_R1.alloc(9 * (size_t)n)); LP_TRY(d_t1.alloc(3 * (size_t)n)); LP_TRY(d_a1.alloc(n)); LP_TRY(d_bi1.alloc(n));
-    MSFM_TRY(pose_epnp_dev(ctx, n, d_off1.p, d_w1.p, d_x1.p, d_rowf.p, opt.max_iter, opt.seed, ws1, d_R1.p, d_t1.p, d_e1.p, d_a1.p, d_bi1.p));
-    a1 = ArmOut{nullptr, d_R1.p, d_t1.p, d_a1.p, nullptr, d_bi1.p};
+    LP_TRY(r1.alloc(n, E1));
+    MSFM_TRY(pose_epnp_dev(ctx, PoseView{n, d_off1.p, d_w1.p, d_x1.p, d_rowf.p, nullptr}, opt.max_iter, opt.seed, r1));
+    a1 = ArmOut{nullptr, r1.R.p, r1.t.p, r1.avg.p, nullptr, r1.best_iter.p};
   }
   if (E2) {   // :673-704
     LP_TRY(sc.up(d_finit, f_init));
-    LP_TRY(d_f2.alloc(n)); LP_TRY(d_R2.alloc(9 * (size_t)n)); LP_TRY(d_t2.alloc(3 * (size_t)n)); LP_TRY(d_a2.alloc(n)); LP_TRY(d_bs2.alloc(n));
-    LP_TRY(d_bi2.alloc(n));
-    MSFM_TRY(pose_epnpf_dev(ctx, n, n_steps, d_off2.p, d_w2.p, d_x2.p, d_finit.p, &opt.sweep, ws2, d_f2.p, d_R2.p, d_t2.p, d_e2.p, d_a2.p,
-                            d_bs2.p, d_bi2.p));
-    a2 = ArmOut{d_f2.p, d_R2.p, d_t2.p, d_a2.p, d_bs2.p, d_bi2.p};
+    LP_TRY(r2.alloc(n, E2));
+    MSFM_TRY(pose_epnpf_dev(ctx, PoseView{n, d_off2.p, d_w2.p, d_x2.p, d_finit.p, nullptr}, n_steps, &opt.sweep, r2));
+    a2 = ArmOut{r2.f.p, r2.R.p, r2.t.p, r2.avg.p, r2.best_step.p, r2.best_iter.p};
   }
   {
     KTimer tm(ctx, "localizepose_state");
     tm.count = 3;
     hipLaunchKernelGGL(k_rows, dim3(cdiv(nt, 64)), dim3(64), 0, s, nt, d_slot.p, a1, a2, d_rowf.p, opt.th_mse_localization, d_f.p, d_R.p, d_t.p,
                        d_avg.p, d_bstep.p, d_biter.p, d_pass.p);
-    hipLaunchKernelGGL(k_first, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, d_e1.p, d_e2.p, d_avg.p, d_pass.p, L->d_cp.p,
+    hipLaunchKernelGGL(k_first, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, r1.err.p, r2.err.p, d_avg.p, d_pass.p, L->d_cp.p,
                        n_points, added_p, d_first.p);
-    hipLaunchKernelGGL(k_state, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, d_e1.p, d_e2.p, d_avg.p, d_pass.p, L->d_cp.p,
+    hipLaunchKernelGGL(k_state, dim3(cdiv(E, 256)), dim3(256), 0, s, E, nt, d_toff.p, d_slot.p, r1.err.p, r2.err.p, d_avg.p, d_pass.p, L->d_cp.p,
                        n_points, added_p, d_first.p, d_err.p, d_state.p, d_nin.p, d_nout.p);
   }
   LP_TRY(hipGetLastError());

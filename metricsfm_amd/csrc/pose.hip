@@ -42,26 +42,43 @@
 
 #define POSE_WAVE 64
 
-__device__ static inline uint64_t pose_sm64(uint64_t& s) {
-  s += 0x9E3779B97F4A7C15ull;
-  uint64_t z = s;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // K distinct indices of [0, n): stands in for math::RandVectorN (utils/basic_funcs.cc:269-281).
 template <int K>
 __device__ static inline void pose_sample(uint64_t seed, uint64_t salt, int problem, int iter, int n, int* idx) {
   uint64_t s = seed ^ salt ^ ((uint64_t)problem * 0xD1342543DE82EF95ull) ^ ((uint64_t)iter * 0xA24BAED4963EE407ull);
   for (int k = 0; k < K; k++) {
     for (;;) {
-      const int v = (int)(pose_sm64(s) % (uint64_t)n);
+      const int v = (int)(sm64(s) % (uint64_t)n);
       bool dup = false;
       for (int j = 0; j < k; j++) dup = dup || (idx[j] == v);
       if (!dup) { idx[k] = v; break; }
     }
   }
+}
+
+// The first smallest of a workgroup of 256 threads, the one selection all four estimators replay: thread tid offers (e, key),
+// key < 0 = nothing to offer, which never displaces a thread that has; a tie goes to the lower key.  Returns the smallest e
+// and leaves its key in s_k[0] (< 0: no thread had anything).  s_e, s_k: LDS [256].  SIDE: the same tree also leaves the
+// smallest `first` in s_first[0] and the sum of `cnt` in s_cnt[0] (LDS [256] each).
+template <bool SIDE = false>
+__device__ static inline double pose_first_smallest(int tid, double e, int key, double* s_e, int* s_k, int first = 0, int cnt = 0,
+                                                    int* s_first = nullptr, int* s_cnt = nullptr) {
+  s_e[tid] = e; s_k[tid] = key;
+  if (SIDE) { s_first[tid] = first; s_cnt[tid] = cnt; }
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) {
+      const double e2 = s_e[tid + st];
+      const int k2 = s_k[tid + st];
+      if (k2 >= 0 && (s_k[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && k2 < s_k[tid]))) { s_e[tid] = e2; s_k[tid] = k2; }
+      if (SIDE) {
+        if (s_first[tid + st] < s_first[tid]) s_first[tid] = s_first[tid + st];
+        s_cnt[tid] += s_cnt[tid + st];
+      }
+    }
+    __syncthreads();
+  }
+  return s_e[0];
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -490,6 +507,43 @@ __device__ static double epnp_minimal(EpnpState& S, double f, double* R, double*
   return count < 2 ? 100000.0 : sqrt(mse / count);
 }
 
+// the four correspondences idx[4] of the problem whose points start at row o
+__device__ static inline void epnp_load_sample(EpnpState& S, const double* __restrict__ pts_w, const double* __restrict__ pts_2d, int o,
+                                               const int* idx) {
+  for (int i = 0; i < 4; i++) {
+    for (int j = 0; j < 3; j++) S.pws[3 * i + j] = pts_w[3 * ((size_t)o + idx[i]) + j];
+    for (int j = 0; j < 2; j++) S.us[2 * i + j] = pts_2d[2 * ((size_t)o + idx[i]) + j];
+  }
+}
+
+// What both absolute-pose selections end with, by all 256 threads of the workgroup: AbsolutePoseEstimation::Error (:67-103) of
+// the pose s_pose = {R[9], t[3]} (LDS, written before the call) at focal length f over the problem's N points from row o on;
+// thread 0 adds the squares in point order and writes avg_error / Rout / tout of the problem.
+__device__ static void pose_abs_tail(const double* s_pose, double f, int tid, int o, int N, const double* __restrict__ pts_w,
+                                     const double* __restrict__ pts_2d, double* __restrict__ errors, double* avg_error, double* Rout,
+                                     double* tout) {
+  __syncthreads();
+  double R[9], t[3];
+  for (int i = 0; i < 9; i++) R[i] = s_pose[i];
+  for (int i = 0; i < 3; i++) t[i] = s_pose[9 + i];
+  for (int i = tid; i < N; i += 256) {
+    const double e = pose_reproj_err(R, t, f, pts_w + 3 * ((size_t)o + i), pts_2d + 2 * ((size_t)o + i));
+    errors[o + i] = fabs(e) < 10.0 ? e : 1000.0;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double sum = 0.0;
+    int count = 0;
+    for (int i = 0; i < N; i++) {
+      const double e = errors[o + i];
+      if (e < 10.0) { sum += e * e; count++; }
+    }
+    *avg_error = count == 0 ? 10000.0 : sqrt(sum / count);
+    for (int i = 0; i < 9; i++) Rout[i] = R[i];
+    for (int i = 0; i < 3; i++) tout[i] = t[i];
+  }
+}
+
 // grid (ceil(H / 64), problems): thread = sample `it` of problem blockIdx.y.  hyp[(p * H + it) * 13] = {err, R[9], t[3]}
 __global__ __launch_bounds__(POSE_WAVE) void k_epnp_hyp(int H, const int* __restrict__ off, const double* __restrict__ pts_w,
                                                         const double* __restrict__ pts_2d, const double* __restrict__ f, uint64_t seed,
@@ -502,10 +556,7 @@ __global__ __launch_bounds__(POSE_WAVE) void k_epnp_hyp(int H, const int* __rest
   int idx[4];
   pose_sample<4>(seed, 0x45506E50ull, p, it, N, idx);
   EpnpState S;
-  for (int i = 0; i < 4; i++) {
-    for (int j = 0; j < 3; j++) S.pws[3 * i + j] = pts_w[3 * ((size_t)o + idx[i]) + j];
-    for (int j = 0; j < 2; j++) S.us[2 * i + j] = pts_2d[2 * ((size_t)o + idx[i]) + j];
-  }
+  epnp_load_sample(S, pts_w, pts_2d, o, idx);
   double R[9], t[3];
   const double e = epnp_minimal(S, f[p], R, t);
   out[0] = e;
@@ -530,40 +581,11 @@ __global__ __launch_bounds__(256) void k_epnp_select(int H, const int* __restric
     const double e = hyp[((size_t)p * H + it) * 13];
     if (e < be) { be = e; bi = it; }
   }
-  s_e[tid] = be; s_i[tid] = bi;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-      const double e2 = s_e[tid + st];
-      const int i2 = s_i[tid + st];
-      if (i2 >= 0 && (s_i[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && i2 < s_i[tid]))) { s_e[tid] = e2; s_i[tid] = i2; }
-    }
-    __syncthreads();
-  }
+  pose_first_smallest(tid, be, bi, s_e, s_i);
   const int best = s_i[0];
   if (tid < 12) s_pose[tid] = best >= 0 ? hyp[((size_t)p * H + best) * 13 + 1 + tid] : 0.0;
-  __syncthreads();
-  double R[9], t[3];
-  for (int i = 0; i < 9; i++) R[i] = s_pose[i];
-  for (int i = 0; i < 3; i++) t[i] = s_pose[9 + i];
-  const double fp = f[p];
-  for (int i = tid; i < N; i += 256) {
-    const double e = pose_reproj_err(R, t, fp, pts_w + 3 * ((size_t)o + i), pts_2d + 2 * ((size_t)o + i));
-    errors[o + i] = fabs(e) < 10.0 ? e : 1000.0;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double sum = 0.0;
-    int count = 0;
-    for (int i = 0; i < N; i++) {
-      const double e = errors[o + i];
-      if (e < 10.0) { sum += e * e; count++; }
-    }
-    avg_error[p] = count == 0 ? 10000.0 : sqrt(sum / count);
-    for (int i = 0; i < 9; i++) Rout[9 * (size_t)p + i] = R[i];
-    for (int i = 0; i < 3; i++) tout[3 * (size_t)p + i] = t[i];
-    best_iter[p] = best;
-  }
+  pose_abs_tail(s_pose, f[p], tid, o, N, pts_w, pts_2d, errors, avg_error + p, Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
+  if (tid == 0) best_iter[p] = best;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -596,10 +618,7 @@ __global__ __launch_bounds__(EPNPF_BLOCK) void k_epnpf_sweep(int H, int n_steps,
       int idx[4];
       pose_sample<4>(seed, 0x45506E50ull, q, it, N, idx);
       EpnpState S;
-      for (int k = 0; k < 4; k++) {
-        for (int j = 0; j < 3; j++) S.pws[3 * k + j] = pts_w[3 * ((size_t)o + idx[k]) + j];
-        for (int j = 0; j < 2; j++) S.us[2 * k + j] = pts_2d[2 * ((size_t)o + idx[k]) + j];
-      }
+      epnp_load_sample(S, pts_w, pts_2d, o, idx);
       double R[9], t[3];
       const double e = epnp_minimal(S, f_i, R, t);
       if (e < be) {
@@ -657,38 +676,12 @@ __global__ __launch_bounds__(256) void k_epnpf_select(int n_steps, const int* __
     const double e = step_err[q0 + i];
     if (e < be) { be = e; bi = i; }
   }
-  s_e[tid] = be; s_i[tid] = bi;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-      const double e2 = s_e[tid + st];
-      const int i2 = s_i[tid + st];
-      if (i2 >= 0 && (s_i[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && i2 < s_i[tid]))) { s_e[tid] = e2; s_i[tid] = i2; }
-    }
-    __syncthreads();
-  }
+  pose_first_smallest(tid, be, bi, s_e, s_i);
   const int best = s_i[0];
   if (tid < 12) s_pose[tid] = best >= 0 ? step_pose[12 * (q0 + best) + tid] : 0.0;
-  __syncthreads();
-  double R[9], t[3];
-  for (int i = 0; i < 9; i++) R[i] = s_pose[i];
-  for (int i = 0; i < 3; i++) t[i] = s_pose[9 + i];
   const double fp = best >= 0 ? (f_ratio_min + (double)best * f_ratio_step) * f_init[p] : f_init[p];
-  for (int i = tid; i < N; i += 256) {
-    const double e = pose_reproj_err(R, t, fp, pts_w + 3 * ((size_t)o + i), pts_2d + 2 * ((size_t)o + i));
-    errors[o + i] = fabs(e) < 10.0 ? e : 1000.0;
-  }
-  __syncthreads();
+  pose_abs_tail(s_pose, fp, tid, o, N, pts_w, pts_2d, errors, avg_error + p, Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
   if (tid == 0) {
-    double sum = 0.0;
-    int count = 0;
-    for (int i = 0; i < N; i++) {
-      const double e = errors[o + i];
-      if (e < 10.0) { sum += e * e; count++; }
-    }
-    avg_error[p] = count == 0 ? 10000.0 : sqrt(sum / count);
-    for (int i = 0; i < 9; i++) Rout[9 * (size_t)p + i] = R[i];
-    for (int i = 0; i < 3; i++) tout[3 * (size_t)p + i] = t[i];
     f_out[p] = fp;
     best_step[p] = best;
     best_iter[p] = best >= 0 ? step_it[q0 + best] : -1;
@@ -1222,18 +1215,7 @@ __global__ __launch_bounds__(256) void k_e5_select(int T, const int* __restrict_
       if (e < be) { be = e; bk = key; }
     }
   }
-  s_e[tid] = be; s_k[tid] = bk; s_first[tid] = first; s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-      const double e2 = s_e[tid + st];
-      const int k2 = s_k[tid + st];
-      if (k2 >= 0 && (s_k[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && k2 < s_k[tid]))) { s_e[tid] = e2; s_k[tid] = k2; }
-      if (s_first[tid + st] < s_first[tid]) s_first[tid] = s_first[tid + st];
-      s_cnt[tid] += s_cnt[tid + st];
-    }
-    __syncthreads();
-  }
+  pose_first_smallest<true>(tid, be, bk, s_e, s_k, first, cnt, s_first, s_cnt);
   const int nE = s_cnt[0];
   const int key = s_k[0] >= 0 ? s_k[0] : s_first[0];
   if (tid < 4) s_votes[tid] = 0;
@@ -1463,18 +1445,7 @@ __global__ __launch_bounds__(256) void k_f8_select(int T, const int* __restrict_
     const double e = cand_err[(size_t)p * T + it];
     if (e < be) { be = e; bk = it; }
   }
-  s_e[tid] = be; s_k[tid] = bk; s_first[tid] = first; s_cnt[tid] = cnt;
-  __syncthreads();
-  for (int st = 128; st > 0; st >>= 1) {
-    if (tid < st) {
-      const double e2 = s_e[tid + st];
-      const int k2 = s_k[tid + st];
-      if (k2 >= 0 && (s_k[tid] < 0 || e2 < s_e[tid] || (e2 == s_e[tid] && k2 < s_k[tid]))) { s_e[tid] = e2; s_k[tid] = k2; }
-      if (s_first[tid + st] < s_first[tid]) s_first[tid] = s_first[tid + st];
-      s_cnt[tid] += s_cnt[tid + st];
-    }
-    __syncthreads();
-  }
+  pose_first_smallest<true>(tid, be, bk, s_e, s_k, first, cnt, s_first, s_cnt);
   const int nC = s_cnt[0];
   if (tid < 4) s_votes[tid] = 0;
   if (tid == 0) {
@@ -1512,19 +1483,29 @@ __global__ __launch_bounds__(256) void k_f8_select(int T, const int* __restrict_
                     Rout + 9 * (size_t)p, tout + 3 * (size_t)p);
 }
 
-int pose_epnp_dev(msfm_ctx* ctx, int n_problems, const int* d_off, const double* d_w, const double* d_2d, const double* d_f, int max_iter,
-                  uint64_t seed, EpnpScratch& ws, double* dR, double* dt, double* d_err, double* d_avg, int* d_best_iter) {
+// What the four exports upload: offsets, the two point arrays of `wa` / `wb` doubles a row, the focal arrays they have.
+struct PoseInputs {
+  DevBuf<int> off;
+  DevBuf<double> a, b, f1, f2;
+  hipError_t up(DevScope& sc, int n, const int* offsets, const double* pa, int wa, const double* pb, int wb, const double* hf1, const double* hf2) {
+    const size_t total = (size_t)offsets[n];
+    return hip_first_error({sc.up(off, offsets, (size_t)n + 1), sc.up(a, pa, wa * total), sc.up(b, pb, wb * total),
+                            hf1 ? sc.up(f1, hf1, (size_t)n) : hipSuccess, hf2 ? sc.up(f2, hf2, (size_t)n) : hipSuccess});
+  }
+  PoseView view(int n) const { return PoseView{n, off.p, a.p, b.p, f1.p, f2.p}; }
+};
+
+int pose_epnp_dev(msfm_ctx* ctx, const PoseView& V, int max_iter, uint64_t seed, EpnpResult& out) {
   hipStream_t s = ctx->stream;
-  HIP_TRY(ctx, ws.hyp.alloc((size_t)n_problems * max_iter * 13));
+  HIP_TRY(ctx, out.hyp.alloc((size_t)V.n * max_iter * 13));
   {
     KTimer tm(ctx, "pose_epnp_hyp");
-    hipLaunchKernelGGL(k_epnp_hyp, dim3(cdiv(max_iter, POSE_WAVE), n_problems), dim3(POSE_WAVE), 0, s, max_iter, d_off, d_w, d_2d, d_f, seed,
-                       ws.hyp.p);
+    hipLaunchKernelGGL(k_epnp_hyp, dim3(cdiv(max_iter, POSE_WAVE), V.n), dim3(POSE_WAVE), 0, s, max_iter, V.off, V.a, V.b, V.f1, seed, out.hyp.p);
   }
   {
     KTimer tm(ctx, "pose_epnp_select");
-    hipLaunchKernelGGL(k_epnp_select, dim3(n_problems), dim3(256), 0, s, max_iter, d_off, d_w, d_2d, d_f, ws.hyp.p, dR, dt, d_err, d_avg,
-                       d_best_iter);
+    hipLaunchKernelGGL(k_epnp_select, dim3(V.n), dim3(256), 0, s, max_iter, V.off, V.a, V.b, V.f1, out.hyp.p, out.R.p, out.t.p, out.err.p,
+                       out.avg.p, out.best_iter.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
@@ -1541,30 +1522,18 @@ MSFM_API int msfm_epnp_ransac_batch(msfm_ctx* ctx, int n_problems, const int* of
   const int total = offsets[n_problems];
   if (total > 0 && (!pts_w || !pts_2d || !errors)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DevBuf<int> d_off, d_best;
-  DevBuf<double> d_w, d_2d, d_f, d_R, d_t, d_err, d_avg;
-  EpnpScratch ws;
+  const size_t n = (size_t)n_problems;
+  PoseInputs in;
+  EpnpResult out;
   DevScope sc(ctx);
-  HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
-  HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_2d.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_w.upload(pts_w, 3 * (size_t)total, s));
-  HIP_TRY(ctx, d_2d.upload(pts_2d, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_f.alloc(n_problems));
-  HIP_TRY(ctx, d_f.upload(f, n_problems, s));
-  HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_problems));
-  HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_problems));
-  HIP_TRY(ctx, d_err.alloc((size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_avg.alloc(n_problems));
-  HIP_TRY(ctx, d_best.alloc(n_problems));
-  MSFM_TRY(pose_epnp_dev(ctx, n_problems, d_off.p, d_w.p, d_2d.p, d_f.p, max_iter, seed, ws, d_R.p, d_t.p, d_err.p, d_avg.p, d_best.p));
-  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(errors, d_err.p, (size_t)total));
-  HIP_TRY(ctx, sc.down(avg_error, d_avg.p, (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(best_iter, d_best.p, (size_t)n_problems));
+  HIP_TRY(ctx, in.up(sc, n_problems, offsets, pts_w, 3, pts_2d, 2, f, nullptr));
+  HIP_TRY(ctx, out.alloc(n, (size_t)total));
+  MSFM_TRY(pose_epnp_dev(ctx, in.view(n_problems), max_iter, seed, out));
+  HIP_TRY(ctx, sc.down(R, out.R.p, 9 * n));
+  HIP_TRY(ctx, sc.down(t, out.t.p, 3 * n));
+  HIP_TRY(ctx, sc.down(errors, out.err.p, (size_t)total));
+  HIP_TRY(ctx, sc.down(avg_error, out.avg.p, n));
+  HIP_TRY(ctx, sc.down(best_iter, out.best_iter.p, n));
   HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
@@ -1586,23 +1555,20 @@ MSFM_API int msfm_epnpf_num_steps(const msfm_epnpf_options* o) {
   return (int)q;
 }
 
-int pose_epnpf_dev(msfm_ctx* ctx, int n_problems, int n_steps, const int* d_off, const double* d_w, const double* d_2d, const double* d_f_init,
-                   const msfm_epnpf_options* opt, EpnpfScratch& ws, double* d_f_out, double* dR, double* dt, double* d_err, double* d_avg,
-                   int* d_best_step, int* d_best_iter) {
+int pose_epnpf_dev(msfm_ctx* ctx, const PoseView& V, int n_steps, const msfm_epnpf_options* opt, EpnpfResult& out) {
   hipStream_t s = ctx->stream;
-  const size_t Q = (size_t)n_problems * n_steps;
-  HIP_TRY(ctx, ws.step_err.alloc(Q));
-  HIP_TRY(ctx, ws.step_it.alloc(Q));
-  HIP_TRY(ctx, ws.step_pose.alloc(12 * Q));
+  const size_t Q = (size_t)V.n * n_steps;
+  HIP_TRY(ctx, hip_first_error({out.step_err.alloc(Q), out.step_it.alloc(Q), out.step_pose.alloc(12 * Q)}));
   {
     KTimer tm(ctx, "pose_epnpf_sweep");
-    hipLaunchKernelGGL(k_epnpf_sweep, dim3(n_steps, n_problems), dim3(EPNPF_BLOCK), 0, s, opt->max_iter, n_steps, d_off, d_w, d_2d, d_f_init,
-                       opt->f_ratio_min, opt->f_ratio_step, opt->seed, ws.step_err.p, ws.step_it.p, ws.step_pose.p);
+    hipLaunchKernelGGL(k_epnpf_sweep, dim3(n_steps, V.n), dim3(EPNPF_BLOCK), 0, s, opt->max_iter, n_steps, V.off, V.a, V.b, V.f1,
+                       opt->f_ratio_min, opt->f_ratio_step, opt->seed, out.step_err.p, out.step_it.p, out.step_pose.p);
   }
   {
     KTimer tm(ctx, "pose_epnpf_select");
-    hipLaunchKernelGGL(k_epnpf_select, dim3(n_problems), dim3(256), 0, s, n_steps, d_off, d_w, d_2d, d_f_init, opt->f_ratio_min,
-                       opt->f_ratio_step, ws.step_err.p, ws.step_it.p, ws.step_pose.p, d_f_out, dR, dt, d_err, d_avg, d_best_step, d_best_iter);
+    hipLaunchKernelGGL(k_epnpf_select, dim3(V.n), dim3(256), 0, s, n_steps, V.off, V.a, V.b, V.f1, opt->f_ratio_min, opt->f_ratio_step,
+                       out.step_err.p, out.step_it.p, out.step_pose.p, out.f.p, out.R.p, out.t.p, out.err.p, out.avg.p, out.best_step.p,
+                       out.best_iter.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
@@ -1625,63 +1591,42 @@ MSFM_API int msfm_epnpf_sweep_batch(msfm_ctx* ctx, int n_problems, const int* of
   const int total = offsets[n_problems];
   if (total > 0 && (!pts_w || !pts_2d || !errors)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  const size_t Q = (size_t)n_problems * n_steps;
-  DevBuf<int> d_off, d_bstep, d_biter;
-  DevBuf<double> d_w, d_2d, d_f, d_fo, d_R, d_t, d_err, d_avg;
-  EpnpfScratch ws;
+  const size_t n = (size_t)n_problems;
+  PoseInputs in;
+  EpnpfResult out;
   DevScope sc(ctx);
-  HIP_TRY(ctx, d_off.alloc((size_t)n_problems + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_problems + 1, s));
-  HIP_TRY(ctx, d_w.alloc(3 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_2d.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_w.upload(pts_w, 3 * (size_t)total, s));
-  HIP_TRY(ctx, d_2d.upload(pts_2d, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_f.alloc(n_problems));
-  HIP_TRY(ctx, d_f.upload(f_init, n_problems, s));
-  HIP_TRY(ctx, d_fo.alloc(n_problems));
-  HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_problems));
-  HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_problems));
-  HIP_TRY(ctx, d_err.alloc((size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_avg.alloc(n_problems));
-  HIP_TRY(ctx, d_bstep.alloc(n_problems));
-  HIP_TRY(ctx, d_biter.alloc(n_problems));
-  MSFM_TRY(pose_epnpf_dev(ctx, n_problems, n_steps, d_off.p, d_w.p, d_2d.p, d_f.p, opt, ws, d_fo.p, d_R.p, d_t.p, d_err.p, d_avg.p, d_bstep.p,
-                          d_biter.p));
-  HIP_TRY(ctx, sc.down(f_out, d_fo.p, (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(errors, d_err.p, (size_t)total));
-  HIP_TRY(ctx, sc.down(avg_error, d_avg.p, (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(best_step, d_bstep.p, (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(best_iter, d_biter.p, (size_t)n_problems));
-  HIP_TRY(ctx, sc.down(step_error, ws.step_err.p, Q));
+  HIP_TRY(ctx, in.up(sc, n_problems, offsets, pts_w, 3, pts_2d, 2, f_init, nullptr));
+  HIP_TRY(ctx, out.alloc(n, (size_t)total));
+  MSFM_TRY(pose_epnpf_dev(ctx, in.view(n_problems), n_steps, opt, out));
+  HIP_TRY(ctx, sc.down(f_out, out.f.p, n));
+  HIP_TRY(ctx, sc.down(R, out.R.p, 9 * n));
+  HIP_TRY(ctx, sc.down(t, out.t.p, 3 * n));
+  HIP_TRY(ctx, sc.down(errors, out.err.p, (size_t)total));
+  HIP_TRY(ctx, sc.down(avg_error, out.avg.p, n));
+  HIP_TRY(ctx, sc.down(best_step, out.best_step.p, n));
+  HIP_TRY(ctx, sc.down(best_iter, out.best_iter.p, n));
+  HIP_TRY(ctx, sc.down(step_error, out.step_err.p, n * n_steps));
   HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
-int pose_relpose5_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, const double* d_f_ref,
-                      const double* d_f_cur, int ransac_times, uint64_t seed, Relpose5Scratch& ws, double* dE, double* dR, double* dt,
-                      uint8_t* d_ok, int* d_ncand) {
+int pose_relpose5_dev(msfm_ctx* ctx, const PoseView& V, int ransac_times, uint64_t seed, Relpose5Result& out) {
   hipStream_t s = ctx->stream;
   const int T = ransac_times;
-  HIP_TRY(ctx, ws.cE.alloc((size_t)n_pairs * T * 90));
-  HIP_TRY(ctx, ws.ce.alloc((size_t)n_pairs * T * 10));
-  HIP_TRY(ctx, ws.cn.alloc((size_t)n_pairs * T));
+  const size_t C = (size_t)V.n * T;
+  HIP_TRY(ctx, hip_first_error({out.cE.alloc(C * 90), out.ce.alloc(C * 10), out.cn.alloc(C)}));
   {
     KTimer tm(ctx, "pose_e5_hyp");
-    hipLaunchKernelGGL(k_e5_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, seed,
-                       ws.cE.p, ws.cn.p);
+    hipLaunchKernelGGL(k_e5_hyp, dim3(cdiv(T, POSE_WAVE), V.n), dim3(POSE_WAVE), 0, s, T, V.off, V.a, V.b, V.f1, V.f2, seed, out.cE.p, out.cn.p);
   }
   {
     KTimer tm(ctx, "pose_e5_score");
-    hipLaunchKernelGGL(k_e5_score, dim3(cdiv(T * 10, 256), n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, ws.cE.p,
-                       ws.cn.p, ws.ce.p);
+    hipLaunchKernelGGL(k_e5_score, dim3(cdiv(T * 10, 256), V.n), dim3(256), 0, s, T, V.off, V.a, V.b, V.f1, V.f2, out.cE.p, out.cn.p, out.ce.p);
   }
   {
     KTimer tm(ctx, "pose_e5_select");
-    hipLaunchKernelGGL(k_e5_select, dim3(n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, d_f_ref, d_f_cur, ws.cE.p, ws.cn.p, ws.ce.p, dE,
-                       dR, dt, d_ok, d_ncand);
+    hipLaunchKernelGGL(k_e5_select, dim3(V.n), dim3(256), 0, s, T, V.off, V.a, V.b, V.f1, V.f2, out.cE.p, out.cn.p, out.ce.p, out.E.p, out.R.p,
+                       out.t.p, out.ok.p, out.n_cand.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
@@ -1698,52 +1643,39 @@ MSFM_API int msfm_relpose_5pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   const int total = offsets[n_pairs];
   if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DevBuf<int> d_off, d_nc;
-  DevBuf<double> d_a, d_b, d_f1, d_f2, d_E, d_R, d_t;
-  DevBuf<uint8_t> d_ok;
-  Relpose5Scratch ws;
+  const size_t n = (size_t)n_pairs;
+  PoseInputs in;
+  Relpose5Result out;
   DevScope sc(ctx);
-  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_b.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_a.upload(pts_ref, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_b.upload(pts_cur, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_f1.alloc(n_pairs)); HIP_TRY(ctx, d_f1.upload(f_ref, n_pairs, s));
-  HIP_TRY(ctx, d_f2.alloc(n_pairs)); HIP_TRY(ctx, d_f2.upload(f_cur, n_pairs, s));
-  HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs));
-  HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
-  MSFM_TRY(pose_relpose5_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, d_f1.p, d_f2.p, ransac_times, seed, ws, d_E.p, d_R.p, d_t.p, d_ok.p, d_nc.p));
-  HIP_TRY(ctx, sc.down(E, d_E.p, 9 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(ok, d_ok.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(n_candidates, d_nc.p, (size_t)n_pairs));
+  HIP_TRY(ctx, in.up(sc, n_pairs, offsets, pts_ref, 2, pts_cur, 2, f_ref, f_cur));
+  HIP_TRY(ctx, out.alloc(n, (size_t)total));
+  MSFM_TRY(pose_relpose5_dev(ctx, in.view(n_pairs), ransac_times, seed, out));
+  HIP_TRY(ctx, sc.down(E, out.E.p, 9 * n));
+  HIP_TRY(ctx, sc.down(R, out.R.p, 9 * n));
+  HIP_TRY(ctx, sc.down(t, out.t.p, 3 * n));
+  HIP_TRY(ctx, sc.down(ok, out.ok.p, n));
+  HIP_TRY(ctx, sc.down(n_candidates, out.n_cand.p, n));
   HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
-int pose_relpose8_dev(msfm_ctx* ctx, int n_pairs, const int* d_off, const double* d_ref, const double* d_cur, int ransac_times,
-                      uint64_t seed, Relpose8Scratch& ws, double* dF, double* d_f_ref, double* d_f_cur, double* dE, double* dR, double* dt,
-                      uint8_t* d_ok, int* d_best_iter, double* d_best_error, int* d_ncand) {
+int pose_relpose8_dev(msfm_ctx* ctx, const PoseView& V, int ransac_times, uint64_t seed, Relpose8Result& out) {
   hipStream_t s = ctx->stream;
   const int T = ransac_times;
-  HIP_TRY(ctx, ws.cF.alloc((size_t)n_pairs * T * 9));
-  HIP_TRY(ctx, ws.ce.alloc((size_t)n_pairs * T));
-  HIP_TRY(ctx, ws.cok.alloc((size_t)n_pairs * T));
+  const size_t C = (size_t)V.n * T;
+  HIP_TRY(ctx, hip_first_error({out.cF.alloc(C * 9), out.ce.alloc(C), out.cok.alloc(C)}));
   {
     KTimer tm(ctx, "pose_f8_hyp");
-    hipLaunchKernelGGL(k_f8_hyp, dim3(cdiv(T, POSE_WAVE), n_pairs), dim3(POSE_WAVE), 0, s, T, d_off, d_ref, d_cur, seed, ws.cF.p, ws.cok.p);
+    hipLaunchKernelGGL(k_f8_hyp, dim3(cdiv(T, POSE_WAVE), V.n), dim3(POSE_WAVE), 0, s, T, V.off, V.a, V.b, seed, out.cF.p, out.cok.p);
   }
   {
     KTimer tm(ctx, "pose_f8_score");
-    hipLaunchKernelGGL(k_f8_score, dim3(T, n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, ws.cF.p, ws.cok.p, ws.ce.p);
+    hipLaunchKernelGGL(k_f8_score, dim3(T, V.n), dim3(256), 0, s, T, V.off, V.a, V.b, out.cF.p, out.cok.p, out.ce.p);
   }
   {
     KTimer tm(ctx, "pose_f8_select");
-    hipLaunchKernelGGL(k_f8_select, dim3(n_pairs), dim3(256), 0, s, T, d_off, d_ref, d_cur, ws.cF.p, ws.cok.p, ws.ce.p, dF, d_f_ref, d_f_cur,
-                       dE, dR, dt, d_ok, d_best_iter, d_best_error, d_ncand);
+    hipLaunchKernelGGL(k_f8_select, dim3(V.n), dim3(256), 0, s, T, V.off, V.a, V.b, out.cF.p, out.cok.p, out.ce.p, out.F.p, out.f_ref.p,
+                       out.f_cur.p, out.E.p, out.R.p, out.t.p, out.ok.p, out.best_iter.p, out.best_error.p, out.n_cand.p);
   }
   HIP_TRY(ctx, hipGetLastError());
   return MSFM_OK;
@@ -1760,33 +1692,23 @@ MSFM_API int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offse
   const int total = offsets[n_pairs];
   if (total > 0 && (!pts_ref || !pts_cur)) return MSFM_E_INVAL;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipStream_t s = ctx->stream;
-  DevBuf<int> d_off, d_bi, d_nc;
-  DevBuf<double> d_a, d_b, d_F, d_f1, d_f2, d_E, d_R, d_t, d_be;
-  DevBuf<uint8_t> d_ok;
-  Relpose8Scratch ws;
+  const size_t n = (size_t)n_pairs;
+  PoseInputs in;
+  Relpose8Result out;
   DevScope sc(ctx);
-  HIP_TRY(ctx, d_off.alloc((size_t)n_pairs + 1));
-  HIP_TRY(ctx, d_off.upload(offsets, (size_t)n_pairs + 1, s));
-  HIP_TRY(ctx, d_a.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_b.alloc(2 * (size_t)std::max(1, total)));
-  HIP_TRY(ctx, d_a.upload(pts_ref, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_b.upload(pts_cur, 2 * (size_t)total, s));
-  HIP_TRY(ctx, d_F.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_E.alloc(9 * (size_t)n_pairs)); HIP_TRY(ctx, d_R.alloc(9 * (size_t)n_pairs));
-  HIP_TRY(ctx, d_t.alloc(3 * (size_t)n_pairs)); HIP_TRY(ctx, d_f1.alloc(n_pairs)); HIP_TRY(ctx, d_f2.alloc(n_pairs));
-  HIP_TRY(ctx, d_ok.alloc(n_pairs)); HIP_TRY(ctx, d_bi.alloc(n_pairs)); HIP_TRY(ctx, d_be.alloc(n_pairs)); HIP_TRY(ctx, d_nc.alloc(n_pairs));
-  MSFM_TRY(pose_relpose8_dev(ctx, n_pairs, d_off.p, d_a.p, d_b.p, ransac_times, seed, ws, d_F.p, d_f1.p, d_f2.p, d_E.p, d_R.p, d_t.p, d_ok.p, d_bi.p,
-                             d_be.p, d_nc.p));
-  HIP_TRY(ctx, sc.down(F, d_F.p, 9 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(f_ref, d_f1.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(f_cur, d_f2.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(E, d_E.p, 9 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(R, d_R.p, 9 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(t, d_t.p, 3 * (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(ok, d_ok.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(best_iter, d_bi.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(best_error, d_be.p, (size_t)n_pairs));
-  HIP_TRY(ctx, sc.down(n_candidates, d_nc.p, (size_t)n_pairs));
+  HIP_TRY(ctx, in.up(sc, n_pairs, offsets, pts_ref, 2, pts_cur, 2, nullptr, nullptr));
+  HIP_TRY(ctx, out.alloc(n, (size_t)total));
+  MSFM_TRY(pose_relpose8_dev(ctx, in.view(n_pairs), ransac_times, seed, out));
+  HIP_TRY(ctx, sc.down(F, out.F.p, 9 * n));
+  HIP_TRY(ctx, sc.down(f_ref, out.f_ref.p, n));
+  HIP_TRY(ctx, sc.down(f_cur, out.f_cur.p, n));
+  HIP_TRY(ctx, sc.down(E, out.E.p, 9 * n));
+  HIP_TRY(ctx, sc.down(R, out.R.p, 9 * n));
+  HIP_TRY(ctx, sc.down(t, out.t.p, 3 * n));
+  HIP_TRY(ctx, sc.down(ok, out.ok.p, n));
+  HIP_TRY(ctx, sc.down(best_iter, out.best_iter.p, n));
+  HIP_TRY(ctx, sc.down(best_error, out.best_error.p, n));
+  HIP_TRY(ctx, sc.down(n_candidates, out.n_cand.p, n));
   HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }

@@ -231,13 +231,13 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<Hyp> d_hyp;
-  DevBuf<int> d_offa, d_off5, d_off8, d_blk, d_nc5, d_bi8, d_nc8, d_ptm, d_count;
-  DevBuf<double> d_fk, d_ref5, d_cur5, d_ref8, d_cur8, d_f5a, d_f5b, d_E5, d_R5, d_t5, d_F8, d_f8a, d_f8b, d_E8, d_R8, d_t8, d_be8;
+  DevBuf<int> d_offa, d_off5, d_off8, d_blk, d_ptm, d_count;
+  DevBuf<double> d_fk, d_ref5, d_cur5, d_ref8, d_cur8, d_f5a, d_f5b;
   DevBuf<double> d_fout, d_cam, d_Xall, d_mseall, d_X, d_mse;
-  DevBuf<uint8_t> d_same, d_ok5, d_ok8, d_pok, d_flag, d_pass;
+  DevBuf<uint8_t> d_same, d_pok, d_flag, d_pass;
   DevBuf<float> d_kp_up;
-  Relpose5Scratch ws5;
-  Relpose8Scratch ws8;
+  Relpose5Result r5;
+  Relpose8Result r8;
   DevScope sc(ctx);
   SD_TRY(sc.up(d_hyp, hyp.data(), (size_t)n)); SD_TRY(sc.up(d_offa, off_all.data(), (size_t)n + 1)); SD_TRY(sc.up(d_off5, off5.data(), (size_t)n + 1));
   SD_TRY(sc.up(d_off8, off8.data(), (size_t)n + 1)); SD_TRY(sc.up(d_blk, blk_off.data(), (size_t)n + 1)); SD_TRY(sc.up(d_fk, P->cam_fk, 6 * (size_t)n));
@@ -255,13 +255,12 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   const size_t Mx = (size_t)std::max(1, M);
   SD_TRY(d_ref5.alloc(2 * (size_t)std::max(1, M5))); SD_TRY(d_cur5.alloc(2 * (size_t)std::max(1, M5)));
   SD_TRY(d_ref8.alloc(2 * (size_t)std::max(1, M8))); SD_TRY(d_cur8.alloc(2 * (size_t)std::max(1, M8)));
-  SD_TRY(d_ok5.alloc(n)); SD_TRY(d_ok8.alloc(n)); SD_TRY(d_R5.alloc(9 * (size_t)n)); SD_TRY(d_t5.alloc(3 * (size_t)n));
-  SD_TRY(d_R8.alloc(9 * (size_t)n)); SD_TRY(d_t8.alloc(3 * (size_t)n)); SD_TRY(d_f8a.alloc(n)); SD_TRY(d_f8b.alloc(n));
+  SD_TRY(r5.alloc(n, M5)); SD_TRY(r8.alloc(n, M8));   // both: k_camera gets every array, and reads an arm's only where its ok is set
   SD_TRY(d_pok.alloc(n)); SD_TRY(d_fout.alloc(2 * (size_t)n)); SD_TRY(d_cam.alloc(SEED_CAM * (size_t)n));
   SD_TRY(d_flag.alloc(Mx)); SD_TRY(d_Xall.alloc(3 * Mx)); SD_TRY(d_mseall.alloc(Mx));
   SD_TRY(d_ptm.alloc(Mx)); SD_TRY(d_X.alloc(3 * Mx)); SD_TRY(d_mse.alloc(Mx)); SD_TRY(d_count.alloc(n)); SD_TRY(d_pass.alloc(n));
   // an arm without a match is not launched: its hypotheses have failed (fewer than 5 / 8 matches)
-  SD_TRY(hipMemsetAsync(d_ok5.p, 0, (size_t)n, s)); SD_TRY(hipMemsetAsync(d_ok8.p, 0, (size_t)n, s));
+  SD_TRY(hipMemsetAsync(r5.ok.p, 0, (size_t)n, s)); SD_TRY(hipMemsetAsync(r8.ok.p, 0, (size_t)n, s));
   if (M) {
     KTimer tm(ctx, "seed_gather");
     hipLaunchKernelGGL(k_gather, dim3(cdiv(M, 256)), dim3(256), 0, s, M, n, d_offa.p, d_hyp.p, d_off5.p, d_off8.p, S->d_match.p, d_kp, d_ref5.p, d_cur5.p,
@@ -272,19 +271,13 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     // the eight-point hypotheses' entries (problems without matches) are not read
     for (int h = 0; h < n; h++) { f5_ref[h] = P->cam_fk[6 * (size_t)h]; f5_cur[h] = P->cam_fk[6 * (size_t)h + 3]; }
     SD_TRY(sc.up(d_f5a, f5_ref.data(), (size_t)n)); SD_TRY(sc.up(d_f5b, f5_cur.data(), (size_t)n));
-    SD_TRY(d_E5.alloc(9 * (size_t)n)); SD_TRY(d_nc5.alloc(n));
-    MSFM_TRY(pose_relpose5_dev(ctx, n, d_off5.p, d_ref5.p, d_cur5.p, d_f5a.p, d_f5b.p, opt.ransac_times_5pt, opt.seed_5pt, ws5, d_E5.p, d_R5.p, d_t5.p,
-                               d_ok5.p, d_nc5.p));
+    MSFM_TRY(pose_relpose5_dev(ctx, PoseView{n, d_off5.p, d_ref5.p, d_cur5.p, d_f5a.p, d_f5b.p}, opt.ransac_times_5pt, opt.seed_5pt, r5));
   }
-  if (M8) {
-    SD_TRY(d_F8.alloc(9 * (size_t)n)); SD_TRY(d_E8.alloc(9 * (size_t)n)); SD_TRY(d_bi8.alloc(n)); SD_TRY(d_be8.alloc(n)); SD_TRY(d_nc8.alloc(n));
-    MSFM_TRY(pose_relpose8_dev(ctx, n, d_off8.p, d_ref8.p, d_cur8.p, opt.ransac_times_8pt, opt.seed_8pt, ws8, d_F8.p, d_f8a.p, d_f8b.p, d_E8.p, d_R8.p,
-                               d_t8.p, d_ok8.p, d_bi8.p, d_be8.p, d_nc8.p));
-  }
+  if (M8) MSFM_TRY(pose_relpose8_dev(ctx, PoseView{n, d_off8.p, d_ref8.p, d_cur8.p, nullptr, nullptr}, opt.ransac_times_8pt, opt.seed_8pt, r8));
   {
     KTimer tm(ctx, "seed_camera");
-    hipLaunchKernelGGL(k_camera, dim3(cdiv(n, 64)), dim3(64), 0, s, n, d_hyp.p, d_fk.p, d_same.p, d_ok5.p, d_R5.p, d_t5.p, d_ok8.p, d_R8.p, d_t8.p,
-                       d_f8a.p, d_f8b.p, d_pok.p, d_fout.p, d_cam.p);
+    hipLaunchKernelGGL(k_camera, dim3(cdiv(n, 64)), dim3(64), 0, s, n, d_hyp.p, d_fk.p, d_same.p, r5.ok.p, r5.R.p, r5.t.p, r8.ok.p, r8.R.p, r8.t.p,
+                       r8.f_ref.p, r8.f_cur.p, d_pok.p, d_fout.p, d_cam.p);
   }
   if (M) {
     KTimer tm(ctx, "seed_triangulate");

@@ -53,6 +53,38 @@ def test_epnp_degenerate_inputs(ctx, O):
     equal(ctx.epnp_ransac(off, X, x, 4800.0, max_iter=64), O.epnp_ransac(off, X, x, 4800.0, max_iter=64))
 
 
+def test_epnp_ties_go_to_the_lowest_sample_past_one_stride(ctx, O):
+    """Every sample of these problems scores the same, so sample 0 must win over the samples a thread meets in its later
+    strides (max_iter > 256) and over those of the other threads."""
+    rng = np.random.default_rng(5)
+    off = np.array([0, 30, 60, 90], np.int32)
+    X = np.concatenate([np.column_stack([rng.uniform(-40, 40, 30), rng.uniform(-30, 30, 30), np.zeros(30)]),
+                        np.tile([[1.0, 2.0, 3.0]], (30, 1)),
+                        np.column_stack([np.arange(30.0), 2 * np.arange(30.0), 3 * np.arange(30.0)])])
+    x = rng.uniform(-1000, 1000, (90, 2))
+    for iters in (1, 65, 300):
+        o = O.epnp_ransac(off, X, x, 4800.0, max_iter=iters)
+        assert o[4].tolist() == [0, 0, 0] and o[3].tolist() == [10000.0] * 3, iters
+        equal(ctx.epnp_ransac(off, X, x, 4800.0, max_iter=iters), o)
+
+
+def test_relpose_no_candidate_below_the_threshold(ctx, O):
+    """Unrelated points: in the pairs of 300 and of 40 matches no Sampson sum is below 1e6, so the first candidate is kept
+    however many follow (65 and 300 samples); one sample gives fewer than four candidates and the zero record.  (Ten
+    unrelated matches do have candidates below 1e6: that pair takes the ordinary path and is compared like the others.)"""
+    rng = np.random.default_rng(3)
+    sizes = [300, 10, 40]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    a = rng.uniform(-2000, 2000, (off[-1], 2))
+    b = rng.uniform(-2000, 2000, (off[-1], 2))
+    want = {times: O.relpose_5pt(off, a, b, 1.0, 1.0, ransac_times=times, seed=4) for times in (1, 65, 300)}
+    assert (want[1][4] == 2).all() and (want[1][3] == 0).all()
+    assert (want[65][3] == 1).all() and (want[300][3] == 1).all()
+    np.testing.assert_array_equal(want[65][0][[0, 2]], want[300][0][[0, 2]])
+    for times, o in want.items():
+        equal(ctx.relpose_5pt(off, a, b, 1.0, 1.0, ransac_times=times, seed=4), o)
+
+
 def test_epnp_is_independent_of_the_batch_split(ctx):
     off, X, x, _, _ = make_pnp_batch(31, [80, 90, 100], outlier_frac=0.2)
     whole = ctx.epnp_ransac(off, X, x, 4800.0)

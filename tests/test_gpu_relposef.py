@@ -53,6 +53,21 @@ def test_options(ctx, ref, seed, times):
     same(ctx.relpose_8pt(off, a, b, ransac_times=times, seed=seed), D.ref_relpose_8pt(ref, off, a, b, ransac_times=times, seed=seed))
 
 
+def test_no_candidate_below_the_threshold(ctx, ref):
+    """Unrelated points: every fit scores 1e6 or more, so the first candidate is kept and best_error stays at its start,
+    whether the candidates fit one stride of the selection's 256 threads or not."""
+    rng = np.random.default_rng(3)
+    sizes = [300, 16, 40]
+    off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    a = rng.uniform(-2000, 2000, (off[-1], 2))
+    b = rng.uniform(-2000, 2000, (off[-1], 2))
+    for times in (1, 65, 300):
+        want = D.ref_relpose_8pt(ref, off, a, b, ransac_times=times, seed=4)
+        ok, bi, be, nc = want[6], want[7], want[8], want[9]
+        assert (be == 1e6).all() and (bi == 0).all() and (nc == times).all() and (ok == 0).all(), times
+        same(ctx.relpose_8pt(off, a, b, ransac_times=times, seed=4), want)
+
+
 def test_golden_fixture(ctx):
     g = np.load(GOLD)
     got = ctx.relpose_8pt(g["off"], g["pts_ref"], g["pts_cur"], ransac_times=int(g["ransac_times"]), seed=int(g["seed"]))
