@@ -306,8 +306,18 @@ typedef struct msfm_ba_layout {
    * were summed into the system by workgroups of the per-camera sums' launch and the blocks finished by the launches that
    * form the per-camera and per-intrinsics sums; 0 = by a launch of its own behind them */
   int assemble_paths;
+  /* what rode along with the launches of the last factor-and-solve of msfm_ba_run instead of being a launch of its own (0
+   * before the first solve, and always with MSFM_SOLVE_RIDERS=0): MSFM_PATH_RIDER_MODELSUM = the per-intrinsics sums and the
+   * intrinsics block of the system, by extra workgroups of the first corner update (only with MSFM_PATH_ASM_BESIDE and an
+   * elimination tree); MSFM_PATH_RIDER_UPDATE = the camera / intrinsics part of the step, by the back substitution's launch
+   * block by block behind the publication of each (only where that is one launch and the point part of the step has the
+   * workgroups for its block sums).  The bits of this field are
+   * distinct from those of the two fields above, so that a value read from the wrong field shows. */
+  int rider_paths;
 } msfm_ba_layout;
 #define MSFM_PATH_ASM_BESIDE 1
+#define MSFM_PATH_RIDER_MODELSUM (1 << 8)
+#define MSFM_PATH_RIDER_UPDATE (1 << 9)
 #define MSFM_PATH_LEVEL_CHAIN(l) (1 << (l))
 #define MSFM_PATH_ROOT_CHAIN (1 << 3)
 #define MSFM_PATH_BACKSOLVE_CHAIN (1 << 4)

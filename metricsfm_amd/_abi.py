@@ -19,6 +19,9 @@ MSFM_PATH_ROOT_CHAIN = 1 << 3
 MSFM_PATH_BACKSOLVE_CHAIN = 1 << 4
 # msfm_ba_layout.assemble_paths
 MSFM_PATH_ASM_BESIDE = 1
+# msfm_ba_layout.rider_paths
+MSFM_PATH_RIDER_MODELSUM = 1 << 8
+MSFM_PATH_RIDER_UPDATE = 1 << 9
 
 
 def MSFM_PATH_LEVEL_CHAIN(level):
@@ -44,7 +47,8 @@ class BaLayout(C.Structure):
                 ("level_begin", C.c_int * 3), ("root_cols", C.c_int),
                 ("cc_entries", C.c_longlong), ("cc_entries_folded", C.c_longlong), ("fold_slots", C.c_int), ("fold_passes", C.c_int),
                 ("mc_entries", C.c_longlong), ("mc_entries_folded", C.c_longlong), ("fold_mc_slots", C.c_int), ("solve_paths", C.c_int),
-                ("npb_S", C.c_int), ("npb_L", C.c_int), ("npb_X", C.c_int), ("npb_S4", C.c_int), ("assemble_paths", C.c_int)]
+                ("npb_S", C.c_int), ("npb_L", C.c_int), ("npb_X", C.c_int), ("npb_S4", C.c_int), ("assemble_paths", C.c_int),
+                ("rider_paths", C.c_int)]
 
 
 class FransacOptions(C.Structure):

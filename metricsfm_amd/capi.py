@@ -1621,7 +1621,7 @@ class BaResident:
                     level_nodes=list(lay.level_nodes)[:lay.n_levels], level_begin=list(lay.level_begin)[:lay.n_levels], root_cols=lay.root_cols,
                     fold=dict(cc_entries=lay.cc_entries, cc_entries_folded=lay.cc_entries_folded, slots=lay.fold_slots, passes=lay.fold_passes,
                               mc_entries=lay.mc_entries, mc_entries_folded=lay.mc_entries_folded, mc_slots=lay.fold_mc_slots),
-                    solve_paths=lay.solve_paths, assemble_paths=lay.assemble_paths, npb_S=lay.npb_S, npb_L=lay.npb_L, npb_X=lay.npb_X, npb_S4=lay.npb_S4)
+                    solve_paths=lay.solve_paths, assemble_paths=lay.assemble_paths, rider_paths=lay.rider_paths, npb_S=lay.npb_S, npb_L=lay.npb_L, npb_X=lay.npb_X, npb_S4=lay.npb_S4)
 
     def upload(self, cam_pose=None, cam_model=None, point=None):
         cp, cm, pt = A.as_c(cam_pose, np.float64), A.as_c(cam_model, np.float64), A.as_c(point, np.float64)

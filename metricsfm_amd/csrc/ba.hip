@@ -27,6 +27,7 @@
 
 #include "ba_device.h"
 #include "common.h"
+#include "solve_riders.h"
 
 
 #define PSTRIDE 80   // doubles per FTF partial
@@ -49,6 +50,7 @@ static int chunk_for(long total, int max_chunk) {
 #define F_JCR 63     // 6
 #define F_JMR 69     // 3
 #define F_TU 72      // 6
+static_assert(PSTRIDE == MODELSUM_PSTRIDE && F_JMJM == MODELSUM_JMJM && F_JMR == MODELSUM_JMR, "solve_riders.h reads the FTF partials");
 
 // scalar slots (device `scal` array)
 // Scalars of one LM iteration.  [0, S_GMAX) are sums over ranks (S_FAIL: non-zero on any rank = failure), S_GMAX a
@@ -961,85 +963,12 @@ __global__ void k_cam_post(int ncb, const double* __restrict__ camftf, double* _
   gmax_c[i] = fabs(f[F_JCR + a] / scale_c[i]);
 }
 
-// Per intrinsics block: sum camftf(Jm^T Jm | Jm^T r) over its cameras (one wave, lanes strided,
-// fixed butterfly) -> modelsum[mb][12]; LM diagonal / raw norms; gradient.
-// fin.M set (see CamFinish; one intrinsics block at most, so its diagonal block is the only intrinsics x intrinsics block): the
-// launch has a second wave, which sums the block's chunk partials (written by the launch before) beside the model sum; the
-// first wave then assembles the block and its rhs entries from both, as asm_mm does.
-struct ModelFinish {
-  double* M; int ld, n, mo, n_mm;
-  const int *mm_row, *mm_col, *mm_first; const double* mm_partial;
-  double radius;
-};
-__device__ __forceinline__ void mm_chunk_sums(int b, const int* __restrict__ blk_chunk_first, const double* __restrict__ partial, int lane, double (&acc)[12]);
-__device__ __forceinline__ void mm_finish(int mb, int lane, const ModelFinish& f, const double* mmacc, const double* __restrict__ modelsum, const double* __restrict__ diag_m) {
-  if (lane < 9) {
-    const int a = lane / 3, c = lane % 3;
-    double v = -mmacc[lane];
-    v += modelsum[12 * (size_t)mb + lane];
-    if (a == c) { const double q = sqrt(diag_m[3 * mb + a] / f.radius); v += q * q; }
-    f.M[(size_t)(f.mo + 3 * mb + a) * f.ld + f.mo + 3 * mb + c] = v;
-  } else if (lane < 12) {
-    f.M[(size_t)f.n * f.ld + f.mo + 3 * mb + lane - 9] = modelsum[12 * (size_t)mb + lane] - mmacc[lane];
-  }
-}
-__global__ __launch_bounds__(128) void k_modelsum(const int* __restrict__ mcam_first, const int* __restrict__ mcam,
-                                                  const double* __restrict__ camftf, double* __restrict__ modelsum,
-                                                  double* __restrict__ diag_m, const double* __restrict__ scale_m, int reuse_diag,
-                                                  int mode, double dmin, double dmax, double* __restrict__ gmax_m, ModelFinish fin) {
-  __shared__ double mmacc[13];   // the second wave's sums; [12]: the block is in the list
-  const int mb = blockIdx.x, lane = threadIdx.x & 63;
-  if (threadIdx.x >= 64) {   // (only with fin.M)
-    int blk = -1;
-    for (int b = 0; b < fin.n_mm; b++) if (fin.mm_row[b] == mb && fin.mm_col[b] == mb) blk = b;
-    if (blk >= 0) {
-      double a12[12];
-      mm_chunk_sums(blk, fin.mm_first, fin.mm_partial, lane, a12);
-#pragma unroll
-      for (int k = 0; k < 12; k++) if (k == lane) mmacc[k] = a12[k];
-    }
-    if (lane == 0) mmacc[12] = blk >= 0 ? 1.0 : 0.0;
-    __syncthreads();
-    return;
-  }
-  double acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = 0.0;
-  // (a lane's cameras q, q + 64, ... in that order; the records of FOUR of them are asked for before the first is added - the
-  //  launch is one wave whose time is its dependent load rounds: 8 rounds of 12 loads at config 3, 12.7 us, before)
-  const int q1 = mcam_first[mb + 1];
-  for (int q = mcam_first[mb] + lane; q < q1; q += 256) {
-    double v[4][12];
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      const int qq = q + 64 * j;
-      const double* f = camftf + (size_t)mcam[min(qq, q1 - 1)] * PSTRIDE;
-#pragma unroll
-      for (int k = 0; k < 9; k++) v[j][k] = f[F_JMJM + k];
-#pragma unroll
-      for (int k = 0; k < 3; k++) v[j][9 + k] = f[F_JMR + k];
-    }
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-      if (q + 64 * j < q1) {
-#pragma unroll
-        for (int k = 0; k < 12; k++) acc[k] += v[j][k];
-      }
-  }
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = wave_sum(acc[k]);
-  if (lane == 0) {
-    for (int k = 0; k < 12; k++) modelsum[12 * (size_t)mb + k] = acc[k];
-    for (int a = 0; a < 3; a++) {
-      const double s = acc[a * 3 + a];
-      if (mode == 1) diag_m[3 * mb + a] = s;
-      else if (!reuse_diag) diag_m[3 * mb + a] = fmin(fmax(s, dmin), dmax);
-      gmax_m[3 * mb + a] = fabs(acc[9 + a] / scale_m[3 * mb + a]);
-    }
-  }
-  if (!fin.M) return;
-  __syncthreads();   // (the second wave's sums; modelsum and diag_m of this block, written by lane 0 above, are read back by the other lanes)
-  if (mmacc[12] != 0.0) mm_finish(mb, lane, fin, mmacc, modelsum, diag_m);
+// Per intrinsics block: the model sums, LM diagonal and gradient entries and, with A.fin.M, the intrinsics block of the reduced
+// system (modelsum_body, solve_riders.h).  A launch of its own wherever the work cannot ride with the factorisation's level-0
+// corner update (run_assemble); 64 threads, 128 with A.fin.M.
+__global__ __launch_bounds__(128) void k_modelsum(ModelSumArgs A) {
+  __shared__ double mmacc[13];
+  modelsum_body(A, blockIdx.x, threadIdx.x, mmacc);
 }
 
 // jacobian_scaling = 1 / (1 + sqrt(squared column norm))  (Ceres, iteration 0)
@@ -1393,30 +1322,7 @@ __device__ __forceinline__ void fold_sum_mc(int b, int lane, const FoldSumArgs& 
   M[(size_t)(f.mo + 3 * mb + t / 6) * ld + f.cb_off[cb] + t % 6] = -s;
 }
 
-// intrinsics-intrinsics blocks: one wave per block, lanes strided over chunks.
-// partial layout per chunk: 9 (Tm Tm'^T) + 3 (sum Tm.u, self pairs only).
-__device__ __forceinline__ void mm_chunk_sums(int b, const int* __restrict__ blk_chunk_first, const double* __restrict__ partial, int lane, double (&acc)[12]) {
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = 0.0;
-  int ch = blk_chunk_first[b] + lane;
-  const int ch1 = blk_chunk_first[b + 1];
-  for (; ch + 192 < ch1; ch += 256) {   // the records of four of a lane's chunks asked for at once, added in chunk order as below
-    double v[4][12];
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-      for (int k = 0; k < 12; k++) v[j][k] = partial[(size_t)(ch + 64 * j) * 12 + k];
-#pragma unroll
-    for (int j = 0; j < 4; j++)
-#pragma unroll
-      for (int k = 0; k < 12; k++) acc[k] += v[j][k];
-  }
-  for (; ch < ch1; ch += 64)
-#pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] += partial[(size_t)ch * 12 + k];
-#pragma unroll
-  for (int k = 0; k < 12; k++) acc[k] = wave_sum(acc[k]);
-}
+// intrinsics-intrinsics blocks: one wave per block, lanes strided over chunks (mm_chunk_sums: solve_riders.h).
 __device__ __forceinline__ void asm_mm(int b, const int* __restrict__ blk_row, const int* __restrict__ blk_col,
                                        const int* __restrict__ blk_chunk_first, const double* __restrict__ partial,
                                        const double* __restrict__ modelsum, const double* __restrict__ diag_m, double radius,
@@ -1555,6 +1461,30 @@ __global__ __launch_bounds__(256) void k_update_params(int ncb, int nmb, const i
   const double t2 = block_sum256(x2, sh);
   if (threadIdx.x == 0) { dx2_partial[blockIdx.x] = t1; x2_partial[blockIdx.x] = t2; }
 }
+// The same work inside the solve (SolveEpilogue, solve_riders.h): k_backsolve_chain forms z, the candidates and the squares per
+// scalar for the columns of each block, and the first workgroups of k_backsub sum the squares in the blocks of 256 above.
+// k_col_map (msfm_ba_create, once): parameter i of k_update_params and its place in cam / model, by column of the system;
+// col_param holds -1 everywhere beforehand (padding columns, the rhs column).
+__global__ void k_col_map(int ncb, int nmb, const int* __restrict__ cb_cam, const int* __restrict__ mb_model, const int* __restrict__ cb_off,
+                          int mo, int* __restrict__ col_param, int* __restrict__ col_slot) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 6 * ncb + 3 * nmb) return;
+  int col, slot;
+  if (i < 6 * ncb) { const int b = i / 6, a = i % 6; col = cb_off[b] + a; slot = cb_cam[b] * 6 + a; }
+  else { const int j = i - 6 * ncb, b = j / 3, a = j % 3; col = mo + j; slot = mb_model[b] * 3 + a; }
+  col_param[col] = i;
+  col_slot[col] = slot;
+}
+// the block sums of k_update_params from the squares per scalar: workgroup b of k_backsub, b < P.nbu
+__device__ __forceinline__ void update_block_sums(int n, const double* __restrict__ dx2s, const double* __restrict__ x2s,
+                                                  double* __restrict__ dx2_partial, double* __restrict__ x2_partial, double* sh) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  double dx2 = 0.0, x2 = 0.0;
+  if (i < n) { dx2 = dx2s[i]; x2 = x2s[i]; }
+  const double t1 = block_sum256(dx2, sh);
+  const double t2 = block_sum256(x2, sh);
+  if (threadIdx.x == 0) { dx2_partial[blockIdx.x] = t1; x2_partial[blockIdx.x] = t2; }
+}
 
 struct BackPtrs {
   BaPtrs B;   // the rows are linearised again (obs_linearize) at the point the reduced system was built at
@@ -1565,8 +1495,16 @@ struct BackPtrs {
   double* pt_c;
   double* cm_Xc;   // the candidate's coordinates again, at the camera-major positions of the point's rows (CamRows::X)
   int Nc;                  // the first Nc threads of the launch also prepare the candidate cameras' rotations
-  const double* cam_c;     // (final before this launch: k_update_params)
+  const double* cam_c;     // (final before this launch: k_update_params, or the solve's epilogue)
   double* rot_c;
+};
+// The solve's epilogue left the squares of the camera / intrinsics step per scalar: the first nbu workgroups of k_backsub also
+// sum them in blocks of 256, into the places k_update_params would have written (nbu = 0: that launch ran).  An argument of
+// its own behind the others, so that nothing moves in front of the point workgroups' own code.
+struct UpdateSums {
+  int nbu, n;
+  const double *dx2, *x2;
+  double *dx2_partial, *x2_partial;
 };
 
 // The workgroups and lane groups of k_point (PtMap: LPP = 4, 8 or 16 lanes per point, lane = observation, or rounds of 8 for
@@ -1658,13 +1596,14 @@ __device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __rest
   if (threadIdx.x == 0) { mcc_partial[blockIdx.x] = t0; dx2_partial[blockIdx.x] = t1; x2_partial[blockIdx.x] = t2; }
 }
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_backsub(BackPtrs P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
-                                                  double* __restrict__ x2_partial) {
+                                                  double* __restrict__ x2_partial, UpdateSums U) {
   __shared__ double sh[4];
   const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
   if (lanes == 4) k_backsub_body<4>(P, mcc_partial, dx2_partial, x2_partial, sh);
   else if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh);
   else if (lanes == 16) k_backsub_body<16>(P, mcc_partial, dx2_partial, x2_partial, sh);
   else k_backsub_body<0>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  if ((int)blockIdx.x < U.nbu) update_block_sums(U.n, U.dx2, U.x2, U.dx2_partial, U.x2_partial, sh);
 }
 
 // model cost change of rows without an eliminated point (obs [AE, A)) and of the GPS rows.
@@ -1885,6 +1824,12 @@ struct msfm_ba {
   DevBuf<double> partial_x;   // cost partials at x (k_point, the rows of frozen points, the GPS rows): alive until the step's last k_reduce
   bool m_zeroed = false;      // M is zeroed for the next assembly (k_tail, behind a completed solve); cleared by every assembly
   int asm_paths = 0;          // MSFM_PATH_ASM_BESIDE of the last assembly (msfm_ba_layout.assemble_paths)
+  // the riders of the factor-and-solve (solve_riders.h; MSFM_SOLVE_RIDERS=0: none)
+  bool modelsum_rides = false;   // the last assembly left its k_modelsum to the solve that follows it: run_solve hands modelsum_args on
+  ModelSumArgs modelsum_args;
+  DevBuf<int> col_param, col_slot;   // SolveEpilogue: by column of the system (k_col_map)
+  DevBuf<double> upd_dx2, upd_x2;    // squares of the camera / intrinsics step per scalar
+  int rider_paths = 0;           // MSFM_PATH_RIDER_* of the last solve (msfm_ba_layout.rider_paths)
   int n_defer = 0;            // jobs of the assembly's k_reduce that the step's last k_reduce takes over (run_solve)
   struct { const double* p; int n; int slot; int is_max; } defer[2];
   double* swrite = nullptr;  // where the kernels put scalars: scal (one rank) or sloc (partials, summed by reduce_scalars)
@@ -3968,9 +3913,15 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart); AL(partial_x, npart);
   AL(gmax_buf, (size_t)ba->nblk_pt + 6 * (size_t)ncb + 3 * (size_t)nmb + 8);
   AL(scal, S_N); AL(sloc, S_N); AL(spec, 8);
+  AL(col_param, ba->npad); AL(col_slot, ba->npad); AL(upd_dx2, ba->nred); AL(upd_x2, ba->nred);
   ba->spec_on = ba->env.spec;
   HIP_TRY(ctx, ba->fail.alloc(4));
 #undef AL
+  HIP_TRY(ctx, hipMemsetAsync(ba->col_param.p, 0xFF, sizeof(int) * (size_t)std::max(1, ba->npad), s));   // -1: no parameter behind the column
+  HIP_TRY(ctx, hipMemsetAsync(ba->col_slot.p, 0, sizeof(int) * (size_t)std::max(1, ba->npad), s));
+  if (ba->nred > 0)
+    hipLaunchKernelGGL(k_col_map, dim3(cdiv(ba->nred, 256)), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo,
+                       ba->col_param.p, ba->col_slot.p);
   // the first solve's solution buffer starts out "pending"; from then on every solve marks the other one (k_backsolve_chain)
   MSFM_TRY(msfm_chol_fill_pending(ctx, ba->zsys.p, ba->npad));
   if (ba->nred > 0) MSFM_TRY(msfm_chol_ws_create(ctx, ba->npad, &ba->chol_ws));
@@ -4056,6 +4007,7 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
   }
   out->solve_paths = ba->solve_paths;
   out->assemble_paths = ba->asm_paths;
+  out->rider_paths = ba->rider_paths;
   out->npb_S = ba->map.nQ + ba->map.nS; out->npb_L = ba->map.nL; out->npb_X = ba->map.nX; out->npb_S4 = ba->n_short4;
   return MSFM_OK;
 }
@@ -4219,7 +4171,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
                          ba->cc.ch_end.p, ba->cc.pa.p, ba->cc.pb.p, ba->T.p, ba->T.p, (const double*)nullptr, ncr, ba->cc.partial.p);
   };
   const bool m_zeroed = ba->m_zeroed;
-  if (mode == 0) { ba->m_zeroed = false; ba->n_defer = 0; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; }
+  if (mode == 0) { ba->m_zeroed = false; ba->n_defer = 0; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; ba->modelsum_rides = false; }
   // zero fill of the reduced system in front of the assembly, as a launch of its own
   auto zero_system = [&]() -> int {
     ZeroMap Z;
@@ -4287,8 +4239,21 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       ModelFinish fin;
       memset(&fin, 0, sizeof fin);
       if (beside) fin = ModelFinish{ba->M.p, ba->npad, ba->nsys, ba->mo, ba->mm.n_blocks, ba->mm.blk_row.p, ba->mm.blk_col.p, ba->mm.blk_chunk_first.p, ba->mm.partial.p, radius};
-      hipLaunchKernelGGL(k_modelsum, dim3(nmb), dim3(beside ? 128 : 64), 0, s, ba->mcam_first.p, ba->mcam.p, ba->camftf.p, ba->modelsum.p,
-                         ba->diag_m.p, ba->scale_m.p, reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_m, fin);
+      const ModelSumArgs ma{nmb, ba->mcam_first.p, ba->mcam.p, ba->camftf.p, ba->modelsum.p, ba->diag_m.p, ba->scale_m.p, reuse_diag ? 1 : 0, mode,
+                            opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_m, fin};
+      // Beside, with an elimination tree and a solve behind this assembly, nothing needs these results before the merge of the
+      // factorisation's level-0 corner update: they are columns of the root (the level-0 chains leave the tiles among the rows
+      // from b0 on out, the corner update writes its own buffers), and gmax_m is read by the step's last k_reduce only.  The
+      // work then rides with that corner update (run_solve hands it on) instead of standing in front of the leaf chains.
+      // (a promise that run_solve follows at once - assemble_and_step - and takes the flag down again.  If the factorisation
+      //  refuses before its level-0 launch, this assembly's modelsum / diag_m / gmax_m and intrinsics block were never
+      //  written: that return ends msfm_ba_run with its error, and the next run assembles afresh.)
+      if (beside && will_solve && ba->env.solve_riders && ba->plan.n_levels > 0 && ba->nred > 0) {
+        ba->modelsum_rides = true;
+        ba->modelsum_args = ma;
+      } else {
+        hipLaunchKernelGGL(k_modelsum, dim3(nmb), dim3(beside ? 128 : 64), 0, s, ma);
+      }
     }
   }
   if (mode == 1) return MSFM_OK;
@@ -4419,16 +4384,31 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
   const int ncb = ba->ncb, nmb = ba->nmb, npb = ba->npb;
   const bool lead = ctx->rank == 0;
   const double* zsolved = ba->zsys.p;
+  const int nbu = cdiv(std::max(1, ba->nred), 256), nbp = npb ? ba->nblk_pt : 0;
+  const double wrep = lead ? 1.0 : 0.0;
+  msfm_chol_riders riders;
+  SolveEpilogue ep;
+  ba->rider_paths = 0;
   if (ba->nred > 0) {
     double* const zcur = ba->zsys.p + (size_t)ba->zflip * (ba->npad + 8);
     double* const znext = ba->zsys.p + (size_t)(ba->zflip ^ 1) * (ba->npad + 8);
+    if (ba->modelsum_rides) { riders.modelsum = &ba->modelsum_args; ba->rider_paths |= MSFM_PATH_RIDER_MODELSUM; }
+    ba->modelsum_rides = false;
+    // the camera / intrinsics part of the step inside the back substitution's launch, where k_backsub has the workgroups for
+    // the block sums (otherwise, or where the back substitution is a chain of launches: k_update_params below)
+    if (ba->env.solve_riders && nbp >= nbu) {
+      ep = SolveEpilogue{ba->col_param.p, ba->col_slot.p, 6 * ncb, ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->model.p, ba->cam_c.p, ba->model_c.p,
+                         ba->z.p, ba->upd_dx2.p, ba->upd_x2.p, ba->fail.p, wrep};
+      riders.epilogue = &ep;
+    }
     const int rc = msfm_chol_factor_solve(ctx, ba->env, ba->M.p, ba->npad, ba->nsys, ba->Linv.p, ba->w.p, zcur, ba->fail.p,
-                                          ba->plan.n_levels > 0 ? &ba->plan : nullptr, znext, ba->chol_ws, &ba->solve_paths);
+                                          ba->plan.n_levels > 0 ? &ba->plan : nullptr, znext, ba->chol_ws, &ba->solve_paths, &riders);
     if (rc != MSFM_OK) {
       // the call may have stopped before the solve kernel marked znext: neither half can be trusted to be "pending"
       // any more (a stale half would be taken for published values by the next solve) - mark both again
       (void)msfm_chol_fill_pending(ctx, ba->zsys.p, 2 * (ba->npad + 8));
       ba->m_zeroed = false;
+      ba->rider_paths = 0;   // (a rider handed over may not have run either: the run ends here, the next assembly starts afresh)
       return rc;
     }
     ba->zflip ^= 1;   // only a completed solve hands the other half over
@@ -4437,21 +4417,23 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
   int off = 0, moff = 0;   // partial2 = |dx|^2 partials, partial3 = |x|^2 partials (off of each), partial = model cost partials (moff)
   {
     KTimer t(ctx, "ba_backsub");
-    const int nbu = cdiv(std::max(1, ba->nred), 256), nbp = ba->nblk_pt;
-    const double wrep = lead ? 1.0 : 0.0;
+    const bool in_solve = riders.epilogue_ran;
+    if (in_solve) ba->rider_paths |= MSFM_PATH_RIDER_UPDATE;
     if (ba->nred > 0) {
-      hipLaunchKernelGGL(k_update_params, dim3(nbu), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo, zsolved,
-                         ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->cam_c.p, ba->model.p, ba->model_c.p, ba->z.p, ba->fail.p,
-                         ba->partial2.p + off, ba->partial3.p + off, wrep);
+      if (!in_solve)
+        hipLaunchKernelGGL(k_update_params, dim3(nbu), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo, zsolved,
+                           ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->cam_c.p, ba->model.p, ba->model_c.p, ba->z.p, ba->fail.p,
+                           ba->partial2.p + off, ba->partial3.p + off, wrep);
       off += nbu;
     }
     if (npb) {
       BackPtrs Q;
+      const UpdateSums U{in_solve ? nbu : 0, ba->nred, ba->upd_dx2.p, ba->upd_x2.p, ba->partial2.p, ba->partial3.p};   // (the places of k_update_params' sums: off was 0 there)
       Q.B = make_ptrs(ba, false, ba->lin_huber);
       Q.map = ba->map; Q.npb = npb; Q.ncb = ncb; Q.pt_first = ba->pt_first.p; Q.pb_pt = ba->pb_pt.p;
       Q.ptL = ba->ptL.p; Q.z = ba->z.p; Q.pt_c = ba->pt_c.p; Q.cm_Xc = ba->cm_Xc.p;
       Q.Nc = ba->Nc; Q.cam_c = ba->cam_c.p; Q.rot_c = ba->rot_c.p;
-      hipLaunchKernelGGL(k_backsub, dim3(nbp), dim3(256), 0, s, Q, ba->partial.p, ba->partial2.p + off, ba->partial3.p + off);
+      hipLaunchKernelGGL(k_backsub, dim3(nbp), dim3(256), 0, s, Q, ba->partial.p, ba->partial2.p + off, ba->partial3.p + off, U);
       off += nbp; moff += nbp;
     } else {
       hipLaunchKernelGGL(k_rot_cache, dim3(cdiv(std::max(1, ba->Nc), 256)), dim3(256), 0, s, ba->Nc, ba->cam_c.p, ba->rot_c.p);

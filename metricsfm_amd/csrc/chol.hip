@@ -11,6 +11,7 @@
 // into the same launch.  The back substitution L^T z = w runs block by block with explicitly
 // inverted diagonal blocks (k_trinv64_full) so each step is a mat-vec.
 #include "common.h"
+#include "solve_riders.h"
 #include <atomic>
 #include <algorithm>
 #include <cstdlib>
@@ -1357,18 +1358,47 @@ __host__ __device__ __forceinline__ int corner_splits(int panels, int target) {
   const int s = (panels + target - 1) / target;
   return s < 1 ? 1 : (s > MSFM_CORNER_SPLIT_MAX ? MSFM_CORNER_SPLIT_MAX : s);
 }
+// Rider (level 0 only, RIDER): the workgroups from n_own on are not the corner update's - workgroup n_own + mb does the
+// caller's per-intrinsics work for block mb (modelsum_body, solve_riders.h) with its first two waves.  It reads nothing the
+// update writes and stores into entries of M that the update does not read (columns from b0 on); the merge behind this
+// launch is the first to touch them.  In the shadow of the update's 45 us its eight dependent load rounds cost nothing.
+// The launches of the higher levels are the instantiation without a rider: they carry neither its 150 bytes of arguments nor
+// the branch.  (Config 3's level-1 launch measures 6.8 -> 7.4 us against the parent's with or without them: DESIGN.md 4.)
+struct NoRider {};
+template <bool RIDER> struct CornerRider { typedef NoRider type; };
+template <> struct CornerRider<true> { typedef ModelSumArgs type; };
+template <bool RIDER>
+__device__ __forceinline__ bool corner_rider(const typename CornerRider<RIDER>::type& rider, int n_own, double* sm) {
+  if constexpr (RIDER) {
+    if ((int)blockIdx.x < n_own) return false;
+    if ((int)threadIdx.x < (rider.fin.M ? 128 : 64))   // (the others leave before any barrier: the body's barrier is between its two waves)
+      modelsum_body(rider, (int)blockIdx.x - n_own, threadIdx.x, sm);
+    return true;
+  } else {
+    return false;
+  }
+}
+__device__ __forceinline__ void corner_single(const double* __restrict__ M, int ld, int b0, int target, double* __restrict__ corners, int ldc,
+                                              const CornerRanges& R, int I, int J, int r, double* sm);
+template <bool RIDER>
 __global__ __launch_bounds__(256) void k_corner_syrk(const double* __restrict__ M, int ld, int b0, int target, int smax,
-                                                      double* __restrict__ corners, int ldc, CornerRanges R) {
+                                                      double* __restrict__ corners, int ldc, CornerRanges R, int n_own,
+                                                      typename CornerRider<RIDER>::type rider) {
   __shared__ double sm[2 * 64 * LDT];
-  double* As = sm;
-  double* Bs = sm + 64 * LDT;
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4;
+  if (corner_rider<RIDER>(rider, n_own, sm)) return;
   const int tile = blockIdx.x / smax, r = blockIdx.x % smax;
   int I = (int)((sqrt(8.0 * tile + 1.0) - 1.0) * 0.5);
   while (I * (I + 1) / 2 > tile) I--;
   while ((I + 1) * (I + 2) / 2 <= tile) I++;
   const int J = tile - I * (I + 1) / 2;
+  corner_single(M, ld, b0, target, corners, ldc, R, I, J, r, sm);
+}
+__device__ __forceinline__ void corner_single(const double* __restrict__ M, int ld, int b0, int target, double* __restrict__ corners, int ldc,
+                                              const CornerRanges& R, int I, int J, int r, double* sm) {
+  double* As = sm;
+  double* Bs = sm + 64 * LDT;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wr = wave >> 1, wc = wave & 1, lr = lane & 15, lk = lane >> 4;
   const int ri = b0 + 64 * I, rj = b0 + 64 * J;
   const int p_begin = max((int)R.plo[I], (int)R.plo[J]), np = min((int)R.phi[I], (int)R.phi[J]);
   const int nsplit = corner_splits(np - p_begin, target);
@@ -1674,7 +1704,7 @@ struct BackTree {
 __global__ __launch_bounds__(256) void k_backsolve_chain(const double* __restrict__ M, int ld, int n, int nblk, BackTree tree,
                                                           const double* __restrict__ Ldiag, const double* __restrict__ Dinv,
                                                           double* __restrict__ z, unsigned long long* __restrict__ z_next,
-                                                          int* __restrict__ fail, unsigned spin_limit) {
+                                                          int* __restrict__ fail, unsigned spin_limit, SolveEpilogue E) {
   __shared__ double part[4][NB];
   __shared__ double zj[NB], wi[NB];
   __shared__ int rlo[5], rhi[5], nr;
@@ -1730,6 +1760,11 @@ __global__ __launch_bounds__(256) void k_backsolve_chain(const double* __restric
   // the own block's inverse while the first tile is in flight (and, for all but the last block, while z of the later
   // blocks is still being produced): what k_trinv64_full did in a launch of its own on the critical path
   trinv64_block(Ldiag, Dinv, i, n, Lb, Vb, Tb);
+  // the caller's epilogue (E.col_param set): a workgroup that has a later block to wait for fetches its columns' inputs now;
+  // the one that starts the chain must not spend a load round in front of its publication and fetches behind it
+  const bool ep = E.col_param != nullptr && tid < NB, ep_early = j >= 0;
+  EpilogueColumn ec = {-1, 0, 0.0, 0.0};
+  if (ep && ep_early) ec = solve_epilogue_fetch(E, i0 + tid);
   while (j >= 0) {
     const int jc = j;
     advance();
@@ -1768,6 +1803,11 @@ __global__ __launch_bounds__(256) void k_backsolve_chain(const double* __restric
     unsigned long long bits = (unsigned long long)__double_as_longlong(zz);
     if (bits == MSFM_Z_PENDING) bits = 0x7FF8000000000000ull;   // (cannot come out of arithmetic; keep the protocol safe anyway)
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(z) + (size_t)i0 + tid, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the caller's use of the block's values, behind the publication: nobody in this launch waits for it
+    if (ep) {
+      if (!ep_early) ec = solve_epilogue_fetch(E, i0 + tid);
+      solve_epilogue_finish(E, ec, __longlong_as_double((long long)bits));
+    }
   }
 }
 
@@ -2053,8 +2093,11 @@ static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int n
 // state - the two buffers alternate from solve to solve and no fill launch sits on the critical path.  Without it the
 // function fills z itself first.
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
-                           const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws, int* paths) {
+                           const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws, int* paths, msfm_chol_riders* riders) {
   if (paths) *paths = 0;   // (a call that fails reports no path)
+  if (riders) riders->epilogue_ran = false;
+  if (riders && riders->modelsum && !(plan && plan->n_levels > 0))
+    return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: the model-sum rider needs an elimination tree");
   if (!M || !work || !w || !z || !fail || npad % NB != 0 || n < 1 || n + 1 > npad)
     return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad workspace (null buffer or size)");
   hipStream_t s = ctx->stream;
@@ -2149,6 +2192,11 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
         chain_timer.count++;
       }
       chain_timer.stop();
+      // the caller's rider goes with the level-0 corner update on either path above (a level without panels has no update: the
+      // launch then holds the rider's workgroups alone)
+      ModelSumArgs rider;
+      memset(&rider, 0, sizeof rider);
+      if (lv == 0 && riders && riders->modelsum) rider = *riders->modelsum;
       if (maxp > 0) {
         KTimer t(ctx, "chol_corner_syrk");
         t.count = 2;
@@ -2159,8 +2207,18 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
         corner_plan(plan, lv, nrows, CP);
         const CornerRanges& R = CP.R;
         const int target = CP.target, smax = CP.smax;
-        hipLaunchKernelGGL(k_corner_syrk, dim3(ntile * smax), dim3(256), 0, s, M, npad, sb, target, smax, plan->corners, ldc, R);
+        if (rider.nmb > 0) {
+          hipLaunchKernelGGL(k_corner_syrk<true>, dim3(ntile * smax + rider.nmb), dim3(256), 0, s, M, npad, sb, target, smax, plan->corners, ldc, R,
+                             ntile * smax, rider);
+        } else {
+          hipLaunchKernelGGL(k_corner_syrk<false>, dim3(ntile * smax), dim3(256), 0, s, M, npad, sb, target, smax, plan->corners, ldc, R,
+                             ntile * smax, NoRider());
+        }
         hipLaunchKernelGGL(k_merge_corners, dim3(4 * ntile), dim3(256), 0, s, M, npad, sb, nB64, plan->corners, ldc, target, R);
+      } else if (rider.nmb > 0) {
+        CornerRanges R;
+        memset(&R, 0, sizeof R);
+        hipLaunchKernelGGL(k_corner_syrk<true>, dim3(rider.nmb), dim3(256), 0, s, M, npad, sb, 1, 1, plan->corners, ldc, R, 0, rider);
       }
       t_first = sb;
     }
@@ -2217,8 +2275,11 @@ int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int np
           bt.level[lv].node[k].leaf_lo = nd.leaf_lo; bt.level[lv].node[k].leaf_hi = nd.leaf_hi;
         }
       }
+      SolveEpilogue ep;
+      memset(&ep, 0, sizeof ep);
+      if (riders && riders->epilogue) { ep = *riders->epilogue; riders->epilogue_ran = true; }
       hipLaunchKernelGGL(k_backsolve_chain, dim3(nblk), dim3(256), 0, s, M, npad, n, nblk, bt, Ldiag, Dinv, z,
-                         reinterpret_cast<unsigned long long*>(z_next), fail, chain_spin_limit());
+                         reinterpret_cast<unsigned long long*>(z_next), fail, chain_spin_limit(), ep);
     } else if (z_next) {
       MSFM_TRY(msfm_chol_fill_pending(ctx, z_next, npad));   // keep the caller's alternation intact on the launch-chain path
     }

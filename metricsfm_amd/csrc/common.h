@@ -35,6 +35,7 @@ struct msfm_env {
   long lanes4_min = -1;           // MSFM_LANES4_MIN: eliminated points above which those of up to 4 rows get 4 lanes (ptmap_use_lanes4; -1: default)
   bool asm_beside = true;         // MSFM_ASM_BESIDE=0: the Schur fold partials summed after the per-camera sums (k_asm_all), not beside them
   bool spec = true;               // MSFM_SPEC=0: the next linearisation enqueued only after the step's read-back
+  bool solve_riders = true;      // MSFM_SOLVE_RIDERS=0: k_modelsum and k_update_params as launches of their own, not inside the factor-and-solve's
   // process-wide
   size_t pool_bytes = (size_t)16384 << 20;   // MSFM_POOL_MB: freed device blocks the cache keeps
   bool pool_debug = false;        // MSFM_POOL_DEBUG (set): a free that disagrees with the pool's record aborts
@@ -557,6 +558,19 @@ int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out);
 void msfm_chol_ws_destroy(msfm_chol_ws* ws);
 // env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE); paths (optional): the
 // MSFM_PATH_* bits of msfm_ba_layout.solve_paths for the launches this call enqueued
+// riders (optional): work of the caller's that the call's launches take along (solve_riders.h).
+//   modelsum  run by extra workgroups of the level-0 corner update, in front of that level's merge; the caller gives it only
+//             with a plan of at least one level, and a call that returns MSFM_OK has launched it.
+//   epilogue  run by k_backsolve_chain behind the publication of every block; `epilogue_ran` says whether the back
+//             substitution took that form - if not, the caller does the work itself.
+struct ModelSumArgs;
+struct SolveEpilogue;
+struct msfm_chol_riders {
+  const ModelSumArgs* modelsum = nullptr;
+  const SolveEpilogue* epilogue = nullptr;
+  bool epilogue_ran = false;
+};
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
-                           const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr, int* paths = nullptr);
+                           const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr, int* paths = nullptr,
+                           msfm_chol_riders* riders = nullptr);
 int msfm_chol_fill_pending(msfm_ctx* ctx, double* z, int npad);   // "not solved yet" marks of k_backsolve_chain

@@ -25,6 +25,7 @@ msfm_env msfm_env_read() {
   if (const char* e = get("MSFM_LANES4_MIN")) E.lanes4_min = atol(e);
   E.asm_beside = num("MSFM_ASM_BESIDE", 1) != 0;
   E.spec = num("MSFM_SPEC", 1) != 0;
+  E.solve_riders = num("MSFM_SOLVE_RIDERS", 1) != 0;
   if (const char* e = get("MSFM_POOL_MB")) E.pool_bytes = (size_t)atol(e) << 20;
   E.pool_debug = get("MSFM_POOL_DEBUG") != nullptr;
   E.host_threads = std::max(1, std::min(num("MSFM_HOST_THREADS", std::min(8, (int)std::thread::hardware_concurrency())), 64));
