@@ -26,6 +26,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "ba_device.h"
+#include "ba_partials.h"
 #include "common.h"
 #include "solve_riders.h"
 
@@ -1779,25 +1780,33 @@ struct PairJobs {
 };
 
 struct msfm_ba {
+  // ---- structure of the problem: fixed by msfm_ba_create ----
   msfm_ctx* ctx = nullptr;
+  msfm_env env;   // the switches as they were at msfm_ba_create (common.h)
+  int world_at_create = 1;
+  double setup_ms = 0;
   int Nc = 0, Nm = 0, Np = 0;
   int ncb = 0, nmb = 0, npb = 0, nred = 0, npad = 0;
-  PtMap map = {0, 0, 0, 0, 0, 0, 0};
-  int n_short4 = 0;   // points of up to 4 rows (the Q class, or the front of S where the problem is too small for it: ptmap_use_lanes4)   // the eliminated points by track length class, and their workgroups
+  PtMap map = {0, 0, 0, 0, 0, 0, 0};   // the eliminated points by track length class, and their workgroups
+  int n_short4 = 0;   // points of up to 4 rows (the Q class, or the front of S where the problem is too small for it: ptmap_use_lanes4)
   // solver layout of the reduced system: camera block cb at column cb_off[cb], intrinsics at mo + 3 mb, order nsys
   int nsys = 0, mo = 0, n_padcol = 0;
-  msfm_env env;   // the switches as they were at msfm_ba_create (common.h)
   msfm_chol_plan plan;
-  msfm_chol_ws* chol_ws = nullptr;   // hand-off state of the persistent panel chain (chol.hip)
-  DevBuf<int> cb_off, padcol;
-  DevBuf<double> zsys, corners;
-  int zflip = 0;   // which half of zsys the next solve writes (the other half is being marked "pending" meanwhile)
-  int solve_paths = 0;   // MSFM_PATH_* of the last factorisation (msfm_ba_layout.solve_paths)
   int A = 0, AE = 0, NCR = 0, NPM = 0;
   bool has_gps = false;
   double gps_weight = 0;
   int n_residuals = 0;
   std::vector<int> h_cb_cam, h_mb_model, h_pb_pt;
+  int n_fchunks = 0;   // ftf jobs
+  int nblk_obs = 0, nblk_pt = 0;   // launch geometry: workgroups over all rows / of the point kernels
+  BaPartials parts;    // layout of partial_x, partial, partial2 / partial3, partial4, gmax_buf and their reduce counts (ba_partials.h)
+  int n_ublk = 0;      // multi-rank: camera-camera blocks present on ANY rank, packed for the per-iteration sum (u_row, u_col, pack)
+  bool spec_on = true;       // MSFM_SPEC=0: the next linearisation is enqueued only after the host has seen the step
+  double* swrite = nullptr;  // where the kernels put scalars: scal (one rank) or sloc (partials, summed by reduce_scalars)
+  // ---- device buffers (and the pinned host words the device writes) ----
+  msfm_chol_ws* chol_ws = nullptr;   // hand-off state of the persistent panel chain (chol.hip)
+  DevBuf<int> cb_off, padcol;
+  DevBuf<double> zsys, corners;
   DevBuf<double> cam, model, pt, cam_c, model_c, pt_c;
   DevBuf<int> cb_cam, mb_model, pb_pt, cb_mb;
   DevBuf<int> o_cam, o_model, o_pt, o_cb, o_mb, o_pb, o_cpos, o_pm;
@@ -1811,8 +1820,6 @@ struct msfm_ba {
   DevBuf<double> scale_c, scale_m, scale_p, diag_c, diag_m, diag_p;
   DevBuf<int> pt_first, pm_first, pm_mb;
   DevBuf<double> ptL, ptg;
-  // ftf jobs
-  int n_fchunks = 0;
   DevBuf<int> f_start, f_end, cam_chunk_first;
   DevBuf<double> f_partial, camftf, modelsum;
   DevBuf<int> mcam_first, mcam;
@@ -1821,34 +1828,23 @@ struct msfm_ba {
   DevBuf<double> M, Linv, w, z;
   DevBuf<double> gps, g_r, g_J;
   DevBuf<double> partial, partial2, partial3, partial4, gmax_buf, scal, sloc;
-  DevBuf<double> partial_x;   // cost partials at x (k_point, the rows of frozen points, the GPS rows): alive until the step's last k_reduce
-  bool m_zeroed = false;      // M is zeroed for the next assembly (k_tail, behind a completed solve); cleared by every assembly
-  int asm_paths = 0;          // MSFM_PATH_ASM_BESIDE of the last assembly (msfm_ba_layout.assemble_paths)
+  DevBuf<double> partial_x;   // cost partials at x (BaPartials): alive until the step's last k_reduce
   // the riders of the factor-and-solve (solve_riders.h; MSFM_SOLVE_RIDERS=0: none)
-  bool modelsum_rides = false;   // the last assembly left its k_modelsum to the solve that follows it: run_solve hands modelsum_args on
-  ModelSumArgs modelsum_args;
   DevBuf<int> col_param, col_slot;   // SolveEpilogue: by column of the system (k_col_map)
   DevBuf<double> upd_dx2, upd_x2;    // squares of the camera / intrinsics step per scalar
-  int rider_paths = 0;           // MSFM_PATH_RIDER_* of the last solve (msfm_ba_layout.rider_paths)
-  int n_defer = 0;            // jobs of the assembly's k_reduce that the step's last k_reduce takes over (run_solve)
-  struct { const double* p; int n; int slot; int is_max; } defer[2];
-  double* swrite = nullptr;  // where the kernels put scalars: scal (one rank) or sloc (partials, summed by reduce_scalars)
   DevBuf<int> fail;
   double* h_scal = nullptr;  // pinned, mapped: [0, 16) scalars, [16] sequence number, [17] decision code, [18] radius (k_publish_scalars)
   DevBuf<double> spec;       // {go, radius} of the device-side decision, read by the launches enqueued ahead of the host (PointPtrs::spec)
-  bool spec_on = true;       // MSFM_SPEC=0: the next linearisation is enqueued only after the host has seen the step
   double* h_scal_dev = nullptr;
-  unsigned long long scal_seq = 0;
   int* h_fail = nullptr;
-  int nblk_obs = 0, nblk_pt = 0;
-  bool lin_pending = false;   // enqueue_linearize_rest was called: the next k_point linearises, writes the camera rows and the cost
-  double lin_huber = 1.0;
-  double setup_ms = 0;
-  int world_at_create = 1;
-  // multi-rank: camera-camera blocks present on ANY rank, packed for the per-iteration sum
-  int n_ublk = 0;
   DevBuf<int> u_row, u_col;
   DevBuf<double> pack;
+  // ---- what persists between runs (the state of one msfm_ba_run is its own: BaRunState) ----
+  int zflip = 0;   // which half of zsys the next solve writes (the other half is being marked "pending" meanwhile)
+  unsigned long long scal_seq = 0;
+  int solve_paths = 0;   // MSFM_PATH_* of the last factorisation (msfm_ba_layout.solve_paths)
+  int asm_paths = 0;     // MSFM_PATH_ASM_BESIDE of the last assembly (msfm_ba_layout.assemble_paths)
+  int rider_paths = 0;   // MSFM_PATH_RIDER_* of the last solve (msfm_ba_layout.rider_paths)
 };
 
 // --------------------------------------------------------------------------------------
@@ -3174,6 +3170,100 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   return MSFM_OK;
 }
 
+// ---- the host steps of msfm_ba_create that do not depend on how the bulk structures are built (O(cameras)) ----
+// A 0/1 matrix max-reduced over the ranks, in place: each rank marks what its shard of the points couples, and the camera graph
+// and the block structure must be the same on every rank.  (the hook sums doubles; bounded wait: a peer that failed never joins)
+template <class Byte>
+static int allreduce_max_01(msfm_ctx* ctx, std::vector<Byte>& m, const char* what) {
+  hipStream_t s = ctx->stream;
+  std::vector<double> md(m.size());
+  for (size_t k = 0; k < md.size(); k++) md[k] = m[k] ? 1.0 : 0.0;
+  DevBuf<double> d;
+  DevScope blk(ctx);
+  HIP_TRY(ctx, d.from(md, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));
+  const int rc = ctx->allreduce(ctx->allreduce_user, d.p, md.size(), MSFM_REDUCE_MAX, (void*)s);
+  if (rc != 0) return msfm_set_error(ctx, MSFM_E_DEVICE, "all-reduce hook failed: %d", rc);
+  HIP_TRY(ctx, hipMemcpyAsync(md.data(), d.p, sizeof(double) * md.size(), hipMemcpyDeviceToHost, s));
+  MSFM_TRY(msfm_stream_wait_bounded(ctx, s, what));
+  blk.dismiss();   // (behind the bounded wait)
+  for (size_t k = 0; k < md.size(); k++) m[k] = md[k] != 0.0;
+  return MSFM_OK;
+}
+
+// Which camera and intrinsics blocks exist besides those some residual uses (cu, mu: the usage flags), the slots of the
+// intrinsics blocks, and the nodes of the camera graph (gnode: camera -> node or -1, gcam: node -> camera).
+static void block_slots_and_nodes(const msfm_ctx* ctx, const msfm_ba_problem* P, msfm_ba* ba, std::vector<uint8_t>& cu, std::vector<uint8_t>& mu,
+                                  std::vector<int>& model_slot, std::vector<int>& gnode, std::vector<int>& gcam) {
+  const int Nc = P->n_cams, Nm = P->n_models;
+  if (P->gps_xyz) for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) cu[c] = 1;
+  if (ctx->world > 1) {
+    // points are sharded over ranks: the block structure of the reduced system must be the same
+    // everywhere, so every mutable camera / intrinsics block gets a slot whether or not this
+    // rank's shard observes it
+    for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) { cu[c] = 1; if (is_mut(P->model_mutable, P->cam_model_of_cam[c])) mu[P->cam_model_of_cam[c]] = 1; }
+  }
+  for (int m = 0; m < Nm; m++) if (mu[m]) { model_slot[m] = ba->nmb++; ba->h_mb_model.push_back(m); }
+  for (int c = 0; c < Nc; c++) if (cu[c]) { gnode[c] = (int)gcam.size(); gcam.push_back(c); }
+}
+
+// Behind order_camera_blocks: the order and padded size of the reduced system, the corner buffers of the elimination tree, and
+// the lists by camera block - its intrinsics block, the cameras of each intrinsics block, its GPS position.
+static int finish_camera_blocks(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_ba* ba, const std::vector<int>& model_slot, std::vector<int>& cb_mb) {
+  hipStream_t s = ctx->stream;
+  const int ncb = ba->ncb, nmb = ba->nmb;
+  ba->nred = 6 * ncb + 3 * nmb;
+  ba->npad = 64 * cdiv(ba->nsys + 1, 64);
+  if (ba->plan.n_levels > 0) {
+    ba->plan.ldc = 64 * cdiv(ba->nsys + 1 - ba->plan.level[0].b0, 64);
+    HIP_TRY(ctx, ba->corners.alloc((size_t)8 * ba->plan.ldc * ba->plan.ldc));   // up to eight K-splits of the corner update (MSFM_CORNER_SPLIT_MAX)
+    ba->plan.corners = ba->corners.p;
+  }
+  ba->has_gps = P->gps_xyz != nullptr;
+  ba->gps_weight = P->gps_weight;
+  std::vector<int> mcam_first(nmb + 1, 0), mcam;
+  cb_mb.assign(std::max(1, ncb), -1);
+  for (int cb = 0; cb < ncb; cb++) {
+    const int m = P->cam_model_of_cam[ba->h_cb_cam[cb]];
+    cb_mb[cb] = is_mut(P->model_mutable, m) ? model_slot[m] : -1;
+  }
+  for (int mb = 0; mb < nmb; mb++) {
+    mcam_first[mb] = (int)mcam.size();
+    for (int cb = 0; cb < ncb; cb++) if (cb_mb[cb] == mb) mcam.push_back(cb);
+  }
+  mcam_first[nmb] = (int)mcam.size();
+  HIP_TRY(ctx, ba->cb_cam.from(ba->h_cb_cam.empty() ? std::vector<int>(1, 0) : ba->h_cb_cam, s));
+  HIP_TRY(ctx, ba->mb_model.from(ba->h_mb_model.empty() ? std::vector<int>(1, 0) : ba->h_mb_model, s));
+  HIP_TRY(ctx, ba->cb_mb.from(cb_mb, s)); HIP_TRY(ctx, ba->mcam_first.from(mcam_first, s));
+  if (!mcam.empty()) HIP_TRY(ctx, ba->mcam.from(mcam, s));
+  if (ba->has_gps) {
+    std::vector<double> gps_cb(3 * (size_t)std::max(1, ncb));
+    for (int cb = 0; cb < ncb; cb++) for (int k = 0; k < 3; k++) gps_cb[3 * (size_t)cb + k] = P->gps_xyz[3 * (size_t)ba->h_cb_cam[cb] + k];
+    HIP_TRY(ctx, ba->gps.from(gps_cb, s));
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the host lists go out of scope)
+  return MSFM_OK;
+}
+
+// The chunks of k_ftf: the camera-major rows of a camera block (cam_first: its first row), cut into pieces of the chunk size.
+static int build_ftf_chunks(msfm_ctx* ctx, msfm_ba* ba, const std::vector<int>& cam_first) {
+  hipStream_t s = ctx->stream;
+  const int ncb = ba->ncb;
+  std::vector<int> f_start, f_end, cam_chunk_first(ncb + 1, 0);
+  const int fchunk = chunk_for(cam_first[ncb], FTF_CHUNK);
+  for (int c = 0; c < ncb; c++) {
+    cam_chunk_first[c] = (int)f_start.size();
+    for (int e = cam_first[c]; e < cam_first[c + 1]; e += fchunk) { f_start.push_back(e); f_end.push_back(std::min(e + fchunk, cam_first[c + 1])); }
+  }
+  cam_chunk_first[ncb] = (int)f_start.size();
+  ba->n_fchunks = (int)f_start.size();
+  HIP_TRY(ctx, ba->f_start.from(f_start.empty() ? std::vector<int>(1, 0) : f_start, s));
+  HIP_TRY(ctx, ba->f_end.from(f_end.empty() ? std::vector<int>(1, 0) : f_end, s));
+  HIP_TRY(ctx, ba->cam_chunk_first.from(cam_chunk_first, s));
+  HIP_TRY(ctx, hipStreamSynchronize(s));   // (the host vectors go out of scope)
+  return MSFM_OK;
+}
+
 // Everything msfm_ba_create needs between the caller's arrays and the allocation of the work buffers, on the device.
 static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_ba* ba, const std::function<void(const char*)>& lap,
                                     bool bulk_on_device) {
@@ -3222,20 +3312,14 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   if (err[1] < 0x7f7f7f7f) return msfm_set_error(ctx, MSFM_E_INVAL, "obs_pt must be non-decreasing (gather order, optimizer.cc:62)");
   lap("uploaded + scanned");
   // ---- slots of the camera / intrinsics blocks (host: O(cameras)) ----
-  if (P->gps_xyz) for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) cu[c] = 1;
-  if (ctx->world > 1)
-    for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) { cu[c] = 1; if (is_mut(P->model_mutable, P->cam_model_of_cam[c])) mu[P->cam_model_of_cam[c]] = 1; }
-  std::vector<int> cam_slot(Nc, -1), model_slot(Nm, -1);
-  for (int m = 0; m < Nm; m++) if (mu[m]) { model_slot[m] = ba->nmb++; ba->h_mb_model.push_back(m); }
-  std::vector<int> gnode(Nc, -1), gcam;
-  for (int c = 0; c < Nc; c++) if (cu[c]) { gnode[c] = (int)gcam.size(); gcam.push_back(c); }
+  std::vector<int> cam_slot(Nc, -1), model_slot(Nm, -1), gnode(Nc, -1), gcam;
+  block_slots_and_nodes(ctx, P, ba, cu, mu, model_slot, gnode, gcam);
   const int ng = (int)gcam.size();
   const int force = ba->env.chol_domains;
   std::vector<uint8_t> adjb;
   if (ng >= 128 && ng <= 4096 && force != 0) {
     DevBuf<int> d_gnode;
     DevBuf<uint8_t> d_adj;
-    DevBuf<double> dadj;
     DevScope blk(ctx);
     DTRY(d_gnode.from(gnode, s));
     DTRY(d_adj.alloc((size_t)ng * ng));
@@ -3244,55 +3328,17 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     adjb.resize((size_t)ng * ng);
     DTRY(hipMemcpyAsync(adjb.data(), d_adj.p, adjb.size(), hipMemcpyDeviceToHost, s));
     DTRY(hipStreamSynchronize(s));
-    if (ctx->world > 1) {   // the graph must be the same on every rank: max-reduce over the ranks' shards
-      std::vector<double> adjm(adjb.size());
-      for (size_t k = 0; k < adjm.size(); k++) adjm[k] = adjb[k] ? 1.0 : 0.0;
-      DTRY(dadj.from(adjm, s));
-      DTRY(hipStreamSynchronize(s));
-      const int rc = ctx->allreduce(ctx->allreduce_user, dadj.p, adjm.size(), MSFM_REDUCE_MAX, (void*)s);
-      if (rc != 0) return msfm_set_error(ctx, MSFM_E_DEVICE, "all-reduce hook failed: %d", rc);
-      DTRY(hipMemcpyAsync(adjm.data(), dadj.p, sizeof(double) * adjm.size(), hipMemcpyDeviceToHost, s));
-      MSFM_TRY(msfm_stream_wait_bounded(ctx, s, "the all-reduce of the camera graph"));   // (bounded: a peer that failed never joins)
-      for (size_t k = 0; k < adjm.size(); k++) adjb[k] = adjm[k] != 0.0;
-    }
+    // the graph must be the same on every rank: max-reduce over the ranks' shards
+    if (ctx->world > 1) MSFM_TRY(allreduce_max_01(ctx, adjb, "the all-reduce of the camera graph"));
     blk.dismiss();   // (behind the wait for the graph, or the bounded one)
   }
-  std::vector<int> cb_off_h, padcol_h;
+  std::vector<int> cb_off_h, padcol_h, cb_mb;
   order_camera_blocks(ctx, ba, gcam, adjb, force, cam_slot, cb_off_h, padcol_h);
-  const int ncb = ba->ncb, nmb = ba->nmb;
-  ba->nred = 6 * ncb + 3 * nmb;
-  ba->npad = 64 * cdiv(ba->nsys + 1, 64);
-  if (ba->plan.n_levels > 0) {
-    ba->plan.ldc = 64 * cdiv(ba->nsys + 1 - ba->plan.level[0].b0, 64);
-    DTRY(ba->corners.alloc((size_t)8 * ba->plan.ldc * ba->plan.ldc));   // up to eight K-splits of the corner update (MSFM_CORNER_SPLIT_MAX)
-    ba->plan.corners = ba->corners.p;
-  }
-  ba->gps_weight = P->gps_weight;
+  MSFM_TRY(finish_camera_blocks(ctx, P, ba, model_slot, cb_mb));
+  const int ncb = ba->ncb;
   DTRY(ba->cb_off.from(cb_off_h.empty() ? std::vector<int>(1, 0) : cb_off_h, s));
   DTRY(ba->padcol.from(padcol_h.empty() ? std::vector<int>(1, 0) : padcol_h, s));
   DTRY(d_cam_slot.from(cam_slot, s)); DTRY(d_model_slot.from(model_slot, s));
-  // cameras of each intrinsics block (host, O(cameras))
-  std::vector<int> cb_mb(std::max(1, ncb), -1), mcam_first(nmb + 1, 0), mcam;
-  for (int cb = 0; cb < ncb; cb++) {
-    const int m = P->cam_model_of_cam[ba->h_cb_cam[cb]];
-    cb_mb[cb] = is_mut(P->model_mutable, m) ? model_slot[m] : -1;
-  }
-  for (int mb = 0; mb < nmb; mb++) {
-    mcam_first[mb] = (int)mcam.size();
-    for (int cb = 0; cb < ncb; cb++) if (cb_mb[cb] == mb) mcam.push_back(cb);
-  }
-  mcam_first[nmb] = (int)mcam.size();
-  DTRY(ba->cb_cam.from(ba->h_cb_cam.empty() ? std::vector<int>(1, 0) : ba->h_cb_cam, s));
-  DTRY(ba->mb_model.from(ba->h_mb_model.empty() ? std::vector<int>(1, 0) : ba->h_mb_model, s));
-  DTRY(ba->cb_mb.from(cb_mb, s)); DTRY(ba->mcam_first.from(mcam_first, s));
-  if (!mcam.empty()) DTRY(ba->mcam.from(mcam, s));
-  std::vector<double> gps_cb;
-  ba->has_gps = P->gps_xyz != nullptr;
-  if (ba->has_gps) {
-    gps_cb.resize(3 * (size_t)std::max(1, ncb));
-    for (int cb = 0; cb < ncb; cb++) for (int k = 0; k < 3; k++) gps_cb[3 * (size_t)cb + k] = P->gps_xyz[3 * (size_t)ba->h_cb_cam[cb] + k];
-    DTRY(ba->gps.from(gps_cb, s));
-  }
   lap("camera order");
   // ---- order of the eliminated points: by length class (PtMap), then by their smallest camera blocks, ties by the caller's
   // index (two stable sorts, the minor key first) ----
@@ -3387,18 +3433,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
   if (npb && NPM) hipLaunchKernelGGL(k_pm_entries, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ba->pt_first.p, ba->o_mb.p, 1, d_pm_count.p, ba->pm_first.p,
                                      ba->pm_mb.p, ba->o_pm.p, d_err.p);
   // ---- FTF chunks (host: O(cameras + rows / 1024)) ----
-  std::vector<int> f_start, f_end, cam_chunk_first(ncb + 1, 0);
-  const int fchunk = chunk_for(cam_first[ncb], FTF_CHUNK);
-  for (int c = 0; c < ncb; c++) {
-    cam_chunk_first[c] = (int)f_start.size();
-    for (int e = cam_first[c]; e < cam_first[c + 1]; e += fchunk) { f_start.push_back(e); f_end.push_back(std::min(e + fchunk, cam_first[c + 1])); }
-  }
-  cam_chunk_first[ncb] = (int)f_start.size();
-  ba->n_fchunks = (int)f_start.size();
-  DTRY(ba->f_start.from(f_start.empty() ? std::vector<int>(1, 0) : f_start, s));
-  DTRY(ba->f_end.from(f_end.empty() ? std::vector<int>(1, 0) : f_end, s));
-  DTRY(ba->cam_chunk_first.from(cam_chunk_first, s));
-  DTRY(hipStreamSynchronize(s));
+  MSFM_TRY(build_ftf_chunks(ctx, ba, cam_first));
   lap("entries + chunks");
   // ---- block-pair lists ----
   const bool want_blocks = ctx->world > 1;
@@ -3446,7 +3481,8 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
   std::vector<int> cam_slot(Nc, -1), model_slot(Nm, -1), pt_slot(Np, -1);
   std::vector<int>& run_first = H.run_first;
   {
-    std::vector<char> cu(Nc, 0), mu(Nm, 0), pu(Np, 0);
+    std::vector<uint8_t> cu(Nc, 0), mu(Nm, 0);
+    std::vector<char> pu(Np, 0);
     par_ranges((size_t)No, host_threads(), [&](int, size_t o0, size_t o1) {   // all stores write 1: relaxed byte stores
       for (size_t o = o0; o < o1; o++) {
         const int c = P->obs_cam[o], p = P->obs_pt[o], m = P->cam_model_of_cam[c];
@@ -3454,8 +3490,8 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
         if (!cm && !pm) continue;
         if (pm && !pu[p]) __atomic_store_n(&pu[p], (char)1, __ATOMIC_RELAXED);
         if (cm) {
-          if (!cu[c]) __atomic_store_n(&cu[c], (char)1, __ATOMIC_RELAXED);
-          if (is_mut(P->model_mutable, m) && !mu[m]) __atomic_store_n(&mu[m], (char)1, __ATOMIC_RELAXED);
+          if (!cu[c]) __atomic_store_n(&cu[c], (uint8_t)1, __ATOMIC_RELAXED);
+          if (is_mut(P->model_mutable, m) && !mu[m]) __atomic_store_n(&mu[m], (uint8_t)1, __ATOMIC_RELAXED);
         }
       }
     });
@@ -3463,18 +3499,10 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
     run_first.assign(Np + 1, 0);
     for (int o = 0; o < No; o++) run_first[P->obs_pt[o] + 1]++;
     for (int p = 0; p < Np; p++) run_first[p + 1] += run_first[p];
-    if (P->gps_xyz) for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) cu[c] = 1;
-    if (ctx->world > 1) {
-      // points are sharded over ranks: the block structure of the reduced system must be the same
-      // everywhere, so every mutable camera / intrinsics block gets a slot whether or not this
-      // rank's shard observes it
-      for (int c = 0; c < Nc; c++) if (is_mut(P->cam_mutable, c)) { cu[c] = 1; if (is_mut(P->model_mutable, P->cam_model_of_cam[c])) mu[P->cam_model_of_cam[c]] = 1; }
-    }
-    for (int m = 0; m < Nm; m++) if (mu[m]) { model_slot[m] = ba->nmb++; ba->h_mb_model.push_back(m); }
     for (int p = 0; p < Np; p++) if (pu[p]) ba->h_pb_pt.push_back(p);  // slots are assigned below, once the camera order is known
     // ---- elimination order of the camera blocks (see partition_cameras) ----
     std::vector<int> gnode(Nc, -1), gcam;
-    for (int c = 0; c < Nc; c++) if (cu[c]) { gnode[c] = (int)gcam.size(); gcam.push_back(c); }
+    block_slots_and_nodes(ctx, P, ba, cu, mu, model_slot, gnode, gcam);
     const int ng = (int)gcam.size();
     const int force = ba->env.chol_domains;  // 0: dense order, 1..3: force that bisection depth
     std::vector<uint8_t> adjb8;
@@ -3491,20 +3519,7 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
           for (int a : run) for (int b : run) if (a != b && !adjb[(size_t)a * ng + b]) __atomic_store_n(&adjb[(size_t)a * ng + b], (char)1, __ATOMIC_RELAXED);
         }
       });
-      if (ctx->world > 1) {
-        std::vector<double> adjm((size_t)ng * ng);
-        for (size_t k = 0; k < adjm.size(); k++) adjm[k] = adjb[k] ? 1.0 : 0.0;
-        DevBuf<double> dadj;
-        DevScope blk(ctx);
-        HIP_TRY(ctx, dadj.from(adjm, s));
-        HIP_TRY(ctx, hipStreamSynchronize(s));
-        const int rc = ctx->allreduce(ctx->allreduce_user, dadj.p, adjm.size(), MSFM_REDUCE_MAX, (void*)s);
-        if (rc != 0) return msfm_set_error(ctx, MSFM_E_DEVICE, "all-reduce hook failed: %d", rc);
-        HIP_TRY(ctx, hipMemcpyAsync(adjm.data(), dadj.p, sizeof(double) * adjm.size(), hipMemcpyDeviceToHost, s));
-        MSFM_TRY(msfm_stream_wait_bounded(ctx, s, "the all-reduce of the camera graph"));
-        blk.dismiss();
-        for (size_t k = 0; k < adjm.size(); k++) adjb[k] = adjm[k] != 0.0;
-      }
+      if (ctx->world > 1) MSFM_TRY(allreduce_max_01(ctx, adjb, "the all-reduce of the camera graph"));
       adjb8.assign(adjb.begin(), adjb.end());
     }
     std::vector<int> cb_off_h, padcol_h;
@@ -3567,15 +3582,8 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
     HIP_TRY(ctx, hipStreamSynchronize(s));
   }
   const int ncb = ba->ncb, nmb = ba->nmb, npb = ba->npb;
-  ba->nred = 6 * ncb + 3 * nmb;
-  ba->npad = 64 * cdiv(ba->nsys + 1, 64);
-  if (ba->plan.n_levels > 0) {
-    ba->plan.ldc = 64 * cdiv(ba->nsys + 1 - ba->plan.level[0].b0, 64);
-    HIP_TRY(ctx, ba->corners.alloc((size_t)8 * ba->plan.ldc * ba->plan.ldc));   // up to eight K-splits of the corner update (MSFM_CORNER_SPLIT_MAX)
-    ba->plan.corners = ba->corners.p;
-  }
-  ba->has_gps = P->gps_xyz != nullptr;
-  ba->gps_weight = P->gps_weight;
+  std::vector<int> cb_mb;
+  MSFM_TRY(finish_camera_blocks(ctx, P, ba, model_slot, cb_mb));
   lap("blocks + orders");
   // ---- active observations: eliminated-point rows first (point-major), then the rest ----
   // Every observation of an eliminated point is active (its point block is free), so row i of point block pb is
@@ -3707,25 +3715,7 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
   const int NPM = ba->NPM = (int)pm_mb.size();
   lap("positions + pm entries");
   // ---- FTF chunks (camera-major rows) ----
-  std::vector<int> f_start, f_end, cam_chunk_first(ncb + 1, 0);
-  const int fchunk = chunk_for(cam_first[ncb], FTF_CHUNK);
-  for (int c = 0; c < ncb; c++) {
-    cam_chunk_first[c] = (int)f_start.size();
-    for (int e = cam_first[c]; e < cam_first[c + 1]; e += fchunk) { f_start.push_back(e); f_end.push_back(std::min(e + fchunk, cam_first[c + 1])); }
-  }
-  cam_chunk_first[ncb] = (int)f_start.size();
-  ba->n_fchunks = (int)f_start.size();
-  // cameras of each intrinsics block
-  std::vector<int> cb_mb(std::max(1, ncb), -1), mcam_first(nmb + 1, 0), mcam;
-  for (int cb = 0; cb < ncb; cb++) {
-    const int m = P->cam_model_of_cam[ba->h_cb_cam[cb]];
-    cb_mb[cb] = is_mut(P->model_mutable, m) ? model_slot[m] : -1;
-  }
-  for (int mb = 0; mb < nmb; mb++) {
-    mcam_first[mb] = (int)mcam.size();
-    for (int cb = 0; cb < ncb; cb++) if (cb_mb[cb] == mb) mcam.push_back(cb);
-  }
-  mcam_first[nmb] = (int)mcam.size();
+  MSFM_TRY(build_ftf_chunks(ctx, ba, cam_first));
   // ---- pair lists, counting-sorted by (block row, block col) ----
   auto build_pairs = [&](int kind, PairJobs& J, int nout) -> int {
     // kind 0: cam-cam (rows cb_a >= cols cb_b), 1: intr-cam, 2: intr-intr (mb_a >= mb_b)
@@ -3801,21 +3791,12 @@ static int create_structures_host(msfm_ctx* ctx, const msfm_ba_problem* P, msfm_
   };
   lap("before upload");
   // ---- upload ----
-  std::vector<double> gps_cb;
-  if (ba->has_gps) {
-    gps_cb.resize(3 * (size_t)ncb);
-    for (int cb = 0; cb < ncb; cb++) for (int k = 0; k < 3; k++) gps_cb[3 * (size_t)cb + k] = P->gps_xyz[3 * (size_t)ba->h_cb_cam[cb] + k];
-  }
 #define UP(buf, vec) HIP_TRY(ctx, ba->buf.from(vec, s))
   UP(o_cam, o_cam); UP(o_model, o_model); UP(o_pt, o_pt); UP(o_cb, o_cb); UP(o_mb, o_mb); UP(o_pb, o_pb);
   UP(o_cpos, o_cpos); UP(o_pm, o_pm); UP(o_x, o_x); UP(o_y, o_y); UP(o_w, o_w);
-  UP(cb_cam, ba->h_cb_cam); UP(mb_model, ba->h_mb_model); UP(pb_pt, ba->h_pb_pt); UP(cb_mb, cb_mb);
+  UP(pb_pt, ba->h_pb_pt);
   UP(cpos_pb, cpos_pb); UP(pt_first, pt_first); UP(pm_first, pm_first);
   if (NPM) UP(pm_mb, pm_mb);
-  UP(f_start, f_start); UP(f_end, f_end); UP(cam_chunk_first, cam_chunk_first);
-  UP(mcam_first, mcam_first);
-  if (!mcam.empty()) UP(mcam, mcam);
-  if (ba->has_gps) UP(gps, gps_cb);
 #undef UP
   HIP_TRY(ctx, hipStreamSynchronize(s));
   lap("uploads");
@@ -3869,27 +3850,18 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   const int Nc = ba->Nc, Nm = ba->Nm, Np = ba->Np, ncb = ba->ncb, nmb = ba->nmb, npb = ba->npb, A = ba->A, NCR = ba->NCR, NPM = ba->NPM;
   if (ctx->world > 1 && ncb > 0 && ncb <= 4096) {
     // union over ranks of the camera-camera block structure: a 0/1 matrix, max-reduced once
-    std::vector<double> ind((size_t)ncb * ncb, 0.0);
-    for (int b = 0; b < ba->cc.n_blocks; b++) ind[(size_t)ba->cc.h_row[b] * ncb + ba->cc.h_col[b]] = 1.0;
-    DevBuf<double> dind;
-    DevScope blk(ctx);
-    HIP_TRY(ctx, dind.from(ind, s));
-    HIP_TRY(ctx, hipStreamSynchronize(s));
-    {
-      const int rc = ctx->allreduce(ctx->allreduce_user, dind.p, ind.size(), MSFM_REDUCE_MAX, (void*)s);
-      if (rc != 0) return msfm_set_error(ctx, MSFM_E_DEVICE, "all-reduce hook failed: %d", rc);
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(ind.data(), dind.p, sizeof(double) * ind.size(), hipMemcpyDeviceToHost, s));
-    MSFM_TRY(msfm_stream_wait_bounded(ctx, s, "the all-reduce of the block structure"));
+    std::vector<uint8_t> ind((size_t)ncb * ncb, 0);
+    for (int b = 0; b < ba->cc.n_blocks; b++) ind[(size_t)ba->cc.h_row[b] * ncb + ba->cc.h_col[b]] = 1;
+    MSFM_TRY(allreduce_max_01(ctx, ind, "the all-reduce of the block structure"));
     std::vector<int> ur, uc;
     for (int r = 0; r < ncb; r++)
       for (int c = 0; c <= r; c++)
-        if (ind[(size_t)r * ncb + c] != 0.0) { ur.push_back(r); uc.push_back(c); }
+        if (ind[(size_t)r * ncb + c]) { ur.push_back(r); uc.push_back(c); }
     ba->n_ublk = (int)ur.size();
     HIP_TRY(ctx, ba->u_row.from(ur, s));
     HIP_TRY(ctx, ba->u_col.from(uc, s));
     HIP_TRY(ctx, ba->pack.alloc((size_t)std::max(1, ba->n_ublk) * 36 + (size_t)(ba->nsys - ba->mo + 1) * ba->npad));
-    HIP_TRY(ctx, blk.finish());
+    HIP_TRY(ctx, hipStreamSynchronize(s));   // (ur and uc go out of scope)
   }
   const size_t As = std::max(1, A);
 #define AL(buf, n) HIP_TRY(ctx, ba->buf.alloc((size_t)std::max<size_t>(1, (n))))
@@ -3909,9 +3881,9 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   AL(g_r, 3 * (size_t)ncb); AL(g_J, 3 * (size_t)ncb);
   ba->nblk_obs = cdiv(As, 256);
   ba->nblk_pt = ptmap_n_wg(ba->map);
-  const size_t npart = (size_t)ba->nblk_obs + ba->nblk_pt + cdiv(std::max(1, ncb), 256) + 64;
-  AL(partial, npart); AL(partial2, npart); AL(partial3, npart); AL(partial4, npart); AL(partial_x, npart);
-  AL(gmax_buf, (size_t)ba->nblk_pt + 6 * (size_t)ncb + 3 * (size_t)nmb + 8);
+  const BaPartials& L = ba->parts = ba_partials(A, ba->AE, ncb, nmb, ba->nred, npb, ba->nblk_pt, ba->has_gps);
+  AL(partial, L.need_m); AL(partial2, L.need_u); AL(partial3, L.need_u); AL(partial4, L.need_c); AL(partial_x, L.need_x);
+  AL(gmax_buf, L.need_g);
   AL(scal, S_N); AL(sloc, S_N); AL(spec, 8);
   AL(col_param, ba->npad); AL(col_slot, ba->npad); AL(upd_dx2, ba->nred); AL(upd_x2, ba->nred);
   ba->spec_on = ba->env.spec;
@@ -4039,6 +4011,21 @@ MSFM_API int msfm_ba_download_params(msfm_ba* ba, double* cam_pose, double* cam_
 const double* ba_device_points(const msfm_ba* ba) { return ba->pt.p; }
 
 // ---- phases ----------------------------------------------------------------------------
+// The state of one msfm_ba_run, which owns it and passes it to the phases.
+struct BaRunState {
+  bool lin_pending = false;   // enqueue_linearize_rest was called: the next k_point linearises, writes the camera rows and the cost
+  double lin_huber = 1.0;
+  bool m_zeroed = false;      // M is zeroed for the next assembly (k_tail, behind a completed solve); cleared by every assembly
+};
+// What an assembly leaves to the solve that follows it at once (run_assemble returns it, run_solve takes it; empty when no solve
+// follows; on an error path it is dropped and the next run assembles afresh).
+struct AsmHandover {
+  ReduceJobs jobs;               // sums of the assembly (S_GMAX, S_XCOST) that the step's last k_reduce takes over
+  bool modelsum_rides = false;   // the assembly left its k_modelsum to the factorisation's level-0 corner update (solve_riders.h)
+  ModelSumArgs modelsum;
+  AsmHandover() { jobs.count = 0; }
+};
+
 static BaPtrs make_ptrs(msfm_ba* ba, bool candidate, double huber) {
   BaPtrs P;
   P.A = ba->A; P.AE = ba->AE; P.ncb = ba->ncb; P.nmb = ba->nmb; P.npb = ba->npb; P.NCR = ba->NCR;
@@ -4066,45 +4053,44 @@ static int allreduce(msfm_ba* ba, double* buf, size_t count, int op) {
 
 // Enqueues the linearisation of the rows that k_point does not take - those of frozen points and the GPS rows - at x or at
 // the candidate, and marks the linearisation point as new.  The rows of the eliminated points are linearised inside the next
-// k_point (run_assemble), which also writes their camera-major copies and cost partials [0, nblk_pt); the partials of these
-// rows follow them (blocks [nblk_pt, nblk_pt + ntail), then the GPS rows'), and run_assemble sums them all into S_XCOST
-// (local partial; summed over ranks together with the other scalars).  spec: see PointPtrs::spec.
-static void enqueue_linearize_rest(msfm_ba* ba, bool candidate, double huber, const double* spec = nullptr) {
+// k_point (run_assemble), which also writes their camera-major copies and cost partials; the partials of these rows follow
+// them in partial_x (BaPartials), and run_assemble sums them all into S_XCOST (local partial; summed over ranks together
+// with the other scalars).  spec: see PointPtrs::spec.
+static void enqueue_linearize_rest(msfm_ba* ba, BaRunState& st, bool candidate, double huber, const double* spec = nullptr) {
   msfm_ctx* ctx = ba->ctx;
   hipStream_t s = ctx->stream;
-  // every rank needs the GPS rows' Jacobian (k_cam_post uses g_J via camftf only on the lead), but
-  // only the lead rank counts their cost
-  const int ng = ba->has_gps ? cdiv(ba->ncb, 256) : 0;
+  const BaPartials& L = ba->parts;
   BaPtrs P = make_ptrs(ba, candidate, huber);
   KTimer t(ctx, "ba_linearize");
-  const int ntail = cdiv(ba->A - ba->AE, 256);
-  if (ntail) hipLaunchKernelGGL(k_linearize<true>, dim3(ntail), dim3(256), 0, s, P, ba->AE, ba->partial_x.p + ba->nblk_pt, spec);
-  if (ng) hipLaunchKernelGGL(k_gps<true>, dim3(ng), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial_x.p + ba->nblk_pt + ntail, spec);
-  ba->lin_pending = true;
-  ba->lin_huber = huber;
+  if (L.x_frozen.n) hipLaunchKernelGGL(k_linearize<true>, dim3(L.x_frozen.n), dim3(256), 0, s, P, ba->AE, ba->partial_x.p + L.x_frozen.off, spec);
+  // every rank needs the GPS rows' Jacobian (k_cam_post uses g_J via camftf only on the lead), but
+  // only the lead rank counts their cost
+  if (L.x_gps.n) hipLaunchKernelGGL(k_gps<true>, dim3(L.x_gps.n), dim3(256), 0, s, ba->ncb, ba->cb_cam.p, P.cam, ba->gps.p, ba->gps_weight, huber, ba->scale_c.p, ba->g_r.p, ba->g_J.p, ba->partial_x.p + L.x_gps.off, spec);
+  st.lin_pending = true;
+  st.lin_huber = huber;
 }
 
 // The point kernel: linearises the rows of the eliminated points at x (or, `candidate`, at the candidate: the launch that
 // msfm_ba_run enqueues ahead of the host's view of a step, gated and given its radius by `spec`), eliminates the points.
-static void launch_point(msfm_ba* ba, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool store_rows, bool candidate,
-                         const double* spec) {
+static void launch_point(msfm_ba* ba, const BaRunState& st, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool store_rows,
+                         bool candidate, const double* spec) {
   msfm_ctx* ctx = ba->ctx;
   KTimer t(ctx, "ba_point");
   PointPtrs Q;
-  Q.B = make_ptrs(ba, candidate, ba->lin_huber);
+  Q.B = make_ptrs(ba, candidate, st.lin_huber);
   Q.map = ba->map; Q.npb = ba->npb; Q.NCR = std::max(1, ba->NCR); Q.pt_first = ba->pt_first.p;
   Q.pm_first = ba->pm_first.p; Q.pm_mb = ba->pm_mb.p;
   Q.diag_p = ba->diag_p.p; Q.ptL = ba->ptL.p; Q.ptg = ba->ptg.p;
   Q.T = ba->T.p; Q.Tu = ba->Tu.p; Q.Tm = ba->Tm.p; Q.Tmu = ba->Tmu.p;
   Q.radius = radius; Q.dmin = opt->min_lm_diagonal; Q.dmax = opt->max_lm_diagonal;
   Q.reuse_diag = reuse_diag; Q.mode = mode; Q.fail = ba->fail.p;
-  Q.store_rows = store_rows ? 1 : 0; Q.cost_partial = ba->partial_x.p;
+  Q.store_rows = store_rows ? 1 : 0; Q.cost_partial = ba->partial_x.p + ba->parts.x_point.off;
   const FoldTables& F = ba->fold;
   Q.fold_wg = F.on ? F.wg_fold.p : nullptr; Q.fold_wg_pass_first = F.wg_pass_first.p; Q.fold_slot_rank = F.slot_rank.p;
   Q.fold_pass = F.pass.p; Q.fold_stream = F.stream.p; Q.fold_partial = F.partial.p;
   Q.fold_mc_partial = (F.on && F.mc_on) ? F.mc_partial.p : nullptr;
   Q.spec = spec;
-  hipLaunchKernelGGL(k_point, dim3(ba->nblk_pt), dim3(256), 0, ctx->stream, Q, ba->gmax_buf.p);
+  hipLaunchKernelGGL(k_point, dim3(ba->nblk_pt), dim3(256), 0, ctx->stream, Q, ba->gmax_buf.p + ba->parts.g_point.off);
 }
 
 // the tiles of M that the zero fill covers as a ZeroMap (0: the plain memset is needed instead)
@@ -4142,18 +4128,68 @@ static AsmForm asm_form(const msfm_ba* ba) {
   return ASM_PLAIN;
 }
 
+// The arguments of k_sums: the fused form's per-camera sums, pair-list residue and zero tiles, or (beside) the fold-sum
+// workgroups in place of the zero tiles.
+static SumsArgs make_sums(msfm_ba* ba, double huber, bool beside) {
+  const size_t ncr = (size_t)std::max(1, ba->NCR);
+  SumsArgs a;
+  // (beside: the fold-sum workgroups store into M, so it is zeroed beforehand - by the k_tail of the last solve, or by run_assemble)
+  a.n_zero = beside ? 0 : ba_zero_map(ba, a.Z);
+  a.M = ba->M.p; a.ld = ba->npad;
+  const bool mc_sparse = ba->fold.on && ba->fold.mc_on;
+  a.mc_n = mc_sparse ? ba->fold.mc_n_live : ba->mc.n_chunks; a.mc_start = ba->mc.ch_start.p; a.mc_end = ba->mc.ch_end.p; a.mc_pa = ba->mc.pa.p; a.mc_pb = ba->mc.pb.p;
+  a.mc_live = mc_sparse ? ba->fold.mc_live_chunk.p : nullptr; a.mc_partial = ba->mc.partial.p;
+  a.mm_n = ba->mm.n_chunks; a.mm_start = ba->mm.ch_start.p; a.mm_end = ba->mm.ch_end.p; a.mm_pa = ba->mm.pa.p; a.mm_pb = ba->mm.pb.p; a.mm_partial = ba->mm.partial.p;
+  a.cc_n = ba->fold.on ? ba->fold.n_live : ba->cc.n_chunks; a.cc_start = ba->cc.ch_start.p; a.cc_end = ba->cc.ch_end.p; a.cc_pa = ba->cc.pa.p; a.cc_pb = ba->cc.pb.p;
+  a.cc_live = ba->fold.on ? ba->fold.live_chunk.p : nullptr; a.cc_partial = ba->cc.partial.p;
+  a.T = ba->T.p; a.Tm = ba->Tm.p; a.Tmu = ba->Tmu.p; a.plane = ncr;
+  a.f_n = ba->n_fchunks; a.f_start = ba->f_start.p; a.f_end = ba->f_end.p; a.P = make_ptrs(ba, false, huber);
+  a.R = CamRows{ba->cm_pt.p, ba->cm_X.p, ba->cm_xyw.p, ba->cm_xyw.p + ncr, ba->cm_xyw.p + 2 * ncr, ba->chunk_cam.p};
+  a.Tu = ba->Tu.p; a.cpos_pb = ba->cpos_pb.p; a.f_partial = ba->f_partial.p;
+  a.n_mc_wg = cdiv(a.mc_n, 4); a.n_mm_wg = cdiv(a.mm_n, 4); a.n_cc_wg = cdiv(a.cc_n, 4); a.n_ftf_wg = cdiv(a.f_n, 4);
+  memset(&a.fs, 0, sizeof a.fs);
+  if (beside) {
+    FoldSumArgs& f = a.fs;
+    f.n_cc = ba->cc.n_blocks; f.n_mc = ba->mc.n_blocks; f.mo = ba->mo;
+    f.n_cc_wg = cdiv(cdiv(f.n_cc, 3), 4); f.n_mc_wg = cdiv(f.n_mc, 4);
+    f.cc_row = ba->cc.blk_row.p; f.cc_col = ba->cc.blk_col.p; f.cc_range = ba->fold.blk_range.p; f.cc_fold_partial = ba->fold.partial.p;
+    f.mc_row = ba->mc.blk_row.p; f.mc_col = ba->mc.blk_col.p; f.mc_range = ba->fold.mc_range.p; f.mc_fold_partial = ba->fold.mc_partial.p;
+    f.cb_off = ba->cb_off.p;
+  }
+  return a;
+}
+// The arguments of k_asm_all: the blocks of the reduced system from the chunk and fold partials, the rhs row, the padding columns.
+static AsmArgs make_asm(const msfm_ba* ba, double radius, int lead) {
+  AsmArgs aa;
+  aa.n_cc = ba->cc.n_blocks; aa.n_mc = ba->mc.n_blocks; aa.n_mm = ba->mm.n_blocks; aa.n_rhs = cdiv(6 * ba->ncb, 64);
+  aa.cc_row = ba->cc.blk_row.p; aa.cc_col = ba->cc.blk_col.p; aa.cc_first = (ba->fold.on && ba->fold.all) ? nullptr : ba->cc.blk_chunk_first.p; aa.cc_partial = ba->cc.partial.p;
+  aa.cc_fold_first = ba->fold.on ? ba->fold.blk_range.p : nullptr; aa.cc_live = ba->fold.on ? ba->fold.blk_live.p : nullptr; aa.cc_fold_partial = ba->fold.partial.p;
+  aa.mc_row = ba->mc.blk_row.p; aa.mc_col = ba->mc.blk_col.p; aa.mc_partial = ba->mc.partial.p;
+  const bool fmc = ba->fold.on && ba->fold.mc_on;
+  aa.mc_first = (fmc && ba->fold.mc_all) ? nullptr : ba->mc.blk_chunk_first.p;
+  aa.mc_fold_range = fmc ? ba->fold.mc_range.p : nullptr; aa.mc_fold_partial = ba->fold.mc_partial.p;
+  aa.mm_row = ba->mm.blk_row.p; aa.mm_col = ba->mm.blk_col.p; aa.mm_first = ba->mm.blk_chunk_first.p; aa.mm_partial = ba->mm.partial.p;
+  aa.cb_mb = ba->cb_mb.p; aa.cb_off = ba->cb_off.p; aa.camftf = ba->camftf.p; aa.diag_c = ba->diag_c.p; aa.modelsum = ba->modelsum.p;
+  aa.diag_m = ba->diag_m.p; aa.radius = radius; aa.ncb = ba->ncb; aa.mo = ba->mo; aa.n = ba->nsys; aa.ld = ba->npad; aa.lead = lead; aa.M = ba->M.p;
+  aa.n_padcol = ba->ctx->world <= 1 ? ba->n_padcol : 0;
+  aa.padcol = ba->padcol.p;
+  return aa;
+}
+
 // point kernel + camera sums (+, for mode 0, the reduced system in M).  point_enqueued: the point kernel of this
-// linearisation point is already in the stream (msfm_ba_run enqueued it ahead of the step's read-back).  will_solve: run_solve
-// follows (its last k_reduce can then take the sums of this call's over).
-static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool point_enqueued = false,
-                        bool will_solve = false) {
+// linearisation point is already in the stream (msfm_ba_run enqueued it ahead of the step's read-back).  out: run_solve
+// follows at once and takes what this assembly leaves to it (AsmHandover; null: no solve follows, nothing is left over).
+static int run_assemble(msfm_ba* ba, BaRunState& st, const msfm_ba_options* opt, double radius, bool reuse_diag, int mode, bool point_enqueued = false,
+                        AsmHandover* out = nullptr) {
   msfm_ctx* ctx = ba->ctx;
   hipStream_t s = ctx->stream;
+  const bool will_solve = out != nullptr;
   const int ncb = ba->ncb, nmb = ba->nmb;
   const int lead = ctx->rank == 0 ? 1 : 0;
-  const bool store_rows = ba->lin_pending;   // new linearisation point (else: the same rows again, new radius)
-  ba->lin_pending = false;
-  if (!point_enqueued) launch_point(ba, opt, radius, reuse_diag, mode, store_rows, false, nullptr);
+  const BaPartials& L = ba->parts;
+  const bool store_rows = st.lin_pending;   // new linearisation point (else: the same rows again, new radius)
+  st.lin_pending = false;
+  if (!point_enqueued) launch_point(ba, st, opt, radius, reuse_diag, mode, store_rows, false, nullptr);
   const AsmForm form = mode == 0 ? asm_form(ba) : ASM_PLAIN;   // (mode 1 takes the per-camera sums only: k_ftf)
   const bool fused = form != ASM_PLAIN, beside = form == ASM_BESIDE;
   // plain form: the Schur pair products read only what k_point wrote (T, Tm, Tmu) and write their own partials (the fold tables
@@ -4170,8 +4206,8 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       hipLaunchKernelGGL((k_pairs<6, 6, false>), dim3(cdiv(ba->cc.n_chunks, 4)), dim3(256), 0, s, ba->cc.n_chunks, ba->cc.ch_start.p,
                          ba->cc.ch_end.p, ba->cc.pa.p, ba->cc.pb.p, ba->T.p, ba->T.p, (const double*)nullptr, ncr, ba->cc.partial.p);
   };
-  const bool m_zeroed = ba->m_zeroed;
-  if (mode == 0) { ba->m_zeroed = false; ba->n_defer = 0; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; ba->modelsum_rides = false; }
+  const bool m_zeroed = st.m_zeroed;
+  if (mode == 0) { st.m_zeroed = false; ba->asm_paths = beside ? MSFM_PATH_ASM_BESIDE : 0; }
   // zero fill of the reduced system in front of the assembly, as a launch of its own
   auto zero_system = [&]() -> int {
     ZeroMap Z;
@@ -4180,45 +4216,18 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     else HIP_TRY(ctx, hipMemsetAsync(ba->M.p, 0, sizeof(double) * (size_t)ba->npad * ba->npad, s));   // (several ranks sum whole rows of M: every entry must be defined)
     return MSFM_OK;
   };
-  double* gmax_c = ba->gmax_buf.p + ba->nblk_pt;
-  double* gmax_m = gmax_c + 6 * (size_t)ncb;
   {
     KTimer t(ctx, "ba_ftf");
     if (fused) {
-      const size_t ncr = (size_t)std::max(1, ba->NCR);
-      SumsArgs a;
-      // (beside: the fold-sum workgroups store into M, so it is zeroed beforehand - by the k_tail of the last solve, or here)
-      a.n_zero = beside ? 0 : ba_zero_map(ba, a.Z);
+      const SumsArgs a = make_sums(ba, st.lin_huber, beside);
       if (beside ? !m_zeroed : a.n_zero == 0) MSFM_TRY(zero_system());
-      a.M = ba->M.p; a.ld = ba->npad;
-      const bool mc_sparse = ba->fold.on && ba->fold.mc_on;
-      a.mc_n = mc_sparse ? ba->fold.mc_n_live : ba->mc.n_chunks; a.mc_start = ba->mc.ch_start.p; a.mc_end = ba->mc.ch_end.p; a.mc_pa = ba->mc.pa.p; a.mc_pb = ba->mc.pb.p;
-      a.mc_live = mc_sparse ? ba->fold.mc_live_chunk.p : nullptr; a.mc_partial = ba->mc.partial.p;
-      a.mm_n = ba->mm.n_chunks; a.mm_start = ba->mm.ch_start.p; a.mm_end = ba->mm.ch_end.p; a.mm_pa = ba->mm.pa.p; a.mm_pb = ba->mm.pb.p; a.mm_partial = ba->mm.partial.p;
-      a.cc_n = ba->fold.on ? ba->fold.n_live : ba->cc.n_chunks; a.cc_start = ba->cc.ch_start.p; a.cc_end = ba->cc.ch_end.p; a.cc_pa = ba->cc.pa.p; a.cc_pb = ba->cc.pb.p;
-      a.cc_live = ba->fold.on ? ba->fold.live_chunk.p : nullptr; a.cc_partial = ba->cc.partial.p;
-      a.T = ba->T.p; a.Tm = ba->Tm.p; a.Tmu = ba->Tmu.p; a.plane = ncr;
-      a.f_n = ba->n_fchunks; a.f_start = ba->f_start.p; a.f_end = ba->f_end.p; a.P = make_ptrs(ba, false, ba->lin_huber);
-      a.R = CamRows{ba->cm_pt.p, ba->cm_X.p, ba->cm_xyw.p, ba->cm_xyw.p + ncr, ba->cm_xyw.p + 2 * ncr, ba->chunk_cam.p};
-      a.Tu = ba->Tu.p; a.cpos_pb = ba->cpos_pb.p; a.f_partial = ba->f_partial.p;
-      a.n_mc_wg = cdiv(a.mc_n, 4); a.n_mm_wg = cdiv(a.mm_n, 4); a.n_cc_wg = cdiv(a.cc_n, 4); a.n_ftf_wg = cdiv(a.f_n, 4);
-      memset(&a.fs, 0, sizeof a.fs);
-      int n_rest = a.n_ftf_wg;   // workgroups behind the pair lists'
-      if (beside) {
-        FoldSumArgs& f = a.fs;
-        f.n_cc = ba->cc.n_blocks; f.n_mc = ba->mc.n_blocks; f.mo = ba->mo;
-        f.n_cc_wg = cdiv(cdiv(f.n_cc, 3), 4); f.n_mc_wg = cdiv(f.n_mc, 4);
-        f.cc_row = ba->cc.blk_row.p; f.cc_col = ba->cc.blk_col.p; f.cc_range = ba->fold.blk_range.p; f.cc_fold_partial = ba->fold.partial.p;
-        f.mc_row = ba->mc.blk_row.p; f.mc_col = ba->mc.blk_col.p; f.mc_range = ba->fold.mc_range.p; f.mc_fold_partial = ba->fold.mc_partial.p;
-        f.cb_off = ba->cb_off.p;
-        n_rest += f.n_mc_wg + f.n_cc_wg;
-      }
-      hipLaunchKernelGGL(k_sums, dim3(a.n_zero + a.n_mc_wg + a.n_mm_wg + a.n_cc_wg + n_rest), dim3(256), 0, s, a);
+      // (the pair lists' workgroups, then the per-camera sums' and, beside, the fold sums')
+      hipLaunchKernelGGL(k_sums, dim3(a.n_zero + a.n_mc_wg + a.n_mm_wg + a.n_cc_wg + a.n_ftf_wg + a.fs.n_mc_wg + a.fs.n_cc_wg), dim3(256), 0, s, a);
     } else if (ba->n_fchunks) {
       const size_t ncr = (size_t)std::max(1, ba->NCR);
       const CamRows R{ba->cm_pt.p, ba->cm_X.p, ba->cm_xyw.p, ba->cm_xyw.p + ncr, ba->cm_xyw.p + 2 * ncr, ba->chunk_cam.p};
       hipLaunchKernelGGL(k_ftf, dim3(cdiv(ba->n_fchunks, 4)), dim3(256), 0, s, ba->n_fchunks, ba->f_start.p, ba->f_end.p,
-                         make_ptrs(ba, false, ba->lin_huber), R, ba->Tu.p, ba->cpos_pb.p, ba->f_partial.p);
+                         make_ptrs(ba, false, st.lin_huber), R, ba->Tu.p, ba->cpos_pb.p, ba->f_partial.p);
     }
     if (ncb) {
       CamFinish fin;
@@ -4226,7 +4235,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
       if (beside) fin = CamFinish{ba->M.p, ba->npad, ba->nsys, ba->mo, ba->cb_off.p, ba->cb_mb.p, radius, ba->n_padcol, ba->padcol.p};
       hipLaunchKernelGGL(k_camftf, dim3(ncb + (beside ? cdiv(ba->n_padcol, 128) : 0)), dim3(128), 0, s, ncb, ba->cam_chunk_first.p, ba->f_partial.p, ba->camftf.p,
                          ba->g_r.p, ba->g_J.p, (ba->has_gps && lead) ? 1 : 0, ctx->world <= 1 ? 1 : 0, ba->diag_c.p, ba->scale_c.p,
-                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_c, fin);
+                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, ba->gmax_buf.p + L.g_cam.off, fin);
     }
   }
   if (ncb) MSFM_TRY(allreduce(ba, ba->camftf.p, (size_t)ncb * PSTRIDE, MSFM_REDUCE_SUM));  // per-camera sums over all shards
@@ -4234,23 +4243,23 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     KTimer t(ctx, "ba_ftf");
     if (ncb && ctx->world > 1)
       hipLaunchKernelGGL(k_cam_post, dim3(cdiv(6 * ncb, 256)), dim3(256), 0, s, ncb, ba->camftf.p, ba->diag_c.p, ba->scale_c.p,
-                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_c);
+                         reuse_diag ? 1 : 0, mode, opt->min_lm_diagonal, opt->max_lm_diagonal, ba->gmax_buf.p + L.g_cam.off);
     if (nmb) {
       ModelFinish fin;
       memset(&fin, 0, sizeof fin);
       if (beside) fin = ModelFinish{ba->M.p, ba->npad, ba->nsys, ba->mo, ba->mm.n_blocks, ba->mm.blk_row.p, ba->mm.blk_col.p, ba->mm.blk_chunk_first.p, ba->mm.partial.p, radius};
       const ModelSumArgs ma{nmb, ba->mcam_first.p, ba->mcam.p, ba->camftf.p, ba->modelsum.p, ba->diag_m.p, ba->scale_m.p, reuse_diag ? 1 : 0, mode,
-                            opt->min_lm_diagonal, opt->max_lm_diagonal, gmax_m, fin};
+                            opt->min_lm_diagonal, opt->max_lm_diagonal, ba->gmax_buf.p + L.g_model.off, fin};
       // Beside, with an elimination tree and a solve behind this assembly, nothing needs these results before the merge of the
       // factorisation's level-0 corner update: they are columns of the root (the level-0 chains leave the tiles among the rows
-      // from b0 on out, the corner update writes its own buffers), and gmax_m is read by the step's last k_reduce only.  The
-      // work then rides with that corner update (run_solve hands it on) instead of standing in front of the leaf chains.
-      // (a promise that run_solve follows at once - assemble_and_step - and takes the flag down again.  If the factorisation
-      //  refuses before its level-0 launch, this assembly's modelsum / diag_m / gmax_m and intrinsics block were never
-      //  written: that return ends msfm_ba_run with its error, and the next run assembles afresh.)
+      // from b0 on out, the corner update writes its own buffers), and the intrinsics' gradient norms are read by the step's last
+      // k_reduce only.  The work then rides with that corner update (run_solve hands it on) instead of standing in front of the
+      // leaf chains.  (If the factorisation refuses before its level-0 launch, this assembly's modelsum / diag_m / gradient
+      // norms and intrinsics block were never written: that return ends msfm_ba_run with its error, and the next run assembles
+      // afresh.)
       if (beside && will_solve && ba->env.solve_riders && ba->plan.n_levels > 0 && ba->nred > 0) {
-        ba->modelsum_rides = true;
-        ba->modelsum_args = ma;
+        out->modelsum_rides = true;
+        out->modelsum = ma;
       } else {
         hipLaunchKernelGGL(k_modelsum, dim3(nmb), dim3(beside ? 128 : 64), 0, s, ma);
       }
@@ -4260,11 +4269,10 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
   {
     ReduceJobs rj;
     rj.count = 1;
-    rj.job[0] = {ba->gmax_buf.p, ba->nblk_pt + 6 * ncb + 3 * nmb, S_GMAX, 1};
+    rj.job[0] = {ba->gmax_buf.p, L.sum_g, S_GMAX, 1};
     if (store_rows) {
       // cost at x: k_point's blocks, the frozen points' rows, the GPS rows (lead rank only) - see enqueue_linearize_rest
-      const int ntail = cdiv(ba->A - ba->AE, 256), ng = (ba->has_gps && lead) ? cdiv(ncb, 256) : 0;
-      rj.job[1] = {ba->partial_x.p, ba->nblk_pt + ntail + ng, S_XCOST, 0};
+      rj.job[1] = {ba->partial_x.p, L.sum_x[lead], S_XCOST, 0};
       rj.count = 2;
     }
     rj.fail = ba->fail.p;
@@ -4272,8 +4280,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
     if (beside && will_solve) {
       // nothing reads these sums before k_publish_scalars: the last k_reduce of the step takes them (run_solve), off the path
       // to the factorisation
-      ba->n_defer = rj.count;
-      for (int j = 0; j < rj.count; j++) { ba->defer[j].p = rj.job[j].p; ba->defer[j].n = rj.job[j].n; ba->defer[j].slot = rj.job[j].slot; ba->defer[j].is_max = rj.job[j].is_max; }
+      out->jobs = rj;
     } else {
       hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
     }
@@ -4285,21 +4292,7 @@ static int run_assemble(msfm_ba* ba, const msfm_ba_options* opt, double radius, 
   {
     KTimer t(ctx, "ba_assemble");
     if (!fused) MSFM_TRY(zero_system());
-    AsmArgs aa;
-    aa.n_cc = ba->cc.n_blocks; aa.n_mc = ba->mc.n_blocks; aa.n_mm = ba->mm.n_blocks; aa.n_rhs = cdiv(6 * ncb, 64);
-    aa.cc_row = ba->cc.blk_row.p; aa.cc_col = ba->cc.blk_col.p; aa.cc_first = (ba->fold.on && ba->fold.all) ? nullptr : ba->cc.blk_chunk_first.p; aa.cc_partial = ba->cc.partial.p;
-    aa.cc_fold_first = ba->fold.on ? ba->fold.blk_range.p : nullptr; aa.cc_live = ba->fold.on ? ba->fold.blk_live.p : nullptr; aa.cc_fold_partial = ba->fold.partial.p;
-    aa.mc_row = ba->mc.blk_row.p; aa.mc_col = ba->mc.blk_col.p; aa.mc_partial = ba->mc.partial.p;
-    {
-      const bool fmc = ba->fold.on && ba->fold.mc_on;
-      aa.mc_first = (fmc && ba->fold.mc_all) ? nullptr : ba->mc.blk_chunk_first.p;
-      aa.mc_fold_range = fmc ? ba->fold.mc_range.p : nullptr; aa.mc_fold_partial = ba->fold.mc_partial.p;
-    }
-    aa.mm_row = ba->mm.blk_row.p; aa.mm_col = ba->mm.blk_col.p; aa.mm_first = ba->mm.blk_chunk_first.p; aa.mm_partial = ba->mm.partial.p;
-    aa.cb_mb = ba->cb_mb.p; aa.cb_off = ba->cb_off.p; aa.camftf = ba->camftf.p; aa.diag_c = ba->diag_c.p; aa.modelsum = ba->modelsum.p;
-    aa.diag_m = ba->diag_m.p; aa.radius = radius; aa.ncb = ncb; aa.mo = ba->mo; aa.n = ba->nsys; aa.ld = ba->npad; aa.lead = lead; aa.M = ba->M.p;
-    aa.n_padcol = ctx->world <= 1 ? ba->n_padcol : 0;
-    aa.padcol = ba->padcol.p;
+    const AsmArgs aa = make_asm(ba, radius, lead);
     const int nasm = aa.n_cc + aa.n_mc + aa.n_mm + aa.n_rhs + cdiv(aa.n_padcol, 64);
     if (nasm && !beside) hipLaunchKernelGGL(k_asm_all, dim3(nasm), dim3(64), 0, s, aa);   // (beside: M is complete already)
   }
@@ -4378,13 +4371,42 @@ static int wait_scalars(msfm_ba* ba) {
 }
 
 // factor + solve + candidate + model cost change + candidate cost
-static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
+// the arguments of k_backsub (huber: of the linearisation point the reduced system was built at)
+static BackPtrs make_back(msfm_ba* ba, double huber) {
+  BackPtrs Q;
+  Q.B = make_ptrs(ba, false, huber);
+  Q.map = ba->map; Q.npb = ba->npb; Q.ncb = ba->ncb; Q.pt_first = ba->pt_first.p; Q.pb_pt = ba->pb_pt.p;
+  Q.ptL = ba->ptL.p; Q.z = ba->z.p; Q.pt_c = ba->pt_c.p; Q.cm_Xc = ba->cm_Xc.p;
+  Q.Nc = ba->Nc; Q.cam_c = ba->cam_c.p; Q.rot_c = ba->rot_c.p;
+  return Q;
+}
+// the arguments of k_tail: model cost change of the remaining rows + cost at the candidate (all rows, GPS rows)
+static TailArgs make_tail(msfm_ba* ba, const msfm_ba_options* opt, int lead) {
+  const BaPartials& L = ba->parts;
+  const int ncb = ba->ncb;
+  TailArgs a;
+  // (the factor in M is dead behind the back substitution: zeroed here for the next assembly where that one sums beside)
+  a.n_zero = (ba->nred > 0 && asm_form(ba) == ASM_BESIDE) ? ba_zero_map(ba, a.Z) : 0;
+  a.M = ba->M.p; a.ld = ba->npad;
+  a.n_mcc = L.m_rest[lead].n;
+  a.A = ba->A; a.AE = ba->AE; a.ncb = ncb; a.o_cb = ba->o_cb.p; a.o_mb = ba->o_mb.p; a.lin_r = ba->lin_r.p; a.lin_Jc = ba->lin_Jc.p; a.lin_Jm = ba->lin_Jm.p;
+  a.z = ba->z.p; a.has_gps = (ba->has_gps && lead && ncb) ? 1 : 0; a.g_r = ba->g_r.p; a.g_J = ba->g_J.p; a.mcc_partial = ba->partial.p + L.m_rest[lead].off;
+  a.P = make_ptrs(ba, /*candidate=*/true, opt->huber_delta);
+  a.n_cost = ba->nblk_obs; a.cost_partial = ba->partial4.p + L.c_rows.off;   // (c_rows.n workgroups; the GPS rows' partials follow them: c_gps)
+  a.n_gps = L.c_gps.n;
+  a.cb_cam = ba->cb_cam.p; a.cam_c = a.P.cam; a.gps = ba->gps.p; a.gps_weight = ba->gps_weight; a.huber = opt->huber_delta; a.scale_c = ba->scale_c.p;
+  a.g_r_w = ba->g_r.p; a.g_J_w = ba->g_J.p;   // (not written: WRITE_JAC is false)
+  return a;
+}
+
+// factor + solve + candidate + model cost change + candidate cost.  h: what the assembly in front left to this call.
+static int run_solve(msfm_ba* ba, BaRunState& st, const msfm_ba_options* opt, const AsmHandover& h) {
   msfm_ctx* ctx = ba->ctx;
   hipStream_t s = ctx->stream;
   const int ncb = ba->ncb, nmb = ba->nmb, npb = ba->npb;
-  const bool lead = ctx->rank == 0;
+  const int lead = ctx->rank == 0 ? 1 : 0;
+  const BaPartials& L = ba->parts;
   const double* zsolved = ba->zsys.p;
-  const int nbu = cdiv(std::max(1, ba->nred), 256), nbp = npb ? ba->nblk_pt : 0;
   const double wrep = lead ? 1.0 : 0.0;
   msfm_chol_riders riders;
   SolveEpilogue ep;
@@ -4392,11 +4414,10 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
   if (ba->nred > 0) {
     double* const zcur = ba->zsys.p + (size_t)ba->zflip * (ba->npad + 8);
     double* const znext = ba->zsys.p + (size_t)(ba->zflip ^ 1) * (ba->npad + 8);
-    if (ba->modelsum_rides) { riders.modelsum = &ba->modelsum_args; ba->rider_paths |= MSFM_PATH_RIDER_MODELSUM; }
-    ba->modelsum_rides = false;
+    if (h.modelsum_rides) { riders.modelsum = &h.modelsum; ba->rider_paths |= MSFM_PATH_RIDER_MODELSUM; }
     // the camera / intrinsics part of the step inside the back substitution's launch, where k_backsub has the workgroups for
     // the block sums (otherwise, or where the back substitution is a chain of launches: k_update_params below)
-    if (ba->env.solve_riders && nbp >= nbu) {
+    if (ba->env.solve_riders && L.u_point.n >= L.u_step.n) {
       ep = SolveEpilogue{ba->col_param.p, ba->col_slot.p, 6 * ncb, ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->model.p, ba->cam_c.p, ba->model_c.p,
                          ba->z.p, ba->upd_dx2.p, ba->upd_x2.p, ba->fail.p, wrep};
       riders.epilogue = &ep;
@@ -4407,34 +4428,26 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
       // the call may have stopped before the solve kernel marked znext: neither half can be trusted to be "pending"
       // any more (a stale half would be taken for published values by the next solve) - mark both again
       (void)msfm_chol_fill_pending(ctx, ba->zsys.p, 2 * (ba->npad + 8));
-      ba->m_zeroed = false;
       ba->rider_paths = 0;   // (a rider handed over may not have run either: the run ends here, the next assembly starts afresh)
       return rc;
     }
     ba->zflip ^= 1;   // only a completed solve hands the other half over
     zsolved = zcur;
   }
-  int off = 0, moff = 0;   // partial2 = |dx|^2 partials, partial3 = |x|^2 partials (off of each), partial = model cost partials (moff)
   {
+    // partial2 = |dx|^2 partials, partial3 = |x|^2 partials: the camera / intrinsics step's (u_step), then k_backsub's (u_point)
     KTimer t(ctx, "ba_backsub");
     const bool in_solve = riders.epilogue_ran;
     if (in_solve) ba->rider_paths |= MSFM_PATH_RIDER_UPDATE;
-    if (ba->nred > 0) {
-      if (!in_solve)
-        hipLaunchKernelGGL(k_update_params, dim3(nbu), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo, zsolved,
-                           ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->cam_c.p, ba->model.p, ba->model_c.p, ba->z.p, ba->fail.p,
-                           ba->partial2.p + off, ba->partial3.p + off, wrep);
-      off += nbu;
-    }
+    if (ba->nred > 0 && !in_solve)
+      hipLaunchKernelGGL(k_update_params, dim3(L.u_step.n), dim3(256), 0, s, ncb, nmb, ba->cb_cam.p, ba->mb_model.p, ba->cb_off.p, ba->mo, zsolved,
+                         ba->scale_c.p, ba->scale_m.p, ba->cam.p, ba->cam_c.p, ba->model.p, ba->model_c.p, ba->z.p, ba->fail.p,
+                         ba->partial2.p + L.u_step.off, ba->partial3.p + L.u_step.off, wrep);
     if (npb) {
-      BackPtrs Q;
-      const UpdateSums U{in_solve ? nbu : 0, ba->nred, ba->upd_dx2.p, ba->upd_x2.p, ba->partial2.p, ba->partial3.p};   // (the places of k_update_params' sums: off was 0 there)
-      Q.B = make_ptrs(ba, false, ba->lin_huber);
-      Q.map = ba->map; Q.npb = npb; Q.ncb = ncb; Q.pt_first = ba->pt_first.p; Q.pb_pt = ba->pb_pt.p;
-      Q.ptL = ba->ptL.p; Q.z = ba->z.p; Q.pt_c = ba->pt_c.p; Q.cm_Xc = ba->cm_Xc.p;
-      Q.Nc = ba->Nc; Q.cam_c = ba->cam_c.p; Q.rot_c = ba->rot_c.p;
-      hipLaunchKernelGGL(k_backsub, dim3(nbp), dim3(256), 0, s, Q, ba->partial.p, ba->partial2.p + off, ba->partial3.p + off, U);
-      off += nbp; moff += nbp;
+      // (in the solve: k_backsub's first workgroups sum the epilogue's squares into the places of k_update_params' sums)
+      const UpdateSums U{in_solve ? L.u_step.n : 0, ba->nred, ba->upd_dx2.p, ba->upd_x2.p, ba->partial2.p + L.u_step.off, ba->partial3.p + L.u_step.off};
+      hipLaunchKernelGGL(k_backsub, dim3(L.u_point.n), dim3(256), 0, s, make_back(ba, st.lin_huber), ba->partial.p + L.m_point.off,
+                         ba->partial2.p + L.u_point.off, ba->partial3.p + L.u_point.off, U);
     } else {
       hipLaunchKernelGGL(k_rot_cache, dim3(cdiv(std::max(1, ba->Nc), 256)), dim3(256), 0, s, ba->Nc, ba->cam_c.p, ba->rot_c.p);
     }
@@ -4443,31 +4456,16 @@ static int run_solve(msfm_ba* ba, const msfm_ba_options* opt) {
     // model cost change of the remaining rows + cost at the candidate (all rows, GPS rows) in one launch, one reduction for
     // the four sums (the failure bits of the factorisation / finiteness checks are final here)
     KTimer t(ctx, "ba_cost");
-    const int ngps = (ba->has_gps && lead) ? ncb : 0;
-    const int nrest = (ba->A - ba->AE) + ngps;
-    TailArgs a;
-    // (the factor in M is dead behind the back substitution: zeroed here for the next assembly where that one sums beside)
-    a.n_zero = (ba->nred > 0 && asm_form(ba) == ASM_BESIDE) ? ba_zero_map(ba, a.Z) : 0;
-    a.M = ba->M.p; a.ld = ba->npad;
-    a.n_mcc = nrest ? cdiv(nrest, 256) : 0;
-    a.A = ba->A; a.AE = ba->AE; a.ncb = ncb; a.o_cb = ba->o_cb.p; a.o_mb = ba->o_mb.p; a.lin_r = ba->lin_r.p; a.lin_Jc = ba->lin_Jc.p; a.lin_Jm = ba->lin_Jm.p;
-    a.z = ba->z.p; a.has_gps = ngps ? 1 : 0; a.g_r = ba->g_r.p; a.g_J = ba->g_J.p; a.mcc_partial = ba->partial.p + moff;
-    moff += a.n_mcc;
-    a.P = make_ptrs(ba, /*candidate=*/true, opt->huber_delta);
-    a.n_cost = ba->nblk_obs; a.cost_partial = ba->partial4.p;
-    a.n_gps = ba->has_gps ? cdiv(ncb, 256) : 0;
-    a.cb_cam = ba->cb_cam.p; a.cam_c = a.P.cam; a.gps = ba->gps.p; a.gps_weight = ba->gps_weight; a.huber = opt->huber_delta; a.scale_c = ba->scale_c.p;
-    a.g_r_w = ba->g_r.p; a.g_J_w = ba->g_J.p;   // (not written: WRITE_JAC is false)
+    const TailArgs a = make_tail(ba, opt, lead);
     hipLaunchKernelGGL(k_tail, dim3(a.n_zero + a.n_mcc + a.n_cost + a.n_gps), dim3(256), 0, s, a);
-    ba->m_zeroed = a.n_zero > 0;
+    st.m_zeroed = a.n_zero > 0;
     ReduceJobs rj;
     rj.count = 4;
-    rj.job[0] = {ba->partial.p, moff, S_MCC, 0};
-    rj.job[1] = {ba->partial2.p, off, S_DX2, 0};
-    rj.job[2] = {ba->partial3.p, off, S_X2, 0};
-    rj.job[3] = {ba->partial4.p, a.n_cost + (lead ? a.n_gps : 0), S_COST, 0};
-    for (int j = 0; j < ba->n_defer; j++) rj.job[rj.count++] = {ba->defer[j].p, ba->defer[j].n, ba->defer[j].slot, ba->defer[j].is_max};   // (the assembly's: S_GMAX, S_XCOST)
-    ba->n_defer = 0;
+    rj.job[0] = {ba->partial.p, L.sum_m[lead], S_MCC, 0};
+    rj.job[1] = {ba->partial2.p, L.sum_u, S_DX2, 0};
+    rj.job[2] = {ba->partial3.p, L.sum_u, S_X2, 0};
+    rj.job[3] = {ba->partial4.p, L.sum_c[lead], S_COST, 0};
+    for (int j = 0; j < h.jobs.count; j++) rj.job[rj.count++] = h.jobs.job[j];   // (the assembly's: S_GMAX, S_XCOST)
     rj.fail = ba->fail.p;
     rj.fail_slot = S_FAIL;
     hipLaunchKernelGGL(k_reduce, dim3(rj.count), dim3(1024), 0, s, rj, ba->swrite);
@@ -4523,19 +4521,19 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     hipLaunchKernelGGL(k_cam_points, dim3(cdiv(ba->NCR, 256)), dim3(256), 0, s, ba->NCR, ba->cm_pt.p, ba->pt.p, ba->cm_X.p, ba->cm_Xc.p);
   lap("scales reset");
   hipLaunchKernelGGL(k_zero_int, dim3(1), dim3(1), 0, s, ba->fail.p);
-  ba->m_zeroed = false;   // (the first assembly of a run zero-fills for itself)
+  BaRunState st;   // (m_zeroed false: the first assembly of a run zero-fills for itself)
   double radius = opt->initial_trust_region_radius, decrease_factor = 2.0;
   bool reuse_diag = false;
   // ---- IterationZero ----
-  enqueue_linearize_rest(ba, false, opt->huber_delta);
+  enqueue_linearize_rest(ba, st, false, opt->huber_delta);
   lap("first evaluate enqueued");
   if (opt->jacobi_scaling) {
     // squared column norms of the corrected, unscaled Jacobian -> scaling -> re-linearise scaled
-    MSFM_TRY(run_assemble(ba, opt, radius, false, /*mode=*/1));
+    MSFM_TRY(run_assemble(ba, st, opt, radius, false, /*mode=*/1));
     if (ncb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(6 * ncb, 256)), dim3(256), 0, s, 6 * ncb, ba->diag_c.p, ba->scale_c.p);
     if (nmb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(3 * nmb, 256)), dim3(256), 0, s, 3 * nmb, ba->diag_m.p, ba->scale_m.p);
     if (npb) hipLaunchKernelGGL(k_make_scale, dim3(cdiv(3 * npb, 256)), dim3(256), 0, s, 3 * npb, ba->diag_p.p, ba->scale_p.p);
-    enqueue_linearize_rest(ba, false, opt->huber_delta);
+    enqueue_linearize_rest(ba, st, false, opt->huber_delta);
   }
   int iteration = 0, num_invalid = 0, termination = 0;
   lap("iteration zero enqueued");
@@ -4551,10 +4549,11 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
   bool spec_inflight = false;
   auto assemble_and_step = [&](bool point_enqueued) -> int {
     LmDecide D;
-    D.fresh = ba->lin_pending ? 1 : 0;
+    D.fresh = st.lin_pending ? 1 : 0;
     D.on = (iteration < opt->max_num_iterations && radius > opt->min_trust_region_radius) ? 1 : 0;
-    MSFM_TRY(run_assemble(ba, opt, radius, reuse_diag, 0, point_enqueued, D.on != 0));
-    if (D.on) MSFM_TRY(run_solve(ba, opt));
+    AsmHandover h;   // from the assembly to the solve that follows it at once (an error return drops it)
+    MSFM_TRY(run_assemble(ba, st, opt, radius, reuse_diag, 0, point_enqueued, D.on ? &h : nullptr));
+    if (D.on) MSFM_TRY(run_solve(ba, st, opt, h));
     MSFM_TRY(reduce_scalars(ba));
     D.x_cost = x_cost; D.radius = radius;
     D.min_relative_decrease = opt->min_relative_decrease; D.parameter_tolerance = opt->parameter_tolerance;
@@ -4563,9 +4562,9 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     spec_inflight = false;
     if (D.on && ba->spec_on) {
       // x_{k+1} would be the present candidate buffers
-      enqueue_linearize_rest(ba, /*candidate=*/true, opt->huber_delta, ba->spec.p);
-      launch_point(ba, opt, radius, false, 0, true, /*candidate=*/true, ba->spec.p);
-      ba->lin_pending = false;   // becomes true again if the host finds the step accepted
+      enqueue_linearize_rest(ba, st, /*candidate=*/true, opt->huber_delta, ba->spec.p);
+      launch_point(ba, st, opt, radius, false, 0, true, /*candidate=*/true, ba->spec.p);
+      st.lin_pending = false;   // becomes true again if the host finds the step accepted
       spec_inflight = true;
     }
     MSFM_TRY(wait_scalars(ba));
@@ -4633,11 +4632,11 @@ MSFM_API int msfm_ba_run(msfm_ba* ba, const msfm_ba_options* opt, msfm_ba_summar
     if (relinearise) {
       if (spec_inflight && radius > opt->min_trust_region_radius) {
         // the launches enqueued ahead found the same verdict on the device and are running
-        ba->lin_pending = true;
-        ba->lin_huber = opt->huber_delta;
+        st.lin_pending = true;
+        st.lin_huber = opt->huber_delta;
         point_enqueued = true;
       } else {
-        enqueue_linearize_rest(ba, false, opt->huber_delta);
+        enqueue_linearize_rest(ba, st, false, opt->huber_delta);
       }
     }
     MSFM_TRY(assemble_and_step(point_enqueued));
