@@ -73,39 +73,13 @@ struct BaPtrs {
 
 // --------------------------------------------------------------------------------------
 // The linearisation of one observation row: corrected (Huber) and column-scaled residual and Jacobian blocks, as the
-// eliminator and the back substitution use them.  Returns the row's cost 1/2 rho(s).  k_point, k_backsub and k_linearize
-// all evaluate THIS function (26 doubles per row are cheaper to recompute from 52 bytes of row data and cached
-// parameters than to write once and read twice: 0.75 GB per LM iteration at config 3).
+// eliminator and the back substitution use them.  Returns the row's cost 1/2 rho(s).  k_point and k_linearize evaluate THIS
+// function (26 doubles per row are cheaper to recompute from 52 bytes of row data and cached parameters than to write once and
+// read twice: 0.75 GB per LM iteration at config 3); k_backsub, which needs the residual, the point block and ONE contraction
+// of the camera and intrinsics blocks, evaluates msfm_backsub_row (ba_device.h) on the same row data.
 // Rows of frozen blocks come out as zeros (their scales are 0).
 // --------------------------------------------------------------------------------------
-// The arithmetic of obs_linearize on values already in registers (k_ftf evaluates it camera by camera: pose, rotation cache,
-// intrinsics and their column scales are the same for a whole chunk of rows).
-__device__ __forceinline__ double linearize_core(const double (&pose)[6], const double (&rc)[4], const double (&cm)[3], const double (&X)[3], double ox,
-                                                 double oy, double ow, const double (&sc)[6], const double (&sm)[3], const double (&sp)[3], double huber,
-                                                 double& r0, double& r1, double (&jc)[12], double (&jm)[6], double (&jp)[6]) {
-  double r[2], J[24];
-  msfm_reproj(pose, rc, cm, X, ox, oy, ow, r, J);
-  double rho0, rho1;
-  msfm_huber(huber, r[0] * r[0] + r[1] * r[1], rho0, rho1);
-  const double sq = sqrt(rho1);
-  r0 = sq * r[0]; r1 = sq * r[1];
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    const double s = sq * sc[j];
-    jc[j] = s * J[j];
-    jc[6 + j] = s * J[12 + j];
-  }
-#pragma unroll
-  for (int j = 0; j < 3; j++) {
-    const double s = sq * sm[j];
-    jm[j] = s * J[6 + j];
-    jm[3 + j] = s * J[12 + 6 + j];
-    const double spj = sq * sp[j];
-    jp[j] = spj * J[9 + j];
-    jp[3 + j] = spj * J[12 + 9 + j];
-  }
-  return 0.5 * rho0;
-}
+// (linearize_core, ba_device.h: the arithmetic of obs_linearize on values already in registers)
 __device__ __forceinline__ double obs_linearize(const BaPtrs& P, int i, double& r0, double& r1, double (&jc)[12], double (&jm)[6], double (&jp)[6]) {
   const int c = P.o_cam[i], m = P.o_model[i], p = P.o_pt[i];
   const int cb = P.o_cb[i], mb = P.o_mb[i], pb = P.o_pb[i];
@@ -416,7 +390,9 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
         // (the diagonal as reciprocals: the back substitution multiplies - six binary64 divisions, ~170 instructions that one lane in
         //  eight needs and the whole wave waits for, were a ninth of k_backsub's instruction stream)
         L[0] = i00; L[1] = l10; L[2] = i11; L[3] = l20; L[4] = l21; L[5] = i22;
-        // (g itself is not stored: the back substitution forms it again from the rows)
+        // (the undamped V and g are not stored: the back substitution sums them again from its rows' point blocks.  Measured at
+        //  config 3: 72 bytes per point from here cost this kernel 7 to 9 us - from lane 0 alone or as contiguous runs over the
+        //  lanes of the group - and reading them left k_backsub at 67.7 us against 65.7 with the nine sums)
         const double* sp = P.B.scale_p + 3 * (size_t)pb;
         gmax = fmax(fabs(g0 / sp[0]), fmax(fabs(g1 / sp[1]), fabs(g2 / sp[2])));
       }
@@ -1488,7 +1464,7 @@ __device__ __forceinline__ void update_block_sums(int n, const double* __restric
 }
 
 struct BackPtrs {
-  BaPtrs B;   // the rows are linearised again (obs_linearize) at the point the reduced system was built at
+  BaPtrs B;   // the rows are evaluated again (msfm_backsub_row) at the point the reduced system was built at
   PtMap map;
   int npb, ncb;
   const int *pt_first, *pb_pt;
@@ -1515,7 +1491,7 @@ struct UpdateSums {
 // so the step sp (known only after the group reduction) never needs a second sweep.
 template <int LPP>
 __device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
-                                               double* __restrict__ x2_partial, double* sh) {
+                                               double* __restrict__ x2_partial, double* sh, double* xacc /*[14 * 256], X body only*/) {
   constexpr int GW = LPP ? LPP : 8;
   const int tid = threadIdx.x, sub = tid & (GW - 1);
   const int pb = ptmap_wg_first(P.map, blockIdx.x) + tid / GW;
@@ -1523,45 +1499,73 @@ __device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __rest
   for (int c = blockIdx.x * 256 + tid; c < P.Nc; c += gridDim.x * 256) msfm_rot_prepare(P.cam_c + 6 * (size_t)c, P.rot_c + 4 * (size_t)c);
   int f = 0, l = 0;
   if (act) { f = P.pt_first[pb]; l = P.pt_first[pb + 1]; }
+  // what the point's rows share: its coordinates and column scales (lane 0 needs them again for the candidate); Lf: the factor
+  // k_point left of the point's 3x3 system, for lane 0
+  size_t p = 0;
+  double X[3] = {0, 0, 0}, sp[3] = {0, 0, 0}, Lf[6] = {0, 0, 0, 0, 0, 0};
+  if (act) {
+    p = P.pb_pt[pb];
+#pragma unroll
+    for (int j = 0; j < 3; j++) { X[j] = P.B.pt[3 * p + j]; sp[j] = P.B.scale_p[3 * (size_t)pb + j]; }
+  }
   double V00 = 0, V10 = 0, V11 = 0, V20 = 0, V21 = 0, V22 = 0, g0 = 0, g1 = 0, g2 = 0, h0 = 0, h1 = 0, h2 = 0, qr = 0, qq = 0;
+  // The X body's sums live in LDS across its rounds (one column per thread: no bank conflicts, nobody else's slots, so no
+  // barrier): 28 registers that the row evaluation does not have at four waves per SIMD - as loop-carried registers eight
+  // of them went through scratch every round, and a problem of long tracks only ran this kernel at 47.8 us against the
+  // 34.0 of the full-Jacobian form at three waves.
+  if constexpr (LPP == 0) {
+#pragma unroll
+    for (int k = 0; k < 14; k++) xacc[k * 256 + tid] = 0.0;
+  }
   const int n_rounds = LPP ? 1 : (l - f + 7) >> 3;   // (S, L: one trip of either loop)
   for (int rd = 0; rd < n_rounds; rd++) {
     const int i = f + GW * rd + sub;
     if (i < l) {
-      // rows of frozen blocks come out as zeros, so no branches
+      // every load of the row is issued here, the step z among them: one round trip.  A frozen block's scales are zeros (and its
+      // z is that of block 0, times zero), so no branches.
+      const int c = P.B.o_cam[i], m = P.B.o_model[i], cb = P.B.o_cb[i], mb = P.B.o_mb[i];
+      const double ox = P.B.o_x[i], oy = P.B.o_y[i], ow = P.B.o_w[i];
+      const double* zcp = P.z + 6 * (cb >= 0 ? cb : 0);
+      const double* zmp = P.z + 6 * P.ncb + 3 * (mb >= 0 ? mb : 0);
+      double pose[6], rc[4], cm[3], sc[6], sm[3], zc[6], zm[3];
+#pragma unroll
+      for (int j = 0; j < 6; j++) { pose[j] = P.B.cam[6 * (size_t)c + j]; sc[j] = cb >= 0 ? P.B.scale_c[6 * cb + j] : 0.0; zc[j] = zcp[j]; }
+#pragma unroll
+      for (int j = 0; j < 4; j++) rc[j] = P.B.rot[4 * (size_t)c + j];
+#pragma unroll
+      for (int j = 0; j < 3; j++) { cm[j] = P.B.model[3 * (size_t)m + j]; sm[j] = mb >= 0 ? P.B.scale_m[3 * mb + j] : 0.0; zm[j] = zmp[j]; }
       double jp[6], r0, r1, q0, q1;
-      {
-        const int cb = P.B.o_cb[i], mb = P.B.o_mb[i];
-        double jc[12], jm[6], zc[6], zm[3];
-        obs_linearize(P.B, i, r0, r1, jc, jm, jp);
-        __builtin_amdgcn_sched_barrier(0);   // the step is fetched after the row is formed: nine registers less before
-        const double* zcp = P.z + 6 * (cb >= 0 ? cb : 0);
-        const double* zmp = P.z + 6 * P.ncb + 3 * (mb >= 0 ? mb : 0);
-#pragma unroll
-        for (int j = 0; j < 6; j++) zc[j] = zcp[j];
-#pragma unroll
-        for (int j = 0; j < 3; j++) zm[j] = zmp[j];
-        q0 = 0.0; q1 = 0.0;
-#pragma unroll
-        for (int j = 0; j < 6; j++) { q0 -= jc[j] * zc[j]; q1 -= jc[6 + j] * zc[j]; }
-#pragma unroll
-        for (int j = 0; j < 3; j++) { q0 -= jm[j] * zm[j]; q1 -= jm[3 + j] * zm[j]; }
-      }
+      msfm_backsub_row(pose, rc, cm, X, ox, oy, ow, sc, sm, sp, zc, zm, P.B.huber, r0, r1, jp, q0, q1);
       const double a0 = jp[0], a1 = jp[1], a2 = jp[2], b0 = jp[3], b1 = jp[4], b2 = jp[5];
-      V00 += a0 * a0 + b0 * b0; V10 += a1 * a0 + b1 * b0; V11 += a1 * a1 + b1 * b1;
-      V20 += a2 * a0 + b2 * b0; V21 += a2 * a1 + b2 * b1; V22 += a2 * a2 + b2 * b2;
-      g0 += a0 * r0 + b0 * r1; g1 += a1 * r0 + b1 * r1; g2 += a2 * r0 + b2 * r1;
-      h0 += a0 * q0 + b0 * q1; h1 += a1 * q0 + b1 * q1; h2 += a2 * q0 + b2 * q1;
-      qr += q0 * r0 + q1 * r1;
-      qq += q0 * q0 + q1 * q1;
+      const double t[14] = {a0 * a0 + b0 * b0, a1 * a0 + b1 * b0, a1 * a1 + b1 * b1, a2 * a0 + b2 * b0, a2 * a1 + b2 * b1, a2 * a2 + b2 * b2,
+                            a0 * r0 + b0 * r1, a1 * r0 + b1 * r1, a2 * r0 + b2 * r1, a0 * q0 + b0 * q1, a1 * q0 + b1 * q1, a2 * q0 + b2 * q1,
+                            q0 * r0 + q1 * r1, q0 * q0 + q1 * q1};
+      if constexpr (LPP == 0) {
+#pragma unroll
+        for (int k = 0; k < 14; k++) xacc[k * 256 + tid] += t[k];
+      } else {
+        V00 += t[0]; V10 += t[1]; V11 += t[2]; V20 += t[3]; V21 += t[4]; V22 += t[5]; g0 += t[6]; g1 += t[7]; g2 += t[8];
+        h0 += t[9]; h1 += t[10]; h2 += t[11]; qr += t[12]; qq += t[13];
+      }
     }
+  }
+  if constexpr (LPP == 0) {
+    V00 = xacc[tid]; V10 = xacc[256 + tid]; V11 = xacc[2 * 256 + tid]; V20 = xacc[3 * 256 + tid]; V21 = xacc[4 * 256 + tid]; V22 = xacc[5 * 256 + tid];
+    g0 = xacc[6 * 256 + tid]; g1 = xacc[7 * 256 + tid]; g2 = xacc[8 * 256 + tid]; h0 = xacc[9 * 256 + tid]; h1 = xacc[10 * 256 + tid]; h2 = xacc[11 * 256 + tid];
+    qr = xacc[12 * 256 + tid]; qq = xacc[13 * 256 + tid];
+  }
+  // Lane 0's loads go out in front of the reduction, which covers part of their way.  (In front of the row evaluation they
+  // are held across it: the kernel is built for four waves per SIMD, 128 registers, and the bodies fit those without
+  // scratch only with nothing else live.)
+  if (act && sub == 0) {
+#pragma unroll
+    for (int j = 0; j < 6; j++) Lf[j] = P.ptL[6 * (size_t)pb + j];
   }
   GROUP_SUM(V00) GROUP_SUM(V10) GROUP_SUM(V11) GROUP_SUM(V20) GROUP_SUM(V21) GROUP_SUM(V22)
   GROUP_SUM(g0) GROUP_SUM(g1) GROUP_SUM(g2) GROUP_SUM(h0) GROUP_SUM(h1) GROUP_SUM(h2) GROUP_SUM(qr) GROUP_SUM(qq)
   double mcc = 0.0, dx2 = 0.0, x2 = 0.0, cand0 = 0.0, cand1 = 0.0, cand2 = 0.0;
   if (act && sub == 0) {
-    const double* L = P.ptL + 6 * (size_t)pb;
-    const double i00 = L[0], l10 = L[1], i11 = L[2], l20 = L[3], l21 = L[4], i22 = L[5];   // (1 / l00, 1 / l11, 1 / l22: k_point)
+    const double i00 = Lf[0], l10 = Lf[1], i11 = Lf[2], l20 = Lf[3], l21 = Lf[4], i22 = Lf[5];   // (1 / l00, 1 / l11, 1 / l22: k_point)
     // (L L^T) y' = y,  y = g + h
     double q0 = (g0 + h0) * i00;
     double q1 = ((g1 + h1) - l10 * q0) * i11;
@@ -1570,10 +1574,8 @@ __device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __rest
     q1 = (q1 - l21 * q2) * i11;
     q0 = (q0 - l10 * q1 - l20 * q2) * i00;
     const double s0 = -q0, s1 = -q1, s2 = -q2;  // step (scaled space)
-    const double* sc = P.B.scale_p + 3 * (size_t)pb;
-    const size_t p = P.pb_pt[pb];
-    const double x0 = P.B.pt[3 * p], x1 = P.B.pt[3 * p + 1], x2v = P.B.pt[3 * p + 2];
-    const double c0 = x0 + s0 * sc[0], c1 = x1 + s1 * sc[1], c2 = x2v + s2 * sc[2];
+    const double x0 = X[0], x1 = X[1], x2v = X[2];
+    const double c0 = x0 + s0 * sp[0], c1 = x1 + s1 * sp[1], c2 = x2v + s2 * sp[2];
     P.pt_c[3 * p] = c0; P.pt_c[3 * p + 1] = c1; P.pt_c[3 * p + 2] = c2;
     cand0 = c0; cand1 = c1; cand2 = c2;
     dx2 = (c0 - x0) * (c0 - x0) + (c1 - x1) * (c1 - x1) + (c2 - x2v) * (c2 - x2v);
@@ -1596,14 +1598,15 @@ __device__ __forceinline__ void k_backsub_body(const BackPtrs& P, double* __rest
   const double t2 = block_sum256(x2, sh);
   if (threadIdx.x == 0) { mcc_partial[blockIdx.x] = t0; dx2_partial[blockIdx.x] = t1; x2_partial[blockIdx.x] = t2; }
 }
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_backsub(BackPtrs P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_backsub(BackPtrs P, double* __restrict__ mcc_partial, double* __restrict__ dx2_partial,
                                                   double* __restrict__ x2_partial, UpdateSums U) {
   __shared__ double sh[4];
+  __shared__ double xacc[14 * 256];   // (28 KB: four workgroups per CU, the sixteen waves the kernel is built for, take 112 of its 160 KB)
   const int lanes = ptmap_lanes(P.map, blockIdx.x);   // (uniform over the workgroup)
-  if (lanes == 4) k_backsub_body<4>(P, mcc_partial, dx2_partial, x2_partial, sh);
-  else if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh);
-  else if (lanes == 16) k_backsub_body<16>(P, mcc_partial, dx2_partial, x2_partial, sh);
-  else k_backsub_body<0>(P, mcc_partial, dx2_partial, x2_partial, sh);
+  if (lanes == 4) k_backsub_body<4>(P, mcc_partial, dx2_partial, x2_partial, sh, xacc);
+  else if (lanes == 8) k_backsub_body<8>(P, mcc_partial, dx2_partial, x2_partial, sh, xacc);
+  else if (lanes == 16) k_backsub_body<16>(P, mcc_partial, dx2_partial, x2_partial, sh, xacc);
+  else k_backsub_body<0>(P, mcc_partial, dx2_partial, x2_partial, sh, xacc);
   if ((int)blockIdx.x < U.nbu) update_block_sums(U.n, U.dx2, U.x2, U.dx2_partial, U.x2_partial, sh);
 }
 

@@ -12,7 +12,7 @@
 // What depends on the camera's angle-axis vector alone: which branch of the rotation formula applies, and sin, cos and
 // 1 / |a|.  A camera is seen by thousands of observations per evaluation; msfm_rot_prepare computes these four numbers
 // once per camera and parameter set (rot[4 c ..]: flag, sin, cos, 1/theta) with the operations msfm_reproj would use.
-__device__ __forceinline__ void msfm_rot_prepare(const double* __restrict__ pose, double* __restrict__ rc) {
+__host__ __device__ __forceinline__ void msfm_rot_prepare(const double* __restrict__ pose, double* __restrict__ rc) {
   const double a0 = pose[0], a1 = pose[1], a2 = pose[2];
   const double theta2 = a0 * a0 + a1 * a1 + a2 * a2;
   double s = 0.0, c = 1.0, ti = 0.0, flag = 0.0;
@@ -25,9 +25,9 @@ __device__ __forceinline__ void msfm_rot_prepare(const double* __restrict__ pose
   rc[0] = flag; rc[1] = s; rc[2] = c; rc[3] = ti;
 }
 
-__device__ __forceinline__ void msfm_reproj(const double* __restrict__ pose, const double* __restrict__ rc, const double* __restrict__ cam,
-                                            const double* __restrict__ xyz, double ox, double oy, double weight,
-                                            double* r, double* J) {
+__host__ __device__ __forceinline__ void msfm_reproj(const double* __restrict__ pose, const double* __restrict__ rc, const double* __restrict__ cam,
+                                                     const double* __restrict__ xyz, double ox, double oy, double weight,
+                                                     double* r, double* J) {
   const double a0 = pose[0], a1 = pose[1], a2 = pose[2];
   const double X0 = xyz[0], X1 = xyz[1], X2 = xyz[2];
   double p0, p1, p2;
@@ -107,7 +107,7 @@ __device__ __forceinline__ void msfm_reproj(const double* __restrict__ pose, con
 }
 
 // ceres::HuberLoss(a) (constructed at optimizer.cc:84): rho0 = rho(s), rho1 = rho'(s).
-__device__ __forceinline__ void msfm_huber(double a, double s, double& rho0, double& rho1) {
+__host__ __device__ __forceinline__ void msfm_huber(double a, double s, double& rho0, double& rho1) {
   const double b = a * a;
   if (s > b) {
     const double r = sqrt(s);
@@ -116,6 +116,118 @@ __device__ __forceinline__ void msfm_huber(double a, double s, double& rho0, dou
   } else {
     rho0 = s;
     rho1 = 1.0;
+  }
+}
+
+// The arithmetic of obs_linearize (ba.hip) on values already in registers (k_ftf evaluates it camera by camera: pose, rotation
+// cache, intrinsics and their column scales are the same for a whole chunk of rows): the Huber-corrected, column-scaled row.
+__host__ __device__ __forceinline__ double linearize_core(const double (&pose)[6], const double (&rc)[4], const double (&cm)[3], const double (&X)[3], double ox,
+                                                          double oy, double ow, const double (&sc)[6], const double (&sm)[3], const double (&sp)[3], double huber,
+                                                          double& r0, double& r1, double (&jc)[12], double (&jm)[6], double (&jp)[6]) {
+  double r[2], J[24];
+  msfm_reproj(pose, rc, cm, X, ox, oy, ow, r, J);
+  double rho0, rho1;
+  msfm_huber(huber, r[0] * r[0] + r[1] * r[1], rho0, rho1);
+  const double sq = sqrt(rho1);
+  r0 = sq * r[0]; r1 = sq * r[1];
+#pragma unroll
+  for (int j = 0; j < 6; j++) {
+    const double s = sq * sc[j];
+    jc[j] = s * J[j];
+    jc[6 + j] = s * J[12 + j];
+  }
+#pragma unroll
+  for (int j = 0; j < 3; j++) {
+    const double s = sq * sm[j];
+    jm[j] = s * J[6 + j];
+    jm[3 + j] = s * J[12 + 6 + j];
+    const double spj = sq * sp[j];
+    jp[j] = spj * J[9 + j];
+    jp[3 + j] = spj * J[12 + 9 + j];
+  }
+  return 0.5 * rho0;
+}
+
+// What the back substitution needs of a row (k_backsub): the corrected residual, the scaled point block jp and
+// q = -(Jc z_c + Jm z_m), the derivative of the residual along ONE direction d = -(scale * z) over the row's camera block
+// (da = d[0..2], dt = d[3..5]) and intrinsics block (df, dl1, dl2).  That is one forward-mode tangent - about one more function
+// evaluation - where the six camera and three intrinsics columns of linearize_core cost three times that and leave 18 numbers
+// to contract.  A frozen block's scales are zero and so is its part of d.  With w = a / theta, wx = w x X, wdx = w.X,
+// omc = 1 - c, tmp = wdx omc (msfm_reproj's names) the tangent of p = c X + s wx + tmp w + t is
+//   dp = v (w.da) + ti ( s (da x X) + omc ((X.da) w + wdx da) ) + dt,   v = u - ti (s wx + 2 tmp w),  u = c wx - s X + (s wdx) w
+// (u = dp/dtheta at fixed w, the rest is dw = (da - w (w.da)) ti), in the first-order branch dp = da x X + dt, and behind the
+// projection  q_u = weight (uxp dxp + uyp dyp + xp m), q_v = weight (uyp dxp + vyp dyp + yp m), dxp = (dp0 - xp dp2) iz,
+// m = dist df + f r2 (dl1 + r2 dl2).  The point block is contracted first, R is never formed: row k = R^T g_k =
+// c g_k + s (g_k x w) + omc (g_k.w) w with g_k the gradient of residual component k by the camera-frame point (first-order
+// branch: g_k + g_k x a, the same expression at w = a, s = c = 1, omc = 0).  The residual is formed by msfm_reproj's operations
+// (its Jacobian mode: xp = p0 * iz), then Huber, then sq, as linearize_core forms it: r0 and r1 keep their bits.
+__host__ __device__ __forceinline__ void msfm_backsub_row(const double (&pose)[6], const double (&rc)[4], const double (&cm)[3], const double (&X)[3],
+                                                          double ox, double oy, double weight, const double (&sc)[6], const double (&sm)[3],
+                                                          const double (&sp)[3], const double (&zc)[6], const double (&zm)[3], double huber,
+                                                          double& r0, double& r1, double (&jp)[6], double& q0, double& q1) {
+  const double a0 = pose[0], a1 = pose[1], a2 = pose[2];
+  const double X0 = X[0], X1 = X[1], X2 = X[2];
+  const double da0 = -(sc[0] * zc[0]), da1 = -(sc[1] * zc[1]), da2 = -(sc[2] * zc[2]);
+  const double dt0 = -(sc[3] * zc[3]), dt1 = -(sc[4] * zc[4]), dt2 = -(sc[5] * zc[5]);
+  const double df = -(sm[0] * zm[0]), dl1 = -(sm[1] * zm[1]), dl2 = -(sm[2] * zm[2]);
+  const double cx0 = da1 * X2 - da2 * X1, cx1 = da2 * X0 - da0 * X2, cx2 = da0 * X1 - da1 * X0;   // da x X
+  double p0, p1, p2, dp0, dp1, dp2;
+  double w0, w1, w2, s, c, omc;   // what rotates the point block below
+  if (rc[0] != 0.0) {
+    s = rc[1]; c = rc[2];
+    const double ti = rc[3];
+    w0 = a0 * ti; w1 = a1 * ti; w2 = a2 * ti;
+    const double wx0 = w1 * X2 - w2 * X1, wx1 = w2 * X0 - w0 * X2, wx2 = w0 * X1 - w1 * X0;
+    const double wdx = w0 * X0 + w1 * X1 + w2 * X2;
+    omc = 1.0 - c;
+    const double tmp = wdx * omc;
+    p0 = X0 * c + wx0 * s + w0 * tmp;
+    p1 = X1 * c + wx1 * s + w1 * tmp;
+    p2 = X2 * c + wx2 * s + w2 * tmp;
+    const double swdx = s * wdx, k2 = 2.0 * tmp;
+    const double v0 = (c * wx0 - s * X0 + swdx * w0) - ti * (s * wx0 + k2 * w0);
+    const double v1 = (c * wx1 - s * X1 + swdx * w1) - ti * (s * wx1 + k2 * w1);
+    const double v2 = (c * wx2 - s * X2 + swdx * w2) - ti * (s * wx2 + k2 * w2);
+    const double wda = w0 * da0 + w1 * da1 + w2 * da2;
+    const double xda = X0 * da0 + X1 * da1 + X2 * da2;
+    dp0 = v0 * wda + ti * (s * cx0 + omc * (xda * w0 + wdx * da0)) + dt0;
+    dp1 = v1 * wda + ti * (s * cx1 + omc * (xda * w1 + wdx * da1)) + dt1;
+    dp2 = v2 * wda + ti * (s * cx2 + omc * (xda * w2 + wdx * da2)) + dt2;
+  } else {
+    p0 = X0 + (a1 * X2 - a2 * X1);
+    p1 = X1 + (a2 * X0 - a0 * X2);
+    p2 = X2 + (a0 * X1 - a1 * X0);
+    dp0 = cx0 + dt0; dp1 = cx1 + dt1; dp2 = cx2 + dt2;
+    w0 = a0; w1 = a1; w2 = a2; s = 1.0; c = 1.0; omc = 0.0;
+  }
+  p0 += pose[3]; p1 += pose[4]; p2 += pose[5];
+  const double iz = 1.0 / p2;
+  const double xp = p0 * iz, yp = p1 * iz;
+  const double f = cm[0], l1 = cm[1], l2 = cm[2];
+  const double r2 = xp * xp + yp * yp;
+  const double dist = 1.0 + r2 * (l1 + l2 * r2);
+  const double ru = weight * (f * dist * xp - ox);
+  const double rv = weight * (f * dist * yp - oy);
+  double rho0, rho1;
+  msfm_huber(huber, ru * ru + rv * rv, rho0, rho1);
+  const double sq = sqrt(rho1);
+  r0 = sq * ru; r1 = sq * rv;
+  const double dd = l1 + 2.0 * l2 * r2;
+  const double uxp = f * (dist + 2.0 * xp * xp * dd), uyp = f * 2.0 * xp * yp * dd, vyp = f * (dist + 2.0 * yp * yp * dd);
+  const double dxp = (dp0 - xp * dp2) * iz, dyp = (dp1 - yp * dp2) * iz;
+  const double m = dist * df + f * r2 * (dl1 + r2 * dl2);
+  const double ws = weight * sq;
+  q0 = ws * (uxp * dxp + uyp * dyp + xp * m);
+  q1 = ws * (uyp * dxp + vyp * dyp + yp * m);
+  const double wi = ws * iz;
+  const double g[2][3] = {{uxp * wi, uyp * wi, -(uxp * xp + uyp * yp) * wi}, {uyp * wi, vyp * wi, -(uyp * xp + vyp * yp) * wi}};
+#pragma unroll
+  for (int k = 0; k < 2; k++) {
+    const double g0 = g[k][0], g1 = g[k][1], g2 = g[k][2];
+    const double gw = omc * (g0 * w0 + g1 * w1 + g2 * w2);
+    jp[3 * k + 0] = sp[0] * (c * g0 + s * (g1 * w2 - g2 * w1) + gw * w0);
+    jp[3 * k + 1] = sp[1] * (c * g1 + s * (g2 * w0 - g0 * w2) + gw * w1);
+    jp[3 * k + 2] = sp[2] * (c * g2 + s * (g0 * w1 - g1 * w0) + gw * w2);
   }
 }
 
