@@ -718,6 +718,64 @@ int msfm_pair_set_fetch(const msfm_pair_set* set, int32_t* n_init, int32_t* n_in
 void msfm_pair_set_destroy(msfm_pair_set* set);
 
 /* ======================================================================================
+ *  The visual word of every feature: the vocabulary-tree descent
+ * ====================================================================================== */
+/* Database::BuildWords / GenerateWordsForImage (SfM/src/database.cc:745-867): one voc_.transform(descriptors, words_id) per
+ * image, the `fBow _transform(features, word_ids)` overload of fbow::Vocabulary (SfM/thirdparty/fbow/include/fbow/fbow.h:417-452),
+ * here for all images of a descriptor set at once, on the float32 rows the set holds.  The tree is the reference's: blocks of
+ * up to k nodes (fbow.h:155-187), a node a 128-float descriptor, id_or_childblock (msb set: a leaf and its word id; else the
+ * block of its children, fbow.h:129-137) and a weight.  Per feature:
+ *   descent     start at block 0.  In the current block the nodes 0 .. N-1 are tried in order with best = 4294967296.0f
+ *               (numeric_limits<uint32_t>::max() as a float); a node wins on d < best: strict, so a tie stays with the lower
+ *               node and a NaN distance never wins.  A winning leaf gives word_id = its id and adds its weight to the image's
+ *               bag; a winning inner node continues in its block, except that a link to block 0 ends the walk
+ *               (`while (!leaf && id != 0)`, :449): such a feature keeps word id -1 and adds nothing.
+ *   distance    L2_avx_generic (fbow.h:247-261): eight binary32 partial sums, element i into partial i % 8 in ascending i, as
+ *               a separate subtract, multiply and add (no fused multiply-add), then ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)).
+ *               UNPINNED: which computeDist a reference build picks is decided in fbow's .cpp, which this project has never
+ *               seen, and so is that build's floating-point mode; this is the form an x64 AVX build takes for 512-byte float
+ *               descriptors.  The SSE and generic forms are not built.
+ *   bag         fBow is a std::map<uint32_t, float>: per image the distinct words ascending, each with the binary32 sum of its
+ *               features' leaf weights in feature order, from 0.0f.
+ *   images      only an image with count > min_features gets words (database.cc:798: 300, strict); the others have
+ *               has_words = 0, word id -1 on every feature, an empty bag - what msfm_wordset_create understands.
+ *   maxima      image_max_id[i] = max(0, largest word id of image i) (:864-866); Database::max_words_id_ after image i is the
+ *               running maximum of these in image order (what the `<i>_words` file records), and the last one is num_words,
+ *               the num_words of msfm_wordset_create.
+ *   DEPARTURE   when no node of a block wins (every distance >= 2^32 or NaN) the reference goes on with whatever index the
+ *               block before, or the feature before, left in best_dist_idx.second.  Here such a feature gets word id -1, adds
+ *               nothing to the bag and is counted in n_unassigned, as are the features the `id != 0` rule stops (counted for
+ *               images with words only).  For finite descriptors with |value| < 2896 the case cannot arise.
+ * msfm_voctree_create uploads the tree once (node_desc [n_blocks][k][128], node_link and node_weight [n_blocks][k], rows past
+ * block_n[b] ignored) and stores the descriptors in the order the kernel reads them.  The tree is walked from block 0 on the
+ * host first.  MSFM_E_INVAL, the context stays usable: a NULL pointer, k outside [2, 64], block_n[b] > k, a reached block with
+ * no node, a child block >= n_blocks, a block reached twice or more than 32 blocks deep (the reference would not come back
+ * from a cycle).  msfm_voctree_size: depth = blocks on the longest path, n_leaves = leaf nodes of the reached blocks.
+ * msfm_descset_words: word ids, per-feature leaf weights, bags and maxima stay on the device inside the result; the host
+ * waits once, for the bag sizes.  The result is a copy - it stays readable when the set changes - and remembers the set's
+ * generation.  msfm_word_result_fetch (every pointer may be NULL): feat_off [n + 1], has_words [n], word_id [n_features],
+ * image_max_id [n], bow_off [n + 1], bow_word / bow_weight [n_bow] (image i's bag is bow_off[i] .. bow_off[i + 1]).
+ * msfm_wordset_create_from_words builds the set of msfm_wordset_create device to device: word ids and num_words from the result,
+ * keypoints from the set's msfm_descset_upload_keypoints; array for array the set msfm_wordset_create makes of the fetched ids
+ * and the same keypoints; msfm_wordset_size reports the few bytes it sends.  MSFM_E_INVAL: an image with words but no
+ * keypoints, a result older than the set's last descriptor upload, n_unassigned > 0 (the reference would index its inverted
+ * file at -1), n_images < 2, max_hypotheses out of range.  Trees, results and sets count as children of their context. */
+typedef struct msfm_voctree msfm_voctree;
+int msfm_voctree_create(msfm_ctx* ctx, int k, int n_blocks, const uint16_t* block_n /*[n_blocks]*/,
+                        const float* node_desc /*[n_blocks][k][128]*/, const uint32_t* node_link /*[n_blocks][k]*/,
+                        const float* node_weight /*[n_blocks][k]*/, msfm_voctree** out);
+int msfm_voctree_size(const msfm_voctree* tree, int* k, int* n_blocks, int* depth, int64_t* n_leaves, int64_t* h2d_bytes);
+void msfm_voctree_destroy(msfm_voctree* tree);
+typedef struct msfm_word_result msfm_word_result;
+int msfm_descset_words(msfm_descset* set, const msfm_voctree* tree, int min_features /* 300 */, msfm_word_result** out);
+int msfm_word_result_size(const msfm_word_result* res, int* n_images, int64_t* n_features, int64_t* n_bow, int* num_words,
+                          int64_t* n_unassigned);
+int msfm_word_result_fetch(const msfm_word_result* res, int32_t* feat_off, uint8_t* has_words, int32_t* word_id, int32_t* image_max_id,
+                           int32_t* bow_off, int32_t* bow_word, float* bow_weight);
+void msfm_word_result_destroy(msfm_word_result* res);
+int msfm_wordset_create_from_words(msfm_descset* set, const msfm_word_result* res, int max_hypotheses, msfm_wordset** out);
+
+/* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search
  * ====================================================================================== */
 /* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference

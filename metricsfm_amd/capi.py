@@ -42,6 +42,8 @@ SYMBOLS = [
     "msfm_epipolar_filter", "msfm_fransac_default_options", "msfm_fundamental_ransac_batch",
     "msfm_pair_select_default_options", "msfm_wordset_create", "msfm_wordset_size", "msfm_wordset_fetch", "msfm_wordset_destroy",
     "msfm_pair_select", "msfm_pair_set_size", "msfm_pair_set_fetch", "msfm_pair_set_destroy",
+    "msfm_voctree_create", "msfm_voctree_size", "msfm_voctree_destroy", "msfm_descset_words", "msfm_word_result_size",
+    "msfm_word_result_fetch", "msfm_word_result_destroy", "msfm_wordset_create_from_words",
     "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
     "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
     "msfm_epnp_ransac_batch", "msfm_epnpf_default_options", "msfm_epnpf_num_steps", "msfm_epnpf_sweep_batch",
@@ -223,6 +225,16 @@ def lib():
     L.msfm_wordset_destroy.argtypes = [vp]
     L.msfm_wordset_destroy.restype = None
     L.msfm_pair_select.argtypes = [vp, i, i, C.POINTER(A.PairSelectOptions), C.POINTER(vp)]
+    L.msfm_voctree_create.argtypes = [vp, i, i, C.POINTER(C.c_uint16), A.c_float_p, C.POINTER(C.c_uint32), A.c_float_p, C.POINTER(vp)]
+    L.msfm_voctree_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, i64p, i64p]
+    L.msfm_voctree_destroy.argtypes = [vp]
+    L.msfm_voctree_destroy.restype = None
+    L.msfm_descset_words.argtypes = [vp, vp, i, C.POINTER(vp)]
+    L.msfm_word_result_size.argtypes = [vp, A.c_int_p, i64p, i64p, A.c_int_p, i64p]
+    L.msfm_word_result_fetch.argtypes = [vp, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_float_p]
+    L.msfm_word_result_destroy.argtypes = [vp]
+    L.msfm_word_result_destroy.restype = None
+    L.msfm_wordset_create_from_words.argtypes = [vp, vp, i, C.POINTER(vp)]
     L.msfm_pair_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, i64p]
     L.msfm_pair_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_double_p, A.c_int_p, A.c_int_p, A.c_u8_p]
     L.msfm_pair_set_destroy.argtypes = [vp]
@@ -667,6 +679,10 @@ class Context:
         words: per image the word id of every feature, or None / empty for an image without words (`<i>_words` empty)."""
         return Wordset(self, n_features, words, num_words, keypoints, max_hypotheses)
 
+    def voctree(self, k, block_n, node_desc, node_link, node_weight):
+        """msfm_voctree_create: a vocabulary tree (featurefiles.read_voctree) resident as a `VocTree`."""
+        return VocTree(self, k, block_n, node_desc, node_link, node_weight)
+
     def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
         """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
         as a `Recon`; cam_pose / cam_model / cam_model_of_cam are the solver's parameter blocks as `adjust.adjust_round` takes
@@ -1054,6 +1070,11 @@ class DescSet:
         """msfm_match_pairs_slam (slam_gps.cc:455-503): ratio test `> th`, then the prior F / H gates; F, H [n_pairs][3][3]."""
         return MatchResult(self, pairs, None, None, keep_knn, slam=(F, H, opts))
 
+    def words(self, tree, min_features=300):
+        """msfm_descset_words (Database::BuildWords): the word of every feature of every image with more than min_features
+        features, as a `WordResult`."""
+        return WordResult(self, tree, min_features)
+
     def close(self):
         if self._h:
             lib().msfm_descset_destroy(self._h)
@@ -1316,6 +1337,17 @@ class Wordset:
             raise ValueError("keypoints must hold one row per feature of every image")
         ctx.check(lib().msfm_wordset_create(ctx._h, len(nf), A.ptr(nf, A.c_int_p), A.ptr(has, A.c_u8_p), A.ptr(flat, A.c_int_p), int(num_words),
                                             A.ptr(kp, A.c_float_p), int(max_hypotheses), C.byref(self._h)))
+        self._read_size()
+
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        """A set the library made by another route (msfm_wordset_create_from_words)."""
+        ws = cls.__new__(cls)
+        ws.ctx, ws._h = ctx, handle
+        ws._read_size()
+        return ws
+
+    def _read_size(self):
         n, k, ni, nm, nb = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
         lib().msfm_wordset_size(self._h, C.byref(n), C.byref(k), C.byref(ni), C.byref(nm), C.byref(nb))
         self.n_images, self.n_hypotheses, self.n_inverted, self.n_mapped, self.h2d_bytes = n.value, k.value, ni.value, nm.value, nb.value
@@ -1360,6 +1392,85 @@ class Wordset:
     def close(self):
         if self._h:
             lib().msfm_wordset_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VocTree:
+    """msfm_voctree: a vocabulary tree resident on the device (include/msfm.h).  block_n [n_blocks], node_desc [n_blocks][k][128],
+    node_link / node_weight [n_blocks][k]: what featurefiles.read_voctree returns."""
+
+    def __init__(self, ctx: Context, k, block_n, node_desc, node_link, node_weight):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        bn = A.as_c(np.asarray(block_n).reshape(-1), np.uint16)
+        nb = len(bn)
+        nd = A.as_c(np.asarray(node_desc, dtype=np.float32).reshape(nb, int(k), 128), np.float32)
+        nl = A.as_c(np.asarray(node_link).reshape(nb, int(k)), np.uint32)
+        nw = A.as_c(np.asarray(node_weight, dtype=np.float32).reshape(nb, int(k)), np.float32)
+        ctx.check(lib().msfm_voctree_create(ctx._h, int(k), nb, A.ptr(bn, C.POINTER(C.c_uint16)), A.ptr(nd, A.c_float_p),
+                                            A.ptr(nl, C.POINTER(C.c_uint32)), A.ptr(nw, A.c_float_p), C.byref(self._h)))
+
+    def size(self):
+        """-> dict(k, n_blocks, depth, n_leaves, h2d_bytes)."""
+        k, nb, d, nl, hb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        lib().msfm_voctree_size(self._h, C.byref(k), C.byref(nb), C.byref(d), C.byref(nl), C.byref(hb))
+        return dict(k=k.value, n_blocks=nb.value, depth=d.value, n_leaves=nl.value, h2d_bytes=hb.value)
+
+    def close(self):
+        if self._h:
+            lib().msfm_voctree_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WordResult:
+    """msfm_word_result: the word of every feature of a descriptor set, its bags of words and maxima, on the device."""
+
+    def __init__(self, ds, tree: VocTree, min_features=300):
+        self.ctx, self.ds = ds.ctx, ds
+        self._h = C.c_void_p()
+        self.ctx.check(lib().msfm_descset_words(ds._h, tree._h, int(min_features), C.byref(self._h)))
+
+    def size(self):
+        """-> dict(n_images, n_features, n_bow, num_words, n_unassigned)."""
+        n, nf, nb, nw, nu = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int32(), C.c_int64()
+        lib().msfm_word_result_size(self._h, C.byref(n), C.byref(nf), C.byref(nb), C.byref(nw), C.byref(nu))
+        return dict(n_images=n.value, n_features=nf.value, n_bow=nb.value, num_words=nw.value, n_unassigned=nu.value)
+
+    def fetch(self):
+        """msfm_word_result_fetch: dict of feat_off [n + 1], has_words [n], word_id [n_features], image_max_id [n], bow_off [n + 1],
+        bow_word / bow_weight [n_bow]."""
+        z = self.size()
+        n, nf, nb = z["n_images"], z["n_features"], z["n_bow"]
+        fo, hw, wid = np.zeros(n + 1, np.int32), np.zeros(n, np.uint8), np.zeros(max(1, nf), np.int32)
+        mx, bo = np.zeros(n, np.int32), np.zeros(n + 1, np.int32)
+        bw, bf = np.zeros(max(1, nb), np.int32), np.zeros(max(1, nb), np.float32)
+        ip = A.c_int_p
+        self.ctx.check(lib().msfm_word_result_fetch(self._h, A.ptr(fo, ip), A.ptr(hw, A.c_u8_p), A.ptr(wid, ip), A.ptr(mx, ip), A.ptr(bo, ip),
+                                                    A.ptr(bw, ip), A.ptr(bf, A.c_float_p)))
+        return {"feat_off": fo, "has_words": hw, "word_id": wid[:nf], "image_max_id": mx, "bow_off": bo, "bow_word": bw[:nb],
+                "bow_weight": bf[:nb]}
+
+    def wordset(self, max_hypotheses=0):
+        """msfm_wordset_create_from_words: the `Wordset` of these words and the descriptor set's resident keypoints."""
+        h = C.c_void_p()
+        self.ctx.check(lib().msfm_wordset_create_from_words(self.ds._h, self._h, int(max_hypotheses), C.byref(h)))
+        return Wordset._adopt(self.ctx, h)
+
+    def close(self):
+        if self._h:
+            lib().msfm_word_result_destroy(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):

@@ -534,6 +534,24 @@ void newpoints_collect(const NewPointsArgs& P, const NewPointsPlan& L, const New
 int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_off, const int* d_nf, const int* d_fo, int n_pairs,
                      const int* d_pair, const int* d_moff, const int* d_match, int M, msfm_track_dev* out);
 
+// ---- the visual words (words.hip): msfm_descset_words reads the set's resident rows, msfm_wordset_create_from_words hands word
+// ids and keypoints to pairsel.hip's core without leaving the device ----
+struct msfm_descset;
+struct DescView {   // what words.hip needs of a descriptor set (defined in knn.hip)
+  msfm_ctx* ctx;
+  int n_images;
+  unsigned long generation;
+  std::vector<int> count;          // features per image
+  std::vector<const float*> f32;   // device [count][128] per image, nullptr: nothing uploaded
+  std::vector<const float*> kp;    // device [count][2] per image, nullptr: no keypoints
+};
+void descset_view(const msfm_descset* s, DescView* out);
+// msfm_wordset_create is its checks + the upload of the four arrays + this core.  feat_off [n + 1] on the host and on the device;
+// d_feat_off and d_kp move into the set, d_hw [n] and d_word [feat_off[n]] are read only and may be freed on return (the core
+// waits for the stream before it returns, also when it fails).  h2d_bytes: what the caller sent, kept for msfm_wordset_size.
+int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::vector<int>& feat_off, DevBuf<int>& d_feat_off, const uint8_t* d_hw,
+                       const int* d_word, DevBuf<float>& d_kp, int64_t h2d_bytes, msfm_wordset** out);
+
 // Elimination structure of the reduced system (chol.hip): a nested-dissection tree of the camera graph laid out level
 // by level.  Level 0 holds the leaf domains, level 1 the deepest separators, ... ; the nodes of one level are mutually
 // uncoupled (their panel chains share launches), each is 64-aligned (identity padding inside) and couples only to its own

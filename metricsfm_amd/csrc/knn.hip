@@ -1420,6 +1420,16 @@ MSFM_API int msfm_descset_upload_keypoints(msfm_descset* s, int image, const flo
   return MSFM_OK;
 }
 
+void descset_view(const msfm_descset* s, DescView* v) {
+  v->ctx = s->ctx; v->n_images = s->n_images; v->generation = s->generation;
+  v->count = s->count;
+  v->f32.assign(s->n_images, nullptr); v->kp.assign(s->n_images, nullptr);
+  for (int i = 0; i < s->n_images; i++) {
+    if (s->f32[i] && s->count[i] > 0) v->f32[i] = s->f32[i]->p;
+    if (s->kp[i]) v->kp[i] = s->kp[i]->p;   // (an image of no features: a DevBuf with a null block)
+  }
+}
+
 int match_result_view(msfm_match_result* R, MatchView* v) {
   if (!R || !v) return MSFM_E_INVAL;
   MSFM_TRY(check_generation(R));

@@ -3,7 +3,9 @@
 //   SimilarityGraph::SimilarityGraphInvFile         SfM/src/graph/similarity_graph.cc:47-117
 // from the word id of every feature (include/msfm.h states the semantics, quirks included).
 //
-// msfm_wordset_create, once per image set, everything resident afterwards:
+// msfm_wordset_create, once per image set, everything resident afterwards.  It is its checks, the upload of the four arrays and
+// wordset_create_dev, the device-array core that msfm_wordset_create_from_words (words.hip) calls on word ids and keypoints that
+// never left the device; k_heads / k_put_heads / k_map_off live in runs_device.h, which words.hip includes too:
 //   k_keys        one thread per feature: key (image << 32 | word), value = the feature index; one stable rocPRIM radix sort, so
 //                 the features of a group (a run of equal keys) stay ascending
 //   k_heads / k_put_heads   group heads by flag + scan + scatter (the group count stays on the device); k_groups marks per group
@@ -29,6 +31,7 @@
 
 #include "common.h"
 #include "pairsel_args.h"
+#include "runs_device.h"
 
 struct msfm_wordset {
   msfm_ctx* ctx = nullptr;
@@ -51,7 +54,7 @@ struct msfm_pair_set {   // host memory only
 
 namespace pairsel {
 
-typedef unsigned long long u64;
+using namespace runs;   // u64, k_heads, k_put_heads, k_map_off
 #define PS_RANK_LDS 2048   // images whose ranking keys (8 bytes each, padded to a power of two) k_rank_lds sorts in LDS
 #define PS_SHORT_BIN 16    // images of a bin that one lane group of k_sim_short pairs up
 
@@ -62,21 +65,6 @@ __global__ __launch_bounds__(256) void k_keys(int total, int n, const int* __res
   const int img = csr_segment_of(feat_off, n, e);
   key[e] = ((u64)img << 32) | (unsigned)word_id[e];
   val[e] = e - feat_off[img];
-}
-
-// flag[e] = 1 where (key >> shift) differs from its predecessor's, e < cnt; flag[cnt] = 0 closes the scan
-__global__ __launch_bounds__(256) void k_heads(int cnt, const u64* __restrict__ key, int shift, int* __restrict__ flag) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e > cnt) return;
-  flag[e] = (e < cnt && (e == 0 || (key[e] >> shift) != (key[e - 1] >> shift))) ? 1 : 0;
-}
-
-// start[g] = first element of run g; start[G] = cnt, G = pos[cnt]
-__global__ __launch_bounds__(256) void k_put_heads(int cnt, const int* __restrict__ flag, const int* __restrict__ pos, int* __restrict__ start) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e > cnt) return;
-  if (e == cnt) start[pos[cnt]] = cnt;
-  else if (flag[e]) start[pos[e]] = e;
 }
 
 // per group: does it enter the inverted file, does it enter the word table (0 for g in [G, cap])
@@ -117,18 +105,6 @@ __global__ __launch_bounds__(256) void k_emit(int cap, const int* __restrict__ G
     const int t = p_tab[g];
     tab_img[t] = img; tab_word[t] = word; tab_feat[t] = val[b];   // the sort is stable: the lowest feature of the group
   }
-}
-
-// map_off[i] = entries of images below i
-__global__ __launch_bounds__(256) void k_map_off(int n, int T, const int* __restrict__ tab_img, int* __restrict__ map_off) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i > n) return;
-  int lo = 0, hi = T;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (tab_img[mid] < i) lo = mid + 1; else hi = mid;
-  }
-  map_off[i] = lo;
 }
 
 __device__ static inline void sim_add(int* __restrict__ S, int n, int a, int b) {
@@ -299,21 +275,6 @@ __global__ __launch_bounds__(1024) void k_gate(int H, int first, int Ks, int K, 
 
 #define PS_TRY(e) HIP_TRY(ctx, (e))
 
-// rocPRIM's scratch is allocated once per call, before the first launch that uses it: a block given back while the stream still
-// runs would go to the next taker of the cache.  ps_scan_tmp sizes it for the longest scan of the call.
-static hipError_t ps_scan_tmp(DevBuf<char>& tmp, size_t n_max, hipStream_t s) {
-  size_t bytes = 0;
-  const hipError_t e = rocprim::exclusive_scan(nullptr, bytes, (const int*)nullptr, (int*)nullptr, 0, n_max, rocprim::plus<int>(), s);
-  return e != hipSuccess ? e : tmp.alloc(std::max<size_t>(1, bytes));
-}
-static hipError_t ps_scan(DevBuf<char>& tmp, const int* in, int* out, size_t n, hipStream_t s) {
-  size_t bytes = 0;
-  const hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-  if (e != hipSuccess) return e;
-  if (bytes > tmp.n) return hipErrorOutOfMemory;
-  return rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-}
-
 MSFM_API void msfm_pair_select_default_options(msfm_pair_select_options* o) {
   if (!o) return;
   o->th_init_matches = 30;
@@ -333,25 +294,37 @@ MSFM_API int msfm_wordset_create(msfm_ctx* ctx, int n, const int* n_features, co
   long total_l = 0;
   const std::string bad = pairsel_check_create(n, n_features, has_words, word_id, num_words, keypoints, max_hypotheses, &K, &total_l);
   if (!bad.empty()) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %s", who, bad.c_str());
-  const int total = (int)total_l;
+  const size_t total = (size_t)total_l;
+  std::vector<int> feat_off(n + 1, 0);
+  for (int i = 0; i < n; i++) feat_off[i + 1] = feat_off[i] + n_features[i];
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevBuf<int> d_feat_off, d_word;
+  DevBuf<float> d_kp;
+  DevBuf<uint8_t> d_hw;
+  DevScope sc(ctx);
+  PS_TRY(sc.up(d_feat_off, feat_off)); PS_TRY(sc.up(d_hw, has_words, (size_t)n)); PS_TRY(sc.up(d_word, word_id, total));
+  PS_TRY(sc.up(d_kp, keypoints, 2 * total));
+  MSFM_TRY(wordset_create_dev(ctx, n, K, num_words, feat_off, d_feat_off, d_hw.p, d_word.p, d_kp, sc.h2d, out));
+  sc.dismiss();   // behind the core's finish()
+  return MSFM_OK;
+}
+
+int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::vector<int>& feat_off, DevBuf<int>& d_feat_off, const uint8_t* d_hw,
+                       const int* d_word, DevBuf<float>& d_kp, int64_t h2d_bytes, msfm_wordset** out) {
+  using namespace pairsel;
+  const int total = feat_off[n];
   std::unique_ptr<msfm_wordset> W(new msfm_wordset());
   W->ctx = ctx; W->n = n; W->K = K; W->num_words = num_words;
-  W->feat_off.assign(n + 1, 0);
-  for (int i = 0; i < n; i++) W->feat_off[i + 1] = W->feat_off[i] + n_features[i];
+  W->feat_off = feat_off;
   W->map_off.assign(n + 1, 0);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t cap = (size_t)total + 1;   // runs of a sorted array of `total` keys, plus the closing entry
-  DevBuf<int> d_feat_off, d_map_off, d_map_word, d_map_feat, d_S, d_hyp_img, d_hyp_sim;
-  DevBuf<float> d_kp;
-  DevBuf<int> d_word, d_val, d_val_s, d_flag, d_pos, d_start, d_finv, d_pinv, d_ftab, d_ptab, d_tab_img, d_seg;
+  DevBuf<int> d_map_off, d_map_word, d_map_feat, d_S, d_hyp_img, d_hyp_sim;
+  DevBuf<int> d_val, d_val_s, d_flag, d_pos, d_start, d_finv, d_pinv, d_ftab, d_ptab, d_tab_img, d_seg;
   DevBuf<u64> d_key, d_key_s, d_inv, d_inv_s, d_rk, d_rk_s;
-  DevBuf<uint8_t> d_hw;
   DevBuf<char> tmp, tmp_words, tmp_bins, tmp_rank;
   DevScope sc(ctx);
   PS_TRY(ps_scan_tmp(tmp, cap, s));
-  PS_TRY(sc.up(d_feat_off, W->feat_off)); PS_TRY(sc.up(d_hw, has_words, (size_t)n)); PS_TRY(sc.up(d_word, word_id, (size_t)total));
-  PS_TRY(sc.up(d_kp, keypoints, 2 * (size_t)total));
   PS_TRY(d_key.alloc(cap)); PS_TRY(d_key_s.alloc(cap)); PS_TRY(d_val.alloc(cap)); PS_TRY(d_val_s.alloc(cap));
   PS_TRY(d_flag.alloc(cap)); PS_TRY(d_pos.alloc(cap)); PS_TRY(d_start.alloc(cap + 1));
   PS_TRY(d_finv.alloc(cap)); PS_TRY(d_pinv.alloc(cap)); PS_TRY(d_ftab.alloc(cap)); PS_TRY(d_ptab.alloc(cap));
@@ -365,7 +338,7 @@ MSFM_API int msfm_wordset_create(msfm_ctx* ctx, int n, const int* n_features, co
   if (total) {
     {
       KTimer t(ctx, "pairsel_keys");
-      hipLaunchKernelGGL(k_keys, dim3(cdiv(total, 256)), dim3(256), 0, s, total, n, d_feat_off.p, d_word.p, d_key.p, d_val.p);
+      hipLaunchKernelGGL(k_keys, dim3(cdiv(total, 256)), dim3(256), 0, s, total, n, d_feat_off.p, d_word, d_key.p, d_val.p);
     }
     {
       const unsigned end_bit = 32u + (unsigned)bits_for((unsigned)(n - 1));
@@ -380,7 +353,7 @@ MSFM_API int msfm_wordset_create(msfm_ctx* ctx, int n, const int* n_features, co
       hipLaunchKernelGGL(k_heads, dim3(gcap), dim3(256), 0, s, total, d_key_s.p, 0, d_flag.p);
       PS_TRY(ps_scan(tmp, d_flag.p, d_pos.p, cap, s));
       hipLaunchKernelGGL(k_put_heads, dim3(gcap), dim3(256), 0, s, total, d_flag.p, d_pos.p, d_start.p);
-      hipLaunchKernelGGL(k_groups, dim3(gcap), dim3(256), 0, s, total, d_G, d_start.p, d_key_s.p, d_hw.p, d_finv.p, d_ftab.p);
+      hipLaunchKernelGGL(k_groups, dim3(gcap), dim3(256), 0, s, total, d_G, d_start.p, d_key_s.p, d_hw, d_finv.p, d_ftab.p);
       PS_TRY(ps_scan(tmp, d_finv.p, d_pinv.p, cap, s));
       PS_TRY(ps_scan(tmp, d_ftab.p, d_ptab.p, cap, s));
       hipLaunchKernelGGL(k_emit, dim3(gcap), dim3(256), 0, s, total, d_G, d_start.p, d_key_s.p, d_val_s.p, d_finv.p, d_pinv.p, d_ftab.p, d_ptab.p,
@@ -432,7 +405,7 @@ MSFM_API int msfm_wordset_create(msfm_ctx* ctx, int n, const int* n_features, co
   PS_TRY(hipGetLastError());
   PS_TRY(sc.down(W->map_off.data(), d_map_off.p, (size_t)n + 1));
   PS_TRY(sc.finish());
-  W->h2d_bytes = sc.h2d;
+  W->h2d_bytes = h2d_bytes;
   W->d_feat_off.swap(d_feat_off); W->d_map_off.swap(d_map_off); W->d_map_word.swap(d_map_word); W->d_map_feat.swap(d_map_feat);
   W->d_kp.swap(d_kp); W->d_S.swap(d_S); W->d_hyp_img.swap(d_hyp_img); W->d_hyp_sim.swap(d_hyp_sim);
   ctx->children++;

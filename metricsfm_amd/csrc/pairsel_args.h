@@ -24,12 +24,12 @@ static inline std::string pairsel_fmt(const char* fmt, long a = 0, long b = 0, l
   return buf;
 }
 
-// msfm_wordset_create: *K = hypotheses per image, *total = features of all images
-static inline std::string pairsel_check_create(int n_images, const int* n_features, const uint8_t* has_words, const int32_t* word_id, int num_words,
-                                               const float* keypoints, int max_hypotheses, int* K, long* total) {
+// What msfm_wordset_create and msfm_wordset_create_from_words (whose word ids never visit the host) check alike: the counts.
+// *K = hypotheses per image, *total = features of all images
+static inline std::string pairsel_check_counts(int n_images, const int* n_features, int num_words, int max_hypotheses, int* K, long* total) {
   if (n_images < 2) return pairsel_fmt("n_images = %ld: at least 2 images", n_images);
   if (n_images > PAIRSEL_MAX_IMAGES) return pairsel_fmt("n_images = %ld above %ld", n_images, PAIRSEL_MAX_IMAGES);
-  if (!n_features || !has_words) return "null argument";
+  if (!n_features) return "null argument";
   if (num_words < 0) return pairsel_fmt("num_words = %ld is negative", num_words);
   if (max_hypotheses < 0 || max_hypotheses > n_images - 1)
     return pairsel_fmt("max_hypotheses = %ld outside [0, n_images - 1 = %ld]", max_hypotheses, n_images - 1);
@@ -39,6 +39,18 @@ static inline std::string pairsel_check_create(int n_images, const int* n_featur
     t += n_features[i];
     if (t > 0x7fffffffL) return "more than 2^31 features";
   }
+  *K = max_hypotheses > 0 ? max_hypotheses : pairsel_rule_k(n_images);
+  *total = t;
+  return "";
+}
+
+// msfm_wordset_create: the counts, and every word id of an image with words
+static inline std::string pairsel_check_create(int n_images, const int* n_features, const uint8_t* has_words, const int32_t* word_id, int num_words,
+                                               const float* keypoints, int max_hypotheses, int* K, long* total) {
+  if (n_images >= 2 && n_images <= PAIRSEL_MAX_IMAGES && (!n_features || !has_words)) return "null argument";
+  long t = 0;
+  const std::string bad = pairsel_check_counts(n_images, n_features, num_words, max_hypotheses, K, &t);
+  if (!bad.empty()) return bad;
   if (t > 0 && (!word_id || !keypoints)) return "null argument";
   t = 0;
   for (int i = 0; i < n_images; i++) {

@@ -12,6 +12,8 @@ the reference's extraction stage can feed libmsfm and libmsfm's results can feed
   <output_fold>/<idx>_words     binary (Database::WriteoutWordsForImage / ReadinWordsForImage, database.cc:869-945): int32 count, int32[count]
       word ids and float32[count] weights of the image's bag of words, int32 max_words_id_, int32 num_pts, int32[num_pts] the word
       id of every feature.  An image without words is an EMPTY file (:911).
+  <output_fold>/voctree         binary (Database::WriteoutVocabularyTree / ReadinVocabularyTree, database.cc:679-735): fbow's params and its
+      block memory; the layout is spelled out above read_voctree / write_voctree below.
   sfm_openmvs.txt, temp_result  text: the OpenMVS hand-over (:1147-1245) and the reconstruction checkpoint (:1465-1749), below.
 Native little-endian, as the reference writes them with ofstream::write."""
 import os
@@ -102,6 +104,102 @@ def read_words(fold, idx):
         max_id, npts = struct.unpack("<ii", f.read(8))
         wid = np.fromfile(f, dtype=np.int32, count=npts)
     return ids, w, max_id, wid
+
+
+def write_all_words(fold, fetched):
+    """Every image's `<i>_words` from WordResult.fetch() (Database::BuildWords, database.cc:789-808): an image without words gets
+    the empty file; the others record Database::max_words_id_ as it stands after them, the running maximum of image_max_id in
+    image order from 0.  -> that running maximum per image [n]."""
+    fo, bo = fetched["feat_off"], fetched["bow_off"]
+    running, out = 0, []
+    for i in range(len(fetched["has_words"])):
+        if fetched["has_words"][i]:
+            running = max(running, int(fetched["image_max_id"][i]))
+            write_words(fold, i, fetched["bow_word"][bo[i]:bo[i + 1]], fetched["bow_weight"][bo[i]:bo[i + 1]], running,
+                        fetched["word_id"][fo[i]:fo[i + 1]])
+        else:
+            write_words(fold, i, None, None, running, None)
+        out.append(running)
+    return np.array(out, dtype=np.int32)
+
+
+# <output_fold>/voctree (Database::WriteoutVocabularyTree / ReadinVocabularyTree, database.cc:679-735): fbow's params without the
+# descriptor name, then its block memory.
+#   uint32 _aligment, uint32 _nblocks, uint64 _desc_size_bytes_wp, uint64 _block_size_bytes_wp, uint64 _feature_off_start,
+#   uint64 _child_off_start, uint64 _total_size, int32 _desc_type, int32 _desc_size, uint32 _m_k, then _total_size bytes.
+# Block b starts at b * _block_size_bytes_wp (fbow.h:155-193): uint16 N, uint16 isLeaf, uint32 parent block; descriptor i at
+# _feature_off_start + i * _desc_size_bytes_wp; block_node_info i = (uint32 id_or_childblock, float32 weight) at
+# _child_off_start + 8 i.  The offsets are read from the header, never assumed.
+_VOC_HEAD = "<IIQQQQQiiI"
+VOC_DIM = 128
+
+
+def _round_up(x, a):
+    return (x + a - 1) // a * a
+
+
+def voctree_layout(k, alignment=32, feature_off_start=None, desc_size_bytes_wp=None):
+    """A block layout for write_voctree: descriptors aligned to `alignment` behind the 8-byte block head, the node infos behind the
+    k descriptors, the block padded to the alignment.  (fbow's own setParams is in its .cpp, which this project has not seen;
+    any layout the header describes reads back the same.)"""
+    wp = _round_up(4 * VOC_DIM, alignment) if desc_size_bytes_wp is None else int(desc_size_bytes_wp)
+    fo = _round_up(8, alignment) if feature_off_start is None else int(feature_off_start)
+    co = fo + k * wp
+    return dict(alignment=alignment, desc_size_bytes_wp=wp, feature_off_start=fo, child_off_start=co,
+                block_size_bytes_wp=_round_up(co + 8 * k, alignment))
+
+
+def write_voctree(path, k, block_n, node_desc, node_link, node_weight, block_leaf=None, block_parent=None, layout=None):
+    """block_n [nb]; node_desc [nb][k][128] float32; node_link [nb][k] uint32 (id_or_childblock); node_weight [nb][k] float32;
+    block_leaf / block_parent [nb] (default 0); layout: voctree_layout(k, ...)."""
+    bn = np.asarray(block_n, dtype=np.uint16).reshape(-1)
+    nb, k = len(bn), int(k)
+    nd = np.ascontiguousarray(node_desc, dtype=np.float32).reshape(nb, k, VOC_DIM)
+    nl = np.asarray(node_link, dtype=np.uint32).reshape(nb, k)
+    nw = np.asarray(node_weight, dtype=np.float32).reshape(nb, k)
+    lay = voctree_layout(k) if layout is None else layout
+    wp, fo, co, bs = lay["desc_size_bytes_wp"], lay["feature_off_start"], lay["child_off_start"], lay["block_size_bytes_wp"]
+    if wp < 4 * VOC_DIM or fo < 8 or co < fo + k * wp or bs < co + 8 * k:
+        raise ValueError("the layout's parts overlap")
+    data = np.zeros((nb, bs), dtype=np.uint8)
+    data[:, 0:2] = bn.view(np.uint8).reshape(nb, 2)
+    data[:, 2:4] = np.zeros(nb, np.uint16).view(np.uint8).reshape(nb, 2) if block_leaf is None else \
+        np.asarray(block_leaf, dtype=np.uint16).reshape(nb).view(np.uint8).reshape(nb, 2)
+    data[:, 4:8] = np.zeros(nb, np.uint32).view(np.uint8).reshape(nb, 4) if block_parent is None else \
+        np.asarray(block_parent, dtype=np.uint32).reshape(nb).view(np.uint8).reshape(nb, 4)
+    for i in range(k):
+        data[:, fo + i * wp: fo + i * wp + 4 * VOC_DIM] = np.ascontiguousarray(nd[:, i]).view(np.uint8).reshape(nb, 4 * VOC_DIM)
+        data[:, co + 8 * i: co + 8 * i + 4] = np.ascontiguousarray(nl[:, i]).view(np.uint8).reshape(nb, 4)
+        data[:, co + 8 * i + 4: co + 8 * i + 8] = np.ascontiguousarray(nw[:, i]).view(np.uint8).reshape(nb, 4)
+    with open(path, "wb") as f:
+        f.write(struct.pack(_VOC_HEAD, lay["alignment"], nb, wp, bs, fo, co, nb * bs, CV_32F, 4 * VOC_DIM, k))
+        data.tofile(f)
+
+
+def read_voctree(path):
+    """-> dict(k, block_n [nb] uint16, node_desc [nb][k][128] float32, node_link [nb][k] uint32, node_weight [nb][k] float32,
+    block_leaf [nb] uint16, block_parent [nb] uint32, layout): the arguments of write_voctree and of Context.voctree."""
+    with open(path, "rb") as f:
+        head = f.read(struct.calcsize(_VOC_HEAD))
+        al, nb, wp, bs, fo, co, total, dtype, dsize, k = struct.unpack(_VOC_HEAD, head)
+        if dtype != CV_32F or dsize != 4 * VOC_DIM:
+            raise ValueError("voctree of descriptor type %d, %d bytes: only CV_32F, 512 bytes (SIFT)" % (dtype, dsize))
+        if total < nb * bs or wp < dsize or co + 8 * k > bs or fo + k * wp > bs:
+            raise ValueError("voctree header: the blocks do not fit")
+        data = np.fromfile(f, dtype=np.uint8, count=total)
+    if len(data) != total:
+        raise ValueError("voctree file is short")
+    data = data[:nb * bs].reshape(nb, bs)
+
+    def col(a, b, dt):
+        return np.ascontiguousarray(data[:, a:b]).view(dt)
+
+    nd = np.stack([col(fo + i * wp, fo + i * wp + dsize, np.float32) for i in range(k)], axis=1)
+    nl = np.concatenate([col(co + 8 * i, co + 8 * i + 4, np.uint32) for i in range(k)], axis=1)
+    nw = np.concatenate([col(co + 8 * i + 4, co + 8 * i + 8, np.float32) for i in range(k)], axis=1)
+    return dict(k=k, block_n=col(0, 2, np.uint16).reshape(nb), node_desc=nd, node_link=nl, node_weight=nw,
+                block_leaf=col(2, 4, np.uint16).reshape(nb), block_parent=col(4, 8, np.uint32).reshape(nb),
+                layout=dict(alignment=al, desc_size_bytes_wp=wp, feature_off_start=fo, child_off_start=co, block_size_bytes_wp=bs))
 
 
 def write_bundle_out(path, cam_fk, cam_R, cam_t, points, views):

@@ -5,7 +5,7 @@ The sampler index of a hypothesis is its position in the msfm_pair_select call, 
 pair sees: two runs agree bit for bit only with the same chunking."""
 import numpy as np
 
-from . import capi, matchfiles
+from . import capi, featurefiles, matchfiles
 
 
 def rule_k(n_images):
@@ -18,7 +18,29 @@ def select_pairs(ctx: capi.Context, n_features, words, num_words, keypoints, row
     every feature (None: the image has no words); keypoints: flat [sum of n_features][2].  opts: fields of
     msfm_pair_select_options / msfm_fransac_options.  record: dict of hyp_img, hyp_sim, n_init, n_inliers, verdict [n][K] and
     match_graph_init (per image the kept images).  With fold, similarity_graph.txt and init_match_graph.txt are written there."""
-    ws = ctx.wordset(n_features, words, num_words, keypoints, max_hypotheses)
+    return _select_chunks(ctx.wordset(n_features, words, num_words, keypoints, max_hypotheses), rows_per_call, fold, opts)
+
+
+def select_pairs_from_descriptors(ctx: capi.Context, descset, tree, rows_per_call=64, fold=None, min_features=300, max_hypotheses=0, **opts):
+    """select_pairs for a descriptor set whose keypoints are resident (DescSet.upload_keypoints) and a `VocTree`: the words are
+    computed on the device (DescSet.words, Database::BuildWords), the word set is built from them device to device
+    (WordResult.wordset), then the same chunk loop.  -> (pairs, record) as select_pairs; record also holds num_words and
+    n_unassigned.  With fold, every image's `<i>_words` file is written as well (featurefiles.write_all_words)."""
+    res = descset.words(tree, min_features)
+    try:
+        size = res.size()
+        if fold is not None:
+            featurefiles.write_all_words(fold, res.fetch())
+        ws = res.wordset(max_hypotheses)
+    finally:
+        res.close()
+    pairs, record = _select_chunks(ws, rows_per_call, fold, opts)
+    record.update(num_words=size["num_words"], n_unassigned=size["n_unassigned"])
+    return pairs, record
+
+
+def _select_chunks(ws, rows_per_call, fold, opts):
+    """The chunk loop over a `Wordset`, which it closes."""
     try:
         n = ws.n_images
         got = ws.fetch(similarity=fold is not None)
