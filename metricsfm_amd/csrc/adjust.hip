@@ -18,8 +18,8 @@
 // The call is three parts: round_tables (the checks that need no bulk array, the O(cameras) tables), round_adjust_dev (everything on
 // device arrays, written in place) and the export, which uploads the bulk arrays in front of the core and reads the points back
 // behind it.  recon.hip calls the first two on the arrays a msfm_recon keeps resident.
-// k_outliers is compiled without fused multiply-adds, + - * / sqrt only (the discipline of newpoints.hip and seed.hip):
-// tests/round_ref.py, a sequential restatement in doubles, agrees bit for bit.
+// k_outliers is Reprojection as point3d_device.h states it, compiled without fused multiply-adds, + - * / sqrt only (the
+// discipline of newpoints.hip and seed.hip): tests/round_ref.py, a sequential restatement in doubles, agrees bit for bit.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,6 +32,7 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "point3d_device.h"   // p3d_row_error, p3d_ordered_mse
 
 namespace adj {
 
@@ -170,31 +171,14 @@ __global__ __launch_bounds__(256) void k_outliers(int n_points, const int* __res
   const int p = blockIdx.x * 256 + threadIdx.x;
   int n_out = 0, n_new = 0, n_out_new = 0;
   if (p < n_points && !pt_bad[p]) {
-    const double X0 = point_xyz[3 * (size_t)p], X1 = point_xyz[3 * (size_t)p + 1], X2 = point_xyz[3 * (size_t)p + 2];
-    double m = 0.0;
-    int rows = 0;
-    bool behind = false;
-    for (int i = seg[p]; i < seg[p + 1]; i++) {
-      if (!first[i]) continue;
+    const double X[3] = {point_xyz[3 * (size_t)p], point_xyz[3 * (size_t)p + 1], point_xyz[3 * (size_t)p + 2]};
+    const double m = p3d_ordered_mse(seg[p], seg[p + 1], [&](int i) {
       const unsigned lo = (unsigned)key_s[i];
       const int c = cam_of_rank[lo >> bf], f = (int)(lo & ((1u << bf) - 1u));
       const double* R = cam + ADJ_CAM * (size_t)c;
-      const double* tt = R + 9;
-      const double* fk = R + 12;
-      const double pc0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + tt[0];
-      const double pc1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + tt[1];
-      const double pc2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + tt[2];
-      if (pc2 < 0) { behind = true; break; }   // (strict; a NaN walks on)
-      const double u0 = pc0 / pc2, v0 = pc1 / pc2;
-      const double r2 = u0 * u0 + v0 * v0;
-      const double distortion = 1.0 + r2 * (fk[1] + fk[2] * r2);
-      const double u = fk[0] * distortion * u0, v = fk[0] * distortion * v0;
       const size_t r = (size_t)kp_base[c] + f;
-      const double du = u - (double)kp[2 * r], dv = v - (double)kp[2 * r + 1];
-      m += du * du + dv * dv;
-      rows++;
-    }
-    m = behind ? 100000.0 : m / (double)rows;
+      return p3d_row_error(R, R + 9, R + 12, X, (double)kp[2 * r], (double)kp[2 * r + 1]);
+    }, [&](int i) { return first[i] != 0; });   // (std::map::insert kept one row per key)
     const int added = pt_new_added[p] ? 1 : 0;
     n_new = added;
     pt_mse[p] = m;

@@ -23,6 +23,7 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
+#include "point3d_device.h"   // p3d_camera_point, p3d_project
 
 namespace gpr {
 
@@ -51,18 +52,13 @@ __device__ static inline void slice_tracks(const int* __restrict__ off, int n_tr
 // (e itself is a sum of two squares: never negative).  std::pow(d, 2) is d * d.
 __device__ __forceinline__ double acc_row(const AccuracyPtrs& P, int i, double X0, double X1, double X2) {
   const int c = P.cam[i];
-  const double* R = P.R + 9 * (size_t)c;
-  const double* tt = P.t + 3 * (size_t)c;
-  const double* fk = P.fk + 3 * (size_t)c;
-  const double pc0 = R[0] * X0 + R[1] * X1 + R[2] * X2 + tt[0];
-  const double pc1 = R[3] * X0 + R[4] * X1 + R[5] * X2 + tt[1];
-  const double pc2 = R[6] * X0 + R[7] * X1 + R[8] * X2 + tt[2];
-  if (!(pc2 > 0)) return -1.0;
-  const double x = pc0 / pc2, y = pc1 / pc2;
-  const double r2 = x * x + y * y;
-  const double distortion = 1.0 + r2 * (fk[1] + fk[2] * r2);
+  const double X[3] = {X0, X1, X2};
+  double pc[3], uv[2];
+  p3d_camera_point(P.R + 9 * (size_t)c, P.t + 3 * (size_t)c, X, pc);
+  if (!(pc[2] > 0)) return -1.0;   // (not Reprojection's strict rule: a zero or NaN depth drops the row here)
+  p3d_project(P.fk + 3 * (size_t)c, pc, uv);
   const double dcx = P.dc ? P.dc[2 * (size_t)c] : 0.0, dcy = P.dc ? P.dc[2 * (size_t)c + 1] : 0.0;
-  const double u = fk[0] * distortion * x + dcx, v = fk[0] * distortion * y + dcy;
+  const double u = uv[0] + dcx, v = uv[1] + dcy;
   const double du = u - P.xy[2 * (size_t)i], dv = v - P.xy[2 * (size_t)i + 1];
   return du * du + dv * dv;
 }

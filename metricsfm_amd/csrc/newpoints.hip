@@ -34,7 +34,7 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "twoview_device.h"   // View, tri_two_views
+#include "point3d_device.h"   // View, tri_two_views
 
 namespace newpts {
 

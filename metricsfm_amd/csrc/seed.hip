@@ -10,9 +10,8 @@
 //               msfm_relpose_5pt_batch / msfm_relpose_8pt_batch, not copies of them
 //   k_camera    one thread per hypothesis: the focal rule (:324-332), c = -(R^T t) (:334), the fk rows of both cameras
 //   k_tri       one thread per match: Point3D::Trianglate2 for two views (structure.cc:211-265 with Reprojection :267-300 and
-//               SufficientTriangulationAngle :325-355) in the operation order of tri.hip's tri_midpoint_track / track_mse /
-//               track_angle_ok.  A workgroup lies inside one hypothesis (block map by binary search in n_hyp + 1 block
-//               offsets); its camera data is loaded once into LDS.
+//               SufficientTriangulationAngle :325-355): tri_two_views of point3d_device.h.  A workgroup lies inside one
+//               hypothesis (block map by binary search in n_hyp + 1 block offsets); its camera data is loaded once into LDS.
 //   k_compact   one workgroup per hypothesis walks its flags in chunks of 256 (wave ballot + the four wave counts): accepted
 //               points in match order, the count and the two gates (:380-381)
 // No host synchronisation between the stages: every size follows from the store's host-side match_off; one synchronisation
@@ -25,7 +24,7 @@
 #include "common.h"
 
 #pragma clang fp contract(off)
-#include "twoview_device.h"   // View, tri_two_views
+#include "point3d_device.h"   // View, tri_two_views
 
 struct msfm_seed_set {
   int n = 0, winner = -1;

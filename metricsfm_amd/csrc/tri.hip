@@ -2,55 +2,49 @@
 // Round 4: the midpoint triangulation and the reprojection run in two kinds of phases inside one workgroup of 64 tracks - what
 // belongs to ONE observation (its ray, its reprojection error, its ray for the angle gate: all the loads, divisions and square
 // roots) is computed with lane = observation from coalesced reads and parked in LDS; what the reference SUMS over a track's
-// observations in their order is then done by one thread per track from LDS.  Every number is formed by the same operations
-// in the same order as in the thread-per-track form (which remains: DLT, and workgroups whose observations do not fit the
-// LDS area), so results are unchanged; the kernel no longer waits for a chain of dependent loads per observation.
+// observations in their order is then done by one thread per track from LDS.  Both forms call the same functions of
+// point3d_device.h - a ray, a row error, the ordered sum are each stated there once - so every number is formed by the same
+// operations in the same order as in the thread-per-track form (which remains: DLT, and workgroups whose observations do not
+// fit the LDS area); tests/test_gpu_tri.py::test_both_workgroup_forms_give_the_same_bits holds the two to the same bits.
+// The kernel no longer waits for a chain of dependent loads per observation.
 // Reference: Point3D::Trianglate2 SfM/src/structure.cc:211-265, Point3D::Trianglate (DLT)
 // :163-209, Point3D::Reprojection :267-300, Point3D::SufficientTriangulationAngle :325-355,
 // GeoVerification::GeoVerificationFundamental (closed form) SfM/src/utils/geo_verification.cc:60-79.
 #include "common.h"
+#include "point3d_device.h"   // contracted here, as the compiler's default has it
 
+// the squared reprojection error of observation i for the point X, -1.0 at negative depth
+__device__ __forceinline__ double obs_error(const TrackPtrs& T, int i, const double* X) {
+  const size_t c = (size_t)T.cam[i];
+  return p3d_row_error(T.R + 9 * c, T.t + 3 * c, T.fk + 3 * c, X, T.xy[2 * (size_t)i], T.xy[2 * (size_t)i + 1]);
+}
 
 // structure.cc:267-300
 __device__ double track_mse(const TrackPtrs& T, int b, int e, const double* X) {
-  double mse = 0.0;
-  int count = 0;
-  for (int i = b; i < e; i++) {
-    const int c = T.cam[i];
-    const double* R = T.R + 9 * (size_t)c;
-    const double* tt = T.t + 3 * (size_t)c;
-    const double* fk = T.fk + 3 * (size_t)c;
-    const double pc0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + tt[0];
-    const double pc1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + tt[1];
-    const double pc2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + tt[2];
-    if (pc2 < 0) return 100000.0;
-    const double x = pc0 / pc2, y = pc1 / pc2;
-    const double r2 = x * x + y * y;
-    const double distortion = 1.0 + r2 * (fk[1] + fk[2] * r2);
-    const double u = fk[0] * distortion * x, v = fk[0] * distortion * y;
-    const double du = u - T.xy[2 * (size_t)i], dv = v - T.xy[2 * (size_t)i + 1];
-    mse += du * du + dv * dv;
-    count++;
-  }
-  return mse / count;
+  return p3d_ordered_mse(b, e, [&](int i) { return obs_error(T, i, X); });
 }
 
 // structure.cc:325-355
 __device__ bool track_angle_ok(const TrackPtrs& T, int b, int e, const double* X, double cos_min) {
   for (int i = b; i + 1 < e; i++) {
-    const double* ci = T.c + 3 * (size_t)T.cam[i];
-    double a[3] = {X[0] - ci[0], X[1] - ci[1], X[2] - ci[2]};
-    const double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    a[0] /= na; a[1] /= na; a[2] /= na;
+    double a[3];
+    p3d_direction(T.c + 3 * (size_t)T.cam[i], X, a);
     for (int j = i + 1; j < e; j++) {
-      const double* cj = T.c + 3 * (size_t)T.cam[j];
-      double d[3] = {X[0] - cj[0], X[1] - cj[1], X[2] - cj[2]};
-      const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-      d[0] /= nd; d[1] /= nd; d[2] /= nd;
-      if (a[0] * d[0] + a[1] * d[1] + a[2] * d[2] < cos_min) return true;
+      double d[3];
+      p3d_direction(T.c + 3 * (size_t)T.cam[j], X, d);
+      if (p3d_pair_wide(a, d, cos_min)) return true;
     }
   }
   return false;
+}
+
+// what every thread-per-track form ends in: the point, its Reprojection, the verdict
+__device__ __forceinline__ void track_finish(const TrackPtrs& T, int t, int b, int e, const double* X, double th_error, double cos_min,
+                                             double* __restrict__ Xo, double* __restrict__ mse, uint8_t* __restrict__ ok) {
+  Xo[3 * (size_t)t] = X[0]; Xo[3 * (size_t)t + 1] = X[1]; Xo[3 * (size_t)t + 2] = X[2];
+  const double m = track_mse(T, b, e, X);
+  mse[t] = m;
+  ok[t] = p3d_accepted(m, th_error, track_angle_ok(T, b, e, X, cos_min));
 }
 
 __device__ __forceinline__ void tri_midpoint_track(const TrackPtrs& T, int t, double th_error, double cos_min, double* __restrict__ Xo,
@@ -60,71 +54,15 @@ __device__ __forceinline__ void tri_midpoint_track(const TrackPtrs& T, int t, do
 #pragma unroll
   for (int k = 0; k < 16; k++) A[k] = 0.0;
   for (int i = b; i < e; i++) {
-    const int c = T.cam[i];
-    const double* R = T.R + 9 * (size_t)c;
-    const double* o = T.c + 3 * (size_t)c;
-    const double f = T.fk[3 * (size_t)c];
-    const double d0 = T.xy[2 * (size_t)i], d1 = T.xy[2 * (size_t)i + 1];
-    double dw[3] = {R[0] * d0 + R[3] * d1 + R[6] * f, R[1] * d0 + R[4] * d1 + R[7] * f, R[2] * d0 + R[5] * d1 + R[8] * f};
-    const double n = sqrt(dw[0] * dw[0] + dw[1] * dw[1] + dw[2] * dw[2]);
-    dw[0] /= n; dw[1] /= n; dw[2] /= n;
-    const double dh[4] = {dw[0], dw[1], dw[2], 0.0};
-    const double oh[4] = {o[0], o[1], o[2], 1.0};
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      double acc = 0.0;
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const double at = (r == q ? 1.0 : 0.0) - dh[r] * dh[q];
-        A[r * 4 + q] += at;
-        acc += at * oh[q];
-      }
-      bv[r] += acc;
-    }
+    const size_t c = (size_t)T.cam[i];
+    double d[3];
+    p3d_ray(T.R + 9 * c, T.fk[3 * c], T.xy[2 * (size_t)i], T.xy[2 * (size_t)i + 1], d);
+    p3d_accumulate(d, T.c + 3 * c, A, bv);
   }
   ok[t] = 0;
   mse[t] = 0.0;
-  // Eigen::LLT<Matrix4d>: fail on a non-positive pivot (structure.cc:247-251)
-  double L[16];
-#pragma unroll
-  for (int k = 0; k < 16; k++) L[k] = 0.0;
-  bool pd = true;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    double d = A[j * 4 + j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= L[j * 4 + k] * L[j * 4 + k];
-    if (!(d > 0.0)) pd = false;
-    L[j * 4 + j] = sqrt(d);
-#pragma unroll
-    for (int i = j + 1; i < 4; i++) {
-      double s = A[i * 4 + j];
-#pragma unroll
-      for (int k = 0; k < j; k++) s -= L[i * 4 + k] * L[j * 4 + k];
-      L[i * 4 + j] = s / L[j * 4 + j];
-    }
-  }
-  if (!pd) return;
-  double y[4], x[4];
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    double s = bv[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) s -= L[i * 4 + k] * y[k];
-    y[i] = s / L[i * 4 + i];
-  }
-#pragma unroll
-  for (int i = 3; i >= 0; i--) {
-    double s = y[i];
-#pragma unroll
-    for (int k = i + 1; k < 4; k++) s -= L[k * 4 + i] * x[k];
-    x[i] = s / L[i * 4 + i];
-  }
-  double X[3] = {x[0] / x[3], x[1] / x[3], x[2] / x[3]};
-  Xo[3 * (size_t)t] = X[0]; Xo[3 * (size_t)t + 1] = X[1]; Xo[3 * (size_t)t + 2] = X[2];
-  const double m = track_mse(T, b, e, X);
-  mse[t] = m;
-  ok[t] = !(sqrt(m) > th_error || !track_angle_ok(T, b, e, X, cos_min));
+  double X[3];
+  if (p3d_solve(A, bv, X)) track_finish(T, t, b, e, X, th_error, cos_min, Xo, mse, ok);
 }
 
 // ---- the staged form: 64 tracks per workgroup, observations through LDS ----
@@ -150,16 +88,12 @@ __global__ __launch_bounds__(256) void k_tri_midpoint_staged(TrackPtrs T, double
   // -- per observation: the unit ray through the image point in world coordinates, the camera centre (structure.cc:224-236)
   for (int j = tid; j < nobs; j += 256) {
     const int i = ob + j;
-    const int c = T.cam[i];
-    const double* R = T.R + 9 * (size_t)c;
-    const double* o = T.c + 3 * (size_t)c;
-    const double f = T.fk[3 * (size_t)c];
-    const double d0 = T.xy[2 * (size_t)i], d1 = T.xy[2 * (size_t)i + 1];
-    double dw[3] = {R[0] * d0 + R[3] * d1 + R[6] * f, R[1] * d0 + R[4] * d1 + R[7] * f, R[2] * d0 + R[5] * d1 + R[8] * f};
-    const double n = sqrt(dw[0] * dw[0] + dw[1] * dw[1] + dw[2] * dw[2]);
-    dw[0] /= n; dw[1] /= n; dw[2] /= n;
+    const size_t c = (size_t)T.cam[i];
+    const double* o = T.c + 3 * c;
+    double d[3];
+    p3d_ray(T.R + 9 * c, T.fk[3 * c], T.xy[2 * (size_t)i], T.xy[2 * (size_t)i + 1], d);
     double* rec = sd + (size_t)j * TRI_REC;
-    rec[0] = dw[0]; rec[1] = dw[1]; rec[2] = dw[2]; rec[3] = o[0]; rec[4] = o[1]; rec[5] = o[2];
+    rec[0] = d[0]; rec[1] = d[1]; rec[2] = d[2]; rec[3] = o[0]; rec[4] = o[1]; rec[5] = o[2];
   }
   __syncthreads();
   // -- per track: the sums over its observations in their order, the 4 x 4 LLT (structure.cc:237-258)
@@ -171,61 +105,16 @@ __global__ __launch_bounds__(256) void k_tri_midpoint_staged(TrackPtrs T, double
     for (int j = b; j < e; j++) {
       const double* rec = sd + (size_t)j * TRI_REC;
       tk[j] = (short)tid;
-      const double dh[4] = {rec[0], rec[1], rec[2], 0.0};
-      const double oh[4] = {rec[3], rec[4], rec[5], 1.0};
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-          const double at = (r == q ? 1.0 : 0.0) - dh[r] * dh[q];
-          A[r * 4 + q] += at;
-          acc += at * oh[q];
-        }
-        bv[r] += acc;
-      }
+      p3d_accumulate(rec, rec + 3, A, bv);
     }
     ok[t] = 0;
     mse[t] = 0.0;
-    double L[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) L[k] = 0.0;
-    bool pd = true;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      double d = A[j * 4 + j];
-#pragma unroll
-      for (int k = 0; k < j; k++) d -= L[j * 4 + k] * L[j * 4 + k];
-      if (!(d > 0.0)) pd = false;
-      L[j * 4 + j] = sqrt(d);
-#pragma unroll
-      for (int i = j + 1; i < 4; i++) {
-        double sacc = A[i * 4 + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) sacc -= L[i * 4 + k] * L[j * 4 + k];
-        L[i * 4 + j] = sacc / L[j * 4 + j];
-      }
-    }
+    double X[3];
+    const bool pd = p3d_solve(A, bv, X);
     alive[tid] = pd ? 1 : 0;
     if (pd) {
-      double y[4], x[4];
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        double sacc = bv[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) sacc -= L[i * 4 + k] * y[k];
-        y[i] = sacc / L[i * 4 + i];
-      }
-#pragma unroll
-      for (int i = 3; i >= 0; i--) {
-        double sacc = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 4; k++) sacc -= L[k * 4 + i] * x[k];
-        x[i] = sacc / L[i * 4 + i];
-      }
-      const double X0 = x[0] / x[3], X1 = x[1] / x[3], X2 = x[2] / x[3];
-      Xo[3 * (size_t)t] = X0; Xo[3 * (size_t)t + 1] = X1; Xo[3 * (size_t)t + 2] = X2;
-      Xs[3 * tid] = X0; Xs[3 * tid + 1] = X1; Xs[3 * tid + 2] = X2;
+      Xo[3 * (size_t)t] = X[0]; Xo[3 * (size_t)t + 1] = X[1]; Xo[3 * (size_t)t + 2] = X[2];
+      Xs[3 * tid] = X[0]; Xs[3 * tid + 1] = X[1]; Xs[3 * tid + 2] = X[2];
     }
   }
   __syncthreads();
@@ -234,54 +123,24 @@ __global__ __launch_bounds__(256) void k_tri_midpoint_staged(TrackPtrs T, double
   for (int j = tid; j < nobs; j += 256) {
     const int trk = tk[j];
     if (!alive[trk]) continue;
-    const int i = ob + j;
-    const int c = T.cam[i];
     const double X[3] = {Xs[3 * trk], Xs[3 * trk + 1], Xs[3 * trk + 2]};
-    const double* R = T.R + 9 * (size_t)c;
-    const double* tt = T.t + 3 * (size_t)c;
-    const double* fk = T.fk + 3 * (size_t)c;
     double* rec = sd + (size_t)j * TRI_REC;
-    const double pc0 = R[0] * X[0] + R[1] * X[1] + R[2] * X[2] + tt[0];
-    const double pc1 = R[3] * X[0] + R[4] * X[1] + R[5] * X[2] + tt[1];
-    const double pc2 = R[6] * X[0] + R[7] * X[1] + R[8] * X[2] + tt[2];
-    double err = -1.0;   // pc2 < 0: the track's error is the constant 100000 (structure.cc:283)
-    if (!(pc2 < 0)) {
-      const double x = pc0 / pc2, y = pc1 / pc2;
-      const double r2 = x * x + y * y;
-      const double distortion = 1.0 + r2 * (fk[1] + fk[2] * r2);
-      const double u = fk[0] * distortion * x, v = fk[0] * distortion * y;
-      const double du = u - T.xy[2 * (size_t)i], dv = v - T.xy[2 * (size_t)i + 1];
-      err = du * du + dv * dv;
-    }
-    double a[3] = {X[0] - rec[3], X[1] - rec[4], X[2] - rec[5]};
-    const double na = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-    a[0] /= na; a[1] /= na; a[2] /= na;
+    const double err = obs_error(T, ob + j, X);
+    double a[3];
+    p3d_direction(rec + 3, X, a);
     rec[0] = a[0]; rec[1] = a[1]; rec[2] = a[2]; rec[6] = err;
   }
   __syncthreads();
   // -- per track: the error sum in observation order, the angle gate over the pairs of rays
   if (tid < nt && alive[tid]) {
     const int t = t0 + tid, b = offs[tid] - ob, e = offs[tid + 1] - ob;
-    double m = 0.0;
-    int count = 0;
-    bool behind = false;
-    for (int j = b; j < e; j++) {
-      const double er = sd[(size_t)j * TRI_REC + 6];
-      if (er < 0.0) { behind = true; break; }
-      m += er;
-      count++;
-    }
-    m = behind ? 100000.0 : m / count;
+    const double m = p3d_ordered_mse(b, e, [&](int j) { return sd[(size_t)j * TRI_REC + 6]; });
     mse[t] = m;
     bool wide = false;
-    for (int i = b; i + 1 < e && !wide; i++) {
-      const double* ai = sd + (size_t)i * TRI_REC;
-      for (int j = i + 1; j < e; j++) {
-        const double* dj = sd + (size_t)j * TRI_REC;
-        if (ai[0] * dj[0] + ai[1] * dj[1] + ai[2] * dj[2] < cos_min) { wide = true; break; }
-      }
-    }
-    ok[t] = !(sqrt(m) > th_error || !wide);
+    for (int i = b; i + 1 < e && !wide; i++)
+      for (int j = i + 1; j < e; j++)
+        if (p3d_pair_wide(sd + (size_t)i * TRI_REC, sd + (size_t)j * TRI_REC, cos_min)) { wide = true; break; }
+    ok[t] = p3d_accepted(m, th_error, wide);
   }
 }
 
@@ -306,39 +165,12 @@ __global__ __launch_bounds__(256) void k_reproject_staged(TrackPtrs T, const dou
     const int i = ob + j;
     int lo = 0, hi = nt - 1;   // the track of observation i: the last one whose first observation is <= i
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (offs[mid] <= i) lo = mid; else hi = mid - 1; }
-    const size_t t = (size_t)(t0 + lo);
-    const double Xt[3] = {X[3 * t], X[3 * t + 1], X[3 * t + 2]};
-    const int c = T.cam[i];
-    const double* R = T.R + 9 * (size_t)c;
-    const double* tt = T.t + 3 * (size_t)c;
-    const double* fk = T.fk + 3 * (size_t)c;
-    const double pc0 = R[0] * Xt[0] + R[1] * Xt[1] + R[2] * Xt[2] + tt[0];
-    const double pc1 = R[3] * Xt[0] + R[4] * Xt[1] + R[5] * Xt[2] + tt[1];
-    const double pc2 = R[6] * Xt[0] + R[7] * Xt[1] + R[8] * Xt[2] + tt[2];
-    double err = -1.0;
-    if (!(pc2 < 0)) {
-      const double x = pc0 / pc2, y = pc1 / pc2;
-      const double r2 = x * x + y * y;
-      const double distortion = 1.0 + r2 * (fk[1] + fk[2] * r2);
-      const double u = fk[0] * distortion * x, v = fk[0] * distortion * y;
-      const double du = u - T.xy[2 * (size_t)i], dv = v - T.xy[2 * (size_t)i + 1];
-      err = du * du + dv * dv;
-    }
-    er_s[j] = err;
+    er_s[j] = obs_error(T, i, X + 3 * (size_t)(t0 + lo));
   }
   __syncthreads();
   if (tid < nt) {
     const int b = offs[tid] - ob, e = offs[tid + 1] - ob;
-    double m = 0.0;
-    int count = 0;
-    bool behind = false;
-    for (int j = b; j < e; j++) {
-      const double er = er_s[j];
-      if (er < 0.0) { behind = true; break; }
-      m += er;
-      count++;
-    }
-    mse[t0 + tid] = behind ? 100000.0 : m / count;
+    mse[t0 + tid] = p3d_ordered_mse(b, e, [&](int j) { return er_s[j]; });
   }
 }
 
@@ -424,11 +256,8 @@ __global__ __launch_bounds__(256) void k_tri_dlt(TrackPtrs T, double th_error, d
     for (int r = 0; r < 4; r++) nn += Rf[r * 4 + q] * Rf[r * 4 + q];
     if (q == 0 || nn < bn) { bn = nn; v0 = V[q]; v1 = V[4 + q]; v2 = V[8 + q]; v3 = V[12 + q]; }
   }
-  double X[3] = {v0 / v3, v1 / v3, v2 / v3};
-  Xo[3 * (size_t)t] = X[0]; Xo[3 * (size_t)t + 1] = X[1]; Xo[3 * (size_t)t + 2] = X[2];
-  const double m = track_mse(T, b, e, X);
-  mse[t] = m;
-  ok[t] = !(sqrt(m) > th_error || !track_angle_ok(T, b, e, X, cos_min));
+  const double X[3] = {v0 / v3, v1 / v3, v2 / v3};
+  track_finish(T, t, b, e, X, th_error, cos_min, Xo, mse, ok);
 }
 
 struct F9 { double f[9]; };

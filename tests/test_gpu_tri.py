@@ -57,6 +57,66 @@ def test_edge_cases(ctx, oracle):
     assert (Xg[3] == 7.0).all()
 
 
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def test_both_workgroup_forms_give_the_same_bits(ctx, oracle):
+    """A workgroup of tri.hip holds 64 tracks.  Up to TRI_CAP = 768 observations it stages them through LDS, above that it
+    runs one thread per track.  The same 63 short tracks go through both forms: alone (staged), followed by a long track
+    that brings the workgroup to exactly 768 observations (staged) and to 769 (thread per track)."""
+    cap = 768
+    sc = scene.make_ring_scene(5, 64, seed=3, noise_px=0.5)
+    R, t, c, fk = scene.cameras_for_tracks(sc)
+    o = sc.track_offsets()
+    # a pinhole mirrors a point behind it through the principal point: the rays of cameras 0 and 1 through these two
+    # observations meet behind both cameras -> negative depth -> mse = 1e5 (structure.cc:280-284)
+    behind, depth = scene.project_Rt(R[:2].reshape(-1, 3, 3), t[:2], fk[:2], 1.5 * (c[0] + c[1]))
+    assert (depth < 0).all()
+    # camera 5 sits at the origin with R = I: its ray through the principal point is (0, 0, 1) exactly, I - d d^T has an
+    # exact zero on its diagonal and the LLT of this single-view track fails in every arithmetic (structure.cc:248-251)
+    R, fk = np.vstack([R, np.eye(3).reshape(1, 9)]), np.vstack([fk, fk[:1]])
+    t, c = np.vstack([t, np.zeros((1, 3))]), np.vstack([c, np.zeros((1, 3))])
+    off, cams, xy = [0], [], []
+    for p in range(63):
+        k = 2 + p % 4                            # 2 to 5 views
+        if p == 41: k = 0                        # an empty track
+        if p == 50: k = 2                        # the point behind cameras 0 and 1
+        cams += [5] if p == 20 else list(sc.obs_cam[o[p]:o[p] + k])
+        xy += [np.zeros(2)] if p == 20 else list(behind if p == 50 else sc.obs_xy[o[p]:o[p] + k])
+        off.append(len(cams))
+    n_a = len(cams)
+    assert n_a < cap // 2
+
+    def tracks(n_long):   # the 63 tracks, then the five observations of point 63 repeated to n_long rows
+        if n_long == 0:
+            return A.TrackArrays(np.array(off), np.array(cams), np.array(xy).reshape(-1, 2), R, t, c, fk)
+        rows = o[63] + np.arange(n_long) % 5
+        return A.TrackArrays(np.array(off + [n_a + n_long]), np.concatenate([cams, sc.obs_cam[rows]]),
+                             np.concatenate([np.array(xy).reshape(-1, 2), sc.obs_xy[rows]]), R, t, c, fk)
+
+    th_err, th_ang = 3.0, np.deg2rad(3.0)
+    Xa, ma, oka = ctx.triangulate_midpoint(tracks(0), th_err, th_ang, np.full((63, 3), 7.0))
+    ra = ctx.reproject_mse(tracks(0), Xa)
+    assert oka.sum() == 60 and not oka[20] and not oka[41] and not oka[50]
+    assert (Xa[20] == 7.0).all() and (Xa[41] == 7.0).all() and ma[50] == 1e5 and ra[50] == 1e5
+    for n_long in (cap - n_a, cap - n_a + 1):    # the last staged workgroup, the first thread-per-track one
+        tr = tracks(n_long)
+        assert tr.track_off[-1] == n_a + n_long
+        X0 = np.full((64, 3), 7.0)
+        Xb, mb, okb = ctx.triangulate_midpoint(tr, th_err, th_ang, X0)
+        np.testing.assert_array_equal(_bits(Xb[:63]), _bits(Xa))
+        np.testing.assert_array_equal(_bits(mb[:63]), _bits(ma))
+        np.testing.assert_array_equal(okb[:63], oka)
+        rb = ctx.reproject_mse(tr, Xb)
+        np.testing.assert_array_equal(_bits(rb[:63]), _bits(ra))
+        Xr, mr, okr = oracle.triangulate_midpoint(tr, th_err, th_ang, X0)
+        assert okr[63] and okb[63] == okr[63]
+        np.testing.assert_allclose(Xb[63], Xr[63], rtol=1e-9, atol=1e-9)
+        np.testing.assert_allclose(mb[63], mr[63], rtol=1e-7, atol=1e-9)
+        np.testing.assert_allclose(rb[63], oracle.reproject_mse(tr, Xb)[63], rtol=1e-12)
+
+
 def test_epipolar_filter(ctx, oracle):
     rng = np.random.default_rng(4)
     F = rng.standard_normal((3, 3)); F[2, 2] = 1.0
