@@ -314,6 +314,13 @@ typedef struct msfm_ba_layout {
    * workgroups for its block sums).  The bits of this field are
    * distinct from those of the two fields above, so that a value read from the wrong field shows. */
   int rider_paths;
+  /* how the point kernel's four waves share the products of a workgroup (0 everywhere: gather path only).  Four threads - a
+   * quad - sum a slot; a slot of more than 8 entries is cut into up to four parts with a quad each, which are added up inside
+   * the wave.  fold_parts = quads with work (= fold_slots where no slot is cut).  The other three count entry steps - one
+   * trip of a quad's loop over its entries - by this model: the sixteen quads of a wave take as long as the longest of them,
+   * and a pass of a workgroup as long as the wave with the most steps.  fold_crit_steps = that wave's steps summed over all
+   * passes, fold_crit_steps_unsplit = the same figure had no slot been cut, fold_wave_steps = the steps of all waves. */
+  long long fold_parts, fold_crit_steps, fold_crit_steps_unsplit, fold_wave_steps;
 } msfm_ba_layout;
 #define MSFM_PATH_ASM_BESIDE 1
 #define MSFM_PATH_RIDER_MODELSUM (1 << 8)

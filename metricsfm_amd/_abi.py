@@ -48,7 +48,8 @@ class BaLayout(C.Structure):
                 ("cc_entries", C.c_longlong), ("cc_entries_folded", C.c_longlong), ("fold_slots", C.c_int), ("fold_passes", C.c_int),
                 ("mc_entries", C.c_longlong), ("mc_entries_folded", C.c_longlong), ("fold_mc_slots", C.c_int), ("solve_paths", C.c_int),
                 ("npb_S", C.c_int), ("npb_L", C.c_int), ("npb_X", C.c_int), ("npb_S4", C.c_int), ("assemble_paths", C.c_int),
-                ("rider_paths", C.c_int)]
+                ("rider_paths", C.c_int), ("fold_parts", C.c_longlong), ("fold_crit_steps", C.c_longlong),
+                ("fold_crit_steps_unsplit", C.c_longlong), ("fold_wave_steps", C.c_longlong)]
 
 
 class FransacOptions(C.Structure):

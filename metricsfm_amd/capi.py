@@ -1731,7 +1731,9 @@ class BaResident:
                     separator_cols=lay.separator_cols, panel_launches=lay.panel_launches, n_levels=lay.n_levels,
                     level_nodes=list(lay.level_nodes)[:lay.n_levels], level_begin=list(lay.level_begin)[:lay.n_levels], root_cols=lay.root_cols,
                     fold=dict(cc_entries=lay.cc_entries, cc_entries_folded=lay.cc_entries_folded, slots=lay.fold_slots, passes=lay.fold_passes,
-                              mc_entries=lay.mc_entries, mc_entries_folded=lay.mc_entries_folded, mc_slots=lay.fold_mc_slots),
+                              mc_entries=lay.mc_entries, mc_entries_folded=lay.mc_entries_folded, mc_slots=lay.fold_mc_slots,
+                              parts=lay.fold_parts, crit_steps=lay.fold_crit_steps, crit_steps_unsplit=lay.fold_crit_steps_unsplit,
+                              wave_steps=lay.fold_wave_steps),
                     solve_paths=lay.solve_paths, assemble_paths=lay.assemble_paths, rider_paths=lay.rider_paths, npb_S=lay.npb_S, npb_L=lay.npb_L, npb_X=lay.npb_X, npb_S4=lay.npb_S4)
 
     def upload(self, cam_pose=None, cam_model=None, point=None):

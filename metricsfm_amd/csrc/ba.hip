@@ -257,11 +257,33 @@ __global__ __launch_bounds__(1024) void k_reduce(ReduceJobs J, double* __restric
 // --------------------------------------------------------------------------------------
 // k_point: the eliminated points.  mode 0: full; mode 1: raw squared column norms only.
 // --------------------------------------------------------------------------------------
-// One pass of a folding workgroup (FoldTables below): `words` 32-bit words at fold_stream + off - the headers of n_slots slots
-// (first entry relative to the entry area | count << 16; padded to a multiple of four words), then the slots' entries
-// (record_i | record_j << 16) - which one wave instruction per 256 words copies straight into LDS.  slot0: the first slot's
-// index in workgroup-major numbering (for its rank); n_diag: how many of the pass's slots (its first ones) are camera-diagonal.
-struct FoldPass { int off, words, slot0, n_slots, n_diag, pad0, pad1, pad2; };
+// One pass of a folding workgroup (FoldTables below): `words` 32-bit words at fold_stream + off - the headers of n_quads quads
+// (fold_hdr below; padded to a multiple of four words), then the slots' entries (record_i | record_j << 16) - which one wave
+// instruction per 256 words copies straight into LDS.  A quad - four threads - sums one slot, or one PART of a slot that was
+// cut (fold_parts).  quad0: the first quad's index in workgroup-major numbering (for the slot's rank); n_diag: how many of the
+// pass's quads (its first ones) belong to camera-diagonal slots; flip: 48 in a workgroup with a cut slot, else 0 (below).
+struct FoldPass { int off, words, quad0, n_quads, n_diag, flip, pad1, pad2; };
+// Header word of a quad: first entry relative to the entry area (bits 0..9) | part (10, 11) | parts of the slot - 1 (12, 13) |
+// entry count << 16.  The word of an uncut slot is first | count << 16.
+#define FOLD_HDR_IDLE (1u << 10)   // a quad without work: it fills a row in front of a cut slot, or lies behind the pass's last quad
+__host__ __device__ inline unsigned fold_hdr(int first, int count, int part, int parts) {
+  return (unsigned)first | ((unsigned)part << 10) | ((unsigned)(parts - 1) << 12) | ((unsigned)count << 16);
+}
+__host__ __device__ inline int fold_hdr_first(unsigned h) { return (int)(h & 0x3ffu); }
+__host__ __device__ inline int fold_hdr_part(unsigned h) { return (int)(h >> 10) & 3; }
+__host__ __device__ inline int fold_hdr_parts(unsigned h) { return ((int)(h >> 12) & 3) + 1; }
+__host__ __device__ inline int fold_hdr_count(unsigned h) { return (int)(h >> 16); }
+// The rule that cuts a slot, from its entry count alone: parts of FOLD_PART_CAP entries and the rest in the last one, four
+// parts at the most - a slot of more than four caps has four longer parts, as equal as they come (part k has count / 4
+// entries, the first count % 4 one more).  The parts are contiguous ranges of the slot's entries in the slot's order.
+// (Equal parts below four caps too - 9 = 5 + 4 - were measured: 2 % fewer steps of the slowest wave by the model, the same
+// time within noise, and another rounding of the sums, which is all that tells the two apart in the results.)
+#define FOLD_PART_CAP 8
+__host__ __device__ inline int fold_parts(int count) { return count <= FOLD_PART_CAP ? 1 : count > 3 * FOLD_PART_CAP ? 4 : (count + FOLD_PART_CAP - 1) / FOLD_PART_CAP; }
+__host__ __device__ inline int fold_part_len(int count, int parts, int k) {
+  if (count > 4 * FOLD_PART_CAP) return count / parts + (k < count % parts ? 1 : 0);
+  return k + 1 < parts ? FOLD_PART_CAP : count - (parts - 1) * FOLD_PART_CAP;
+}
 struct PointPtrs {
   BaPtrs B;            // row data, parameters and scales the rows are linearised with
   PtMap map;
@@ -298,7 +320,8 @@ struct PointPtrs {
 // T = (Jc^T Jp) L^-T.
 #define FOLD_NREC 256        // records of 2 x 10 doubles (two 16-byte aligned halves of 9) in the 48 KB row park: one per lane
 #define FOLD_WORDS 1024      // words (slot headers + entries) of one pass, staged in LDS
-#define FOLD_PASS_SLOTS 128  // slots of one pass at most: four threads per slot, two rounds
+#define FOLD_PASS_SLOTS 128  // slots of one pass at most in a workgroup with no cut slot: four threads per slot, two rounds
+#define FOLD_PASS_QUADS 256  // quads of one pass at most in a workgroup with a cut slot: four rounds
 template <int LPP>
 __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restrict__ gmax_partial, double* sh, double* park, unsigned* ent_s) {
   constexpr int GW = LPP ? LPP : 8;    // lanes of a point
@@ -585,8 +608,9 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
     if (fold) {
       const int q = tid & 3, ra = q >> 1, rb = q & 1, sl4 = tid >> 2;   // rows 3 ra .. of record i times rows 3 rb .. of record j
       for (int p = fp0; p < fp1; p++) {
-        const int slot0 = __builtin_amdgcn_readfirstlane(P.fold_pass[p].slot0), n_slots = __builtin_amdgcn_readfirstlane(P.fold_pass[p].n_slots);
+        const int quad0 = __builtin_amdgcn_readfirstlane(P.fold_pass[p].quad0), n_quads = __builtin_amdgcn_readfirstlane(P.fold_pass[p].n_quads);
         const int n_diag = P.fold_mc_partial ? __builtin_amdgcn_readfirstlane(P.fold_pass[p].n_diag) : 0;
+        const int flip = __builtin_amdgcn_readfirstlane(P.fold_pass[p].flip);
         if (p > fp0) {
           __syncthreads();   // (the previous pass is done with the staged words)
           stage(__builtin_amdgcn_readfirstlane(P.fold_pass[p].off), __builtin_amdgcn_readfirstlane(P.fold_pass[p].words));
@@ -595,18 +619,24 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
         // copy explicitly before the barrier (this toolchain happens to emit the wait; nothing guarantees that it always will)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();     // records stored (first pass); the pass's words have arrived in LDS
-        // where the results go: asked for now, needed after the loops
-        int rank0 = 0, rank1 = 0;
-        if (sl4 < n_slots) rank0 = P.fold_slot_rank[slot0 + sl4];
-        if (sl4 + 64 < n_slots) rank1 = P.fold_slot_rank[slot0 + sl4 + 64];
-        const int hdr = (n_slots + 3) & ~3;
-        for (int sl = sl4, rnk = rank0; sl < n_slots; sl += 64, rnk = rank1) {
-          // the slot's four threads form nine entries of the 6 x 6 product each, over the slot's entries in point order
+        const int hdr = (n_quads + 3) & ~3;
+        // Rounds of 64 quads, the same trip count for every lane (the sums across the quads of a cut slot below want their
+        // partner lanes active).  The slots of a pass are in order of falling length: where slots are cut (flip = 48), the
+        // waves take their sixteen quads of an odd round in reverse order, so that the wave with the longest quads of one
+        // round has the shortest of the next.
+        for (int rd = 0; 64 * rd < n_quads; rd++) {
+          const int sl = 64 * rd + ((rd & 1) ? sl4 ^ flip : sl4);
+          const bool on = sl < n_quads;
+          // the quad's four threads form nine entries of the 6 x 6 product each, over the quad's entries in point order
           // (measured alternatives, config 3: the next entry's records kept in flight behind the multiplies - no change; every
           // fourth entry per thread with the whole 6 x 6 product and a sum across the quad - k_point 0.41 -> 0.52 ms.  The
           // phase is bound by the LDS array: the records a lane group gathers fall on the 16 four-bank groups at random)
-          const unsigned h = ent_s[sl];
-          const int e0 = hdr + (int)(h & 0xffffu), e1 = e0 + (int)(h >> 16);
+          const unsigned h = on ? ent_s[sl] : FOLD_HDR_IDLE;
+          const int part = fold_hdr_part(h), n_parts = fold_hdr_parts(h);
+          const int e0 = hdr + fold_hdr_first(h), e1 = e0 + fold_hdr_count(h);
+          // where the result goes: asked for now, needed after the loop
+          int rnk = 0;
+          if (on && part == 0) rnk = P.fold_slot_rank[quad0 + sl];
           // intrinsics x camera: Tm_p T_rec^T summed over the records of one camera in this workgroup - exactly the entries of
           // the camera's diagonal slot that pair a record with itself (a camera that sees a point twice also has the two cross
           // entries there).  The two threads that hold rows 0..2 of record i take nine entries of the 3 x 6 product each: the
@@ -648,20 +678,38 @@ __device__ __forceinline__ void k_point_body(const PointPtrs& P, double* __restr
                   accm[a * 3 + c] += tm[a * 3] * tj[c * 3] + tm[a * 3 + 1] * tj[c * 3 + 1] + tm[a * 3 + 2] * tj[c * 3 + 2];
             }
           }
-          if (mcd) {
-            double* om = P.fold_mc_partial + (size_t)rnk * 18;
+          // A cut slot (fold_parts): its parts are the sums of neighbouring quads of one 16-lane row, and the quad of part 0
+          // collects them in a fixed order - (p0 + p1) + (p2 + p3), (p0 + p1) + p2 or p0 + p1.  An uncut slot adds nothing,
+          // so its sums keep the bits they had before slots were cut.
+          if (__any(n_parts > 1)) {
+            const bool pair = (part & 1) == 0 && part + 1 < n_parts, last = part == 0 && n_parts > 2;
+            auto gather = [&](double& v) {
+              const double up1 = dpp_f64<MSFM_DPP_SHL4>(v);
+              if (pair) v += up1;
+              const double up2 = dpp_f64<MSFM_DPP_SHL8>(v);
+              if (last) v += up2;
+            };
 #pragma unroll
-            for (int a = 0; a < 2; a++)
-              if (ma0 + a < 3) {
+            for (int k = 0; k < 9; k++) gather(acc[k]);
 #pragma unroll
-                for (int c = 0; c < 3; c++) om[(ma0 + a) * 6 + 3 * rb + c] = accm[a * 3 + c];
-              }
+            for (int k = 0; k < 6; k++) gather(accm[k]);
           }
-          double* out = P.fold_partial + (size_t)rnk * 36;
+          if (on && part == 0) {
+            if (mcd) {
+              double* om = P.fold_mc_partial + (size_t)rnk * 18;
 #pragma unroll
-          for (int a = 0; a < 3; a++)
+              for (int a = 0; a < 2; a++)
+                if (ma0 + a < 3) {
 #pragma unroll
-            for (int c = 0; c < 3; c++) out[(3 * ra + a) * 6 + 3 * rb + c] = acc[a * 3 + c];
+                  for (int c = 0; c < 3; c++) om[(ma0 + a) * 6 + 3 * rb + c] = accm[a * 3 + c];
+                }
+            }
+            double* out = P.fold_partial + (size_t)rnk * 36;
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+#pragma unroll
+              for (int c = 0; c < 3; c++) out[(3 * ra + a) * 6 + 3 * rb + c] = acc[a * 3 + c];
+          }
         }
       }
     }
@@ -1755,12 +1803,15 @@ __global__ __launch_bounds__(256) void k_pack_blocks(int nblk, const int* __rest
 // block's slot partials (ranked by block) to its chunk partials.  A record is the T of one lane's row, so the S and L
 // workgroups (PtMap) fold; the X workgroups (points with more than 16 rows) keep the gather path: their entries stay live in
 // the pair list, the others are marked (pa < 0) and skipped by k_pairs.
+// A slot of more than FOLD_PART_CAP entries is cut into parts with four threads each (fold_parts, k_fold_passes): the waves of a
+// workgroup then share the long camera-diagonal slots instead of the first wave carrying them; the slot still has one partial.
 struct FoldTables {
   bool on = false;
   bool all = false;   // every entry of the camera x camera list is folded: k_pairs<6,6> and its chunk partials are not needed at all
   int n_live = 0;     // chunks of the camera x camera list that still hold a live entry (the others' partials stay zero)
   DevBuf<int> live_chunk;
   int n_wg = 0, n_slots = 0, n_entries = 0, n_pass = 0;
+  long long n_parts = 0, crit_steps = 0, crit_steps_unsplit = 0, wave_steps = 0;   // (k_fold_passes)
   DevBuf<int> wg_fold, wg_pass_first, slot_rank, blk_range;
   DevBuf<uint8_t> blk_live;   // camera x camera blocks that still have an entry on the gather path
   DevBuf<FoldPass> pass;
@@ -2875,53 +2926,115 @@ __global__ __launch_bounds__(256) void k_fold_perm_key(int NS, int ncb, const un
   key[sl] = ((unsigned long long)w << 32) | (dg << 31) | ((0x7fffu - cnt) << 16) | loc;
   id[sl] = sl;
 }
-__global__ __launch_bounds__(256) void k_fold_gather_rank(int NS, const int* __restrict__ perm, const int* __restrict__ rank, int* __restrict__ rank_pos) {
-  const int pos = blockIdx.x * 256 + threadIdx.x;
-  if (pos < NS) rank_pos[pos] = rank[perm[pos]];
+// (k_point asks for a slot's rank by the quad of its part 0: k_fold_passes)
+__global__ __launch_bounds__(256) void k_fold_quad_rank(int NS, const int* __restrict__ slot_quad, const int* __restrict__ rank, int* __restrict__ rank_quad) {
+  const int sl = blockIdx.x * 256 + threadIdx.x;
+  if (sl < NS) rank_quad[slot_quad[sl]] = rank[sl];
 }
-// passes of every workgroup: as many slots as fit FOLD_WORDS words and FOLD_PASS_SLOTS slots.  COUNT: passes and words per
-// workgroup; EMIT: the pass descriptors, the slot headers (written into the stream here) and where every slot's entries go.
+// The model the cut is judged by: an entry step is one trip of a quad's loop over its entries, the sixteen quads of a wave in
+// a round take as many steps as the longest of them, and a pass lasts as long as the wave with the most steps over its rounds.
+// (quad(): the quads of a pass in position order; flip: as in k_point)
+struct FoldWaveSteps {
+  int w[4], longest, pos;
+  __device__ void start() { w[0] = w[1] = w[2] = w[3] = 0; longest = 0; pos = 0; }
+  __device__ void close(bool flip) {
+    const int rd = (pos - 1) >> 6, wv = ((pos - 1) >> 4) & 3;
+    w[(flip && (rd & 1)) ? 3 - wv : wv] += longest;
+    longest = 0;
+  }
+  __device__ void quad(int len, bool flip) { longest = max(longest, len); pos++; if ((pos & 15) == 0) close(flip); }
+  __device__ void finish(bool flip) { if (pos & 15) close(flip); }
+  __device__ int crit() const { return max(max(w[0], w[1]), max(w[2], w[3])); }
+  __device__ int sum() const { return w[0] + w[1] + w[2] + w[3]; }
+};
+// Passes of every workgroup.  A workgroup in which fold_parts cuts no slot: as many slots as fit FOLD_WORDS words and
+// FOLD_PASS_SLOTS slots, one quad per slot - the stream it had before slots were cut.  A workgroup with a cut slot: up to
+// FOLD_PASS_QUADS quads; the parts of a slot are neighbouring quads of one row of four (16 lanes of one wave in one round),
+// behind idle quads where the row would end before the slot does.  The slots keep their order (k_fold_perm_key).
+// COUNT: passes, words and quads per workgroup; EMIT: the pass descriptors, the quad headers (written into the stream here),
+// where every slot's entries go, the quad of its part 0 and, summed over the workgroups into stats[0..3], what
+// msfm_ba_layout reports: quads with work, FoldWaveSteps' longest wave per pass for these tables and for the slots uncut, and
+// the steps of all waves.
 template <bool EMIT>
 __global__ __launch_bounds__(256) void k_fold_passes(int n_wg, int ncb, const int* __restrict__ wg_slot_first, const int* __restrict__ slot_ent_first,
                                                       const unsigned long long* __restrict__ slot_key2, const int* __restrict__ perm, int* __restrict__ wg_npass, int* __restrict__ wg_words,
-                                                      const int* __restrict__ pass_first, const int* __restrict__ words_first, FoldPass* __restrict__ pass,
-                                                      unsigned* __restrict__ stream, int* __restrict__ slot_ent_pos, int* __restrict__ too_large) {
+                                                      int* __restrict__ wg_quads, const int* __restrict__ pass_first, const int* __restrict__ words_first,
+                                                      const int* __restrict__ quads_first, FoldPass* __restrict__ pass, unsigned* __restrict__ stream,
+                                                      int* __restrict__ slot_ent_pos, int* __restrict__ slot_quad, unsigned long long* __restrict__ stats, int* __restrict__ too_large) {
   const int w = blockIdx.x * 256 + threadIdx.x;
   if (w >= n_wg) return;
   const int s0 = wg_slot_first[w], s1 = wg_slot_first[w + 1];
-  int np = 0, words = 0;
+  auto count = [&](int pos) { return slot_ent_first[perm[pos] + 1] - slot_ent_first[perm[pos]]; };
+  bool cut = false;
+  for (int pos = s0; pos < s1; pos++) cut = cut || fold_parts(count(pos)) > 1;
+  const int bound = cut ? FOLD_PASS_QUADS : FOLD_PASS_SLOTS;
+  // (a cut slot starts a new row where the row it would start in has not the quads left for its parts)
+  auto idle_before = [](int nq, int parts) { return parts > 1 && (nq & 3) + parts > 4 ? 4 - (nq & 3) : 0; };
+  int np = 0, words = 0, quads = 0;
+  FoldWaveSteps built, uncut;
+  long long n_parts = 0, crit = 0, wave = 0;
   int a = s0;
   while (a < s1) {
-    int b = a, ent = 0;
-    while (b < s1 && b - a < FOLD_PASS_SLOTS) {
-      const int c = slot_ent_first[perm[b] + 1] - slot_ent_first[perm[b]];
-      if (b > a && ((b + 1 - a + 3) & ~3) + ent + c > FOLD_WORDS) break;   // (one slot always fits: at most one entry per pair of records)
-      ent += c; b++;
+    int b = a, ent = 0, nq = 0;
+    while (b < s1) {
+      const int c = count(b), parts = fold_parts(c), nq1 = nq + idle_before(nq, parts) + parts;
+      if (nq1 > bound) break;
+      if (b > a && ((nq1 + 3) & ~3) + ent + c > FOLD_WORDS) break;   // (one slot always fits: at most one entry per pair of records)
+      nq = nq1; ent += c; b++;
     }
-    const int hdr = (b - a + 3) & ~3, pw = (hdr + ent + 3) & ~3;
+    const int hdr = (nq + 3) & ~3, pw = (hdr + ent + 3) & ~3;
     if (EMIT) {
-      const int off = words_first[w] + words;
-      int nd = 0, rel = 0;
+      const int off = words_first[w] + words, quad0 = quads_first[w] + quads;
+      int nd = 0, rel = 0, q = 0;
+      built.start();
       for (int pos = a; pos < b; pos++) {
         const int sl = perm[pos];
-        const int c = slot_ent_first[sl + 1] - slot_ent_first[sl];
-        if ((unsigned)(slot_key2[sl] >> 32) < (unsigned)ncb) nd++;
-        stream[off + (pos - a)] = (unsigned)rel | ((unsigned)c << 16);
+        const int c = count(pos), parts = fold_parts(c);
+        for (int idle = idle_before(q, parts); idle > 0; idle--) { stream[off + q] = FOLD_HDR_IDLE; built.quad(0, cut); q++; }
+        slot_quad[sl] = quad0 + q;
         slot_ent_pos[sl] = off + hdr + rel;
-        rel += c;
+        for (int k = 0; k < parts; k++) {
+          const int len = fold_part_len(c, parts, k);
+          stream[off + q] = fold_hdr(rel, len, k, parts);
+          built.quad(len, cut);
+          rel += len; q++;
+        }
+        if ((unsigned)(slot_key2[sl] >> 32) < (unsigned)ncb) nd = q;
+        n_parts += parts;
       }
+      built.finish(cut);
+      crit += built.crit(); wave += built.sum();
       FoldPass fp;
-      fp.off = off; fp.words = pw; fp.slot0 = a; fp.n_slots = b - a; fp.n_diag = nd; fp.pad0 = fp.pad1 = fp.pad2 = 0;
+      fp.off = off; fp.words = pw; fp.quad0 = quad0; fp.n_quads = nq; fp.n_diag = nd; fp.flip = cut ? 48 : 0; fp.pad1 = fp.pad2 = 0;
       pass[pass_first[w] + np] = fp;
     }
     // one slot alone does not fit the staging area (thousands of repeated observations of one camera pair inside 32 points):
     // the host reads the flag beside the counts and keeps the gather path (a flag of its own: the counts are summed by a
     // 32-bit scan, a sentinel inside them could wrap)
     if (pw > FOLD_WORDS && too_large) atomicOr(too_large, 1);
-    np++; words += pw;
+    np++; words += pw; quads += nq;
     a = b;
   }
-  if (!EMIT) { wg_npass[w] = np; wg_words[w] = words; }
+  if (!EMIT) { wg_npass[w] = np; wg_words[w] = words; wg_quads[w] = quads; }
+  if (EMIT && stats) {
+    // the same slots uncut: the passes and the rounds they had before slots were cut
+    long long crit_uncut = 0;
+    for (a = s0; a < s1;) {
+      int b = a, ent = 0;
+      uncut.start();
+      while (b < s1 && b - a < FOLD_PASS_SLOTS) {
+        const int c = count(b);
+        if (b > a && ((b + 1 - a + 3) & ~3) + ent + c > FOLD_WORDS) break;
+        uncut.quad(c, false);
+        ent += c; b++;
+      }
+      uncut.finish(false);
+      crit_uncut += uncut.crit();
+      a = b;
+    }
+    atomicAdd(stats + 0, (unsigned long long)n_parts); atomicAdd(stats + 1, (unsigned long long)crit);
+    atomicAdd(stats + 2, (unsigned long long)crit_uncut); atomicAdd(stats + 3, (unsigned long long)wave);
+  }
 }
 __global__ __launch_bounds__(256) void k_fold_stream_entries(int E, const int* __restrict__ head, const int* __restrict__ slot_of, const int* __restrict__ slot_ent_first,
                                                               const int* __restrict__ slot_ent_pos, const unsigned* __restrict__ ent, unsigned* __restrict__ stream) {
@@ -2994,7 +3107,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   if (ba->env.no_fold || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < ba->env.fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
   hipStream_t s = ctx->stream;
   DevBuf<char> tmp;
-  DevBuf<int> count, offset, head, slot_of, slot_id, slot_id_s, slot_ent_first, wg_slot_first, perm;
+  DevBuf<int> count, offset, head, slot_of, slot_id, slot_id_s, slot_ent_first, wg_slot_first, perm, slot_quad;
   DevBuf<unsigned long long> key, key_s, slot_key2, slot_key2_s;
   DevBuf<unsigned> val, ent_sorted;
   DevBuf<uint8_t> folded;
@@ -3048,33 +3161,45 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
     DTRY(blk.finish());
   }
+  int nquads = 0;
+  DTRY(slot_quad.alloc(NS));
   {
-    DevBuf<int> wg_npass, wg_words, words_first, slot_ent_pos, too_large;
+    DevBuf<int> wg_npass, wg_words, wg_quads, words_first, quads_first, slot_ent_pos, too_large;
+    DevBuf<unsigned long long> stats;
     DevScope blk(ctx);
-    DTRY(wg_npass.alloc((size_t)n_wg + 1)); DTRY(wg_words.alloc((size_t)n_wg + 1)); DTRY(words_first.alloc((size_t)n_wg + 1));
+    DTRY(wg_npass.alloc((size_t)n_wg + 1)); DTRY(wg_words.alloc((size_t)n_wg + 1)); DTRY(wg_quads.alloc((size_t)n_wg + 1));
+    DTRY(words_first.alloc((size_t)n_wg + 1)); DTRY(quads_first.alloc((size_t)n_wg + 1));
     DTRY(F.wg_pass_first.alloc((size_t)n_wg + 1)); DTRY(slot_ent_pos.alloc(NS));
     DTRY(too_large.alloc(1)); DTRY(hipMemsetAsync(too_large.p, 0, sizeof(int), s));
+    DTRY(stats.alloc(4)); DTRY(hipMemsetAsync(stats.p, 0, 4 * sizeof(unsigned long long), s));
     DTRY(hipMemsetAsync(wg_npass.p + n_wg, 0, sizeof(int), s)); DTRY(hipMemsetAsync(wg_words.p + n_wg, 0, sizeof(int), s));
+    DTRY(hipMemsetAsync(wg_quads.p + n_wg, 0, sizeof(int), s));
     hipLaunchKernelGGL((k_fold_passes<false>), dim3(cdiv(n_wg, 256)), dim3(256), 0, s, n_wg, ncb, wg_slot_first.p, slot_ent_first.p, slot_key2.p, perm.p, wg_npass.p, wg_words.p,
-                       (const int*)nullptr, (const int*)nullptr, (FoldPass*)nullptr, (unsigned*)nullptr, (int*)nullptr, too_large.p);
+                       wg_quads.p, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr, (FoldPass*)nullptr, (unsigned*)nullptr, (int*)nullptr, (int*)nullptr,
+                       (unsigned long long*)nullptr, too_large.p);
     DTRY(excl_scan(wg_npass.p, F.wg_pass_first.p, (size_t)n_wg + 1, s, tmp));
     DTRY(excl_scan(wg_words.p, words_first.p, (size_t)n_wg + 1, s, tmp));
+    DTRY(excl_scan(wg_quads.p, quads_first.p, (size_t)n_wg + 1, s, tmp));
     int npass = 0, nwords = 0, h_too_large = 0;
     DTRY(hipMemcpyAsync(&h_too_large, too_large.p, sizeof(int), hipMemcpyDeviceToHost, s));
     DTRY(hipMemcpyAsync(&npass, F.wg_pass_first.p + n_wg, sizeof(int), hipMemcpyDeviceToHost, s));
     DTRY(hipMemcpyAsync(&nwords, words_first.p + n_wg, sizeof(int), hipMemcpyDeviceToHost, s));
+    DTRY(hipMemcpyAsync(&nquads, quads_first.p + n_wg, sizeof(int), hipMemcpyDeviceToHost, s));
     DTRY(hipStreamSynchronize(s));
-    if (h_too_large || npass < 0 || nwords < 0) {   // (k_fold_passes: a slot too large to stage; nothing has been marked yet)
+    if (h_too_large || npass < 0 || nwords < 0 || nquads < 0) {   // (k_fold_passes: a slot too large to stage; nothing has been marked yet)
       blk.dismiss(); sc.dismiss();   // (behind the wait above)
       return MSFM_OK;
     }
     DTRY(F.pass.alloc((size_t)std::max(1, npass))); DTRY(F.stream.alloc((size_t)nwords + FOLD_WORDS));
     DTRY(hipMemsetAsync(F.stream.p, 0, sizeof(unsigned) * ((size_t)nwords + FOLD_WORDS), s));
     hipLaunchKernelGGL((k_fold_passes<true>), dim3(cdiv(n_wg, 256)), dim3(256), 0, s, n_wg, ncb, wg_slot_first.p, slot_ent_first.p, slot_key2.p, perm.p, (int*)nullptr, (int*)nullptr,
-                       F.wg_pass_first.p, words_first.p, F.pass.p, F.stream.p, slot_ent_pos.p, (int*)nullptr);
+                       (int*)nullptr, F.wg_pass_first.p, words_first.p, quads_first.p, F.pass.p, F.stream.p, slot_ent_pos.p, slot_quad.p, stats.p, (int*)nullptr);
     hipLaunchKernelGGL(k_fold_stream_entries, dim3(cdiv(E, 256)), dim3(256), 0, s, E, head.p, slot_of.p, slot_ent_first.p, slot_ent_pos.p, ent_sorted.p, F.stream.p);
+    unsigned long long h_stats[4] = {0, 0, 0, 0};
+    DTRY(hipMemcpyAsync(h_stats, stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, s));
     F.n_pass = npass;
     DTRY(blk.finish());
+    F.n_parts = (long long)h_stats[0]; F.crit_steps = (long long)h_stats[1]; F.crit_steps_unsplit = (long long)h_stats[2]; F.wave_steps = (long long)h_stats[3];
   }
   {
     size_t bytes = 0;
@@ -3083,11 +3208,12 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, slot_key2.p, slot_key2_s.p, slot_id.p, slot_id_s.p, (size_t)NS, 0, 64, s));
   }
   {
-    DevBuf<int> rank;   // by slot; k_point asks by position inside the workgroup's passes
+    DevBuf<int> rank;   // by slot; k_point asks by quad inside the workgroup's passes
     DevScope blk(ctx);
-    DTRY(rank.alloc(NS)); DTRY(F.slot_rank.alloc(NS));
+    DTRY(rank.alloc(NS)); DTRY(F.slot_rank.alloc((size_t)std::max(1, nquads)));
+    DTRY(hipMemsetAsync(F.slot_rank.p, 0, sizeof(int) * (size_t)std::max(1, nquads), s));
     hipLaunchKernelGGL(k_fold_rank, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, slot_id_s.p, rank.p);
-    hipLaunchKernelGGL(k_fold_gather_rank, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, perm.p, rank.p, F.slot_rank.p);
+    hipLaunchKernelGGL(k_fold_quad_rank, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, slot_quad.p, rank.p, F.slot_rank.p);
     DTRY(blk.finish());
   }
   DTRY(F.blk_range.alloc(2 * (size_t)std::max(1, ba->cc.n_blocks)));
@@ -3978,6 +4104,8 @@ MSFM_API int msfm_ba_get_layout(const msfm_ba* ba, msfm_ba_layout* out) {
     out->cc_entries_folded = ba->fold.n_entries;
     out->fold_slots = ba->fold.n_slots;
     out->fold_passes = ba->fold.n_pass;
+    out->fold_parts = ba->fold.n_parts; out->fold_crit_steps = ba->fold.crit_steps;
+    out->fold_crit_steps_unsplit = ba->fold.crit_steps_unsplit; out->fold_wave_steps = ba->fold.wave_steps;
     if (ba->fold.mc_on) { out->mc_entries_folded = ba->fold.mc_entries_folded; out->fold_mc_slots = ba->fold.n_diag; }
   }
   out->solve_paths = ba->solve_paths;

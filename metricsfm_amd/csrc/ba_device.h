@@ -245,6 +245,8 @@ __device__ __forceinline__ double dpp_f64(double v) {
 #define MSFM_DPP_XOR2 0x4E          // quad_perm [2,3,0,1]
 #define MSFM_DPP_ROR8 0x128         // row_ror:8 = lane ^ 8 inside a row
 #define MSFM_DPP_HALF_MIRROR 0x141  // lane -> 7 - lane inside each half row
+#define MSFM_DPP_SHL4 0x104         // row_shl:4 = from lane + 4 of the row (the next quad); the row's last quad gets 0
+#define MSFM_DPP_SHL8 0x108         // row_shl:8 = from lane + 8 of the row; the row's upper half gets 0
 __device__ __forceinline__ int dpp_xor4_b32(int x) {
   // lane ^ 4: quads 0 and 2 take from the quad above (row_shl:4), quads 1 and 3 from the quad below (row_shr:4)
   const int t = __builtin_amdgcn_update_dpp(0, x, 0x104, 0xf, 0x5, false);
