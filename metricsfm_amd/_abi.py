@@ -203,9 +203,7 @@ class KernelStat(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
 
-ITER_DTYPE = np.dtype([("cost", "f8"), ("cost_change", "f8"), ("gradient_max_norm", "f8"), ("step_norm", "f8"),
-                       ("relative_decrease", "f8"), ("trust_region_radius", "f8"), ("step_is_valid", "i4"),
-                       ("step_is_successful", "i4")])
+ITER_DTYPE = np.dtype(BaIteration)
 
 
 def ptr(a, typ):

@@ -6,51 +6,17 @@ import os
 import numpy as np
 
 from . import _abi as A
+from . import _header
+from ._header import ALLREDUCE_FN  # noqa: F401  (part of this module's interface)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSFM_LIB") or os.path.join(_HERE, "libmsfm.so")   # (MSFM_LIB: a differently built libmsfm, for A/B timing)
 _lib = None
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p)
-
-# every symbol include/msfm.h declares (checked by tests/test_abi.py against the header text)
-SYMBOLS = [
-    "msfm_version", "msfm_ctx_create", "msfm_ctx_destroy", "msfm_last_error", "msfm_ctx_stream",
-    "msfm_ctx_synchronize", "msfm_ctx_profile_enable", "msfm_ctx_profile_reset", "msfm_ctx_profile_get",
-    "msfm_knn2_f32", "msfm_descset_create", "msfm_descset_upload", "msfm_descset_count", "msfm_descset_destroy",
-    "msfm_match_pairs", "msfm_match_result_counts", "msfm_match_result_fetch", "msfm_match_result_stats", "msfm_match_result_destroy",
-    "msfm_match_pairs_rerun", "msfm_descset_upload_keypoints", "msfm_slam_match_default_options", "msfm_match_pairs_slam",
-    "msfm_chain_create", "msfm_chain_verify", "msfm_chain_verify_slam", "msfm_chain_matches", "msfm_chain_fetch_matches", "msfm_chain_build_tracks",
-    "msfm_chain_fetch_tracks", "msfm_chain_triangulate", "msfm_chain_fetch_points", "msfm_chain_ba_create", "msfm_chain_fetch_point_tracks",
-    "msfm_chain_destroy",
-    "msfm_gpsreg_default_options", "msfm_gps_orient_global", "msfm_point_accuracy_batch", "msfm_gps_register_points",
-    "msfm_chain_accuracy", "msfm_chain_fetch_accuracy", "msfm_chain_gps_register", "msfm_chain_ba_create_gps", "msfm_chain_store_points",
-    "msfm_match_store_create", "msfm_match_store_from_chain", "msfm_match_store_destroy", "msfm_localize_candidates",
-    "msfm_localize_set_size", "msfm_localize_set_fetch", "msfm_localize_set_destroy",
-    "msfm_localize_pose_default_options", "msfm_localize_poses", "msfm_localize_pose_set_size", "msfm_localize_pose_set_fetch",
-    "msfm_localize_pose_set_destroy",
-    "msfm_seed_default_options", "msfm_seed_hypotheses", "msfm_seed_set_size", "msfm_seed_set_fetch", "msfm_seed_set_destroy",
-    "msfm_new_points_default_options", "msfm_new_points", "msfm_new_points_set_size", "msfm_new_points_set_fetch", "msfm_new_points_set_destroy",
-    "msfm_round_default_options", "msfm_round_adjust", "msfm_round_set_size", "msfm_round_set_fetch", "msfm_round_set_fetch_problem",
-    "msfm_round_set_destroy",
-    "msfm_recon_create", "msfm_recon_size", "msfm_recon_fetch", "msfm_recon_adjust", "msfm_recon_new_points", "msfm_recon_localize", "msfm_recon_localize_fetch",
-    "msfm_recon_commit_camera",
-    "msfm_recon_destroy",
-    "msfm_ba_options_default", "msfm_ba_solve", "msfm_ba_create", "msfm_ba_run",
-    "msfm_ba_upload_params", "msfm_ba_download_params", "msfm_ba_destroy", "msfm_ba_get_layout", "msfm_camera_graph_dissection", "msfm_ctx_set_allreduce",
-    "msfm_triangulate_midpoint_batch", "msfm_triangulate_dlt_batch", "msfm_reproject_mse_batch",
-    "msfm_epipolar_filter", "msfm_fransac_default_options", "msfm_fundamental_ransac_batch",
-    "msfm_pair_select_default_options", "msfm_wordset_create", "msfm_wordset_size", "msfm_wordset_fetch", "msfm_wordset_destroy",
-    "msfm_pair_select", "msfm_pair_set_size", "msfm_pair_set_fetch", "msfm_pair_set_destroy",
-    "msfm_voctree_create", "msfm_voctree_size", "msfm_voctree_destroy", "msfm_descset_words", "msfm_word_result_size",
-    "msfm_word_result_fetch", "msfm_word_result_destroy", "msfm_wordset_create_from_words",
-    "msfm_epipolar_filter_batch", "msfm_hransac_default_options", "msfm_homography_ransac_batch", "msfm_slam_prior_default_options",
-    "msfm_slam_priors", "msfm_tracks_build", "msfm_tracks_build_device", "msfm_track_set_size", "msfm_track_set_fetch", "msfm_track_set_destroy",
-    "msfm_epnp_ransac_batch", "msfm_epnpf_default_options", "msfm_epnpf_num_steps", "msfm_epnpf_sweep_batch",
-    "msfm_relpose_5pt_batch", "msfm_relpose_8pt_batch", "msfm_rccl_get_unique_id", "msfm_ctx_init_rccl", "msfm_ctx_allreduce",
-    "msfm_ctx_create_multi", "msfm_multi_destroy", "msfm_multi_size", "msfm_multi_ctx", "msfm_multi_last_error", "msfm_multi_ba_solve",
-    "msfm_multi_triangulate_midpoint_batch", "msfm_multi_triangulate_dlt_batch", "msfm_multi_reproject_mse_batch", "msfm_multi_match_pairs",
-]
+# {name: (restype, argtypes)} of every function include/msfm.h declares, and their names
+with open(_header.HEADER) as _f:
+    PROTOTYPES = _header.prototypes(_f.read())
+SYMBOLS = list(PROTOTYPES)
 
 
 class MsfmError(RuntimeError):
@@ -61,289 +27,87 @@ class MsfmError(RuntimeError):
 
 def lib():
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
-                          "`make -C metricsfm_amd/csrc` (no CPU fallback exists)" % LIB_PATH)
-    L = C.CDLL(LIB_PATH)
-    vp, i, d, f = C.c_void_p, C.c_int, C.c_double, C.c_float
-    L.msfm_version.restype = i
-    L.msfm_ctx_create.argtypes = [i, C.POINTER(vp)]
-    L.msfm_ctx_destroy.argtypes = [vp]
-    L.msfm_ctx_destroy.restype = None
-    L.msfm_last_error.argtypes = [vp]
-    L.msfm_last_error.restype = C.c_char_p
-    L.msfm_ctx_stream.argtypes = [vp]
-    L.msfm_ctx_stream.restype = vp
-    L.msfm_ctx_synchronize.argtypes = [vp]
-    L.msfm_ctx_profile_enable.argtypes = [vp, i]
-    L.msfm_ctx_profile_reset.argtypes = [vp]
-    L.msfm_ctx_profile_get.argtypes = [vp, C.POINTER(A.KernelStat), i, C.POINTER(i)]
-    L.msfm_knn2_f32.argtypes = [vp, A.c_float_p, i, A.c_float_p, i, i, A.c_int_p, A.c_float_p]
-    L.msfm_descset_create.argtypes = [vp, i, i, C.POINTER(vp)]
-    L.msfm_descset_upload.argtypes = [vp, i, A.c_float_p, i]
-    L.msfm_descset_count.argtypes = [vp, i]
-    L.msfm_descset_destroy.argtypes = [vp]
-    L.msfm_descset_destroy.restype = None
-    L.msfm_match_pairs.argtypes = [vp, A.c_int_p, i, f, f, i, C.POINTER(vp)]
-    L.msfm_match_pairs_rerun.argtypes = [vp, vp]
-    L.msfm_descset_upload_keypoints.argtypes = [vp, i, A.c_float_p, i]
-    L.msfm_slam_match_default_options.argtypes = [C.POINTER(A.SlamMatchOptions)]
-    L.msfm_slam_match_default_options.restype = None
-    L.msfm_match_pairs_slam.argtypes = [vp, A.c_int_p, i, A.c_double_p, A.c_double_p, C.POINTER(A.SlamMatchOptions), i, C.POINTER(vp)]
-    L.msfm_match_result_counts.argtypes = [vp, A.c_int_p, A.c_int_p]
-    L.msfm_match_result_fetch.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_float_p]
-    L.msfm_match_result_stats.argtypes = [vp, A.c_int_p, A.c_int_p]
-    L.msfm_match_result_destroy.argtypes = [vp]
-    L.msfm_match_result_destroy.restype = None
-    L.msfm_ba_options_default.argtypes = [C.POINTER(A.BaOptions)]
-    L.msfm_ba_options_default.restype = None
-    L.msfm_ba_solve.argtypes = [vp, C.POINTER(A.BaProblem), C.POINTER(A.BaOptions), C.POINTER(A.BaSummary)]
-    L.msfm_ba_create.argtypes = [vp, C.POINTER(A.BaProblem), C.POINTER(vp)]
-    L.msfm_ba_run.argtypes = [vp, C.POINTER(A.BaOptions), C.POINTER(A.BaSummary)]
-    L.msfm_ba_upload_params.argtypes = [vp, A.c_double_p, A.c_double_p, A.c_double_p]
-    L.msfm_ba_download_params.argtypes = [vp, A.c_double_p, A.c_double_p, A.c_double_p]
-    L.msfm_ba_destroy.argtypes = [vp]
-    L.msfm_ba_destroy.restype = None
-    L.msfm_ctx_set_allreduce.argtypes = [vp, ALLREDUCE_FN, vp, i, i]
-    for fn in (L.msfm_triangulate_midpoint_batch, L.msfm_triangulate_dlt_batch):
-        fn.argtypes = [vp, C.POINTER(A.Tracks), d, d, A.c_double_p, A.c_double_p, A.c_u8_p]
-    L.msfm_reproject_mse_batch.argtypes = [vp, C.POINTER(A.Tracks), A.c_double_p, A.c_double_p]
-    L.msfm_epipolar_filter.argtypes = [vp, A.c_float_p, A.c_float_p, i, A.c_double_p, d, A.c_u8_p]
-    L.msfm_ba_get_layout.argtypes = [vp, C.POINTER(A.BaLayout)]
-    L.msfm_camera_graph_dissection.argtypes = [i, vp, i, i, vp, C.POINTER(i), C.POINTER(i)]
-    L.msfm_fransac_default_options.argtypes = [C.POINTER(A.FransacOptions)]
-    L.msfm_fransac_default_options.restype = None
-    L.msfm_fundamental_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, C.POINTER(A.FransacOptions),
-                                                A.c_double_p, A.c_u8_p, A.c_int_p, A.c_u8_p]
-    L.msfm_hransac_default_options.argtypes = [C.POINTER(A.HransacOptions)]
-    L.msfm_hransac_default_options.restype = None
-    L.msfm_homography_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, C.POINTER(A.HransacOptions),
-                                               A.c_double_p, A.c_u8_p, A.c_int_p, A.c_u8_p]
-    L.msfm_slam_prior_default_options.argtypes = [C.POINTER(A.SlamPriorOptions)]
-    L.msfm_slam_prior_default_options.restype = None
-    L.msfm_slam_priors.argtypes = [vp, C.POINTER(A.Tracks), C.POINTER(A.SlamPriorOptions), C.POINTER(i), A.c_int_p, A.c_double_p,
-                                   A.c_double_p, C.POINTER(i), A.c_int_p]
-    L.msfm_epipolar_filter_batch.argtypes = [vp, i, A.c_int_p, A.c_float_p, A.c_float_p, A.c_double_p, A.c_u8_p, d, A.c_u8_p]
-    L.msfm_epnp_ransac_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64, A.c_double_p,
-                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p]
-    L.msfm_epnpf_default_options.argtypes = [C.POINTER(A.EpnpfOptions)]
-    L.msfm_epnpf_default_options.restype = None
-    L.msfm_epnpf_num_steps.argtypes = [C.POINTER(A.EpnpfOptions)]
-    L.msfm_epnpf_sweep_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, C.POINTER(A.EpnpfOptions),
-                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p, A.c_int_p,
-                                         A.c_double_p]
-    L.msfm_relpose_5pt_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, i, C.c_uint64,
-                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_u8_p, A.c_int_p]
-    L.msfm_relpose_8pt_batch.argtypes = [vp, i, A.c_int_p, A.c_double_p, A.c_double_p, i, C.c_uint64, A.c_double_p, A.c_double_p,
-                                         A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_u8_p, A.c_int_p, A.c_double_p,
-                                         A.c_int_p]
-    L.msfm_rccl_get_unique_id.argtypes = [vp, C.POINTER(C.c_ubyte)]
-    L.msfm_ctx_init_rccl.argtypes = [vp, C.POINTER(C.c_ubyte), i, i]
-    L.msfm_ctx_allreduce.argtypes = [vp, vp, C.c_size_t, i]
-    L.msfm_tracks_build.argtypes = [i, A.c_int_p, i, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(vp)]
-    L.msfm_tracks_build_device.argtypes = [vp, i, A.c_int_p, i, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(vp)]
-    L.msfm_track_set_size.argtypes = [vp, A.c_int_p, A.c_int_p]
-    L.msfm_track_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p]
-    L.msfm_track_set_destroy.argtypes = [vp]
-    L.msfm_track_set_destroy.restype = None
-    L.msfm_chain_create.argtypes = [vp, C.POINTER(vp)]
-    L.msfm_chain_verify.argtypes = [vp, vp, C.POINTER(A.FransacOptions), d]
-    L.msfm_chain_verify_slam.argtypes = [vp, vp, C.POINTER(A.FransacOptions)]
-    L.msfm_chain_matches.argtypes = [vp, A.c_int_p, A.c_u8_p, A.c_double_p]
-    L.msfm_chain_fetch_matches.argtypes = [vp, i, A.c_int_p]
-    L.msfm_chain_build_tracks.argtypes = [vp, A.c_int_p, A.c_int_p]
-    L.msfm_chain_fetch_tracks.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p]
-    L.msfm_chain_triangulate.argtypes = [vp, i, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, d, d, A.c_int_p]
-    L.msfm_chain_fetch_points.argtypes = [vp, A.c_double_p, A.c_double_p, A.c_u8_p]
-    L.msfm_chain_ba_create.argtypes = [vp, i, i, A.c_double_p, A.c_double_p, A.c_int_p, i, d, C.POINTER(vp), A.c_int_p, A.c_int_p]
-    L.msfm_chain_fetch_point_tracks.argtypes = [vp, A.c_int_p]
-    L.msfm_chain_destroy.argtypes = [vp]
-    L.msfm_chain_destroy.restype = None
-    L.msfm_gpsreg_default_options.argtypes = [C.POINTER(A.GpsregOptions)]
-    L.msfm_gpsreg_default_options.restype = None
-    L.msfm_gps_orient_global.argtypes = [i, A.c_double_p, A.c_double_p, A.c_double_p, C.POINTER(A.GpsregOptions), C.POINTER(A.GpsOrientResult)]
-    L.msfm_point_accuracy_batch.argtypes = [vp, C.POINTER(A.Tracks), A.c_double_p, A.c_double_p, A.c_u8_p, i, d, A.c_double_p, A.c_double_p,
-                                            A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p]
-    L.msfm_gps_register_points.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_u8_p, i, A.c_double_p, A.c_double_p, A.c_double_p]
-    L.msfm_chain_accuracy.argtypes = [vp, i, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, i, d, A.c_int_p, A.c_int_p]
-    L.msfm_chain_fetch_accuracy.argtypes = [vp, A.c_double_p, A.c_double_p, A.c_int_p]
-    L.msfm_chain_gps_register.argtypes = [vp, i, A.c_double_p, A.c_double_p]
-    L.msfm_chain_ba_create_gps.argtypes = [vp, i, i, A.c_double_p, A.c_double_p, A.c_int_p, i, d, A.c_double_p, d, A.c_double_p, C.POINTER(vp),
-                                           A.c_int_p, A.c_int_p]
-    L.msfm_chain_store_points.argtypes = [vp, vp]
-    L.msfm_match_store_create.argtypes = [vp, i, A.c_int_p, i, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(vp)]
-    L.msfm_match_store_from_chain.argtypes = [vp, C.POINTER(vp)]
-    L.msfm_match_store_destroy.argtypes = [vp]
-    L.msfm_match_store_destroy.restype = None
-    L.msfm_localize_candidates.argtypes = [vp, vp, C.POINTER(A.LocalizeProblem), C.POINTER(vp)]
-    L.msfm_localize_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
-    L.msfm_localize_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
-    L.msfm_localize_set_destroy.argtypes = [vp]
-    L.msfm_localize_set_destroy.restype = None
-    L.msfm_localize_pose_default_options.argtypes = [C.POINTER(A.LocalizePoseOptions)]
-    L.msfm_localize_pose_default_options.restype = None
-    L.msfm_localize_poses.argtypes = [vp, vp, A.c_double_p, A.c_double_p, C.c_int, A.c_u8_p, C.POINTER(A.LocalizePoseOptions), C.POINTER(vp)]
-    L.msfm_localize_pose_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p]
-    L.msfm_localize_pose_set_fetch.argtypes = [vp, A.c_u8_p, A.c_u8_p, A.c_u8_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_int_p,
-                                               A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_u8_p]
-    L.msfm_localize_pose_set_destroy.argtypes = [vp]
-    L.msfm_localize_pose_set_destroy.restype = None
-    L.msfm_seed_default_options.argtypes = [C.POINTER(A.SeedOptions)]
-    L.msfm_seed_default_options.restype = None
-    L.msfm_seed_hypotheses.argtypes = [vp, vp, C.POINTER(A.SeedProblem), C.POINTER(A.SeedOptions), C.POINTER(vp)]
-    L.msfm_seed_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
-    L.msfm_seed_set_fetch.argtypes = [vp, A.c_u8_p, A.c_u8_p, A.c_u8_p, A.c_int_p, A.c_double_p, A.c_double_p, A.c_double_p, A.c_double_p,
-                                      A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p]
-    L.msfm_seed_set_destroy.argtypes = [vp]
-    L.msfm_seed_set_destroy.restype = None
-    L.msfm_new_points_default_options.argtypes = [C.POINTER(A.NewPointsOptions)]
-    L.msfm_new_points_default_options.restype = None
-    L.msfm_new_points.argtypes = [vp, vp, C.POINTER(A.NewPointsProblem), C.POINTER(A.NewPointsOptions), C.POINTER(vp)]
-    L.msfm_new_points_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
-    L.msfm_new_points_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p,
-                                            A.c_u8_p, A.c_u8_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p]
-    L.msfm_new_points_set_destroy.argtypes = [vp]
-    L.msfm_new_points_set_destroy.restype = None
-    L.msfm_round_default_options.argtypes = [C.POINTER(A.RoundOptions)]
-    L.msfm_round_default_options.restype = None
-    L.msfm_round_adjust.argtypes = [vp, vp, C.POINTER(A.RoundProblem), C.POINTER(A.RoundOptions), C.POINTER(vp)]
-    L.msfm_round_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, C.POINTER(C.c_int64)]
-    L.msfm_round_set_fetch.argtypes = [vp] + [A.c_double_p] * 7 + [A.c_u8_p, A.c_u8_p, A.c_double_p, A.c_u8_p, A.c_int_p, A.c_int_p, A.c_int_p,
-                                              A.c_int_p, C.POINTER(A.BaSummary)]
-    L.msfm_round_set_fetch_problem.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p, A.c_u8_p,
-                                               A.c_u8_p]
-    L.msfm_round_set_destroy.argtypes = [vp]
-    L.msfm_round_set_destroy.restype = None
-    i64p = C.POINTER(C.c_int64)
-    L.msfm_pair_select_default_options.argtypes = [C.POINTER(A.PairSelectOptions)]
-    L.msfm_pair_select_default_options.restype = None
-    L.msfm_wordset_create.argtypes = [vp, i, A.c_int_p, A.c_u8_p, A.c_int_p, i, A.c_float_p, i, C.POINTER(vp)]
-    L.msfm_wordset_size.argtypes = [vp, A.c_int_p, A.c_int_p, i64p, i64p, i64p]
-    L.msfm_wordset_fetch.argtypes = [vp] + [A.c_int_p] * 6
-    L.msfm_wordset_destroy.argtypes = [vp]
-    L.msfm_wordset_destroy.restype = None
-    L.msfm_pair_select.argtypes = [vp, i, i, C.POINTER(A.PairSelectOptions), C.POINTER(vp)]
-    L.msfm_voctree_create.argtypes = [vp, i, i, C.POINTER(C.c_uint16), A.c_float_p, C.POINTER(C.c_uint32), A.c_float_p, C.POINTER(vp)]
-    L.msfm_voctree_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, i64p, i64p]
-    L.msfm_voctree_destroy.argtypes = [vp]
-    L.msfm_voctree_destroy.restype = None
-    L.msfm_descset_words.argtypes = [vp, vp, i, C.POINTER(vp)]
-    L.msfm_word_result_size.argtypes = [vp, A.c_int_p, i64p, i64p, A.c_int_p, i64p]
-    L.msfm_word_result_fetch.argtypes = [vp, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, A.c_float_p]
-    L.msfm_word_result_destroy.argtypes = [vp]
-    L.msfm_word_result_destroy.restype = None
-    L.msfm_wordset_create_from_words.argtypes = [vp, vp, i, C.POINTER(vp)]
-    L.msfm_pair_set_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, i64p]
-    L.msfm_pair_set_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_u8_p, A.c_int_p, A.c_double_p, A.c_int_p, A.c_int_p, A.c_u8_p]
-    L.msfm_pair_set_destroy.argtypes = [vp]
-    L.msfm_pair_set_destroy.restype = None
-    L.msfm_recon_create.argtypes = [vp, vp, C.POINTER(A.ReconInit), C.POINTER(vp)]
-    L.msfm_recon_size.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p, A.c_int_p, i64p, i64p, i64p]
-    L.msfm_recon_fetch.argtypes = [vp] + [A.c_int_p] * 5 + [A.c_double_p, A.c_u8_p, A.c_double_p, A.c_int_p, A.c_u8_p, A.c_u8_p, A.c_double_p,
-                                          A.c_double_p, A.c_int_p] + [A.c_double_p] * 4
-    L.msfm_recon_adjust.argtypes = [vp, i, i, A.c_int_p, i, i, i, C.POINTER(A.RoundOptions), C.POINTER(vp)]
-    L.msfm_recon_new_points.argtypes = [vp, i, i, A.c_int_p, C.POINTER(A.NewPointsOptions), A.c_int_p, C.POINTER(vp)]
-    L.msfm_recon_localize.argtypes = [vp, i, A.c_int_p, A.c_int_p, A.c_double_p, A.c_double_p, C.POINTER(A.LocalizePoseOptions), C.POINTER(A.ReconWinner)]
-    L.msfm_recon_localize_fetch.argtypes = [vp, A.c_int_p, A.c_int_p, A.c_int_p]
-    L.msfm_recon_commit_camera.argtypes = [vp, A.c_double_p, i, A.c_double_p, i, A.c_int_p, A.c_int_p]
-    L.msfm_recon_destroy.argtypes = [vp]
-    L.msfm_recon_destroy.restype = None
-    L.msfm_ctx_create_multi.argtypes = [i, A.c_int_p, C.POINTER(vp)]
-    L.msfm_multi_destroy.argtypes = [vp]
-    L.msfm_multi_destroy.restype = None
-    L.msfm_multi_size.argtypes = [vp]
-    L.msfm_multi_ctx.argtypes = [vp, i]
-    L.msfm_multi_ctx.restype = vp
-    L.msfm_multi_last_error.argtypes = [vp]
-    L.msfm_multi_last_error.restype = C.c_char_p
-    L.msfm_multi_ba_solve.argtypes = [vp, C.POINTER(A.BaProblem), C.POINTER(A.BaOptions), C.POINTER(A.BaSummary)]
-    L.msfm_multi_triangulate_midpoint_batch.argtypes = [vp, C.POINTER(A.Tracks), d, d, A.c_double_p, A.c_double_p, A.c_u8_p]
-    L.msfm_multi_triangulate_dlt_batch.argtypes = [vp, C.POINTER(A.Tracks), d, d, A.c_double_p, A.c_double_p, A.c_u8_p]
-    L.msfm_multi_reproject_mse_batch.argtypes = [vp, C.POINTER(A.Tracks), A.c_double_p, A.c_double_p]
-    L.msfm_multi_match_pairs.argtypes = [vp, i, C.POINTER(A.c_float_p), A.c_int_p, i, A.c_int_p, i, f, f, C.POINTER(A.c_int_p), A.c_int_p, A.c_int_p]
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError("%s not built: run `python -c 'import __graft_entry__ as g; g.build()'` or "
+                              "`make -C metricsfm_amd/csrc` (no CPU fallback exists)" % LIB_PATH)
+        _lib = _header.bind(C.CDLL(LIB_PATH), PROTOTYPES)
+    return _lib
 
 
-def default_options(**kw):
-    o = A.BaOptions()
-    lib().msfm_ba_options_default(C.byref(o))
+def _set_fields(o, kw):
     for k, v in kw.items():
         if not hasattr(o, k):
             raise AttributeError(k)
-        setattr(o, k, v)
+        if isinstance(v, dict) and isinstance(getattr(o, k), C.Structure):
+            _set_fields(getattr(o, k), v)
+        else:
+            setattr(o, k, v)
+
+
+def _options(struct_cls, default_fn_name, kw):
+    """struct_cls as the library's default function fills it, then the fields kw names; a nested struct takes a dict of its fields."""
+    o = struct_cls()
+    getattr(lib(), default_fn_name)(C.byref(o))
+    _set_fields(o, kw)
     return o
+
+
+class _Handle:
+    """Owns the library handle `_h`; `close` (also at the end of a `with` block and on collection) hands it to the destroy
+    function `_destroy` names.  As it stands it holds a short-lived result: `with _Handle(h, "msfm_x_set_destroy"): ...`."""
+    _destroy = None
+
+    def __init__(self, h, destroy):
+        self._h, self._destroy = h, destroy
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._destroy)(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def default_options(**kw):
+    return _options(A.BaOptions, "msfm_ba_options_default", kw)
 
 
 def epnpf_options(**kw):
     """msfm_epnpf_options with the reference's values (0.5, 4.0, 0.01, 200 samples); keywords override fields."""
-    o = A.EpnpfOptions()
-    lib().msfm_epnpf_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.EpnpfOptions, "msfm_epnpf_default_options", kw)
 
 
 def localize_pose_options(**kw):
     """msfm_localize_pose_options with the reference's values (5.0 px, 20 correspondences, 200 samples, the default sweep, 16 tries);
     keywords override fields, `sweep` takes a dict of msfm_epnpf_options fields."""
-    o = A.LocalizePoseOptions()
-    lib().msfm_localize_pose_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        if k == "sweep" and isinstance(v, dict):
-            for sk, sv in v.items():
-                if not hasattr(o.sweep, sk):
-                    raise AttributeError(sk)
-                setattr(o.sweep, sk, sv)
-        else:
-            setattr(o, k, v)
-    return o
+    return _options(A.LocalizePoseOptions, "msfm_localize_pose_default_options", kw)
 
 
 def seed_options(**kw):
     """msfm_seed_options with the reference's values (3.0 px, 3 degrees, 20 points, 100 / 200 samples); keywords override fields."""
-    o = A.SeedOptions()
-    lib().msfm_seed_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.SeedOptions, "msfm_seed_default_options", kw)
 
 
 def new_points_options(**kw):
     """msfm_new_points_options with the reference's values (3.0 px, 3 and 5 degrees, 500 matches); keywords override fields."""
-    o = A.NewPointsOptions()
-    lib().msfm_new_points_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.NewPointsOptions, "msfm_new_points_default_options", kw)
 
 
 def round_options(**kw):
     """msfm_round_options with the reference's values (100 iterations for both solves, weights 2.0 / 1.0, 1.0 px); keywords
     override fields, `partial` / `full` take a dict of msfm_ba_options fields."""
-    o = A.RoundOptions()
-    lib().msfm_round_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        if k in ("partial", "full") and isinstance(v, dict):
-            for sk, sv in v.items():
-                if not hasattr(getattr(o, k), sk):
-                    raise AttributeError(sk)
-                setattr(getattr(o, k), sk, sv)
-        else:
-            setattr(o, k, v)
-    return o
+    return _options(A.RoundOptions, "msfm_round_default_options", kw)
 
 
 def epnpf_num_steps(**kw):
@@ -353,13 +117,7 @@ def epnpf_num_steps(**kw):
 
 def gpsreg_options(**kw):
     """msfm_gpsreg_options with the reference's values (window 20, min_views 3, clip 80 degrees, th_outlier 3.0)."""
-    o = A.GpsregOptions()
-    lib().msfm_gpsreg_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.GpsregOptions, "msfm_gpsreg_default_options", kw)
 
 
 def gps_orient_global(cam_R, cam_c, gps, **opts):
@@ -396,14 +154,12 @@ def _flatten_matches(n_features, pairs, matches_per_pair):
 
 
 def _fetch_track_set(h):
-    try:
+    with _Handle(h, "msfm_track_set_destroy"):
         nt, no = C.c_int32(), C.c_int32()
         lib().msfm_track_set_size(h, C.byref(nt), C.byref(no))
         toff = np.zeros(nt.value + 1, dtype=np.int32)
         oi, of = np.zeros(max(1, no.value), dtype=np.int32), np.zeros(max(1, no.value), dtype=np.int32)
         lib().msfm_track_set_fetch(h, A.ptr(toff, A.c_int_p), A.ptr(oi, A.c_int_p), A.ptr(of, A.c_int_p))
-    finally:
-        lib().msfm_track_set_destroy(h)
     return toff, oi[:no.value], of[:no.value]
 
 
@@ -435,48 +191,22 @@ def build_tracks_flat(n_features, pairs, match_off, matches):
 
 
 def fransac_options(**kw):
-    o = A.FransacOptions()
-    lib().msfm_fransac_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.FransacOptions, "msfm_fransac_default_options", kw)
 
 
 def pair_select_options(**kw):
     """msfm_pair_select_options with the reference's values (30 joined matches, more than 20 inliers, the set's K); keywords
     override fields, and the fields of msfm_fransac_options go to `fransac`."""
-    o = A.PairSelectOptions()
-    lib().msfm_pair_select_default_options(C.byref(o))
-    for k, v in kw.items():
-        if k != "fransac" and hasattr(o, k):
-            setattr(o, k, v)
-        elif hasattr(o.fransac, k):
-            setattr(o.fransac, k, v)
-        else:
-            raise AttributeError(k)
-    return o
+    own = {k: v for k, v in kw.items() if k != "fransac" and hasattr(A.PairSelectOptions, k)}
+    return _options(A.PairSelectOptions, "msfm_pair_select_default_options", dict(own, fransac={k: kw[k] for k in kw if k not in own}))
 
 
 def hransac_options(**kw):
-    o = A.HransacOptions()
-    lib().msfm_hransac_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.HransacOptions, "msfm_hransac_default_options", kw)
 
 
 def slam_prior_options(**kw):
-    o = A.SlamPriorOptions()
-    lib().msfm_slam_prior_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise AttributeError(k)
-        setattr(o, k, v)
-    return o
+    return _options(A.SlamPriorOptions, "msfm_slam_prior_default_options", kw)
 
 
 def _new_points_set_result(h, nn):
@@ -542,8 +272,9 @@ def _round_set_result(ctx, h, nc, nm, npt, partial, full, keep_problem, capacity
     return out
 
 
-class Context:
+class Context(_Handle):
     """One per GPU (one process per GPU)."""
+    _destroy = "msfm_ctx_destroy"
 
     def __init__(self, device=-1):
         self._h = C.c_void_p()
@@ -551,23 +282,6 @@ class Context:
         if rc != 0:
             raise MsfmError(rc, "msfm_ctx_create failed (no visible GPU? libmsfm has no CPU fallback)")
         self._cb = None
-
-    def close(self):
-        if self._h:
-            lib().msfm_ctx_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def check(self, rc):
         if rc != 0:
@@ -623,7 +337,7 @@ class Context:
 
     def allreduce(self, dev_ptr, count, op=0):
         """msfm_ctx_allreduce on a device buffer of doubles (op 0 = sum, 1 = max), ordered on the context's stream."""
-        self.check(lib().msfm_ctx_allreduce(self._h, dev_ptr, count, op))
+        self.check(lib().msfm_ctx_allreduce(self._h, C.cast(dev_ptr, A.c_double_p), count, op))
 
     # -- matching --
     def knn2(self, train, query):
@@ -719,11 +433,9 @@ class Context:
         image, ranked.  Returns a dict: rank [n_kept] (indices into cand_img), corr_off, corr_feat, corr_point, vis_off, vis_cam,
         h2d_bytes and, with point_xyz, pts_w [n_corr][3] / pts_2d [n_corr][2] (offsets = corr_off for `epnp_ransac`).
         keypoints: flat float [sum of n_features][2] for a store that was not made from a chain."""
-        st = self.localize_set(store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=point_xyz, keypoints=keypoints)
-        try:
+        with self.localize_set(store, cam_img, feat_point, pt_bad, pt_mse, pt_views, cand_img, fail_times, point_xyz=point_xyz,
+                               keypoints=keypoints) as st:
             return st.fetch()
-        finally:
-            st.close()
 
     def seed_hypotheses(self, store, hyp_img, cam_fk, same_model, keypoints=None, **opts):
         """msfm_seed_hypotheses (sfm_incremental.cc:235-390): pose, two-view points and the two gates of every seed-pair
@@ -743,7 +455,7 @@ class Context:
         o = seed_options(**opts)
         h = C.c_void_p()
         self.check(lib().msfm_seed_hypotheses(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
-        try:
+        with _Handle(h, "msfm_seed_set_destroy"):
             nh, npt, win, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
             lib().msfm_seed_set_size(h, C.byref(nh), C.byref(npt), C.byref(win), C.byref(nb))
             npt, m = npt.value, max(1, n)
@@ -755,8 +467,6 @@ class Context:
             lib().msfm_seed_set_fetch(h, A.ptr(arm, A.c_u8_p), A.ptr(pok, A.c_u8_p), A.ptr(pas, A.c_u8_p), A.ptr(nm, A.c_int_p), A.ptr(f, dp),
                                       A.ptr(R, dp), A.ptr(t, dp), A.ptr(c, dp), A.ptr(poff, A.c_int_p), A.ptr(ptm, A.c_int_p), A.ptr(X, dp),
                                       A.ptr(mse, dp))
-        finally:
-            lib().msfm_seed_set_destroy(h)
         return {"arm": arm[:n], "pose_ok": pok[:n], "pass": pas[:n], "n_matches": nm[:n], "f": f[:n], "R": R[:n], "t": t[:n], "c": c[:n],
                 "pt_off": poff, "pt_match": ptm[:npt], "X": X[:npt], "mse": mse[:npt], "winner": win.value, "h2d_bytes": nb.value}
 
@@ -789,10 +499,8 @@ class Context:
         o = new_points_options(**opts)
         h = C.c_void_p()
         self.check(lib().msfm_new_points(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
-        try:
+        with _Handle(h, "msfm_new_points_set_destroy"):
             return _new_points_set_result(h, nn)
-        finally:
-            lib().msfm_new_points_set_destroy(h)
 
     def round_adjust(self, store, cam_img, feat_point, obs_point, obs_cam, obs_feat, cam_pose, cam_model, cam_model_of_cam, point_xyz, pt_bad,
                      pt_mse, pt_mutable, pt_new_added=None, new_cam=-1, visible=(), partial=True, full=False, outliers=True, model_mutable=None,
@@ -842,11 +550,8 @@ class Context:
         o = round_options(**opts)
         h = C.c_void_p()
         self.check(lib().msfm_round_adjust(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
-        try:
-            out = _round_set_result(self, h, nc, nm, npt, partial, full, o.keep_problem, capacity)
-        finally:
-            lib().msfm_round_set_destroy(h)
-        return out
+        with _Handle(h, "msfm_round_set_destroy"):
+            return _round_set_result(self, h, nc, nm, npt, partial, full, o.keep_problem, capacity)
 
     def triangulate_midpoint(self, tracks, th_error, th_angle, X0=None):
         return self._tri(lib().msfm_triangulate_midpoint_batch, tracks, th_error, th_angle, X0)
@@ -1041,8 +746,9 @@ class Context:
         return out[:len(pt1)]
 
 
-class DescSet:
+class DescSet(_Handle):
     """Device-resident descriptors of a set of images (msfm_descset)."""
+    _destroy = "msfm_descset_destroy"
 
     def __init__(self, ctx: Context, descs, keypoints=None):
         self.ctx = ctx
@@ -1075,19 +781,10 @@ class DescSet:
         features, as a `WordResult`."""
         return WordResult(self, tree, min_features)
 
-    def close(self):
-        if self._h:
-            lib().msfm_descset_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class MatchResult(_Handle):
+    _destroy = "msfm_match_result_destroy"
 
-
-class MatchResult:
     def __init__(self, ds: DescSet, pairs, ratio_good, ratio_all, keep_knn, slam=None):
         self.ds, self.ctx = ds, ds.ctx
         self.pairs = A.as_c(np.asarray(pairs).reshape(-1, 2), np.int32)
@@ -1100,12 +797,7 @@ class MatchResult:
             H = A.as_c(np.asarray(H, dtype=np.float64).reshape(-1, 9), np.float64)
             if len(F) != len(self.pairs) or len(H) != len(self.pairs):
                 raise ValueError("one F and one H per pair")
-            o = A.SlamMatchOptions()
-            lib().msfm_slam_match_default_options(C.byref(o))
-            for k, v in kw.items():
-                if not hasattr(o, k):
-                    raise AttributeError(k)
-                setattr(o, k, v)
+            o = _options(A.SlamMatchOptions, "msfm_slam_match_default_options", kw)
             self.ctx.check(lib().msfm_match_pairs_slam(ds._h, A.ptr(self.pairs, A.c_int_p), len(self.pairs), A.ptr(F, A.c_double_p),
                                                        A.ptr(H, A.c_double_p), C.byref(o), int(keep_knn), C.byref(self._h)))
             return
@@ -1134,21 +826,11 @@ class MatchResult:
                                                      A.ptr(d, A.c_float_p)))
         return code, ids, d
 
-    def close(self):
-        if self._h:
-            lib().msfm_match_result_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Chain:
+class Chain(_Handle):
     """msfm_chain: match codes -> verification -> tracks -> triangulation -> bundle adjustment, everything resident
     (include/msfm.h).  Built from a MatchResult whose DescSet holds the keypoints."""
+    _destroy = "msfm_chain_destroy"
 
     def __init__(self, res):
         self.ctx, self.res = res.ctx, res
@@ -1267,20 +949,10 @@ class Chain:
         """msfm_chain_store_points: the adjusted points of `ba` (the BaResident this chain made last) back into the resident X."""
         self.ctx.check(lib().msfm_chain_store_points(self._h, ba._h))
 
-    def close(self):
-        if self._h:
-            lib().msfm_chain_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MatchStore:
+class MatchStore(_Handle):
     """msfm_match_store: the verified matches of an image set resident on the device, indexed by idx1 (include/msfm.h)."""
+    _destroy = "msfm_match_store_destroy"
 
     def __init__(self, ctx: Context, n_features, pairs, match_off, matches):
         self.ctx = ctx
@@ -1303,20 +975,10 @@ class MatchStore:
         self.ctx.check(lib().msfm_match_store_from_chain(chain._h, C.byref(self._h)))
         return self
 
-    def close(self):
-        if self._h:
-            lib().msfm_match_store_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Wordset:
+class Wordset(_Handle):
     """msfm_wordset: which image pairs to match, from the word id of every feature (include/msfm.h)."""
+    _destroy = "msfm_wordset_destroy"
 
     def __init__(self, ctx: Context, n_features, words, num_words, keypoints, max_hypotheses=0):
         self.ctx = ctx
@@ -1370,7 +1032,7 @@ class Wordset:
         o = pair_select_options(**opts)
         h = C.c_void_p()
         self.ctx.check(lib().msfm_pair_select(self._h, first_image, rows, C.byref(o), C.byref(h)))
-        try:
+        with _Handle(h, "msfm_pair_set_destroy"):
             nr, k, nk, tot = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
             lib().msfm_pair_set_size(h, C.byref(nr), C.byref(k), C.byref(nk), C.byref(tot))
             rows, k, nk, tot = nr.value, k.value, nk.value, tot.value
@@ -1382,28 +1044,16 @@ class Wordset:
             inl = np.zeros(max(1, tot), np.uint8) if details else None
             lib().msfm_pair_set_fetch(h, A.ptr(ni, A.c_int_p), A.ptr(nin, A.c_int_p), A.ptr(ver, A.c_u8_p), A.ptr(pairs, A.c_int_p),
                                       A.ptr(F, A.c_double_p), A.ptr(off, A.c_int_p), A.ptr(im, A.c_int_p), A.ptr(inl, A.c_u8_p))
-        finally:
-            lib().msfm_pair_set_destroy(h)
         out = {"pairs": pairs[:nk], "n_init": ni, "n_inliers": nin, "verdict": ver}
         if details:
             out.update(F=F, init_off=off, init_matches=im[:tot], init_inlier=inl[:tot])
         return out
 
-    def close(self):
-        if self._h:
-            lib().msfm_wordset_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class VocTree:
+class VocTree(_Handle):
     """msfm_voctree: a vocabulary tree resident on the device (include/msfm.h).  block_n [n_blocks], node_desc [n_blocks][k][128],
     node_link / node_weight [n_blocks][k]: what featurefiles.read_voctree returns."""
+    _destroy = "msfm_voctree_destroy"
 
     def __init__(self, ctx: Context, k, block_n, node_desc, node_link, node_weight):
         self.ctx = ctx
@@ -1422,20 +1072,10 @@ class VocTree:
         lib().msfm_voctree_size(self._h, C.byref(k), C.byref(nb), C.byref(d), C.byref(nl), C.byref(hb))
         return dict(k=k.value, n_blocks=nb.value, depth=d.value, n_leaves=nl.value, h2d_bytes=hb.value)
 
-    def close(self):
-        if self._h:
-            lib().msfm_voctree_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class WordResult:
+class WordResult(_Handle):
     """msfm_word_result: the word of every feature of a descriptor set, its bags of words and maxima, on the device."""
+    _destroy = "msfm_word_result_destroy"
 
     def __init__(self, ds, tree: VocTree, min_features=300):
         self.ctx, self.ds = ds.ctx, ds
@@ -1468,20 +1108,10 @@ class WordResult:
         self.ctx.check(lib().msfm_wordset_create_from_words(self.ds._h, self._h, int(max_hypotheses), C.byref(h)))
         return Wordset._adopt(self.ctx, h)
 
-    def close(self):
-        if self._h:
-            lib().msfm_word_result_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Recon:
+class Recon(_Handle):
     """msfm_recon: a model's flat state resident on the device across its rounds (include/msfm.h)."""
+    _destroy = "msfm_recon_destroy"
     INT = ("cam_img", "feat_point", "obs_point", "obs_cam", "obs_feat", "pt_views")
     U8 = ("pt_bad", "pt_mutable", "pt_new_added")
 
@@ -1596,10 +1226,8 @@ class Recon:
                                                    C.byref(h) if stats else None))
         if not stats:
             return n.value
-        try:
+        with _Handle(h, "msfm_new_points_set_destroy"):
             return dict(_new_points_set_result(h, 1), n_new=n.value)
-        finally:
-            lib().msfm_new_points_set_destroy(h)
 
     def adjust(self, new_cam=-1, visible=(), partial=True, full=False, outliers=True, capacity=512, **opts):
         """msfm_recon_adjust: `Context.round_adjust` on the resident state, written in place.  Returns its dict without the point
@@ -1615,28 +1243,16 @@ class Recon:
         h = C.c_void_p()
         self.ctx.check(lib().msfm_recon_adjust(self._h, int(new_cam), len(visible), A.ptr(visible, A.c_int_p), int(bool(partial)), int(bool(full)),
                                                int(bool(outliers)), C.byref(o), C.byref(h)))
-        try:
+        with _Handle(h, "msfm_round_set_destroy"):
             out = _round_set_result(self.ctx, h, z["n_cams"], z["n_models"], 0, partial, full, o.keep_problem, capacity)
-        finally:
-            lib().msfm_round_set_destroy(h)
         for k in ("point_xyz", "pt_mutable", "pt_bad", "pt_mse", "pt_new_added", "pt_views"):
             del out[k]
         return out
 
-    def close(self):
-        if self._h:
-            lib().msfm_recon_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class LocalizeSet:
+class LocalizeSet(_Handle):
     """msfm_localize_set: the ranked candidates of one round; made with point_xyz it keeps their correspondences on the device."""
+    _destroy = "msfm_localize_set_destroy"
 
     def __init__(self, ctx: Context, h):
         self.ctx, self._h = ctx, h
@@ -1674,7 +1290,7 @@ class LocalizeSet:
         h = C.c_void_p()
         self.ctx.check(lib().msfm_localize_poses(self.ctx._h, self._h, A.ptr(f, A.c_double_p), A.ptr(fi, A.c_double_p), int(n_points),
                                                  A.ptr(added, A.c_u8_p), C.byref(o), C.byref(h)))
-        try:
+        with _Handle(h, "msfm_localize_pose_set_destroy"):
             nr, nc, ntr, win, nxt = (C.c_int32() for _ in range(5))
             lib().msfm_localize_pose_set_size(h, C.byref(nr), C.byref(nc), C.byref(ntr), C.byref(win), C.byref(nxt))
             nc, m = nc.value, max(1, n)
@@ -1685,32 +1301,14 @@ class LocalizeSet:
             lib().msfm_localize_pose_set_fetch(h, A.ptr(tried, up), A.ptr(arm, up), A.ptr(pas, up), A.ptr(fo, dp), A.ptr(R, dp), A.ptr(t, dp),
                                                A.ptr(avg, dp), A.ptr(bs, ip), A.ptr(bi, ip), A.ptr(nin, ip), A.ptr(nout, ip), A.ptr(err, dp),
                                                A.ptr(state, up))
-        finally:
-            lib().msfm_localize_pose_set_destroy(h)
         return {"tried": tried[:n], "arm": arm[:n], "pass": pas[:n], "f": fo[:n], "R": R[:n], "t": t[:n], "avg_error": avg[:n],
                 "best_step": bs[:n], "best_iter": bi[:n], "n_inliers": nin[:n], "n_outliers": nout[:n], "errors": err[:nc],
                 "corr_state": state[:nc], "n_tried": ntr.value, "winner": win.value, "next_row": nxt.value}
 
-    def close(self):
-        if self._h:
-            lib().msfm_localize_set_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class BaResident:
+class BaResident(_Handle):
     """msfm_ba_create / run / upload / download: a BA problem kept in HBM across solves."""
+    _destroy = "msfm_ba_destroy"
 
     def __init__(self, ctx: Context, arrays: A.BaArrays):
         self.ctx, self.arrays = ctx, arrays
@@ -1748,22 +1346,12 @@ class BaResident:
                                                      A.ptr(pt, A.c_double_p)))
         return cp, cm, pt
 
-    def close(self):
-        if self._h:
-            lib().msfm_ba_destroy(self._h)
-            self._h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class MultiContext:
+class MultiContext(_Handle):
     """msfm_ctx_create_multi: one process, several GPUs - the library owns a context and a host thread per device and the
     communicator between them (ncclCommInitAll over xGMI; an in-process reduction when `devices` names one device several
     times, which is how the path runs on a one-GPU box).  The calls take the whole problem; the split is inside."""
+    _destroy = "msfm_multi_destroy"
 
     def __init__(self, n_gpus, devices=None):
         self._h = C.c_void_p()
@@ -1814,28 +1402,17 @@ class MultiContext:
                                                 ratio_good, ratio_all, cp, A.ptr(na, A.c_int_p), A.ptr(ng, A.c_int_p)))
         return [c[:count[j]] for c, (_, j) in zip(codes, pairs)], na[:len(pairs)], ng[:len(pairs)]
 
-    def close(self):
-        if self._h:
-            lib().msfm_multi_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def camera_graph_dissection(adjacency, tail_cols=4, force_depth=-1):
     """msfm_camera_graph_dissection (host only: works without a GPU): labels per camera (leaf id, or -(d + 1) for a separator cut
     at depth d), number of leaves (0: dense order kept) and the critical path in 64-column panel steps."""
-    import numpy as np
     adj = np.ascontiguousarray(adjacency, dtype=np.uint8)
     n = adj.shape[0]
     assert adj.shape == (n, n)
     label = np.zeros(n, np.int32)
     nl, steps = C.c_int(0), C.c_int(0)
-    rc = lib().msfm_camera_graph_dissection(n, adj.ctypes.data, int(tail_cols), int(force_depth), label.ctypes.data, C.byref(nl), C.byref(steps))
+    rc = lib().msfm_camera_graph_dissection(n, A.ptr(adj, A.c_u8_p), int(tail_cols), int(force_depth), A.ptr(label, A.c_int_p), C.byref(nl),
+                                            C.byref(steps))
     if rc != 0:
         raise MsfmError(rc, "msfm_camera_graph_dissection")
     return label, nl.value, steps.value

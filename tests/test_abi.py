@@ -10,7 +10,7 @@ import sys
 import pytest
 
 from metricsfm_amd import _abi as A
-from metricsfm_amd import capi
+from metricsfm_amd import _header, capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "msfm.h")
@@ -35,23 +35,92 @@ def test_every_declared_symbol_is_exported_and_bound():
     assert L.msfm_version() == 100
 
 
-def test_struct_layouts_match_the_c_compiler(tmp_path):
+def test_every_struct_and_constant_matches_the_c_compiler(tmp_path):
+    """Every struct of the header against its mirror in _abi.py (paired by name: msfm_round_options -> RoundOptions): size,
+    and offset and size of every field the mirror names; and every constant _abi.py repeats.  One C99 program prints them all."""
+    pairs = [(s, _header.mirror(s)) for s in _header.struct_names(open(HDR).read())]
+    assert len(pairs) == 25 and all(cls is not None for _, cls in pairs), [s for s, cls in pairs if cls is None]
+    mirrors = {v for v in vars(A).values() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert mirrors == {cls for _, cls in pairs}, "mirrors without a struct in the header"
+    exprs, want = [], []
+    for s, cls in pairs:
+        exprs.append("sizeof(%s)" % s)
+        want.append(C.sizeof(cls))
+        for f, _ in cls._fields_:
+            exprs += ["offsetof(%s,%s)" % (s, f), "sizeof(((%s*)0)->%s)" % (s, f)]
+            want += [getattr(cls, f).offset, getattr(cls, f).size]
+    consts = ["MSFM_OK", "MSFM_E_INVAL", "MSFM_E_NOMEM", "MSFM_E_DEVICE", "MSFM_E_NUMERIC", "MSFM_MATCH_GOOD", "MSFM_MATCH_NOT_ALL",
+              "MSFM_MATCH_ID_MASK", "MSFM_MAX_KERNEL_STATS", "MSFM_PATH_ROOT_CHAIN", "MSFM_PATH_BACKSOLVE_CHAIN", "MSFM_PATH_ASM_BESIDE",
+              "MSFM_PATH_RIDER_MODELSUM", "MSFM_PATH_RIDER_UPDATE"]
+    assert sorted(consts) == sorted(k for k in vars(A) if k.startswith("MSFM_") and k != "MSFM_PATH_LEVEL_CHAIN")
+    levels = (0, 1, 2)
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu %zu %zu %zu '
-                   '%zu %zu %zu %d %d %d %d\\n",'
-                   'sizeof(msfm_ba_problem),sizeof(msfm_ba_options),sizeof(msfm_ba_iteration),sizeof(msfm_ba_summary),'
-                   'sizeof(msfm_tracks),sizeof(msfm_kernel_stat),offsetof(msfm_ba_problem,gps_weight),'
-                   'offsetof(msfm_ba_summary,solve_ms),offsetof(msfm_ba_options,jacobi_scaling),'
-                   'sizeof(msfm_ba_layout),offsetof(msfm_ba_layout,fold_mc_slots),offsetof(msfm_ba_layout,solve_paths),'
-                   'MSFM_PATH_LEVEL_CHAIN(0),MSFM_PATH_LEVEL_CHAIN(2),MSFM_PATH_ROOT_CHAIN,MSFM_PATH_BACKSOLVE_CHAIN);return 0;}\n')
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){size_t v[]={%s};long long c[]={%s};'
+                   'for(size_t i=0;i<sizeof v/sizeof v[0];i++)printf("%%zu ",v[i]);'
+                   'for(size_t i=0;i<sizeof c/sizeof c[0];i++)printf("%%lld ",c[i]);return 0;}\n'
+                   % (",".join(exprs), ",".join(consts + ["MSFM_PATH_LEVEL_CHAIN(%d)" % l for l in levels])))
     exe = tmp_path / "sz"
     subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
     got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    want = [C.sizeof(A.BaProblem), C.sizeof(A.BaOptions), C.sizeof(A.BaIteration), C.sizeof(A.BaSummary), C.sizeof(A.Tracks),
-            C.sizeof(A.KernelStat), A.BaProblem.gps_weight.offset, A.BaSummary.solve_ms.offset, A.BaOptions.jacobi_scaling.offset,
-            C.sizeof(A.BaLayout), A.BaLayout.fold_mc_slots.offset, A.BaLayout.solve_paths.offset,
-            A.MSFM_PATH_LEVEL_CHAIN(0), A.MSFM_PATH_LEVEL_CHAIN(2), A.MSFM_PATH_ROOT_CHAIN, A.MSFM_PATH_BACKSOLVE_CHAIN]
-    assert got == want
+    want += [getattr(A, k) for k in consts] + [A.MSFM_PATH_LEVEL_CHAIN(l) for l in levels]
+    labels = exprs + consts + ["MSFM_PATH_LEVEL_CHAIN(%d)" % l for l in levels]
+    assert len(got) == len(want)
+    assert got == want, [(e, g, w) for e, g, w in zip(labels, got, want) if g != w]
+    # the field lists the single layout tests used to spell out
+    names = {s: [f for f, _ in cls._fields_] for s, cls in pairs}
+    assert names["msfm_round_options"] == ["partial", "full", "weight_partial", "weight_full", "th_mse_outliers", "keep_problem"]
+    assert len(names["msfm_round_problem"]) == 25 and names["msfm_round_problem"][-3:] == ["do_partial", "do_full", "do_outliers"]
+    assert names["msfm_recon_winner"][:2] == ["image", "row"] and names["msfm_recon_winner"][-1] == "avg_error"
+    assert len(names["msfm_recon_init"]) == 26 and names["msfm_recon_init"][-2:] == ["reserve_points", "reserve_obs"]
+    assert A.ITER_DTYPE.itemsize == C.sizeof(A.BaIteration) and list(A.ITER_DTYPE.names) == names["msfm_ba_iteration"]
+
+
+def test_prototypes_read_from_the_header_are_the_ones_written_by_hand():
+    """The reader (metricsfm_amd/_header.py) is not trusted: restype and argtypes of functions that between them use every type
+    shape and every return type of its table, written out here as lib() used to assign them."""
+    vp, i, d, f, P = C.c_void_p, C.c_int, C.c_double, C.c_float, C.POINTER
+    dp, fp, ip, up, i64p = A.c_double_p, A.c_float_p, A.c_int_p, A.c_u8_p, C.POINTER(C.c_int64)
+    want = {
+        "msfm_version": (i, []),
+        "msfm_last_error": (C.c_char_p, [vp]),
+        "msfm_ctx_stream": (vp, [vp]),
+        "msfm_multi_ctx": (vp, [vp, i]),
+        "msfm_ctx_destroy": (None, [vp]),
+        "msfm_ctx_create": (i, [i, P(vp)]),
+        "msfm_knn2_f32": (i, [vp, fp, i, fp, i, i, ip, fp]),
+        "msfm_match_pairs": (i, [vp, ip, i, f, f, i, P(vp)]),
+        "msfm_match_result_fetch": (i, [vp, i, ip, ip, fp]),
+        "msfm_ba_solve": (i, [vp, P(A.BaProblem), P(A.BaOptions), P(A.BaSummary)]),
+        "msfm_epipolar_filter": (i, [vp, fp, fp, i, dp, d, up]),
+        "msfm_relpose_5pt_batch": (i, [vp, i, ip, dp, dp, dp, dp, i, C.c_uint64, dp, dp, dp, up, ip]),
+        "msfm_voctree_create": (i, [vp, i, i, P(C.c_uint16), fp, P(C.c_uint32), fp, P(vp)]),
+        "msfm_wordset_size": (i, [vp, ip, ip, i64p, i64p, i64p]),
+        "msfm_multi_match_pairs": (i, [vp, i, P(fp), ip, i, ip, i, f, f, P(ip), ip, ip]),
+        "msfm_ctx_allreduce": (i, [vp, dp, C.c_size_t, i]),
+        "msfm_ctx_set_allreduce": (i, [vp, capi.ALLREDUCE_FN, vp, i, i]),
+        "msfm_rccl_get_unique_id": (i, [vp, P(C.c_ubyte)]),
+        "msfm_recon_localize": (i, [vp, i, ip, ip, dp, dp, P(A.LocalizePoseOptions), P(A.ReconWinner)]),
+        "msfm_camera_graph_dissection": (i, [i, up, i, i, ip, ip, ip]),
+    }
+    L = capi.lib()
+    for name, (restype, argtypes) in want.items():
+        assert capi.PROTOTYPES[name] == (restype, argtypes), name
+        assert getattr(L, name).restype is restype and list(getattr(L, name).argtypes) == argtypes, name
+    used = {t for restype, argtypes in want.values() for t in argtypes}
+    assert used >= {t for t in _header.SHAPES.values()}, "a type shape of the table that no function above uses"
+    assert {restype for restype, _ in want.values()} == set(_header.RETURNS.values())
+
+
+@pytest.mark.parametrize("text", [
+    "int msfm_foo(msfm_ctx* ctx, long n);",                                                       # a type the table does not hold
+    "typedef struct msfm_no_such_thing { int a; } msfm_no_such_thing;\nint msfm_foo(const msfm_no_such_thing* p);",   # no mirror
+    "int msfm_foo(int (*fn)(void));",                                       # the name is found, the declaration is not understood
+    "int msfm_foo(double*);",                                                                     # a parameter without a name
+])
+def test_the_reader_refuses_what_it_does_not_know(text):
+    with pytest.raises(ImportError, match="msfm_foo"):
+        _header.prototypes("typedef struct msfm_ctx msfm_ctx;\nint msfm_version(void);\n" + text)
+    assert list(_header.prototypes("typedef struct msfm_ctx msfm_ctx;\nint msfm_version(void);\n")) == ["msfm_version"]
 
 
 def test_defaults_are_the_ceres_defaults():

@@ -1,8 +1,6 @@
 """The focal sweep's CPU side (no GPU): the reference composed from the oracle (tests/epnpf_ref.py), the step count of
-msfm_epnpf_num_steps, the options struct against the C compiler, and the committed fixture."""
-import ctypes as C
+msfm_epnpf_num_steps, and the committed fixture (the options struct against the C compiler: tests/test_abi.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -62,19 +60,6 @@ def test_defaults_and_invalid_step_counts():
         assert capi.epnpf_num_steps(**kw) == A.MSFM_E_INVAL, kw
     assert capi.epnpf_num_steps(f_ratio_min=0.0, f_ratio_max=65535.5, f_ratio_step=1.0) == 65535
     assert capi.epnpf_num_steps(f_ratio_min=0.0, f_ratio_max=65536.0, f_ratio_step=1.0) == A.MSFM_E_INVAL
-
-
-def test_options_struct_matches_the_c_compiler(tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(msfm_epnpf_options),offsetof(msfm_epnpf_options,f_ratio_min),offsetof(msfm_epnpf_options,f_ratio_max),'
-                   'offsetof(msfm_epnpf_options,f_ratio_step),offsetof(msfm_epnpf_options,max_iter),offsetof(msfm_epnpf_options,seed));'
-                   'return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    E = A.EpnpfOptions
-    assert got == [C.sizeof(E), E.f_ratio_min.offset, E.f_ratio_max.offset, E.f_ratio_step.offset, E.max_iter.offset, E.seed.offset]
 
 
 def test_golden_fixture_reproduces_from_the_reference(oracle):

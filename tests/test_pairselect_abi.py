@@ -1,27 +1,10 @@
-"""The structs of the "Which image pairs to match" section of include/msfm.h against a C compiler, the default values, and
-the refusals that need no device."""
+"""The default values of the "Which image pairs to match" section of include/msfm.h and the refusals that need no device
+(the struct layouts: tests/test_abi.py)."""
 import ctypes as C
-import os
 import subprocess
 
 from metricsfm_amd import _abi as A
 from metricsfm_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def test_struct_layouts_match_the_c_compiler(tmp_path):
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu %zu %zu %zu %zu\\n",'
-                   'sizeof(msfm_pair_select_options),offsetof(msfm_pair_select_options,th_inliers),'
-                   'offsetof(msfm_pair_select_options,max_hypotheses),offsetof(msfm_pair_select_options,fransac),'
-                   'sizeof(msfm_fransac_options),offsetof(msfm_fransac_options,seed));return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    want = [C.sizeof(A.PairSelectOptions), A.PairSelectOptions.th_inliers.offset, A.PairSelectOptions.max_hypotheses.offset,
-            A.PairSelectOptions.fransac.offset, C.sizeof(A.FransacOptions), A.FransacOptions.seed.offset]
-    assert got == want
 
 
 def test_defaults_are_the_references():

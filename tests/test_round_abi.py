@@ -1,29 +1,5 @@
-"""The structs of msfm_round_adjust (include/msfm.h) as the ctypes host mirrors them (metricsfm_amd/_abi.py) against a C compiler's
-layout, in the manner of tests/test_abi.py, and the defaults msfm_round_default_options documents."""
-import ctypes as C
-import os
-import subprocess
-
-from metricsfm_amd import _abi as A
+"""The defaults msfm_round_default_options documents (the layouts of the structs of msfm_round_adjust: tests/test_abi.py)."""
 from metricsfm_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OPTION_FIELDS = ("partial", "full", "weight_partial", "weight_full", "th_mse_outliers", "keep_problem")
-PROBLEM_FIELDS = [f for f, _ in A.RoundProblem._fields_]
-
-
-def test_round_struct_layouts_match_the_c_compiler(tmp_path):
-    fields = [("msfm_round_options", f) for f in OPTION_FIELDS] + [("msfm_round_problem", f) for f in PROBLEM_FIELDS]
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "msfm.h"\nint main(){printf("%zu %zu", sizeof(msfm_round_options), '
-                   'sizeof(msfm_round_problem));\n' + "".join('printf(" %%zu", offsetof(%s, %s));\n' % sf for sf in fields) + 'printf("\\n");return 0;}\n')
-    exe = tmp_path / "sz"
-    subprocess.check_call(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
-    got = [int(v) for v in subprocess.check_output([str(exe)], text=True).split()]
-    want = [C.sizeof(A.RoundOptions), C.sizeof(A.RoundProblem)] + [getattr(A.RoundOptions, f).offset for f in OPTION_FIELDS] + \
-           [getattr(A.RoundProblem, f).offset for f in PROBLEM_FIELDS]
-    assert got == want
-    assert len(PROBLEM_FIELDS) == 25 and PROBLEM_FIELDS[-3:] == ["do_partial", "do_full", "do_outliers"]
 
 
 def test_round_defaults_are_the_references():
