@@ -6,12 +6,24 @@
 // Layout: M is npad x npad row-major (ld = npad, npad a multiple of 64), lower triangle.
 // Rows/cols [0,n) hold S; row n holds rhs^T (the forward substitution L w = rhs then falls out
 // of the factorisation: row n of the factor is w^T); indices > n are zero padding.
-// Right-looking by 64-column panels, ONE launch per panel (k_panel_v2): the trailing update with
-// panel j0 as 64x64 f64-MFMA tiles, with the factorisation (potrf + trsm) of the next panel folded
-// into the same launch.  The back substitution L^T z = w runs block by block with explicitly
-// inverted diagonal blocks (k_trinv64_full) so each step is a mat-vec.
+//
+// The elimination order is a plan (chol_plan.h): tree levels of mutually uncoupled nodes, then the dense root chain (no plan:
+// the root chain alone).  What is launched for a plan is its schedule (chol_schedule.h), read by the driver at the end of the file.
+//  * Factorisation, right-looking by 64-column panels, in two forms with the same arithmetic in the same order:
+//      k_panel_v2  one launch per step: the trailing update with the panel before as 64 x 64 f64-MFMA tiles, the potrf + trsm of
+//                  the step's panel folded into the same launch.  Runs with MSFM_CHOL_LAUNCHES=1, for chains the device cannot
+//                  hold at once, and for systems past 4 GB;
+//      k_chain     the chains of a tree level (or the root chain) as ONE persistent launch: row owners keep their rows in
+//                  registers from step to step, bulk workgroups take the trailing tiles by ticket.  Runs wherever the schedule
+//                  calls the launch usable.
+//  * Corner update of a tree level: the tiles among the rows behind the level, which the chains leave out, as one SYRK over
+//    the level's panels (k_corner_syrk; it can take the caller's model-sum rider along), summed into M by k_merge_corners.
+//  * Back substitution L^T z = w in two forms: k_backsolve_chain, one launch with z handed from block to block through
+//    self-tagged values, while the device holds a workgroup per block at once; otherwise explicitly inverted diagonal blocks
+//    (k_trinv64_full) and two blocks per launch (k_backsolve_pair; a chain's odd block: k_backsolve_step), each step a mat-vec.
 #include "common.h"
 #include "solve_riders.h"
+#include "chol_schedule.h"
 #include <atomic>
 #include <algorithm>
 #include <cstdlib>
@@ -70,7 +82,7 @@ __device__ __forceinline__ void quad_abt(const double* X, const double* Y, int w
 //  * The triangular solve of the own rows is pipelined behind the sub-panels: when sub-panel jb
 //    is being factored the helpers already compute X_(jb-1) and subtract it from the later blocks,
 //    so only X_3 = T_3 Dinv_3^T (4 MFMAs) and the store follow the last pivot.
-// j0 = -64 means "no previous panel" (first block: t0 = 0, nothing to subtract).
+// A job's j0 < 0 means "no previous panel" (first block of a chain: nothing to subtract).
 // =======================================================================================
 #define DV 17  // row stride of the 16x16 inverse blocks in LDS
 
@@ -261,41 +273,7 @@ __device__ __forceinline__ void tile_st(double* Ls, int a, int b, int lr, int lk
   for (int i = 0; i < 4; i++) Ls[(16 * a + lk + 4 * i) * LDT + 16 * b + lr] = v[i];
 }
 
-// One launch can carry several independent panel steps ("jobs"): with an elimination order that puts
-// K mutually uncoupled camera domains first and their separator last, the K domain chains advance in
-// the same launch.  A job's rows are two ranges: A = [a0, a0 + 16 na16) (rest of its own domain,
-// starting with the 64 x 64 block to factor) and B = [b0, b0 + 16 nb16) (separator + rhs row); the
-// B x B tiles, which every job's trailing update would write, are left out of the chains (defer_corner)
-// and formed afterwards by one SYRK over all panels (k_corner_syrk, then k_merge_corners).  The plain dense
-// factorisation is one job with B empty.
-struct PanelJob {
-  int j0;          // panel to apply, < 0: none (first block of a chain)
-  int t0;          // block to factor, < 0: update only
-  int a0, na16;    // range A, na16 a multiple of 4
-  int b0, nb16;    // range B: nb16 16-row tiles that carry data, in up to four segments (a node's ancestors, one per level,
-  int nseg;        // then the root with the rhs row): segment g starts at row sb0[g] and holds sn16[g] tiles, every segment but
-  int sb0[4], sn16[4];   // the last a multiple of four.  nseg == 0: one segment starting at b0
-  int nrt;         // 16-row tiles that carry data, over A then B
-  int ncw;         // column-0 workgroups
-  int wg0, nwg;    // workgroups [wg0, wg0 + nwg) of the launch: ncw column-0 ones, then the bulk ones
-  int ntile;       // 64x64 tiles of the trailing update, dealt round-robin to the nwg - ncw bulk workgroups
-  int ldc;         // leading dimension of corner
-  double* corner;  // destination of B x B tiles, nullptr: M itself
-  int defer_corner;  // the B x B tiles are left out here: one SYRK over all panels forms them after the domain chains
-};
-struct PanelJobs {
-  int count;
-  PanelJob job[8];
-};
-__device__ __forceinline__ int job_row16(const PanelJob& jb, int rt) {
-  if (rt < jb.na16) return jb.a0 + 16 * rt;
-  int r = rt - jb.na16;
-  if (jb.nseg == 0) return jb.b0 + 16 * r;
-  int g = 0;
-  while (g + 1 < jb.nseg && r >= jb.sn16[g]) { r -= jb.sn16[g]; g++; }
-  return jb.sb0[g] + 16 * r;
-}
-__device__ __forceinline__ int job_row64(const PanelJob& jb, int ti) { return job_row16(jb, 4 * ti); }
+// (PanelJob, ChainJob and their row decode row16(): chol_schedule.h)
 
 __device__ __forceinline__ void p0_load(const double* __restrict__ M, int ld, int t0, int j0, int tid, d2 (&pv)[8]) {
 #pragma unroll
@@ -334,7 +312,7 @@ __device__ __forceinline__ void panel_col0(double* __restrict__ M, int ld, const
                                            double* __restrict__ Ldiag, int* fail, double* Bs, double* Ls, double* dinv, double* dvec) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int lr = lane & 15, lk = lane >> 4;
-  const int j0 = jb.j0, t0 = jb.t0, nrt = jb.nrt;
+  const int j0 = jb.j0, t0 = jb.begin, nrt = jb.nrt;
   const bool upd = j0 >= 0;
   const int ncol = min(NB, n - t0);
   if (wave == 0) {
@@ -371,7 +349,7 @@ __device__ __forceinline__ void panel_col0(double* __restrict__ M, int ld, const
     const bool own = rt < nrt;
     double* const pub_lo = Ldiag + (size_t)(t0 / NB) * NB * NB;
     double* const pub_out = Dinv + (size_t)(t0 / NB) * 1024;
-    const size_t r0 = (size_t)job_row16(jb, own ? rt : 0);
+    const size_t r0 = (size_t)row16(jb, own ? rt : 0);
     // The own rows are read and written as 32 contiguous bytes per lane (one row's 128 bytes across the four lanes lk of a
     // row): a lane's four doubles of a 16-column block are the columns 4 lk + i, i.e. accumulator register i stands for row
     // pl(4 i + lk) = 4 lk + i of the transposed tile instead of row 4 i + lk, and step s of a K = 64 product takes the panel
@@ -509,8 +487,8 @@ __device__ __forceinline__ void panel_col0(double* __restrict__ M, int ld, const
   }
 }
 
-// grid: for every job its column-0 workgroups, then the 64x64 tiles (I, J), jmin <= J <= I < nt, of the
-// trailing update  C_IJ -= P_I P_J^T  (jmin = 1 when the job also factors: the column-0 workgroups own J = 0).
+// grid: for every job its column-0 workgroups, then the 64x64 tiles (I, J), 1 <= J <= I, of the trailing update
+// C_IJ -= P_I P_J^T  (the column-0 workgroups own J = 0; J stays inside range A: the B x B tiles are k_corner_syrk's).
 template <bool FULL>
 __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld, int n, double* __restrict__ Dinv,
                                                       double* __restrict__ Ldiag, int* fail, PanelJobs jobs) {
@@ -532,18 +510,17 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
   const int wr = wave >> 1, wc = wave & 1;
   const int lr = lane & 15, lk = lane >> 4;
   const int j0 = jb.j0;
-  const int jmin = jb.t0 >= 0 ? 1 : 0, nA64 = jb.na16 / 4;
+  const int nA64 = jb.na16 / 4;
   const int nbw = jb.nwg - jb.ncw;
   const int qrow = 32 * wr + lk, qcol = 32 * wc + lr;
   // A bulk workgroup walks tiles q, q + nbw, ...: the panel tiles and the C quadrant of the NEXT tile are
   // fetched into registers while the MFMAs of the current one run (the kernel runs one workgroup per CU,
   // so nothing else hides that latency).
-  auto locate = [&](int q, int& ri, int& rj, double*& C, int& ldC) {
-    // pairs (I, J) with jmin <= J <= I < nt, enumerated row by row (shifted by one when jmin == 0)
+  auto locate = [&](int q, int& ri, int& rj, double*& C) {
+    // pairs (I, J) with 1 <= J <= I < nA64 row by row, then the rows of range B against the columns of range A
     int I, J;
-    const int ntri = nA64 * (nA64 - 1) / 2;  // pairs 1 <= J <= I < nA64
-    if (jb.defer_corner && q >= ntri) {
-      // rows of range B against the columns of range A only (defer_corner jobs always factor: jmin == 1)
+    const int ntri = nA64 * (nA64 - 1) / 2;
+    if (q >= ntri) {
       const int w = nA64 - 1, e = q - ntri;
       I = nA64 + e / w;
       J = 1 + e % w;
@@ -552,22 +529,14 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
       while (I * (I - 1) / 2 > q) I--;
       while ((I + 1) * I / 2 <= q) I++;
       J = q - I * (I - 1) / 2 + 1;
-      if (!jmin) { I--; J--; }
     }
-    ri = job_row64(jb, I);
-    rj = job_row64(jb, J);
-    // destination of the tile: M, or the job's private corner when both tiles lie in range B
-    if (jb.corner && I >= nA64 && J >= nA64) {
-      ldC = jb.ldc;
-      C = jb.corner + (size_t)(64 * (I - nA64)) * ldC + 64 * (J - nA64);
-    } else {
-      ldC = ld;
-      C = M + (size_t)ri * ld + rj;
-    }
+    ri = row16(jb, 4 * I);
+    rj = row16(jb, 4 * J);
+    C = M + (size_t)ri * ld + rj;
   };
   d2 va[8], vb[8];
   d4 c00, c01, c10, c11;
-  auto fetch = [&](int ri, int rj, const double* C, int ldC) {
+  auto fetch = [&](int ri, int rj, const double* C) {
 #pragma unroll
     for (int it = 0; it < 8; it++) {
       const int e = tid + 256 * it, r = e >> 5, c2 = (e & 31) * 2;
@@ -576,16 +545,16 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const double* p0 = &C[(size_t)(qrow + 4 * i) * ldC + qcol];
-      const double* p1 = &C[(size_t)(qrow + 16 + 4 * i) * ldC + qcol];
+      const double* p0 = &C[(size_t)(qrow + 4 * i) * ld + qcol];
+      const double* p1 = &C[(size_t)(qrow + 16 + 4 * i) * ld + qcol];
       c00[i] = p0[0]; c01[i] = p0[16]; c10[i] = p1[0]; c11[i] = p1[16];
     }
   };
   int q = bl - jb.ncw;
-  int ri, rj, ldC;
+  int ri, rj;
   double* C;
-  locate(q, ri, rj, C, ldC);
-  fetch(ri, rj, C, ldC);
+  locate(q, ri, rj, C);
+  fetch(ri, rj, C);
   for (;;) {
 #pragma unroll
     for (int it = 0; it < 8; it++) {
@@ -597,19 +566,18 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
     }
     d4 acc00 = c00, acc01 = c01, acc10 = c10, acc11 = c11;
     double* Cw = C;
-    const int ldw = ldC;
     __syncthreads();
     const int qn = q + nbw;
     const bool more = qn < jb.ntile;
     if (more) {
-      locate(qn, ri, rj, C, ldC);
-      fetch(ri, rj, C, ldC);
+      locate(qn, ri, rj, C);
+      fetch(ri, rj, C);
     }
     quad_abt(As, Bs, wr, wc, lr, lk, acc00, acc01, acc10, acc11);
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      double* p0 = &Cw[(size_t)(qrow + 4 * i) * ldw + qcol];
-      double* p1 = &Cw[(size_t)(qrow + 16 + 4 * i) * ldw + qcol];
+      double* p0 = &Cw[(size_t)(qrow + 4 * i) * ld + qcol];
+      double* p1 = &Cw[(size_t)(qrow + 16 + 4 * i) * ld + qcol];
       p0[0] = acc00[i]; p0[16] = acc01[i]; p1[0] = acc10[i]; p1[16] = acc11[i];
     }
     if (!more) break;
@@ -640,25 +608,6 @@ __global__ __launch_bounds__(256) void k_panel_v2(double* __restrict__ M, int ld
 // Every poll is bounded and gives up for the whole launch once MSFM_FAIL_SYNC is set (the host returns MSFM_E_DEVICE).
 // The arithmetic and its order are exactly those of the launch chain: the factor is bit-identical.
 // =======================================================================================
-struct ChainJob {
-  int begin;            // first column of the node
-  int P;                // factor steps = 64-column blocks of the node
-  int nA64;             // 64-row blocks of range A (the node itself; the dense root chain: everything down to the rhs row)
-  int nb16, nB64, nseg; // range B: 16-row tiles with data, 64-row blocks, segments
-  int sb0[4], sn16[4];
-  int nrt;              // 16-row tiles that carry data, A then B, counted from the node's first row
-  int ncw, wg0;         // row-owner workgroups [wg0, wg0 + ncw)
-  int flag0;            // first entry of the job in rowflag
-};
-struct ChainJobs {
-  int count, n_row_wg, n_bulk_wg, n_steps;   // n_steps: entries of task_first / 8
-  ChainJob job[8];
-};
-// A bulk task.  type 0: trailing tile - apply the panel of step l - 1 of job k to the tile at row tiles (ti, tj) of the job.
-// type 1: corner piece - add the product of the job's panel of step l, rows of the B blocks I and J, to split `piece` of the
-// level's corner tile (I, J) (what k_corner_syrk does after the chains; `seq` = panels the piece has received before).
-// type 2: merge - M[corner tile (I, J)] += the sum of its pieces (k_merge_corners); l = panels of the tile, piece = its splits.
-struct ChainTask { short type, k, l, ti, tj, I, J, piece, seq, urgent, pad0, pad1; };
 struct ChainCtl {
   unsigned* rowflag;          // [jobs][tiles]
   unsigned* tileflag;         // [nblk][nblk] by absolute 64-blocks of M
@@ -671,10 +620,6 @@ struct ChainCtl {
   unsigned base;              // epoch << 12
   unsigned spin_limit;
   int nblk;                   // npad / 64
-  // the level's corner update folded into the launch (corners == nullptr: done by launches behind it)
-  double* corners;            // [8][ldc][ldc] the pieces
-  unsigned* cornerflag;       // [tile (I, J) of the B square][8]: panels a piece has received
-  int ldc, corner_b0;         // leading dimension of a piece; first row of the B square
   int* dbg;                   // [8] the first poll that gave up: site, workgroup, step, awaited count, seen value, index
 };
 __device__ __forceinline__ void chain_note(int* dbg, int site, int step, unsigned need, unsigned seen, int index) {
@@ -724,12 +669,6 @@ __device__ __forceinline__ void wait_count(const unsigned* f, unsigned base, uns
     }
     __builtin_amdgcn_s_sleep(1);
   }
-}
-__device__ __forceinline__ int chain_row16(const ChainJob& jb, int at) {
-  if (at < 4 * jb.nA64) return jb.begin + 16 * at;
-  int r = at - 4 * jb.nA64, g = 0;
-  while (g + 1 < jb.nseg && r >= jb.sn16[g]) { r -= jb.sn16[g]; g++; }
-  return jb.sb0[g] + 16 * r;
 }
 // the 64 x 64 block L[t, t-1] from the hand-off buffer into pv (the layout of p0_load), polled value by value
 // (rows from `rows` on carry no data - the system's last block - and have no owner: they are zero, as in M)
@@ -1056,7 +995,7 @@ __device__ __forceinline__ void chain_helper_step(double* __restrict__ M, coh_bu
 }
 
 // Bulk workgroup (and every row owner after its last step): 64 x 64 tiles of the trailing updates, taken by ticket from a
-// list the host has put in PRIORITY order (chain_build): tile (I, J) of launch step l - "apply the panel of step l - 1" -
+// list the host has put in PRIORITY order (chol_sched::chain_launch, chol_schedule.h): tile (I, J) of launch step l - "apply the panel of step l - 1" -
 // has the key 0.4 l + 0.6 J, so the tiles of the column right behind the diagonal block (what the next step's row owners
 // wait for) come before the far columns of the step before, and a far tile receives its panels a little later, in order.
 // The key grows by less than 1 per step for one tile and every task's inputs have smaller keys: the list is a linear
@@ -1080,53 +1019,36 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
   const int lr = lane & 15, lk = lane >> 4;
   const int qrow = 32 * wr + lk, qcol = 32 * wc + lr;
   const int total = ctl.n_tasks;
-  int* const tkt = task + 37;   // the tickets of the three slots (read by nothing now that the cycle stamps are gone; k_chain is kept as measured)
-  const coh_buf cC = coh_make(ctl.corners ? ctl.corners : M, ctl.corners ? (size_t)8 * ctl.ldc * ctl.ldc * sizeof(double) : 8);
-  // l < 0: none.  For the products (types 0, 1): rows ri / rj of the panel at column j0; the tile lives at coff in M (type 0) or in
-  // the corner pieces (type 1, leading dimension cld; zero: its first panel, nothing to load); the counters it waits for are
-  // the eight row tiles of the panel (>= rneed) and its own history (hist >= hneed); done = the value its history gets
-  struct Tile { int l, type, ri, rj, j0, urgent, flag0, ti, tj, nrt, tk, rneed, cld, zero, hneed, dval, I, J, piece; size_t coff; unsigned* hist; };
-  auto take = [&](int slot) {   // thread 0: next ticket -> task[slot * 12 ..]
+  // l < 0: none.  The tile lives at coff in M and takes the rows ri / rj of the panel at column j0; the counters it waits for are
+  // the eight row tiles of that panel (>= l) and its own history (hist >= l - 1), which gets l when it is done
+  struct Tile { int l, ri, rj, j0, urgent, flag0, ti, tj, nrt; size_t coff; unsigned* hist; };
+  auto take = [&](int slot) {   // thread 0: next ticket -> task[slot * 8 ..]
     const int t = atomicAdd(ctl.ticket, 1);
-    ChainTask q = {0, 0, -1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ChainTask q = {0, -1, 0, 0, 0};
     if (t < total) q = ctl.tasks[t];
-    int* o = task + 12 * slot;
-    o[0] = q.l; o[1] = q.k; o[2] = q.type; o[3] = q.ti; o[4] = q.tj; o[5] = q.I; o[6] = q.J; o[7] = q.piece; o[8] = q.seq; o[9] = q.urgent;
-    tkt[slot] = t;
+    int* o = task + 8 * slot;
+    o[0] = q.l; o[1] = q.k; o[2] = q.ti; o[3] = q.tj; o[4] = q.urgent;
   };
   auto decode = [&](int slot, Tile& T) {
-    const int* o = task + 12 * slot;
+    const int* o = task + 8 * slot;
     T.l = o[0];
-    T.tk = tkt[slot];
     if (T.l < 0) return;
     const ChainJob& jb = jobs.job[o[1]];
-    T.type = o[2]; T.ti = o[3]; T.tj = o[4]; T.I = o[5]; T.J = o[6]; T.piece = o[7];
+    T.ti = o[2]; T.tj = o[3]; T.urgent = o[4];
     T.flag0 = jb.flag0; T.nrt = jb.nrt;
-    if (T.type == 2) return;   // (merge: handled outside the pipeline)
-    T.ri = chain_row16(jb, T.ti); T.rj = chain_row16(jb, T.tj);
-    T.urgent = o[9];
-    if (T.type == 0) {
-      T.j0 = jb.begin + NB * (T.l - 1);
-      T.rneed = T.l;
-      T.coff = (size_t)T.ri * ld + T.rj; T.cld = ld; T.zero = 0;
-      T.hist = &ctl.tileflag[(size_t)(T.ri / NB) * ctl.nblk + T.rj / NB];
-      T.hneed = T.l - 1; T.dval = T.l;
-    } else {
-      T.j0 = jb.begin + NB * T.l;
-      T.rneed = T.l + 1;
-      T.coff = (size_t)T.piece * ctl.ldc * ctl.ldc + (size_t)(NB * T.I) * ctl.ldc + NB * T.J; T.cld = ctl.ldc; T.zero = o[8] == 0;
-      T.hist = &ctl.cornerflag[(size_t)(T.I * (T.I + 1) / 2 + T.J) * 8 + T.piece];
-      T.hneed = o[8]; T.dval = o[8] + 1;
-    }
+    T.ri = row16(jb, T.ti); T.rj = row16(jb, T.tj);
+    T.j0 = jb.begin + NB * (T.l - 1);
+    T.coff = (size_t)T.ri * ld + T.rj;
+    T.hist = &ctl.tileflag[(size_t)(T.ri / NB) * ctl.nblk + T.rj / NB];
   };
   // the counters a tile waits for: the eight row tiles of its panel (lanes 0..7 of wave 0) and its own history (lane 8)
   auto flag_ptr = [&](const Tile& T, unsigned& need) -> const unsigned* {
     need = 0u;
     if (lane < 8) {
       const int tt = (lane < 4 ? T.ti : T.tj) + (lane & 3);
-      if (tt < T.nrt) { need = (unsigned)T.rneed; return &ctl.rowflag[T.flag0 + tt]; }
-    } else if (lane == 8 && T.hneed >= 1) {
-      need = (unsigned)T.hneed;
+      if (tt < T.nrt) { need = (unsigned)T.l; return &ctl.rowflag[T.flag0 + tt]; }
+    } else if (lane == 8 && T.l >= 2) {
+      need = (unsigned)(T.l - 1);
       return T.hist;
     }
     return nullptr;
@@ -1140,55 +1062,17 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       va[it] = ld_coh2(cM, (size_t)(T.ri + r) * ld + T.j0 + c2);
       vb[it] = ld_coh2(cM, (size_t)(T.rj + r) * ld + T.j0 + c2);
     }
-    if (T.zero) {
-      c00 = d4{0, 0, 0, 0}; c01 = c00; c10 = c00; c11 = c00;
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      const size_t p0 = T.coff + (size_t)(qrow + 4 * i) * T.cld + qcol;
-      const size_t p1 = T.coff + (size_t)(qrow + 16 + 4 * i) * T.cld + qcol;
-      if (T.type == 0) { c00[i] = ld_coh(cM, p0); c01[i] = ld_coh(cM, p0 + 16); c10[i] = ld_coh(cM, p1); c11[i] = ld_coh(cM, p1 + 16); }
-      else { c00[i] = ld_coh(cC, p0); c01[i] = ld_coh(cC, p0 + 16); c10[i] = ld_coh(cC, p1); c11[i] = ld_coh(cC, p1 + 16); }
+      const size_t p0 = T.coff + (size_t)(qrow + 4 * i) * ld + qcol;
+      const size_t p1 = T.coff + (size_t)(qrow + 16 + 4 * i) * ld + qcol;
+      c00[i] = ld_coh(cM, p0); c01[i] = ld_coh(cM, p0 + 16); c10[i] = ld_coh(cM, p1); c11[i] = ld_coh(cM, p1 + 16);
     }
   };
   auto wait_flags = [&](const Tile& T) {   // wave 0, blocking
     unsigned need;
     const unsigned* f = flag_ptr(T, need);
     if (f) wait_count(f, ctl.base, need, ctl.spin_limit, fail, ctl.dbg, lane < 8 ? 4 : 5, T.l, lane);
-  };
-  // M[corner tile] += the sum of its pieces, once every piece has all its panels (k_merge_corners' sums, in its order)
-  auto merge = [&](const Tile& T) {
-    const int len = T.l, ns = T.piece;
-    if (wave == 0 && lane < ns) {
-      const int cnt = len > lane ? (len - lane - 1) / ns + 1 : 0;
-      if (cnt > 0)
-        wait_count(&ctl.cornerflag[(size_t)(T.I * (T.I + 1) / 2 + T.J) * 8 + lane], ctl.base, (unsigned)cnt, ctl.spin_limit, fail, ctl.dbg, 6, len, lane);
-    }
-    __syncthreads();
-    const size_t pl = (size_t)ctl.ldc * ctl.ldc;
-#pragma unroll
-    for (int u = 0; u < 16; u++) {
-      const int e = u * 256 + tid, r = NB * T.I + (e >> 6), c = NB * T.J + (e & 63);
-      double v[8];
-#pragma unroll
-      for (int k = 0; k < 8; k++) v[k] = k < ns ? ld_coh(cC, (size_t)k * pl + (size_t)r * ctl.ldc + c) : 0.0;
-      double sacc = 0.0;
-#pragma unroll
-      for (int k = 0; k < 8; k++) sacc += v[k];
-      M[(size_t)(ctl.corner_b0 + r) * ld + ctl.corner_b0 + c] += sacc;
-    }
-    __syncthreads();
-  };
-  // the merges sit behind every product in the list: from the first one on a workgroup only merges
-  auto merge_loop = [&](Tile T) {
-    for (;;) {
-      merge(T);
-      if (tid == 0) take(0);
-      __syncthreads();
-      decode(0, T);
-      if (T.l < 0) return;
-    }
   };
   // Three tasks in flight: `cur` (operands in registers, then in LDS under the products), `nxt` (known; its counters asked
   // for a round earlier; fetched under cur's products when they are there) and `nn` (ticket taken, counters asked for).
@@ -1208,15 +1092,10 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
   __syncthreads();
   decode(0, cur);
   if (cur.l < 0) return;
-  if (cur.type == 2) { merge_loop(cur); return; }
   if (tid == 0) take(1);
   __syncthreads();
   decode(1, nxt);
-  const auto is_product = [](const Tile& T) { return T.l >= 0 && T.type != 2; };
-  Tile mtask;          // the first merge task this workgroup drew (handled when the products before it are done)
-  mtask.l = -1;
-  if (nxt.l >= 0 && nxt.type == 2) { mtask = nxt; nxt.l = -1; }
-  if (wave == 0) { wait_flags(cur); if (is_product(nxt)) ask(nxt); }
+  if (wave == 0) { wait_flags(cur); if (nxt.l >= 0) ask(nxt); }
   __syncthreads();
   fetch(cur);
   for (;;) {
@@ -1234,10 +1113,10 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       const bool ok = nxt.l < 0 || !fp || count_ready(fval, ctl.base, fneed);
       const bool all = __builtin_amdgcn_ballot_w64(!ok) == 0ull;
       if (lane == 0) {
-        task[36] = all ? 1 : 0;
+        task[24] = all ? 1 : 0;
         // a third ticket only when the second one can go ahead: a workgroup that is going to wait for its next tile must not
         // sit on another one meanwhile (-2: not taken yet)
-        if (all && nxt.l >= 0) take(2); else task[24] = nxt.l >= 0 ? -2 : -1;
+        if (all && nxt.l >= 0) take(2); else task[16] = nxt.l >= 0 ? -2 : -1;
       }
     }
     __syncthreads();   // B1: the operands are in LDS; the stores of the tile before are out (every wave waited above)
@@ -1245,27 +1124,25 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       __hip_atomic_store(pending, ctl.base + (unsigned)pending_l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       pending = nullptr;
     }
-    const bool ready = task[36] != 0 && nxt.l >= 0;
+    const bool ready = task[24] != 0 && nxt.l >= 0;
     if (ready) fetch(nxt);   // in flight under the products below
     decode(2, nn);
-    if (nn.l >= 0 && nn.type == 2) { mtask = nn; nn.l = -1; }   // a merge: no more products for this workgroup
     if (wave == 0 && nn.l >= 0) ask(nn);
     quad_abt(As, Bs, wr, wc, lr, lk, a00, a01, a10, a11);
     {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
-        const size_t p0 = cur.coff + (size_t)(qrow + 4 * i) * cur.cld + qcol;
-        const size_t p1 = cur.coff + (size_t)(qrow + 16 + 4 * i) * cur.cld + qcol;
-        if (cur.type == 0) { st_coh(cM, p0, a00[i]); st_coh(cM, p0 + 16, a01[i]); st_coh(cM, p1, a10[i]); st_coh(cM, p1 + 16, a11[i]); }
-        else { st_coh(cC, p0, a00[i]); st_coh(cC, p0 + 16, a01[i]); st_coh(cC, p1, a10[i]); st_coh(cC, p1 + 16, a11[i]); }
+        const size_t p0 = cur.coff + (size_t)(qrow + 4 * i) * ld + qcol;
+        const size_t p1 = cur.coff + (size_t)(qrow + 16 + 4 * i) * ld + qcol;
+        st_coh(cM, p0, a00[i]); st_coh(cM, p0 + 16, a01[i]); st_coh(cM, p1, a10[i]); st_coh(cM, p1 + 16, a11[i]);
       }
     }
     const bool last = nxt.l < 0;
     if (cur.urgent || last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next step's row owners wait for this tile
     __syncthreads();   // B2: every wave's part of the tile is issued (urgent: out); everybody is done with As / Bs and task[]
     if (tid == 0) {
-      if (cur.urgent || last) __hip_atomic_store(cur.hist, ctl.base + (unsigned)cur.dval, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      else { pending = cur.hist; pending_l = cur.dval; }
+      if (cur.urgent || last) __hip_atomic_store(cur.hist, ctl.base + (unsigned)cur.l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      else { pending = cur.hist; pending_l = cur.l; }
     }
     if (last) break;
     if (!ready) {   // (uniform) the counters were not there a round ago: wait for them now
@@ -1285,19 +1162,17 @@ __device__ __forceinline__ void chain_bulk(double* __restrict__ M, coh_buf cM, i
       if (tid == 0) take(2);
       __syncthreads();
       decode(2, nn);
-      if (nn.l >= 0 && nn.type == 2) { mtask = nn; nn.l = -1; }
       if (wave == 0 && nn.l >= 0) ask(nn);
     }
     nxt = nn;
   }
-  if (mtask.l >= 0) { __syncthreads(); merge_loop(mtask); }
 }
 
 __global__ __launch_bounds__(256) void k_chain(double* __restrict__ M, int ld, int n, double* __restrict__ Dinv, double* __restrict__ Ldiag,
                                                 int* fail, ChainJobs jobs, ChainCtl ctl) {
   __shared__ double sm[80 + 64 * DV + 2 * 64 * LDT];
   __shared__ double d00s[256];
-  __shared__ int task[40];   // three ticket slots of 12 words, the 'next is ready' word, the three tickets
+  __shared__ int task[25];   // three ticket slots of 8 words, the 'next is ready' word
   __shared__ int barlog_s[4];   // (MSFM_CHAIN_BARCHECK: what every wave says it is waiting at)
   int* const barlog = barlog_s;
   double* As = sm + 80 + 64 * DV;
@@ -1321,7 +1196,7 @@ __global__ __launch_bounds__(256) void k_chain(double* __restrict__ M, int ld, i
       ChainWave W;
       W.b = b;
       W.at = 4 + 3 * b + wave - 1;
-      W.r0 = (size_t)chain_row16(jb, W.at < jb.nrt ? W.at : 0);
+      W.r0 = (size_t)row16(jb, W.at < jb.nrt ? W.at : 0);
       ChainCarry C;
 #pragma unroll
       for (int i = 0; i < 16; i++) C.xr[i] = 0.0;
@@ -1352,12 +1227,6 @@ __global__ __launch_bounds__(256) void k_chain(double* __restrict__ M, int ld, i
 // and set the launch's length (config 3, level 0: 11 panel products against 5-6).  Now tile (I, J) is cut into
 // ceil(panels / target) pieces, at most MSFM_CORNER_SPLIT_MAX; the grid holds MSFM_CORNER_SPLIT_MAX workgroups per tile and
 // the surplus ones leave at once (a thousand empty workgroups start and end within a microsecond).
-#define MSFM_CORNER_SPLIT_MAX 8
-struct CornerRanges { short plo[MSFM_CORNER_MAX_BLOCKS], phi[MSFM_CORNER_MAX_BLOCKS]; };
-__host__ __device__ __forceinline__ int corner_splits(int panels, int target) {
-  const int s = (panels + target - 1) / target;
-  return s < 1 ? 1 : (s > MSFM_CORNER_SPLIT_MAX ? MSFM_CORNER_SPLIT_MAX : s);
-}
 // Rider (level 0 only, RIDER): the workgroups from n_own on are not the corner update's - workgroup n_own + mb does the
 // caller's per-intrinsics work for block mb (modelsum_body, solve_riders.h) with its first two waves.  It reads nothing the
 // update writes and stores into entries of M that the update does not read (columns from b0 on); the merge behind this
@@ -1529,16 +1398,13 @@ __device__ __forceinline__ void trinv64_block(const double* __restrict__ Ldiag, 
 
 __global__ __launch_bounds__(256) void k_trinv64_full(const double* __restrict__ Ldiag, int n, const double* __restrict__ Dinv,
                                                        double* __restrict__ Linv, int nblk, const double* __restrict__ M, int ld,
-                                                       double* __restrict__ w, int npad, unsigned long long* __restrict__ zfill) {
+                                                       double* __restrict__ w, int npad) {
   __shared__ double L[NB * LDT];
   __shared__ double v[NB * LDT];
   __shared__ double t[NB * LDT];
   if ((int)blockIdx.x >= nblk) {
     const int i = ((int)blockIdx.x - nblk) * 256 + (int)threadIdx.x;
-    if (i < npad) {
-      w[i] = (i < n) ? M[(size_t)n * ld + i] : 0.0;
-      if (zfill) zfill[i] = MSFM_Z_PENDING;   // "not solved yet" for k_backsolve_chain
-    }
+    if (i < npad) w[i] = (i < n) ? M[(size_t)n * ld + i] : 0.0;
     return;
   }
   trinv64_block(Ldiag, Dinv, (int)blockIdx.x, n, L, v, t);
@@ -1555,8 +1421,6 @@ __global__ __launch_bounds__(256) void k_trinv64_full(const double* __restrict__
 // mat-vec against the explicit inverse) so there is no in-launch dependency; the job's first
 // workgroup stores z_j.  Nobody writes w_j in this launch.
 // ---------------------------------------------------------------------------------------
-struct BackJob { int jb, ib, ni, wg0; };
-struct BackJobs { int count; BackJob job[16]; };
 __global__ __launch_bounds__(256) void k_backsolve_step(const double* __restrict__ M, int ld, int n, BackJobs jobs,
                                                          const double* __restrict__ Linv, double* __restrict__ w,
                                                          double* __restrict__ z) {
@@ -1696,11 +1560,6 @@ __global__ __launch_bounds__(256) void k_backsolve_pair(const double* __restrict
 // gets MSFM_FAIL_SYNC (the host returns MSFM_E_DEVICE) and the value is taken as 0 so that every workgroup still drains.
 // ---------------------------------------------------------------------------------------
 #define MSFM_BACKSOLVE_CHAIN_MAX 224   // upper bound; the limit in force is what the device can hold at once (resident_workgroups)
-struct BackTree {
-  int n_levels;
-  int root_blk;                       // first block of the root chain
-  struct { int K; struct { int b0, b1, leaf_lo, leaf_hi; } node[8]; } level[3];   // block ranges of the nodes
-};
 __global__ __launch_bounds__(256) void k_backsolve_chain(const double* __restrict__ M, int ld, int n, int nblk, BackTree tree,
                                                           const double* __restrict__ Ldiag, const double* __restrict__ Dinv,
                                                           double* __restrict__ z, unsigned long long* __restrict__ z_next,
@@ -1811,39 +1670,13 @@ __global__ __launch_bounds__(256) void k_backsolve_chain(const double* __restric
   }
 }
 
-// Host driver.  M: npad x npad, row n = rhs.  On return z[0..n) solves S z = rhs.
-// `fail` (device int) is OR-ed with 1 when S is not positive definite.
-// work: npad*16 doubles (16x16 inverses) + npad*64 (full block inverses) + npad*64 (diagonal blocks of L).
-// plan (optional): K uncoupled domains whose panel chains advance together, one job each per launch.
-// One tile per bulk workgroup: the hardware dispatcher balances them over the CUs the column-0 workgroups leave free
-// (4 tiles per workgroup with register prefetch of the next tile measured slower: coarser quantisation, same time per tile).
-static int bulk_workgroups(int ntile) { return ntile; }
-
-static PanelJob make_job(int j0, int t0, int a0, int nA64, int b0, int nrows_b /*data rows in B*/, double* corner, int ldc) {
-  PanelJob jb;
-  jb.j0 = j0; jb.t0 = t0; jb.a0 = a0; jb.na16 = 4 * nA64; jb.b0 = b0; jb.nb16 = cdiv(std::max(0, nrows_b), 16);
-  jb.nseg = 0;
-  for (int g = 0; g < 4; g++) { jb.sb0[g] = 0; jb.sn16[g] = 0; }
-  jb.nrt = jb.na16 + jb.nb16;
-  const int nt = nA64 + cdiv(jb.nb16, 4);
-  if (t0 >= 0) {
-    jb.ncw = std::max(1, cdiv(jb.nrt - 4, 3));  // column-0 workgroups: three 16-row tiles each
-    jb.ntile = j0 >= 0 ? nt * (nt - 1) / 2 : 0;
-  } else {
-    jb.ncw = 0;
-    jb.ntile = nt * (nt + 1) / 2;
-  }
-  jb.nwg = jb.ncw + bulk_workgroups(jb.ntile);
-  jb.wg0 = 0; jb.corner = corner; jb.ldc = ldc; jb.defer_corner = 0;
-  return jb;
-}
-
+// ---- Host driver: the steps below read the plan's CholSchedule and add what belongs to the call (buffers, epochs, riders, timers) ----
 // Workgroups of `kernel` (256 threads, static LDS only) that the device of `ctx` keeps resident at the same time: a kernel
 // whose workgroups wait for each other inside one launch is used only up to this many (asked once per device and kernel).
 // k_backsolve_chain's waits only ever go to workgroups with a LOWER blockIdx, so with every workgroup resident no dispatch
 // order can starve them.  k_chain is different: its row owners (the first blocks of the grid) also wait for tiles that BULK
 // workgroups - higher blockIdx - publish, so it needs every row owner AND at least one bulk workgroup resident; that is what
-// the `fits` rule of chain_build leaves room for.  Every poll is bounded besides (MSFM_FAIL_SYNC -> MSFM_E_DEVICE).
+// the `fits` rule of the schedule leaves room for.  Every poll is bounded besides (MSFM_FAIL_SYNC -> MSFM_E_DEVICE).
 template <class K>
 static int resident_workgroups(msfm_ctx* ctx, K kernel, int threads) {
   int per_cu = 0, cus = 0;
@@ -1863,64 +1696,16 @@ int msfm_chol_fill_pending(msfm_ctx* ctx, double* z, int npad) {
   return MSFM_OK;
 }
 
-// ---- host side of the persistent chain ----
-struct ChainLaunch {
-  ChainJobs jobs;
-  int task_off = 0, n_tasks = 0;   // the launch's tiles in ws->tasks
-  int steps = 0;        // panel steps on its critical path (for the timers)
-  bool usable = false;
-};
-// The deferred corner update of a tree level: per 64-row block of the B square (rows from b0 on) the panels of the level that lie
-// under the block's node, and into how many pieces a tile's panels are cut (k_corner_syrk / the corner tasks of k_chain).
-struct CornerPlan { CornerRanges R; int nB64 = 0, target = 1, smax = 1, sb = 0; };
-static void corner_plan(const msfm_chol_plan* plan, int lv, int nrows, CornerPlan& C) {
-  const int n_levels = plan->n_levels;
-  const msfm_chol_level& L = plan->level[lv];
-  const int K = L.K, sb = L.b0;
-  C.sb = sb;
-  C.nB64 = cdiv(nrows - sb, 64);
-  const int nB64 = std::min(C.nB64, MSFM_CORNER_MAX_BLOCKS);
-  CornerRanges& R = C.R;
-  for (int I = 0; I < nB64; I++) {
-    const int row = sb + 64 * I;
-    int lo = 0, hi = 0x7fffffff;   // leaf interval of the block's node; the root covers everything
-    for (int h = lv + 1; h < n_levels; h++)
-      for (int q = 0; q < plan->level[h].K; q++)
-        if (row >= plan->level[h].node[q].begin && row < plan->level[h].node[q].end) { lo = plan->level[h].node[q].leaf_lo; hi = plan->level[h].node[q].leaf_hi; }
-    int plo = 0, phi = 0;
-    bool any = false;
-    for (int q = 0; q < K; q++)
-      if (L.node[q].leaf_lo >= lo && L.node[q].leaf_hi <= hi) { if (!any) plo = L.node[q].begin / NB; phi = L.node[q].end / NB; any = true; }
-    R.plo[I] = (short)plo; R.phi[I] = (short)phi;
-  }
-  // panels per piece: the smallest count with which the pieces cover the chip about once
-  int target = 1, smax = 1;
-  for (;; target++) {
-    long wgs = 0;
-    smax = 1;
-    for (int I = 0; I < nB64; I++)
-      for (int J = 0; J <= I; J++) {
-        const int sp = corner_splits(std::min((int)R.phi[I], (int)R.phi[J]) - std::max((int)R.plo[I], (int)R.plo[J]), target);
-        wgs += sp;
-        smax = std::max(smax, sp);
-      }
-    if (wgs <= 560 || target >= 64) break;
-  }
-  C.target = target; C.smax = smax;
-}
-
 struct msfm_chol_ws {
   msfm_ctx* ctx = nullptr;
   int npad = 0;
   DevBuf<unsigned> flags;     // rowflag [8][npad / 16], then tileflag [(npad / 64)^2]
   DevBuf<double> hb;          // two hand-off buffers of npad x 64
   DevBuf<int> tickets;        // [8]
-  DevBuf<ChainTask> tasks;
+  DevBuf<ChainTask> tasks;    // sched.tasks on the device
   unsigned epoch = 0, n_launch = 0, flag_epoch = 0;   // solves (hand-off buffer parity), launches (ticket slot), launches (counter tag)
   bool dirty = true;          // the hand-off buffers and tickets must be (re)initialised before the next use
-  // launches of the plan they were built for (levels in order, then the root chain)
-  std::vector<ChainLaunch> launch;
-  unsigned long long sig = 0;
+  CholSchedule sched;         // of the plan of the last call (sched.sig)
   int capacity = 0;           // resident workgroups of k_chain on the context's device
 };
 
@@ -1929,7 +1714,7 @@ int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out) {
   std::unique_ptr<msfm_chol_ws> w(new msfm_chol_ws());
   w->ctx = ctx; w->npad = npad;
   const size_t nt16 = npad / 16, nb = npad / NB;
-  HIP_TRY(ctx, w->flags.alloc(8 * nt16 + nb * nb + 8 * (nb * (nb + 1) / 2)));   // ... then cornerflag [tiles of the B square][8]
+  HIP_TRY(ctx, w->flags.alloc(8 * nt16 + nb * nb));
   HIP_TRY(ctx, w->hb.alloc(2 * (size_t)npad * NB));
   HIP_TRY(ctx, w->tickets.alloc(16));   // eight ticket counters, then the eight words of the give-up note
   HIP_TRY(ctx, hipMemsetAsync(w->tickets.p, 0, sizeof(int) * 16, ctx->stream));
@@ -1940,128 +1725,62 @@ int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out) {
 }
 void msfm_chol_ws_destroy(msfm_chol_ws* w) { delete w; }
 
-// The launches of a plan: one per tree level (its K node chains side by side), then the root chain.
-static int chain_build(msfm_chol_ws* ws, int n, const msfm_chol_plan* plan, bool force) {
-  msfm_ctx* ctx = ws->ctx;
-  const int nrows = n + 1, n_levels = plan ? plan->n_levels : 0;
-  unsigned long long sig = 1469598103934665603ull;
-  auto mix = [&](long v) { sig = (sig ^ (unsigned long long)v) * 1099511628211ull; };
-  mix(n); mix(n_levels); mix(force);
-  for (int lv = 0; lv < n_levels; lv++) {
-    mix(plan->level[lv].K); mix(plan->level[lv].b0);
-    for (int k = 0; k < plan->level[lv].K; k++) { mix(plan->level[lv].node[k].begin); mix(plan->level[lv].node[k].end); mix(plan->level[lv].node[k].leaf_lo); mix(plan->level[lv].node[k].leaf_hi); }
-  }
-  if (sig == ws->sig && !ws->launch.empty()) return MSFM_OK;
-  ws->launch.clear();
-  std::vector<ChainTask> table;
-  const int root_begin = n_levels ? plan->level[n_levels - 1].b0 : 0;
-  const int nt16 = ws->npad / 16;
-  for (int lv = 0; lv <= n_levels; lv++) {
-    ChainLaunch L;
-    ChainJobs& J = L.jobs;
-    memset(&J, 0, sizeof J);
-    int wg = 0, maxp = 0;
-    if (lv < n_levels) {
-      const msfm_chol_level& PL = plan->level[lv];
-      for (int k = 0; k < PL.K; k++) {
-        const msfm_chol_node& nd = PL.node[k];
-        const int P = (nd.end - nd.begin) / NB;
-        if (P <= 0) continue;
-        ChainJob& jb = J.job[J.count];
-        jb.begin = nd.begin; jb.P = P; jb.nA64 = P;
-        jb.nseg = 0;
-        int rows16 = 0;
-        for (int h = lv + 1; h < n_levels; h++)
-          for (int q = 0; q < plan->level[h].K; q++) {
-            const msfm_chol_node& a = plan->level[h].node[q];
-            if (a.leaf_lo <= nd.leaf_lo && a.leaf_hi >= nd.leaf_hi) { jb.sb0[jb.nseg] = a.begin; jb.sn16[jb.nseg] = (a.end - a.begin) / 16; rows16 += jb.sn16[jb.nseg]; jb.nseg++; }
-          }
-        jb.sb0[jb.nseg] = root_begin; jb.sn16[jb.nseg] = cdiv(nrows - root_begin, 16); rows16 += jb.sn16[jb.nseg]; jb.nseg++;
-        jb.nb16 = rows16; jb.nB64 = cdiv(rows16, 4);
-        jb.nrt = 4 * P + rows16;
-        jb.ncw = std::max(1, cdiv(jb.nrt - 4, 3));
-        jb.wg0 = wg; wg += jb.ncw;
-        jb.flag0 = J.count * nt16;
-        if (jb.nrt > nt16) return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: chain job larger than the flag table");
-        maxp = std::max(maxp, P);
-        J.count++;
-      }
-    } else {
-      const int t_first = root_begin;
-      if (t_first < n) {
-        ChainJob& jb = J.job[0];
-        jb.begin = t_first; jb.P = cdiv(n - t_first, NB); jb.nA64 = cdiv(nrows - t_first, NB);
-        jb.nseg = 0; jb.nb16 = 0; jb.nB64 = 0;
-        jb.nrt = cdiv(nrows - t_first, 16);
-        jb.ncw = std::max(1, cdiv(jb.nrt - 4, 3));
-        jb.wg0 = 0; wg = jb.ncw; jb.flag0 = 0;
-        maxp = jb.P;
-        J.count = 1;
-      }
-    }
-    J.n_row_wg = wg;
-    J.n_steps = std::max(0, maxp - 1);
-    L.steps = maxp;
-    L.task_off = (int)table.size();
-    int max_step_tasks = 0;
-    {
-      // every tile of every launch step, in priority order: key = l + 0.6 (J - 1) (see chain_bulk)
-      struct Keyed { int key; ChainTask t; };
-      std::vector<Keyed> lt;
-      for (int l = 1; l <= J.n_steps; l++) {
-        int step_tasks = 0;
-        for (int k = 0; k < J.count; k++) {
-          if (l >= J.job[k].P) continue;
-          const int nA = J.job[k].nA64 - l, nB = J.job[k].nB64;
-          for (int Jc = 1; Jc < nA; Jc++)
-            for (int I = Jc; I < nA + nB; I++) {
-              lt.push_back(Keyed{10 * l + 6 * (Jc - 1), ChainTask{0, (short)k, (short)l, (short)(4 * (I + l)), (short)(4 * (Jc + l)), (short)I, (short)Jc, 0, 0,
-                                                                           (short)(Jc == 1 ? 1 : 0), 0, 0}});
-              step_tasks++;
-            }
-        }
-        max_step_tasks = std::max(max_step_tasks, step_tasks);
-      }
-      std::stable_sort(lt.begin(), lt.end(), [](const Keyed& a, const Keyed& b) { return a.key < b.key; });
-      for (const Keyed& q : lt) table.push_back(q.t);
-      L.n_tasks = (int)lt.size();
-    }
-    // bulk workgroups: what the device holds beside the row owners, at most one per tile of the busiest step
-    const int room = ws->capacity - wg;
-    J.n_bulk_wg = std::max(1, std::min(room, max_step_tasks));
-    // usable: every row owner resident with room to spare (other processes may share the device), a bulk workgroup for
-    // every three tiles of the busiest step at least
-    // (force, MSFM_CHAIN_FORCE: take the chain whatever the tile count)
-    // (a device shared with other contexts that launch the same kernel at the same time - ranks are synchronised by the
-    //  reduction in front of the factorisation - must hold the row owners of all of them, or none makes progress)
-    const int share = std::max(1, ctx->device_share);
-    // One context per device: the row owners may take just under half of the resident workgroups.  Two independent PROCESSES
-    // that share a GPU without MSFM_DEVICE_SHARE set each see share == 1; with exactly half each, their row owners together
-    // could fill the device and leave no bulk workgroup of either resident - both would spin to the poll limit.  Two short of
-    // half, one bulk workgroup of one of the two launches always finds a slot, that launch drains (whoever holds the lowest
-    // open ticket can finish), and the other follows.  (A quarter, as the round-4 review suggested, would send systems of more
-    // than ~170 blocks - config 5 in full - back to the launch chain for a case the bounded polls already turn into an error.)
-    const bool fits = share == 1 ? wg <= ws->capacity / 2 - 2 : (long)wg * share <= 3L * ws->capacity / 4;
-    L.usable = J.count > 0 && fits && (max_step_tasks == 0 || 3 * room >= max_step_tasks || force) && maxp < 4000;
-    ws->launch.push_back(L);
-  }
-  HIP_TRY(ctx, ws->tasks.alloc(std::max<size_t>(1, table.size())));
-  HIP_TRY(ctx, hipMemcpyAsync(ws->tasks.p, table.data(), sizeof(ChainTask) * table.size(), hipMemcpyHostToDevice, ctx->stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the host table goes away on return; built once per plan)
-  ws->sig = sig;
-  ws->dirty = true;   // a new plan: hand-off blocks of the old layout must not be read as published values
-  return MSFM_OK;
-}
-
 // polls of a bounded in-kernel wait: a poll is an L2 round trip plus s_sleep, ~0.3 us; the bound is MSFM_SYNC_TIMEOUT_S, as for the
 // host's own spin
 static unsigned chain_spin_limit() {
   return (unsigned)std::min(4.0e9, std::max(1.0e4, msfm_env_process().sync_timeout_s * 3.0e6));
 }
 
-static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int npad, int n, double* Dinv, double* Ldiag, int* fail,
-                        int ldc, bool trace) {
+// One call of msfm_chol_factor_solve: its arguments, the plan's schedule and the forms it may take
+struct CholCall {
+  msfm_ctx* ctx;
+  const msfm_env& env;
+  double* M; int npad, n;
+  double *Dinv, *Linv, *Ldiag;   // work: npad * 16 doubles (16x16 inverses) + npad * 64 (full block inverses) + npad * 64 (diagonal blocks of L)
+  double *w, *z, *z_next; int* fail;
+  const msfm_chol_plan* plan; msfm_chol_ws* ws; msfm_chol_riders* riders;
+  const CholSchedule* S;
+  bool use_chain;   // the persistent form, for the groups whose launch is usable
+  int ran;          // the MSFM_PATH_* bits of this call
+};
+
+// The workspace's schedule, rebuilt when the plan (or anything else it depends on) has changed.  A plan that cannot run is
+// refused here, before the first launch.
+static int get_schedule(msfm_chol_ws* ws, const msfm_env& env, int npad, int n, const msfm_chol_plan* plan) {
   msfm_ctx* ctx = ws->ctx;
+  const unsigned long long sig = chol_schedule_sig(n, npad, plan, ws->capacity, ctx->device_share, env.chain_force);
+  if (ws->sched.sig == sig) return MSFM_OK;
+  std::string err;
+  const int rc = chol_schedule_build(n, npad, plan, ws->capacity, ctx->device_share, env.chain_force, ws->sched, &err);
+  if (rc != MSFM_OK) return msfm_set_error(ctx, rc, "%s", err.c_str());
+  const std::vector<ChainTask>& table = ws->sched.tasks;
+  ws->sched.sig = 0;   // (until the table is on the device)
+  HIP_TRY(ctx, ws->tasks.alloc(std::max<size_t>(1, table.size())));
+  HIP_TRY(ctx, hipMemcpyAsync(ws->tasks.p, table.data(), sizeof(ChainTask) * table.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (built once per plan)
+  ws->sched.sig = sig;
+  ws->dirty = true;   // a new plan: hand-off blocks of the old layout must not be read as published values
+  return MSFM_OK;
+}
+
+// The hand-off state of k_chain for this solve: the next epoch; buffers and tickets initialised again after a new plan or a
+// launch error
+static int prepare_handoff(CholCall& c) {
+  if (!c.use_chain) return MSFM_OK;
+  msfm_chol_ws* ws = c.ws;
+  ws->epoch++;
+  if (ws->dirty) {
+    MSFM_TRY(msfm_chol_fill_pending(c.ctx, ws->hb.p, 2 * c.npad * NB));
+    HIP_TRY(c.ctx, hipMemsetAsync(ws->tickets.p, 0, sizeof(int) * 8, c.ctx->stream));
+    ws->n_launch = 0;
+    ws->dirty = false;
+  }
+  return MSFM_OK;
+}
+
+static void chain_launch(CholCall& call, const ChainLaunch& L) {
+  msfm_chol_ws* ws = call.ws;
+  const int npad = call.npad;
   ChainCtl c;
   const size_t nt16 = npad / 16, nb = npad / NB;
   c.rowflag = ws->flags.p;
@@ -2077,271 +1796,123 @@ static int chain_launch(msfm_chol_ws* ws, const ChainLaunch& L, double* M, int n
   c.base = (++ws->flag_epoch & 0xFFFFFu) << 12;   // per LAUNCH: the launches of one solve reuse the rowflag slots of their jobs
   c.spin_limit = chain_spin_limit();
   c.nblk = (int)nb;
-  c.corners = nullptr;   // (the corner update runs as k_corner_syrk / k_merge_corners behind the launch)
-  c.cornerflag = ws->flags.p + 8 * nt16 + nb * nb;
-  c.ldc = ldc; c.corner_b0 = 0;
   c.dbg = ws->tickets.p + 8;
 #ifdef MSFM_CHAIN_BARCHECK
-  if (trace) fprintf(stderr, "k_chain: n %d, %d row owners, %d bulk workgroups, %d steps\n", n, L.jobs.n_row_wg, L.jobs.n_bulk_wg, L.steps);
+  if (call.env.chain_trace)
+    fprintf(stderr, "k_chain: n %d, %d row owners, %d bulk workgroups, %d steps\n", call.n, L.jobs.n_row_wg, L.jobs.n_bulk_wg, L.steps);
 #endif
-  hipLaunchKernelGGL(k_chain, dim3(L.jobs.n_row_wg + L.jobs.n_bulk_wg), dim3(256), 0, ctx->stream, M, npad, n, Dinv, Ldiag, fail, L.jobs, c);
+  hipLaunchKernelGGL(k_chain, dim3(L.jobs.n_row_wg + L.jobs.n_bulk_wg), dim3(256), 0, call.ctx->stream, call.M, npad, call.n, call.Dinv, call.Ldiag,
+                     call.fail, L.jobs, c);
+}
+
+// The panel chains of a group (a tree level's, or the root chain): one k_chain launch where the device can hold it, otherwise
+// one k_panel_v2 launch per 64-column step.  Timed as a whole and counted in panel steps on either form, so that a step's time
+// compares.
+static void factor_group(CholCall& c, const ChainGroup& G, int path_bit) {
+  KTimer timer(c.ctx, "chol_panel_mfma");
+  timer.count = 0;
+  if (c.use_chain && G.chain.usable) {
+    chain_launch(c, G.chain);
+    timer.count = G.chain.steps;
+    c.ran |= path_bit;
+    return;
+  }
+  for (const PanelLaunch& P : G.panels) {
+    // trailing update with the panels of the step before + potrf / trsm of the step's blocks
+    if (P.full) hipLaunchKernelGGL(k_panel_v2<true>, dim3(P.grid), dim3(256), 0, c.ctx->stream, c.M, c.npad, c.n, c.Dinv, c.Ldiag, c.fail, P.jobs);
+    else hipLaunchKernelGGL(k_panel_v2<false>, dim3(P.grid), dim3(256), 0, c.ctx->stream, c.M, c.npad, c.n, c.Dinv, c.Ldiag, c.fail, P.jobs);
+    timer.count++;
+  }
+}
+static void factor_level(CholCall& c, int lv) { factor_group(c, c.S->group[lv], MSFM_PATH_LEVEL_CHAIN(lv)); }
+static void factor_root(CholCall& c) { factor_group(c, c.S->group[c.S->n_levels], MSFM_PATH_ROOT_CHAIN); }
+
+// The B x B tiles that the level's chains left out: the products of all panels (k_corner_syrk), then their sums into M
+// (k_merge_corners).  The caller's model-sum rider goes with the level-0 update on either factorisation form; a level without
+// panels has no update, and the launch then holds the rider's workgroups alone.
+static void corner_update(CholCall& c, int lv) {
+  const ChainGroup& G = c.S->group[lv];
+  const CornerPlan& C = G.corner;
+  hipStream_t s = c.ctx->stream;
+  double* const corners = c.plan->corners; const int ldc = c.plan->ldc;
+  ModelSumArgs rider;
+  memset(&rider, 0, sizeof rider);
+  if (lv == 0 && c.riders->modelsum) rider = *c.riders->modelsum;
+  if (G.has_corner) {
+    KTimer t(c.ctx, "chol_corner_syrk");
+    t.count = 2;
+    const int n_own = C.ntile * C.smax;
+    if (rider.nmb > 0)
+      hipLaunchKernelGGL(k_corner_syrk<true>, dim3(n_own + rider.nmb), dim3(256), 0, s, c.M, c.npad, C.sb, C.target, C.smax, corners, ldc, C.R, n_own, rider);
+    else
+      hipLaunchKernelGGL(k_corner_syrk<false>, dim3(n_own), dim3(256), 0, s, c.M, c.npad, C.sb, C.target, C.smax, corners, ldc, C.R, n_own, NoRider());
+    hipLaunchKernelGGL(k_merge_corners, dim3(4 * C.ntile), dim3(256), 0, s, c.M, c.npad, C.sb, C.nB64, corners, ldc, C.target, C.R);
+  } else if (rider.nmb > 0) {
+    hipLaunchKernelGGL(k_corner_syrk<true>, dim3(rider.nmb), dim3(256), 0, s, c.M, c.npad, C.sb, 1, 1, corners, ldc, C.R, 0, rider);
+  }
+}
+
+// L^T z = w.  One launch (k_backsolve_chain, which also takes the caller's epilogue along and leaves z_next "pending") while
+// the device holds a workgroup per block at once; otherwise the full inverses of the diagonal blocks (k_trinv64_full) and the
+// schedule's pair / step launches.  z holds MSFM_Z_PENDING everywhere on entry (msfm_chol_fill_pending once, afterwards the
+// call before's z_next) and z_next does on return: the two alternate from solve to solve on both forms.
+static int back_substitute(CholCall& c) {
+  const CholSchedule& S = *c.S;
+  hipStream_t s = c.ctx->stream;
+  KTimer t(c.ctx, "chol_backsolve");
+  // per device: min(MSFM_BACKSOLVE_CHAIN_MAX, resident workgroups of k_backsolve_chain), 0 = not asked yet (atomic: the
+  // per-rank host threads of msfm_multi come through here at the same time; both would store the same value)
+  static std::atomic<int> chain_max[64];
+  int cmax = chain_max[c.ctx->device & 63].load(std::memory_order_relaxed);
+  if (cmax == 0) {
+    cmax = std::max(1, std::min(MSFM_BACKSOLVE_CHAIN_MAX, resident_workgroups(c.ctx, k_backsolve_chain, 256)));
+    chain_max[c.ctx->device & 63].store(cmax, std::memory_order_relaxed);
+  }
+  if (S.nblk <= cmax && !c.env.chol_launches) {
+    c.ran |= MSFM_PATH_BACKSOLVE_CHAIN;
+    SolveEpilogue ep;
+    memset(&ep, 0, sizeof ep);
+    if (c.riders->epilogue) { ep = *c.riders->epilogue; c.riders->epilogue_ran = true; }
+    hipLaunchKernelGGL(k_backsolve_chain, dim3(S.nblk), dim3(256), 0, s, c.M, c.npad, c.n, S.nblk, S.tree, c.Ldiag, c.Dinv, c.z,
+                       reinterpret_cast<unsigned long long*>(c.z_next), c.fail, chain_spin_limit(), ep);
+    return MSFM_OK;
+  }
+  hipLaunchKernelGGL(k_trinv64_full, dim3(S.trinv_grid), dim3(256), 0, s, c.Ldiag, c.n, c.Dinv, c.Linv, S.nblk, c.M, c.npad, c.w, c.npad);
+  MSFM_TRY(msfm_chol_fill_pending(c.ctx, c.z_next, c.npad));
+  for (const BackLaunch& B : S.back) {
+    if (B.pair) hipLaunchKernelGGL(k_backsolve_pair, dim3(B.grid), dim3(256), 0, s, c.M, c.npad, c.n, B.jobs, c.Linv, c.w, c.z);
+    else hipLaunchKernelGGL(k_backsolve_step, dim3(B.grid), dim3(256), 0, s, c.M, c.npad, c.n, B.jobs, c.Linv, c.w, c.z);
+  }
   return MSFM_OK;
 }
 
-// z_next (optional): a second solution buffer of npad doubles.  With it the caller promises that `z` already holds
-// MSFM_Z_PENDING everywhere (msfm_chol_fill_pending once, afterwards the previous call's z_next) and gets z_next back in that
-// state - the two buffers alternate from solve to solve and no fill launch sits on the critical path.  Without it the
-// function fills z itself first.
+// M: npad x npad, row n = rhs.  On return z[0..n) solves S z = rhs; `fail` (device int) is OR-ed with 1 when S is not positive
+// definite.  plan: nullptr or no levels for the dense order.  z / z_next: see back_substitute.
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
                            const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws, int* paths, msfm_chol_riders* riders) {
   if (paths) *paths = 0;   // (a call that fails reports no path)
   if (riders) riders->epilogue_ran = false;
-  if (riders && riders->modelsum && !(plan && plan->n_levels > 0))
-    return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: the model-sum rider needs an elimination tree");
-  if (!M || !work || !w || !z || !fail || npad % NB != 0 || n < 1 || n + 1 > npad)
+  if (!paths || !riders || !ws || !z_next || !M || !work || !w || !z || !fail || npad % NB != 0 || n < 1 || n + 1 > npad)
     return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad workspace (null buffer or size)");
-  hipStream_t s = ctx->stream;
-  const int nrows = n + 1;  // rows that carry data (S plus the rhs row)
-  double* Dinv = work;
-  double* Linv = work + (size_t)npad * 16;
-  double* Ldiag = work + (size_t)npad * 80;
-  int t_first = 0, ran = 0;   // ran: the MSFM_PATH_* bits of this call
-  const int n_levels = plan ? plan->n_levels : 0;
-  // the persistent chain (one launch per tree level) when the caller keeps a workspace for it; MSFM_CHOL_LAUNCHES=1: the
-  // round-3 chain of one launch per 64-column panel and the back substitution by block pairs, for comparison
-  bool use_chain = ws && !env.chol_launches && ws->npad == npad && ws->capacity > 0 && (size_t)npad * npad * sizeof(double) < 0xFFFFFFFFull;   // (32-bit buffer offsets)
-  if (use_chain) {
-    MSFM_TRY(chain_build(ws, n, plan, env.chain_force));
-    if ((int)ws->launch.size() != n_levels + 1) use_chain = false;
+  if (riders->modelsum && !(plan && plan->n_levels > 0))
+    return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: the model-sum rider needs an elimination tree");
+  MSFM_TRY(get_schedule(ws, env, npad, n, plan));
+  // the persistent chain (one launch per tree level) where the workspace was made for this size; MSFM_CHOL_LAUNCHES=1: one
+  // launch per 64-column panel and the back substitution by block pairs, the form for systems past 4 GB and the tests' reference
+  const bool use_chain = !env.chol_launches && ws->npad == npad && ws->capacity > 0 && (size_t)npad * npad * sizeof(double) < 0xFFFFFFFFull;   // (32-bit buffer offsets)
+  CholCall c = {ctx, env, M, npad, n, work, work + (size_t)npad * 16, work + (size_t)npad * 80, w, z, z_next, fail, plan, ws, riders, &ws->sched, use_chain, 0};
+  MSFM_TRY(prepare_handoff(c));
+  for (int lv = 0; lv < c.S->n_levels; lv++) {
+    factor_level(c, lv);
+    corner_update(c, lv);
   }
-  if (use_chain) {
-    ws->epoch++;
-    if (ws->dirty) {
-      MSFM_TRY(msfm_chol_fill_pending(ctx, ws->hb.p, 2 * npad * NB));
-      HIP_TRY(ctx, hipMemsetAsync(ws->tickets.p, 0, sizeof(int) * 8, s));
-      ws->n_launch = 0;
-      ws->dirty = false;
-    }
-  }
-  if (n_levels > 0) {
-    if (n_levels > 3 || !plan->corners) return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad plan");
-    // every level is checked before the first launch: a refusal must not leave half a factorisation behind
-    for (int lv = 0; lv < n_levels; lv++) {
-      const msfm_chol_level& L = plan->level[lv];
-      if (L.K < 1 || L.K > 8 || L.b0 % NB || L.begin % NB || plan->ldc < 64 * cdiv(nrows - L.b0, 64))
-        return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad plan level");
-      if (cdiv(nrows - L.b0, 64) > MSFM_CORNER_MAX_BLOCKS)
-        return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: separator part too large for the corner update (%d blocks)", cdiv(nrows - L.b0, 64));
-    }
-    for (int lv = 0; lv < n_levels; lv++) {
-      // ---- the K chains of this level, step by step: step l of node k factors its block l (after applying its panel
-      //      l-1); the step after a node's last block only applies that last panel to the rows from b0 on ----
-      const msfm_chol_level& L = plan->level[lv];
-      const int K = L.K, sb = L.b0, ldc = plan->ldc;
-      if (K < 1 || K > 8 || sb % NB || L.begin % NB || ldc < 64 * cdiv(nrows - sb, 64)) return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: bad plan level");
-      const int root_begin = plan->level[n_levels - 1].b0;
-      // rows a node's panels reach below the node itself: its ancestors (one node per higher level), then the root
-      // chain with the rhs row - everything else from b0 on is structurally zero in its columns
-      auto ancestors = [&](const msfm_chol_node& nd, PanelJob& jb) {
-        jb.nseg = 0;
-        int rows = 0;
-        for (int h = lv + 1; h < n_levels; h++)
-          for (int q = 0; q < plan->level[h].K; q++) {
-            const msfm_chol_node& a = plan->level[h].node[q];
-            if (a.leaf_lo <= nd.leaf_lo && a.leaf_hi >= nd.leaf_hi) { jb.sb0[jb.nseg] = a.begin; jb.sn16[jb.nseg] = (a.end - a.begin) / 16; jb.nseg++; rows += a.end - a.begin; }
-          }
-        jb.sb0[jb.nseg] = root_begin; jb.sn16[jb.nseg] = cdiv(nrows - root_begin, 16); jb.nseg++;
-        rows += nrows - root_begin;
-        return rows;
-      };
-      int maxp = 0;
-      for (int k = 0; k < K; k++) maxp = std::max(maxp, (L.node[k].end - L.node[k].begin) / NB);
-      KTimer chain_timer(ctx, "chol_panel_mfma");   // the level's chain of panel launches as a whole
-      chain_timer.count = 0;
-      const bool lv_chain = use_chain && ws->launch[lv].usable;
-      if (lv_chain) {
-        MSFM_TRY(chain_launch(ws, ws->launch[lv], M, npad, n, Dinv, Ldiag, fail, ldc, env.chain_trace));
-        chain_timer.count = ws->launch[lv].steps;   // (counted in panel steps, so that a step's time compares with the launch chain's)
-        ran |= MSFM_PATH_LEVEL_CHAIN(lv);
-      }
-      for (int l = 0; l < maxp && !lv_chain; l++) {
-        PanelJobs jobs;
-        jobs.count = 0;
-        int wg = 0;
-        for (int k = 0; k < K; k++) {
-          const int P = (L.node[k].end - L.node[k].begin) / NB;
-          if (l >= P) continue;
-          const int t0 = L.node[k].begin + NB * l;
-          const int j0 = l > 0 ? L.node[k].begin + NB * (l - 1) : -1;
-          PanelJob seg;
-          const int brows = ancestors(L.node[k], seg);
-          PanelJob jb = make_job(j0, t0, t0, P - l, sb, brows, nullptr, 0);
-          jb.nseg = seg.nseg;
-          for (int g = 0; g < 4; g++) { jb.sb0[g] = seg.sb0[g]; jb.sn16[g] = seg.sn16[g]; }
-          // the tiles among the rows from b0 on are formed once, after the chains (k_corner_syrk): leave them out here
-          const int nA64 = P - l, nB64 = cdiv(jb.nb16, 4);
-          jb.defer_corner = 1;
-          jb.ntile = j0 >= 0 ? nA64 * (nA64 - 1) / 2 + nB64 * (nA64 - 1) : 0;
-          jb.nwg = jb.ncw + bulk_workgroups(jb.ntile);
-          jb.wg0 = wg;
-          wg += jb.nwg;
-          jobs.job[jobs.count++] = jb;
-        }
-        if (!jobs.count) break;
-        hipLaunchKernelGGL(k_panel_v2<true>, dim3(wg), dim3(256), 0, s, M, npad, n, Dinv, Ldiag, fail, jobs);
-        chain_timer.count++;
-      }
-      chain_timer.stop();
-      // the caller's rider goes with the level-0 corner update on either path above (a level without panels has no update: the
-      // launch then holds the rider's workgroups alone)
-      ModelSumArgs rider;
-      memset(&rider, 0, sizeof rider);
-      if (lv == 0 && riders && riders->modelsum) rider = *riders->modelsum;
-      if (maxp > 0) {
-        KTimer t(ctx, "chol_corner_syrk");
-        t.count = 2;
-        const int nB64 = cdiv(nrows - sb, 64), ntile = nB64 * (nB64 + 1) / 2;
-        if (nB64 > MSFM_CORNER_MAX_BLOCKS)   // (choose_dissection never picks such a tree: checked before anything is launched)
-          return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: separator part too large for the corner update (%d blocks)", nB64);
-        CornerPlan CP;
-        corner_plan(plan, lv, nrows, CP);
-        const CornerRanges& R = CP.R;
-        const int target = CP.target, smax = CP.smax;
-        if (rider.nmb > 0) {
-          hipLaunchKernelGGL(k_corner_syrk<true>, dim3(ntile * smax + rider.nmb), dim3(256), 0, s, M, npad, sb, target, smax, plan->corners, ldc, R,
-                             ntile * smax, rider);
-        } else {
-          hipLaunchKernelGGL(k_corner_syrk<false>, dim3(ntile * smax), dim3(256), 0, s, M, npad, sb, target, smax, plan->corners, ldc, R,
-                             ntile * smax, NoRider());
-        }
-        hipLaunchKernelGGL(k_merge_corners, dim3(4 * ntile), dim3(256), 0, s, M, npad, sb, nB64, plan->corners, ldc, target, R);
-      } else if (rider.nmb > 0) {
-        CornerRanges R;
-        memset(&R, 0, sizeof R);
-        hipLaunchKernelGGL(k_corner_syrk<true>, dim3(rider.nmb), dim3(256), 0, s, M, npad, sb, 1, 1, plan->corners, ldc, R, 0, rider);
-      }
-      t_first = sb;
-    }
-  }
-  KTimer root_timer(ctx, "chol_panel_mfma");
-  root_timer.count = 0;
-  const bool root_chain = use_chain && ws->launch[n_levels].usable;
-  if (root_chain) {
-    MSFM_TRY(chain_launch(ws, ws->launch[n_levels], M, npad, n, Dinv, Ldiag, fail, 0, env.chain_trace));
-    root_timer.count = ws->launch[n_levels].steps;
-    ran |= MSFM_PATH_ROOT_CHAIN;
-  }
-  for (int t0 = t_first; t0 < n && !root_chain; t0 += NB) {
-    // the separator (or the whole matrix): one job per launch, its first block has nothing left to apply
-    const int j0 = t0 > t_first ? t0 - NB : -1;
-    PanelJobs jobs;
-    jobs.count = 1;
-    jobs.job[0] = make_job(j0, t0, t0, cdiv(nrows - t0, 64), 0, 0, nullptr, 0);
-    jobs.job[0].nrt = cdiv(nrows - t0, 16);  // 16-row tiles from t0 down that carry data
-    jobs.job[0].ncw = std::max(1, cdiv(jobs.job[0].nrt - 4, 3));
-    jobs.job[0].nwg = jobs.job[0].ncw + bulk_workgroups(jobs.job[0].ntile);
-    // trailing update with panel j0 + potrf / trsm of the panel at t0
-    if (n - t0 >= NB) hipLaunchKernelGGL(k_panel_v2<true>, dim3(jobs.job[0].nwg), dim3(256), 0, s, M, npad, n, Dinv, Ldiag, fail, jobs);
-    else hipLaunchKernelGGL(k_panel_v2<false>, dim3(jobs.job[0].nwg), dim3(256), 0, s, M, npad, n, Dinv, Ldiag, fail, jobs);
-    root_timer.count++;
-  }
-  root_timer.stop();
-  {
-    KTimer t(ctx, "chol_backsolve");
-    const int nblk = cdiv(n, NB);
-    // per device: min(MSFM_BACKSOLVE_CHAIN_MAX, resident workgroups of k_backsolve_chain), 0 = not asked yet (atomic: the
-    // per-rank host threads of msfm_multi come through here at the same time; both would store the same value)
-    static std::atomic<int> chain_max[64];
-    int cmax = chain_max[ctx->device & 63].load(std::memory_order_relaxed);
-    if (cmax == 0) {
-      cmax = std::max(1, std::min(MSFM_BACKSOLVE_CHAIN_MAX, resident_workgroups(ctx, k_backsolve_chain, 256)));
-      chain_max[ctx->device & 63].store(cmax, std::memory_order_relaxed);
-    }
-    const bool chain = nblk <= cmax && !env.chol_launches;   // (otherwise the round-2 chain of launches)
-    if (chain) ran |= MSFM_PATH_BACKSOLVE_CHAIN;
-    if (!chain) hipLaunchKernelGGL(k_trinv64_full, dim3(nblk + cdiv(npad, 256)), dim3(256), 0, s, Ldiag, n, Dinv, Linv, nblk, M, npad, w, npad,
-                                   (unsigned long long*)nullptr);
-    if (chain) {
-      if (!z_next) MSFM_TRY(msfm_chol_fill_pending(ctx, z, npad));
-      BackTree bt;
-      bt.n_levels = n_levels;
-      bt.root_blk = t_first / NB;
-      for (int lv = 0; lv < 3; lv++) {
-        bt.level[lv].K = lv < n_levels ? plan->level[lv].K : 0;
-        for (int k = 0; k < 8; k++) {
-          const bool live = lv < n_levels && k < plan->level[lv].K;
-          const msfm_chol_node nd = live ? plan->level[lv].node[k] : msfm_chol_node{0, 0, 0, 0};
-          bt.level[lv].node[k].b0 = nd.begin / NB; bt.level[lv].node[k].b1 = nd.end / NB;
-          bt.level[lv].node[k].leaf_lo = nd.leaf_lo; bt.level[lv].node[k].leaf_hi = nd.leaf_hi;
-        }
-      }
-      SolveEpilogue ep;
-      memset(&ep, 0, sizeof ep);
-      if (riders && riders->epilogue) { ep = *riders->epilogue; riders->epilogue_ran = true; }
-      hipLaunchKernelGGL(k_backsolve_chain, dim3(nblk), dim3(256), 0, s, M, npad, n, nblk, bt, Ldiag, Dinv, z,
-                         reinterpret_cast<unsigned long long*>(z_next), fail, chain_spin_limit(), ep);
-    } else if (z_next) {
-      MSFM_TRY(msfm_chol_fill_pending(ctx, z_next, npad));   // keep the caller's alternation intact on the launch-chain path
-    }
-    const int first_dense = t_first / NB;
-    for (int jb = nblk - 1; !chain && jb >= first_dense;) {  // root chain (or everything): couples to every block before it
-      BackJobs bj;
-      bj.count = 1;
-      if (jb - 1 >= first_dense) {   // blocks jb and jb-1 together
-        bj.job[0] = BackJob{jb, 0, jb - 1, 0};
-        hipLaunchKernelGGL(k_backsolve_pair, dim3(jb - 1 > 0 ? jb - 1 : 1), dim3(256), 0, s, M, npad, n, bj, Linv, w, z);
-        jb -= 2;
-      } else {
-        bj.job[0] = BackJob{jb, 0, jb, 0};
-        hipLaunchKernelGGL(k_backsolve_step, dim3(jb > 0 ? jb : 1), dim3(256), 0, s, M, npad, n, bj, Linv, w, z);
-        jb -= 1;
-      }
-    }
-    for (int lv = n_levels - 1; !chain && lv >= 0; lv--) {
-      // Blocks P_k - 1 - 2l and P_k - 2 - 2l of every node of the level in one launch (a node's last odd block alone).  A
-      // block couples to the earlier blocks of its own node and to its descendants in the lower levels (contiguous in
-      // every level: tree order) - one job per range, all of them recomputing z for themselves; siblings never touch the
-      // same rows.
-      const msfm_chol_level& L = plan->level[lv];
-      int maxp = 0;
-      for (int k = 0; k < L.K; k++) maxp = std::max(maxp, (L.node[k].end - L.node[k].begin) / NB);
-      for (int l = 0; 2 * l < maxp; l++) {
-        BackJobs pj, sj;
-        pj.count = sj.count = 0;
-        int pwg = 0, swg = 0;
-        for (int k = 0; k < L.K; k++) {
-          const int ib = L.node[k].begin / NB, P = (L.node[k].end - L.node[k].begin) / NB;
-          if (2 * l >= P) continue;
-          const int jb = ib + P - 1 - 2 * l;
-          const bool pair = jb - 1 >= ib;
-          BackJobs& J = pair ? pj : sj;
-          int& wg = pair ? pwg : swg;
-          const int own = pair ? jb - 1 - ib : jb - ib;   // earlier blocks of the node itself
-          J.job[J.count++] = BackJob{jb, ib, own, wg};
-          wg += std::max(1, own);
-          for (int lo = lv - 1; lo >= 0; lo--) {   // descendants, level by level
-            const msfm_chol_level& D = plan->level[lo];
-            int d0 = -1, d1 = -1;
-            for (int q = 0; q < D.K; q++)
-              if (D.node[q].leaf_lo >= L.node[k].leaf_lo && D.node[q].leaf_hi <= L.node[k].leaf_hi) { if (d0 < 0) d0 = q; d1 = q; }
-            if (d0 < 0) continue;
-            const int rb = D.node[d0].begin / NB, rn = (D.node[d1].end - D.node[d0].begin) / NB;
-            if (rn <= 0) continue;
-            if (J.count >= 16) return msfm_set_error(ctx, MSFM_E_INVAL, "cholesky: too many back-substitution ranges in one launch");
-            J.job[J.count++] = BackJob{jb, rb, rn, wg};
-            wg += rn;
-          }
-        }
-        if (pj.count) hipLaunchKernelGGL(k_backsolve_pair, dim3(pwg), dim3(256), 0, s, M, npad, n, pj, Linv, w, z);
-        if (sj.count) hipLaunchKernelGGL(k_backsolve_step, dim3(swg), dim3(256), 0, s, M, npad, n, sj, Linv, w, z);
-      }
-    }
-  }
+  factor_root(c);
+  MSFM_TRY(back_substitute(c));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
-    if (ws) ws->dirty = true;
+    ws->dirty = true;
     return msfm_set_error(ctx, MSFM_E_DEVICE, "cholesky launch: %s", hipGetErrorString(e));
   }
-  if (paths) *paths = ran;
+  *paths = c.ran;
   return MSFM_OK;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/msfm.h"
+#include "chol_plan.h"
 
 #define MSFM_API extern "C" __attribute__((visibility("default")))
 
@@ -552,31 +553,16 @@ void descset_view(const msfm_descset* s, DescView* out);
 int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::vector<int>& feat_off, DevBuf<int>& d_feat_off, const uint8_t* d_hw,
                        const int* d_word, DevBuf<float>& d_kp, int64_t h2d_bytes, msfm_wordset** out);
 
-// Elimination structure of the reduced system (chol.hip): a nested-dissection tree of the camera graph laid out level
-// by level.  Level 0 holds the leaf domains, level 1 the deepest separators, ... ; the nodes of one level are mutually
-// uncoupled (their panel chains share launches), each is 64-aligned (identity padding inside) and couples only to its own
-// descendants and to later columns.  Columns from the last level's b0 on (root separator + intrinsics) form the final
-// dense chain.  n_levels = 0: plain dense order.  A node's descendants in a lower level are the nodes whose leaf interval
-// lies inside its own (tree order inside every level makes them contiguous).
-// corners: scratch for the deferred separator x separator updates, `nsplit` buffers of ldc x ldc doubles.
 // bits of the device-side failure word of a solve: 1 = reduced system not positive definite, 2 = a 3x3 point block, 4 = non-finite step;
 // MSFM_FAIL_SYNC = a bounded in-kernel wait ran out (the host turns it into MSFM_E_DEVICE)
 #define MSFM_FAIL_SYNC (1 << 20)
-#define MSFM_CORNER_MAX_BLOCKS 128   // 64-column blocks behind the leaf level that k_corner_syrk's range table holds
-struct msfm_chol_node { int begin, end, leaf_lo, leaf_hi; };
-struct msfm_chol_level { int K = 0; msfm_chol_node node[8]; int begin = 0, b0 = 0; };
-struct msfm_chol_plan {
-  int n_levels = 0;
-  msfm_chol_level level[3];
-  double* corners = nullptr;
-  int ldc = 0;
-};
+// msfm_chol_plan (chol_plan.h): the elimination structure of the reduced system
 struct msfm_chol_ws;   // hand-off state of the persistent panel chain (chol.hip): flags, hand-off buffers, ticket counters
 int msfm_chol_ws_create(msfm_ctx* ctx, int npad, msfm_chol_ws** out);
 void msfm_chol_ws_destroy(msfm_chol_ws* ws);
-// env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE); paths (optional): the
+// env: the problem's copy of the switches (MSFM_CHOL_LAUNCHES, MSFM_CHAIN_FORCE, MSFM_CHAIN_TRACE); paths: the
 // MSFM_PATH_* bits of msfm_ba_layout.solve_paths for the launches this call enqueued
-// riders (optional): work of the caller's that the call's launches take along (solve_riders.h).
+// riders: work of the caller's that the call's launches take along (solve_riders.h), either of them optional.
 //   modelsum  run by extra workgroups of the level-0 corner update, in front of that level's merge; the caller gives it only
 //             with a plan of at least one level, and a call that returns MSFM_OK has launched it.
 //   epilogue  run by k_backsolve_chain behind the publication of every block; `epilogue_ran` says whether the back
@@ -589,6 +575,5 @@ struct msfm_chol_riders {
   bool epilogue_ran = false;
 };
 int msfm_chol_factor_solve(msfm_ctx* ctx, const msfm_env& env, double* M, int npad, int n, double* work, double* w, double* z, int* fail,
-                           const msfm_chol_plan* plan, double* z_next = nullptr, msfm_chol_ws* ws = nullptr, int* paths = nullptr,
-                           msfm_chol_riders* riders = nullptr);
+                           const msfm_chol_plan* plan, double* z_next, msfm_chol_ws* ws, int* paths, msfm_chol_riders* riders);
 int msfm_chol_fill_pending(msfm_ctx* ctx, double* z, int npad);   // "not solved yet" marks of k_backsolve_chain

@@ -8,7 +8,7 @@
 #include <random>
 #include <vector>
 #define MSFM_POTRF_PROBE 1
-#include "../metricsfm_amd/csrc/chol_potrf16.h"
+#include "chol_potrf16.h"
 #ifndef POTRF
 #define POTRF potrf16_m
 #endif
