@@ -783,6 +783,82 @@ void msfm_word_result_destroy(msfm_word_result* res);
 int msfm_wordset_create_from_words(msfm_descset* set, const msfm_word_result* res, int max_hypotheses, msfm_wordset** out);
 
 /* ======================================================================================
+ *  Building the vocabulary tree: level-wide hierarchical k-means on a descriptor set
+ * ====================================================================================== */
+/* Database::BuildVocabularyTree (SfM/src/database.cc:655-677): fbow::VocabularyCreator::create over the descriptors of every
+ * image_step-th image, here on the float32 rows a descriptor set already holds.  The result is an ordinary msfm_voctree, made on
+ * the device in the layout the descent reads: no tree byte crosses PCIe, and msfm_voctree_size reports h2d_bytes = 0 for it.
+ * PARITY IS UNPINNED.  fbow's vocabulary_creator.cpp is not in the reference tree; its header names Params{k, L, nthreads,
+ * maxIters = 11}, getInitialClusterCenters, assignToClusters, recomputeCenters, a stop on an unchanged assignment hash and
+ * feat_idx leaves for nodes too small to split, and the reference seeds from the C library's generator on three racing
+ * threads, so a reference run does not reproduce itself.  What is restated is the published algorithm those names stand for -
+ * k-means++ seeding, Lloyd iterations, recursion to L levels - with the definitions below, which are this project's and are
+ * chosen so that the result does not depend on how the device schedules the work.  tests/voctrain_ref.py and
+ * tests/voctrain_ref.cpp restate them; the device reproduces them bit for bit.
+ *   sample      the images 0, image_step, 2 image_step, ... (database.cc:658-668) with all their features, whatever their count
+ *               (the 300-feature rule belongs to BuildWords); the features are numbered s = 0, 1, ... in that order.
+ *   distance    the descent's, exactly (above): eight unfused partial sums, ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)); a member goes
+ *               to the centre that wins with a strict < in centre order, so a tie stays with the lower cluster.  Sampled values
+ *               are finite with |value| < 2896, the bound under which the descent's best = 2^32 start can never matter:
+ *               training and descent agree on every distance.
+ *   scales      maxabs = the largest |value| of the sample (an integer maximum over the bit patterns), e = the smallest
+ *               integer with maxabs < 2^e taken from its exponent field (biased exponent - 126; -126 for zero and subnormals).
+ *               E = 9 + 2 e, so 512 maxabs^2 < 2^E and every distance is below 2^E; weight_shift = 40 - E.  sum_shift S =
+ *               39 - e, so maxabs 2^S < 2^39.  Both are per call, and are reported in the stats.
+ *   nodes       a node is a set of sampled features in ascending s; the root holds all.  Level l = 0 .. levels - 1 processes
+ *               every open node of the level together; the nodes of a level are numbered by their ordinal o = 0, 1, ...
+ *               A node of m <= k members becomes a block of m leaves, node i carrying member i's descriptor.  A larger node is
+ *               seeded and iterated; its non-empty clusters, in cluster order, become its block (emptied clusters are dropped,
+ *               so block_n may be below k).  A cluster is a leaf when l = levels - 1 or when it has one member; every other
+ *               cluster is an open node of level l + 1, in (node, cluster) order.  A node whose seeding ends with one centre
+ *               becomes a block of one leaf that carries that centre (the descriptor of the drawn member).
+ *   seeding     k-means++ with integer weights.  Centre 0 is member draw(0) mod m.  For centre j >= 1 every member has the
+ *               weight w = (uint64) trunc(d * 2^weight_shift), d its smallest distance to the centres chosen so far (in binary64:
+ *               scaling by a power of two and truncating are exact); W = the sum of w over the node.  W = 0 ends the seeding
+ *               with j centres; otherwise centre j is the first member, in ascending s, whose inclusive prefix sum of w exceeds
+ *               draw(j) mod W.  All sums are 64-bit integers, so any scan order gives the same draw.
+ *   draw        splitmix64 (z = (x += 0x9E3779B97F4A7C15), two xor-shift-multiplies, as everywhere in this library):
+ *               x = seed ^ 0x766F637472616E31; h = next(x); x = h ^ ((uint64) level << 40 | ordinal); h = next(x);
+ *               x = h ^ j; draw(j) = next(x).
+ *   iterations  one iteration assigns every member to its nearest centre and then recomputes the centres: a coordinate is
+ *               (float)(((double) sum of q(x) / (double) count) * 2^-S) with q(x) = (int64) trunc(x * 2^S), the sum a 64-bit
+ *               integer - exact for integer-valued descriptors, for others a truncation of the bits below 2^-S.  An emptied
+ *               cluster keeps its centre.  A node stops after the iteration whose assignment equals the previous one's (the first
+ *               never counts as equal), otherwise after max_iters iterations; either way its centres are the means of its final
+ *               assignment.
+ *   numbering   blocks breadth first: block 0 is the root's, the blocks of level l + 1 follow those of level l in (parent
+ *               block, node) order, so no link points to block 0, which the descent treats as a stop.  Word ids run from 0 over
+ *               the leaves in (block, node) order.  node_weight is 1.0f for a leaf and 0.0f for an inner node (fbow's weights are
+ *               in the unseen .cpp; nothing here reads them but the bag sums).
+ *   DEPARTURES  from what the creator's header implies: the stop compares the assignments themselves, not a hash of them; the
+ *               seeding weights are truncated to integers; a small node's leaves carry the members' descriptors (the header's
+ *               feat_idx leaves) and a node of one distinct descriptor becomes one leaf; one generator per (level, node, centre)
+ *               instead of one shared by the threads.
+ * msfm_descset_voctree_train: MSFM_E_INVAL, context and set stay usable: a NULL pointer, k outside [2, 64], levels outside
+ * [1, 32] (the descent's depth limit), max_iters < 1, image_step < 1, no sampled feature, more than 2^23 sampled features, a
+ * sampled value that is not finite or has |value| >= 2896 (values of images outside the sample are not looked at).
+ * The options are plain arguments - the reference's values are k = 10, levels = 6, max_iters = 11 (fbow's Params), image_step = 1,
+ * seed = 0 - and the statistics come from a getter, as the sizes of the other objects do: the header gains no struct.
+ * msfm_voctree_train_stats (every pointer may be NULL; MSFM_E_INVAL for a tree that was uploaded, not trained): the sample
+ * (n_images, n_features), the tree's size (n_blocks, n_leaves, depth = levels that hold a block), and per level l < depth, in
+ * arrays of 32 entries, the open nodes (= blocks of the level), how many of them were iterated (level_split), the largest
+ * iteration count of one of them and how many stopped at max_iters and not by an unchanged assignment (level_capped); the two
+ * shifts; host_waits = the times the host waited for the stream: one for the value scan, two per level for the sizes of this and
+ * of the next level, one per iteration for "is a node of this level still open" (asked at least once in a level that has a node
+ * of more than k members), one at the end.
+ * msfm_voctree_fetch (every pointer may be NULL) works on trained and uploaded trees alike and undoes the relay: block_n
+ * [n_blocks], node_desc [n_blocks][k][128], node_link / node_weight [n_blocks][k] as msfm_voctree_create takes them, and the two
+ * block fields featurefiles.write_voctree takes besides, derived from the links: block_leaf[b] = 1 where every node of block b
+ * is a leaf, block_parent[b] = the block that links b (0 for block 0 and for a block nothing links). */
+int msfm_descset_voctree_train(msfm_descset* set, int k /* 10 */, int levels /* 6 */, int max_iters /* 11 */, int image_step /* 1 */,
+                               uint64_t seed, msfm_voctree** out);
+int msfm_voctree_train_stats(const msfm_voctree* tree, int* n_images, int64_t* n_features, int* n_blocks, int64_t* n_leaves, int* depth,
+                             int* weight_shift, int* sum_shift, int* host_waits, int32_t* level_nodes /*[32]*/,
+                             int32_t* level_split /*[32]*/, int32_t* level_max_iters /*[32]*/, int32_t* level_capped /*[32]*/);
+int msfm_voctree_fetch(const msfm_voctree* tree, uint16_t* block_n, float* node_desc, uint32_t* node_link, float* node_weight,
+                       uint16_t* block_leaf, uint32_t* block_parent);
+
+/* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search
  * ====================================================================================== */
 /* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference

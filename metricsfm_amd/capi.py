@@ -781,6 +781,14 @@ class DescSet(_Handle):
         features, as a `WordResult`."""
         return WordResult(self, tree, min_features)
 
+    def train_voctree(self, k=10, levels=6, max_iters=11, image_step=1, seed=0):
+        """msfm_descset_voctree_train (Database::BuildVocabularyTree): hierarchical k-means over the descriptors of every
+        image_step-th image, on the device; the defaults are the reference's.  -> a `VocTree` whose `stats` holds the training's
+        statistics (msfm_voctree_train_stats) as a dict."""
+        h = C.c_void_p()
+        self.ctx.check(lib().msfm_descset_voctree_train(self._h, int(k), int(levels), int(max_iters), int(image_step), int(seed), C.byref(h)))
+        return VocTree._adopt(self.ctx, h)
+
 
 class MatchResult(_Handle):
     _destroy = "msfm_match_result_destroy"
@@ -1065,6 +1073,34 @@ class VocTree(_Handle):
         nw = A.as_c(np.asarray(node_weight, dtype=np.float32).reshape(nb, int(k)), np.float32)
         ctx.check(lib().msfm_voctree_create(ctx._h, int(k), nb, A.ptr(bn, C.POINTER(C.c_uint16)), A.ptr(nd, A.c_float_p),
                                             A.ptr(nl, C.POINTER(C.c_uint32)), A.ptr(nw, A.c_float_p), C.byref(self._h)))
+
+    stats = None   # msfm_voctree_train_stats of a trained tree (DescSet.train_voctree) as a dict; None for an uploaded one
+
+    @classmethod
+    def _adopt(cls, ctx, handle):
+        """A tree the library made on the device (msfm_descset_voctree_train)."""
+        vt = cls.__new__(cls)
+        vt.ctx, vt._h = ctx, handle
+        ni, nb, d, ws, ss, hw = (C.c_int32() for _ in range(6))
+        nf, nl = C.c_int64(), C.c_int64()
+        lv = {name: np.zeros(32, np.int32) for name in ("level_nodes", "level_split", "level_max_iters", "level_capped")}
+        ctx.check(lib().msfm_voctree_train_stats(handle, C.byref(ni), C.byref(nf), C.byref(nb), C.byref(nl), C.byref(d), C.byref(ws), C.byref(ss),
+                                                 C.byref(hw), *(A.ptr(v, A.c_int_p) for v in lv.values())))
+        vt.stats = dict(n_images=ni.value, n_features=nf.value, n_blocks=nb.value, n_leaves=nl.value, depth=d.value, weight_shift=ws.value,
+                        sum_shift=ss.value, host_waits=hw.value, **{name: v[:max(1, d.value)].tolist() for name, v in lv.items()})
+        return vt
+
+    def fetch(self):
+        """msfm_voctree_fetch: dict of k, block_n [nb], node_desc [nb][k][128], node_link / node_weight [nb][k], block_leaf,
+        block_parent [nb] - the keywords of featurefiles.write_voctree, and (without the last two) of Context.voctree."""
+        z = self.size()
+        nb, k = z["n_blocks"], z["k"]
+        bn, bl, bp = np.zeros(nb, np.uint16), np.zeros(nb, np.uint16), np.zeros(nb, np.uint32)
+        nd, nl, nw = np.zeros((nb, k, 128), np.float32), np.zeros((nb, k), np.uint32), np.zeros((nb, k), np.float32)
+        u16, u32 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)
+        self.ctx.check(lib().msfm_voctree_fetch(self._h, A.ptr(bn, u16), A.ptr(nd, A.c_float_p), A.ptr(nl, u32), A.ptr(nw, A.c_float_p),
+                                                A.ptr(bl, u16), A.ptr(bp, u32)))
+        return dict(k=k, block_n=bn, node_desc=nd, node_link=nl, node_weight=nw, block_leaf=bl, block_parent=bp)
 
     def size(self):
         """-> dict(k, n_blocks, depth, n_leaves, h2d_bytes)."""

@@ -547,6 +547,22 @@ struct DescView {   // what words.hip needs of a descriptor set (defined in knn.
   std::vector<const float*> kp;    // device [count][2] per image, nullptr: no keypoints
 };
 void descset_view(const msfm_descset* s, DescView* out);
+struct voctrain_stats {   // what msfm_voctree_train_stats reports (include/msfm.h)
+  int64_t n_features = 0, n_leaves = 0;
+  int n_images = 0, n_blocks = 0, depth = 0, weight_shift = 0, sum_shift = 0, host_waits = 0;
+  int level_nodes[32] = {}, level_split[32] = {}, level_max_iters[32] = {}, level_capped[32] = {};
+};
+struct msfm_voctree {   // words.hip uploads one, voctrain.hip trains one; both leave it in the layout k_descend reads
+  msfm_ctx* ctx = nullptr;
+  int k = 0, n_blocks = 0, depth = 0;
+  int64_t n_leaves = 0, h2d_bytes = 0;
+  bool trained = false;        // made by msfm_descset_voctree_train: `train` holds its statistics
+  voctrain_stats train;
+  DevBuf<uint16_t> d_n;        // [n_blocks]
+  DevBuf<float> d_desc;        // [n_blocks][k][8][16]
+  DevBuf<uint32_t> d_link;     // [n_blocks][k]
+  DevBuf<float> d_weight;      // [n_blocks][k]
+};
 // msfm_wordset_create is its checks + the upload of the four arrays + this core.  feat_off [n + 1] on the host and on the device;
 // d_feat_off and d_kp move into the set, d_hw [n] and d_word [feat_off[n]] are read only and may be freed on return (the core
 // waits for the stream before it returns, also when it fails).  h2d_bytes: what the caller sent, kept for msfm_wordset_size.

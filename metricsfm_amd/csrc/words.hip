@@ -21,16 +21,7 @@
 #include "pairsel_args.h"
 #include "runs_device.h"
 #include "words_args.h"
-
-struct msfm_voctree {
-  msfm_ctx* ctx = nullptr;
-  int k = 0, n_blocks = 0, depth = 0;
-  int64_t n_leaves = 0, h2d_bytes = 0;
-  DevBuf<uint16_t> d_n;        // [n_blocks]
-  DevBuf<float> d_desc;        // [n_blocks][k][8][16]
-  DevBuf<uint32_t> d_link;     // [n_blocks][k]
-  DevBuf<float> d_weight;      // [n_blocks][k]
-};
+#include "words_dist.h"
 
 struct msfm_word_result {
   msfm_ctx* ctx = nullptr;
@@ -60,19 +51,10 @@ __global__ __launch_bounds__(256) void k_relay(size_t n_floats, const float* __r
   out[o] = raw[node * WORDS_DIM + j + 8 * t];
 }
 
-// s + (a - b)^2 in three roundings
-__device__ static inline float sq_step(float s, float a, float b) {
-#pragma clang fp contract(off)
-  const float d = a - b;
-  const float q = d * d;
-  return s + q;
-}
-
-__device__ static inline float add8(float s) {   // the sum over a group of eight lanes: ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)), in all of them
-  s = s + __shfl_xor(s, 1, 8);
-  s = s + __shfl_xor(s, 2, 8);
-  s = s + __shfl_xor(s, 4, 8);
-  return s;
+__global__ __launch_bounds__(256) void k_unrelay(size_t n_floats, const float* __restrict__ relayed, float* __restrict__ out) {
+  const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (o >= n_floats) return;
+  out[o] = relayed[(o >> 7) * WORDS_DIM + relay_pos((int)(o & 127))];
 }
 
 // Eight lanes per feature e, 32 features per workgroup.  The loops run while any lane of the wave needs them, so the shuffles
@@ -112,14 +94,7 @@ __global__ __launch_bounds__(256) void k_descend(int total, int n, int k, const 
     for (int i = 0; i < k; i++) {
       if (!__any(i < N)) break;
       float s = 0.f;
-      if (i < N) {
-        const float4* p = reinterpret_cast<const float4*>(nb + (size_t)i * WORDS_DIM);
-        const float4 a = p[0], b = p[1], c = p[2], d = p[3];
-        s = sq_step(s, f[0], a.x); s = sq_step(s, f[1], a.y); s = sq_step(s, f[2], a.z); s = sq_step(s, f[3], a.w);
-        s = sq_step(s, f[4], b.x); s = sq_step(s, f[5], b.y); s = sq_step(s, f[6], b.z); s = sq_step(s, f[7], b.w);
-        s = sq_step(s, f[8], c.x); s = sq_step(s, f[9], c.y); s = sq_step(s, f[10], c.z); s = sq_step(s, f[11], c.w);
-        s = sq_step(s, f[12], d.x); s = sq_step(s, f[13], d.y); s = sq_step(s, f[14], d.z); s = sq_step(s, f[15], d.w);
-      }
+      if (i < N) s = part16(f, nb + (size_t)i * WORDS_DIM);
       s = add8(s);
       if (i < N && s < best) { best = s; best_i = i; }   // strict: a tie stays with the lower node, a NaN never wins
     }
@@ -214,6 +189,42 @@ MSFM_API int msfm_voctree_size(const msfm_voctree* T, int* k, int* n_blocks, int
   if (depth) *depth = T->depth;
   if (n_leaves) *n_leaves = T->n_leaves;
   if (h2d_bytes) *h2d_bytes = T->h2d_bytes;
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_voctree_fetch(const msfm_voctree* T, uint16_t* block_n, float* node_desc, uint32_t* node_link, float* node_weight,
+                                uint16_t* block_leaf, uint32_t* block_parent) {
+  using namespace words;
+  if (!T) return MSFM_E_INVAL;
+  msfm_ctx* ctx = T->ctx;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nb = (size_t)T->n_blocks, nodes = nb * T->k;
+  std::vector<uint16_t> n(nb);
+  std::vector<uint32_t> link(nodes);
+  DevBuf<float> d_raw;
+  DevScope sc(ctx);
+  if (node_desc) {
+    WD_TRY(d_raw.alloc(nodes * WORDS_DIM));
+    hipLaunchKernelGGL(k_unrelay, dim3(cdiv((long)(nodes * WORDS_DIM), 256)), dim3(256), 0, ctx->stream, nodes * WORDS_DIM, T->d_desc.p, d_raw.p);
+    WD_TRY(hipGetLastError());
+    WD_TRY(sc.down(node_desc, d_raw.p, nodes * WORDS_DIM));
+  }
+  WD_TRY(sc.down(n.data(), T->d_n.p, nb)); WD_TRY(sc.down(link.data(), T->d_link.p, nodes));
+  WD_TRY(sc.down(node_weight, T->d_weight.p, nodes));
+  WD_TRY(sc.finish());
+  if (block_n) std::copy(n.begin(), n.end(), block_n);
+  if (node_link) std::copy(link.begin(), link.end(), node_link);
+  for (size_t b = 0; b < nb; b++) {
+    if (block_leaf) block_leaf[b] = 1;
+    if (block_parent) block_parent[b] = 0;
+  }
+  for (size_t b = 0; b < nb; b++)
+    for (int i = 0; i < n[b]; i++) {
+      const uint32_t l = link[b * T->k + i];
+      if (l & WORDS_LEAF) continue;
+      if (block_leaf) block_leaf[b] = 0;
+      if (block_parent && l != 0 && l < nb) block_parent[l] = (uint32_t)b;
+    }
   return MSFM_OK;
 }
 

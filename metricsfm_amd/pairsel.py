@@ -3,6 +3,8 @@
 
 The sampler index of a hypothesis is its position in the msfm_pair_select call, so `rows_per_call` decides which samples a
 pair sees: two runs agree bit for bit only with the same chunking."""
+import os
+
 import numpy as np
 
 from . import capi, featurefiles, matchfiles
@@ -37,6 +39,18 @@ def select_pairs_from_descriptors(ctx: capi.Context, descset, tree, rows_per_cal
     pairs, record = _select_chunks(ws, rows_per_call, fold, opts)
     record.update(num_words=size["num_words"], n_unassigned=size["n_unassigned"])
     return pairs, record
+
+
+def build_vocabulary(descset, num_image_voc=500, k=10, levels=6, seed=0, fold=None, **options):
+    """Database::BuildVocabularyTree (SfM/src/database.cc:655-677) on a resident descriptor set: the tree is trained on every
+    image_step-th image, image_step = max(n_images // num_image_voc, 1), by DescSet.train_voctree.  -> the resident `VocTree`
+    (what select_pairs_from_descriptors takes).  With fold, `<fold>/voctree` is written in the reference's format; only then
+    does the tree leave the device.  options: further arguments of DescSet.train_voctree (max_iters)."""
+    step = max(len(descset.counts) // int(num_image_voc), 1)
+    tree = descset.train_voctree(k=k, levels=levels, seed=seed, image_step=step, **options)
+    if fold is not None:
+        featurefiles.write_voctree(os.path.join(fold, "voctree"), **tree.fetch())
+    return tree
 
 
 def _select_chunks(ws, rows_per_call, fold, opts):
