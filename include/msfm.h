@@ -1103,7 +1103,10 @@ int msfm_relpose_8pt_batch(msfm_ctx* ctx, int n_pairs, const int* offsets, const
  * a negative or NaN f, th_mse_reprojection or th_angle_small NaN, th_seedpair_structures < 0, ransac_times outside
  * [1, 65536].  The context stays usable.
  * msfm_seed_set_fetch (every pointer may be NULL): arm [n] (5 or 8), pose_ok [n], pass [n], n_matches [n], f [n][2],
- * R [n][9] row-major, t [n][3], c [n][3] of camera 1, pt_off [n+1], pt_match / X [..][3] / mse over pt_off[n] points. */
+ * R [n][9] row-major, t [n][3], c [n][3] of camera 1, pt_off [n+1], pt_match / X [..][3] / mse over pt_off[n] points.
+ * The set also keeps the winner's pt_match / X / mse on the device, with its place in the store, for
+ * msfm_recon_create_from_seed - of the winner only, in blocks sized by the longest hypothesis of the call.  It is a child of
+ * its context, like a store: destroy it before the context; msfm_seed_set_destroy waits for the context's stream. */
 typedef struct msfm_seed_options {      /* msfm_seed_default_options fills the reference's values */
   double th_mse_reprojection;           /* 3.0                  basic_structs.h:187 */
   double th_angle_small;                /* 3.0 / 180.0 * 3.1415 basic_structs.h:190, radians */
@@ -1414,6 +1417,47 @@ int msfm_recon_new_points(msfm_recon* recon, int new_cam, int n_visible, const i
  * points, while the host tables keep the cameras of before the call: such an object is to be destroyed. */
 int msfm_recon_adjust(msfm_recon* recon, int new_cam, int n_visible, const int32_t* visible, int do_partial, int do_full, int do_outliers,
                       const msfm_round_options* opt, msfm_round_set** out);
+/* msfm_recon_create_from_seed is the rest of FindSeedPairThenReconstruct (sfm_incremental.cc:290-374) for the winner of a
+ * msfm_seed_set, which keeps its winner's points on the device: the state of a model of two cameras, made where those points
+ * are.  The set must come from this store and is only read (it may be destroyed behind the call).
+ *   cameras  cam_img = (id_img1, id_img2); camera 0 is [I|0] with centre 0, camera 1 has the set's R, t, c;
+ *            cam_fk[c] = (the set's f of camera c, k1, k2 of cam_model[cam_model_of_cam[c]]).  The caller gives the solver's
+ *            blocks as msfm_recon_commit_camera's caller does: cam_pose [2][6] (angle-axis, t), n_models (1 or 2), cam_model
+ *            [n_models][3], cam_model_of_cam [2], model_mutable (optional).
+ *   points   p = 0 .. P-1 in the set's order: point_xyz = X, pt_mse = mse, pt_views 2, pt_bad 0, pt_mutable 1,
+ *            pt_new_added 1 (structure.cc:30-37)
+ *   rows     (p, 0, feat1) at 2p and (p, 1, feat2) at 2p + 1, feat1 / feat2 read from the store's matches through pt_match
+ *   feat_point  Camera::AddPoints is a std::map::insert: a feature that occurs in two accepted matches belongs to the first
+ *            point (the lower id; both points keep both rows).  The two rows start as -1, and every point inserts itself
+ *            with an integer minimum, so the result does not depend on the scheduling.
+ * The arguments are plain, as msfm_recon_commit_camera's are.  keypoints (optional) as in msfm_recon_init; without it the
+ * store must hold the keypoints of both images; reserve_points / reserve_obs: capacities to start with, where larger than P /
+ * 2P.  Nothing that
+ * scales with P or the store's matches is sent: h2d_bytes counts the keypoints of a host-made store, the upload
+ * msfm_recon_create makes too.  The host waits once.  MSFM_E_INVAL, with nothing kept and the context usable: a set without a
+ * winner, a set made on another store, n_models outside {1, 2}, a cam_model_of_cam outside n_models, no keypoints of either
+ * image. */
+int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* store, const msfm_seed_set* set, const double* cam_pose /*[2][6]*/,
+                                int n_models /*1 or 2*/, const double* cam_model /*[n_models][3]*/, const int32_t* cam_model_of_cam /*[2]*/,
+                                const uint8_t* model_mutable /*optional*/, const float* keypoints /*optional*/, int reserve_points,
+                                int reserve_obs, msfm_recon** out);
+/* msfm_recon_normalize is the point side of BundleAdjuster::Normalize and Perturb (optimizer.cc:155-232) on the resident
+ * points of any msfm_recon.  The arithmetic is this, in binary64 with + - * / and fabs only and no fused multiply-add, so a
+ * sequential loop agrees bit for bit:
+ *   mid[k] = (0.0 + x_0k + x_1k + ...) / n         left to right over all n points, bad ones included
+ *   mad    = (0.0 + d_0 + d_1 + ...) / n           left to right, d_i = (|x_i0 - mid0| + |x_i1 - mid1|) + |x_i2 - mid2|
+ *   scale  = target_deviation / mad
+ *   x_ik   = scale * (x_ik - mid[k])               then, with noise, x_ik = x_ik + noise_ik * point_sigma (multiply, then add)
+ * noise [n_points][3] (NULL: none) is the only upload that scales with the state and is counted in h2d_bytes; the reference
+ * draws it from std::rand, which no restatement reproduces, so it is an input.  The reference's values: target_deviation 100.0 (optimizer.cc:182), point_sigma 0.5 (:201).
+ * The host waits once, for mid and scale, which it returns; the points are written behind that wait.  n_points == 0 is
+ * MSFM_E_INVAL, a scale that is not finite (all points equal) MSFM_E_NUMERIC; the state is untouched in both cases.
+ * The camera side - SetACPose(a, scale (c - mid)), then SetACPose(a + n_r, c) and SetRTPose(R, t + n_t) per camera
+ * (optimizer.cc:190-231) - needs the C library's trigonometry and stays with the caller, who writes the result with
+ * msfm_recon_set_cameras: cam_pose [n_cams][6], cam_R [n_cams][9], cam_t, cam_c [n_cams][3] replace the object's host
+ * tables (a NULL pointer keeps that table). */
+int msfm_recon_normalize(msfm_recon* recon, const double* noise, double target_deviation, double point_sigma, double mid[3], double* scale);
+int msfm_recon_set_cameras(msfm_recon* recon, const double* cam_pose, const double* cam_R, const double* cam_t, const double* cam_c);
 /* msfm_recon_destroy waits for the context's stream before the blocks go back to the pool. */
 void msfm_recon_destroy(msfm_recon* recon);
 

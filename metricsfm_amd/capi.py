@@ -437,11 +437,12 @@ class Context(_Handle):
                                keypoints=keypoints) as st:
             return st.fetch()
 
-    def seed_hypotheses(self, store, hyp_img, cam_fk, same_model, keypoints=None, **opts):
+    def seed_hypotheses(self, store, hyp_img, cam_fk, same_model, keypoints=None, keep=False, **opts):
         """msfm_seed_hypotheses (sfm_incremental.cc:235-390): pose, two-view points and the two gates of every seed-pair
         hypothesis, on the resident store.  hyp_img [n][2], cam_fk [n][2][3] (f with 0 = unknown, k1, k2), same_model [n];
         opts: fields of msfm_seed_options.  Returns a dict: arm, pose_ok, pass, n_matches, f [n][2], R [n][3][3], t, c [n][3],
-        pt_off [n+1], pt_match, X [..][3], mse, winner (-1: none), h2d_bytes."""
+        pt_off [n+1], pt_match, X [..][3], mse, winner (-1: none), h2d_bytes.  keep=True: the dict also holds the live `SeedSet`
+        under "set", whose winner's points stay on the device for `Recon.from_seed`; close it before the context."""
         hyp = A.as_c(np.asarray(hyp_img, dtype=np.int32).reshape(-1, 2), np.int32)
         n = len(hyp)
         fk = A.as_c(np.asarray(cam_fk, dtype=np.float64).reshape(-1, 2, 3), np.float64)
@@ -455,7 +456,8 @@ class Context(_Handle):
         o = seed_options(**opts)
         h = C.c_void_p()
         self.check(lib().msfm_seed_hypotheses(self._h, store._h, C.byref(P), C.byref(o), C.byref(h)))
-        with _Handle(h, "msfm_seed_set_destroy"):
+        st = SeedSet(self, store, h)
+        try:
             nh, npt, win, nb = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
             lib().msfm_seed_set_size(h, C.byref(nh), C.byref(npt), C.byref(win), C.byref(nb))
             npt, m = npt.value, max(1, n)
@@ -467,8 +469,14 @@ class Context(_Handle):
             lib().msfm_seed_set_fetch(h, A.ptr(arm, A.c_u8_p), A.ptr(pok, A.c_u8_p), A.ptr(pas, A.c_u8_p), A.ptr(nm, A.c_int_p), A.ptr(f, dp),
                                       A.ptr(R, dp), A.ptr(t, dp), A.ptr(c, dp), A.ptr(poff, A.c_int_p), A.ptr(ptm, A.c_int_p), A.ptr(X, dp),
                                       A.ptr(mse, dp))
-        return {"arm": arm[:n], "pose_ok": pok[:n], "pass": pas[:n], "n_matches": nm[:n], "f": f[:n], "R": R[:n], "t": t[:n], "c": c[:n],
-                "pt_off": poff, "pt_match": ptm[:npt], "X": X[:npt], "mse": mse[:npt], "winner": win.value, "h2d_bytes": nb.value}
+        finally:
+            if not keep:
+                st.close()
+        out = {"arm": arm[:n], "pose_ok": pok[:n], "pass": pas[:n], "n_matches": nm[:n], "f": f[:n], "R": R[:n], "t": t[:n], "c": c[:n],
+               "pt_off": poff, "pt_match": ptm[:npt], "X": X[:npt], "mse": mse[:npt], "winner": win.value, "h2d_bytes": nb.value}
+        if keep:
+            out["set"] = st
+        return out
 
     def new_points(self, store, cam_img, feat_point, n_points, cam_R, cam_t, cam_c, cam_fk, new_cam, vis_off, vis_cam, keypoints=None, **opts):
         """msfm_new_points (sfm_incremental.cc:755-915): the new two-view points of every new camera against its visible cameras,
@@ -1145,6 +1153,14 @@ class WordResult(_Handle):
         return Wordset._adopt(self.ctx, h)
 
 
+class SeedSet(_Handle):
+    """msfm_seed_set kept alive behind `Context.seed_hypotheses(keep=True)`: the winner's points stay on the device."""
+    _destroy = "msfm_seed_set_destroy"
+
+    def __init__(self, ctx: Context, store, h):
+        self.ctx, self.store, self._h = ctx, store, h
+
+
 class Recon(_Handle):
     """msfm_recon: a model's flat state resident on the device across its rounds (include/msfm.h)."""
     _destroy = "msfm_recon_destroy"
@@ -1184,6 +1200,49 @@ class Recon(_Handle):
                         A.ptr(g("cam_fk"), dp), A.ptr(g("point_xyz"), dp), A.ptr(g("pt_bad"), up), A.ptr(g("pt_mse"), dp), A.ptr(g("pt_views"), ip),
                         A.ptr(g("pt_mutable"), up), A.ptr(g("pt_new_added"), up), int(reserve_points), int(reserve_obs))
         ctx.check(lib().msfm_recon_create(ctx._h, store._h, C.byref(P), C.byref(self._h)))
+
+    @classmethod
+    def from_seed(cls, ctx: Context, store, seed_set, cam_pose, cam_model, cam_model_of_cam, keypoints=None, model_mutable=None, reserve_points=0,
+                  reserve_obs=0):
+        """msfm_recon_create_from_seed: the two-camera model of `seed_set`'s winner (a `SeedSet` of `seed_hypotheses(keep=True)` on
+        this store), made on the device from the points the set keeps there.  cam_pose [2][6], cam_model [n_models][3] (one or two
+        models) and cam_model_of_cam [2] are the solver's blocks, as `seed.find_seed_pair` returns them."""
+        pose = A.as_c(np.asarray(cam_pose, dtype=np.float64).reshape(2, 6), np.float64)
+        model = A.as_c(np.asarray(cam_model, dtype=np.float64).reshape(-1, 3), np.float64)
+        moc = A.as_c(np.asarray(cam_model_of_cam, dtype=np.int32).reshape(2), np.int32)
+        mm = None if model_mutable is None else A.as_c(np.asarray(model_mutable, dtype=np.uint8).reshape(-1), np.uint8)
+        if mm is not None and len(mm) != len(model):
+            raise ValueError("model_mutable must hold one entry per model")
+        kp = None if keypoints is None else A.as_c(np.asarray(keypoints, dtype=np.float32).reshape(-1, 2), np.float32)
+        if kp is not None and len(kp) != int(store.n_features.sum()):
+            raise ValueError("keypoints must hold one row per feature of every image")
+        q = cls.__new__(cls)
+        q.ctx, q.store, q._h, q._n_visible = ctx, store, C.c_void_p(), 0
+        ctx.check(lib().msfm_recon_create_from_seed(ctx._h, store._h, seed_set._h, A.ptr(pose, A.c_double_p), len(model), A.ptr(model, A.c_double_p),
+                                                    A.ptr(moc, A.c_int_p), A.ptr(mm, A.c_u8_p), A.ptr(kp, A.c_float_p), int(reserve_points),
+                                                    int(reserve_obs), C.byref(q._h)))
+        return q
+
+    def normalize(self, noise=None, target_deviation=100.0, point_sigma=0.5):
+        """msfm_recon_normalize: the point side of BundleAdjuster::Normalize and Perturb on the resident points.  noise [n_points][3]
+        standard normal draws (None: no perturbation); the defaults are the reference's values.  Returns (mid [3], scale)."""
+        nz = None
+        if noise is not None:
+            nz = A.as_c(np.asarray(noise, dtype=np.float64).reshape(-1, 3), np.float64)
+            if len(nz) != self.size()["n_points"]:
+                raise ValueError("noise must hold one row per point")
+        mid, scale = np.zeros(3), C.c_double()
+        self.ctx.check(lib().msfm_recon_normalize(self._h, A.ptr(nz, A.c_double_p), float(target_deviation), float(point_sigma),
+                                                  A.ptr(mid, A.c_double_p), C.byref(scale)))
+        return mid, scale.value
+
+    def set_cameras(self, cam_pose=None, cam_R=None, cam_t=None, cam_c=None):
+        """msfm_recon_set_cameras: replaces the object's host camera tables (None keeps one): cam_pose [n_cams][6], cam_R
+        [n_cams][3][3], cam_t, cam_c [n_cams][3]."""
+        nc = self.size()["n_cams"]
+        a = [None if v is None else A.as_c(np.asarray(v, dtype=np.float64).reshape(nc, w), np.float64)
+             for v, w in ((cam_pose, 6), (cam_R, 9), (cam_t, 3), (cam_c, 3))]
+        self.ctx.check(lib().msfm_recon_set_cameras(self._h, *[A.ptr(v, A.c_double_p) for v in a]))
 
     def size(self):
         """msfm_recon_size: n_cams, n_models, n_points, n_obs, cap_points, cap_obs and h2d_bytes (sent since creation, creation included)."""

@@ -315,6 +315,26 @@ struct msfm_match_store {
   DevBuf<float> d_kp;             // [feat_off[n_images]][2]
 };
 
+// What msfm_seed_hypotheses leaves behind (seed.hip creates and destroys it; recon.hip starts a model from its winner).  The
+// answer of every hypothesis is host memory; the winner's accepted points stay on the device as well, in blocks sized by the
+// longest hypothesis of the call (the winner is not known on the host when they are made), with its place in the store.
+// A child of its context: msfm_seed_set_destroy waits for the stream before the blocks go back to the pool.
+struct msfm_seed_set {
+  msfm_ctx* ctx = nullptr;
+  const msfm_match_store* store = nullptr;
+  int n = 0, winner = -1;
+  std::vector<uint8_t> arm, pose_ok, pass;
+  std::vector<int> n_matches, pt_off, pt_match;
+  std::vector<double> f, R, t, c, X, mse;
+  int64_t h2d_bytes = 0;
+  // the winner (winner >= 0 only)
+  int win_img[2] = {-1, -1};      // id_img1, id_img2
+  int win_m0 = 0;                 // its first match in the store
+  int win_kp[2] = {0, 0};         // the first keypoint row of either image in an array of every image's rows (feat_off)
+  DevBuf<int> d_ptm;              // [n_points of the winner] pt_match
+  DevBuf<double> d_X, d_mse;      // [..][3], [..]
+};
+
 // What msfm_localize_candidates leaves behind (localize.hip creates and destroys it; localize_pose.hip reads it).  A set made
 // with point_xyz keeps the device arrays its gather kernel wrote - corr_point, pts_w, pts_2d in the layout of corr_off - until
 // msfm_localize_set_destroy, so msfm_localize_poses moves no correspondence over PCIe.

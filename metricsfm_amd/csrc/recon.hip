@@ -2,6 +2,8 @@
 // Point3D::cams_ / pts2d_, the point arrays and flags, the keypoints of a host-made store) uploaded once, at msfm_recon_create,
 // read by msfm_recon_localize (the cores of the two localize calls; the winner's row stays pending on the device), given a
 // camera by msfm_recon_commit_camera (k_commit_flags, a scan, k_commit),
+// made from a seed set's winner by msfm_recon_create_from_seed (k_seed_state on the points the set keeps on the device), normalised
+// by msfm_recon_normalize (k_normalize_sums: the ordered sums of BundleAdjuster::Normalize; k_normalize_write),
 // extended by msfm_recon_new_points - the kernels of msfm_new_points (newpoints.hip: newpoints_dev) on the resident feat_point and
 // keypoints, then k_append_points - and adjusted in place by msfm_recon_adjust - the core of msfm_round_adjust (adjust.hip:
 // round_adjust_dev) on these buffers.
@@ -17,6 +19,7 @@
 // the object may then index by it.  The kernels here compare and copy; the unit keeps the no-contraction discipline of
 // adjust.hip all the same.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 
@@ -38,6 +41,7 @@ struct msfm_recon {
   DevBuf<double> d_xyz, d_mse;
   DevBuf<uint8_t> d_bad, d_mut, d_added;
   DevBuf<float> d_kp;                   // empty: the store's
+  DevBuf<double> d_noise;               // the last msfm_recon_normalize's noise: its write kernel is not waited for
   bool own_kp = false;
   int64_t h2d_bytes = 0;
   bool poisoned = false;                // a solve failed behind a stage that had written: the state is mixed
@@ -120,6 +124,81 @@ __global__ __launch_bounds__(256) void k_commit(int n, int new_cam, int fp_off, 
     const size_t r = (size_t)n_obs + pos[i];
     obs_point[r] = p; obs_cam[r] = new_cam; obs_feat[r] = f;
   }
+}
+
+// sfm_incremental.cc:344-374 for the P accepted points of a seed set's winner, in the set's order: point p is the set's X / mse
+// with two views, not bad, mutable, new (structure.cc:30-37); its rows (p, 0, feat1), (p, 1, feat2) go to 2p, 2p + 1, the
+// features read from the store's matches through pt_match.  Camera::AddPoints is a std::map::insert - the first point of a
+// feature keeps it: fp (nf1 + nf2 entries of -1 on entry) takes the unsigned minimum of the ids, which is the lowest id whatever
+// the scheduling (-1 is the largest unsigned value).  The store's matches name features inside their images (checked when
+// the store was made).
+__global__ __launch_bounds__(256) void k_seed_state(int P, int m0, int nf1, const int* __restrict__ pt_match, const int* __restrict__ matches,
+                                                     const double* __restrict__ X, const double* __restrict__ mse, int* __restrict__ fp,
+                                                     int* __restrict__ obs_point, int* __restrict__ obs_cam, int* __restrict__ obs_feat,
+                                                     double* __restrict__ point_xyz, double* __restrict__ pt_mse, int* __restrict__ pt_views,
+                                                     uint8_t* __restrict__ pt_bad, uint8_t* __restrict__ pt_mutable, uint8_t* __restrict__ pt_new_added) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  const size_t i = (size_t)p, m = (size_t)m0 + pt_match[p];
+  const int f1 = matches[2 * m], f2 = matches[2 * m + 1];
+  point_xyz[3 * i] = X[3 * i]; point_xyz[3 * i + 1] = X[3 * i + 1]; point_xyz[3 * i + 2] = X[3 * i + 2];
+  pt_mse[i] = mse[i];
+  pt_views[i] = 2; pt_bad[i] = 0; pt_mutable[i] = 1; pt_new_added[i] = 1;
+  obs_point[2 * i] = p; obs_cam[2 * i] = 0; obs_feat[2 * i] = f1;
+  obs_point[2 * i + 1] = p; obs_cam[2 * i + 1] = 1; obs_feat[2 * i + 1] = f2;
+  atomicMin((unsigned*)fp + f1, (unsigned)p);
+  atomicMin((unsigned*)fp + (size_t)nf1 + f2, (unsigned)p);
+}
+
+// BundleAdjuster::Normalize's two sums (optimizer.cc:160-179), in the order of its loops: the definition is the left-to-right
+// sum, so one wave does it.  Chunks of NORM_CHUNK points are staged through LDS by all 64 lanes (coalesced); lanes 0-2 carry
+// the three chains of mid, then every lane forms the deviations d_i of its points and lane 0 carries the chain of mad.
+// out [5]: mid (3), mad, scale = target / mad.
+#define NORM_CHUNK 1024
+__global__ __launch_bounds__(64) void k_normalize_sums(int n, const double* __restrict__ x, double target, double* __restrict__ out) {
+  __shared__ double s_x[3 * NORM_CHUNK];
+  __shared__ double s_mid[3];
+  const int lane = threadIdx.x;
+  double acc = 0.0;
+  for (int c0 = 0; c0 < n; c0 += NORM_CHUNK) {
+    const int cnt = min(NORM_CHUNK, n - c0);
+    for (int k = lane; k < 3 * cnt; k += 64) s_x[k] = x[3 * (size_t)c0 + k];
+    __syncthreads();
+    if (lane < 3)
+      for (int j = 0; j < cnt; j++) acc += s_x[3 * j + lane];
+    __syncthreads();
+  }
+  if (lane < 3) s_mid[lane] = acc / n;
+  __syncthreads();
+  const double m0 = s_mid[0], m1 = s_mid[1], m2 = s_mid[2];
+  double mad = 0.0;
+  for (int c0 = 0; c0 < n; c0 += NORM_CHUNK) {
+    const int cnt = min(NORM_CHUNK, n - c0);
+    for (int j = lane; j < cnt; j += 64) {
+      const double* q = x + 3 * ((size_t)c0 + j);
+      s_x[j] = (fabs(q[0] - m0) + fabs(q[1] - m1)) + fabs(q[2] - m2);
+    }
+    __syncthreads();
+    if (lane == 0)
+      for (int j = 0; j < cnt; j++) mad += s_x[j];
+    __syncthreads();
+  }
+  if (lane == 0) {
+    mad = mad / n;
+    out[0] = m0; out[1] = m1; out[2] = m2; out[3] = mad; out[4] = target / mad;
+  }
+}
+
+// x = scale * (x - mid), then x = x + noise * sigma (optimizer.cc:183-188, :204-209); one thread per coordinate
+__global__ __launch_bounds__(256) void k_normalize_write(long n3, double m0, double m1, double m2, double scale, const double* __restrict__ noise,
+                                                          double sigma, double* __restrict__ x) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n3) return;
+  const int k = (int)(i % 3);
+  const double mid = k == 0 ? m0 : (k == 1 ? m1 : m2);
+  double v = scale * (x[i] - mid);
+  if (noise) v = v + noise[i] * sigma;
+  x[i] = v;
 }
 
 static RoundArgs args_of(const msfm_recon* Q) {
@@ -212,6 +291,124 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   Q->h2d_bytes = sc.h2d;
   ctx->children++;   // a child of its context, like a store
   *out = Q.release();
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* S, const msfm_seed_set* W, const double* cam_pose, int nm,
+                                         const double* cam_model, const int32_t* cam_model_of_cam, const uint8_t* model_mutable,
+                                         const float* keypoints, int reserve_points, int reserve_obs, msfm_recon** out) {
+  using namespace rec;
+  const char* who = "msfm_recon_create_from_seed";
+  if (!ctx) return MSFM_E_INVAL;
+  if (!S || !W || !out) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
+  *out = nullptr;
+  if (S->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the store belongs to another context", who);
+  if (W->store != S || W->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the seed set was made on another store", who);
+  if (W->winner < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the seed set has no winner", who);
+  if (nm != 1 && nm != 2) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: n_models = %d outside {1, 2}", who, nm);
+  if (!cam_pose || !cam_model || !cam_model_of_cam) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null array", who);
+  if (reserve_points < 0 || reserve_obs < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: negative count", who);
+  for (int c = 0; c < 2; c++) {
+    if (cam_model_of_cam[c] < 0 || cam_model_of_cam[c] >= nm)
+      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: cam_model_of_cam[%d] = %d outside n_models = %d", who, c, cam_model_of_cam[c], nm);
+    if (!keypoints && !S->has_kp[W->win_img[c]])
+      return msfm_set_error(ctx, MSFM_E_INVAL, "%s: no keypoints of image %d (argument or chain)", who, W->win_img[c]);
+  }
+  const int w = W->winner, i1 = W->win_img[0], i2 = W->win_img[1];
+  const int np = W->pt_off[w + 1] - W->pt_off[w], no = 2 * np;
+  const int nf1 = S->n_features[i1], nf2 = S->n_features[i2];
+  std::unique_ptr<msfm_recon> Q(new msfm_recon());
+  Q->ctx = ctx; Q->store = S;
+  Q->n_cams = 2; Q->n_models = nm; Q->n_points = np; Q->n_obs = no;
+  Q->cap_points = std::max<size_t>(1, std::max((size_t)np, (size_t)reserve_points));
+  Q->cap_obs = std::max<size_t>(1, std::max((size_t)no, (size_t)reserve_obs));
+  const size_t total = (size_t)S->feat_off[S->n_images];
+  // the host tables: camera 0 is [I|0] (:290), camera 1 the set's pose; fk = (the set's f, the model's k1, k2)
+  Q->cam_img = {i1, i2};
+  Q->cam_model_of_cam.assign(cam_model_of_cam, cam_model_of_cam + 2);
+  if (model_mutable) Q->model_mutable.assign(model_mutable, model_mutable + (size_t)nm);
+  Q->cam_pose.assign(cam_pose, cam_pose + 12); Q->cam_model.assign(cam_model, cam_model + 3 * (size_t)nm);
+  Q->cam_R = {1, 0, 0, 0, 1, 0, 0, 0, 1}; Q->cam_t.assign(3, 0.0); Q->cam_c.assign(3, 0.0);
+  Q->cam_R.insert(Q->cam_R.end(), W->R.begin() + 9 * (size_t)w, W->R.begin() + 9 * (size_t)w + 9);
+  Q->cam_t.insert(Q->cam_t.end(), W->t.begin() + 3 * (size_t)w, W->t.begin() + 3 * (size_t)w + 3);
+  Q->cam_c.insert(Q->cam_c.end(), W->c.begin() + 3 * (size_t)w, W->c.begin() + 3 * (size_t)w + 3);
+  for (int c = 0; c < 2; c++) {
+    const double* M = cam_model + 3 * (size_t)cam_model_of_cam[c];
+    Q->cam_fk.push_back(W->f[2 * (size_t)w + c]); Q->cam_fk.push_back(M[1]); Q->cam_fk.push_back(M[2]);
+  }
+  RC_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevScope sc(ctx);   // (Q's blocks too: an error return deletes the object)
+  RC_TRY(Q->d_fp.alloc(std::max<size_t>(1, total)));
+  RC_TRY(Q->d_op.alloc(Q->cap_obs)); RC_TRY(Q->d_oc.alloc(Q->cap_obs)); RC_TRY(Q->d_of.alloc(Q->cap_obs));
+  RC_TRY(Q->d_xyz.alloc(3 * Q->cap_points)); RC_TRY(Q->d_mse.alloc(Q->cap_points)); RC_TRY(Q->d_views.alloc(Q->cap_points));
+  RC_TRY(Q->d_bad.alloc(Q->cap_points)); RC_TRY(Q->d_mut.alloc(Q->cap_points)); RC_TRY(Q->d_added.alloc(Q->cap_points));
+  if (keypoints) {   // every image's rows, as msfm_recon_create keeps them
+    RC_TRY(sc.up(Q->d_kp, keypoints, 2 * total, 2 * total));
+    Q->own_kp = true;
+  }
+  if (nf1 + nf2) RC_TRY(hipMemsetD32Async((hipDeviceptr_t)Q->d_fp.p, -1, (size_t)nf1 + (size_t)nf2, s));   // Camera::pts_ of two new cameras
+  if (np) {
+    KTimer tm(ctx, "recon_from_seed");
+    hipLaunchKernelGGL(k_seed_state, dim3(cdiv(np, 256)), dim3(256), 0, s, np, W->win_m0, nf1, W->d_ptm.p, S->d_match.p, W->d_X.p, W->d_mse.p, Q->d_fp.p,
+                       Q->d_op.p, Q->d_oc.p, Q->d_of.p, Q->d_xyz.p, Q->d_mse.p, Q->d_views.p, Q->d_bad.p, Q->d_mut.p, Q->d_added.p);
+  }
+  RC_TRY(hipGetLastError());
+  RC_TRY(sc.finish());   // the one wait: the set may be destroyed behind the call
+  Q->h2d_bytes = sc.h2d;
+  ctx->children++;
+  *out = Q.release();
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_recon_normalize(msfm_recon* Q, const double* noise, double target_deviation, double point_sigma, double mid[3], double* scale) {
+  using namespace rec;
+  const char* who = "msfm_recon_normalize";
+  if (!Q) return MSFM_E_INVAL;
+  msfm_ctx* ctx = Q->ctx;
+  if (Q->poisoned) return rec::poisoned_error(ctx, who);
+  if (target_deviation != target_deviation || point_sigma != point_sigma)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "%s: an option is NaN", who);
+  const int n = Q->n_points;
+  if (n == 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the state has no point", who);
+  RC_TRY(hipSetDevice(ctx->device));
+  hipStream_t s = ctx->stream;
+  DevBuf<double> d_out, d_noise;
+  DevScope sc(ctx);
+  RC_TRY(d_out.alloc(5));
+  if (noise) RC_TRY(sc.up(d_noise, noise, 3 * (size_t)n));
+  {
+    KTimer tm(ctx, "recon_normalize_sums");
+    hipLaunchKernelGGL(k_normalize_sums, dim3(1), dim3(64), 0, s, n, Q->d_xyz.p, target_deviation, d_out.p);
+  }
+  RC_TRY(hipGetLastError());
+  double h[5] = {0, 0, 0, 0, 0};
+  RC_TRY(sc.down(h, (const double*)d_out.p, 5));
+  RC_TRY(sc.finish());   // the one wait
+  if (!std::isfinite(h[4]) || !std::isfinite(h[0]) || !std::isfinite(h[1]) || !std::isfinite(h[2]))
+    return msfm_set_error(ctx, MSFM_E_NUMERIC, "%s: scale = %g / %g is not finite", who, target_deviation, h[3]);
+  {
+    KTimer tm(ctx, "recon_normalize_write");
+    hipLaunchKernelGGL(k_normalize_write, dim3(cdiv(3 * (long)n, 256)), dim3(256), 0, s, 3 * (long)n, h[0], h[1], h[2], h[4], noise ? d_noise.p : nullptr,
+                       point_sigma, Q->d_xyz.p);
+  }
+  RC_TRY(hipGetLastError());
+  // the write kernel reads the noise behind this return: the object keeps the block; the one it held has been waited for above
+  Q->d_noise.swap(d_noise);
+  Q->h2d_bytes += sc.h2d;
+  if (mid) { mid[0] = h[0]; mid[1] = h[1]; mid[2] = h[2]; }
+  if (scale) *scale = h[4];
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_recon_set_cameras(msfm_recon* Q, const double* cam_pose, const double* cam_R, const double* cam_t, const double* cam_c) {
+  if (!Q) return MSFM_E_INVAL;
+  if (Q->poisoned) return rec::poisoned_error(Q->ctx, "msfm_recon_set_cameras");
+  const size_t nc = (size_t)Q->n_cams;
+  if (cam_pose) Q->cam_pose.assign(cam_pose, cam_pose + 6 * nc);
+  if (cam_R) Q->cam_R.assign(cam_R, cam_R + 9 * nc);
+  if (cam_t) Q->cam_t.assign(cam_t, cam_t + 3 * nc);
+  if (cam_c) Q->cam_c.assign(cam_c, cam_c + 3 * nc);
   return MSFM_OK;
 }
 

@@ -13,7 +13,9 @@
 //               SufficientTriangulationAngle :325-355): tri_two_views of point3d_device.h.  A workgroup lies inside one
 //               hypothesis (block map by binary search in n_hyp + 1 block offsets); its camera data is loaded once into LDS.
 //   k_compact   one workgroup per hypothesis walks its flags in chunks of 256 (wave ballot + the four wave counts): accepted
-//               points in match order, the count and the two gates (:380-381)
+//               points in match order, the count and the two gates (:380-381); a hypothesis that passes enters the minimum
+//               that names the winner
+//   k_keep      the winner's points into blocks of their own, which the set keeps (msfm_recon_create_from_seed reads them)
 // No host synchronisation between the stages: every size follows from the store's host-side match_off; one synchronisation
 // at the end.  This file is compiled without fused multiply-adds and uses + - * / sqrt only (pose.hip's discipline), so
 // tests/seed_ref.cpp built with -ffp-contract=off agrees bit for bit; tri.hip is contracted and agrees to 1e-9.
@@ -25,14 +27,6 @@
 
 #pragma clang fp contract(off)
 #include "point3d_device.h"   // View, tri_two_views
-
-struct msfm_seed_set {
-  int n = 0, winner = -1;
-  std::vector<uint8_t> arm, pose_ok, pass;
-  std::vector<int> n_matches, pt_off, pt_match;
-  std::vector<double> f, R, t, c, X, mse;
-  int64_t h2d_bytes = 0;
-};
 
 namespace seed {
 
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(256) void k_tri(int n, const int* __restrict__ blk_
 __global__ __launch_bounds__(256) void k_compact(const int* __restrict__ off_all, const uint8_t* __restrict__ flag, const double* __restrict__ Xall,
                                                   const double* __restrict__ mse_all, const uint8_t* __restrict__ pose_ok, int th_structures,
                                                   int* __restrict__ pt_match, double* __restrict__ Xout, double* __restrict__ mse_out,
-                                                  int* __restrict__ count, uint8_t* __restrict__ pass) {
+                                                  int* __restrict__ count, uint8_t* __restrict__ pass, int* __restrict__ winner) {
   __shared__ int part[4];
   const int h = blockIdx.x;
   const int b = off_all[h], N = off_all[h + 1] - b;
@@ -150,8 +144,25 @@ __global__ __launch_bounds__(256) void k_compact(const int* __restrict__ off_all
   }
   if (threadIdx.x == 0) {
     count[h] = base;
-    pass[h] = (pose_ok[h] && base >= th_structures && base >= N / 5) ? 1 : 0;   // :380-381
+    const bool ok = pose_ok[h] && base >= th_structures && base >= N / 5;   // :380-381
+    pass[h] = ok ? 1 : 0;
+    if (ok) atomicMin(winner, h);
   }
+}
+
+// The winner's segment of k_compact's outputs, copied to the front of blocks of `cap` points (cap >= the matches of any
+// hypothesis); *winner is INT_MAX when no hypothesis passed.
+__global__ __launch_bounds__(256) void k_keep(int cap, const int* __restrict__ winner, const int* __restrict__ off_all, const int* __restrict__ count,
+                                               const int* __restrict__ pt_match, const double* __restrict__ X, const double* __restrict__ mse,
+                                               int* __restrict__ w_match, double* __restrict__ w_X, double* __restrict__ w_mse) {
+  const int w = *winner;
+  if (w == INT_MAX) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= count[w] || j >= cap) return;
+  const size_t s = (size_t)off_all[w] + j;
+  w_match[j] = pt_match[s];
+  w_X[3 * (size_t)j] = X[3 * s]; w_X[3 * (size_t)j + 1] = X[3 * s + 1]; w_X[3 * (size_t)j + 2] = X[3 * s + 2];
+  w_mse[j] = mse[s];
 }
 
 }  // namespace seed
@@ -188,10 +199,11 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     return msfm_set_error(ctx, MSFM_E_INVAL, "%s: ransac_times out of range", who);
   // ---- O(hypotheses) on the host: the store pair of each, its arm, the three CSRs, the block map ----
   std::unique_ptr<msfm_seed_set> R(new msfm_seed_set());
-  R->n = n;
+  R->ctx = ctx; R->store = S; R->n = n;
   R->arm.assign(n, 0); R->n_matches.assign(n, 0);
   std::vector<Hyp> hyp(n);
   std::vector<int> off_all(n + 1, 0), off5(n + 1, 0), off8(n + 1, 0), blk_off(n + 1, 0);
+  int longest = 0;                           // matches of the longest hypothesis: the capacity of the winner's blocks
   std::vector<int> kp_base;                  // per image: its first row in the uploaded keypoints, -1: not uploaded
   std::vector<int> kp_imgs;
   std::vector<double> f5_ref(n), f5_cur(n);   // f of the five-point arm = the given values (uploaded only if that arm has a match)
@@ -217,6 +229,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     const int arm = (f1 != 0.0 && f2 != 0.0) ? 5 : 8;   // :307
     hyp[h] = Hyp{m0, P->keypoints ? kp_base[i1] : S->feat_off[i1], P->keypoints ? kp_base[i2] : S->feat_off[i2], arm};
     R->arm[h] = (uint8_t)arm; R->n_matches[h] = cnt;
+    longest = std::max(longest, cnt);
     if ((long)off_all[h] + cnt > 0x7fffffffL) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: more than 2^31 matches in one call", who);
     off_all[h + 1] = off_all[h] + cnt;
     off5[h + 1] = off5[h] + (arm == 5 ? cnt : 0);
@@ -226,11 +239,11 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   const int M = off_all[n], M5 = off5[n], M8 = off8[n];
   R->pose_ok.assign(n, 0); R->pass.assign(n, 0); R->pt_off.assign(n + 1, 0);
   R->f.assign(2 * (size_t)n, 0.0); R->R.assign(9 * (size_t)n, 0.0); R->t.assign(3 * (size_t)n, 0.0); R->c.assign(3 * (size_t)n, 0.0);
-  if (n == 0) { *out = R.release(); return MSFM_OK; }
+  if (n == 0) { ctx->children++; *out = R.release(); return MSFM_OK; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<Hyp> d_hyp;
-  DevBuf<int> d_offa, d_off5, d_off8, d_blk, d_ptm, d_count;
+  DevBuf<int> d_offa, d_off5, d_off8, d_blk, d_ptm, d_count, d_win;
   DevBuf<double> d_fk, d_ref5, d_cur5, d_ref8, d_cur8, d_f5a, d_f5b;
   DevBuf<double> d_fout, d_cam, d_Xall, d_mseall, d_X, d_mse;
   DevBuf<uint8_t> d_same, d_pok, d_flag, d_pass;
@@ -258,6 +271,11 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   SD_TRY(d_pok.alloc(n)); SD_TRY(d_fout.alloc(2 * (size_t)n)); SD_TRY(d_cam.alloc(SEED_CAM * (size_t)n));
   SD_TRY(d_flag.alloc(Mx)); SD_TRY(d_Xall.alloc(3 * Mx)); SD_TRY(d_mseall.alloc(Mx));
   SD_TRY(d_ptm.alloc(Mx)); SD_TRY(d_X.alloc(3 * Mx)); SD_TRY(d_mse.alloc(Mx)); SD_TRY(d_count.alloc(n)); SD_TRY(d_pass.alloc(n));
+  SD_TRY(d_win.alloc(1));
+  SD_TRY(hipMemsetD32Async((hipDeviceptr_t)d_win.p, INT_MAX, 1, s));
+  if (longest) {   // (R's blocks: an error return deletes the set behind the scope's wait)
+    SD_TRY(R->d_ptm.alloc((size_t)longest)); SD_TRY(R->d_X.alloc(3 * (size_t)longest)); SD_TRY(R->d_mse.alloc((size_t)longest));
+  }
   // an arm without a match is not launched: its hypotheses have failed (fewer than 5 / 8 matches)
   SD_TRY(hipMemsetAsync(r5.ok.p, 0, (size_t)n, s)); SD_TRY(hipMemsetAsync(r8.ok.p, 0, (size_t)n, s));
   if (M) {
@@ -286,7 +304,12 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   {
     KTimer tm(ctx, "seed_compact");
     hipLaunchKernelGGL(k_compact, dim3(n), dim3(256), 0, s, d_offa.p, d_flag.p, d_Xall.p, d_mseall.p, d_pok.p, (int)opt.th_seedpair_structures, d_ptm.p,
-                       d_X.p, d_mse.p, d_count.p, d_pass.p);
+                       d_X.p, d_mse.p, d_count.p, d_pass.p, d_win.p);
+  }
+  if (longest) {
+    KTimer tm(ctx, "seed_keep");
+    hipLaunchKernelGGL(k_keep, dim3(cdiv(longest, 256)), dim3(256), 0, s, longest, d_win.p, d_offa.p, d_count.p, d_ptm.p, d_X.p, d_mse.p, R->d_ptm.p,
+                       R->d_X.p, R->d_mse.p);
   }
   SD_TRY(hipGetLastError());
   // ---- one read-back: the per-hypothesis records and the point arrays at their uncompacted capacity (M is known here, the
@@ -320,7 +343,16 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     std::copy(X.begin() + 3 * b, X.begin() + 3 * (b + k), R->X.begin() + 3 * e);
     std::copy(mse.begin() + b, mse.begin() + b + k, R->mse.begin() + e);
   }
+  if (R->winner >= 0) {
+    const Hyp& W = hyp[R->winner];
+    R->win_img[0] = P->hyp_img[2 * R->winner]; R->win_img[1] = P->hyp_img[2 * R->winner + 1];
+    R->win_m0 = W.m0;
+    R->win_kp[0] = S->feat_off[R->win_img[0]]; R->win_kp[1] = S->feat_off[R->win_img[1]];
+  } else {   // nothing to keep
+    R->d_ptm.release(); R->d_X.release(); R->d_mse.release();
+  }
   R->h2d_bytes = sc.h2d;
+  ctx->children++;   // a child of its context, like a store
   *out = R.release();
   return MSFM_OK;
 }
@@ -352,4 +384,13 @@ MSFM_API int msfm_seed_set_fetch(const msfm_seed_set* R, uint8_t* arm, uint8_t* 
   return MSFM_OK;
 }
 
-MSFM_API void msfm_seed_set_destroy(msfm_seed_set* R) { delete R; }
+MSFM_API void msfm_seed_set_destroy(msfm_seed_set* R) {
+  if (!R) return;
+  msfm_ctx* ctx = R->ctx;
+  if (R->d_ptm.p) {   // blocks go back to the pool only behind the work that may still read them
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  delete R;
+  msfm_ctx_child_released(ctx);
+}

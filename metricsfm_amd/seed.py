@@ -45,7 +45,7 @@ def seed_hypotheses(ctx: capi.Context, store, hyp_img, cam_fk, same_model, keypo
 
 
 def find_seed_pair(ctx: capi.Context, store, match_graph, processed, f_of_image, model_of_image, k=64, keypoints=None,
-                   k12_of_image=None, pair_matches=None, image_keypoints=None, **opts):
+                   k12_of_image=None, pair_matches=None, image_keypoints=None, keep=False, **opts):
     """FindSeedPairThenReconstruct up to and including its gates (:224-390).  The ranked pairs go to the device in chunks of
     `k` until a chunk has a winner; every chunk is a call of its own, so a hypothesis' sample key is its index in its chunk.
     f_of_image [n] (0 = unknown), model_of_image [n] (ids of CameraAssociateCameraModel; two images with the same id share
@@ -58,7 +58,9 @@ def find_seed_pair(ctx: capi.Context, store, match_graph, processed, f_of_image,
       cam_pose [2][6] (angle-axis, t), cam_model [n_models][3] (f, k1, k2), cam_model_of_cam [2], cam_R, cam_t, cam_c;
       point [P][3], mse [P], obs_cam / obs_pt [2P], obs_xy [2P][2] (camera 0's observation of a point first), obs_feature [2P]
       (feature index inside its image), pt_match [P]: what `_abi.BaArrays(cam_pose, cam_model, cam_model_of_cam, point, obs_cam,
-      obs_pt, obs_xy)` takes; hypotheses = the chunk's full answer."""
+      obs_pt, obs_xy)` takes; hypotheses = the chunk's full answer.
+    keep=True: the winning chunk's `capi.SeedSet` stays alive under "set" (the caller closes it), so `capi.Recon.from_seed` makes
+    the model's state on the device and no pair_matches callback is needed."""
     if k < 1:
         raise ValueError("k must be at least 1")
     hyps = sort_image_pairs(match_graph, processed)
@@ -71,9 +73,11 @@ def find_seed_pair(ctx: capi.Context, store, match_graph, processed, f_of_image,
         fk[:, :, 0] = f_of_image[chunk]
         fk[:, :, 1:] = k12[chunk]
         same = model_of_image[chunk[:, 0]] == model_of_image[chunk[:, 1]]
-        r = ctx.seed_hypotheses(store, chunk, fk, same, keypoints=keypoints, **opts)
+        r = ctx.seed_hypotheses(store, chunk, fk, same, keypoints=keypoints, keep=keep, **opts)
         w = r["winner"]
         if w < 0:
+            if keep:
+                r.pop("set").close()
             continue
         i1, i2 = (int(v) for v in chunk[w])
         b, e = r["pt_off"][w], r["pt_off"][w + 1]
@@ -86,6 +90,8 @@ def find_seed_pair(ctx: capi.Context, store, match_graph, processed, f_of_image,
                    cam_model=cam_model, cam_model_of_cam=np.array([0, 0 if shared else 1], np.int32),
                    cam_R=np.array([np.eye(3), R1]), cam_t=np.array([np.zeros(3), t1]), cam_c=np.array([np.zeros(3), r["c"][w]]),
                    point=r["X"][b:e].copy(), mse=r["mse"][b:e].copy(), pt_match=r["pt_match"][b:e].copy(), hypotheses=r)
+        if keep:
+            out["set"] = r["set"]
         if pair_matches is not None:
             if image_keypoints is None:
                 if keypoints is None:
