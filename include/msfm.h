@@ -859,6 +859,84 @@ int msfm_voctree_fetch(const msfm_voctree* tree, uint16_t* block_n, float* node_
                        uint16_t* block_leaf, uint32_t* block_parent);
 
 /* ======================================================================================
+ *  Describing given SIFT frames: image to resident descriptor rows
+ * ====================================================================================== */
+/* The given-frames arm of Database::ExtractImageFeatures (SfM/src/database.cc:289-349), that is VLSiftExtractor::initialize
+ * (SfM/src/feature/feature_extractor_vl_sift.h:41-71, the stretch) and VLSiftExtractor::run_sift with nikeys >= 0
+ * (feature_extractor_vl_sift.cpp:75-216; :150-169 vl_sift_keypoint_init on a supplied (x, y, sigma, angle), :182
+ * vl_sift_calc_keypoint_descriptor, :183 transpose_descriptor, :202 the factor 512): the Gaussian scale space of a uint8 image,
+ * its gradients, and the 4 x 4 x 8 descriptor of every given frame, written straight into a descriptor set.  The DoG detector,
+ * the orientation histogram, o_min = -1 upsampling and the CUDA-SIFT arm are not built.
+ * PARITY IS UNPINNED.  VLFeat's sift.c / imopv.c are not in the reference tree (only vl/sift.h and import libraries).  The
+ * definitions below are this project's; where they differ from VLFeat's, these hold.  They are chosen so that the result depends
+ * neither on the device's scheduling nor on a library's transcendental functions: tests/sift_ref.cpp and tests/sift_ref.py
+ * restate them and the device reproduces them bit for bit.
+ *   arithmetic  binary32 on the device, every + - * / sqrtf rounded on its own (never contracted), / and sqrtf correctly
+ *               rounded.  EPS = 1.19209290e-07f (2^-23), PI2 = 6.28318548f.  S = n_levels, O = n_octaves, levels s = -1 .. S + 1.
+ *   host data   what needs exp, pow, log2, fmod, sin or cos is computed once on the host in binary64 with the C library, rounded
+ *               to binary32, and used as data: the taps of every blur, the table T[i] = exp(-i * 25.0 / 256.0), i = 0 .. 256, and
+ *               per frame (o, is, thr, st, ct).  k = pow(2, 1.0 / S), sigma0 = 1.6 * k, dsigma0 = sigma0 * sqrt(1 - 1 / (k * k)).
+ *               The blur of level -1 is sd(-1) = sqrt(sa * sa - 0.25) with sa = sigma0 * pow(k, -1.0); of level s >= 0 it is
+ *               sd(s) = dsigma0 * pow(k, (double) s): the same in every octave.
+ *   stretch     (feature_extractor_vl_sift.h:51-62) p = (float(v) - fmin) / frange * 255.0f in that order, fmin and frange = max - min from an
+ *               integer reduction over the width x height pixels (the bytes between width and stride are not looked at).
+ *   blur by sd  W = max((int) ceil(4 sd), 1); g[i] = exp(-0.5 * (i - W)^2 / (sd * sd)), i = 0 .. 2W, divided by their sum (added
+ *               in ascending i) in binary64, then rounded.  out(x) = ((0 + g[0] a_0) + g[1] a_1) + ... in ascending i with
+ *               a_i = src[clamp(x + i - W, 0, w - 1)]: rows first, then the columns of that result with the same rule on y.
+ *   octaves     octave o is (width >> o) x (height >> o).  Level (0, -1) is the stretched image blurred by sd(-1); level s is
+ *               level s - 1 blurred by sd(s); level (o + 1, -1) is the pixels (2x, 2y) of level (o, S - 1).
+ *   gradient    on the levels 0 .. S - 1: gx = 0.5f * (I[x + 1] - I[x - 1]) inside, I[1] - I[0] and I[w - 1] - I[w - 2] at the
+ *               borders, gy likewise; mod = sqrtf(gx * gx + gy * gy).  angle in [0, PI2): ax = |gx|, ay = |gy|,
+ *               mx = max(ax, ay), mn = min(ax, ay); mx = 0 gives 0; otherwise t = mn / mx, q = t * t,
+ *               r = t * (c1 + q * (c3 + q * (c5 + q * (c7 + q * (c9 + q * c11))))) with c1 = 0.99997726f, c3 = -0.33262347f,
+ *               c5 = 0.19354346f, c7 = -0.11643287f, c9 = 0.05265332f, c11 = -0.01172120f (the published degree-11 odd
+ *               polynomial for atan on [0, 1], error below 2e-5 rad); if ay > ax: r = 1.57079637f - r; if gx < 0:
+ *               r = 3.14159274f - r; if gy < 0: r = PI2 - r; if r >= PI2: r = r - PI2.
+ *   frame       (x, y, sigma, theta) as binary32, widened to binary64: phi = log2((sigma + 2^-23) / sigma0),
+ *               o = clamp(floor(phi - (-1 + 0.5) / S), 0, O - 1), is = clamp(floor(S * (phi - o) + 0.5), 0, S - 1);
+ *               thr = fmod(theta, 6.283185307179586), plus that constant when negative; st = sin(theta), ct = cos(theta); thr, st
+ *               and ct rounded to binary32.
+ *   descriptor  on level (o, is) of w x h pixels: x' = x / 2^o, y' = y / 2^o, sigma' = sigma / 2^o; xf = x' + 0.5f,
+ *               yf = y' + 0.5f.  The row is zero unless -1 < xf < w and -1 < yf < h - 1 (that is, unless xi = (int) xf, yi = (int) yf
+ *               have 0 <= xi < w and 0 <= yi < h - 1).  SBP = 3.0f * sigma' + EPS, Wf = floorf(1.41421356f * SBP * 2.5f + 0.5f),
+ *               W = Wf < 32768 ? (int) Wf : 32768.  The pixels (xi + dxi, yi + dyi), dyi = max(-W, 1 - yi) .. min(W, h - yi - 2)
+ *               and inside it dxi = max(-W, 1 - xi) .. min(W, w - xi - 2), are visited in that (raster) order.  At pixel (px, py):
+ *                 dx = float(px) - x', dy = float(py) - y';  nx = (ct * dx + st * dy) / SBP,  ny = ((-st) * dx + ct * dy) / SBP
+ *                 th = angle - thr; if th < 0: th = th + PI2; if th >= PI2: th = th - PI2;  nt = (8.0f * th) / PI2
+ *                 u = ((nx * nx + ny * ny) * 0.125f) * 10.24f; the pixel is skipped unless u < 256; i = (int) u, f = u - float(i),
+ *                 win = T[i] + f * (T[i + 1] - T[i])
+ *                 bx = floorf(nx - 0.5f), by = floorf(ny - 0.5f), bt = floorf(nt); the pixel is skipped unless -3 <= bx <= 1 and
+ *                 -3 <= by <= 1;  rx = nx - (bx + 0.5f), ry = ny - (by + 0.5f), rt = nt - bt
+ *                 wx[0] = |1.0f - rx|, wx[1] = |rx|, wy and wt likewise; for dbx, dby, dbt in {0, 1} with -2 <= bx + dbx <= 1 and
+ *                 -2 <= by + dby <= 1 the value (((win * mod) * wx[dbx]) * wy[dby]) * wt[dbt] is added to
+ *                 bin ((bt + dbt) mod 8) + 8 (bx + dbx + 2) + 32 (by + dby + 2).
+ *               Each bin is the sum, from 0, of its contributions in the order of the pixels (two contributions of one pixel never
+ *               share a bin).  Then n = sqrtf(sum of h[b] * h[b], b ascending from 0) + EPS, h = h / n, h = min(h, 0.2f), n again
+ *               the same way, h = h / n; the value of bin t + 8 i + 32 j goes to column ((8 - t) mod 8) + 8 i + 32 (3 - j)
+ *               (transpose_descriptor, :37-53) as 512.0f * h, or with quantize as min(float((int) (512.0f * h)), 255.0f).
+ * A scale space is a child of its context and keeps the GSS levels and the gradient levels of every octave, nothing else.
+ * msfm_scalespace_create: MSFM_E_INVAL for a NULL pointer, width or height < 2 or > 16384, stride < width, n_octaves or n_levels
+ * outside [1, 8], min(width, height) >> (n_octaves - 1) < 2, a constant image; MSFM_E_NOMEM when the levels do not fit.
+ * msfm_scalespace_fetch: kind 0 a GSS level, level in [-1, S + 1]; kind 1 / 2 the gradient modulus / angle, level in [0, S - 1];
+ * out [h_o][w_o] float.  msfm_scalespace_size: the octave's size and the bytes create sent (image, taps, table).
+ * msfm_descset_describe replaces the image's descriptors AND keypoints (xy = the frames' x, y) by the route
+ * msfm_descset_upload takes - integrality flag, largest |value|, int8 forms, generation, stale match results - device to
+ * device: no descriptor byte crosses PCIe, h2d_bytes (optional) counts the frames and the per-frame host values.
+ * MSFM_E_INVAL, found before the first write, set and scale space stay usable: a NULL pointer, n < 0 or n > 65535, a non-finite
+ * frame value, sigma <= 0, an image outside the set, set and scale space of different contexts (a set of dim != 128 does not
+ * exist: msfm_descset_create refuses it).
+ * msfm_descset_fetch: the image's rows [count][128] and keypoints [count][2]; either may be NULL. */
+typedef struct msfm_scalespace msfm_scalespace;
+int msfm_scalespace_create(msfm_ctx* ctx, const uint8_t* gray, int width, int height, int stride, int n_octaves /* 4 */,
+                           int n_levels /* 5 */, msfm_scalespace** out);
+int msfm_scalespace_fetch(const msfm_scalespace* ss, int octave, int level, int kind, float* out);
+int msfm_scalespace_size(const msfm_scalespace* ss, int octave, int* w, int* h, int64_t* h2d_bytes);
+void msfm_scalespace_destroy(msfm_scalespace* ss);
+int msfm_descset_describe(msfm_descset* set, int image, const msfm_scalespace* ss, const float* frames /*[n][4]: x, y, sigma, angle*/,
+                          int n, int quantize, int64_t* h2d_bytes);
+int msfm_descset_fetch(const msfm_descset* set, int image, float* desc /*[count][128]*/, float* xy /*[count][2]*/);
+
+/* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search
  * ====================================================================================== */
 /* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference

@@ -397,6 +397,11 @@ class Context(_Handle):
         """msfm_voctree_create: a vocabulary tree (featurefiles.read_voctree) resident as a `VocTree`."""
         return VocTree(self, k, block_n, node_desc, node_link, node_weight)
 
+    def scalespace(self, gray, n_octaves=4, n_levels=5, stride=None):
+        """msfm_scalespace_create: the Gaussian scale space and gradients of a uint8 image [h][w] resident as a `ScaleSpace`;
+        stride (>= w) hands the image over in a buffer of that many bytes per row."""
+        return ScaleSpace(self, gray, n_octaves, n_levels, stride)
+
     def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
         """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
         as a `Recon`; cam_pose / cam_model / cam_model_of_cam are the solver's parameter blocks as `adjust.adjust_round` takes
@@ -789,6 +794,27 @@ class DescSet(_Handle):
         features, as a `WordResult`."""
         return WordResult(self, tree, min_features)
 
+    def describe(self, image, ss, frames, quantize=False):
+        """msfm_descset_describe: the image's descriptors and keypoints become those of the frames [n][4] (x, y, sigma, angle)
+        on the scale space `ss`, device to device.  -> the bytes sent (frames and per-frame host values)."""
+        fr = A.as_c(np.asarray(frames, dtype=np.float32).reshape(-1, 4), np.float32)
+        hb = C.c_int64()
+        self.ctx.check(lib().msfm_descset_describe(self._h, int(image), ss._h, A.ptr(fr, A.c_float_p), len(fr), int(bool(quantize)), C.byref(hb)))
+        self.counts[image] = len(fr)
+        return hb.value
+
+    def fetch(self, image):
+        """msfm_descset_fetch -> (rows [count][128], xy [count][2] or None for an image without keypoints): what
+        featurefiles.write_feature takes."""
+        n = lib().msfm_descset_count(self._h, int(image))
+        if n < 0:
+            raise MsfmError(n, "image %d outside the set" % image)
+        rows, xy = np.zeros((n, 128), np.float32), np.zeros((n, 2), np.float32)
+        if lib().msfm_descset_fetch(self._h, int(image), A.ptr(rows, A.c_float_p), A.ptr(xy, A.c_float_p)) != 0:
+            xy = None
+            self.ctx.check(lib().msfm_descset_fetch(self._h, int(image), A.ptr(rows, A.c_float_p), None))
+        return rows, xy
+
     def train_voctree(self, k=10, levels=6, max_iters=11, image_step=1, seed=0):
         """msfm_descset_voctree_train (Database::BuildVocabularyTree): hierarchical k-means over the descriptors of every
         image_step-th image, on the device; the defaults are the reference's.  -> a `VocTree` whose `stats` holds the training's
@@ -796,6 +822,49 @@ class DescSet(_Handle):
         h = C.c_void_p()
         self.ctx.check(lib().msfm_descset_voctree_train(self._h, int(k), int(levels), int(max_iters), int(image_step), int(seed), C.byref(h)))
         return VocTree._adopt(self.ctx, h)
+
+
+class ScaleSpace(_Handle):
+    """msfm_scalespace: the Gaussian levels s = -1 .. S + 1 and the gradient levels 0 .. S - 1 of every octave of one image, on the
+    device (include/msfm.h states the definitions).  gray: uint8 [h][w]; stride: bytes per row of the buffer gray is a view of."""
+    _destroy = "msfm_scalespace_destroy"
+
+    def __init__(self, ctx: Context, gray, n_octaves=4, n_levels=5, stride=None):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        gray = np.asarray(gray)
+        if gray.dtype != np.uint8 or gray.ndim != 2:
+            raise ValueError("gray must be uint8 [h][w]")
+        h, w = gray.shape
+        if stride is None:
+            stride = w
+            buf = np.ascontiguousarray(gray)
+        else:
+            buf = np.zeros((h, max(int(stride), w)), np.uint8)
+            buf[:, :w] = gray
+            buf[0::2, w:] = 255   # the padding is never read: it would change the range
+        self.n_octaves, self.n_levels = int(n_octaves), int(n_levels)
+        ctx.check(lib().msfm_scalespace_create(ctx._h, A.ptr(buf, A.c_u8_p), w, h, int(stride), self.n_octaves, self.n_levels, C.byref(self._h)))
+
+    def size(self, octave=0):
+        """-> dict(w, h, h2d_bytes) of an octave."""
+        w, h, hb = C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx.check(lib().msfm_scalespace_size(self._h, int(octave), C.byref(w), C.byref(h), C.byref(hb)))
+        return dict(w=w.value, h=h.value, h2d_bytes=hb.value)
+
+    def _fetch(self, octave, level, kind):
+        z = self.size(octave)
+        out = np.zeros((z["h"], z["w"]), np.float32)
+        self.ctx.check(lib().msfm_scalespace_fetch(self._h, int(octave), int(level), kind, A.ptr(out, A.c_float_p)))
+        return out
+
+    def level(self, octave, level):
+        """The GSS level `level` in [-1, S + 1] of an octave, float32 [h_o][w_o]."""
+        return self._fetch(octave, level, 0)
+
+    def gradient(self, octave, level):
+        """-> (modulus, angle) of level `level` in [0, S - 1] of an octave."""
+        return self._fetch(octave, level, 1), self._fetch(octave, level, 2)
 
 
 class MatchResult(_Handle):

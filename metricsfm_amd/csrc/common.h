@@ -8,6 +8,7 @@
 #include <cstring>
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <initializer_list>
 #include <string>
 #include <thread>
@@ -567,6 +568,10 @@ struct DescView {   // what words.hip needs of a descriptor set (defined in knn.
   std::vector<const float*> kp;    // device [count][2] per image, nullptr: no keypoints
 };
 void descset_view(const msfm_descset* s, DescView* out);
+// msfm_descset_upload is its checks + this core with a fill that copies from the host; msfm_descset_describe (sift.hip) fills the
+// same blocks by kernel.  fill(rows, kp, stream) enqueues what writes rows [count][128] and, with_kp, kp [count][2].
+typedef std::function<hipError_t(float*, float*, hipStream_t)> DescFill;
+int descset_put_dev(msfm_descset* s, int image, int count, bool with_kp, const char* prep_stat, const DescFill& fill);
 struct voctrain_stats {   // what msfm_voctree_train_stats reports (include/msfm.h)
   int64_t n_features = 0, n_leaves = 0;
   int n_images = 0, n_blocks = 0, depth = 0, weight_shift = 0, sum_shift = 0, host_waits = 0;

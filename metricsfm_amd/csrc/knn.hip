@@ -1089,8 +1089,11 @@ MSFM_API int msfm_descset_count(const msfm_descset* s, int image) {
   return s->count[image];
 }
 
-MSFM_API int msfm_descset_upload(msfm_descset* s, int image, const float* desc, int count) {
-  if (!s || image < 0 || image >= s->n_images || count < 0 || (count > 0 && !desc)) return MSFM_E_INVAL;
+// The device-array core of msfm_descset_upload: replaces the image's rows by what `fill` enqueues into the new blocks (rows
+// [count][128]; kp [count][2] with with_kp, else the image is left without keypoints), then the integrality flag, the largest
+// |value| and the int8 forms (timed as the kernel class `prep_stat` where that is given).  The caller has checked its arguments;
+// `fill` is not called for count = 0.
+int descset_put_dev(msfm_descset* s, int image, int count, bool with_kp, const char* prep_stat, const DescFill& fill) {
   msfm_ctx* ctx = s->ctx;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -1111,20 +1114,47 @@ MSFM_API int msfm_descset_upload(msfm_descset* s, int image, const float* desc, 
   s->ti8[image] = new DevBuf<signed char>(); s->qi8[image] = new DevBuf<signed char>();
   s->tcin[image] = new DevBuf<int>(); s->tpar[image] = new DevBuf<int>(); s->qbeta[image] = new DevBuf<int>();
   s->count[image] = count;
+  if (with_kp) s->kp[image] = new DevBuf<float>();
   if (count == 0) return MSFM_OK;
+  if (with_kp) HIP_TRY(ctx, s->kp[image]->alloc(2 * (size_t)count));
   HIP_TRY(ctx, s->f32[image]->alloc((size_t)count * DIM));
   HIP_TRY(ctx, s->ti8[image]->alloc((size_t)count * DIM)); HIP_TRY(ctx, s->qi8[image]->alloc((size_t)count * DIM));
   HIP_TRY(ctx, s->tcin[image]->alloc(count)); HIP_TRY(ctx, s->tpar[image]->alloc(count)); HIP_TRY(ctx, s->qbeta[image]->alloc(count));
-  HIP_TRY(ctx, s->f32[image]->upload(desc, (size_t)count * DIM, st));
+  HIP_TRY(ctx, fill(s->f32[image]->p, with_kp ? s->kp[image]->p : nullptr, st));
+  KTimer t(prep_stat ? ctx : nullptr, prep_stat ? prep_stat : "");
+  t.count = 2;
   hipLaunchKernelGGL(k_desc_prep, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->nonint.p, s->vmax_dev.p);
   hipLaunchKernelGGL(k_desc_prep_i8, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->ti8[image]->p,
                      s->qi8[image]->p, s->tcin[image]->p, s->tpar[image]->p, s->qbeta[image]->p);
   HIP_TRY(ctx, hipGetLastError());
+  t.stop();
   unsigned vbits = 0;
   HIP_TRY(ctx, hipMemcpyAsync(&s->h_nonint, s->nonint.p, sizeof(int), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(&vbits, s->vmax_dev.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   memcpy(&s->vabs_max, &vbits, sizeof(float));   // running maximum over every upload so far (never reset)
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_descset_upload(msfm_descset* s, int image, const float* desc, int count) {
+  if (!s || image < 0 || image >= s->n_images || count < 0 || (count > 0 && !desc)) return MSFM_E_INVAL;
+  return descset_put_dev(s, image, count, false, nullptr, [&](float* d_rows, float*, hipStream_t st) {
+    return hipMemcpyAsync(d_rows, desc, sizeof(float) * (size_t)count * DIM, hipMemcpyHostToDevice, st);
+  });
+}
+
+MSFM_API int msfm_descset_fetch(const msfm_descset* s, int image, float* desc, float* xy) {
+  if (!s || image < 0 || image >= s->n_images) return MSFM_E_INVAL;
+  msfm_ctx* ctx = s->ctx;
+  const size_t count = (size_t)s->count[image];
+  if (xy && count && !(s->kp[image] && s->kp[image]->p)) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_descset_fetch: image %d has no keypoints", image);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DevScope sc(ctx);
+  if (count) {
+    HIP_TRY(ctx, sc.down(desc, s->f32[image]->p, count * DIM));
+    if (xy) HIP_TRY(ctx, sc.down(xy, s->kp[image]->p, 2 * count));
+  }
+  HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
 }
 
