@@ -865,8 +865,8 @@ int msfm_voctree_fetch(const msfm_voctree* tree, uint16_t* block_n, float* node_
  * (SfM/src/feature/feature_extractor_vl_sift.h:41-71, the stretch) and VLSiftExtractor::run_sift with nikeys >= 0
  * (feature_extractor_vl_sift.cpp:75-216; :150-169 vl_sift_keypoint_init on a supplied (x, y, sigma, angle), :182
  * vl_sift_calc_keypoint_descriptor, :183 transpose_descriptor, :202 the factor 512): the Gaussian scale space of a uint8 image,
- * its gradients, and the 4 x 4 x 8 descriptor of every given frame, written straight into a descriptor set.  The DoG detector,
- * the orientation histogram, o_min = -1 upsampling and the CUDA-SIFT arm are not built.
+ * its gradients, and the 4 x 4 x 8 descriptor of every given frame, written straight into a descriptor set.  The DoG detector
+ * and the orientation histogram follow in the next section; o_min = -1 upsampling and the CUDA-SIFT arm are not built.
  * PARITY IS UNPINNED.  VLFeat's sift.c / imopv.c are not in the reference tree (only vl/sift.h and import libraries).  The
  * definitions below are this project's; where they differ from VLFeat's, these hold.  They are chosen so that the result depends
  * neither on the device's scheduling nor on a library's transcendental functions: tests/sift_ref.cpp and tests/sift_ref.py
@@ -935,6 +935,81 @@ void msfm_scalespace_destroy(msfm_scalespace* ss);
 int msfm_descset_describe(msfm_descset* set, int image, const msfm_scalespace* ss, const float* frames /*[n][4]: x, y, sigma, angle*/,
                           int n, int quantize, int64_t* h2d_bytes);
 int msfm_descset_fetch(const msfm_descset* set, int image, float* desc /*[count][128]*/, float* xy /*[count][2]*/);
+
+/* ======================================================================================
+ *  Detecting SIFT keypoints: DoG extrema and orientations to frames
+ * ====================================================================================== */
+/* The detecting arm of VLSiftExtractor::run_sift, nikeys < 0 (feature_extractor_vl_sift.cpp:130-136 vl_sift_detect, :171-173
+ * vl_sift_calc_keypoint_orientations), on a scale space made above, with the reference's parameters as defaults
+ * (feature_extractor_vl_sift.cpp:80-86): peak_thresh 0, edge_thresh 10, 36 orientation bins, at most 4 angles per keypoint,
+ * o_min = 0.  PARITY IS UNPINNED as above, and the same principles hold: binary32 on the device with every operation rounded on
+ * its own, no library transcendental on the device, nothing depends on the device's scheduling, what needs pow is computed on the
+ * host in binary64 with the C library and used as data.  tests/siftdetect_ref.cpp restates what follows.
+ *   DoG         D(o, s) = G(o, s + 1) - G(o, s), s = -1 .. S, one subtraction per value.  No plane of D is kept: the kernels form
+ *               it from the resident levels where they need it, and the scale space object holds what it held before.
+ *   extrema     on the levels s = 0 .. S - 1 and the pixels x = 1 .. w - 2, y = 1 .. h - 2 of every octave.  With v = D(x, y, s),
+ *               t = 0.8f * peak_thresh and the 26 neighbours n = D(x + i, y + j, s + k), (i, j, k) in {-1, 0, 1}^3 \ {0}: a maximum
+ *               has v > n for all of them and v >= t, a minimum v < n for all of them and v <= -t.  Ties are not extrema.
+ *   refinement  of a candidate (x, y, s), at most 5 passes.  A pass, with d(i, j, k) = D(x + i, y + j, s + k):
+ *                 Dx = 0.5f * (d(1,0,0) - d(-1,0,0)), Dy and Ds likewise;  Dxx = (d(1,0,0) + d(-1,0,0)) - 2.0f * d(0,0,0), Dyy and
+ *                 Dss likewise;  Dxy = 0.25f * (((d(1,1,0) + d(-1,-1,0)) - d(-1,1,0)) - d(1,-1,0)), Dxs and Dys likewise (Dxs from
+ *                 (1,0,1), (-1,0,-1), (-1,0,1), (1,0,-1); Dys from (0,1,1), (0,-1,-1), (0,-1,1), (0,1,-1)).
+ *                 A = [Dxx Dxy Dxs; Dxy Dyy Dys; Dxs Dys Dss], b = (-Dx, -Dy, -Ds).  Gaussian elimination, for j = 0, 1, 2: the
+ *                 pivot row is the first i >= j with the largest |A(i, j)| (a later row replaces it only when strictly larger); a
+ *                 largest |A(i, j)| of 0 sets b = (0, 0, 0) and ends the elimination; else rows i and j are exchanged from column j
+ *                 on, A(j, jj) = A(j, jj) / p for jj = j .. 2 and b(j) = b(j) / p with p the pivot's value, and for ii > j, with
+ *                 f = A(ii, j): A(ii, jj) = A(ii, jj) - f * A(j, jj), jj = j .. 2, b(ii) = b(ii) - f * b(j).  Back substitution:
+ *                 for i = 2, 1 and ii = i - 1 .. 0: b(ii) = b(ii) - b(i) * A(ii, i).
+ *                 mx = +1 if b(0) > 0.6f and x < w - 2, -1 if b(0) < -0.6f and x > 1, else 0; my likewise from b(1), y and h.  If both
+ *                 are 0 the loop ends; after the fifth pass it ends anyway (the keypoint is then `unconverged`); otherwise
+ *                 x = x + mx, y = y + my (never s) and the next pass follows.  A keypoint whose (x, y) has changed has `moved`.
+ *               With the last pass's values: val = d(0,0,0) + 0.5f * ((Dx * b(0) + Dy * b(1)) + Ds * b(2)),
+ *               score = ((Dxx + Dyy) * (Dxx + Dyy)) / (Dxx * Dyy - Dxy * Dxy), xn = float(x) + b(0), yn = float(y) + b(1),
+ *               sn = float(s) + b(2), bound = (float) ((e + 1) * (e + 1) / e) with e = (double) edge_thresh.  The candidate is
+ *               rejected by the first of these that does not hold, each written so that a NaN fails it:
+ *                 peak    |val| > peak_thresh                     edge    score < bound                  negative  score >= 0
+ *                 offset  |b(0)|, |b(1)|, |b(2)| all < 1.5f        bounds  0 <= xn <= w - 1, 0 <= yn <= h - 1, -1 <= sn <= S + 1
+ *               and is otherwise the raw keypoint (o, ix, iy, is, xn, yn, sn) with (ix, iy) the last pass's (x, y) and is = s.
+ *   orientation of a raw keypoint, on the gradient planes of its (o, is).  Host: sigmaw = (float) (1.5 * sigma0 * pow(2, sn / S))
+ *               in binary64 with sn widened.  The device makes the raw keypoints, the host this number, the device the angles: two
+ *               device passes around one host step.  xi = (int) (xn + 0.5f), yi = (int) (yn + 0.5f), W = (int) floorf(3.0f * sigmaw).
+ *               The pixels (xi + dxi, yi + dyi) with the descriptor's clipping, dyi = max(-W, 1 - yi) .. min(W, h - yi - 2) and
+ *               inside it dxi = max(-W, 1 - xi) .. min(W, w - xi - 2), in that (raster) order.  At pixel (px, py):
+ *                 dx = float(px) - xn, dy = float(py) - yn, r2 = dx * dx + dy * dy; skipped unless r2 < float(W * W) + 0.6f
+ *                 u = (r2 / ((2.0f * sigmaw) * sigmaw)) * 10.24f; skipped unless u < 256; i = (int) u, f = u - float(i),
+ *                 win = T[i] + f * (T[i + 1] - T[i]), v = win * mod
+ *                 fb = (36.0f * angle) / PI2, bf = floorf(fb - 0.5f), rb = fb - (bf + 0.5f), ib = ((int) bf + 36) mod 36
+ *                 (1.0f - rb) * v is added to bin ib and rb * v to bin (ib + 1) mod 36.
+ *               Each bin is the sum, from 0, of its contributions in the order of the pixels.  Then six times, from the old values:
+ *               h[i] = ((h[(i + 35) mod 36] + h[i]) + h[(i + 1) mod 36]) / 3.0f.  m = the largest h.  Bin i is a peak when
+ *               h[i] > 0.8f * m, h[i] > hm and h[i] > hp, with hm = h[(i + 35) mod 36], hp = h[(i + 1) mod 36]; then
+ *               di = (-0.5f * (hp - hm)) / ((hp + hm) - 2.0f * h[i]), theta = (PI2 * ((float(i) + di) + 0.5f)) / 36.0f.  The first
+ *               four peaks in ascending i are the keypoint's angles (it may have none).
+ *   frames      on the host, per raw keypoint and angle: x = xn * 2^o, y = yn * 2^o (binary32, exact),
+ *               sigma = (float) (1.6 * pow(2, 1.0 / S) * pow(2, o + (double) sn / S)), angle = theta: the [n][4] frames
+ *               msfm_descset_describe takes.  ONE DEPARTURE from the reference: the descriptor of such a frame is the one of the
+ *               section above, with (o, is) derived from sigma by its frame rule, not the detection's (o, is); so extract equals
+ *               detect followed by describe bit for bit and there is one descriptor definition.
+ *   order       frames are ordered by ascending (o, is, iy, ix) of the cell the extremum was DETECTED in, then by ascending
+ *               bin; two extrema that refine to the same place both stay.  Positions come from a scan over the extremum masks
+ *               and ordered compaction, never from the arrival order of an atomic.
+ *   capacity    max_frames in [0, 65535] (what one describe call takes).  n_found counts every frame; when it exceeds max_frames
+ *               the first max_frames in the order above are returned.  The candidate buffers are sized from a count pass with
+ *               one host wait; no buffer is sized by a guess.
+ * msfm_scalespace_detect: frames_out [max_frames][4] receives *n_out = min(n_found, max_frames) frames.  It waits three times: for
+ * the candidate count, for the raw keypoints (the host step above, which also compacts the accepted ones in order and counts the
+ * rejections), for the angles.  stats (optional) [MSFM_SIFT_DETECT_STATS]: 0 candidates; rejected by 1 peak, 2 edge, 3 negative
+ * score, 4 offset, 5 bounds; 6 keypoints; 7 n_found; 8 .. 12 keypoints with 0 .. 4 angles; 13 keypoints that moved; 14 keypoints
+ * unconverged; 15 host waits; 16 bytes to the device; 17 bytes from the device.
+ * msfm_descset_extract: that detection, then its frames through msfm_descset_describe's own route into the image of the set; stats
+ * as above with describe's waits and bytes added.
+ * MSFM_E_INVAL, found before the first write, set and scale space stay usable: a NULL pointer (stats may be NULL), a non-finite or
+ * negative threshold, max_frames outside [0, 65535], an image outside the set, set and scale space of different contexts. */
+#define MSFM_SIFT_DETECT_STATS 18
+int msfm_scalespace_detect(const msfm_scalespace* ss, float peak_thresh /* 0 */, float edge_thresh /* 10 */, int max_frames,
+                           float* frames_out /*[max_frames][4]*/, int* n_out, int64_t* stats /*[MSFM_SIFT_DETECT_STATS]*/);
+int msfm_descset_extract(msfm_descset* set, int image, const msfm_scalespace* ss, float peak_thresh, float edge_thresh, int max_frames,
+                         int quantize, int64_t* stats /*[MSFM_SIFT_DETECT_STATS]*/);
 
 /* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search

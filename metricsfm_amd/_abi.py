@@ -204,6 +204,14 @@ class KernelStat(C.Structure):
 
 
 ITER_DTYPE = np.dtype(BaIteration)
+# the entries of msfm_scalespace_detect's stats [MSFM_SIFT_DETECT_STATS] (include/msfm.h), in its order
+SIFT_DETECT_STATS = ("candidates", "rejected_peak", "rejected_edge", "rejected_negative", "rejected_offset", "rejected_bounds", "keypoints",
+                     "n_found", "angles_0", "angles_1", "angles_2", "angles_3", "angles_4", "moved", "unconverged", "host_waits", "h2d_bytes",
+                     "d2h_bytes")
+
+
+def sift_detect_stats(values):
+    return dict(zip(SIFT_DETECT_STATS, (int(v) for v in values)))
 
 
 def ptr(a, typ):

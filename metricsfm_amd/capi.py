@@ -803,6 +803,16 @@ class DescSet(_Handle):
         self.counts[image] = len(fr)
         return hb.value
 
+    def extract(self, image, ss, peak_thresh=0.0, edge_thresh=10.0, max_frames=65535, quantize=False):
+        """msfm_descset_extract: the keypoints `ss.detect` finds, described into the image of this set without leaving the device
+        (the frames alone pass through the host).  -> the stats dict of `ScaleSpace.detect`, describe's waits and bytes added."""
+        st = np.zeros(len(A.SIFT_DETECT_STATS), np.int64)
+        self.ctx.check(lib().msfm_descset_extract(self._h, int(image), ss._h, float(peak_thresh), float(edge_thresh), int(max_frames),
+                                                  int(bool(quantize)), A.ptr(st, C.POINTER(C.c_int64))))
+        st = A.sift_detect_stats(st)
+        self.counts[image] = min(st["n_found"], int(max_frames))
+        return st
+
     def fetch(self, image):
         """msfm_descset_fetch -> (rows [count][128], xy [count][2] or None for an image without keypoints): what
         featurefiles.write_feature takes."""
@@ -851,6 +861,15 @@ class ScaleSpace(_Handle):
         w, h, hb = C.c_int32(), C.c_int32(), C.c_int64()
         self.ctx.check(lib().msfm_scalespace_size(self._h, int(octave), C.byref(w), C.byref(h), C.byref(hb)))
         return dict(w=w.value, h=h.value, h2d_bytes=hb.value)
+
+    def detect(self, peak_thresh=0.0, edge_thresh=10.0, max_frames=65535):
+        """msfm_scalespace_detect: the DoG extrema of every octave, refined, with their orientations.
+        -> (frames [n][4] float32 (x, y, sigma, angle) as `DescSet.describe` takes them, the stats dict: `A.SIFT_DETECT_STATS`)"""
+        frames = np.zeros((max(int(max_frames), 0), 4), np.float32)
+        n, st = C.c_int32(), np.zeros(len(A.SIFT_DETECT_STATS), np.int64)
+        self.ctx.check(lib().msfm_scalespace_detect(self._h, float(peak_thresh), float(edge_thresh), int(max_frames), A.ptr(frames, A.c_float_p),
+                                                    C.byref(n), A.ptr(st, C.POINTER(C.c_int64))))
+        return frames[:n.value].copy(), A.sift_detect_stats(st)
 
     def _fetch(self, octave, level, kind):
         z = self.size(octave)

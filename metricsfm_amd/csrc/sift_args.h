@@ -97,3 +97,71 @@ static inline std::string sift_frames(const float* frames, int n, int O, int S, 
   }
   return "";
 }
+
+// ---- the detector (include/msfm.h, "Detecting SIFT keypoints") ----
+#define SIFT_ORI_BINS 36
+#define SIFT_MAX_ANGLES 4
+#define SIFT_DETECT_STATS 18
+enum {   // indices of msfm_scalespace_detect's stats
+  SIFT_ST_CAND = 0, SIFT_ST_REJ_PEAK, SIFT_ST_REJ_EDGE, SIFT_ST_REJ_NEG, SIFT_ST_REJ_OFFSET, SIFT_ST_REJ_BOUNDS, SIFT_ST_KEYPOINTS, SIFT_ST_FOUND,
+  SIFT_ST_ANGLES0, SIFT_ST_MOVED = SIFT_ST_ANGLES0 + SIFT_MAX_ANGLES + 1, SIFT_ST_UNCONVERGED, SIFT_ST_WAITS, SIFT_ST_H2D, SIFT_ST_D2H
+};
+enum { SIFT_KP_STATUS = 15, SIFT_KP_MOVED = 16, SIFT_KP_UNCONVERGED = 32 };   // SiftRawKp.flags: the rejecting rule (0: accepted) and two bits
+
+struct SiftRawKp {   // what the refinement leaves per candidate
+  int o, ix, iy, is;
+  float xn, yn, sn;
+  int flags;
+};
+
+struct SiftOrientIn {   // what the orientation kernel reads per keypoint: the raw keypoint's place and the host's sigmaw
+  int o, is;
+  float xn, yn, sigmaw;
+};
+
+static inline std::string sift_check_detect(float peak_thresh, float edge_thresh, int max_frames) {
+  if (!std::isfinite(peak_thresh) || peak_thresh < 0.f) return "peak_thresh is negative or not finite";
+  if (!std::isfinite(edge_thresh) || edge_thresh < 0.f) return "edge_thresh is negative or not finite";
+  if (max_frames < 0 || max_frames > SIFT_MAX_FRAMES) return sift_fmt("max_frames = %ld outside [0, %ld]", max_frames, SIFT_MAX_FRAMES);
+  return "";
+}
+
+static inline float sift_edge_bound(float edge_thresh) {
+  const double e = (double)edge_thresh;
+  return (float)((e + 1) * (e + 1) / e);
+}
+
+static inline float sift_sigmaw(int S, float sn) { return (float)(1.5 * sift_sigma0(S) * std::pow(2.0, (double)sn / S)); }
+
+static inline float sift_frame_sigma(int S, int o, float sn) { return (float)(1.6 * std::pow(2.0, 1.0 / S) * std::pow(2.0, o + (double)sn / S)); }
+
+// raw keypoints [n] (the refinement's, every candidate in order) -> the counters of the rejections and the accepted ones in order
+static inline void sift_collect(const std::vector<SiftRawKp>& raw, int S, int64_t* st, std::vector<int>* kept, std::vector<SiftOrientIn>* in) {
+  st[SIFT_ST_CAND] = (int64_t)raw.size();
+  for (size_t c = 0; c < raw.size(); c++) {
+    const SiftRawKp& r = raw[c];
+    const int status = r.flags & SIFT_KP_STATUS;
+    if (status) { st[SIFT_ST_REJ_PEAK + status - 1]++; continue; }
+    st[SIFT_ST_KEYPOINTS]++;
+    if (r.flags & SIFT_KP_MOVED) st[SIFT_ST_MOVED]++;
+    if (r.flags & SIFT_KP_UNCONVERGED) st[SIFT_ST_UNCONVERGED]++;
+    kept->push_back((int)c);
+    in->push_back(SiftOrientIn{r.o, r.is, r.xn, r.yn, sift_sigmaw(S, r.sn)});
+  }
+}
+
+// the frames [n_found][4] of the kept raw keypoints and their angles, in order; n_found is also counted into st
+static inline void sift_make_frames(const std::vector<SiftRawKp>& raw, const std::vector<int>& kept, const int* nang, const float* theta, int S,
+                                    int64_t* st, std::vector<float>* frames) {
+  for (size_t k = 0; k < kept.size(); k++) {
+    const SiftRawKp& r = raw[kept[k]];
+    const int na = std::min(std::max(nang[k], 0), SIFT_MAX_ANGLES);
+    st[SIFT_ST_ANGLES0 + na]++;
+    st[SIFT_ST_FOUND] += na;
+    const float sc = (float)(1 << r.o), sigma = sift_frame_sigma(S, r.o, r.sn);
+    for (int a = 0; a < na; a++) {
+      const float f[4] = {r.xn * sc, r.yn * sc, sigma, theta[SIFT_MAX_ANGLES * k + a]};
+      frames->insert(frames->end(), f, f + 4);
+    }
+  }
+}
