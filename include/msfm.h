@@ -1012,6 +1012,73 @@ int msfm_descset_extract(msfm_descset* set, int image, const msfm_scalespace* ss
                          int quantize, int64_t* stats /*[MSFM_SIFT_DETECT_STATS]*/);
 
 /* ======================================================================================
+ *  Dense stereo: census, eight-path semi-global matching, disparity to depth
+ * ====================================================================================== */
+/* DenseReconstruction::SGMDense (SfM/src/dense_reconstruction.cc:113-190): sgm::StereoSGM::execute of libSGM
+ * (SfM/src/dense/cudasgm) on a rectified pair of uint8 images, width x height, each with its own stride, and the disparity turned
+ * into a depth image.  D = disp_size is 64 or 128; the reference's call (dense_reconstruction.cc:154-155, basic_structs.h:240-241)
+ * is P1 = 10, P2 = 120, uniqueness 0.96, D = 128, 8-bit input, 8-bit output, no subpixel.  THE DEFINITIONS BELOW ARE RESTATED FROM
+ * READING libSGM's sources; every kept behaviour cites its file and line; no build of those sources has been run against them.
+ * The arithmetic is integer but for one binary32 product, nothing depends on the device's scheduling, and tests/sgm_ref.cpp
+ * restates what follows sequentially: the device equals it byte for byte in every plane msfm_sgm_fetch returns.
+ *   census      uint32, for the left and the right image (census_transform.cu:31-119, the 9 x 7 symmetric form).  For a pixel with
+ *               4 <= x < width - 4 and 3 <= y < height - 3 the value has 31 bits: from f = 0, first for dy = -3, -2, -1 and inside
+ *               it dx = -4 .. 4, then for dy = 0 and dx = -4 .. -1:  f = (f << 1) | (I(x + dx, y + dy) > I(x - dx, y - dy)).
+ *               Every other pixel has census 0.  DEPARTURE 1: the reference never writes these border features and leaves the
+ *               buffer as it came from the allocator.
+ *   cost        C(x, y, d) = popcount(census_L(x, y) ^ census_R(x - d, y)), d = 0 .. D - 1; census_R is 0 where x - d < 0.
+ *   paths       eight, r = 0 (+1, 0), 1 (-1, 0), 2 (0, +1), 3 (0, -1), 4 (+1, +1), 5 (-1, +1), 6 (-1, -1), 7 (+1, -1)
+ *               (path_aggregation.cu).  With q = p - r: if q is outside the image, L_r(p, d) = C(p, d); otherwise, with
+ *               m = min_e L_r(q, e):  L_r(p, d) = C(p, d) + min(L_r(q, d) - m, L_r(q, d - 1) - m + P1, L_r(q, d + 1) - m + P1, P2),
+ *               the d - 1 and d + 1 terms only inside [0, D) (path_aggregation_common.hpp:47-89).  Unsigned 32-bit inside the
+ *               recurrence, stored as one byte: L <= 31 + P2.  DEPARTURE 2: P2 > 224, P1 > P2 or a negative value is
+ *               MSFM_E_INVAL; the reference would silently truncate to 8 bits.
+ *   sum         S(x, y, d) = the sum of L_r over the eight paths, uint16.
+ *   left        among key(d) = (S(x, y, d) << 16) | d the two smallest keys k0 < k1, so equal costs go to the lower disparity
+ *               (winner_takes_all.cu:100-113, :139-227).  c0 = k0 >> 16, d0 = k0 & 0xffff, c1, d1 likewise.  float(c1) * uniqueness
+ *               is one binary32 multiplication.  dispL = d0 if that product is >= float(c0); otherwise d0 if |d1 - d0| <= 1;
+ *               otherwise 0.
+ *   right       for the right pixel p the same rule on the keys (S(p + d, y, d) << 16) | d over d = 0 .. min(D - 1, width - 1 - p);
+ *               with a single candidate the second key is 0xffffffff (winner_takes_all.cu:228-261).  DEPARTURE 3: width < D is
+ *               MSFM_E_INVAL; the reference's final flush writes in front of the row there.
+ *   median      of both disparity planes, uint16: for 1 <= x <= width - 2 and 1 <= y <= height - 2 the median of the 3 x 3
+ *               neighbourhood; every other pixel is 0 (median_filter.cu:111-125: the output buffer is zeroed once and never written there).
+ *   consistency on the median-filtered left plane, only for x < 16 * (width / 16) and y < 16 * (height / 16) (integer division:
+ *               the reference's launch grid, check_consistency.cu:61, KEPT AS A QUIRK; pixels outside it keep the median's value).
+ *               With d the left value and k = x - d the value becomes 0 when I_L(x, y) == 0, or d <= 0, or 0 <= k < width and
+ *               |R_med(k, y) - d| > 1 (check_consistency.cu:22-35).  A k < 0 does not invalidate.
+ *   output      the final left plane cast to uint8 (values < D <= 128).
+ *   depth       dense_reconstruction.cc:160-181.  Per pixel with disp != 0: t = ((200.0 * baseline) * focal) / double(disp) in
+ *               binary64; depth = t > 255 || t < 0 ? 0 : (uint8) t by truncation; disp == 0 gives 0.  The 128 values are made
+ *               on the host (the division is the host's) and applied to the final plane as a table.
+ * NOT BUILT: 16-bit input; the subpixel arm (its 16-bit median in the reference truncates columns to 8 bits, which would need a
+ * ruling of its own); EpipolarRectification (OpenCV's stereoRectify + remap, parity unpinned); ELASDense; Depth2Points; a C++
+ * host mirror; a multi-GPU form.
+ * msfm_sgm is a child of its context like msfm_scalespace.  It owns all its device planes for its lifetime - two images, two
+ * census planes, eight cost volumes [h][w][D] of uint8, four uint16 planes, the uint8 result - and is reused pair after pair, as the
+ * reference reuses a StereoSGM.  MSFM_E_NOMEM when the planes do not fit (4 000 x 3 000 at D = 128: 11.5 GB of cost volumes).
+ * msfm_sgm_execute copies the pair into pinned staging of the object, uploads it and enqueues everything on the context's stream;
+ * it does NOT wait, and the caller's buffers are free on return.  A second execute replaces the first's result.
+ * stats (optional) [MSFM_SGM_STATS]: 0 host waits (0, unless the caller is two executes ahead of the device and the staging
+ * slot's copy has not run), 1 bytes to the device, 2 kernel launches.
+ * msfm_sgm_fetch waits and copies one plane, [h][w] of: kind 0 / 1 census L / R (uint32); 2 the cost volume of path `index`
+ * (uint8 [h][w][D]); 3 / 4 raw left / right disparity (uint16); 5 / 6 median-filtered left / right (uint16); 7 final left (uint8).
+ * index is 0 for every kind but 2.  msfm_sgm_depth waits and writes the depth of the final plane.
+ * MSFM_E_INVAL before any write, with the object still usable: a NULL pointer (stats may be NULL); disp_size not 64 or 128;
+ * width < disp_size or > 16384; height < 1 or > 16384; stride < width; the parameter rules above; uniqueness non-finite or outside
+ * [0, 1]; a fetch kind or index out of range; a non-finite baseline or focal; a fetch or depth before the first execute. */
+#define MSFM_SGM_STATS 3
+typedef struct msfm_sgm msfm_sgm;
+int msfm_sgm_create(msfm_ctx* ctx, int width, int height, int disp_size /* 128 */, int p1 /* 10 */, int p2 /* 120 */,
+                    float uniqueness /* 0.96 */, msfm_sgm** out);
+int msfm_sgm_execute(msfm_sgm* sgm, const uint8_t* left, int left_stride, const uint8_t* right, int right_stride,
+                     int64_t* stats /*[MSFM_SGM_STATS]*/);
+int msfm_sgm_fetch(const msfm_sgm* sgm, int kind, int index, void* out);
+int msfm_sgm_depth(const msfm_sgm* sgm, double baseline, double focal, uint8_t* depth_out /*[h][w]*/);
+int msfm_sgm_size(const msfm_sgm* sgm, int* width, int* height, int* disp_size, int64_t* device_bytes);
+void msfm_sgm_destroy(msfm_sgm* sgm);
+
+/* ======================================================================================
  *  Which image to localise next: the batched 2D-3D correspondence search
  * ====================================================================================== */
 /* A resident copy of the verified matches, so that the search below moves no match over PCIe per round (the reference

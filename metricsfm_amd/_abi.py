@@ -214,6 +214,19 @@ def sift_detect_stats(values):
     return dict(zip(SIFT_DETECT_STATS, (int(v) for v in values)))
 
 
+# the entries of msfm_sgm_execute's stats [MSFM_SGM_STATS] (include/msfm.h), in its order
+SGM_STATS = ("host_waits", "h2d_bytes", "kernel_launches")
+# msfm_sgm_fetch: kind -> (name, dtype of a pixel); kind 2 is [h][w][D], every other kind [h][w]
+SGM_FETCH = ((0, "census_left", np.uint32), (1, "census_right", np.uint32), (2, "path_cost", np.uint8), (3, "raw_left", np.uint16),
+             (4, "raw_right", np.uint16), (5, "median_left", np.uint16), (6, "median_right", np.uint16), (7, "disparity", np.uint8))
+# the launch constants of metricsfm_amd/csrc/sgm_args.h the tests derive their shapes from
+SGM_LANE_DISP, SGM_PATH_THREADS, SGM_WTA_TILE = 8, 256, 64
+
+
+def sgm_stats(values):
+    return dict(zip(SGM_STATS, (int(v) for v in values)))
+
+
 def ptr(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 

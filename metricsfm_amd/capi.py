@@ -402,6 +402,11 @@ class Context(_Handle):
         stride (>= w) hands the image over in a buffer of that many bytes per row."""
         return ScaleSpace(self, gray, n_octaves, n_levels, stride)
 
+    def stereo_sgm(self, width, height, disp_size=128, p1=10, p2=120, uniqueness=0.96):
+        """msfm_sgm_create: a dense-stereo object for rectified uint8 pairs of width x height, resident as a `StereoSGM` and reused
+        pair after pair; the defaults are the reference's call."""
+        return StereoSGM(self, width, height, disp_size, p1, p2, uniqueness)
+
     def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
         """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
         as a `Recon`; cam_pose / cam_model / cam_model_of_cam are the solver's parameter blocks as `adjust.adjust_round` takes
@@ -884,6 +889,68 @@ class ScaleSpace(_Handle):
     def gradient(self, octave, level):
         """-> (modulus, angle) of level `level` in [0, S - 1] of an octave."""
         return self._fetch(octave, level, 1), self._fetch(octave, level, 2)
+
+
+class StereoSGM(_Handle):
+    """msfm_sgm: census, eight-path semi-global matching and the left disparity of a rectified pair (include/msfm.h, "Dense stereo",
+    states the definitions).  It owns its device planes; `execute` replaces the result of the one before."""
+    _destroy = "msfm_sgm_destroy"
+
+    def __init__(self, ctx: Context, width, height, disp_size=128, p1=10, p2=120, uniqueness=0.96):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        self.stats = None
+        ctx.check(lib().msfm_sgm_create(ctx._h, int(width), int(height), int(disp_size), int(p1), int(p2), float(uniqueness), C.byref(self._h)))
+        self.width, self.height, self.disp_size = int(width), int(height), int(disp_size)
+
+    @staticmethod
+    def _image(a, name):
+        """-> (the array whose buffer is handed over, its stride in bytes): uint8 [h][w], rows contiguous, any row stride"""
+        a = np.asarray(a)
+        if a.dtype != np.uint8 or a.ndim != 2:
+            raise ValueError("%s must be uint8 [h][w]" % name)
+        if a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+            a = np.ascontiguousarray(a)
+        return a, a.strides[0]
+
+    def execute(self, left, right):
+        """msfm_sgm_execute: uploads the pair and enqueues the whole chain without waiting.  -> the stats dict (`A.SGM_STATS`),
+        also kept as `self.stats`.  A view with a row stride (a[:, :w] of a wider array) is handed over as it is."""
+        (l, ls), (r, rs) = self._image(left, "left"), self._image(right, "right")
+        if l.shape != (self.height, self.width) or r.shape != l.shape:
+            raise ValueError("the pair must be two images of %d x %d" % (self.width, self.height))
+        st = np.zeros(len(A.SGM_STATS), np.int64)
+        self.ctx.check(lib().msfm_sgm_execute(self._h, C.cast(l.ctypes.data, A.c_u8_p), int(ls), C.cast(r.ctypes.data, A.c_u8_p), int(rs),
+                                              A.ptr(st, C.POINTER(C.c_int64))))
+        self.stats = A.sgm_stats(st)
+        return self.stats
+
+    def fetch(self, kind, index=0):
+        """msfm_sgm_fetch: waits and returns one plane (`A.SGM_FETCH`): [h][w], the cost volume of path `index` [h][w][D] for kind 2."""
+        dt = {k: d for k, _, d in A.SGM_FETCH}.get(int(kind), np.uint8)
+        out = np.zeros((self.height, self.width, self.disp_size) if int(kind) == 2 else (self.height, self.width), dt)
+        self.ctx.check(lib().msfm_sgm_fetch(self._h, int(kind), int(index), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def disparity(self):
+        """The final left disparity, uint8 [h][w] (0: invalid)."""
+        return self.fetch(7)
+
+    def right_disparity(self):
+        """The median-filtered right disparity, uint16 [h][w]."""
+        return self.fetch(6)
+
+    def depth(self, baseline, focal):
+        """msfm_sgm_depth: the depth image of the final disparity, uint8 [h][w]."""
+        out = np.zeros((self.height, self.width), np.uint8)
+        self.ctx.check(lib().msfm_sgm_depth(self._h, float(baseline), float(focal), A.ptr(out, A.c_u8_p)))
+        return out
+
+    def size(self):
+        """-> dict(width, height, disp_size, device_bytes)"""
+        w, h, d, b = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx.check(lib().msfm_sgm_size(self._h, C.byref(w), C.byref(h), C.byref(d), C.byref(b)))
+        return dict(width=w.value, height=h.value, disp_size=d.value, device_bytes=b.value)
 
 
 class MatchResult(_Handle):
