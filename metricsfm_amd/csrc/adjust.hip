@@ -27,9 +27,7 @@
 #include <memory>
 #include <numeric>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 #pragma clang fp contract(off)
 #include "point3d_device.h"   // p3d_row_error, p3d_ordered_mse
@@ -311,7 +309,7 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   DevBuf<double> d_cam;
   DevBuf<uint8_t> d_free, d_call, d_first, d_att, d_freed, d_mut;
   DevBuf<unsigned long long> d_key, d_key_s;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
   AJ_TRY(sc.up(d_fo, cam_fo.data(), (size_t)nc + 1));
   AJ_TRY(sc.up(d_rank, T.rank.data(), (size_t)nc)); AJ_TRY(sc.up(d_cor, T.cam_of_rank.data(), (size_t)nc)); AJ_TRY(sc.up(d_kpb, T.kp_base.data(), (size_t)nc));
@@ -325,15 +323,6 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   AJ_TRY(d_key.alloc(std::max<size_t>(1, nox))); AJ_TRY(d_key_s.alloc(std::max<size_t>(1, nox))); AJ_TRY(d_first.alloc(std::max<size_t>(1, nox)));
   AJ_TRY(d_views.alloc(npx + 1)); AJ_TRY(d_seg.alloc(npx + 2));
   AJ_TRY(d_att.alloc(std::max<size_t>(1, npx))); AJ_TRY(d_freed.alloc(std::max<size_t>(1, npx))); AJ_TRY(d_mut.alloc(std::max<size_t>(1, npx)));
-  {   // one scratch block for the sort and the scans, sized before anything is enqueued that uses it
-    size_t b_sort = 0, b_row = 0, b_pt = 0;
-    if (no) AJ_TRY(rocprim::radix_sort_keys(nullptr, b_sort, d_key.p, d_key_s.p, nox, 0u, 32u + (unsigned)bits_for((unsigned)np), s));
-    if (solve) {
-      AJ_TRY(rocprim::exclusive_scan(nullptr, b_row, (const int*)nullptr, (int*)nullptr, 0, nox + 1, rocprim::plus<int>(), s));
-      AJ_TRY(rocprim::exclusive_scan(nullptr, b_pt, (const int*)nullptr, (int*)nullptr, 0, npx + 1, rocprim::plus<int>(), s));
-    }
-    AJ_TRY(tmp.alloc(std::max<size_t>(1, std::max(b_sort, std::max(b_row, b_pt)))));
-  }
   AJ_TRY(hipMemsetAsync(d_views.p, 0, sizeof(int) * (npx + 1), s));
   AJ_TRY(hipMemsetAsync(d_seg.p, 0, sizeof(int) * (npx + 2), s));   // (n_obs = 0: every segment is empty)
   AJ_TRY(hipMemsetAsync(d_att.p, 0, std::max<size_t>(1, npx), s)); AJ_TRY(hipMemsetAsync(d_freed.p, 0, std::max<size_t>(1, npx), s));
@@ -347,11 +336,9 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   AJ_TRY(hipGetLastError());
   if (no) {
     const unsigned end_bit = 32u + (unsigned)bits_for((unsigned)np);
-    size_t bytes = 0;
-    AJ_TRY(rocprim::radix_sort_keys(nullptr, bytes, d_key.p, d_key_s.p, nox, 0u, end_bit, s));
     {
       KTimer tm(ctx, "round_sort");
-      AJ_TRY(rocprim::radix_sort_keys(tmp.p, bytes, d_key.p, d_key_s.p, nox, 0u, end_bit, s));
+      AJ_TRY(prim_sort_keys(tmp, d_key.p, d_key_s.p, nox, 0u, end_bit, s));
     }
     KTimer tm(ctx, "round_first");
     tm.count = 2;
@@ -386,13 +373,6 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
   if (solve) {
     AJ_TRY(keep_row.alloc(nox + 1)); AJ_TRY(keep_pt.alloc(npx + 1)); AJ_TRY(new_row.alloc(nox + 1)); AJ_TRY(new_pt.alloc(npx + 1));
   }
-  auto scan = [&](const int* in, int* o, size_t n) -> hipError_t {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, o, 0, n, rocprim::plus<int>(), s);
-    if (e != hipSuccess) return e;
-    if (tmp.n < bytes) return hipErrorOutOfMemory;   // (sized above for both scans)
-    return rocprim::exclusive_scan(tmp.p, bytes, in, o, 0, n, rocprim::plus<int>(), s);
-  };
   bool mut_done = false;
   for (int stage = 0; stage < 2; stage++) {
     if (!(stage == 0 ? A.do_partial : A.do_full)) continue;
@@ -408,8 +388,8 @@ int round_adjust_dev(msfm_ctx* ctx, const char* who, const RoundArgs& A, const R
                          keep_pt.p);
     }
     mut_done = true;
-    AJ_TRY(scan(keep_row.p, new_row.p, nox + 1));
-    AJ_TRY(scan(keep_pt.p, new_pt.p, npx + 1));
+    AJ_TRY(prim_scan_excl(tmp, keep_row.p, new_row.p, nox + 1, s));
+    AJ_TRY(prim_scan_excl(tmp, keep_pt.p, new_pt.p, npx + 1, s));
     int npk = 0, nok = 0, free_pts = 0;
     AJ_TRY(hipMemcpyAsync(&nok, new_row.p + no, sizeof(int), hipMemcpyDeviceToHost, s));
     AJ_TRY(hipMemcpyAsync(&npk, new_pt.p + np, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -23,11 +23,9 @@
 #include <cstring>
 #include <functional>
 
-#include <rocprim/rocprim.hpp>
-
 #include "ba_device.h"
 #include "ba_partials.h"
-#include "common.h"
+#include "prim_device.h"
 #include "solve_riders.h"
 
 
@@ -2412,28 +2410,15 @@ __global__ __launch_bounds__(1024) void k_scan_small(const T* __restrict__ in, T
 }
 #define MSFM_SCAN_SMALL_MAX 65536
 template <class T>
-static hipError_t excl_scan(const T* in, T* out, size_t n, hipStream_t s, DevBuf<char>& tmp) {
+static hipError_t excl_scan(const T* in, T* out, size_t n, hipStream_t s, PrimTmp& tmp) {
   if (n == 0) return hipSuccess;
   if (n <= MSFM_SCAN_SMALL_MAX && in != out) {
     hipLaunchKernelGGL((k_scan_small<T>), dim3(1), dim3(1024), 0, s, in, out, (int)n);
     return hipGetLastError();
   }
-  size_t bytes = 0;
-  hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), s);
-  if (e != hipSuccess) return e;
-  if (tmp.n < bytes) { e = tmp.alloc(bytes); if (e != hipSuccess) return e; }
-  return rocprim::exclusive_scan(tmp.p, bytes, in, out, T(0), n, rocprim::plus<T>(), s);
+  return prim_scan_excl(tmp, in, out, n, s);
 }
-template <class K>
-static hipError_t sort_pairs(const K* kin, K* kout, const int* vin, int* vout, size_t n, int bits, hipStream_t s, DevBuf<char>& tmp) {
-  if (n == 0) return hipSuccess;
-  size_t bytes = 0;
-  hipError_t e = rocprim::radix_sort_pairs(nullptr, bytes, kin, kout, vin, vout, n, 0, bits, s);
-  if (e != hipSuccess) return e;
-  if (tmp.n < bytes) { e = tmp.alloc(bytes); if (e != hipSuccess) return e; }
-  return rocprim::radix_sort_pairs(tmp.p, bytes, kin, kout, vin, vout, n, 0, bits, s);   // stable
-}
-static int bits_for(long n) { int b = 1; while ((1L << b) < n) b++; return b; }
+static int bits_below(long n) { int b = 1; while ((1L << b) < n) b++; return b; }   // the smallest b >= 1 with 2^b >= n: bits that hold 0 .. n - 1
 
 __device__ __forceinline__ bool dmut(const uint8_t* m, int i) { return m == nullptr || m[i] != 0; }
 
@@ -2743,12 +2728,12 @@ __global__ __launch_bounds__(256) void k_block_lists(long nkey, long ncol, const
 // new camera - are a few dozen short launches each, and nine stream synchronisations were a third of its set-up.
 template <int KIND>
 struct PairBuild {
-  msfm_ctx* ctx; msfm_ba* ba; PairJobs& J; int nout; const int *d_pt_first, *d_pm_first, *d_pm_mb; DevBuf<char>& tmp; bool want_host_blocks;
+  msfm_ctx* ctx; msfm_ba* ba; PairJobs& J; int nout; const int *d_pt_first, *d_pm_first, *d_pm_mb; PrimTmp& tmp; bool want_host_blocks;
   long nrow = 0, ncol = 0, nkey = 0;
   DevBuf<int> count, offset, key, pa, pbv, key_hist, key_sorted, perm, perm_sorted, key_first, flag, nchunk, blk_of_key, chunk_first;
   int total = 0, nbc[2] = {0, 0}, chunk = 0;
   bool empty = false;
-  PairBuild(msfm_ctx* c, msfm_ba* b, PairJobs& j, int no, const int* pf, const int* pmf, const int* pmm, DevBuf<char>& t, bool w)
+  PairBuild(msfm_ctx* c, msfm_ba* b, PairJobs& j, int no, const int* pf, const int* pmf, const int* pmm, PrimTmp& t, bool w)
       : ctx(c), ba(b), J(j), nout(no), d_pt_first(pf), d_pm_first(pmf), d_pm_mb(pmm), tmp(t), want_host_blocks(w) {}
   // entries per point, their offsets; asks for the total
   int phase1() {
@@ -2792,7 +2777,7 @@ struct PairBuild {
     if (total) {
       DTRY(perm.alloc(nt)); DTRY(perm_sorted.alloc(nt));
       hipLaunchKernelGGL(k_iota, dim3(cdiv(total, 256)), dim3(256), 0, s, total, perm.p);
-      DTRY(sort_pairs(key.p, key_sorted.p, perm.p, perm_sorted.p, (size_t)total, bits_for(nkey), s, tmp));
+      DTRY(prim_sort_pairs(tmp, key.p, key_sorted.p, perm.p, perm_sorted.p, (size_t)total, 0, bits_below(nkey), s));   // stable
       hipLaunchKernelGGL(k_gather2, dim3(cdiv(total, 256)), dim3(256), 0, s, total, perm_sorted.p, pa.p, pbv.p, J.pa.p, J.pb.p);
     }
     hipLaunchKernelGGL(k_key_first, dim3(cdiv(nkey + 1, 256)), dim3(256), 0, s, nkey, total, key_sorted.p, key_first.p);
@@ -3106,7 +3091,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   //  MSFM_FOLD_MIN overrides the threshold, e.g. 0 to fold everything in a test)
   if (ba->env.no_fold || npb == 0 || ncb == 0 || ba->cc.n_pairs == 0 || ba->cc.n_pairs < ba->env.fold_min || (long)ncb * (ncb + 1) > 0x7fffffffL) return MSFM_OK;
   hipStream_t s = ctx->stream;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevBuf<int> count, offset, head, slot_of, slot_id, slot_id_s, slot_ent_first, wg_slot_first, perm, slot_quad;
   DevBuf<unsigned long long> key, key_s, slot_key2, slot_key2_s;
   DevBuf<unsigned> val, ent_sorted;
@@ -3129,11 +3114,8 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
   hipLaunchKernelGGL((k_fold_entries<true>), dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ncb, ba->map, ba->pt_first.p, ba->o_cb.p, ba->o_cpos.p, F.wg_fold.p,
                      (int*)nullptr, offset.p, key.p, val.p);
   {
-    size_t bytes = 0;
-    const int bits = 32 + bits_for((long)std::max(2, n_wg));
-    DTRY(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));
-    if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
-    DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));   // stable: point order inside a slot
+    const int bits = 32 + bits_below((long)std::max(2, n_wg));
+    DTRY(prim_sort_pairs(tmp, key.p, key_s.p, val.p, ent_sorted.p, (size_t)E, 0, bits, s));   // stable: point order inside a slot
   }
   DTRY(head.alloc((size_t)E + 1)); DTRY(slot_of.alloc((size_t)E + 1));
   DTRY(hipMemsetAsync(head.p + E, 0, sizeof(int), s));
@@ -3154,11 +3136,8 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DevScope blk(ctx);
     DTRY(pk.alloc(NS)); DTRY(pk_s.alloc(NS)); DTRY(pid.alloc(NS)); DTRY(perm.alloc(NS));
     hipLaunchKernelGGL(k_fold_perm_key, dim3(cdiv(NS, 256)), dim3(256), 0, s, NS, ncb, slot_key2.p, slot_ent_first.p, wg_slot_first.p, pk.p, pid.p);
-    size_t bytes = 0;
-    const int bits = 32 + bits_for((long)std::max(2, n_wg));
-    DTRY(rocprim::radix_sort_pairs(nullptr, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
-    if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
-    DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
+    const int bits = 32 + bits_below((long)std::max(2, n_wg));
+    DTRY(prim_sort_pairs(tmp, pk.p, pk_s.p, pid.p, perm.p, (size_t)NS, 0, bits, s));
     DTRY(blk.finish());
   }
   int nquads = 0;
@@ -3201,12 +3180,7 @@ static int build_fold_device(msfm_ctx* ctx, msfm_ba* ba) {
     DTRY(blk.finish());
     F.n_parts = (long long)h_stats[0]; F.crit_steps = (long long)h_stats[1]; F.crit_steps_unsplit = (long long)h_stats[2]; F.wave_steps = (long long)h_stats[3];
   }
-  {
-    size_t bytes = 0;
-    DTRY(rocprim::radix_sort_pairs(nullptr, bytes, slot_key2.p, slot_key2_s.p, slot_id.p, slot_id_s.p, (size_t)NS, 0, 64, s));
-    if (tmp.n < bytes) DTRY(tmp.alloc(bytes));
-    DTRY(rocprim::radix_sort_pairs(tmp.p, bytes, slot_key2.p, slot_key2_s.p, slot_id.p, slot_id_s.p, (size_t)NS, 0, 64, s));
-  }
+  DTRY(prim_sort_pairs(tmp, slot_key2.p, slot_key2_s.p, slot_id.p, slot_id_s.p, (size_t)NS, 0, 64, s));
   {
     DevBuf<int> rank;   // by slot; k_point asks by quad inside the workgroup's passes
     DevScope blk(ctx);
@@ -3403,7 +3377,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     return hipMemcpyAsync(dst, src, bytes, bulk_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
   };
   const int Nc = ba->Nc = P->n_cams, Nm = ba->Nm = P->n_models, Np = ba->Np = P->n_points, No = P->n_obs;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevBuf<int> d_obs_cam, d_obs_pt, d_model_of_cam, d_cnt, d_run_first, d_err, d_cam_slot, d_model_slot, d_fflag, d_fpos, d_cam_hist, d_cam_first, d_pm_count;
   DevBuf<int> d_pu_int, d_pu_pos, d_vals, d_vals_sorted, d_pt_slot, d_len, d_cls, d_cls_sorted, d_n_class;
   DevBuf<double> d_obs_xy, d_ptw;
@@ -3487,9 +3461,9 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
                        ncb >= 0xFFFF ? 1 : 0, d_keys.p, d_vals.p);
     DTRY(d_vals_sorted.alloc(npb)); DTRY(d_cls.alloc(npb)); DTRY(d_cls_sorted.alloc(npb)); DTRY(d_n_class.alloc(PTMAP_CLASSES));
     DTRY(hipMemsetAsync(d_n_class.p, 0, sizeof(int) * PTMAP_CLASSES, s));
-    DTRY(sort_pairs(d_keys.p, d_keys_sorted.p, d_vals.p, d_vals_sorted.p, (size_t)npb, 64, s, tmp));
+    DTRY(prim_sort_pairs(tmp, d_keys.p, d_keys_sorted.p, d_vals.p, d_vals_sorted.p, (size_t)npb, 0, 64, s));
     hipLaunchKernelGGL(k_point_classes, dim3(cdiv(npb, 256)), dim3(256), 0, s, npb, ptmap_use_lanes4(npb, ba->env.lanes4_min) ? 1 : 0, d_vals_sorted.p, d_cnt.p, d_cls.p, d_n_class.p);
-    DTRY(sort_pairs(d_cls.p, d_cls_sorted.p, d_vals_sorted.p, ba->pb_pt.p, (size_t)npb, 2, s, tmp));
+    DTRY(prim_sort_pairs(tmp, d_cls.p, d_cls_sorted.p, d_vals_sorted.p, ba->pb_pt.p, (size_t)npb, 0, 2, s));
     DTRY(hipMemcpyAsync(n_class, d_n_class.p, sizeof n_class, hipMemcpyDeviceToHost, s));   // (read with AE below)
   }
   DTRY(d_pt_slot.alloc((size_t)std::max(1, Np))); DTRY(d_len.alloc((size_t)npb + 1)); DTRY(ba->pt_first.alloc((size_t)npb + 1));
@@ -3540,7 +3514,7 @@ static int create_structures_device(msfm_ctx* ctx, const msfm_ba_problem* P, msf
     DevScope blk(ctx);
     DTRY(rk.alloc(A)); DTRY(rv.alloc(A)); DTRY(rks.alloc(A)); DTRY(rvs.alloc(A));
     hipLaunchKernelGGL(k_row_keys, dim3(cdiv(A, 256)), dim3(256), 0, s, A, ncb, ba->o_cb.p, rk.p, rv.p);
-    DTRY(sort_pairs(rk.p, rks.p, rv.p, rvs.p, (size_t)A, bits_for((long)ncb + 1), s, tmp));
+    DTRY(prim_sort_pairs(tmp, rk.p, rks.p, rv.p, rvs.p, (size_t)A, 0, bits_below((long)ncb + 1), s));
     hipLaunchKernelGGL(k_assign_positions, dim3(cdiv(NCR, 256)), dim3(256), 0, s, NCR, rks.p, rvs.p, ba->o_pb.p, ba->o_cpos.p, ba->cpos_pb.p);
     DTRY(blk.finish());   // the sort buffers go out of scope
   }

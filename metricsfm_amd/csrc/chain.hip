@@ -33,26 +33,10 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 #include "../../include/msfm.h"
 
 namespace chn {
-
-// exclusive position of a set flag among the flags of the workgroup (256 threads), and the workgroup's total
-__device__ __forceinline__ int block_rank(bool f, int* wave_tot /*[4] LDS*/, int& total) {
-  const unsigned long long b = __ballot(f);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int within = __popcll(b & ((1ull << lane) - 1ull));
-  __syncthreads();   // (wave_tot is reused by consecutive calls)
-  if (lane == 0) wave_tot[wave] = __popcll(b);
-  __syncthreads();
-  int base = 0;
-  for (int w = 0; w < wave; w++) base += wave_tot[w];
-  total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-  return base + within;
-}
 
 struct PairSrc {
   const float* kp1;   // train image positions
@@ -79,14 +63,14 @@ __global__ __launch_bounds__(256) void k_gather_sets(const PairSrc* __restrict__
     float x1 = 0.f, y1 = 0.f, x2 = 0.f, y2 = 0.f;
     if (any) { x1 = S.kp1[2 * id]; y1 = S.kp1[2 * id + 1]; x2 = S.kp2[2 * m]; y2 = S.kp2[2 * m + 1]; }
     int tot;
-    const int rg = block_rank(good, wt, tot);
+    const int rg = wg_rank<4>(good, wt, tot);
     if (good) {
       const size_t e = (size_t)S.off_good + ng + rg;
       m_good[2 * e] = id; m_good[2 * e + 1] = m;
       g1[2 * e] = x1; g1[2 * e + 1] = y1; g2[2 * e] = x2; g2[2 * e + 1] = y2;
     }
     ng += tot;
-    const int ra = block_rank(all, wt, tot);
+    const int ra = wg_rank<4>(all, wt, tot);
     if (all) {
       const size_t e = (size_t)S.off_all + na + ra;
       m_all[2 * e] = id; m_all[2 * e + 1] = m;
@@ -112,7 +96,7 @@ __global__ __launch_bounds__(256) void k_gather_slam(const PairSrc* __restrict__
     const int32_t c = m < S.nq ? code[S.off + m] : -1;
     const bool any = c >= 0;
     int tot;
-    const int ra = block_rank(any, wt, tot);
+    const int ra = wg_rank<4>(any, wt, tot);
     if (any && na + ra < cap) {
       const int id = c & MSFM_MATCH_ID_MASK;
       const size_t e = (size_t)S.off_all + na + ra;
@@ -131,7 +115,7 @@ __global__ __launch_bounds__(256) void k_count_inliers(const int* __restrict__ o
   for (int i0 = b; i0 < e; i0 += 256) {
     const int i = i0 + threadIdx.x;
     int tot;
-    (void)block_rank(i < e && in_all[i] != 0, wt, tot);
+    (void)wg_rank<4>(i < e && in_all[i] != 0, wt, tot);
     n += tot;
   }
   if (threadIdx.x == 0) n_fin[blockIdx.x] = n;
@@ -147,7 +131,7 @@ __global__ __launch_bounds__(256) void k_compact_matches(const int* __restrict__
     const int i = i0 + threadIdx.x;
     const bool f = i < e && in_all[i] != 0;
     int tot;
-    const int r = block_rank(f, wt, tot);
+    const int r = wg_rank<4>(f, wt, tot);
     if (f) {
       const size_t o = (size_t)off_fin[blockIdx.x] + n + r;
       m_fin[2 * o] = m_all[2 * (size_t)i]; m_fin[2 * o + 1] = m_all[2 * (size_t)i + 1];
@@ -551,19 +535,12 @@ static int chain_ba_create(msfm_chain* C, int n_cams, int n_models, double* cam_
   const int nt = T.n_tracks;
   DevBuf<int> keep, keep_obs, new_pt, new_obs, obs_cam, obs_pt;
   DevBuf<double> obs_xy, point, ptw;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
   CH_TRY(keep.alloc((size_t)nt + 1)); CH_TRY(keep_obs.alloc((size_t)nt + 1)); CH_TRY(new_pt.alloc((size_t)nt + 1)); CH_TRY(new_obs.alloc((size_t)nt + 1));
   hipLaunchKernelGGL(chn::k_keep, dim3(cdiv(nt + 1, 256)), dim3(256), 0, s, nt, T.off.p, C->tok.p, min_views, keep.p, keep_obs.p);
-  auto scan = [&](const int* in, int* o, size_t n) -> hipError_t {
-    size_t bytes = 0;
-    hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, o, 0, n, rocprim::plus<int>(), s);
-    if (e != hipSuccess) return e;
-    if (tmp.n < bytes) { e = tmp.alloc(bytes); if (e != hipSuccess) return e; }
-    return rocprim::exclusive_scan(tmp.p, bytes, in, o, 0, n, rocprim::plus<int>(), s);
-  };
-  CH_TRY(scan(keep.p, new_pt.p, (size_t)nt + 1));
-  CH_TRY(scan(keep_obs.p, new_obs.p, (size_t)nt + 1));
+  CH_TRY(prim_scan_excl(tmp, keep.p, new_pt.p, (size_t)nt + 1, s));
+  CH_TRY(prim_scan_excl(tmp, keep_obs.p, new_obs.p, (size_t)nt + 1, s));
   int np = 0, no = 0;
   CH_TRY(hipMemcpyAsync(&np, new_pt.p + nt, sizeof(int), hipMemcpyDeviceToHost, s));
   CH_TRY(hipMemcpyAsync(&no, new_obs.p + nt, sizeof(int), hipMemcpyDeviceToHost, s));

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <functional>
 #include <initializer_list>
+#include <list>
 #include <string>
 #include <thread>
 #include <utility>
@@ -205,6 +206,23 @@ struct DevScope {
   void dismiss() { settled = true; }
 };
 
+// The temporary block of every rocPRIM call that one function enqueues.  A call that needs more than the block holds gets a
+// larger one, and the smaller one is retired: kept until the PrimTmp is destroyed, because the calls enqueued before may still
+// run in it.  Nothing goes back to the cache between construction and destruction.  The rule is DevBuf's: declare the PrimTmp
+// BEFORE the function's DevScope, so that it is destroyed behind the scope's wait.
+struct PrimTmp {
+  DevBuf<char> cur;
+  std::list<DevBuf<char>> retired;   // (a DevBuf neither copies nor moves: a default-made node, then swap)
+  hipError_t fit(size_t bytes) {
+    if (cur.p && cur.cap >= bytes) return hipSuccess;
+    if (cur.p) {
+      retired.emplace_back();
+      retired.back().swap(cur);
+    }
+    return cur.alloc(std::max<size_t>(1, bytes));
+  }
+};
+
 static inline int bits_for(unsigned v) {   // bits that hold every value 0 .. v
   int b = 1;
   while (b < 32 && (v >> b)) b++;
@@ -226,6 +244,26 @@ __host__ __device__ static inline uint64_t sm64(uint64_t& s) {
 __device__ static inline int wave_sum_int(int c) {
   for (int d = 32; d > 0; d >>= 1) c += __shfl_xor(c, d);
   return c;
+}
+
+// the ordered position of a set flag among the flags of a workgroup of 64 * WAVES lanes, and their count; part [WAVES] in LDS.
+// Two barriers; every lane of the workgroup calls it.  Safe to call again with the same `part` at once.
+template <int WAVES>
+__device__ static inline int wg_rank(bool flag, int* part, int& total) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long bal = __ballot(flag);
+  if (lane == 0) part[wv] = __popcll(bal);
+  __syncthreads();
+  int before = __popcll(bal & ((1ull << lane) - 1)), sum = 0;
+#pragma unroll
+  for (int w = 0; w < WAVES; w++) {
+    const int c = part[w];
+    if (w < wv) before += c;
+    sum += c;
+  }
+  __syncthreads();
+  total = sum;
+  return before;
 }
 
 // the segment of position x in CSR offsets: off[lo] <= x < off[lo + 1] (empty segments are stepped over)
@@ -544,7 +582,8 @@ struct NewPointsDev {   // what newpoints_dev allocates; d_out is the result blo
   DevBuf<int> d_offa, d_blk, d_val, d_val_s, d_slot;
   DevBuf<double> d_cam, d_Xall, d_mseall;
   DevBuf<unsigned long long> d_key, d_key_s;
-  DevBuf<char> tmp, d_out;
+  PrimTmp tmp;          // of the sort: the owner of a NewPointsDev declares it before its DevScope
+  DevBuf<char> d_out;
   size_t o_mse = 0, o_w = 0, o_f1 = 0, o_f2 = 0, o_nc = 0, o_na = 0, o_t1 = 0, o_t2 = 0, out_bytes = 0;
 };
 struct msfm_new_points_options;

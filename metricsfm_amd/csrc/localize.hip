@@ -26,9 +26,7 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 // Longest segment k_sort_lds takes: 4096 x (8-byte key + 4-byte index) = 48 KiB of the CU's 160 KiB LDS, below the 64 KiB a
 // workgroup may declare statically, and three such workgroups fit a CU.  MSFM_LOCALIZE_LDS_MAX lowers it (0: everything
@@ -124,19 +122,13 @@ __global__ __launch_bounds__(256) void k_emit(const int* __restrict__ slot_off, 
   const int o0 = out_off[k];
   if (o0 < 0) return;   // a dropped candidate (score 0)
   const int b = slot_off[k], n = slot_off[k + 1] - b;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int base = 0;
   for (int c0 = 0; c0 < n; c0 += 256) {
     const int f = c0 + threadIdx.x;
     const int w = f < n ? first[b + f] : LOC_BIG;
     const bool win = w != LOC_BIG;
-    const unsigned long long bal = __ballot(win);
-    if (lane == 0) part[wv] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1));
-    for (int i = 0; i < wv; i++) before += part[i];
-    const int total = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
+    int total;
+    const int before = wg_rank<4>(win, part, total);
     if (win) {
       const WorkPair P = wp[pair_of(wp, nwp, w)];
       const size_t m = (size_t)P.m0 + (w - P.w0);
@@ -374,7 +366,7 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
   DevBuf<float> d_kp_up;
   DevBuf<int> d_out, d_kpo, d_idx, d_idx_s, d_feat, d_point, d_kprow, d_cf, d_cp, d_sb, d_se, d_lb, d_le;   // (of the second half: emit, sort, gather)
   DevBuf<unsigned long long> d_key, d_key_s;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
   LC_TRY(sc.up(d_wp, wp.data(), (size_t)nwp)); LC_TRY(sc.up(d_slot, slot_off.data(), (size_t)nk + 1));
   if (!dev) {
@@ -482,11 +474,8 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     // stable, so equal keys keep the emit order = ascending f_i: the order k_sort_lds spells out
     LC_TRY(sc.up(d_lb, lb)); LC_TRY(sc.up(d_le, le));
     LC_TRY(d_key_s.alloc(T));
-    size_t bytes = 0;
-    LC_TRY(rocprim::segmented_radix_sort_pairs(nullptr, bytes, d_key.p, d_key_s.p, d_idx.p, d_idx_s.p, (unsigned)T, (unsigned)lb.size(), d_lb.p, d_le.p, 0, 64, s));
-    LC_TRY(tmp.alloc(std::max<size_t>(1, bytes)));
     KTimer t(ctx, "localize_sort_rocprim");
-    LC_TRY(rocprim::segmented_radix_sort_pairs(tmp.p, bytes, d_key.p, d_key_s.p, d_idx.p, d_idx_s.p, (unsigned)T, (unsigned)lb.size(), d_lb.p, d_le.p, 0, 64, s));
+    LC_TRY(prim_seg_sort_pairs(tmp, d_key.p, d_key_s.p, d_idx.p, d_idx_s.p, (unsigned)T, (unsigned)lb.size(), d_lb.p, d_le.p, 0, 64, s));
   }
   {
     KTimer t(ctx, "localize_gather");

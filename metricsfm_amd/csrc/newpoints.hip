@@ -29,9 +29,7 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 #pragma clang fp contract(off)
 #include "point3d_device.h"   // View, tri_two_views
@@ -283,11 +281,8 @@ int newpoints_dev(msfm_ctx* ctx, const msfm_match_store* S, const NewPointsArgs&
   }
   NP_TRY(hipGetLastError());
   {
-    size_t bytes = 0;
-    NP_TRY(rocprim::radix_sort_pairs(nullptr, bytes, W->d_key.p, W->d_key_s.p, W->d_val.p, W->d_val_s.p, Mx, 0u, (unsigned)(key_bits + cam_bits), s));
-    NP_TRY(W->tmp.alloc(std::max<size_t>(1, bytes)));
     KTimer tm(ctx, "newpoints_sort");
-    NP_TRY(rocprim::radix_sort_pairs(W->tmp.p, bytes, W->d_key.p, W->d_key_s.p, W->d_val.p, W->d_val_s.p, Mx, 0u, (unsigned)(key_bits + cam_bits), s));
+    NP_TRY(prim_sort_pairs(W->tmp, W->d_key.p, W->d_key_s.p, W->d_val.p, W->d_val_s.p, Mx, 0u, (unsigned)(key_bits + cam_bits), s));
   }
   {
     KTimer tm(ctx, "newpoints_claim");

@@ -27,8 +27,6 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
 #include "common.h"
 #include "pairsel_args.h"
 #include "runs_device.h"
@@ -209,7 +207,6 @@ __global__ __launch_bounds__(256) void k_join(int first, int Ks, int K, const in
   const int h = blockIdx.x;
   const int i = first + h / Ks, j = hyp_img[(size_t)i * K + h % Ks];
   const int bi = map_off[i], ni = map_off[i + 1] - bi, bj = map_off[j], ej = map_off[j + 1];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const size_t o = FILL ? (size_t)off[h] : 0;
   int base = 0;
   for (int c0 = 0; c0 < ni; c0 += 256) {   // (uniform trip count: the barriers below are reached by every thread)
@@ -220,13 +217,8 @@ __global__ __launch_bounds__(256) void k_join(int first, int Ks, int K, const in
       fj = table_find(map_word, map_feat, bj, ej, map_word[bi + t]);
     }
     const bool hit = fj >= 0;
-    const u64 bal = __ballot(hit);
-    if (lane == 0) part[wv] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1));
-    for (int w = 0; w < wv; w++) before += part[w];
-    const int piece = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
+    int piece;
+    const int before = wg_rank<4>(hit, part, piece);
     if (FILL && hit) {
       const size_t e = o + base + before;
       matches[e] = make_int2(fi, fj);
@@ -246,7 +238,6 @@ __global__ __launch_bounds__(1024) void k_gate(int H, int first, int Ks, int K, 
                                                 const uint8_t* __restrict__ ok, const int* __restrict__ n_in, int th_init, int th_inl,
                                                 uint8_t* __restrict__ verdict, int2* __restrict__ pairs, int* __restrict__ n_kept) {
   __shared__ int part[16];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int base = 0;
   for (int c0 = 0; c0 < H; c0 += 1024) {
     const int h = c0 + threadIdx.x;
@@ -256,12 +247,8 @@ __global__ __launch_bounds__(1024) void k_gate(int H, int first, int Ks, int K, 
       v = ni < th_init ? 1 : !ok[h] ? 2 : !(n_in[h] > th_inl) ? 3 : 0;   // :254, :270, :274
       verdict[h] = (uint8_t)v;
     }
-    const u64 bal = __ballot(v == 0);
-    if (lane == 0) part[wv] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1)), piece = 0;
-    for (int w = 0; w < 16; w++) { if (w < wv) before += part[w]; piece += part[w]; }
-    __syncthreads();
+    int piece;
+    const int before = wg_rank<16>(v == 0, part, piece);
     if (v == 0) {
       const int i = first + h / Ks;
       pairs[base + before] = make_int2(i, hyp_img[(size_t)i * K + h % Ks]);
@@ -322,9 +309,8 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
   DevBuf<int> d_map_off, d_map_word, d_map_feat, d_S, d_hyp_img, d_hyp_sim;
   DevBuf<int> d_val, d_val_s, d_flag, d_pos, d_start, d_finv, d_pinv, d_ftab, d_ptab, d_tab_img, d_seg;
   DevBuf<u64> d_key, d_key_s, d_inv, d_inv_s, d_rk, d_rk_s;
-  DevBuf<char> tmp, tmp_words, tmp_bins, tmp_rank;
+  PrimTmp tmp;
   DevScope sc(ctx);
-  PS_TRY(ps_scan_tmp(tmp, cap, s));
   PS_TRY(d_key.alloc(cap)); PS_TRY(d_key_s.alloc(cap)); PS_TRY(d_val.alloc(cap)); PS_TRY(d_val_s.alloc(cap));
   PS_TRY(d_flag.alloc(cap)); PS_TRY(d_pos.alloc(cap)); PS_TRY(d_start.alloc(cap + 1));
   PS_TRY(d_finv.alloc(cap)); PS_TRY(d_pinv.alloc(cap)); PS_TRY(d_ftab.alloc(cap)); PS_TRY(d_ptab.alloc(cap));
@@ -342,20 +328,17 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
     }
     {
       const unsigned end_bit = 32u + (unsigned)bits_for((unsigned)(n - 1));
-      size_t bytes = 0;
-      PS_TRY(rocprim::radix_sort_pairs(nullptr, bytes, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));
-      PS_TRY(tmp_words.alloc(std::max<size_t>(1, bytes)));
       KTimer t(ctx, "pairsel_sort_words");
-      PS_TRY(rocprim::radix_sort_pairs(tmp_words.p, bytes, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));   // stable
+      PS_TRY(prim_sort_pairs(tmp, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));   // stable
     }
     {
       KTimer t(ctx, "pairsel_groups");
       hipLaunchKernelGGL(k_heads, dim3(gcap), dim3(256), 0, s, total, d_key_s.p, 0, d_flag.p);
-      PS_TRY(ps_scan(tmp, d_flag.p, d_pos.p, cap, s));
+      PS_TRY(prim_scan_excl(tmp, d_flag.p, d_pos.p, cap, s));
       hipLaunchKernelGGL(k_put_heads, dim3(gcap), dim3(256), 0, s, total, d_flag.p, d_pos.p, d_start.p);
       hipLaunchKernelGGL(k_groups, dim3(gcap), dim3(256), 0, s, total, d_G, d_start.p, d_key_s.p, d_hw, d_finv.p, d_ftab.p);
-      PS_TRY(ps_scan(tmp, d_finv.p, d_pinv.p, cap, s));
-      PS_TRY(ps_scan(tmp, d_ftab.p, d_ptab.p, cap, s));
+      PS_TRY(prim_scan_excl(tmp, d_finv.p, d_pinv.p, cap, s));
+      PS_TRY(prim_scan_excl(tmp, d_ftab.p, d_ptab.p, cap, s));
       hipLaunchKernelGGL(k_emit, dim3(gcap), dim3(256), 0, s, total, d_G, d_start.p, d_key_s.p, d_val_s.p, d_finv.p, d_pinv.p, d_ftab.p, d_ptab.p,
                          d_inv.p, d_tab_img.p, d_map_word.p, d_map_feat.p);
     }
@@ -370,16 +353,13 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
   if (n_inv > 1 && num_words / 100 >= 2) {
     {
       const unsigned end_bit = 32u + (unsigned)bits_for((unsigned)num_words);
-      size_t bytes = 0;
-      PS_TRY(rocprim::radix_sort_keys(nullptr, bytes, d_inv.p, d_inv_s.p, (size_t)n_inv, 0u, end_bit, s));
-      PS_TRY(tmp_bins.alloc(std::max<size_t>(1, bytes)));
       KTimer t(ctx, "pairsel_sort_bins");
-      PS_TRY(rocprim::radix_sort_keys(tmp_bins.p, bytes, d_inv.p, d_inv_s.p, (size_t)n_inv, 0u, end_bit, s));
+      PS_TRY(prim_sort_keys(tmp, d_inv.p, d_inv_s.p, (size_t)n_inv, 0u, end_bit, s));
     }
     KTimer t(ctx, "pairsel_similarity");
     const int icap = cdiv((long)n_inv + 1, 256);
     hipLaunchKernelGGL(k_heads, dim3(icap), dim3(256), 0, s, n_inv, d_inv_s.p, 32, d_flag.p);
-    PS_TRY(ps_scan(tmp, d_flag.p, d_pos.p, (size_t)n_inv + 1, s));
+    PS_TRY(prim_scan_excl(tmp, d_flag.p, d_pos.p, (size_t)n_inv + 1, s));
     hipLaunchKernelGGL(k_put_heads, dim3(icap), dim3(256), 0, s, n_inv, d_flag.p, d_pos.p, d_start.p);
     const int* d_B = d_pos.p + n_inv;
     const int stop = num_words / 100;   // :109
@@ -393,13 +373,10 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
     hipLaunchKernelGGL(k_rank_lds, dim3(n), dim3(256), sizeof(u64) * (size_t)P, s, n, P, K, d_S.p, d_hyp_img.p, d_hyp_sim.p);
   } else {
     PS_TRY(d_rk.alloc((size_t)n * n)); PS_TRY(d_rk_s.alloc((size_t)n * n)); PS_TRY(d_seg.alloc((size_t)n + 1));
-    size_t bytes = 0;
-    PS_TRY(rocprim::segmented_radix_sort_keys(nullptr, bytes, d_rk.p, d_rk_s.p, (unsigned)((size_t)n * n), (unsigned)n, d_seg.p, d_seg.p + 1, 0, 64, s));
-    PS_TRY(tmp_rank.alloc(std::max<size_t>(1, bytes)));
     KTimer t(ctx, "pairsel_rank_rocprim");
     hipLaunchKernelGGL(k_seg_off, dim3(cdiv(n + 1, 256)), dim3(256), 0, s, n, d_seg.p);
     hipLaunchKernelGGL(k_rank_keys, dim3(cdiv(n, 256), n), dim3(256), 0, s, n, d_S.p, d_rk.p);
-    PS_TRY(rocprim::segmented_radix_sort_keys(tmp_rank.p, bytes, d_rk.p, d_rk_s.p, (unsigned)((size_t)n * n), (unsigned)n, d_seg.p, d_seg.p + 1, 0, 64, s));
+    PS_TRY(prim_seg_sort_keys(tmp, d_rk.p, d_rk_s.p, (unsigned)((size_t)n * n), (unsigned)n, d_seg.p, d_seg.p + 1, 0, 64, s));
     hipLaunchKernelGGL(k_rank_take, dim3(cdiv(K, 256), n), dim3(256), 0, s, n, K, d_rk_s.p, d_hyp_img.p, d_hyp_sim.p);
   }
   PS_TRY(hipGetLastError());
@@ -473,9 +450,8 @@ MSFM_API int msfm_pair_select(msfm_wordset* W, int first, int n_rows, const msfm
   DevBuf<float2> d_p1, d_p2;
   DevBuf<double> d_F;
   DevBuf<uint8_t> d_in, d_ok, d_verdict;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
-  PS_TRY(ps_scan_tmp(tmp, (size_t)H + 1, s));
   PS_TRY(d_count.alloc((size_t)H + 1)); PS_TRY(d_off.alloc((size_t)H + 1)); PS_TRY(d_total.alloc(1));
   PS_TRY(hipMemsetAsync(d_count.p + H, 0, sizeof(int), s)); PS_TRY(hipMemsetAsync(d_total.p, 0, sizeof(u64), s));
   const float2* kp = reinterpret_cast<const float2*>(W->d_kp.p);
@@ -483,7 +459,7 @@ MSFM_API int msfm_pair_select(msfm_wordset* W, int first, int n_rows, const msfm
     KTimer t(ctx, "pairsel_join_count");
     hipLaunchKernelGGL(k_join<false>, dim3(H), dim3(256), 0, s, first, Ks, K, W->d_hyp_img.p, W->d_map_off.p, W->d_map_word.p, W->d_map_feat.p,
                        W->d_feat_off.p, kp, (const int*)nullptr, d_count.p, d_total.p, (int2*)nullptr, (float2*)nullptr, (float2*)nullptr);
-    PS_TRY(ps_scan(tmp, d_count.p, d_off.p, (size_t)H + 1, s));
+    PS_TRY(prim_scan_excl(tmp, d_count.p, d_off.p, (size_t)H + 1, s));
   }
   PS_TRY(hipGetLastError());
   // the first wait: geo_fransac_dev wants the offsets on the host, and the match arrays are sized by their last entry

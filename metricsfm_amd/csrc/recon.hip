@@ -23,9 +23,7 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 #pragma clang fp contract(off)
 
@@ -713,18 +711,15 @@ MSFM_API int msfm_recon_commit_camera(msfm_recon* Q, const double* cam_pose6, in
   hipStream_t s = ctx->stream;
   MSFM_TRY(recon_reserve(Q, (size_t)Q->n_points, (size_t)Q->n_obs + (size_t)n2));
   DevBuf<int> flag, pos;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
   RC_TRY(flag.alloc((size_t)n + 1)); RC_TRY(pos.alloc((size_t)n + 1));
-  size_t bytes = 0;
-  RC_TRY(rocprim::exclusive_scan(nullptr, bytes, flag.p, pos.p, 0, (size_t)n + 1, rocprim::plus<int>(), s));
-  RC_TRY(tmp.alloc(std::max<size_t>(1, bytes)));
   if (nf) RC_TRY(hipMemsetD32Async((hipDeviceptr_t)(Q->d_fp.p + fp_off), -1, (size_t)nf, s));   // Camera::pts_ of a new camera: no point anywhere
   {
     KTimer tm(ctx, "recon_commit");
     tm.count = 3;
     hipLaunchKernelGGL(k_commit_flags, dim3(cdiv(n + 1, 256)), dim3(256), 0, s, n, Q->pend_state.p, flag.p);
-    RC_TRY(rocprim::exclusive_scan(tmp.p, bytes, flag.p, pos.p, 0, (size_t)n + 1, rocprim::plus<int>(), s));
+    RC_TRY(prim_scan_excl(tmp, flag.p, pos.p, (size_t)n + 1, s));
     hipLaunchKernelGGL(k_commit, dim3(cdiv(n, 256)), dim3(256), 0, s, n, c1, (int)fp_off, Q->n_obs, Q->pend_feat.p, Q->pend_point.p, Q->pend_state.p, pos.p,
                        Q->d_fp.p, Q->d_bad.p, Q->d_views.p, Q->d_added.p, Q->d_op.p, Q->d_oc.p, Q->d_of.p);
   }

@@ -1,10 +1,8 @@
-// Runs of equal keys in a sorted array, on the device: group heads by flag, an exclusive scan, a scatter of the heads.
+// Runs of equal keys in a sorted array, on the device: group heads by flag, an exclusive scan (prim_scan_excl), a scatter of the heads.
 // pairsel.hip (the groups of an image's words, the bins of the inverted file) and words.hip (the bags of words) include it;
 // the kernels are static, so each unit carries its own copy.
 #pragma once
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 namespace runs {
 
@@ -38,18 +36,3 @@ static __global__ __launch_bounds__(256) void k_map_off(int n, int T, const int*
 }
 
 }  // namespace runs
-
-// rocPRIM's scratch is allocated once per call, before the first launch that uses it: a block given back while the stream still
-// runs would go to the next taker of the cache.  ps_scan_tmp sizes it for the longest scan of the call.
-static inline hipError_t ps_scan_tmp(DevBuf<char>& tmp, size_t n_max, hipStream_t s) {
-  size_t bytes = 0;
-  const hipError_t e = rocprim::exclusive_scan(nullptr, bytes, (const int*)nullptr, (int*)nullptr, 0, n_max, rocprim::plus<int>(), s);
-  return e != hipSuccess ? e : tmp.alloc(std::max<size_t>(1, bytes));
-}
-static inline hipError_t ps_scan(DevBuf<char>& tmp, const int* in, int* out, size_t n, hipStream_t s) {
-  size_t bytes = 0;
-  const hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-  if (e != hipSuccess) return e;
-  if (bytes > tmp.n) return hipErrorOutOfMemory;
-  return rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-}

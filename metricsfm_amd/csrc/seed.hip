@@ -122,18 +122,12 @@ __global__ __launch_bounds__(256) void k_compact(const int* __restrict__ off_all
   __shared__ int part[4];
   const int h = blockIdx.x;
   const int b = off_all[h], N = off_all[h + 1] - b;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   int base = 0;
   for (int c0 = 0; c0 < N; c0 += 256) {
     const int j = c0 + threadIdx.x;
     const bool keep = j < N && flag[(size_t)b + j] != 0;
-    const unsigned long long bal = __ballot(keep);
-    if (lane == 0) part[wv] = __popcll(bal);
-    __syncthreads();
-    int before = __popcll(bal & ((1ull << lane) - 1));
-    for (int i = 0; i < wv; i++) before += part[i];
-    const int total = part[0] + part[1] + part[2] + part[3];
-    __syncthreads();
+    int total;
+    const int before = wg_rank<4>(keep, part, total);
     if (keep) {
       const size_t s = (size_t)b + j, e = (size_t)b + base + before;
       pt_match[e] = j;

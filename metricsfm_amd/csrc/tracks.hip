@@ -10,9 +10,7 @@
 #include <cstring>
 #include <memory>
 
-#include <rocprim/rocprim.hpp>
-
-#include "common.h"
+#include "prim_device.h"
 
 struct msfm_track_set {
   std::vector<int> off, img, feat;
@@ -192,15 +190,6 @@ __global__ __launch_bounds__(256) void k_compact(long E, int n_images, const uns
   if (e == 0 || key[e - 1] / ni != t) off[t] = j;   // first observation of point t (every point has at least one)
 }
 
-static hipError_t scan_excl(const int* in, int* out, size_t n, hipStream_t s, DevBuf<char>& tmp) {
-  if (n == 0) return hipSuccess;
-  size_t bytes = 0;
-  hipError_t e = rocprim::exclusive_scan(nullptr, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-  if (e != hipSuccess) return e;
-  if (tmp.n < bytes) { e = tmp.alloc(bytes); if (e != hipSuccess) return e; }
-  return rocprim::exclusive_scan(tmp.p, bytes, in, out, 0, n, rocprim::plus<int>(), s);
-}
-
 }  // namespace trk
 
 // The association on match lists that are already resident (d_pair [n_pairs][2], d_moff [n_pairs+1], d_match [M][2]; the
@@ -221,7 +210,7 @@ int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_o
 #define TTRY(e) HIP_TRY(ctx, (e))
   DevBuf<int> ga, gb, ia, ib, first, parent, is_new, new_before, point_of, err, val, val_s, head, slot;
   DevBuf<unsigned long long> key, key_s;
-  DevBuf<char> tmp;
+  PrimTmp tmp;
   DevScope sc(ctx);
   TTRY(ga.alloc(M)); TTRY(gb.alloc(M)); TTRY(ia.alloc(M)); TTRY(ib.alloc(M));
   TTRY(first.alloc(std::max(1, NF))); TTRY(parent.alloc(std::max(1, NF))); TTRY(point_of.alloc(std::max(1, NF)));
@@ -237,7 +226,7 @@ int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_o
   TTRY(hipStreamSynchronize(s));
   if (bad != big) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_tracks_build_device: match %d names a feature outside its image", bad);
   hipLaunchKernelGGL(k_parent, dim3(cdiv(M, 256)), dim3(256), 0, s, M, ga.p, gb.p, first.p, parent.p, is_new.p);
-  TTRY(scan_excl(is_new.p, new_before.p, (size_t)M + 1, s, tmp));
+  TTRY(prim_scan_excl(tmp, is_new.p, new_before.p, (size_t)M + 1, s));
   hipLaunchKernelGGL(k_root, dim3(cdiv(NF, 256)), dim3(256), 0, s, NF, parent.p, first.p, new_before.p, point_of.p);
   int n_tracks = 0;
   TTRY(hipMemcpyAsync(&n_tracks, new_before.p + M, sizeof(int), hipMemcpyDeviceToHost, s));
@@ -250,14 +239,11 @@ int tracks_build_dev(msfm_ctx* ctx, int n_images, const std::vector<int>& feat_o
     // stable: within one (point, image) the earliest match stays first
     int bits = 1;
     while (bits < 64 && ((unsigned long long)n_tracks * (unsigned long long)std::max(1, n_images)) >> bits) bits++;
-    size_t bytes = 0;
-    TTRY(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key_s.p, val.p, val_s.p, (size_t)E, 0, bits, s));
-    if (tmp.n < bytes) TTRY(tmp.alloc(bytes));
-    TTRY(rocprim::radix_sort_pairs(tmp.p, bytes, key.p, key_s.p, val.p, val_s.p, (size_t)E, 0, bits, s));
+    TTRY(prim_sort_pairs(tmp, key.p, key_s.p, val.p, val_s.p, (size_t)E, 0, bits, s));
   }
   TTRY(hipMemsetAsync(head.p + E, 0, sizeof(int), s));
   hipLaunchKernelGGL(k_heads, dim3(cdiv(E, 256)), dim3(256), 0, s, E, key_s.p, head.p);
-  TTRY(scan_excl(head.p, slot.p, (size_t)E + 1, s, tmp));
+  TTRY(prim_scan_excl(tmp, head.p, slot.p, (size_t)E + 1, s));
   int n_obs = 0;
   TTRY(hipMemcpyAsync(&n_obs, slot.p + E, sizeof(int), hipMemcpyDeviceToHost, s));
   TTRY(hipStreamSynchronize(s));

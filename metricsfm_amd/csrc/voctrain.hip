@@ -371,7 +371,7 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
   DevBuf<float> d_cent, d_mind;
   DevBuf<uint8_t> d_asg;
   DevBuf<u64> d_w, d_P, d_gacc;
-  DevBuf<char> tmp, tmp_inc, tmp_sort;
+  PrimTmp tmp;
   std::vector<std::unique_ptr<LevelOut>> levels;
   std::unique_ptr<msfm_voctree> T(new msfm_voctree());
   DevScope sc(ctx);
@@ -383,13 +383,7 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
   VT_TRY(hip_first_error({d_nm.alloc(NN), d_nm2.alloc(NN), d_nstart.alloc(NN), d_coff.alloc(NN), d_choff.alloc(NN), d_moff.alloc(NN), d_nc.alloc(NN),
                           d_kind.alloc(NN), d_done.alloc(NN), d_iters.alloc(NN), d_changed.alloc(NN), d_capped.alloc(NN), d_t1.alloc(NN),
                           d_t2.alloc(NN), d_t3.alloc(NN)}));
-  VT_TRY(ps_scan_tmp(tmp, RR + 1, s));
-  size_t inc_bytes = 0, sort_bytes = 0;
   const unsigned end_bit = (unsigned)bits_for((unsigned)M0);   // child ordinals are below M0 / 2, the sentinel is M0
-  VT_TRY(rocprim::inclusive_scan(nullptr, inc_bytes, d_w.p, d_P.p, Mx, rocprim::plus<u64>(), s));
-  VT_TRY(tmp_inc.alloc(std::max<size_t>(1, inc_bytes)));
-  VT_TRY(rocprim::radix_sort_pairs(nullptr, sort_bytes, d_key.p, d_key2.p, d_perm.p, d_perm2.p, Mx, 0u, end_bit, s));
-  VT_TRY(tmp_sort.alloc(std::max<size_t>(1, sort_bytes)));
   int* d_tot = d_small.p;         // [4] member, row, chunk and accumulator-row totals of a level
   int* d_st = d_small.p + 4;      // [3] k_rows' statistics
   int* d_nopen = d_small.p + 8;
@@ -422,10 +416,10 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
       KTimer t(ctx, "voctrain_level");
       hipLaunchKernelGGL(k_prep_sizes, dim3(cdiv(nn + 1, 256)), dim3(256), 0, s, nn, k, A.nm, d_t1.p, d_t2.p, d_t3.p);
       VT_TRY(hipMemsetAsync(A.nm + nn, 0, sizeof(int), s));   // a zero behind the member counts closes their scan
-      VT_TRY(ps_scan(tmp, A.nm, A.nstart, (size_t)nn + 1, s));
-      VT_TRY(ps_scan(tmp, d_t1.p, A.coff, (size_t)nn + 1, s));
-      VT_TRY(ps_scan(tmp, d_t2.p, A.choff, (size_t)nn + 1, s));
-      VT_TRY(ps_scan(tmp, d_t3.p, A.moff, (size_t)nn + 1, s));
+      VT_TRY(prim_scan_excl(tmp, A.nm, A.nstart, (size_t)nn + 1, s));
+      VT_TRY(prim_scan_excl(tmp, d_t1.p, A.coff, (size_t)nn + 1, s));
+      VT_TRY(prim_scan_excl(tmp, d_t2.p, A.choff, (size_t)nn + 1, s));
+      VT_TRY(prim_scan_excl(tmp, d_t3.p, A.moff, (size_t)nn + 1, s));
       hipLaunchKernelGGL(k_totals, dim3(1), dim3(1), 0, s, nn, A.nstart, A.coff, A.choff, A.moff, d_tot);
     }
     VT_TRY(hipGetLastError());
@@ -443,7 +437,7 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
       hipLaunchKernelGGL(k_gather, dim3(nn), dim3(128), 0, s, 0, A, d_csrc.p, d_rowptr.p, d_cent.p);
       for (int j = 1; j < k && n_chunks > 0; j++) {
         hipLaunchKernelGGL(k_seed_dist, dim3(gM8), dim3(256), 0, s, M, j, wscale, A, d_perm.p, d_node.p, d_rowptr.p, d_cent.p, d_mind.p, d_w.p);
-        VT_TRY(rocprim::inclusive_scan(tmp_inc.p, inc_bytes, d_w.p, d_P.p, (size_t)M, rocprim::plus<u64>(), s));
+        VT_TRY(prim_scan_incl(tmp, d_w.p, d_P.p, (size_t)M, s));
         hipLaunchKernelGGL(k_seed_pick, dim3(gN), dim3(256), 0, s, nn, j, level, opt->seed, A, d_perm.p, d_P.p, d_csrc.p);
         hipLaunchKernelGGL(k_gather, dim3(nn), dim3(128), 0, s, j, A, d_csrc.p, d_rowptr.p, d_cent.p);
       }
@@ -487,13 +481,13 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
       KTimer t(ctx, "voctrain_level");
       VT_TRY(hipMemsetAsync(d_st, 0, sizeof(int) * 3, s));
       hipLaunchKernelGGL(k_rows, dim3(gN), dim3(256), 0, s, nn, k, R, last, A, d_ccount.p, d_fleaf.p, d_fopen.p, d_st);
-      VT_TRY(ps_scan(tmp, d_fleaf.p, d_leafidx.p, (size_t)R + 1, s));
-      VT_TRY(ps_scan(tmp, d_fopen.p, d_openidx.p, (size_t)R + 1, s));
+      VT_TRY(prim_scan_excl(tmp, d_fleaf.p, d_leafidx.p, (size_t)R + 1, s));
+      VT_TRY(prim_scan_excl(tmp, d_fopen.p, d_openidx.p, (size_t)R + 1, s));
       hipLaunchKernelGGL(k_emit, dim3(nn), dim3(128), 0, s, k, (int)word_base, block_base + nn, A, d_cent.p, d_ccount.p, d_fleaf.p, d_fopen.p,
                          d_leafidx.p, d_openidx.p, L->n.p, L->desc.p, L->link.p, L->weight.p, nm_next);
       hipLaunchKernelGGL(k_next_key, dim3(cdiv(M, 256)), dim3(256), 0, s, M, (unsigned)M0, A, d_perm.p, d_node.p, d_asg.p, d_fopen.p, d_openidx.p,
                          d_key.p, d_perm2.p);
-      VT_TRY(rocprim::radix_sort_pairs(tmp_sort.p, sort_bytes, d_key.p, d_key2.p, d_perm2.p, d_perm.p, (size_t)M, 0u, end_bit, s));   // stable
+      VT_TRY(prim_sort_pairs(tmp, d_key.p, d_key2.p, d_perm2.p, d_perm.p, (size_t)M, 0u, end_bit, s));   // stable
       VT_TRY(hipMemcpyAsync(d_node.p, d_key2.p, sizeof(int) * (size_t)M, hipMemcpyDeviceToDevice, s));
     }
     VT_TRY(hipGetLastError());

@@ -267,9 +267,8 @@ MSFM_API int msfm_descset_words(msfm_descset* set, const msfm_voctree* T, int mi
   DevBuf<int> d_feat_off, d_val, d_val_s, d_flag, d_pos, d_start, d_grp_img, d_nun;
   DevBuf<const float*> d_rows;
   DevBuf<u64> d_key, d_key_s;
-  DevBuf<char> tmp, tmp_sort;
+  PrimTmp tmp;
   DevScope sc(ctx);
-  WD_TRY(ps_scan_tmp(tmp, cap, s));
   WD_TRY(sc.up(d_feat_off, R->feat_off)); WD_TRY(sc.up(R->d_hw, R->has_words)); WD_TRY(sc.up(d_rows, V.f32));
   WD_TRY(R->d_word.alloc(tx)); WD_TRY(R->d_leaf_w.alloc(tx)); WD_TRY(R->d_image_max.alloc(n)); WD_TRY(R->d_bow_off.alloc((size_t)n + 1));
   WD_TRY(R->d_bow_word.alloc(tx)); WD_TRY(R->d_bow_weight.alloc(tx));
@@ -287,18 +286,15 @@ MSFM_API int msfm_descset_words(msfm_descset* set, const msfm_voctree* T, int mi
     }
     {
       const unsigned end_bit = 32u + (unsigned)bits_for((unsigned)n);   // image n: the features without a word
-      size_t bytes = 0;
-      WD_TRY(rocprim::radix_sort_pairs(nullptr, bytes, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));
-      WD_TRY(tmp_sort.alloc(std::max<size_t>(1, bytes)));
       KTimer t(ctx, "words_sort");
-      WD_TRY(rocprim::radix_sort_pairs(tmp_sort.p, bytes, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));   // stable
+      WD_TRY(prim_sort_pairs(tmp, d_key.p, d_key_s.p, d_val.p, d_val_s.p, (size_t)total, 0u, end_bit, s));   // stable
     }
     {
       KTimer t(ctx, "words_bags");
       const int gcap = cdiv((long)cap, 256);
       const int* d_G = d_pos.p + total;   // runs found by the scan over [0, total]
       hipLaunchKernelGGL(k_heads, dim3(gcap), dim3(256), 0, s, total, d_key_s.p, 0, d_flag.p);
-      WD_TRY(ps_scan(tmp, d_flag.p, d_pos.p, cap, s));
+      WD_TRY(prim_scan_excl(tmp, d_flag.p, d_pos.p, cap, s));
       hipLaunchKernelGGL(k_put_heads, dim3(gcap), dim3(256), 0, s, total, d_flag.p, d_pos.p, d_start.p);
       hipLaunchKernelGGL(k_bags, dim3(gcap), dim3(256), 0, s, total, n, d_G, d_start.p, d_key_s.p, d_val_s.p, R->d_leaf_w.p, d_grp_img.p,
                          R->d_bow_word.p, R->d_bow_weight.p);
