@@ -41,8 +41,14 @@ int msfm_version(void);
 /* device < 0: use the current HIP device.  Fails with MSFM_E_DEVICE when no GPU is
  * visible — there is no CPU fallback behind this ABI. */
 int msfm_ctx_create(int device, msfm_ctx** out);
-/* Objects created from a ctx (descriptor sets, match results, resident BA problems) should be destroyed first; if some
- * are still alive the context is kept until the last of them is destroyed, then released. */
+/* Every object made from a ctx that keeps it is a child of that context: descriptor sets, match results, chains, resident BA
+ * problems, word sets, vocabulary trees, word results, scale spaces, stereo objects, match stores, seed / localize / round
+ * sets and resident states.  Children should be destroyed first; if some are still alive the context is kept until the last
+ * of them is destroyed, then released.  A create that fails leaves no child behind.
+ * The msfm_*_destroy of a child accepts NULL, sets the context's device itself and, where the object holds device memory,
+ * waits for the context's stream before that memory is given back: always, except msfm_seed_set_destroy and
+ * msfm_localize_set_destroy (only for a set that kept arrays on the device) and msfm_round_set_destroy (host memory only,
+ * never).  The host-only results - track, pair, new-points and localize-pose sets - belong to no context. */
 void msfm_ctx_destroy(msfm_ctx* ctx);
 const char* msfm_last_error(const msfm_ctx* ctx);
 /* The HIP stream (hipStream_t) every kernel of this ctx is launched on. */
@@ -1678,7 +1684,6 @@ int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* store, co
  * tables (a NULL pointer keeps that table). */
 int msfm_recon_normalize(msfm_recon* recon, const double* noise, double target_deviation, double point_sigma, double mid[3], double* scale);
 int msfm_recon_set_cameras(msfm_recon* recon, const double* cam_pose, const double* cam_R, const double* cam_t, const double* cam_c);
-/* msfm_recon_destroy waits for the context's stream before the blocks go back to the pool. */
 void msfm_recon_destroy(msfm_recon* recon);
 
 /* ==================================================================================== *

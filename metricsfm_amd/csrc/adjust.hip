@@ -522,8 +522,8 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   const int FP = T.cam_fo[nc];
   if (FP && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
   MSFM_TRY(round_key_check(ctx, who, nc, T));
-  std::unique_ptr<msfm_round_set> R(new msfm_round_set());
-  R->ctx = ctx; R->n_cams = nc; R->n_models = nm; R->n_points = np;
+  Child<msfm_round_set> R = child_new<msfm_round_set>(ctx);
+  R->n_cams = nc; R->n_models = nm; R->n_points = np;
   R->keep_problem = opt.keep_problem != 0;
   R->cam_pose.assign(P->cam_pose, P->cam_pose + 6 * (size_t)nc);
   R->cam_model.assign(P->cam_model, P->cam_model + 3 * (size_t)nm);
@@ -559,7 +559,6 @@ MSFM_API int msfm_round_adjust(msfm_ctx* ctx, const msfm_match_store* S, const m
   MSFM_TRY(round_adjust_dev(ctx, who, A, T, D, opt, &sc.h2d, R.get(), /*fetch_points=*/true));
   sc.dismiss();   // (the core's finish())
   R->h2d_bytes = sc.h2d;
-  ctx->children++;   // a set is a child of its context, like a store
   *out = R.release();
   return MSFM_OK;
 }
@@ -625,9 +624,4 @@ MSFM_API int msfm_round_set_fetch_problem(const msfm_round_set* R, int stage, in
   return MSFM_OK;
 }
 
-MSFM_API void msfm_round_set_destroy(msfm_round_set* R) {
-  if (!R) return;
-  msfm_ctx* ctx = R->ctx;
-  delete R;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_round_set_destroy(msfm_round_set* R) { msfm_child_destroy(R); }

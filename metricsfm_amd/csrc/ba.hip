@@ -1897,6 +1897,11 @@ struct msfm_ba {
   int solve_paths = 0;   // MSFM_PATH_* of the last factorisation (msfm_ba_layout.solve_paths)
   int asm_paths = 0;     // MSFM_PATH_ASM_BESIDE of the last assembly (msfm_ba_layout.assemble_paths)
   int rider_paths = 0;   // MSFM_PATH_RIDER_* of the last solve (msfm_ba_layout.rider_paths)
+  ~msfm_ba() {
+    msfm_chol_ws_destroy(chol_ws);
+    if (h_scal) (void)hipHostFree(h_scal);
+    if (h_fail) (void)hipHostFree(h_fail);
+  }
 };
 
 // --------------------------------------------------------------------------------------
@@ -2350,18 +2355,7 @@ MSFM_API void msfm_ba_options_default(msfm_ba_options* o) {
   o->jacobi_scaling = 1;
 }
 
-MSFM_API void msfm_ba_destroy(msfm_ba* ba) {
-  if (!ba) return;
-  msfm_ctx* ctx = ba->ctx;
-  (void)hipSetDevice(ctx->device);   // the caller's thread may have another device current (Python __del__ after set_device)
-  (void)hipStreamSynchronize(ctx->stream);
-  msfm_chol_ws_destroy(ba->chol_ws);
-  ba->chol_ws = nullptr;
-  if (ba->h_scal) (void)hipHostFree(ba->h_scal);
-  if (ba->h_fail) (void)hipHostFree(ba->h_fail);
-  delete ba;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_ba_destroy(msfm_ba* ba) { msfm_child_destroy(ba); }
 
 // Host work arrays of msfm_ba_create that scale with the observation count; owned by the context and reused.
 struct BaScratch {
@@ -3937,11 +3931,9 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   };
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  msfm_ba* ba = new msfm_ba();
-  struct Guard { msfm_ba* p; ~Guard() { if (p) msfm_ba_destroy(p); } } guard{ba};
-  ba->ctx = ctx;
+  Child<msfm_ba> own = child_new<msfm_ba>(ctx);
+  msfm_ba* ba = own.get();
   ba->env = msfm_env_read();
-  ctx->children++;
   ba->world_at_create = ctx->world;
   {
     const bool on_host = ba->env.create_host;
@@ -4044,8 +4036,7 @@ int ba_create_impl(msfm_ctx* ctx, const msfm_ba_problem* P, bool bulk_on_device,
   HIP_TRY(ctx, hipStreamSynchronize(s));
   lap("done");
   ba->setup_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  guard.p = nullptr;
-  *out = ba;
+  *out = own.release();
   return MSFM_OK;
 }
 

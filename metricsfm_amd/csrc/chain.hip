@@ -235,15 +235,15 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
       return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_chain_create: pair %d needs the keypoints of both images (msfm_descset_upload_keypoints)", p);
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<msfm_chain> C(new msfm_chain());
-  C->ctx = ctx; C->n_images = v.n_images; C->n_pairs = v.n_pairs;
+  Child<msfm_chain> C = child_new<msfm_chain>(ctx);
+  C->n_images = v.n_images; C->n_pairs = v.n_pairs;
   C->slam = v.slam; C->src = res;
   C->pairs.assign(v.pairs, v.pairs + 2 * (size_t)v.n_pairs);
   C->count = v.count;
   C->feat_off.assign(v.n_images + 1, 0);
   for (int i = 0; i < v.n_images; i++) C->feat_off[i + 1] = C->feat_off[i] + v.count[i];
   hipStream_t s = ctx->stream;
-  DevScope sc(ctx);   // (an error return deletes the chain)
+  DevScope sc(ctx);
   C->kp.assign(v.n_images, nullptr);
   CH_TRY(C->kp_own.alloc(2 * (size_t)std::max(1, C->feat_off[v.n_images])));
   for (int i = 0; i < v.n_images; i++) {
@@ -260,7 +260,6 @@ MSFM_API int msfm_chain_create(msfm_match_result* res, msfm_chain** out) {
     CH_TRY(hipStreamSynchronize(s));
   }
   C->n_good = ng; C->n_all = na;   // sizes of matches_good / matches_all per pair: msfm_chain_verify gathers them
-  ctx->children++;
   *out = C.release();
   sc.dismiss();   // the chain keeps its block (with pairs: behind the wait above)
   return MSFM_OK;
@@ -672,11 +671,4 @@ MSFM_API int msfm_chain_fetch_point_tracks(msfm_chain* C, int* track_of_point) {
   return MSFM_OK;
 }
 
-MSFM_API void msfm_chain_destroy(msfm_chain* C) {
-  if (!C) return;
-  msfm_ctx* ctx = C->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  delete C;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_chain_destroy(msfm_chain* C) { msfm_child_destroy(C); }

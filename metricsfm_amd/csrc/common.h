@@ -11,6 +11,7 @@
 #include <functional>
 #include <initializer_list>
 #include <list>
+#include <memory>
 #include <string>
 #include <thread>
 #include <utility>
@@ -77,8 +78,8 @@ struct msfm_ctx {
   // mapping + unmapping that much fresh memory on every call cost a quarter of the setup time
   void* ba_scratch = nullptr;
   void (*ba_scratch_free)(void*) = nullptr;
-  // objects created from this context that are still alive (descriptor sets, match results, resident problems);
-  // msfm_ctx_destroy refuses while there are any, and the last child of an orphaned context destroys it
+  // objects created from this context that are still alive (Child below); msfm_ctx_destroy refuses while there are any, and
+  // the last child of an orphaned context destroys it
   int children = 0;
   bool orphaned = false;
   // native collective (msfm_ctx_init_rccl): librccl handle, communicator and the entry points resolved from it
@@ -89,6 +90,40 @@ struct msfm_ctx {
   void* rccl_error_string = nullptr;
 };
 void msfm_ctx_child_released(msfm_ctx* ctx);
+
+// A child of a context: an object the library hands to the caller that keeps its msfm_ctx* (member `ctx`) and, most of them,
+// device blocks.  child_new counts it from the moment it exists; the hand-over is `*out = X.release()`.  It goes one way only,
+// msfm_child_destroy, which is every public msfm_*_destroy of a child and the deleter of Child: wait for the stream if the
+// object holds blocks (they go back to the cache only behind the work that may still use them), delete, and last the release,
+// which may destroy the context and the stream with it.  A create that fails with the object in hand therefore takes the same
+// path as a destroy.  Whether an object holds blocks: always, unless its type says otherwise beside its definition
+// (msfm_seed_set, msfm_localize_set: one block tells; msfm_round_set: host memory only, never).
+template <class T>
+static inline bool child_holds_blocks(const T*) { return true; }
+template <class T>
+static inline void msfm_child_destroy(T* obj) {
+  if (!obj) return;
+  msfm_ctx* ctx = obj->ctx;
+  if (child_holds_blocks(obj)) {
+    (void)hipSetDevice(ctx->device);   // the caller's thread may have another device current (Python __del__ after set_device)
+    (void)hipStreamSynchronize(ctx->stream);
+  }
+  delete obj;
+  msfm_ctx_child_released(ctx);
+}
+struct ChildDelete {
+  template <class T>
+  void operator()(T* obj) const { msfm_child_destroy(obj); }
+};
+template <class T>
+using Child = std::unique_ptr<T, ChildDelete>;
+template <class T>
+static inline Child<T> child_new(msfm_ctx* ctx) {
+  Child<T> c(new T());
+  c->ctx = ctx;
+  ctx->children++;
+  return c;
+}
 
 int msfm_set_error(msfm_ctx* ctx, int code, const char* fmt, ...);
 
@@ -357,7 +392,6 @@ struct msfm_match_store {
 // What msfm_seed_hypotheses leaves behind (seed.hip creates and destroys it; recon.hip starts a model from its winner).  The
 // answer of every hypothesis is host memory; the winner's accepted points stay on the device as well, in blocks sized by the
 // longest hypothesis of the call (the winner is not known on the host when they are made), with its place in the store.
-// A child of its context: msfm_seed_set_destroy waits for the stream before the blocks go back to the pool.
 struct msfm_seed_set {
   msfm_ctx* ctx = nullptr;
   const msfm_match_store* store = nullptr;
@@ -373,6 +407,7 @@ struct msfm_seed_set {
   DevBuf<int> d_ptm;              // [n_points of the winner] pt_match
   DevBuf<double> d_X, d_mse;      // [..][3], [..]
 };
+static inline bool child_holds_blocks(const msfm_seed_set* R) { return R->d_ptm.p != nullptr; }
 
 // What msfm_localize_candidates leaves behind (localize.hip creates and destroys it; localize_pose.hip reads it).  A set made
 // with point_xyz keeps the device arrays its gather kernel wrote - corr_point, pts_w, pts_2d in the layout of corr_off - until
@@ -387,6 +422,7 @@ struct msfm_localize_set {
   DevBuf<int> d_cf;               // [n_corr] corr_feat (sets of localize_candidates_dev with resident arrays only)
   DevBuf<double> d_pw, d_p2;      // [n_corr][3], [n_corr][2]
 };
+static inline bool child_holds_blocks(const msfm_localize_set* R) { return R->d_cp.p != nullptr; }
 
 struct LocalizeDev {   // the bulk arrays of the state on the device (recon.hip's); kp: every image's rows, or NULL = the store's
   const int* feat_point; const uint8_t* pt_bad; const double* pt_mse; const int* pt_views; const double* point_xyz; const float* kp;
@@ -512,6 +548,7 @@ struct msfm_round_set {
   } problem[2];
   int64_t h2d_bytes = 0;
 };
+static inline bool child_holds_blocks(const msfm_round_set*) { return false; }   // its destroy runs between the rounds of a model: no wait
 struct RoundArgs {     // counts and the O(cameras) arguments, host pointers
   int n_cams = 0, n_models = 0, n_points = 0, n_obs = 0;
   const int* cam_img = nullptr; const int* cam_model_of_cam = nullptr; const uint8_t* model_mutable = nullptr;

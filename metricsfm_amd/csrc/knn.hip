@@ -31,25 +31,40 @@ typedef unsigned int u32;
 #define TT 64          // train rows per LDS tile
 #define QPB 256        // queries per workgroup (4 waves x 64)
 
+// One image of a descriptor set.  An image nothing was uploaded to, or one of no features, holds no block.
+struct DescImage {
+  int count = 0;
+  bool has_kp = false;                   // keypoints were uploaded (an image of no features with keypoints: kp holds no block)
+  DevBuf<float> f32;                     // [count][128]
+  DevBuf<float> kp;                      // [count][2] keypoint positions (msfm_descset_upload_keypoints)
+  // int8 forms for the i8 MFMA kernel: train rows a-128, query rows 127-b, and the per-row terms of
+  //   |a-b|^2 = 2 sum (a-128)(127-b) + sum (a-127)^2 + sum (128-b)^2 - 128
+  DevBuf<signed char> ti8, qi8;          // [count][128]
+  DevBuf<int> tcin, tpar, qbeta;         // (alpha>>1)+2^21 ; alpha&1 ; beta
+  // f16 forms for non-integral descriptors (made at match time, once the common power-of-two scale is known):
+  // f16(s v), -2 f16(s v), fl32(s^2 |v|^2) and its per-image maximum
+  DevBuf<unsigned short> th16, qh16;     // [count][128]
+  DevBuf<float> n2s, rerr;               // [count]  fl32(s^2 |v|^2), |s v - f16(s v)|_2 (rounded up)
+  float n2s_max = 0.f, rerr_max = 0.f;   // host copies of their maxima
+  int f16_exp = INT_MIN;                 // log2 of the scale the f16 forms were made with (INT_MIN: none)
+  // the blocks every image of `rows` features has from its upload on (the f16 forms are made at match time)
+  hipError_t alloc(size_t rows, bool with_kp) {
+    return hip_first_error({with_kp ? kp.alloc(2 * rows) : hipSuccess, f32.alloc(rows * DIM), ti8.alloc(rows * DIM), qi8.alloc(rows * DIM),
+                            tcin.alloc(rows), tpar.alloc(rows), qbeta.alloc(rows)});
+  }
+  void swap(DescImage& o) {
+    std::swap(count, o.count); std::swap(has_kp, o.has_kp); std::swap(n2s_max, o.n2s_max); std::swap(rerr_max, o.rerr_max); std::swap(f16_exp, o.f16_exp);
+    f32.swap(o.f32); kp.swap(o.kp); ti8.swap(o.ti8); qi8.swap(o.qi8); tcin.swap(o.tcin); tpar.swap(o.tpar); qbeta.swap(o.qbeta);
+    th16.swap(o.th16); qh16.swap(o.qh16); n2s.swap(o.n2s); rerr.swap(o.rerr);
+  }
+};
+
 struct msfm_match_result;
-static void orphan_result(msfm_match_result* R);
 struct msfm_descset {
   msfm_ctx* ctx;
   int n_images, dim;
   std::vector<msfm_match_result*> results;   // live results of this set: orphaned (set = nullptr) when the set is destroyed first
-  std::vector<DevBuf<float>*> kp;            // [count][2] keypoint positions (msfm_descset_upload_keypoints), nullptr: none
-  std::vector<int> count;
-  std::vector<DevBuf<float>*> f32;       // [count][dim]
-  // int8 forms for the i8 MFMA kernel: train rows a-128, query rows 127-b, and the per-row terms of
-  //   |a-b|^2 = 2 sum (a-128)(127-b) + sum (a-127)^2 + sum (128-b)^2 - 128
-  std::vector<DevBuf<signed char>*> ti8, qi8;   // [count][128]
-  std::vector<DevBuf<int>*> tcin, tpar, qbeta;  // (alpha>>1)+2^21 ; alpha&1 ; beta
-  // f16 forms for non-integral descriptors (made at match time, once the common power-of-two scale is known):
-  // f16(s v), -2 f16(s v), fl32(s^2 |v|^2) and its per-image maximum
-  std::vector<DevBuf<unsigned short>*> th16, qh16;  // [count][128]
-  std::vector<DevBuf<float>*> n2s, rerr;            // [count]  fl32(s^2 |v|^2), |s v - f16(s v)|_2 (rounded up)
-  std::vector<float> n2s_max, rerr_max;             // per image (host copies)
-  std::vector<int> f16_exp;                         // log2 of the scale an image's f16 forms were made with (INT_MIN: none)
+  std::unique_ptr<DescImage[]> img;          // [n_images], sized once at create (a DevBuf neither copies nor moves)
   float vabs_max = 0.f;                             // largest |value| uploaded so far
   DevBuf<unsigned> vmax_dev, n2smax_dev;            // [1], [2 n_images]: n2s maxima, then rerr maxima
   DevBuf<signed char> zero_row;          // 128 zero bytes (k_knn2_i8 reads them for train rows past the end)
@@ -58,8 +73,9 @@ struct msfm_descset {
   // bumped by every upload: a match result remembers the generation its device pointer tables were built at and
   // refuses to run or to be read once an image has been replaced under it
   unsigned long generation = 0;
-  // bumped by every keypoint upload: the gate tables of a SLAM match result hold raw pointers into kp[]
+  // bumped by every keypoint upload: the gate tables of a SLAM match result hold raw pointers into the images' kp
   unsigned long kp_generation = 0;
+  ~msfm_descset();   // orphans the live results
 };
 
 // ---- prep: integrality flag, largest |value| -----------------------------------------------
@@ -1043,50 +1059,22 @@ MSFM_API int msfm_descset_create(msfm_ctx* ctx, int n_images, int dim, msfm_desc
   if (!ctx || !out || n_images <= 0) return MSFM_E_INVAL;
   if (dim != DIM) return msfm_set_error(ctx, MSFM_E_INVAL, "descriptor dim %d not supported (128 = SIFT)", dim);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<msfm_descset> s(new msfm_descset());
-  DevScope sc(ctx);   // (a failed create deletes the set)
-  s->ctx = ctx; s->n_images = n_images; s->dim = dim;
-  s->count.assign(n_images, 0);
-  s->kp.assign(n_images, nullptr);
-  s->f32.assign(n_images, nullptr);
-  s->th16.assign(n_images, nullptr); s->qh16.assign(n_images, nullptr); s->n2s.assign(n_images, nullptr); s->n2s_max.assign(n_images, 0.f);
-  s->rerr.assign(n_images, nullptr); s->rerr_max.assign(n_images, 0.f);
-  s->f16_exp.assign(n_images, INT_MIN);
-  s->ti8.assign(n_images, nullptr); s->qi8.assign(n_images, nullptr); s->tcin.assign(n_images, nullptr); s->tpar.assign(n_images, nullptr); s->qbeta.assign(n_images, nullptr);
+  Child<msfm_descset> s = child_new<msfm_descset>(ctx);
+  s->n_images = n_images; s->dim = dim;
+  s->img.reset(new DescImage[n_images]);
   if (s->vmax_dev.alloc(1) != hipSuccess || s->n2smax_dev.alloc(2 * (size_t)n_images) != hipSuccess || s->nonint.alloc(1) != hipSuccess ||
       s->zero_row.alloc(256) != hipSuccess || hipMemsetAsync(s->zero_row.p, 0, 256, ctx->stream) != hipSuccess ||
       hipMemsetAsync(s->nonint.p, 0, sizeof(int), ctx->stream) != hipSuccess || hipMemsetAsync(s->vmax_dev.p, 0, sizeof(unsigned), ctx->stream) != hipSuccess)
     return msfm_set_error(ctx, MSFM_E_NOMEM, "descset alloc");
-  ctx->children++;   // only a set that exists counts: a failed create must not keep the context alive for good
   *out = s.release();
-  sc.dismiss();   // the set keeps its blocks
   return MSFM_OK;
 }
 
-MSFM_API void msfm_descset_destroy(msfm_descset* s) {
-  if (!s) return;
-  msfm_ctx* ctx = s->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  for (msfm_match_result* r : s->results) orphan_result(r);   // their codes / counts stay readable, a rerun is refused
-  for (auto p : s->kp) delete p;
-  for (auto p : s->f32) delete p;
-  for (auto p : s->th16) delete p;
-  for (auto p : s->qh16) delete p;
-  for (auto p : s->n2s) delete p;
-  for (auto p : s->rerr) delete p;
-  for (auto p : s->ti8) delete p;
-  for (auto p : s->qi8) delete p;
-  for (auto p : s->tcin) delete p;
-  for (auto p : s->tpar) delete p;
-  for (auto p : s->qbeta) delete p;
-  delete s;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_descset_destroy(msfm_descset* s) { msfm_child_destroy(s); }
 
 MSFM_API int msfm_descset_count(const msfm_descset* s, int image) {
   if (!s || image < 0 || image >= s->n_images) return MSFM_E_INVAL;
-  return s->count[image];
+  return s->img[image].count;
 }
 
 // The device-array core of msfm_descset_upload: replaces the image's rows by what `fill` enqueues into the new blocks (rows
@@ -1101,31 +1089,23 @@ int descset_put_dev(msfm_descset* s, int image, int count, bool with_kp, const c
   // after their stream has drained (common.h)
   HIP_TRY(ctx, hipStreamSynchronize(st));
   s->generation++;
-  delete s->kp[image]; s->kp[image] = nullptr;   // positions belong to the features they were uploaded with
-  s->kp_generation++;
-  delete s->f32[image];
-  delete s->th16[image]; delete s->qh16[image]; delete s->n2s[image]; delete s->rerr[image];
-  s->th16[image] = new DevBuf<unsigned short>(); s->qh16[image] = new DevBuf<unsigned short>(); s->n2s[image] = new DevBuf<float>();
-  s->rerr[image] = new DevBuf<float>();
-  s->n2s_max[image] = 0.f;
-  s->f16_exp[image] = INT_MIN;
-  delete s->ti8[image]; delete s->qi8[image]; delete s->tcin[image]; delete s->tpar[image]; delete s->qbeta[image];
-  s->f32[image] = new DevBuf<float>();
-  s->ti8[image] = new DevBuf<signed char>(); s->qi8[image] = new DevBuf<signed char>();
-  s->tcin[image] = new DevBuf<int>(); s->tpar[image] = new DevBuf<int>(); s->qbeta[image] = new DevBuf<int>();
-  s->count[image] = count;
-  if (with_kp) s->kp[image] = new DevBuf<float>();
+  s->kp_generation++;   // positions belong to the features they were uploaded with
+  DescImage& im = s->img[image];
+  { DescImage old; im.swap(old); }   // the old blocks go back behind the wait above, in front of the allocations that may reuse them
+  {
+    // the new image is built beside the set's and swapped in only with every block in hand: an allocation that fails leaves the
+    // image empty, never one that claims rows over blocks it does not have
+    DescImage nu;
+    if (count) HIP_TRY(ctx, nu.alloc((size_t)count, with_kp));
+    nu.count = count; nu.has_kp = with_kp;
+    im.swap(nu);
+  }
   if (count == 0) return MSFM_OK;
-  if (with_kp) HIP_TRY(ctx, s->kp[image]->alloc(2 * (size_t)count));
-  HIP_TRY(ctx, s->f32[image]->alloc((size_t)count * DIM));
-  HIP_TRY(ctx, s->ti8[image]->alloc((size_t)count * DIM)); HIP_TRY(ctx, s->qi8[image]->alloc((size_t)count * DIM));
-  HIP_TRY(ctx, s->tcin[image]->alloc(count)); HIP_TRY(ctx, s->tpar[image]->alloc(count)); HIP_TRY(ctx, s->qbeta[image]->alloc(count));
-  HIP_TRY(ctx, fill(s->f32[image]->p, with_kp ? s->kp[image]->p : nullptr, st));
+  HIP_TRY(ctx, fill(im.f32.p, with_kp ? im.kp.p : nullptr, st));
   KTimer t(prep_stat ? ctx : nullptr, prep_stat ? prep_stat : "");
   t.count = 2;
-  hipLaunchKernelGGL(k_desc_prep, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->nonint.p, s->vmax_dev.p);
-  hipLaunchKernelGGL(k_desc_prep_i8, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[image]->p, count, s->ti8[image]->p,
-                     s->qi8[image]->p, s->tcin[image]->p, s->tpar[image]->p, s->qbeta[image]->p);
+  hipLaunchKernelGGL(k_desc_prep, dim3(cdiv(count, 4)), dim3(256), 0, st, im.f32.p, count, s->nonint.p, s->vmax_dev.p);
+  hipLaunchKernelGGL(k_desc_prep_i8, dim3(cdiv(count, 4)), dim3(256), 0, st, im.f32.p, count, im.ti8.p, im.qi8.p, im.tcin.p, im.tpar.p, im.qbeta.p);
   HIP_TRY(ctx, hipGetLastError());
   t.stop();
   unsigned vbits = 0;
@@ -1146,13 +1126,14 @@ MSFM_API int msfm_descset_upload(msfm_descset* s, int image, const float* desc, 
 MSFM_API int msfm_descset_fetch(const msfm_descset* s, int image, float* desc, float* xy) {
   if (!s || image < 0 || image >= s->n_images) return MSFM_E_INVAL;
   msfm_ctx* ctx = s->ctx;
-  const size_t count = (size_t)s->count[image];
-  if (xy && count && !(s->kp[image] && s->kp[image]->p)) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_descset_fetch: image %d has no keypoints", image);
+  const DescImage& im = s->img[image];
+  const size_t count = (size_t)im.count;
+  if (xy && count && !(im.has_kp && im.kp.p)) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_descset_fetch: image %d has no keypoints", image);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   DevScope sc(ctx);
   if (count) {
-    HIP_TRY(ctx, sc.down(desc, s->f32[image]->p, count * DIM));
-    if (xy) HIP_TRY(ctx, sc.down(xy, s->kp[image]->p, 2 * count));
+    HIP_TRY(ctx, sc.down(desc, im.f32.p, count * DIM));
+    if (xy) HIP_TRY(ctx, sc.down(xy, im.kp.p, 2 * count));
   }
   HIP_TRY(ctx, sc.finish());
   return MSFM_OK;
@@ -1173,18 +1154,19 @@ static int ensure_f16_forms(msfm_descset* s) {
   const float scale = ldexpf(1.0f, e);
   bool any = false;
   for (int i = 0; i < s->n_images; i++) {
-    if (s->count[i] == 0 || s->f16_exp[i] == e) continue;
-    const int count = s->count[i];
+    DescImage& im = s->img[i];
+    if (im.count == 0 || im.f16_exp == e) continue;
+    const int count = im.count;
     if (!any) HIP_TRY(ctx, hipMemsetAsync(s->n2smax_dev.p, 0, sizeof(unsigned) * 2 * s->n_images, st));
     any = true;
-    if (s->th16[i]->n != (size_t)count * DIM) {
-      HIP_TRY(ctx, s->th16[i]->alloc((size_t)count * DIM)); HIP_TRY(ctx, s->qh16[i]->alloc((size_t)count * DIM));
-      HIP_TRY(ctx, s->n2s[i]->alloc(count)); HIP_TRY(ctx, s->rerr[i]->alloc(count));
+    if (im.th16.n != (size_t)count * DIM) {
+      HIP_TRY(ctx, im.th16.alloc((size_t)count * DIM)); HIP_TRY(ctx, im.qh16.alloc((size_t)count * DIM));
+      HIP_TRY(ctx, im.n2s.alloc(count)); HIP_TRY(ctx, im.rerr.alloc(count));
     }
-    hipLaunchKernelGGL(k_desc_prep_f16, dim3(cdiv(count, 4)), dim3(256), 0, st, s->f32[i]->p, count, scale, s->th16[i]->p, s->qh16[i]->p,
-                       s->n2s[i]->p, s->rerr[i]->p, s->n2smax_dev.p + i, s->n2smax_dev.p + s->n_images + i);
-    s->f16_exp[i] = e;
-    s->n2s_max[i] = -1.f;   // to be read back
+    hipLaunchKernelGGL(k_desc_prep_f16, dim3(cdiv(count, 4)), dim3(256), 0, st, im.f32.p, count, scale, im.th16.p, im.qh16.p, im.n2s.p, im.rerr.p,
+                       s->n2smax_dev.p + i, s->n2smax_dev.p + s->n_images + i);
+    im.f16_exp = e;
+    im.n2s_max = -1.f;   // to be read back
   }
   if (any) {
     HIP_TRY(ctx, hipGetLastError());
@@ -1192,7 +1174,7 @@ static int ensure_f16_forms(msfm_descset* s) {
     HIP_TRY(ctx, hipMemcpyAsync(bits.data(), s->n2smax_dev.p, sizeof(unsigned) * bits.size(), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     for (int i = 0; i < s->n_images; i++)
-      if (s->n2s_max[i] < 0.f) { memcpy(&s->n2s_max[i], &bits[i], sizeof(float)); memcpy(&s->rerr_max[i], &bits[s->n_images + i], sizeof(float)); }
+      if (s->img[i].n2s_max < 0.f) { memcpy(&s->img[i].n2s_max, &bits[i], sizeof(float)); memcpy(&s->img[i].rerr_max, &bits[s->n_images + i], sizeof(float)); }
   }
   return MSFM_OK;
 }
@@ -1237,7 +1219,7 @@ __global__ __launch_bounds__(256) void k_slam_gate(const SlamGateTask* __restric
 }
 
 struct msfm_match_result {
-  msfm_descset* set;
+  msfm_descset* set = nullptr;   // from the hand-over on: the set knows the result (~msfm_match_result unlinks it)
   msfm_ctx* ctx = nullptr;   // kept separately: the descriptor set may be destroyed before its results
   int n_pairs = 0;
   long total_q = 0;
@@ -1260,11 +1242,16 @@ struct msfm_match_result {
   DevBuf<SlamGateTask> gate_tasks;
   int gate_max_nq = 0;
   double th_epipolar = 0, th_homography = 0;
+  ~msfm_match_result() {
+    if (set) set->results.erase(std::remove(set->results.begin(), set->results.end(), this), set->results.end());
+  }
 };
 
-// The set is going away before one of its results: the result keeps what it owns (codes, counts, 2-NN arrays) and its
-// context; everything that would read the set's descriptors (rerun, the slow-path kernels) is refused from now on.
-static void orphan_result(msfm_match_result* R) { R->set = nullptr; }
+// The set is going away before its results: each keeps what it owns (codes, counts, 2-NN arrays) and its context; everything
+// that would read the set's descriptors (rerun, the slow-path kernels) is refused from now on.
+msfm_descset::~msfm_descset() {
+  for (msfm_match_result* r : results) r->set = nullptr;
+}
 
 static int check_generation(const msfm_match_result* R) {
   if (!R->set) return msfm_set_error(R->ctx, MSFM_E_INVAL, "the descriptor set of this match result has been destroyed");
@@ -1324,17 +1311,14 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   for (int p = 0; p < n_pairs; p++) {
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
     if (a < 0 || a >= s->n_images || b < 0 || b >= s->n_images) return msfm_set_error(ctx, MSFM_E_INVAL, "pair %d: image index out of range", p);
-    if (s->count[a] < 2) return msfm_set_error(ctx, MSFM_E_INVAL, "pair %d: train image %d has %d < 2 descriptors", p, a, s->count[a]);
-    if (slam && (!s->kp[a] || (s->count[b] > 0 && !s->kp[b])))
+    if (s->img[a].count < 2) return msfm_set_error(ctx, MSFM_E_INVAL, "pair %d: train image %d has %d < 2 descriptors", p, a, s->img[a].count);
+    if (slam && (!s->img[a].has_kp || (s->img[b].count > 0 && !s->img[b].has_kp)))
       return msfm_set_error(ctx, MSFM_E_INVAL, "pair %d: the prior F / H gates need the keypoints of both images (msfm_descset_upload_keypoints)", p);
   }
-  msfm_match_result* R = new msfm_match_result();
-  struct Guard { msfm_match_result* p; msfm_ctx* c; ~Guard() { if (p) { delete p; msfm_ctx_child_released(c); } } } guard{R, ctx};
-  DevScope sc(ctx);   // (an error return deletes the result)
-  ctx->children++;
+  Child<msfm_match_result> own = child_new<msfm_match_result>(ctx);
+  msfm_match_result* R = own.get();
   R->generation = s->generation;
   R->kp_generation = s->kp_generation;
-  R->ctx = ctx;
   R->set = s; R->n_pairs = n_pairs; R->keep_knn = keep_knn != 0; R->ratio_good = ratio_good; R->ratio_all = ratio_all;
   R->pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
   R->exact_path = s->h_nonint != 0;
@@ -1348,23 +1332,24 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   long tiles = 0;
   for (int p = 0; p < n_pairs; p++) {
     const int a = pairs[2 * p], b = pairs[2 * p + 1];
-    const int nq = s->count[b];
+    const DescImage &A = s->img[a], &B = s->img[b];
+    const int nq = B.count;
     R->out_off.push_back((int)off);
     R->nq.push_back(nq);
     tile_first[p] = (int)tiles;
-    tasks8[p] = PairTask8{s->ti8[a]->p, nq ? s->qi8[b]->p : nullptr, s->tcin[a]->p, s->tpar[a]->p, nq ? s->qbeta[b]->p : nullptr, s->count[a], nq, (int)off, s->zero_row.p};
+    tasks8[p] = PairTask8{A.ti8.p, nq ? B.qi8.p : nullptr, A.tcin.p, A.tpar.p, nq ? B.qbeta.p : nullptr, A.count, nq, (int)off, s->zero_row.p};
     pair_off[p] = (int)off;
     if (certified) {
-      const float ex = (float)s->f16_exp[a];
-      const double a2max = s->n2s_max[a], b2max = nq ? s->n2s_max[b] : 0.0;
+      const float ex = (float)A.f16_exp;
+      const double a2max = A.n2s_max, b2max = nq ? B.n2s_max : 0.0;
       // SHIFT >= max |b|^2 + 2 E keeps every accumulator positive; E itself depends (weakly) on SHIFT: two sweeps settle it
       double shift = b2max;
-      for (int it = 0; it < 3; it++) shift = b2max + 2.0 * f16_error_bound(a2max, s->rerr_max[a], b2max, nq ? s->rerr_max[b] : 0.0, shift * 1.001);
+      for (int it = 0; it < 3; it++) shift = b2max + 2.0 * f16_error_bound(a2max, A.rerr_max, b2max, nq ? B.rerr_max : 0.0, shift * 1.001);
       float shift_f = (float)(shift * 1.001);
       shift_f = nextafterf(shift_f, INFINITY);
       if (p == 0 || pairs[2 * (p - 1)] != a) group_first.push_back(p);   // a new train image starts a new group
-      tasksh[p] = PairTaskH{s->th16[a]->p, nq ? s->qh16[b]->p : nullptr, s->n2s[a]->p, nq ? s->n2s[b]->p : nullptr, nq ? s->rerr[b]->p : nullptr,
-                            s->f32[a]->p, nq ? s->f32[b]->p : nullptr, (float)a2max, s->rerr_max[a], shift_f, ldexpf(1.0f, 2 * (int)ex), s->count[a], nq,
+      tasksh[p] = PairTaskH{A.th16.p, nq ? B.qh16.p : nullptr, A.n2s.p, nq ? B.n2s.p : nullptr, nq ? B.rerr.p : nullptr,
+                            A.f32.p, nq ? B.f32.p : nullptr, (float)a2max, A.rerr_max, shift_f, ldexpf(1.0f, 2 * (int)ex), A.count, nq,
                             (int)off, (int)group_first.size() - 1, pair_off[group_first.back()]};
     }
     off += nq;
@@ -1395,7 +1380,7 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
     std::vector<SlamGateTask> gt(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
       const int a = pairs[2 * p], b = pairs[2 * p + 1];
-      gt[p].kp1 = s->kp[a]->p; gt[p].kp2 = R->nq[p] ? s->kp[b]->p : nullptr; gt[p].nq = R->nq[p]; gt[p].off = R->out_off[p];
+      gt[p].kp1 = s->img[a].kp.p; gt[p].kp2 = R->nq[p] ? s->img[b].kp.p : nullptr; gt[p].nq = R->nq[p]; gt[p].off = R->out_off[p];
       for (int k = 0; k < 9; k++) { gt[p].F[k] = Fs[9 * (size_t)p + k]; gt[p].H[k] = Hs[9 * (size_t)p + k]; }
       R->gate_max_nq = std::max(R->gate_max_nq, R->nq[p]);
     }
@@ -1407,10 +1392,8 @@ static int match_pairs_impl(msfm_descset* s, const int* pairs, int n_pairs, floa
   }
   HIP_TRY(ctx, hipStreamSynchronize(st));
   MSFM_TRY(launch_match(R));
-  guard.p = nullptr;
-  sc.dismiss();   // the result keeps its blocks
   s->results.push_back(R);
-  *out = R;
+  *out = own.release();
   return MSFM_OK;
 }
 
@@ -1436,27 +1419,27 @@ MSFM_API int msfm_match_pairs_slam(msfm_descset* s, const int* pairs, int n_pair
 MSFM_API int msfm_descset_upload_keypoints(msfm_descset* s, int image, const float* xy, int count) {
   if (!s || image < 0 || image >= s->n_images || count < 0 || (count > 0 && !xy)) return MSFM_E_INVAL;
   msfm_ctx* ctx = s->ctx;
-  if (count != s->count[image])
-    return msfm_set_error(ctx, MSFM_E_INVAL, "image %d has %d descriptors, %d keypoints given (upload the descriptors first)", image, s->count[image], count);
+  DescImage& im = s->img[image];
+  if (count != im.count)
+    return msfm_set_error(ctx, MSFM_E_INVAL, "image %d has %d descriptors, %d keypoints given (upload the descriptors first)", image, im.count, count);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // a gate kernel may still be reading the old positions
   s->kp_generation++;   // SLAM results built on the old positions refuse to run from now on (check_generation)
-  delete s->kp[image];
-  s->kp[image] = new DevBuf<float>();
+  im.has_kp = false;   // (until the block is there: an allocation that fails leaves the image without keypoints)
+  HIP_TRY(ctx, im.kp.alloc(2 * (size_t)count));
+  im.has_kp = true;
   if (count == 0) return MSFM_OK;
-  HIP_TRY(ctx, s->kp[image]->alloc(2 * (size_t)count));
-  HIP_TRY(ctx, s->kp[image]->upload(xy, 2 * (size_t)count, ctx->stream));
+  HIP_TRY(ctx, im.kp.upload(xy, 2 * (size_t)count, ctx->stream));
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the caller's buffer is not retained
   return MSFM_OK;
 }
 
 void descset_view(const msfm_descset* s, DescView* v) {
   v->ctx = s->ctx; v->n_images = s->n_images; v->generation = s->generation;
-  v->count = s->count;
-  v->f32.assign(s->n_images, nullptr); v->kp.assign(s->n_images, nullptr);
+  v->count.resize(s->n_images); v->f32.resize(s->n_images); v->kp.resize(s->n_images);
   for (int i = 0; i < s->n_images; i++) {
-    if (s->f32[i] && s->count[i] > 0) v->f32[i] = s->f32[i]->p;
-    if (s->kp[i]) v->kp[i] = s->kp[i]->p;   // (an image of no features: a DevBuf with a null block)
+    const DescImage& im = s->img[i];
+    v->count[i] = im.count; v->f32[i] = im.f32.p; v->kp[i] = im.kp.p;   // (no features, or no keypoints: no block)
   }
 }
 
@@ -1467,9 +1450,8 @@ int match_result_view(msfm_match_result* R, MatchView* v) {
   v->ctx = R->ctx; v->n_images = s->n_images; v->n_pairs = R->n_pairs; v->total_q = R->total_q;
   v->pairs = R->pairs.data(); v->out_off = R->out_off.data(); v->nq = R->nq.data();
   v->code = R->code.p; v->n_all = R->n_all.p; v->n_good = R->n_good.p;
-  v->count = s->count;
-  v->kp.assign(s->n_images, nullptr);
-  for (int i = 0; i < s->n_images; i++) if (s->kp[i]) v->kp[i] = s->kp[i]->p;
+  v->count.resize(s->n_images); v->kp.resize(s->n_images);
+  for (int i = 0; i < s->n_images; i++) { v->count[i] = s->img[i].count; v->kp[i] = s->img[i].kp.p; }
   v->slam = R->slam;
   return MSFM_OK;
 }
@@ -1519,18 +1501,7 @@ MSFM_API int msfm_match_result_stats(msfm_match_result* R, int* n_queries, int* 
   return MSFM_OK;
 }
 
-MSFM_API void msfm_match_result_destroy(msfm_match_result* R) {
-  if (!R) return;
-  msfm_ctx* ctx = R->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (R->set) {
-    auto& v = R->set->results;
-    v.erase(std::remove(v.begin(), v.end(), R), v.end());
-  }
-  delete R;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_match_result_destroy(msfm_match_result* R) { msfm_child_destroy(R); }
 
 // The FLANN-shaped entry point: one train set, one query set, host buffers in and out.
 MSFM_API int msfm_knn2_f32(msfm_ctx* ctx, const float* train, int n_train, const float* query, int n_query, int dim, int* ids,

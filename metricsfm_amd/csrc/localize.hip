@@ -236,18 +236,17 @@ MSFM_API int msfm_match_store_create(msfm_ctx* ctx, int n_images, const int* n_f
   const int M = n_pairs ? match_off[n_pairs] : 0;
   if (M < 0 || (M > 0 && !matches)) return msfm_set_error(ctx, MSFM_E_INVAL, "msfm_match_store_create: null matches");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<msfm_match_store> S(new msfm_match_store());
-  S->ctx = ctx; S->n_images = n_images; S->n_pairs = n_pairs; S->M = M;
+  Child<msfm_match_store> S = child_new<msfm_match_store>(ctx);
+  S->n_images = n_images; S->n_pairs = n_pairs; S->M = M;
   S->n_features.assign(n_features, n_features + n_images);
   S->pair_img.assign(pair_img, pair_img + 2 * (size_t)n_pairs);
   if (n_pairs) S->match_off.assign(match_off, match_off + n_pairs + 1); else S->match_off.assign(1, 0);
   S->has_kp.assign(std::max(1, n_images), 0);
-  DevScope sc(ctx);   // (an error return deletes the store: the upload is over before its block goes back)
+  DevScope sc(ctx);
   LC_TRY(S->d_match.alloc(2 * (size_t)std::max(1, M)));
   LC_TRY(S->d_match.upload(matches, 2 * (size_t)M, ctx->stream));
   MSFM_TRY(store_finish(ctx, S.get(), "msfm_match_store_create"));
   LC_TRY(sc.finish());
-  ctx->children++;
   *out = S.release();
   return MSFM_OK;
 }
@@ -260,8 +259,8 @@ MSFM_API int msfm_match_store_from_chain(msfm_chain* chain, msfm_match_store** o
   msfm_ctx* ctx = v.ctx;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  std::unique_ptr<msfm_match_store> S(new msfm_match_store());
-  S->ctx = ctx; S->n_images = v.n_images; S->n_pairs = v.n_pairs; S->M = v.match_off[v.n_pairs];
+  Child<msfm_match_store> S = child_new<msfm_match_store>(ctx);
+  S->n_images = v.n_images; S->n_pairs = v.n_pairs; S->M = v.match_off[v.n_pairs];
   S->n_features.assign(v.count, v.count + v.n_images);
   S->pair_img.assign(v.pairs, v.pairs + 2 * (size_t)v.n_pairs);
   S->match_off.assign(v.match_off, v.match_off + v.n_pairs + 1);
@@ -276,19 +275,11 @@ MSFM_API int msfm_match_store_from_chain(msfm_chain* chain, msfm_match_store** o
   if (nf) LC_TRY(hipMemcpyAsync(S->d_kp.p, v.d_kp, sizeof(float) * 2 * (size_t)nf, hipMemcpyDeviceToDevice, s));
   MSFM_TRY(store_finish(ctx, S.get(), "msfm_match_store_from_chain"));
   LC_TRY(sc.finish());
-  ctx->children++;
   *out = S.release();
   return MSFM_OK;
 }
 
-MSFM_API void msfm_match_store_destroy(msfm_match_store* S) {
-  if (!S) return;
-  msfm_ctx* ctx = S->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  delete S;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_match_store_destroy(msfm_match_store* S) { msfm_child_destroy(S); }
 
 // The call on device arrays: with `dev` the bulk arrays of the state (feat_point, pt_bad, pt_mse, pt_views, point_xyz, keypoints)
 // are the caller's resident ones - P then carries counts and the O(cameras + candidates) lists only - and the set keeps its
@@ -348,12 +339,10 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     }
   }
   const int nwp = (int)wp.size();
-  std::unique_ptr<msfm_localize_set> R(new msfm_localize_set());
-  R->ctx = ctx;
+  Child<msfm_localize_set> R = child_new<msfm_localize_set>(ctx);
   R->have_pts = want_pts;
   R->corr_off.assign(1, 0); R->vis_off.assign(1, 0);
-  auto hand_over = [&]() { ctx->children++; *out = R.release(); return MSFM_OK; };   // a set is a child of its context, like a store
-  if (nk == 0) return hand_over();
+  if (nk == 0) { *out = R.release(); return MSFM_OK; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const msfm_env env = msfm_env_read();
@@ -424,7 +413,7 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
     R->vis_off.push_back((int)R->vis_cam.size());
   }
   R->h2d_bytes = sc.h2d;
-  if (T == 0) { sc.dismiss(); return hand_over(); }   // (behind the wait above: nothing has been enqueued since)
+  if (T == 0) { sc.dismiss(); *out = R.release(); return MSFM_OK; }   // (behind the wait above: nothing has been enqueued since)
   // ---- emit, sort, gather ----
   std::vector<int> kp_off(nk, 0);
   const float* d_kp = nullptr;
@@ -495,7 +484,8 @@ int localize_candidates_dev(msfm_ctx* ctx, const char* who, const msfm_match_sto
   R->h2d_bytes = sc.h2d;
   if (want_pts) { R->d_cp.swap(d_cp); R->d_pw.swap(d_pw); R->d_p2.swap(d_p2); }   // resident for msfm_localize_poses
   if (dev) R->d_cf.swap(d_cf);   // (a resident state commits the winner's row from the device)
-  return hand_over();
+  *out = R.release();
+  return MSFM_OK;
 }
 
 MSFM_API int msfm_localize_candidates(msfm_ctx* ctx, const msfm_match_store* S, const msfm_localize_problem* P, msfm_localize_set** out) {
@@ -527,13 +517,4 @@ MSFM_API int msfm_localize_set_fetch(const msfm_localize_set* R, int* rank, int*
   return MSFM_OK;
 }
 
-MSFM_API void msfm_localize_set_destroy(msfm_localize_set* R) {
-  if (!R) return;
-  msfm_ctx* ctx = R->ctx;
-  if (R->d_cp.p) {   // blocks go back to the pool only behind the work that may still read them
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-  }
-  delete R;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_localize_set_destroy(msfm_localize_set* R) { msfm_child_destroy(R); }

@@ -300,8 +300,8 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
                        const int* d_word, DevBuf<float>& d_kp, int64_t h2d_bytes, msfm_wordset** out) {
   using namespace pairsel;
   const int total = feat_off[n];
-  std::unique_ptr<msfm_wordset> W(new msfm_wordset());
-  W->ctx = ctx; W->n = n; W->K = K; W->num_words = num_words;
+  Child<msfm_wordset> W = child_new<msfm_wordset>(ctx);
+  W->n = n; W->K = K; W->num_words = num_words;
   W->feat_off = feat_off;
   W->map_off.assign(n + 1, 0);
   hipStream_t s = ctx->stream;
@@ -385,7 +385,6 @@ int wordset_create_dev(msfm_ctx* ctx, int n, int K, int num_words, const std::ve
   W->h2d_bytes = h2d_bytes;
   W->d_feat_off.swap(d_feat_off); W->d_map_off.swap(d_map_off); W->d_map_word.swap(d_map_word); W->d_map_feat.swap(d_map_feat);
   W->d_kp.swap(d_kp); W->d_S.swap(d_S); W->d_hyp_img.swap(d_hyp_img); W->d_hyp_sim.swap(d_hyp_sim);
-  ctx->children++;
   *out = W.release();
   return MSFM_OK;
 }
@@ -417,14 +416,7 @@ MSFM_API int msfm_wordset_fetch(const msfm_wordset* W, int32_t* similarity, int3
   return MSFM_OK;
 }
 
-MSFM_API void msfm_wordset_destroy(msfm_wordset* W) {
-  if (!W) return;
-  msfm_ctx* ctx = W->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);   // blocks go back to the pool only behind the work that may still read them
-  delete W;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_wordset_destroy(msfm_wordset* W) { msfm_child_destroy(W); }
 
 MSFM_API int msfm_pair_select(msfm_wordset* W, int first, int n_rows, const msfm_pair_select_options* opt_in, msfm_pair_set** out) {
   using namespace pairsel;

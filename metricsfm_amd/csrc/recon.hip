@@ -244,8 +244,8 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   const int FP = T.cam_fo[nc];
   if (FP && !P->feat_point) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null feat_point", who);
   MSFM_TRY(round_key_check(ctx, who, nc, T));
-  std::unique_ptr<msfm_recon> Q(new msfm_recon());
-  Q->ctx = ctx; Q->store = S;
+  Child<msfm_recon> Q = child_new<msfm_recon>(ctx);
+  Q->store = S;
   Q->n_cams = nc; Q->n_models = nm; Q->n_points = np; Q->n_obs = no;
   Q->cap_points = std::max<size_t>(1, std::max((size_t)np, (size_t)P->reserve_points));
   Q->cap_obs = std::max<size_t>(1, std::max((size_t)no, (size_t)P->reserve_obs));
@@ -259,7 +259,7 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   RC_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<int> d_fo, d_err;
-  DevScope sc(ctx);   // (Q's blocks too: an error return deletes the object)
+  DevScope sc(ctx);
   RC_TRY(sc.up(Q->d_fp, P->feat_point, (size_t)FP, total));
   RC_TRY(sc.up(Q->d_op, P->obs_point, nox, Q->cap_obs)); RC_TRY(sc.up(Q->d_oc, P->obs_cam, nox, Q->cap_obs)); RC_TRY(sc.up(Q->d_of, P->obs_feat, nox, Q->cap_obs));
   RC_TRY(sc.up(Q->d_xyz, P->point_xyz, 3 * npx, 3 * Q->cap_points)); RC_TRY(sc.up(Q->d_mse, P->pt_mse, npx, Q->cap_points));
@@ -287,7 +287,6 @@ MSFM_API int msfm_recon_create(msfm_ctx* ctx, const msfm_match_store* S, const m
   if (err[0] != REC_BIG) return round_fp_error(ctx, who, T.cam_fo, nc, np, err[0]);
   if (err[1] != REC_BIG) return round_row_error(ctx, who, err[1], P->obs_point[err[1]], P->obs_cam[err[1]], P->obs_feat[err[1]]);
   Q->h2d_bytes = sc.h2d;
-  ctx->children++;   // a child of its context, like a store
   *out = Q.release();
   return MSFM_OK;
 }
@@ -315,8 +314,8 @@ MSFM_API int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* 
   const int w = W->winner, i1 = W->win_img[0], i2 = W->win_img[1];
   const int np = W->pt_off[w + 1] - W->pt_off[w], no = 2 * np;
   const int nf1 = S->n_features[i1], nf2 = S->n_features[i2];
-  std::unique_ptr<msfm_recon> Q(new msfm_recon());
-  Q->ctx = ctx; Q->store = S;
+  Child<msfm_recon> Q = child_new<msfm_recon>(ctx);
+  Q->store = S;
   Q->n_cams = 2; Q->n_models = nm; Q->n_points = np; Q->n_obs = no;
   Q->cap_points = std::max<size_t>(1, std::max((size_t)np, (size_t)reserve_points));
   Q->cap_obs = std::max<size_t>(1, std::max((size_t)no, (size_t)reserve_obs));
@@ -336,7 +335,7 @@ MSFM_API int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* 
   }
   RC_TRY(hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
-  DevScope sc(ctx);   // (Q's blocks too: an error return deletes the object)
+  DevScope sc(ctx);
   RC_TRY(Q->d_fp.alloc(std::max<size_t>(1, total)));
   RC_TRY(Q->d_op.alloc(Q->cap_obs)); RC_TRY(Q->d_oc.alloc(Q->cap_obs)); RC_TRY(Q->d_of.alloc(Q->cap_obs));
   RC_TRY(Q->d_xyz.alloc(3 * Q->cap_points)); RC_TRY(Q->d_mse.alloc(Q->cap_points)); RC_TRY(Q->d_views.alloc(Q->cap_points));
@@ -354,7 +353,6 @@ MSFM_API int msfm_recon_create_from_seed(msfm_ctx* ctx, const msfm_match_store* 
   RC_TRY(hipGetLastError());
   RC_TRY(sc.finish());   // the one wait: the set may be destroyed behind the call
   Q->h2d_bytes = sc.h2d;
-  ctx->children++;
   *out = Q.release();
   return MSFM_OK;
 }
@@ -470,8 +468,8 @@ MSFM_API int msfm_recon_adjust(msfm_recon* Q, int new_cam, int n_visible, const 
   RoundTables T;
   MSFM_TRY(round_tables(ctx, who, Q->store, A, /*packed_kp=*/false, opt, &T));
   MSFM_TRY(round_key_check(ctx, who, Q->n_cams, T));
-  std::unique_ptr<msfm_round_set> R(new msfm_round_set());
-  R->ctx = ctx; R->n_cams = Q->n_cams; R->n_models = Q->n_models; R->n_points = 0;   // the points stay where they are
+  Child<msfm_round_set> R = child_new<msfm_round_set>(ctx);
+  R->n_cams = Q->n_cams; R->n_models = Q->n_models; R->n_points = 0;   // the points stay where they are
   R->keep_problem = opt.keep_problem != 0;
   R->cam_pose = Q->cam_pose; R->cam_model = Q->cam_model;
   memset(R->summary, 0, sizeof R->summary);
@@ -490,7 +488,6 @@ MSFM_API int msfm_recon_adjust(msfm_recon* Q, int new_cam, int n_visible, const 
   Q->cam_R = R->cam_R; Q->cam_t = R->cam_t; Q->cam_c = R->cam_c; Q->cam_fk = R->cam_fk;
   Q->h2d_bytes += h2d;
   R->h2d_bytes = h2d;
-  ctx->children++;
   *out = R.release();
   return MSFM_OK;
 }
@@ -753,11 +750,4 @@ MSFM_API int msfm_recon_commit_camera(msfm_recon* Q, const double* cam_pose6, in
   return MSFM_OK;
 }
 
-MSFM_API void msfm_recon_destroy(msfm_recon* Q) {
-  if (!Q) return;
-  msfm_ctx* ctx = Q->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);   // the blocks go back to the pool behind what was enqueued on them
-  delete Q;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_recon_destroy(msfm_recon* Q) { msfm_child_destroy(Q); }

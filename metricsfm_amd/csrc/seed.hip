@@ -192,8 +192,8 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   if (opt.ransac_times_5pt < 1 || opt.ransac_times_5pt > 65536 || opt.ransac_times_8pt < 1 || opt.ransac_times_8pt > 65536)
     return msfm_set_error(ctx, MSFM_E_INVAL, "%s: ransac_times out of range", who);
   // ---- O(hypotheses) on the host: the store pair of each, its arm, the three CSRs, the block map ----
-  std::unique_ptr<msfm_seed_set> R(new msfm_seed_set());
-  R->ctx = ctx; R->store = S; R->n = n;
+  Child<msfm_seed_set> R = child_new<msfm_seed_set>(ctx);
+  R->store = S; R->n = n;
   R->arm.assign(n, 0); R->n_matches.assign(n, 0);
   std::vector<Hyp> hyp(n);
   std::vector<int> off_all(n + 1, 0), off5(n + 1, 0), off8(n + 1, 0), blk_off(n + 1, 0);
@@ -233,7 +233,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   const int M = off_all[n], M5 = off5[n], M8 = off8[n];
   R->pose_ok.assign(n, 0); R->pass.assign(n, 0); R->pt_off.assign(n + 1, 0);
   R->f.assign(2 * (size_t)n, 0.0); R->R.assign(9 * (size_t)n, 0.0); R->t.assign(3 * (size_t)n, 0.0); R->c.assign(3 * (size_t)n, 0.0);
-  if (n == 0) { ctx->children++; *out = R.release(); return MSFM_OK; }
+  if (n == 0) { *out = R.release(); return MSFM_OK; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   DevBuf<Hyp> d_hyp;
@@ -267,7 +267,7 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
   SD_TRY(d_ptm.alloc(Mx)); SD_TRY(d_X.alloc(3 * Mx)); SD_TRY(d_mse.alloc(Mx)); SD_TRY(d_count.alloc(n)); SD_TRY(d_pass.alloc(n));
   SD_TRY(d_win.alloc(1));
   SD_TRY(hipMemsetD32Async((hipDeviceptr_t)d_win.p, INT_MAX, 1, s));
-  if (longest) {   // (R's blocks: an error return deletes the set behind the scope's wait)
+  if (longest) {
     SD_TRY(R->d_ptm.alloc((size_t)longest)); SD_TRY(R->d_X.alloc(3 * (size_t)longest)); SD_TRY(R->d_mse.alloc((size_t)longest));
   }
   // an arm without a match is not launched: its hypotheses have failed (fewer than 5 / 8 matches)
@@ -346,7 +346,6 @@ MSFM_API int msfm_seed_hypotheses(msfm_ctx* ctx, const msfm_match_store* S, cons
     R->d_ptm.release(); R->d_X.release(); R->d_mse.release();
   }
   R->h2d_bytes = sc.h2d;
-  ctx->children++;   // a child of its context, like a store
   *out = R.release();
   return MSFM_OK;
 }
@@ -378,13 +377,4 @@ MSFM_API int msfm_seed_set_fetch(const msfm_seed_set* R, uint8_t* arm, uint8_t* 
   return MSFM_OK;
 }
 
-MSFM_API void msfm_seed_set_destroy(msfm_seed_set* R) {
-  if (!R) return;
-  msfm_ctx* ctx = R->ctx;
-  if (R->d_ptm.p) {   // blocks go back to the pool only behind the work that may still read them
-    (void)hipSetDevice(ctx->device);
-    (void)hipStreamSynchronize(ctx->stream);
-  }
-  delete R;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_seed_set_destroy(msfm_seed_set* R) { msfm_child_destroy(R); }

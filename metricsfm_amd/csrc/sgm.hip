@@ -367,8 +367,8 @@ MSFM_API int msfm_sgm_create(msfm_ctx* ctx, int width, int height, int disp_size
   const std::string bad = sgm_check_create(width, height, disp_size, p1, p2, uniqueness);
   if (!bad.empty()) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %s", who, bad.c_str());
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::unique_ptr<msfm_sgm> P(new msfm_sgm());
-  P->ctx = ctx; P->w = width; P->h = height; P->D = disp_size; P->P1 = p1; P->P2 = p2; P->uniqueness = uniqueness;
+  Child<msfm_sgm> P = child_new<msfm_sgm>(ctx);
+  P->w = width; P->h = height; P->D = disp_size; P->P1 = p1; P->P2 = p2; P->uniqueness = uniqueness;
   const size_t npx = P->npx();
   for (int r = 0; r < 8; r++) SG_ALLOC(P->vol[r].alloc(npx * disp_size));
   SG_ALLOC(P->img.alloc(2 * npx));
@@ -379,7 +379,6 @@ MSFM_API int msfm_sgm_create(msfm_ctx* ctx, int width, int height, int disp_size
     SG_ALLOC(hipHostMalloc((void**)&P->stage[i], 2 * npx));
     SG_TRY(hipEventCreateWithFlags(&P->staged[i], hipEventDisableTiming));
   }
-  ctx->children++;
   *out = P.release();
   return MSFM_OK;
 }
@@ -516,11 +515,4 @@ MSFM_API int msfm_sgm_size(const msfm_sgm* P, int* width, int* height, int* disp
   return MSFM_OK;
 }
 
-MSFM_API void msfm_sgm_destroy(msfm_sgm* P) {
-  if (!P) return;
-  msfm_ctx* ctx = P->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);   // blocks go back to the pool only behind the work that may still read them
-  delete P;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_sgm_destroy(msfm_sgm* P) { msfm_child_destroy(P); }

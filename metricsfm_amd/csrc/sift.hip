@@ -583,8 +583,8 @@ MSFM_API int msfm_scalespace_create(msfm_ctx* ctx, const uint8_t* gray, int widt
     if (tap_W[s + 1] > SIFT_MAX_RADIUS) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: a blur radius of %d exceeds %d", who, tap_W[s + 1], SIFT_MAX_RADIUS);
     taps.insert(taps.end(), g.begin(), g.end());
   }
-  std::unique_ptr<msfm_scalespace> P(new msfm_scalespace());
-  P->ctx = ctx; P->w = width; P->h = height; P->O = O; P->S = S;
+  Child<msfm_scalespace> P = child_new<msfm_scalespace>(ctx);
+  P->w = width; P->h = height; P->O = O; P->S = S;
   for (int o = 0; o < O; o++) { P->ow[o] = width >> o; P->oh[o] = height >> o; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -644,7 +644,6 @@ MSFM_API int msfm_scalespace_create(msfm_ctx* ctx, const uint8_t* gray, int widt
   SF_TRY(hipGetLastError());
   SF_TRY(sc.finish());
   P->h2d_bytes = sc.h2d;
-  ctx->children++;
   *out = P.release();
   return MSFM_OK;
 }
@@ -674,14 +673,7 @@ MSFM_API int msfm_scalespace_fetch(const msfm_scalespace* P, int octave, int lev
   return MSFM_OK;
 }
 
-MSFM_API void msfm_scalespace_destroy(msfm_scalespace* P) {
-  if (!P) return;
-  msfm_ctx* ctx = P->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);   // blocks go back to the pool only behind the work that may still read them
-  delete P;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_scalespace_destroy(msfm_scalespace* P) { msfm_child_destroy(P); }
 
 // what describe and extract refuse before anything else: -> the set's context through *out
 static int check_set_and_space(const char* who, const msfm_descset* set, int image, const msfm_scalespace* P, msfm_ctx** out) {

@@ -373,7 +373,7 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
   DevBuf<u64> d_w, d_P, d_gacc;
   PrimTmp tmp;
   std::vector<std::unique_ptr<LevelOut>> levels;
-  std::unique_ptr<msfm_voctree> T(new msfm_voctree());
+  Child<msfm_voctree> T = child_new<msfm_voctree>(ctx);
   DevScope sc(ctx);
   VT_TRY(sc.up(d_samp_off, samp_off)); VT_TRY(sc.up(d_samp_rows, samp_rows));
   VT_TRY(hip_first_error({d_perm.alloc(Mx), d_perm2.alloc(Mx), d_node.alloc(Mx), d_key.alloc(Mx), d_key2.alloc(Mx), d_rowptr.alloc(Mx),
@@ -505,7 +505,7 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
   }
   // the tree: the levels' blocks back to back
   const int nb = block_base;
-  T->ctx = ctx; T->k = k; T->n_blocks = nb; T->depth = S.depth; T->n_leaves = word_base; T->h2d_bytes = 0;
+  T->k = k; T->n_blocks = nb; T->depth = S.depth; T->n_leaves = word_base; T->h2d_bytes = 0;
   VT_TRY(hip_first_error({T->d_n.alloc((size_t)nb), T->d_desc.alloc((size_t)nb * k * WORDS_DIM), T->d_link.alloc((size_t)nb * k),
                           T->d_weight.alloc((size_t)nb * k)}));
   size_t b0 = 0;
@@ -521,7 +521,6 @@ MSFM_API int msfm_descset_voctree_train(msfm_descset* set, int k_in, int n_level
   S.host_waits++;
   S.n_blocks = nb; S.n_leaves = word_base;
   T->trained = true; T->train = S;
-  ctx->children++;
   *out = T.release();
   return MSFM_OK;
 }

@@ -160,8 +160,8 @@ MSFM_API int msfm_voctree_create(msfm_ctx* ctx, int k, int n_blocks, const uint1
   int64_t n_leaves = 0;
   const std::string bad = words_check_tree(k, n_blocks, block_n, node_desc, node_link, node_weight, &depth, &n_leaves);
   if (!bad.empty()) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %s", who, bad.c_str());
-  std::unique_ptr<msfm_voctree> T(new msfm_voctree());
-  T->ctx = ctx; T->k = k; T->n_blocks = n_blocks; T->depth = depth; T->n_leaves = n_leaves;
+  Child<msfm_voctree> T = child_new<msfm_voctree>(ctx);
+  T->k = k; T->n_blocks = n_blocks; T->depth = depth; T->n_leaves = n_leaves;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t s = ctx->stream;
   const size_t nodes = (size_t)n_blocks * k;
@@ -177,7 +177,6 @@ MSFM_API int msfm_voctree_create(msfm_ctx* ctx, int k, int n_blocks, const uint1
   WD_TRY(hipGetLastError());
   WD_TRY(sc.finish());
   T->h2d_bytes = sc.h2d;
-  ctx->children++;
   *out = T.release();
   return MSFM_OK;
 }
@@ -228,14 +227,7 @@ MSFM_API int msfm_voctree_fetch(const msfm_voctree* T, uint16_t* block_n, float*
   return MSFM_OK;
 }
 
-MSFM_API void msfm_voctree_destroy(msfm_voctree* T) {
-  if (!T) return;
-  msfm_ctx* ctx = T->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);   // blocks go back to the pool only behind the work that may still read them
-  delete T;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_voctree_destroy(msfm_voctree* T) { msfm_child_destroy(T); }
 
 MSFM_API int msfm_descset_words(msfm_descset* set, const msfm_voctree* T, int min_features, msfm_word_result** out) {
   using namespace words;
@@ -249,8 +241,8 @@ MSFM_API int msfm_descset_words(msfm_descset* set, const msfm_voctree* T, int mi
   if (T->ctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the tree belongs to another context", who);
   if (min_features < 0) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: min_features = %d is negative", who, min_features);
   const int n = V.n_images;
-  std::unique_ptr<msfm_word_result> R(new msfm_word_result());
-  R->ctx = ctx; R->set = set; R->generation = V.generation; R->n = n;
+  Child<msfm_word_result> R = child_new<msfm_word_result>(ctx);
+  R->set = set; R->generation = V.generation; R->n = n;
   R->feat_off.assign(n + 1, 0); R->bow_off.assign(n + 1, 0); R->image_max.assign(n, 0); R->has_words.assign(n, 0);
   long total_l = 0;
   for (int i = 0; i < n; i++) {
@@ -310,7 +302,6 @@ MSFM_API int msfm_descset_words(msfm_descset* set, const msfm_voctree* T, int mi
   R->n_bow = R->bow_off[n];
   R->n_unassigned = n_unassigned;
   for (int i = 0; i < n; i++) R->num_words = std::max(R->num_words, R->image_max[i]);   // the last running max_words_id_
-  ctx->children++;
   *out = R.release();
   return MSFM_OK;
 }
@@ -343,14 +334,7 @@ MSFM_API int msfm_word_result_fetch(const msfm_word_result* R, int32_t* feat_off
   return MSFM_OK;
 }
 
-MSFM_API void msfm_word_result_destroy(msfm_word_result* R) {
-  if (!R) return;
-  msfm_ctx* ctx = R->ctx;
-  (void)hipSetDevice(ctx->device);
-  (void)hipStreamSynchronize(ctx->stream);
-  delete R;
-  msfm_ctx_child_released(ctx);
-}
+MSFM_API void msfm_word_result_destroy(msfm_word_result* R) { msfm_child_destroy(R); }
 
 MSFM_API int msfm_wordset_create_from_words(msfm_descset* set, const msfm_word_result* R, int max_hypotheses, msfm_wordset** out) {
   const char* who = "msfm_wordset_create_from_words";
