@@ -1018,6 +1018,87 @@ int msfm_descset_extract(msfm_descset* set, int image, const msfm_scalespace* ss
                          int quantize, int64_t* stats /*[MSFM_SIFT_DETECT_STATS]*/);
 
 /* ======================================================================================
+ *  Stereo rectification: geometry on the host, maps and bilinear warp on the device
+ * ====================================================================================== */
+/* DenseReconstruction::EpipolarRectification (SfM/src/dense_reconstruction.cc:299-331): cv::stereoRectify, two
+ * cv::initUndistortRectifyMap and two cv::remap(INTER_LINEAR), the first step per pair of SGMDense (:134) and of ELASDense (:226).
+ * PARITY WITH OPENCV IS UNPINNED: the calib3d and imgproc sources are not in the reference tree and no build of them has been run
+ * against this.  THE DEFINITIONS BELOW ARE THIS PROJECT'S OWN; where they differ from OpenCV, they hold.  Everything past the map
+ * is integer arithmetic and the map is unfused binary64 without a library function on the device, so tests/rectify_ref.cpp restates
+ * geometry, maps and warp sequentially and the device equals it bit for bit in every plane msfm_rectifier_fetch returns.
+ * Camera 1 is the reference's left image i + 1, camera 2 its right image i.  All host arithmetic is binary64, every product and
+ * sum rounded on its own, a three-term sum as (a + b) + c; acos, sin, cos and sqrt are the host C library's, and their results are
+ * used as data.  Matrices are row-major.
+ *
+ * msfm_stereo_rectify: host only, no context (like msfm_camera_graph_dissection).  cv::stereoRectify with zero distortion,
+ * CALIB_ZERO_DISPARITY, alpha = -1 and newImageSize = imageSize (dense_reconstruction.cc:308-314).
+ *   relative    R21 = R2 inv(R1), the 3 x 3 inverse by the adjugate (every cofactor divided by the determinant);
+ *               t21 = -(R21 t1) + t2.  The pose file's header calls t a camera position (:342), the reference passes it as a
+ *               translation (:309): KEPT.
+ *   halves      om = the rotation vector of R21: c = clamp((trace - 1) / 2, -1, 1), theta = acos(c), r = the skew part
+ *               ((R21[2][1] - R21[1][2]) / 2, ...), om = r * (theta / |r|), 0 when |r| = 0.  DEPARTURE 1: no SVD clean-up of R21
+ *               is done, and theta has acos's resolution (1e-8 rad beside theta = 0).  rodrigues(v), theta = |v|, k = v / theta:
+ *               cos(theta) I + (1 - cos(theta)) k k^T + sin(theta) [k]x, the identity for v = 0.  r_r = rodrigues(-0.5 om);
+ *               t = r_r t21.
+ *   axis        idx = |t[0]| > |t[1]| ? 0 : 1 (0: a horizontal pair, 1: a vertical one); c = t[idx]; nt = |t|; uu = 0 but for
+ *               uu[idx] = c > 0 ? 1 : -1; ww = t x uu; nw = |ww|; if nw > 0, ww *= acos(|c| / nt) / nw; wR = rodrigues(ww).
+ *   rotations   R1_ = wR r_r^T, R2_ = wR r_r, t_rect = R2_ t21 (only its idx component is not roundoff).
+ *   focal       fc = min(K1[idx^1][idx^1], K2[idx^1][idx^1]).
+ *   centre      per camera k the corners (0, 0), (w - 1, 0), (0, h - 1), (w - 1, h - 1): n = ((x - cx) / fx, (y - cy) / fy, 1),
+ *               p = Rk_ n, (p.x / p.z) * fc and (p.y / p.z) * fc, summed in that order and times 0.25: avg.
+ *               cc_k = ((w - 1) / 2 - avg.x, (h - 1) / 2 - avg.y); zero disparity: cc = (cc_1 + cc_2) * 0.5 for both cameras.
+ *   outputs     P1_ = [fc 0 cc.x 0; 0 fc cc.y 0; 0 0 1 0]; P2_ the same with P2_[idx][3] = t_rect[idx] * fc;
+ *               Q = [1 0 0 -cc.x; 0 1 0 -cc.y; 0 0 0 fc; 0 0 -1 / t_rect[idx] 0].  Every output pointer is optional.
+ *   KEPT        when camera 1 is not the left one, P2_[0][3] > 0 and every true disparity is negative, so the matching behind it
+ *               finds nothing.  The reference does not look either; dense.sgm_dense_posed returns the sign per pair.
+ * MSFM_E_INVAL before any write: a NULL input; a non-finite value; K[0][0] or K[1][1] of either camera not positive; nt == 0
+ * (no baseline); a relative rotation within 1e-6 of pi (the skew part has lost the axis); width or height outside [1, 16384];
+ * an R1 without an inverse, or poses that give a non-finite output.
+ *
+ * maps         cv::initUndistortRectifyMap with zero distortion and CV_32FC1, per camera k and output pixel, column j, row i.
+ *               On the host iR = inv(Pk_[:, :3] Rk_) by the adjugate.  On the device in unfused binary64:
+ *               X = (iR[0][0] * j + iR[0][1] * i) + iR[0][2], Y and W likewise from rows 1 and 2; wi = 1.0 / W;
+ *               mapx = (float)(fx * (X * wi) + cx), mapy = (float)(fy * (Y * wi) + cy) with the camera's own K, whose skew entry
+ *               is ignored.  DEPARTURE 2: OpenCV accumulates X, Y and W along the row by repeated addition; here every pixel is
+ *               evaluated directly, so no pixel depends on its neighbour.
+ * warp         cv::remap(INTER_LINEAR) on uint8 with BORDER_CONSTANT 0, as its 5-bit fixed-point arithmetic, in integers.
+ *               px = mapx * 32.0f, py = mapy * 32.0f (binary32, exact).  If either is not finite or of magnitude >= 2^30 the
+ *               pixel is 0.  Otherwise sx = rint(px) (half to even), ix = sx >> 5 (arithmetic), ax = sx & 31; sy, iy, ay likewise.
+ *               S = (32 - ax)(32 - ay) p00 + ax (32 - ay) p01 + (32 - ax) ay p10 + ax ay p11, p00 = src(ix, iy), p01 = src(ix + 1,
+ *               iy), p10 = src(ix, iy + 1), p11 = src(ix + 1, iy + 1); a tap outside the source counts 0, each tap on its own.
+ *               out = (S + 512) >> 10.  This equals OpenCV's table of 15-bit weights: a product of two 5-bit fractions times
+ *               2^15 is an integer, so the table rounds nothing.
+ * NOT BUILT: distortion coefficients (the reference passes zeros); alpha >= 0; a new image size; colour input for the ELASDense
+ * arm; ELASDense itself; Depth2Points; a C++ host mirror.
+ *
+ * msfm_rectifier is a child of its context like msfm_sgm, made for one image size.  It owns the parameter block of a call
+ * (2 cameras x (iR, fx, fy, cx, cy) = 208 bytes) with the two source planes behind it, the two rectified planes [2][h][w], and
+ * four float map planes; msfm_rectifier_size reports them (208 + 20 w h bytes), the SGM object does not.
+ * msfm_rectifier_rectify does the geometry on the host (MSFM_E_INVAL as above, before anything is staged), copies block and pair
+ * into pinned staging of the object, uploads them in one copy and enqueues ONE launch for both images on the context's stream; it
+ * does NOT wait, and the caller's buffers are free on return.  keep_maps != 0 also writes the four map planes.  R1_out, R2_out
+ * [9], P1_out, P2_out [12] (each optional) receive the geometry.  stats (optional) [MSFM_RECTIFY_STATS], as MSFM_SGM_STATS:
+ * 0 host waits, 1 bytes to the device (208 + 2 w h), 2 kernel launches (1).
+ * msfm_rectifier_fetch waits and copies one plane [h][w]: kind 0 / 1 rectified left / right (uint8); 2 / 3 mapx / mapy of the
+ * left image, 4 / 5 of the right (float).
+ * MSFM_E_INVAL before any write, with the object still usable: a NULL pointer (stats and the geometry outputs may be NULL); a
+ * side outside [1, 16384]; stride < width; a kind out of range; a fetch before the first rectify; a map fetch when the last
+ * rectify kept none. */
+#define MSFM_RECTIFY_STATS 3
+typedef struct msfm_rectifier msfm_rectifier;
+int msfm_stereo_rectify(const double K1[9], const double R1[9], const double t1[3], const double K2[9], const double R2[9],
+                        const double t2[3], int width, int height, double* R1_out /*[9]*/, double* R2_out /*[9]*/,
+                        double* P1_out /*[12]*/, double* P2_out /*[12]*/, double* Q_out /*[16]*/, int* idx_out);
+int msfm_rectifier_create(msfm_ctx* ctx, int width, int height, msfm_rectifier** out);
+int msfm_rectifier_rectify(msfm_rectifier* rect, const uint8_t* left, int left_stride, const uint8_t* right, int right_stride,
+                           const double K1[9], const double R1[9], const double t1[3], const double K2[9], const double R2[9],
+                           const double t2[3], int keep_maps, double* R1_out /*[9]*/, double* R2_out /*[9]*/,
+                           double* P1_out /*[12]*/, double* P2_out /*[12]*/, int64_t* stats /*[MSFM_RECTIFY_STATS]*/);
+int msfm_rectifier_fetch(const msfm_rectifier* rect, int kind, void* out);
+int msfm_rectifier_size(const msfm_rectifier* rect, int* width, int* height, int64_t* device_bytes);
+void msfm_rectifier_destroy(msfm_rectifier* rect);
+
+/* ======================================================================================
  *  Dense stereo: census, eight-path semi-global matching, disparity to depth
  * ====================================================================================== */
 /* DenseReconstruction::SGMDense (SfM/src/dense_reconstruction.cc:113-190): sgm::StereoSGM::execute of libSGM
@@ -1058,8 +1139,8 @@ int msfm_descset_extract(msfm_descset* set, int image, const msfm_scalespace* ss
  *               binary64; depth = t > 255 || t < 0 ? 0 : (uint8) t by truncation; disp == 0 gives 0.  The 128 values are made
  *               on the host (the division is the host's) and applied to the final plane as a table.
  * NOT BUILT: 16-bit input; the subpixel arm (its 16-bit median in the reference truncates columns to 8 bits, which would need a
- * ruling of its own); EpipolarRectification (OpenCV's stereoRectify + remap, parity unpinned); ELASDense; Depth2Points; a C++
- * host mirror; a multi-GPU form.
+ * ruling of its own); ELASDense; Depth2Points; a C++ host mirror; a multi-GPU form.  (EpipolarRectification is the section
+ * above, by this project's own definitions.)
  * msfm_sgm is a child of its context like msfm_scalespace.  It owns all its device planes for its lifetime - two images, two
  * census planes, eight cost volumes [h][w][D] of uint8, four uint16 planes, the uint8 result - and is reused pair after pair, as the
  * reference reuses a StereoSGM.  MSFM_E_NOMEM when the planes do not fit (4 000 x 3 000 at D = 128: 11.5 GB of cost volumes).
@@ -1067,6 +1148,9 @@ int msfm_descset_extract(msfm_descset* set, int image, const msfm_scalespace* ss
  * it does NOT wait, and the caller's buffers are free on return.  A second execute replaces the first's result.
  * stats (optional) [MSFM_SGM_STATS]: 0 host waits (0, unless the caller is two executes ahead of the device and the staging
  * slot's copy has not run), 1 bytes to the device, 2 kernel launches.
+ * msfm_sgm_execute_rectified runs the same chain on the rectified planes of a msfm_rectifier where its last rectify put them:
+ * same stream, no wait, no copy; stats reports 0 waits, 0 bytes and the 7 launches.  The two executes may follow each other on
+ * one object in any order.  MSFM_E_INVAL: a NULL rectifier, one of another context or another size, one that has not rectified yet.
  * msfm_sgm_fetch waits and copies one plane, [h][w] of: kind 0 / 1 census L / R (uint32); 2 the cost volume of path `index`
  * (uint8 [h][w][D]); 3 / 4 raw left / right disparity (uint16); 5 / 6 median-filtered left / right (uint16); 7 final left (uint8).
  * index is 0 for every kind but 2.  msfm_sgm_depth waits and writes the depth of the final plane.
@@ -1079,6 +1163,7 @@ int msfm_sgm_create(msfm_ctx* ctx, int width, int height, int disp_size /* 128 *
                     float uniqueness /* 0.96 */, msfm_sgm** out);
 int msfm_sgm_execute(msfm_sgm* sgm, const uint8_t* left, int left_stride, const uint8_t* right, int right_stride,
                      int64_t* stats /*[MSFM_SGM_STATS]*/);
+int msfm_sgm_execute_rectified(msfm_sgm* sgm, const msfm_rectifier* rect, int64_t* stats /*[MSFM_SGM_STATS]*/);
 int msfm_sgm_fetch(const msfm_sgm* sgm, int kind, int index, void* out);
 int msfm_sgm_depth(const msfm_sgm* sgm, double baseline, double focal, uint8_t* depth_out /*[h][w]*/);
 int msfm_sgm_size(const msfm_sgm* sgm, int* width, int* height, int* disp_size, int64_t* device_bytes);

@@ -227,6 +227,15 @@ def sgm_stats(values):
     return dict(zip(SGM_STATS, (int(v) for v in values)))
 
 
+# the entries of msfm_rectifier_rectify's stats [MSFM_RECTIFY_STATS] (include/msfm.h): order and meaning of SGM_STATS
+RECTIFY_STATS = SGM_STATS
+# msfm_rectifier_fetch: kind -> (name, dtype of a pixel), every kind [h][w]
+RECTIFY_FETCH = ((0, "left", np.uint8), (1, "right", np.uint8), (2, "mapx_left", np.float32), (3, "mapy_left", np.float32),
+                 (4, "mapx_right", np.float32), (5, "mapy_right", np.float32))
+# the parameter block a rectify uploads in front of the pair (RECT_PARAM_BYTES of metricsfm_amd/csrc/rectify_args.h)
+RECTIFY_PARAM_BYTES = 208
+
+
 def ptr(a, typ):
     return None if a is None else a.ctypes.data_as(typ)
 

@@ -407,6 +407,11 @@ class Context(_Handle):
         pair after pair; the defaults are the reference's call."""
         return StereoSGM(self, width, height, disp_size, p1, p2, uniqueness)
 
+    def rectifier(self, width, height):
+        """msfm_rectifier_create: a stereo rectifier for posed uint8 pairs of width x height, resident as a `Rectifier` and reused
+        pair after pair; `StereoSGM.execute_rectified` reads its planes on the device."""
+        return Rectifier(self, width, height)
+
     def recon(self, store, state, cam_pose, cam_model, cam_model_of_cam, keypoints=None, reserve_points=0, reserve_obs=0, *, model_mutable=None):
         """msfm_recon_create: the flat state `newpoints.py` documents, with its point side and pt_new_added, resident on the device
         as a `Recon`; cam_pose / cam_model / cam_model_of_cam are the solver's parameter blocks as `adjust.adjust_round` takes
@@ -925,6 +930,14 @@ class StereoSGM(_Handle):
         self.stats = A.sgm_stats(st)
         return self.stats
 
+    def execute_rectified(self, rect):
+        """msfm_sgm_execute_rectified: the chain on the rectified planes of a `Rectifier` of this context and size, device to
+        device, without waiting.  -> the stats dict (0 bytes to the device), also kept as `self.stats`."""
+        st = np.zeros(len(A.SGM_STATS), np.int64)
+        self.ctx.check(lib().msfm_sgm_execute_rectified(self._h, rect._h, A.ptr(st, C.POINTER(C.c_int64))))
+        self.stats = A.sgm_stats(st)
+        return self.stats
+
     def fetch(self, kind, index=0):
         """msfm_sgm_fetch: waits and returns one plane (`A.SGM_FETCH`): [h][w], the cost volume of path `index` [h][w][D] for kind 2."""
         dt = {k: d for k, _, d in A.SGM_FETCH}.get(int(kind), np.uint8)
@@ -951,6 +964,67 @@ class StereoSGM(_Handle):
         w, h, d, b = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
         self.ctx.check(lib().msfm_sgm_size(self._h, C.byref(w), C.byref(h), C.byref(d), C.byref(b)))
         return dict(width=w.value, height=h.value, disp_size=d.value, device_bytes=b.value)
+
+
+def _pose_args(K1, R1, t1, K2, R2, t2):
+    """-> the six arrays as binary64, row-major, and their pointers in the order the library takes them"""
+    arrs = [A.as_c(np.asarray(a, dtype=np.float64).reshape(n), np.float64) for a, n in zip((K1, R1, t1, K2, R2, t2), (9, 9, 3, 9, 9, 3))]
+    return arrs, [A.ptr(a, A.c_double_p) for a in arrs]
+
+
+def stereo_rectify(K1, R1, t1, K2, R2, t2, width, height):
+    """msfm_stereo_rectify (host only, no context): the rectification geometry of a posed pair by the definitions of
+    include/msfm.h, "Stereo rectification"; camera 1 is the left image.  -> dict(R_left [3][3], R_right [3][3], P_left [3][4],
+    P_right [3][4], Q [4][4], idx: 0 a horizontal pair, 1 a vertical one).  MsfmError for poses the header refuses."""
+    keep, ptrs = _pose_args(K1, R1, t1, K2, R2, t2)
+    out = dict(R_left=np.zeros((3, 3)), R_right=np.zeros((3, 3)), P_left=np.zeros((3, 4)), P_right=np.zeros((3, 4)), Q=np.zeros((4, 4)))
+    idx = C.c_int32(-1)
+    rc = lib().msfm_stereo_rectify(*ptrs, int(width), int(height), *[A.ptr(v, A.c_double_p) for v in out.values()], C.byref(idx))
+    if rc != 0:
+        raise MsfmError(rc, "msfm_stereo_rectify: poses or size refused (non-finite, no baseline, a half turn, a side outside [1, 16384])")
+    out["idx"] = idx.value
+    return out
+
+
+class Rectifier(_Handle):
+    """msfm_rectifier: rectification geometry on the host, maps and bilinear warp of a posed pair on the device (include/msfm.h,
+    "Stereo rectification", states the definitions).  It owns its device planes; `rectify` replaces the result of the one before."""
+    _destroy = "msfm_rectifier_destroy"
+
+    def __init__(self, ctx: Context, width, height):
+        self.ctx = ctx
+        self._h = C.c_void_p()
+        self.stats = None
+        ctx.check(lib().msfm_rectifier_create(ctx._h, int(width), int(height), C.byref(self._h)))
+        self.width, self.height = int(width), int(height)
+
+    def rectify(self, left, right, K1, R1, t1, K2, R2, t2, keep_maps=False):
+        """msfm_rectifier_rectify: camera 1 (K1, R1, t1) is `left`.  Uploads the pair and enqueues the one launch without waiting.
+        -> dict(R_left, R_right, P_left, P_right, stats); the stats (`A.RECTIFY_STATS`) are also kept as `self.stats`."""
+        (l, ls), (r, rs) = StereoSGM._image(left, "left"), StereoSGM._image(right, "right")
+        if l.shape != (self.height, self.width) or r.shape != l.shape:
+            raise ValueError("the pair must be two images of %d x %d" % (self.width, self.height))
+        keep, ptrs = _pose_args(K1, R1, t1, K2, R2, t2)
+        out = dict(R_left=np.zeros((3, 3)), R_right=np.zeros((3, 3)), P_left=np.zeros((3, 4)), P_right=np.zeros((3, 4)))
+        st = np.zeros(len(A.RECTIFY_STATS), np.int64)
+        self.ctx.check(lib().msfm_rectifier_rectify(self._h, C.cast(l.ctypes.data, A.c_u8_p), int(ls), C.cast(r.ctypes.data, A.c_u8_p), int(rs),
+                                                    *ptrs, int(bool(keep_maps)), *[A.ptr(v, A.c_double_p) for v in out.values()],
+                                                    A.ptr(st, C.POINTER(C.c_int64))))
+        self.stats = out["stats"] = dict(zip(A.RECTIFY_STATS, (int(v) for v in st)))
+        return out
+
+    def fetch(self, kind):
+        """msfm_rectifier_fetch: waits and returns one plane [h][w] (`A.RECTIFY_FETCH`): 0 / 1 rectified left / right, 2 .. 5 the maps."""
+        dt = {k: d for k, _, d in A.RECTIFY_FETCH}.get(int(kind), np.uint8)
+        out = np.zeros((self.height, self.width), dt)
+        self.ctx.check(lib().msfm_rectifier_fetch(self._h, int(kind), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def size(self):
+        """-> dict(width, height, device_bytes)"""
+        w, h, b = C.c_int32(), C.c_int32(), C.c_int64()
+        self.ctx.check(lib().msfm_rectifier_size(self._h, C.byref(w), C.byref(h), C.byref(b)))
+        return dict(width=w.value, height=h.value, device_bytes=b.value)
 
 
 class MatchResult(_Handle):

@@ -206,6 +206,58 @@ struct DevBuf {
   }
 };
 
+// Pinned staging of what one call of a resident object uploads (msfm_sgm, msfm_rectifier): two slots in turn, each with the event
+// behind its copy, so the caller's buffers are free on return and the call does not wait for its own copy.  The slot of the call
+// before last is taken again: its copy has long run unless the caller is two calls ahead of the device.
+struct StageSlots {
+  uint8_t* buf[2] = {nullptr, nullptr};
+  hipEvent_t staged[2] = {nullptr, nullptr};
+  bool in_flight[2] = {false, false};
+  int slot = 0;
+  StageSlots() = default;
+  StageSlots(const StageSlots&) = delete;
+  StageSlots& operator=(const StageSlots&) = delete;
+  ~StageSlots() {
+    for (int i = 0; i < 2; i++) {
+      if (buf[i]) (void)hipHostFree(buf[i]);
+      if (staged[i]) (void)hipEventDestroy(staged[i]);
+    }
+  }
+  hipError_t create(size_t bytes) {
+    for (int i = 0; i < 2; i++) {
+      hipError_t e = hipHostMalloc((void**)&buf[i], bytes);
+      if (e != hipSuccess) { buf[i] = nullptr; return e; }
+      if ((e = hipEventCreateWithFlags(&staged[i], hipEventDisableTiming)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
+  // -> *out: the slot to fill; *waits is counted up if its earlier copy had to be waited for
+  hipError_t take(uint8_t** out, int64_t* waits) {
+    if (in_flight[slot] && hipEventQuery(staged[slot]) != hipSuccess) {
+      (void)hipGetLastError();
+      const hipError_t e = hipEventSynchronize(staged[slot]);
+      if (e != hipSuccess) return e;
+      (*waits)++;
+    }
+    *out = buf[slot];
+    return hipSuccess;
+  }
+  // bytes of the taken slot to dst on s, the event behind the copy, and the turn to the other slot
+  hipError_t send(void* dst, size_t bytes, hipStream_t s) {
+    hipError_t e = hipMemcpyAsync(dst, buf[slot], bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    if ((e = hipEventRecord(staged[slot], s)) != hipSuccess) return e;
+    in_flight[slot] = true;
+    slot ^= 1;
+    return hipSuccess;
+  }
+};
+
+// rectify.hip, for msfm_sgm_execute_rectified: the rectified pair [2][h][w] of a rectifier on the device (nullptr before its
+// first rectify), its context and its size
+struct msfm_rectifier;
+const uint8_t* rectifier_planes(const msfm_rectifier* rect, msfm_ctx** ctx, int* width, int* height);
+
 // The device scratch of one call: what a function enqueues on ctx->stream while it owns local blocks happens inside a DevScope.
 // Its destructor waits for the stream unless the scope has been settled, so a return at any point - HIP_TRY, MSFM_TRY - gives no
 // block back to the cache that the stream still uses (the cache hands a freed block to the next context at once).

@@ -15,6 +15,8 @@
 //                    pixels whose last candidate column has just arrived, four lanes per pixel, top-2 by min / max.
 //   k_median         3 x 3 median of both raw planes;  k_check  the consistency rule into the uint8 plane.
 // Every path kernel writes a lane's 8 cost bytes as one store and a group's D bytes as one line.
+// msfm_sgm_execute_rectified   the same seven launches (sgm_execute_dev) on the rectified planes of a msfm_rectifier (rectify.hip),
+//                    where its kernel wrote them: no copy, no wait.
 #include <memory>
 
 #include "common.h"
@@ -30,19 +32,9 @@ struct msfm_sgm {
   DevBuf<uint8_t> vol[8];      // [h][w][D] each
   DevBuf<uint16_t> planes;     // [4][h][w]: raw left, raw right, median left, median right
   DevBuf<uint8_t> fin;         // [h][w]
-  // pinned staging of the packed pair, two slots in turn, each with the event behind its copy
-  uint8_t* stage[2] = {nullptr, nullptr};
-  hipEvent_t staged[2] = {nullptr, nullptr};
-  bool in_flight[2] = {false, false};
-  int slot = 0;
+  StageSlots stage;            // pinned staging of the packed pair
   size_t npx() const { return (size_t)w * h; }
   int64_t device_bytes() const { return (int64_t)(npx() * (2 + 8 + 8 * (size_t)D + 8 + 1)); }
-  ~msfm_sgm() {
-    for (int i = 0; i < 2; i++) {
-      if (stage[i]) (void)hipHostFree(stage[i]);
-      if (staged[i]) (void)hipEventDestroy(staged[i]);
-    }
-  }
 };
 
 namespace sgm {
@@ -375,42 +367,19 @@ MSFM_API int msfm_sgm_create(msfm_ctx* ctx, int width, int height, int disp_size
   SG_ALLOC(P->census.alloc(2 * npx));
   SG_ALLOC(P->planes.alloc(4 * npx));
   SG_ALLOC(P->fin.alloc(npx));
-  for (int i = 0; i < 2; i++) {
-    SG_ALLOC(hipHostMalloc((void**)&P->stage[i], 2 * npx));
-    SG_TRY(hipEventCreateWithFlags(&P->staged[i], hipEventDisableTiming));
-  }
+  SG_ALLOC(P->stage.create(2 * npx));
   *out = P.release();
   return MSFM_OK;
 }
 
-MSFM_API int msfm_sgm_execute(msfm_sgm* P, const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int64_t* stats) {
+// The chain on a pair that is on the device: img [2][h][w] packed, left then right, of the object's size.  Seven launches on the
+// context's stream, no wait, no copy.  k_census and k_check are the two readers of img.
+static int sgm_execute_dev(msfm_sgm* P, const uint8_t* img) {
   using namespace sgm;
-  const char* who = "msfm_sgm_execute";
-  if (!P) return MSFM_E_INVAL;
   msfm_ctx* ctx = P->ctx;
   const int w = P->w, h = P->h, D = P->D;
-  const std::string bad = sgm_check_execute(left, left_stride, right, right_stride, w);
-  if (!bad.empty()) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %s", who, bad.c_str());
-  SG_TRY(hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
-  int64_t waits = 0, launches = 0;
   const size_t npx = P->npx();
-  // the staging slot of the call before last: its copy has long run unless the caller is two calls ahead of the device
-  const int slot = P->slot;
-  if (P->in_flight[slot] && hipEventQuery(P->staged[slot]) != hipSuccess) {
-    (void)hipGetLastError();
-    SG_TRY(hipEventSynchronize(P->staged[slot]));
-    waits++;
-  }
-  uint8_t* const stage = P->stage[slot];
-  for (int y = 0; y < h; y++) {
-    memcpy(stage + (size_t)y * w, left + (size_t)y * left_stride, (size_t)w);
-    memcpy(stage + npx + (size_t)y * w, right + (size_t)y * right_stride, (size_t)w);
-  }
-  SG_TRY(hipMemcpyAsync(P->img.p, stage, 2 * npx, hipMemcpyHostToDevice, st));
-  SG_TRY(hipEventRecord(P->staged[slot], st));
-  P->in_flight[slot] = true;
-  P->slot = slot ^ 1;
   const uint32_t* cl = P->census.p;
   const uint32_t* cr = P->census.p + npx;
   Vols vols;
@@ -419,7 +388,7 @@ MSFM_API int msfm_sgm_execute(msfm_sgm* P, const uint8_t* left, int left_stride,
   const int G = D / SGM_LANE_DISP, NG = SGM_PATH_THREADS / G;
   {
     KTimer t(ctx, "sgm_census");
-    hipLaunchKernelGGL(k_census, dim3(px.x, px.y, 2), dim3(256), 0, st, P->img.p, w, h, P->census.p);
+    hipLaunchKernelGGL(k_census, dim3(px.x, px.y, 2), dim3(256), 0, st, img, w, h, P->census.p);
   }
   {
     KTimer t(ctx, "sgm_path_h");
@@ -452,15 +421,57 @@ MSFM_API int msfm_sgm_execute(msfm_sgm* P, const uint8_t* left, int left_stride,
   }
   {
     KTimer t(ctx, "sgm_check");
-    hipLaunchKernelGGL(k_check, px, dim3(256), 0, st, P->img.p, med, med + npx, w, h, P->fin.p);
+    hipLaunchKernelGGL(k_check, px, dim3(256), 0, st, img, med, med + npx, w, h, P->fin.p);
   }
-  launches = 7;
   SG_TRY(hipGetLastError());
   P->executed = true;
+  return MSFM_OK;
+}
+#define SGM_CHAIN_LAUNCHES 7
+
+MSFM_API int msfm_sgm_execute(msfm_sgm* P, const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int64_t* stats) {
+  const char* who = "msfm_sgm_execute";
+  if (!P) return MSFM_E_INVAL;
+  msfm_ctx* ctx = P->ctx;
+  const int w = P->w, h = P->h;
+  const std::string bad = sgm_check_execute(left, left_stride, right, right_stride, w);
+  if (!bad.empty()) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: %s", who, bad.c_str());
+  SG_TRY(hipSetDevice(ctx->device));
+  int64_t waits = 0;
+  const size_t npx = P->npx();
+  uint8_t* stage = nullptr;
+  SG_TRY(P->stage.take(&stage, &waits));
+  for (int y = 0; y < h; y++) {
+    memcpy(stage + (size_t)y * w, left + (size_t)y * left_stride, (size_t)w);
+    memcpy(stage + npx + (size_t)y * w, right + (size_t)y * right_stride, (size_t)w);
+  }
+  SG_TRY(P->stage.send(P->img.p, 2 * npx, ctx->stream));
+  MSFM_TRY(sgm_execute_dev(P, P->img.p));
   if (stats) {
     stats[SGM_ST_WAITS] = waits;
     stats[SGM_ST_H2D] = (int64_t)(2 * npx);
-    stats[SGM_ST_LAUNCHES] = launches;
+    stats[SGM_ST_LAUNCHES] = SGM_CHAIN_LAUNCHES;
+  }
+  return MSFM_OK;
+}
+
+MSFM_API int msfm_sgm_execute_rectified(msfm_sgm* P, const msfm_rectifier* rect, int64_t* stats) {
+  const char* who = "msfm_sgm_execute_rectified";
+  if (!P) return MSFM_E_INVAL;
+  msfm_ctx* ctx = P->ctx;
+  if (!rect) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: null argument", who);
+  msfm_ctx* rctx = nullptr;
+  int rw = 0, rh = 0;
+  const uint8_t* planes = rectifier_planes(rect, &rctx, &rw, &rh);
+  if (rctx != ctx) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the rectifier belongs to another context", who);
+  if (rw != P->w || rh != P->h) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: a rectifier of %d x %d for an object of %d x %d", who, rw, rh, P->w, P->h);
+  if (!planes) return msfm_set_error(ctx, MSFM_E_INVAL, "%s: the rectifier has not rectified anything yet", who);
+  SG_TRY(hipSetDevice(ctx->device));
+  MSFM_TRY(sgm_execute_dev(P, planes));
+  if (stats) {
+    stats[SGM_ST_WAITS] = 0;
+    stats[SGM_ST_H2D] = 0;
+    stats[SGM_ST_LAUNCHES] = SGM_CHAIN_LAUNCHES;
   }
   return MSFM_OK;
 }
